@@ -340,6 +340,28 @@ def token_agreement(mine: np.ndarray, ref_file: str, model: str, clips: str):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict, limit: int = DUMP_LIMIT_BYTES) -> dict:
+    """Write every array as float64 `out_dir/<name>.npy` so that two builds can be compared output for output.  An array whose
+    share of `limit` is too small for it keeps a fixed, seeded sample of its rows (the same rows in every run).
+    -> {name: {"shape": written shape, "rows_of": original row count}}."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = limit // max(1, len(arrays))
+    written = {}
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        rows = a.shape[0]
+        row_bytes = max(1, a[:1].nbytes)
+        if a.nbytes > share:
+            keep = np.sort(np.random.Generator(np.random.Philox(key=0)).choice(rows, size=max(1, share // row_bytes), replace=False))
+            a = a[keep]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        written[name] = {"shape": list(a.shape), "rows_of": rows}
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -368,6 +390,10 @@ def main():
                          "cross-attention (ttasr_set_option xkv_fp8); the line's dtype says so and output_check reports the token "
                          "agreement with the bf16 and the f32 engines")
     ap.add_argument("--dump-tokens", default=None, help="save rank 0's int32 [B][new_tokens] token ids of the last timed step as .npy")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (the token ids of every rank's clips, "
+                         "-1 = padding) as DIR/tokens.npy in float64; inputs are seeded, so runs with the same arguments compare "
+                         "output for output")
     ap.add_argument("--no-side", action="store_true",
                     help="skip the side modes of the default run (fp16 engine, fp8 cross-KV cache, two contexts in flight): a "
                          "rocprofv3 run then sees only the headline configuration's launches")
@@ -379,6 +405,8 @@ def main():
                     help="synthetic clip set of the timed steps (SURVEY.md 8d: 0.1 N(0,1) noise; the tonal set - five sines - is "
                          "also measured as a side number by the default run)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(_self_launch(args.gpus))
@@ -497,6 +525,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     assert toks.shape == (world * B * C_, args.new_tokens)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {"tokens": toks})
 
     logits_spread = None
     if args.validate or grp:
@@ -700,6 +731,8 @@ def main():
                                             "audio_s_per_s": round(B * 30.0 / float(np.median(tt)), 1), "steps": 3}
         if check is not None:
             out["output_check"] = check
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "dtype": "float64", "arrays": dumped}
         if world == 1 and C_ == 1 and (args.more_in_flight or not args.no_side):
             # Side modes, NEVER `value` (measured by the default run, under the driver's clock).  Each is
             # the same step (pinned host PCM -> tokens) for `--side-steps` timed passes after one warm-up:

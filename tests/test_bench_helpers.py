@@ -39,3 +39,19 @@ def test_token_agreement_reports_margins_at_divergences():
     # another workload (other model / clip set) has no committed reference: no claim is made
     assert b.token_agreement(mine, "bench_tokens_f32.npy", "small", "noise") is None
     assert b.token_agreement(mine, "bench_tokens_f32.npy", "large-v3", "tonal") is None
+
+
+def test_dump_outputs_writes_float64_and_a_fixed_sample_under_the_limit(tmp_path):
+    b = _bench()
+    toks = np.arange(64 * 16, dtype=np.int32).reshape(64, 16)
+    w = b.dump_outputs(str(tmp_path / "a"), {"tokens": toks})
+    got = np.load(tmp_path / "a" / "tokens.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, toks) and w == {"tokens": {"shape": [64, 16], "rows_of": 64}}
+    # over the limit: a seeded subset of whole rows, identical from run to run
+    lim = 10 * 16 * 8
+    for d in ("b", "c"):
+        b.dump_outputs(str(tmp_path / d), {"tokens": toks}, limit=lim)
+    x, y = np.load(tmp_path / "b" / "tokens.npy"), np.load(tmp_path / "c" / "tokens.npy")
+    assert x.shape == (10, 16) and x.nbytes <= lim and np.array_equal(x, y)
+    rows = x[:, 0].astype(np.int64) // 16
+    assert (np.diff(rows) > 0).all() and np.array_equal(x, toks[rows])
