@@ -212,6 +212,45 @@ TTASR_API int ttasr_decode_step(ttasr_ctx* ctx, const int32_t* tokens_host, int3
 TTASR_API int ttasr_apply_rules(ttasr_ctx* ctx, const float* rows_host, const int32_t* hist_host, int32_t hist_stride,
                       int32_t n, const ttasr_gen_opts* opts, float* out_rows_host, int32_t* out_choice_host);
 
+/* ---- continuous batching: greedy single-window decoding with slot refill ----------------------------------------------
+ * Clips are submitted at any time; each takes a free row of the context's max_batch-row decode batch, decodes until EOT or its
+ * own token budget, and its row is handed to the next queued clip.  The batch always runs at max_batch rows (the full-width
+ * kernel forms), and every encoder pass of a session runs one GEMM family whatever the number of clips it encodes, so a clip's
+ * result does not depend on its neighbours, on when it was submitted or on GPU timing: its tokens, sum_logprob and no_speech
+ * are bit-identical to the same clip in a static batch of max_batch rows decoded by ttasr_generate_capped with option
+ * "prefill" = 0, in every compute mode.  Prompt tokens are forced through ordinary decode steps.  While a session is open
+ * every other search, step, encoder, mel, rule-hook, audio-window and option call on the context is refused (TTASR_E_INVALID); ttasr_session_end closes it and leaves no resident encoder state (log-mel and encode
+ * again before a static ttasr_generate).
+ *
+ * ttasr_session_begin: opts as for ttasr_generate (opts->check_interval = decode steps between two polls of the finished
+ *   flags); max_prompt = the longest prompt a clip may bring; temperature must be 0 (greedy only).  Refused: the e4m3
+ *   cross-KV mode (option xkv_fp8).  The first session of a context allocates its staging cross-KV (the size of the
+ *   context's cross-KV cache), the row positions and the admission table; later sessions reuse them.
+ * ttasr_session_submit: n clips, clip i = pcm_host[i][0 .. n_samples[i]) (at most one window), prompt [n][max_prompt] with
+ *   prompt_len[i] tokens valid, max_new[i] in [1, opts->max_new_tokens] = the clip's token budget; out_ids (optional)
+ *   receives the ids the session gave the clips (0, 1, 2 ... in submission order).  Everything is validated before
+ *   anything is queued; the PCM and prompts are copied.
+ * ttasr_session_poll: admits ready clips into free rows, runs decode steps until at least one clip finished, nothing is
+ *   left, or max_steps steps ran; returns up to `cap` finished clips: ids [cap], tokens [cap][opts->max_new_tokens]
+ *   (lens[k] valid, EOT kept when sampled, as ttasr_generate), sum_lp / no_speech [cap] (optional), *n_out.  Clips that
+ *   finished beyond `cap` are returned by the next poll.  *n_out == 0 means "idle" (nothing submitted is unfinished) only
+ *   when the poll did not stop at max_steps: with a bounded max_steps, count the clips received against those submitted (or
+ *   read ttasr_session_stats out[7] and ttasr_session_rows) before concluding that the session is idle.
+ * ttasr_session_rows: the batch's rows now (after the work enqueued so far has run): row_pos [max_batch] positions, done
+ *   [max_batch] finished flags (1 = finished or free), row_clip [max_batch] id of the clip holding the row or -1 (free);
+ *   any of the three may be NULL.  For monitoring and tests.
+ * ttasr_session_stats: out[0] decode steps, [1] polls, [2] encoder passes, [3] clips encoded, [4] live row-steps of the
+ *   clips returned so far (prompt_len - 1 + tokens each), [5] encoder ms (GPU events: mel + encoder + cross-KV),
+ *   [6] decode ms (GPU events around the step runs), [7] clips submitted and not yet admitted. */
+TTASR_API int ttasr_session_begin(ttasr_ctx* ctx, const ttasr_gen_opts* opts, int32_t max_prompt, float temperature);
+TTASR_API int ttasr_session_submit(ttasr_ctx* ctx, int32_t n, const float* const* pcm_host, const int64_t* n_samples,
+                                   const int32_t* prompt, const int32_t* prompt_len, const int32_t* max_new, int64_t* out_ids);
+TTASR_API int ttasr_session_poll(ttasr_ctx* ctx, int32_t max_steps, int32_t cap, int64_t* ids, int32_t* tokens, int32_t* lens,
+                                 float* sum_lp, float* no_speech, int32_t* n_out);
+TTASR_API int ttasr_session_stats(ttasr_ctx* ctx, double out[8]);
+TTASR_API int ttasr_session_rows(ttasr_ctx* ctx, int32_t* row_pos, int32_t* done, int64_t* row_clip);
+TTASR_API int ttasr_session_end(ttasr_ctx* ctx);
+
 /* ---- word timestamps (faster-whisper find_alignment -> ctranslate2 Whisper.align; WhisperModel.transcribe(word_timestamps=True),
  * requested at faster_whisper_asr.py:289-294) -------------------------------------------------------------------------- */
 /* Teacher-forces tokens_host[0..n_tokens) (sot sequence + text tokens + eot) against the resident encoder state of
@@ -244,8 +283,12 @@ TTASR_API int ttasr_dtw(const float* cost, int32_t n_rows, int32_t n_cols, int32
  * queries per wave; bit-identical);
  * "enc_kernel_timing" [0] per-launch events in ttasr_encode (see ttasr_encoder_kernel_ms); "xkv_fp8" [0] (16-bit engines; opt-in serving
  * mode, NOT the measured configuration) keeps an OCP e4m3 copy of the cross-KV cache with one scale per (layer, K | V, clip, head),
- * built by the next ttasr_encode and read by the decode step's cross-attention (half the bytes of the dominant kernel).
- * Drops the captured decode graphs.  Unknown key or value out of range: TTASR_E_INVALID. */
+ * built by the next ttasr_encode and read by the decode step's cross-attention (half the bytes of the dominant kernel);
+ * "refill_overlap" [0] the continuous-batching session encodes the next clips on a second stream of the context while the
+ * decode steps run (0: synchronously between two step runs on the context's one stream; results identical; read by
+ * ttasr_session_begin).  Opt-in: the second stream is a second hardware queue, and several processes sharing a GPU are then
+ * time-sliced;
+ * Drops the captured decode graphs (except "enc_kernel_timing" and "refill_overlap").  Unknown key or value out of range: TTASR_E_INVALID. */
 TTASR_API int ttasr_set_option(ttasr_ctx* ctx, const char* key, int32_t value);
 
 /* ---- measurement --------------------------------------------------------------------------------- */

@@ -247,6 +247,9 @@ struct LnPre {
 template <typename T>
 void launch_layernorm_rows(const float* x, const float* gamma, const float* beta, T* out, int rows, int d, const LnPre& pre,
                            hipStream_t s);
+// the embed form with PER-ROW positions (continuous-batching session): x_out[row] = emb[tok[row]] + pos[step[row]]
+template <typename T>
+void launch_layernorm_rows_embed_pos(const float* gamma, const float* beta, T* out, int rows, int d, const LnPre& pre, hipStream_t s);
 
 // K-split partial results of a decode GEMM handed to an attention kernel instead of T rows: value = round_T(bias +
 // slab[0] + ... + slab[n-1]) (slab order, bit-reproducible); n == 0 means "read the T rows as before"
@@ -346,6 +349,10 @@ void launch_self_attn_decode(const T* qkv /*[B][3d]*/, T* kv_pool, const int32_t
                              int64_t pool_layer_off, int identity_pages, int row0, const int32_t* step, T* out /*[B][d]*/, int B, int H,
                              hipStream_t s, SlabIn sq = SlabIn{} /*qkv from K-split partial tiles*/,
                              const int32_t* done = nullptr /*[B] (already offset by row0): finished rows leave the kernel*/);
+// the same kernel with a PER-ROW position row_pos[row0 + b] (continuous-batching session; identity pages)
+template <typename T>
+void launch_self_attn_decode_rows(const T* qkv, T* kv_pool, const int32_t* page_table, int pages_per_seq, int64_t pool_layer_off,
+                                  int row0, const int32_t* row_pos, T* out, int B, int H, hipStream_t s, SlabIn sq, const int32_t* done);
 template <typename T>
 void launch_copy_pages(T* pool, const int32_t* pairs_dev, int n_pairs, int n_layers, int H, int64_t layer_elems, hipStream_t s);
 template <typename T>
@@ -396,6 +403,13 @@ void launch_beam_topk(const float* logits, BeamRowState st, RuleParams rp, int R
 void launch_select(const float* logits, DecState st, RuleParams rp, int B, float* out_rows /*nullable*/, hipStream_t s,
                    int32_t* ticket, int total_rows);
 void launch_advance(int32_t* step, hipStream_t s);
+// the continuous-batching session's select (engine_refill.hip): st.step = per-row positions [B]; each live row advances its own
+void launch_select_rows(const float* logits, DecState st, RuleParams rp, int B, hipStream_t s);
+// row admission of the session: for each of the n entries of `tab` ([n][3 + max_prompt]: row, prompt length, token budget, prompt
+// tokens) every per-row field of the search state is reset, the prompt row and budget are stored, the row's position is set to 0
+// and its first token to prompt[0]; n_done is corrected for the rows that were finished
+void launch_admit_rows(const int32_t* tab, int n, int B, int max_prompt, DecState st, int32_t* prompt, int32_t* prompt_len, int32_t* row_cap,
+                       int32_t* row_pos, hipStream_t s);
 void launch_prep_weight(const void* src, int src_type /*0 f32, 1 bf16 bits, 2 fp16 bits*/, float* dst, int64_t n, int64_t conv_in, float scale,
                         hipStream_t s);
 template <typename T> void launch_cast(const float* in, T* out, int64_t n, hipStream_t s);

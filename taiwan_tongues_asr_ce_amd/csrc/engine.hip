@@ -5,33 +5,6 @@
 // =====================================================================================================
 // C ABI
 // =====================================================================================================
-// No C++ exception may cross the C ABI (std::bad_alloc from a host vector would otherwise terminate the caller's process)
-template <class F>
-static int guarded(ttasr_ctx* c, F&& f) {
-  // a context is not re-entrant (ttasr.h): a call that arrives while another is in flight on the same context is
-  // refused instead of corrupting the search state (its error text is not stored: the other call owns c->err)
-  struct Busy {
-    ttasr_ctx* c; bool own;
-    explicit Busy(ttasr_ctx* c_) : c(c_), own(c_ == nullptr || !c_->busy.test_and_set(std::memory_order_acquire)) {}
-    ~Busy() { if (c && own) c->busy.clear(std::memory_order_release); }
-  } busy(c);
-  if (!busy.own) return TTASR_E_INVALID;
-  if (c) { g_xattn_variant = c->xattn_nt | (c->xattn_pipe << 1); g_skinny_nt = c->weights_nt; g_skinny_narrow = c->dec_narrow ? 1 : 0; g_skinny_x_lds = c->dec_x_lds ? 1 : 0; g_xattn_deep_items = c->xattn_deep_items; g_xattn_mq_slices = c->xattn_mq_slices; g_flash_qw = c->flash_qw; }   // this context's kernel variants for everything f launches
-  g_launch_fault[0] = 0;
-  try {
-    const int rc = f();
-    // a launcher that had no kernel for what it was asked (common.hpp launch_fault) launched nothing: the call's output is invalid
-    if (g_launch_fault[0] && rc == TTASR_OK) return fail(c, TTASR_E_INVALID, "launcher refused: %s", g_launch_fault);
-    return rc;
-  } catch (const std::bad_alloc&) {
-    return fail(c, TTASR_E_NOMEM, "host allocation failed");
-  } catch (const std::exception& e) {
-    return fail(c, TTASR_E_INVALID, "C++ exception: %s", e.what());
-  } catch (...) {
-    return fail(c, TTASR_E_INVALID, "unknown C++ exception");
-  }
-}
-
 extern "C" {
 
 const char* ttasr_version(void) { return "ttasr 0.4 (gfx950, HIP; f32 | bf16 | fp16)"; }
@@ -150,6 +123,7 @@ int ttasr_set_option(ttasr_ctx* c, const char* key, int32_t value) {
   return guarded(c, [&]() -> int {
   if (!c) return TTASR_E_INVALID;
   if (!key) return fail(c, TTASR_E_INVALID, "key is NULL");
+  TRY(session_refusal(c));
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const int rc = set_option(c, key, value);
@@ -169,6 +143,7 @@ void ttasr_destroy(ttasr_ctx* c) {
       return;
     } }
   ttasr_ctx* owner = c->weight_owner;
+  session_free(c);
   drop_graphs(c);
   for (auto& e : c->ev) if (e) hipEventDestroy(e);
   for (auto& e : c->enc_ev) hipEventDestroy(e);
@@ -232,6 +207,7 @@ int ttasr_log_mel(ttasr_ctx* c, const float* pcm, int64_t pcm_stride, const int6
                   int32_t on_device, float* out_mel) {
   return guarded(c, [&]() -> int {
   if (!c) return TTASR_E_INVALID;
+  TRY(session_refusal(c));
   if (B < 1 || B > c->maxB) return fail(c, TTASR_E_INVALID, "batch %d outside [1, %d]", B, c->maxB);
   if (!pcm || !n_samples) return fail(c, TTASR_E_INVALID, "pcm / n_samples is NULL");
   HIPCHK(c, hipSetDevice(c->device));
@@ -276,6 +252,7 @@ int ttasr_log_mel_windows(ttasr_ctx* c, const float* const* file_pcm_of, const i
                           int32_t B, const float* floor_max, float* out_window_max, float* out_mel) {
   return guarded(c, [&]() -> int {
   if (!c) return TTASR_E_INVALID;
+  TRY(session_refusal(c));
   if (B < 1 || B > c->maxB) return fail(c, TTASR_E_INVALID, "batch %d outside [1, %d]", B, c->maxB);
   if (!file_pcm_of || !file_samples_of || !seek_frames) return fail(c, TTASR_E_INVALID, "NULL argument");
   HIPCHK(c, hipSetDevice(c->device));
@@ -326,6 +303,7 @@ int ttasr_log_mel_windows(ttasr_ctx* c, const float* const* file_pcm_of, const i
 int ttasr_set_mel(ttasr_ctx* c, const float* mel, int32_t B) {
   return guarded(c, [&]() -> int {
   if (!c) return TTASR_E_INVALID;
+  TRY(session_refusal(c));
   if (B < 1 || B > c->maxB || !mel) return fail(c, TTASR_E_INVALID, "bad arguments");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipMemcpyAsync(c->mel, mel, (size_t)B * c->M * c->F * 4, hipMemcpyHostToDevice, c->stream));
@@ -517,6 +495,7 @@ int ttasr_apply_rules(ttasr_ctx* c, const float* rows, const int32_t* hist, int3
                       const ttasr_gen_opts* o, float* out_rows, int32_t* out_choice) {
   return guarded(c, [&]() -> int {
   if (!c) return TTASR_E_INVALID;
+  TRY(session_refusal(c));
   if (n < 1 || n > c->maxB || !rows || !hist || !out_rows) return fail(c, TTASR_E_INVALID, "bad arguments (n <= max_batch)");
   HIPCHK(c, hipSetDevice(c->device));
   RuleParams old = c->rp;
@@ -665,6 +644,7 @@ int ttasr_dtw(const float* cost, int32_t n_rows, int32_t n_cols, int32_t* out_ro
 int ttasr_set_audio_ctx(ttasr_ctx* c, int32_t n_ctx) {
   return guarded(c, [&]() -> int {
   if (!c) return TTASR_E_INVALID;
+  TRY(session_refusal(c));
   if (n_ctx == 0) n_ctx = c->cfg.n_audio_ctx;
   if (n_ctx < 4 || n_ctx > c->cfg.n_audio_ctx || (n_ctx & 1))
     return fail(c, TTASR_E_INVALID, "audio context %d outside [4, %d] or odd", n_ctx, c->cfg.n_audio_ctx);

@@ -37,6 +37,7 @@ struct Slot {              // where one named tensor lands on the device
   int sh_rows_total = 0;    // rows of the whole packed matrix (a fused q/k/v matrix is packed as three parts): decides the block height
 };
 
+struct Session;            // continuous-batching session state (engine_refill.hip)
 struct EncLayerW { float *ln1g, *ln1b, *bqkv, *bo, *ln2g, *ln2b, *b1, *b2; void *wqkv, *wo, *w1, *w2; };
 struct DecLayerW {
   float *ln1g, *ln1b, *bqkv, *bo, *ln2g, *ln2b, *bqx, *bkvx, *box, *ln3g, *ln3b, *b1, *b2;
@@ -134,6 +135,15 @@ struct ttasr_ctx {
   float beam_prof_ms[4]{0, 0, 0, 0};   // last beam search: host time enqueueing, waiting for the GPU, selecting candidates; positions
   int max_new_alloc = 0, max_prompt_alloc = 0;
 
+  // continuous-batching session (engine_refill.hip): open between ttasr_session_begin and ttasr_session_end
+  ttasr_detail::Session* sess = nullptr;
+  bool session_rows = false;      // the decode step runs the per-row-position kernel forms (row_pos instead of st.step)
+  bool refill_overlap = false;    // option refill_overlap: encode the next clips on a second stream under the step graphs (opt-in:
+                                  // a second stream = a second hardware queue, which makes processes sharing the GPU time-slice)
+  int32_t* row_pos = nullptr;     // [maxB] per-row positions of the session (allocated by the first session)
+  void* xkv_stage = nullptr;      // [dec_layers][2][maxB][H][T][64] T: the session's encoder writes the admitted clips' cross-KV here
+  int32_t* admit_dev = nullptr;   // [maxB][3 + max_prompt_alloc] row-admission table (launch_admit_rows)
+
   int B_mel = 0, B_enc = 0, B_dec = 0;
   std::atomic_flag busy = ATOMIC_FLAG_INIT;  // one call in flight per context: a second concurrent call is refused
   int xattn_nt = 1, xattn_pipe = 1, weights_nt = 1;  // options xattn_nontemporal / xattn_pipeline / weights_nontemporal (per context; copied into the launchers' thread-locals by guarded())
@@ -175,6 +185,33 @@ int fail(ttasr_ctx* c, int code, const char* fmt, ...);
                                       __FILE__, __LINE__);                                                    \
   } while (0)
 
+
+// No C++ exception may cross the C ABI (std::bad_alloc from a host vector would otherwise terminate the caller's process)
+template <class F>
+inline int guarded(ttasr_ctx* c, F&& f) {
+  // a context is not re-entrant (ttasr.h): a call that arrives while another is in flight on the same context is
+  // refused instead of corrupting the search state (its error text is not stored: the other call owns c->err)
+  struct Busy {
+    ttasr_ctx* c; bool own;
+    explicit Busy(ttasr_ctx* c_) : c(c_), own(c_ == nullptr || !c_->busy.test_and_set(std::memory_order_acquire)) {}
+    ~Busy() { if (c && own) c->busy.clear(std::memory_order_release); }
+  } busy(c);
+  if (!busy.own) return TTASR_E_INVALID;
+  if (c) { g_xattn_variant = c->xattn_nt | (c->xattn_pipe << 1); g_skinny_nt = c->weights_nt; g_skinny_narrow = c->dec_narrow ? 1 : 0; g_skinny_x_lds = c->dec_x_lds ? 1 : 0; g_xattn_deep_items = c->xattn_deep_items; g_xattn_mq_slices = c->xattn_mq_slices; g_flash_qw = c->flash_qw; }   // this context's kernel variants for everything f launches
+  g_launch_fault[0] = 0;
+  try {
+    const int rc = f();
+    // a launcher that had no kernel for what it was asked (common.hpp launch_fault) launched nothing: the call's output is invalid
+    if (g_launch_fault[0] && rc == TTASR_OK) return fail(c, TTASR_E_INVALID, "launcher refused: %s", g_launch_fault);
+    return rc;
+  } catch (const std::bad_alloc&) {
+    return fail(c, TTASR_E_NOMEM, "host allocation failed");
+  } catch (const std::exception& e) {
+    return fail(c, TTASR_E_INVALID, "C++ exception: %s", e.what());
+  } catch (...) {
+    return fail(c, TTASR_E_INVALID, "unknown C++ exception");
+  }
+}
 
 // Device memory comes from a few large arenas, not one hipMalloc per tensor: the decode step is ~350 dependent launches
 // whose first access is to a small, rarely touched buffer (LayerNorm gamma / beta, a bias, the residual rows).  With ~2500
@@ -261,6 +298,10 @@ int prefill_positions(const ttasr_ctx* c, int min_plen, const ttasr_gen_opts* o,
 int step_graph(ttasr_ctx* c, int B, int mode, int nsteps = 1);
 void drop_graphs(ttasr_ctx* c);
 void drop_rule_graphs(ttasr_ctx* c);
+
+// ---- engine_refill.hip: the continuous-batching session ----
+int session_refusal(ttasr_ctx* c);   // TTASR_E_INVALID with a message while a session is open, else 0
+void session_free(ttasr_ctx* c);     // ttasr_destroy: the session's stream, events and pinned memory
 
 // ---- engine_search.hip: rules, options, greedy / sampled / beam search ----
 int check_ready(ttasr_ctx* c, int B);

@@ -208,7 +208,10 @@ void run_decode_rows(ttasr_ctx* c, int row0, int n, int mode, int total_rows) {
   const bool skinny = sizeof(T) == 2 && !c->force_basic;
   // round 6: rows whose search has FINISHED (st.done, set by select_kernel / uploaded by the beam search) leave the attention
   // kernels of the step - the per-row cross-KV and self-KV streams are the bytes of a decode step that scale with the rows
-  const int32_t* done = c->ragged_exit ? c->st.done + row0 : nullptr;
+  // the continuous-batching session (engine_refill.hip) runs the per-row-position forms of the three kernels that read the position;
+  // its idle and finished rows always leave the attention kernels (their slots may be refilled by a concurrent encode)
+  const bool rows_pos = c->session_rows;
+  const int32_t* done = (c->ragged_exit || rows_pos) ? c->st.done + row0 : nullptr;
   float* slab_base = c->slab;
   // K slices per GEMM kind (0 out-proj, 1 q, 2 qkv, 3 fc2); attention consumers sum at most 4 slabs
   auto slices = [&](int kind, int N, int K) {
@@ -256,9 +259,10 @@ void run_decode_rows(ttasr_ctx* c, int row0, int n, int mode, int total_rows) {
     if (c->skip_mask & 1) return;
     LnPre pre;
     pre.x_out = dx;
-    if (pend.embed) { pre.tok = c->st.cur_tok + row0; pre.step = c->st.step; pre.emb = c->emb; pre.pos = c->dpos; }
+    if (pend.embed) { pre.tok = c->st.cur_tok + row0; pre.step = rows_pos ? c->row_pos + row0 : c->st.step; pre.emb = c->emb; pre.pos = c->dpos; }
     else if (pend.n_slab) { pre.bias = pend.bias; pre.slab = slab_base; pre.n_slab = pend.n_slab; pre.slab_stride = (int64_t)c->maxB * d; }
-    launch_layernorm_rows<T>(dx, g_, b_, (T*)dh, n, d, pre, s);
+    if (pend.embed && rows_pos) launch_layernorm_rows_embed_pos<T>(g_, b_, (T*)dh, n, d, pre, s);
+    else launch_layernorm_rows<T>(dx, g_, b_, (T*)dh, n, d, pre, s);
     pend.bias = nullptr; pend.n_slab = 0; pend.embed = false;
   };
   for (int l = 0; l < c->cfg.dec_layers; ++l) {
@@ -268,7 +272,10 @@ void run_decode_rows(ttasr_ctx* c, int row0, int n, int mode, int total_rows) {
     { GemmArgs g = lin_args<T>(dh, L.wqkv, n, 3 * d, d);
       sqkv = split_gemm(g, L.wqkv_sh, L.bqkv, slices(2, 3 * d, d));
       if (!sqkv.n) { g.epi.bias = L.bqkv; g.epi.out_t = dqkv; dec_gemm<T>(c, g, L.wqkv_sh); } }
-    if (!(c->skip_mask & 4))
+    if (!(c->skip_mask & 4) && rows_pos)
+      launch_self_attn_decode_rows<T>((const T*)dqkv, (T*)c->pool, c->page_table, c->pages_per_seq, (int64_t)l * c->pool_layer_elems,
+                                      row0, c->row_pos, (T*)datt, n, c->H, s, sqkv, done);
+    else if (!(c->skip_mask & 4))
       launch_self_attn_decode<T>((const T*)dqkv, (T*)c->pool, c->page_table, c->pages_per_seq, (int64_t)l * c->pool_layer_elems,
                                  c->identity_pages, row0, c->st.step, (T*)datt, n, c->H, s, sqkv, done);
     residual_gemm(datt, L.wo, L.wo_sh, L.bo, d, 0);
@@ -307,7 +314,8 @@ void run_decode_rows(ttasr_ctx* c, int row0, int n, int mode, int total_rows) {
     st.cur_tok += row0; st.n_sampled += row0; st.last_tok += row0; st.pen_tok += row0; st.last_ts += row0; st.done += row0;
     st.sum_logprob += row0; st.no_speech += row0; st.out_tokens += (size_t)row0 * c->rp.max_new; st.row_cap += row0;
     if (st.prompt) { st.prompt += (size_t)row0 * c->rp.max_prompt; st.prompt_len += row0; }
-    launch_select(logits, st, c->rp, n, nullptr, s, c->st.step + 1, total_rows);
+    if (rows_pos) { st.step = c->row_pos + row0; launch_select_rows(logits, st, c->rp, n, s); }
+    else launch_select(logits, st, c->rp, n, nullptr, s, c->st.step + 1, total_rows);
   }
 }
 
@@ -452,7 +460,7 @@ int step_graph(ttasr_ctx* c, int B, int mode, int nsteps) {
   // changes with encode (run_cross_kv builds it), not only with set_option (a graph captured between
   // set_option(xkv_fp8) and the next encode held the 16-bit kernel and kept replaying after the copy existed)
   const int fp8_live = (c->xkv_fp8 && c->xkv8_valid) ? 1 : 0;
-  const int variant = ((c->kv_div * 2 + c->identity_pages) * 2 + fp8_live) * 64 + nsteps;
+  const int variant = ((c->kv_div * 2 + c->identity_pages) * 2 + fp8_live) * 64 + nsteps + (c->session_rows ? 1 << 24 : 0);
   for (size_t i = 0; i < c->graphs.size(); ++i) {
     if (c->graphs[i].B == B && c->graphs[i].mode == mode && c->graphs[i].variant == variant) {
       // most recently used at the back: the cache is bounded (the streaming micro-batcher varies B from 1 to max_batch rows)

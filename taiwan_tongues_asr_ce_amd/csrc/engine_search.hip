@@ -8,6 +8,7 @@ namespace ttasr_detail {
 int check_ready(ttasr_ctx* c, int B) {
   if (!c) return TTASR_E_INVALID;
   if (!c->finalized) return fail(c, TTASR_E_INVALID, "weights not finalized (call ttasr_finalize_weights first)");
+  TRY(session_refusal(c));
   if (B < 1 || B > c->maxB) return fail(c, TTASR_E_INVALID, "batch %d outside [1, max_batch=%d]", B, c->maxB);
   HIPCHK(c, hipSetDevice(c->device));
   return 0;
@@ -57,6 +58,7 @@ int commit_rules(ttasr_ctx* c, const RuleParams& old) {
 int set_option(ttasr_ctx* c, const std::string& key, int v) {
   const bool on = v != 0;
   if (key == "enc_kernel_timing") { c->enc_timing = on; return 0; }   // measurement only: the captured decode graphs stay
+  if (key == "refill_overlap") { c->refill_overlap = on; return 0; }   // host-side schedule of the session: the graphs stay
   if (key == "flash") c->no_flash = !on;
   else if (key == "prefill") c->no_prefill = !on;
   else if (key == "vocab_persistent") c->vocab_persistent = on;

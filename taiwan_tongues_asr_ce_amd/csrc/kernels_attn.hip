@@ -178,6 +178,7 @@ using u32x4_t = __attribute__((ext_vector_type(4))) unsigned;
 // grid row b is position (b % npos) of sequence (b / npos); launch 1 only appends every position's k,v to the
 // pool, launch 2 attends causally (keys 0..pos-1 from the pool, its own from registers) without appending - two
 // launches because a position reads keys that other workgroups of the first launch write.
+// MODE 3 is MODE 0 with a PER-ROW position (the continuous-batching session, engine_refill.hip): step[row0 + b] instead of *step.
 template <typename T, int MODE, bool SLAB, bool IDENT>
 __global__ __launch_bounds__(256) void self_attn_decode_kernel(const T* qkv, T* pool, const int32_t* page_table,
                                                                int pages_per_seq, int identity_pages, int row0,
@@ -195,12 +196,12 @@ __global__ __launch_bounds__(256) void self_attn_decode_kernel(const T* qkv, T* 
   sq.slab = sgpr_pin_ptr(sq.slab); sq.bias = sgpr_pin_ptr(sq.bias); sq.n = sgpr_pin(sq.n); sq.stride = sgpr_pin(sq.stride);
   sq.ld = sgpr_pin(sq.ld);
   const int b = blockIdx.y, h = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int d = H * 64, pos = MODE == 0 ? *step : b % npos;
+  const int d = H * 64, pos = MODE == 0 ? *step : (MODE == 3 ? step[b + row0] : b % npos);
   const int done_raw = row_done_issue(done, b, pool);   // scalar load, in flight under the vector loads below (see row_done_exit)
   const T* qp = qkv + (int64_t)b * 3 * d + h * 64;
   const int sub = lane % LPR, rin = lane / LPR;
   // global row: qkv / out are already offset to the half-batch, the KV pages are not
-  const int bg = MODE == 0 ? b + row0 : b / npos;
+  const int bg = (MODE == 0 || MODE == 3) ? b + row0 : b / npos;
   const int32_t* pt = page_table + bg * pages_per_seq;
   // IDENT (greedy decoding never re-indexes the table): the page id is computed, not loaded - no dependent load
   auto page_of = [&](int t) { return IDENT ? bg * pages_per_seq + t / PAGE : pt[t / PAGE]; };
@@ -241,7 +242,7 @@ __global__ __launch_bounds__(256) void self_attn_decode_kernel(const T* qkv, T* 
   // Round 6: a FINISHED row of the batch (select_kernel set done[b] at an earlier step: EOT sampled, or the row's token budget
   // reached) leaves the kernel here - nothing appended, nothing attended, `out` keeps the row's last live values.  Rows are
   // computed independently of their neighbours everywhere in the decode step, so the live rows' bits do not change.
-  if (MODE == 0 && done && done_raw) { if (npos < 0) red[0][0] = kv[0][0] + vv[0][0] + q[0]; return; }   // (never-taken store: row_done_exit)
+  if ((MODE == 0 || MODE == 3) && done && done_raw) { if (npos < 0) red[0][0] = kv[0][0] + vv[0][0] + q[0]; return; }   // (never-taken store: row_done_exit)
   if (MODE != 2 && wave == 0 && rin == 0) {  // append this step's k, v
     const int page = page_of(pos);
     T* kdst = pool + ((((int64_t)page * 2 + 0) * H + h) * PAGE + (pos % PAGE)) * 64;
@@ -322,6 +323,18 @@ void launch_self_attn_decode(const T* qkv, T* kv_pool, const int32_t* page_table
   else { if (identity_pages) TTASR_SA(false, true); else TTASR_SA(false, false); }
 #undef TTASR_SA
 }
+// the session form: row_pos [row0 + B] per-row positions, identity pages (greedy), finished / idle rows leave via `done`
+template <typename T>
+void launch_self_attn_decode_rows(const T* qkv, T* kv_pool, const int32_t* page_table, int pages_per_seq, int64_t pool_layer_off,
+                                  int row0, const int32_t* row_pos, T* out, int B, int H, hipStream_t s, SlabIn sq,
+                                  const int32_t* done) {
+  if (sq.n > 0)
+    hipLaunchKernelGGL((self_attn_decode_kernel<T, 3, true, true>), dim3(H, B), dim3(256), 0, s, qkv, kv_pool + pool_layer_off,
+                       page_table, pages_per_seq, 1, row0, row_pos, out, done, H, 1, sq);
+  else
+    hipLaunchKernelGGL((self_attn_decode_kernel<T, 3, false, true>), dim3(H, B), dim3(256), 0, s, qkv, kv_pool + pool_layer_off,
+                       page_table, pages_per_seq, 1, row0, row_pos, out, done, H, 1, sq);
+}
 // prompt prefill: rows = n_seq * npos, row-major [sequence][position]; positions 0..npos-1 of every sequence
 template <typename T>
 void launch_self_attn_prefill(const T* qkv, T* kv_pool, const int32_t* page_table, int pages_per_seq, int64_t pool_layer_off,
@@ -363,6 +376,11 @@ template void launch_self_attn_decode<bf16_t>(const bf16_t*, bf16_t*, const int3
                                               bf16_t*, int, int, hipStream_t, SlabIn, const int32_t*);
 template void launch_self_attn_decode<f16_t>(const f16_t*, f16_t*, const int32_t*, int, int64_t, int, int, const int32_t*,
                                               f16_t*, int, int, hipStream_t, SlabIn, const int32_t*);
+#define TTASR_SA_ROWS(T_)                                                                                                 \
+  template void launch_self_attn_decode_rows<T_>(const T_*, T_*, const int32_t*, int, int64_t, int, const int32_t*, T_*, int, int, \
+                                                 hipStream_t, SlabIn, const int32_t*)
+TTASR_SA_ROWS(float); TTASR_SA_ROWS(bf16_t); TTASR_SA_ROWS(f16_t);
+#undef TTASR_SA_ROWS
 
 // ------------------------------------------------------------------------------------------------
 // decoder cross-attention.  K, V: [B][H][Tk][64] (head-major, written by the cross-KV GEMM epilogue), so

@@ -185,10 +185,13 @@ __device__ __forceinline__ void step_ticket(int32_t* ticket, int total_rows, int
   if (ticket && atomicAdd(ticket, 1) == total_rows - 1) { *ticket = 0; *step = step_now + 1; }
 }
 // SAMPLE: temperature > 0 (Gumbel-max pass); HOOK: out_rows != nullptr (test API: the processed row is written out).  The decode
-// step of the benchmark is <false, false>.
-template <bool SAMPLE, bool HOOK>
-__global__ __launch_bounds__(1024) void select_kernel(const float* logits, DecState st, RuleParams p, float* out_rows,
-                                                      int32_t* ticket, int total_rows) {
+// step of the benchmark is select_kernel<false, false>.
+// ROWPOS (select_rows_kernel only, the continuous-batching session of engine_refill.hip): st.step is a PER-ROW position array
+// [B]; the row's own position decides forced vs sampled, the no-speech capture and the sampling key, and the workgroup advances
+// its own row (a live row only: a finished or idle row keeps its position), so no ticket is drawn.
+template <bool SAMPLE, bool HOOK, bool ROWPOS>
+__device__ __forceinline__ void select_body(const float* logits, DecState st, RuleParams p, float* out_rows, int32_t* ticket,
+                                            int total_rows) {
   __shared__ ArgMax s_am[2][16];
   __shared__ float s_sum[3][16];
   __shared__ float s_b[8];
@@ -211,7 +214,7 @@ __global__ __launch_bounds__(1024) void select_kernel(const float* logits, DecSt
   RowRegs R;
   uint32_t mw[LOGIT_NIT], tmw;
   load_row_regs(R, mw, tmw, row, st.mask, p.V, tid);
-  const int step = *st.step;
+  const int step = ROWPOS ? st.step[b] : *st.step;
   const int plen_raw = *(st.prompt_len ? st.prompt_len + b : st.n_sampled + b);  // unconditional: no branch in front of the loads below
   RowRule r;
   r.n = st.n_sampled[b];
@@ -224,12 +227,16 @@ __global__ __launch_bounds__(1024) void select_kernel(const float* logits, DecSt
   const int plen = st.prompt_len ? plen_raw : 1;
 
   const bool forced = st.prompt && (step + 1 < plen);
-  const bool want_ns = p.no_speech >= 0 && step == p.sot_index && st.no_speech;
+  const bool want_ns = p.no_speech >= 0 && step == p.sot_index && st.no_speech && !(ROWPOS && done_b);
   if (forced && !want_ns && !HOOK) {
     // every wave of this workgroup has read *st.step before its ticket is drawn: the workgroup that draws the last ticket
     // stores step + 1, and a slower wave must not see that value and leave this branch alone
     __syncthreads();
-    if (tid == 0) { st.cur_tok[b] = st.prompt[b * p.max_prompt + step + 1]; step_ticket(ticket, total_rows, st.step, step); }
+    if (tid == 0) {
+      st.cur_tok[b] = st.prompt[b * p.max_prompt + step + 1];
+      if constexpr (ROWPOS) { if (!done_b) st.step[b] = step + 1; }
+      else step_ticket(ticket, total_rows, st.step, step);
+    }
     return;
   }
   const int tb = p.timestamp_begin;
@@ -335,12 +342,55 @@ __global__ __launch_bounds__(1024) void select_kernel(const float* logits, DecSt
     // row (done[b]: kernels_attn.hip row_done_exit) and the `done_b` branch above feeds it EOT without touching its state.
     if (choice == p.eot || r.n + 1 >= min(p.max_new, cap_b)) { st.done[b] = 1; atomicAdd(st.n_done, 1); }
   }
-  if (tid == 0) step_ticket(ticket, total_rows, st.step, step);
+  if constexpr (ROWPOS) { if (tid == 0 && !done_b) st.step[b] = step + 1; }
+  else if (tid == 0) step_ticket(ticket, total_rows, st.step, step);
   if constexpr (HOOK) {  // known-answer hook: the forced-timestamp branch also masks the text range
     __syncthreads();
     if (s_i[2])
       for (int i = tid; i < tb; i += 1024) out_rows[(int64_t)b * p.V + i] = -INFINITY;
   }
+}
+
+template <bool SAMPLE, bool HOOK>
+__global__ __launch_bounds__(1024) void select_kernel(const float* logits, DecState st, RuleParams p, float* out_rows,
+                                                      int32_t* ticket, int total_rows) {
+  select_body<SAMPLE, HOOK, false>(logits, st, p, out_rows, ticket, total_rows);
+}
+template <bool SAMPLE>
+__global__ __launch_bounds__(1024) void select_rows_kernel(const float* logits, DecState st, RuleParams p) {
+  select_body<SAMPLE, false, true>(logits, st, p, nullptr, nullptr, 0);
+}
+
+void launch_select_rows(const float* logits, DecState st, RuleParams rp, int B, hipStream_t s) {
+  if (rp.V > LOGIT_NIT * 4096) { launch_fault("select: vocabulary %d > %d", rp.V, LOGIT_NIT * 4096); return; }
+  if (rp.temperature > 0.f) hipLaunchKernelGGL((select_rows_kernel<true>), dim3(B), dim3(1024), 0, s, logits, st, rp);
+  else hipLaunchKernelGGL((select_rows_kernel<false>), dim3(B), dim3(1024), 0, s, logits, st, rp);
+}
+
+// Row admission (continuous-batching session): one workgroup per admitted row.  Runs on the decode stream between two step
+// graphs, which read everything reset here from device memory.  Entry e of `tab`: {row, prompt length, token budget, prompt[max_prompt]}.
+__global__ __launch_bounds__(64) void admit_rows_kernel(const int32_t* __restrict__ tab, int B, int max_prompt, DecState st,
+                                                        int32_t* __restrict__ prompt, int32_t* __restrict__ prompt_len,
+                                                        int32_t* __restrict__ row_cap, int32_t* __restrict__ row_pos) {
+  const int32_t* e = tab + (int64_t)blockIdx.x * (3 + max_prompt);
+  const int row = e[0];
+  if (row < 0 || row >= B) return;   // the host validated the table; never write outside the batch
+  for (int j = threadIdx.x; j < max_prompt; j += 64) prompt[(int64_t)row * max_prompt + j] = e[3 + j];
+  if (threadIdx.x == 0) {
+    prompt_len[row] = e[1];
+    row_cap[row] = e[2];
+    row_pos[row] = 0;
+    st.cur_tok[row] = e[3];
+    st.n_sampled[row] = 0;
+    st.last_tok[row] = -1; st.pen_tok[row] = -1; st.last_ts[row] = -1;
+    st.sum_logprob[row] = 0.f; st.no_speech[row] = 0.f;
+    if (st.done[row]) atomicSub(st.n_done, 1);
+    st.done[row] = 0;
+  }
+}
+void launch_admit_rows(const int32_t* tab, int n, int B, int max_prompt, DecState st, int32_t* prompt, int32_t* prompt_len,
+                       int32_t* row_cap, int32_t* row_pos, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(admit_rows_kernel, dim3(n), dim3(64), 0, s, tab, B, max_prompt, st, prompt, prompt_len, row_cap, row_pos);
 }
 
 void launch_select(const float* logits, DecState st, RuleParams rp, int B, float* out_rows, hipStream_t s, int32_t* ticket,

@@ -303,7 +303,10 @@ template void launch_layernorm_add<f16_t>(float*, const f16_t*, const float*, co
 // token + position embedding of this step (first LayerNorm of the decoder: replaces the embed launch).
 // MAXS = compile-time bound on n_slab: the loads of all slabs are issued unconditionally (index clamped), nothing
 // branches around a load.
+// MAXS = LN_ROW_POS with EMBED (the continuous-batching session, engine_refill.hip): pre.step is a PER-ROW position array and
+// row r's positional-embedding row is pos[step[r]] instead of pos[*step].
 // ------------------------------------------------------------------------------------------------
+constexpr int LN_ROW_POS = -1;
 template <typename T, int MAXS, bool EMBED>
 __global__ __launch_bounds__(320) void layernorm_rows_kernel(const float* __restrict__ x_, const float* __restrict__ gamma_,
                                                              const float* __restrict__ beta_, T* __restrict__ out_, int d_,
@@ -325,7 +328,7 @@ __global__ __launch_bounds__(320) void layernorm_rows_kernel(const float* __rest
   const float4 gm = ((const float4*)gamma)[i], bt = ((const float4*)beta)[i];
   if constexpr (EMBED) {
     const T* er = (const T*)pre.emb + (int64_t)pre.tok[row] * d;
-    const T* pr = (const T*)pre.pos + (int64_t)(*pre.step) * d;
+    const T* pr = (const T*)pre.pos + (int64_t)(MAXS == LN_ROW_POS ? pre.step[row] : *pre.step) * d;
     if constexpr (sizeof(T) == 4) {
       const float4 a = ((const float4*)er)[i], b = ((const float4*)pr)[i];
       v = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
@@ -391,6 +394,16 @@ void launch_layernorm_rows(const float* x, const float* gamma, const float* beta
   else if (pre.n_slab <= 8) hipLaunchKernelGGL((layernorm_rows_kernel<T, 8, false>), grid, block, 0, s, x, gamma, beta, out, d, pre);
   else hipLaunchKernelGGL((layernorm_rows_kernel<T, 16, false>), grid, block, 0, s, x, gamma, beta, out, d, pre);
 }
+// the session's first decoder LayerNorm: embedding form with per-row positions (pre.tok and pre.step = row positions [rows])
+template <typename T>
+void launch_layernorm_rows_embed_pos(const float* gamma, const float* beta, T* out, int rows, int d, const LnPre& pre, hipStream_t s) {
+  if (d > 1280 || (d & 3)) { launch_fault("layernorm_rows needs d <= 1280, d %% 4 == 0 (got %d)", d); return; }
+  if (!pre.tok || !pre.step) { launch_fault("layernorm_rows_embed_pos needs tokens and row positions"); return; }
+  hipLaunchKernelGGL((layernorm_rows_kernel<T, LN_ROW_POS, true>), dim3(rows), dim3(320), 0, s, nullptr, gamma, beta, out, d, pre);
+}
+template void launch_layernorm_rows_embed_pos<float>(const float*, const float*, float*, int, int, const LnPre&, hipStream_t);
+template void launch_layernorm_rows_embed_pos<bf16_t>(const float*, const float*, bf16_t*, int, int, const LnPre&, hipStream_t);
+template void launch_layernorm_rows_embed_pos<f16_t>(const float*, const float*, f16_t*, int, int, const LnPre&, hipStream_t);
 template void launch_layernorm_rows<float>(const float*, const float*, const float*, float*, int, int, const LnPre&, hipStream_t);
 template void launch_layernorm_rows<bf16_t>(const float*, const float*, const float*, bf16_t*, int, int, const LnPre&, hipStream_t);
 template void launch_layernorm_rows<f16_t>(const float*, const float*, const float*, f16_t*, int, int, const LnPre&, hipStream_t);

@@ -241,6 +241,12 @@ class Engine:
                                             lp.ctypes.data_as(f32p), ns.ctypes.data_as(f32p)), "generate")
         return GenResult([toks[b, :lens[b]].tolist() for b in range(B)], lp, ns)
 
+    def session(self, opts, max_prompt: int, temperature: float = 0.0) -> "Session":
+        """Continuous-batching session (ttasr_session_*): greedy, single-window decoding of clips submitted at any time; each clip
+        takes a free row of the max_batch-row decode batch and hands it to the next queued clip when it finishes.  A context
+        manager: the session ends when the block is left.  While it is open the engine's other search / encode calls are refused."""
+        return Session(self, opts, max_prompt, temperature)
+
     def generate_beam(self, prompts: Sequence[Sequence[int]], beam: int, opts, patience: float = 1.0,
                       sot_index: Optional[Sequence[int]] = None) -> GenResult:
         """Beam search over len(prompts) clips; rows = clips * beam <= max_batch.  Prompts may differ in length (one
@@ -352,3 +358,122 @@ class Engine:
 
     def sync(self):
         self._check(self.lib.ttasr_sync(self.h), "sync")
+
+
+@dataclass
+class SessionResult:
+    id: int
+    tokens: List[int]
+    sum_logprob: float
+    no_speech_prob: float
+
+
+class Session:
+    """Engine.session(): submit(clips, prompts, max_new) -> clip ids; poll() -> finished clips (SessionResult, any order)."""
+
+    def __init__(self, engine: Engine, opts, max_prompt: int, temperature: float = 0.0):
+        self.engine, self.opts, self.max_prompt = engine, opts, int(max_prompt)
+        self.max_new_tokens = int(opts.max_new_tokens)
+        self.window = 2 * engine.audio_ctx * 160
+        self.open = False
+        self.pending = 0
+        engine._check(engine.lib.ttasr_session_begin(engine.h, C.byref(opts), self.max_prompt, C.c_float(temperature)),
+                      "session_begin")
+        self.open = True
+
+    def __enter__(self) -> "Session":
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self.open:
+            self.open = False
+            self.engine._check(self.engine.lib.ttasr_session_end(self.engine.h), "session_end")
+
+    def submit(self, clips: Sequence[np.ndarray], prompts: Sequence[Sequence[int]], max_new: Optional[Sequence[int]] = None
+               ) -> List[int]:
+        """Queue clips (float32 PCM, at most one window each) with one prompt each; max_new = per-clip token budgets in
+        [1, opts.max_new_tokens] (default: opts.max_new_tokens).  Shapes and budgets are checked here before the library is called."""
+        if not self.open:
+            raise TtasrError("session is closed")
+        n = len(clips)
+        if n < 1 or len(prompts) != n:
+            raise ValueError(f"need >= 1 clip and one prompt per clip (clips {n}, prompts {len(prompts)})")
+        caps = np.full(n, self.max_new_tokens, dtype=np.int32) if max_new is None else np.ascontiguousarray(max_new, dtype=np.int32)
+        if caps.shape != (n,):
+            raise ValueError(f"max_new needs one entry per clip ({n}), got shape {caps.shape}")
+        if caps.min() < 1 or caps.max() > self.max_new_tokens:
+            raise ValueError(f"max_new entries must lie in [1, {self.max_new_tokens}]")
+        pcm = []
+        for i, c in enumerate(clips):
+            a = np.ascontiguousarray(c, dtype=np.float32)
+            if a.ndim != 1:
+                raise ValueError(f"clip {i}: PCM must be one-dimensional, got shape {a.shape}")
+            if len(a) > self.window:
+                raise ValueError(f"clip {i}: {len(a)} samples is longer than one window ({self.window})")
+            pcm.append(a)
+        pr = np.zeros((n, self.max_prompt), dtype=np.int32)
+        pl = np.zeros(n, dtype=np.int32)
+        for i, p in enumerate(prompts):
+            if not 1 <= len(p) <= self.max_prompt:
+                raise ValueError(f"clip {i}: prompt length {len(p)} outside [1, {self.max_prompt}]")
+            pr[i, :len(p)] = p
+            pl[i] = len(p)
+        ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in pcm])
+        ns = np.asarray([len(a) for a in pcm], dtype=np.int64)
+        ids = np.zeros(n, dtype=np.int64)
+        i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        self.engine._check(self.engine.lib.ttasr_session_submit(
+            self.engine.h, n, ptrs, ns.ctypes.data_as(i64p), pr.ctypes.data_as(i32p), pl.ctypes.data_as(i32p),
+            caps.ctypes.data_as(i32p), ids.ctypes.data_as(i64p)), "session_submit")
+        self.pending += n
+        return ids.tolist()
+
+    def poll(self, max_steps: int = 1 << 30, cap: Optional[int] = None) -> List[SessionResult]:
+        """Admit ready clips, decode until at least one clip finished (or nothing is left, or max_steps steps ran); returns the
+        finished clips (at most `cap`, default max_batch)."""
+        if not self.open:
+            raise TtasrError("session is closed")
+        cap = self.engine.max_batch if cap is None else int(cap)
+        if cap < 1 or max_steps < 1:
+            raise ValueError("cap and max_steps must be >= 1")
+        ids = np.zeros(cap, dtype=np.int64)
+        toks = np.zeros((cap, self.max_new_tokens), dtype=np.int32)
+        lens = np.zeros(cap, dtype=np.int32)
+        lp = np.zeros(cap, dtype=np.float32)
+        nsp = np.zeros(cap, dtype=np.float32)
+        n_out = C.c_int32(0)
+        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        self.engine._check(self.engine.lib.ttasr_session_poll(
+            self.engine.h, int(min(max_steps, 2**31 - 1)), cap, ids.ctypes.data_as(C.POINTER(C.c_int64)), toks.ctypes.data_as(i32p),
+            lens.ctypes.data_as(i32p), lp.ctypes.data_as(f32p), nsp.ctypes.data_as(f32p), C.byref(n_out)), "session_poll")
+        k = n_out.value
+        self.pending -= k
+        return [SessionResult(int(ids[i]), toks[i, :lens[i]].tolist(), float(lp[i]), float(nsp[i])) for i in range(k)]
+
+    def drain(self) -> List[SessionResult]:
+        """Poll until every submitted clip has finished."""
+        out: List[SessionResult] = []
+        while self.pending > 0:
+            got = self.poll()
+            if not got:
+                raise TtasrError(f"session idle with {self.pending} clips unfinished")
+            out.extend(got)
+        return out
+
+    def rows(self) -> Dict[str, np.ndarray]:
+        """The batch's rows now (ttasr_session_rows): position, finished flag (1 = finished or free), clip id (-1 = free)."""
+        B = self.engine.max_batch
+        pos, done, clip = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int64)
+        i32p = C.POINTER(C.c_int32)
+        self.engine._check(self.engine.lib.ttasr_session_rows(self.engine.h, pos.ctypes.data_as(i32p), done.ctypes.data_as(i32p),
+                                                              clip.ctypes.data_as(C.POINTER(C.c_int64))), "session_rows")
+        return dict(row_pos=pos, done=done, clip=clip)
+
+    def stats(self) -> Dict[str, float]:
+        a = (C.c_double * 8)()
+        self.engine._check(self.engine.lib.ttasr_session_stats(self.engine.h, a), "session_stats")
+        return dict(zip(("steps", "polls", "encodes", "clips_encoded", "live_row_steps", "encode_ms", "decode_ms", "queued"),
+                        (float(v) for v in a)))

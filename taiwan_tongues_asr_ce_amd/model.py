@@ -784,6 +784,36 @@ class WhisperModel:
             out.extend(eng.generate([prompt] * len(chunk), opts).tokens)
         return out
 
+    def transcribe_stream(self, clips: Sequence[np.ndarray], language: str = "zh", task: str = "transcribe",
+                          without_timestamps: bool = True, max_new_tokens: int = 224,
+                          row_max_new: Optional[Sequence[int]] = None) -> List[List[int]]:
+        """transcribe_batch's contract (clips <= 30 s each, sampled token ids per clip, input order) for any number of clips,
+        through a continuous-batching session: a clip that finishes hands its decode row to the next one instead of waiting for
+        the rest of its batch.  row_max_new (optional): one token budget per clip, each in [1, max_new_tokens]."""
+        if len(clips) == 0:
+            return []
+        eng = self.engine
+        lang_tok = self._lang_token(language)
+        prompt, sot_index = self._prompt(lang_tok, task, without_timestamps, [])
+        n_new = min(max_new_tokens, self.dims.n_text_ctx - len(prompt))
+        caps = None
+        if row_max_new is not None:
+            caps = [int(v) for v in row_max_new]
+            if len(caps) != len(clips) or min(caps) < 1 or max(caps) > n_new:
+                raise ValueError(f"row_max_new needs one budget in [1, {n_new}] per clip")
+        for c in clips:
+            if len(c) > self.n_window:
+                raise ValueError(f"transcribe_stream takes clips of at most one window ({self.n_window} samples)")
+        eng.set_audio_ctx(0)
+        opts = eng.gen_opts(n_new, timestamps=not without_timestamps, sot_index=sot_index)
+        out: List[Optional[List[int]]] = [None] * len(clips)
+        with eng.session(opts, len(prompt)) as s:
+            ids = s.submit([np.ascontiguousarray(c, dtype=np.float32) for c in clips], [prompt] * len(clips), caps)
+            where = {cid: i for i, cid in enumerate(ids)}
+            for r in s.drain():
+                out[where[r.id]] = r.tokens
+        return out  # type: ignore[return-value]
+
     def _pick_audio_ctx(self, audio_ctx: Union[None, int, str], longest_samples: int) -> int:
         full = self.dims.n_audio_ctx
         if audio_ctx is None:

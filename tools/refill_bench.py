@@ -1,0 +1,133 @@
+"""Continuous batching against the static path, in one process on the same clips and budgets.
+
+Workload: large-v3 geometry (synthetic weights), bf16, 256 synthetic 30-s clips, 4-token prompt, seeded per-clip token budgets
+uniform in 32 ... 128 (synthetic weights emit no meaningful EOT: the budgets are the lengths).
+  (a) static: batches of 32 clips through log-mel, encoder and ttasr_generate_capped (what bench.py side.ragged times);
+  (b) the session (ttasr_session_*) with option refill_overlap = 0 (the default): the next clips are encoded between two step runs;
+  (c) the session with refill_overlap = 1 (opt-in, a second stream): the next clips are encoded while the decode steps run.
+Prints one JSON line: audio-s/s, encoder / decode GPU ms, mean live rows per decode step, b/a and c/a, and whether every clip's
+tokens agree across the three runs.
+
+    python tools/refill_bench.py [--clips 256] [--model large-v3] [--check-interval 8] [--out profiles/refill_bench.json]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from taiwan_tongues_asr_ce_amd import synth  # noqa: E402
+from taiwan_tongues_asr_ce_amd.config import COMPUTE_BF16, PRESETS  # noqa: E402
+from taiwan_tongues_asr_ce_amd.engine import Engine  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="large-v3")
+    ap.add_argument("--clips", type=int, default=256)
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--new-tokens", type=int, default=128)
+    ap.add_argument("--check-interval", type=int, default=8)
+    ap.add_argument("--seed", type=int, default=6)
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    ap.add_argument("--only-overlap", action="store_true", help="time (c) alone (for a kernel trace of the session)")
+    ap.add_argument("--no-graph", action="store_true",
+                    help="option graph = 0 (decode steps launched one by one): for rocprofv3, which crashes inside hipGraph capture")
+    args = ap.parse_args()
+    dims = PRESETS[args.model]
+    B, N = args.batch, args.clips
+    eng = Engine(dims, COMPUTE_BF16, B)
+    eng.load_weights(synth.iter_weights(dims))
+    if args.no_graph:
+        eng.set_option("graph", 0)
+    st = eng.special
+    prompt = [st.sot, st.lang_zh, st.transcribe, st.no_timestamps]
+    opts = eng.gen_opts(args.new_tokens, timestamps=False, suppress_eot=True, check_interval=args.check_interval)
+    clips = [synth.noise_clip(i) for i in range(N)]
+    caps = np.random.Generator(np.random.Philox(key=args.seed)).integers(32, args.new_tokens + 1, size=N).astype(np.int32)
+    audio_s = 30.0 * N
+
+    def static():
+        toks, enc_ms, dec_ms, steps = [], 0.0, 0.0, 0
+        for i in range(0, N, B):
+            chunk = clips[i:i + B]
+            eng.log_mel(chunk, want_output=False)
+            eng.encode(len(chunk))
+            toks += eng.generate([prompt] * len(chunk), opts, row_max_new=caps[i:i + B]).tokens
+            ph = eng.phase_ms()
+            enc_ms += ph["mel"] + ph["encoder"] + ph["cross_kv"]
+            dec_ms += ph["decode"]
+            steps += int(caps[i:i + B].max())
+        live = float(caps.sum()) / steps     # sampling steps (the prompt is prefilled in one pass)
+        return toks, {"encode_ms": round(enc_ms, 1), "decode_ms": round(dec_ms, 1), "decode_steps": steps,
+                      "mean_live_rows_per_step": round(live, 2)}
+
+    def session():
+        out = [None] * N
+        with eng.session(opts, len(prompt)) as s:
+            ids = s.submit(clips, [prompt] * N, caps)
+            where = {cid: i for i, cid in enumerate(ids)}
+            for r in s.drain():
+                out[where[r.id]] = r.tokens
+            stt = s.stats()
+        return out, {"encode_ms": round(stt["encode_ms"], 1), "decode_ms": round(stt["decode_ms"], 1), "decode_steps": int(stt["steps"]),
+                     "polls": int(stt["polls"]), "encoder_passes": int(stt["encodes"]),
+                     "mean_live_rows_per_step": round(stt["live_row_steps"] / max(1.0, stt["steps"]), 2)}
+
+    def timed(fn):
+        t0 = time.perf_counter()
+        toks, m = fn()
+        dt = time.perf_counter() - t0
+        m.update({"wall_s": round(dt, 3), "audio_s_per_s": round(audio_s / dt, 1)})
+        return toks, m
+
+    # warm-up: graph captures and first-touch allocations of every path (the session's staging buffer included)
+    keep = clips, caps, N
+    clips, caps, N = clips[:B + 4], caps[:B + 4], B + 4
+    static()
+    eng.set_option("refill_overlap", 0)
+    session()
+    eng.set_option("refill_overlap", 1)
+    session()
+    clips, caps, N = keep
+
+    if args.only_overlap:
+        _, c = timed(session)
+        print(json.dumps({"metric": "refill_audio_s_per_s", "model": args.model, "clips": N, "session_overlap": c}))
+        eng.close()
+        return
+    ta, a = timed(static)
+    eng.set_option("refill_overlap", 0)
+    tb, b = timed(session)
+    eng.set_option("refill_overlap", 1)
+    tc, c = timed(session)
+    line = {
+        "metric": "refill_audio_s_per_s", "model": args.model, "compute": "bf16", "clips": N, "batch": B,
+        "budgets": {"lo": 32, "hi": args.new_tokens, "seed": args.seed, "mean": round(float(caps.mean()), 1)},
+        "check_interval": args.check_interval, "prompt_tokens": len(prompt),
+        "static": a, "session_sync": b, "session_overlap": c,
+        "ratio_b_over_a": round(b["audio_s_per_s"] / a["audio_s_per_s"], 3),
+        "ratio_c_over_a": round(c["audio_s_per_s"] / a["audio_s_per_s"], 3),
+        "clips_equal_b_c": int(sum(x == y for x, y in zip(tb, tc))),
+        "clips_equal_a_c": int(sum(x == y for x, y in zip(ta, tc))),
+        "note": "b and c must agree on every clip (every session encoder pass runs the same GEMM family, so a clip's bits do "
+                "not depend on how clips were grouped into passes); (a) prefills the prompt in one pass where the session "
+                "forces it through decode steps, so a/c token equality holds only where those two prompt paths agree",
+    }
+    s = json.dumps(line)
+    print(s)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(s + "\n")
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()
