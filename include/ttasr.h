@@ -243,6 +243,26 @@ TTASR_API int ttasr_apply_rules(ttasr_ctx* ctx, const float* rows_host, const in
  *   clips returned so far (prompt_len - 1 + tokens each), [5] encoder ms (GPU events: mel + encoder + cross-KV),
  *   [6] decode ms (GPU events around the step runs), [7] clips submitted and not yet admitted. */
 TTASR_API int ttasr_session_begin(ttasr_ctx* ctx, const ttasr_gen_opts* opts, int32_t max_prompt, float temperature);
+/* Beam-search mode of the session.  beam in 1..7; the batch is G = max_batch / beam groups of `beam` rows (rows G*beam ..
+ * max_batch-1 stay free).  Submit, poll, stats, rows and end are the calls above, with these differences:
+ *   - A clip occupies one group of `beam` rows and one cross-KV slot: group g uses slot g, read with kv_div = beam exactly as
+ *     in ttasr_generate_beam.
+ *   - max_new[i] of ttasr_session_submit is clip i's token budget: its search ends when round(beam * patience) hypotheses
+ *     have finished, or when its best live hypothesis holds min(max_new[i], n_text_ctx - prompt_len) tokens.
+ *   - The winner has the highest sum_logprob / length (as ttasr_generate_beam); tokens come back with EOT stripped (the
+ *     greedy session keeps it), sum_lp is the winner's sum, no_speech is the group's first row at opts->sot_index, which must
+ *     lie inside every clip's prompt when opts->no_speech >= 0 (checked by submit).
+ *   - Candidate selection runs on the host, so a poll runs one step per host exchange; opts->check_interval is ignored.  A
+ *     finished group is handed to the next clip at the following step.
+ *   - ttasr_session_rows: every row of a group reports the group's clip and the group's position (the next one to compute).
+ *   - ttasr_session_stats: the values keep their meaning; out[4] counts the live row-steps of all `beam` rows of a group.
+ * A clip equals, bit for bit (tokens, sum_logprob, no_speech), the same clip in ttasr_generate_beam over a static pass of
+ * exactly G clips on the same context with option prefill = 0 (and, in 16-bit, option enc_gemm = 3).
+ * Refused, leaving the context usable and no session open: beam outside 1..7, max_batch < beam, patience <= 0, option xkv_fp8
+ * on, a session already open, and everything ttasr_session_begin refuses.  While a beam session is open, every call that the
+ * greedy session refuses is refused too. */
+TTASR_API int ttasr_session_begin_beam(ttasr_ctx* ctx, const ttasr_gen_opts* opts, int32_t max_prompt, int32_t beam,
+                                       float patience);
 TTASR_API int ttasr_session_submit(ttasr_ctx* ctx, int32_t n, const float* const* pcm_host, const int64_t* n_samples,
                                    const int32_t* prompt, const int32_t* prompt_len, const int32_t* max_new, int64_t* out_ids);
 TTASR_API int ttasr_session_poll(ttasr_ctx* ctx, int32_t max_steps, int32_t cap, int64_t* ids, int32_t* tokens, int32_t* lens,

@@ -349,10 +349,12 @@ void launch_self_attn_decode(const T* qkv /*[B][3d]*/, T* kv_pool, const int32_t
                              int64_t pool_layer_off, int identity_pages, int row0, const int32_t* step, T* out /*[B][d]*/, int B, int H,
                              hipStream_t s, SlabIn sq = SlabIn{} /*qkv from K-split partial tiles*/,
                              const int32_t* done = nullptr /*[B] (already offset by row0): finished rows leave the kernel*/);
-// the same kernel with a PER-ROW position row_pos[row0 + b] (continuous-batching session; identity pages)
+// the same kernel with a PER-ROW position row_pos[row0 + b] (continuous-batching session: identity pages for greedy decoding,
+// a loaded page table for beam search)
 template <typename T>
 void launch_self_attn_decode_rows(const T* qkv, T* kv_pool, const int32_t* page_table, int pages_per_seq, int64_t pool_layer_off,
-                                  int row0, const int32_t* row_pos, T* out, int B, int H, hipStream_t s, SlabIn sq, const int32_t* done);
+                                  int identity_pages, int row0, const int32_t* row_pos, T* out, int B, int H, hipStream_t s, SlabIn sq,
+                                  const int32_t* done);
 template <typename T>
 void launch_copy_pages(T* pool, const int32_t* pairs_dev, int n_pairs, int n_layers, int H, int64_t layer_elems, hipStream_t s);
 template <typename T>

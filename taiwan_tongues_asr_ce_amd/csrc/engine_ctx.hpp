@@ -135,7 +135,7 @@ struct ttasr_ctx {
   float beam_prof_ms[4]{0, 0, 0, 0};   // last beam search: host time enqueueing, waiting for the GPU, selecting candidates; positions
   int max_new_alloc = 0, max_prompt_alloc = 0;
 
-  // continuous-batching session (engine_refill.hip): open between ttasr_session_begin and ttasr_session_end
+  // continuous-batching session (engine_refill.hip): open between ttasr_session_begin[_beam] and ttasr_session_end
   ttasr_detail::Session* sess = nullptr;
   bool session_rows = false;      // the decode step runs the per-row-position kernel forms (row_pos instead of st.step)
   bool refill_overlap = false;    // option refill_overlap: encode the next clips on a second stream under the step graphs (opt-in:
@@ -299,7 +299,7 @@ int step_graph(ttasr_ctx* c, int B, int mode, int nsteps = 1);
 void drop_graphs(ttasr_ctx* c);
 void drop_rule_graphs(ttasr_ctx* c);
 
-// ---- engine_refill.hip: the continuous-batching session ----
+// ---- engine_refill.hip: the continuous-batching session (greedy and beam search) ----
 int session_refusal(ttasr_ctx* c);   // TTASR_E_INVALID with a message while a session is open, else 0
 void session_free(ttasr_ctx* c);     // ttasr_destroy: the session's stream, events and pinned memory
 
@@ -312,6 +312,11 @@ int reset_search(ttasr_ctx* c, int B);
 int generate_rows(ttasr_ctx* c, int R, int rows_per_clip, const int32_t* prompt, const int32_t* prompt_len, int max_prompt,
                   const ttasr_gen_opts* o, float temperature, uint32_t seed, int32_t* out_tokens, int32_t* out_len, float* out_lp,
                   float* out_ns, const int32_t* row_cap = nullptr /*host [R] per-row token budgets, each in [1, max_new_tokens]*/);
+bool beam_select(const std::vector<std::vector<int>>& seqs, const std::vector<double>& sums, int r0, int beam, int K,
+                 const float* lp, const int32_t* id, int eot, int max_cand, std::map<std::vector<int>, double>& finished,
+                 std::vector<std::vector<int>>& nseq, std::vector<double>& nsum, std::vector<int>& src);
+int beam_pick(const std::map<std::vector<int>, double>& finished, const std::vector<std::vector<int>>& seqs,
+              const std::vector<double>& sums, int r0, int beam, int eot, int max_new, int32_t* out, double* out_sum);
 int beam_search_impl(ttasr_ctx* c, int32_t A, int32_t beam, const int32_t* prompt, int32_t max_prompt, const int32_t* plens,
                      const int32_t* sots, const ttasr_gen_opts* o, float patience, int32_t* out_tokens, int32_t* out_len,
                      float* out_lp, float* out_ns);

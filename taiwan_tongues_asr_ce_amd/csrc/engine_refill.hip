@@ -10,7 +10,15 @@
 // second stream of the context while the step graphs replay on the main one: it shares no buffer with the decode step (the
 // encoder's activations, mel and PCM buffers are its own; the decode step uses the d* rows, the K-split slabs, the logits and
 // the KV pool), and the staging buffer is only rewritten after the copies of its previous batch (event ev_copy).
+//
+// Beam mode (ttasr_session_begin_beam, DESIGN.md "Beam search in a session"): the unit of admission is a GROUP of `beam` rows
+// (group g = rows g*beam .. g*beam + beam - 1, cross-KV slot g read with kv_div = beam), the batch is R = G*beam rows.  The
+// search runs on the host as in beam_search_impl: every step is the logits-only decode step (mode 1, per-row positions, loaded
+// page tables) plus the candidate kernel, with ONE host exchange: page tables, fed tokens, positions, finished flags, history and
+// copy-on-write pairs go out from one pinned block, the top-k candidates come back, and the shared selection code
+// (beam_select / beam_pick) advances every searching group.  Positions belong to the host; nothing on the device advances them.
 #include "engine_ctx.hpp"
+#include <cassert>
 #include <chrono>
 #include <deque>
 
@@ -38,6 +46,16 @@ struct Session {
   // statistics (ttasr_session_stats)
   int64_t steps = 0, polls = 0, encodes = 0, clips_encoded = 0, live_row_steps = 0;
   double enc_ms = 0, dec_ms = 0;
+  // beam mode (beam > 0): G groups of `beam` rows; per group the clip, its prompt, budget, position, no-speech value and finished
+  // hypotheses; per row the hypothesis and its double-precision sum; one page table [maxB][pages_per_seq] with reference counts
+  struct Group { int64_t clip = -1; std::vector<int32_t> prompt; int32_t cap = 0; int pos = 0; float ns = 0.f;
+                 std::map<std::vector<int>, double> finished; };
+  int beam = 0, G = 0, max_cand = 0;
+  std::vector<Group> grp;
+  std::vector<std::vector<int>> seqs;
+  std::vector<double> sums;
+  std::vector<int32_t> tbl, refcnt, free_pages, cur_tok, done_rows, pairs;
+  int32_t* bpin = nullptr;         // pinned exchange block of a beam step (see beam_step)
 };
 
 int session_refusal(ttasr_ctx* c) {
@@ -51,14 +69,25 @@ void session_free(ttasr_ctx* c) {
   if (S->es && S->es != c->stream) { hipStreamSynchronize(S->es); hipStreamDestroy(S->es); }
   for (hipEvent_t e : {S->ev_enc0, S->ev_enc, S->ev_copy, S->ev_dec0, S->ev_dec1}) if (e) hipEventDestroy(e);
   if (S->pin) hipHostFree(S->pin);
+  if (S->bpin) hipHostFree(S->bpin);
   delete S;
   c->sess = nullptr;
   c->session_rows = false;
+  c->kv_div = 1; c->identity_pages = 1;
 }
 
 static int n_free_rows(const Session* S) {
   int n = 0;
   for (int64_t id : S->row_clip) n += id < 0;
+  return n;
+}
+
+// units of admission: rows (greedy) or groups of `beam` rows (beam mode)
+static int n_units(const ttasr_ctx* c, const Session* S) { return S->beam ? S->G : c->maxB; }
+static int n_free_units(const Session* S) {
+  if (!S->beam) return n_free_rows(S);
+  int n = 0;
+  for (const Session::Group& g : S->grp) n += g.clip < 0;
   return n;
 }
 
@@ -106,9 +135,34 @@ static int admit(ttasr_ctx* c, Session* S) {
     float ms = 0.f;
     if (S->staged_next == 0 && hipEventElapsedTime(&ms, S->ev_enc0, S->ev_enc) == hipSuccess) S->enc_ms += ms;
   }
+  const size_t blk = (size_t)c->H * c->T * 64 * c->esz, pitch = (size_t)c->xkv_which_elems * c->esz;
+  if (S->beam) {
+    // a free group takes the clip: its cross-KV goes to slot g; the search state is host-side and goes out with the next step
+    for (int g = 0; g < S->G && (int)S->staged_next < (int)S->staged.size(); ++g) {
+      Session::Group& gr = S->grp[g];
+      if (gr.clip >= 0) continue;
+      const int j = (int)S->staged_next++;
+      Session::Clip& cl = S->staged[j];
+      HIPCHK(c, hipMemcpy2DAsync((char*)c->xkv + (size_t)g * blk, pitch, (const char*)c->xkv_stage + (size_t)j * blk, pitch, blk,
+                                 2 * (size_t)c->cfg.dec_layers, hipMemcpyDeviceToDevice, s));
+      const int plen = (int)cl.prompt.size();
+      gr.clip = cl.id; gr.prompt = std::move(cl.prompt); gr.pos = 0; gr.ns = 0.f; gr.finished.clear();
+      // the static search's last sampled position is n_text_ctx - 2: a clip never holds more than n_text_ctx - plen tokens
+      gr.cap = std::min(cl.cap, c->cfg.n_text_ctx - plen);
+      for (int b = 0; b < S->beam; ++b) {
+        const int r = g * S->beam + b;
+        S->seqs[r].clear(); S->sums[r] = 0.0;
+        S->row_clip[r] = cl.id; S->cur_tok[r] = gr.prompt[0]; S->done_rows[r] = 0;
+      }
+    }
+    if (S->staged_next == S->staged.size()) {
+      S->staged.clear(); S->staged_next = 0;
+      HIPCHK(c, hipEventRecord(S->ev_copy, s));
+    }
+    return 0;
+  }
   const int W = 3 + S->max_prompt;
   int32_t* tab = S->pin + (size_t)c->maxB * (4 + c->rp.max_new);
-  const size_t blk = (size_t)c->H * c->T * 64 * c->esz, pitch = (size_t)c->xkv_which_elems * c->esz;
   int n = 0;
   for (int r = 0; r < c->maxB && (int)S->staged_next < (int)S->staged.size(); ++r) {
     if (S->row_clip[r] >= 0) continue;
@@ -144,7 +198,7 @@ static int pump(ttasr_ctx* c, Session* S) {
   }
   TRY(admit(c, S));
   if (S->staged.empty() && !S->queue.empty()) {
-    const int free_now = n_free_rows(S);
+    const int free_now = n_free_units(S), units = n_units(c, S);
     if (!S->overlap) {
       if (free_now == 0) return 0;
       // synchronous mode: the encode sits on the decode stream between two steps, and the host waits for it (the staged clips'
@@ -156,8 +210,8 @@ static int pump(ttasr_ctx* c, Session* S) {
       TRY(admit(c, S));
     } else {
       // encode ahead: at least an eighth of the batch per encode (small-k encoder passes are inefficient), more when rows are free now
-      const int k = std::min<int>((int)S->queue.size(), std::max(free_now, std::max(1, c->maxB / 8)));
-      TRY(start_encode(c, S, std::min(k, c->maxB)));
+      const int k = std::min<int>((int)S->queue.size(), std::max(free_now, std::max(1, units / 8)));
+      TRY(start_encode(c, S, std::min(k, units)));
     }
   }
   return 0;
@@ -228,6 +282,157 @@ static int session_begin(ttasr_ctx* c, const ttasr_gen_opts* o, int max_prompt, 
   return TTASR_OK;
 }
 
+// ---- beam mode ----
+
+static int session_begin_beam(ttasr_ctx* c, const ttasr_gen_opts* o, int max_prompt, int beam, float patience) {
+  if (!c) return TTASR_E_INVALID;
+  if (!c->finalized) return fail(c, TTASR_E_INVALID, "weights not finalized (call ttasr_finalize_weights first)");
+  TRY(session_refusal(c));
+  if (beam < 1 || beam > 7) return fail(c, TTASR_E_INVALID, "beam %d outside [1, 7]", beam);
+  if (c->maxB < beam) return fail(c, TTASR_E_INVALID, "max_batch %d holds no group of %d rows", c->maxB, beam);
+  if (!(patience > 0.f)) return fail(c, TTASR_E_INVALID, "patience %g must be > 0", patience);
+  TRY(session_begin(c, o, max_prompt, 0.f));   // rules, buffers, streams; every row free (done = 1)
+  Session* S = c->sess;
+  const int G = c->maxB / beam, R = G * beam, pps = c->pages_per_seq, K = beam + 1;
+  S->beam = beam; S->G = G; S->max_cand = std::max(1, (int)std::lround(beam * patience));
+  S->grp.assign(G, Session::Group{});
+  S->seqs.assign(R, {}); S->sums.assign(R, 0.0);
+  S->tbl.assign((size_t)c->maxB * pps, -1); S->refcnt.assign((size_t)c->maxB * pps, 0);
+  S->free_pages.clear();
+  for (int p = c->maxB * pps - 1; p >= 0; --p) S->free_pages.push_back(p);
+  S->cur_tok.assign(R, 0); S->done_rows.assign(R, 1);
+  // [page tables R x pps | fed tokens R | positions R | done R | histories 4 R | page pairs 2 R] out, [lp R x K | ids R x K | no-speech R] back
+  const size_t words = (size_t)R * pps + 9 * (size_t)R + 2 * (size_t)R * K + R;
+  const hipError_t e = hipHostMalloc((void**)&S->bpin, words * 4);
+  if (e != hipSuccess) { S->bpin = nullptr; session_free(c); return fail(c, TTASR_E_HIP, "hipHostMalloc: %s", hipGetErrorString(e)); }
+  c->kv_div = beam; c->identity_pages = 0;   // group g reads cross-KV slot g; rows read their own (shared) page lists
+  return TTASR_OK;
+}
+
+// One decode position of every live group: copy-on-write, one staged upload, the logits-only step over R rows, the candidate
+// kernel, ONE synchronisation, then selection, re-indexing and the finished groups' results on the host.
+static int beam_step(ttasr_ctx* c, Session* S) {
+  const int beam = S->beam, G = S->G, R = G * beam, pps = c->pages_per_seq, K = beam + 1, n_pages = c->maxB * pps;
+  const ttasr_gen_opts& o = S->o;
+  hipStream_t s = c->stream;
+  std::vector<int32_t>& tbl = S->tbl;
+  // 1. the page each live row writes must exist and be private to the row.  The pool never runs dry: a row holds at most pps
+  // pages (positions < n_text_ctx), at most maxB rows hold pages, the pool has maxB * pps, and a page is back on the free list
+  // as soon as no row references it (rebuilt below; a finished group drops its rows' lists).
+  S->pairs.clear();
+  bool any_sampling = false, any_ns = false;
+  for (int g = 0; g < G; ++g) {
+    const Session::Group& gr = S->grp[g];
+    if (gr.clip < 0) continue;
+    const int j = gr.pos / 16;
+    for (int b = 0; b < beam; ++b) {
+      int32_t& pg = tbl[(size_t)(g * beam + b) * pps + j];
+      if (gr.pos % 16 == 0 || pg < 0) {
+        assert(!S->free_pages.empty());
+        pg = S->free_pages.back(); S->free_pages.pop_back(); S->refcnt[pg] = 1;
+      } else if (S->refcnt[pg] > 1) {
+        assert(!S->free_pages.empty());
+        const int32_t np = S->free_pages.back(); S->free_pages.pop_back();
+        S->pairs.push_back(pg); S->pairs.push_back(np);
+        S->refcnt[pg]--; S->refcnt[np] = 1; pg = np;
+      }
+    }
+    any_sampling |= gr.pos + 1 >= (int)gr.prompt.size();
+    any_ns |= o.no_speech >= 0 && gr.pos == o.sot_index;
+  }
+  // 2. the step's input, staged in the pinned block (unused table entries clamped to a valid page id)
+  int32_t* const pb = S->bpin;
+  int32_t *const p_up = pb, *const p_tok = p_up + (size_t)R * pps, *const p_pos = p_tok + R, *const p_done = p_pos + R,
+          *const h_state = p_done + R, *const p_pairs = h_state + 4 * R, *const h_id = p_pairs + 2 * R + R * K;
+  float *const h_lp = (float*)(p_pairs + 2 * R), *const h_ns = (float*)(h_id + R * K);
+  for (size_t i = 0; i < (size_t)R * pps; ++i) p_up[i] = tbl[i] < 0 ? 0 : tbl[i];
+  for (int r = 0; r < R; ++r) {
+    const Session::Group& gr = S->grp[r / beam];
+    p_tok[r] = S->cur_tok[r]; p_pos[r] = gr.clip < 0 ? 0 : gr.pos; p_done[r] = S->done_rows[r];
+  }
+  HIPCHK(c, hipMemcpyAsync(c->page_table, p_up, (size_t)R * pps * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->st.cur_tok, p_tok, (size_t)R * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->row_pos, p_pos, (size_t)R * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->st.done, p_done, (size_t)R * 4, hipMemcpyHostToDevice, s));
+  if (!S->pairs.empty()) {
+    memcpy(p_pairs, S->pairs.data(), S->pairs.size() * 4);
+    HIPCHK(c, hipMemcpyAsync(c->pairs_dev, p_pairs, S->pairs.size() * 4, hipMemcpyHostToDevice, s));
+    TT_DISPATCH(c, launch_copy_pages<T>((T*)c->pool, c->pairs_dev, (int)S->pairs.size() / 2, c->cfg.dec_layers, c->H, c->pool_layer_elems, s));
+  }
+  const bool topk = any_sampling || any_ns;
+  if (topk) {   // the row histories the candidate kernel applies the rules from
+    for (int r = 0; r < R; ++r) {
+      int last = -1, pen = -1, lts = -1;
+      for (int t : S->seqs[r]) { pen = last; last = t; if (t >= o.timestamp_begin) lts = t; }
+      h_state[r] = (int)S->seqs[r].size(); h_state[R + r] = last; h_state[2 * R + r] = pen; h_state[3 * R + r] = lts;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->row_state, h_state, (size_t)4 * R * 4, hipMemcpyHostToDevice, s));
+  }
+  // 3. the decoder step (logits only) and, behind it, the candidates of every row
+  HIPCHK(c, hipEventRecord(S->ev_dec0, s));
+  TRY(step_graph(c, R, 1));
+  if (topk) {
+    BeamRowState bs{c->row_state, c->row_state + R, c->row_state + 2 * R, c->row_state + 3 * R, c->mask_dev};
+    launch_beam_topk(c->logits, bs, c->rp, R, K, c->topk_lp, c->topk_id, any_ns ? c->st.no_speech : nullptr, s);
+    HIPCHK(c, hipMemcpyAsync(h_lp, c->topk_lp, (size_t)R * K * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(h_id, c->topk_id, (size_t)R * K * 4, hipMemcpyDeviceToHost, s));
+    if (any_ns) HIPCHK(c, hipMemcpyAsync(h_ns, c->st.no_speech, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(c, hipEventRecord(S->ev_dec1, s));
+  HIPCHK(c, hipStreamSynchronize(s));   // the one synchronisation of the step
+  HIPCHK(c, hipGetLastError());
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, S->ev_dec0, S->ev_dec1) == hipSuccess) S->dec_ms += ms;
+  // 4. selection per searching group (the code beam_search_impl runs), re-index, finished groups out
+  std::vector<std::vector<int>> nseq; std::vector<double> nsum; std::vector<int> src;
+  std::vector<char> searching(G, 0);
+  for (int g = 0; g < G; ++g) {
+    Session::Group& gr = S->grp[g];
+    searching[g] = gr.clip >= 0 && gr.pos + 1 >= (int)gr.prompt.size();
+    if (gr.clip >= 0 && any_ns && gr.pos == o.sot_index) gr.ns = h_ns[g * beam];
+    if (!searching[g]) {
+      for (int b = 0; b < beam; ++b) { const int r = g * beam + b; nseq.push_back(S->seqs[r]); nsum.push_back(S->sums[r]); src.push_back(r); }
+      continue;
+    }
+    if (!beam_select(S->seqs, S->sums, g * beam, beam, K, h_lp, h_id, o.eot, S->max_cand, gr.finished, nseq, nsum, src))
+      return fail(c, TTASR_E_INVALID, "beam search: no live candidate (every token masked)");
+  }
+  std::vector<int32_t> ntbl((size_t)c->maxB * pps, -1);
+  for (int r = 0; r < R; ++r) memcpy(&ntbl[(size_t)r * pps], &tbl[(size_t)src[r] * pps], (size_t)pps * 4);
+  tbl.swap(ntbl);
+  S->seqs.swap(nseq); S->sums.swap(nsum);
+  for (int g = 0; g < G; ++g) {
+    Session::Group& gr = S->grp[g];
+    if (gr.clip < 0) continue;
+    S->live_row_steps += beam;
+    gr.pos++;
+    const int r0 = g * beam;
+    if (searching[g] && ((int)gr.finished.size() >= S->max_cand || (int)S->seqs[r0].size() >= gr.cap)) {
+      Session::Done d;
+      d.id = gr.clip;
+      d.tok.resize(c->rp.max_new);
+      double best = 0;
+      d.tok.resize(beam_pick(gr.finished, S->seqs, S->sums, r0, beam, o.eot, c->rp.max_new, d.tok.data(), &best));
+      d.lp = (float)best; d.ns = gr.ns;
+      S->finished.push_back(std::move(d));
+      // the group is free: its page lists go back to the pool, its rows leave the attention kernels
+      gr.clip = -1; gr.finished.clear();
+      for (int b = 0; b < beam; ++b) {
+        const int r = r0 + b;
+        std::fill(tbl.begin() + (size_t)r * pps, tbl.begin() + (size_t)(r + 1) * pps, -1);
+        S->done_rows[r] = 1; S->row_clip[r] = -1; S->cur_tok[r] = 0;
+      }
+      continue;
+    }
+    for (int b = 0; b < beam; ++b) S->cur_tok[r0 + b] = searching[g] ? S->seqs[r0 + b].back() : gr.prompt[gr.pos];
+  }
+  std::fill(S->refcnt.begin(), S->refcnt.end(), 0);
+  for (int32_t p : tbl) if (p >= 0) S->refcnt[p]++;
+  S->free_pages.clear();
+  for (int p = n_pages - 1; p >= 0; --p) if (S->refcnt[p] == 0) S->free_pages.push_back(p);
+  return 0;
+}
+
 static int session_submit(ttasr_ctx* c, int n, const float* const* pcm, const int64_t* n_samples, const int32_t* prompt,
                           const int32_t* prompt_len, const int32_t* max_new, int64_t* out_ids) {
   if (!c) return TTASR_E_INVALID;
@@ -248,6 +453,8 @@ static int session_submit(ttasr_ctx* c, int n, const float* const* pcm, const in
       if (prompt[(size_t)i * P + j] < 0 || prompt[(size_t)i * P + j] >= c->V) return fail(c, TTASR_E_INVALID, "clip %d: prompt token outside vocabulary", i);
     if (max_new[i] < 1 || max_new[i] > S->o.max_new_tokens)
       return fail(c, TTASR_E_INVALID, "clip %d: max_new %d outside [1, max_new_tokens=%d]", i, max_new[i], S->o.max_new_tokens);
+    if (S->beam && S->o.no_speech >= 0 && (S->o.sot_index < 0 || S->o.sot_index >= prompt_len[i]))
+      return fail(c, TTASR_E_INVALID, "clip %d: sot_index %d outside the %d-token prompt", i, S->o.sot_index, prompt_len[i]);
   }
   for (int i = 0; i < n; ++i) {
     Session::Clip cl;
@@ -286,7 +493,7 @@ static int session_poll(ttasr_ctx* c, int max_steps, int cap, int64_t* ids, int3
   int steps = 0;
   while (S->finished.empty()) {
     TRY(pump(c, S));
-    int live = B - n_free_rows(S);
+    const int live = n_units(c, S) - n_free_units(S);
     if (live == 0) {
       if (S->enc_pending) {   // nothing to decode until the encode is done
         HIPCHK(c, hipEventSynchronize(S->ev_enc));
@@ -297,6 +504,11 @@ static int session_poll(ttasr_ctx* c, int max_steps, int cap, int64_t* ids, int3
       continue;
     }
     if (steps >= max_steps) break;
+    if (S->beam) {   // selection is on the host: one step per exchange
+      TRY(beam_step(c, S));
+      steps++; S->steps++; S->polls++;
+      continue;
+    }
     const int n = std::min(interval, max_steps - steps);
     TRY(run_steps(c, S, n));
     steps += n; S->steps += n; S->polls++;
@@ -363,6 +575,10 @@ int ttasr_session_begin(ttasr_ctx* c, const ttasr_gen_opts* o, int32_t max_promp
   return guarded(c, [&]() -> int { return session_begin(c, o, max_prompt, temperature); });
 }
 
+int ttasr_session_begin_beam(ttasr_ctx* c, const ttasr_gen_opts* o, int32_t max_prompt, int32_t beam, float patience) {
+  return guarded(c, [&]() -> int { return session_begin_beam(c, o, max_prompt, beam, patience); });
+}
+
 int ttasr_session_submit(ttasr_ctx* c, int32_t n, const float* const* pcm_host, const int64_t* n_samples, const int32_t* prompt,
                          const int32_t* prompt_len, const int32_t* max_new, int64_t* out_ids) {
   return guarded(c, [&]() -> int { return session_submit(c, n, pcm_host, n_samples, prompt, prompt_len, max_new, out_ids); });
@@ -393,6 +609,16 @@ int ttasr_session_rows(ttasr_ctx* c, int32_t* row_pos, int32_t* done, int64_t* r
     if (!S) return fail(c, TTASR_E_INVALID, "no session is open");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (S->beam) {   // positions and flags are the host's: every row of a group reports the group's position
+      for (int r = 0; r < c->maxB; ++r) {
+        const bool in = r < S->G * S->beam;
+        const Session::Group* g = in ? &S->grp[r / S->beam] : nullptr;
+        if (row_pos) row_pos[r] = g && g->clip >= 0 ? g->pos : 0;
+        if (done) done[r] = in ? S->done_rows[r] : 1;
+      }
+      if (row_clip) memcpy(row_clip, S->row_clip.data(), (size_t)c->maxB * 8);
+      return TTASR_OK;
+    }
     if (row_pos) HIPCHK(c, hipMemcpy(row_pos, c->row_pos, (size_t)c->maxB * 4, hipMemcpyDeviceToHost));
     if (done) HIPCHK(c, hipMemcpy(done, c->st.done, (size_t)c->maxB * 4, hipMemcpyDeviceToHost));
     if (row_clip) memcpy(row_clip, S->row_clip.data(), (size_t)c->maxB * 8);

@@ -274,7 +274,7 @@ void run_decode_rows(ttasr_ctx* c, int row0, int n, int mode, int total_rows) {
       if (!sqkv.n) { g.epi.bias = L.bqkv; g.epi.out_t = dqkv; dec_gemm<T>(c, g, L.wqkv_sh); } }
     if (!(c->skip_mask & 4) && rows_pos)
       launch_self_attn_decode_rows<T>((const T*)dqkv, (T*)c->pool, c->page_table, c->pages_per_seq, (int64_t)l * c->pool_layer_elems,
-                                      row0, c->row_pos, (T*)datt, n, c->H, s, sqkv, done);
+                                      c->identity_pages, row0, c->row_pos, (T*)datt, n, c->H, s, sqkv, done);
     else if (!(c->skip_mask & 4))
       launch_self_attn_decode<T>((const T*)dqkv, (T*)c->pool, c->page_table, c->pages_per_seq, (int64_t)l * c->pool_layer_elems,
                                  c->identity_pages, row0, c->st.step, (T*)datt, n, c->H, s, sqkv, done);

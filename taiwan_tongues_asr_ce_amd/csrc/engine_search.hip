@@ -214,6 +214,63 @@ int generate_rows(ttasr_ctx* c, int R, int rows_per_clip, const int32_t* prompt,
   return TTASR_OK;
 }
 
+// Candidate selection of one clip at a searching position (Whisper BeamSearchDecoder semantics), shared by beam_search_impl and
+// the beam session: rows r0 .. r0 + beam - 1 hold the clip's hypotheses, lp / id [row][K] the candidate kernel's top K of every
+// row.  Identical sequences collapse (the best score stays), ties break by sequence, finished hypotheses (EOT) go to `finished`
+// up to max_cand; the `beam` best live ones are appended to nseq / nsum with their parent rows in src.  false: no live candidate.
+bool beam_select(const std::vector<std::vector<int>>& seqs, const std::vector<double>& sums, int r0, int beam, int K,
+                 const float* lp, const int32_t* id, int eot, int max_cand, std::map<std::vector<int>, double>& finished,
+                 std::vector<std::vector<int>>& nseq, std::vector<double>& nsum, std::vector<int>& src) {
+  std::map<std::vector<int>, std::pair<double, int>> cand;
+  for (int b = 0; b < beam; ++b) {
+    const int r = r0 + b;
+    for (int q = 0; q < K; ++q) {
+      const int tok = id[(size_t)r * K + q];
+      if (tok < 0) continue;
+      std::vector<int> key(seqs[r]); key.push_back(tok);
+      const double val = sums[r] + (double)lp[(size_t)r * K + q];
+      auto it = cand.find(key);
+      if (it == cand.end() || val > it->second.first) cand[key] = {val, r};
+    }
+  }
+  std::vector<std::pair<double, const std::vector<int>*>> order;
+  for (auto& kv : cand) order.push_back({kv.second.first, &kv.first});
+  std::sort(order.begin(), order.end(), [](auto& x, auto& y) { return x.first != y.first ? x.first > y.first : *x.second < *y.second; });
+  int saved = 0;
+  std::vector<std::pair<double, const std::vector<int>*>> fin_new;
+  for (auto& e : order) {
+    if (e.second->back() == eot) { fin_new.push_back(e); continue; }
+    nseq.push_back(*e.second); nsum.push_back(e.first); src.push_back(cand[*e.second].second);
+    if (++saved == beam) break;
+  }
+  for (auto& e : fin_new) { if ((int)finished.size() >= max_cand) break; finished[*e.second] = e.first; }
+  if (saved == 0) return false;
+  while (saved < beam) { nseq.push_back(nseq.back()); nsum.push_back(-1e30); src.push_back(src.back()); ++saved; }
+  return true;
+}
+
+// The final pick of one clip: the finished hypotheses, topped up with the best live ones to `beam`, ranked by sum_logprob / length.
+// Writes the winner's tokens without EOT (at most max_new) to out and returns their count; *out_sum = the winner's sum.
+int beam_pick(const std::map<std::vector<int>, double>& finished, const std::vector<std::vector<int>>& seqs,
+              const std::vector<double>& sums, int r0, int beam, int eot, int max_new, int32_t* out, double* out_sum) {
+  std::map<std::vector<int>, double> pool(finished);
+  if ((int)pool.size() < beam) {
+    std::vector<int> idx(beam);
+    for (int b = 0; b < beam; ++b) idx[b] = b;
+    std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) { return sums[r0 + x] > sums[r0 + y]; });
+    for (int b : idx) { if ((int)pool.size() >= beam) break; pool.insert({seqs[r0 + b], sums[r0 + b]}); }
+  }
+  const std::vector<int>* best = nullptr; double best_v = -1e300, best_sum = 0;
+  for (auto& kv : pool) {
+    const double v = kv.second / std::max<size_t>(kv.first.size(), 1);
+    if (!best || v > best_v) { best = &kv.first; best_v = v; best_sum = kv.second; }
+  }
+  int n = 0;
+  for (int t : *best) if (t != eot && n < max_new) out[n++] = t;
+  *out_sum = best_sum;
+  return n;
+}
+
 // Beam search over A clips x `beam` rows.  Prompts may be ragged: clip a has plens[a] tokens at prompt + a * max_prompt and
 // its <|startoftranscript|> at sots[a]; the step loop is position-synchronous, so at a given position some clips are
 // still being forced through their prompt while others already search.
@@ -393,31 +450,8 @@ int beam_search_impl(ttasr_ctx* c, int32_t A, int32_t beam, const int32_t* promp
         for (int b = 0; b < beam; ++b) { nseq.push_back(seqs[a * beam + b]); nsum.push_back(sums[a * beam + b]); src.push_back(a * beam + b); }
         continue;
       }
-      std::map<std::vector<int>, std::pair<double, int>> cand;
-      for (int b = 0; b < beam; ++b) {
-        const int r = a * beam + b;
-        for (int q = 0; q < K; ++q) {
-          const int tok = h_id[(size_t)r * K + q];
-          if (tok < 0) continue;
-          std::vector<int> key(seqs[r]); key.push_back(tok);
-          const double val = sums[r] + (double)h_lp[(size_t)r * K + q];
-          auto it = cand.find(key);
-          if (it == cand.end() || val > it->second.first) cand[key] = {val, r};
-        }
-      }
-      std::vector<std::pair<double, const std::vector<int>*>> order;
-      for (auto& kv : cand) order.push_back({kv.second.first, &kv.first});
-      std::sort(order.begin(), order.end(), [](auto& x, auto& y) { return x.first != y.first ? x.first > y.first : *x.second < *y.second; });
-      int saved = 0;
-      std::vector<std::pair<double, const std::vector<int>*>> fin_new;
-      for (auto& e : order) {
-        if (e.second->back() == o->eot) { fin_new.push_back(e); continue; }
-        nseq.push_back(*e.second); nsum.push_back(e.first); src.push_back(cand[*e.second].second);
-        if (++saved == beam) break;
-      }
-      for (auto& e : fin_new) { if ((int)finished[a].size() >= max_cand) break; finished[a][*e.second] = e.first; }
-      if (saved == 0) return fail(c, TTASR_E_INVALID, "beam search: no live candidate (every token masked)");
-      while (saved < beam) { nseq.push_back(nseq.back()); nsum.push_back(-1e30); src.push_back(src.back()); ++saved; }
+      if (!beam_select(seqs, sums, a * beam, beam, K, h_lp, h_id, o->eot, max_cand, finished[a], nseq, nsum, src))
+        return fail(c, TTASR_E_INVALID, "beam search: no live candidate (every token masked)");
     }
     // 4. re-index: hypotheses inherit their parent's page list (shared pages; refcounts rebuilt)
     std::vector<int32_t> ntbl((size_t)R * pps, -1);
@@ -448,21 +482,8 @@ int beam_search_impl(ttasr_ctx* c, int32_t A, int32_t beam, const int32_t* promp
   HIPCHK(c, hipGetLastError());
   hipEventElapsedTime(&c->phase_ms[3], c->ev[5], c->ev[6]);
   for (int a = 0; a < A; ++a) {
-    std::map<std::vector<int>, double> pool(finished[a]);
-    if ((int)pool.size() < beam) {
-      std::vector<int> idx(beam);
-      for (int b = 0; b < beam; ++b) idx[b] = b;
-      std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) { return sums[a * beam + x] > sums[a * beam + y]; });
-      for (int b : idx) { if ((int)pool.size() >= beam) break; pool.insert({seqs[a * beam + b], sums[a * beam + b]}); }
-    }
-    const std::vector<int>* best = nullptr; double best_v = -1e300, best_sum = 0;
-    for (auto& kv : pool) {
-      const double v = kv.second / std::max<size_t>(kv.first.size(), 1);
-      if (!best || v > best_v) { best = &kv.first; best_v = v; best_sum = kv.second; }
-    }
-    int n = 0;
-    for (int t : *best) if (t != o->eot && n < max_new) out_tokens[(size_t)a * max_new + n++] = t;
-    out_len[a] = n;
+    double best_sum = 0;
+    out_len[a] = beam_pick(finished[a], seqs, sums, a * beam, beam, o->eot, max_new, out_tokens + (size_t)a * max_new, &best_sum);
     if (out_lp) out_lp[a] = (float)best_sum;
     if (out_ns) out_ns[a] = ns_final[a];
   }

@@ -323,17 +323,18 @@ void launch_self_attn_decode(const T* qkv, T* kv_pool, const int32_t* page_table
   else { if (identity_pages) TTASR_SA(false, true); else TTASR_SA(false, false); }
 #undef TTASR_SA
 }
-// the session form: row_pos [row0 + B] per-row positions, identity pages (greedy), finished / idle rows leave via `done`
+// the session form: row_pos [row0 + B] per-row positions, finished / idle rows leave via `done`; identity pages for the greedy
+// session, the loaded page table (copy-on-write sharing) for the beam session
 template <typename T>
 void launch_self_attn_decode_rows(const T* qkv, T* kv_pool, const int32_t* page_table, int pages_per_seq, int64_t pool_layer_off,
-                                  int row0, const int32_t* row_pos, T* out, int B, int H, hipStream_t s, SlabIn sq,
+                                  int identity_pages, int row0, const int32_t* row_pos, T* out, int B, int H, hipStream_t s, SlabIn sq,
                                   const int32_t* done) {
-  if (sq.n > 0)
-    hipLaunchKernelGGL((self_attn_decode_kernel<T, 3, true, true>), dim3(H, B), dim3(256), 0, s, qkv, kv_pool + pool_layer_off,
-                       page_table, pages_per_seq, 1, row0, row_pos, out, done, H, 1, sq);
-  else
-    hipLaunchKernelGGL((self_attn_decode_kernel<T, 3, false, true>), dim3(H, B), dim3(256), 0, s, qkv, kv_pool + pool_layer_off,
-                       page_table, pages_per_seq, 1, row0, row_pos, out, done, H, 1, sq);
+#define TTASR_SA(SLAB_, IDENT_)                                                                                              \
+  hipLaunchKernelGGL((self_attn_decode_kernel<T, 3, SLAB_, IDENT_>), dim3(H, B), dim3(256), 0, s, qkv, kv_pool + pool_layer_off, \
+                     page_table, pages_per_seq, identity_pages, row0, row_pos, out, done, H, 1, sq)
+  if (sq.n > 0) { if (identity_pages) TTASR_SA(true, true); else TTASR_SA(true, false); }
+  else { if (identity_pages) TTASR_SA(false, true); else TTASR_SA(false, false); }
+#undef TTASR_SA
 }
 // prompt prefill: rows = n_seq * npos, row-major [sequence][position]; positions 0..npos-1 of every sequence
 template <typename T>
@@ -377,8 +378,8 @@ template void launch_self_attn_decode<bf16_t>(const bf16_t*, bf16_t*, const int3
 template void launch_self_attn_decode<f16_t>(const f16_t*, f16_t*, const int32_t*, int, int64_t, int, int, const int32_t*,
                                               f16_t*, int, int, hipStream_t, SlabIn, const int32_t*);
 #define TTASR_SA_ROWS(T_)                                                                                                 \
-  template void launch_self_attn_decode_rows<T_>(const T_*, T_*, const int32_t*, int, int64_t, int, const int32_t*, T_*, int, int, \
-                                                 hipStream_t, SlabIn, const int32_t*)
+  template void launch_self_attn_decode_rows<T_>(const T_*, T_*, const int32_t*, int, int64_t, int, int, const int32_t*, T_*, int, \
+                                                 int, hipStream_t, SlabIn, const int32_t*)
 TTASR_SA_ROWS(float); TTASR_SA_ROWS(bf16_t); TTASR_SA_ROWS(f16_t);
 #undef TTASR_SA_ROWS
 

@@ -241,11 +241,15 @@ class Engine:
                                             lp.ctypes.data_as(f32p), ns.ctypes.data_as(f32p)), "generate")
         return GenResult([toks[b, :lens[b]].tolist() for b in range(B)], lp, ns)
 
-    def session(self, opts, max_prompt: int, temperature: float = 0.0) -> "Session":
+    def session(self, opts, max_prompt: int, temperature: float = 0.0, beam: int = 1,
+                patience: Optional[float] = None) -> "Session":
         """Continuous-batching session (ttasr_session_*): greedy, single-window decoding of clips submitted at any time; each clip
         takes a free row of the max_batch-row decode batch and hands it to the next queued clip when it finishes.  A context
-        manager: the session ends when the block is left.  While it is open the engine's other search / encode calls are refused."""
-        return Session(self, opts, max_prompt, temperature)
+        manager: the session ends when the block is left.  While it is open the engine's other search / encode calls are refused.
+
+        beam > 1, or beam given together with a patience (default 1.0): beam search (ttasr_session_begin_beam); a clip takes a
+        group of `beam` rows, and its result equals ttasr_generate_beam's (tokens without EOT)."""
+        return Session(self, opts, max_prompt, temperature, beam, patience)
 
     def generate_beam(self, prompts: Sequence[Sequence[int]], beam: int, opts, patience: float = 1.0,
                       sot_index: Optional[Sequence[int]] = None) -> GenResult:
@@ -371,14 +375,30 @@ class SessionResult:
 class Session:
     """Engine.session(): submit(clips, prompts, max_new) -> clip ids; poll() -> finished clips (SessionResult, any order)."""
 
-    def __init__(self, engine: Engine, opts, max_prompt: int, temperature: float = 0.0):
+    def __init__(self, engine: Engine, opts, max_prompt: int, temperature: float = 0.0, beam: int = 1,
+                 patience: Optional[float] = None):
         self.engine, self.opts, self.max_prompt = engine, opts, int(max_prompt)
         self.max_new_tokens = int(opts.max_new_tokens)
         self.window = 2 * engine.audio_ctx * 160
         self.open = False
         self.pending = 0
-        engine._check(engine.lib.ttasr_session_begin(engine.h, C.byref(opts), self.max_prompt, C.c_float(temperature)),
-                      "session_begin")
+        beam = int(beam)
+        if not 1 <= beam <= 7:
+            raise ValueError(f"beam {beam} outside [1, 7]")
+        self.beam = beam if (beam > 1 or patience is not None) else 0   # 0: the greedy session
+        if self.beam:
+            patience = 1.0 if patience is None else float(patience)
+            if not patience > 0:
+                raise ValueError(f"patience {patience} must be > 0")
+            if temperature != 0.0:
+                raise ValueError("a beam session decodes without sampling (temperature must be 0)")
+            if beam > engine.max_batch:
+                raise ValueError(f"max_batch {engine.max_batch} holds no group of {beam} rows")
+            engine._check(engine.lib.ttasr_session_begin_beam(engine.h, C.byref(opts), self.max_prompt, beam, C.c_float(patience)),
+                          "session_begin_beam")
+        else:
+            engine._check(engine.lib.ttasr_session_begin(engine.h, C.byref(opts), self.max_prompt, C.c_float(temperature)),
+                          "session_begin")
         self.open = True
 
     def __enter__(self) -> "Session":

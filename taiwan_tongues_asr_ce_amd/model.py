@@ -786,15 +786,22 @@ class WhisperModel:
 
     def transcribe_stream(self, clips: Sequence[np.ndarray], language: str = "zh", task: str = "transcribe",
                           without_timestamps: bool = True, max_new_tokens: int = 224,
-                          row_max_new: Optional[Sequence[int]] = None) -> List[List[int]]:
+                          row_max_new: Optional[Sequence[int]] = None, beam_size: int = 1, patience: float = 1.0,
+                          initial_prompt: Optional[str] = None) -> List[List[int]]:
         """transcribe_batch's contract (clips <= 30 s each, sampled token ids per clip, input order) for any number of clips,
         through a continuous-batching session: a clip that finishes hands its decode row to the next one instead of waiting for
-        the rest of its batch.  row_max_new (optional): one token budget per clip, each in [1, max_new_tokens]."""
+        the rest of its batch.  row_max_new (optional): one token budget per clip, each in [1, max_new_tokens].
+        beam_size > 1: beam search (a clip takes a group of beam_size rows; tokens without EOT, as transcribe_windows decodes
+        them); initial_prompt: previous text in front of <|startoftranscript|>, as transcribe_windows builds it."""
         if len(clips) == 0:
             return []
         eng = self.engine
+        beam = int(beam_size)
+        if not 1 <= beam <= 7:
+            raise ValueError(f"beam_size {beam} outside [1, 7]")
         lang_tok = self._lang_token(language)
-        prompt, sot_index = self._prompt(lang_tok, task, without_timestamps, [])
+        prev = self.tokenizer.encode(" " + initial_prompt.strip()) if initial_prompt else []
+        prompt, sot_index = self._prompt(lang_tok, task, without_timestamps, prev)
         n_new = min(max_new_tokens, self.dims.n_text_ctx - len(prompt))
         caps = None
         if row_max_new is not None:
@@ -807,7 +814,7 @@ class WhisperModel:
         eng.set_audio_ctx(0)
         opts = eng.gen_opts(n_new, timestamps=not without_timestamps, sot_index=sot_index)
         out: List[Optional[List[int]]] = [None] * len(clips)
-        with eng.session(opts, len(prompt)) as s:
+        with (eng.session(opts, len(prompt), beam=beam, patience=patience) if beam > 1 else eng.session(opts, len(prompt))) as s:
             ids = s.submit([np.ascontiguousarray(c, dtype=np.float32) for c in clips], [prompt] * len(clips), caps)
             where = {cid: i for i, cid in enumerate(ids)}
             for r in s.drain():
@@ -834,7 +841,7 @@ class WhisperModel:
 
         audio_ctx (opt-in, SURVEY 8f N2): encode only that many positions (20 ms each) instead of the 30-s window;
         "auto" = the longest clip of the pass + 0.5 s, rounded up to a multiple of 50.  None keeps Whisper's window."""
-        eng, st = self.engine, self.special
+        eng = self.engine
         beam = max(1, min(beam_size, 7))
         per_pass = max(1, self.max_batch // beam)
         lang_tok = self._lang_token(language)
@@ -851,10 +858,16 @@ class WhisperModel:
                                     sot_index=sot_index)
                 res = eng.generate_beam([prompt] * len(chunk), beam, opts) if beam > 1 else eng.generate([prompt] * len(chunk), opts)
                 for c, toks in zip(chunk, res.tokens):
-                    toks = [t for t in toks if t != st.eot]
-                    ts = [t for t in toks if t >= st.timestamp_begin]
-                    end = (ts[-1] - st.timestamp_begin) * 0.02 if ts else len(c) / SAMPLE_RATE
-                    out.append((self.tokenizer.decode([t for t in toks if t < st.eot]), float(end)))
+                    out.append(self.window_text(toks, len(c)))
         finally:
             eng.set_audio_ctx(0)   # never leave a reduced window behind: the file-level paths assume the model's 30-s window
         return out
+
+    def window_text(self, toks: Sequence[int], n_samples: int) -> Tuple[str, float]:
+        """(text, end_time_seconds) of one window's tokens, as transcribe_windows returns them: the text of the tokens below
+        EOT, the end at the last timestamp token or, without one, at the clip's length."""
+        st = self.special
+        toks = [t for t in toks if t != st.eot]
+        ts = [t for t in toks if t >= st.timestamp_begin]
+        end = (ts[-1] - st.timestamp_begin) * 0.02 if ts else n_samples / SAMPLE_RATE
+        return self.tokenizer.decode([t for t in toks if t < st.eot]), float(end)

@@ -10,6 +10,8 @@ from __future__ import annotations
 
 import asyncio
 import logging
+import queue
+import threading
 import warnings
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
@@ -38,9 +40,18 @@ class BatchedWhisperASR(MI355XWhisperASR):
 
     max_clips * beam_size must fit the model's row budget (max_batch, <= 32 on the bf16 fast path).
     `audio_ctx="auto"` additionally encodes only as many positions as the longest utterance of a batch needs
-    (a 3-s utterance: 200 of 1500 positions), which is a behavioural change and therefore opt-in."""
+    (a 3-s utterance: 200 of 1500 positions), which is a behavioural change and therefore opt-in.
 
-    def __init__(self, max_clips: int = 6, max_wait_ms: float = 5.0, audio_ctx=None, max_new_tokens: int = 224, **kwargs):
+    `continuous=True` (opt-in) replaces the lock-step passes with one continuous-batching session (WhisperModel engine,
+    ttasr_session_begin_beam): a request is submitted as it arrives, takes a free group of beam_size rows and resolves when
+    its own search ends, not when the longest clip of its pass does.  max_clips groups of beam_size rows; the full 30-s window
+    is encoded, so it cannot be combined with audio_ctx."""
+
+    def __init__(self, max_clips: int = 6, max_wait_ms: float = 5.0, audio_ctx=None, max_new_tokens: int = 224,
+                 continuous: bool = False, **kwargs):
+        if continuous and audio_ctx is not None:
+            raise ValueError("continuous=True encodes the full window: audio_ctx must be None")
+        self.continuous = bool(continuous)
         beam = int(kwargs.pop("beam_size", 5))
         self.audio_ctx = audio_ctx            # None = Whisper's 30-s window; "auto"/int = opt-in short window (N2)
         self.max_new_tokens = max_new_tokens
@@ -52,6 +63,8 @@ class BatchedWhisperASR(MI355XWhisperASR):
         self._queue: Optional[asyncio.Queue] = None
         self._worker_task: Optional[asyncio.Task] = None
         self.batches_run: List[int] = []  # sizes of the batches actually executed (observability / tests)
+        self._cq: Optional[queue.Queue] = None          # continuous mode: requests for the session thread (None = stop)
+        self._session_thread: Optional[threading.Thread] = None
 
     def _ensure_worker(self):
         if self._queue is None:
@@ -91,10 +104,56 @@ class BatchedWhisperASR(MI355XWhisperASR):
             outs = self.asr_pipeline.transcribe_windows(audios, language="zh", beam_size=kw["beam_size"],
                                                         initial_prompt=kw["initial_prompt"], audio_ctx=self.audio_ctx,
                                                         max_new_tokens=self.max_new_tokens)
-        res: List[Optional[Tuple[str, float]]] = []
-        for audio, (text, end_time) in zip(audios, outs):
-            res.append((text, min(end_time, len(audio) / 16000.0)) if text.strip() else None)
-        return res
+        return [_window_result(audio, text, end_time) for audio, (text, end_time) in zip(audios, outs)]
+
+    def _ensure_session(self):
+        if self._cq is None:
+            self._cq = queue.Queue()
+        if self._session_thread is None or not self._session_thread.is_alive():
+            self._session_thread = threading.Thread(target=self._session_loop, args=(self._cq,), name="ttasr-session", daemon=True)
+            self._session_thread.start()
+
+    def _session_loop(self, q: "queue.Queue"):
+        """Continuous mode: this thread owns one open session on the model's engine; requests are submitted as they arrive and
+        their futures resolve as polls return them.  The prompt and options are transcribe_windows' for the same arguments."""
+        model = self.asr_pipeline
+        eng, kw = model.engine, self.default_transcribe_kwargs
+        beam = max(1, min(int(kw["beam_size"]), 7))
+        prev = model.tokenizer.encode(" " + kw["initial_prompt"].strip()) if kw.get("initial_prompt") else []
+        prompt, sot_index = model._prompt(model._lang_token("zh"), "transcribe", False, prev)
+        pending: Dict[int, Tuple[np.ndarray, float, Any, Any]] = {}
+
+        def resolve(fut, loop, value):
+            loop.call_soon_threadsafe(lambda: fut.done() or fut.set_result(value))
+
+        try:
+            eng.set_audio_ctx(0)
+            opts = eng.gen_opts(min(self.max_new_tokens, model.dims.n_text_ctx - len(prompt)), timestamps=True, sot_index=sot_index)
+            with (eng.session(opts, len(prompt), beam=beam) if beam > 1 else eng.session(opts, len(prompt))) as s:
+                while True:
+                    items = [] if pending else [q.get()]        # idle: wait for a request
+                    while True:
+                        try:
+                            items.append(q.get_nowait())
+                        except queue.Empty:
+                            break
+                    if any(it is None for it in items):
+                        for it in items:
+                            if it is not None:
+                                resolve(it[2], it[3], None)
+                        break
+                    for audio, last_start, fut, loop in items:
+                        a = np.ascontiguousarray(audio[: model.n_window], dtype=np.float32)
+                        pending[s.submit([a], [prompt])[0]] = (audio, last_start, fut, loop)
+                    for r in s.poll(max_steps=1 if beam > 1 else 8):
+                        audio, last_start, fut, loop = pending.pop(r.id)
+                        n = min(len(audio), model.n_window)
+                        resolve(fut, loop, self._result_dict(_window_result(audio, *model.window_text(r.tokens, n)), last_start))
+        except Exception as e:  # the reference logs and returns None per request
+            logger.error("continuous transcribe failed: %s", e)
+        finally:
+            for _, _, fut, loop in pending.values():
+                resolve(fut, loop, None)
 
     def _result_dict(self, res, last_start) -> Optional[Dict[str, Any]]:
         if res is None:
@@ -108,6 +167,12 @@ class BatchedWhisperASR(MI355XWhisperASR):
     async def transcribe(self, client) -> Optional[Dict[str, Any]]:
         try:
             audio = pcm16_bytes_to_float(client.scratch_buffer)
+            if self.continuous:
+                self._ensure_session()
+                loop = asyncio.get_running_loop()
+                fut = loop.create_future()
+                self._cq.put((audio, getattr(client, "last_start_time", 0) or 0, fut, loop))
+                return await fut
             self._ensure_worker()
             fut = asyncio.get_running_loop().create_future()
             await self._queue.put((audio, getattr(client, "last_start_time", 0) or 0, fut))
@@ -117,6 +182,10 @@ class BatchedWhisperASR(MI355XWhisperASR):
             return None
 
     async def aclose(self):
+        if self._session_thread is not None:   # continuous mode: the thread ends the session and resolves what is left
+            self._cq.put(None)
+            await asyncio.get_running_loop().run_in_executor(None, self._session_thread.join)
+            self._session_thread = None
         if self._worker_task is not None:
             self._worker_task.cancel()
             try:
@@ -124,3 +193,8 @@ class BatchedWhisperASR(MI355XWhisperASR):
             except (asyncio.CancelledError, Exception):
                 pass
             self._worker_task = None
+
+
+def _window_result(audio: np.ndarray, text: str, end_time: float) -> Optional[Tuple[str, float]]:
+    """(text, end_time) of one request, its end capped at the audio's length; None when nothing was said."""
+    return (text, min(end_time, len(audio) / 16000.0)) if text.strip() else None

@@ -9,6 +9,12 @@ Prints one JSON line: audio-s/s, encoder / decode GPU ms, mean live rows per dec
 tokens agree across the three runs.
 
     python tools/refill_bench.py [--clips 256] [--model large-v3] [--check-interval 8] [--out profiles/refill_bench.json]
+
+--beam K: the beam-search form.  max_batch 30 (the streaming default, 6 groups of 5), 120 synthetic clips of 10 ... 30 s; the EOT
+row of the token embedding is scaled (--eot-boost) so that hypotheses finish at spread positions (the length histogram is printed).
+  (a) static: lock-step ttasr_generate_beam passes of G = max_batch / K clips (prefill = 0 and enc_gemm = 3, the session's forms);
+  (b) the beam session (ttasr_session_begin_beam), refill_overlap = 0;  (c) the same with refill_overlap = 1.
+    python tools/refill_bench.py --beam 5 [--clips 120] [--eot-boost 8] [--out profiles/refill_beam_bench.json]
 """
 from __future__ import annotations
 
@@ -40,7 +46,11 @@ def main():
     ap.add_argument("--only-overlap", action="store_true", help="time (c) alone (for a kernel trace of the session)")
     ap.add_argument("--no-graph", action="store_true",
                     help="option graph = 0 (decode steps launched one by one): for rocprofv3, which crashes inside hipGraph capture")
+    ap.add_argument("--beam", type=int, default=0, help="beam width: compare static beam passes with the beam session")
+    ap.add_argument("--eot-boost", type=float, default=8.0, help="--beam: scale of the EOT embedding row (synthetic weights)")
     args = ap.parse_args()
+    if args.beam:
+        return main_beam(args)
     dims = PRESETS[args.model]
     B, N = args.batch, args.clips
     eng = Engine(dims, COMPUTE_BF16, B)
@@ -120,6 +130,108 @@ def main():
         "note": "b and c must agree on every clip (every session encoder pass runs the same GEMM family, so a clip's bits do "
                 "not depend on how clips were grouped into passes); (a) prefills the prompt in one pass where the session "
                 "forces it through decode steps, so a/c token equality holds only where those two prompt paths agree",
+    }
+    s = json.dumps(line)
+    print(s)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(s + "\n")
+    eng.close()
+
+
+def main_beam(args):
+    dims = PRESETS[args.model]
+    K = args.beam
+    B = 30 if args.batch == 32 else args.batch      # --batch keeps its greedy default of 32; the beam form's default is 30
+    G = B // K
+    N = args.clips if args.clips != 256 else 120
+    N = max(G, N - N % G)                            # whole static passes
+    new_tokens = args.new_tokens if args.new_tokens != 128 else 96
+    eng = Engine(dims, COMPUTE_BF16, B)
+    st = eng.special
+
+    def weights():
+        for name, w in synth.iter_weights(dims):
+            if name == "model.decoder.embed_tokens.weight":
+                w = w.copy()
+                w[st.eot] *= args.eot_boost
+            yield name, w
+    eng.load_weights(weights())
+    prompt = [st.sot, st.lang_zh, st.transcribe, st.no_timestamps]
+    opts = eng.gen_opts(new_tokens, timestamps=False)
+    clips_all = [synth.noise_clip(i)[: 16000 * (10 + (7 * i) % 21)] for i in range(N)]
+    audio_s_all = sum(len(c) for c in clips_all) / 16000.0
+    clips = clips_all
+
+    def static():
+        toks, enc_ms, dec_ms, steps = [], 0.0, 0.0, 0
+        eng.set_option("prefill", 0)
+        eng.set_option("enc_gemm", 3)
+        for i in range(0, len(clips), G):
+            chunk = clips[i:i + G]
+            eng.log_mel(chunk, want_output=False)
+            eng.encode(len(chunk))
+            toks += eng.generate_beam([prompt] * len(chunk), K, opts).tokens
+            ph = eng.phase_ms()
+            enc_ms += ph["mel"] + ph["encoder"] + ph["cross_kv"]
+            dec_ms += ph["decode"]
+            steps += int(eng.beam_profile()["positions"])
+        eng.set_option("prefill", 1)
+        eng.set_option("enc_gemm", 0)
+        return toks, {"encode_ms": round(enc_ms, 1), "decode_ms": round(dec_ms, 1), "decode_steps": steps}
+
+    def session():
+        out = [None] * len(clips)
+        with eng.session(opts, len(prompt), beam=K) as s:
+            ids = s.submit(clips, [prompt] * len(clips))
+            where = {cid: i for i, cid in enumerate(ids)}
+            for r in s.drain():
+                out[where[r.id]] = r.tokens
+            stt = s.stats()
+        return out, {"encode_ms": round(stt["encode_ms"], 1), "decode_ms": round(stt["decode_ms"], 1), "decode_steps": int(stt["steps"]),
+                     "encoder_passes": int(stt["encodes"]), "live_row_steps": int(stt["live_row_steps"]),
+                     "mean_live_rows_per_step": round(stt["live_row_steps"] / max(1.0, stt["steps"]), 2)}
+
+    def timed(fn):
+        t0 = time.perf_counter()
+        toks, m = fn()
+        dt = time.perf_counter() - t0
+        audio_s = sum(len(c) for c in clips) / 16000.0
+        m.update({"wall_s": round(dt, 3), "audio_s_per_s": round(audio_s / dt, 1),
+                  "ms_per_step": round(m["decode_ms"] / max(1, m["decode_steps"]), 3)})
+        return toks, m
+
+    # warm-up: graph captures and first-touch allocations of every path
+    clips = clips_all[:2 * G]
+    static()
+    for ov in (0, 1):
+        eng.set_option("refill_overlap", ov)
+        session()
+    clips = clips_all
+    ta, a = timed(static)
+    eng.set_option("refill_overlap", 0)
+    tb, b = timed(session)
+    eng.set_option("refill_overlap", 1)
+    tc, c = timed(session)
+    eng.set_option("refill_overlap", 0)
+    # every clip takes the same number of steps in both forms (same decisions), so the static pass's live row-steps are the session's
+    a["mean_live_rows_per_step"] = round(b["live_row_steps"] / max(1, a["decode_steps"]), 2)
+    lens = [len(t) for t in tb]
+    hist = {}
+    for n in lens:
+        k = f"{(n // 8) * 8}-{(n // 8) * 8 + 7}"
+        hist[k] = hist.get(k, 0) + 1
+    print("token-length histogram:", dict(sorted(hist.items(), key=lambda kv: int(kv[0].split("-")[0]))), file=sys.stderr)
+    line = {
+        "metric": "refill_beam_audio_s_per_s", "model": args.model, "compute": "bf16", "beam": K, "max_batch": B, "groups": G,
+        "clips": N, "audio_s": round(audio_s_all, 1), "eot_boost": args.eot_boost, "max_new_tokens": new_tokens,
+        "prompt_tokens": len(prompt), "length_histogram": hist, "mean_tokens": round(float(np.mean(lens)), 1),
+        "static": a, "session_sync": b, "session_overlap": c,
+        "ratio_b_over_a": round(b["audio_s_per_s"] / a["audio_s_per_s"], 3),
+        "ratio_c_over_a": round(c["audio_s_per_s"] / a["audio_s_per_s"], 3),
+        "clips_equal_a_b": int(sum(x == y for x, y in zip(ta, tb))),
+        "clips_equal_a_c": int(sum(x == y for x, y in zip(ta, tc))),
+        "all_clips_agree": all(x == y == z for x, y, z in zip(ta, tb, tc)),
     }
     s = json.dumps(line)
     print(s)

@@ -8,6 +8,7 @@ weights never emit EOT, so `--new-tokens` caps the decode length (16 ≈ a 3-s M
 
     python tools/stream_bench.py --model large-v3 --streams 8 --rounds 6 --beam 5
     python tools/stream_bench.py --model large-v3 --streams 8 --rounds 6 --beam 5 --audio-ctx auto   # N2 short window
+    python tools/stream_bench.py --model large-v3 --streams 8 --rounds 6 --beam 5 --continuous       # beam session backend
 """
 import argparse
 import asyncio
@@ -28,7 +29,9 @@ async def run(args):
     from taiwan_tongues_asr_ce_amd.streaming import BatchedWhisperASR
     beam = args.beam
     max_clips = max(1, 32 // beam) if args.max_clips == 0 else args.max_clips
-    asr = BatchedWhisperASR(max_clips=max_clips, max_wait_ms=args.max_wait_ms, beam_size=beam,
+    if args.continuous and args.audio_ctx != "none":
+        raise SystemExit("--continuous encodes the full window: --audio-ctx must be none")
+    asr = BatchedWhisperASR(max_clips=max_clips, max_wait_ms=args.max_wait_ms, beam_size=beam, continuous=args.continuous,
                             audio_ctx=None if args.audio_ctx == "none" else (args.audio_ctx if args.audio_ctx == "auto" else int(args.audio_ctx)),
                             max_new_tokens=args.new_tokens, model_size=f"synthetic:{args.model}", compute_type="bfloat16")
     utter = [np.clip(synth.noise_clip(1000 + i, int(args.utterance_s * 16000)) * 32768.0, -32768, 32767).astype("<i2").tobytes()
@@ -52,15 +55,15 @@ async def run(args):
     wall = time.perf_counter() - t0
     await asr.aclose()
     lat_ms = np.asarray(lat) * 1e3
-    sizes = asr.batches_run
+    sizes = asr.batches_run                              # empty for the continuous backend (no lock-step passes)
     out = {
         "workload": f"C5 streaming: {args.streams} concurrent streams x {args.rounds} utterances of {args.utterance_s} s, "
                     f"whisper-{args.model} geometry bf16, beam {beam}, <= {args.new_tokens} tokens, audio_ctx={args.audio_ctx}, "
-                    f"period {args.period} s, 1 GPU",
+                    f"period {args.period} s, 1 GPU" + (", continuous beam session" if args.continuous else ""),
         "latency_ms": {"p50": round(float(np.percentile(lat_ms, 50)), 1), "p99": round(float(np.percentile(lat_ms, 99)), 1),
                        "max": round(float(lat_ms.max()), 1)},
         "audio_s_per_s": round(len(lat) * args.utterance_s / (wall * args.rounds / (args.rounds + 1)), 1),
-        "engine_passes": len(sizes), "mean_clips_per_pass": round(float(np.mean(sizes)), 2),
+        "engine_passes": len(sizes), "mean_clips_per_pass": round(float(np.mean(sizes)), 2) if sizes else None,
         "last_pass_phase_ms": {k: round(v, 2) for k, v in asr.asr_pipeline.engine.phase_ms().items()},
     }
     print(json.dumps(out), flush=True)
@@ -78,6 +81,7 @@ def main():
     ap.add_argument("--audio-ctx", default="none", help="none | auto | <positions>")
     ap.add_argument("--max-clips", type=int, default=0)
     ap.add_argument("--max-wait-ms", type=float, default=5.0)
+    ap.add_argument("--continuous", action="store_true", help="BatchedWhisperASR(continuous=True): one beam session, no passes")
     asyncio.run(run(ap.parse_args()))
 
 
