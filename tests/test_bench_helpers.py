@@ -55,3 +55,28 @@ def test_dump_outputs_writes_float64_and_a_fixed_sample_under_the_limit(tmp_path
     assert x.shape == (10, 16) and x.nbytes <= lim and np.array_equal(x, y)
     rows = x[:, 0].astype(np.int64) // 16
     assert (np.diff(rows) > 0).all() and np.array_equal(x, toks[rows])
+
+
+def test_seeded_weights_equal_the_serial_generator():
+    """bench.py generates the synthetic weights on a few threads: same names, same order, same bits as synth.iter_weights."""
+    import sys
+    sys.path.insert(0, ROOT)
+    from taiwan_tongues_asr_ce_amd import synth
+    from taiwan_tongues_asr_ce_amd.config import PRESETS
+    b = _bench()
+    dims = PRESETS["tiny"]
+    got = list(b.seeded_weights(dims, workers=4, ahead=3))
+    want = list(synth.iter_weights(dims))
+    assert [n for n, _ in got] == [n for n, _ in want]
+    for (n, x), (_, y) in zip(got, want):
+        assert x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x, y), n
+
+
+def test_full_only_options_are_refused_without_full():
+    """A plain run measures the headline value only: options that belong to the --full measurements fail at once (before any GPU
+    work) instead of being ignored."""
+    import subprocess
+    import sys
+    for extra in (["--write-crc"], ["--dump-tokens", "t.npy"], ["--cpu-full"], ["--more-in-flight"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "add --full" in r.stderr, (extra, r.returncode, r.stderr[-500:])

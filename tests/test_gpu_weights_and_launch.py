@@ -66,10 +66,11 @@ def test_device_intake_rejects_bad_arguments():
 
 
 def test_bench_launches_its_own_ranks():
-    """The driver's invocation form: `python bench.py --gpus 2` with no torchrun environment."""
+    """The driver's invocation form: `python bench.py --gpus 2` with no torchrun environment (--full: the ranks' logits are
+    compared)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--model", "tiny", "--batch", "2",
-                        "--steps", "2", "--warmup", "1", "--new-tokens", "8", "--no-cpu-baseline"],
+                        "--steps", "2", "--warmup", "1", "--new-tokens", "8", "--full", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -99,12 +100,12 @@ def test_rccl_transport_runs_on_one_rank():
 
 
 def test_bench_single_gpu_through_the_forced_rccl_group():
-    """`bench.py --gpus 1` with TTASR_DIST_FORCE=1: weights arrive through the RCCL broadcast, tokens leave through the RCCL
+    """`bench.py --gpus 1 --full` with TTASR_DIST_FORCE=1: weights arrive through the RCCL broadcast, tokens leave through the RCCL
     all-gather, the validation probe gathers first-step logits - and the spread across the (one) rank is exactly 0."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "TTASR_DIST_BACKEND")}
     env["TTASR_DIST_FORCE"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--model", "tiny", "--batch", "2",
-                        "--steps", "2", "--warmup", "1", "--new-tokens", "8", "--no-cpu-baseline"],
+                        "--steps", "2", "--warmup", "1", "--new-tokens", "8", "--full", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Aggregate three separate rocprofv3 --pmc passes (FETCH_SIZE; WRITE_SIZE; SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES
-GRBM_GUI_ACTIVE SQ_WAVE_CYCLES) of `python3 bench.py --steps 1 --warmup 0 --new-tokens 8 --no-cpu-baseline` into
+GRBM_GUI_ACTIVE SQ_WAVE_CYCLES) of `python3 bench.py --steps 1 --warmup 0 --new-tokens 8 --full --no-cpu-baseline` into
 profiles/<tag>_pmc.json and profiles/xattn_pmc.json (what bench.py reports as roofline.traffic).
 
     python tools/microbench/pmc_report.py <dir_fetch> <dir_write> <dir_mfma> <tag> <out_dir>
@@ -80,7 +80,7 @@ def main():
     for lab in kernels:
         kernels[lab]["signatures"] = sorted(SIGNATURES.get(lab, ()))
     src = ("rocprofv3 --pmc <counters> (three separate passes: FETCH_SIZE; WRITE_SIZE; SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES "
-           "GRBM_GUI_ACTIVE SQ_WAVE_CYCLES) -- python3 bench.py --steps 1 --warmup 0 --new-tokens 8 --no-cpu-baseline; per-kernel means "
+           "GRBM_GUI_ACTIVE SQ_WAVE_CYCLES) -- python3 bench.py --steps 1 --warmup 0 --new-tokens 8 --full --no-cpu-baseline; per-kernel means "
            "over all launches (tools/microbench/pmc_report.py); gfx950 corrections applied (FETCH_SIZE x2)")
     with open(os.path.join(out_dir, f"{tag}_pmc.json"), "w") as f:
         json.dump({"source": src, "kernels": dict(sorted(kernels.items()))}, f, indent=1)
