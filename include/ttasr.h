@@ -267,6 +267,31 @@ TTASR_API int ttasr_session_submit(ttasr_ctx* ctx, int32_t n, const float* const
                                    const int32_t* prompt, const int32_t* prompt_len, const int32_t* max_new, int64_t* out_ids);
 TTASR_API int ttasr_session_poll(ttasr_ctx* ctx, int32_t max_steps, int32_t cap, int64_t* ids, int32_t* tokens, int32_t* lens,
                                  float* sum_lp, float* no_speech, int32_t* n_out);
+/* Window clips and independent rows in a beam session (ttasr_session_begin_beam; refused in a greedy session).  Window i is
+ * the 30-s window of the recording file_pcm[i][0 .. file_samples[i]) that starts at 10-ms frame seek_frames[i], with its own
+ * prompt (prompt [n][max_prompt], prompt_len[i] valid), <|startoftranscript|> position sot_index[i], budget max_new[i] in
+ * [1, opts->max_new_tokens], temperature[i] >= 0 (temperature NULL: all 0), rows[i] in [1, beam] and seed[i].
+ *   - Its log-mel is bit-identical to ttasr_log_mel_windows for the same (file, seek, floor_max[i]) (floor_max NULL: each
+ *     window's own maximum decides its dynamic-range floor): true neighbour samples across the window seam, reflection only at
+ *     the file ends, frames past the recording 0 in feature space.  Only the samples the window's frames read are copied.
+ *     Plain clips (ttasr_session_submit) and window clips may share an encoder pass; plain clips keep their own mel.
+ *   - temperature 0 and rows > 1: beam search of width rows[i], as for a plain clip (tokens without EOT).
+ *   - temperature 0 and one row: greedy; temperature > 0: rows[i] independent Gumbel-max samples, row b keyed
+ *     pcg_hash(seed ^ pcg_hash(b * 0x9E3779B9 + position)); a row ends at EOT or its budget, the clip when all its rows have
+ *     ended, and the row with the highest sum_logprob / length wins.  Tokens come back as ttasr_generate_sample returns them
+ *     (EOT kept when sampled), sum_lp is the winner's f32 sum, no_speech the group's first row at sot_index[i].  Such a clip
+ *     equals, bit for bit, the same clip in slot 0 of a static ttasr_generate_sample pass of G clips with best_of = rows = beam
+ *     and the same seed (prefill = 0; in 16-bit enc_gemm = 3), and with temperature 0 and beam = 1 the same clip of a static
+ *     ttasr_generate_capped pass.
+ * Everything is validated before anything is queued: rows outside [1, beam], a negative or non-finite temperature, a seek at
+ * or beyond the end of the file, a NULL pcm with samples, a non-finite floor_max, a sot_index outside the prompt when
+ * opts->no_speech >= 0, and what ttasr_session_submit refuses.  Results come back through ttasr_session_poll; out_ids as
+ * there. */
+TTASR_API int ttasr_session_submit_windows(ttasr_ctx* ctx, int32_t n, const float* const* file_pcm, const int64_t* file_samples,
+                                           const int64_t* seek_frames, const float* floor_max, const int32_t* prompt,
+                                           const int32_t* prompt_len, const int32_t* sot_index, const int32_t* max_new,
+                                           const float* temperature, const int32_t* rows, const uint32_t* seed, int64_t* out_ids);
+
 TTASR_API int ttasr_session_stats(ttasr_ctx* ctx, double out[8]);
 TTASR_API int ttasr_session_rows(ttasr_ctx* ctx, int32_t* row_pos, int32_t* done, int64_t* row_clip);
 TTASR_API int ttasr_session_end(ttasr_ctx* ctx);

@@ -16,7 +16,7 @@ SYMBOLS = [
     "ttasr_finalize_weights", "ttasr_log_mel", "ttasr_log_mel_windows", "ttasr_set_mel", "ttasr_encode", "ttasr_set_encoder_output",
     "ttasr_get_cross_kv", "ttasr_set_audio_ctx", "ttasr_generate", "ttasr_generate_capped", "ttasr_generate_beam", "ttasr_generate_beam_ragged", "ttasr_generate_sample", "ttasr_decode_reset", "ttasr_decode_step", "ttasr_apply_rules", "ttasr_align", "ttasr_dtw",
     "ttasr_set_option", "ttasr_phase_ms", "ttasr_beam_profile", "ttasr_encoder_kernel_ms", "ttasr_bench_kernel", "ttasr_bench_kernel_signature", "ttasr_sync",
-    "ttasr_session_begin", "ttasr_session_begin_beam", "ttasr_session_submit", "ttasr_session_poll", "ttasr_session_stats", "ttasr_session_rows", "ttasr_session_end",
+    "ttasr_session_begin", "ttasr_session_begin_beam", "ttasr_session_submit", "ttasr_session_submit_windows", "ttasr_session_poll", "ttasr_session_stats", "ttasr_session_rows", "ttasr_session_end",
 ]
 
 
@@ -94,6 +94,8 @@ def load() -> C.CDLL:
     lib.ttasr_session_begin.argtypes = [vp, C.POINTER(GenOpts), i32, C.c_float]
     lib.ttasr_session_begin_beam.argtypes = [vp, C.POINTER(GenOpts), i32, i32, C.c_float]
     lib.ttasr_session_submit.argtypes = [vp, i32, C.POINTER(vp), i64p, i32p, i32p, i32p, i64p]
+    lib.ttasr_session_submit_windows.argtypes = [vp, i32, C.POINTER(vp), i64p, i64p, f32p, i32p, i32p, i32p, i32p, f32p, i32p,
+                                                 C.POINTER(C.c_uint32), i64p]
     lib.ttasr_session_poll.argtypes = [vp, i32, i32, i64p, i32p, i32p, f32p, f32p, i32p]
     lib.ttasr_session_stats.argtypes = [vp, C.POINTER(C.c_double)]
     lib.ttasr_session_rows.argtypes = [vp, i32p, i32p, i64p]

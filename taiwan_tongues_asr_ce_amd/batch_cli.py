@@ -117,7 +117,11 @@ def summarise(results: List[Dict]) -> Dict:
 def process_audio_folder(folder_path: str, model=None, model_path: str = "models", device: str = "cuda",
                          device_index: int = 0, compute_type: str = "float16", max_batch: int = 120, output_json: Optional[str] = None, rank: int = 0,
                          world: int = 1, load_audio: Callable = _load_audio, log: Callable = print,
-                         group_files: int = 0, pipeline_depth: int = 0) -> Optional[Dict]:
+                         group_files: int = 0, pipeline_depth: int = 0, continuous: bool = False) -> Optional[Dict]:
+    if continuous:
+        if int(pipeline_depth or getattr(model, "pipeline_depth", 1)) > 1:
+            log("continuous mode runs one session on one engine context: pipeline depth 1")
+        pipeline_depth = 1
     files = list_audio_files(folder_path)
     if not files:
         log(f"no audio files in {folder_path}")
@@ -136,6 +140,10 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
         # MI355X-first: `group` files advance in lock step through one engine pass per window round; every file keeps the
         # sequential algorithm (own seek / prompt / fallback), so the outputs equal the one-by-one run
         kw = {k: v for k, v in TRANSCRIBE_KWARGS.items() if k != "vad_filter"}   # no VAD source configured: all-speech
+        if continuous:
+            # one continuous-batching session per group on one engine context: windows of the group's files refill decode rows
+            # as others finish, fallback attempts included (WhisperModel.transcribe_many(continuous=True))
+            kw["continuous"] = True
         depth0 = max(1, int(pipeline_depth or getattr(model, "pipeline_depth", 1)))
         if group_files <= 0 and depth0 > 1 and len(mine) < group * depth0:
             group = max(1, -(-len(mine) // depth0))            # few files: one group per context rather than one big group and an idle lane
@@ -144,6 +152,8 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
         # copy of the weights; one group's log-mel / encoder under another's decode) - same groups, same results, in file order.
         # Audio is loaded a few groups ahead only (a folder may hold many hours).
         depth = max(1, int(pipeline_depth or getattr(model, "pipeline_depth", 1)))
+        if continuous:
+            depth = 1
         groups_fn = getattr(model, "transcribe_groups", None) if depth > 1 else None
         span = 2 * depth if groups_fn is not None else 1
         for g0 in range(0, len(parts), span):
@@ -207,6 +217,9 @@ def main(argv=None) -> int:
     ap.add_argument("--pipeline-depth", type=int, default=2,
                     help="groups of files in flight per GPU (engine contexts sharing one copy of the weights; 1 = the reference's "
                          "serial loop, asr_core.py:151); results do not depend on it")
+    ap.add_argument("--continuous", action="store_true",
+                    help="opt-in: decode each group's windows in one continuous-batching session (finished rows are refilled, "
+                         "fallback attempts run in the session); pipeline depth 1.  Same per-file algorithm")
     args = ap.parse_args(argv)
     if not os.path.exists(args.folder):
         print(f"folder does not exist: {args.folder}")
@@ -217,7 +230,7 @@ def main(argv=None) -> int:
         rank, world, local = init_process_group()
     process_audio_folder(args.folder, model_path=args.model, device="cuda", device_index=local,
                          compute_type=args.compute_type, rank=rank, world=world, group_files=args.group_files,
-                         max_batch=args.max_batch, pipeline_depth=args.pipeline_depth)
+                         max_batch=args.max_batch, pipeline_depth=args.pipeline_depth, continuous=args.continuous)
     return 0
 
 

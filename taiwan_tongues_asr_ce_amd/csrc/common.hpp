@@ -400,6 +400,10 @@ extern thread_local int g_xattn_deep_items;   // option xattn_deep_items (kernel
 struct BeamRowState { const int32_t *n_sampled, *last_tok, *pen_tok, *last_ts; const uint8_t* mask; };
 void launch_beam_topk(const float* logits, BeamRowState st, RuleParams rp, int R, int k, float* out_lp /*[R][k]*/,
                       int32_t* out_id /*[R][k]*/, float* out_no_speech /*[R] or null*/, hipStream_t s);
+// per-entry inputs and outputs of session_rows_select_kernel (kernels_decode.hip): ent [n][4] = {row, position, key row, flags},
+// temp [n], seed [n] in; out [n][3] = {choice (int bits; -1 when the entry does not choose), lp increment, no-speech}
+struct SessRowsArgs { const int32_t* ent; const float* temp; const uint32_t* seed; float* out; };
+void launch_session_rows_select(const float* logits, BeamRowState hs, RuleParams rp, SessRowsArgs a, int n, hipStream_t s);
 // ticket != nullptr: the workgroup that finishes last (of `total_rows` over all select launches of the step) advances
 // *st.step, which replaces the separate advance launch
 void launch_select(const float* logits, DecState st, RuleParams rp, int B, float* out_rows /*nullable*/, hipStream_t s,

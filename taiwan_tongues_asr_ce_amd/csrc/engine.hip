@@ -460,9 +460,7 @@ int ttasr_generate_sample(ttasr_ctx* c, int32_t A, int32_t best_of, const int32_
   std::vector<float> lp(R), ns(R);
   TRY(generate_rows(c, R, best_of, prompt, plens.data(), plen, o, temperature, seed, toks.data(), lens.data(), lp.data(), ns.data()));
   for (int a = 0; a < A; ++a) {
-    int best = a * best_of;
-    for (int r = a * best_of; r < (a + 1) * best_of; ++r)
-      if (lp[r] / std::max(lens[r], 1) > lp[best] / std::max(lens[best], 1)) best = r;
+    const int best = a * best_of + sample_pick(&lp[(size_t)a * best_of], &lens[(size_t)a * best_of], best_of);
     memcpy(out_tokens + (size_t)a * max_new, &toks[(size_t)best * max_new], (size_t)max_new * 4);
     out_len[a] = lens[best];
     if (out_lp) out_lp[a] = lp[best];

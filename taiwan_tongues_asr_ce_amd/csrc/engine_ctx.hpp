@@ -143,6 +143,7 @@ struct ttasr_ctx {
   int32_t* row_pos = nullptr;     // [maxB] per-row positions of the session (allocated by the first session)
   void* xkv_stage = nullptr;      // [dec_layers][2][maxB][H][T][64] T: the session's encoder writes the admitted clips' cross-KV here
   int32_t* admit_dev = nullptr;   // [maxB][3 + max_prompt_alloc] row-admission table (launch_admit_rows)
+  int32_t* sess_sel = nullptr;    // [maxB][9] beam session: entries, temperatures, seeds and results of the independent-row kernel
 
   int B_mel = 0, B_enc = 0, B_dec = 0;
   std::atomic_flag busy = ATOMIC_FLAG_INIT;  // one call in flight per context: a second concurrent call is refused
@@ -314,7 +315,9 @@ int generate_rows(ttasr_ctx* c, int R, int rows_per_clip, const int32_t* prompt,
                   float* out_ns, const int32_t* row_cap = nullptr /*host [R] per-row token budgets, each in [1, max_new_tokens]*/);
 bool beam_select(const std::vector<std::vector<int>>& seqs, const std::vector<double>& sums, int r0, int beam, int K,
                  const float* lp, const int32_t* id, int eot, int max_cand, std::map<std::vector<int>, double>& finished,
-                 std::vector<std::vector<int>>& nseq, std::vector<double>& nsum, std::vector<int>& src);
+                 std::vector<std::vector<int>>& nseq, std::vector<double>& nsum, std::vector<int>& src,
+                 int stride = 0 /*row stride of lp / id: 0 = K*/);
+int sample_pick(const float* lp, const int32_t* len, int n);
 int beam_pick(const std::map<std::vector<int>, double>& finished, const std::vector<std::vector<int>>& seqs,
               const std::vector<double>& sums, int r0, int beam, int eot, int max_new, int32_t* out, double* out_sum);
 int beam_search_impl(ttasr_ctx* c, int32_t A, int32_t beam, const int32_t* prompt, int32_t max_prompt, const int32_t* plens,

@@ -1,5 +1,5 @@
-// libttasr: the continuous-batching session for greedy, single-window decoding (one of the engine translation units, see
-// engine_ctx.hpp; the life cycle is described in DESIGN.md "Continuous batching").
+// libttasr: the continuous-batching session: greedy single-window clips, and beam groups that also take windows of long files and
+// sampled attempts (one of the engine translation units, see engine_ctx.hpp; DESIGN.md "Continuous batching" and §4.13-4.15).
 //
 // The decode batch is always max_batch rows, so every step runs the same full-width kernel forms whatever the occupancy and a
 // clip's bits do not depend on its neighbours.  Each row carries its own position (ttasr_ctx::row_pos, read by the MODE 3
@@ -17,15 +17,27 @@
 // page tables) plus the candidate kernel, with ONE host exchange: page tables, fed tokens, positions, finished flags, history and
 // copy-on-write pairs go out from one pinned block, the top-k candidates come back, and the shared selection code
 // (beam_select / beam_pick) advances every searching group.  Positions belong to the host; nothing on the device advances them.
+//
+// A group has a MODE, fixed when a clip is admitted: BEAM (temperature 0, rows > 1, and every clip of ttasr_session_submit) is
+// the search above; ROWS (ttasr_session_submit_windows with temperature 0 and one row: greedy; temperature > 0: `rows`
+// Gumbel-max samples) decodes independent rows, chosen on the device by session_rows_select_kernel in the same step as the
+// candidate kernel, with the same one synchronisation.  A ROWS row ends at EOT or at its budget and its group when all its
+// rows have ended; the pick is ttasr_generate_sample's (sample_pick).  Window clips (ttasr_session_submit_windows) carry the
+// samples their window's STFT reads and the geometry of ttasr_log_mel_windows; a pass that holds one runs the mel in window form.
 #include "engine_ctx.hpp"
 #include <cassert>
 #include <chrono>
+#include <cmath>
 #include <deque>
 
 namespace ttasr_detail {
 
 struct Session {
-  struct Clip { int64_t id; std::vector<float> pcm; std::vector<int32_t> prompt; int32_t cap; };
+  struct Clip { int64_t id; std::vector<float> pcm; std::vector<int32_t> prompt; int32_t cap;
+                // window clips: pcm = the samples the window's frames read, geom = ttasr_log_mel_windows' geometry, floor = the
+                // ordered dynamic-range maximum (has_floor) ; search: mode (0 BEAM, 1 ROWS), rows, temperature, seed, sot index
+                bool win = false, has_floor = false; int64_t geom[3] = {0, 0, 0}; unsigned floor = 0;
+                int mode = 0, rows = 0; float temp = 0.f; uint32_t seed = 0; int32_t sot = 0; };
   struct Done { int64_t id; std::vector<int32_t> tok; float lp, ns; };
   ttasr_gen_opts o{};
   int max_prompt = 0;
@@ -34,6 +46,8 @@ struct Session {
   std::vector<Clip> staged;        // encoded into staging slots 0..k-1 (slot = index); admitted in order
   size_t staged_next = 0;          // first staged clip not admitted yet
   std::vector<int64_t> stage_ns;   // n_samples of the staged batch (source of an asynchronous copy: kept alive with it)
+  std::vector<int64_t> stage_geom; // [k][3] mel geometry of a pass that holds a window clip (idem)
+  std::vector<unsigned> stage_floor;   // [k] ordered dynamic-range maxima of its window clips (idem)
   bool enc_pending = false;        // overlapped encode enqueued and not yet seen complete
   std::vector<int64_t> row_clip;   // [maxB] clip id in the row, or -1 (free)
   std::vector<int32_t> row_plen;   // [maxB] prompt length of the row's clip
@@ -49,8 +63,12 @@ struct Session {
   // beam mode (beam > 0): G groups of `beam` rows; per group the clip, its prompt, budget, position, no-speech value and finished
   // hypotheses; per row the hypothesis and its double-precision sum; one page table [maxB][pages_per_seq] with reference counts
   struct Group { int64_t clip = -1; std::vector<int32_t> prompt; int32_t cap = 0; int pos = 0; float ns = 0.f;
-                 std::map<std::vector<int>, double> finished; };
+                 std::map<std::vector<int>, double> finished;
+                 int mode = 0, rows = 0, sot = 0, max_cand = 1; float temp = 0.f; uint32_t seed = 0; };
+  enum { BEAM = 0, ROWS = 1 };
   int beam = 0, G = 0, max_cand = 0;
+  float patience = 1.f;
+  std::vector<float> fsums;        // [R] f32 sum_logprob of the rows of ROWS groups (the device's order of additions)
   std::vector<Group> grp;
   std::vector<std::vector<int>> seqs;
   std::vector<double> sums;
@@ -98,17 +116,43 @@ static int start_encode(ttasr_ctx* c, Session* S, int k) {
   S->stage_ns.assign(k, 0);
   if (es != c->stream) HIPCHK(c, hipStreamWaitEvent(es, S->ev_copy, 0));   // the previous batch's cross-KV has left the staging buffer
   HIPCHK(c, hipEventRecord(S->ev_enc0, es));
+  bool any_win = false;
   for (int j = 0; j < k; ++j) {
     S->staged.push_back(std::move(S->queue.front()));
     S->queue.pop_front();
-    const Session::Clip& cl = S->staged.back();
+    any_win |= S->staged.back().win;
+  }
+  // a pass that holds a window clip runs the mel in window form (ttasr_log_mel_windows: PCM stride n_samples + 512, per-clip
+  // geometry); its plain clips get the geometry that reproduces the single-clip form exactly (lead 0, reflection at the window
+  // end, every frame valid).  A pass of plain clips only runs the single-clip form, as before.
+  const int64_t stride = any_win ? c->n_samples + 512 : c->n_samples;
+  S->stage_geom.assign(any_win ? 3 * (size_t)k : 0, 0);
+  S->stage_floor.assign(k, 0);
+  for (int j = 0; j < k; ++j) {
+    const Session::Clip& cl = S->staged[j];
     S->stage_ns[j] = (int64_t)cl.pcm.size();
+    if (any_win) {
+      const int64_t plain[3] = {0, (int64_t)c->F * 160, c->F};
+      memcpy(&S->stage_geom[3 * (size_t)j], cl.win ? cl.geom : plain, 24);
+      if (!cl.win) S->stage_ns[j] = std::min<int64_t>(S->stage_ns[j], (int64_t)c->F * 160);
+    }
     if (!cl.pcm.empty())
-      HIPCHK(c, hipMemcpyAsync(c->pcm_dev + (int64_t)j * c->n_samples, cl.pcm.data(), cl.pcm.size() * 4, hipMemcpyHostToDevice, es));
+      HIPCHK(c, hipMemcpyAsync(c->pcm_dev + (int64_t)j * stride, cl.pcm.data(), cl.pcm.size() * 4, hipMemcpyHostToDevice, es));
   }
   HIPCHK(c, hipMemcpyAsync(c->nsamp_dev, S->stage_ns.data(), (size_t)k * 8, hipMemcpyHostToDevice, es));
-  launch_mel(c->pcm_dev, c->n_samples, c->nsamp_dev, k, c->M, c->F, c->filters, c->dcos, c->dsin, c->window, c->mel, c->clip_max, es);
-  TT_DISPATCH(c, launch_mel_finish<T>(c->mel, c->clip_max, (T*)c->mel_t, k, c->M, c->F, es));
+  const int64_t* geom = nullptr;
+  if (any_win) {
+    HIPCHK(c, hipMemcpyAsync(c->mel_geom, S->stage_geom.data(), (size_t)k * 24, hipMemcpyHostToDevice, es));
+    geom = c->mel_geom;
+  }
+  launch_mel(c->pcm_dev, stride, c->nsamp_dev, k, c->M, c->F, c->filters, c->dcos, c->dsin, c->window, c->mel, c->clip_max, es, geom);
+  for (int j = 0; j < k; ++j) {   // the file's maximum decides a window's dynamic-range floor (ttasr_log_mel_windows floor_max)
+    const Session::Clip& cl = S->staged[j];
+    if (!cl.has_floor) continue;
+    S->stage_floor[j] = cl.floor;
+    HIPCHK(c, hipMemcpyAsync(c->clip_max + j, &S->stage_floor[j], 4, hipMemcpyHostToDevice, es));
+  }
+  TT_DISPATCH(c, launch_mel_finish<T>(c->mel, c->clip_max, (T*)c->mel_t, k, c->M, c->F, es, geom));
   // Every session pass runs the 256 x 256 GEMM family (gemm_bf16_v3; bit-identical to the persistent v4 / v5 forms that a 32-clip
   // encode picks).  The automatic choice goes by tile count, i.e. by k, and for a few clips it takes the 256 x 128 gemm_bf16_v2,
   // which rounds differently: a clip's bits would then depend on how many clips shared its pass - in overlap mode a matter of
@@ -149,10 +193,12 @@ static int admit(ttasr_ctx* c, Session* S) {
       gr.clip = cl.id; gr.prompt = std::move(cl.prompt); gr.pos = 0; gr.ns = 0.f; gr.finished.clear();
       // the static search's last sampled position is n_text_ctx - 2: a clip never holds more than n_text_ctx - plen tokens
       gr.cap = std::min(cl.cap, c->cfg.n_text_ctx - plen);
-      for (int b = 0; b < S->beam; ++b) {
+      gr.mode = cl.mode; gr.rows = cl.rows; gr.temp = cl.temp; gr.seed = cl.seed; gr.sot = cl.sot;
+      gr.max_cand = std::max(1, (int)std::lround(cl.rows * S->patience));
+      for (int b = 0; b < S->beam; ++b) {   // rows beyond the clip's `rows` stay finished
         const int r = g * S->beam + b;
-        S->seqs[r].clear(); S->sums[r] = 0.0;
-        S->row_clip[r] = cl.id; S->cur_tok[r] = gr.prompt[0]; S->done_rows[r] = 0;
+        S->seqs[r].clear(); S->sums[r] = 0.0; S->fsums[r] = 0.f;
+        S->row_clip[r] = cl.id; S->cur_tok[r] = gr.prompt[0]; S->done_rows[r] = b < cl.rows ? 0 : 1;
       }
     }
     if (S->staged_next == S->staged.size()) {
@@ -294,23 +340,26 @@ static int session_begin_beam(ttasr_ctx* c, const ttasr_gen_opts* o, int max_pro
   TRY(session_begin(c, o, max_prompt, 0.f));   // rules, buffers, streams; every row free (done = 1)
   Session* S = c->sess;
   const int G = c->maxB / beam, R = G * beam, pps = c->pages_per_seq, K = beam + 1;
-  S->beam = beam; S->G = G; S->max_cand = std::max(1, (int)std::lround(beam * patience));
+  S->beam = beam; S->G = G; S->max_cand = std::max(1, (int)std::lround(beam * patience)); S->patience = patience;
   S->grp.assign(G, Session::Group{});
-  S->seqs.assign(R, {}); S->sums.assign(R, 0.0);
+  S->seqs.assign(R, {}); S->sums.assign(R, 0.0); S->fsums.assign(R, 0.f);
   S->tbl.assign((size_t)c->maxB * pps, -1); S->refcnt.assign((size_t)c->maxB * pps, 0);
   S->free_pages.clear();
   for (int p = c->maxB * pps - 1; p >= 0; --p) S->free_pages.push_back(p);
   S->cur_tok.assign(R, 0); S->done_rows.assign(R, 1);
-  // [page tables R x pps | fed tokens R | positions R | done R | histories 4 R | page pairs 2 R] out, [lp R x K | ids R x K | no-speech R] back
-  const size_t words = (size_t)R * pps + 9 * (size_t)R + 2 * (size_t)R * K + R;
+  // [page tables R x pps | fed tokens R | positions R | done R | histories 4 R | page pairs 2 R] out, [lp R x K | ids R x K | no-speech R] back,
+  // then the independent-row kernel's [entries 4 R | temperatures R | seeds R] out and [results 3 R] back
+  const size_t words = (size_t)R * pps + 9 * (size_t)R + 2 * (size_t)R * K + R + 9 * (size_t)R;
   const hipError_t e = hipHostMalloc((void**)&S->bpin, words * 4);
   if (e != hipSuccess) { S->bpin = nullptr; session_free(c); return fail(c, TTASR_E_HIP, "hipHostMalloc: %s", hipGetErrorString(e)); }
+  if (!c->sess_sel && dalloc(c, &c->sess_sel, (size_t)c->maxB * 9 * 4) != 0) { session_free(c); return TTASR_E_HIP; }
   c->kv_div = beam; c->identity_pages = 0;   // group g reads cross-KV slot g; rows read their own (shared) page lists
   return TTASR_OK;
 }
 
 // One decode position of every live group: copy-on-write, one staged upload, the logits-only step over R rows, the candidate
-// kernel, ONE synchronisation, then selection, re-indexing and the finished groups' results on the host.
+// kernel (BEAM groups) and the independent-row kernel (ROWS groups), ONE synchronisation, then selection, re-indexing and the
+// finished groups' results on the host.
 static int beam_step(ttasr_ctx* c, Session* S) {
   const int beam = S->beam, G = S->G, R = G * beam, pps = c->pages_per_seq, K = beam + 1, n_pages = c->maxB * pps;
   const ttasr_gen_opts& o = S->o;
@@ -337,14 +386,36 @@ static int beam_step(ttasr_ctx* c, Session* S) {
         S->refcnt[pg]--; S->refcnt[np] = 1; pg = np;
       }
     }
+    if (gr.mode != Session::BEAM) continue;
     any_sampling |= gr.pos + 1 >= (int)gr.prompt.size();
-    any_ns |= o.no_speech >= 0 && gr.pos == o.sot_index;
+    any_ns |= o.no_speech >= 0 && gr.pos == gr.sot;
   }
   // 2. the step's input, staged in the pinned block (unused table entries clamped to a valid page id)
   int32_t* const pb = S->bpin;
   int32_t *const p_up = pb, *const p_tok = p_up + (size_t)R * pps, *const p_pos = p_tok + R, *const p_done = p_pos + R,
           *const h_state = p_done + R, *const p_pairs = h_state + 4 * R, *const h_id = p_pairs + 2 * R + R * K;
   float *const h_lp = (float*)(p_pairs + 2 * R), *const h_ns = (float*)(h_id + R * K);
+  int32_t* const p_ent = (int32_t*)(h_ns + R);
+  float* const p_temp = (float*)(p_ent + 4 * R);
+  uint32_t* const p_seed = (uint32_t*)(p_temp + R);
+  float* const h_sel = (float*)(p_seed + R);
+  // the rows of ROWS groups that need the independent-row kernel: past their prompt and not finished (choose), or the first row
+  // at the group's <|startoftranscript|> position (no-speech)
+  int n_ent = 0;
+  for (int g = 0; g < G; ++g) {
+    const Session::Group& gr = S->grp[g];
+    if (gr.clip < 0 || gr.mode != Session::ROWS) continue;
+    const bool past = gr.pos + 1 >= (int)gr.prompt.size(), ns_here = o.no_speech >= 0 && gr.pos == gr.sot;
+    for (int b = 0; b < gr.rows; ++b) {
+      const int r = g * beam + b;
+      const int flags = (past && !S->done_rows[r] ? 1 : 0) | (ns_here && b == 0 ? 2 : 0);
+      if (!flags) continue;
+      int32_t* e = p_ent + 4 * n_ent;
+      e[0] = r; e[1] = gr.pos; e[2] = b; e[3] = flags;
+      p_temp[n_ent] = gr.temp; p_seed[n_ent] = gr.seed;
+      ++n_ent;
+    }
+  }
   for (size_t i = 0; i < (size_t)R * pps; ++i) p_up[i] = tbl[i] < 0 ? 0 : tbl[i];
   for (int r = 0; r < R; ++r) {
     const Session::Group& gr = S->grp[r / beam];
@@ -360,7 +431,7 @@ static int beam_step(ttasr_ctx* c, Session* S) {
     TT_DISPATCH(c, launch_copy_pages<T>((T*)c->pool, c->pairs_dev, (int)S->pairs.size() / 2, c->cfg.dec_layers, c->H, c->pool_layer_elems, s));
   }
   const bool topk = any_sampling || any_ns;
-  if (topk) {   // the row histories the candidate kernel applies the rules from
+  if (topk || n_ent > 0) {   // the row histories the candidate and independent-row kernels apply the rules from
     for (int r = 0; r < R; ++r) {
       int last = -1, pen = -1, lts = -1;
       for (int t : S->seqs[r]) { pen = last; last = t; if (t >= o.timestamp_begin) lts = t; }
@@ -368,52 +439,102 @@ static int beam_step(ttasr_ctx* c, Session* S) {
     }
     HIPCHK(c, hipMemcpyAsync(c->row_state, h_state, (size_t)4 * R * 4, hipMemcpyHostToDevice, s));
   }
-  // 3. the decoder step (logits only) and, behind it, the candidates of every row
+  // device layout of the independent-row block (c->sess_sel): entries [4 R] | temperatures [R] | seeds [R] | results [3 R]
+  int32_t* const d_ent = c->sess_sel;
+  float* const d_temp = (float*)(d_ent + 4 * R);
+  uint32_t* const d_seed = (uint32_t*)(d_temp + R);
+  float* const d_out = (float*)(d_seed + R);
+  if (n_ent > 0) {   // entries, temperatures and seeds are contiguous in both blocks: one copy
+    memmove(p_ent + 4 * n_ent, p_temp, (size_t)n_ent * 4);
+    memmove(p_ent + 5 * n_ent, p_seed, (size_t)n_ent * 4);
+    HIPCHK(c, hipMemcpyAsync(d_ent, p_ent, (size_t)6 * n_ent * 4, hipMemcpyHostToDevice, s));
+  }
+  // 3. the decoder step (logits only) and, behind it, the candidates of every row and the choices of the independent rows
   HIPCHK(c, hipEventRecord(S->ev_dec0, s));
   TRY(step_graph(c, R, 1));
+  const BeamRowState bs{c->row_state, c->row_state + R, c->row_state + 2 * R, c->row_state + 3 * R, c->mask_dev};
   if (topk) {
-    BeamRowState bs{c->row_state, c->row_state + R, c->row_state + 2 * R, c->row_state + 3 * R, c->mask_dev};
     launch_beam_topk(c->logits, bs, c->rp, R, K, c->topk_lp, c->topk_id, any_ns ? c->st.no_speech : nullptr, s);
     HIPCHK(c, hipMemcpyAsync(h_lp, c->topk_lp, (size_t)R * K * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(h_id, c->topk_id, (size_t)R * K * 4, hipMemcpyDeviceToHost, s));
     if (any_ns) HIPCHK(c, hipMemcpyAsync(h_ns, c->st.no_speech, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+  }
+  if (n_ent > 0) {
+    const SessRowsArgs sa{d_ent, (const float*)(d_ent + 4 * n_ent), (const uint32_t*)(d_ent + 5 * n_ent), d_out};
+    launch_session_rows_select(c->logits, bs, c->rp, sa, n_ent, s);
+    HIPCHK(c, hipMemcpyAsync(h_sel, d_out, (size_t)3 * n_ent * 4, hipMemcpyDeviceToHost, s));
   }
   HIPCHK(c, hipEventRecord(S->ev_dec1, s));
   HIPCHK(c, hipStreamSynchronize(s));   // the one synchronisation of the step
   HIPCHK(c, hipGetLastError());
   float ms = 0.f;
   if (hipEventElapsedTime(&ms, S->ev_dec0, S->ev_dec1) == hipSuccess) S->dec_ms += ms;
-  // 4. selection per searching group (the code beam_search_impl runs), re-index, finished groups out
+  // 4. selection per searching BEAM group (the code beam_search_impl runs), re-index; ROWS groups keep their rows
   std::vector<std::vector<int>> nseq; std::vector<double> nsum; std::vector<int> src;
   std::vector<char> searching(G, 0);
   for (int g = 0; g < G; ++g) {
     Session::Group& gr = S->grp[g];
     searching[g] = gr.clip >= 0 && gr.pos + 1 >= (int)gr.prompt.size();
-    if (gr.clip >= 0 && any_ns && gr.pos == o.sot_index) gr.ns = h_ns[g * beam];
-    if (!searching[g]) {
-      for (int b = 0; b < beam; ++b) { const int r = g * beam + b; nseq.push_back(S->seqs[r]); nsum.push_back(S->sums[r]); src.push_back(r); }
-      continue;
+    const bool beam_search = searching[g] && gr.mode == Session::BEAM;
+    if (gr.clip >= 0 && gr.mode == Session::BEAM && any_ns && gr.pos == gr.sot) gr.ns = h_ns[g * beam];
+    int b0 = 0;
+    if (beam_search) {
+      if (!beam_select(S->seqs, S->sums, g * beam, gr.rows, gr.rows + 1, h_lp, h_id, o.eot, gr.max_cand, gr.finished, nseq, nsum, src, K))
+        return fail(c, TTASR_E_INVALID, "beam search: no live candidate (every token masked)");
+      b0 = gr.rows;
     }
-    if (!beam_select(S->seqs, S->sums, g * beam, beam, K, h_lp, h_id, o.eot, S->max_cand, gr.finished, nseq, nsum, src))
-      return fail(c, TTASR_E_INVALID, "beam search: no live candidate (every token masked)");
+    for (int b = b0; b < beam; ++b) { const int r = g * beam + b; nseq.push_back(S->seqs[r]); nsum.push_back(S->sums[r]); src.push_back(r); }
   }
   std::vector<int32_t> ntbl((size_t)c->maxB * pps, -1);
   for (int r = 0; r < R; ++r) memcpy(&ntbl[(size_t)r * pps], &tbl[(size_t)src[r] * pps], (size_t)pps * 4);
   tbl.swap(ntbl);
   S->seqs.swap(nseq); S->sums.swap(nsum);
+  // the independent rows' choices: the token, the f32 sum in the order select_body adds, EOT or the budget end the row
+  std::vector<int> live_rows(G, 0);
+  for (int g = 0; g < G; ++g)
+    for (int b = 0; b < beam; ++b) live_rows[g] += !S->done_rows[g * beam + b];
+  for (int e = 0; e < n_ent; ++e) {
+    const int32_t* en = p_ent + 4 * e;   // (the temperatures and seeds moved behind the entries; the entries stayed)
+    const int r = en[0];
+    Session::Group& gr = S->grp[r / beam];
+    if (en[3] & 2) gr.ns = h_sel[3 * e + 2];
+    if (!(en[3] & 1)) continue;
+    int choice;
+    memcpy(&choice, &h_sel[3 * e], 4);
+    if (choice < 0 || choice >= c->V) return fail(c, TTASR_E_INVALID, "session row %d: no live token (every token masked)", r);
+    S->seqs[r].push_back(choice);
+    S->fsums[r] += h_sel[3 * e + 1];
+    if (choice == o.eot || (int)S->seqs[r].size() >= gr.cap) S->done_rows[r] = 1;
+  }
   for (int g = 0; g < G; ++g) {
     Session::Group& gr = S->grp[g];
     if (gr.clip < 0) continue;
-    S->live_row_steps += beam;
+    S->live_row_steps += live_rows[g];
     gr.pos++;
     const int r0 = g * beam;
-    if (searching[g] && ((int)gr.finished.size() >= S->max_cand || (int)S->seqs[r0].size() >= gr.cap)) {
+    bool ended = false;
+    if (searching[g] && gr.mode == Session::BEAM) ended = (int)gr.finished.size() >= gr.max_cand || (int)S->seqs[r0].size() >= gr.cap;
+    if (searching[g] && gr.mode == Session::ROWS) {
+      ended = true;
+      for (int b = 0; b < gr.rows; ++b) ended &= S->done_rows[r0 + b] != 0;
+    }
+    if (ended) {
       Session::Done d;
       d.id = gr.clip;
-      d.tok.resize(c->rp.max_new);
-      double best = 0;
-      d.tok.resize(beam_pick(gr.finished, S->seqs, S->sums, r0, beam, o.eot, c->rp.max_new, d.tok.data(), &best));
-      d.lp = (float)best; d.ns = gr.ns;
+      if (gr.mode == Session::BEAM) {
+        d.tok.resize(c->rp.max_new);
+        double best = 0;
+        d.tok.resize(beam_pick(gr.finished, S->seqs, S->sums, r0, gr.rows, o.eot, c->rp.max_new, d.tok.data(), &best));
+        d.lp = (float)best;
+      } else {   // ttasr_generate_sample's pick and tokens (EOT kept)
+        std::vector<int32_t> lens(gr.rows);
+        for (int b = 0; b < gr.rows; ++b) lens[b] = (int32_t)S->seqs[r0 + b].size();
+        const int best = sample_pick(&S->fsums[r0], lens.data(), gr.rows);
+        const std::vector<int>& w = S->seqs[r0 + best];
+        d.tok.assign(w.begin(), w.begin() + std::min<size_t>(w.size(), (size_t)c->rp.max_new));
+        d.lp = S->fsums[r0 + best];
+      }
+      d.ns = gr.ns;
       S->finished.push_back(std::move(d));
       // the group is free: its page lists go back to the pool, its rows leave the attention kernels
       gr.clip = -1; gr.finished.clear();
@@ -424,7 +545,10 @@ static int beam_step(ttasr_ctx* c, Session* S) {
       }
       continue;
     }
-    for (int b = 0; b < beam; ++b) S->cur_tok[r0 + b] = searching[g] ? S->seqs[r0 + b].back() : gr.prompt[gr.pos];
+    for (int b = 0; b < beam; ++b) {
+      const int r = r0 + b;
+      S->cur_tok[r] = S->done_rows[r] ? o.eot : (searching[g] ? S->seqs[r].back() : gr.prompt[gr.pos]);
+    }
   }
   std::fill(S->refcnt.begin(), S->refcnt.end(), 0);
   for (int32_t p : tbl) if (p >= 0) S->refcnt[p]++;
@@ -462,6 +586,68 @@ static int session_submit(ttasr_ctx* c, int n, const float* const* pcm, const in
     cl.pcm.assign(pcm[i], pcm[i] + n_samples[i]);
     cl.prompt.assign(prompt + (size_t)i * P, prompt + (size_t)i * P + prompt_len[i]);
     cl.cap = max_new[i];
+    cl.mode = Session::BEAM; cl.rows = S->beam; cl.sot = S->o.sot_index;
+    if (out_ids) out_ids[i] = cl.id;
+    S->queue.push_back(std::move(cl));
+  }
+  return TTASR_OK;
+}
+
+// Window clips (beam session only): window i = 30 s of file_pcm[i] from frame seek_frames[i], with its own prompt, sot index,
+// budget, temperature, rows and seed.  Only the samples the window's STFT reads are copied (ttasr_log_mel_windows' span).
+static int session_submit_windows(ttasr_ctx* c, int n, const float* const* file_pcm, const int64_t* file_samples, const int64_t* seek_frames,
+                                  const float* floor_max, const int32_t* prompt, const int32_t* prompt_len, const int32_t* sot_index,
+                                  const int32_t* max_new, const float* temperature, const int32_t* rows, const uint32_t* seed,
+                                  int64_t* out_ids) {
+  if (!c) return TTASR_E_INVALID;
+  Session* S = c->sess;
+  if (!S) return fail(c, TTASR_E_INVALID, "no session is open (ttasr_session_begin_beam first)");
+  if (!S->beam) return fail(c, TTASR_E_INVALID, "window clips need a session opened with ttasr_session_begin_beam");
+  if (n < 1) return fail(c, TTASR_E_INVALID, "n %d < 1", n);
+  if (!file_pcm || !file_samples || !seek_frames || !prompt || !prompt_len || !sot_index || !max_new || !rows || !seed)
+    return fail(c, TTASR_E_INVALID, "NULL argument");
+  const int P = S->max_prompt;
+  // everything is validated before a clip is queued: a refused call leaves the session as it was
+  for (int i = 0; i < n; ++i) {
+    if (file_samples[i] < 0) return fail(c, TTASR_E_INVALID, "window %d: negative file length", i);
+    if (file_samples[i] > 0 && !file_pcm[i]) return fail(c, TTASR_E_INVALID, "window %d: pcm is NULL", i);
+    if (seek_frames[i] < 0 || seek_frames[i] >= (file_samples[i] + 159) / 160)
+      return fail(c, TTASR_E_INVALID, "window %d: seek %lld at or beyond the file (%lld samples)", i, (long long)seek_frames[i],
+                  (long long)file_samples[i]);
+    if (floor_max && !std::isfinite(floor_max[i])) return fail(c, TTASR_E_INVALID, "window %d: floor_max is not finite", i);
+    if (prompt_len[i] < 1 || prompt_len[i] > P) return fail(c, TTASR_E_INVALID, "window %d: prompt_len %d outside [1, %d]", i, prompt_len[i], P);
+    if (prompt_len[i] >= c->cfg.n_text_ctx)
+      return fail(c, TTASR_E_INVALID, "window %d: prompt_len %d leaves no room in the %d-token context", i, prompt_len[i], c->cfg.n_text_ctx);
+    for (int j = 0; j < prompt_len[i]; ++j)
+      if (prompt[(size_t)i * P + j] < 0 || prompt[(size_t)i * P + j] >= c->V) return fail(c, TTASR_E_INVALID, "window %d: prompt token outside vocabulary", i);
+    if (max_new[i] < 1 || max_new[i] > S->o.max_new_tokens)
+      return fail(c, TTASR_E_INVALID, "window %d: max_new %d outside [1, max_new_tokens=%d]", i, max_new[i], S->o.max_new_tokens);
+    if (S->o.no_speech >= 0 && (sot_index[i] < 0 || sot_index[i] >= prompt_len[i]))
+      return fail(c, TTASR_E_INVALID, "window %d: sot_index %d outside the %d-token prompt", i, sot_index[i], prompt_len[i]);
+    if (rows[i] < 1 || rows[i] > S->beam) return fail(c, TTASR_E_INVALID, "window %d: rows %d outside [1, %d]", i, rows[i], S->beam);
+    if (temperature && !(std::isfinite(temperature[i]) && temperature[i] >= 0.f))
+      return fail(c, TTASR_E_INVALID, "window %d: temperature %g must be finite and >= 0", i, temperature ? temperature[i] : 0.f);
+  }
+  for (int i = 0; i < n; ++i) {
+    Session::Clip cl;
+    cl.id = S->next_id++;
+    // the span of ttasr_log_mel_windows: `lead` samples before the window (200, fewer at the file start), the window, 200 after
+    const int64_t fs = file_samples[i], file_frames = fs / 160, seek = seek_frames[i];
+    const int64_t start = seek * 160, lead = std::min<int64_t>(200, start);
+    const int64_t avail = std::max<int64_t>(std::min<int64_t>(fs - (start - lead), lead + c->n_samples + 200), 0);
+    cl.pcm.assign(file_pcm[i] + (start - lead), file_pcm[i] + (start - lead) + avail);
+    cl.win = true;
+    cl.geom[0] = lead;
+    cl.geom[1] = (fs - (start - lead) < lead + c->n_samples + 200) ? fs - (start - lead) : ((int64_t)1 << 40);
+    cl.geom[2] = std::max<int64_t>(std::min<int64_t>(c->F, file_frames - seek), 0);
+    if (floor_max) { cl.has_floor = true; cl.floor = mel_max_to_ordered(floor_max[i]); }
+    cl.prompt.assign(prompt + (size_t)i * P, prompt + (size_t)i * P + prompt_len[i]);
+    cl.cap = max_new[i];
+    cl.sot = sot_index[i];
+    cl.temp = temperature ? temperature[i] : 0.f;
+    cl.rows = rows[i];
+    cl.seed = seed[i];
+    cl.mode = (cl.temp == 0.f && cl.rows > 1) ? Session::BEAM : Session::ROWS;
     if (out_ids) out_ids[i] = cl.id;
     S->queue.push_back(std::move(cl));
   }
@@ -582,6 +768,16 @@ int ttasr_session_begin_beam(ttasr_ctx* c, const ttasr_gen_opts* o, int32_t max_
 int ttasr_session_submit(ttasr_ctx* c, int32_t n, const float* const* pcm_host, const int64_t* n_samples, const int32_t* prompt,
                          const int32_t* prompt_len, const int32_t* max_new, int64_t* out_ids) {
   return guarded(c, [&]() -> int { return session_submit(c, n, pcm_host, n_samples, prompt, prompt_len, max_new, out_ids); });
+}
+
+int ttasr_session_submit_windows(ttasr_ctx* c, int32_t n, const float* const* file_pcm, const int64_t* file_samples,
+                                 const int64_t* seek_frames, const float* floor_max, const int32_t* prompt, const int32_t* prompt_len,
+                                 const int32_t* sot_index, const int32_t* max_new, const float* temperature, const int32_t* rows,
+                                 const uint32_t* seed, int64_t* out_ids) {
+  return guarded(c, [&]() -> int {
+    return session_submit_windows(c, n, file_pcm, file_samples, seek_frames, floor_max, prompt, prompt_len, sot_index, max_new,
+                                  temperature, rows, seed, out_ids);
+  });
 }
 
 int ttasr_session_poll(ttasr_ctx* c, int32_t max_steps, int32_t cap, int64_t* ids, int32_t* tokens, int32_t* lens, float* sum_lp,

@@ -220,15 +220,16 @@ int generate_rows(ttasr_ctx* c, int R, int rows_per_clip, const int32_t* prompt,
 // up to max_cand; the `beam` best live ones are appended to nseq / nsum with their parent rows in src.  false: no live candidate.
 bool beam_select(const std::vector<std::vector<int>>& seqs, const std::vector<double>& sums, int r0, int beam, int K,
                  const float* lp, const int32_t* id, int eot, int max_cand, std::map<std::vector<int>, double>& finished,
-                 std::vector<std::vector<int>>& nseq, std::vector<double>& nsum, std::vector<int>& src) {
+                 std::vector<std::vector<int>>& nseq, std::vector<double>& nsum, std::vector<int>& src, int stride) {
+  if (stride == 0) stride = K;   // the beam session's groups may use fewer rows than the candidate kernel ran for
   std::map<std::vector<int>, std::pair<double, int>> cand;
   for (int b = 0; b < beam; ++b) {
     const int r = r0 + b;
     for (int q = 0; q < K; ++q) {
-      const int tok = id[(size_t)r * K + q];
+      const int tok = id[(size_t)r * stride + q];
       if (tok < 0) continue;
       std::vector<int> key(seqs[r]); key.push_back(tok);
-      const double val = sums[r] + (double)lp[(size_t)r * K + q];
+      const double val = sums[r] + (double)lp[(size_t)r * stride + q];
       auto it = cand.find(key);
       if (it == cand.end() || val > it->second.first) cand[key] = {val, r};
     }
@@ -247,6 +248,15 @@ bool beam_select(const std::vector<std::vector<int>>& seqs, const std::vector<do
   if (saved == 0) return false;
   while (saved < beam) { nseq.push_back(nseq.back()); nsum.push_back(-1e30); src.push_back(src.back()); ++saved; }
   return true;
+}
+
+// The pick among a clip's n sampled rows (ttasr_generate_sample and the beam session's sampled groups): the highest
+// sum_logprob / length (length with EOT, at least 1), the first row among equals.  Returns the row's index in 0 .. n-1.
+int sample_pick(const float* lp, const int32_t* len, int n) {
+  int best = 0;
+  for (int r = 1; r < n; ++r)
+    if (lp[r] / std::max(len[r], 1) > lp[best] / std::max(len[best], 1)) best = r;
+  return best;
 }
 
 // The final pick of one clip: the finished hypotheses, topped up with the best live ones to `beam`, ranked by sum_logprob / length.

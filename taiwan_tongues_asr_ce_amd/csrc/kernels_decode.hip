@@ -175,6 +175,98 @@ __device__ __forceinline__ float gumbel_noise(uint32_t key, int i) {
   return -logf(-logf(u));
 }
 
+// The selection of one row held in registers, after the rules (shared by select_body and session_rows_select_kernel, so the
+// session's independent rows choose exactly what a static pass chooses).  Pass 1: (max, first index) of the allowed text and
+// timestamp tokens and the maximum of the unprocessed row (want_ns); pass 2: the sums of exp relative to the overall maximum.
+// On return the per-wave partial sums are in s_sum[0..2][wave] (text, timestamps, unprocessed row) for thread 0 to add up.
+struct SelectMax { float mx_txt, mx_ts, mx_raw; int i_txt, i_ts; float mx_all; };
+__device__ __forceinline__ SelectMax select_passes(RowRegs& R, int V, int tid, int lane, int wave, const RowRanges& rq, bool want_ns,
+                                                   const float* row, float raw_max, ArgMax (&s_am)[2][16], float (&s_sum)[3][16],
+                                                   float (&s_b)[8], int (&s_i)[4]) {
+  // pass 1: (max, lowest index) of the allowed text and timestamp tokens.  A thread visits its elements in increasing index
+  // order, so the strict comparison keeps the first maximum; across threads am_merge breaks ties towards the lower index.
+  ArgMax a_txt{-INFINITY, 0x7fffffff}, a_ts{-INFINITY, 0x7fffffff};
+  for_each_by_range(R, V, tid, rq.tb,
+                    [&](int i, float& v) { if (v > a_txt.v) { a_txt.v = v; a_txt.i = i; } },
+                    [&](int i, float& v) { if (v > a_ts.v) { a_ts.v = v; a_ts.i = i; } });
+  a_txt = am_wave(a_txt);
+  a_ts = am_wave(a_ts);
+  raw_max = wave_max(raw_max);
+  if (lane == 0) { s_am[0][wave] = a_txt; s_am[1][wave] = a_ts; s_sum[2][wave] = raw_max; }
+  __syncthreads();
+  if (wave == 0) {
+    ArgMax x = lane < 16 ? s_am[0][lane] : ArgMax{-INFINITY, 0x7fffffff};
+    ArgMax y = lane < 16 ? s_am[1][lane] : ArgMax{-INFINITY, 0x7fffffff};
+    float z = lane < 16 ? s_sum[2][lane] : -INFINITY;
+    x = am_wave(x); y = am_wave(y); z = wave_max(z);
+    if (lane == 0) { s_b[0] = x.v; s_i[0] = x.i; s_b[1] = y.v; s_i[1] = y.i; s_b[2] = z; }
+  }
+  __syncthreads();
+  const float mx_txt = s_b[0], mx_ts = s_b[1], mx_raw = s_b[2];
+  const int i_txt = s_i[0], i_ts = s_i[1];
+  const float mx_all = fmaxf(mx_txt, mx_ts);
+  // pass 2: sums of exp relative to mx_all (masked elements are -inf: they add exp2(-inf) = 0; everything masked: mref = 0)
+  constexpr float LOG2E = 1.4426950408889634f;
+  const float mref = (mx_all == -INFINITY ? 0.f : mx_all) * LOG2E;
+  float sum_txt = 0.f, sum_ts = 0.f, sum_raw = 0.f;
+  for_each_by_range(R, V, tid, rq.tb,
+                    [&](int, float& v) { sum_txt += __builtin_amdgcn_exp2f(fmaf(v, LOG2E, -mref)); },
+                    [&](int, float& v) { sum_ts += __builtin_amdgcn_exp2f(fmaf(v, LOG2E, -mref)); });
+  if (want_ns)  // the raw row once more, from memory (the registers hold the processed values)
+    for (int i = tid; i < V; i += 1024) sum_raw += __expf(row[i] - mx_raw);
+  sum_txt = wave_sum(sum_txt); sum_ts = wave_sum(sum_ts); sum_raw = wave_sum(sum_raw);
+  __syncthreads();
+  if (lane == 0) { s_sum[0][wave] = sum_txt; s_sum[1][wave] = sum_ts; s_sum[2][wave] = sum_raw; }
+  __syncthreads();
+  return SelectMax{mx_txt, mx_ts, mx_raw, i_txt, i_ts, mx_all};
+}
+// thread 0: the per-wave sums of select_passes added up (t0 text, t1 timestamps, t2 unprocessed row), in wave order
+__device__ __forceinline__ void select_totals(const float (&s_sum)[3][16], float& t0_out, float& t1_out, float& t2_out) {
+  float t0 = 0.f, t1 = 0.f, t2 = 0.f;
+#pragma unroll
+  for (int w = 0; w < 16; ++w) { t0 += s_sum[0][w]; t1 += s_sum[1][w]; t2 += s_sum[2][w]; }
+  t0_out = t0; t1_out = t1; t2_out = t2;
+}
+// thread 0: the forced-timestamp rule, the log-normaliser and the greedy choice, stored to the caller's shared variables
+// (s_force: the timestamp rule fired; s_live = 1: a choice was made).  The same statements as select_body's decision, in the
+// same order.
+__device__ __forceinline__ void select_decide(const SelectMax& m, float t0, float t1, const RuleParams& p, int& s_force, int& s_live,
+                                              int& s_choice, float& s_cv, float& s_lse) {
+  const float mx_all = m.mx_all;
+  // logsumexp(timestamps) > max(text)  <=>  log(t1) + mx_all > mx_txt   (common -lse cancels)
+  const bool force_ts = p.timestamps && t1 > 0.f && (__logf(t1) + mx_all > m.mx_txt);
+  s_force = force_ts; s_live = 1;
+  if (force_ts) { s_choice = m.i_ts; s_cv = m.mx_ts; s_lse = __logf(t1) + mx_all; }
+  else {
+    const bool pick_ts = m.mx_ts > m.mx_txt;  // ties go to the lower index, i.e. text
+    s_choice = pick_ts ? m.i_ts : m.i_txt; s_cv = pick_ts ? m.mx_ts : m.mx_txt; s_lse = __logf(t0 + t1) + mx_all;
+  }
+}
+// pass 3: Gumbel-max sample over the allowed set (the text range too unless the timestamp rule forced a timestamp); the
+// sampling key is pcg_hash(seed ^ pcg_hash(key_row * 0x9E3779B9 + position)).  Thread 0 of wave 0 stores the choice and its
+// raw logit in s_choice / s_cv.
+__device__ __forceinline__ void select_sample(RowRegs& R, int V, int tid, int lane, int wave, bool force_ts, int tb, uint32_t key,
+                                              float temperature, const float* row, ArgMax (&s_am)[2][16], int& s_choice, float& s_cv) {
+  ArgMax best{-INFINITY, 0x7fffffff};
+  for_each_logit(R, V, tid, [&](int i, float& v) {
+    if (force_ts && i < tb) return;
+    if (v == -INFINITY) return;
+    best = am_merge(best, ArgMax{v / temperature + gumbel_noise(key, i), i});
+  });
+  best = am_wave(best);
+  if (lane == 0) s_am[0][wave] = best;
+  __syncthreads();
+  if (wave == 0) {
+    ArgMax x = lane < 16 ? s_am[0][lane] : ArgMax{-INFINITY, 0x7fffffff};
+    x = am_wave(x);
+    if (lane == 0) { s_choice = x.i; s_cv = row[x.i]; }
+  }
+  __syncthreads();
+}
+__device__ __forceinline__ uint32_t sample_key(uint32_t seed, int key_row, int position) {
+  return pcg_hash(seed ^ pcg_hash((uint32_t)key_row * 0x9E3779B9u + (uint32_t)position));
+}
+
 // One workgroup (1024 threads) per row.  Everything the kernel reads is addressed by the row index alone and requested in ONE
 // batch (the logits row, the mask words, the row's search state); masked elements become -inf in the registers; pass 1 finds the
 // (max, first index) of the text and timestamp ranges, pass 2 the sums of exp (f32); then the "timestamp mass > best text token"
@@ -250,41 +342,7 @@ __device__ __forceinline__ void select_body(const float* logits, DecState st, Ru
   apply_rules_regs(R, mw, tmw, p.V, tid, rq);
   if constexpr (HOOK) for_each_logit(R, p.V, tid, [&](int i, float& v) { out_rows[(int64_t)b * p.V + i] = v; });
 
-  // pass 1: (max, lowest index) of the allowed text and timestamp tokens.  A thread visits its elements in increasing index
-  // order, so the strict comparison keeps the first maximum; across threads am_merge breaks ties towards the lower index.
-  ArgMax a_txt{-INFINITY, 0x7fffffff}, a_ts{-INFINITY, 0x7fffffff};
-  for_each_by_range(R, p.V, tid, rq.tb,
-                    [&](int i, float& v) { if (v > a_txt.v) { a_txt.v = v; a_txt.i = i; } },
-                    [&](int i, float& v) { if (v > a_ts.v) { a_ts.v = v; a_ts.i = i; } });
-  a_txt = am_wave(a_txt);
-  a_ts = am_wave(a_ts);
-  raw_max = wave_max(raw_max);
-  if (lane == 0) { s_am[0][wave] = a_txt; s_am[1][wave] = a_ts; s_sum[2][wave] = raw_max; }
-  __syncthreads();
-  if (wave == 0) {
-    ArgMax x = lane < 16 ? s_am[0][lane] : ArgMax{-INFINITY, 0x7fffffff};
-    ArgMax y = lane < 16 ? s_am[1][lane] : ArgMax{-INFINITY, 0x7fffffff};
-    float z = lane < 16 ? s_sum[2][lane] : -INFINITY;
-    x = am_wave(x); y = am_wave(y); z = wave_max(z);
-    if (lane == 0) { s_b[0] = x.v; s_i[0] = x.i; s_b[1] = y.v; s_i[1] = y.i; s_b[2] = z; }
-  }
-  __syncthreads();
-  const float mx_txt = s_b[0], mx_ts = s_b[1], mx_raw = s_b[2];
-  const int i_txt = s_i[0], i_ts = s_i[1];
-  const float mx_all = fmaxf(mx_txt, mx_ts);
-  // pass 2: sums of exp relative to mx_all (masked elements are -inf: they add exp2(-inf) = 0; everything masked: mref = 0)
-  constexpr float LOG2E = 1.4426950408889634f;
-  const float mref = (mx_all == -INFINITY ? 0.f : mx_all) * LOG2E;
-  float sum_txt = 0.f, sum_ts = 0.f, sum_raw = 0.f;
-  for_each_by_range(R, p.V, tid, rq.tb,
-                    [&](int, float& v) { sum_txt += __builtin_amdgcn_exp2f(fmaf(v, LOG2E, -mref)); },
-                    [&](int, float& v) { sum_ts += __builtin_amdgcn_exp2f(fmaf(v, LOG2E, -mref)); });
-  if (want_ns)  // the raw row once more, from memory (the registers hold the processed values)
-    for (int i = tid; i < p.V; i += 1024) sum_raw += __expf(row[i] - mx_raw);
-  sum_txt = wave_sum(sum_txt); sum_ts = wave_sum(sum_ts); sum_raw = wave_sum(sum_raw);
-  __syncthreads();
-  if (lane == 0) { s_sum[0][wave] = sum_txt; s_sum[1][wave] = sum_ts; s_sum[2][wave] = sum_raw; }
-  __syncthreads();
+  const SelectMax m = select_passes(R, p.V, tid, lane, wave, rq, want_ns, row, raw_max, s_am, s_sum, s_b, s_i);
   // decision by thread 0: forced-timestamp rule, log-normaliser, greedy choice
   __shared__ float s_lse, s_cv;
   __shared__ int s_choice, s_live;
@@ -293,42 +351,26 @@ __device__ __forceinline__ void select_body(const float* logits, DecState st, Ru
     float t0 = 0.f, t1 = 0.f, t2 = 0.f;
 #pragma unroll
     for (int w = 0; w < 16; ++w) { t0 += s_sum[0][w]; t1 += s_sum[1][w]; t2 += s_sum[2][w]; }
-    if (want_ns) st.no_speech[b] = __expf(row[p.no_speech] - mx_raw) / t2;
+    if (want_ns) st.no_speech[b] = __expf(row[p.no_speech] - m.mx_raw) / t2;
     if (forced) {
       st.cur_tok[b] = st.prompt[b * p.max_prompt + step + 1];
     } else if (done_b) {
       st.cur_tok[b] = p.eot;
     } else {
-      // logsumexp(timestamps) > max(text)  <=>  log(t1) + mx_all > mx_txt   (common -lse cancels)
-      const bool force_ts = p.timestamps && t1 > 0.f && (__logf(t1) + mx_all > mx_txt);
+      // (select_decide states the same rule for the session kernel; kept inline here: the helper form changes the branch layout
+      // of select_kernel<false, false>, the benchmark's kernel)
+      const bool force_ts = p.timestamps && t1 > 0.f && (__logf(t1) + m.mx_all > m.mx_txt);
       s_i[2] = force_ts; s_live = 1;
-      if (force_ts) { s_choice = i_ts; s_cv = mx_ts; s_lse = __logf(t1) + mx_all; }
+      if (force_ts) { s_choice = m.i_ts; s_cv = m.mx_ts; s_lse = __logf(t1) + m.mx_all; }
       else {
-        const bool pick_ts = mx_ts > mx_txt;  // ties go to the lower index, i.e. text
-        s_choice = pick_ts ? i_ts : i_txt; s_cv = pick_ts ? mx_ts : mx_txt; s_lse = __logf(t0 + t1) + mx_all;
+        const bool pick_ts = m.mx_ts > m.mx_txt;  // ties go to the lower index, i.e. text
+        s_choice = pick_ts ? m.i_ts : m.i_txt; s_cv = pick_ts ? m.mx_ts : m.mx_txt; s_lse = __logf(t0 + t1) + m.mx_all;
       }
     }
   }
   __syncthreads();
-  if (SAMPLE && s_live) {  // pass 3: Gumbel-max sample over the allowed set
-    const bool force_ts = s_i[2] != 0;
-    const uint32_t key = pcg_hash(p.seed ^ pcg_hash((uint32_t)b * 0x9E3779B9u + (uint32_t)step));
-    ArgMax best{-INFINITY, 0x7fffffff};
-    for_each_logit(R, p.V, tid, [&](int i, float& v) {
-      if (force_ts && i < tb) return;
-      if (v == -INFINITY) return;
-      best = am_merge(best, ArgMax{v / p.temperature + gumbel_noise(key, i), i});
-    });
-    best = am_wave(best);
-    if (lane == 0) s_am[0][wave] = best;
-    __syncthreads();
-    if (wave == 0) {
-      ArgMax x = lane < 16 ? s_am[0][lane] : ArgMax{-INFINITY, 0x7fffffff};
-      x = am_wave(x);
-      if (lane == 0) { s_choice = x.i; s_cv = row[x.i]; }
-    }
-    __syncthreads();
-  }
+  if (SAMPLE && s_live)  // pass 3: Gumbel-max sample over the allowed set
+    select_sample(R, p.V, tid, lane, wave, s_i[2] != 0, tb, sample_key(p.seed, b, step), p.temperature, row, s_am, s_choice, s_cv);
   if (tid == 0 && s_live) {
     const int choice = s_choice;
     st.cur_tok[b] = choice;
@@ -365,6 +407,61 @@ void launch_select_rows(const float* logits, DecState st, RuleParams rp, int B, 
   if (rp.V > LOGIT_NIT * 4096) { launch_fault("select: vocabulary %d > %d", rp.V, LOGIT_NIT * 4096); return; }
   if (rp.temperature > 0.f) hipLaunchKernelGGL((select_rows_kernel<true>), dim3(B), dim3(1024), 0, s, logits, st, rp);
   else hipLaunchKernelGGL((select_rows_kernel<false>), dim3(B), dim3(1024), 0, s, logits, st, rp);
+}
+
+// Independent rows of the beam session (engine_refill.hip, ROWS groups: greedy with one row, or best_of Gumbel-max samples): one
+// workgroup per entry of `ent`, only for rows past their prompt (bit 0 of the flags: choose) or at their group's
+// <|startoftranscript|> position (bit 1: no-speech capture).  The row's rule history comes from the host as for beam_topk_kernel
+// (BeamRowState), its temperature, seed and key row (the row's index inside its group) from the entry.  Writes out[e] = {choice,
+// log-probability increment s_cv - s_lse, no-speech} exactly as select_body computes them for row `key row` of a static pass at
+// the same position; the host adds the increment to the row's f32 sum.
+__global__ __launch_bounds__(1024) void session_rows_select_kernel(const float* __restrict__ logits, BeamRowState hs, RuleParams p,
+                                                                   SessRowsArgs a) {
+  __shared__ ArgMax s_am[2][16];
+  __shared__ float s_sum[3][16];
+  __shared__ float s_b[8];
+  __shared__ int s_i[4];
+  __shared__ float s_lse, s_cv;
+  __shared__ int s_choice;
+  const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = a.ent[4 * e], pos = a.ent[4 * e + 1], key_row = a.ent[4 * e + 2], flags = a.ent[4 * e + 3];
+  const float temperature = a.temp[e];
+  const uint32_t seed = a.seed[e];
+  const float* row = logits + (int64_t)b * p.ldv;
+  RowRegs R;
+  uint32_t mw[LOGIT_NIT], tmw;
+  load_row_regs(R, mw, tmw, row, hs.mask, p.V, tid);
+  RowRule r;
+  r.n = hs.n_sampled[b];
+  const int last = hs.last_tok[b], pen = hs.pen_tok[b], lts = hs.last_ts[b];
+  __builtin_amdgcn_sched_barrier(0);
+  const bool choose = (flags & 1) != 0, want_ns = (flags & 2) != 0 && p.no_speech >= 0;
+  const int tb = p.timestamp_begin;
+  r.last_is_ts = (r.n >= 1 && last >= tb);
+  r.pen_is_ts = (r.n < 2 || pen >= tb);
+  r.ts_floor = (lts >= 0) ? ((r.last_is_ts && !r.pen_is_ts) ? lts : lts + 1) : 0;
+  const RowRanges rq = make_ranges(r, p);
+  float raw_max = -INFINITY;
+  if (want_ns) for_each_logit(R, p.V, tid, [&](int, float& v) { raw_max = fmaxf(raw_max, v); });
+  apply_rules_regs(R, mw, tmw, p.V, tid, rq);
+  const SelectMax m = select_passes(R, p.V, tid, lane, wave, rq, want_ns, row, raw_max, s_am, s_sum, s_b, s_i);
+  if (tid == 0) {
+    float t0, t1, t2;
+    select_totals(s_sum, t0, t1, t2);
+    a.out[3 * e + 2] = want_ns ? __expf(row[p.no_speech] - m.mx_raw) / t2 : 0.f;
+    select_decide(m, t0, t1, p, s_i[2], s_i[3], s_choice, s_cv, s_lse);
+  }
+  __syncthreads();
+  if (choose && temperature > 0.f)
+    select_sample(R, p.V, tid, lane, wave, s_i[2] != 0, tb, sample_key(seed, key_row, pos), temperature, row, s_am, s_choice, s_cv);
+  if (tid == 0) {
+    a.out[3 * e] = __int_as_float(choose ? s_choice : -1);
+    a.out[3 * e + 1] = s_cv - s_lse;
+  }
+}
+void launch_session_rows_select(const float* logits, BeamRowState hs, RuleParams rp, SessRowsArgs a, int n, hipStream_t s) {
+  if (rp.V > LOGIT_NIT * 4096) { launch_fault("select: vocabulary %d > %d", rp.V, LOGIT_NIT * 4096); return; }
+  if (n > 0) hipLaunchKernelGGL(session_rows_select_kernel, dim3(n), dim3(1024), 0, s, logits, hs, rp, a);
 }
 
 // Row admission (continuous-batching session): one workgroup per admitted row.  Runs on the decode stream between two step

@@ -451,6 +451,76 @@ class Session:
         self.pending += n
         return ids.tolist()
 
+    def submit_windows(self, files: Sequence[np.ndarray], seeks: Sequence[int], prompts: Sequence[Sequence[int]],
+                       sot_index: Sequence[int], max_new: Optional[Sequence[int]] = None,
+                       floor_max: Optional[Sequence[float]] = None, temperature: Optional[Sequence[float]] = None,
+                       rows: Optional[Sequence[int]] = None, seed: Optional[Sequence[int]] = None) -> List[int]:
+        """Queue 30-s windows of recordings (beam sessions only; ttasr_session_submit_windows): window i starts at 10-ms frame
+        seeks[i] of files[i] (float32 PCM), with its prompt, <|startoftranscript|> index, budget (default opts.max_new_tokens),
+        dynamic-range maximum (floor_max, default: the window's own), temperature (default 0), rows (default: the session's
+        beam width) and sampling seed (default 0).  Temperature 0 with rows > 1 is beam search; one row at temperature 0 is
+        greedy; temperature > 0 draws `rows` samples.  Shapes and ranges are checked here before the library is called."""
+        if not self.open:
+            raise TtasrError("session is closed")
+        if not self.beam:
+            raise ValueError("window clips need a beam session (Engine.session(beam=..., patience=...))")
+        n = len(files)
+        if n < 1 or any(len(x) != n for x in (seeks, prompts, sot_index)):
+            raise ValueError(f"need >= 1 window and one seek, prompt and sot index per window (files {n}, seeks {len(seeks)}, "
+                             f"prompts {len(prompts)}, sot_index {len(sot_index)})")
+
+        def per_window(v, default, dtype, name):
+            a = np.full(n, default, dtype=dtype) if v is None else np.ascontiguousarray(v, dtype=dtype)
+            if a.shape != (n,):
+                raise ValueError(f"{name} needs one entry per window ({n}), got shape {a.shape}")
+            return a
+        caps = per_window(max_new, self.max_new_tokens, np.int32, "max_new")
+        if caps.min() < 1 or caps.max() > self.max_new_tokens:
+            raise ValueError(f"max_new entries must lie in [1, {self.max_new_tokens}]")
+        sk = per_window(seeks, 0, np.int64, "seeks")
+        temps = per_window(temperature, 0.0, np.float32, "temperature")
+        if not (np.all(np.isfinite(temps)) and temps.min() >= 0):
+            raise ValueError("temperatures must be finite and >= 0")
+        rw = per_window(rows, self.beam, np.int32, "rows")
+        if rw.min() < 1 or rw.max() > self.beam:
+            raise ValueError(f"rows entries must lie in [1, {self.beam}] (the session's group width)")
+        sd = per_window(seed, 0, np.int64, "seed")
+        if sd.min() < 0 or sd.max() > 0xFFFFFFFF:
+            raise ValueError("seeds must lie in [0, 2**32)")
+        sd = sd.astype(np.uint32)
+        fm = None if floor_max is None else per_window(floor_max, 0.0, np.float32, "floor_max")
+        if fm is not None and not np.all(np.isfinite(fm)):
+            raise ValueError("floor_max entries must be finite")
+        pcm = []
+        for i, f in enumerate(files):
+            a = np.ascontiguousarray(f, dtype=np.float32)
+            if a.ndim != 1:
+                raise ValueError(f"window {i}: PCM must be one-dimensional, got shape {a.shape}")
+            if not 0 <= sk[i] * 160 < len(a):
+                raise ValueError(f"window {i}: seek {sk[i]} lies outside the recording ({len(a)} samples)")
+            pcm.append(a)
+        pr = np.zeros((n, self.max_prompt), dtype=np.int32)
+        pl = np.zeros(n, dtype=np.int32)
+        so = per_window(sot_index, 0, np.int32, "sot_index")
+        for i, p in enumerate(prompts):
+            if not 1 <= len(p) <= self.max_prompt:
+                raise ValueError(f"window {i}: prompt length {len(p)} outside [1, {self.max_prompt}]")
+            if not 0 <= so[i] < len(p):
+                raise ValueError(f"window {i}: sot_index {so[i]} outside the {len(p)}-token prompt")
+            pr[i, :len(p)] = p
+            pl[i] = len(p)
+        ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in pcm])
+        ns = np.asarray([len(a) for a in pcm], dtype=np.int64)
+        ids = np.zeros(n, dtype=np.int64)
+        i32p, i64p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_float)
+        self.engine._check(self.engine.lib.ttasr_session_submit_windows(
+            self.engine.h, n, ptrs, ns.ctypes.data_as(i64p), sk.ctypes.data_as(i64p), fm.ctypes.data_as(f32p) if fm is not None else None,
+            pr.ctypes.data_as(i32p), pl.ctypes.data_as(i32p), so.ctypes.data_as(i32p), caps.ctypes.data_as(i32p),
+            temps.ctypes.data_as(f32p), rw.ctypes.data_as(i32p), sd.ctypes.data_as(C.POINTER(C.c_uint32)), ids.ctypes.data_as(i64p)),
+            "session_submit_windows")
+        self.pending += n
+        return ids.tolist()
+
     def poll(self, max_steps: int = 1 << 30, cap: Optional[int] = None) -> List[SessionResult]:
         """Admit ready clips, decode until at least one clip finished (or nothing is left, or max_steps steps ran); returns the
         finished clips (at most `cap`, default max_batch)."""

@@ -563,15 +563,23 @@ class WhisperModel:
                         else eng.generate([prompt], opts)
                 else:
                     rows = max(1, min(p["best_of"], self.max_batch))
-                    res = eng.generate_sample([prompt], rows, opts, temp, seed=(seek * 1000003 + int(temp * 1000)) & 0x7FFFFFFF)
+                    res = eng.generate_sample([prompt], rows, opts, temp, seed=self._fallback_seed(seek, temp))
                 toks, avg_lp, ns, cr = self._score(res, 0)
             attempts.append((temp, toks, avg_lp, ns, cr))
             if not self._needs_fallback(avg_lp, ns, cr, p):
                 return attempts[-1]
-        # every temperature failed: keep the most likely attempt among the non-repetitive ones
+        return self._best_attempt(attempts, p)
+
+    @staticmethod
+    def _best_attempt(attempts, p):
+        """Every temperature failed: keep the most likely attempt among the non-repetitive ones."""
         thr = p["compression_ratio_threshold"]
         ok = [a for a in attempts if thr is None or a[4] <= thr]
         return max(ok or attempts, key=lambda a: a[2])
+
+    @staticmethod
+    def _fallback_seed(seek: int, temp: float) -> int:
+        return (seek * 1000003 + int(temp * 1000)) & 0x7FFFFFFF
 
     def _window_opts(self, prompt_len: int, sot_index: int, p):
         st = self.special
@@ -698,20 +706,30 @@ class WhisperModel:
                         log_prob_threshold: Optional[float] = -1.0, max_initial_timestamp: float = 1.0,
                         suppress_blank: bool = True, temperature: Union[float, Sequence[float]] = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0),
                         best_of: int = 5, compression_ratio_threshold: Optional[float] = 2.4, patience: float = 1.0,
-                        hotwords: Optional[str] = None, prefix: Optional[str] = None
+                        hotwords: Optional[str] = None, prefix: Optional[str] = None, continuous: bool = False
                         ) -> List[Tuple[List[Segment], TranscriptionInfo]]:
         """Several FILES in lock step: every round takes the next 30-s window of each unfinished file and runs them as
         ONE engine pass (log-mel, encoder, beam search with one previous-text prompt per file), so a folder is
         transcribed at batch throughput while each file keeps exactly the sequential algorithm of `transcribe` — its
         own seek, prompt, thresholds.  A window that fails the temperature-0 thresholds is re-decoded alone through the
-        same fallback ladder.  Files are sharded by file across GPUs by the caller (batch_cli), never by window."""
+        same fallback ladder.  Files are sharded by file across GPUs by the caller (batch_cli), never by window.
+
+        continuous=True: one continuous-batching beam session instead of lock-step passes (DESIGN.md "Long-form files in the
+        session"): every file keeps one window in flight, a window that fails the thresholds goes back in at the next
+        temperature (sampled attempts run in the session too), and a file's next window is submitted as soon as its current
+        one is settled.  Each file gets exactly `transcribe()`'s algorithm.  word_timestamps is not supported there."""
         eng = self.engine
+        if continuous and word_timestamps:
+            raise ValueError("word_timestamps=True is not supported with continuous=True (the alignment pass needs the window's "
+                             "encoder state, which the session hands to the next window)")
         beam = max(1, min(beam_size, 7, self.max_batch))
         per_pass = max(1, self.max_batch // beam)
         temps = tuple(temperature) if isinstance(temperature, (list, tuple)) else (float(temperature),)
         p = self._params(language, task, condition_on_previous_text, without_timestamps, max_new_tokens, no_speech_threshold,
                          log_prob_threshold, max_initial_timestamp, suppress_blank, beam, patience, temps, best_of,
                          compression_ratio_threshold, bool(word_timestamps), hotwords, prefix)
+        if continuous:
+            p["beam_size"] = int(beam_size)
         files = []
         for a in audios:
             a = decode_audio(a) if isinstance(a, str) else np.asarray(a)
@@ -721,7 +739,9 @@ class WhisperModel:
             fs["segments"] = []
             fs["file_max"] = self._file_feature_max(fs["audio"])   # whole-file dynamic-range floor, as `transcribe`
             files.append(fs)
-        while True:
+        if continuous:
+            self._run_continuous(files, p)
+        while not continuous:
             active = [fs for fs in files if fs["seek"] < fs["n_total"]]
             if not active:
                 break
@@ -764,6 +784,69 @@ class WhisperModel:
                                                                 initial_prompt=initial_prompt))
             out.append((fs["segments"], info))
         return out
+
+    def _run_continuous(self, files: List[dict], p: dict):
+        """transcribe_many(continuous=True): the windows of all files through one beam session, one window per file in flight.
+        A window's attempts follow `_decode_with_fallback` (temperature 0: beam search of beam_size rows, or greedy with one;
+        temperature > 0: best_of samples seeded as `transcribe` seeds them), its result `_finish_window`."""
+        from .engine import GenResult, TtasrError
+        eng = self.engine
+        temps, beam = p["temperatures"], p["beam_size"]
+        if not 1 <= beam <= 7:
+            raise ValueError(f"beam_size={beam} outside [1, 7]")
+        if beam > self.max_batch:
+            raise ValueError(f"beam_size={beam} needs {beam} decode rows but this model was built with max_batch={self.max_batch}")
+        rows_sampled = max(1, min(p["best_of"], self.max_batch))
+        width = max(beam, rows_sampled) if any(t > 0.0 for t in temps) else beam
+        if width > 7:
+            raise ValueError(f"best_of={p['best_of']}: a continuous session holds at most 7 rows per window")
+        todo = [fs for fs in files if fs["seek"] < fs["n_total"]]
+        if not todo:
+            return
+        n_ctx = self.dims.n_text_ctx
+        opts = self._window_opts(1, 0, p)   # the session's rules; budgets and sot indices are per window
+        eng.set_audio_ctx(0)
+        with eng.session(opts, n_ctx - 1, beam=width, patience=p["patience"]) as s:
+            inflight: Dict[int, dict] = {}
+
+            def submit(fs: dict):
+                w = fs["window"]
+                temp = temps[len(w["attempts"])]
+                ids = s.submit_windows([fs["audio"]], [fs["seek"]], [w["prompt"]], [w["sot"]], max_new=[w["budget"]],
+                                       floor_max=[fs["file_max"]], temperature=[temp],
+                                       rows=[rows_sampled if temp > 0.0 else beam], seed=[self._fallback_seed(fs["seek"], temp)])
+                inflight[ids[0]] = fs
+
+            def next_window(fs: dict):
+                pr, si = self._prompt(p["lang_tok"], p["task"], p["without_timestamps"], fs["prev"][fs["prompt_reset"]:],
+                                      p["hotwords_tokens"], p["prefix_tokens"] if fs["seek"] == 0 else None)
+                fs["window"] = dict(prompt=pr, sot=si, budget=min(p["max_new"], n_ctx - len(pr)), attempts=[],
+                                    frames=min(self.dims.n_frames, fs["n_total"] - fs["seek"]))
+                submit(fs)
+
+            for fs in todo:
+                next_window(fs)
+            while inflight:
+                got = s.poll()
+                if not got:
+                    raise TtasrError(f"session idle with {len(inflight)} windows unfinished")
+                for r in got:
+                    fs = inflight.pop(r.id)
+                    w = fs["window"]
+                    temp = temps[len(w["attempts"])]
+                    res = GenResult([r.tokens], np.asarray([r.sum_logprob], np.float32), np.asarray([r.no_speech_prob], np.float32))
+                    toks, avg_lp, ns, cr = self._score(res, 0)
+                    w["attempts"].append((temp, toks, avg_lp, ns, cr))
+                    if self._needs_fallback(avg_lp, ns, cr, p):
+                        if len(w["attempts"]) < len(temps):
+                            submit(fs)   # the next temperature of the ladder
+                            continue
+                        attempt = self._best_attempt(w["attempts"], p)
+                    else:
+                        attempt = w["attempts"][-1]
+                    fs["segments"].extend(self._finish_window(fs, 0, attempt, w["frames"], p))
+                    if fs["seek"] < fs["n_total"]:
+                        next_window(fs)
 
     # ------------------------------------------------------------------------------------------
     def transcribe_batch(self, clips: Sequence[np.ndarray], language: str = "zh", task: str = "transcribe",
