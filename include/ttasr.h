@@ -306,6 +306,53 @@ TTASR_API int ttasr_session_end(ttasr_ctx* ctx);
  * Invalidates any step-level decode state (it reuses row 0's self-attention pages). */
 TTASR_API int ttasr_align(ttasr_ctx* ctx, int32_t clip, const int32_t* tokens_host, int32_t n_tokens, const int32_t* pairs_host,
                 int32_t n_pairs, float* out_weights_host, float* out_logprob_host);
+/* The same alignment for n sequences in ONE pass, with the host part of the algorithm on the device as well.  Sequence i is
+ * tokens_host[i][0 .. n_tokens_host[i]) (rows of max_tokens entries; the rest of a row is ignored) against the resident
+ * encoder state of clip clip_host[i]; several sequences may name the same clip.  Shorter sequences are padded to max_tokens
+ * positions behind their real ones (causal self-attention: the real positions do not see them).  Behind the pass, per sequence:
+ *   rows [first_row_i, n_tokens_i - 1) and frames [0, F_i), F_i = max(1, num_frames_i / 2) capped at n_ctx, of every pair's
+ *   map -> per pair and frame, mean and population standard deviation over the rows (a zero deviation divides by 1) ->
+ *   median of medfilt_width along time, edges reflected (no filter when F_i <= medfilt_width / 2) -> mean over the pairs,
+ *   negated = the cost matrix C_i [rows_i][F_i] -> the DTW of ttasr_dtw (same f32 operations, same tie rule: for one cost
+ *   matrix the same path) -> per row the first frame of the path in it.
+ * Out (host):
+ *   out_start_frame_host  int32 [n][max_tokens]    rows_i = n_tokens_i - 1 - first_row_i entries valid per sequence
+ *   out_logprob_host      optional float32 [n][max_tokens]   n_tokens_i - 1 valid: log p(tokens[t+1] | tokens[0..t])
+ *   out_cost_host         optional float32 [n][max_tokens][n_ctx]   C_i in the top-left rows_i x F_i corner (tests)
+ *   out_weights_host      optional float32 [n][n_pairs][max_tokens][n_ctx]   the raw maps of every position (tests)
+ * (n_ctx = the current audio window.)  Checked before anything is enqueued, TTASR_E_INVALID: n outside [1, max_batch];
+ * max_tokens outside [2, min(n_text_ctx, n_audio_ctx)] or n * max_tokens > max_batch * n_audio_ctx (the rows of the borrowed
+ * workspaces); n_tokens_i outside [2, max_tokens]; first_row_i outside [0, n_tokens_i - 2]; num_frames_i < 0; medfilt_width
+ * even or outside [1, 15]; a token outside the vocabulary; the heads as for ttasr_align; a clip the encoder state does not
+ * hold; an open session.  The scratch (tables, maps [n_pairs][n * max_tokens][n_ctx] f32, cost matrices, DTW traces that do
+ * not fit the CU's LDS) is one block owned by the context: allocated by the first call, grown when a call needs more, freed by
+ * ttasr_destroy; a request that cannot be allocated returns TTASR_E_NOMEM and leaves the context usable.  Like ttasr_align the
+ * call invalidates any step-level decode state (sequence i uses row i's self-attention pages). */
+TTASR_API int ttasr_align_batch(ttasr_ctx* ctx, int32_t n, const int32_t* clip_host, const int32_t* tokens_host,
+                                const int32_t* n_tokens_host, int32_t max_tokens, const int32_t* first_row_host,
+                                const int32_t* num_frames_host, const int32_t* pairs_host, int32_t n_pairs, int32_t medfilt_width,
+                                int32_t* out_start_frame_host, float* out_logprob_host, float* out_cost_host,
+                                float* out_weights_host);
+/* Alignment inside a continuous-batching session (greedy or beam).
+ * ttasr_session_hold(ctx, 1): from now on a clip that finishes is returned by ttasr_session_poll as usual but KEEPS its row
+ *   (beam: its group) and its cross-KV slot; its rows are finished rows, which have left the attention kernels, so no live
+ *   row's result changes.  ttasr_session_rows shows the clip's id on its rows until it is aligned or released.  The host MUST
+ *   align or release held clips: a poll that can start nothing because every free unit is held returns *n_out == 0 with
+ *   ttasr_session_stats out[7] > 0.  Refused with option refill_overlap = 1 (the pass borrows the encoder workspaces, which the
+ *   overlapped encode writes from its own stream).  ttasr_session_hold(ctx, 0) switches the mode off and releases every
+ *   held clip.  A session that never calls it behaves as before.
+ * ttasr_session_align: ttasr_align_batch (same arguments, checks, outputs and scratch) for n DISTINCT held clips ids[i],
+ *   each with its own cross-KV slot, in self-attention pages no live row uses; on success the clips are released.
+ * ttasr_session_release: frees held clips without aligning them.
+ * An unknown id, an id that is not held, an id listed twice and any of the two calls with hold mode off are TTASR_E_INVALID,
+ * and nothing happens.  ttasr_session_end releases everything. */
+TTASR_API int ttasr_session_hold(ttasr_ctx* ctx, int32_t on);
+TTASR_API int ttasr_session_align(ttasr_ctx* ctx, int32_t n, const int64_t* ids, const int32_t* tokens_host,
+                                  const int32_t* n_tokens_host, int32_t max_tokens, const int32_t* first_row_host,
+                                  const int32_t* num_frames_host, const int32_t* pairs_host, int32_t n_pairs, int32_t medfilt_width,
+                                  int32_t* out_start_frame_host, float* out_logprob_host, float* out_cost_host,
+                                  float* out_weights_host);
+TTASR_API int ttasr_session_release(ttasr_ctx* ctx, int32_t n, const int64_t* ids);
 /* Host-side dynamic time warping over a row-major cost matrix [n_rows][n_cols] (tokens x frames): the monotone path
  * of minimum total cost from (0,0) to (n_rows-1, n_cols-1); out_row / out_col need n_rows + n_cols entries.  Pure CPU
  * (no context): CTranslate2 does this step in C++ too. */

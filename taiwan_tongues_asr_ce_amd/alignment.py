@@ -164,6 +164,13 @@ def find_alignment(engine, tokenizer, special, clip: int, text_tokens: Sequence[
     n_sot = len(sot_seq)
     # rows n_sot .. -1: <|notimestamps|> and the text tokens as FED tokens = the text tokens and <|eot|> as predictions
     starts = token_start_times(weights, n_sot, len(tokens) - 1, num_frames, medfilt_width)
+    return words_from_alignment(tokenizer, special, text_tokens, starts, logprob, n_sot, language)
+
+
+def words_from_alignment(tokenizer, special, text_tokens: Sequence[int], starts: np.ndarray, logprob: np.ndarray, n_sot: int,
+                         language: str) -> List[dict]:
+    """The host tail find_alignment and find_alignment_batch share: start times (seconds) of the rows <|notimestamps|>,
+    text... and the teacher-forced log-probs -> [{word, tokens, start, end, probability}]."""
     text_probs = np.exp(logprob[n_sot: n_sot + len(text_tokens)])          # p(text token k) = logprob[index of k - 1]
     words, word_tokens = split_to_word_tokens(tokenizer, list(text_tokens) + [special.eot], language, special.eot)
     if len(word_tokens) <= 1:
@@ -177,6 +184,33 @@ def find_alignment(engine, tokenizer, special, clip: int, text_tokens: Sequence[
     for w, toks, s, e, i, j in zip(words, word_tokens, start_t, end_t, bounds[:-1], bounds[1:]):
         p = float(np.mean(text_probs[i:j])) if j > i else 0.0
         out.append(dict(word=w, tokens=list(toks), start=float(s), end=float(e), probability=p))
+    return out
+
+
+def find_alignment_batch(aligner, tokenizer, special, clips: Sequence[int], text_tokens: Sequence[Sequence[int]],
+                         num_frames: Sequence[int], heads: Sequence[Tuple[int, int]], language: str = "zh",
+                         lang_token: Optional[int] = None, task_token: Optional[int] = None,
+                         medfilt_width: int = 7) -> List[List[dict]]:
+    """find_alignment for several clips in ONE device pass: `aligner` is an Engine (clips = indices of resident clips,
+    Engine.align_batch) or a Session in hold mode (clips = ids of held clips, Session.align, which also releases them).
+    Normalisation, median filter and DTW run on the device; the word building is find_alignment's.  A clip without text
+    tokens gets [] (and, in a session, is released)."""
+    sot_seq = [special.sot, special.lang_zh if lang_token is None else lang_token,
+               special.transcribe if task_token is None else task_token]
+    n_sot = len(sot_seq)
+    out: List[List[dict]] = [[] for _ in clips]
+    live = [i for i, t in enumerate(text_tokens) if len(t) > 0]
+    in_session = hasattr(aligner, "release")
+    if in_session and len(live) < len(clips):
+        aligner.release([clips[i] for i in range(len(clips)) if i not in live])
+    if not live:
+        return out
+    seqs = [sot_seq + [special.no_timestamps] + list(text_tokens[i]) + [special.eot] for i in live]
+    call = aligner.align if in_session else aligner.align_batch
+    r = call([clips[i] for i in live], seqs, [n_sot] * len(live), [int(num_frames[i]) for i in live], heads, medfilt_width)
+    for k, i in enumerate(live):
+        starts = r.start_frames[k] / TOKENS_PER_SECOND
+        out[i] = words_from_alignment(tokenizer, special, text_tokens[i], starts, r.logprobs[k], n_sot, language)
     return out
 
 

@@ -148,6 +148,7 @@ void ttasr_destroy(ttasr_ctx* c) {
   for (auto& e : c->ev) if (e) hipEventDestroy(e);
   for (auto& e : c->enc_ev) hipEventDestroy(e);
   for (void* p : c->allocs) hipFree(p);
+  if (c->align_dev) hipFree(c->align_dev);
   if (c->pinned_i32) hipHostFree(c->pinned_i32);
   if (c->pinned_beam) hipHostFree(c->pinned_beam);
   if (c->stream) hipStreamDestroy(c->stream);
@@ -619,8 +620,8 @@ int ttasr_dtw(const float* cost, int32_t n_rows, int32_t n_cols, int32_t* out_ro
   for (int j = 1; j <= n_cols; ++j)
     for (int i = 1; i <= n_rows; ++i) {
       const float c0 = acc[(size_t)(i - 1) * W_ + j - 1], c1 = acc[(size_t)(i - 1) * W_ + j], c2 = acc[(size_t)i * W_ + j - 1];
-      float best; int8_t t;
-      if (c0 < c1 && c0 < c2) { best = c0; t = 0; } else if (c1 < c0 && c1 < c2) { best = c1; t = 1; } else { best = c2; t = 2; }
+      float best;
+      const int8_t t = (int8_t)dtw_step(c0, c1, c2, &best);   // the step the device DTW runs too (align_batch.hpp)
       acc[(size_t)i * W_ + j] = cost[(size_t)(i - 1) * n_cols + j - 1] + best;
       trace[(size_t)i * W_ + j] = t;
     }

@@ -1,0 +1,162 @@
+// libttasr: batched word alignment (one of the engine translation units, see engine_ctx.hpp): the teacher-forced pass over n
+// sequences, the post-processing and DTW kernels of kernels_align.hip behind it, and ttasr_align_batch.  The session's
+// ttasr_session_align (engine_refill.hip) runs the same align_batch_run on its held clips.
+#include "engine_ctx.hpp"
+
+namespace ttasr_detail {
+
+// Everything that can be refused is refused here, before anything is enqueued (the slots are the caller's to check).
+int align_batch_validate(ttasr_ctx* c, const AlignBatch& a) {
+  if (a.n < 1 || a.n > c->maxB) return fail(c, TTASR_E_INVALID, "n %d outside [1, max_batch = %d]", a.n, c->maxB);
+  if (!a.tokens || !a.n_tokens || !a.first_row || !a.num_frames || !a.pairs || !a.out_start)
+    return fail(c, TTASR_E_INVALID, "NULL argument");
+  if (a.medfilt < 1 || a.medfilt > kAlignMaxMedfilt || !(a.medfilt & 1))
+    return fail(c, TTASR_E_INVALID, "medfilt_width %d must be odd and in [1, %d]", a.medfilt, kAlignMaxMedfilt);
+  const int tok_max = std::min(c->cfg.n_text_ctx, c->cfg.n_audio_ctx);
+  if (a.max_tokens < 2 || a.max_tokens > tok_max) return fail(c, TTASR_E_INVALID, "max_tokens %d outside [2, %d]", a.max_tokens, tok_max);
+  if ((int64_t)a.n * a.max_tokens > (int64_t)c->maxB * c->cfg.n_audio_ctx)
+    return fail(c, TTASR_E_INVALID, "%d x %d rows exceed the prefill workspaces (%lld rows)", a.n, a.max_tokens,
+                (long long)c->maxB * c->cfg.n_audio_ctx);
+  if (c->T > 6 * 256) return fail(c, TTASR_E_INVALID, "audio window %d > 1536 frames", c->T);
+  for (int i = 0; i < a.n; ++i) {
+    const int nt = a.n_tokens[i];
+    if (nt < 2 || nt > a.max_tokens) return fail(c, TTASR_E_INVALID, "sequence %d: n_tokens %d outside [2, max_tokens = %d]", i, nt, a.max_tokens);
+    if (a.first_row[i] < 0 || a.first_row[i] > nt - 2) return fail(c, TTASR_E_INVALID, "sequence %d: first_row %d outside [0, %d]", i, a.first_row[i], nt - 2);
+    if (a.num_frames[i] < 0) return fail(c, TTASR_E_INVALID, "sequence %d: num_frames %d < 0", i, a.num_frames[i]);
+    for (int t = 0; t < nt; ++t) {
+      const int tok = a.tokens[(size_t)i * a.max_tokens + t];
+      if (tok < 0 || tok >= c->V) return fail(c, TTASR_E_INVALID, "sequence %d: token outside vocabulary", i);
+    }
+  }
+  if (a.n_pairs < 1 || a.n_pairs > c->cfg.dec_layers * c->H) return fail(c, TTASR_E_INVALID, "n_pairs %d", a.n_pairs);
+  std::vector<char> seen((size_t)c->cfg.dec_layers * c->H, 0);
+  for (int i = 0; i < a.n_pairs; ++i) {
+    const int l = a.pairs[2 * i], h = a.pairs[2 * i + 1];
+    if (l < 0 || l >= c->cfg.dec_layers || h < 0 || h >= c->H) return fail(c, TTASR_E_INVALID, "alignment head (%d, %d)", l, h);
+    if (seen[(size_t)l * c->H + h]) return fail(c, TTASR_E_INVALID, "alignment head (%d, %d) listed twice", l, h);
+    seen[(size_t)l * c->H + h] = 1;
+  }
+  return 0;
+}
+
+// The context's alignment scratch: one device block, grown to the largest request and freed by ttasr_destroy.  A request that
+// cannot be allocated leaves the context without a block (the next call allocates again) and otherwise as it was.
+static int align_scratch(ttasr_ctx* c, size_t bytes) {
+  if (bytes <= c->align_dev_bytes) return 0;
+  HIPCHK(c, hipStreamSynchronize(c->stream));   // the old block may still be read
+  if (c->align_dev) hipFree(c->align_dev);
+  c->align_dev = nullptr; c->align_dev_bytes = 0;
+  const hipError_t e = hipMalloc(&c->align_dev, bytes);
+  if (e != hipSuccess) {
+    c->align_dev = nullptr;
+    (void)hipGetLastError();
+    return fail(c, TTASR_E_NOMEM, "alignment scratch (%zu bytes): %s", bytes, hipGetErrorString(e));
+  }
+  c->align_dev_bytes = bytes;
+  return 0;
+}
+
+// validated arguments -> pass, post-processing, DTW, results on the host.  slot [n]: cross-KV slot of every sequence; pages
+// [n][pages_per_seq]: the self-attention pages the sequence's K/V may use.
+int align_batch_run(ttasr_ctx* c, const AlignBatch& a, const int32_t* slot, const int32_t* pages) {
+  const int n = a.n, npos = a.max_tokens, T_ = c->T, pps = c->pages_per_seq, LH = c->cfg.dec_layers * c->H, R = n * npos;
+  hipStream_t s = c->stream;
+  // host image of the inputs: tokens [n][npos] | AlignSeq [n] | slots [n] | pages [n][pps] | sel [LH]
+  const size_t in_words = (size_t)R + 4 * (size_t)n + n + (size_t)n * pps + LH;
+  std::vector<int32_t> in(in_words, 0);
+  int32_t* h_tok = in.data();
+  AlignSeq* h_seq = (AlignSeq*)(h_tok + R);
+  int32_t* h_slot = (int32_t*)(h_seq + n);
+  int32_t* h_pages = h_slot + n;
+  int32_t* h_sel = h_pages + (size_t)n * pps;
+  int max_rows = 0;
+  size_t lds_words = 0, spill_words = 0;
+  for (int i = 0; i < n; ++i) {
+    memcpy(h_tok + (size_t)i * npos, a.tokens + (size_t)i * npos, (size_t)a.n_tokens[i] * 4);   // padding positions feed token 0
+    AlignSeq& q = h_seq[i];
+    q.first_row = a.first_row[i]; q.n_tokens = a.n_tokens[i]; q.rows = q.n_tokens - 1 - q.first_row;
+    q.frames = std::min(T_, std::max(1, a.num_frames[i] / 2));
+    max_rows = std::max(max_rows, q.rows);
+    const size_t w = dtw_trace_words(q.rows, q.frames);
+    if (w * 4 <= kDtwLdsTraceBytes) lds_words = std::max(lds_words, w); else spill_words = std::max(spill_words, w);
+    h_slot[i] = slot[i];
+  }
+  memcpy(h_pages, pages, (size_t)n * pps * 4);
+  for (int i = 0; i < LH; ++i) h_sel[i] = -1;
+  for (int i = 0; i < a.n_pairs; ++i) h_sel[(size_t)a.pairs[2 * i] * c->H + a.pairs[2 * i + 1]] = i;
+  // device block: inputs | lp [R] | start [R] | stats [n][pairs][2][T] | cost [R][T] | probs [pairs][R][T] | spilled traces
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t o_lp = up(in_words * 4), o_start = o_lp + up((size_t)R * 4), o_stats = o_start + up((size_t)R * 4),
+               o_cost = o_stats + up((size_t)n * a.n_pairs * 2 * T_ * 4), o_probs = o_cost + up((size_t)R * T_ * 4),
+               o_spill = o_probs + up((size_t)a.n_pairs * R * T_ * 4), total = o_spill + up((size_t)n * spill_words * 4);
+  TRY(align_scratch(c, total));
+  char* base = (char*)c->align_dev;
+  const int32_t* d_tok = (const int32_t*)base;
+  const AlignSeq* d_seq = (const AlignSeq*)(d_tok + R);
+  const int32_t* d_slot = (const int32_t*)(d_seq + n);
+  const int32_t* d_pages = d_slot + n;
+  const int32_t* d_sel = d_pages + (size_t)n * pps;
+  float* d_lp = (float*)(base + o_lp);
+  int32_t* d_start = (int32_t*)(base + o_start);
+  float *d_stats = (float*)(base + o_stats), *d_cost = (float*)(base + o_cost), *d_probs = (float*)(base + o_probs);
+  HIPCHK(c, hipMemcpyAsync(base, in.data(), in_words * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemsetAsync(base + o_lp, 0, o_stats - o_lp, s));
+  if (a.out_cost) HIPCHK(c, hipMemsetAsync(d_cost, 0, (size_t)R * T_ * 4, s));
+  // (a) the teacher-forced pass; the residual rows stay in c->x
+  AlignOut al{0, d_sel, d_probs, d_slot, d_tok, d_pages};
+  sched_prefill(c, n, npos, 1, npos, &al);
+  if (a.out_lp) {
+    // raw log p(tokens[t + 1] | tokens[0..t]) of every real row: final LayerNorm + vocabulary projection, max_batch rows at a time
+    for (int i = 0; i < n; ++i)
+      for (int r0 = 0; r0 < a.n_tokens[i] - 1; r0 += c->maxB) {
+        const int m = std::min(c->maxB, a.n_tokens[i] - 1 - r0);
+        const size_t row = (size_t)i * npos + r0;
+        c->cur = s;
+        TT_DISPATCH(c, {
+          launch_layernorm<T>(c->x + row * c->d, c->dlnf_g, c->dlnf_b, (T*)c->dh, m, c->d, s);
+          GemmArgs g = lin_args<T>(c->dh, c->emb, m, c->V, c->d); g.epi.out_f32 = c->logits; g.epi.ldc = c->ldv;
+          sched_dec_gemm(c, g, c->emb_sh);
+        });
+        launch_token_logprob(c->logits, c->ldv, c->V, d_tok + row + 1, d_lp + row, m, s);
+      }
+  }
+  // (b) cost matrices, (c) DTW
+  launch_align_stats(d_probs, d_seq, n, npos, a.n_pairs, T_, d_stats, s);
+  launch_align_cost(d_probs, d_stats, d_seq, n, npos, max_rows, a.n_pairs, T_, a.medfilt, d_cost, s);
+  launch_align_dtw(d_cost, d_seq, n, npos, max_rows, T_, lds_words, (uint32_t*)(base + o_spill), spill_words, d_start, s, c->device);
+  HIPCHK(c, hipMemcpyAsync(a.out_start, d_start, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+  if (a.out_lp) HIPCHK(c, hipMemcpyAsync(a.out_lp, d_lp, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+  if (a.out_cost) HIPCHK(c, hipMemcpyAsync(a.out_cost, d_cost, (size_t)R * T_ * 4, hipMemcpyDeviceToHost, s));
+  if (a.out_weights)   // [n][pairs][npos][T] on the host, [pairs][n][npos][T] on the device
+    for (int i = 0; i < n; ++i)
+      HIPCHK(c, hipMemcpy2DAsync(a.out_weights + (size_t)i * a.n_pairs * npos * T_, (size_t)npos * T_ * 4, d_probs + (size_t)i * npos * T_,
+                                 (size_t)R * T_ * 4, (size_t)npos * T_ * 4, a.n_pairs, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));   // `in` is a stack temporary; the results are on the host
+  HIPCHK(c, hipGetLastError());
+  return TTASR_OK;
+}
+
+}  // namespace ttasr_detail
+
+extern "C" {
+
+int ttasr_align_batch(ttasr_ctx* c, int32_t n, const int32_t* clip, const int32_t* tokens, const int32_t* n_tokens, int32_t max_tokens,
+                      const int32_t* first_row, const int32_t* num_frames, const int32_t* pairs, int32_t n_pairs, int32_t medfilt_width,
+                      int32_t* out_start_frame, float* out_logprob, float* out_cost, float* out_weights) {
+  return guarded(c, [&]() -> int {
+  TRY(check_ready(c, 1));
+  const AlignBatch a{n, tokens, n_tokens, max_tokens, first_row, num_frames, pairs, n_pairs, medfilt_width,
+                     out_start_frame, out_logprob, out_cost, out_weights};
+  TRY(align_batch_validate(c, a));
+  if (!clip) return fail(c, TTASR_E_INVALID, "NULL argument");
+  for (int i = 0; i < n; ++i)
+    if (clip[i] < 0 || clip[i] >= c->B_enc) return fail(c, TTASR_E_INVALID, "sequence %d: clip %d but the encoder state holds %d", i, clip[i], c->B_enc);
+  // sequence i borrows the self-attention pages of row i: any step-level decode state is gone
+  std::vector<int32_t> pages((size_t)n * c->pages_per_seq);
+  for (size_t i = 0; i < pages.size(); ++i) pages[i] = (int32_t)i;
+  c->B_dec = 0;
+  return align_batch_run(c, a, clip, pages.data());
+  });
+}
+
+}  // extern "C"

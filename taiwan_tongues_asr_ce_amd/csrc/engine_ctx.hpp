@@ -20,6 +20,7 @@
 
 #include "../../include/ttasr.h"
 #include "common.hpp"
+#include "align_batch.hpp"
 
 namespace ttasr_detail {
 
@@ -144,6 +145,10 @@ struct ttasr_ctx {
   void* xkv_stage = nullptr;      // [dec_layers][2][maxB][H][T][64] T: the session's encoder writes the admitted clips' cross-KV here
   int32_t* admit_dev = nullptr;   // [maxB][3 + max_prompt_alloc] row-admission table (launch_admit_rows)
   int32_t* sess_sel = nullptr;    // [maxB][9] beam session: entries, temperatures, seeds and results of the independent-row kernel
+
+  // batched alignment (engine_align.hip): ONE device block for the pass's tables, softmax maps, cost matrices and spilled DTW
+  // traces; allocated by the first call, grown to the largest request, freed by ttasr_destroy
+  void* align_dev = nullptr; size_t align_dev_bytes = 0;
 
   int B_mel = 0, B_enc = 0, B_dec = 0;
   std::atomic_flag busy = ATOMIC_FLAG_INIT;  // one call in flight per context: a second concurrent call is refused
@@ -276,10 +281,16 @@ enum EncClass { EC_CONV = 0, EC_LN = 1, EC_QKV = 2, EC_ATTN = 3, EC_OUT = 4, EC_
 // GEMMs go through the encoder dispatch (M = n_seq * npos rows; 256x256 MFMA tiles once M >= 256).
 // Alignment variant (ttasr_align): one sequence of clip `al->clip`; the cross-attention rows of the selected
 // (layer, head) pairs are written to al->probs, and the residual stream is left in c->x for the token log-probs.
+// Batched form (ttasr_align_batch / ttasr_session_align): n_seq sequences padded to npos positions; sequence s reads the
+// cross-KV slot seq_clip[s], its tokens come from `tokens` [n_seq][npos] and its self-attention K/V go to the pages
+// page_table[s][..] (the pass never touches another row's pages); probs is [n_sel][n_seq * npos][T].
 struct AlignOut {
   int clip;
   const int* sel;   // device [dec_layers][H]: index into probs or -1
   float* probs;     // device [n_sel][npos][T]
+  const int* seq_clip = nullptr;          // device [n_seq], batched form only
+  const int32_t* tokens = nullptr;        // device [n_seq][npos], batched form only
+  const int32_t* page_table = nullptr;    // device [n_seq][pages_per_seq], batched form only
 };
 
 // ---- engine_alloc.hip: arenas, weight slots, workspaces, weight intake ----
@@ -303,6 +314,14 @@ void drop_rule_graphs(ttasr_ctx* c);
 // ---- engine_refill.hip: the continuous-batching session (greedy and beam search) ----
 int session_refusal(ttasr_ctx* c);   // TTASR_E_INVALID with a message while a session is open, else 0
 void session_free(ttasr_ctx* c);     // ttasr_destroy: the session's stream, events and pinned memory
+
+// ---- engine_align.hip: the batched alignment pass (ttasr_align_batch, ttasr_session_align) ----
+struct AlignBatch {   // the host arguments of ttasr_align_batch without the clips
+  int n; const int32_t* tokens; const int32_t* n_tokens; int max_tokens; const int32_t* first_row; const int32_t* num_frames;
+  const int32_t* pairs; int n_pairs; int medfilt; int32_t* out_start; float* out_lp; float* out_cost; float* out_weights;
+};
+int align_batch_validate(ttasr_ctx* c, const AlignBatch& a);
+int align_batch_run(ttasr_ctx* c, const AlignBatch& a, const int32_t* slot /*[n]*/, const int32_t* pages /*[n][pages_per_seq]*/);
 
 // ---- engine_search.hip: rules, options, greedy / sampled / beam search ----
 int check_ready(ttasr_ctx* c, int B);

@@ -52,6 +52,10 @@ struct Session {
   std::vector<int64_t> row_clip;   // [maxB] clip id in the row, or -1 (free)
   std::vector<int32_t> row_plen;   // [maxB] prompt length of the row's clip
   std::deque<Done> finished;       // finished clips not yet returned by a poll
+  // hold mode (ttasr_session_hold): a finished clip keeps its unit - row (greedy) or group (beam) - and its cross-KV slot until
+  // ttasr_session_align or ttasr_session_release; its rows are finished rows (done = 1), out of the attention kernels
+  bool hold = false;
+  std::vector<char> held;          // [maxB] greedy: the row's clip has finished and is held (row_clip keeps its id)
   int32_t* pin = nullptr;          // pinned: done | n_sampled | sum_logprob | no_speech [maxB] each, tokens [maxB][max_new], admit table
   size_t pin_words = 0;
   hipStream_t es = nullptr;        // encode stream (== the context's stream when refill_overlap = 0)
@@ -64,7 +68,8 @@ struct Session {
   // hypotheses; per row the hypothesis and its double-precision sum; one page table [maxB][pages_per_seq] with reference counts
   struct Group { int64_t clip = -1; std::vector<int32_t> prompt; int32_t cap = 0; int pos = 0; float ns = 0.f;
                  std::map<std::vector<int>, double> finished;
-                 int mode = 0, rows = 0, sot = 0, max_cand = 1; float temp = 0.f; uint32_t seed = 0; };
+                 int mode = 0, rows = 0, sot = 0, max_cand = 1; float temp = 0.f; uint32_t seed = 0;
+                 int64_t held = -1; };   // hold mode: the finished clip that still owns the group (clip is -1 then)
   enum { BEAM = 0, ROWS = 1 };
   int beam = 0, G = 0, max_cand = 0;
   float patience = 1.f;
@@ -105,7 +110,13 @@ static int n_units(const ttasr_ctx* c, const Session* S) { return S->beam ? S->G
 static int n_free_units(const Session* S) {
   if (!S->beam) return n_free_rows(S);
   int n = 0;
-  for (const Session::Group& g : S->grp) n += g.clip < 0;
+  for (const Session::Group& g : S->grp) n += g.clip < 0 && g.held < 0;
+  return n;
+}
+static int n_held_units(const Session* S) {
+  int n = 0;
+  if (S->beam) { for (const Session::Group& g : S->grp) n += g.held >= 0; }
+  else for (char h : S->held) n += h != 0;
   return n;
 }
 
@@ -184,7 +195,7 @@ static int admit(ttasr_ctx* c, Session* S) {
     // a free group takes the clip: its cross-KV goes to slot g; the search state is host-side and goes out with the next step
     for (int g = 0; g < S->G && (int)S->staged_next < (int)S->staged.size(); ++g) {
       Session::Group& gr = S->grp[g];
-      if (gr.clip >= 0) continue;
+      if (gr.clip >= 0 || gr.held >= 0) continue;
       const int j = (int)S->staged_next++;
       Session::Clip& cl = S->staged[j];
       HIPCHK(c, hipMemcpy2DAsync((char*)c->xkv + (size_t)g * blk, pitch, (const char*)c->xkv_stage + (size_t)j * blk, pitch, blk,
@@ -288,7 +299,7 @@ static int session_begin(ttasr_ctx* c, const ttasr_gen_opts* o, int max_prompt, 
   S->o = *o; S->o.suppress = nullptr; S->o.begin_suppress = nullptr;   // the rules are uploaded; the caller's arrays are not kept
   S->max_prompt = max_prompt;
   S->overlap = c->refill_overlap;
-  S->row_clip.assign(B, -1); S->row_plen.assign(B, 1);
+  S->row_clip.assign(B, -1); S->row_plen.assign(B, 1); S->held.assign(B, 0);
   S->pin_words = (size_t)B * (4 + c->rp.max_new) + (size_t)B * (3 + max_prompt);
   struct Undo { ttasr_ctx* c; Session* s; ~Undo() { if (s) { c->sess = s; session_free(c); } } } undo{c, nullptr};
   HIPCHK(c, hipHostMalloc((void**)&S->pin, S->pin_words * 4));
@@ -537,11 +548,13 @@ static int beam_step(ttasr_ctx* c, Session* S) {
       d.ns = gr.ns;
       S->finished.push_back(std::move(d));
       // the group is free: its page lists go back to the pool, its rows leave the attention kernels
+      // (hold mode: the pages go back, the group and its cross-KV slot stay with the clip until it is aligned or released)
+      if (S->hold) gr.held = gr.clip;
       gr.clip = -1; gr.finished.clear();
       for (int b = 0; b < beam; ++b) {
         const int r = r0 + b;
         std::fill(tbl.begin() + (size_t)r * pps, tbl.begin() + (size_t)(r + 1) * pps, -1);
-        S->done_rows[r] = 1; S->row_clip[r] = -1; S->cur_tok[r] = 0;
+        S->done_rows[r] = 1; S->row_clip[r] = S->hold ? gr.held : -1; S->cur_tok[r] = 0;
       }
       continue;
     }
@@ -679,7 +692,7 @@ static int session_poll(ttasr_ctx* c, int max_steps, int cap, int64_t* ids, int3
   int steps = 0;
   while (S->finished.empty()) {
     TRY(pump(c, S));
-    const int live = n_units(c, S) - n_free_units(S);
+    const int live = n_units(c, S) - n_free_units(S) - n_held_units(S);
     if (live == 0) {
       if (S->enc_pending) {   // nothing to decode until the encode is done
         HIPCHK(c, hipEventSynchronize(S->ev_enc));
@@ -687,6 +700,7 @@ static int session_poll(ttasr_ctx* c, int max_steps, int cap, int64_t* ids, int3
         continue;
       }
       if (S->staged.empty() && S->queue.empty()) break;   // nothing left
+      if (n_free_units(S) == 0) break;   // every unit is held: the host has to align or release before a queued clip can start
       continue;
     }
     if (steps >= max_steps) break;
@@ -711,7 +725,7 @@ static int session_poll(ttasr_ctx* c, int max_steps, int cap, int64_t* ids, int3
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, S->ev_dec0, S->ev_dec1) == hipSuccess) S->dec_ms += ms;
     for (int r = 0; r < B; ++r) {
-      if (S->row_clip[r] < 0 || !p[r]) continue;
+      if (S->row_clip[r] < 0 || !p[r] || S->held[r]) continue;
       Session::Done d;
       d.id = S->row_clip[r];
       const int len = std::min(p[B + r], max_new);
@@ -719,7 +733,7 @@ static int session_poll(ttasr_ctx* c, int max_steps, int cap, int64_t* ids, int3
       memcpy(&d.lp, &p[2 * B + r], 4); memcpy(&d.ns, &p[3 * B + r], 4);
       S->live_row_steps += S->row_plen[r] - 1 + len;
       S->finished.push_back(std::move(d));
-      S->row_clip[r] = -1;
+      if (S->hold) S->held[r] = 1; else S->row_clip[r] = -1;
     }
   }
   int k = 0;
@@ -733,6 +747,87 @@ static int session_poll(ttasr_ctx* c, int max_steps, int cap, int64_t* ids, int3
     ++k;
   }
   *n_out = k;
+  return TTASR_OK;
+}
+
+// ---- hold mode: finished clips keep their unit until the host has aligned or released them ----
+
+// unit (greedy: row, beam: group) that holds clip `id`, or -1
+static int held_unit(const Session* S, int64_t id) {
+  if (S->beam) { for (int g = 0; g < S->G; ++g) if (S->grp[g].held == id) return g; }
+  else for (size_t r = 0; r < S->held.size(); ++r) if (S->held[r] && S->row_clip[r] == id) return (int)r;
+  return -1;
+}
+
+static void release_unit(Session* S, int u) {
+  if (S->beam) {
+    S->grp[u].held = -1;
+    for (int b = 0; b < S->beam; ++b) S->row_clip[(size_t)u * S->beam + b] = -1;
+  } else {
+    S->held[u] = 0; S->row_clip[u] = -1;
+  }
+}
+
+static int session_hold(ttasr_ctx* c, int on) {
+  if (!c) return TTASR_E_INVALID;
+  Session* S = c->sess;
+  if (!S) return fail(c, TTASR_E_INVALID, "no session is open (ttasr_session_begin first)");
+  // the alignment pass borrows the encoder's activation workspaces, which an overlapped encode writes from the second stream
+  if (on && S->overlap) return fail(c, TTASR_E_INVALID, "hold mode is not available with option refill_overlap = 1");
+  S->hold = on != 0;
+  if (!S->hold) {   // nothing stays held that could no longer be released
+    for (int u = 0; u < (S->beam ? S->G : c->maxB); ++u)
+      if (S->beam ? S->grp[u].held >= 0 : S->held[u] != 0) release_unit(S, u);
+  }
+  return TTASR_OK;
+}
+
+// ids -> units; every id must be a held clip and appear once.  Nothing is changed.
+static int held_units(ttasr_ctx* c, Session* S, int n, const int64_t* ids, std::vector<int>& units) {
+  if (!S->hold) return fail(c, TTASR_E_INVALID, "hold mode is off (ttasr_session_hold first)");
+  if (n < 1 || n > c->maxB || !ids) return fail(c, TTASR_E_INVALID, "n %d outside [1, max_batch = %d] or ids NULL", n, c->maxB);
+  units.assign(n, -1);
+  for (int i = 0; i < n; ++i) {
+    units[i] = held_unit(S, ids[i]);
+    if (units[i] < 0) return fail(c, TTASR_E_INVALID, "clip %lld is not held", (long long)ids[i]);
+    for (int j = 0; j < i; ++j) if (ids[j] == ids[i]) return fail(c, TTASR_E_INVALID, "clip %lld listed twice", (long long)ids[i]);
+  }
+  return 0;
+}
+
+static int session_release(ttasr_ctx* c, int n, const int64_t* ids) {
+  if (!c) return TTASR_E_INVALID;
+  Session* S = c->sess;
+  if (!S) return fail(c, TTASR_E_INVALID, "no session is open (ttasr_session_begin first)");
+  std::vector<int> units;
+  TRY(held_units(c, S, n, ids, units));
+  for (int u : units) release_unit(S, u);
+  return TTASR_OK;
+}
+
+// The batched alignment pass (engine_align.hip) over held clips: sequence i reads the cross-KV slot of clip ids[i]'s unit and
+// keeps its self-attention K/V in pages no live row uses - the held row's own (greedy: a row owns its pages for good) or free
+// pool pages (beam: a finished group's page lists are back in the pool, and a held group accounts for beam x pages_per_seq of
+// them).  The pass runs between two decode steps on the decode stream; the clips are released when it has succeeded.
+static int session_align(ttasr_ctx* c, int n, const int64_t* ids, const AlignBatch& a) {
+  if (!c) return TTASR_E_INVALID;
+  Session* S = c->sess;
+  if (!S) return fail(c, TTASR_E_INVALID, "no session is open (ttasr_session_begin first)");
+  std::vector<int> units;
+  TRY(held_units(c, S, n, ids, units));
+  TRY(align_batch_validate(c, a));
+  HIPCHK(c, hipSetDevice(c->device));
+  const int pps = c->pages_per_seq;
+  std::vector<int32_t> slot(units.begin(), units.end()), pages((size_t)n * pps);
+  if (S->beam) {
+    if (S->free_pages.size() < pages.size()) return fail(c, TTASR_E_INVALID, "session align: %zu free pages, %zu needed", S->free_pages.size(), pages.size());
+    std::copy(S->free_pages.end() - (ptrdiff_t)pages.size(), S->free_pages.end(), pages.begin());
+  } else {
+    for (int i = 0; i < n; ++i)
+      for (int p = 0; p < pps; ++p) pages[(size_t)i * pps + p] = units[i] * pps + p;
+  }
+  TRY(align_batch_run(c, a, slot.data(), pages.data()));
+  for (int u : units) release_unit(S, u);
   return TTASR_OK;
 }
 
@@ -820,6 +915,24 @@ int ttasr_session_rows(ttasr_ctx* c, int32_t* row_pos, int32_t* done, int64_t* r
     if (row_clip) memcpy(row_clip, S->row_clip.data(), (size_t)c->maxB * 8);
     return TTASR_OK;
   });
+}
+
+int ttasr_session_hold(ttasr_ctx* c, int32_t on) {
+  return guarded(c, [&]() -> int { return session_hold(c, on); });
+}
+
+int ttasr_session_align(ttasr_ctx* c, int32_t n, const int64_t* ids, const int32_t* tokens, const int32_t* n_tokens, int32_t max_tokens,
+                        const int32_t* first_row, const int32_t* num_frames, const int32_t* pairs, int32_t n_pairs, int32_t medfilt_width,
+                        int32_t* out_start_frame, float* out_logprob, float* out_cost, float* out_weights) {
+  return guarded(c, [&]() -> int {
+    const AlignBatch a{n, tokens, n_tokens, max_tokens, first_row, num_frames, pairs, n_pairs, medfilt_width,
+                       out_start_frame, out_logprob, out_cost, out_weights};
+    return session_align(c, n, ids, a);
+  });
+}
+
+int ttasr_session_release(ttasr_ctx* c, int32_t n, const int64_t* ids) {
+  return guarded(c, [&]() -> int { return session_release(c, n, ids); });
 }
 
 int ttasr_session_end(ttasr_ctx* c) {

@@ -326,7 +326,7 @@ void run_prefill(ttasr_ctx* c, int n_seq, int npos, int seq_per_clip, int max_pr
   hipStream_t s = c->cur = c->stream;
   float* x = c->x;
   void *h = c->h, *qkv = c->qkv, *att = c->att, *mid = c->mid;
-  launch_embed_prefill<T>(c->prompt_dev, max_prompt, 1, n_seq, npos, (const T*)c->emb, (const T*)c->dpos, x, d, s);
+  launch_embed_prefill<T>(al && al->tokens ? al->tokens : c->prompt_dev, max_prompt, 1, n_seq, npos, (const T*)c->emb, (const T*)c->dpos, x, d, s);
   // up to 128 rows (short prompts: a handful of positions x the clips of a pass) the fragment-packed decode GEMM streams each
   // weight once for all rows; beyond that the rows are a real M dimension for the tiled encoder GEMMs
   const bool small = n <= 128 && !c->force_basic && !c->prefill_tiled;
@@ -335,6 +335,7 @@ void run_prefill(ttasr_ctx* c, int n_seq, int npos, int seq_per_clip, int max_pr
   // partial tiles go to the f32 slabs, and the per-row LayerNorm / the cross-attention kernel sum them in slab order (no
   // atomics: bit-reproducible).  A 3-position prompt of 32 clips then costs about 1.3 decode steps instead of 3.
   const bool slabbed = small && sizeof(T) == 2;
+  const bool own_pages = al && al->page_table;   // batched alignment: the sequences' own page lists, not the rows' of the search
   const int64_t slab_cap = (int64_t)16 * c->maxB * 3 * d;   // floats in c->slab
   struct { const float* bias = nullptr; int n_slab = 0; int64_t stride = 0; } pend;
   auto pgemm = [&](const GemmArgs& g, const void* Wsh) {
@@ -381,8 +382,8 @@ void run_prefill(ttasr_ctx* c, int n_seq, int npos, int seq_per_clip, int max_pr
     const DecLayerW& L = c->dec[l];
     ln(L.ln1g, L.ln1b);
     { GemmArgs g = lin_args<T>(h, L.wqkv, n, 3 * d, d); g.epi.bias = L.bqkv; g.epi.out_t = qkv; pgemm(g, L.wqkv_sh); }
-    launch_self_attn_prefill<T>((const T*)qkv, (T*)c->pool, c->page_table, c->pages_per_seq, (int64_t)l * c->pool_layer_elems,
-                                c->identity_pages, (T*)att, n_seq, npos, c->H, s);
+    launch_self_attn_prefill<T>((const T*)qkv, (T*)c->pool, own_pages ? al->page_table : c->page_table, c->pages_per_seq,
+                                (int64_t)l * c->pool_layer_elems, own_pages ? 0 : c->identity_pages, (T*)att, n_seq, npos, c->H, s);
     residual_gemm(att, L.wo, L.wo_sh, L.bo, d);
     ln(L.ln2g, L.ln2b);
     SlabIn sq;   // the query of the cross-attention: K-split too when its consumer can sum slabs (not the alignment pass)
@@ -390,7 +391,10 @@ void run_prefill(ttasr_ctx* c, int n_seq, int npos, int seq_per_clip, int max_pr
       if (!al && npos * seq_per_clip < 32) sq = split_gemm(g, L.wqx_sh, L.bqx, 4);   // >= 32 rows per clip: the MFMA flash pass reads T rows
       if (!sq.n) { g.epi.bias = L.bqx; g.epi.out_t = qkv; pgemm(g, L.wqx_sh); } }  // q reuses the qkv buffer
     const T* Kx = (const T*)c->xkv + (int64_t)l * c->xkv_layer_elems;
-    if (al) {
+    if (al && al->seq_clip) {
+      launch_cross_attn_probs_batch<T>((const T*)qkv, Kx, Kx + c->xkv_which_elems, (T*)att, n_seq, npos, c->H, c->T,
+                                       al->sel + (size_t)l * c->H, al->seq_clip, al->probs, s);
+    } else if (al) {
       const T* Kc = Kx + (int64_t)al->clip * c->H * c->T * 64;
       launch_cross_attn_probs<T>((const T*)qkv, Kc, Kc + c->xkv_which_elems, (T*)att, n, c->H, c->T, al->sel + (size_t)l * c->H,
                                  al->probs, s);

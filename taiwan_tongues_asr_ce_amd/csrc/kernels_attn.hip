@@ -6,6 +6,7 @@
 // Replaces CTranslate2's MultiHeadAttention layer (un-vendored; arithmetic per HF modeling_whisper.py
 // :215-238, 241-356): q arrives pre-scaled by 1/8 (folded into the weights), softmax in f32.
 #include "common.hpp"
+#include "align_batch.hpp"
 #include <cstdarg>
 #include <cstdio>
 #include <type_traits>
@@ -410,7 +411,7 @@ template <typename T, bool NT> __device__ __forceinline__ void load_row(const T*
 template <typename T, bool PROBS, int NWV, int UNROLL, bool NT, int QMODE>
 __global__ __launch_bounds__(NWV * 64) void cross_attn_decode_kernel(const T* q, const T* K, const T* V, T* out, const int32_t* done,
                                                                      int H, int Tk, int kv_div, const int* sel, float* probs, SlabIn sq,
-                                                                     QProj qp) {
+                                                                     QProj qp, const int* seq_clip) {
   constexpr int VEC = RowVec<T>::VEC, LPR = 64 / VEC, RPI = 64 / LPR;
   extern __shared__ float sc[];  // [Tk] scores, then [NWV][64] partial outputs, [2 * NWV] reductions
   // every kernel argument fetched in ONE batch at entry (common.hpp sgpr_pin): the K stream starts one round trip after launch
@@ -424,7 +425,8 @@ __global__ __launch_bounds__(NWV * 64) void cross_attn_decode_kernel(const T* q,
   const int sub = lane % LPR, rin = lane / LPR;
   float* part = sc + Tk;          // [NWV][64]
   float* red = part + NWV * 64;   // [2 * NWV]
-  const int bk = kv_div == 1 ? b : b / kv_div;  // beam search: the kv_div rows of one clip share its cross-KV (never replicated)
+  int bk = kv_div == 1 ? b : b / kv_div;  // beam search: the kv_div rows of one clip share its cross-KV (never replicated)
+  if constexpr (PROBS) { if (seq_clip) bk = seq_clip[bk]; }   // batched alignment: sequence bk reads the cross-KV of its own slot
   const int done_raw = row_done_issue(done, b, K);   // finished row of the batch: see row_done_exit below
   const T* Kp = K + ((int64_t)bk * H + h) * Tk * 64;
   const T* Vp = V + ((int64_t)bk * H + h) * Tk * 64;
@@ -1140,7 +1142,7 @@ void launch_cross_attn_decode(const T* q, const T* K, const T* V, T* out, int B,
   if constexpr (sizeof(T) == 2) {                                                                                                      \
     if (qp.W) {                                                                                                                        \
       hipLaunchKernelGGL((cross_attn_decode_kernel<T, false, 4, 8, NT_, 2>), dim3(H, B), dim3(256), lds, s, q, K, V, out, done, H, Tk, \
-                         kv_div, (const int*)nullptr, (float*)nullptr, sq, qp);                                                        \
+                         kv_div, (const int*)nullptr, (float*)nullptr, sq, qp, (const int*)nullptr);                                  \
       return;                                                                                                                          \
     }                                                                                                                                  \
   }
@@ -1151,9 +1153,9 @@ void launch_cross_attn_decode(const T* q, const T* K, const T* V, T* out, int B,
   do {                                                                                                                                 \
     TTASR_XA_QPROJ(NT_)                                                                                                                \
     if (sq.n > 0) hipLaunchKernelGGL((cross_attn_decode_kernel<T, false, 4, 8, NT_, 1>), dim3(H, B), dim3(256), lds, s, q, K, V, out, done, \
-                                     H, Tk, kv_div, (const int*)nullptr, (float*)nullptr, sq, qp);                                     \
+                                     H, Tk, kv_div, (const int*)nullptr, (float*)nullptr, sq, qp, (const int*)nullptr);               \
     else hipLaunchKernelGGL((cross_attn_decode_kernel<T, false, 4, 8, NT_, 0>), dim3(H, B), dim3(256), lds, s, q, K, V, out, done, H, \
-                            Tk, kv_div, (const int*)nullptr, (float*)nullptr, sq, qp);                                                 \
+                            Tk, kv_div, (const int*)nullptr, (float*)nullptr, sq, qp, (const int*)nullptr);                           \
   } while (0)
   if constexpr (sizeof(T) == 2) {
     if ((g_xattn_variant & 2) && !qp.W) {   // software-pipelined form (default since round 4), 3 rows per lane and batch
@@ -1176,8 +1178,18 @@ template <typename T>
 void launch_cross_attn_probs(const T* q, const T* K, const T* V, T* out, int rows, int H, int Tk, const int* sel, float* probs,
                              hipStream_t s) {
   size_t lds = sizeof(float) * (Tk + 4 * 64 + 8);
-  hipLaunchKernelGGL((cross_attn_decode_kernel<T, true, 4, 8, false, 0>), dim3(H, rows), dim3(256), lds, s, q, K, V, out, (const int32_t*)nullptr, H, Tk, rows, sel, probs, SlabIn{}, QProj{});
+  hipLaunchKernelGGL((cross_attn_decode_kernel<T, true, 4, 8, false, 0>), dim3(H, rows), dim3(256), lds, s, q, K, V, out, (const int32_t*)nullptr, H, Tk, rows, sel, probs, SlabIn{}, QProj{}, (const int*)nullptr);
 }
+template <typename T>
+void launch_cross_attn_probs_batch(const T* q, const T* K, const T* V, T* out, int n_seq, int npos, int H, int Tk, const int* sel,
+                                   const int* seq_clip, float* probs, hipStream_t s) {
+  size_t lds = sizeof(float) * (Tk + 4 * 64 + 8);
+  hipLaunchKernelGGL((cross_attn_decode_kernel<T, true, 4, 8, false, 0>), dim3(H, n_seq * npos), dim3(256), lds, s, q, K, V, out, (const int32_t*)nullptr, H, Tk, npos, sel, probs, SlabIn{}, QProj{}, seq_clip);
+}
+#define TTASR_PROBS_BATCH(T_) \
+  template void launch_cross_attn_probs_batch<T_>(const T_*, const T_*, const T_*, T_*, int, int, int, int, const int*, const int*, float*, hipStream_t)
+TTASR_PROBS_BATCH(float); TTASR_PROBS_BATCH(bf16_t); TTASR_PROBS_BATCH(f16_t);
+#undef TTASR_PROBS_BATCH
 template void launch_cross_attn_probs<float>(const float*, const float*, const float*, float*, int, int, int, const int*, float*,
                                              hipStream_t);
 template void launch_cross_attn_probs<bf16_t>(const bf16_t*, const bf16_t*, const bf16_t*, bf16_t*, int, int, int, const int*, float*,

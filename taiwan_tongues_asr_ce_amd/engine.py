@@ -313,6 +313,23 @@ class Engine:
                                          lp.ctypes.data_as(C.POINTER(C.c_float)) if want_logprob else None), "align")
         return w, (lp[: len(tok) - 1] if want_logprob else None)
 
+    def align_batch(self, clips: Sequence[int], tokens: Sequence[Sequence[int]], first_row: Sequence[int],
+                    num_frames: Sequence[int], heads: Sequence[Tuple[int, int]], medfilt_width: int = 7,
+                    debug: bool = False) -> AlignBatchResult:
+        """Word alignment of len(tokens) teacher-forced sequences in one device pass (ttasr_align_batch): sequence i belongs to
+        the resident clip clips[i] (several may share a clip); first_row[i] is the first token row of its cost matrix,
+        num_frames[i] the clip's length in 10-ms frames.  Normalisation, median filter and DTW run on the device; only the
+        start frames and the token log-probs come back (debug=True: the cost matrices and raw maps too).  Arguments are checked
+        here before the library is called."""
+        packed = _align_batch_args(self, tokens, first_row, num_frames, heads, medfilt_width)
+        cl = np.ascontiguousarray(clips, dtype=np.int32)
+        if cl.shape != (len(tokens),):
+            raise ValueError(f"need one clip index per sequence ({len(tokens)}), got shape {cl.shape}")
+        if cl.min() < 0 or cl.max() >= self.max_batch:
+            raise ValueError(f"clip indices must lie in [0, {self.max_batch})")
+        return _align_batch_call(self, self.lib.ttasr_align_batch, "align_batch", cl.ctypes.data_as(C.POINTER(C.c_int32)), packed,
+                                 debug)
+
     def decode_reset(self, B: int):
         self._check(self.lib.ttasr_decode_reset(self.h, B), "decode_reset")
 
@@ -365,6 +382,78 @@ class Engine:
 
 
 @dataclass
+class AlignBatchResult:
+    """Engine.align_batch / Session.align: per sequence the start frame (encoder frames of 20 ms) of the token each row
+    first_row .. n_tokens - 2 predicts, and log p(tokens[t + 1] | tokens[..t]) for t = 0 .. n_tokens - 2; with debug=True also
+    the cost matrices [rows][F] and the raw attention maps [n_pairs][n_tokens][audio_ctx]."""
+    start_frames: List[np.ndarray]
+    logprobs: List[np.ndarray]
+    costs: Optional[List[np.ndarray]] = None
+    weights: Optional[List[np.ndarray]] = None
+
+
+def _align_batch_args(engine: "Engine", tokens, first_row, num_frames, heads, medfilt_width):
+    """Validates and packs the arguments ttasr_align_batch / ttasr_session_align share (raises ValueError before the library
+    is called) -> (tok [n][max_tokens], n_tokens, first_row, num_frames, pairs)."""
+    n = len(tokens)
+    if n < 1 or n > engine.max_batch:
+        raise ValueError(f"{n} sequences outside [1, max_batch = {engine.max_batch}]")
+    if len(first_row) != n or len(num_frames) != n:
+        raise ValueError(f"need one first_row and one num_frames per sequence ({n}), got {len(first_row)} and {len(num_frames)}")
+    medfilt_width = int(medfilt_width)
+    if not 1 <= medfilt_width <= 15 or medfilt_width % 2 == 0:
+        raise ValueError(f"medfilt_width {medfilt_width} must be odd and in [1, 15]")
+    d = engine.dims
+    tok_max = min(d.n_text_ctx, d.n_audio_ctx)
+    nt = np.asarray([len(t) for t in tokens], dtype=np.int32)
+    if nt.min() < 2 or nt.max() > tok_max:
+        raise ValueError(f"every sequence needs between 2 and {tok_max} tokens, got {nt.min()} .. {nt.max()}")
+    if n * int(nt.max()) > engine.max_batch * d.n_audio_ctx:
+        raise ValueError(f"{n} sequences x {nt.max()} positions exceed the pass's {engine.max_batch * d.n_audio_ctx} rows")
+    fr = np.ascontiguousarray(first_row, dtype=np.int32)
+    nf = np.ascontiguousarray(num_frames, dtype=np.int32)
+    if fr.shape != (n,) or nf.shape != (n,):
+        raise ValueError("first_row and num_frames must be one-dimensional")
+    if np.any(fr < 0) or np.any(fr > nt - 2):
+        raise ValueError("first_row entries must lie in [0, n_tokens - 2]")
+    if nf.min() < 0:
+        raise ValueError("num_frames entries must be >= 0")
+    tok = np.zeros((n, int(nt.max())), dtype=np.int32)
+    for i, t in enumerate(tokens):
+        tok[i, :len(t)] = t
+        if min(t) < 0 or max(t) >= d.vocab:
+            raise ValueError(f"sequence {i}: token outside the vocabulary")
+    pr = np.ascontiguousarray(heads, dtype=np.int32).reshape(-1, 2)
+    if len(pr) < 1:
+        raise ValueError("need at least one alignment head")
+    if np.any(pr < 0) or np.any(pr[:, 0] >= d.dec_layers) or np.any(pr[:, 1] >= d.n_heads):
+        raise ValueError("alignment head outside the decoder")
+    if len({(int(l), int(h)) for l, h in pr}) != len(pr):
+        raise ValueError("an alignment head is listed twice")
+    return tok, nt, fr, nf, pr, medfilt_width
+
+
+def _align_batch_call(engine: "Engine", fn, what: str, lead, packed, debug: bool) -> AlignBatchResult:
+    tok, nt, fr, nf, pr, width = packed
+    n, mt = tok.shape
+    i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+    start = np.zeros((n, mt), dtype=np.int32)
+    lp = np.zeros((n, mt), dtype=np.float32)
+    cost = np.zeros((n, mt, engine.audio_ctx), dtype=np.float32) if debug else None
+    w = np.zeros((n, len(pr), mt, engine.audio_ctx), dtype=np.float32) if debug else None
+    engine._check(fn(engine.h, n, lead, tok.ctypes.data_as(i32p), nt.ctypes.data_as(i32p), mt, fr.ctypes.data_as(i32p),
+                     nf.ctypes.data_as(i32p), pr.ctypes.data_as(i32p), len(pr), width, start.ctypes.data_as(i32p),
+                     lp.ctypes.data_as(f32p), cost.ctypes.data_as(f32p) if debug else None,
+                     w.ctypes.data_as(f32p) if debug else None), what)
+    rows = nt - 1 - fr
+    frames = np.minimum(engine.audio_ctx, np.maximum(1, nf // 2))
+    return AlignBatchResult(
+        [start[i, :rows[i]].copy() for i in range(n)], [lp[i, :nt[i] - 1].copy() for i in range(n)],
+        [cost[i, :rows[i], :frames[i]].copy() for i in range(n)] if debug else None,
+        [w[i, :, :nt[i]].copy() for i in range(n)] if debug else None)
+
+
+@dataclass
 class SessionResult:
     id: int
     tokens: List[int]
@@ -381,6 +470,7 @@ class Session:
         self.max_new_tokens = int(opts.max_new_tokens)
         self.window = 2 * engine.audio_ctx * 160
         self.open = False
+        self.holding = False
         self.pending = 0
         beam = int(beam)
         if not 1 <= beam <= 7:
@@ -552,6 +642,44 @@ class Session:
                 raise TtasrError(f"session idle with {self.pending} clips unfinished")
             out.extend(got)
         return out
+
+    def hold(self, on: bool = True):
+        """Hold mode (ttasr_session_hold): a clip that finishes keeps its row (beam: group) and cross-KV slot until align() or
+        release(); the caller must do one of the two for every clip poll() returns, or queued clips cannot start.  Not
+        available with option refill_overlap = 1.  hold(False) releases whatever is held."""
+        if not self.open:
+            raise TtasrError("session is closed")
+        self.engine._check(self.engine.lib.ttasr_session_hold(self.engine.h, 1 if on else 0), "session_hold")
+        self.holding = bool(on)
+
+    def _ids(self, ids) -> np.ndarray:
+        if not self.open:
+            raise TtasrError("session is closed")
+        if not getattr(self, "holding", False):
+            raise ValueError("hold mode is off (Session.hold() first)")
+        a = np.ascontiguousarray(ids, dtype=np.int64)
+        if a.ndim != 1 or not 1 <= len(a) <= self.engine.max_batch:
+            raise ValueError(f"need between 1 and {self.engine.max_batch} clip ids")
+        if len(set(a.tolist())) != len(a):
+            raise ValueError("a clip id is listed twice")
+        return a
+
+    def align(self, ids: Sequence[int], tokens: Sequence[Sequence[int]], first_row: Sequence[int], num_frames: Sequence[int],
+              heads: Sequence[Tuple[int, int]], medfilt_width: int = 7, debug: bool = False) -> AlignBatchResult:
+        """Engine.align_batch for held clips (ttasr_session_align): sequence i belongs to the held clip ids[i]; the clips are
+        released when the call has succeeded.  Arguments are checked here before the library is called."""
+        a = self._ids(ids)
+        if len(tokens) != len(a):
+            raise ValueError(f"need one token sequence per clip id ({len(a)}), got {len(tokens)}")
+        packed = _align_batch_args(self.engine, tokens, first_row, num_frames, heads, medfilt_width)
+        return _align_batch_call(self.engine, self.engine.lib.ttasr_session_align, "session_align",
+                                 a.ctypes.data_as(C.POINTER(C.c_int64)), packed, debug)
+
+    def release(self, ids: Sequence[int]):
+        """Free held clips without aligning them (ttasr_session_release)."""
+        a = self._ids(ids)
+        self.engine._check(self.engine.lib.ttasr_session_release(self.engine.h, len(a), a.ctypes.data_as(C.POINTER(C.c_int64))),
+                           "session_release")
 
     def rows(self) -> Dict[str, np.ndarray]:
         """The batch's rows now (ttasr_session_rows): position, finished flag (1 = finished or free), clip id (-1 = free)."""

@@ -717,7 +717,9 @@ class WhisperModel:
         continuous=True: one continuous-batching beam session instead of lock-step passes (DESIGN.md "Long-form files in the
         session"): every file keeps one window in flight, a window that fails the thresholds goes back in at the next
         temperature (sampled attempts run in the session too), and a file's next window is submitted as soon as its current
-        one is settled.  Each file gets exactly `transcribe()`'s algorithm.  word_timestamps is not supported there."""
+        one is settled.  Each file gets exactly `transcribe()`'s algorithm.  word_timestamps is not supported there: the
+        session can align now (Session.hold / Session.align, used by transcribe_stream and the streaming backend), but moving
+        this path and transcribe() onto the batched device alignment is a follow-up."""
         eng = self.engine
         if continuous and word_timestamps:
             raise ValueError("word_timestamps=True is not supported with continuous=True (the alignment pass needs the window's "
@@ -870,12 +872,14 @@ class WhisperModel:
     def transcribe_stream(self, clips: Sequence[np.ndarray], language: str = "zh", task: str = "transcribe",
                           without_timestamps: bool = True, max_new_tokens: int = 224,
                           row_max_new: Optional[Sequence[int]] = None, beam_size: int = 1, patience: float = 1.0,
-                          initial_prompt: Optional[str] = None) -> List[List[int]]:
+                          initial_prompt: Optional[str] = None, word_timestamps: bool = False):
         """transcribe_batch's contract (clips <= 30 s each, sampled token ids per clip, input order) for any number of clips,
         through a continuous-batching session: a clip that finishes hands its decode row to the next one instead of waiting for
         the rest of its batch.  row_max_new (optional): one token budget per clip, each in [1, max_new_tokens].
         beam_size > 1: beam search (a clip takes a group of beam_size rows; tokens without EOT, as transcribe_windows decodes
-        them); initial_prompt: previous text in front of <|startoftranscript|>, as transcribe_windows builds it."""
+        them); initial_prompt: previous text in front of <|startoftranscript|>, as transcribe_windows builds it.
+        word_timestamps=True: (tokens, words) per clip, words as transcribe_windows returns them; the session runs in hold mode
+        (a finished clip keeps its row and cross-KV slot) and the clips one poll returned are aligned in one device pass."""
         if len(clips) == 0:
             return []
         eng = self.engine
@@ -900,9 +904,38 @@ class WhisperModel:
         with (eng.session(opts, len(prompt), beam=beam, patience=patience) if beam > 1 else eng.session(opts, len(prompt))) as s:
             ids = s.submit([np.ascontiguousarray(c, dtype=np.float32) for c in clips], [prompt] * len(clips), caps)
             where = {cid: i for i, cid in enumerate(ids)}
-            for r in s.drain():
-                out[where[r.id]] = r.tokens
+            if not word_timestamps:
+                for r in s.drain():
+                    out[where[r.id]] = r.tokens
+                return out  # type: ignore[return-value]
+            s.hold()
+            while s.pending > 0:
+                got = s.poll()
+                if not got:
+                    raise RuntimeError(f"session idle with {s.pending} clips unfinished")
+                words = self._window_words(s, [r.id for r in got], [r.tokens for r in got],
+                                           [len(clips[where[r.id]]) for r in got], language, lang_tok, task)
+                for r, w in zip(got, words):
+                    out[where[r.id]] = (r.tokens, w)
         return out  # type: ignore[return-value]
+
+    def _window_words(self, aligner, refs: Sequence[int], tokens: Sequence[Sequence[int]], n_samples: Sequence[int],
+                      language: str, lang_tok: int, task: str = "transcribe") -> List[List[dict]]:
+        """Words of single-window results, one batched alignment pass (alignment.find_alignment_batch) for all of them:
+        `aligner` is the engine (refs = clip indices of the resident pass) or a session in hold mode (refs = held clip ids).
+        -> per clip [{word, start, end, probability}], seconds from the start of the clip."""
+        st = self.special
+        text = [[t for t in toks if t < st.eot] for toks in tokens]
+        found = alignment.find_alignment_batch(aligner, self.tokenizer, st, list(refs), text, [n // 160 for n in n_samples],
+                                               self.alignment_heads, language=language, lang_token=lang_tok,
+                                               task_token=st.translate if task == "translate" else st.transcribe)
+        out = []
+        for toks, txt, al, n in zip(tokens, text, found, n_samples):
+            # one segment over the window: add_word_timestamps clamps over-long words and merges punctuation as in transcribe()
+            seg = dict(tokens=txt, start=0.0, end=self.window_text(toks, n)[1], eot=st.eot)
+            alignment.add_word_timestamps([seg], al, 0.0)
+            out.append([dict(word=w.word, start=w.start, end=w.end, probability=w.probability) for w in seg["words"]])
+        return out
 
     def _pick_audio_ctx(self, audio_ctx: Union[None, int, str], longest_samples: int) -> int:
         full = self.dims.n_audio_ctx
@@ -918,12 +951,17 @@ class WhisperModel:
 
     def transcribe_windows(self, clips: Sequence[np.ndarray], language: str = "zh", beam_size: int = 5,
                            initial_prompt: Optional[str] = None, without_timestamps: bool = False,
-                           max_new_tokens: int = 224, audio_ctx: Union[None, int, str] = None) -> List[Tuple[str, float]]:
+                           max_new_tokens: int = 224, audio_ctx: Union[None, int, str] = None,
+                           word_timestamps: bool = False) -> List[Tuple[str, float]]:
         """Batched single-window transcription for the streaming path: every clip (<= 30 s) is one row group of the
         same engine pass (beam_size rows per clip sharing its cross-KV).  Returns (text, end_time_seconds) per clip.
 
         audio_ctx (opt-in, SURVEY 8f N2): encode only that many positions (20 ms each) instead of the 30-s window;
-        "auto" = the longest clip of the pass + 0.5 s, rounded up to a multiple of 50.  None keeps Whisper's window."""
+        "auto" = the longest clip of the pass + 0.5 s, rounded up to a multiple of 50.  None keeps Whisper's window.
+
+        word_timestamps=True: (text, end_time_seconds, words) per clip, words = [{word, start, end, probability}] in seconds
+        from the start of the clip; all clips of a pass are aligned in ONE device pass (Engine.align_batch) against the
+        pass's encoder state, reduced audio_ctx included.  (transcribe() and transcribe_many() keep the one-window path.)"""
         eng = self.engine
         beam = max(1, min(beam_size, 7))
         per_pass = max(1, self.max_batch // beam)
@@ -940,8 +978,10 @@ class WhisperModel:
                 opts = eng.gen_opts(min(max_new_tokens, self.dims.n_text_ctx - len(prompt)), timestamps=not without_timestamps,
                                     sot_index=sot_index)
                 res = eng.generate_beam([prompt] * len(chunk), beam, opts) if beam > 1 else eng.generate([prompt] * len(chunk), opts)
-                for c, toks in zip(chunk, res.tokens):
-                    out.append(self.window_text(toks, len(c)))
+                words = (self._window_words(eng, range(len(chunk)), res.tokens, [len(c) for c in chunk], language, lang_tok)
+                         if word_timestamps else None)
+                for k, (c, toks) in enumerate(zip(chunk, res.tokens)):
+                    out.append(self.window_text(toks, len(c)) + ((words[k],) if word_timestamps else ()))
         finally:
             eng.set_audio_ctx(0)   # never leave a reduced window behind: the file-level paths assume the model's 30-s window
         return out

@@ -45,13 +45,18 @@ class BatchedWhisperASR(MI355XWhisperASR):
     `continuous=True` (opt-in) replaces the lock-step passes with one continuous-batching session (WhisperModel engine,
     ttasr_session_begin_beam): a request is submitted as it arrives, takes a free group of beam_size rows and resolves when
     its own search ends, not when the longest clip of its pass does.  max_clips groups of beam_size rows; the full 30-s window
-    is encoded, so it cannot be combined with audio_ctx."""
+    is encoded, so it cannot be combined with audio_ctx.
+
+    `word_timestamps=True` (opt-in, both modes): "words" holds {"word", "start", "end", "probability"} with the client's
+    last_start_time added to start and end, and "duration" is the last word's end, as in the reference's result; the clips of
+    a pass (lock-step) or of a poll (continuous: the session runs in hold mode) are aligned in one device pass."""
 
     def __init__(self, max_clips: int = 6, max_wait_ms: float = 5.0, audio_ctx=None, max_new_tokens: int = 224,
-                 continuous: bool = False, **kwargs):
+                 continuous: bool = False, word_timestamps: bool = False, **kwargs):
         if continuous and audio_ctx is not None:
             raise ValueError("continuous=True encodes the full window: audio_ctx must be None")
         self.continuous = bool(continuous)
+        self.word_timestamps = bool(word_timestamps)
         beam = int(kwargs.pop("beam_size", 5))
         self.audio_ctx = audio_ctx            # None = Whisper's 30-s window; "auto"/int = opt-in short window (N2)
         self.max_new_tokens = max_new_tokens
@@ -103,8 +108,8 @@ class BatchedWhisperASR(MI355XWhisperASR):
             warnings.simplefilter("ignore")
             outs = self.asr_pipeline.transcribe_windows(audios, language="zh", beam_size=kw["beam_size"],
                                                         initial_prompt=kw["initial_prompt"], audio_ctx=self.audio_ctx,
-                                                        max_new_tokens=self.max_new_tokens)
-        return [_window_result(audio, text, end_time) for audio, (text, end_time) in zip(audios, outs)]
+                                                        max_new_tokens=self.max_new_tokens, word_timestamps=self.word_timestamps)
+        return [_window_result(audio, *o) for audio, o in zip(audios, outs)]
 
     def _ensure_session(self):
         if self._cq is None:
@@ -130,6 +135,8 @@ class BatchedWhisperASR(MI355XWhisperASR):
             eng.set_audio_ctx(0)
             opts = eng.gen_opts(min(self.max_new_tokens, model.dims.n_text_ctx - len(prompt)), timestamps=True, sot_index=sot_index)
             with (eng.session(opts, len(prompt), beam=beam) if beam > 1 else eng.session(opts, len(prompt))) as s:
+                if self.word_timestamps:
+                    s.hold()
                 while True:
                     items = [] if pending else [q.get()]        # idle: wait for a request
                     while True:
@@ -145,10 +152,14 @@ class BatchedWhisperASR(MI355XWhisperASR):
                     for audio, last_start, fut, loop in items:
                         a = np.ascontiguousarray(audio[: model.n_window], dtype=np.float32)
                         pending[s.submit([a], [prompt])[0]] = (audio, last_start, fut, loop)
-                    for r in s.poll(max_steps=1 if beam > 1 else 8):
+                    got = s.poll(max_steps=1 if beam > 1 else 8)
+                    sizes = [min(len(pending[r.id][0]), model.n_window) for r in got]
+                    words = (model._window_words(s, [r.id for r in got], [r.tokens for r in got], sizes, "zh", model._lang_token("zh"))
+                             if self.word_timestamps and got else [None] * len(got))
+                    for r, n, w in zip(got, sizes, words):
                         audio, last_start, fut, loop = pending.pop(r.id)
-                        n = min(len(audio), model.n_window)
-                        resolve(fut, loop, self._result_dict(_window_result(audio, *model.window_text(r.tokens, n)), last_start))
+                        res = model.window_text(r.tokens, n) + ((w,) if w is not None else ())
+                        resolve(fut, loop, self._result_dict(_window_result(audio, *res), last_start))
         except Exception as e:  # the reference logs and returns None per request
             logger.error("continuous transcribe failed: %s", e)
         finally:
@@ -158,11 +169,15 @@ class BatchedWhisperASR(MI355XWhisperASR):
     def _result_dict(self, res, last_start) -> Optional[Dict[str, Any]]:
         if res is None:
             return None
-        text, duration = res
+        text, duration = res[0], res[1]
+        words = [{"word": w["word"], "start": w["start"] + last_start, "end": w["end"] + last_start, "probability": w["probability"]}
+                 for w in (res[2] if len(res) > 2 else [])]
+        if words:
+            duration = res[2][-1]["end"]
         if self.text_filter is not None:
             filtered = self.text_filter(text)
             text = text if filtered is None else filtered
-        return {"language": "zh", "language_probability": 1.0, "final": True, "text": text, "duration": duration, "words": []}
+        return {"language": "zh", "language_probability": 1.0, "final": True, "text": text, "duration": duration, "words": words}
 
     async def transcribe(self, client) -> Optional[Dict[str, Any]]:
         try:
@@ -195,6 +210,8 @@ class BatchedWhisperASR(MI355XWhisperASR):
             self._worker_task = None
 
 
-def _window_result(audio: np.ndarray, text: str, end_time: float) -> Optional[Tuple[str, float]]:
-    """(text, end_time) of one request, its end capped at the audio's length; None when nothing was said."""
-    return (text, min(end_time, len(audio) / 16000.0)) if text.strip() else None
+def _window_result(audio: np.ndarray, text: str, end_time: float, words: Optional[list] = None) -> Optional[tuple]:
+    """(text, end_time[, words]) of one request, its end capped at the audio's length; None when nothing was said."""
+    if not text.strip():
+        return None
+    return (text, min(end_time, len(audio) / 16000.0)) + ((words,) if words is not None else ())
