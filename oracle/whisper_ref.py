@@ -192,16 +192,44 @@ def _sat(y: torch.Tensor) -> torch.Tensor:
     return y if _ACT_CLAMP is None else y.clamp(-_ACT_CLAMP, _ACT_CLAMP)
 
 
+# Rounding of STORED activations (test-side switch, default off).  A 16-bit engine keeps the input and the output of every linear
+# layer in its storage type; `with activation_rounding(torch.bfloat16):` rounds both at those places (and the input of the tied
+# vocabulary projection, whose f32 output the engine keeps) while all arithmetic stays f32.  The distance between this run and the
+# plain one measures how sensitive a given geometry is to 16-bit storage, independently of any engine
+# (tests/test_gpu_geometry_sweep.py derives its fall-back bounds from it).
+_ACT_ROUND: Optional[torch.dtype] = None
+
+
+class activation_rounding:
+    def __init__(self, dtype: Optional[torch.dtype]):
+        self.dtype = dtype
+
+    def __enter__(self):
+        global _ACT_ROUND
+        self.prev = _ACT_ROUND
+        _ACT_ROUND = self.dtype
+        return self
+
+    def __exit__(self, *exc):
+        global _ACT_ROUND
+        _ACT_ROUND = self.prev
+        return False
+
+
+def _rnd(y: torch.Tensor) -> torch.Tensor:
+    return y if _ACT_ROUND is None else y.to(_ACT_ROUND).float()
+
+
 def _lin(x: torch.Tensor, W: Dict[str, torch.Tensor], p: str, scale: Optional[float] = None, dec_residual: bool = False
          ) -> torch.Tensor:
     """dec_residual: this is a decoder out-proj / fc2 (its output is added to the residual stream)."""
-    y = x @ W[p + ".weight"].t()
+    y = _rnd(x) @ W[p + ".weight"].t()
     b = W.get(p + ".bias")
     if b is not None:
         y = y + b
     if scale is not None:
         y = y * scale
-    return y if (dec_residual and not _ACT_CLAMP_DEC_RESIDUAL) else _sat(y)
+    return _rnd(y if (dec_residual and not _ACT_CLAMP_DEC_RESIDUAL) else _sat(y))
 
 
 def _split_heads(x: torch.Tensor, H: int) -> torch.Tensor:
@@ -317,7 +345,7 @@ def decoder_forward(tokens: torch.Tensor, cache: SelfCache, xkv, W: Dict[str, to
         h = _ln(x, W[p + ".final_layer_norm.weight"], W[p + ".final_layer_norm.bias"])
         x = x + _lin(_gelu(_lin(h, W, p + ".fc1")), W, p + ".fc2", dec_residual=True)
     x = _ln(x, W["model.decoder.layer_norm.weight"], W["model.decoder.layer_norm.bias"])
-    return x @ W["model.decoder.embed_tokens.weight"].t()  # proj_out tied, [HF-M]:965,970
+    return _rnd(x) @ W["model.decoder.embed_tokens.weight"].t()  # proj_out tied, [HF-M]:965,970
 
 
 # --------------------------------------------------------------------------------------------------
