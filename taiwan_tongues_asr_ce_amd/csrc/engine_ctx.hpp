@@ -21,6 +21,7 @@
 #include "../../include/ttasr.h"
 #include "common.hpp"
 #include "align_batch.hpp"
+#include "beam_pages.hpp"
 
 namespace ttasr_detail {
 
@@ -131,8 +132,10 @@ struct ttasr_ctx {
   // beam search (round 6): every per-position host <-> device exchange goes through ONE pinned block - page tables, fed tokens,
   // row histories and copy-on-write pairs out, top-k candidates back - so the copies are truly asynchronous (a pageable source
   // makes hipMemcpyAsync stage and block: measured ~0.5 ms of host time per position in round 5's loop) and a searching position
-  // costs ONE stream synchronisation instead of two
-  char* pinned_beam = nullptr; size_t pinned_beam_bytes = 0;
+  // costs ONE stream synchronisation instead of two.  The beam session's steps use the same block (BeamExchange below carves
+  // it for either search): a context never runs a static search while a session is open (session_refusal).  Allocated by the
+  // first search for the largest one this context can run, freed by ttasr_destroy.
+  char* pinned_beam = nullptr;
   float beam_prof_ms[4]{0, 0, 0, 0};   // last beam search: host time enqueueing, waiting for the GPU, selecting candidates; positions
   int max_new_alloc = 0, max_prompt_alloc = 0;
 
@@ -329,16 +332,37 @@ int upload_rules(ttasr_ctx* c, const ttasr_gen_opts* o, int max_prompt);
 int commit_rules(ttasr_ctx* c, const RuleParams& old);
 int set_option(ttasr_ctx* c, const std::string& key, int v);
 int reset_search(ttasr_ctx* c, int B);
+// One prompt of a call: `len` tokens at `row`, 1 <= len <= max_prompt with room left in the text context, every id inside the
+// vocabulary and, where the no-speech probability is wanted, *sot inside the prompt (sot = nullptr: not wanted).  i names the
+// prompt in the error text.
+int check_prompt(ttasr_ctx* c, int i, const int32_t* row, int len, int max_prompt, const int32_t* sot);
 int generate_rows(ttasr_ctx* c, int R, int rows_per_clip, const int32_t* prompt, const int32_t* prompt_len, int max_prompt,
                   const ttasr_gen_opts* o, float temperature, uint32_t seed, int32_t* out_tokens, int32_t* out_len, float* out_lp,
                   float* out_ns, const int32_t* row_cap = nullptr /*host [R] per-row token budgets, each in [1, max_new_tokens]*/);
 bool beam_select(const std::vector<std::vector<int>>& seqs, const std::vector<double>& sums, int r0, int beam, int K,
                  const float* lp, const int32_t* id, int eot, int max_cand, std::map<std::vector<int>, double>& finished,
-                 std::vector<std::vector<int>>& nseq, std::vector<double>& nsum, std::vector<int>& src,
-                 int stride = 0 /*row stride of lp / id: 0 = K*/);
+                 std::vector<std::vector<int>>& nseq, std::vector<double>& nsum, std::vector<int>& src, int stride /*of the rows of lp / id*/);
 int sample_pick(const float* lp, const int32_t* len, int n);
 int beam_pick(const std::map<std::vector<int>, double>& finished, const std::vector<std::vector<int>>& seqs,
               const std::vector<double>& sums, int r0, int beam, int eot, int max_new, int32_t* out, double* out_sum);
+// The pinned exchange block of one beam position (ttasr_ctx::pinned_beam) carved for R rows, K candidates per row: out go the
+// page tables [R][pps], fed tokens, positions and finished flags [R], row histories [4][R] and copy-on-write pairs [2 R]; back
+// come the candidates lp / id [R][K] and the no-speech values [R].  The session's independent-row kernel adds entries [4 R],
+// temperatures [R] and seeds [R] out (contiguous in this order: they go out in one copy) and results [3 R] back.
+struct BeamExchange {
+  int32_t *tbl, *tok, *pos, *done, *state, *pairs; float* lp; int32_t* id; float* ns;
+  int32_t* ent; float* temp; uint32_t* seed; float* sel;
+};
+inline size_t beam_exchange_words(int R, int pps, int K) { return (size_t)R * (pps + 19 + 2 * K); }
+int beam_exchange(ttasr_ctx* c, int R, int K, BeamExchange& x);   // allocates the block on first use
+inline BeamRowState beam_row_state(const ttasr_ctx* c, int R) {
+  return BeamRowState{c->row_state, c->row_state + R, c->row_state + 2 * R, c->row_state + 3 * R, c->mask_dev};
+}
+// the steps both searches enqueue alike around the decoder step: the copy-on-write page copies, the row histories the candidate
+// kernels apply the rules from (length, last, penultimate, last timestamp), and the candidates of every row with their way back
+int enqueue_page_copies(ttasr_ctx* c, const std::vector<int32_t>& pairs, const BeamExchange& x);
+int enqueue_row_histories(ttasr_ctx* c, const std::vector<std::vector<int>>& seqs, int R, int timestamp_begin, const BeamExchange& x);
+int enqueue_candidates(ttasr_ctx* c, int R, int K, bool no_speech, const BeamExchange& x);
 int beam_search_impl(ttasr_ctx* c, int32_t A, int32_t beam, const int32_t* prompt, int32_t max_prompt, const int32_t* plens,
                      const int32_t* sots, const ttasr_gen_opts* o, float patience, int32_t* out_tokens, int32_t* out_len,
                      float* out_lp, float* out_ns);

@@ -16,7 +16,9 @@
 // search runs on the host as in beam_search_impl: every step is the logits-only decode step (mode 1, per-row positions, loaded
 // page tables) plus the candidate kernel, with ONE host exchange: page tables, fed tokens, positions, finished flags, history and
 // copy-on-write pairs go out from one pinned block, the top-k candidates come back, and the shared selection code
-// (beam_select / beam_pick) advances every searching group.  Positions belong to the host; nothing on the device advances them.
+// (beam_select / beam_pick) advances every searching group.  The page book (BeamPages), the pinned block (BeamExchange) and the
+// history / candidate enqueues are beam_search_impl's own; only the loop around them differs.  Positions belong to the host;
+// nothing on the device advances them.
 //
 // A group has a MODE, fixed when a clip is admitted: BEAM (temperature 0, rows > 1, and every clip of ttasr_session_submit) is
 // the search above; ROWS (ttasr_session_submit_windows with temperature 0 and one row: greedy; temperature > 0: `rows`
@@ -25,7 +27,6 @@
 // rows have ended; the pick is ttasr_generate_sample's (sample_pick).  Window clips (ttasr_session_submit_windows) carry the
 // samples their window's STFT reads and the geometry of ttasr_log_mel_windows; a pass that holds one runs the mel in window form.
 #include "engine_ctx.hpp"
-#include <cassert>
 #include <chrono>
 #include <cmath>
 #include <deque>
@@ -65,7 +66,7 @@ struct Session {
   int64_t steps = 0, polls = 0, encodes = 0, clips_encoded = 0, live_row_steps = 0;
   double enc_ms = 0, dec_ms = 0;
   // beam mode (beam > 0): G groups of `beam` rows; per group the clip, its prompt, budget, position, no-speech value and finished
-  // hypotheses; per row the hypothesis and its double-precision sum; one page table [maxB][pages_per_seq] with reference counts
+  // hypotheses; per row the hypothesis and its double-precision sum; one page book for all groups
   struct Group { int64_t clip = -1; std::vector<int32_t> prompt; int32_t cap = 0; int pos = 0; float ns = 0.f;
                  std::map<std::vector<int>, double> finished;
                  int mode = 0, rows = 0, sot = 0, max_cand = 1; float temp = 0.f; uint32_t seed = 0;
@@ -77,8 +78,8 @@ struct Session {
   std::vector<Group> grp;
   std::vector<std::vector<int>> seqs;
   std::vector<double> sums;
-  std::vector<int32_t> tbl, refcnt, free_pages, cur_tok, done_rows, pairs;
-  int32_t* bpin = nullptr;         // pinned exchange block of a beam step (see beam_step)
+  BeamPages pages;
+  std::vector<int32_t> cur_tok, done_rows, pairs;
 };
 
 int session_refusal(ttasr_ctx* c) {
@@ -92,7 +93,6 @@ void session_free(ttasr_ctx* c) {
   if (S->es && S->es != c->stream) { hipStreamSynchronize(S->es); hipStreamDestroy(S->es); }
   for (hipEvent_t e : {S->ev_enc0, S->ev_enc, S->ev_copy, S->ev_dec0, S->ev_dec1}) if (e) hipEventDestroy(e);
   if (S->pin) hipHostFree(S->pin);
-  if (S->bpin) hipHostFree(S->bpin);
   delete S;
   c->sess = nullptr;
   c->session_rows = false;
@@ -350,19 +350,14 @@ static int session_begin_beam(ttasr_ctx* c, const ttasr_gen_opts* o, int max_pro
   if (!(patience > 0.f)) return fail(c, TTASR_E_INVALID, "patience %g must be > 0", patience);
   TRY(session_begin(c, o, max_prompt, 0.f));   // rules, buffers, streams; every row free (done = 1)
   Session* S = c->sess;
-  const int G = c->maxB / beam, R = G * beam, pps = c->pages_per_seq, K = beam + 1;
+  const int G = c->maxB / beam, R = G * beam;
   S->beam = beam; S->G = G; S->max_cand = std::max(1, (int)std::lround(beam * patience)); S->patience = patience;
   S->grp.assign(G, Session::Group{});
   S->seqs.assign(R, {}); S->sums.assign(R, 0.0); S->fsums.assign(R, 0.f);
-  S->tbl.assign((size_t)c->maxB * pps, -1); S->refcnt.assign((size_t)c->maxB * pps, 0);
-  S->free_pages.clear();
-  for (int p = c->maxB * pps - 1; p >= 0; --p) S->free_pages.push_back(p);
+  S->pages.reset(R, c->pages_per_seq, c->maxB * c->pages_per_seq);
   S->cur_tok.assign(R, 0); S->done_rows.assign(R, 1);
-  // [page tables R x pps | fed tokens R | positions R | done R | histories 4 R | page pairs 2 R] out, [lp R x K | ids R x K | no-speech R] back,
-  // then the independent-row kernel's [entries 4 R | temperatures R | seeds R] out and [results 3 R] back
-  const size_t words = (size_t)R * pps + 9 * (size_t)R + 2 * (size_t)R * K + R + 9 * (size_t)R;
-  const hipError_t e = hipHostMalloc((void**)&S->bpin, words * 4);
-  if (e != hipSuccess) { S->bpin = nullptr; session_free(c); return fail(c, TTASR_E_HIP, "hipHostMalloc: %s", hipGetErrorString(e)); }
+  BeamExchange x;
+  if (beam_exchange(c, R, beam + 1, x) != 0) { session_free(c); return TTASR_E_HIP; }   // the steps' pinned block exists from here on
   if (!c->sess_sel && dalloc(c, &c->sess_sel, (size_t)c->maxB * 9 * 4) != 0) { session_free(c); return TTASR_E_HIP; }
   c->kv_div = beam; c->identity_pages = 0;   // group g reads cross-KV slot g; rows read their own (shared) page lists
   return TTASR_OK;
@@ -372,44 +367,26 @@ static int session_begin_beam(ttasr_ctx* c, const ttasr_gen_opts* o, int max_pro
 // kernel (BEAM groups) and the independent-row kernel (ROWS groups), ONE synchronisation, then selection, re-indexing and the
 // finished groups' results on the host.
 static int beam_step(ttasr_ctx* c, Session* S) {
-  const int beam = S->beam, G = S->G, R = G * beam, pps = c->pages_per_seq, K = beam + 1, n_pages = c->maxB * pps;
+  const int beam = S->beam, G = S->G, R = G * beam, pps = c->pages_per_seq, K = beam + 1;
   const ttasr_gen_opts& o = S->o;
   hipStream_t s = c->stream;
-  std::vector<int32_t>& tbl = S->tbl;
-  // 1. the page each live row writes must exist and be private to the row.  The pool never runs dry: a row holds at most pps
-  // pages (positions < n_text_ctx), at most maxB rows hold pages, the pool has maxB * pps, and a page is back on the free list
-  // as soon as no row references it (rebuilt below; a finished group drops its rows' lists).
+  // 1. the page each live row writes must exist and be private to the row.  The pool should never run dry: a row holds at most
+  // pps pages (positions < n_text_ctx), at most maxB rows hold pages, the pool has maxB * pps, and a page is back on the free
+  // list as soon as no row references it (a finished group drops its rows' lists).
   S->pairs.clear();
   bool any_sampling = false, any_ns = false;
   for (int g = 0; g < G; ++g) {
     const Session::Group& gr = S->grp[g];
     if (gr.clip < 0) continue;
-    const int j = gr.pos / 16;
-    for (int b = 0; b < beam; ++b) {
-      int32_t& pg = tbl[(size_t)(g * beam + b) * pps + j];
-      if (gr.pos % 16 == 0 || pg < 0) {
-        assert(!S->free_pages.empty());
-        pg = S->free_pages.back(); S->free_pages.pop_back(); S->refcnt[pg] = 1;
-      } else if (S->refcnt[pg] > 1) {
-        assert(!S->free_pages.empty());
-        const int32_t np = S->free_pages.back(); S->free_pages.pop_back();
-        S->pairs.push_back(pg); S->pairs.push_back(np);
-        S->refcnt[pg]--; S->refcnt[np] = 1; pg = np;
-      }
-    }
+    for (int b = 0; b < beam; ++b)
+      if (!S->pages.make_private(g * beam + b, gr.pos, S->pairs)) return fail(c, TTASR_E_NOMEM, "KV page pool exhausted");
     if (gr.mode != Session::BEAM) continue;
     any_sampling |= gr.pos + 1 >= (int)gr.prompt.size();
     any_ns |= o.no_speech >= 0 && gr.pos == gr.sot;
   }
-  // 2. the step's input, staged in the pinned block (unused table entries clamped to a valid page id)
-  int32_t* const pb = S->bpin;
-  int32_t *const p_up = pb, *const p_tok = p_up + (size_t)R * pps, *const p_pos = p_tok + R, *const p_done = p_pos + R,
-          *const h_state = p_done + R, *const p_pairs = h_state + 4 * R, *const h_id = p_pairs + 2 * R + R * K;
-  float *const h_lp = (float*)(p_pairs + 2 * R), *const h_ns = (float*)(h_id + R * K);
-  int32_t* const p_ent = (int32_t*)(h_ns + R);
-  float* const p_temp = (float*)(p_ent + 4 * R);
-  uint32_t* const p_seed = (uint32_t*)(p_temp + R);
-  float* const h_sel = (float*)(p_seed + R);
+  // 2. the step's input, staged in the pinned block
+  BeamExchange x;
+  TRY(beam_exchange(c, R, K, x));
   // the rows of ROWS groups that need the independent-row kernel: past their prompt and not finished (choose), or the first row
   // at the group's <|startoftranscript|> position (no-speech)
   int n_ent = 0;
@@ -421,59 +398,40 @@ static int beam_step(ttasr_ctx* c, Session* S) {
       const int r = g * beam + b;
       const int flags = (past && !S->done_rows[r] ? 1 : 0) | (ns_here && b == 0 ? 2 : 0);
       if (!flags) continue;
-      int32_t* e = p_ent + 4 * n_ent;
+      int32_t* e = x.ent + 4 * n_ent;
       e[0] = r; e[1] = gr.pos; e[2] = b; e[3] = flags;
-      p_temp[n_ent] = gr.temp; p_seed[n_ent] = gr.seed;
+      x.temp[n_ent] = gr.temp; x.seed[n_ent] = gr.seed;
       ++n_ent;
     }
   }
-  for (size_t i = 0; i < (size_t)R * pps; ++i) p_up[i] = tbl[i] < 0 ? 0 : tbl[i];
+  S->pages.write_upload(x.tbl);
   for (int r = 0; r < R; ++r) {
     const Session::Group& gr = S->grp[r / beam];
-    p_tok[r] = S->cur_tok[r]; p_pos[r] = gr.clip < 0 ? 0 : gr.pos; p_done[r] = S->done_rows[r];
+    x.tok[r] = S->cur_tok[r]; x.pos[r] = gr.clip < 0 ? 0 : gr.pos; x.done[r] = S->done_rows[r];
   }
-  HIPCHK(c, hipMemcpyAsync(c->page_table, p_up, (size_t)R * pps * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(c->st.cur_tok, p_tok, (size_t)R * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(c->row_pos, p_pos, (size_t)R * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(c->st.done, p_done, (size_t)R * 4, hipMemcpyHostToDevice, s));
-  if (!S->pairs.empty()) {
-    memcpy(p_pairs, S->pairs.data(), S->pairs.size() * 4);
-    HIPCHK(c, hipMemcpyAsync(c->pairs_dev, p_pairs, S->pairs.size() * 4, hipMemcpyHostToDevice, s));
-    TT_DISPATCH(c, launch_copy_pages<T>((T*)c->pool, c->pairs_dev, (int)S->pairs.size() / 2, c->cfg.dec_layers, c->H, c->pool_layer_elems, s));
-  }
+  HIPCHK(c, hipMemcpyAsync(c->page_table, x.tbl, (size_t)R * pps * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->st.cur_tok, x.tok, (size_t)R * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->row_pos, x.pos, (size_t)R * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->st.done, x.done, (size_t)R * 4, hipMemcpyHostToDevice, s));
+  TRY(enqueue_page_copies(c, S->pairs, x));
   const bool topk = any_sampling || any_ns;
-  if (topk || n_ent > 0) {   // the row histories the candidate and independent-row kernels apply the rules from
-    for (int r = 0; r < R; ++r) {
-      int last = -1, pen = -1, lts = -1;
-      for (int t : S->seqs[r]) { pen = last; last = t; if (t >= o.timestamp_begin) lts = t; }
-      h_state[r] = (int)S->seqs[r].size(); h_state[R + r] = last; h_state[2 * R + r] = pen; h_state[3 * R + r] = lts;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->row_state, h_state, (size_t)4 * R * 4, hipMemcpyHostToDevice, s));
-  }
+  if (topk || n_ent > 0) TRY(enqueue_row_histories(c, S->seqs, R, o.timestamp_begin, x));
   // device layout of the independent-row block (c->sess_sel): entries [4 R] | temperatures [R] | seeds [R] | results [3 R]
   int32_t* const d_ent = c->sess_sel;
-  float* const d_temp = (float*)(d_ent + 4 * R);
-  uint32_t* const d_seed = (uint32_t*)(d_temp + R);
-  float* const d_out = (float*)(d_seed + R);
+  float* const d_out = (float*)(d_ent + 6 * R);
   if (n_ent > 0) {   // entries, temperatures and seeds are contiguous in both blocks: one copy
-    memmove(p_ent + 4 * n_ent, p_temp, (size_t)n_ent * 4);
-    memmove(p_ent + 5 * n_ent, p_seed, (size_t)n_ent * 4);
-    HIPCHK(c, hipMemcpyAsync(d_ent, p_ent, (size_t)6 * n_ent * 4, hipMemcpyHostToDevice, s));
+    memmove(x.ent + 4 * n_ent, x.temp, (size_t)n_ent * 4);
+    memmove(x.ent + 5 * n_ent, x.seed, (size_t)n_ent * 4);
+    HIPCHK(c, hipMemcpyAsync(d_ent, x.ent, (size_t)6 * n_ent * 4, hipMemcpyHostToDevice, s));
   }
   // 3. the decoder step (logits only) and, behind it, the candidates of every row and the choices of the independent rows
   HIPCHK(c, hipEventRecord(S->ev_dec0, s));
   TRY(step_graph(c, R, 1));
-  const BeamRowState bs{c->row_state, c->row_state + R, c->row_state + 2 * R, c->row_state + 3 * R, c->mask_dev};
-  if (topk) {
-    launch_beam_topk(c->logits, bs, c->rp, R, K, c->topk_lp, c->topk_id, any_ns ? c->st.no_speech : nullptr, s);
-    HIPCHK(c, hipMemcpyAsync(h_lp, c->topk_lp, (size_t)R * K * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(h_id, c->topk_id, (size_t)R * K * 4, hipMemcpyDeviceToHost, s));
-    if (any_ns) HIPCHK(c, hipMemcpyAsync(h_ns, c->st.no_speech, (size_t)R * 4, hipMemcpyDeviceToHost, s));
-  }
+  if (topk) TRY(enqueue_candidates(c, R, K, any_ns, x));
   if (n_ent > 0) {
     const SessRowsArgs sa{d_ent, (const float*)(d_ent + 4 * n_ent), (const uint32_t*)(d_ent + 5 * n_ent), d_out};
-    launch_session_rows_select(c->logits, bs, c->rp, sa, n_ent, s);
-    HIPCHK(c, hipMemcpyAsync(h_sel, d_out, (size_t)3 * n_ent * 4, hipMemcpyDeviceToHost, s));
+    launch_session_rows_select(c->logits, beam_row_state(c, R), c->rp, sa, n_ent, s);
+    HIPCHK(c, hipMemcpyAsync(x.sel, d_out, (size_t)3 * n_ent * 4, hipMemcpyDeviceToHost, s));
   }
   HIPCHK(c, hipEventRecord(S->ev_dec1, s));
   HIPCHK(c, hipStreamSynchronize(s));   // the one synchronisation of the step
@@ -487,34 +445,32 @@ static int beam_step(ttasr_ctx* c, Session* S) {
     Session::Group& gr = S->grp[g];
     searching[g] = gr.clip >= 0 && gr.pos + 1 >= (int)gr.prompt.size();
     const bool beam_search = searching[g] && gr.mode == Session::BEAM;
-    if (gr.clip >= 0 && gr.mode == Session::BEAM && any_ns && gr.pos == gr.sot) gr.ns = h_ns[g * beam];
+    if (gr.clip >= 0 && gr.mode == Session::BEAM && any_ns && gr.pos == gr.sot) gr.ns = x.ns[g * beam];
     int b0 = 0;
     if (beam_search) {
-      if (!beam_select(S->seqs, S->sums, g * beam, gr.rows, gr.rows + 1, h_lp, h_id, o.eot, gr.max_cand, gr.finished, nseq, nsum, src, K))
+      if (!beam_select(S->seqs, S->sums, g * beam, gr.rows, gr.rows + 1, x.lp, x.id, o.eot, gr.max_cand, gr.finished, nseq, nsum, src, K))
         return fail(c, TTASR_E_INVALID, "beam search: no live candidate (every token masked)");
       b0 = gr.rows;
     }
     for (int b = b0; b < beam; ++b) { const int r = g * beam + b; nseq.push_back(S->seqs[r]); nsum.push_back(S->sums[r]); src.push_back(r); }
   }
-  std::vector<int32_t> ntbl((size_t)c->maxB * pps, -1);
-  for (int r = 0; r < R; ++r) memcpy(&ntbl[(size_t)r * pps], &tbl[(size_t)src[r] * pps], (size_t)pps * 4);
-  tbl.swap(ntbl);
+  S->pages.reindex(src);
   S->seqs.swap(nseq); S->sums.swap(nsum);
   // the independent rows' choices: the token, the f32 sum in the order select_body adds, EOT or the budget end the row
   std::vector<int> live_rows(G, 0);
   for (int g = 0; g < G; ++g)
     for (int b = 0; b < beam; ++b) live_rows[g] += !S->done_rows[g * beam + b];
   for (int e = 0; e < n_ent; ++e) {
-    const int32_t* en = p_ent + 4 * e;   // (the temperatures and seeds moved behind the entries; the entries stayed)
+    const int32_t* en = x.ent + 4 * e;   // (the temperatures and seeds moved behind the entries; the entries stayed)
     const int r = en[0];
     Session::Group& gr = S->grp[r / beam];
-    if (en[3] & 2) gr.ns = h_sel[3 * e + 2];
+    if (en[3] & 2) gr.ns = x.sel[3 * e + 2];
     if (!(en[3] & 1)) continue;
     int choice;
-    memcpy(&choice, &h_sel[3 * e], 4);
+    memcpy(&choice, &x.sel[3 * e], 4);
     if (choice < 0 || choice >= c->V) return fail(c, TTASR_E_INVALID, "session row %d: no live token (every token masked)", r);
     S->seqs[r].push_back(choice);
-    S->fsums[r] += h_sel[3 * e + 1];
+    S->fsums[r] += x.sel[3 * e + 1];
     if (choice == o.eot || (int)S->seqs[r].size() >= gr.cap) S->done_rows[r] = 1;
   }
   for (int g = 0; g < G; ++g) {
@@ -553,7 +509,7 @@ static int beam_step(ttasr_ctx* c, Session* S) {
       gr.clip = -1; gr.finished.clear();
       for (int b = 0; b < beam; ++b) {
         const int r = r0 + b;
-        std::fill(tbl.begin() + (size_t)r * pps, tbl.begin() + (size_t)(r + 1) * pps, -1);
+        S->pages.drop_row(r);
         S->done_rows[r] = 1; S->row_clip[r] = S->hold ? gr.held : -1; S->cur_tok[r] = 0;
       }
       continue;
@@ -563,11 +519,28 @@ static int beam_step(ttasr_ctx* c, Session* S) {
       S->cur_tok[r] = S->done_rows[r] ? o.eot : (searching[g] ? S->seqs[r].back() : gr.prompt[gr.pos]);
     }
   }
-  std::fill(S->refcnt.begin(), S->refcnt.end(), 0);
-  for (int32_t p : tbl) if (p >= 0) S->refcnt[p]++;
-  S->free_pages.clear();
-  for (int p = n_pages - 1; p >= 0; --p) if (S->refcnt[p] == 0) S->free_pages.push_back(p);
   return 0;
+}
+
+// What both submit calls build alike of clip i: its prompt (checked, with the sot index where no-speech is wanted) and its budget.
+// A call validates and builds ALL its clips before queue_clips gives them ids: a refused call leaves the session as it was.
+static int init_clip(ttasr_ctx* c, const Session* S, int i, const int32_t* prompt, const int32_t* prompt_len, const int32_t* sot,
+                     const int32_t* max_new, Session::Clip& cl) {
+  const int32_t* row = prompt + (size_t)i * S->max_prompt;
+  TRY(check_prompt(c, i, row, prompt_len[i], S->max_prompt, sot));
+  if (max_new[i] < 1 || max_new[i] > S->o.max_new_tokens)
+    return fail(c, TTASR_E_INVALID, "clip %d: max_new %d outside [1, max_new_tokens=%d]", i, max_new[i], S->o.max_new_tokens);
+  cl.prompt.assign(row, row + prompt_len[i]);
+  cl.cap = max_new[i];
+  return 0;
+}
+
+static void queue_clips(Session* S, std::vector<Session::Clip>& cls, int64_t* out_ids) {
+  for (size_t i = 0; i < cls.size(); ++i) {
+    cls[i].id = S->next_id++;
+    if (out_ids) out_ids[i] = cls[i].id;
+    S->queue.push_back(std::move(cls[i]));
+  }
 }
 
 static int session_submit(ttasr_ctx* c, int n, const float* const* pcm, const int64_t* n_samples, const int32_t* prompt,
@@ -577,32 +550,17 @@ static int session_submit(ttasr_ctx* c, int n, const float* const* pcm, const in
   if (!S) return fail(c, TTASR_E_INVALID, "no session is open (ttasr_session_begin first)");
   if (n < 1) return fail(c, TTASR_E_INVALID, "n %d < 1", n);
   if (!pcm || !n_samples || !prompt || !prompt_len || !max_new) return fail(c, TTASR_E_INVALID, "NULL argument");
-  const int P = S->max_prompt;
-  // everything is validated before a clip is queued: a refused call leaves the session as it was
+  std::vector<Session::Clip> cls(n);
   for (int i = 0; i < n; ++i) {
     if (n_samples[i] < 0 || n_samples[i] > c->n_samples)
       return fail(c, TTASR_E_INVALID, "clip %d: %lld samples outside [0, %d] (one window)", i, (long long)n_samples[i], c->n_samples);
     if (n_samples[i] > 0 && !pcm[i]) return fail(c, TTASR_E_INVALID, "clip %d: pcm is NULL", i);
-    if (prompt_len[i] < 1 || prompt_len[i] > P) return fail(c, TTASR_E_INVALID, "clip %d: prompt_len %d outside [1, %d]", i, prompt_len[i], P);
-    if (prompt_len[i] >= c->cfg.n_text_ctx)
-      return fail(c, TTASR_E_INVALID, "clip %d: prompt_len %d leaves no room in the %d-token context", i, prompt_len[i], c->cfg.n_text_ctx);
-    for (int j = 0; j < prompt_len[i]; ++j)
-      if (prompt[(size_t)i * P + j] < 0 || prompt[(size_t)i * P + j] >= c->V) return fail(c, TTASR_E_INVALID, "clip %d: prompt token outside vocabulary", i);
-    if (max_new[i] < 1 || max_new[i] > S->o.max_new_tokens)
-      return fail(c, TTASR_E_INVALID, "clip %d: max_new %d outside [1, max_new_tokens=%d]", i, max_new[i], S->o.max_new_tokens);
-    if (S->beam && S->o.no_speech >= 0 && (S->o.sot_index < 0 || S->o.sot_index >= prompt_len[i]))
-      return fail(c, TTASR_E_INVALID, "clip %d: sot_index %d outside the %d-token prompt", i, S->o.sot_index, prompt_len[i]);
-  }
-  for (int i = 0; i < n; ++i) {
-    Session::Clip cl;
-    cl.id = S->next_id++;
+    Session::Clip& cl = cls[i];
+    TRY(init_clip(c, S, i, prompt, prompt_len, S->beam && S->o.no_speech >= 0 ? &S->o.sot_index : nullptr, max_new, cl));
     cl.pcm.assign(pcm[i], pcm[i] + n_samples[i]);
-    cl.prompt.assign(prompt + (size_t)i * P, prompt + (size_t)i * P + prompt_len[i]);
-    cl.cap = max_new[i];
     cl.mode = Session::BEAM; cl.rows = S->beam; cl.sot = S->o.sot_index;
-    if (out_ids) out_ids[i] = cl.id;
-    S->queue.push_back(std::move(cl));
   }
+  queue_clips(S, cls, out_ids);
   return TTASR_OK;
 }
 
@@ -619,8 +577,7 @@ static int session_submit_windows(ttasr_ctx* c, int n, const float* const* file_
   if (n < 1) return fail(c, TTASR_E_INVALID, "n %d < 1", n);
   if (!file_pcm || !file_samples || !seek_frames || !prompt || !prompt_len || !sot_index || !max_new || !rows || !seed)
     return fail(c, TTASR_E_INVALID, "NULL argument");
-  const int P = S->max_prompt;
-  // everything is validated before a clip is queued: a refused call leaves the session as it was
+  std::vector<Session::Clip> cls(n);
   for (int i = 0; i < n; ++i) {
     if (file_samples[i] < 0) return fail(c, TTASR_E_INVALID, "window %d: negative file length", i);
     if (file_samples[i] > 0 && !file_pcm[i]) return fail(c, TTASR_E_INVALID, "window %d: pcm is NULL", i);
@@ -628,22 +585,11 @@ static int session_submit_windows(ttasr_ctx* c, int n, const float* const* file_
       return fail(c, TTASR_E_INVALID, "window %d: seek %lld at or beyond the file (%lld samples)", i, (long long)seek_frames[i],
                   (long long)file_samples[i]);
     if (floor_max && !std::isfinite(floor_max[i])) return fail(c, TTASR_E_INVALID, "window %d: floor_max is not finite", i);
-    if (prompt_len[i] < 1 || prompt_len[i] > P) return fail(c, TTASR_E_INVALID, "window %d: prompt_len %d outside [1, %d]", i, prompt_len[i], P);
-    if (prompt_len[i] >= c->cfg.n_text_ctx)
-      return fail(c, TTASR_E_INVALID, "window %d: prompt_len %d leaves no room in the %d-token context", i, prompt_len[i], c->cfg.n_text_ctx);
-    for (int j = 0; j < prompt_len[i]; ++j)
-      if (prompt[(size_t)i * P + j] < 0 || prompt[(size_t)i * P + j] >= c->V) return fail(c, TTASR_E_INVALID, "window %d: prompt token outside vocabulary", i);
-    if (max_new[i] < 1 || max_new[i] > S->o.max_new_tokens)
-      return fail(c, TTASR_E_INVALID, "window %d: max_new %d outside [1, max_new_tokens=%d]", i, max_new[i], S->o.max_new_tokens);
-    if (S->o.no_speech >= 0 && (sot_index[i] < 0 || sot_index[i] >= prompt_len[i]))
-      return fail(c, TTASR_E_INVALID, "window %d: sot_index %d outside the %d-token prompt", i, sot_index[i], prompt_len[i]);
     if (rows[i] < 1 || rows[i] > S->beam) return fail(c, TTASR_E_INVALID, "window %d: rows %d outside [1, %d]", i, rows[i], S->beam);
     if (temperature && !(std::isfinite(temperature[i]) && temperature[i] >= 0.f))
-      return fail(c, TTASR_E_INVALID, "window %d: temperature %g must be finite and >= 0", i, temperature ? temperature[i] : 0.f);
-  }
-  for (int i = 0; i < n; ++i) {
-    Session::Clip cl;
-    cl.id = S->next_id++;
+      return fail(c, TTASR_E_INVALID, "window %d: temperature %g must be finite and >= 0", i, temperature[i]);
+    Session::Clip& cl = cls[i];
+    TRY(init_clip(c, S, i, prompt, prompt_len, S->o.no_speech >= 0 ? &sot_index[i] : nullptr, max_new, cl));
     // the span of ttasr_log_mel_windows: `lead` samples before the window (200, fewer at the file start), the window, 200 after
     const int64_t fs = file_samples[i], file_frames = fs / 160, seek = seek_frames[i];
     const int64_t start = seek * 160, lead = std::min<int64_t>(200, start);
@@ -654,16 +600,13 @@ static int session_submit_windows(ttasr_ctx* c, int n, const float* const* file_
     cl.geom[1] = (fs - (start - lead) < lead + c->n_samples + 200) ? fs - (start - lead) : ((int64_t)1 << 40);
     cl.geom[2] = std::max<int64_t>(std::min<int64_t>(c->F, file_frames - seek), 0);
     if (floor_max) { cl.has_floor = true; cl.floor = mel_max_to_ordered(floor_max[i]); }
-    cl.prompt.assign(prompt + (size_t)i * P, prompt + (size_t)i * P + prompt_len[i]);
-    cl.cap = max_new[i];
     cl.sot = sot_index[i];
     cl.temp = temperature ? temperature[i] : 0.f;
     cl.rows = rows[i];
     cl.seed = seed[i];
     cl.mode = (cl.temp == 0.f && cl.rows > 1) ? Session::BEAM : Session::ROWS;
-    if (out_ids) out_ids[i] = cl.id;
-    S->queue.push_back(std::move(cl));
   }
+  queue_clips(S, cls, out_ids);
   return TTASR_OK;
 }
 
@@ -820,8 +763,9 @@ static int session_align(ttasr_ctx* c, int n, const int64_t* ids, const AlignBat
   const int pps = c->pages_per_seq;
   std::vector<int32_t> slot(units.begin(), units.end()), pages((size_t)n * pps);
   if (S->beam) {
-    if (S->free_pages.size() < pages.size()) return fail(c, TTASR_E_INVALID, "session align: %zu free pages, %zu needed", S->free_pages.size(), pages.size());
-    std::copy(S->free_pages.end() - (ptrdiff_t)pages.size(), S->free_pages.end(), pages.begin());
+    const int32_t* spare = S->pages.peek_free(pages.size());
+    if (!spare) return fail(c, TTASR_E_INVALID, "session align: %zu free pages, %zu needed", S->pages.free_pages.size(), pages.size());
+    std::copy_n(spare, pages.size(), pages.begin());
   } else {
     for (int i = 0; i < n; ++i)
       for (int p = 0; p < pps; ++p) pages[(size_t)i * pps + p] = units[i] * pps + p;

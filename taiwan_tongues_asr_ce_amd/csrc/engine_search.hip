@@ -119,6 +119,16 @@ int reset_search(ttasr_ctx* c, int B) {
   return 0;
 }
 
+int check_prompt(ttasr_ctx* c, int i, const int32_t* row, int len, int max_prompt, const int32_t* sot) {
+  if (len < 1 || len > max_prompt) return fail(c, TTASR_E_INVALID, "prompt %d: length %d outside [1, %d]", i, len, max_prompt);
+  if (len >= c->cfg.n_text_ctx)
+    return fail(c, TTASR_E_INVALID, "prompt %d: length %d leaves no room in the %d-token context", i, len, c->cfg.n_text_ctx);
+  for (int j = 0; j < len; ++j)
+    if (row[j] < 0 || row[j] >= c->V) return fail(c, TTASR_E_INVALID, "prompt %d: token %d at %d outside the vocabulary", i, row[j], j);
+  if (sot && (*sot < 0 || *sot >= len)) return fail(c, TTASR_E_INVALID, "prompt %d: sot_index %d outside the %d-token prompt", i, *sot, len);
+  return 0;
+}
+
 // shared by ttasr_generate and ttasr_generate_sample: R rows, row r uses prompt (r / rows_per_clip)
 int generate_rows(ttasr_ctx* c, int R, int rows_per_clip, const int32_t* prompt, const int32_t* prompt_len, int max_prompt,
                   const ttasr_gen_opts* o, float temperature, uint32_t seed, int32_t* out_tokens, int32_t* out_len, float* out_lp,
@@ -126,13 +136,8 @@ int generate_rows(ttasr_ctx* c, int R, int rows_per_clip, const int32_t* prompt,
   int min_plen = 1 << 30, max_plen = 0;
   const int A = R / rows_per_clip;
   for (int a = 0; a < A; ++a) {
-    if (prompt_len[a] < 1 || prompt_len[a] > max_prompt) return fail(c, TTASR_E_INVALID, "prompt_len[%d]=%d", a, prompt_len[a]);
-    if (prompt_len[a] >= c->cfg.n_text_ctx)
-      return fail(c, TTASR_E_INVALID, "prompt_len[%d]=%d leaves no room in the %d-token context", a, prompt_len[a], c->cfg.n_text_ctx);
+    TRY(check_prompt(c, a, prompt + (size_t)a * max_prompt, prompt_len[a], max_prompt, nullptr));
     min_plen = std::min(min_plen, prompt_len[a]); max_plen = std::max(max_plen, prompt_len[a]);
-    for (int j = 0; j < prompt_len[a]; ++j)
-      if (prompt[a * max_prompt + j] < 0 || prompt[a * max_prompt + j] >= c->V)
-        return fail(c, TTASR_E_INVALID, "prompt token outside vocabulary");
   }
   RuleParams old = c->rp;
   TRY(upload_rules(c, o, max_prompt));
@@ -215,13 +220,12 @@ int generate_rows(ttasr_ctx* c, int R, int rows_per_clip, const int32_t* prompt,
 }
 
 // Candidate selection of one clip at a searching position (Whisper BeamSearchDecoder semantics), shared by beam_search_impl and
-// the beam session: rows r0 .. r0 + beam - 1 hold the clip's hypotheses, lp / id [row][K] the candidate kernel's top K of every
-// row.  Identical sequences collapse (the best score stays), ties break by sequence, finished hypotheses (EOT) go to `finished`
+// the beam session: rows r0 .. r0 + beam - 1 hold the clip's hypotheses, lp / id [row][stride] the candidate kernel's top K of every
+// row (stride >= K: a group of the beam session may search with fewer rows than the candidate kernel ran for).  Identical sequences collapse (the best score stays), ties break by sequence, finished hypotheses (EOT) go to `finished`
 // up to max_cand; the `beam` best live ones are appended to nseq / nsum with their parent rows in src.  false: no live candidate.
 bool beam_select(const std::vector<std::vector<int>>& seqs, const std::vector<double>& sums, int r0, int beam, int K,
                  const float* lp, const int32_t* id, int eot, int max_cand, std::map<std::vector<int>, double>& finished,
                  std::vector<std::vector<int>>& nseq, std::vector<double>& nsum, std::vector<int>& src, int stride) {
-  if (stride == 0) stride = K;   // the beam session's groups may use fewer rows than the candidate kernel ran for
   std::map<std::vector<int>, std::pair<double, int>> cand;
   for (int b = 0; b < beam; ++b) {
     const int r = r0 + b;
@@ -281,6 +285,45 @@ int beam_pick(const std::map<std::vector<int>, double>& finished, const std::vec
   return n;
 }
 
+int beam_exchange(ttasr_ctx* c, int R, int K, BeamExchange& x) {
+  const int pps = c->pages_per_seq;
+  if (!c->pinned_beam)   // the largest search this context can run: max_batch rows, beam 7
+    HIPCHK(c, hipHostMalloc((void**)&c->pinned_beam, beam_exchange_words(c->maxB, pps, 8) * 4));
+  int32_t* p = (int32_t*)c->pinned_beam;
+  auto take = [&](size_t n) { int32_t* q = p; p += n; return q; };
+  x.tbl = take((size_t)R * pps); x.tok = take(R); x.pos = take(R); x.done = take(R); x.state = take(4 * (size_t)R); x.pairs = take(2 * (size_t)R);
+  x.lp = (float*)take((size_t)R * K); x.id = take((size_t)R * K); x.ns = (float*)take(R);
+  x.ent = take(4 * (size_t)R); x.temp = (float*)take(R); x.seed = (uint32_t*)take(R); x.sel = (float*)take(3 * (size_t)R);
+  return 0;
+}
+
+int enqueue_page_copies(ttasr_ctx* c, const std::vector<int32_t>& pairs, const BeamExchange& x) {
+  if (pairs.empty()) return 0;
+  memcpy(x.pairs, pairs.data(), pairs.size() * 4);
+  HIPCHK(c, hipMemcpyAsync(c->pairs_dev, x.pairs, pairs.size() * 4, hipMemcpyHostToDevice, c->stream));
+  TT_DISPATCH(c, launch_copy_pages<T>((T*)c->pool, c->pairs_dev, (int)pairs.size() / 2, c->cfg.dec_layers, c->H, c->pool_layer_elems, c->stream));
+  return 0;
+}
+
+int enqueue_row_histories(ttasr_ctx* c, const std::vector<std::vector<int>>& seqs, int R, int timestamp_begin, const BeamExchange& x) {
+  for (int r = 0; r < R; ++r) {
+    int last = -1, pen = -1, lts = -1;
+    for (int t : seqs[r]) { pen = last; last = t; if (t >= timestamp_begin) lts = t; }
+    x.state[r] = (int)seqs[r].size(); x.state[R + r] = last; x.state[2 * R + r] = pen; x.state[3 * R + r] = lts;
+  }
+  HIPCHK(c, hipMemcpyAsync(c->row_state, x.state, (size_t)4 * R * 4, hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+
+int enqueue_candidates(ttasr_ctx* c, int R, int K, bool no_speech, const BeamExchange& x) {
+  hipStream_t s = c->stream;
+  launch_beam_topk(c->logits, beam_row_state(c, R), c->rp, R, K, c->topk_lp, c->topk_id, no_speech ? c->st.no_speech : nullptr, s);
+  HIPCHK(c, hipMemcpyAsync(x.lp, c->topk_lp, (size_t)R * K * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(x.id, c->topk_id, (size_t)R * K * 4, hipMemcpyDeviceToHost, s));
+  if (no_speech) HIPCHK(c, hipMemcpyAsync(x.ns, c->st.no_speech, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+  return 0;
+}
+
 // Beam search over A clips x `beam` rows.  Prompts may be ragged: clip a has plens[a] tokens at prompt + a * max_prompt and
 // its <|startoftranscript|> at sots[a]; the step loop is position-synchronous, so at a given position some clips are
 // still being forced through their prompt while others already search.
@@ -294,17 +337,13 @@ int beam_search_impl(ttasr_ctx* c, int32_t A, int32_t beam, const int32_t* promp
   if (!prompt || !plens || !out_tokens || !out_len || !o) return fail(c, TTASR_E_INVALID, "NULL argument");
   if (A > c->B_enc) return fail(c, TTASR_E_INVALID, "encoder state holds %d clips, %d requested", c->B_enc, A);
   if (max_prompt < 1 || max_prompt > c->max_prompt_alloc) return fail(c, TTASR_E_INVALID, "max_prompt %d", max_prompt);
+  auto sot_of = [&](int a) { return sots ? sots[a] : o->sot_index; };
   int min_plen = 1 << 30, min_sot = 1 << 30;
   for (int a = 0; a < A; ++a) {
-    if (plens[a] < 1 || plens[a] > max_prompt || plens[a] >= c->cfg.n_text_ctx) return fail(c, TTASR_E_INVALID, "prompt_len[%d]=%d", a, plens[a]);
-    const int sot = sots ? sots[a] : o->sot_index;
-    if (o->no_speech >= 0 && out_ns && (sot < 0 || sot >= plens[a])) return fail(c, TTASR_E_INVALID, "sot_index[%d]=%d outside the prompt", a, sot);
-    min_plen = std::min(min_plen, (int)plens[a]); min_sot = std::min(min_sot, sot);
-    for (int i = 0; i < plens[a]; ++i)
-      if (prompt[(size_t)a * max_prompt + i] < 0 || prompt[(size_t)a * max_prompt + i] >= c->V)
-        return fail(c, TTASR_E_INVALID, "prompt token outside vocabulary");
+    const int32_t sot = sot_of(a);
+    TRY(check_prompt(c, a, prompt + (size_t)a * max_prompt, plens[a], max_prompt, o->no_speech >= 0 && out_ns ? &sot : nullptr));
+    min_plen = std::min(min_plen, (int)plens[a]); min_sot = std::min(min_sot, (int)sot);
   }
-  auto sot_of = [&](int a) { return sots ? sots[a] : o->sot_index; };
   RuleParams old_rp = c->rp;
   TRY(upload_rules(c, o, max_prompt));
   TRY(commit_rules(c, old_rp));
@@ -314,40 +353,21 @@ int beam_search_impl(ttasr_ctx* c, int32_t A, int32_t beam, const int32_t* promp
   c->kv_div = beam; c->identity_pages = 0;
   struct Restore { ttasr_ctx* c; ~Restore() { c->kv_div = 1; c->identity_pages = 1; } } restore{c};
   hipStream_t s = c->stream;
-  const int pps = c->pages_per_seq, n_pages = c->maxB * pps, max_new = c->rp.max_new, K = beam + 1;
+  const int pps = c->pages_per_seq, max_new = c->rp.max_new, K = beam + 1;
   const int max_cand = std::max(1, (int)std::lround(beam * patience));
-  std::vector<int32_t> tbl((size_t)R * pps, -1), refcnt(n_pages, 0), free_pages, cur_tok(R), pairs;
+  auto pool_empty = [&] { return fail(c, TTASR_E_NOMEM, "KV page pool exhausted"); };
+  BeamPages pages;
+  pages.reset(R, pps, c->maxB * pps);
+  std::vector<int32_t> cur_tok(R), pairs;
   std::vector<std::vector<int>> seqs(R);
   std::vector<double> sums(R, 0.0);
   std::vector<std::map<std::vector<int>, double>> finished(A);
-  // the pinned exchange block (engine_ctx.hpp): [page tables R x pps | fed tokens R | row histories 4 R | page pairs 2 R | done R]
-  // out, [log-probs R x K | ids R x K | no-speech R] back
-  const size_t n_up = (size_t)R * pps, o_tok = n_up, o_state = o_tok + R, o_pairs = o_state + 4 * (size_t)R, o_done = o_pairs + 2 * (size_t)R,
-               o_lp = o_done + R, o_id = o_lp + (size_t)R * K, o_ns = o_id + (size_t)R * K, n_words = o_ns + R;
-  if (c->pinned_beam_bytes < n_words * 4) {
-    if (c->pinned_beam) hipHostFree(c->pinned_beam);
-    c->pinned_beam = nullptr; c->pinned_beam_bytes = 0;
-    const size_t want = (size_t)c->maxB * (pps + 8 + 2 * 8 + 1) * 4 + 4096;     // the largest search this context can run
-    HIPCHK(c, hipHostMalloc((void**)&c->pinned_beam, std::max(want, n_words * 4)));
-    c->pinned_beam_bytes = std::max(want, n_words * 4);
-  }
-  int32_t* const pb = (int32_t*)c->pinned_beam;
-  int32_t *const p_up = pb, *const p_tok = pb + o_tok, *const h_state = pb + o_state, *const p_pairs = pb + o_pairs, *const p_done = pb + o_done,
-          *const h_id = pb + o_id;
-  float *const h_lp = (float*)(pb + o_lp), *const h_ns = (float*)(pb + o_ns);
-  for (int r = 0; r < R; ++r) h_ns[r] = 0.f;
+  BeamExchange x;
+  TRY(beam_exchange(c, R, K, x));
+  for (int r = 0; r < R; ++r) x.ns[r] = 0.f;
   using clk = std::chrono::steady_clock;
   double t_enq = 0, t_wait = 0, t_sel = 0; int n_pos = 0;
   auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
-  auto rebuild_free = [&](int upto_idx) {
-    std::fill(refcnt.begin(), refcnt.end(), 0);
-    for (int r = 0; r < R; ++r)
-      for (int j = 0; j <= upto_idx && j < pps; ++j)
-        if (tbl[(size_t)r * pps + j] >= 0) refcnt[tbl[(size_t)r * pps + j]]++;
-    free_pages.clear();
-    for (int p = n_pages - 1; p >= 0; --p) if (refcnt[p] == 0) free_pages.push_back(p);
-  };
-  rebuild_free(-1);
   for (int r = 0; r < R; ++r) cur_tok[r] = prompt[(size_t)(r / beam) * max_prompt];
   std::vector<char> done(A, 0);
   std::vector<int32_t> done_rows(R, 0);   // device copy of `done`, one flag per row: finished clips leave the attention kernels (round 6)
@@ -364,40 +384,24 @@ int beam_search_impl(ttasr_ctx* c, int32_t A, int32_t beam, const int32_t* promp
     const int n_pg = (pre + 15) / 16;
     std::vector<int32_t> ptab((size_t)A * pps, 0);
     for (int a = 0; a < A; ++a)
-      for (int q = 0; q < n_pg; ++q) {
-        if (free_pages.empty()) return fail(c, TTASR_E_NOMEM, "KV page pool exhausted");
-        const int32_t pg = free_pages.back(); free_pages.pop_back();
-        for (int b = 0; b < beam; ++b) tbl[(size_t)(a * beam + b) * pps + q] = pg;
-        ptab[(size_t)a * pps + q] = pg;
-      }
+      for (int q = 0; q < n_pg; ++q)
+        if ((ptab[(size_t)a * pps + q] = pages.share_fresh(a * beam, beam, q)) < 0) return pool_empty();
     HIPCHK(c, hipMemcpyAsync(c->page_table, ptab.data(), ptab.size() * 4, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(c->prompt_dev, prompt, (size_t)A * max_prompt * 4, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipStreamSynchronize(s));  // ptab is a stack temporary
     sched_prefill(c, A, pre, 1, max_prompt);
     c->pinned_i32[1] = pre;
     HIPCHK(c, hipMemcpyAsync(c->st.step, &c->pinned_i32[1], 4, hipMemcpyHostToDevice, s));
-    rebuild_free(n_pg - 1);
     for (int r = 0; r < R; ++r) cur_tok[r] = prompt[(size_t)(r / beam) * max_prompt + pre];
   }
   bool stop = false;
   for (int pos = pre; pos < c->cfg.n_text_ctx - 1 && !stop; ++pos) {
-    // 1. the page this step writes must exist and be private to the row (copy-on-write after a re-index)
+    // 1. the page this step writes must exist and be private to the row (copy-on-write after a re-index); finished clips included
     auto t0 = clk::now();
     ++n_pos;
-    const int j = pos / 16;
     pairs.clear();
-    for (int r = 0; r < R; ++r) {
-      int32_t& pg = tbl[(size_t)r * pps + j];
-      if (pos % 16 == 0 || pg < 0) {
-        if (free_pages.empty()) return fail(c, TTASR_E_NOMEM, "KV page pool exhausted");
-        pg = free_pages.back(); free_pages.pop_back(); refcnt[pg] = 1;
-      } else if (refcnt[pg] > 1) {
-        if (free_pages.empty()) return fail(c, TTASR_E_NOMEM, "KV page pool exhausted");
-        const int32_t np = free_pages.back(); free_pages.pop_back();
-        pairs.push_back(pg); pairs.push_back(np);
-        refcnt[pg]--; refcnt[np] = 1; pg = np;
-      }
-    }
+    for (int r = 0; r < R; ++r)
+      if (!pages.make_private(r, pos, pairs)) return pool_empty();
     // per clip: still forced through its prompt, searching, or finished
     auto forced_next = [&](int a) { return prompt[(size_t)a * max_prompt + pos + 1]; };
     bool any_sampling = false, any_ns = false;
@@ -405,50 +409,29 @@ int beam_search_impl(ttasr_ctx* c, int32_t A, int32_t beam, const int32_t* promp
       any_sampling |= !done[a] && pos + 1 >= plens[a];
       any_ns |= o->no_speech >= 0 && out_ns && pos == sot_of(a);
     }
-    // everything the device needs for this position, staged in the pinned block and copied asynchronously: page tables ([row][pps],
-    // unused entries clamped to a valid page id), the fed tokens, the copy-on-write pairs, finished flags, and - when a clip
-    // searches at this position - the row histories the candidate kernel applies the rules from (host-known before the step)
-    for (size_t i = 0; i < n_up; ++i) p_up[i] = tbl[i] < 0 ? 0 : tbl[i];
-    memcpy(p_tok, cur_tok.data(), (size_t)R * 4);
-    HIPCHK(c, hipMemcpyAsync(c->page_table, p_up, n_up * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->st.cur_tok, p_tok, (size_t)R * 4, hipMemcpyHostToDevice, s));
-    if (!pairs.empty()) {
-      memcpy(p_pairs, pairs.data(), pairs.size() * 4);
-      HIPCHK(c, hipMemcpyAsync(c->pairs_dev, p_pairs, pairs.size() * 4, hipMemcpyHostToDevice, s));
-      TT_DISPATCH(c, launch_copy_pages<T>((T*)c->pool, c->pairs_dev, (int)pairs.size() / 2, c->cfg.dec_layers, c->H, c->pool_layer_elems, s));
-    }
+    // everything the device needs for this position, staged in the pinned block and copied asynchronously: page tables, the fed
+    // tokens, the copy-on-write pairs, finished flags, and - when a clip searches at this position - the row histories the
+    // candidate kernel applies the rules from (host-known before the step)
+    pages.write_upload(x.tbl);
+    memcpy(x.tok, cur_tok.data(), (size_t)R * 4);
+    HIPCHK(c, hipMemcpyAsync(c->page_table, x.tbl, (size_t)R * pps * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->st.cur_tok, x.tok, (size_t)R * 4, hipMemcpyHostToDevice, s));
+    TRY(enqueue_page_copies(c, pairs, x));
     if (done_dirty) {
-      memcpy(p_done, done_rows.data(), (size_t)R * 4);
-      HIPCHK(c, hipMemcpyAsync(c->st.done, p_done, (size_t)R * 4, hipMemcpyHostToDevice, s));
+      memcpy(x.done, done_rows.data(), (size_t)R * 4);
+      HIPCHK(c, hipMemcpyAsync(c->st.done, x.done, (size_t)R * 4, hipMemcpyHostToDevice, s));
       done_dirty = false;
     }
-    if (any_sampling || any_ns) {
-      for (int r = 0; r < R; ++r) {
-        int last = -1, pen = -1, lts = -1;
-        for (int t : seqs[r]) { pen = last; last = t; if (t >= o->timestamp_begin) lts = t; }
-        h_state[r] = (int)seqs[r].size(); h_state[R + r] = last; h_state[2 * R + r] = pen; h_state[3 * R + r] = lts;
-      }
-      HIPCHK(c, hipMemcpyAsync(c->row_state, h_state, (size_t)4 * R * 4, hipMemcpyHostToDevice, s));
-    }
+    if (any_sampling || any_ns) TRY(enqueue_row_histories(c, seqs, R, o->timestamp_begin, x));
     // 2. one decoder step over the R rows (logits only; the search itself runs on the host) and, behind it, the candidates
     TRY(step_graph(c, R, 1));
-    if (any_sampling || any_ns) {
-      BeamRowState bs{c->row_state, c->row_state + R, c->row_state + 2 * R, c->row_state + 3 * R, c->mask_dev};
-      launch_beam_topk(c->logits, bs, c->rp, R, K, c->topk_lp, c->topk_id, any_ns ? c->st.no_speech : nullptr, s);
-      HIPCHK(c, hipMemcpyAsync(h_lp, c->topk_lp, (size_t)R * K * 4, hipMemcpyDeviceToHost, s));
-      HIPCHK(c, hipMemcpyAsync(h_id, c->topk_id, (size_t)R * K * 4, hipMemcpyDeviceToHost, s));
-      if (any_ns) HIPCHK(c, hipMemcpyAsync(h_ns, c->st.no_speech, (size_t)R * 4, hipMemcpyDeviceToHost, s));
-    }
+    if (any_sampling || any_ns) TRY(enqueue_candidates(c, R, K, any_ns, x));
     t_enq += ms_since(t0); t0 = clk::now();
     HIPCHK(c, hipStreamSynchronize(s));   // the ONE synchronisation of the position (also frees the pinned block for the next one)
     t_wait += ms_since(t0); t0 = clk::now();
     struct Sel { double& acc; clk::time_point t0; ~Sel() { acc += std::chrono::duration<double, std::milli>(clk::now() - t0).count(); } } sel_timer{t_sel, t0};
-    if (!any_sampling && !any_ns) {
-      for (int r = 0; r < R; ++r) cur_tok[r] = done[r / beam] ? o->eot : forced_next(r / beam);
-      continue;
-    }
     for (int a = 0; a < A; ++a)
-      if (o->no_speech >= 0 && out_ns && pos == sot_of(a)) ns_final[a] = h_ns[a * beam];
+      if (o->no_speech >= 0 && out_ns && pos == sot_of(a)) ns_final[a] = x.ns[a * beam];
     if (!any_sampling) {
       for (int r = 0; r < R; ++r) cur_tok[r] = done[r / beam] ? o->eot : forced_next(r / beam);
       continue;
@@ -460,15 +443,11 @@ int beam_search_impl(ttasr_ctx* c, int32_t A, int32_t beam, const int32_t* promp
         for (int b = 0; b < beam; ++b) { nseq.push_back(seqs[a * beam + b]); nsum.push_back(sums[a * beam + b]); src.push_back(a * beam + b); }
         continue;
       }
-      if (!beam_select(seqs, sums, a * beam, beam, K, h_lp, h_id, o->eot, max_cand, finished[a], nseq, nsum, src))
+      if (!beam_select(seqs, sums, a * beam, beam, K, x.lp, x.id, o->eot, max_cand, finished[a], nseq, nsum, src, K))
         return fail(c, TTASR_E_INVALID, "beam search: no live candidate (every token masked)");
     }
-    // 4. re-index: hypotheses inherit their parent's page list (shared pages; refcounts rebuilt)
-    std::vector<int32_t> ntbl((size_t)R * pps, -1);
-    for (int r = 0; r < R; ++r)
-      for (int q = 0; q <= j; ++q) ntbl[(size_t)r * pps + q] = tbl[(size_t)src[r] * pps + q];
-    tbl.swap(ntbl);
-    rebuild_free(j);
+    // 4. re-index: hypotheses inherit their parent's page list (shared pages)
+    pages.reindex(src);
     seqs.swap(nseq); sums.swap(nsum);
     bool all_done = true;
     for (int a = 0; a < A; ++a) {
