@@ -218,13 +218,15 @@ TTASR_API int ttasr_apply_rules(ttasr_ctx* ctx, const float* rows_host, const in
  * kernel forms), and every encoder pass of a session runs one GEMM family whatever the number of clips it encodes, so a clip's
  * result does not depend on its neighbours, on when it was submitted or on GPU timing: its tokens, sum_logprob and no_speech
  * are bit-identical to the same clip in a static batch of max_batch rows decoded by ttasr_generate_capped with option
- * "prefill" = 0, in every compute mode.  Prompt tokens are forced through ordinary decode steps.  While a session is open
+ * "prefill" = 0, in every compute mode.  With option "xkv_fp8" = 2 the same holds against that static pass run with the option
+ * at 2 as well: an admitted clip's e4m3 block and scales are those a static ttasr_encode builds for it.  Prompt tokens are forced through ordinary decode steps.  While a session is open
  * every other search, step, encoder, mel, rule-hook, audio-window and option call on the context is refused (TTASR_E_INVALID); ttasr_session_end closes it and leaves no resident encoder state (log-mel and encode
  * again before a static ttasr_generate).
  *
  * ttasr_session_begin: opts as for ttasr_generate (opts->check_interval = decode steps between two polls of the finished
  *   flags); max_prompt = the longest prompt a clip may bring; temperature must be 0 (greedy only).  Refused: the e4m3
- *   cross-KV mode (option xkv_fp8).  The first session of a context allocates its staging cross-KV (the size of the
+ *   cross-KV mode at value 1 (option xkv_fp8; value 2 is the session-capable mode: the session quantises every admitted clip
+ *   from its staging cross-KV into the clip's live slot).  The first session of a context allocates its staging cross-KV (the size of the
  *   context's cross-KV cache), the row positions and the admission table; later sessions reuse them.
  * ttasr_session_submit: n clips, clip i = pcm_host[i][0 .. n_samples[i]) (at most one window), prompt [n][max_prompt] with
  *   prompt_len[i] tokens valid, max_new[i] in [1, opts->max_new_tokens] = the clip's token budget; out_ids (optional)
@@ -257,9 +259,11 @@ TTASR_API int ttasr_session_begin(ttasr_ctx* ctx, const ttasr_gen_opts* opts, in
  *   - ttasr_session_rows: every row of a group reports the group's clip and the group's position (the next one to compute).
  *   - ttasr_session_stats: the values keep their meaning; out[4] counts the live row-steps of all `beam` rows of a group.
  * A clip equals, bit for bit (tokens, sum_logprob, no_speech), the same clip in ttasr_generate_beam over a static pass of
- * exactly G clips on the same context with option prefill = 0 (and, in 16-bit, option enc_gemm = 3).
+ * exactly G clips on the same context with option prefill = 0 (and, in 16-bit, option enc_gemm = 3).  With option "xkv_fp8" = 2
+ * on both sides the same holds - the groups' rows read the e4m3 copy through the shared-clip kernel in either form - and a
+ * sampled window clip equals slot 0 of a static ttasr_generate_sample pass under that option.
  * Refused, leaving the context usable and no session open: beam outside 1..7, max_batch < beam, patience <= 0, option xkv_fp8
- * on, a session already open, and everything ttasr_session_begin refuses.  While a beam session is open, every call that the
+ * = 1, a session already open, and everything ttasr_session_begin refuses.  While a beam session is open, every call that the
  * greedy session refuses is refused too. */
 TTASR_API int ttasr_session_begin_beam(ttasr_ctx* ctx, const ttasr_gen_opts* opts, int32_t max_prompt, int32_t beam,
                                        float patience);
@@ -375,7 +379,13 @@ TTASR_API int ttasr_dtw(const float* cost, int32_t n_rows, int32_t n_cols, int32
  * queries per wave; bit-identical);
  * "enc_kernel_timing" [0] per-launch events in ttasr_encode (see ttasr_encoder_kernel_ms); "xkv_fp8" [0] (16-bit engines; opt-in serving
  * mode, NOT the measured configuration) keeps an OCP e4m3 copy of the cross-KV cache with one scale per (layer, K | V, clip, head),
- * built by the next ttasr_encode and read by the decode step's cross-attention (half the bytes of the dominant kernel);
+ * built by the next ttasr_encode and read by the decode step's cross-attention (half the bytes of the dominant kernel).  Values:
+ * 0 off; 1 the copy is read by a static greedy batch of unshared rows with rows x heads >= 256 only - beam and sampled rows read
+ * the 16-bit cache and sessions are refused; 2 the copy is read wherever a kernel for it exists: those greedy rows, the rows that
+ * share a clip (ttasr_generate_beam, ttasr_generate_sample: 2..7 rows per clip and rows x heads >= 256), and continuous-batching
+ * sessions of either kind, which quantise a clip when it is admitted.  Prefill, alignment and the frame-split kernels of small
+ * batches read the 16-bit cache in every mode.  Other values: TTASR_E_INVALID; the f32 engine refuses 1 and 2;
+ * "xattn_mq_fp8" [1] under "xkv_fp8" = 2, rows that share a clip read the e4m3 copy (0: the 16-bit cache; A/B);
  * "refill_overlap" [0] the continuous-batching session encodes the next clips on a second stream of the context while the
  * decode steps run (0: synchronously between two step runs on the context's one stream; results identical; read by
  * ttasr_session_begin).  Opt-in: the second stream is a second hardware queue, and several processes sharing a GPU are then

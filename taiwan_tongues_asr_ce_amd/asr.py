@@ -37,7 +37,8 @@ class MI355XWhisperASR(ASRInterface):
         # decode rows: the adapter's default call is beam 5 with a best_of-5 temperature fallback (faster_whisper_asr.py:139-149),
         # so the model needs at least that many rows or transcribe() refuses the beam
         self.asr_pipeline = WhisperModel(model_path, device=device, compute_type=compute_type,
-                                         max_batch=max(8, int(kwargs.get("max_batch", 8))))
+                                         max_batch=max(8, int(kwargs.get("max_batch", 8))),
+                                         cross_kv_fp8=bool(kwargs.get("cross_kv_fp8", False)))   # opt-in e4m3 cross-KV cache
         # health-check attributes (faster_whisper_asr.py:111-114, streaming_asr.py:455-463)
         self.device, self.compute_type, self.model_size, self.model_path = device, compute_type, model_size, model_path
         self.default_transcribe_kwargs = {  # faster_whisper_asr.py:139-149

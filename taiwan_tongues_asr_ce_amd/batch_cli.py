@@ -117,7 +117,8 @@ def summarise(results: List[Dict]) -> Dict:
 def process_audio_folder(folder_path: str, model=None, model_path: str = "models", device: str = "cuda",
                          device_index: int = 0, compute_type: str = "float16", max_batch: int = 120, output_json: Optional[str] = None, rank: int = 0,
                          world: int = 1, load_audio: Callable = _load_audio, log: Callable = print,
-                         group_files: int = 0, pipeline_depth: int = 0, continuous: bool = False) -> Optional[Dict]:
+                         group_files: int = 0, pipeline_depth: int = 0, continuous: bool = False,
+                         cross_kv_fp8: bool = False) -> Optional[Dict]:
     if continuous:
         if int(pipeline_depth or getattr(model, "pipeline_depth", 1)) > 1:
             log("continuous mode runs one session on one engine context: pipeline depth 1")
@@ -129,7 +130,7 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
     if model is None:
         from .model import WhisperModel
         model = WhisperModel(model_path, device=device, device_index=device_index, compute_type=compute_type,
-                             max_batch=max_batch, pipeline_depth=max(1, pipeline_depth))
+                             max_batch=max_batch, pipeline_depth=max(1, pipeline_depth), cross_kv_fp8=cross_kv_fp8)
     mine = files[rank::world]                                   # shard by file
     results = []
     many = getattr(model, "transcribe_many", None)
@@ -193,6 +194,10 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
         order = {os.path.basename(f): i for i, f in enumerate(files)}
         results = sorted((r for part in gathered for r in part), key=lambda r: order[r["audio_file"]])
     final = summarise(results)
+    # the opt-in e4m3 cross-attention cache (WhisperModel(cross_kv_fp8=True)) is named in the summary; a run on the 16-bit cache
+    # keeps the reference's summary keys exactly
+    if getattr(model, "cross_kv_fp8", False):
+        final["summary"]["cross_kv_cache"] = "fp8_e4m3"
     if rank == 0:
         path = output_json or os.path.join(os.getcwd(), "asr_comparison_results.json")
         with open(path, "w", encoding="utf-8") as f:
@@ -202,7 +207,7 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
     return final
 
 
-def main(argv=None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="Transcribe every audio file of a folder on MI355X and score against transcripts")
     ap.add_argument("folder")
     ap.add_argument("--output", default="transcription_results.txt", help="accepted for compatibility; unused")
@@ -220,7 +225,14 @@ def main(argv=None) -> int:
     ap.add_argument("--continuous", action="store_true",
                     help="opt-in: decode each group's windows in one continuous-batching session (finished rows are refilled, "
                          "fallback attempts run in the session); pipeline depth 1.  Same per-file algorithm")
-    args = ap.parse_args(argv)
+    ap.add_argument("--xkv-fp8", action="store_true",
+                    help="opt-in serving mode: decode from the e4m3 copy of the cross-attention cache (16-bit compute types; "
+                         "WhisperModel(cross_kv_fp8=True)); the summary JSON names the cache that was read")
+    return ap
+
+
+def main(argv=None) -> int:
+    args = build_parser().parse_args(argv)
     if not os.path.exists(args.folder):
         print(f"folder does not exist: {args.folder}")
         return 1
@@ -230,7 +242,8 @@ def main(argv=None) -> int:
         rank, world, local = init_process_group()
     process_audio_folder(args.folder, model_path=args.model, device="cuda", device_index=local,
                          compute_type=args.compute_type, rank=rank, world=world, group_files=args.group_files,
-                         max_batch=args.max_batch, pipeline_depth=args.pipeline_depth, continuous=args.continuous)
+                         max_batch=args.max_batch, pipeline_depth=args.pipeline_depth, continuous=args.continuous,
+                         cross_kv_fp8=args.xkv_fp8)
     return 0
 
 

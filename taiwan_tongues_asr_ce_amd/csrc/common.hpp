@@ -261,6 +261,54 @@ struct SlabIn {
   int ld = 0;
 };
 
+// ------------------------------------------------------------------------------------------------
+// helpers: one 16-byte chunk of a K/V row per lane.  VEC elements, LPR lanes per 64-element row.
+// ------------------------------------------------------------------------------------------------
+template <typename T> struct RowVec;
+template <> struct RowVec<float> {
+  static constexpr int VEC = 4;
+  __device__ static void load(const float* p, float (&v)[4]) {
+    float4 t = *(const float4*)p;
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  }
+};
+template <typename T16> struct RowVec16 {
+  static constexpr int VEC = 8;
+  __device__ static void load(const T16* p, float (&v)[8]) {
+    const uint4 t = *(const uint4*)p;
+    up8<T16>(t, v);
+  }
+};
+template <> struct RowVec<bf16_t> : RowVec16<bf16_t> {};
+template <> struct RowVec<f16_t> : RowVec16<f16_t> {};
+
+// One 16-byte chunk of a query / key / value row from the K-split partial tiles of the decode GEMM that produced it:
+// v = round_T(bias + slab[0] + ... + slab[n-1]) in slab order (bit-reproducible), i.e. exactly what the unsplit GEMM's
+// epilogue would have stored.  All loads are issued first (slab index clamped), n <= 4.
+template <typename T>
+__device__ __forceinline__ void load_row_slabs(const SlabIn& si, int64_t off, int col /*= off % si.ld, known to the caller*/,
+                                               float (&v)[RowVec<T>::VEC]) {
+  constexpr int VEC = RowVec<T>::VEC, NF4 = VEC / 4, MAXS = 4;
+  float4 t[MAXS][NF4], bs[NF4];
+#pragma unroll
+  for (int c = 0; c < NF4; ++c) bs[c] = *(const float4*)(si.bias + col + 4 * c);
+#pragma unroll
+  for (int s = 0; s < MAXS; ++s) {
+    const float* p = si.slab + (int64_t)min(s, si.n - 1) * si.stride + off;
+#pragma unroll
+    for (int c = 0; c < NF4; ++c) t[s][c] = *(const float4*)(p + 4 * c);
+  }
+  __builtin_amdgcn_sched_barrier(0);  // all loads issued before the first use: one round trip
+#pragma unroll
+  for (int c = 0; c < NF4; ++c) {
+    float4 a = bs[c];
+#pragma unroll
+    for (int s = 0; s < MAXS; ++s)   // slab 0 unconditionally (n >= 1): its load must not be sunk behind a branch
+      if (s == 0 || s < si.n) { a.x += t[s][c].x; a.y += t[s][c].y; a.z += t[s][c].z; a.w += t[s][c].w; }
+    v[4 * c] = to_f<T>(from_f<T>(a.x)); v[4 * c + 1] = to_f<T>(from_f<T>(a.y));
+    v[4 * c + 2] = to_f<T>(from_f<T>(a.z)); v[4 * c + 3] = to_f<T>(from_f<T>(a.w));
+  }
+}
 // cross-attention query computed inside the attention kernel (round-4 experiment): x = LayerNorm output rows T [B][d],
 // W = the q projection T [d][d] row-major (pre-scaled by 1/8), bias f32 [d]; W == nullptr: not used
 struct QProj {
@@ -376,6 +424,19 @@ template <typename T> void launch_xkv_quant(const T* src, uint8_t* dst, float* s
 template <typename T>
 bool launch_cross_attn_fp8(const T* q, const uint8_t* K8, const uint8_t* V8, const float* kscale, const float* vscale, T* out, int B, int H,
                            int Tk, hipStream_t s, struct SlabIn sq, const int32_t* done = nullptr);
+// option xkv_fp8 = 2: the shared-clip form (rows of a beam / a sampled attempt, kv_div = 2..7) on the e4m3 copy; same shapes, slice
+// rule and workspace check as the cross_attn_mq_kernel branch of launch_cross_attn_decode; false: shape not taken
+template <typename T>
+bool launch_cross_attn_mq_fp8(const T* q, const uint8_t* K8, const uint8_t* V8, const float* kscale, const float* vscale, T* out, int B,
+                              int H, int Tk, int kv_div, hipStream_t s, float* split_ws, struct SlabIn sq, int ws_rows,
+                              const int32_t* done = nullptr);
+// the quantiser of a session's admission: n <= XkvSlotPairs::N (source slot of `src`, destination slot of the e4m3 copy) pairs
+struct XkvSlotPairs { static constexpr int N = 64; uint16_t src[N], dst[N]; };
+template <typename T>
+void launch_xkv_quant_slots(const T* src, uint8_t* dst, float* scale, int n_layers, int H, int rows, int maxB, int64_t which_elems,
+                            const XkvSlotPairs& p, int n, hipStream_t s);
+int cross_attn_splits(int B, int H, int Tk);   // frame slices of a cross-attention over B x H (row | group, head) items (kernels_attn.hip)
+template <typename T> void launch_cross_attn_merge(const float* ws, T* out, int B, int H, int S, const int32_t* done, hipStream_t s);
 extern thread_local bool g_kernel_sig_on;
 extern thread_local char g_kernel_sig[192];
 template <typename T> inline const char* sig_type() { return sizeof(T) == 4 ? "float" : "unsigned short"; }

@@ -89,7 +89,10 @@ struct ttasr_ctx {
   void* xkv = nullptr; int64_t xkv_layer_elems = 0, xkv_which_elems = 0;
   // option xkv_fp8 (opt-in serving mode, kernels_fp8.hip): an e4m3 copy of the cross-KV cache (same element strides, one byte per
   // value) + one f32 scale per (layer, K | V, clip, head); read by the decode step's cross-attention only
-  bool xkv_fp8 = false, xkv8_valid = false; uint8_t* xkv8 = nullptr; float* xkv8_scale = nullptr;
+  // xkv_fp8: 0 off; 1 unshared greedy rows of a static pass only (sessions refused); 2 wherever a kernel for the copy exists -
+  // shared rows (beam, sampled attempts) too, and in sessions, which quantise at admission
+  int xkv_fp8 = 0; bool xkv8_valid = false; uint8_t* xkv8 = nullptr; float* xkv8_scale = nullptr;
+  bool xattn_mq_fp8 = true;   // option xattn_mq_fp8 [1]: 0 = shared rows read the 16-bit cache under xkv_fp8 = 2 (A/B)
   void* pool = nullptr; int64_t pool_layer_elems = 0; int32_t* page_table = nullptr;
   float* xsplit_ws = nullptr;  // split-frame cross-attention (small batches)
   float* dx = nullptr; void *dh = nullptr, *dqkv = nullptr, *dq = nullptr, *datt = nullptr, *dmid = nullptr; float* logits = nullptr;

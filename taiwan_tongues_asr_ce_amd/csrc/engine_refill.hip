@@ -180,6 +180,16 @@ static int start_encode(ttasr_ctx* c, Session* S, int k) {
   return 0;
 }
 
+// one xkv_quant_slots_kernel launch for the n (staging slot, live slot) pairs collected by an admission (n = 0: nothing to do)
+static int flush_quant_pairs(ttasr_ctx* c, const XkvSlotPairs& qp, int& n) {
+  if (n == 0) return 0;
+  TT_DISPATCH(c, launch_xkv_quant_slots<T>((const T*)c->xkv_stage, c->xkv8, c->xkv8_scale, c->cfg.dec_layers, c->H, c->T, c->maxB,
+                                           c->xkv_which_elems, qp, n, c->stream));
+  n = 0;
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
 // staged clips -> free rows: cross-KV copies and one admit launch on the decode stream
 static int admit(ttasr_ctx* c, Session* S) {
   const int avail = (int)(S->staged.size() - S->staged_next);
@@ -191,6 +201,15 @@ static int admit(ttasr_ctx* c, Session* S) {
     if (S->staged_next == 0 && hipEventElapsedTime(&ms, S->ev_enc0, S->ev_enc) == hipSuccess) S->enc_ms += ms;
   }
   const size_t blk = (size_t)c->H * c->T * 64 * c->esz, pitch = (size_t)c->xkv_which_elems * c->esz;
+  // mode 2 of option xkv_fp8: the admitted clips' e4m3 blocks and scales, quantised from staging slot j straight into live slot r
+  // (or group slot g) on the decode stream, behind the same event as the 16-bit copies; pairs by value, no copy to wait for
+  XkvSlotPairs qp; int nq = 0;
+  auto quant_pair = [&](int from, int to) -> int {
+    if (!c->xkv8_valid) return 0;
+    qp.src[nq] = (uint16_t)from; qp.dst[nq] = (uint16_t)to;
+    if (++nq == XkvSlotPairs::N) return flush_quant_pairs(c, qp, nq);
+    return 0;
+  };
   if (S->beam) {
     // a free group takes the clip: its cross-KV goes to slot g; the search state is host-side and goes out with the next step
     for (int g = 0; g < S->G && (int)S->staged_next < (int)S->staged.size(); ++g) {
@@ -200,6 +219,7 @@ static int admit(ttasr_ctx* c, Session* S) {
       Session::Clip& cl = S->staged[j];
       HIPCHK(c, hipMemcpy2DAsync((char*)c->xkv + (size_t)g * blk, pitch, (const char*)c->xkv_stage + (size_t)j * blk, pitch, blk,
                                  2 * (size_t)c->cfg.dec_layers, hipMemcpyDeviceToDevice, s));
+      TRY(quant_pair(j, g));
       const int plen = (int)cl.prompt.size();
       gr.clip = cl.id; gr.prompt = std::move(cl.prompt); gr.pos = 0; gr.ns = 0.f; gr.finished.clear();
       // the static search's last sampled position is n_text_ctx - 2: a clip never holds more than n_text_ctx - plen tokens
@@ -212,6 +232,7 @@ static int admit(ttasr_ctx* c, Session* S) {
         S->row_clip[r] = cl.id; S->cur_tok[r] = gr.prompt[0]; S->done_rows[r] = b < cl.rows ? 0 : 1;
       }
     }
+    TRY(flush_quant_pairs(c, qp, nq));
     if (S->staged_next == S->staged.size()) {
       S->staged.clear(); S->staged_next = 0;
       HIPCHK(c, hipEventRecord(S->ev_copy, s));
@@ -227,6 +248,7 @@ static int admit(ttasr_ctx* c, Session* S) {
     Session::Clip& cl = S->staged[j];
     HIPCHK(c, hipMemcpy2DAsync((char*)c->xkv + (size_t)r * blk, pitch, (const char*)c->xkv_stage + (size_t)j * blk, pitch, blk,
                                2 * (size_t)c->cfg.dec_layers, hipMemcpyDeviceToDevice, s));
+    TRY(quant_pair(j, r));
     int32_t* e = tab + (size_t)n * W;
     const int plen = (int)cl.prompt.size();
     // a row never samples past the text context: the static loop's last sampled position is n_text_ctx - 2
@@ -235,6 +257,7 @@ static int admit(ttasr_ctx* c, Session* S) {
     S->row_clip[r] = cl.id; S->row_plen[r] = plen;
     ++n;
   }
+  TRY(flush_quant_pairs(c, qp, nq));
   if (n > 0) {
     HIPCHK(c, hipMemcpyAsync(c->admit_dev, tab, (size_t)n * W * 4, hipMemcpyHostToDevice, s));
     launch_admit_rows(c->admit_dev, n, c->maxB, S->max_prompt, c->st, c->prompt_dev, c->plen_dev, c->row_cap_dev, c->row_pos, s);
@@ -280,7 +303,8 @@ static int session_begin(ttasr_ctx* c, const ttasr_gen_opts* o, int max_prompt, 
   TRY(session_refusal(c));
   if (!o) return fail(c, TTASR_E_INVALID, "opts is NULL");
   if (!(temperature == 0.f)) return fail(c, TTASR_E_INVALID, "a session decodes greedily (temperature %g: only 0)", temperature);
-  if (c->xkv_fp8) return fail(c, TTASR_E_INVALID, "the e4m3 cross-KV mode (option xkv_fp8) is not supported in a session");
+  // value 2 of the option is the session-capable mode: admitted clips are quantised from the staging buffer into their live slots
+  if (c->xkv_fp8 == 1) return fail(c, TTASR_E_INVALID, "the e4m3 cross-KV mode (option xkv_fp8) is not supported in a session");
   if (max_prompt < 1 || max_prompt > c->max_prompt_alloc || max_prompt >= c->cfg.n_text_ctx)
     return fail(c, TTASR_E_INVALID, "max_prompt %d outside [1, %d]", max_prompt, std::min(c->max_prompt_alloc, c->cfg.n_text_ctx - 1));
   if (o->n_suppress < 0 || o->n_begin_suppress < 0 || (o->n_suppress && !o->suppress) || (o->n_begin_suppress && !o->begin_suppress))
@@ -335,6 +359,8 @@ static int session_begin(ttasr_ctx* c, const ttasr_gen_opts* o, int max_prompt, 
   c->kv_div = 1; c->identity_pages = 1;
   c->B_mel = c->B_enc = c->B_dec = 0;   // the session rewrites the encoder state and the cross-KV of every row
   c->session_rows = true;
+  // mode 2: the e4m3 copy is live for the whole session.  A free slot's stale block is never read: its rows are finished rows
+  c->xkv8_valid = c->xkv_fp8 == 2 && c->xkv8 && c->xkv8_scale && c->lowp;
   c->sess = S.release();
   return TTASR_OK;
 }
@@ -357,8 +383,8 @@ static int session_begin_beam(ttasr_ctx* c, const ttasr_gen_opts* o, int max_pro
   S->pages.reset(R, c->pages_per_seq, c->maxB * c->pages_per_seq);
   S->cur_tok.assign(R, 0); S->done_rows.assign(R, 1);
   BeamExchange x;
-  if (beam_exchange(c, R, beam + 1, x) != 0) { session_free(c); return TTASR_E_HIP; }   // the steps' pinned block exists from here on
-  if (!c->sess_sel && dalloc(c, &c->sess_sel, (size_t)c->maxB * 9 * 4) != 0) { session_free(c); return TTASR_E_HIP; }
+  if (beam_exchange(c, R, beam + 1, x) != 0) { session_free(c); c->xkv8_valid = false; return TTASR_E_HIP; }   // the steps' pinned block exists from here on
+  if (!c->sess_sel && dalloc(c, &c->sess_sel, (size_t)c->maxB * 9 * 4) != 0) { session_free(c); c->xkv8_valid = false; return TTASR_E_HIP; }
   c->kv_div = beam; c->identity_pages = 0;   // group g reads cross-KV slot g; rows read their own (shared) page lists
   return TTASR_OK;
 }
@@ -787,6 +813,7 @@ static int session_end(ttasr_ctx* c) {
   session_free(c);
   c->st.prompt = nullptr; c->st.prompt_len = nullptr;
   c->B_mel = c->B_enc = c->B_dec = 0;
+  c->xkv8_valid = false;   // like the rest of the resident encoder state: rebuilt by the next encode
   if (e != hipSuccess) return fail(c, TTASR_E_HIP, "session end: %s", hipGetErrorString(e));
   return TTASR_OK;
 }

@@ -91,10 +91,14 @@ int run_cross_kv(ttasr_ctx* c, int B) {
       enc_mark(c, EC_XKV);
     }
   }
+  // a session encodes into its staging buffer (c->xkv is swapped): slot j there is not slot j of the live e4m3 copy, whose rows
+  // are decoding - the session quantises at admission instead (engine_refill.hip admit), and the copy's validity is the session's
+  const bool staging = c->xkv_stage && c->xkv == c->xkv_stage;
+  const bool quant = c->xkv_fp8 && c->xkv8 && !staging;
   for (int l = 0; l < L; ++l) {
     if (!grouped) gemm<T>(c, layer_args(l));
     if constexpr (sizeof(T) == 2) {
-      if (c->xkv_fp8 && c->xkv8) {   // quantise this layer's K and V blocks of the B clips (one workgroup per (clip, head) block)
+      if (quant) {   // quantise this layer's K and V blocks of the B clips (one workgroup per (clip, head) block)
         for (int which = 0; which < 2; ++which) {
           const int64_t off = (int64_t)l * c->xkv_layer_elems + which * c->xkv_which_elems;
           launch_xkv_quant<T>((const T*)c->xkv + off, c->xkv8 + off, c->xkv8_scale + ((size_t)l * 2 + which) * c->maxB * c->H,
@@ -102,9 +106,9 @@ int run_cross_kv(ttasr_ctx* c, int B) {
         }
       }
     }
-    if (!grouped || (c->xkv_fp8 && c->xkv8)) enc_mark(c, EC_XKV);
+    if (!grouped || quant) enc_mark(c, EC_XKV);
   }
-  c->xkv8_valid = c->xkv_fp8 && c->xkv8 != nullptr && sizeof(T) == 2;
+  if (!staging) c->xkv8_valid = quant && sizeof(T) == 2;
   return 0;
 }
 
@@ -293,6 +297,15 @@ void run_decode_rows(ttasr_ctx* c, int row0, int n, int mode, int total_rows) {
         const float* ksc = c->xkv8_scale + ((size_t)l * 2) * c->maxB * c->H + (size_t)row0 * c->H;
         fp8_done = launch_cross_attn_fp8<T>((const T*)dq, c->xkv8 + off, c->xkv8 + off + c->xkv_which_elems, ksc, ksc + (size_t)c->maxB * c->H,
                                             (T*)datt, n, c->H, c->T, s, sq, done);
+      } else if (c->xkv_fp8 == 2 && c->xattn_mq_fp8 && c->xkv8_valid && c->kv_div >= 2 && skinny && !c->no_xsplit && !(c->skip_mask & 8)) {
+        // mode 2: rows that share a clip (beam hypotheses, sampled attempts) - wherever the 16-bit path would take
+        // cross_attn_mq_kernel with kv_div = 2..7, its e4m3 form; every other shape falls through to the 16-bit kernels
+        const int clip0 = row0 / c->kv_div;
+        const int64_t off = (int64_t)l * c->xkv_layer_elems + (int64_t)clip0 * c->H * c->T * 64;
+        const float* ksc = c->xkv8_scale + ((size_t)l * 2) * c->maxB * c->H + (size_t)clip0 * c->H;
+        fp8_done = launch_cross_attn_mq_fp8<T>((const T*)dq, c->xkv8 + off, c->xkv8 + off + c->xkv_which_elems, ksc, ksc + (size_t)c->maxB * c->H,
+                                               (T*)datt, n, c->H, c->T, c->kv_div, s, c->xsplit_ws + (size_t)row0 * c->H * 8 * 66, sq,
+                                               c->maxB - row0, done);
       }
     }
     if (!fp8_done && !(c->skip_mask & 8))
@@ -463,8 +476,9 @@ int step_graph(ttasr_ctx* c, int B, int mode, int nsteps) {
   // everything that decides WHICH kernels a captured step holds is part of the key: whether the e4m3 cross-KV copy is live
   // changes with encode (run_cross_kv builds it), not only with set_option (a graph captured between
   // set_option(xkv_fp8) and the next encode held the 16-bit kernel and kept replaying after the copy existed)
-  const int fp8_live = (c->xkv_fp8 && c->xkv8_valid) ? 1 : 0;
-  const int variant = ((c->kv_div * 2 + c->identity_pages) * 2 + fp8_live) * 64 + nsteps + (c->session_rows ? 1 << 24 : 0);
+  // ... and WHICH mode it is read in: 1 and 2 pick different kernels for shared rows, and so does option xattn_mq_fp8 under mode 2
+  const int fp8_live = (c->xkv_fp8 && c->xkv8_valid) ? (c->xkv_fp8 == 2 ? (c->xattn_mq_fp8 ? 3 : 2) : 1) : 0;
+  const int variant = ((c->kv_div * 2 + c->identity_pages) * 4 + fp8_live) * 64 + nsteps + (c->session_rows ? 1 << 24 : 0);
   for (size_t i = 0; i < c->graphs.size(); ++i) {
     if (c->graphs[i].B == B && c->graphs[i].mode == mode && c->graphs[i].variant == variant) {
       // most recently used at the back: the cache is bounded (the streaming micro-batcher varies B from 1 to max_batch rows)

@@ -82,54 +82,7 @@ template void launch_enc_attn_simple<float>(const float*, float*, int, int, int,
 template void launch_enc_attn_simple<bf16_t>(const bf16_t*, bf16_t*, int, int, int, hipStream_t);
 template void launch_enc_attn_simple<f16_t>(const f16_t*, f16_t*, int, int, int, hipStream_t);
 
-// ------------------------------------------------------------------------------------------------
-// helpers: one 16-byte chunk of a K/V row per lane.  VEC elements, LPR lanes per 64-element row.
-// ------------------------------------------------------------------------------------------------
-template <typename T> struct RowVec;
-template <> struct RowVec<float> {
-  static constexpr int VEC = 4;
-  __device__ static void load(const float* p, float (&v)[4]) {
-    float4 t = *(const float4*)p;
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  }
-};
-template <typename T16> struct RowVec16 {
-  static constexpr int VEC = 8;
-  __device__ static void load(const T16* p, float (&v)[8]) {
-    const uint4 t = *(const uint4*)p;
-    up8<T16>(t, v);
-  }
-};
-template <> struct RowVec<bf16_t> : RowVec16<bf16_t> {};
-template <> struct RowVec<f16_t> : RowVec16<f16_t> {};
-
-// One 16-byte chunk of a query / key / value row from the K-split partial tiles of the decode GEMM that produced it:
-// v = round_T(bias + slab[0] + ... + slab[n-1]) in slab order (bit-reproducible), i.e. exactly what the unsplit GEMM's
-// epilogue would have stored.  All loads are issued first (slab index clamped), n <= 4.
-template <typename T>
-__device__ __forceinline__ void load_row_slabs(const SlabIn& si, int64_t off, int col /*= off % si.ld, known to the caller*/,
-                                               float (&v)[RowVec<T>::VEC]) {
-  constexpr int VEC = RowVec<T>::VEC, NF4 = VEC / 4, MAXS = 4;
-  float4 t[MAXS][NF4], bs[NF4];
-#pragma unroll
-  for (int c = 0; c < NF4; ++c) bs[c] = *(const float4*)(si.bias + col + 4 * c);
-#pragma unroll
-  for (int s = 0; s < MAXS; ++s) {
-    const float* p = si.slab + (int64_t)min(s, si.n - 1) * si.stride + off;
-#pragma unroll
-    for (int c = 0; c < NF4; ++c) t[s][c] = *(const float4*)(p + 4 * c);
-  }
-  __builtin_amdgcn_sched_barrier(0);  // all loads issued before the first use: one round trip
-#pragma unroll
-  for (int c = 0; c < NF4; ++c) {
-    float4 a = bs[c];
-#pragma unroll
-    for (int s = 0; s < MAXS; ++s)   // slab 0 unconditionally (n >= 1): its load must not be sunk behind a branch
-      if (s == 0 || s < si.n) { a.x += t[s][c].x; a.y += t[s][c].y; a.z += t[s][c].z; a.w += t[s][c].w; }
-    v[4 * c] = to_f<T>(from_f<T>(a.x)); v[4 * c + 1] = to_f<T>(from_f<T>(a.y));
-    v[4 * c + 2] = to_f<T>(from_f<T>(a.z)); v[4 * c + 3] = to_f<T>(from_f<T>(a.w));
-  }
-}
+// (RowVec and load_row_slabs, the helpers for one 16-byte chunk of a row per lane, live in common.hpp: kernels_fp8.hip uses them too)
 template <typename T> __device__ __forceinline__ void store_row(T* p, const float (&v)[RowVec<T>::VEC]);
 template <> __device__ __forceinline__ void store_row<float>(float* p, const float (&v)[4]) {
   *(float4*)p = make_float4(v[0], v[1], v[2], v[3]);
@@ -895,6 +848,14 @@ __global__ __launch_bounds__(64) void cross_attn_merge_kernel(const float* __res
   out[((int64_t)b * H + h) * 64 + tid] = from_f<T>(num / den);
 }
 
+template <typename T>
+void launch_cross_attn_merge(const float* ws, T* out, int B, int H, int S, const int32_t* done, hipStream_t s) {
+  hipLaunchKernelGGL(cross_attn_merge_kernel<T>, dim3(H, B), dim3(64), 0, s, ws, out, H, S, done);
+}
+template void launch_cross_attn_merge<float>(const float*, float*, int, int, int, const int32_t*, hipStream_t);
+template void launch_cross_attn_merge<bf16_t>(const float*, bf16_t*, int, int, int, const int32_t*, hipStream_t);
+template void launch_cross_attn_merge<f16_t>(const float*, f16_t*, int, int, int, const int32_t*, hipStream_t);
+
 // Rows that share a clip's cross-KV (the `kv_div` hypotheses of a beam, or the prompt positions of a prefill pass) in ONE
 // workgroup per (clip, head, frame slice): K and V are streamed ONCE for all NQ queries instead of once per row - the per-row
 // kernels above re-read the same 384 KB per (clip, head) NQ times (the Infinity Cache removes the HBM traffic, not the
@@ -1121,7 +1082,7 @@ void launch_cross_attn_decode(const T* q, const T* K, const T* V, T* out, int B,
         case 6: TTASR_MQ(6); break; case 7: TTASR_MQ(7); break; default: TTASR_MQ(8); break;
       }
 #undef TTASR_MQ
-      if (S2 > 1) hipLaunchKernelGGL(cross_attn_merge_kernel<T>, dim3(H, B), dim3(64), 0, s, split_ws, out, H, S2, done);
+      if (S2 > 1) launch_cross_attn_merge<T>(split_ws, out, B, H, S2, done, s);
       return;
     }
   }
@@ -1131,7 +1092,7 @@ void launch_cross_attn_decode(const T* q, const T* K, const T* V, T* out, int B,
     const int S2 = (Tk + chunk - 1) / chunk;  // every slice non-empty
     size_t lds = sizeof(float) * (chunk + 4 * 64 + 8);
     hipLaunchKernelGGL(cross_attn_split_kernel<T>, dim3(H, B, S2), dim3(256), lds, s, q, K, V, H, Tk, kv_div, chunk, split_ws, sq, done);
-    hipLaunchKernelGGL(cross_attn_merge_kernel<T>, dim3(H, B), dim3(64), 0, s, split_ws, out, H, S2, done);
+    launch_cross_attn_merge<T>(split_ws, out, B, H, S2, done, s);
     return;
   }
   // g_xattn_variant (option xattn_nontemporal, A/B testing): 1 = nontemporal K/V loads (default), 0 = plain.  (16 rows in flight per lane and

@@ -211,8 +211,16 @@ def _read_hf_dir(path: str) -> Tuple[WhisperDims, Iterable[Tuple[str, np.ndarray
 
 class WhisperModel:
     def __init__(self, model_size_or_path: str, device: str = "auto", device_index: int = 0,
-                 compute_type: str = "default", max_batch: int = 8, pipeline_depth: int = 1, _engine_factory=None, **_unused):
-        """`pipeline_depth` (MI355X extension, default 1 = the reference's serial behaviour, asr_core.py:151): how many engine
+                 compute_type: str = "default", max_batch: int = 8, pipeline_depth: int = 1, cross_kv_fp8: bool = False,
+                 _engine_factory=None, **_unused):
+        """`cross_kv_fp8` (MI355X extension, opt-in serving mode, 16-bit compute types only): every engine context of the model
+        reads the e4m3 copy of the decoder's cross-attention cache wherever a kernel for it exists (engine option xkv_fp8 = 2:
+        greedy rows, the rows of a beam or a sampled attempt, continuous-batching sessions).  Outputs are no longer those of the
+        16-bit cache.  The lock-step and the continuous form of transcribe_many agree bit for bit only under the session's
+        contract (include/ttasr.h): prompts forced through decode steps (engine option prefill = 0) and G = max_batch / beam
+        files per lock-step pass; with the default prefill the lock-step form reads the 16-bit cache for the prompt positions
+        and the two forms may differ in the last bits.  Ignored by an engine without options (the oracle test seam).
+        `pipeline_depth` (MI355X extension, default 1 = the reference's serial behaviour, asr_core.py:151): how many engine
         contexts `transcribe_groups` / the folder tool may keep in flight on this GPU.  The extra contexts SHARE the first one's
         device weights (ttasr_create_shared: workspaces only) and are created on first use; pass i + 1's log-mel / encoder then
         runs under pass i's latency-bound decode chain.  Results are identical, file by file, to pipeline_depth = 1.
@@ -222,6 +230,8 @@ class WhisperModel:
             raise RuntimeError(f"device={device!r}: this build has only the MI355X HIP path (no CPU fallback)")
         if compute_type not in _COMPUTE_ALIASES:
             raise ValueError(f"unknown compute_type {compute_type!r}")
+        if cross_kv_fp8 and _COMPUTE_ALIASES[compute_type] == COMPUTE_F32:
+            raise ValueError("cross_kv_fp8=True needs a 16-bit compute_type (the float32 engine has no e4m3 cross-KV copy)")
         from .engine import Engine  # imports/loads libttasr; raises when the extension is missing
         self.model_size_or_path = model_size_or_path
         self.device = "cuda"
@@ -263,10 +273,14 @@ class WhisperModel:
         if pipeline_depth < 1 or pipeline_depth > 4:
             raise ValueError(f"pipeline_depth={pipeline_depth}: 1 ... 4 contexts per GPU")
         self.pipeline_depth = int(pipeline_depth)
+        self.cross_kv_fp8 = bool(cross_kv_fp8)
+        # engine options of the MODEL: set on lane 0 before its first encode and replayed on every lane created later (_lane)
+        self._lane_options: List[Tuple[str, int]] = [("xkv_fp8", 2)] if self.cross_kv_fp8 else []
         self._engine_ctor = (_engine_factory or Engine)
         self._engine_args = (dims, _COMPUTE_ALIASES[compute_type], max_batch, device_index)
         self._lanes = [self._engine_ctor(*self._engine_args)]     # lane 0 owns the device weights
         self._lanes[0].load_weights(tensors)
+        self._apply_lane_options(self._lanes[0])
         self._tls = threading.local()                             # which lane the calling thread drives (default: 0)
         self.special = self.engine.special
         self.max_batch = max_batch
@@ -290,13 +304,23 @@ class WhisperModel:
         else:
             lanes.append(e)
 
+    def _apply_lane_options(self, engine) -> None:
+        """The model-level engine options on one engine context (an engine without set_option - the oracle seam - has none)."""
+        setter = getattr(engine, "set_option", None)
+        if setter is None:
+            return
+        for key, value in getattr(self, "_lane_options", ()):   # a bare model (tests build one without __init__) has none
+            setter(key, value)
+
     def _lane(self, i: int):
-        """Engine context `i` (created on first use, sharing lane 0's device weights)."""
+        """Engine context `i` (created on first use, sharing lane 0's device weights and the model's engine options)."""
         while len(self._lanes) <= i:
             try:
-                self._lanes.append(self._engine_ctor(*self._engine_args, share_weights_with=self._lanes[0]))
+                lane = self._engine_ctor(*self._engine_args, share_weights_with=self._lanes[0])
             except TypeError:       # the oracle test seam has no weight sharing: pipelining is a HIP-engine feature
                 raise RuntimeError("pipeline_depth > 1 needs the HIP engine")
+            self._lanes.append(lane)
+            self._apply_lane_options(lane)
         return self._lanes[i]
 
     def transcribe_groups(self, groups: Sequence[Sequence[Union[str, np.ndarray]]], pipeline_depth: Optional[int] = None, **kw

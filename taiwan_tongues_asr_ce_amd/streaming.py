@@ -47,6 +47,9 @@ class BatchedWhisperASR(MI355XWhisperASR):
     its own search ends, not when the longest clip of its pass does.  max_clips groups of beam_size rows; the full 30-s window
     is encoded, so it cannot be combined with audio_ctx.
 
+    `cross_kv_fp8=True` (opt-in, both modes; passed on to WhisperModel): the decode steps read the e4m3 copy of the
+    cross-attention cache (16-bit compute types only).
+
     `word_timestamps=True` (opt-in, both modes): "words" holds {"word", "start", "end", "probability"} with the client's
     last_start_time added to start and end, and "duration" is the last word's end, as in the reference's result; the clips of
     a pass (lock-step) or of a poll (continuous: the session runs in hold mode) are aligned in one device pass."""

@@ -22,6 +22,9 @@ def main():
     ap.add_argument("--clips", default="1,6")
     ap.add_argument("--beam", type=int, default=5)
     ap.add_argument("--new-tokens", type=int, default=32)
+    ap.add_argument("--xkv-fp8", type=int, default=0, choices=[0, 1, 2],
+                    help="option xkv_fp8: 0 the 16-bit cross-KV cache, 1 the e4m3 copy for unshared static rows only, 2 wherever a "
+                         "kernel for it exists (shared rows, sessions)")
     ap.add_argument("--option", action="append", default=[], help="key=value kernel-selection override (ttasr_set_option)")
     args = ap.parse_args()
     from taiwan_tongues_asr_ce_amd import synth
@@ -33,6 +36,8 @@ def main():
     for A in [int(x) for x in args.clips.split(",")]:
         e = Engine(dims, COMPUTE_BF16, A * args.beam)
         e.load_weights(weights)
+        if args.xkv_fp8:
+            e.set_option("xkv_fp8", args.xkv_fp8)   # before the encode: the copy is built with the cross-KV
         for kv in args.option:
             e.set_option(kv.split("=", 1)[0], int(kv.split("=", 1)[1]))
         st = e.special
@@ -50,6 +55,7 @@ def main():
         n_steps = max(len(t) for t in toks) + len(prompt)
         print(json.dumps({"clips": A, "beam": args.beam, "rows": A * args.beam, "wall_ms": round(min(ms[1:]), 2),
                           "steps_upper_bound": n_steps, "ms_per_step": round(min(ms[1:]) / n_steps, 3),
+                          "xkv_fp8": args.xkv_fp8,
                           "host_split_last_run": {k: round(v, 2) for k, v in e.beam_profile().items()},
                           "options": args.option}), flush=True)
         e.close()

@@ -143,10 +143,16 @@ def main():
     ap.add_argument("--regime", default="both", choices=["off", "ref", "both"],
                     help="off: thresholds off only; ref: reference defaults only (on --fallback-files files)")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    ap.add_argument("--xkv-fp8", type=int, default=0, choices=[0, 1, 2],
+                    help="option xkv_fp8: 0 the 16-bit cross-KV cache, 1 the e4m3 copy for unshared static rows only, 2 wherever a "
+                         "kernel for it exists (shared rows, sessions)")
     args = ap.parse_args()
     counters = {}
     model = WhisperModel(f"synthetic:{args.model}", device="cuda", compute_type="bfloat16", max_batch=args.max_batch,
-                         pipeline_depth=1, _engine_factory=make_engine_class(args.eot_boost, counters))
+                         pipeline_depth=1, cross_kv_fp8=args.xkv_fp8 == 2,
+                         _engine_factory=make_engine_class(args.eot_boost, counters))
+    if args.xkv_fp8 == 1:
+        model.engine.set_option("xkv_fp8", 1)   # the continuous runs are refused in this mode
     base = dict(language="zh", beam_size=5, condition_on_previous_text=True, max_new_tokens=args.max_new)
     off = dict(base, temperature=0.0, no_speech_threshold=None, log_prob_threshold=None, compression_ratio_threshold=None)
     ref = dict(base)   # the reference defaults: ladder 0.0 ... 1.0, best_of 5, thresholds 2.4 / -1.0 / 0.6
@@ -155,7 +161,7 @@ def main():
     warm = [f[: 16000 * 45] for f in files[:2]]
     for cont in (False, True):
         run(model, counters, warm, dict(off, max_new_tokens=16), cont)
-    line = {"metric": "longform_audio_s_per_s", "model": args.model, "compute": "bf16", "max_batch": args.max_batch, "beam": 5,
+    line = {"metric": "longform_audio_s_per_s", "model": args.model, "compute": "bf16", "xkv_fp8": args.xkv_fp8, "max_batch": args.max_batch, "beam": 5,
             "eot_boost": args.eot_boost, "max_new_tokens": args.max_new, "files": args.files,
             "audio_s": round(sum(len(f) for f in files) / 16000.0, 1)}
     if args.regime in ("off", "both"):

@@ -48,6 +48,9 @@ def main():
                     help="option graph = 0 (decode steps launched one by one): for rocprofv3, which crashes inside hipGraph capture")
     ap.add_argument("--beam", type=int, default=0, help="beam width: compare static beam passes with the beam session")
     ap.add_argument("--eot-boost", type=float, default=8.0, help="--beam: scale of the EOT embedding row (synthetic weights)")
+    ap.add_argument("--xkv-fp8", type=int, default=0, choices=[0, 1, 2],
+                    help="option xkv_fp8: 0 the 16-bit cross-KV cache, 1 the e4m3 copy for unshared static rows only, 2 wherever a "
+                         "kernel for it exists (shared rows, sessions)")
     args = ap.parse_args()
     if args.beam:
         return main_beam(args)
@@ -55,6 +58,8 @@ def main():
     B, N = args.batch, args.clips
     eng = Engine(dims, COMPUTE_BF16, B)
     eng.load_weights(synth.iter_weights(dims))
+    if args.xkv_fp8:
+        eng.set_option("xkv_fp8", args.xkv_fp8)   # 1: the session calls are refused
     if args.no_graph:
         eng.set_option("graph", 0)
     st = eng.special
@@ -119,7 +124,7 @@ def main():
     eng.set_option("refill_overlap", 1)
     tc, c = timed(session)
     line = {
-        "metric": "refill_audio_s_per_s", "model": args.model, "compute": "bf16", "clips": N, "batch": B,
+        "metric": "refill_audio_s_per_s", "model": args.model, "compute": "bf16", "xkv_fp8": args.xkv_fp8, "clips": N, "batch": B,
         "budgets": {"lo": 32, "hi": args.new_tokens, "seed": args.seed, "mean": round(float(caps.mean()), 1)},
         "check_interval": args.check_interval, "prompt_tokens": len(prompt),
         "static": a, "session_sync": b, "session_overlap": c,
@@ -157,6 +162,8 @@ def main_beam(args):
                 w[st.eot] *= args.eot_boost
             yield name, w
     eng.load_weights(weights())
+    if args.xkv_fp8:
+        eng.set_option("xkv_fp8", args.xkv_fp8)   # 1: the session calls are refused (and a static beam reads the 16-bit cache)
     prompt = [st.sot, st.lang_zh, st.transcribe, st.no_timestamps]
     opts = eng.gen_opts(new_tokens, timestamps=False)
     clips_all = [synth.noise_clip(i)[: 16000 * (10 + (7 * i) % 21)] for i in range(N)]
@@ -223,7 +230,7 @@ def main_beam(args):
         hist[k] = hist.get(k, 0) + 1
     print("token-length histogram:", dict(sorted(hist.items(), key=lambda kv: int(kv[0].split("-")[0]))), file=sys.stderr)
     line = {
-        "metric": "refill_beam_audio_s_per_s", "model": args.model, "compute": "bf16", "beam": K, "max_batch": B, "groups": G,
+        "metric": "refill_beam_audio_s_per_s", "model": args.model, "compute": "bf16", "xkv_fp8": args.xkv_fp8, "beam": K, "max_batch": B, "groups": G,
         "clips": N, "audio_s": round(audio_s_all, 1), "eot_boost": args.eot_boost, "max_new_tokens": new_tokens,
         "prompt_tokens": len(prompt), "length_histogram": hist, "mean_tokens": round(float(np.mean(lens)), 1),
         "static": a, "session_sync": b, "session_overlap": c,
