@@ -202,6 +202,19 @@ struct GemmArgs {
   GemmEpi epi;
 };
 
+// Kernel-variant switches of the launchers (A/B options of ttasr_set_option).  A context owns one (ttasr_ctx::ko) and passes it
+// to every launcher that picks a variant, so an option set on one context never changes what another context launches or what
+// its captured graphs hold.
+struct KernelOpts {
+  int xattn_variant = 3;       // bit 0: option xattn_nontemporal (nontemporal K/V loads), bit 1: option xattn_pipeline (software-pipelined form)
+  int xattn_deep_items = 512;  // option xattn_deep_items: live (row, head) items at or below which a workgroup streams deep (kernels_attn.hip cross_attn_pipe_kernel; 0 = never)
+  int xattn_mq_slices = 0;     // option xattn_mq_slices (A/B): frame slices of the shared-clip cross-attention, 0 = automatic
+  int skinny_nt = 1;           // option weights_nontemporal: nontemporal weight loads in the decode GEMMs
+  int skinny_narrow = 1;       // option dec_narrow_blocks: 20-row n-blocks where they fill the CUs evenly (fixed once the weights are packed)
+  int skinny_x_lds = 1;        // option dec_x_lds: the decode GEMMs stage their activation tile through LDS (0 = fragment loads from memory; bit-identical)
+  int flash_qw = 2;            // option flash_qw: query blocks of 32 per wave in the encoder's flash attention (1 = the round-5 form)
+};
+
 // ---- launchers (defined in the .hip files) ---------------------------------------------------------
 template <typename T> void launch_gemm_basic(const GemmArgs& g, hipStream_t s);
 // the tiled 16-bit GEMMs (names keep "bf16": the kernels were written for it; T16 = bf16_t or f16_t picks the MFMA form and
@@ -318,16 +331,15 @@ struct QProj {
 };
 
 // decode-time weight-streaming GEMM over MFMA-fragment-packed weights (kernels_skinny.hip)
-template <typename T16> void launch_shuffle_cast(const float* src, T16* dst_base, int rows, int K, int row_offset, hipStream_t s, int rows_total = 0);
-int skinny_rows_per_block(int N, int K);   // 32 or 20 output rows per n-block of a packed decode matrix (kernels_skinny.hip)
-extern thread_local int g_skinny_narrow;    // option dec_narrow_blocks (set per C-ABI call from the context, like g_skinny_nt)
+template <typename T16> void launch_shuffle_cast(const float* src, T16* dst_base, int rows, int K, int row_offset, const KernelOpts& ko, hipStream_t s, int rows_total = 0);
+int skinny_rows_per_block(int N, int K, const KernelOpts& ko);   // 32 or 20 output rows per n-block of a packed decode matrix (kernels_skinny.hip)
 // ksplit > 1 (from gemm_skinny_ksplit): workgroup (nb, ks) writes its partial tile to slab[ks]; bias is the consumer's
 template <typename T16>
-bool launch_gemm_skinny(const T16* Wsh, const T16* x, int B, int N, int K, const GemmEpi& e, hipStream_t s, int ksplit = 1,
+bool launch_gemm_skinny(const T16* Wsh, const T16* x, int B, int N, int K, const GemmEpi& e, const KernelOpts& ko, hipStream_t s, int ksplit = 1,
                         float* slab = nullptr, int64_t slab_stride = 0);
-int gemm_skinny_ksplit(int B, int N, int K, int want);
+int gemm_skinny_ksplit(int B, int N, int K, int want, const KernelOpts& ko);
 // vocabulary projection: persistent workgroups that keep the activation rows in registers (kernels_skinny.hip); false: shape unsupported
-template <typename T16> bool launch_gemm_vocab(const T16* Wsh, const T16* x, int B, int N, int K, float* out, int64_t ldc, hipStream_t s, int device);
+template <typename T16> bool launch_gemm_vocab(const T16* Wsh, const T16* x, int B, int N, int K, float* out, int64_t ldc, const KernelOpts& ko, hipStream_t s, int device);
 void gemm_vocab_init(int device);   // once per device (std::call_once), outside any stream capture (ttasr_create)
 void gemm_tiles_init(int device);   // same for the tiled encoder GEMMs: dynamic-LDS opt-ins + CU count of the persistent grid
 // mel
@@ -346,7 +358,7 @@ void launch_mel_transpose(const float* mel, T* mel_t, int B, int n_mels, int n_f
 
 // encoder attention over fused qkv [B*T][3d] -> out [B*T][d]
 template <typename T> void launch_enc_attn_simple(const T* qkv, T* out, int B, int T_, int H, hipStream_t s);
-template <typename T16> void launch_enc_attn_flash_bf16(const T16* qkv, T16* out, int B, int T_, int H, hipStream_t s);
+template <typename T16> void launch_enc_attn_flash_bf16(const T16* qkv, T16* out, int B, int T_, int H, const KernelOpts& ko, hipStream_t s);
 // cross-attention of n_q consecutive rows per clip against that clip's cross-KV cache, as one MFMA flash pass (prefill)
 template <typename T16>
 void launch_cross_attn_flash_bf16(const T16* q, const T16* K, const T16* V, T16* out, int n_clips, int n_q, int H, int Tk, hipStream_t s);
@@ -407,7 +419,7 @@ template <typename T>
 void launch_copy_pages(T* pool, const int32_t* pairs_dev, int n_pairs, int n_layers, int H, int64_t layer_elems, hipStream_t s);
 template <typename T>
 void launch_cross_attn_decode(const T* q /*[B][d]*/, const T* K, const T* V /*[B / kv_div][H][Tk][64]*/, T* out, int B, int H,
-                              int Tk, int kv_div, hipStream_t s,
+                              int Tk, int kv_div, const KernelOpts& ko, hipStream_t s,
                               float* split_ws = nullptr /*[B*H*8][66]: enables the split-frame variant for small B*H*/,
                               SlabIn sq = SlabIn{} /*q from K-split partial tiles*/,
                               int ws_rows = 0 /*rows the workspace was sized for (0: B); rows that share a clip (kv_div 2..8)
@@ -428,7 +440,7 @@ bool launch_cross_attn_fp8(const T* q, const uint8_t* K8, const uint8_t* V8, con
 // rule and workspace check as the cross_attn_mq_kernel branch of launch_cross_attn_decode; false: shape not taken
 template <typename T>
 bool launch_cross_attn_mq_fp8(const T* q, const uint8_t* K8, const uint8_t* V8, const float* kscale, const float* vscale, T* out, int B,
-                              int H, int Tk, int kv_div, hipStream_t s, float* split_ws, struct SlabIn sq, int ws_rows,
+                              int H, int Tk, int kv_div, const KernelOpts& ko, hipStream_t s, float* split_ws, struct SlabIn sq, int ws_rows,
                               const int32_t* done = nullptr);
 // the quantiser of a session's admission: n <= XkvSlotPairs::N (source slot of `src`, destination slot of the e4m3 copy) pairs
 struct XkvSlotPairs { static constexpr int N = 64; uint16_t src[N], dst[N]; };
@@ -442,20 +454,11 @@ extern thread_local char g_kernel_sig[192];
 template <typename T> inline const char* sig_type() { return sizeof(T) == 4 ? "float" : "unsigned short"; }
 template <> inline const char* sig_type<struct f16_t>() { return "f16_t"; }
 
-// Kernel-variant switches of the launchers (A/B experiments).  Thread-local: every C-ABI call copies its CONTEXT's setting in
-// before it launches anything (engine.hip guarded()), so an option set on one context never changes what another context's
-// thread launches or what its captured graphs hold.
 // A launcher asked for a configuration it has no kernel for (unreachable behind ttasr_create's geometry limits and
 // ttasr_set_option's ranges; kept as a guard for future callers): it records the reason here and launches NOTHING; the C-ABI
 // call that was running returns TTASR_E_INVALID with this text (engine.hip guarded()).  A library never abort()s its host.
 extern thread_local char g_launch_fault[160];
 void launch_fault(const char* fmt, ...);
-extern thread_local int g_skinny_x_lds;  // option dec_x_lds: decode GEMMs stage their activation tile through LDS (kernels_skinny.hip)
-extern thread_local int g_skinny_nt;     // option weights_nontemporal: nontemporal weight loads in the decode GEMMs
-extern thread_local int g_xattn_variant;  // option xattn_nontemporal: cross-attention kernel variant
-extern thread_local int g_flash_qw;           // option flash_qw (kernels_flash.hip): query blocks of 32 per wave, 1 | 2
-extern thread_local int g_xattn_mq_slices;    // option xattn_mq_slices (A/B)
-extern thread_local int g_xattn_deep_items;   // option xattn_deep_items (kernels_attn.hip cross_attn_pipe_kernel)
 // beam search: processed log-probabilities and ids of the k best tokens of every row (rules applied from the
 // per-row history state uploaded by the host)
 struct BeamRowState { const int32_t *n_sampled, *last_tok, *pen_tok, *last_ts; const uint8_t* mask; };

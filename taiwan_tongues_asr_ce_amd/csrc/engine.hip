@@ -40,7 +40,7 @@ static void adopt_weights(ttasr_ctx* c, ttasr_ctx* o) {
   c->conv1_b = o->conv1_b; c->conv2_b = o->conv2_b; c->epos = o->epos; c->elnf_g = o->elnf_g; c->elnf_b = o->elnf_b;
   c->dlnf_g = o->dlnf_g; c->dlnf_b = o->dlnf_b;
   c->enc = o->enc; c->dec = o->dec;
-  c->dec_narrow = o->dec_narrow; c->weights_packed = o->weights_packed;
+  c->ko.skinny_narrow = o->ko.skinny_narrow; c->weights_packed = o->weights_packed;
   c->finalized = true;
   c->weight_owner = o;
   std::lock_guard<std::mutex> lk(g_share_mu);
@@ -268,14 +268,10 @@ int ttasr_log_mel_windows(ttasr_ctx* c, const float* const* file_pcm_of, const i
     const int64_t file_frames = file_samples / 160;   // the whole-file STFT drops its last frame (HF feature extractor :154)
     const int64_t seek = seek_frames[b];
     if (seek < 0 || seek > file_frames) return fail(c, TTASR_E_INVALID, "seek_frames[%d]=%lld outside the recording (%lld frames)", b, (long long)seek, (long long)file_frames);
-    const int64_t start = seek * 160, lead = std::min<int64_t>(200, start);
-    const int64_t avail = std::min<int64_t>(file_samples - (start - lead), lead + c->n_samples + 200);  // samples from x[0]
-    ns[b] = std::max<int64_t>(avail, 0);
-    geom[3 * b] = lead;
-    // reflect where the FILE ends if that is inside the span this window's frames touch; otherwise never
-    geom[3 * b + 1] = (file_samples - (start - lead) < lead + c->n_samples + 200) ? file_samples - (start - lead) : ((int64_t)1 << 40);
-    geom[3 * b + 2] = std::min<int64_t>(c->F, file_frames - seek);
-    if (ns[b] > 0) HIPCHK(c, hipMemcpyAsync(c->pcm_dev + (int64_t)b * stride, file_pcm + (start - lead), ns[b] * 4, hipMemcpyHostToDevice, s));
+    const WindowSpan w = window_span(c, file_samples, seek);
+    ns[b] = w.n;
+    memcpy(&geom[3 * (size_t)b], w.geom, sizeof w.geom);
+    if (ns[b] > 0) HIPCHK(c, hipMemcpyAsync(c->pcm_dev + (int64_t)b * stride, file_pcm + w.first, ns[b] * 4, hipMemcpyHostToDevice, s));
   }
   HIPCHK(c, hipMemcpyAsync(c->nsamp_dev, ns.data(), B * 8, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpyAsync(c->mel_geom, geom.data(), (size_t)B * 24, hipMemcpyHostToDevice, s));
@@ -391,7 +387,6 @@ int ttasr_decode_reset(ttasr_ctx* c, int32_t B) {
   return guarded(c, [&]() -> int {
   TRY(check_ready(c, B));
   TRY(reset_search(c, B));
-  c->st.prompt = nullptr; c->st.prompt_len = nullptr;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->B_dec = B;
   return TTASR_OK;
@@ -417,11 +412,6 @@ int ttasr_decode_step(ttasr_ctx* c, const int32_t* tokens, int32_t B, float* log
   return TTASR_OK;
   });
 }
-
-int ttasr_generate(ttasr_ctx* c, int32_t B, const int32_t* prompt, const int32_t* prompt_len, int32_t max_prompt,
-                   const ttasr_gen_opts* o, int32_t* out_tokens, int32_t* out_len, float* out_lp, float* out_ns);
-
-
 
 int ttasr_generate(ttasr_ctx* c, int32_t B, const int32_t* prompt, const int32_t* prompt_len, int32_t max_prompt,
                    const ttasr_gen_opts* o, int32_t* out_tokens, int32_t* out_len, float* out_lp, float* out_ns) {
@@ -684,11 +674,11 @@ int ttasr_bench_kernel(ttasr_ctx* c, const char* name, int32_t B, int32_t iters,
       // the instantiation the decode step launches: 16-bit engines read the query from the q GEMM's K-split partial tiles
       SlabIn sqb;
       if (c->lowp && !c->force_basic && c->slab) {
-        const int ks = gemm_skinny_ksplit(B, c->d, c->d, c->ks_want[1] ? c->ks_want[1] : 4);
+        const int ks = gemm_skinny_ksplit(B, c->d, c->d, c->ks_want[1] ? c->ks_want[1] : 4, c->ko);
         if (ks > 1) { sqb.slab = c->slab; sqb.bias = c->dec[0].bqx; sqb.n = ks; sqb.stride = (int64_t)c->maxB * c->d; sqb.ld = c->d; }
       }
       TT_DISPATCH(c, launch_cross_attn_decode<T>((const T*)c->dq, (const T*)Kx, (const T*)Kx + c->xkv_which_elems, (T*)c->datt, B, c->H,
-                                                 c->T, 1, s, nullptr, sqb));
+                                                 c->T, 1, c->ko, s, nullptr, sqb));
       bytes = (double)B * (2.0 * T_ * d + 2.0 * d) * e; flops = (double)B * 4.0 * T_ * d;
     } else if (k == "xattn_beam5" || k == "xattn_beam5_rows") {
       // B rows = B / 5 clips x 5 hypotheses sharing their clip's cross-KV: one stream per clip ("xattn_beam5") or the
@@ -698,7 +688,7 @@ int ttasr_bench_kernel(ttasr_ctx* c, const char* name, int32_t B, int32_t iters,
       const char* Kx = (const char*)c->xkv + (size_t)(layer_rr2++ % c->cfg.dec_layers) * c->xkv_layer_elems * c->esz;
       float* ws = k == "xattn_beam5" ? c->xsplit_ws : nullptr;
       TT_DISPATCH(c, launch_cross_attn_decode<T>((const T*)c->dq, (const T*)Kx, (const T*)Kx + c->xkv_which_elems, (T*)c->datt, B, c->H,
-                                                 c->T, 5, s, ws, SlabIn{}, c->maxB));
+                                                 c->T, 5, c->ko, s, ws, SlabIn{}, c->maxB));
       bytes = (double)(B / 5) * 2.0 * T_ * d * e + (double)B * 2.0 * d * e; flops = (double)B * 4.0 * T_ * d;
     } else if (k == "enc_gemm_fc1") {
       GemmArgs g; g.A = c->h; g.W = c->enc[0].w1; g.M = B * c->T; g.N = c->ffn; g.K = c->d; g.lda = c->d; g.ldw = c->d;
@@ -728,7 +718,7 @@ int ttasr_bench_kernel(ttasr_ctx* c, const char* name, int32_t B, int32_t iters,
       TT_DISPATCH(c, {
         bool flash = false;
         if constexpr (sizeof(T) == 2) {
-          if (!c->force_basic && !c->no_flash) { launch_enc_attn_flash_bf16<T>((const T*)c->qkv, (T*)c->att, B, c->T, c->H, s); flash = true; }
+          if (!c->force_basic && !c->no_flash) { launch_enc_attn_flash_bf16<T>((const T*)c->qkv, (T*)c->att, B, c->T, c->H, c->ko, s); flash = true; }
         }
         if (!flash) launch_enc_attn_simple<T>((const T*)c->qkv, (T*)c->att, B, c->T, c->H, s);
       });

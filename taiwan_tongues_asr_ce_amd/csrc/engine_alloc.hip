@@ -249,10 +249,10 @@ int ingest_tensor(ttasr_ctx* c, const char* name, const void* src, int src_type,
   if (!to_f32) {
     if (c->f16) {
       launch_cast<f16_t>(c->stage_f32, (f16_t*)s.dst, n, c->stream);
-      if (s.sh_base) { launch_shuffle_cast<f16_t>(c->stage_f32, (f16_t*)s.sh_base, (int)s.rows, (int)s.cols, s.sh_row_off, c->stream, s.sh_rows_total); c->weights_packed = true; }
+      if (s.sh_base) { launch_shuffle_cast<f16_t>(c->stage_f32, (f16_t*)s.sh_base, (int)s.rows, (int)s.cols, s.sh_row_off, c->ko, c->stream, s.sh_rows_total); c->weights_packed = true; }
     } else {
       launch_cast<bf16_t>(c->stage_f32, (bf16_t*)s.dst, n, c->stream);
-      if (s.sh_base) { launch_shuffle_cast<bf16_t>(c->stage_f32, (bf16_t*)s.sh_base, (int)s.rows, (int)s.cols, s.sh_row_off, c->stream, s.sh_rows_total); c->weights_packed = true; }
+      if (s.sh_base) { launch_shuffle_cast<bf16_t>(c->stage_f32, (bf16_t*)s.sh_base, (int)s.rows, (int)s.cols, s.sh_row_off, c->ko, c->stream, s.sh_rows_total); c->weights_packed = true; }
     }
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));  // the staging buffers are reused by the next tensor

@@ -40,6 +40,14 @@ struct Slot {              // where one named tensor lands on the device
 };
 
 struct Session;            // continuous-batching session state (engine_refill.hip)
+// What run_decode_rows reads about the rows of a step, and (with the batch, the mode and the e4m3 state) what a captured step
+// graph is keyed on.  Installed and restored by SearchScope only.
+struct StepShape {
+  int kv_div = 1;            // rows per clip sharing one cross-KV (beam width); 1 for greedy
+  int identity_pages = 1;    // page_table is the identity map (greedy): the self-attention kernel computes page ids
+  bool rows_pos = false;     // per-row positions (continuous-batching session: row_pos instead of st.step)
+  bool operator==(const StepShape& o) const { return kv_div == o.kv_div && identity_pages == o.identity_pages && rows_pos == o.rows_pos; }
+};
 struct EncLayerW { float *ln1g, *ln1b, *bqkv, *bo, *ln2g, *ln2b, *b1, *b2; void *wqkv, *wo, *w1, *w2; };
 struct DecLayerW {
   float *ln1g, *ln1b, *bqkv, *bo, *ln2g, *ln2b, *bqx, *bkvx, *box, *ln3g, *ln3b, *b1, *b2;
@@ -97,8 +105,7 @@ struct ttasr_ctx {
   float* xsplit_ws = nullptr;  // split-frame cross-attention (small batches)
   float* dx = nullptr; void *dh = nullptr, *dqkv = nullptr, *dq = nullptr, *datt = nullptr, *dmid = nullptr; float* logits = nullptr;
   float* rows_out = nullptr;
-  int kv_div = 1;            // rows per clip sharing one cross-KV (beam width); 1 for greedy
-  int identity_pages = 1;    // page_table is the identity map (greedy): the self-attention kernel computes page ids
+  StepShape shape;           // the decode shape of the search that is running (SearchScope); the defaults between searches
   int32_t* pairs_dev = nullptr;  // beam search: copy-on-write page pairs
   float* topk_lp = nullptr; int32_t* topk_id = nullptr; int32_t* row_state = nullptr;  // beam search scratch
 #ifdef TTASR_EXPERIMENTS
@@ -125,9 +132,6 @@ struct ttasr_ctx {
   std::atomic<int> sharers{0};
   bool destroy_pending = false;
   int32_t* row_cap_dev = nullptr;   // [maxB] per-row token budgets (st.row_cap; ttasr_generate_capped), "no budget" = 0x7f7f7f7f
-  int flash_qw = 2;                 // option flash_qw: query blocks of 32 per wave in the encoder's flash attention (1 = the round-5 kernel)
-  int xattn_mq_slices = 0;          // option xattn_mq_slices (A/B): 0 = automatic
-  int xattn_deep_items = 512;       // option xattn_deep_items: see kernels_attn.hip cross_attn_pipe_kernel (0: never stream deep; 512 = 2 per CU: measured optimum, profiles/r6_xattn_deep_sweep.jsonl)
   bool ragged_exit = true;          // option ragged_exit [1]: finished rows (st.done) leave the attention kernels of the decode step
                                     // (0: the static batch of rounds 1-5 - every row streams its cross-KV until the last one ends; A/B)
   RuleDyn* rule_dyn_dev = nullptr; RuleDyn rule_dyn_host{};  // per-window rule scalars read by select_kernel (common.hpp RuleDyn)
@@ -144,7 +148,6 @@ struct ttasr_ctx {
 
   // continuous-batching session (engine_refill.hip): open between ttasr_session_begin[_beam] and ttasr_session_end
   ttasr_detail::Session* sess = nullptr;
-  bool session_rows = false;      // the decode step runs the per-row-position kernel forms (row_pos instead of st.step)
   bool refill_overlap = false;    // option refill_overlap: encode the next clips on a second stream under the step graphs (opt-in:
                                   // a second stream = a second hardware queue, which makes processes sharing the GPU time-slice)
   int32_t* row_pos = nullptr;     // [maxB] per-row positions of the session (allocated by the first session)
@@ -158,11 +161,9 @@ struct ttasr_ctx {
 
   int B_mel = 0, B_enc = 0, B_dec = 0;
   std::atomic_flag busy = ATOMIC_FLAG_INIT;  // one call in flight per context: a second concurrent call is refused
-  int xattn_nt = 1, xattn_pipe = 1, weights_nt = 1;  // options xattn_nontemporal / xattn_pipeline / weights_nontemporal (per context; copied into the launchers' thread-locals by guarded())
-  bool dec_narrow = true;   // option dec_narrow_blocks: 20-row n-blocks for the decode matrices whose 32-row block count does not fill the 256 CUs evenly (fixed once weights are packed)
+  KernelOpts ko;            // the kernel-variant options of this context (common.hpp), handed to every launcher that picks a variant
   bool weights_packed = false;
   bool enc_ln_defer = true; // option enc_ln_defer = 0: every encoder LayerNorm folds its delta into the f32 residual stream (two read-modify-writes per layer; A/B testing, bit-identical)
-  bool dec_x_lds = true;    // option dec_x_lds = 0: decode GEMM activation fragments loaded straight from memory (the round-5 form; A/B, bit-identical)
   bool gemm_tail = true;    // option enc_gemm_tail = 0: plain 256-row tiling in the persistent encoder GEMM (A/B testing; bit-identical)
   bool xkv_grouped = true;  // option xkv_grouped = 0: one cross-KV GEMM launch per decoder layer instead of one grouped launch (A/B testing; bit-identical)
   bool multi_step = true;   // option multi_step_graph = 0: one graph replay per decode step (A/B testing)
@@ -179,9 +180,13 @@ struct ttasr_ctx {
   std::vector<int> enc_ev_class;
   float enc_class_ms[8]{0, 0, 0, 0, 0, 0, 0, 0};
 
-  // decode-step graphs keyed by (B, with_logits)
-  struct GraphKey { int B; int mode; int variant; hipGraphExec_t exec; };
-  std::vector<GraphKey> graphs;   // least recently used first
+  // decode-step graphs, keyed by everything that decides which kernels a captured step holds (engine_sched.hip step_graph)
+  struct GraphKey {
+    int B, mode, nsteps; StepShape shape; int fp8_live;
+    bool operator==(const GraphKey& o) const { return B == o.B && mode == o.mode && nsteps == o.nsteps && shape == o.shape && fp8_live == o.fp8_live; }
+  };
+  struct Graph { GraphKey key; hipGraphExec_t exec; };
+  std::vector<Graph> graphs;   // least recently used first
   static constexpr size_t kMaxGraphs = 32;   // per batch size up to four step graphs exist (1- / 4- / 8-step greedy, logits-only): 8 batch sizes stay resident
   RuleParams rp{};
 };
@@ -209,7 +214,6 @@ inline int guarded(ttasr_ctx* c, F&& f) {
     ~Busy() { if (c && own) c->busy.clear(std::memory_order_release); }
   } busy(c);
   if (!busy.own) return TTASR_E_INVALID;
-  if (c) { g_xattn_variant = c->xattn_nt | (c->xattn_pipe << 1); g_skinny_nt = c->weights_nt; g_skinny_narrow = c->dec_narrow ? 1 : 0; g_skinny_x_lds = c->dec_x_lds ? 1 : 0; g_xattn_deep_items = c->xattn_deep_items; g_xattn_mq_slices = c->xattn_mq_slices; g_flash_qw = c->flash_qw; }   // this context's kernel variants for everything f launches
   g_launch_fault[0] = 0;
   try {
     const int rc = f();
@@ -317,6 +321,18 @@ int step_graph(ttasr_ctx* c, int B, int mode, int nsteps = 1);
 void drop_graphs(ttasr_ctx* c);
 void drop_rule_graphs(ttasr_ctx* c);
 
+// One 30-s window of a recording from frame `seek`: the samples its STFT reads - `lead` before the window (200, fewer at the file
+// start), the window, 200 after, cut at the end of the file - and the geometry launch_mel takes: {lead, reflect_end, valid_frames}.
+// The signal is reflected where the FILE ends if that is inside the span; the whole-file STFT drops its last frame (HF feature
+// extractor :154).  Callers check seek against the recording first.
+struct WindowSpan { int64_t first, n, geom[3]; };
+inline WindowSpan window_span(const ttasr_ctx* c, int64_t file_samples, int64_t seek) {
+  const int64_t start = seek * 160, lead = std::min<int64_t>(200, start);
+  const int64_t left = file_samples - (start - lead), span = lead + c->n_samples + 200;
+  return WindowSpan{start - lead, std::max<int64_t>(std::min(left, span), 0),
+                    {lead, left < span ? left : ((int64_t)1 << 40), std::max<int64_t>(std::min<int64_t>(c->F, file_samples / 160 - seek), 0)}};
+}
+
 // ---- engine_refill.hip: the continuous-batching session (greedy and beam search) ----
 int session_refusal(ttasr_ctx* c);   // TTASR_E_INVALID with a message while a session is open, else 0
 void session_free(ttasr_ctx* c);     // ttasr_destroy: the session's stream, events and pinned memory
@@ -330,6 +346,21 @@ int align_batch_validate(ttasr_ctx* c, const AlignBatch& a);
 int align_batch_run(ttasr_ctx* c, const AlignBatch& a, const int32_t* slot /*[n]*/, const int32_t* pages /*[n][pages_per_seq]*/);
 
 // ---- engine_search.hip: rules, options, greedy / sampled / beam search ----
+// The decode shape of ONE search (a static search's call, or a session from begin to end / free): installs the StepShape and the
+// prompt rows the select kernel forces; every exit - error returns included - restores the defaults (kv_div 1, identity pages,
+// static positions, no prompt) and enqueues the clear of the rows' finished flags, which belong to the search: later step-level
+// calls see live rows.
+struct SearchScope {
+  ttasr_ctx* c; int rows;
+  SearchScope(ttasr_ctx* c_, StepShape shape, const int32_t* prompt, const int32_t* prompt_len, int rows_) : c(c_), rows(rows_) {
+    c->shape = shape; c->st.prompt = prompt; c->st.prompt_len = prompt_len;
+  }
+  ~SearchScope() {
+    c->shape = StepShape{}; c->st.prompt = nullptr; c->st.prompt_len = nullptr;
+    (void)hipMemsetAsync(c->st.done, 0, (size_t)rows * 4, c->stream);
+  }
+  SearchScope(const SearchScope&) = delete; SearchScope& operator=(const SearchScope&) = delete;
+};
 int check_ready(ttasr_ctx* c, int B);
 int upload_rules(ttasr_ctx* c, const ttasr_gen_opts* o, int max_prompt);
 int commit_rules(ttasr_ctx* c, const RuleParams& old);

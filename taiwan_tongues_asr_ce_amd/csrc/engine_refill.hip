@@ -80,6 +80,7 @@ struct Session {
   std::vector<double> sums;
   BeamPages pages;
   std::vector<int32_t> cur_tok, done_rows, pairs;
+  std::unique_ptr<SearchScope> scope;   // the session's decode shape, from session_begin to session_end / session_free
 };
 
 int session_refusal(ttasr_ctx* c) {
@@ -93,10 +94,8 @@ void session_free(ttasr_ctx* c) {
   if (S->es && S->es != c->stream) { hipStreamSynchronize(S->es); hipStreamDestroy(S->es); }
   for (hipEvent_t e : {S->ev_enc0, S->ev_enc, S->ev_copy, S->ev_dec0, S->ev_dec1}) if (e) hipEventDestroy(e);
   if (S->pin) hipHostFree(S->pin);
-  delete S;
+  delete S;   // with its scope: the context is back to the defaults of a static search
   c->sess = nullptr;
-  c->session_rows = false;
-  c->kv_div = 1; c->identity_pages = 1;
 }
 
 static int n_free_rows(const Session* S) {
@@ -297,7 +296,7 @@ static int pump(ttasr_ctx* c, Session* S) {
   return 0;
 }
 
-static int session_begin(ttasr_ctx* c, const ttasr_gen_opts* o, int max_prompt, float temperature) {
+static int session_begin(ttasr_ctx* c, const ttasr_gen_opts* o, int max_prompt, float temperature, StepShape shape) {
   if (!c) return TTASR_E_INVALID;
   if (!c->finalized) return fail(c, TTASR_E_INVALID, "weights not finalized (call ttasr_finalize_weights first)");
   TRY(session_refusal(c));
@@ -337,8 +336,10 @@ static int session_begin(ttasr_ctx* c, const ttasr_gen_opts* o, int max_prompt, 
   } else {
     S->es = c->stream;
   }
-  // every row free: finished (done = 1, n_done = max_batch), position 0, a valid token, a one-token prompt
+  // the search state of a static search, except: every row free - finished (done = 1, n_done = max_batch) - at position 0 with a
+  // valid token and a one-token prompt
   hipStream_t s = c->stream;
+  TRY(reset_search(c, B));
   int32_t* p = S->pin;
   for (int r = 0; r < B; ++r) { p[r] = 1; p[B + r] = 0; p[2 * B + r] = 1; p[3 * B + r] = B; }
   HIPCHK(c, hipMemcpyAsync(c->st.done, p, (size_t)B * 4, hipMemcpyHostToDevice, s));
@@ -346,19 +347,10 @@ static int session_begin(ttasr_ctx* c, const ttasr_gen_opts* o, int max_prompt, 
   HIPCHK(c, hipMemcpyAsync(c->plen_dev, p + 2 * B, (size_t)B * 4, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemsetAsync(c->row_pos, 0, (size_t)B * 4, s));
   HIPCHK(c, hipMemsetAsync(c->st.cur_tok, 0, (size_t)B * 4, s));
-  HIPCHK(c, hipMemsetAsync(c->st.n_sampled, 0, (size_t)B * 4, s));
-  HIPCHK(c, hipMemsetAsync(c->st.last_tok, 0xff, (size_t)B * 4, s));
-  HIPCHK(c, hipMemsetAsync(c->st.pen_tok, 0xff, (size_t)B * 4, s));
-  HIPCHK(c, hipMemsetAsync(c->st.last_ts, 0xff, (size_t)B * 4, s));
-  HIPCHK(c, hipMemsetAsync(c->st.sum_logprob, 0, (size_t)B * 4, s));
-  HIPCHK(c, hipMemsetAsync(c->st.no_speech, 0, (size_t)B * 4, s));
-  HIPCHK(c, hipMemsetAsync(c->row_cap_dev, 0x7f, (size_t)B * 4, s));
   HIPCHK(c, hipEventRecord(S->ev_copy, s));
   HIPCHK(c, hipStreamSynchronize(s));
-  c->st.prompt = c->prompt_dev; c->st.prompt_len = c->plen_dev;
-  c->kv_div = 1; c->identity_pages = 1;
+  S->scope.reset(new SearchScope(c, shape, c->prompt_dev, c->plen_dev, B));
   c->B_mel = c->B_enc = c->B_dec = 0;   // the session rewrites the encoder state and the cross-KV of every row
-  c->session_rows = true;
   // mode 2: the e4m3 copy is live for the whole session.  A free slot's stale block is never read: its rows are finished rows
   c->xkv8_valid = c->xkv_fp8 == 2 && c->xkv8 && c->xkv8_scale && c->lowp;
   c->sess = S.release();
@@ -374,7 +366,8 @@ static int session_begin_beam(ttasr_ctx* c, const ttasr_gen_opts* o, int max_pro
   if (beam < 1 || beam > 7) return fail(c, TTASR_E_INVALID, "beam %d outside [1, 7]", beam);
   if (c->maxB < beam) return fail(c, TTASR_E_INVALID, "max_batch %d holds no group of %d rows", c->maxB, beam);
   if (!(patience > 0.f)) return fail(c, TTASR_E_INVALID, "patience %g must be > 0", patience);
-  TRY(session_begin(c, o, max_prompt, 0.f));   // rules, buffers, streams; every row free (done = 1)
+  // rules, buffers, streams; every row free (done = 1).  Group g reads cross-KV slot g; rows read their own (shared) page lists
+  TRY(session_begin(c, o, max_prompt, 0.f, StepShape{beam, 0, true}));
   Session* S = c->sess;
   const int G = c->maxB / beam, R = G * beam;
   S->beam = beam; S->G = G; S->max_cand = std::max(1, (int)std::lround(beam * patience)); S->patience = patience;
@@ -385,7 +378,6 @@ static int session_begin_beam(ttasr_ctx* c, const ttasr_gen_opts* o, int max_pro
   BeamExchange x;
   if (beam_exchange(c, R, beam + 1, x) != 0) { session_free(c); c->xkv8_valid = false; return TTASR_E_HIP; }   // the steps' pinned block exists from here on
   if (!c->sess_sel && dalloc(c, &c->sess_sel, (size_t)c->maxB * 9 * 4) != 0) { session_free(c); c->xkv8_valid = false; return TTASR_E_HIP; }
-  c->kv_div = beam; c->identity_pages = 0;   // group g reads cross-KV slot g; rows read their own (shared) page lists
   return TTASR_OK;
 }
 
@@ -616,15 +608,10 @@ static int session_submit_windows(ttasr_ctx* c, int n, const float* const* file_
       return fail(c, TTASR_E_INVALID, "window %d: temperature %g must be finite and >= 0", i, temperature[i]);
     Session::Clip& cl = cls[i];
     TRY(init_clip(c, S, i, prompt, prompt_len, S->o.no_speech >= 0 ? &sot_index[i] : nullptr, max_new, cl));
-    // the span of ttasr_log_mel_windows: `lead` samples before the window (200, fewer at the file start), the window, 200 after
-    const int64_t fs = file_samples[i], file_frames = fs / 160, seek = seek_frames[i];
-    const int64_t start = seek * 160, lead = std::min<int64_t>(200, start);
-    const int64_t avail = std::max<int64_t>(std::min<int64_t>(fs - (start - lead), lead + c->n_samples + 200), 0);
-    cl.pcm.assign(file_pcm[i] + (start - lead), file_pcm[i] + (start - lead) + avail);
+    const WindowSpan w = window_span(c, file_samples[i], seek_frames[i]);   // the span and geometry of ttasr_log_mel_windows
+    cl.pcm.assign(file_pcm[i] + w.first, file_pcm[i] + w.first + w.n);
     cl.win = true;
-    cl.geom[0] = lead;
-    cl.geom[1] = (fs - (start - lead) < lead + c->n_samples + 200) ? fs - (start - lead) : ((int64_t)1 << 40);
-    cl.geom[2] = std::max<int64_t>(std::min<int64_t>(c->F, file_frames - seek), 0);
+    memcpy(cl.geom, w.geom, sizeof w.geom);
     if (floor_max) { cl.has_floor = true; cl.floor = mel_max_to_ordered(floor_max[i]); }
     cl.sot = sot_index[i];
     cl.temp = temperature ? temperature[i] : 0.f;
@@ -806,12 +793,9 @@ static int session_end(ttasr_ctx* c) {
   if (!c->sess) return fail(c, TTASR_E_INVALID, "no session is open");
   Session* S = c->sess;
   if (S->es && S->es != c->stream) hipStreamSynchronize(S->es);
-  // the flags belong to the session: later step-level calls see live rows (as after every search)
-  hipMemsetAsync(c->st.done, 0, (size_t)c->maxB * 4, c->stream);
+  session_free(c);   // the session's scope ends: default decode shape, the rows' finished flags cleared (as after every search)
   hipMemsetAsync(c->st.n_done, 0, 16, c->stream);
   const hipError_t e = hipStreamSynchronize(c->stream);
-  session_free(c);
-  c->st.prompt = nullptr; c->st.prompt_len = nullptr;
   c->B_mel = c->B_enc = c->B_dec = 0;
   c->xkv8_valid = false;   // like the rest of the resident encoder state: rebuilt by the next encode
   if (e != hipSuccess) return fail(c, TTASR_E_HIP, "session end: %s", hipGetErrorString(e));
@@ -824,7 +808,7 @@ static int session_end(ttasr_ctx* c) {
 extern "C" {
 
 int ttasr_session_begin(ttasr_ctx* c, const ttasr_gen_opts* o, int32_t max_prompt, float temperature) {
-  return guarded(c, [&]() -> int { return session_begin(c, o, max_prompt, temperature); });
+  return guarded(c, [&]() -> int { return session_begin(c, o, max_prompt, temperature, StepShape{1, 1, true}); });
 }
 
 int ttasr_session_begin_beam(ttasr_ctx* c, const ttasr_gen_opts* o, int32_t max_prompt, int32_t beam, float patience) {

@@ -49,8 +49,8 @@ void dec_gemm(ttasr_ctx* c, const GemmArgs& g, const void* Wsh) {
       // the vocabulary projection (f32 logits, nothing else in the epilogue): persistent workgroups, activation rows in registers
       const GemmEpi& e = g.epi;
       if (c->vocab_persistent && e.out_f32 && !e.out_t && !e.bias && !e.residual && e.act == 0 &&
-          launch_gemm_vocab<T>((const T*)Wsh, (const T*)g.A, g.M, g.N, g.K, e.out_f32, e.ldc, c->cur, c->device)) return;
-      if (launch_gemm_skinny<T>((const T*)Wsh, (const T*)g.A, g.M, g.N, g.K, g.epi, c->cur)) return;
+          launch_gemm_vocab<T>((const T*)Wsh, (const T*)g.A, g.M, g.N, g.K, e.out_f32, e.ldc, c->ko, c->cur, c->device)) return;
+      if (launch_gemm_skinny<T>((const T*)Wsh, (const T*)g.A, g.M, g.N, g.K, g.epi, c->ko, c->cur)) return;
     }
   }
   launch_gemm_basic<T>(g, c->cur);
@@ -171,7 +171,7 @@ int run_encoder(ttasr_ctx* c, int B) {
     enc_mark(c, EC_QKV);
     bool flash = false;
     if constexpr (sizeof(T) == 2) {
-      if (!c->force_basic && !c->no_flash) { launch_enc_attn_flash_bf16<T>((const T*)c->qkv, (T*)c->att, B, T_, c->H, s); flash = true; }
+      if (!c->force_basic && !c->no_flash) { launch_enc_attn_flash_bf16<T>((const T*)c->qkv, (T*)c->att, B, T_, c->H, c->ko, s); flash = true; }
     }
     if (!flash) launch_enc_attn_simple<T>((const T*)c->qkv, (T*)c->att, B, T_, c->H, s);
     enc_mark(c, EC_ATTN);
@@ -214,7 +214,8 @@ void run_decode_rows(ttasr_ctx* c, int row0, int n, int mode, int total_rows) {
   // kernels of the step - the per-row cross-KV and self-KV streams are the bytes of a decode step that scale with the rows
   // the continuous-batching session (engine_refill.hip) runs the per-row-position forms of the three kernels that read the position;
   // its idle and finished rows always leave the attention kernels (their slots may be refilled by a concurrent encode)
-  const bool rows_pos = c->session_rows;
+  const StepShape& sh = c->shape;
+  const bool rows_pos = sh.rows_pos;
   const int32_t* done = (c->ragged_exit || rows_pos) ? c->st.done + row0 : nullptr;
   float* slab_base = c->slab;
   // K slices per GEMM kind (0 out-proj, 1 q, 2 qkv, 3 fc2); attention consumers sum at most 4 slabs
@@ -228,8 +229,8 @@ void run_decode_rows(ttasr_ctx* c, int row0, int n, int mode, int total_rows) {
     // search, streaming: 33-128 rows) keep the automatic choice, whose k-steps per wave fit the straight-line form.
     // (A different K split is a different summation order: the 16-bit token CRC of the benchmark was re-recorded with this change.)
     if (kind == 2 && want == 0 && n <= 32 && (N + 31) / 32 >= 96) want = 1;
-    int ks = gemm_skinny_ksplit(n, N, K, want);
-    if ((kind == 1 || kind == 2) && ks > 4) ks = gemm_skinny_ksplit(n, N, K, 4);
+    int ks = gemm_skinny_ksplit(n, N, K, want, c->ko);
+    if ((kind == 1 || kind == 2) && ks > 4) ks = gemm_skinny_ksplit(n, N, K, 4, c->ko);
     return ks;
   };
   // what the next LayerNorm still has to add to the residual rows (K-split residual GEMM) or to create (embedding)
@@ -243,7 +244,7 @@ void run_decode_rows(ttasr_ctx* c, int row0, int n, int mode, int total_rows) {
         GemmEpi ep; ep.ldc = g.N;
         float* slab = slab_base;  // rows are local to this chain's region: [ks][maxB][N]
         const int64_t stride = (int64_t)c->maxB * g.N;
-        if (launch_gemm_skinny<T>((const T*)Wsh, (const T*)g.A, n, g.N, g.K, ep, s, ks, slab, stride)) {
+        if (launch_gemm_skinny<T>((const T*)Wsh, (const T*)g.A, n, g.N, g.K, ep, c->ko, s, ks, slab, stride)) {
           si.slab = slab; si.bias = bias; si.n = ks; si.stride = stride; si.ld = g.N;
         }
       }
@@ -278,10 +279,10 @@ void run_decode_rows(ttasr_ctx* c, int row0, int n, int mode, int total_rows) {
       if (!sqkv.n) { g.epi.bias = L.bqkv; g.epi.out_t = dqkv; dec_gemm<T>(c, g, L.wqkv_sh); } }
     if (!(c->skip_mask & 4) && rows_pos)
       launch_self_attn_decode_rows<T>((const T*)dqkv, (T*)c->pool, c->page_table, c->pages_per_seq, (int64_t)l * c->pool_layer_elems,
-                                      c->identity_pages, row0, c->row_pos, (T*)datt, n, c->H, s, sqkv, done);
+                                      sh.identity_pages, row0, c->row_pos, (T*)datt, n, c->H, s, sqkv, done);
     else if (!(c->skip_mask & 4))
       launch_self_attn_decode<T>((const T*)dqkv, (T*)c->pool, c->page_table, c->pages_per_seq, (int64_t)l * c->pool_layer_elems,
-                                 c->identity_pages, row0, c->st.step, (T*)datt, n, c->H, s, sqkv, done);
+                                 sh.identity_pages, row0, c->st.step, (T*)datt, n, c->H, s, sqkv, done);
     residual_gemm(datt, L.wo, L.wo_sh, L.bo, d, 0);
     ln(L.ln2g, L.ln2b);
     SlabIn sq;
@@ -289,27 +290,27 @@ void run_decode_rows(ttasr_ctx* c, int row0, int n, int mode, int total_rows) {
       sq = split_gemm(g, L.wqx_sh, L.bqx, slices(1, d, d));
       if (!sq.n) { g.epi.bias = L.bqx; g.epi.out_t = dq; dec_gemm<T>(c, g, L.wqx_sh); } }
     // cross-KV of clip (row / kv_div); a half-batch offset is only used with kv_div == 1
-    const T* Kx = (const T*)c->xkv + (int64_t)l * c->xkv_layer_elems + (int64_t)(row0 / c->kv_div) * c->H * c->T * 64;
+    const T* Kx = (const T*)c->xkv + (int64_t)l * c->xkv_layer_elems + (int64_t)(row0 / sh.kv_div) * c->H * c->T * 64;
     bool fp8_done = false;
     if constexpr (sizeof(T) == 2) {   // opt-in: the e4m3 copy of the cache, unshared rows that fill the chip (the single-pass kernel's case)
-      if (c->xkv_fp8 && c->xkv8_valid && c->kv_div == 1 && n * c->H >= 256 && skinny && !(c->skip_mask & 8)) {
+      if (c->xkv_fp8 && c->xkv8_valid && sh.kv_div == 1 && n * c->H >= 256 && skinny && !(c->skip_mask & 8)) {
         const int64_t off = (int64_t)l * c->xkv_layer_elems + (int64_t)row0 * c->H * c->T * 64;
         const float* ksc = c->xkv8_scale + ((size_t)l * 2) * c->maxB * c->H + (size_t)row0 * c->H;
         fp8_done = launch_cross_attn_fp8<T>((const T*)dq, c->xkv8 + off, c->xkv8 + off + c->xkv_which_elems, ksc, ksc + (size_t)c->maxB * c->H,
                                             (T*)datt, n, c->H, c->T, s, sq, done);
-      } else if (c->xkv_fp8 == 2 && c->xattn_mq_fp8 && c->xkv8_valid && c->kv_div >= 2 && skinny && !c->no_xsplit && !(c->skip_mask & 8)) {
+      } else if (c->xkv_fp8 == 2 && c->xattn_mq_fp8 && c->xkv8_valid && sh.kv_div >= 2 && skinny && !c->no_xsplit && !(c->skip_mask & 8)) {
         // mode 2: rows that share a clip (beam hypotheses, sampled attempts) - wherever the 16-bit path would take
         // cross_attn_mq_kernel with kv_div = 2..7, its e4m3 form; every other shape falls through to the 16-bit kernels
-        const int clip0 = row0 / c->kv_div;
+        const int clip0 = row0 / sh.kv_div;
         const int64_t off = (int64_t)l * c->xkv_layer_elems + (int64_t)clip0 * c->H * c->T * 64;
         const float* ksc = c->xkv8_scale + ((size_t)l * 2) * c->maxB * c->H + (size_t)clip0 * c->H;
         fp8_done = launch_cross_attn_mq_fp8<T>((const T*)dq, c->xkv8 + off, c->xkv8 + off + c->xkv_which_elems, ksc, ksc + (size_t)c->maxB * c->H,
-                                               (T*)datt, n, c->H, c->T, c->kv_div, s, c->xsplit_ws + (size_t)row0 * c->H * 8 * 66, sq,
+                                               (T*)datt, n, c->H, c->T, sh.kv_div, c->ko, s, c->xsplit_ws + (size_t)row0 * c->H * 8 * 66, sq,
                                                c->maxB - row0, done);
       }
     }
     if (!fp8_done && !(c->skip_mask & 8))
-      launch_cross_attn_decode<T>((const T*)dq, Kx, Kx + c->xkv_which_elems, (T*)datt, n, c->H, c->T, c->kv_div, s,
+      launch_cross_attn_decode<T>((const T*)dq, Kx, Kx + c->xkv_which_elems, (T*)datt, n, c->H, c->T, sh.kv_div, c->ko, s,
                                   c->no_xsplit ? nullptr : c->xsplit_ws + (size_t)row0 * c->H * 8 * 66, sq, c->maxB - row0, QProj{}, done);
     residual_gemm(datt, L.wox, L.wox_sh, L.box, d, 0);
     ln(L.ln3g, L.ln3b);
@@ -353,7 +354,7 @@ void run_prefill(ttasr_ctx* c, int n_seq, int npos, int seq_per_clip, int max_pr
   struct { const float* bias = nullptr; int n_slab = 0; int64_t stride = 0; } pend;
   auto pgemm = [&](const GemmArgs& g, const void* Wsh) {
     if constexpr (sizeof(T) == 2) {
-      if (small && Wsh && launch_gemm_skinny<T>((const T*)Wsh, (const T*)g.A, g.M, g.N, g.K, g.epi, s)) return;
+      if (small && Wsh && launch_gemm_skinny<T>((const T*)Wsh, (const T*)g.A, g.M, g.N, g.K, g.epi, c->ko, s)) return;
     }
     gemm<T>(c, g);
   };
@@ -362,12 +363,12 @@ void run_prefill(ttasr_ctx* c, int n_seq, int npos, int seq_per_clip, int max_pr
     SlabIn si;
     if constexpr (sizeof(T) == 2) {
       if (slabbed && Wsh) {
-        int ks = gemm_skinny_ksplit(n, g.N, g.K, 0);
-        if (ks > max_ks) ks = gemm_skinny_ksplit(n, g.N, g.K, max_ks);
+        int ks = gemm_skinny_ksplit(n, g.N, g.K, 0, c->ko);
+        if (ks > max_ks) ks = gemm_skinny_ksplit(n, g.N, g.K, max_ks, c->ko);
         const int64_t stride = (int64_t)n * g.N;
         GemmEpi ep; ep.ldc = g.N;
         if (ks > 1 && ks * stride <= slab_cap &&
-            launch_gemm_skinny<T>((const T*)Wsh, (const T*)g.A, n, g.N, g.K, ep, s, ks, c->slab, stride)) {
+            launch_gemm_skinny<T>((const T*)Wsh, (const T*)g.A, n, g.N, g.K, ep, c->ko, s, ks, c->slab, stride)) {
           si.slab = c->slab; si.bias = bias; si.n = ks; si.stride = stride; si.ld = g.N;
         }
       }
@@ -396,7 +397,7 @@ void run_prefill(ttasr_ctx* c, int n_seq, int npos, int seq_per_clip, int max_pr
     ln(L.ln1g, L.ln1b);
     { GemmArgs g = lin_args<T>(h, L.wqkv, n, 3 * d, d); g.epi.bias = L.bqkv; g.epi.out_t = qkv; pgemm(g, L.wqkv_sh); }
     launch_self_attn_prefill<T>((const T*)qkv, (T*)c->pool, own_pages ? al->page_table : c->page_table, c->pages_per_seq,
-                                (int64_t)l * c->pool_layer_elems, own_pages ? 0 : c->identity_pages, (T*)att, n_seq, npos, c->H, s);
+                                (int64_t)l * c->pool_layer_elems, own_pages ? 0 : c->shape.identity_pages, (T*)att, n_seq, npos, c->H, s);
     residual_gemm(att, L.wo, L.wo_sh, L.bo, d);
     ln(L.ln2g, L.ln2b);
     SlabIn sq;   // the query of the cross-attention: K-split too when its consumer can sum slabs (not the alignment pass)
@@ -412,7 +413,7 @@ void run_prefill(ttasr_ctx* c, int n_seq, int npos, int seq_per_clip, int max_pr
       launch_cross_attn_probs<T>((const T*)qkv, Kc, Kc + c->xkv_which_elems, (T*)att, n, c->H, c->T, al->sel + (size_t)l * c->H,
                                  al->probs, s);
     } else {
-      launch_cross_attn_decode<T>((const T*)qkv, Kx, Kx + c->xkv_which_elems, (T*)att, n, c->H, c->T, npos * seq_per_clip, s,
+      launch_cross_attn_decode<T>((const T*)qkv, Kx, Kx + c->xkv_which_elems, (T*)att, n, c->H, c->T, npos * seq_per_clip, c->ko, s,
                                   c->no_xsplit ? nullptr : c->xsplit_ws, sq, c->maxB);
     }
     residual_gemm(att, L.wox, L.wox_sh, L.box, d);
@@ -478,9 +479,9 @@ int step_graph(ttasr_ctx* c, int B, int mode, int nsteps) {
   // set_option(xkv_fp8) and the next encode held the 16-bit kernel and kept replaying after the copy existed)
   // ... and WHICH mode it is read in: 1 and 2 pick different kernels for shared rows, and so does option xattn_mq_fp8 under mode 2
   const int fp8_live = (c->xkv_fp8 && c->xkv8_valid) ? (c->xkv_fp8 == 2 ? (c->xattn_mq_fp8 ? 3 : 2) : 1) : 0;
-  const int variant = ((c->kv_div * 2 + c->identity_pages) * 4 + fp8_live) * 64 + nsteps + (c->session_rows ? 1 << 24 : 0);
+  const ttasr_ctx::GraphKey key{B, mode, nsteps, c->shape, fp8_live};
   for (size_t i = 0; i < c->graphs.size(); ++i) {
-    if (c->graphs[i].B == B && c->graphs[i].mode == mode && c->graphs[i].variant == variant) {
+    if (c->graphs[i].key == key) {
       // most recently used at the back: the cache is bounded (the streaming micro-batcher varies B from 1 to max_batch rows)
       if (i + 1 != c->graphs.size()) std::rotate(c->graphs.begin() + i, c->graphs.begin() + i + 1, c->graphs.end());
       HIPCHK(c, hipGraphLaunch(c->graphs.back().exec, c->stream));
@@ -499,7 +500,7 @@ int step_graph(ttasr_ctx* c, int B, int mode, int nsteps) {
     hipGraphExecDestroy(c->graphs.front().exec);
     c->graphs.erase(c->graphs.begin());
   }
-  c->graphs.push_back({B, mode, variant, exec});
+  c->graphs.push_back({key, exec});
   HIPCHK(c, hipGraphLaunch(exec, c->stream));
   return 0;
 }
@@ -515,7 +516,7 @@ void drop_graphs(ttasr_ctx* c) {
 void drop_rule_graphs(ttasr_ctx* c) {
   size_t k = 0;
   for (auto& g : c->graphs) {
-    if (g.mode == 1) c->graphs[k++] = g; else hipGraphExecDestroy(g.exec);
+    if (g.key.mode == 1) c->graphs[k++] = g; else hipGraphExecDestroy(g.exec);
   }
   c->graphs.resize(k);
 }

@@ -74,13 +74,13 @@ int set_option(ttasr_ctx* c, const std::string& key, int v) {
   else if (key == "xkv_grouped") c->xkv_grouped = on;
   else if (key == "enc_gemm_tail") c->gemm_tail = on;
   else if (key == "enc_ln_defer") c->enc_ln_defer = on;
-  else if (key == "dec_narrow_blocks") { if (c->weights_packed && on != c->dec_narrow) return 1; c->dec_narrow = on; }   // a layout choice: before the first weight arrives
+  else if (key == "dec_narrow_blocks") { if (c->weights_packed && on != (c->ko.skinny_narrow != 0)) return 1; c->ko.skinny_narrow = on; }   // a layout choice: before the first weight arrives
   else if (key == "ksplit_out") { if (v < 0 || v > 16) return 1; c->ks_want[0] = v; }
   else if (key == "ksplit_q") { if (v < 0 || v > 16) return 1; c->ks_want[1] = v; }
   else if (key == "ksplit_qkv") { if (v < 0 || v > 16) return 1; c->ks_want[2] = v; }
   else if (key == "ksplit_fc2") { if (v < 0 || v > 16) return 1; c->ks_want[3] = v; }
-  else if (key == "xattn_nontemporal") c->xattn_nt = on ? 1 : 0;   // per context (kernel template choice)
-  else if (key == "xattn_pipeline") c->xattn_pipe = on ? 1 : 0;
+  else if (key == "xattn_nontemporal") c->ko.xattn_variant = (c->ko.xattn_variant & ~1) | (on ? 1 : 0);   // per context (kernel template choice)
+  else if (key == "xattn_pipeline") c->ko.xattn_variant = (c->ko.xattn_variant & ~2) | (on ? 2 : 0);
   else if (key == "xkv_fp8") {
     if (v < 0 || v > 2) return 1;   // 0 off, 1 unshared static rows, 2 every path that has a kernel for the copy (sessions included)
     if (on && !c->lowp) return 1;   // 16-bit engines only
@@ -92,16 +92,13 @@ int set_option(ttasr_ctx* c, const std::string& key, int v) {
     c->xkv_fp8 = v; c->xkv8_valid = false;   // the e4m3 copy is (re)built by the next encode
   }
   else if (key == "xattn_mq_fp8") c->xattn_mq_fp8 = on;
-  else if (key == "weights_nontemporal") c->weights_nt = on ? 1 : 0;
-  else if (key == "dec_x_lds") c->dec_x_lds = on;
+  else if (key == "weights_nontemporal") c->ko.skinny_nt = on;
+  else if (key == "dec_x_lds") c->ko.skinny_x_lds = on;
   else if (key == "ragged_exit") c->ragged_exit = on;
-  else if (key == "flash_qw") { if (v < 1 || v > 2) return 1; c->flash_qw = v; }
-  else if (key == "xattn_mq_slices") { if (v < 0 || v > 8) return 1; c->xattn_mq_slices = v; }
-  else if (key == "xattn_deep_items") { if (v < 0 || v > 1 << 20) return 1; c->xattn_deep_items = v; }
+  else if (key == "flash_qw") { if (v < 1 || v > 2) return 1; c->ko.flash_qw = v; }
+  else if (key == "xattn_mq_slices") { if (v < 0 || v > 8) return 1; c->ko.xattn_mq_slices = v; }
+  else if (key == "xattn_deep_items") { if (v < 0 || v > 1 << 20) return 1; c->ko.xattn_deep_items = v; }
   else return 1;
-  g_xattn_variant = c->xattn_nt | (c->xattn_pipe << 1); g_skinny_nt = c->weights_nt; g_skinny_narrow = c->dec_narrow ? 1 : 0;
-  g_skinny_x_lds = c->dec_x_lds ? 1 : 0;
-  g_xattn_deep_items = c->xattn_deep_items; g_xattn_mq_slices = c->xattn_mq_slices; g_flash_qw = c->flash_qw;
   drop_graphs(c);
   return 0;
 }
@@ -141,6 +138,18 @@ int generate_rows(ttasr_ctx* c, int R, int rows_per_clip, const int32_t* prompt,
     TRY(check_prompt(c, a, prompt + (size_t)a * max_prompt, prompt_len[a], max_prompt, nullptr));
     min_plen = std::min(min_plen, prompt_len[a]); max_plen = std::max(max_plen, prompt_len[a]);
   }
+  // per-row token budgets: row r is finished after min(row_cap[r], max_new_tokens) sampled tokens (or EOT).  Checked before
+  // anything is uploaded or enqueued: a refused call leaves no copy in flight
+  int max_cap = o->max_new_tokens;
+  if (row_cap) {
+    max_cap = 1;
+    for (int r = 0; r < R; ++r) {
+      if (row_cap[r] < 1 || row_cap[r] > o->max_new_tokens)
+        return fail(c, TTASR_E_INVALID, "row_max_new[%d]=%d outside [1, max_new_tokens=%d]", r, row_cap[r], o->max_new_tokens);
+      max_cap = std::max(max_cap, (int)row_cap[r]);
+    }
+  }
+  SearchScope scope(c, StepShape{rows_per_clip, 1, false}, c->prompt_dev, c->plen_dev, R);
   RuleParams old = c->rp;
   TRY(upload_rules(c, o, max_prompt));
   c->rp.temperature = temperature; c->rp.seed = seed;
@@ -156,21 +165,9 @@ int generate_rows(ttasr_ctx* c, int R, int rows_per_clip, const int32_t* prompt,
   HIPCHK(c, hipMemcpyAsync(c->prompt_dev, pr.data(), pr.size() * 4, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpyAsync(c->plen_dev, pl.data(), R * 4, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpy2DAsync(c->st.cur_tok, 4, c->prompt_dev, (size_t)max_prompt * 4, 4, R, hipMemcpyDeviceToDevice, s));
-  int max_cap = o->max_new_tokens;
-  if (row_cap) {   // per-row token budgets: row r is finished after min(row_cap[r], max_new_tokens) sampled tokens (or EOT)
-    max_cap = 1;
-    for (int r = 0; r < R; ++r) {
-      if (row_cap[r] < 1 || row_cap[r] > o->max_new_tokens)
-        return fail(c, TTASR_E_INVALID, "row_max_new[%d]=%d outside [1, max_new_tokens=%d]", r, row_cap[r], o->max_new_tokens);
-      max_cap = std::max(max_cap, (int)row_cap[r]);
-    }
-    HIPCHK(c, hipMemcpyAsync(c->row_cap_dev, row_cap, (size_t)R * 4, hipMemcpyHostToDevice, s));
-  }
+  if (row_cap) HIPCHK(c, hipMemcpyAsync(c->row_cap_dev, row_cap, (size_t)R * 4, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipStreamSynchronize(s));  // pr / pl (and the caller's row_cap) are read by the copies above
-  c->st.prompt = c->prompt_dev; c->st.prompt_len = c->plen_dev;
   c->B_dec = R;
-  c->kv_div = rows_per_clip;
-  struct Restore { ttasr_ctx* c; ~Restore() { c->kv_div = 1; } } restore{c};
   const int interval = std::max(1, o->check_interval);
   // exclusive; prompt + sampled tokens never exceed n_text_ctx (the reference's max_length = 448: the token sampled
   // from position n_text_ctx - 2 is the last one, position n_text_ctx - 1 is never fed)
@@ -213,7 +210,6 @@ int generate_rows(ttasr_ctx* c, int R, int rows_per_clip, const int32_t* prompt,
   HIPCHK(c, hipMemcpyAsync(out_len, c->st.n_sampled, R * 4, hipMemcpyDeviceToHost, s));
   if (out_lp) HIPCHK(c, hipMemcpyAsync(out_lp, c->st.sum_logprob, R * 4, hipMemcpyDeviceToHost, s));
   if (out_ns) HIPCHK(c, hipMemcpyAsync(out_ns, c->st.no_speech, R * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemsetAsync(c->st.done, 0, (size_t)R * 4, s));   // the flags belong to THIS search: later step-API calls see live rows
   HIPCHK(c, hipStreamSynchronize(s));
   HIPCHK(c, hipGetLastError());
   hipEventElapsedTime(&c->phase_ms[3], c->ev[5], c->ev[6]);
@@ -346,14 +342,12 @@ int beam_search_impl(ttasr_ctx* c, int32_t A, int32_t beam, const int32_t* promp
     TRY(check_prompt(c, a, prompt + (size_t)a * max_prompt, plens[a], max_prompt, o->no_speech >= 0 && out_ns ? &sot : nullptr));
     min_plen = std::min(min_plen, (int)plens[a]); min_sot = std::min(min_sot, (int)sot);
   }
+  SearchScope scope(c, StepShape{beam, 0, false}, nullptr, nullptr, R);
   RuleParams old_rp = c->rp;
   TRY(upload_rules(c, o, max_prompt));
   TRY(commit_rules(c, old_rp));
   TRY(reset_search(c, R));
-  c->st.prompt = nullptr; c->st.prompt_len = nullptr;
   c->B_dec = R;
-  c->kv_div = beam; c->identity_pages = 0;
-  struct Restore { ttasr_ctx* c; ~Restore() { c->kv_div = 1; c->identity_pages = 1; } } restore{c};
   hipStream_t s = c->stream;
   const int pps = c->pages_per_seq, max_new = c->rp.max_new, K = beam + 1;
   const int max_cand = std::max(1, (int)std::lround(beam * patience));
@@ -468,7 +462,6 @@ int beam_search_impl(ttasr_ctx* c, int32_t A, int32_t beam, const int32_t* promp
   }
   hipEventRecord(c->ev[6], s);
   c->beam_prof_ms[0] = (float)t_enq; c->beam_prof_ms[1] = (float)t_wait; c->beam_prof_ms[2] = (float)t_sel; c->beam_prof_ms[3] = (float)n_pos;
-  HIPCHK(c, hipMemsetAsync(c->st.done, 0, (size_t)R * 4, s));   // the flags belong to THIS search
   HIPCHK(c, hipStreamSynchronize(s));
   HIPCHK(c, hipGetLastError());
   hipEventElapsedTime(&c->phase_ms[3], c->ev[5], c->ev[6]);

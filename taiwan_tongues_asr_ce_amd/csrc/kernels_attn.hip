@@ -120,7 +120,6 @@ void launch_fault(const char* fmt, ...) {
 }
 thread_local bool g_kernel_sig_on = false;
 thread_local char g_kernel_sig[192] = "";
-thread_local int g_xattn_variant = 3;  // bit 0: option xattn_nontemporal (nontemporal K/V loads), bit 1: option xattn_pipeline (software-pipelined form); default both
 using u32x4_t = __attribute__((ext_vector_type(4))) unsigned;
 
 // Single pass, one memory round trip for pos <= 32*UNROLL cached keys: every lane keeps an online-softmax
@@ -532,9 +531,6 @@ __global__ __launch_bounds__(NWV * 64) void cross_attn_decode_kernel(const T* q,
 // 2 43.8 (tools/microbench/xattn_bench.hip, profiles/r4_xattn_pipeline.txt).  At a balanced 2.97 workgroups per CU (B = 38) every
 // form runs 6.42-6.48 TB/s: the gain at B = 32 is a shorter tail of the uneven 3-vs-2 workgroup split, not a faster stream.
 // 16-bit storage, 4 waves, decode step only (no PROBS).
-thread_local int g_xattn_mq_slices = 0;     // option xattn_mq_slices (A/B): frame slices of the shared-clip cross-attention, 0 = automatic
-thread_local int g_xattn_deep_items = 512;   // option xattn_deep_items: live (row, head) items at or below which a workgroup streams
-                                             // DEEP (default 2 per CU of 256 - sweep: 448 loses 0.08 ms per step at 24 live rows, 576 costs 0.15 ms at 26-28; 0 = never) - per context, like g_xattn_variant
 constexpr int XATTN_DEEP_U = 8;              // rows per lane and batch of the deep form
 template <typename T, bool NT, bool QSLAB, int U>
 __global__ __launch_bounds__(256) void cross_attn_pipe_kernel(const T* q, const T* K, const T* V, T* out, const int32_t* done, int H,
@@ -1045,8 +1041,8 @@ int cross_attn_splits(int B, int H, int Tk) {
 }
 
 template <typename T>
-void launch_cross_attn_decode(const T* q, const T* K, const T* V, T* out, int B, int H, int Tk, int kv_div, hipStream_t s,
-                              float* split_ws, SlabIn sq, int ws_rows, QProj qp, const int32_t* done) {
+void launch_cross_attn_decode(const T* q, const T* K, const T* V, T* out, int B, int H, int Tk, int kv_div, const KernelOpts& ko,
+                              hipStream_t s, float* split_ws, SlabIn sq, int ws_rows, QProj qp, const int32_t* done) {
   if (ws_rows <= 0) ws_rows = B;
   if (qp.W) split_ws = nullptr;   // in-kernel q projection (lab builds): the single-pass per-row kernel only (B * H >= 256, kv_div == 1)  // the workspace holds ws_rows rows x 8 slices x H heads x 66 floats
   // many rows per clip (a long previous-text prompt in one prefill pass): the rows are the M dimension of an MFMA flash pass over
@@ -1068,7 +1064,7 @@ void launch_cross_attn_decode(const T* q, const T* K, const T* V, T* out, int B,
     // workspace, no merge launch - was measured with the pipelined stream and is SLOWER at 8 clips x beam 5 (160 workgroups,
     // one per CU: 2.98 vs 2.74 ms per step): a lone workgroup scores 5 queries against every row on one wave per SIMD.
     int Sq = cross_attn_splits(A * groups, H, Tk);
-    if (g_xattn_mq_slices > 0) Sq = g_xattn_mq_slices > 8 ? 8 : g_xattn_mq_slices;
+    if (ko.xattn_mq_slices > 0) Sq = ko.xattn_mq_slices > 8 ? 8 : ko.xattn_mq_slices;
     const int chunk = ((Tk + Sq - 1) / Sq + 31) / 32 * 32;
     const int S2 = (Tk + chunk - 1) / chunk;  // every slice non-empty; S2 <= 8
     const size_t lds = sizeof(float) * ((size_t)NQ * chunk + 4 * NQ * 64 + 8 * NQ);
@@ -1095,7 +1091,7 @@ void launch_cross_attn_decode(const T* q, const T* K, const T* V, T* out, int B,
     launch_cross_attn_merge<T>(split_ws, out, B, H, S2, done, s);
     return;
   }
-  // g_xattn_variant (option xattn_nontemporal, A/B testing): 1 = nontemporal K/V loads (default), 0 = plain.  (16 rows in flight per lane and
+  // ko.xattn_variant bit 0 (option xattn_nontemporal, A/B testing): 1 = nontemporal K/V loads (default), 0 = plain.  (16 rows in flight per lane and
   // 8-wave workgroups were measured slower - DESIGN.md 4.11a - and are no longer instantiated.)
   size_t lds = sizeof(float) * (Tk + 4 * 64 + 2 * 4);
 #ifdef TTASR_EXPERIMENTS   /* lab builds only: the in-kernel q projection (QMODE 2), measured slower - DESIGN.md 4.11 */
@@ -1119,9 +1115,9 @@ void launch_cross_attn_decode(const T* q, const T* K, const T* V, T* out, int B,
                             Tk, kv_div, (const int*)nullptr, (float*)nullptr, sq, qp, (const int*)nullptr);                           \
   } while (0)
   if constexpr (sizeof(T) == 2) {
-    if ((g_xattn_variant & 2) && !qp.W) {   // software-pipelined form (default since round 4), 3 rows per lane and batch
-#define TTASR_XP(NT_, QS_) hipLaunchKernelGGL((cross_attn_pipe_kernel<T, NT_, QS_, 3>), dim3(H, B), dim3(256), lds, s, q, K, V, out, done, H, Tk, kv_div, g_xattn_deep_items, sq)
-      const bool nt = g_xattn_variant & 1, qs = sq.n > 0;
+    if ((ko.xattn_variant & 2) && !qp.W) {   // software-pipelined form (default since round 4), 3 rows per lane and batch
+#define TTASR_XP(NT_, QS_) hipLaunchKernelGGL((cross_attn_pipe_kernel<T, NT_, QS_, 3>), dim3(H, B), dim3(256), lds, s, q, K, V, out, done, H, Tk, kv_div, ko.xattn_deep_items, sq)
+      const bool nt = ko.xattn_variant & 1, qs = sq.n > 0;
       if (g_kernel_sig_on) snprintf(g_kernel_sig, sizeof g_kernel_sig, "cross_attn_pipe_kernel<%s, %s, %s, 3> grid %d", sig_type<T>(),
                                     nt ? "true" : "false", qs ? "true" : "false", H * B * 256);
       if (nt) { if (qs) TTASR_XP(true, true); else TTASR_XP(true, false); } else { if (qs) TTASR_XP(false, true); else TTASR_XP(false, false); }
@@ -1130,8 +1126,8 @@ void launch_cross_attn_decode(const T* q, const T* K, const T* V, T* out, int B,
     }
   }
   if (g_kernel_sig_on) snprintf(g_kernel_sig, sizeof g_kernel_sig, "cross_attn_decode_kernel<%s, false, 4, 8, %s, %d> grid %d", sig_type<T>(),
-                                (g_xattn_variant & 1) ? "true" : "false", sq.n > 0 ? 1 : 0, H * B * 256);
-  if (g_xattn_variant & 1) TTASR_XA(true); else TTASR_XA(false);
+                                (ko.xattn_variant & 1) ? "true" : "false", sq.n > 0 ? 1 : 0, H * B * 256);
+  if (ko.xattn_variant & 1) TTASR_XA(true); else TTASR_XA(false);
 #undef TTASR_XA
 }
 // alignment pass: rows = token positions of one sequence; heads with sel[h] >= 0 dump their attention rows
@@ -1157,9 +1153,9 @@ template void launch_cross_attn_probs<bf16_t>(const bf16_t*, const bf16_t*, cons
                                               hipStream_t);
 template void launch_cross_attn_probs<f16_t>(const f16_t*, const f16_t*, const f16_t*, f16_t*, int, int, int, const int*, float*,
                                               hipStream_t);
-template void launch_cross_attn_decode<float>(const float*, const float*, const float*, float*, int, int, int, int, hipStream_t, float*,
+template void launch_cross_attn_decode<float>(const float*, const float*, const float*, float*, int, int, int, int, const KernelOpts&, hipStream_t, float*,
                                               SlabIn, int, QProj, const int32_t*);
-template void launch_cross_attn_decode<bf16_t>(const bf16_t*, const bf16_t*, const bf16_t*, bf16_t*, int, int, int, int, hipStream_t,
+template void launch_cross_attn_decode<bf16_t>(const bf16_t*, const bf16_t*, const bf16_t*, bf16_t*, int, int, int, int, const KernelOpts&, hipStream_t,
                                                float*, SlabIn, int, QProj, const int32_t*);
-template void launch_cross_attn_decode<f16_t>(const f16_t*, const f16_t*, const f16_t*, f16_t*, int, int, int, int, hipStream_t,
+template void launch_cross_attn_decode<f16_t>(const f16_t*, const f16_t*, const f16_t*, f16_t*, int, int, int, int, const KernelOpts&, hipStream_t,
                                                float*, SlabIn, int, QProj, const int32_t*);

@@ -309,10 +309,9 @@ __global__ __launch_bounds__(256, QW == 2 ? 2 : 3) void enc_attn_flash_kernel(co
   }
 }
 
-thread_local int g_flash_qw = 2;   // option flash_qw: query blocks of 32 per wave in the encoder's flash attention (1 = the round-5 form)
 template <typename T16>
-void launch_enc_attn_flash_bf16(const T16* qkv, T16* out, int B, int T_, int H, hipStream_t s) {
-  if (g_flash_qw >= 2) {
+void launch_enc_attn_flash_bf16(const T16* qkv, T16* out, int B, int T_, int H, const KernelOpts& ko, hipStream_t s) {
+  if (ko.flash_qw >= 2) {
     dim3 grid((T_ + 255) / 256, H, B);
     hipLaunchKernelGGL((enc_attn_flash_kernel<T16, false, 2>), grid, dim3(256), 32768, s, (const bf16_t*)qkv, (bf16_t*)out, T_, H,
                        (const bf16_t*)nullptr, (const bf16_t*)nullptr, 0);
@@ -329,7 +328,7 @@ void launch_cross_attn_flash_bf16(const T16* q, const T16* K, const T16* V, T16*
   hipLaunchKernelGGL((enc_attn_flash_kernel<T16, true, 1>), grid, dim3(256), 32768, s, (const bf16_t*)q, (bf16_t*)out, n_q, H,
                      (const bf16_t*)K, (const bf16_t*)V, Tk);
 }
-template void launch_enc_attn_flash_bf16<bf16_t>(const bf16_t*, bf16_t*, int, int, int, hipStream_t);
-template void launch_enc_attn_flash_bf16<f16_t>(const f16_t*, f16_t*, int, int, int, hipStream_t);
+template void launch_enc_attn_flash_bf16<bf16_t>(const bf16_t*, bf16_t*, int, int, int, const KernelOpts&, hipStream_t);
+template void launch_enc_attn_flash_bf16<f16_t>(const f16_t*, f16_t*, int, int, int, const KernelOpts&, hipStream_t);
 template void launch_cross_attn_flash_bf16<bf16_t>(const bf16_t*, const bf16_t*, const bf16_t*, bf16_t*, int, int, int, int, hipStream_t);
 template void launch_cross_attn_flash_bf16<f16_t>(const f16_t*, const f16_t*, const f16_t*, f16_t*, int, int, int, int, hipStream_t);

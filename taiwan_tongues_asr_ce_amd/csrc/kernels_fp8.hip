@@ -463,14 +463,14 @@ __global__ __launch_bounds__(256) void cross_attn_mq_fp8_kernel(const T* __restr
 // same workspace check; false: not taken (the caller runs the 16-bit path, which then decides by its own rule).
 template <typename T>
 bool launch_cross_attn_mq_fp8(const T* q, const uint8_t* K8, const uint8_t* V8, const float* kscale, const float* vscale, T* out, int B,
-                              int H, int Tk, int kv_div, hipStream_t s, float* split_ws, SlabIn sq, int ws_rows, const int32_t* done) {
+                              int H, int Tk, int kv_div, const KernelOpts& ko, hipStream_t s, float* split_ws, SlabIn sq, int ws_rows, const int32_t* done) {
   if constexpr (sizeof(T) != 2) return false;
   else {
     if (ws_rows <= 0) ws_rows = B;
     if (!split_ws || kv_div < 2 || kv_div > 7 || B % kv_div != 0 || B * H < 256 || sq.n > 4 || Tk < 1) return false;
     const int A = B / kv_div;
     int Sq = cross_attn_splits(A, H, Tk);
-    if (g_xattn_mq_slices > 0) Sq = g_xattn_mq_slices > 8 ? 8 : g_xattn_mq_slices;
+    if (ko.xattn_mq_slices > 0) Sq = ko.xattn_mq_slices > 8 ? 8 : ko.xattn_mq_slices;
     const int chunk = ((Tk + Sq - 1) / Sq + 31) / 32 * 32;
     const int S2 = (Tk + chunk - 1) / chunk;  // every slice non-empty; S2 <= 8
     const size_t lds = sizeof(float) * ((size_t)kv_div * chunk + 4 * kv_div * 64 + 8 * kv_div);
@@ -490,6 +490,6 @@ bool launch_cross_attn_mq_fp8(const T* q, const uint8_t* K8, const uint8_t* V8, 
 }
 #define TTASR_MQ8_INST(T_) \
   template bool launch_cross_attn_mq_fp8<T_>(const T_*, const uint8_t*, const uint8_t*, const float*, const float*, T_*, int, int, int, int, \
-                                             hipStream_t, float*, SlabIn, int, const int32_t*)
+                                             const KernelOpts&, hipStream_t, float*, SlabIn, int, const int32_t*)
 TTASR_MQ8_INST(bf16_t); TTASR_MQ8_INST(f16_t); TTASR_MQ8_INST(float);
 #undef TTASR_MQ8_INST

@@ -37,10 +37,9 @@ using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 //   fc1 7.83 -> 7.53 us;  fc2 (8 K slices) 7.27 -> 7.26;  out-proj / q 3.45 (32 rows, 5 slices) vs 3.77 (20 rows, 4 slices).
 // So only fc1 takes the narrow blocks (rule: the 20-row block count is a multiple of the 256 CUs); what these kernels wait for is
 // not the per-CU share of the stream alone - they sit 1.3-1.7 us above a kernel that only moves the same bytes on the same grid.
-thread_local int g_skinny_narrow = 1;   // option dec_narrow_blocks (per context; fixed once the weights are packed)
-int skinny_rows_per_block(int N, int K) {
+int skinny_rows_per_block(int N, int K, const KernelOpts& ko) {
   (void)K;
-  if (!g_skinny_narrow) return 32;
+  if (!ko.skinny_narrow) return 32;
   return (N % 20 == 0 && (N / 20) % 256 == 0) ? 20 : 32;
 }
 
@@ -69,20 +68,19 @@ __global__ void shuffle_cast_kernel(const float* __restrict__ src, bf16_t* __res
 }
 // rows_total = rows of the whole packed matrix (a fused q/k/v matrix arrives as three parts): it decides the block height
 template <typename T16>
-void launch_shuffle_cast(const float* src, T16* dst_base, int rows, int K, int row_offset, hipStream_t s, int rows_total) {
-  const int rpb = skinny_rows_per_block(rows_total > 0 ? rows_total : rows, K);
+void launch_shuffle_cast(const float* src, T16* dst_base, int rows, int K, int row_offset, const KernelOpts& ko, hipStream_t s, int rows_total) {
+  const int rpb = skinny_rows_per_block(rows_total > 0 ? rows_total : rows, K, ko);
   const int64_t n_chunks = (int64_t)((rows + rpb - 1) / rpb) * (K / 16) * 2 * rpb;
   const int64_t nb = (n_chunks + 255) / 256;
   hipLaunchKernelGGL(shuffle_cast_kernel<T16>, dim3((unsigned)(nb < 8192 ? nb : 8192)), dim3(256), 0, s, src, (bf16_t*)dst_base, rows, K,
                      row_offset, rpb);
 }
-template void launch_shuffle_cast<bf16_t>(const float*, bf16_t*, int, int, int, hipStream_t, int);
-template void launch_shuffle_cast<f16_t>(const float*, f16_t*, int, int, int, hipStream_t, int);
+template void launch_shuffle_cast<bf16_t>(const float*, bf16_t*, int, int, int, const KernelOpts&, hipStream_t, int);
+template void launch_shuffle_cast<f16_t>(const float*, f16_t*, int, int, int, const KernelOpts&, hipStream_t, int);
 
 // NW waves per workgroup, each owning steps_per_wave k-steps of 16; RB groups of 32 batch rows share every weight
 // fragment (RB = 1 is the B <= 32 kernel of the benchmark; RB = 2..4 carry 64..128 rows through one weight stream,
 // which is what amortises the per-step latency when more clips are in flight).
-thread_local int g_skinny_x_lds = 1;   // option dec_x_lds: the decode GEMMs stage their activation tile through LDS (0 = fragment loads straight from memory; bit-identical)
 // dynamic LDS of gemm_skinny_kernel: the reduction buffer, or the (larger) activation tile it is aliased with
 static size_t skinny_lds_bytes(int nw, int rb, int steps, bool x_lds) {
   const size_t red = (size_t)nw * rb * 4096;
@@ -98,7 +96,6 @@ static void skinny_allow_big_lds() {
   (void)hipGetDevice(&dev);
   std::call_once(once[dev & 63], []() { (void)hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
 }
-thread_local int g_skinny_nt = 1;  // nontemporal weight loads in the decode GEMMs (option weights_nontemporal = 0 switches them off: A/B experiments; the 1.8 GB of decoder weights a step streams can never stay cached: -1 % per step)
 
 // ONE = the wave's k-steps fit one batch of loads (steps <= U): straight-line code.  (As a loop, the register reuse of
 // the next iteration forces an early s_waitcnt that, in the first iteration, waits for the bias / residual prefetch
@@ -432,33 +429,33 @@ static void vocab_init_once(int device) {
 
 // Returns false when the shape does not fit (caller falls back to launch_gemm_skinny).
 template <typename T16>
-bool launch_gemm_vocab(const T16* Wsh, const T16* x, int B, int N, int K, float* out, int64_t ldc, hipStream_t s, int device) {
+bool launch_gemm_vocab(const T16* Wsh, const T16* x, int B, int N, int K, float* out, int64_t ldc, const KernelOpts& ko, hipStream_t s, int device) {
   const int n_cu = g_vocab_cus[device & 63];
   if (n_cu <= 0 || B < 1 || B > 64 || K % 128 != 0 || K / 128 > 10 || N < 8192 || ldc % 4 != 0) return false;
   // this kernel walks 32-row n-blocks (64 chunks per k-step); a vocabulary whose size makes skinny_rows_per_block choose the
   // 20-row layout (V % 5120 == 0: 10 240, 51 200 ...) was packed that way by build_weights and belongs to the generic kernel,
   // which takes the block height as an argument (read as 32-row blocks the logits were silently wrong)
-  if (skinny_rows_per_block(N, K) != 32) return false;
+  if (skinny_rows_per_block(N, K, ko) != 32) return false;
   const int rb = (B + 31) / 32, steps = K / 128, n_blocks = (N + 31) / 32;
   const int grid = n_blocks < n_cu ? n_blocks : n_cu;
   const size_t lds = (size_t)2 * 8 * rb * 1024 * sizeof(float);   // 64 KiB per row group
 #define TTASR_VOCAB(RB_)                                                                                                           \
   do {                                                                                                                             \
-    if (g_skinny_nt) hipLaunchKernelGGL((gemm_vocab_kernel<T16, RB_, true>), dim3(grid), dim3(512), lds, s, (const bf16_t*)Wsh, (const bf16_t*)x, B, N, K, steps, out, ldc); \
+    if (ko.skinny_nt) hipLaunchKernelGGL((gemm_vocab_kernel<T16, RB_, true>), dim3(grid), dim3(512), lds, s, (const bf16_t*)Wsh, (const bf16_t*)x, B, N, K, steps, out, ldc); \
     else hipLaunchKernelGGL((gemm_vocab_kernel<T16, RB_, false>), dim3(grid), dim3(512), lds, s, (const bf16_t*)Wsh, (const bf16_t*)x, B, N, K, steps, out, ldc); \
   } while (0)
   if (rb == 1) TTASR_VOCAB(1); else TTASR_VOCAB(2);
 #undef TTASR_VOCAB
   return true;
 }
-template bool launch_gemm_vocab<bf16_t>(const bf16_t*, const bf16_t*, int, int, int, float*, int64_t, hipStream_t, int);
-template bool launch_gemm_vocab<f16_t>(const f16_t*, const f16_t*, int, int, int, float*, int64_t, hipStream_t, int);
+template bool launch_gemm_vocab<bf16_t>(const bf16_t*, const bf16_t*, int, int, int, float*, int64_t, const KernelOpts&, hipStream_t, int);
+template bool launch_gemm_vocab<f16_t>(const f16_t*, const f16_t*, int, int, int, float*, int64_t, const KernelOpts&, hipStream_t, int);
 
 // K slices a split decode GEMM is cut into (1 = unsplit).  `want` = requested slice count (0 = automatic: weights in
 // pieces of <= ~20 KB per workgroup, a few hundred workgroups); the result divides the k-steps evenly over 4 waves.
-int gemm_skinny_ksplit(int B, int N, int K, int want) {
+int gemm_skinny_ksplit(int B, int N, int K, int want, const KernelOpts& ko) {
   if (B < 1 || B > 128 || K % 64 != 0) return 1;
-  const int rpb = skinny_rows_per_block(N, K);
+  const int rpb = skinny_rows_per_block(N, K, ko);
   const int rb = (B + 31) / 32, n_blocks = (N + rpb - 1) / rpb, ks_per = K / 16;
   const int per4 = ks_per / 4;  // k-steps per wave of a 4-wave workgroup when unsplit
   if (ks_per % 4 != 0) return 1;
@@ -482,13 +479,13 @@ int gemm_skinny_ksplit(int B, int N, int K, int want) {
 // ksplit > 1 (gemm_skinny_ksplit): partial tiles go to `slab`, bias / activation / residual are the consumer's job.
 // Returns false when the shape does not fit (caller falls back to gemm_basic).
 template <typename T16>
-bool launch_gemm_skinny(const T16* Wsh_, const T16* x_, int B, int N, int K, const GemmEpi& e, hipStream_t s, int ksplit,
+bool launch_gemm_skinny(const T16* Wsh_, const T16* x_, int B, int N, int K, const GemmEpi& e, const KernelOpts& ko, hipStream_t s, int ksplit,
                         float* slab, int64_t slab_stride) {
   const bf16_t* Wsh = (const bf16_t*)Wsh_;   // raw 16-bit words: the kernel only moves them; T16 picks the MFMA form
   const bf16_t* x = (const bf16_t*)x_;
   if (B < 1 || B > 128 || K % 64 != 0 || e.rowtab || e.headsplit) return false;
   const int rb = (B + 31) / 32;  // 32-row groups sharing one weight stream
-  const int rpb = skinny_rows_per_block(N, K);
+  const int rpb = skinny_rows_per_block(N, K, ko);
   const int n_blocks = (N + rpb - 1) / rpb;
   const int ks_per = K / 16;
   const int u_max = rb == 1 ? 10 : (rb == 2 ? 8 : 5);  // k-steps a wave can keep in flight (registers)
@@ -506,10 +503,10 @@ bool launch_gemm_skinny(const T16* Wsh_, const T16* x_, int B, int N, int K, con
   dim3 grid(n_blocks, ksplit);
 #define TTASR_SKINNY(NW_, RB_, U_, ONE_)                                                                                              \
   do {                                                                                                                                \
-    const bool xl_ = g_skinny_x_lds && ONE_ && (NW_ == 4 || (NW_ == 8 && RB_ == 1));                                                  \
+    const bool xl_ = ko.skinny_x_lds && ONE_ && (NW_ == 4 || (NW_ == 8 && RB_ == 1));                                                  \
     const size_t lds_ = skinny_lds_bytes(NW_, RB_, steps, xl_);                                                                       \
     const int rpbx_ = rpb | (xl_ ? 256 : 0);                                                                                          \
-    if (g_skinny_nt) {                                                                                                                \
+    if (ko.skinny_nt) {                                                                                                                \
       if (lds_ > 65536) skinny_allow_big_lds<gemm_skinny_kernel<T16, NW_, RB_, U_, true, ONE_>>();                                     \
       hipLaunchKernelGGL((gemm_skinny_kernel<T16, NW_, RB_, U_, true, ONE_>), grid, dim3(NW_ * 64), lds_, s, Wsh, x, B, N, K, ksplit, steps, e, slab, slab_stride, rpbx_); \
     } else {                                                                                                                          \
@@ -541,5 +538,5 @@ bool launch_gemm_skinny(const T16* Wsh_, const T16* x_, int B, int N, int K, con
 #undef TTASR_SKINNY
   return true;
 }
-template bool launch_gemm_skinny<bf16_t>(const bf16_t*, const bf16_t*, int, int, int, const GemmEpi&, hipStream_t, int, float*, int64_t);
-template bool launch_gemm_skinny<f16_t>(const f16_t*, const f16_t*, int, int, int, const GemmEpi&, hipStream_t, int, float*, int64_t);
+template bool launch_gemm_skinny<bf16_t>(const bf16_t*, const bf16_t*, int, int, int, const GemmEpi&, const KernelOpts&, hipStream_t, int, float*, int64_t);
+template bool launch_gemm_skinny<f16_t>(const f16_t*, const f16_t*, int, int, int, const GemmEpi&, const KernelOpts&, hipStream_t, int, float*, int64_t);

@@ -231,6 +231,8 @@ class Engine:
             caps = np.ascontiguousarray(row_max_new, dtype=np.int32)
             if caps.shape != (B,):
                 raise ValueError(f"row_max_new needs one entry per row ({B}), got shape {caps.shape}")
+            if caps.min() < 1 or caps.max() > opts.max_new_tokens:
+                raise ValueError(f"row_max_new entries must lie in [1, max_new_tokens={opts.max_new_tokens}], got {caps.tolist()}")
             self._check(self.lib.ttasr_generate_capped(self.h, B, pr.ctypes.data_as(i32p), pl.ctypes.data_as(i32p), max_prompt,
                                                        C.byref(opts), caps.ctypes.data_as(i32p), toks.ctypes.data_as(i32p),
                                                        lens.ctypes.data_as(i32p), lp.ctypes.data_as(f32p),

@@ -498,9 +498,10 @@ def test_round4_options_are_bit_identical_to_their_off_form():
 
 def test_kernel_options_are_per_context_and_the_graph_cache_is_bounded():
     """ADVICE round 3: `xattn_nontemporal` / `weights_nontemporal` used to be process-wide globals - an option set on one context
-    changed what another context's thread launched.  Now every C-ABI call copies its own context's options into the launchers'
-    thread-locals: context A with the pipelined cross-attention switched off launches `cross_attn_decode_kernel`, context B
-    (untouched, used after A's call) still launches `cross_attn_pipe_kernel` (ttasr_bench_kernel_signature).  And the captured
+    changed what another context's thread launched.  Now the options travel with the context: each context holds its own
+    `KernelOpts` and hands it to every launcher as an argument.  Context A with the pipelined cross-attention switched off
+    launches `cross_attn_decode_kernel`, context B (untouched, used after A's call) still launches `cross_attn_pipe_kernel`
+    (ttasr_bench_kernel_signature).  And the captured
     decode-step graphs live in an LRU cache of 32: twenty batch sizes x two graphs each (4-step runs and single steps) evict the oldest, which are then re-captured with
     identical results (VERDICT round 3, next #8)."""
     from taiwan_tongues_asr_ce_amd.engine import Engine

@@ -16,6 +16,8 @@ single-pass kernel) and on the small-batch paths:
     f32 1e-3, bf16 / fp16 0.15 + token equality under margin - the same gates as test_gpu_measured_shape.py;
   * option `ragged_exit` = 0 (the static batch) returns the same tokens and the same log-probabilities, bit for bit;
   * the fp8 cross-KV mode, the frame-split kernels (B x H < 256) and sampled rows sharing a clip behave the same way."""
+import ctypes as C
+
 import numpy as np
 import pytest
 import torch
@@ -131,9 +133,18 @@ def test_bad_budgets_are_refused_and_natural_eot_still_polls(world):
     e.encode(4)
     prompt = [st.sot, st.lang_zh, st.transcribe, st.no_timestamps]
     opts = e.gen_opts(16, False, suppress_eot=True)
+    i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+    pr, pl = np.ascontiguousarray([prompt] * 4, dtype=np.int32), np.full(4, len(prompt), dtype=np.int32)
+    toks, lens, lp, ns = np.zeros((4, 16), np.int32), np.zeros(4, np.int32), np.zeros(4, np.float32), np.zeros(4, np.float32)
     for bad in ([0, 4, 4, 4], [4, 4, 4, 17], [-1, 1, 1, 1]):
-        with pytest.raises(TtasrError):
+        with pytest.raises(ValueError):   # Engine.generate checks the range before it calls the library ...
             e.generate([prompt] * 4, opts, row_max_new=bad)
+        caps = np.asarray(bad, dtype=np.int32)   # ... which refuses the same budgets itself
+        rc = e.lib.ttasr_generate_capped(e.h, 4, pr.ctypes.data_as(i32p), pl.ctypes.data_as(i32p), len(prompt), C.byref(opts),
+                                         caps.ctypes.data_as(i32p), toks.ctypes.data_as(i32p), lens.ctypes.data_as(i32p),
+                                         lp.ctypes.data_as(f32p), ns.ctypes.data_as(f32p))
+        with pytest.raises(TtasrError, match="row_max_new"):
+            e._check(rc, "generate_capped")
     with pytest.raises(ValueError):
         e.generate([prompt] * 4, opts, row_max_new=[4, 4])
     # after a refused call the context still works, and budgets combine with natural stopping (EOT allowed, host polls every step)

@@ -20,6 +20,7 @@ static void* dmal(size_t bytes, int fill, float scale = 1.f) {
   return p;
 }
 int main(int argc, char** argv) {
+  KernelOpts ko;   // the kernel-variant options the launchers are handed (common.hpp)
   const int B = argc > 1 ? atoi(argv[1]) : 32, d = 1280, H = 20, posv = argc > 2 ? atoi(argv[2]) : 64, G = argc > 3 ? atoi(argv[3]) : 4;
   hipStream_t s; hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
   float* bias = (float*)dmal(3 * d * 4, 2, 0.1f);
@@ -35,7 +36,7 @@ int main(int argc, char** argv) {
   // reference
   launch_self_attn_decode<bf16_t>(qkv, pool, pt, pps, 0, 1, 0, step, att, B, H, s, sq);
   GemmEpi e; e.ldc = d;
-  launch_gemm_skinny(wo, att, B, d, d, e, s, 4, slab, (int64_t)B * d);
+  launch_gemm_skinny(wo, att, B, d, d, e, ko, s, 4, slab, (int64_t)B * d);
   hipStreamSynchronize(s);
   std::vector<float> r((size_t)4 * B * d), ref((size_t)B * d, 0.f);
   hipMemcpy(r.data(), slab, r.size() * 4, hipMemcpyDeviceToHost);

@@ -21,6 +21,7 @@ static void* dmal(size_t bytes, int fill_rand) {
   return p;
 }
 int main(int argc, char** argv) {
+  KernelOpts ko;   // the kernel-variant options the launchers are handed (common.hpp)
   const int Bfull = 32, d = 1280, F = 5120, H = 20, T = 1500, L = 8;
   int mask = argc > 1 ? atoi(argv[1]) : 0;
   const int dual = argc > 2 ? atoi(argv[2]) : 0;
@@ -44,16 +45,16 @@ int main(int argc, char** argv) {
     float* x_ = x + r0 * d; (void)x_;
     GemmEpi e;
     if (!(mask & 1)) launch_layernorm<bf16_t>(x, g, bt, h, B, d, s);
-    if (!(mask & 2)) { e = GemmEpi(); e.bias = bias; e.out_t = qkv; e.ldc = 3 * d; launch_gemm_skinny(wqkv[l], h, B, 3 * d, d, e, s); }
+    if (!(mask & 2)) { e = GemmEpi(); e.bias = bias; e.out_t = qkv; e.ldc = 3 * d; launch_gemm_skinny(wqkv[l], h, B, 3 * d, d, e, ko, s); }
     if (!(mask & 4)) launch_self_attn_decode<bf16_t>(qkv, pool, pt, pps, 0, 1, 0, step, att, B, H, s);
-    if (!(mask & 2)) { e = GemmEpi(); e.bias = bias; e.residual = x; e.out_f32 = x; e.ldc = d; launch_gemm_skinny(wo[l], att, B, d, d, e, s); }
+    if (!(mask & 2)) { e = GemmEpi(); e.bias = bias; e.residual = x; e.out_f32 = x; e.ldc = d; launch_gemm_skinny(wo[l], att, B, d, d, e, ko, s); }
     if (!(mask & 1)) launch_layernorm<bf16_t>(x, g, bt, h, B, d, s);
-    if (!(mask & 2)) { e = GemmEpi(); e.bias = bias; e.out_t = q; e.ldc = d; launch_gemm_skinny(wq[l], h, B, d, d, e, s); }
-    if (!(mask & 8)) launch_cross_attn_decode<bf16_t>(q, xk[l], xv[l], att, B, H, T, 1, s);
-    if (!(mask & 2)) { e = GemmEpi(); e.bias = bias; e.residual = x; e.out_f32 = x; e.ldc = d; launch_gemm_skinny(wox[l], att, B, d, d, e, s); }
+    if (!(mask & 2)) { e = GemmEpi(); e.bias = bias; e.out_t = q; e.ldc = d; launch_gemm_skinny(wq[l], h, B, d, d, e, ko, s); }
+    if (!(mask & 8)) launch_cross_attn_decode<bf16_t>(q, xk[l], xv[l], att, B, H, T, 1, ko, s);
+    if (!(mask & 2)) { e = GemmEpi(); e.bias = bias; e.residual = x; e.out_f32 = x; e.ldc = d; launch_gemm_skinny(wox[l], att, B, d, d, e, ko, s); }
     if (!(mask & 1)) launch_layernorm<bf16_t>(x, g, bt, h, B, d, s);
-    if (!(mask & 2)) { e = GemmEpi(); e.bias = bias; e.act = 1; e.out_t = mid; e.ldc = F; launch_gemm_skinny(w1[l], h, B, F, d, e, s); }
-    if (!(mask & 2)) { e = GemmEpi(); e.bias = bias; e.residual = x; e.out_f32 = x; e.ldc = d; launch_gemm_skinny(w2[l], mid, B, d, F, e, s); }
+    if (!(mask & 2)) { e = GemmEpi(); e.bias = bias; e.act = 1; e.out_t = mid; e.ldc = F; launch_gemm_skinny(w1[l], h, B, F, d, e, ko, s); }
+    if (!(mask & 2)) { e = GemmEpi(); e.bias = bias; e.residual = x; e.out_f32 = x; e.ldc = d; launch_gemm_skinny(w2[l], mid, B, d, F, e, ko, s); }
   };
   hipGraph_t gr; hipGraphExec_t ex;
   hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);

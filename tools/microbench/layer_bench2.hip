@@ -30,8 +30,9 @@ static void* dmal(size_t bytes, int fill_rand) {
 int main(int argc, char** argv) {
   const int B = 32, d = 1280, F = 5120, H = 20, T = 1500, L = 32;
   const int ks_d = argc > 2 ? atoi(argv[2]) : 4, ks_q = argc > 3 ? atoi(argv[3]) : 4, ks_qkv = argc > 4 ? atoi(argv[4]) : 4, ks_f = argc > 5 ? atoi(argv[5]) : 8;
-  g_xattn_variant = 1;
-  g_skinny_nt = getenv("TTASR_W_NT") != nullptr;
+  KernelOpts ko;
+  ko.xattn_variant = 1;
+  ko.skinny_nt = getenv("TTASR_W_NT") != nullptr;
   hipStream_t s; hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
   float* x = (float*)dmal(B * d * 4, 0); float* g = (float*)dmal(d * 4, 0); float* bt = (float*)dmal(d * 4, 0);
   float* bias = (float*)dmal(F * 4, 0); float* slab = (float*)dmal((size_t)16 * B * 3 * d * 4, 0);
@@ -52,7 +53,7 @@ int main(int argc, char** argv) {
       SlabIn si;
       if (mask & 2) return si;
       GemmEpi e; e.ldc = N;
-      if (ks > 1) { launch_gemm_skinny(W, A, B, N, K, e, s, ks, slab, (int64_t)B * N); si.slab = slab; si.bias = b; si.n = ks; si.stride = (int64_t)B * N; si.ld = N; }
+      if (ks > 1) { launch_gemm_skinny(W, A, B, N, K, e, ko, s, ks, slab, (int64_t)B * N); si.slab = slab; si.bias = b; si.n = ks; si.stride = (int64_t)B * N; si.ld = N; }
       return si;
     };
     int pend = 0;
@@ -66,16 +67,16 @@ int main(int argc, char** argv) {
     auto layer = [&](int l) {
       ln();
       SlabIn sqkv = split(wqkv[l], h, 3 * d, d, ks_qkv, bias);
-      if (!(mask & 2) && !sqkv.n) { GemmEpi e; e.bias = bias; e.out_t = qkv; e.ldc = 3 * d; launch_gemm_skinny(wqkv[l], h, B, 3 * d, d, e, s); }
+      if (!(mask & 2) && !sqkv.n) { GemmEpi e; e.bias = bias; e.out_t = qkv; e.ldc = 3 * d; launch_gemm_skinny(wqkv[l], h, B, 3 * d, d, e, ko, s); }
       if (!(mask & 4)) launch_self_attn_decode<bf16_t>(qkv, pool, pt, pps, 0, 1, 0, step, att, B, H, s, sqkv);
       pend = split(wo[l], att, d, d, ks_d, bias).n;
       ln();
       SlabIn sq = split(wq[l], h, d, d, ks_q, bias);
-      if (!(mask & 2) && !sq.n) { GemmEpi e; e.bias = bias; e.out_t = q; e.ldc = d; launch_gemm_skinny(wq[l], h, B, d, d, e, s); }
-      if (!(mask & 8)) launch_cross_attn_decode<bf16_t>(q, xk[l], xv[l], att, B, H, T, 1, s, nullptr, sq);
+      if (!(mask & 2) && !sq.n) { GemmEpi e; e.bias = bias; e.out_t = q; e.ldc = d; launch_gemm_skinny(wq[l], h, B, d, d, e, ko, s); }
+      if (!(mask & 8)) launch_cross_attn_decode<bf16_t>(q, xk[l], xv[l], att, B, H, T, 1, ko, s, nullptr, sq);
       pend = split(wox[l], att, d, d, ks_d, bias).n;
       ln();
-      if (!(mask & 2)) { GemmEpi e; e.bias = bias; e.act = 1; e.out_t = mid; e.ldc = F; launch_gemm_skinny(w1[l], h, B, F, d, e, s); }
+      if (!(mask & 2)) { GemmEpi e; e.bias = bias; e.act = 1; e.out_t = mid; e.ldc = F; launch_gemm_skinny(w1[l], h, B, F, d, e, ko, s); }
       pend = split(w2[l], mid, d, F, ks_f, bias).n;
     };
     hipGraph_t gr; hipGraphExec_t ex;

@@ -54,8 +54,9 @@ int main(int argc, char** argv) {
   const int B = 32, d = 1280, F = 5120, H = 20, T = 1500, L = 32;
   const int mode = argc > 1 ? atoi(argv[1]) : 0, pf_wgs = argc > 2 ? atoi(argv[2]) : 128, nt = argc > 3 ? atoi(argv[3]) : 1;
   const int ks_d = 4, ks_q = 4, ks_qkv = 2, ks_f = 8;
-  g_xattn_variant = 1;
-  g_skinny_nt = nt;
+  KernelOpts ko;
+  ko.xattn_variant = 1;
+  ko.skinny_nt = nt;
   hipStream_t s, s2; hipStreamCreateWithFlags(&s, hipStreamNonBlocking); hipStreamCreateWithFlags(&s2, hipStreamNonBlocking);
   float* x = (float*)dmal(B * d * 4, 0); float* g = (float*)dmal(d * 4, 0); float* bt = (float*)dmal(d * 4, 0);
   float* bias = (float*)dmal(F * 4, 0); float* slab = (float*)dmal((size_t)16 * B * 3 * d * 4, 0);
@@ -82,7 +83,7 @@ int main(int argc, char** argv) {
   auto split = [&](const bf16_t* W, const bf16_t* A, int N, int K, int ks, const float* b) {
     SlabIn si;
     GemmEpi e; e.ldc = N;
-    if (ks > 1) { launch_gemm_skinny(W, A, B, N, K, e, s, ks, slab, (int64_t)B * N); si.slab = slab; si.bias = b; si.n = ks; si.stride = (int64_t)B * N; si.ld = N; }
+    if (ks > 1) { launch_gemm_skinny(W, A, B, N, K, e, ko, s, ks, slab, (int64_t)B * N); si.slab = slab; si.bias = b; si.n = ks; si.stride = (int64_t)B * N; si.ld = N; }
     return si;
   };
   int pend = 0;
@@ -105,12 +106,12 @@ int main(int argc, char** argv) {
     ln();
     SlabIn sq = split(wq[lw], h, d, d, ks_q, bias);
     if (mode == 1 && pending_join[l]) { hipStreamWaitEvent(s, evj[l - 1], 0); pending_join[l] = false; }
-    launch_cross_attn_decode<bf16_t>(q, xk[lk], xv[lk], att, B, H, T, 1, s, nullptr, sq);
+    launch_cross_attn_decode<bf16_t>(q, xk[lk], xv[lk], att, B, H, T, 1, ko, s, nullptr, sq);
     if (mode == 4 && l + 1 < L) { hipStream_t keep = s2; s2 = s; pf(l + 1); s2 = keep; }
     if ((mode == 1 || mode == 2) && l + 1 < L) { hipEventRecord(evf[l], s); hipStreamWaitEvent(s2, evf[l], 0); pf(l + 1); hipEventRecord(evj[l], s2); pending_join[l + 1] = true; }
     pend = split(wox[lw], att, d, d, ks_d, bias).n;
     ln();
-    { GemmEpi e; e.bias = bias; e.act = 1; e.out_t = mid; e.ldc = F; launch_gemm_skinny(w1[lw], h, B, F, d, e, s); }
+    { GemmEpi e; e.bias = bias; e.act = 1; e.out_t = mid; e.ldc = F; launch_gemm_skinny(w1[lw], h, B, F, d, e, ko, s); }
     pend = split(w2[lw], mid, d, F, ks_f, bias).n;
     if (mode == 2 && l + 1 < L) { hipStreamWaitEvent(s, evj[l], 0); pending_join[l + 1] = false; }
   };

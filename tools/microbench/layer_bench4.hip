@@ -45,7 +45,7 @@ int main(int argc, char** argv) {
   const int B = 32, d = 1280, F = 5120, H = 20, T = 1500, L = 32;
   const int only = argc > 1 ? atoi(argv[1]) : -1;
   const int reps = argc > 2 ? atoi(argv[2]) : 10;
-  g_xattn_variant = 3; g_skinny_nt = 1;   // shipped: nontemporal, software-pipelined cross-attention
+  KernelOpts ko;   // the defaults are what ships: nontemporal, software-pipelined cross-attention
   hipStream_t s; hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
   float* x = (float*)dmal(B * d * 4, 2); float* x0 = (float*)dmal(B * d * 4, 2); float* g = (float*)dmal(d * 4, 2); float* bt = (float*)dmal(d * 4, 2);
   float* bias = (float*)dmal(F * 4, 2, 0.1f);
@@ -65,7 +65,7 @@ int main(int argc, char** argv) {
   {  // layer 0: packed Wq = shuffle(row-major Wq) so that variant 1 can be checked against variant 0
     float* tmp = (float*)dmal((size_t)d * d * 4, 0);
     launch_uncast<bf16_t>(wq_rm[0], tmp, (int64_t)d * d, s);
-    launch_shuffle_cast<bf16_t>(tmp, wq[0], d, d, 0, s);
+    launch_shuffle_cast<bf16_t>(tmp, wq[0], d, d, 0, ko, s);
     hipStreamSynchronize(s); hipFree(tmp);
   }
   const int pps = 28; bf16_t* pool = (bf16_t*)dmal((size_t)B * pps * 2 * H * 16 * 64 * 2, 1);
@@ -82,7 +82,7 @@ int main(int argc, char** argv) {
     };
     auto split = [&](const bf16_t* W, const bf16_t* A, int N, int K, int ks, const float* b) {
       SlabIn si; GemmEpi e; e.ldc = N;
-      launch_gemm_skinny(W, A, B, N, K, e, s, ks, slab, (int64_t)B * N);
+      launch_gemm_skinny(W, A, B, N, K, e, ko, s, ks, slab, (int64_t)B * N);
       si.slab = slab; si.bias = b; si.n = ks; si.stride = (int64_t)B * N; si.ld = N;
       return si;
     };
@@ -108,14 +108,14 @@ int main(int argc, char** argv) {
     if (snap) hipMemcpyAsync(x_ln2, x, (size_t)B * d * 4, hipMemcpyDeviceToDevice, s);
     if (fuse_q) {
       QProj qp; qp.x = h; qp.W = wq_rm[l]; qp.bias = bias;
-      launch_cross_attn_decode<bf16_t>(q, xk[l], xv[l], att, B, H, T, 1, s, nullptr, SlabIn{}, 0, qp);
+      launch_cross_attn_decode<bf16_t>(q, xk[l], xv[l], att, B, H, T, 1, ko, s, nullptr, SlabIn{}, 0, qp);
     } else {
       SlabIn sq = split(wq[l], h, d, d, 4, bias);
-      launch_cross_attn_decode<bf16_t>(q, xk[l], xv[l], att, B, H, T, 1, s, nullptr, sq);
+      launch_cross_attn_decode<bf16_t>(q, xk[l], xv[l], att, B, H, T, 1, ko, s, nullptr, sq);
     }
     pend = split(wox[l], att, d, d, 4, bias).n; pend_stride = (int64_t)B * d;
     ln();
-    { GemmEpi e; e.bias = bias; e.act = 1; e.out_t = mid; e.ldc = F; launch_gemm_skinny(w1[l], h, B, F, d, e, s); }
+    { GemmEpi e; e.bias = bias; e.act = 1; e.out_t = mid; e.ldc = F; launch_gemm_skinny(w1[l], h, B, F, d, e, ko, s); }
     pend = split(w2[l], mid, d, F, 8, bias).n; pend_stride = (int64_t)B * d;
   };
   // ---- checks on layer 0: x after the layer's LN3 input sums (residual rows) and the cross-attention output

@@ -146,6 +146,7 @@ static void* dmal(size_t bytes, int mode) {
 }
 
 int main() {
+  KernelOpts ko;   // the kernel-variant options the launchers are handed (common.hpp)
   const int B = 32, d = 1280, L = 16;   // L independent (counter, weights) instances per replay, like layers
   hipStream_t s; hipStreamCreate(&s);
   struct Shape { const char* name; int N; } shapes[] = {{"q (N=1280)", 1280}, {"qkv (N=3840)", 3840}, {"fc1 (N=5120)", 5120}};
@@ -160,11 +161,11 @@ int main() {
   const int NW = 8, n_prod = (B + NW - 1) / NW;
   for (auto& sh : shapes) {
     const int N = sh.N;
-    auto residual = [&](int l) { GemmEpi e; e.bias = bias; e.residual = x; e.out_f32 = x; e.ldc = d; launch_gemm_skinny(wo[l], att, B, d, d, e, s); };
+    auto residual = [&](int l) { GemmEpi e; e.bias = bias; e.residual = x; e.out_f32 = x; e.ldc = d; launch_gemm_skinny(wo[l], att, B, d, d, e, ko, s); };
     auto sep = [&](int l) {
       residual(l);
       launch_layernorm<bf16_t>(x, gamma, beta, h_sep, B, d, s);
-      GemmEpi e; e.bias = bias; e.out_t = out_sep; e.ldc = N; launch_gemm_skinny(wg[l], h_sep, B, N, d, e, s);
+      GemmEpi e; e.bias = bias; e.out_t = out_sep; e.ldc = N; launch_gemm_skinny(wg[l], h_sep, B, N, d, e, ko, s);
     };
     auto fus = [&](int l) {
       residual(l);
@@ -190,7 +191,7 @@ int main() {
     hipMemsetAsync(counters, 0, 4096, s); hipMemsetAsync(step, 0, 16, s);
     { std::vector<float> hx((size_t)B * d); for (auto& v : hx) v = (rand() % 4001 - 2000) * 1e-3f; hipMemcpyAsync(x, hx.data(), hx.size() * 4, hipMemcpyHostToDevice, s); hipStreamSynchronize(s); }
     launch_layernorm<bf16_t>(x, gamma, beta, h_sep, B, d, s);
-    { GemmEpi e; e.bias = bias; e.out_t = out_sep; e.ldc = N; launch_gemm_skinny(wg[0], h_sep, B, N, d, e, s); }
+    { GemmEpi e; e.bias = bias; e.out_t = out_sep; e.ldc = N; launch_gemm_skinny(wg[0], h_sep, B, N, d, e, ko, s); }
     { GemmEpi e; e.bias = bias; e.out_t = out_fus; e.ldc = N;
       hipLaunchKernelGGL((ln_gemm_fused_kernel<NW>), dim3(n_prod + N / 32), dim3(NW * 64), 0, s, wg[0], x, gamma, beta, h_fus, counters, step, timeout, B, N, d, n_prod, e); }
     hipStreamSynchronize(s);

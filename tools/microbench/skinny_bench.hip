@@ -18,6 +18,7 @@ static void* dmal(size_t bytes, int fill_rand) {
   return p;
 }
 int main() {
+  KernelOpts ko;   // the kernel-variant options the launchers are handed (common.hpp)
   const int B = 32, L = 16;
   hipStream_t s; hipStreamCreate(&s);
   struct Shape { const char* name; int N, K; int residual; int act; } shapes[] = {
@@ -33,7 +34,7 @@ int main() {
     for (int i = 0; i < 64; ++i) {
       GemmEpi e; e.bias = bias; e.ldc = sh.N; e.act = sh.act;
       if (sh.residual) { e.residual = x; e.out_f32 = x; } else e.out_t = out;
-      launch_gemm_skinny(w[i % L], in, B, sh.N, sh.K, e, s);
+      launch_gemm_skinny(w[i % L], in, B, sh.N, sh.K, e, ko, s);
     }
     hipStreamEndCapture(s, &gr); hipGraphInstantiate(&ex, gr, nullptr, nullptr, 0);
     double us = timeit(s, [&] { hipGraphLaunch(ex, s); }, 10) / 64;

@@ -37,6 +37,7 @@ __global__ void k_traffic(const u32x4* __restrict__ W, const bf16_t* __restrict_
   if (a == 0x12345u) out[threadIdx.x] = 1.f;
 }
 int main() {
+  KernelOpts ko;   // the kernel-variant options the launchers are handed (common.hpp)
   const int B = 32, L = 40;
   hipStream_t s; hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
   struct Shape { const char* name; int N, K, ks, act; } shapes[] = {
@@ -60,8 +61,8 @@ int main() {
     };
     const double real = chain([&](bf16_t* W) {
       GemmEpi e; e.ldc = sh.N; e.act = sh.act;
-      if (sh.ks > 1) launch_gemm_skinny(W, in, B, sh.N, sh.K, e, s, sh.ks, slab, (int64_t)B * sh.N);
-      else { e.bias = bias; e.out_t = out; launch_gemm_skinny(W, in, B, sh.N, sh.K, e, s); } });
+      if (sh.ks > 1) launch_gemm_skinny(W, in, B, sh.N, sh.K, e, ko, s, sh.ks, slab, (int64_t)B * sh.N);
+      else { e.bias = bias; e.out_t = out; launch_gemm_skinny(W, in, B, sh.N, sh.K, e, ko, s); } });
     const int ks_per = sh.K / 16;
     int nw = 4; if (sh.ks == 1) { while (nw < 16 && ks_per % (nw * 2) == 0 && ks_per / nw > 10) nw *= 2; if (nw < 8) nw = 8; }
     const int steps = ks_per / (nw * sh.ks);

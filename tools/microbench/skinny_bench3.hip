@@ -1,4 +1,4 @@
-// Round 5: as skinny_bench2, for the 20-row n-block layout (g_skinny_narrow = 1) against the 32-row one (= 0).
+// Round 5: as skinny_bench2, for the 20-row n-block layout (KernelOpts::skinny_narrow = 1) against the 32-row one (= 0).
 // The real decode GEMM per Whisper-large shape in the round-2 form (K slices -> f32 slabs), un-profiled wall time per
 // launch in a graph-replayed chain over 40 distinct (cold: 40 x 3..13 MB > Infinity Cache for the big ones) weight
 // matrices, next to a synthetic kernel that only moves the same bytes (k_traffic: W once, x per workgroup).
@@ -38,6 +38,7 @@ __global__ void k_traffic(const u32x4* __restrict__ W, const bf16_t* __restrict_
   if (a == 0x12345u) out[threadIdx.x] = 1.f;
 }
 int main() {
+  KernelOpts ko;   // the kernel-variant options the launchers are handed (common.hpp)
   const int B = 32, L = 40;
   hipStream_t s; hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
   struct Shape { const char* name; int N, K, ks, act; } shapes[] = {
@@ -60,11 +61,11 @@ int main() {
     };
     double real_by[2];
     for (int narrow = 0; narrow < 2; ++narrow) {
-      g_skinny_narrow = narrow;
+      ko.skinny_narrow = narrow;
       real_by[narrow] = chain([&](bf16_t* W) {
         GemmEpi e; e.ldc = sh.N; e.act = sh.act;
-        if (sh.ks > 1) launch_gemm_skinny(W, in, B, sh.N, sh.K, e, s, sh.ks, slab, (int64_t)B * sh.N);
-        else { e.bias = bias; e.out_t = out; launch_gemm_skinny(W, in, B, sh.N, sh.K, e, s); } });
+        if (sh.ks > 1) launch_gemm_skinny(W, in, B, sh.N, sh.K, e, ko, s, sh.ks, slab, (int64_t)B * sh.N);
+        else { e.bias = bias; e.out_t = out; launch_gemm_skinny(W, in, B, sh.N, sh.K, e, ko, s); } });
     }
     const double real = real_by[0];
     const int ks_per = sh.K / 16;

@@ -1,5 +1,5 @@
 // Cross-attention decode kernel variants over 32 layers of cold cross-KV (B = 32, large-v3: 246 MB per launch), graph replays.
-//   g_xattn_variant: bit0 nontemporal loads, bit1 software-pipelined form (the U / row-mapping sweep of round 4 edited the
+//   KernelOpts::xattn_variant: bit0 nontemporal loads, bit1 software-pipelined form (the U / row-mapping sweep of round 4 edited the
 //   template argument in launch_cross_attn_decode: results in profiles/r4_xattn_pipeline.txt)
 // Checks that every variant's output is bit-identical to variant 1 (the shipped kernel), then interleaved timing rounds.
 #include "../../taiwan_tongues_asr_ce_amd/csrc/kernels_attn.hip"
@@ -21,6 +21,7 @@ static void* dmal(size_t bytes, int fill, float scale = 1.f) {
   return p;
 }
 int main(int argc, char** argv) {
+  KernelOpts ko;   // the kernel-variant options the launchers are handed (common.hpp)
   const int B = argc > 1 ? atoi(argv[1]) : 32, d = 1280, H = 20, T = argc > 2 ? atoi(argv[2]) : 1500, L = 32;
   hipStream_t s; hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
   float* bias = (float*)dmal(d * 4, 2, 0.1f);
@@ -32,19 +33,19 @@ int main(int argc, char** argv) {
   const int variants[] = {1, 3, 0, 2};
   std::vector<uint16_t> ref((size_t)B * d), got((size_t)B * d);
   for (int v : variants) {
-    g_xattn_variant = v;
+    ko.xattn_variant = v;
     hipMemset(att, 0, B * d * 2);
-    launch_cross_attn_decode<bf16_t>(q, xk[0], xv[0], att, B, H, T, 1, s, nullptr, sq);
+    launch_cross_attn_decode<bf16_t>(q, xk[0], xv[0], att, B, H, T, 1, ko, s, nullptr, sq);
     hipStreamSynchronize(s);
     hipMemcpy(v == 1 ? ref.data() : got.data(), att, ref.size() * 2, hipMemcpyDeviceToHost);
     if (v != 1) { size_t nd = 0; for (size_t i = 0; i < ref.size(); ++i) nd += ref[i] != got[i]; printf("variant %d: %zu of %zu outputs differ from variant 1 (%s)\n", v, nd, ref.size(), hipGetErrorString(hipGetLastError())); }
   }
   hipGraphExec_t ex[32];
   for (int v : variants) {
-    g_xattn_variant = v;
+    ko.xattn_variant = v;
     hipGraph_t gr;
     hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-    for (int l = 0; l < L; ++l) launch_cross_attn_decode<bf16_t>(q, xk[l], xv[l], att, B, H, T, 1, s, nullptr, sq);
+    for (int l = 0; l < L; ++l) launch_cross_attn_decode<bf16_t>(q, xk[l], xv[l], att, B, H, T, 1, ko, s, nullptr, sq);
     hipStreamEndCapture(s, &gr); hipGraphInstantiate(&ex[v], gr, nullptr, nullptr, 0); hipGraphDestroy(gr);
   }
   const double bytes = (double)B * (2.0 * T * d + 2 * d) * 2;

@@ -6,7 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-thread_local bool g_kernel_sig_on = false; thread_local char g_kernel_sig[192] = ""; thread_local int g_xattn_variant = 3; thread_local int g_skinny_nt = 1;
+thread_local bool g_kernel_sig_on = false; thread_local char g_kernel_sig[192] = "";
 static void* dmal(size_t bytes, int fill) {
   void* p; if (hipMalloc(&p, bytes) != hipSuccess) { printf("alloc failed\n"); exit(1); }
   if (fill) { std::vector<uint8_t> h(1 << 22); for (auto& v : h) { v = rand() & 0xff; if ((v & 0x7f) == 0x7f) v &= 0xf7; }   // no NaN encodings
@@ -16,7 +16,7 @@ static void* dmal(size_t bytes, int fill) {
 }
 template <int U> void launch(const bf16_t* q, const uint8_t* K, const uint8_t* V, const float* ks, const float* vs, bf16_t* out, int B, int H, int T, SlabIn sq, hipStream_t s) {
   const size_t lds = sizeof(float) * (T + 4 * 64 + 8);
-  hipLaunchKernelGGL((cross_attn_fp8_kernel<bf16_t, true, U>), dim3(H, B), dim3(256), lds, s, q, K, V, ks, vs, out, H, T, sq);
+  hipLaunchKernelGGL((cross_attn_fp8_kernel<bf16_t, true, U>), dim3(H, B), dim3(256), lds, s, q, K, V, ks, vs, out, (const int32_t*)nullptr /*every row live*/, H, T, sq);
 }
 int main(int argc, char** argv) {
   const int B = argc > 1 ? atoi(argv[1]) : 32, d = 1280, H = 20, T = 1500, L = 32;
