@@ -10,9 +10,6 @@
 #include "common.hpp"
 #include <type_traits>
 #include <mutex>
-#ifndef TTASR_V5_DMA
-#define TTASR_V5_DMA 0   // where the persistent GEMM issues stage t + 3 (lab builds: 1 / 2 / 3 = variants measured in round 5)
-#endif
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -413,7 +410,7 @@ template void launch_gemm_bf16_v2<bf16_t>(const GemmArgs&, hipStream_t);
 template void launch_gemm_bf16_v2<f16_t>(const GemmArgs&, hipStream_t);
 
 // ------------------------------------------------------------------------------------------------
-// gemm_bf16_v3: 256x256x32 stages, FOUR-stage LDS ring (128 KiB), 8 waves as 2 (M) x 4 (N), 128x64 per wave.
+// The 256x256x32 tile: 32-deep stages, FOUR-stage LDS ring (128 KiB), 8 waves as 2 (M) x 4 (N), 128x64 per wave.
 // The two wave groups (waves 0-3 / 4-7, i.e. the two SIMD partners) run staggered by one barrier: while
 // one group issues its LDS-DMA (4 x global_load_lds) and fragment reads (12 x ds_read_b128), its partner
 // on the same SIMD runs its 32 MFMAs, so the matrix pipe sees matrix-beside-memory instead of two waves
@@ -427,99 +424,244 @@ template void launch_gemm_bf16_v2<f16_t>(const GemmArgs&, hipStream_t);
 // before the barrier that precedes the first overwrite.
 // LDS image per operand stage: [256 rows][4 chunks of 16 B]; chunk c of row r sits in slot c ^ H((r>>2)&3),
 // H = {0,2,3,1}, which makes every ds_read_b128 lane group hit 16 distinct 16-byte bank slots.
+//
+// The tile is written ONCE, as the blocks of namespace t256:
+//   xcd_chunk, raster       which tile a workgroup runs: contiguous chunk per XCD, bands of GM m-tiles inside it
+//   Lane                    where a thread sits in the workgroup; its fragment offsets
+//   Stager                  a wave's 2 + 2 LDS-DMA source pointers; stage(slot, k0); prologue() = stages 0..2
+//   mainloop<T16, MI, ..>   the phase-A / phase-B loop above with its counted waits, for MI row blocks of 16 per wave group
+//   load_bias               the lane's 16 bias values, waited for on the spot
+//   out_cols, store_tile_t  the T-output epilogue: bias, GELU, pack, permlane16_swap, 16-byte stores (guarded or clamped)
+// and two kernels compose them: gemm_bf16_v3_kernel (one workgroup per tile; adds the f32 / residual / row-table epilogue) and
+// gemm_bf16_persistent_kernel (one workgroup per CU walks its tiles; TAIL = false is "v4", TAIL = true is "v5").
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int v3_h(int q) { return (0x78 >> (q * 2)) & 3; }  // {0,2,3,1} packed two bits each
 
-template <typename T16, int EPI>  // EPI: bit0 GELU, bit1 residual, bit2 row table (positions), bit3 head-split T output, bit4 f32 output
-__global__ __launch_bounds__(512, 2) void gemm_bf16_v3_kernel(GemmArgs g, int tiles_m, int tiles_n) {
-  constexpr int BM = 256, BN = 256, BK = 32;
-  constexpr int OP_BYTES = BM * BK * 2, STAGE_BYTES = 2 * OP_BYTES;  // 16K + 16K
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 2, wn = wave & 3;
-  const int nwg = tiles_m * tiles_n;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  constexpr int GM = 4;
+namespace t256 {
+constexpr int BM = 256, BN = 256, BK = 32;
+constexpr int OP_BYTES = BM * BK * 2, STAGE_BYTES = 2 * OP_BYTES, LDS_BYTES = 4 * STAGE_BYTES;  // 16K + 16K per stage
+constexpr int GM = 4;
+
+// The workgroups that share an XCD (blockIdx % 8, round-robin dispatch) own one contiguous range [lo, hi) of n tiles.
+__device__ __forceinline__ void xcd_chunk(int n, int xcd, int& lo, int& hi) {
+  const int q = n >> 3, r = n & 7;
+  lo = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+  hi = lo + (xcd < r ? q + 1 : q);
+}
+
+// Grouped raster of a region of tiles_m x tiles_n tiles that starts at row base_row: bands of GM m-tiles, n-tile fastest across
+// the band, m-tile fastest inside it, so the ~32 tiles an XCD runs at once form a 4 x 8 patch (see gemm_bf16_v2_kernel).
+__device__ __forceinline__ void raster(int tile, int tiles_m, int tiles_n, int base_row, int rows_per_tile, int& m0, int& n0) {
   const int band = tile / (GM * tiles_n);
   const int rows_in_band = min(GM, tiles_m - band * GM);
   const int in_band = tile - band * GM * tiles_n;
   const int tn = in_band / rows_in_band;
   const int tm = band * GM + (in_band - tn * rows_in_band);
-  const int m0 = tm * BM, n0 = tn * BN;
-  const bf16_t* A = (const bf16_t*)g.A + (int64_t)blockIdx.z * g.batch_stride_a;
-  const bf16_t* W = (const bf16_t*)g.W;
-  // staging: one wave-instruction = 16 rows x 64 B; wave w moves rows (2w+p)*16 .. +15 of A and of W
-  const int srow = lane >> 2, sslot = lane & 3;
+  m0 = base_row + tm * rows_per_tile; n0 = tn * BN;
+}
+
+struct Lane {
+  char* smem;
+  int lane, wave, wm, wn, fr, fq;
+  uint32_t lds_base, frag_off;
+  __device__ __forceinline__ explicit Lane(char* smem_) : smem(smem_) {
+    lane = threadIdx.x & 63;
+    wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    wm = wave >> 2; wn = wave & 3;
+    fr = lane & 15; fq = lane >> 4;
+    lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+    // per-lane fragment offset inside an operand stage (row r = base + 16*i + fr -> (r>>2)&3 == (fr>>2)&3)
+    frag_off = (uint32_t)(fr * 64 + ((fq ^ v3_h((fr >> 2) & 3)) << 4));
+  }
+  // LDS addresses of the lane's first A / W fragment in slot 0 (mi = row blocks of 16 per wave group)
+  __device__ __forceinline__ uint32_t a_off(int mi) const { return lds_base + wm * (mi * 16) * 64 + frag_off; }
+  __device__ __forceinline__ uint32_t w_off() const { return lds_base + OP_BYTES + wn * 64 * 64 + frag_off; }
+  __device__ __forceinline__ int nbase(int n0) const { return n0 + wn * 64 + fq * 4; }   // the lane's first output column
+};
+
+// staging: one wave-instruction = 16 rows x 64 B; wave w moves rows (2w+p)*16 .. +15 of A and of W
+struct Stager {
   const bf16_t* a_src[2];
   const bf16_t* w_src[2];
+  // A rows from m0 (clamped to row_lim: rows past it are loaded but never stored), W rows from n0
+  __device__ __forceinline__ void point(const Lane& L, const bf16_t* A, int64_t lda, int m0, int row_lim, const bf16_t* W, int64_t ldw, int n0) {
+    const int srow = L.lane >> 2, sslot = L.lane & 3;
 #pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    const int row = (wave * 2 + p) * 16 + srow;
-    const int chunk = sslot ^ v3_h((row >> 2) & 3);
-    a_src[p] = A + (int64_t)min(m0 + row, g.M - 1) * g.lda + chunk * 8;
-    w_src[p] = W + (int64_t)(n0 + row) * g.ldw + chunk * 8;
+    for (int p = 0; p < 2; ++p) {
+      const int row = (L.wave * 2 + p) * 16 + srow;
+      const int chunk = sslot ^ v3_h((row >> 2) & 3);
+      a_src[p] = A + (int64_t)min(m0 + row, row_lim) * lda + chunk * 8;
+      w_src[p] = W + (int64_t)(n0 + row) * ldw + chunk * 8;
+    }
   }
-#define V3_STAGE(slot_, k0_)                                                                   \
-  do {                                                                                         \
-    char* base_ = smem + (slot_) * STAGE_BYTES;                                                \
-    _Pragma("unroll") for (int p = 0; p < 2; ++p) {                                            \
-      glds16(a_src[p] + (k0_), base_ + (wave * 2 + p) * 1024);                                 \
-      glds16(w_src[p] + (k0_), base_ + OP_BYTES + (wave * 2 + p) * 1024);                      \
-    }                                                                                          \
-  } while (0)
-
-  f32x4 acc[8][4];
+  __device__ __forceinline__ void stage(const Lane& L, int slot, int k0) const {
+    char* base = L.smem + slot * STAGE_BYTES;
 #pragma unroll
-  for (int i = 0; i < 8; ++i)
+    for (int p = 0; p < 2; ++p) {
+      glds16(a_src[p] + k0, base + (L.wave * 2 + p) * 1024);
+      glds16(w_src[p] + k0, base + OP_BYTES + (L.wave * 2 + p) * 1024);
+    }
+  }
+  __device__ __forceinline__ void prologue(const Lane& L) const { stage(L, 0, 0); stage(L, 1, BK); stage(L, 2, 2 * BK); }
+};
+
+// "own pieces of the wanted stage landed": everything but the 4 youngest pieces and the `carried` stores of the previous tile's
+// epilogue (vmcnt retires in issue order).  carried = 2 per row block of that tile (16 / 12 / 8), or 0.
+__device__ __forceinline__ void wait_stage(int carried) {
+  if (carried == 16) asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
+  else if (carried == 12) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+  else if (carried == 8) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+  else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+}
+template <int MI>
+__device__ __forceinline__ void wait_frags(s16x8 (&a)[MI], s16x8 (&b)[4]) {
+  static_assert(MI == 8 || MI == 6 || MI == 4, "row blocks per wave group");
+  if constexpr (MI == 8)
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]),
+                   "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]));
+  else if constexpr (MI == 6)
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]));
+  else
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]));
+}
+
+// One tile's K loop: acc = A[m-rows] * W[n-rows]^T for MI x 4 fragments of 16 x 16 per wave.  On entry the three stages of
+// Stager::prologue are in flight, with `carried` stores of the previous tile's epilogue issued behind them (persistent kernel) or
+// none (v3); on exit every fragment read is drained, so the ring is free.  A shorter tile (MI = 6 / 4) is the same body with
+// fewer row blocks: the A image is still staged 256 rows deep, every output element sees the same K loop in the same order.
+// PEEL: the test for the carried waits does not look at `carried`, so the compiler peels iterations 0 and 1 off the loop (what the
+// tail-re-tiled form has always had; measured: without it its qkv / out-proj / fc1 are 1.5-4 % slower, LAB_NOTEBOOK).
+template <typename T16, int MI, bool PEEL>
+__device__ __forceinline__ void mainloop(f32x4 (&acc)[MI][4], const Lane& L, const Stager& st, uint32_t a_off, uint32_t w_off, int nt,
+                                         int carried) {
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int nt = g.K / BK;  // >= 4
-  V3_STAGE(0, 0);
-  V3_STAGE(1, BK);
-  V3_STAGE(2, 2 * BK);
-  asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // stages 0 and 1 landed (own pieces)
-  if (wm == 1) __builtin_amdgcn_s_barrier();        // stagger: group 1 runs one barrier behind
-
-  const int fr = lane & 15, fq = lane >> 4;
-  const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  // per-lane fragment offsets inside an operand stage (row r = base + 16*i + fr -> (r>>2)&3 == (fr>>2)&3)
-  const uint32_t frag_off = (uint32_t)(fr * 64 + ((fq ^ v3_h((fr >> 2) & 3)) << 4));
-  const uint32_t a_off = lds_base + wm * 128 * 64 + frag_off;
-  const uint32_t w_off = lds_base + OP_BYTES + wn * 64 * 64 + frag_off;
-
+  // stages 0 and 1 landed (own pieces); queue behind them: stage 2 (4) [+ the carried stores]
+  wait_stage(carried);
+  if (L.wm == 1) __builtin_amdgcn_s_barrier();  // stagger: group 1 runs one barrier behind
   for (int t = 0; t < nt; ++t) {
     // ---- phase A ----
-    if (t + 2 < nt) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (t + 2 < nt) {
+      // own pieces of stage t + 1 landed; queue behind them: stage t + 2 (4), and for t < 2 of a carried tile its stores
+      // (t = 0: [stage 2][stores]; t = 1: [stores][stage 3] - from t = 2 on the stores are older than what is waited for)
+      if ((PEEL || carried) && t < 2) wait_stage(carried); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    if (t + 3 < nt) V3_STAGE((t + 3) & 3, (t + 3) * BK);
-    s16x8 a[8], b[4];
+    if (t + 3 < nt) st.stage(L, (t + 3) & 3, (t + 3) * BK);
+    s16x8 a[MI], b[4];
     const uint32_t so = (uint32_t)((t & 3) * STAGE_BYTES);
 #pragma unroll
     for (int j = 0; j < 4; ++j) asm volatile("ds_read_b128 %0, %1" : "=v"(b[j]) : "v"(w_off + so + j * 16 * 64));
 #pragma unroll
-    for (int i = 0; i < 8; ++i) asm volatile("ds_read_b128 %0, %1" : "=v"(a[i]) : "v"(a_off + so + i * 16 * 64));
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]),
-                   "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]));
+    for (int i = 0; i < MI; ++i) asm volatile("ds_read_b128 %0, %1" : "=v"(a[i]) : "v"(a_off + so + i * 16 * 64));
+    wait_frags<MI>(a, b);
     __builtin_amdgcn_sched_barrier(0);
     // ---- phase B ----
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-    for (int i = 0; i < 8; ++i)
+    for (int i = 0; i < MI; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j)  // A operand = weight rows (n), B operand = activation rows (m)
         acc[i][j] = N16<T16>::mfma16(b[j], a[i], acc[i][j]);
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
   }
-  if (wm == 0) __builtin_amdgcn_s_barrier();  // balance the barrier count
-#undef V3_STAGE
+  if (L.wm == 0) __builtin_amdgcn_s_barrier();  // balance the barrier count: every fragment read of this tile is drained
+}
+
+// the lane's bias values for columns n + 16 j .. + 3 (bias_n = bias + Lane::nbase)
+__device__ __forceinline__ void load_bias(const float* bias_n, float4 (&b4)[4]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) b4[j] = *(const float4*)(bias_n + j * 16);
+  // waited for HERE, while nothing else is in flight: no later use of these registers may drain the LDS-DMA queue
+  asm volatile("s_waitcnt vmcnt(0)" : "+v"(b4[0].x), "+v"(b4[0].y), "+v"(b4[0].z), "+v"(b4[0].w), "+v"(b4[1].x), "+v"(b4[1].y),
+               "+v"(b4[1].z), "+v"(b4[1].w), "+v"(b4[2].x), "+v"(b4[2].y), "+v"(b4[2].z), "+v"(b4[2].w), "+v"(b4[3].x),
+               "+v"(b4[3].y), "+v"(b4[3].z), "+v"(b4[3].w));
+}
+
+// column part of the T-output index of the lane's four column groups nbase + 16 j, on top of `base` (HS: head-split scatter)
+template <bool HS>
+__device__ __forceinline__ void out_cols(const GemmEpi& e, int nbase, int64_t base, int64_t (&coloff)[4]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int n = nbase + j * 16;
+    if (HS) {
+      const int which = n / e.hs_d, nn = n - which * e.hs_d;
+      coloff[j] = base + (int64_t)which * e.hs_which + (int64_t)(nn >> 6) * e.hs_T * 64 + (nn & 63);
+    } else {
+      coloff[j] = base + n;
+    }
+  }
+}
+
+// T-output epilogue of MI row blocks (rows mrow0 + 16 i): bias, GELU (EPI bit 0), pack, 2 x 16-byte stores per row block and lane;
+// the row part of the index is head-split (EPI bit 3) or zoff + m * ldc.  GUARD: rows >= M are not stored (v3); otherwise the stores
+// are unconditional with the row index clamped (rows past M replicate row M-1's operands, so they write row M-1's own values again):
+// the in-flight count the next tile's first waits rely on is then exact for every wave.
+template <typename T16, int MI, int EPI, bool GUARD>
+__device__ __forceinline__ void store_tile_t(const f32x4 (&acc)[MI][4], const float4 (&bias4)[4], const GemmEpi& e, int M, int64_t zoff,
+                                             int mrow0, const int64_t (&coloff)[4], const Lane& L) {
+  constexpr bool ACT = EPI & 1, HS = EPI & 8;
+  static_assert((EPI & ~9) == 0, "T output: no residual, no row table");
+  // Widen the 16-bit stores (guide T21, 16-lane form): lanes l and l^16 hold columns 4q..4q+3 and 4q+4..4q+7 of
+  // the same row, so one v_permlane16_swap per dword over a pair of column groups (j, j+1) leaves the even
+  // 16-lane rows with 16 contiguous bytes of group j and the odd rows with 16 contiguous bytes of group j+1:
+  // 16 x 16-byte stores per lane instead of 32 x 8-byte (the store tail is issue-bound, not bandwidth-bound).
+  const bool odd = (L.fq & 1) != 0;
+#pragma unroll
+  for (int i = 0; i < MI; ++i) {
+    const int m = min(mrow0 + i * 16, M - 1);
+    int64_t rowoff;
+    if (HS) {
+      const int bb = m / e.hs_T, tt = m - bb * e.hs_T;
+      rowoff = ((int64_t)bb * e.hs_H * e.hs_T + tt) * 64;
+    } else rowoff = zoff + (int64_t)m * e.ldc;
+    uint2 pk[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      f32x4 v = acc[i][j];
+      v[0] += bias4[j].x; v[1] += bias4[j].y; v[2] += bias4[j].z; v[3] += bias4[j].w;
+      if (ACT) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) v[t] = gelu_fast(v[t]);
+      }
+      pk[j].x = N16<T16>::pk(v[0], v[1]);
+      pk[j].y = N16<T16>::pk(v[2], v[3]);
+    }
+#pragma unroll
+    for (int jp = 0; jp < 4; jp += 2) {
+      auto sx = __builtin_amdgcn_permlane16_swap(pk[jp].x, pk[jp + 1].x, false, false);
+      auto sy = __builtin_amdgcn_permlane16_swap(pk[jp].y, pk[jp + 1].y, false, false);
+      // even row: {own group jp, partner's group jp}; odd row: {partner's group jp+1, own group jp+1}
+      const uint4 w = make_uint4(sx[0], sy[0], sx[1], sy[1]);
+      const int jj = odd ? jp + 1 : jp;
+      if (!GUARD || mrow0 + i * 16 < M) *(uint4*)((bf16_t*)e.out_t + rowoff + coloff[jj] - (odd ? 4 : 0)) = w;
+    }
+  }
+}
+}  // namespace t256
+
+// ------------------------------------------------------------------------------------------------
+// gemm_bf16_v3: one workgroup per 256x256 tile.
+// ------------------------------------------------------------------------------------------------
+template <typename T16, int EPI>  // EPI: bit0 GELU, bit1 residual, bit2 row table (positions), bit3 head-split T output, bit4 f32 output
+__global__ __launch_bounds__(512, 2) void gemm_bf16_v3_kernel(GemmArgs g, int tiles_m, int tiles_n) {
+  using namespace t256;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const Lane L(smem);
+  int lo, hi, m0, n0;
+  xcd_chunk(tiles_m * tiles_n, blockIdx.x & 7, lo, hi);
+  raster(lo + (blockIdx.x >> 3), tiles_m, tiles_n, 0, BM, m0, n0);
+  Stager st;
+  st.point(L, (const bf16_t*)g.A + (int64_t)blockIdx.z * g.batch_stride_a, g.lda, m0, g.M - 1, (const bf16_t*)g.W, g.ldw, n0);
+  st.prologue(L);
+  f32x4 acc[8][4];
+  mainloop<T16, 8, false>(acc, L, st, L.a_off(8), L.w_off(), g.K / BK /* >= 4 */, 0);
   // ---- epilogue, specialised at compile time (EPI) so no integer division / dead branch survives for the
   // common shapes; row offsets are computed once per row, column parts once per column group, and every load
   // (bias, positions, residual) is issued ahead of the stores it feeds.  (The generic per-element epilogue cost
@@ -527,588 +669,204 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_v3_kernel(GemmArgs g, int ti
   constexpr bool ACT = EPI & 1, RES = EPI & 2, ROWTAB = EPI & 4, HS = EPI & 8, OUTF = EPI & 16;
   const GemmEpi& e = g.epi;
   const int64_t zoff = (int64_t)blockIdx.z * e.batch_stride_c;
-  const int nbase = n0 + wn * 64 + fq * 4;
+  const int nbase = L.nbase(n0);
   float4 bias4[4];
-  int64_t coloff[4];  // column part of the output index
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int n = nbase + j * 16;
-    bias4[j] = e.bias ? *(const float4*)(e.bias + n) : make_float4(0.f, 0.f, 0.f, 0.f);
-    if (HS) {
-      const int which = n / e.hs_d, nn = n - which * e.hs_d;
-      coloff[j] = (int64_t)which * e.hs_which + (int64_t)(nn >> 6) * e.hs_T * 64 + (nn & 63);
-    } else {
-      coloff[j] = n;
-    }
-  }
+  for (int j = 0; j < 4; ++j) bias4[j] = e.bias ? *(const float4*)(e.bias + nbase + j * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
+  if constexpr (!OUTF) {
+    int64_t coloff[4];
+    out_cols<HS>(e, nbase, 0, coloff);
+    store_tile_t<T16, 8, EPI, true>(acc, bias4, e, g.M, zoff, m0 + L.wm * 128 + L.fr, coloff, L);
+  } else {
+    // f32 output at zoff + m * ldc + n, with the residual and / or the row table (positions) added
 #pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    float4 extra[4][4];
-    int64_t rowoff[4];  // row part of the output index (T output); f32 / residual use zoff + m * ldc
-    int64_t rowlin[4];
+    for (int half = 0; half < 2; ++half) {
+      float4 extra[4][4];
+      int64_t rowlin[4];
 #pragma unroll
-    for (int ii = 0; ii < 4; ++ii) {
-      const int m = min(m0 + wm * 128 + (half * 4 + ii) * 16 + fr, g.M - 1);
-      rowlin[ii] = zoff + (int64_t)m * e.ldc;
-      if (HS) {
-        const int bb = m / e.hs_T, tt = m - bb * e.hs_T;
-        rowoff[ii] = ((int64_t)bb * e.hs_H * e.hs_T + tt) * 64;
-      } else {
-        rowoff[ii] = rowlin[ii];
+      for (int ii = 0; ii < 4; ++ii) {
+        const int m = min(m0 + L.wm * 128 + (half * 4 + ii) * 16 + L.fr, g.M - 1);
+        rowlin[ii] = zoff + (int64_t)m * e.ldc;
+        if (RES || ROWTAB) {
+          const int64_t tabrow = ROWTAB ? (int64_t)(m % e.rowmod) * e.ldc : 0;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (RES) r = *(const float4*)(e.residual + rowlin[ii] + nbase + j * 16);
+            if (ROWTAB) {
+              const float4 t = *(const float4*)(e.rowtab + tabrow + nbase + j * 16);
+              r.x += t.x; r.y += t.y; r.z += t.z; r.w += t.w;
+            }
+            extra[ii][j] = r;
+          }
+        }
       }
-      if (RES || ROWTAB) {
-        const int64_t tabrow = ROWTAB ? (int64_t)(m % e.rowmod) * e.ldc : 0;
+#pragma unroll
+      for (int ii = 0; ii < 4; ++ii) {
+        const int i = half * 4 + ii;
+        const bool row_ok = m0 + L.wm * 128 + i * 16 + L.fr < g.M;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (RES) r = *(const float4*)(e.residual + rowlin[ii] + nbase + j * 16);
-          if (ROWTAB) {
-            const float4 t = *(const float4*)(e.rowtab + tabrow + nbase + j * 16);
-            r.x += t.x; r.y += t.y; r.z += t.z; r.w += t.w;
+          f32x4 v = acc[i][j];
+          v[0] += bias4[j].x; v[1] += bias4[j].y; v[2] += bias4[j].z; v[3] += bias4[j].w;
+          if (ACT) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) v[t] = gelu_fast(v[t]);
           }
-          extra[ii][j] = r;
-        }
-      }
-    }
-#pragma unroll
-    for (int ii = 0; ii < 4; ++ii) {
-      const int i = half * 4 + ii;
-      const bool row_ok = m0 + wm * 128 + i * 16 + fr < g.M;
-      uint2 pk[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        f32x4 v = acc[i][j];
-        v[0] += bias4[j].x; v[1] += bias4[j].y; v[2] += bias4[j].z; v[3] += bias4[j].w;
-        if (ACT) {
-#pragma unroll
-          for (int t = 0; t < 4; ++t) v[t] = gelu_fast(v[t]);
-        }
-        if (RES || ROWTAB) { v[0] += extra[ii][j].x; v[1] += extra[ii][j].y; v[2] += extra[ii][j].z; v[3] += extra[ii][j].w; }
-        if (OUTF) {
+          if (RES || ROWTAB) { v[0] += extra[ii][j].x; v[1] += extra[ii][j].y; v[2] += extra[ii][j].z; v[3] += extra[ii][j].w; }
           if (row_ok) *(float4*)(e.out_f32 + rowlin[ii] + nbase + j * 16) = make_float4(v[0], v[1], v[2], v[3]);
-        } else {
-          pk[j].x = N16<T16>::pk(v[0], v[1]);
-          pk[j].y = N16<T16>::pk(v[2], v[3]);
-        }
-      }
-      if (!OUTF) {
-        // Widen the bf16 stores (guide T21, 16-lane form): lanes l and l^16 hold columns 4q..4q+3 and 4q+4..4q+7 of
-        // the same row, so one v_permlane16_swap per dword over a pair of column groups (j, j+1) leaves the even
-        // 16-lane rows with 16 contiguous bytes of group j and the odd rows with 16 contiguous bytes of group j+1:
-        // 16 x 16-byte stores per lane instead of 32 x 8-byte (the store tail is issue-bound, not bandwidth-bound).
-        const bool odd = (fq & 1) != 0;
-#pragma unroll
-        for (int jp = 0; jp < 4; jp += 2) {
-          auto sx = __builtin_amdgcn_permlane16_swap(pk[jp].x, pk[jp + 1].x, false, false);
-          auto sy = __builtin_amdgcn_permlane16_swap(pk[jp].y, pk[jp + 1].y, false, false);
-          // even row: {own group jp, partner's group jp}; odd row: {partner's group jp+1, own group jp+1}
-          const uint4 w = make_uint4(sx[0], sy[0], sx[1], sy[1]);
-          const int jj = odd ? jp + 1 : jp;
-          if (row_ok) *(uint4*)((bf16_t*)e.out_t + rowoff[ii] + coloff[jj] - (odd ? 4 : 0)) = w;
         }
       }
     }
   }
 }
-
-// epilogue variants actually used by the encoder / cross-KV schedules; anything else takes the v2 kernel
-static int v3_epi_code(const GemmEpi& e) {
-  return (e.act == 1 ? 1 : 0) | (e.residual ? 2 : 0) | (e.rowtab ? 4 : 0) | (e.headsplit ? 8 : 0) | (e.out_f32 ? 16 : 0);
-}
-bool gemm_bf16_v3_ok(const GemmArgs& g) {
-  const int code = v3_epi_code(g.epi);
-  const bool known = code == 0 || code == 1 || code == 18 || code == 21 || code == 8;
-  const bool one_out = (g.epi.out_f32 != nullptr) != (g.epi.out_t != nullptr);
-  return known && one_out && g.N % 256 == 0 && g.K % 32 == 0 && g.K >= 128 && g.lda % 8 == 0 && g.ldw % 8 == 0 &&
-         g.epi.ldc % 8 == 0 && ((uintptr_t)g.A % 16) == 0 && ((uintptr_t)g.W % 16) == 0 &&
-         (!g.epi.headsplit || g.epi.hs_d % 64 == 0);
-}
-template <typename T16, int EPI>
-static void launch_v3(const GemmArgs& g, hipStream_t s) {
-  const int tiles_m = (g.M + 255) / 256, tiles_n = g.N / 256;
-  if (g_kernel_sig_on) snprintf(g_kernel_sig, sizeof g_kernel_sig, "gemm_bf16_v3_kernel<%s, %d> grid %d", sig_type<T16>(), EPI,
-                                tiles_m * tiles_n * g.batch * 512);
-  hipLaunchKernelGGL((gemm_bf16_v3_kernel<T16, EPI>), dim3(tiles_m * tiles_n, 1, g.batch), dim3(512), 4 * 32768, s, g, tiles_m, tiles_n);
-}
-template <typename T16>
-void launch_gemm_bf16_v3(const GemmArgs& g, hipStream_t s) {
-  switch (v3_epi_code(g.epi)) {
-    case 0: launch_v3<T16, 0>(g, s); break;    // bias -> T                 (qkv)
-    case 1: launch_v3<T16, 1>(g, s); break;    // bias + GELU -> T          (fc1, conv1)
-    case 18: launch_v3<T16, 18>(g, s); break;  // bias + residual -> f32    (out-proj, fc2)
-    case 21: launch_v3<T16, 21>(g, s); break;  // bias + GELU + positions -> f32 (conv2)
-    case 8: launch_v3<T16, 8>(g, s); break;    // bias -> head-split T      (cross-KV)
-    default: break;                            // excluded by gemm_bf16_v3_ok
-  }
-}
-template void launch_gemm_bf16_v3<bf16_t>(const GemmArgs&, hipStream_t);
-template void launch_gemm_bf16_v3<f16_t>(const GemmArgs&, hipStream_t);
 
 // ------------------------------------------------------------------------------------------------
-// gemm_bf16_v4 (round 4): the v3 tile body as a PERSISTENT workgroup (one per CU) that walks its tiles, so that the part of
-// a tile that v3 leaves exposed at one workgroup per CU - the store-issue-bound epilogue, the workgroup relaunch and the
-// first stages' HBM/L2 latency - overlaps with neighbouring work:
+// gemm_bf16_persistent: the tile body as a PERSISTENT workgroup (one per CU) that walks its tiles, so that the part of a tile that
+// v3 leaves exposed at one workgroup per CU - the store-issue-bound epilogue, the workgroup relaunch and the first stages' HBM/L2
+// latency - overlaps with neighbouring work:
 //   main loop of tile i  ->  bias of tile i+1 (waited for here: nothing else is in flight)  ->  LDS-DMA of stages 0..2 of tile
 //   i+1 (the ring is free: every fragment read of tile i was drained before the last barrier)  ->  epilogue of tile i (VALU +
-//   16 x 16-byte stores per lane, no LDS, no load)  ->  main loop of tile i+1, whose first two counted waits allow the 16 stores
-//   to be still in flight (vmcnt retires in issue order: [4 pieces of stage 2][16 stores][4 pieces of stage 3] ...).
-// Stores are unconditional with the row index clamped (rows past M replicate row M-1's operands, so they write row M-1's own
-// values again): the in-flight count the first waits rely on is then exact for every wave.
+//   2 x 16-byte stores per row block and lane, no LDS, no load)  ->  main loop of tile i+1, whose first two counted waits allow
+//   those stores to be still in flight (vmcnt retires in issue order: [4 pieces of stage 2][stores][4 pieces of stage 3] ...).
 // Same arithmetic as v3 (accumulation order, bias added after the loop, same conversions): bit-identical outputs.
 // EPI 0 (bias -> T), 1 (bias + GELU -> T), 8 (bias -> head-split T); batch == 1.
+//
+// TAIL = false ("v4", round 4): tiles_m x tiles_n tiles of 256 rows per group; g.groups > 1 walks the groups' tiles as one range
+// (weights group_stride_w apart, bias N apart, outputs group_stride_out apart: the grouped cross-KV launch).
+// TAIL = true ("v5", round 5; groups == 1, gemm_bf16_v5_ok): the LAST partial round of workgroups is re-tiled.  The rows are cut
+// into a FULL region of tiles_m 256-row m-tiles whose tile count fills whole rounds of the persistent workgroups, and a TAIL region
+// of tail_tiles_m shorter tiles - tail_mi * 32 rows (tail_mi = 6 or 4 row blocks of 16 per wave group instead of 8), all 256
+// columns - chosen by v5_plan so that the tail's tile count fits ONE round: e.g. out-proj / fc2 at B = 32 (940 tiles = 3.67 rounds
+// -> 4): 765 full tiles (2.99 rounds) + 230 tiles of 192 rows (one round of ~0.78 of a tile).  Stage t + 3 is issued right after
+// the phase-A barrier; DESIGN 4.11 records the three other placements that were measured in round 5.
 // ------------------------------------------------------------------------------------------------
-template <typename T16, int EPI>
-__global__ __launch_bounds__(512, 2) void gemm_bf16_v4_kernel(GemmArgs g, int tiles_m, int tiles_n) {
-  constexpr int BM = 256, BN = 256, BK = 32;
-  constexpr int OP_BYTES = BM * BK * 2, STAGE_BYTES = 2 * OP_BYTES;
-  constexpr bool ACT = EPI & 1, HS = EPI & 8;
-  static_assert((EPI & ~9) == 0, "v4 carries the T-output epilogues only");
+template <typename T16, int EPI, bool TAIL>
+__global__ __launch_bounds__(512, 2) void gemm_bf16_persistent_kernel(GemmArgs g, int tiles_m, int tiles_n, int tail_tiles_m, int tail_mi) {
+  using namespace t256;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 2, wn = wave & 3;
+  const Lane L(smem);
+  // tile ids: [0, n_full) 256-row tiles (of all groups), n_full + [0, n_tail) tail tiles
   const int tiles_per_group = tiles_m * tiles_n;
-  const int nwg = tiles_per_group * g.groups;
-  // static schedule: the workgroups that share an XCD (bid % 8) own one contiguous range of tiles and walk it round-robin
-  const int bid = blockIdx.x, xcd = bid & 7, slot = bid >> 3, per_xcd = (gridDim.x + 7 - xcd) >> 3;  // workgroups of this class
-  const int q = nwg >> 3, r = nwg & 7;
-  const int t_begin = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q, t_end = t_begin + (xcd < r ? q + 1 : q);
-  const bf16_t* A = (const bf16_t*)g.A;
-  const bf16_t* W = (const bf16_t*)g.W;
-  const GemmEpi& e = g.epi;
-  const int srow = lane >> 2, sslot = lane & 3;
-  const int fr = lane & 15, fq = lane >> 4;
-  const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  const uint32_t frag_off = (uint32_t)(fr * 64 + ((fq ^ v3_h((fr >> 2) & 3)) << 4));
-  const uint32_t a_off = lds_base + wm * 128 * 64 + frag_off;
-  const uint32_t w_off = lds_base + OP_BYTES + wn * 64 * 64 + frag_off;
-  const int nt = g.K / BK;  // >= 4
-  constexpr int GM = 4;
-
-  int m0 = 0, n0 = 0;
-  int64_t oofs = 0;          // output offset of the tile's group (elements)
-  const float* bias_g = e.bias;
-  const bf16_t* a_src[2];
-  const bf16_t* w_src[2];
-  auto place = [&](int tile) {   // tile -> (group,) (m0, n0), staging source pointers (same raster as v3 inside a group)
-    const bf16_t* Wg = W;
-    if (g.groups > 1) {
-      const int grp = tile / tiles_per_group;
-      tile -= grp * tiles_per_group;
-      Wg = W + (int64_t)grp * g.group_stride_w;
-      bias_g = e.bias + (int64_t)grp * g.N;
-      oofs = (int64_t)grp * g.group_stride_out;
-    }
-    const int band = tile / (GM * tiles_n);
-    const int rows_in_band = min(GM, tiles_m - band * GM);
-    const int in_band = tile - band * GM * tiles_n;
-    const int tn = in_band / rows_in_band;
-    const int tm = band * GM + (in_band - tn * rows_in_band);
-    m0 = tm * BM; n0 = tn * BN;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int row = (wave * 2 + p) * 16 + srow;
-      const int chunk = sslot ^ v3_h((row >> 2) & 3);
-      a_src[p] = A + (int64_t)min(m0 + row, g.M - 1) * g.lda + chunk * 8;
-      w_src[p] = Wg + (int64_t)(n0 + row) * g.ldw + chunk * 8;
-    }
-  };
-#define V4_STAGE(slot_, k0_)                                                                   \
-  do {                                                                                         \
-    char* base_ = smem + (slot_) * STAGE_BYTES;                                                \
-    _Pragma("unroll") for (int p = 0; p < 2; ++p) {                                            \
-      glds16(a_src[p] + (k0_), base_ + (wave * 2 + p) * 1024);                                 \
-      glds16(w_src[p] + (k0_), base_ + OP_BYTES + (wave * 2 + p) * 1024);                      \
-    }                                                                                          \
-  } while (0)
-  auto load_bias = [&](float4 (&b4)[4]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) b4[j] = *(const float4*)(bias_g + n0 + wn * 64 + fq * 4 + j * 16);   // bias != nullptr (gemm_bf16_v4_ok)
-    // waited for HERE, while nothing else is in flight: no later use of these registers may drain the LDS-DMA queue
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(b4[0].x), "+v"(b4[0].y), "+v"(b4[0].z), "+v"(b4[0].w), "+v"(b4[1].x), "+v"(b4[1].y),
-                 "+v"(b4[1].z), "+v"(b4[1].w), "+v"(b4[2].x), "+v"(b4[2].y), "+v"(b4[2].z), "+v"(b4[2].w), "+v"(b4[3].x),
-                 "+v"(b4[3].y), "+v"(b4[3].z), "+v"(b4[3].w));
-  };
-
-  int tile = t_begin + slot;
-  if (tile >= t_end) return;
-  place(tile);
-  float4 bias4[4];
-  load_bias(bias4);
-  V4_STAGE(0, 0);
-  V4_STAGE(1, BK);
-  V4_STAGE(2, 2 * BK);
-  bool carry = false;   // 16 stores of the previous tile's epilogue sit behind the three prefetched stages
-
-  for (;;) {
-    f32x4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // stages 0 and 1 landed (own pieces); queue behind them: stage 2 (4) [+ 16 stores]
-    if (carry) asm volatile("s_waitcnt vmcnt(20)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    if (wm == 1) __builtin_amdgcn_s_barrier();  // stagger: group 1 runs one barrier behind
-    for (int t = 0; t < nt; ++t) {
-      // ---- phase A ----
-      if (t + 2 < nt) {
-        // own pieces of stage t + 1 landed; queue behind them: stage t + 2 (4), and for t < 2 of a carried tile the 16 stores
-        // (t = 0: [stage 2][stores]; t = 1: [stores][stage 3] - from t = 2 on the stores are older than what is waited for)
-        if (carry && t < 2) asm volatile("s_waitcnt vmcnt(20)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      if (t + 3 < nt) V4_STAGE((t + 3) & 3, (t + 3) * BK);
-      s16x8 a[8], b[4];
-      const uint32_t so = (uint32_t)((t & 3) * STAGE_BYTES);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) asm volatile("ds_read_b128 %0, %1" : "=v"(b[j]) : "v"(w_off + so + j * 16 * 64));
-#pragma unroll
-      for (int i = 0; i < 8; ++i) asm volatile("ds_read_b128 %0, %1" : "=v"(a[i]) : "v"(a_off + so + i * 16 * 64));
-      asm volatile("s_waitcnt lgkmcnt(0)"
-                   : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]),
-                     "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]));
-      __builtin_amdgcn_sched_barrier(0);
-      // ---- phase B ----
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = N16<T16>::mfma16(b[j], a[i], acc[i][j]);
-      __builtin_amdgcn_s_setprio(0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (wm == 0) __builtin_amdgcn_s_barrier();  // balance the barrier count: every fragment read of this tile is drained
-    // ---- this tile's output coordinates (before the staging pointers move on) ----
-    const int nbase = n0 + wn * 64 + fq * 4;
-    int64_t coloff[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = nbase + j * 16;
-      if (HS) {
-        const int which = n / e.hs_d, nn = n - which * e.hs_d;
-        coloff[j] = oofs + (int64_t)which * e.hs_which + (int64_t)(nn >> 6) * e.hs_T * 64 + (nn & 63);
-      } else coloff[j] = oofs + n;
-    }
-    const int mrow0 = m0 + wm * 128 + fr;
-    // ---- next tile: bias (waited for now), then its first three stages into the free ring ----
-    const int next = tile + per_xcd;
-    const bool has_next = next < t_end;
-    float4 bias_next[4];
-    if (has_next) {
-      place(next);
-      load_bias(bias_next);
-      V4_STAGE(0, 0);
-      V4_STAGE(1, BK);
-      V4_STAGE(2, 2 * BK);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    // ---- epilogue of this tile: VALU + 16 unconditional 16-byte stores per lane ----
-    const bool odd = (fq & 1) != 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int m = min(mrow0 + i * 16, g.M - 1);
-      int64_t rowoff;
-      if (HS) {
-        const int bb = m / e.hs_T, tt = m - bb * e.hs_T;
-        rowoff = ((int64_t)bb * e.hs_H * e.hs_T + tt) * 64;
-      } else rowoff = (int64_t)m * e.ldc;
-      uint2 pk[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        f32x4 v = acc[i][j];
-        v[0] += bias4[j].x; v[1] += bias4[j].y; v[2] += bias4[j].z; v[3] += bias4[j].w;
-        if (ACT) {
-#pragma unroll
-          for (int t = 0; t < 4; ++t) v[t] = gelu_fast(v[t]);
-        }
-        pk[j].x = N16<T16>::pk(v[0], v[1]);
-        pk[j].y = N16<T16>::pk(v[2], v[3]);
-      }
-#pragma unroll
-      for (int jp = 0; jp < 4; jp += 2) {
-        auto sx = __builtin_amdgcn_permlane16_swap(pk[jp].x, pk[jp + 1].x, false, false);
-        auto sy = __builtin_amdgcn_permlane16_swap(pk[jp].y, pk[jp + 1].y, false, false);
-        const uint4 w = make_uint4(sx[0], sy[0], sx[1], sy[1]);
-        const int jj = odd ? jp + 1 : jp;
-        *(uint4*)((bf16_t*)e.out_t + rowoff + coloff[jj] - (odd ? 4 : 0)) = w;
-      }
-    }
-    if (!has_next) break;
-    tile = next;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) bias4[j] = bias_next[j];
-    carry = true;
-  }
-#undef V4_STAGE
-}
-
-// ------------------------------------------------------------------------------------------------
-// gemm_bf16_v5 (round 5): v4 whose LAST partial round of workgroups is re-tiled ("give the surplus tiles to
-// ALL CUs by splitting them along M ... no f32 partials").  The rows are cut into a FULL region of 256-row m-tiles whose tile count
-// fills whole rounds of the 256 persistent workgroups, and a TAIL region of shorter tiles - 192 or 128 rows (6 or 4 row blocks
-// of 16 per wave group instead of 8), all 256 columns - chosen so that the tail's tile count fits ONE round: e.g. out-proj / fc2 at
-// B = 32 (940 tiles = 3.67 rounds -> 4): 765 full tiles (2.99 rounds) + 230 tiles of 192 rows (one round of ~0.78 of a tile).
-// A shorter tile is the same tile body with fewer row blocks (template MI): the A image is still staged 256 rows deep (the extra
-// rows are the next tile's, read only), every output element sees the same K loop in the same order: bit-identical to v3 / v4.
-// ------------------------------------------------------------------------------------------------
-template <typename T16, int EPI>
-__global__ __launch_bounds__(512, 2) void gemm_bf16_v5_kernel(GemmArgs g, int tiles_m, int tiles_n, int tail_tiles_m, int tail_mi) {
-  constexpr int BM = 256, BN = 256, BK = 32;
-  constexpr int OP_BYTES = BM * BK * 2, STAGE_BYTES = 2 * OP_BYTES;
-  constexpr bool ACT = EPI & 1, HS = EPI & 8;
-  static_assert((EPI & ~9) == 0, "v4 carries the T-output epilogues only");
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 2, wn = wave & 3;
-  // tiles_m = 256-row m-tiles of the FULL region; the rows behind it are the TAIL region: tail_tiles_m m-tiles of tail_mi * 32 rows
-  // (tail_mi = row blocks of 16 per wave group: 6 -> 192-row tiles, 4 -> 128-row tiles).  groups == 1 (gemm_bf16_v5_ok).
-  const int n_full = tiles_m * tiles_n, n_tail = tail_tiles_m * tiles_n;
+  const int n_full = TAIL ? tiles_per_group : tiles_per_group * g.groups, n_tail = TAIL ? tail_tiles_m * tiles_n : 0;
   // static schedule: the workgroups that share an XCD (bid % 8) own one contiguous chunk of the full tiles and one of the tail
   // tiles; a workgroup walks its full tiles round-robin (slot, slot + per_xcd, ...), then its tail tiles from the OTHER end of
   // the slot order (the workgroups that got one full tile less take the tail tiles first)
   const int bid = blockIdx.x, xcd = bid & 7, slot = bid >> 3, per_xcd = (gridDim.x + 7 - xcd) >> 3;  // workgroups of this class
-  auto chunk = [&](int n, int& lo, int& hi) { const int q = n >> 3, r = n & 7; lo = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q; hi = lo + (xcd < r ? q + 1 : q); };
-  int fb, fe, tb, te;
-  chunk(n_full, fb, fe);
-  chunk(n_tail, tb, te);
-  // tile ids: [0, n_full) full tiles, n_full + [0, n_tail) tail tiles
-  auto first_tail = [&]() { const int t = tb + (per_xcd - 1 - slot); return t < te ? n_full + t : -1; };
-  auto next_of = [&](int id) {
+  int fb, fe, tb = 0, te = 0;
+  xcd_chunk(n_full, xcd, fb, fe);
+  if (TAIL) xcd_chunk(n_tail, xcd, tb, te);
+  auto first_tail = [&]() { const int t = tb + (per_xcd - 1 - slot); return TAIL && t < te ? n_full + t : -1; };
+  auto next_of = [&](int id) {   // -1: that was the workgroup's last tile
     const int nx = id + per_xcd;
-    if (id < n_full) return nx < fe ? nx : first_tail();
+    if (!TAIL || id < n_full) return nx < fe ? nx : first_tail();
     return nx - n_full < te ? nx : -1;
   };
-  const bf16_t* A = (const bf16_t*)g.A;
-  const bf16_t* W = (const bf16_t*)g.W;
   const GemmEpi& e = g.epi;
-  const int srow = lane >> 2, sslot = lane & 3;
-  const int fr = lane & 15, fq = lane >> 4;
-  const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  const uint32_t frag_off = (uint32_t)(fr * 64 + ((fq ^ v3_h((fr >> 2) & 3)) << 4));
-  const uint32_t w_off = lds_base + OP_BYTES + wn * 64 * 64 + frag_off;
   const int nt = g.K / BK;  // >= 4
-  constexpr int GM = 4;
 
   int m0 = 0, n0 = 0;
-  const float* bias_g = e.bias;
-  const bf16_t* a_src[2];
-  const bf16_t* w_src[2];
+  int64_t oofs = 0;          // output offset of the tile's group (elements)
+  const float* bias_g = e.bias;   // != nullptr (gemm_bf16_v4_ok)
   int mi_placed = 8;         // row blocks per wave group of the tile place() was last called for
-  auto place = [&](int tile) {   // tile id -> (m0, n0), staging source pointers (the v3 raster inside each region)
+  Stager st;
+  auto place = [&](int tile) {   // tile id -> (group,) (m0, n0), staging source pointers
+    const bf16_t* W = (const bf16_t*)g.W;
     int tm_n = tiles_m, base_row = 0, rows_per_tile = BM;
     mi_placed = 8;
-    if (tile >= n_full) { tile -= n_full; tm_n = tail_tiles_m; base_row = tiles_m * BM; rows_per_tile = tail_mi * 32; mi_placed = tail_mi; }
-    const int band = tile / (GM * tiles_n);
-    const int rows_in_band = min(GM, tm_n - band * GM);
-    const int in_band = tile - band * GM * tiles_n;
-    const int tn = in_band / rows_in_band;
-    const int tm = band * GM + (in_band - tn * rows_in_band);
-    m0 = base_row + tm * rows_per_tile; n0 = tn * BN;
+    if (TAIL) {
+      if (tile >= n_full) { tile -= n_full; tm_n = tail_tiles_m; base_row = tiles_m * BM; rows_per_tile = tail_mi * 32; mi_placed = tail_mi; }
+    } else if (g.groups > 1) {
+      const int grp = tile / tiles_per_group;
+      tile -= grp * tiles_per_group;
+      W += (int64_t)grp * g.group_stride_w;
+      bias_g = e.bias + (int64_t)grp * g.N;
+      oofs = (int64_t)grp * g.group_stride_out;
+    }
+    raster(tile, tm_n, tiles_n, base_row, rows_per_tile, m0, n0);
     // every wave stages its 2 + 2 pieces for EVERY tile (the counted waits rely on it), but the A pieces of a short tile that lie
     // past its last row re-read that one row (one cache line per piece instead of sixteen): a short tile does not pay for A rows
     // it does not use - what fc2, whose 492 MB A operand streams from beyond L2, needs to gain anything
-    const int row_lim = min(g.M - 1, m0 + rows_per_tile - 1);
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int row = (wave * 2 + p) * 16 + srow;
-      const int chunk = sslot ^ v3_h((row >> 2) & 3);
-      a_src[p] = A + (int64_t)min(m0 + row, row_lim) * g.lda + chunk * 8;
-      w_src[p] = W + (int64_t)(n0 + row) * g.ldw + chunk * 8;
-    }
-  };
-#define V4_STAGE(slot_, k0_)                                                                   \
-  do {                                                                                         \
-    char* base_ = smem + (slot_) * STAGE_BYTES;                                                \
-    _Pragma("unroll") for (int p = 0; p < 2; ++p) {                                            \
-      glds16(a_src[p] + (k0_), base_ + (wave * 2 + p) * 1024);                                 \
-      glds16(w_src[p] + (k0_), base_ + OP_BYTES + (wave * 2 + p) * 1024);                      \
-    }                                                                                          \
-  } while (0)
-  auto load_bias = [&](float4 (&b4)[4]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) b4[j] = *(const float4*)(bias_g + n0 + wn * 64 + fq * 4 + j * 16);   // bias != nullptr (gemm_bf16_v4_ok)
-    // waited for HERE, while nothing else is in flight: no later use of these registers may drain the LDS-DMA queue
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(b4[0].x), "+v"(b4[0].y), "+v"(b4[0].z), "+v"(b4[0].w), "+v"(b4[1].x), "+v"(b4[1].y),
-                 "+v"(b4[1].z), "+v"(b4[1].w), "+v"(b4[2].x), "+v"(b4[2].y), "+v"(b4[2].z), "+v"(b4[2].w), "+v"(b4[3].x),
-                 "+v"(b4[3].y), "+v"(b4[3].z), "+v"(b4[3].w));
+    const int row_lim = TAIL ? min(g.M - 1, m0 + rows_per_tile - 1) : g.M - 1;
+    st.point(L, (const bf16_t*)g.A, g.lda, m0, row_lim, W, g.ldw, n0);
   };
 
   int tile = fb + slot < fe ? fb + slot : first_tail();
   if (tile < 0) return;
   place(tile);
   float4 bias4[4];
-  load_bias(bias4);
-  V4_STAGE(0, 0);
-  V4_STAGE(1, BK);
-  V4_STAGE(2, 2 * BK);
-  int carry = 0;   // stores of the previous tile's epilogue (2 per row block) that sit behind the three prefetched stages
-  // "own pieces of the wanted stage landed": everything but the 4 youngest pieces and the carried stores (issue order)
-#define V5_WAIT_CARRY()                                                          \
-  do {                                                                           \
-    if (carry == 16) asm volatile("s_waitcnt vmcnt(20)" ::: "memory");           \
-    else if (carry == 12) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");      \
-    else if (carry == 8) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");       \
-    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                        \
-  } while (0)
+  load_bias(bias_g + L.nbase(n0), bias4);
+  st.prologue(L);
+  int carried = 0;   // stores of the previous tile's epilogue (2 per row block) that sit behind the three prefetched stages
 
-  // one tile of MI row blocks per wave group (MI = 8: the 256 x 256 tile of v4; 6 / 4: the shorter tiles of the tail region);
-  // returns false after the workgroup's last tile
+  // one tile of MI row blocks per wave group (8: the 256 x 256 tile; 6 / 4: the shorter tiles of the tail region); false after
+  // the workgroup's last tile
   auto run_tile = [&](auto mi_tag) -> bool {
     constexpr int MI = decltype(mi_tag)::value;
-    const uint32_t a_off = lds_base + wm * (MI * 16) * 64 + frag_off;
     f32x4 acc[MI][4];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // stages 0 and 1 landed (own pieces); queue behind them: stage 2 (4) [+ the carried stores]
-    V5_WAIT_CARRY();
-    if (wm == 1) __builtin_amdgcn_s_barrier();  // stagger: group 1 runs one barrier behind
-    for (int t = 0; t < nt; ++t) {
-      // ---- phase A ----
-      if (t + 2 < nt) {
-        // own pieces of stage t + 1 landed; queue behind them: stage t + 2 (4), and for t < 2 of a carried tile its stores
-        // (t = 0: [stage 2][stores]; t = 1: [stores][stage 3] - from t = 2 on the stores are older than what is waited for)
-        if (t < 2) V5_WAIT_CARRY(); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-#if TTASR_V5_DMA == 0
-      if (t + 3 < nt) V4_STAGE((t + 3) & 3, (t + 3) * BK);
-#elif TTASR_V5_DMA == 2
-      if (t + 3 < nt) { char* base_ = smem + ((t + 3) & 3) * STAGE_BYTES;
-        _Pragma("unroll") for (int p = 0; p < 2; ++p) glds16(a_src[p] + (t + 3) * BK, base_ + (wave * 2 + p) * 1024); }
-#endif
-      s16x8 a[MI], b[4];
-      const uint32_t so = (uint32_t)((t & 3) * STAGE_BYTES);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) asm volatile("ds_read_b128 %0, %1" : "=v"(b[j]) : "v"(w_off + so + j * 16 * 64));
-#pragma unroll
-      for (int i = 0; i < MI; ++i) asm volatile("ds_read_b128 %0, %1" : "=v"(a[i]) : "v"(a_off + so + i * 16 * 64));
-      if constexpr (MI == 8)
-        asm volatile("s_waitcnt lgkmcnt(0)"
-                     : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]),
-                       "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]));
-      else if constexpr (MI == 6)
-        asm volatile("s_waitcnt lgkmcnt(0)"
-                     : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]));
-      else
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]));
-      __builtin_amdgcn_sched_barrier(0);
-      // ---- phase B ----
-      __builtin_amdgcn_s_barrier();
-#if TTASR_V5_DMA == 3
-      if (t + 3 < nt) V4_STAGE((t + 3) & 3, (t + 3) * BK);
-      __builtin_amdgcn_sched_barrier(0);
-#endif
-      __builtin_amdgcn_s_setprio(1);
-#if TTASR_V5_DMA == 0 || TTASR_V5_DMA == 3
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = N16<T16>::mfma16(b[j], a[i], acc[i][j]);
-#else
-#pragma unroll
-      for (int i = 0; i < MI / 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = N16<T16>::mfma16(b[j], a[i], acc[i][j]);
-      __builtin_amdgcn_sched_barrier(0);
-#if TTASR_V5_DMA == 1
-      if (t + 3 < nt) V4_STAGE((t + 3) & 3, (t + 3) * BK);
-#else
-      if (t + 3 < nt) { char* base_ = smem + ((t + 3) & 3) * STAGE_BYTES;
-        _Pragma("unroll") for (int p = 0; p < 2; ++p) glds16(w_src[p] + (t + 3) * BK, base_ + OP_BYTES + (wave * 2 + p) * 1024); }
-#endif
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = MI / 2; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = N16<T16>::mfma16(b[j], a[i], acc[i][j]);
-#endif
-      __builtin_amdgcn_s_setprio(0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (wm == 0) __builtin_amdgcn_s_barrier();  // balance the barrier count: every fragment read of this tile is drained
+    mainloop<T16, MI, TAIL>(acc, L, st, L.a_off(MI), L.w_off(), nt, carried);
     // ---- this tile's output coordinates (before the staging pointers move on) ----
-    const int nbase = n0 + wn * 64 + fq * 4;
     int64_t coloff[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = nbase + j * 16;
-      if (HS) {
-        const int which = n / e.hs_d, nn = n - which * e.hs_d;
-        coloff[j] = (int64_t)which * e.hs_which + (int64_t)(nn >> 6) * e.hs_T * 64 + (nn & 63);
-      } else coloff[j] = n;
-    }
-    const int mrow0 = m0 + wm * (MI * 16) + fr;
+    out_cols<(EPI & 8) != 0>(e, L.nbase(n0), oofs, coloff);
+    const int mrow0 = m0 + L.wm * (MI * 16) + L.fr;
     // ---- next tile: bias (waited for now), then its first three stages into the free ring ----
     const int next = next_of(tile);
-    const bool has_next = next >= 0;
     float4 bias_next[4];
-    if (has_next) {
+    if (next >= 0) {
       place(next);
-      load_bias(bias_next);
-      V4_STAGE(0, 0);
-      V4_STAGE(1, BK);
-      V4_STAGE(2, 2 * BK);
+      load_bias(bias_g + L.nbase(n0), bias_next);
+      st.prologue(L);
     }
     __builtin_amdgcn_sched_barrier(0);
     // ---- epilogue of this tile: VALU + 2 unconditional 16-byte stores per row block and lane ----
-    const bool odd = (fq & 1) != 0;
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-      const int m = min(mrow0 + i * 16, g.M - 1);
-      int64_t rowoff;
-      if (HS) {
-        const int bb = m / e.hs_T, tt = m - bb * e.hs_T;
-        rowoff = ((int64_t)bb * e.hs_H * e.hs_T + tt) * 64;
-      } else rowoff = (int64_t)m * e.ldc;
-      uint2 pk[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        f32x4 v = acc[i][j];
-        v[0] += bias4[j].x; v[1] += bias4[j].y; v[2] += bias4[j].z; v[3] += bias4[j].w;
-        if (ACT) {
-#pragma unroll
-          for (int t = 0; t < 4; ++t) v[t] = gelu_fast(v[t]);
-        }
-        pk[j].x = N16<T16>::pk(v[0], v[1]);
-        pk[j].y = N16<T16>::pk(v[2], v[3]);
-      }
-#pragma unroll
-      for (int jp = 0; jp < 4; jp += 2) {
-        auto sx = __builtin_amdgcn_permlane16_swap(pk[jp].x, pk[jp + 1].x, false, false);
-        auto sy = __builtin_amdgcn_permlane16_swap(pk[jp].y, pk[jp + 1].y, false, false);
-        const uint4 w = make_uint4(sx[0], sy[0], sx[1], sy[1]);
-        const int jj = odd ? jp + 1 : jp;
-        *(uint4*)((bf16_t*)e.out_t + rowoff + coloff[jj] - (odd ? 4 : 0)) = w;
-      }
-    }
-    if (!has_next) return false;
+    store_tile_t<T16, MI, EPI, false>(acc, bias4, e, g.M, 0, mrow0, coloff, L);
+    if (next < 0) return false;
     tile = next;
 #pragma unroll
     for (int j = 0; j < 4; ++j) bias4[j] = bias_next[j];
-    carry = 2 * MI;
+    carried = 2 * MI;
     return true;
   };
-  int mi_cur = mi_placed;
-  for (;;) {
+  for (;;) {   // mi_placed: place(next) ran inside run_tile
     bool more;
-    if (mi_cur == 8) more = run_tile(std::integral_constant<int, 8>{});
-    else if (mi_cur == 6) more = run_tile(std::integral_constant<int, 6>{});
+    if (!TAIL || mi_placed == 8) more = run_tile(std::integral_constant<int, 8>{});
+    else if (mi_placed == 6) more = run_tile(std::integral_constant<int, 6>{});
     else more = run_tile(std::integral_constant<int, 4>{});
     if (!more) break;
-    mi_cur = mi_placed;   // place(next) ran inside run_tile
   }
-#undef V5_WAIT_CARRY
-#undef V4_STAGE
 }
 
-bool gemm_bf16_v4_ok(const GemmArgs& g) {
-  const int code = v3_epi_code(g.epi);
-  return (code == 0 || code == 1 || code == 8) && g.batch <= 1 && g.groups >= 1 && g.epi.bias != nullptr && gemm_bf16_v3_ok(g);
+// ---- host side of the tiled kernels ----
+// epilogue variants actually used by the encoder / cross-KV schedules; anything else takes the v2 kernel
+static int v3_epi_code(const GemmEpi& e) {
+  return (e.act == 1 ? 1 : 0) | (e.residual ? 2 : 0) | (e.rowtab ? 4 : 0) | (e.headsplit ? 8 : 0) | (e.out_f32 ? 16 : 0);
 }
+// THE list of EPI instantiations: calls f(std::integral_constant<int, EPI>) for a v3_epi_code the tiled kernels are built for
+// (T_ONLY: the T-output ones, which is what the persistent kernel carries); false for any other code.
+template <bool T_ONLY, typename F>
+static bool with_epi(int code, F&& f) {
+  switch (code) {
+    case 0: f(std::integral_constant<int, 0>{}); return true;    // bias -> T                 (qkv)
+    case 1: f(std::integral_constant<int, 1>{}); return true;    // bias + GELU -> T          (fc1, conv1)
+    case 8: f(std::integral_constant<int, 8>{}); return true;    // bias -> head-split T      (cross-KV)
+    case 18: if constexpr (!T_ONLY) { f(std::integral_constant<int, 18>{}); return true; } return false;  // bias + residual -> f32 (out-proj, fc2)
+    case 21: if constexpr (!T_ONLY) { f(std::integral_constant<int, 21>{}); return true; } return false;  // bias + GELU + positions -> f32 (conv2)
+    default: return false;
+  }
+}
+static bool epi_known(int code, bool t_only) { return t_only ? with_epi<true>(code, [](auto) {}) : with_epi<false>(code, [](auto) {}); }
+
+bool gemm_bf16_v3_ok(const GemmArgs& g) {
+  const bool one_out = (g.epi.out_f32 != nullptr) != (g.epi.out_t != nullptr);
+  return epi_known(v3_epi_code(g.epi), false) && one_out && g.N % 256 == 0 && g.K % 32 == 0 && g.K >= 128 && g.lda % 8 == 0 &&
+         g.ldw % 8 == 0 && g.epi.ldc % 8 == 0 && ((uintptr_t)g.A % 16) == 0 && ((uintptr_t)g.W % 16) == 0 &&
+         (!g.epi.headsplit || g.epi.hs_d % 64 == 0);
+}
+bool gemm_bf16_v4_ok(const GemmArgs& g) {
+  return epi_known(v3_epi_code(g.epi), true) && g.batch <= 1 && g.groups >= 1 && g.epi.bias != nullptr && gemm_bf16_v3_ok(g);
+}
+bool gemm_bf16_v5_ok(const GemmArgs& g) { return g.groups <= 1 && gemm_bf16_v4_ok(g); }
+
 // Per-device launcher state, set ONCE per device by gemm_tiles_init (ttasr_create calls it before the context can launch
 // anything; std::call_once orders the writes before every later reader): the opt-in to > 64 KiB of dynamic LDS for every tiled
 // instantiation and the CU count that sizes the persistent grid.  Nothing is set lazily from a launcher any more (VERDICT
@@ -1117,16 +875,15 @@ static int g_v4_cus[64] = {0};
 static std::once_flag g_tiles_once[64];
 template <typename T16>
 static void tiles_attrs() {
-  hipFuncSetAttribute((const void*)gemm_bf16_v2_kernel<T16>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 49152);
-#define TTASR_V3_ATTR(E_) hipFuncSetAttribute((const void*)gemm_bf16_v3_kernel<T16, E_>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 32768)
-#define TTASR_V4_ATTR(E_) hipFuncSetAttribute((const void*)gemm_bf16_v4_kernel<T16, E_>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 32768)
-  TTASR_V3_ATTR(0); TTASR_V3_ATTR(1); TTASR_V3_ATTR(18); TTASR_V3_ATTR(21); TTASR_V3_ATTR(8);
-  TTASR_V4_ATTR(0); TTASR_V4_ATTR(1); TTASR_V4_ATTR(8);
-#define TTASR_V5_ATTR(E_) hipFuncSetAttribute((const void*)gemm_bf16_v5_kernel<T16, E_>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 32768)
-  TTASR_V5_ATTR(0); TTASR_V5_ATTR(1); TTASR_V5_ATTR(8);
-#undef TTASR_V5_ATTR
-#undef TTASR_V3_ATTR
-#undef TTASR_V4_ATTR
+  auto opt_in = [](const void* kernel, int bytes) { hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); };
+  opt_in((const void*)gemm_bf16_v2_kernel<T16>, 3 * 49152);
+  for (int code = 0; code < 32; ++code) {   // every instantiation with_epi knows
+    with_epi<false>(code, [&](auto epi) { opt_in((const void*)gemm_bf16_v3_kernel<T16, decltype(epi)::value>, t256::LDS_BYTES); });
+    with_epi<true>(code, [&](auto epi) {
+      opt_in((const void*)gemm_bf16_persistent_kernel<T16, decltype(epi)::value, false>, t256::LDS_BYTES);
+      opt_in((const void*)gemm_bf16_persistent_kernel<T16, decltype(epi)::value, true>, t256::LDS_BYTES);
+    });
+  }
 }
 void gemm_tiles_init(int device) {
   std::call_once(g_tiles_once[device & 63], [device]() {
@@ -1136,23 +893,40 @@ void gemm_tiles_init(int device) {
     tiles_attrs<f16_t>();
   });
 }
-template <typename T16, int EPI>
-static void launch_v4(const GemmArgs& g, hipStream_t s) {
+static int tiles_cus() {
   int dev = 0;
   hipGetDevice(&dev);
-  const int tiles_m = (g.M + 255) / 256, tiles_n = g.N / 256;   // per group
-  const int grid = std::min(tiles_m * tiles_n * std::max(1, g.groups), g_v4_cus[dev & 63]);
-  if (g_kernel_sig_on) snprintf(g_kernel_sig, sizeof g_kernel_sig, "gemm_bf16_v4_kernel<%s, %d> grid %d", sig_type<T16>(), EPI, grid * 512);
-  hipLaunchKernelGGL((gemm_bf16_v4_kernel<T16, EPI>), dim3(grid), dim3(512), 4 * 32768, s, g, tiles_m, tiles_n);
+  return g_v4_cus[dev & 63];
+}
+
+template <typename T16>
+void launch_gemm_bf16_v3(const GemmArgs& g, hipStream_t s) {
+  const int tiles_m = (g.M + 255) / 256, tiles_n = g.N / 256;
+  with_epi<false>(v3_epi_code(g.epi), [&](auto epi) {   // any other code is excluded by gemm_bf16_v3_ok
+    constexpr int EPI = decltype(epi)::value;
+    if (g_kernel_sig_on) snprintf(g_kernel_sig, sizeof g_kernel_sig, "gemm_bf16_v3_kernel<%s, %d> grid %d", sig_type<T16>(), EPI,
+                                  tiles_m * tiles_n * g.batch * 512);
+    hipLaunchKernelGGL((gemm_bf16_v3_kernel<T16, EPI>), dim3(tiles_m * tiles_n, 1, g.batch), dim3(512), t256::LDS_BYTES, s, g, tiles_m, tiles_n);
+  });
+}
+template void launch_gemm_bf16_v3<bf16_t>(const GemmArgs&, hipStream_t);
+template void launch_gemm_bf16_v3<f16_t>(const GemmArgs&, hipStream_t);
+
+// the recorded signature keeps the names the two forms had as separate kernels (profiles and tests match on them)
+template <typename T16, bool TAIL>
+static void launch_persistent(const GemmArgs& g, int tiles, int cus, int full_m, int tiles_n, int tail_m, int tail_mi, hipStream_t s) {
+  const int grid = std::min(tiles, cus);
+  with_epi<true>(v3_epi_code(g.epi), [&](auto epi) {   // any other code is excluded by gemm_bf16_v4_ok
+    constexpr int EPI = decltype(epi)::value;
+    if (g_kernel_sig_on) snprintf(g_kernel_sig, sizeof g_kernel_sig, "gemm_bf16_%s_kernel<%s, %d> grid %d", TAIL ? "v5" : "v4", sig_type<T16>(),
+                                  EPI, grid * 512);
+    hipLaunchKernelGGL((gemm_bf16_persistent_kernel<T16, EPI, TAIL>), dim3(grid), dim3(512), t256::LDS_BYTES, s, g, full_m, tiles_n, tail_m, tail_mi);
+  });
 }
 template <typename T16>
 void launch_gemm_bf16_v4(const GemmArgs& g, hipStream_t s) {
-  switch (v3_epi_code(g.epi)) {
-    case 0: launch_v4<T16, 0>(g, s); break;
-    case 1: launch_v4<T16, 1>(g, s); break;
-    case 8: launch_v4<T16, 8>(g, s); break;
-    default: break;
-  }
+  const int tiles_m = (g.M + 255) / 256, tiles_n = g.N / 256;   // per group
+  launch_persistent<T16, false>(g, tiles_m * tiles_n * std::max(1, g.groups), tiles_cus(), tiles_m, tiles_n, 0, 0, s);
 }
 template void launch_gemm_bf16_v4<bf16_t>(const GemmArgs&, hipStream_t);
 template void launch_gemm_bf16_v4<f16_t>(const GemmArgs&, hipStream_t);
@@ -1181,28 +955,13 @@ static bool v5_plan(int M, int tiles_n, int cus, V5Plan& plan) {
   }
   return found;
 }
-bool gemm_bf16_v5_ok(const GemmArgs& g) { return g.groups <= 1 && gemm_bf16_v4_ok(g); }
-template <typename T16, int EPI>
-static void launch_v5(const GemmArgs& g, const V5Plan& p, int cus, hipStream_t s) {
-  const int tiles_n = g.N / 256;
-  const int grid = std::min((p.full_m + p.tail_m) * tiles_n, cus);
-  if (g_kernel_sig_on) snprintf(g_kernel_sig, sizeof g_kernel_sig, "gemm_bf16_v5_kernel<%s, %d> grid %d", sig_type<T16>(), EPI, grid * 512);
-  hipLaunchKernelGGL((gemm_bf16_v5_kernel<T16, EPI>), dim3(grid), dim3(512), 4 * 32768, s, g, p.full_m, tiles_n, p.tail_m, p.tail_mi);
-}
 // false: no plan beats the plain tiling for this shape (the caller launches v4)
 template <typename T16>
 bool launch_gemm_bf16_v5(const GemmArgs& g, hipStream_t s) {
-  int dev = 0;
-  hipGetDevice(&dev);
-  const int cus = g_v4_cus[dev & 63];
+  const int cus = tiles_cus(), tiles_n = g.N / 256;
   V5Plan p;
-  if (!gemm_bf16_v5_ok(g) || !v5_plan(g.M, g.N / 256, cus, p)) return false;
-  switch (v3_epi_code(g.epi)) {
-    case 0: launch_v5<T16, 0>(g, p, cus, s); break;
-    case 1: launch_v5<T16, 1>(g, p, cus, s); break;
-    case 8: launch_v5<T16, 8>(g, p, cus, s); break;
-    default: return false;
-  }
+  if (!gemm_bf16_v5_ok(g) || !v5_plan(g.M, tiles_n, cus, p)) return false;
+  launch_persistent<T16, true>(g, (p.full_m + p.tail_m) * tiles_n, cus, p.full_m, tiles_n, p.tail_m, p.tail_mi, s);
   return true;
 }
 template bool launch_gemm_bf16_v5<bf16_t>(const GemmArgs&, hipStream_t);
