@@ -310,6 +310,23 @@ TTASR_API int ttasr_session_end(ttasr_ctx* ctx);
  * Invalidates any step-level decode state (it reuses row 0's self-attention pages). */
 TTASR_API int ttasr_align(ttasr_ctx* ctx, int32_t clip, const int32_t* tokens_host, int32_t n_tokens, const int32_t* pairs_host,
                 int32_t n_pairs, float* out_weights_host, float* out_logprob_host);
+/* ---- language identification (faster-whisper detect_language / transcribe(language=None): info.language,
+ * info.language_probability, all_language_probs) ------------------------------------------------------------------------ */
+/* Detects the language of the B clips whose encoder state is resident (log_mel -> encode -> detect -> generate: no second
+ * encoder pass).  One decoder pass of B rows at position 0 with the token `sot` - the attention and GEMM kernels a
+ * ttasr_decode_step of B rows at position 0 takes, under every option - that ends in the language head instead of the
+ * vocabulary projection: the dot products of each row's final LayerNorm output with the rows [lang_begin, lang_begin + n_lang)
+ * of the tied embedding (f32 accumulation), their softmax and its first maximum, on the device.  Bit-reproducible, and a
+ * clip's results do not depend on the other clips of the call.
+ *   out_lang_host    int32 [B]            index into the span (language token = lang_begin + index)
+ *   out_probs_host   optional float32 [B][n_lang]   softmax over the span
+ *   out_logits_host  optional float32 [B][n_lang]   the raw span logits (tests)
+ * Checked before anything is enqueued, TTASR_E_INVALID, the context stays usable: out_lang_host NULL; no resident encoder state;
+ * B outside [1, clips of the encoder state]; sot outside the vocabulary; n_lang outside [1, 128]; a span past the vocabulary;
+ * an open session.  Like ttasr_align the call invalidates any step-level decode state (row i uses position 0 of row i's
+ * self-attention pages); a following ttasr_generate* is bit-identical to one without the detection in between. */
+TTASR_API int ttasr_detect_language(ttasr_ctx* ctx, int32_t B, int32_t sot, int32_t lang_begin, int32_t n_lang,
+                                    int32_t* out_lang_host, float* out_probs_host, float* out_logits_host);
 /* The same alignment for n sequences in ONE pass, with the host part of the algorithm on the device as well.  Sequence i is
  * tokens_host[i][0 .. n_tokens_host[i]) (rows of max_tokens entries; the rest of a row is ignored) against the resident
  * encoder state of clip clip_host[i]; several sequences may name the same clip.  Shorter sequences are padded to max_tokens

@@ -17,7 +17,7 @@ SYMBOLS = [
     "ttasr_get_cross_kv", "ttasr_set_audio_ctx", "ttasr_generate", "ttasr_generate_capped", "ttasr_generate_beam", "ttasr_generate_beam_ragged", "ttasr_generate_sample", "ttasr_decode_reset", "ttasr_decode_step", "ttasr_apply_rules", "ttasr_align", "ttasr_dtw",
     "ttasr_set_option", "ttasr_phase_ms", "ttasr_beam_profile", "ttasr_encoder_kernel_ms", "ttasr_bench_kernel", "ttasr_bench_kernel_signature", "ttasr_sync",
     "ttasr_session_begin", "ttasr_session_begin_beam", "ttasr_session_submit", "ttasr_session_submit_windows", "ttasr_session_poll", "ttasr_session_stats", "ttasr_session_rows", "ttasr_session_end",
-    "ttasr_align_batch", "ttasr_session_hold", "ttasr_session_align", "ttasr_session_release",
+    "ttasr_align_batch", "ttasr_session_hold", "ttasr_session_align", "ttasr_session_release", "ttasr_detect_language",
 ]
 
 
@@ -85,6 +85,7 @@ def load() -> C.CDLL:
     lib.ttasr_decode_step.argtypes = [vp, i32p, i32, vp]
     lib.ttasr_apply_rules.argtypes = [vp, vp, i32p, i32, i32, C.POINTER(GenOpts), vp, i32p]
     lib.ttasr_align.argtypes = [vp, i32, i32p, i32, i32p, i32, f32p, f32p]
+    lib.ttasr_detect_language.argtypes = [vp, i32, i32, i32, i32, i32p, f32p, f32p]
     lib.ttasr_align_batch.argtypes = [vp, i32, i32p, i32p, i32p, i32, i32p, i32p, i32p, i32, i32, i32p, f32p, f32p, f32p]
     lib.ttasr_session_hold.argtypes = [vp, i32]
     lib.ttasr_session_align.argtypes = [vp, i32, i64p, i32p, i32p, i32, i32p, i32p, i32p, i32, i32, i32p, f32p, f32p, f32p]

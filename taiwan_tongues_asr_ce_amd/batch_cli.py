@@ -57,15 +57,17 @@ def _load_audio(path: str):
     return decode_audio(path)
 
 
-def transcribe_file(model, audio_file: str, load_audio: Callable = _load_audio, log: Callable = print, segments=None) -> Dict:
-    """One unit of work → one entry of `detailed_results`.  `segments`: already transcribed (group mode), else runs it."""
+def transcribe_file(model, audio_file: str, load_audio: Callable = _load_audio, log: Callable = print, segments=None,
+                    language: Optional[str] = TRANSCRIBE_KWARGS["language"], info=None) -> Dict:
+    """One unit of work → one entry of `detailed_results`.  `segments`: already transcribed (group mode, with its `info`), else
+    runs it.  language=None (`--language auto`): the language is detected, and the entry names it with its probability."""
     name = os.path.basename(audio_file)
     out_path = os.path.splitext(audio_file)[0] + "_asr.txt"
     try:
         if isinstance(segments, Exception):
             raise segments
         if segments is None:
-            segments, _info = model.transcribe(load_audio(audio_file), **TRANSCRIBE_KWARGS)
+            segments, info = model.transcribe(load_audio(audio_file), **dict(TRANSCRIBE_KWARGS, language=language))
         text = "".join(seg.text for seg in segments)            # consumes the lazy generator: this is where it runs
         processed = scoring.normalise_transcript(text)
         with open(out_path, "w", encoding="utf-8") as f:
@@ -73,6 +75,9 @@ def transcribe_file(model, audio_file: str, load_audio: Callable = _load_audio, 
         log(f"{name}: {processed}")
         entry = {"audio_file": name, "asr_result": processed, "original_transcript": None, "cer_result": None,
                  "has_original_transcript": False}
+        if language is None and info is not None:   # auto mode only: the forced-language run keeps the reference's keys exactly
+            entry["language"] = info.language
+            entry["language_probability"] = float(info.language_probability)
         ref_path = find_original_transcript(audio_file)
         if ref_path is not None:
             try:
@@ -118,7 +123,9 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
                          device_index: int = 0, compute_type: str = "float16", max_batch: int = 120, output_json: Optional[str] = None, rank: int = 0,
                          world: int = 1, load_audio: Callable = _load_audio, log: Callable = print,
                          group_files: int = 0, pipeline_depth: int = 0, continuous: bool = False,
-                         cross_kv_fp8: bool = False) -> Optional[Dict]:
+                         cross_kv_fp8: bool = False, language: Optional[str] = TRANSCRIBE_KWARGS["language"]) -> Optional[Dict]:
+    """language: the forced language of every file (the reference's "zh"), or None = detect each file's language (`--language
+    auto`); the detected language and its probability are then part of every entry of `detailed_results`."""
     if continuous:
         if int(pipeline_depth or getattr(model, "pipeline_depth", 1)) > 1:
             log("continuous mode runs one session on one engine context: pipeline depth 1")
@@ -136,11 +143,12 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
     many = getattr(model, "transcribe_many", None)
     group = group_files if group_files > 0 else max(1, getattr(model, "max_batch", 1) // TRANSCRIBE_KWARGS["beam_size"])
     if many is None or group < 2 or getattr(model, "vad_speech_prob_fn", None) is not None:
-        results = [transcribe_file(model, f, load_audio, log) for f in mine]
+        results = [transcribe_file(model, f, load_audio, log, language=language) for f in mine]
     else:
         # MI355X-first: `group` files advance in lock step through one engine pass per window round; every file keeps the
         # sequential algorithm (own seek / prompt / fallback), so the outputs equal the one-by-one run
         kw = {k: v for k, v in TRANSCRIBE_KWARGS.items() if k != "vad_filter"}   # no VAD source configured: all-speech
+        kw["language"] = language
         if continuous:
             # one continuous-batching session per group on one engine context: windows of the group's files refill decode rows
             # as others finish, fallback attempts included (WhisperModel.transcribe_many(continuous=True))
@@ -182,11 +190,12 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
                         done = iter(done_of[gi])
                     else:
                         done = iter(many(audios_of[gi], **kw)) if audios_of[gi] else iter(())
-                    segs = [err if err is not None else next(done)[0] for err in loaded_of[gi]]
+                    pairs = [(err, None) if err is not None else next(done) for err in loaded_of[gi]]
                 except Exception as e:  # engine-level failure of the group: fall back to one by one
                     log(f"group transcription failed ({e}); retrying file by file")
-                    segs = [None] * len(part)
-                results.extend(transcribe_file(model, f, load_audio, log, segments=sg) for f, sg in zip(part, segs))
+                    pairs = [(None, None)] * len(part)
+                results.extend(transcribe_file(model, f, load_audio, log, segments=sg, language=language, info=nfo)
+                               for f, (sg, nfo) in zip(part, pairs))
     if world > 1:
         import torch.distributed as dist
         gathered = [None] * world
@@ -228,6 +237,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--xkv-fp8", action="store_true",
                     help="opt-in serving mode: decode from the e4m3 copy of the cross-attention cache (16-bit compute types; "
                          "WhisperModel(cross_kv_fp8=True)); the summary JSON names the cache that was read")
+    ap.add_argument("--language", default=TRANSCRIBE_KWARGS["language"],
+                    help="language code forced on every file (default: the reference's zh), or 'auto': detect each file's language "
+                         "on the device; the summary JSON then holds language and language_probability per file")
     return ap
 
 
@@ -243,7 +255,7 @@ def main(argv=None) -> int:
     process_audio_folder(args.folder, model_path=args.model, device="cuda", device_index=local,
                          compute_type=args.compute_type, rank=rank, world=world, group_files=args.group_files,
                          max_batch=args.max_batch, pipeline_depth=args.pipeline_depth, continuous=args.continuous,
-                         cross_kv_fp8=args.xkv_fp8)
+                         cross_kv_fp8=args.xkv_fp8, language=None if args.language == "auto" else args.language)
     return 0
 
 

@@ -398,6 +398,12 @@ void launch_cross_attn_probs(const T* q, const T* K, const T* V, T* out, int row
                              float* probs /*[n_sel][rows][Tk]*/, hipStream_t s);
 void launch_token_logprob(const float* logits, int ldv, int V, const int32_t* target, float* out, int rows, hipStream_t s);
 void launch_token_prob(const float* logits, int ldv, int V, int tok, float* out /*[rows]*/, int rows, hipStream_t s);
+// language head (kernels_lang.hip): per row the dot products of the final-LayerNorm output dh [rows][d] with the rows
+// [lang_begin, lang_begin + n_lang) of the tied embedding emb [V][d], their softmax probs [rows][n_lang], the first maximum
+// best [rows] and (optional) the raw span logits [rows][n_lang]; 1 <= n_lang <= 128
+template <typename T>
+void launch_lang_head(const T* dh, const T* emb, int rows, int d, int V, int lang_begin, int n_lang, float* probs, int32_t* best,
+                      float* logits, hipStream_t s);
 template <typename T>
 void launch_embed_prefill(const int32_t* prompt, int max_prompt, int rows_per_prompt, int n_seq, int npos, const T* emb, const T* pos,
                           float* x, int d, hipStream_t s);

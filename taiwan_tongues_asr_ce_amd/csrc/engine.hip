@@ -600,6 +600,38 @@ int ttasr_align(ttasr_ctx* c, int32_t clip, const int32_t* tokens, int32_t n_tok
   });
 }
 
+int ttasr_detect_language(ttasr_ctx* c, int32_t B, int32_t sot, int32_t lang_begin, int32_t n_lang, int32_t* out_lang,
+                          float* out_probs, float* out_logits) {
+  return guarded(c, [&]() -> int {
+  if (!c) return TTASR_E_INVALID;
+  if (!c->finalized) return fail(c, TTASR_E_INVALID, "weights not finalized (call ttasr_finalize_weights first)");
+  TRY(session_refusal(c));
+  if (!out_lang) return fail(c, TTASR_E_INVALID, "out_lang_host is NULL");
+  if (c->B_enc < 1) return fail(c, TTASR_E_INVALID, "no encoder state is resident (ttasr_encode first)");
+  if (B < 1 || B > c->B_enc) return fail(c, TTASR_E_INVALID, "batch %d outside [1, %d] (the clips of the resident encoder state)", B, c->B_enc);
+  if (sot < 0 || sot >= c->V) return fail(c, TTASR_E_INVALID, "sot %d outside the vocabulary (%d)", sot, c->V);
+  if (n_lang < 1 || n_lang > 128) return fail(c, TTASR_E_INVALID, "n_lang %d outside [1, 128]", n_lang);
+  if (lang_begin < 0 || lang_begin > c->V - n_lang)
+    return fail(c, TTASR_E_INVALID, "language span [%d, %d) outside the vocabulary (%d)", lang_begin, lang_begin + n_lang, c->V);
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  if (!c->lang_out) TRY(dalloc(c, &c->lang_out, (size_t)c->maxB * 257 * 4));
+  c->B_dec = 0;  // the pass writes position 0 of the rows' self-attention pages: any step-level decode state is gone
+  TRY(reset_search(c, B));
+  const std::vector<int32_t> tok(B, sot);
+  HIPCHK(c, hipMemcpyAsync(c->st.cur_tok, tok.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
+  c->lang_begin = lang_begin; c->lang_n = n_lang; c->lang_want_logits = out_logits != nullptr;
+  sched_detect_rows(c, B);
+  const size_t n = (size_t)B * n_lang * 4;
+  HIPCHK(c, hipMemcpyAsync(out_lang, c->lang_out + (size_t)c->maxB * 256, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+  if (out_probs) HIPCHK(c, hipMemcpyAsync(out_probs, c->lang_out, n, hipMemcpyDeviceToHost, s));
+  if (out_logits) HIPCHK(c, hipMemcpyAsync(out_logits, c->lang_out + (size_t)c->maxB * 128, n, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));   // tok is a stack temporary
+  HIPCHK(c, hipGetLastError());
+  return TTASR_OK;
+  });
+}
+
 int ttasr_dtw(const float* cost, int32_t n_rows, int32_t n_cols, int32_t* out_row, int32_t* out_col, int32_t* out_len) {
   return guarded(nullptr, [&]() -> int {
   if (!cost || !out_row || !out_col || !out_len || n_rows < 1 || n_cols < 1) return TTASR_E_INVALID;

@@ -105,6 +105,9 @@ struct ttasr_ctx {
   float* xsplit_ws = nullptr;  // split-frame cross-attention (small batches)
   float* dx = nullptr; void *dh = nullptr, *dqkv = nullptr, *dq = nullptr, *datt = nullptr, *dmid = nullptr; float* logits = nullptr;
   float* rows_out = nullptr;
+  // language detection (ttasr_detect_language): the span of the tied embedding the pass ends in and its device results -
+  // probs [maxB][128] f32, span logits [maxB][128] f32, winners [maxB] i32 (rows packed at n_lang); allocated by the first call
+  float* lang_out = nullptr; int lang_begin = 0, lang_n = 0; bool lang_want_logits = false;
   StepShape shape;           // the decode shape of the search that is running (SearchScope); the defaults between searches
   int32_t* pairs_dev = nullptr;  // beam search: copy-on-write page pairs
   float* topk_lp = nullptr; int32_t* topk_id = nullptr; int32_t* row_state = nullptr;  // beam search scratch
@@ -318,6 +321,7 @@ void sched_gemm(ttasr_ctx* c, const GemmArgs& g);              // encoder-side G
 void sched_dec_gemm(ttasr_ctx* c, const GemmArgs& g, const void* Wsh);
 int prefill_positions(const ttasr_ctx* c, int min_plen, const ttasr_gen_opts* o, bool ns_from_prefill = false);
 int step_graph(ttasr_ctx* c, int B, int mode, int nsteps = 1);
+void sched_detect_rows(ttasr_ctx* c, int B);                  // decode pass of B rows that ends in the language head (mode 3), launched directly
 void drop_graphs(ttasr_ctx* c);
 void drop_rule_graphs(ttasr_ctx* c);
 

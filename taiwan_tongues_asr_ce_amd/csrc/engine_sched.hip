@@ -190,7 +190,8 @@ int run_encoder(ttasr_ctx* c, int B) {
 
 // One decoder step for rows [row0, row0 + n) at position *st.step, enqueued on c->cur.
 // mode 0: through logits + select; 1: logits only (test API / beam search); 2: no logits (all rows forced by
-// the prompt), select just advances the forced token.  `total_rows` = rows of the whole step (both half-batch chains):
+// the prompt), select just advances the forced token; 3: the language head (kernels_lang.hip) over the span c->lang_begin /
+// c->lang_n instead of the vocabulary projection, no select (ttasr_detect_language).  `total_rows` = rows of the whole step (both half-batch chains):
 // the select launch that finishes last advances the position counter.
 //
 // bf16 launch plan per layer (the measured mode; no float atomics anywhere, every launch bit-reproducible):
@@ -319,6 +320,13 @@ void run_decode_rows(ttasr_ctx* c, int row0, int n, int mode, int total_rows) {
   }
   if (mode != 2) {
     ln(c->dlnf_g, c->dlnf_b);
+    if (mode == 3) {   // the rows of the plain tied embedding (not the packed copy): n_lang dot products per row, softmax, winner
+      float* probs = c->lang_out + (size_t)row0 * c->lang_n;
+      float* span = c->lang_out + (size_t)c->maxB * 128 + (size_t)row0 * c->lang_n;
+      launch_lang_head<T>((const T*)dh, (const T*)c->emb, n, d, c->V, c->lang_begin, c->lang_n, probs,
+                          (int32_t*)(c->lang_out + (size_t)c->maxB * 256) + row0, c->lang_want_logits ? span : nullptr, s);
+      return;
+    }
     GemmArgs g = lin_args<T>(dh, c->emb, n, c->V, d);  // proj_out tied to embed_tokens (modeling_whisper.py:965)
     g.epi.out_f32 = logits; g.epi.ldc = c->ldv;
     dec_gemm<T>(c, g, c->emb_sh);
@@ -531,6 +539,7 @@ int sched_prefill_no_speech(ttasr_ctx* c, int n_seq, int npos, int sot, int no_s
   TT_DISPATCH(c, return prefill_no_speech<T>(c, n_seq, npos, sot, no_speech_tok));
   return 0;
 }
+void sched_detect_rows(ttasr_ctx* c, int B) { c->cur = c->stream; TT_DISPATCH(c, run_decode_rows<T>(c, 0, B, 3, B)); }
 void sched_gemm(ttasr_ctx* c, const GemmArgs& g) { TT_DISPATCH(c, gemm<T>(c, g)); }
 void sched_dec_gemm(ttasr_ctx* c, const GemmArgs& g, const void* Wsh) { TT_DISPATCH(c, dec_gemm<T>(c, g, Wsh)); }
 

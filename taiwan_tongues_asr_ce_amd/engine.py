@@ -332,6 +332,31 @@ class Engine:
         return _align_batch_call(self, self.lib.ttasr_align_batch, "align_batch", cl.ctypes.data_as(C.POINTER(C.c_int32)), packed,
                                  debug)
 
+    def language_span(self) -> Tuple[int, int]:
+        """(first language token, number of language tokens): sot + 1 up to the first of <|translate|> / <|transcribe|>, capped at
+        the languages this build can name."""
+        from .model import LANGUAGES
+        st = self.special
+        n = min(st.translate, st.transcribe) - (st.sot + 1)
+        return st.sot + 1, max(1, min(n, len(LANGUAGES)))
+
+    def detect_language(self, B: int, want_logits: bool = False, span: Optional[Tuple[int, int]] = None):
+        """Language identification of the B clips whose encoder state is resident (ttasr_detect_language: one decoder pass at
+        <|startoftranscript|> ending in the language head; no vocabulary projection, no second encoder pass).
+        -> (indices int32 [B] into the span, probs float32 [B][n_lang][, span logits float32 [B][n_lang]]).
+        span = (first token, count), default language_span().  Invalidates any step-level decode state."""
+        begin, n_lang = self.language_span() if span is None else (int(span[0]), int(span[1]))
+        B = int(B)
+        idx = np.zeros(max(B, 1), dtype=np.int32)
+        probs = np.zeros((max(B, 1), max(n_lang, 1)), dtype=np.float32)
+        logits = np.zeros_like(probs) if want_logits else None
+        self._check(self.lib.ttasr_detect_language(self.h, B, self.special.sot, begin, n_lang,
+                                                   idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                   probs.ctypes.data_as(C.POINTER(C.c_float)),
+                                                   logits.ctypes.data_as(C.POINTER(C.c_float)) if want_logits else None),
+                    "detect_language")
+        return (idx, probs, logits) if want_logits else (idx, probs)
+
     def decode_reset(self, B: int):
         self._check(self.lib.ttasr_decode_reset(self.h, B), "decode_reset")
 

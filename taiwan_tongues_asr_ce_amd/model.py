@@ -79,6 +79,23 @@ LANGUAGES = ("en zh de es ru ko fr ja pt tr pl ca nl ar sv it id hi fi vi he uk 
              "tg sd gu am yi lo uz fo ht ps tk nn mt sa lb my bo tl mg as tt haw ln ha ba jw su yue").split()
 
 
+def select_language(tops: Sequence[Tuple[str, float]], threshold: Optional[float] = 0.5) -> Tuple[str, float, int]:
+    """faster-whisper's language_detection_segments / language_detection_threshold rule over the top (language, probability) of
+    the windows that were examined, in file order -> (language, probability, index of the window the answer is taken from).
+    The first window whose top probability exceeds the threshold decides; when none does, the language that won the most
+    windows (a tie goes to the one seen first), with the largest probability it reached, taken from that window."""
+    if not tops:
+        raise ValueError("select_language needs at least one window")
+    votes: Dict[str, List[Tuple[float, int]]] = {}
+    for i, (lang, prob) in enumerate(tops):
+        if threshold is None or prob > threshold:
+            return lang, float(prob), i
+        votes.setdefault(lang, []).append((float(prob), i))
+    lang = max(votes, key=lambda k: len(votes[k]))      # dicts keep insertion order: the first of equally frequent languages
+    prob, i = max(votes[lang], key=lambda e: e[0])      # the first of equal probabilities
+    return lang, prob, i
+
+
 def _to_mono_16k(x: np.ndarray, sr: int, sampling_rate: int) -> np.ndarray:
     if sr != sampling_rate:
         from math import gcd
@@ -377,20 +394,61 @@ class WhisperModel:
 
     def detect_language(self, audio: np.ndarray) -> Tuple[str, float, List[Tuple[str, float]]]:
         """Language = argmax over the language tokens of the logits after <|startoftranscript|>."""
-        eng, st = self.engine, self.special
-        eng.set_audio_ctx(0)
-        eng.log_mel([audio[: self.n_window]], want_output=False)
-        eng.encode(1)
-        eng.decode_reset(1)
-        logits = eng.decode_step([st.sot])[0]
-        n_lang = (st.translate if st.translate < st.transcribe else st.transcribe) - (st.sot + 1)
-        n_lang = max(1, min(n_lang, len(LANGUAGES)))
-        ll = logits[st.sot + 1: st.sot + 1 + n_lang].astype(np.float64)
-        p = np.exp(ll - ll.max())
-        p /= p.sum()
-        order = np.argsort(-p)
-        probs = [(LANGUAGES[i], float(p[i])) for i in order]
-        return probs[0][0], probs[0][1], probs
+        return self.detect_language_batch([audio])[0]
+
+    def _ranked(self, probs: np.ndarray) -> List[Tuple[str, float]]:
+        """One row of language probabilities -> [(language, probability)] by falling probability (ties: vocabulary order)."""
+        order = np.argsort(-probs, kind="stable")
+        return [(LANGUAGES[i], float(probs[i])) for i in order]
+
+    def _detect_resident(self, B: int) -> List[Tuple[str, float, List[Tuple[str, float]]]]:
+        """(language, probability, all probabilities) of the B clips whose encoder state is resident (Engine.detect_language)."""
+        idx, probs = self.engine.detect_language(B)
+        return [(LANGUAGES[int(idx[b])], float(probs[b, int(idx[b])]), self._ranked(probs[b])) for b in range(B)]
+
+    def detect_language_batch(self, audios_or_windows: Sequence[np.ndarray]) -> List[Tuple[str, float, List[Tuple[str, float]]]]:
+        """detect_language for many clips: the first 30-s window of each, max_batch at a time - one log-mel, one encoder pass and
+        one decoder pass that ends in the language head (ttasr_detect_language) per chunk; softmax and argmax run on the device."""
+        eng = self.engine
+        out: List[Tuple[str, float, List[Tuple[str, float]]]] = []
+        for i in range(0, len(audios_or_windows), self.max_batch):
+            chunk = [np.ascontiguousarray(np.asarray(a)[: self.n_window], dtype=np.float32) for a in audios_or_windows[i:i + self.max_batch]]
+            eng.set_audio_ctx(0)
+            eng.log_mel(chunk, want_output=False)
+            eng.encode(len(chunk))
+            out.extend(self._detect_resident(len(chunk)))
+        return out
+
+    def _check_languages(self, language, n: int, what: str) -> List[Optional[str]]:
+        """`language` of a batched surface -> one entry per item: a string (every item), None (detect every item) or a sequence
+        of n strings / None."""
+        if language is None or isinstance(language, str):
+            langs: List[Optional[str]] = [language] * n
+        else:
+            langs = list(language)
+            if len(langs) != n:
+                raise ValueError(f"language needs one entry per {what} ({n}), got {len(langs)}")
+        for l in langs:
+            if l is not None and not isinstance(l, str):
+                raise ValueError(f"language entries must be a language code or None, got {l!r}")
+            if l is not None:
+                self._lang_token(l)   # raises on a code this build cannot name
+        return langs
+
+    def _resolve_languages(self, language, first_windows: Sequence[np.ndarray], what: str
+                           ) -> List[Tuple[str, float, Optional[List[Tuple[str, float]]]]]:
+        """(language, probability, all probabilities or None) per item: given languages count as certain, None entries are
+        detected from `first_windows` in batched passes (detect_language_batch)."""
+        langs = self._check_languages(language, len(first_windows), what)
+        out: List = [(l, 1.0, None) for l in langs]
+        todo = [i for i, l in enumerate(langs) if l is None]
+        if todo and not self.is_multilingual:
+            for i in todo:
+                out[i] = ("en", 1.0, None)
+        elif todo:
+            for i, r in zip(todo, self.detect_language_batch([first_windows[i] for i in todo])):
+                out[i] = r
+        return out
 
     def _prompt(self, lang_tok: int, task: str, without_timestamps: bool, prev: Sequence[int],
                 hotwords: Optional[Sequence[int]] = None, prefix: Optional[Sequence[int]] = None) -> Tuple[List[int], int]:
@@ -468,15 +526,19 @@ class WhisperModel:
                    no_speech_threshold: Optional[float] = 0.6, log_prob_threshold: Optional[float] = -1.0,
                    max_initial_timestamp: float = 1.0, suppress_blank: bool = True,
                    temperature: Union[float, Sequence[float]] = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0), best_of: int = 5,
-                   compression_ratio_threshold: Optional[float] = 2.4, **kwargs
+                   compression_ratio_threshold: Optional[float] = 2.4, multilingual: bool = False,
+                   language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1, **kwargs
                    ) -> Tuple[Iterator[Segment], TranscriptionInfo]:
+        """language=None: the language is detected from the first `language_detection_segments` 30-s windows (select_language:
+        the first window whose top probability exceeds `language_detection_threshold`, else the majority).  multilingual=True:
+        every window is detected again between its encoder pass and its search, and its prompt carries that window's language
+        token (code-switched speech); info.language stays the file-level answer."""
         # faster-whisper options this build does not implement are never silently ignored when they differ from
         # their defaults (the reference call sites pass none of them)
         neutral = {"patience": None, "vad_parameters": None, "vad_speech_prob_fn": None, "length_penalty": 1, "repetition_penalty": 1,
                    "no_repeat_ngram_size": 0, "clip_timestamps": "0",
                    "hallucination_silence_threshold": None, "prompt_reset_on_temperature": 0.5, "suppress_tokens": [-1],
                    "prepend_punctuations": alignment.PREPEND_PUNCTUATIONS, "append_punctuations": alignment.APPEND_PUNCTUATIONS,
-                   "multilingual": False, "language_detection_threshold": 0.5, "language_detection_segments": 1,
                    "chunk_length": None, "log_progress": False}
         for k, v in kwargs.items():
             if k in ("patience", "vad_parameters", "vad_speech_prob_fn", "hotwords", "prefix"):
@@ -520,9 +582,14 @@ class WhisperModel:
                 audio = vad.collect_chunks(audio, chunks)
         duration_after_vad = len(audio) / SAMPLE_RATE
         duration = (audio_full_len if chunks is not None else len(audio)) / SAMPLE_RATE
+        if int(language_detection_segments) < 1:
+            raise ValueError("language_detection_segments must be >= 1")
         if language is None:
             if self.is_multilingual:
-                language, lang_p, all_p = self.detect_language(audio)
+                k = int(language_detection_segments)
+                found = self.detect_language_batch([audio[i * self.n_window:] for i in range(k) if i == 0 or i * self.n_window < len(audio)])
+                language, lang_p, i = select_language([(f[0], f[1]) for f in found], language_detection_threshold)
+                all_p = found[i][2]
             else:
                 language, lang_p, all_p = "en", 1.0, None
         else:
@@ -537,7 +604,8 @@ class WhisperModel:
                                            max_initial_timestamp, suppress_blank, beam_size, kwargs.get("patience", 1.0),
                                            tuple(temperature) if isinstance(temperature, (list, tuple)) else (float(temperature),),
                                            best_of, compression_ratio_threshold, bool(word_timestamps),
-                                           kwargs.get("hotwords"), kwargs.get("prefix"))
+                                           kwargs.get("hotwords"), kwargs.get("prefix"),
+                                           multilingual=bool(multilingual) and self.is_multilingual)
         if chunks is not None:
             segments = vad.restore_speech_timestamps(segments, chunks)
         return segments, info
@@ -647,7 +715,7 @@ class WhisperModel:
             text_tokens = [t for seg in kept for t in seg["tokens"] if t < st.eot]
             task_tok = st.translate if p["task"] == "translate" else st.transcribe
             found = alignment.find_alignment(eng, self.tokenizer, st, clip_index, text_tokens, win_frames, self.alignment_heads,
-                                             p["language"], p["lang_tok"], task_tok)
+                                             fs.get("language", p["language"]), fs.get("lang_tok", p["lang_tok"]), task_tok)
             alignment.add_word_timestamps(kept, found, time_offset)
             for seg in kept:
                 seg["start"], seg["end"] = min(seg["start"], limit), min(seg["end"], limit)
@@ -704,7 +772,7 @@ class WhisperModel:
     def _generate_segments(self, audio, language, task, condition, initial_prompt, without_timestamps, max_new_tokens,
                            no_speech_threshold, log_prob_threshold, max_initial_timestamp, suppress_blank, beam_size=1,
                            patience=1.0, temperatures=(0.0,), best_of=5, compression_ratio_threshold=2.4,
-                           word_timestamps=False, hotwords=None, prefix=None) -> Iterator[Segment]:
+                           word_timestamps=False, hotwords=None, prefix=None, multilingual=False) -> Iterator[Segment]:
         eng = self.engine
         p = self._params(language, task, condition, without_timestamps, max_new_tokens, no_speech_threshold,
                          log_prob_threshold, max_initial_timestamp, suppress_blank, beam_size, patience, temperatures, best_of,
@@ -718,20 +786,24 @@ class WhisperModel:
             eng.set_audio_ctx(0)
             eng.log_mel_windows(audio, [seek], floor_max=[file_max])
             eng.encode(1)
+            if multilingual:   # this window's language, from the encoder state that is resident anyway
+                p["language"] = self._detect_resident(1)[0][0]
+                p["lang_tok"] = self._lang_token(p["language"])
             prompt, sot_index = self._prompt(p["lang_tok"], task, without_timestamps, fs["prev"][fs["prompt_reset"]:],
                                              p["hotwords_tokens"], p["prefix_tokens"] if seek == 0 else None)
             attempt = self._decode_with_fallback(prompt, self._window_opts(len(prompt), sot_index, p), seek, p)
             yield from self._finish_window(fs, 0, attempt, win_frames, p)
 
-    def transcribe_many(self, audios: Sequence[Union[str, np.ndarray]], language: str = "zh", task: str = "transcribe",
+    def transcribe_many(self, audios: Sequence[Union[str, np.ndarray]],
+                        language: Union[None, str, Sequence[Optional[str]]] = "zh", task: str = "transcribe",
                         beam_size: int = 5, word_timestamps: bool = False, condition_on_previous_text: bool = True,
                         initial_prompt: Optional[str] = None, without_timestamps: bool = False,
                         max_new_tokens: Optional[int] = None, no_speech_threshold: Optional[float] = 0.6,
                         log_prob_threshold: Optional[float] = -1.0, max_initial_timestamp: float = 1.0,
                         suppress_blank: bool = True, temperature: Union[float, Sequence[float]] = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0),
                         best_of: int = 5, compression_ratio_threshold: Optional[float] = 2.4, patience: float = 1.0,
-                        hotwords: Optional[str] = None, prefix: Optional[str] = None, continuous: bool = False
-                        ) -> List[Tuple[List[Segment], TranscriptionInfo]]:
+                        hotwords: Optional[str] = None, prefix: Optional[str] = None, continuous: bool = False,
+                        multilingual: bool = False) -> List[Tuple[List[Segment], TranscriptionInfo]]:
         """Several FILES in lock step: every round takes the next 30-s window of each unfinished file and runs them as
         ONE engine pass (log-mel, encoder, beam search with one previous-text prompt per file), so a folder is
         transcribed at batch throughput while each file keeps exactly the sequential algorithm of `transcribe` — its
@@ -743,17 +815,28 @@ class WhisperModel:
         temperature (sampled attempts run in the session too), and a file's next window is submitted as soon as its current
         one is settled.  Each file gets exactly `transcribe()`'s algorithm.  word_timestamps is not supported there: the
         session can align now (Session.hold / Session.align, used by transcribe_stream and the streaming backend), but moving
-        this path and transcribe() onto the batched device alignment is a follow-up."""
+        this path and transcribe() onto the batched device alignment is a follow-up.
+
+        language: one code for every file (as before), None (detect every file) or one entry per file, each a code or None.
+        The None files are detected from their first windows in batched passes BEFORE decoding starts - with continuous=True
+        before the session begins, which costs one extra encoder pass over those first windows (a session owns the encoder
+        while it is open).  Each file's TranscriptionInfo carries its own language, probability and all_language_probs.
+        multilingual=True (lock-step form only): every window is detected again between its encoder pass and its search, from
+        the encoder state that is resident anyway, and its prompt carries that window's language token."""
         eng = self.engine
+        if continuous and multilingual:
+            raise ValueError("multilingual=True is not supported with continuous=True (per-window detection inside a session "
+                             "is not implemented)")
         if continuous and word_timestamps:
             raise ValueError("word_timestamps=True is not supported with continuous=True (the alignment pass needs the window's "
                              "encoder state, which the session hands to the next window)")
         beam = max(1, min(beam_size, 7, self.max_batch))
         per_pass = max(1, self.max_batch // beam)
         temps = tuple(temperature) if isinstance(temperature, (list, tuple)) else (float(temperature),)
-        p = self._params(language, task, condition_on_previous_text, without_timestamps, max_new_tokens, no_speech_threshold,
-                         log_prob_threshold, max_initial_timestamp, suppress_blank, beam, patience, temps, best_of,
-                         compression_ratio_threshold, bool(word_timestamps), hotwords, prefix)
+        langs = self._check_languages(language, len(audios), "file")
+        p = self._params(next((l for l in langs if l is not None), "en"), task, condition_on_previous_text, without_timestamps,
+                         max_new_tokens, no_speech_threshold, log_prob_threshold, max_initial_timestamp, suppress_blank, beam,
+                         patience, temps, best_of, compression_ratio_threshold, bool(word_timestamps), hotwords, prefix)
         if continuous:
             p["beam_size"] = int(beam_size)
         files = []
@@ -765,6 +848,10 @@ class WhisperModel:
             fs["segments"] = []
             fs["file_max"] = self._file_feature_max(fs["audio"])   # whole-file dynamic-range floor, as `transcribe`
             files.append(fs)
+        found = self._resolve_languages(langs, [fs["audio"] for fs in files], "file")
+        for fs, (lang, lang_p, all_p) in zip(files, found):
+            fs["language"], fs["lang_tok"], fs["lang_info"] = lang, self._lang_token(lang), (lang, lang_p, all_p)
+        multilingual = bool(multilingual) and self.is_multilingual
         if continuous:
             self._run_continuous(files, p)
         while not continuous:
@@ -777,9 +864,12 @@ class WhisperModel:
                 eng.log_mel_windows([fs["audio"] for fs in group], [fs["seek"] for fs in group],
                                     floor_max=[fs["file_max"] for fs in group])
                 eng.encode(len(group))
+                if multilingual:   # the windows' own languages, from the encoder state of the pass
+                    for fs, r in zip(group, self._detect_resident(len(group))):
+                        fs["language"], fs["lang_tok"] = r[0], self._lang_token(r[0])
                 prompts, sots = [], []
                 for fs in group:
-                    pr, si = self._prompt(p["lang_tok"], task, without_timestamps, fs["prev"][fs["prompt_reset"]:],
+                    pr, si = self._prompt(fs["lang_tok"], task, without_timestamps, fs["prev"][fs["prompt_reset"]:],
                                           p["hotwords_tokens"], p["prefix_tokens"] if fs["seek"] == 0 else None)
                     prompts.append(pr)
                     sots.append(si)
@@ -803,8 +893,9 @@ class WhisperModel:
         out = []
         for fs in files:
             dur = len(fs["audio"]) / SAMPLE_RATE
-            info = TranscriptionInfo(language=language, language_probability=1.0, duration=dur, duration_after_vad=dur,
-                                     all_language_probs=None,
+            lang, lang_p, all_p = fs["lang_info"]
+            info = TranscriptionInfo(language=lang, language_probability=lang_p, duration=dur, duration_after_vad=dur,
+                                     all_language_probs=all_p,
                                      transcription_options=dict(beam_size=beam, task=task, without_timestamps=without_timestamps,
                                                                 condition_on_previous_text=condition_on_previous_text,
                                                                 initial_prompt=initial_prompt))
@@ -844,7 +935,7 @@ class WhisperModel:
                 inflight[ids[0]] = fs
 
             def next_window(fs: dict):
-                pr, si = self._prompt(p["lang_tok"], p["task"], p["without_timestamps"], fs["prev"][fs["prompt_reset"]:],
+                pr, si = self._prompt(fs.get("lang_tok", p["lang_tok"]), p["task"], p["without_timestamps"], fs["prev"][fs["prompt_reset"]:],
                                       p["hotwords_tokens"], p["prefix_tokens"] if fs["seek"] == 0 else None)
                 fs["window"] = dict(prompt=pr, sot=si, budget=min(p["max_new"], n_ctx - len(pr)), attempts=[],
                                     frames=min(self.dims.n_frames, fs["n_total"] - fs["seek"]))
@@ -875,25 +966,42 @@ class WhisperModel:
                         next_window(fs)
 
     # ------------------------------------------------------------------------------------------
-    def transcribe_batch(self, clips: Sequence[np.ndarray], language: str = "zh", task: str = "transcribe",
-                         without_timestamps: bool = True, max_new_tokens: int = 224) -> List[List[int]]:
+    def _pass_languages(self, langs: Sequence[Optional[str]], info: List[Tuple[str, float]]) -> List[str]:
+        """Languages of one resident pass: the None entries are detected from the pass's encoder state (no extra encoder pass);
+        (language, probability) of every clip is appended to `info`."""
+        found: List[Tuple[str, float]] = [(l, 1.0) for l in langs]   # type: ignore[misc]
+        if any(l is None for l in langs):
+            det = self._detect_resident(len(langs)) if self.is_multilingual else [("en", 1.0, None)] * len(langs)
+            found = [(d[0], d[1]) if l is None else (l, 1.0) for l, d in zip(langs, det)]
+        info.extend(found)
+        return [f[0] for f in found]
+
+    def transcribe_batch(self, clips: Sequence[np.ndarray], language: Union[None, str, Sequence[Optional[str]]] = "zh",
+                         task: str = "transcribe", without_timestamps: bool = True, max_new_tokens: int = 224) -> List[List[int]]:
         """Batched single-window path (clips <= 30 s each): one engine pass for up to max_batch clips.
-        Returns the sampled token ids per clip.  This is the unit the data-parallel layer shards."""
+        Returns the sampled token ids per clip.  This is the unit the data-parallel layer shards.
+        language: one code, None (detect every clip) or one entry per clip (a code or None); None clips are detected from the
+        pass's own encoder state.  (language, probability) per clip of the last call: `last_language_info`."""
         eng = self.engine
         out: List[List[int]] = []
-        lang_tok = self._lang_token(language)
+        langs = self._check_languages(language, len(clips), "clip")
+        info: List[Tuple[str, float]] = []
         for i in range(0, len(clips), self.max_batch):
             chunk = [np.ascontiguousarray(c[: self.n_window], dtype=np.float32) for c in clips[i:i + self.max_batch]]
             eng.set_audio_ctx(0)
             eng.log_mel(chunk, want_output=False)
             eng.encode(len(chunk))
-            prompt, sot_index = self._prompt(lang_tok, task, without_timestamps, [])
+            prompts = [self._prompt(self._lang_token(l), task, without_timestamps, []) for l in
+                       self._pass_languages(langs[i:i + self.max_batch], info)]
+            prompt, sot_index = prompts[0]
             opts = eng.gen_opts(min(max_new_tokens, self.dims.n_text_ctx - len(prompt)), timestamps=not without_timestamps,
                                 sot_index=sot_index)
-            out.extend(eng.generate([prompt] * len(chunk), opts).tokens)
+            out.extend(eng.generate([pr for pr, _ in prompts], opts).tokens)
+        self.last_language_info = info
         return out
 
-    def transcribe_stream(self, clips: Sequence[np.ndarray], language: str = "zh", task: str = "transcribe",
+    def transcribe_stream(self, clips: Sequence[np.ndarray], language: Union[None, str, Sequence[Optional[str]]] = "zh",
+                          task: str = "transcribe",
                           without_timestamps: bool = True, max_new_tokens: int = 224,
                           row_max_new: Optional[Sequence[int]] = None, beam_size: int = 1, patience: float = 1.0,
                           initial_prompt: Optional[str] = None, word_timestamps: bool = False):
@@ -903,30 +1011,37 @@ class WhisperModel:
         beam_size > 1: beam search (a clip takes a group of beam_size rows; tokens without EOT, as transcribe_windows decodes
         them); initial_prompt: previous text in front of <|startoftranscript|>, as transcribe_windows builds it.
         word_timestamps=True: (tokens, words) per clip, words as transcribe_windows returns them; the session runs in hold mode
-        (a finished clip keeps its row and cross-KV slot) and the clips one poll returned are aligned in one device pass."""
+        (a finished clip keeps its row and cross-KV slot) and the clips one poll returned are aligned in one device pass.
+        language: one code, None (detect every clip) or one entry per clip (a code or None).  None clips are detected in batched
+        passes BEFORE the session begins (a session owns the encoder while it is open): one extra encoder pass over those
+        clips.  (language, probability) per clip of the last call: `last_language_info`."""
         if len(clips) == 0:
+            self.last_language_info = []
             return []
         eng = self.engine
         beam = int(beam_size)
         if not 1 <= beam <= 7:
             raise ValueError(f"beam_size {beam} outside [1, 7]")
-        lang_tok = self._lang_token(language)
+        for c in clips:
+            if len(c) > self.n_window:
+                raise ValueError(f"transcribe_stream takes clips of at most one window ({self.n_window} samples)")
+        found = self._resolve_languages(language, clips, "clip")
+        self.last_language_info = [(f[0], f[1]) for f in found]
+        clip_lang = [f[0] for f in found]
         prev = self.tokenizer.encode(" " + initial_prompt.strip()) if initial_prompt else []
-        prompt, sot_index = self._prompt(lang_tok, task, without_timestamps, prev)
+        prompts = [self._prompt(self._lang_token(l), task, without_timestamps, prev)[0] for l in clip_lang]
+        prompt, sot_index = self._prompt(self._lang_token(clip_lang[0]), task, without_timestamps, prev)
         n_new = min(max_new_tokens, self.dims.n_text_ctx - len(prompt))
         caps = None
         if row_max_new is not None:
             caps = [int(v) for v in row_max_new]
             if len(caps) != len(clips) or min(caps) < 1 or max(caps) > n_new:
                 raise ValueError(f"row_max_new needs one budget in [1, {n_new}] per clip")
-        for c in clips:
-            if len(c) > self.n_window:
-                raise ValueError(f"transcribe_stream takes clips of at most one window ({self.n_window} samples)")
         eng.set_audio_ctx(0)
         opts = eng.gen_opts(n_new, timestamps=not without_timestamps, sot_index=sot_index)
         out: List[Optional[List[int]]] = [None] * len(clips)
         with (eng.session(opts, len(prompt), beam=beam, patience=patience) if beam > 1 else eng.session(opts, len(prompt))) as s:
-            ids = s.submit([np.ascontiguousarray(c, dtype=np.float32) for c in clips], [prompt] * len(clips), caps)
+            ids = s.submit([np.ascontiguousarray(c, dtype=np.float32) for c in clips], prompts, caps)
             where = {cid: i for i, cid in enumerate(ids)}
             if not word_timestamps:
                 for r in s.drain():
@@ -937,10 +1052,12 @@ class WhisperModel:
                 got = s.poll()
                 if not got:
                     raise RuntimeError(f"session idle with {s.pending} clips unfinished")
-                words = self._window_words(s, [r.id for r in got], [r.tokens for r in got],
-                                           [len(clips[where[r.id]]) for r in got], language, lang_tok, task)
-                for r, w in zip(got, words):
-                    out[where[r.id]] = (r.tokens, w)
+                for lang in sorted({clip_lang[where[r.id]] for r in got}):   # one alignment pass per language of the poll
+                    grp = [r for r in got if clip_lang[where[r.id]] == lang]
+                    words = self._window_words(s, [r.id for r in grp], [r.tokens for r in grp],
+                                               [len(clips[where[r.id]]) for r in grp], lang, self._lang_token(lang), task)
+                    for r, w in zip(grp, words):
+                        out[where[r.id]] = (r.tokens, w)
         return out  # type: ignore[return-value]
 
     def _window_words(self, aligner, refs: Sequence[int], tokens: Sequence[Sequence[int]], n_samples: Sequence[int],
@@ -973,7 +1090,8 @@ class WhisperModel:
             raise ValueError(f"audio_ctx={audio_ctx!r}: need an even value in [4, {full}], 'auto' or None")
         return n
 
-    def transcribe_windows(self, clips: Sequence[np.ndarray], language: str = "zh", beam_size: int = 5,
+    def transcribe_windows(self, clips: Sequence[np.ndarray], language: Union[None, str, Sequence[Optional[str]]] = "zh",
+                           beam_size: int = 5,
                            initial_prompt: Optional[str] = None, without_timestamps: bool = False,
                            max_new_tokens: int = 224, audio_ctx: Union[None, int, str] = None,
                            word_timestamps: bool = False) -> List[Tuple[str, float]]:
@@ -985,11 +1103,16 @@ class WhisperModel:
 
         word_timestamps=True: (text, end_time_seconds, words) per clip, words = [{word, start, end, probability}] in seconds
         from the start of the clip; all clips of a pass are aligned in ONE device pass (Engine.align_batch) against the
-        pass's encoder state, reduced audio_ctx included.  (transcribe() and transcribe_many() keep the one-window path.)"""
+        pass's encoder state, reduced audio_ctx included.  (transcribe() and transcribe_many() keep the one-window path.)
+
+        language: one code, None (detect every clip) or one entry per clip (a code or None); None clips are detected from the
+        pass's own encoder state (reduced audio_ctx included).  (language, probability) per clip of the last call:
+        `last_language_info`."""
         eng = self.engine
         beam = max(1, min(beam_size, 7))
         per_pass = max(1, self.max_batch // beam)
-        lang_tok = self._lang_token(language)
+        langs = self._check_languages(language, len(clips), "clip")
+        info: List[Tuple[str, float]] = []
         prev = self.tokenizer.encode(" " + initial_prompt.strip()) if initial_prompt else []
         out: List[Tuple[str, float]] = []
         try:
@@ -998,14 +1121,22 @@ class WhisperModel:
                 eng.set_audio_ctx(self._pick_audio_ctx(audio_ctx, max(len(c) for c in chunk)))
                 eng.log_mel(chunk, want_output=False)
                 eng.encode(len(chunk))
-                prompt, sot_index = self._prompt(lang_tok, "transcribe", without_timestamps, prev)
+                pass_lang = self._pass_languages(langs[i:i + per_pass], info)
+                prompts = [self._prompt(self._lang_token(l), "transcribe", without_timestamps, prev)[0] for l in pass_lang]
+                prompt, sot_index = self._prompt(self._lang_token(pass_lang[0]), "transcribe", without_timestamps, prev)
                 opts = eng.gen_opts(min(max_new_tokens, self.dims.n_text_ctx - len(prompt)), timestamps=not without_timestamps,
                                     sot_index=sot_index)
-                res = eng.generate_beam([prompt] * len(chunk), beam, opts) if beam > 1 else eng.generate([prompt] * len(chunk), opts)
-                words = (self._window_words(eng, range(len(chunk)), res.tokens, [len(c) for c in chunk], language, lang_tok)
-                         if word_timestamps else None)
+                res = eng.generate_beam(prompts, beam, opts) if beam > 1 else eng.generate(prompts, opts)
+                words: List = [None] * len(chunk)
+                if word_timestamps:   # one alignment pass per language of the pass
+                    for lang in sorted(set(pass_lang)):
+                        ks = [k for k, l in enumerate(pass_lang) if l == lang]
+                        for k, w in zip(ks, self._window_words(eng, ks, [res.tokens[k] for k in ks], [len(chunk[k]) for k in ks],
+                                                               lang, self._lang_token(lang))):
+                            words[k] = w
                 for k, (c, toks) in enumerate(zip(chunk, res.tokens)):
                     out.append(self.window_text(toks, len(c)) + ((words[k],) if word_timestamps else ()))
+            self.last_language_info = info
         finally:
             eng.set_audio_ctx(0)   # never leave a reduced window behind: the file-level paths assume the model's 30-s window
         return out

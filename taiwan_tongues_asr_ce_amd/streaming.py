@@ -52,7 +52,12 @@ class BatchedWhisperASR(MI355XWhisperASR):
 
     `word_timestamps=True` (opt-in, both modes): "words" holds {"word", "start", "end", "probability"} with the client's
     last_start_time added to start and end, and "duration" is the last word's end, as in the reference's result; the clips of
-    a pass (lock-step) or of a poll (continuous: the session runs in hold mode) are aligned in one device pass."""
+    a pass (lock-step) or of a poll (continuous: the session runs in hold mode) are aligned in one device pass.
+
+    `language` (default "zh", the reference's forced language): None detects every utterance from its pass's encoder state
+    (WhisperModel.transcribe_windows(language=None)) and reports the detected language and probability instead of "zh" and
+    1.0, with a warning when the probability is under 0.5 as the reference's adapter logs it.  Lock-step mode only: a
+    continuous session owns the encoder while it is open, and per-request detection inside it is not implemented."""
 
     def __init__(self, max_clips: int = 6, max_wait_ms: float = 5.0, audio_ctx=None, max_new_tokens: int = 224,
                  continuous: bool = False, word_timestamps: bool = False, **kwargs):
@@ -61,6 +66,9 @@ class BatchedWhisperASR(MI355XWhisperASR):
         self.continuous = bool(continuous)
         self.word_timestamps = bool(word_timestamps)
         beam = int(kwargs.pop("beam_size", 5))
+        self.language = kwargs.pop("language", "zh")
+        if continuous and self.language is None:
+            raise ValueError("language=None needs the lock-step mode (continuous=False): detection inside a session is not implemented")
         self.audio_ctx = audio_ctx            # None = Whisper's 30-s window; "auto"/int = opt-in short window (N2)
         self.max_new_tokens = max_new_tokens
         kwargs.setdefault("max_batch", max(8, max_clips * beam))
@@ -95,21 +103,24 @@ class BatchedWhisperASR(MI355XWhisperASR):
                 except asyncio.TimeoutError:
                     break
             audios = [a for a, _, _ in batch]
+            langs: List[Tuple[str, float]] = [("zh", 1.0)] * len(batch)
             try:
                 results = await loop.run_in_executor(None, self._run_batch, audios)
+                if self.language is None:
+                    langs = list(self.asr_pipeline.last_language_info)
             except Exception as e:  # the reference logs and returns None per request
                 logger.error("batched transcribe failed: %s", e)
                 results = [None] * len(batch)
             self.batches_run.append(len(batch))
-            for (_, last_start, fut), res in zip(batch, results):
+            for (_, last_start, fut), res, lang in zip(batch, results, langs):
                 if not fut.done():
-                    fut.set_result(self._result_dict(res, last_start))
+                    fut.set_result(self._result_dict(res, last_start, lang))
 
     def _run_batch(self, audios: Sequence[np.ndarray]) -> List[Optional[Tuple[str, float]]]:
         kw = self.default_transcribe_kwargs
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
-            outs = self.asr_pipeline.transcribe_windows(audios, language="zh", beam_size=kw["beam_size"],
+            outs = self.asr_pipeline.transcribe_windows(audios, language=self.language, beam_size=kw["beam_size"],
                                                         initial_prompt=kw["initial_prompt"], audio_ctx=self.audio_ctx,
                                                         max_new_tokens=self.max_new_tokens, word_timestamps=self.word_timestamps)
         return [_window_result(audio, *o) for audio, o in zip(audios, outs)]
@@ -169,9 +180,11 @@ class BatchedWhisperASR(MI355XWhisperASR):
             for _, _, fut, loop in pending.values():
                 resolve(fut, loop, None)
 
-    def _result_dict(self, res, last_start) -> Optional[Dict[str, Any]]:
+    def _result_dict(self, res, last_start, lang: Tuple[str, float] = ("zh", 1.0)) -> Optional[Dict[str, Any]]:
         if res is None:
             return None
+        if lang[1] < 0.5:   # the reference's adapter logs a low-confidence detection the same way
+            logger.warning("language %s detected with probability %.2f", lang[0], lang[1])
         text, duration = res[0], res[1]
         words = [{"word": w["word"], "start": w["start"] + last_start, "end": w["end"] + last_start, "probability": w["probability"]}
                  for w in (res[2] if len(res) > 2 else [])]
@@ -180,7 +193,7 @@ class BatchedWhisperASR(MI355XWhisperASR):
         if self.text_filter is not None:
             filtered = self.text_filter(text)
             text = text if filtered is None else filtered
-        return {"language": "zh", "language_probability": 1.0, "final": True, "text": text, "duration": duration, "words": words}
+        return {"language": lang[0], "language_probability": lang[1], "final": True, "text": text, "duration": duration, "words": words}
 
     async def transcribe(self, client) -> Optional[Dict[str, Any]]:
         try:
