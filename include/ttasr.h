@@ -296,6 +296,42 @@ TTASR_API int ttasr_session_submit_windows(ttasr_ctx* ctx, int32_t n, const floa
                                            const int32_t* prompt_len, const int32_t* sot_index, const int32_t* max_new,
                                            const float* temperature, const int32_t* rows, const uint32_t* seed, int64_t* out_ids);
 
+/* Language identification INSIDE a session (greedy or beam): no detection pass, and no second encoder pass, before the session.
+ * ttasr_session_detect_language arms the open session for the span [lang_begin, lang_begin + n_lang) of the tied embedding and
+ * the <|startoftranscript|> token `sot`.  From then on a prompt given to ttasr_session_submit / ttasr_session_submit_windows
+ * may hold the placeholder TTASR_TOKEN_DETECT, at most once and only directly behind a token equal to `sot`.
+ *   - When such a clip is admitted, its row (beam session: its group) first runs ONE detect step: `sot` at position 0 against
+ *     the clip's own cross-KV, an ordinary step of the session's max_batch rows.  Behind it the language head of
+ *     ttasr_detect_language - the same dot products, softmax and first maximum, in the same order - runs for that row on the
+ *     device, the placeholder is replaced by lang_begin + winner, and the row starts over at position 0 with prompt[0]
+ *     (position 0 of its self-attention pages is written again).  From there the clip decodes as if the language had been
+ *     given: its tokens, sum_logprob and no_speech are bit-identical to the same clip submitted with that token written out,
+ *     and winner, probabilities and span logits are those of ttasr_detect_language for the clip in a static pass of max_batch
+ *     clips.  A detected clip costs one more decode step and no encoder work; clips without the placeholder, and their
+ *     neighbours, are untouched.
+ *   - Greedy session: the head is one more launch in every step of the armed session's step graphs (also inside a run of
+ *     opts->check_interval steps); the device patches the prompt itself.  Beam session: the head runs behind the logits-only
+ *     step for the first row of each detecting group, its results come back with the step's one synchronisation, and the group
+ *     takes no part in that step's candidate, no-speech or independent-row work (BEAM and ROWS groups, plain and window clips).
+ *   - An unarmed session enqueues exactly what it did before this call existed.
+ *   - ttasr_session_stats: a detect step is a decode step (out[0]); out[4] counts one more live row-step per detected clip
+ *     (beam session: one per live row of its group).  ttasr_session_rows shows position 0 during the detect step.
+ * Refused with TTASR_E_INVALID, the context and the session stay usable: no session open; a clip was submitted already; the
+ * session is armed already; sot outside the vocabulary; n_lang outside [1, 128]; a span past the vocabulary.  The device
+ * buffers (flags, slots, results: max_batch * 261 words) belong to the context: allocated by the first armed session, freed by
+ * ttasr_destroy.  The submit calls refuse, before anything is queued: the placeholder in an unarmed session (as before: it is no
+ * token), not directly behind `sot`, or twice in a prompt.
+ * ttasr_session_poll_lang: ttasr_session_poll (same arguments, same behaviour; both are one implementation) plus
+ *   lang         int32 [cap]                   index into the span, -1 for a clip that carried no placeholder (required)
+ *   lang_probs   optional float32 [cap][n_lang] softmax over the span (rows of clips without placeholder are not written)
+ *   lang_logits  optional float32 [cap][n_lang] the raw span logits (idem)
+ * In an unarmed session every lang[k] is -1.  ttasr_session_poll on an armed session works and drops the language. */
+#define TTASR_TOKEN_DETECT (-1)
+TTASR_API int ttasr_session_detect_language(ttasr_ctx* ctx, int32_t sot, int32_t lang_begin, int32_t n_lang);
+TTASR_API int ttasr_session_poll_lang(ttasr_ctx* ctx, int32_t max_steps, int32_t cap, int64_t* ids, int32_t* tokens, int32_t* lens,
+                                      float* sum_lp, float* no_speech, int32_t* lang, float* lang_probs, float* lang_logits,
+                                      int32_t* n_out);
+
 TTASR_API int ttasr_session_stats(ttasr_ctx* ctx, double out[8]);
 TTASR_API int ttasr_session_rows(ttasr_ctx* ctx, int32_t* row_pos, int32_t* done, int64_t* row_clip);
 TTASR_API int ttasr_session_end(ttasr_ctx* ctx);

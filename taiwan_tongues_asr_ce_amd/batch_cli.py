@@ -123,9 +123,12 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
                          device_index: int = 0, compute_type: str = "float16", max_batch: int = 120, output_json: Optional[str] = None, rank: int = 0,
                          world: int = 1, load_audio: Callable = _load_audio, log: Callable = print,
                          group_files: int = 0, pipeline_depth: int = 0, continuous: bool = False,
-                         cross_kv_fp8: bool = False, language: Optional[str] = TRANSCRIBE_KWARGS["language"]) -> Optional[Dict]:
+                         cross_kv_fp8: bool = False, language: Optional[str] = TRANSCRIBE_KWARGS["language"],
+                         detect_in_session: bool = False) -> Optional[Dict]:
     """language: the forced language of every file (the reference's "zh"), or None = detect each file's language (`--language
-    auto`); the detected language and its probability are then part of every entry of `detailed_results`."""
+    auto`); the detected language and its probability are then part of every entry of `detailed_results`.
+    detect_in_session (`--detect-in-session`, with continuous and language None): the session finds each file's language in the
+    first decode step of its first window instead of a detection pass, with its own encoder pass, before the session."""
     if continuous:
         if int(pipeline_depth or getattr(model, "pipeline_depth", 1)) > 1:
             log("continuous mode runs one session on one engine context: pipeline depth 1")
@@ -153,6 +156,8 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
             # one continuous-batching session per group on one engine context: windows of the group's files refill decode rows
             # as others finish, fallback attempts included (WhisperModel.transcribe_many(continuous=True))
             kw["continuous"] = True
+            if detect_in_session and language is None:
+                kw["detect_in_session"] = True
         depth0 = max(1, int(pipeline_depth or getattr(model, "pipeline_depth", 1)))
         if group_files <= 0 and depth0 > 1 and len(mine) < group * depth0:
             group = max(1, -(-len(mine) // depth0))            # few files: one group per context rather than one big group and an idle lane
@@ -240,6 +245,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--language", default=TRANSCRIBE_KWARGS["language"],
                     help="language code forced on every file (default: the reference's zh), or 'auto': detect each file's language "
                          "on the device; the summary JSON then holds language and language_probability per file")
+    ap.add_argument("--detect-in-session", action="store_true",
+                    help="opt-in, with --continuous --language auto: each file's language is found inside the session, in the first "
+                         "decode step of its first window, instead of a detection pass with its own encoder pass beforehand")
     return ap
 
 
@@ -255,7 +263,8 @@ def main(argv=None) -> int:
     process_audio_folder(args.folder, model_path=args.model, device="cuda", device_index=local,
                          compute_type=args.compute_type, rank=rank, world=world, group_files=args.group_files,
                          max_batch=args.max_batch, pipeline_depth=args.pipeline_depth, continuous=args.continuous,
-                         cross_kv_fp8=args.xkv_fp8, language=None if args.language == "auto" else args.language)
+                         cross_kv_fp8=args.xkv_fp8, language=None if args.language == "auto" else args.language,
+                         detect_in_session=args.detect_in_session)
     return 0
 
 

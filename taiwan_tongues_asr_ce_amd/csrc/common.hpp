@@ -404,6 +404,18 @@ void launch_token_prob(const float* logits, int ldv, int V, int tok, float* out 
 template <typename T>
 void launch_lang_head(const T* dh, const T* emb, int rows, int d, int V, int lang_begin, int n_lang, float* probs, int32_t* best,
                       float* logits, hipStream_t s);
+// The language head inside a continuous-batching session's step: one workgroup per row, only rows with pending[row] != 0 work.
+// best [rows], probs / logits [rows][n_lang] are per-row result slots.  prompt != NULL (greedy session): the kernel replaces
+// prompt[row][slot[row]] by the winner's token, feeds prompt[row][0] at position 0 next and clears the flag; prompt == NULL
+// (beam session): results only, the host owns flags and positions.
+struct LangRows {
+  int32_t* pending; const int32_t* slot; int32_t* prompt; int max_prompt; int32_t* cur_tok; int32_t* row_pos;
+  int32_t* best; float* probs; float* logits;
+};
+template <typename T>
+void launch_lang_head_rows(const T* dh, const T* emb, int rows, int d, int V, int lang_begin, int n_lang, const LangRows& a, hipStream_t s);
+// greedy-session admission of n detecting rows: tab [n][2] = {row, slot}; the row is fed `sot` and its pending flag raised
+void launch_lang_admit_rows(const int32_t* tab, int n, int B, int sot, int32_t* pending, int32_t* slot, int32_t* cur_tok, hipStream_t s);
 template <typename T>
 void launch_embed_prefill(const int32_t* prompt, int max_prompt, int rows_per_prompt, int n_seq, int npos, const T* emb, const T* pos,
                           float* x, int d, hipStream_t s);

@@ -46,7 +46,10 @@ struct StepShape {
   int kv_div = 1;            // rows per clip sharing one cross-KV (beam width); 1 for greedy
   int identity_pages = 1;    // page_table is the identity map (greedy): the self-attention kernel computes page ids
   bool rows_pos = false;     // per-row positions (continuous-batching session: row_pos instead of st.step)
-  bool operator==(const StepShape& o) const { return kv_div == o.kv_div && identity_pages == o.identity_pages && rows_pos == o.rows_pos; }
+  bool lang_rows = false;    // the language head runs behind the select of every step (greedy session armed by ttasr_session_detect_language)
+  bool operator==(const StepShape& o) const {
+    return kv_div == o.kv_div && identity_pages == o.identity_pages && rows_pos == o.rows_pos && lang_rows == o.lang_rows;
+  }
 };
 struct EncLayerW { float *ln1g, *ln1b, *bqkv, *bo, *ln2g, *ln2b, *b1, *b2; void *wqkv, *wo, *w1, *w2; };
 struct DecLayerW {
@@ -108,6 +111,10 @@ struct ttasr_ctx {
   // language detection (ttasr_detect_language): the span of the tied embedding the pass ends in and its device results -
   // probs [maxB][128] f32, span logits [maxB][128] f32, winners [maxB] i32 (rows packed at n_lang); allocated by the first call
   float* lang_out = nullptr; int lang_begin = 0, lang_n = 0; bool lang_want_logits = false;
+  // ... inside a session (ttasr_session_detect_language): ONE block, allocated by the first armed session - pending flags [maxB],
+  // placeholder slots [maxB], admission table [maxB][2], winners [maxB] (i32), probs [maxB][128], span logits [maxB][128] (f32; rows
+  // packed at n_lang) - and the span and prompt stride the armed sessions' step graphs were captured with
+  int32_t* lang_sess = nullptr; int sess_lang_begin = 0, sess_lang_n = 0, sess_lang_stride = 0;
   StepShape shape;           // the decode shape of the search that is running (SearchScope); the defaults between searches
   int32_t* pairs_dev = nullptr;  // beam search: copy-on-write page pairs
   float* topk_lp = nullptr; int32_t* topk_id = nullptr; int32_t* row_state = nullptr;  // beam search scratch
@@ -324,6 +331,7 @@ int step_graph(ttasr_ctx* c, int B, int mode, int nsteps = 1);
 void sched_detect_rows(ttasr_ctx* c, int B);                  // decode pass of B rows that ends in the language head (mode 3), launched directly
 void drop_graphs(ttasr_ctx* c);
 void drop_rule_graphs(ttasr_ctx* c);
+void drop_lang_graphs(ttasr_ctx* c);                          // the step graphs of armed sessions (StepShape::lang_rows)
 
 // One 30-s window of a recording from frame `seek`: the samples its STFT reads - `lead` before the window (200, fewer at the file
 // start), the window, 200 after, cut at the end of the file - and the geometry launch_mel takes: {lead, reflect_end, valid_frames}.
@@ -363,6 +371,8 @@ struct SearchScope {
     c->shape = StepShape{}; c->st.prompt = nullptr; c->st.prompt_len = nullptr;
     (void)hipMemsetAsync(c->st.done, 0, (size_t)rows * 4, c->stream);
   }
+  // arming a session for language detection changes which kernels its steps hold, not its rows: no other member moves
+  void set_lang_rows(bool on) { c->shape.lang_rows = on; }
   SearchScope(const SearchScope&) = delete; SearchScope& operator=(const SearchScope&) = delete;
 };
 int check_ready(ttasr_ctx* c, int B);

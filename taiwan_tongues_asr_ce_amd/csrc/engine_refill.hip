@@ -26,6 +26,16 @@
 // candidate kernel, with the same one synchronisation.  A ROWS row ends at EOT or at its budget and its group when all its
 // rows have ended; the pick is ttasr_generate_sample's (sample_pick).  Window clips (ttasr_session_submit_windows) carry the
 // samples their window's STFT reads and the geometry of ttasr_log_mel_windows; a pass that holds one runs the mel in window form.
+//
+// Language detection inside the session (ttasr_session_detect_language): an ARMED session takes prompts
+// that hold the placeholder TTASR_TOKEN_DETECT directly behind a <|startoftranscript|> token.  Such a clip's first step after
+// admission is a detect step - <|startoftranscript|> at position 0 against the clip's own cross-KV, an ordinary step of the
+// batch - and behind it lang_head_rows_kernel (kernels_lang.hip) computes the language of the rows whose pending flag is up.
+// Greedy: the flag, the placeholder's slot and the fed token are set on the device at admission, the kernel patches the device
+// prompt and restarts the row itself, and the launch is part of the armed session's step graphs (StepShape::lang_rows).  Beam: the
+// kernel runs behind the logits-only step for the first row of each detecting group, its results come back in the step's one
+// synchronisation, and the host patches the group's prompt and leaves its position at 0.  Either way the clip then decodes as if
+// the language had been given: position 0 of its self-attention pages is simply written again.
 #include "engine_ctx.hpp"
 #include <chrono>
 #include <cmath>
@@ -38,8 +48,11 @@ struct Session {
                 // window clips: pcm = the samples the window's frames read, geom = ttasr_log_mel_windows' geometry, floor = the
                 // ordered dynamic-range maximum (has_floor) ; search: mode (0 BEAM, 1 ROWS), rows, temperature, seed, sot index
                 bool win = false, has_floor = false; int64_t geom[3] = {0, 0, 0}; unsigned floor = 0;
-                int mode = 0, rows = 0; float temp = 0.f; uint32_t seed = 0; int32_t sot = 0; };
-  struct Done { int64_t id; std::vector<int32_t> tok; float lp, ns; };
+                int mode = 0, rows = 0; float temp = 0.f; uint32_t seed = 0; int32_t sot = 0;
+                int det = -1; };   // armed session: the prompt index of the language placeholder, or -1
+  // the language found for a clip inside the session: index into the span (-1: the clip carried no placeholder), softmax, span logits
+  struct Lang { int idx = -1; std::vector<float> probs, logits; };
+  struct Done { int64_t id; std::vector<int32_t> tok; float lp, ns; Lang lang; };
   ttasr_gen_opts o{};
   int max_prompt = 0;
   int64_t next_id = 0;
@@ -52,6 +65,13 @@ struct Session {
   bool enc_pending = false;        // overlapped encode enqueued and not yet seen complete
   std::vector<int64_t> row_clip;   // [maxB] clip id in the row, or -1 (free)
   std::vector<int32_t> row_plen;   // [maxB] prompt length of the row's clip
+  // language detection (ttasr_session_detect_language): the span, and per row (greedy) whether its clip's result is still on the
+  // device (row_det 1) and the result once it is here; pinned block: admission table [maxB][2] | pending flags [maxB] (beam
+  // upload) | winners [maxB] | probs [maxB][128] | logits [maxB][128] (the device block's result part, one copy)
+  bool armed = false; int lang_sot = 0, lang_begin = 0, lang_n = 0;
+  std::vector<char> row_det;
+  std::vector<Lang> row_lang;
+  int32_t* lang_pin = nullptr;
   std::deque<Done> finished;       // finished clips not yet returned by a poll
   // hold mode (ttasr_session_hold): a finished clip keeps its unit - row (greedy) or group (beam) - and its cross-KV slot until
   // ttasr_session_align or ttasr_session_release; its rows are finished rows (done = 1), out of the attention kernels
@@ -70,6 +90,7 @@ struct Session {
   struct Group { int64_t clip = -1; std::vector<int32_t> prompt; int32_t cap = 0; int pos = 0; float ns = 0.f;
                  std::map<std::vector<int>, double> finished;
                  int mode = 0, rows = 0, sot = 0, max_cand = 1; float temp = 0.f; uint32_t seed = 0;
+                 int det = -1; Lang lang;   // det >= 0: the group's next step is its detect step (placeholder at prompt[det])
                  int64_t held = -1; };   // hold mode: the finished clip that still owns the group (clip is -1 then)
   enum { BEAM = 0, ROWS = 1 };
   int beam = 0, G = 0, max_cand = 0;
@@ -94,6 +115,7 @@ void session_free(ttasr_ctx* c) {
   if (S->es && S->es != c->stream) { hipStreamSynchronize(S->es); hipStreamDestroy(S->es); }
   for (hipEvent_t e : {S->ev_enc0, S->ev_enc, S->ev_copy, S->ev_dec0, S->ev_dec1}) if (e) hipEventDestroy(e);
   if (S->pin) hipHostFree(S->pin);
+  if (S->lang_pin) hipHostFree(S->lang_pin);
   delete S;   // with its scope: the context is back to the defaults of a static search
   c->sess = nullptr;
 }
@@ -224,11 +246,12 @@ static int admit(ttasr_ctx* c, Session* S) {
       // the static search's last sampled position is n_text_ctx - 2: a clip never holds more than n_text_ctx - plen tokens
       gr.cap = std::min(cl.cap, c->cfg.n_text_ctx - plen);
       gr.mode = cl.mode; gr.rows = cl.rows; gr.temp = cl.temp; gr.seed = cl.seed; gr.sot = cl.sot;
+      gr.det = cl.det; gr.lang = Session::Lang{};
       gr.max_cand = std::max(1, (int)std::lround(cl.rows * S->patience));
       for (int b = 0; b < S->beam; ++b) {   // rows beyond the clip's `rows` stay finished
         const int r = g * S->beam + b;
         S->seqs[r].clear(); S->sums[r] = 0.0; S->fsums[r] = 0.f;
-        S->row_clip[r] = cl.id; S->cur_tok[r] = gr.prompt[0]; S->done_rows[r] = b < cl.rows ? 0 : 1;
+        S->row_clip[r] = cl.id; S->cur_tok[r] = gr.det >= 0 ? S->lang_sot : gr.prompt[0]; S->done_rows[r] = b < cl.rows ? 0 : 1;
       }
     }
     TRY(flush_quant_pairs(c, qp, nq));
@@ -240,7 +263,7 @@ static int admit(ttasr_ctx* c, Session* S) {
   }
   const int W = 3 + S->max_prompt;
   int32_t* tab = S->pin + (size_t)c->maxB * (4 + c->rp.max_new);
-  int n = 0;
+  int n = 0, n_det = 0;
   for (int r = 0; r < c->maxB && (int)S->staged_next < (int)S->staged.size(); ++r) {
     if (S->row_clip[r] >= 0) continue;
     const int j = (int)S->staged_next++;
@@ -254,12 +277,21 @@ static int admit(ttasr_ctx* c, Session* S) {
     e[0] = r; e[1] = plen; e[2] = std::min(cl.cap, c->cfg.n_text_ctx - plen);
     for (int q = 0; q < S->max_prompt; ++q) e[3 + q] = q < plen ? cl.prompt[q] : 0;
     S->row_clip[r] = cl.id; S->row_plen[r] = plen;
+    if (S->armed) {
+      S->row_det[r] = cl.det >= 0; S->row_lang[r] = Session::Lang{};
+      if (cl.det >= 0) { S->lang_pin[2 * n_det] = r; S->lang_pin[2 * n_det + 1] = cl.det; ++n_det; }
+    }
     ++n;
   }
   TRY(flush_quant_pairs(c, qp, nq));
   if (n > 0) {
     HIPCHK(c, hipMemcpyAsync(c->admit_dev, tab, (size_t)n * W * 4, hipMemcpyHostToDevice, s));
     launch_admit_rows(c->admit_dev, n, c->maxB, S->max_prompt, c->st, c->prompt_dev, c->plen_dev, c->row_cap_dev, c->row_pos, s);
+  }
+  if (n_det > 0) {   // detecting rows: fed <|startoftranscript|> instead of prompt[0], flag and slot for lang_head_rows_kernel
+    int32_t* const ls = c->lang_sess;
+    HIPCHK(c, hipMemcpyAsync(ls + 2 * c->maxB, S->lang_pin, (size_t)n_det * 8, hipMemcpyHostToDevice, s));
+    launch_lang_admit_rows(ls + 2 * c->maxB, n_det, c->maxB, S->lang_sot, ls, ls + c->maxB, c->st.cur_tok, s);
   }
   if (S->staged_next == S->staged.size()) {
     S->staged.clear(); S->staged_next = 0;
@@ -381,6 +413,16 @@ static int session_begin_beam(ttasr_ctx* c, const ttasr_gen_opts* o, int max_pro
   return TTASR_OK;
 }
 
+// the language result of row r from the pinned copy of the device block's result part (winners | probs | logits, rows at n_lang)
+static void session_lang_result(const Session* S, int B, int r, Session::Lang& out) {
+  const int32_t* best = S->lang_pin + 3 * B;
+  const float* probs = (const float*)(best + B) + (size_t)r * S->lang_n;
+  const float* logits = (const float*)(best + B) + (size_t)B * 128 + (size_t)r * S->lang_n;
+  out.idx = std::min(std::max(best[r], 0), S->lang_n - 1);
+  out.probs.assign(probs, probs + S->lang_n);
+  out.logits.assign(logits, logits + S->lang_n);
+}
+
 // One decode position of every live group: copy-on-write, one staged upload, the logits-only step over R rows, the candidate
 // kernel (BEAM groups) and the independent-row kernel (ROWS groups), ONE synchronisation, then selection, re-indexing and the
 // finished groups' results on the host.
@@ -393,12 +435,14 @@ static int beam_step(ttasr_ctx* c, Session* S) {
   // list as soon as no row references it (a finished group drops its rows' lists).
   S->pairs.clear();
   bool any_sampling = false, any_ns = false;
+  int n_detect = 0;   // groups whose step this is the detect step
   for (int g = 0; g < G; ++g) {
     const Session::Group& gr = S->grp[g];
     if (gr.clip < 0) continue;
     for (int b = 0; b < beam; ++b)
       if (!S->pages.make_private(g * beam + b, gr.pos, S->pairs)) return fail(c, TTASR_E_NOMEM, "KV page pool exhausted");
-    if (gr.mode != Session::BEAM) continue;
+    n_detect += gr.det >= 0;
+    if (gr.mode != Session::BEAM || gr.det >= 0) continue;   // a detecting group takes no part in the candidate or no-speech work
     any_sampling |= gr.pos + 1 >= (int)gr.prompt.size();
     any_ns |= o.no_speech >= 0 && gr.pos == gr.sot;
   }
@@ -410,7 +454,7 @@ static int beam_step(ttasr_ctx* c, Session* S) {
   int n_ent = 0;
   for (int g = 0; g < G; ++g) {
     const Session::Group& gr = S->grp[g];
-    if (gr.clip < 0 || gr.mode != Session::ROWS) continue;
+    if (gr.clip < 0 || gr.mode != Session::ROWS || gr.det >= 0) continue;
     const bool past = gr.pos + 1 >= (int)gr.prompt.size(), ns_here = o.no_speech >= 0 && gr.pos == gr.sot;
     for (int b = 0; b < gr.rows; ++b) {
       const int r = g * beam + b;
@@ -451,6 +495,16 @@ static int beam_step(ttasr_ctx* c, Session* S) {
     launch_session_rows_select(c->logits, beam_row_state(c, R), c->rp, sa, n_ent, s);
     HIPCHK(c, hipMemcpyAsync(x.sel, d_out, (size_t)3 * n_ent * 4, hipMemcpyDeviceToHost, s));
   }
+  if (n_detect > 0) {   // the language head for the first row of every detecting group; results back with the step's synchronisation
+    const int B = c->maxB;
+    int32_t* const ls = c->lang_sess;
+    int32_t* const flags = S->lang_pin + 2 * B;
+    for (int r = 0; r < R; ++r) flags[r] = r % beam == 0 && S->grp[r / beam].clip >= 0 && S->grp[r / beam].det >= 0;
+    HIPCHK(c, hipMemcpyAsync(ls, flags, (size_t)R * 4, hipMemcpyHostToDevice, s));
+    const LangRows a{ls, nullptr, nullptr, 0, nullptr, nullptr, ls + 4 * B, (float*)(ls + 5 * B), (float*)(ls + 5 * B) + (size_t)B * 128};
+    TT_DISPATCH(c, launch_lang_head_rows<T>((const T*)c->dh, (const T*)c->emb, R, c->d, c->V, S->lang_begin, S->lang_n, a, s));
+    HIPCHK(c, hipMemcpyAsync(S->lang_pin + 3 * B, ls + 4 * B, (size_t)B * 257 * 4, hipMemcpyDeviceToHost, s));
+  }
   HIPCHK(c, hipEventRecord(S->ev_dec1, s));
   HIPCHK(c, hipStreamSynchronize(s));   // the one synchronisation of the step
   HIPCHK(c, hipGetLastError());
@@ -461,9 +515,9 @@ static int beam_step(ttasr_ctx* c, Session* S) {
   std::vector<char> searching(G, 0);
   for (int g = 0; g < G; ++g) {
     Session::Group& gr = S->grp[g];
-    searching[g] = gr.clip >= 0 && gr.pos + 1 >= (int)gr.prompt.size();
+    searching[g] = gr.clip >= 0 && gr.det < 0 && gr.pos + 1 >= (int)gr.prompt.size();
     const bool beam_search = searching[g] && gr.mode == Session::BEAM;
-    if (gr.clip >= 0 && gr.mode == Session::BEAM && any_ns && gr.pos == gr.sot) gr.ns = x.ns[g * beam];
+    if (gr.clip >= 0 && gr.det < 0 && gr.mode == Session::BEAM && any_ns && gr.pos == gr.sot) gr.ns = x.ns[g * beam];
     int b0 = 0;
     if (beam_search) {
       if (!beam_select(S->seqs, S->sums, g * beam, gr.rows, gr.rows + 1, x.lp, x.id, o.eot, gr.max_cand, gr.finished, nseq, nsum, src, K))
@@ -495,8 +549,15 @@ static int beam_step(ttasr_ctx* c, Session* S) {
     Session::Group& gr = S->grp[g];
     if (gr.clip < 0) continue;
     S->live_row_steps += live_rows[g];
-    gr.pos++;
     const int r0 = g * beam;
+    if (gr.det >= 0) {   // the detect step: the winner's token replaces the placeholder, the group starts over at position 0
+      session_lang_result(S, c->maxB, r0, gr.lang);
+      gr.prompt[gr.det] = S->lang_begin + gr.lang.idx;
+      gr.det = -1;
+      for (int b = 0; b < beam; ++b) S->cur_tok[r0 + b] = S->done_rows[r0 + b] ? o.eot : gr.prompt[0];
+      continue;
+    }
+    gr.pos++;
     bool ended = false;
     if (searching[g] && gr.mode == Session::BEAM) ended = (int)gr.finished.size() >= gr.max_cand || (int)S->seqs[r0].size() >= gr.cap;
     if (searching[g] && gr.mode == Session::ROWS) {
@@ -520,6 +581,7 @@ static int beam_step(ttasr_ctx* c, Session* S) {
         d.lp = S->fsums[r0 + best];
       }
       d.ns = gr.ns;
+      d.lang = std::move(gr.lang);
       S->finished.push_back(std::move(d));
       // the group is free: its page lists go back to the pool, its rows leave the attention kernels
       // (hold mode: the pages go back, the group and its cross-KV slot stay with the clip until it is aligned or released)
@@ -545,7 +607,19 @@ static int beam_step(ttasr_ctx* c, Session* S) {
 static int init_clip(ttasr_ctx* c, const Session* S, int i, const int32_t* prompt, const int32_t* prompt_len, const int32_t* sot,
                      const int32_t* max_new, Session::Clip& cl) {
   const int32_t* row = prompt + (size_t)i * S->max_prompt;
-  TRY(check_prompt(c, i, row, prompt_len[i], S->max_prompt, sot));
+  const int len = prompt_len[i];
+  std::vector<int32_t> checked;   // armed session: the prompt with a valid token in the placeholder's place
+  if (S->armed && len >= 1 && len <= S->max_prompt) {
+    for (int j = 0; j < len; ++j) {
+      if (row[j] != TTASR_TOKEN_DETECT) continue;
+      if (cl.det >= 0) return fail(c, TTASR_E_INVALID, "clip %d: two language placeholders (at %d and %d)", i, cl.det, j);
+      if (j == 0 || row[j - 1] != S->lang_sot)
+        return fail(c, TTASR_E_INVALID, "clip %d: the language placeholder at %d is not directly behind token %d (sot)", i, j, S->lang_sot);
+      cl.det = j;
+    }
+    if (cl.det >= 0) { checked.assign(row, row + len); checked[cl.det] = S->lang_begin; }
+  }
+  TRY(check_prompt(c, i, cl.det >= 0 ? checked.data() : row, len, S->max_prompt, sot));
   if (max_new[i] < 1 || max_new[i] > S->o.max_new_tokens)
     return fail(c, TTASR_E_INVALID, "clip %d: max_new %d outside [1, max_new_tokens=%d]", i, max_new[i], S->o.max_new_tokens);
   cl.prompt.assign(row, row + prompt_len[i]);
@@ -634,8 +708,10 @@ static int run_steps(ttasr_ctx* c, Session* S, int n) {
   return 0;
 }
 
+// ttasr_session_poll and ttasr_session_poll_lang: the plain poll passes no language outputs and drops what was detected
 static int session_poll(ttasr_ctx* c, int max_steps, int cap, int64_t* ids, int32_t* tokens, int32_t* lens, float* sum_lp,
-                        float* no_speech, int32_t* n_out) {
+                        float* no_speech, int32_t* n_out, int32_t* lang = nullptr, float* lang_probs = nullptr,
+                        float* lang_logits = nullptr) {
   if (!c) return TTASR_E_INVALID;
   Session* S = c->sess;
   if (!S) return fail(c, TTASR_E_INVALID, "no session is open (ttasr_session_begin first)");
@@ -676,10 +752,15 @@ static int session_poll(ttasr_ctx* c, int max_steps, int cap, int64_t* ids, int3
     HIPCHK(c, hipMemcpyAsync(p + 2 * B, c->st.sum_logprob, (size_t)B * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(p + 3 * B, c->st.no_speech, (size_t)B * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(p + 4 * B, c->st.out_tokens, (size_t)B * max_new * 4, hipMemcpyDeviceToHost, s));
+    bool lang_back = false;   // rows whose detect step has run since the last exchange: their results ride along
+    for (int r = 0; r < B && S->armed; ++r) lang_back |= S->row_clip[r] >= 0 && S->row_det[r] == 1;
+    if (lang_back) HIPCHK(c, hipMemcpyAsync(S->lang_pin + 3 * B, c->lang_sess + 4 * B, (size_t)B * 257 * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     HIPCHK(c, hipGetLastError());
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, S->ev_dec0, S->ev_dec1) == hipSuccess) S->dec_ms += ms;
+    for (int r = 0; r < B && lang_back; ++r)
+      if (S->row_clip[r] >= 0 && S->row_det[r] == 1) { session_lang_result(S, B, r, S->row_lang[r]); S->row_det[r] = 2; }
     for (int r = 0; r < B; ++r) {
       if (S->row_clip[r] < 0 || !p[r] || S->held[r]) continue;
       Session::Done d;
@@ -688,6 +769,10 @@ static int session_poll(ttasr_ctx* c, int max_steps, int cap, int64_t* ids, int3
       d.tok.assign(p + 4 * B + (size_t)r * max_new, p + 4 * B + (size_t)r * max_new + len);
       memcpy(&d.lp, &p[2 * B + r], 4); memcpy(&d.ns, &p[3 * B + r], 4);
       S->live_row_steps += S->row_plen[r] - 1 + len;
+      if (S->armed) {   // a detected clip ran one more live row-step
+        S->live_row_steps += S->row_det[r] != 0;
+        d.lang = std::move(S->row_lang[r]); S->row_det[r] = 0; S->row_lang[r] = Session::Lang{};
+      }
       S->finished.push_back(std::move(d));
       if (S->hold) S->held[r] = 1; else S->row_clip[r] = -1;
     }
@@ -699,10 +784,41 @@ static int session_poll(ttasr_ctx* c, int max_steps, int cap, int64_t* ids, int3
     memcpy(tokens + (size_t)k * max_new, d.tok.data(), d.tok.size() * 4);
     if (sum_lp) sum_lp[k] = d.lp;
     if (no_speech) no_speech[k] = d.ns;
+    if (lang) lang[k] = d.lang.idx;
+    if (d.lang.idx >= 0 && lang_probs) memcpy(lang_probs + (size_t)k * S->lang_n, d.lang.probs.data(), (size_t)S->lang_n * 4);
+    if (d.lang.idx >= 0 && lang_logits) memcpy(lang_logits + (size_t)k * S->lang_n, d.lang.logits.data(), (size_t)S->lang_n * 4);
     S->finished.pop_front();
     ++k;
   }
   *n_out = k;
+  return TTASR_OK;
+}
+
+// ---- language detection inside the session ----
+
+static int session_detect_language(ttasr_ctx* c, int sot, int lang_begin, int n_lang) {
+  if (!c) return TTASR_E_INVALID;
+  Session* S = c->sess;
+  if (!S) return fail(c, TTASR_E_INVALID, "no session is open (ttasr_session_begin first)");
+  if (S->armed) return fail(c, TTASR_E_INVALID, "the session is armed for language detection already");
+  if (S->next_id > 0) return fail(c, TTASR_E_INVALID, "language detection is armed before the first submit of a session");
+  if (sot < 0 || sot >= c->V) return fail(c, TTASR_E_INVALID, "sot %d outside the vocabulary (%d)", sot, c->V);
+  if (n_lang < 1 || n_lang > 128) return fail(c, TTASR_E_INVALID, "n_lang %d outside [1, 128]", n_lang);
+  if (lang_begin < 0 || lang_begin > c->V - n_lang)
+    return fail(c, TTASR_E_INVALID, "language span [%d, %d) outside the vocabulary (%d)", lang_begin, lang_begin + n_lang, c->V);
+  HIPCHK(c, hipSetDevice(c->device));
+  const int B = c->maxB;
+  if (!c->lang_sess) TRY(dalloc(c, &c->lang_sess, (size_t)B * 261 * 4));
+  if (!S->lang_pin) HIPCHK(c, hipHostMalloc((void**)&S->lang_pin, (size_t)B * 260 * 4));
+  // a session that ended between a clip's admission and its detect step left a flag up
+  HIPCHK(c, hipMemsetAsync(c->lang_sess, 0, (size_t)B * 4, c->stream));
+  if (c->sess_lang_begin != lang_begin || c->sess_lang_n != n_lang || c->sess_lang_stride != S->max_prompt) drop_lang_graphs(c);
+  c->sess_lang_begin = lang_begin; c->sess_lang_n = n_lang; c->sess_lang_stride = S->max_prompt;
+  S->lang_sot = sot; S->lang_begin = lang_begin; S->lang_n = n_lang;
+  S->row_det.assign(B, 0); S->row_lang.assign(B, Session::Lang{});
+  // greedy: the head is part of every step from here on (its graphs are keyed on the flag); beam: launched by beam_step
+  if (!S->beam) S->scope->set_lang_rows(true);
+  S->armed = true;
   return TTASR_OK;
 }
 
@@ -833,6 +949,18 @@ int ttasr_session_submit_windows(ttasr_ctx* c, int32_t n, const float* const* fi
 int ttasr_session_poll(ttasr_ctx* c, int32_t max_steps, int32_t cap, int64_t* ids, int32_t* tokens, int32_t* lens, float* sum_lp,
                        float* no_speech, int32_t* n_out) {
   return guarded(c, [&]() -> int { return session_poll(c, max_steps, cap, ids, tokens, lens, sum_lp, no_speech, n_out); });
+}
+
+int ttasr_session_poll_lang(ttasr_ctx* c, int32_t max_steps, int32_t cap, int64_t* ids, int32_t* tokens, int32_t* lens, float* sum_lp,
+                            float* no_speech, int32_t* lang, float* lang_probs, float* lang_logits, int32_t* n_out) {
+  return guarded(c, [&]() -> int {
+    if (c && c->sess && !lang) return fail(c, TTASR_E_INVALID, "lang is NULL");
+    return session_poll(c, max_steps, cap, ids, tokens, lens, sum_lp, no_speech, n_out, lang, lang_probs, lang_logits);
+  });
+}
+
+int ttasr_session_detect_language(ttasr_ctx* c, int32_t sot, int32_t lang_begin, int32_t n_lang) {
+  return guarded(c, [&]() -> int { return session_detect_language(c, sot, lang_begin, n_lang); });
 }
 
 int ttasr_session_stats(ttasr_ctx* c, double out[8]) {

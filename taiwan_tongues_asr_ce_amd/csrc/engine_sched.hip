@@ -338,6 +338,16 @@ void run_decode_rows(ttasr_ctx* c, int row0, int n, int mode, int total_rows) {
     if (st.prompt) { st.prompt += (size_t)row0 * c->rp.max_prompt; st.prompt_len += row0; }
     if (rows_pos) { st.step = c->row_pos + row0; launch_select_rows(logits, st, c->rp, n, s); }
     else launch_select(logits, st, c->rp, n, nullptr, s, c->st.step + 1, total_rows);
+    if (rows_pos && sh.lang_rows && mode == 0) {
+      // armed session: the rows that were admitted with the language placeholder have just run <|startoftranscript|> at position
+      // 0; the head overwrites what select did to them (forced prompt rows: fed token and position) and restarts them
+      int32_t* const ls = c->lang_sess + row0;
+      const int B = c->maxB;
+      const LangRows a{ls, ls + B, c->prompt_dev + (size_t)row0 * c->sess_lang_stride, c->sess_lang_stride, c->st.cur_tok + row0, c->row_pos + row0,
+                       ls + 4 * B, (float*)(c->lang_sess + 5 * B) + (size_t)row0 * c->sess_lang_n,
+                       (float*)(c->lang_sess + 5 * B) + (size_t)B * 128 + (size_t)row0 * c->sess_lang_n};
+      launch_lang_head_rows<T>((const T*)dh, (const T*)c->emb, n, d, c->V, c->sess_lang_begin, c->sess_lang_n, a, s);
+    }
   }
 }
 
@@ -525,6 +535,16 @@ void drop_rule_graphs(ttasr_ctx* c) {
   size_t k = 0;
   for (auto& g : c->graphs) {
     if (g.key.mode == 1) c->graphs[k++] = g; else hipGraphExecDestroy(g.exec);
+  }
+  c->graphs.resize(k);
+}
+
+// The span and the prompt stride are baked into the language-head launch of an armed session's graphs: a session armed with
+// other values captures its own.
+void drop_lang_graphs(ttasr_ctx* c) {
+  size_t k = 0;
+  for (auto& g : c->graphs) {
+    if (!g.key.shape.lang_rows) c->graphs[k++] = g; else hipGraphExecDestroy(g.exec);
   }
   c->graphs.resize(k);
 }

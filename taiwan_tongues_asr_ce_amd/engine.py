@@ -244,14 +244,19 @@ class Engine:
         return GenResult([toks[b, :lens[b]].tolist() for b in range(B)], lp, ns)
 
     def session(self, opts, max_prompt: int, temperature: float = 0.0, beam: int = 1,
-                patience: Optional[float] = None) -> "Session":
+                patience: Optional[float] = None, detect_language=False) -> "Session":
         """Continuous-batching session (ttasr_session_*): greedy, single-window decoding of clips submitted at any time; each clip
         takes a free row of the max_batch-row decode batch and hands it to the next queued clip when it finishes.  A context
         manager: the session ends when the block is left.  While it is open the engine's other search / encode calls are refused.
 
         beam > 1, or beam given together with a patience (default 1.0): beam search (ttasr_session_begin_beam); a clip takes a
-        group of `beam` rows, and its result equals ttasr_generate_beam's (tokens without EOT)."""
-        return Session(self, opts, max_prompt, temperature, beam, patience)
+        group of `beam` rows, and its result equals ttasr_generate_beam's (tokens without EOT).
+
+        detect_language=True, or (sot, first language token, count): the session is armed for language identification
+        (ttasr_session_detect_language; True = this engine's <|startoftranscript|> and language_span()).  A prompt may then hold
+        Session.DETECT directly behind <|startoftranscript|>: the clip's first step finds its language on the device and writes
+        it over the placeholder; SessionResult.language / language_probs carry the answer."""
+        return Session(self, opts, max_prompt, temperature, beam, patience, detect_language)
 
     def generate_beam(self, prompts: Sequence[Sequence[int]], beam: int, opts, patience: float = 1.0,
                       sot_index: Optional[Sequence[int]] = None) -> GenResult:
@@ -486,19 +491,25 @@ class SessionResult:
     tokens: List[int]
     sum_logprob: float
     no_speech_prob: float
+    language: Optional[int] = None               # index into the session's language span; None: the clip carried no placeholder
+    language_probs: Optional[np.ndarray] = None  # float32 [n_lang] softmax over the span
+    language_logits: Optional[np.ndarray] = None # float32 [n_lang] raw span logits
 
 
 class Session:
     """Engine.session(): submit(clips, prompts, max_new) -> clip ids; poll() -> finished clips (SessionResult, any order)."""
 
+    DETECT = -1   # TTASR_TOKEN_DETECT: the language placeholder of an armed session's prompts
+
     def __init__(self, engine: Engine, opts, max_prompt: int, temperature: float = 0.0, beam: int = 1,
-                 patience: Optional[float] = None):
+                 patience: Optional[float] = None, detect_language=False):
         self.engine, self.opts, self.max_prompt = engine, opts, int(max_prompt)
         self.max_new_tokens = int(opts.max_new_tokens)
         self.window = 2 * engine.audio_ctx * 160
         self.open = False
         self.holding = False
         self.pending = 0
+        self.lang_span: Optional[Tuple[int, int, int]] = None   # (sot, first language token, count) once armed
         beam = int(beam)
         if not 1 <= beam <= 7:
             raise ValueError(f"beam {beam} outside [1, 7]")
@@ -517,6 +528,20 @@ class Session:
             engine._check(engine.lib.ttasr_session_begin(engine.h, C.byref(opts), self.max_prompt, C.c_float(temperature)),
                           "session_begin")
         self.open = True
+        if detect_language:   # armed before the first submit; a refusal closes the session again
+            try:
+                if detect_language is True:
+                    span = (engine.special.sot,) + tuple(engine.language_span())
+                else:
+                    span = tuple(int(v) for v in detect_language)
+                    if len(span) != 3:
+                        raise ValueError("detect_language is True or (sot, first language token, count)")
+                engine._check(engine.lib.ttasr_session_detect_language(engine.h, span[0], span[1], span[2]),
+                              "session_detect_language")
+                self.lang_span = span
+            except Exception:
+                self.close()
+                raise
 
     def __enter__(self) -> "Session":
         return self
@@ -638,9 +663,10 @@ class Session:
         self.pending += n
         return ids.tolist()
 
-    def poll(self, max_steps: int = 1 << 30, cap: Optional[int] = None) -> List[SessionResult]:
+    def poll(self, max_steps: int = 1 << 30, cap: Optional[int] = None, with_language: bool = True) -> List[SessionResult]:
         """Admit ready clips, decode until at least one clip finished (or nothing is left, or max_steps steps ran); returns the
-        finished clips (at most `cap`, default max_batch)."""
+        finished clips (at most `cap`, default max_batch).  An armed session returns each clip's language too
+        (ttasr_session_poll_lang); with_language=False takes the plain poll, which drops it."""
         if not self.open:
             raise TtasrError("session is closed")
         cap = self.engine.max_batch if cap is None else int(cap)
@@ -653,6 +679,21 @@ class Session:
         nsp = np.zeros(cap, dtype=np.float32)
         n_out = C.c_int32(0)
         i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        if self.lang_span is not None and with_language:   # only an armed session calls the entry point that returns languages
+            n_lang = self.lang_span[2]
+            lang = np.full(cap, -1, dtype=np.int32)
+            probs = np.zeros((cap, n_lang), dtype=np.float32)
+            logits = np.zeros((cap, n_lang), dtype=np.float32)
+            self.engine._check(self.engine.lib.ttasr_session_poll_lang(
+                self.engine.h, int(min(max_steps, 2**31 - 1)), cap, ids.ctypes.data_as(C.POINTER(C.c_int64)),
+                toks.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), lp.ctypes.data_as(f32p), nsp.ctypes.data_as(f32p),
+                lang.ctypes.data_as(i32p), probs.ctypes.data_as(f32p), logits.ctypes.data_as(f32p), C.byref(n_out)),
+                "session_poll_lang")
+            k = n_out.value
+            self.pending -= k
+            return [SessionResult(int(ids[i]), toks[i, :lens[i]].tolist(), float(lp[i]), float(nsp[i]),
+                                  int(lang[i]) if lang[i] >= 0 else None, probs[i].copy() if lang[i] >= 0 else None,
+                                  logits[i].copy() if lang[i] >= 0 else None) for i in range(k)]
         self.engine._check(self.engine.lib.ttasr_session_poll(
             self.engine.h, int(min(max_steps, 2**31 - 1)), cap, ids.ctypes.data_as(C.POINTER(C.c_int64)), toks.ctypes.data_as(i32p),
             lens.ctypes.data_as(i32p), lp.ctypes.data_as(f32p), nsp.ctypes.data_as(f32p), C.byref(n_out)), "session_poll")

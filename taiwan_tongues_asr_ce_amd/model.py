@@ -56,6 +56,8 @@ class TranscriptionInfo:
     all_language_probs: Optional[List[Tuple[str, float]]] = None
     transcription_options: Dict = field(default_factory=dict)
     vad_options: Optional[Dict] = None
+    # transcribe_many(continuous=True, multilingual=True): the language found for every window that was decoded, in file order
+    window_languages: Optional[List[str]] = None
 
 
 _COMPUTE_ALIASES = {
@@ -803,7 +805,8 @@ class WhisperModel:
                         suppress_blank: bool = True, temperature: Union[float, Sequence[float]] = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0),
                         best_of: int = 5, compression_ratio_threshold: Optional[float] = 2.4, patience: float = 1.0,
                         hotwords: Optional[str] = None, prefix: Optional[str] = None, continuous: bool = False,
-                        multilingual: bool = False) -> List[Tuple[List[Segment], TranscriptionInfo]]:
+                        multilingual: bool = False, detect_in_session: bool = False
+                        ) -> List[Tuple[List[Segment], TranscriptionInfo]]:
         """Several FILES in lock step: every round takes the next 30-s window of each unfinished file and runs them as
         ONE engine pass (log-mel, encoder, beam search with one previous-text prompt per file), so a folder is
         transcribed at batch throughput while each file keeps exactly the sequential algorithm of `transcribe` — its
@@ -821,12 +824,18 @@ class WhisperModel:
         The None files are detected from their first windows in batched passes BEFORE decoding starts - with continuous=True
         before the session begins, which costs one extra encoder pass over those first windows (a session owns the encoder
         while it is open).  Each file's TranscriptionInfo carries its own language, probability and all_language_probs.
-        multilingual=True (lock-step form only): every window is detected again between its encoder pass and its search, from
-        the encoder state that is resident anyway, and its prompt carries that window's language token."""
+        detect_in_session=True (continuous=True only): no pass before the session - a None file's first window goes in with the
+        language placeholder (Session.DETECT), its first decode step finds the language on the device, and that answer fills the
+        file's TranscriptionInfo and the prompts of its later windows; a fallback attempt carries the language already found.
+        multilingual=True: every window is detected again - lock-step form: between its encoder pass and its search, from the
+        encoder state that is resident anyway; continuous=True: inside the session, every window goes in with the placeholder -
+        and its prompt carries that window's language token (info.window_languages lists them); info.language stays the
+        file-level answer."""
         eng = self.engine
-        if continuous and multilingual:
-            raise ValueError("multilingual=True is not supported with continuous=True (per-window detection inside a session "
-                             "is not implemented)")
+        if continuous and not callable(getattr(eng, "session", None)):
+            raise ValueError("continuous=True needs an engine with continuous-batching sessions (Engine.session)")
+        if detect_in_session and not continuous:
+            raise ValueError("detect_in_session=True needs continuous=True (the lock-step form detects from its resident passes)")
         if continuous and word_timestamps:
             raise ValueError("word_timestamps=True is not supported with continuous=True (the alignment pass needs the window's "
                              "encoder state, which the session hands to the next window)")
@@ -848,12 +857,15 @@ class WhisperModel:
             fs["segments"] = []
             fs["file_max"] = self._file_feature_max(fs["audio"])   # whole-file dynamic-range floor, as `transcribe`
             files.append(fs)
-        found = self._resolve_languages(langs, [fs["audio"] for fs in files], "file")
-        for fs, (lang, lang_p, all_p) in zip(files, found):
-            fs["language"], fs["lang_tok"], fs["lang_info"] = lang, self._lang_token(lang), (lang, lang_p, all_p)
         multilingual = bool(multilingual) and self.is_multilingual
+        # files whose language the session itself finds: they skip the detection pass; "decided" = the file-level answer is known
+        late = [l is None and bool(detect_in_session) and self.is_multilingual for l in langs]
+        found = self._resolve_languages(["en" if w else l for l, w in zip(langs, late)], [fs["audio"] for fs in files], "file")
+        for fs, (lang, lang_p, all_p), w in zip(files, found, late):
+            fs["language"], fs["lang_tok"], fs["lang_info"] = lang, self._lang_token(lang), (lang, lang_p, all_p)
+            fs["decided"] = not w
         if continuous:
-            self._run_continuous(files, p)
+            self._run_continuous(files, p, per_window=multilingual)
         while not continuous:
             active = [fs for fs in files if fs["seek"] < fs["n_total"]]
             if not active:
@@ -898,15 +910,23 @@ class WhisperModel:
                                      all_language_probs=all_p,
                                      transcription_options=dict(beam_size=beam, task=task, without_timestamps=without_timestamps,
                                                                 condition_on_previous_text=condition_on_previous_text,
-                                                                initial_prompt=initial_prompt))
+                                                                initial_prompt=initial_prompt),
+                                     window_languages=fs.get("window_languages"))
             out.append((fs["segments"], info))
         return out
 
-    def _run_continuous(self, files: List[dict], p: dict):
+    def _session_language(self, r) -> Tuple[str, float, List[Tuple[str, float]]]:
+        """(language, probability, all probabilities) of a SessionResult that was detected inside its session."""
+        return LANGUAGES[r.language], float(r.language_probs[r.language]), self._ranked(r.language_probs)
+
+    def _run_continuous(self, files: List[dict], p: dict, per_window: bool = False):
         """transcribe_many(continuous=True): the windows of all files through one beam session, one window per file in flight.
         A window's attempts follow `_decode_with_fallback` (temperature 0: beam search of beam_size rows, or greedy with one;
-        temperature > 0: best_of samples seeded as `transcribe` seeds them), its result `_finish_window`."""
-        from .engine import GenResult, TtasrError
+        temperature > 0: best_of samples seeded as `transcribe` seeds them), its result `_finish_window`.
+        A window of a file whose language is not decided yet (fs["decided"] False: detect_in_session), and with per_window
+        (multilingual) every window, goes in with the language placeholder; the session's answer replaces it in the window's
+        prompt, so a fallback attempt carries the language already found."""
+        from .engine import GenResult, Session, TtasrError
         eng = self.engine
         temps, beam = p["temperatures"], p["beam_size"]
         if not 1 <= beam <= 7:
@@ -923,7 +943,9 @@ class WhisperModel:
         n_ctx = self.dims.n_text_ctx
         opts = self._window_opts(1, 0, p)   # the session's rules; budgets and sot indices are per window
         eng.set_audio_ctx(0)
-        with eng.session(opts, n_ctx - 1, beam=width, patience=p["patience"]) as s:
+        arm = per_window or any(not fs["decided"] for fs in todo)
+        kw = dict(detect_language=True) if arm else {}   # armed only when a window asks for it
+        with eng.session(opts, n_ctx - 1, beam=width, patience=p["patience"], **kw) as s:
             inflight: Dict[int, dict] = {}
 
             def submit(fs: dict):
@@ -935,8 +957,9 @@ class WhisperModel:
                 inflight[ids[0]] = fs
 
             def next_window(fs: dict):
-                pr, si = self._prompt(fs.get("lang_tok", p["lang_tok"]), p["task"], p["without_timestamps"], fs["prev"][fs["prompt_reset"]:],
-                                      p["hotwords_tokens"], p["prefix_tokens"] if fs["seek"] == 0 else None)
+                detect = per_window or not fs["decided"]
+                pr, si = self._prompt(Session.DETECT if detect else fs.get("lang_tok", p["lang_tok"]), p["task"], p["without_timestamps"],
+                                      fs["prev"][fs["prompt_reset"]:], p["hotwords_tokens"], p["prefix_tokens"] if fs["seek"] == 0 else None)
                 fs["window"] = dict(prompt=pr, sot=si, budget=min(p["max_new"], n_ctx - len(pr)), attempts=[],
                                     frames=min(self.dims.n_frames, fs["n_total"] - fs["seek"]))
                 submit(fs)
@@ -950,6 +973,14 @@ class WhisperModel:
                 for r in got:
                     fs = inflight.pop(r.id)
                     w = fs["window"]
+                    if r.language is not None:   # detected inside the session: this window's language, and the file's if undecided
+                        found = self._session_language(r)
+                        fs["language"], fs["lang_tok"] = found[0], self._lang_token(found[0])
+                        w["prompt"][w["sot"] + 1] = fs["lang_tok"]
+                        if not fs["decided"]:
+                            fs["lang_info"], fs["decided"] = found, True
+                        if per_window:
+                            fs.setdefault("window_languages", []).append(found[0])
                     temp = temps[len(w["attempts"])]
                     res = GenResult([r.tokens], np.asarray([r.sum_logprob], np.float32), np.asarray([r.no_speech_prob], np.float32))
                     toks, avg_lp, ns, cr = self._score(res, 0)
@@ -1004,7 +1035,7 @@ class WhisperModel:
                           task: str = "transcribe",
                           without_timestamps: bool = True, max_new_tokens: int = 224,
                           row_max_new: Optional[Sequence[int]] = None, beam_size: int = 1, patience: float = 1.0,
-                          initial_prompt: Optional[str] = None, word_timestamps: bool = False):
+                          initial_prompt: Optional[str] = None, word_timestamps: bool = False, detect_in_session: bool = False):
         """transcribe_batch's contract (clips <= 30 s each, sampled token ids per clip, input order) for any number of clips,
         through a continuous-batching session: a clip that finishes hands its decode row to the next one instead of waiting for
         the rest of its batch.  row_max_new (optional): one token budget per clip, each in [1, max_new_tokens].
@@ -1014,7 +1045,10 @@ class WhisperModel:
         (a finished clip keeps its row and cross-KV slot) and the clips one poll returned are aligned in one device pass.
         language: one code, None (detect every clip) or one entry per clip (a code or None).  None clips are detected in batched
         passes BEFORE the session begins (a session owns the encoder while it is open): one extra encoder pass over those
-        clips.  (language, probability) per clip of the last call: `last_language_info`."""
+        clips.  detect_in_session=True: no pass before the session - a None clip goes in with the language placeholder
+        (Session.DETECT) and its first decode step finds the language on the device (one more decode step, no encoder work).
+        (language, probability) per clip of the last call: `last_language_info`."""
+        from .engine import Session
         if len(clips) == 0:
             self.last_language_info = []
             return []
@@ -1025,11 +1059,15 @@ class WhisperModel:
         for c in clips:
             if len(c) > self.n_window:
                 raise ValueError(f"transcribe_stream takes clips of at most one window ({self.n_window} samples)")
-        found = self._resolve_languages(language, clips, "clip")
-        self.last_language_info = [(f[0], f[1]) for f in found]
+        langs = self._check_languages(language, len(clips), "clip")
+        late = [l is None and bool(detect_in_session) and self.is_multilingual for l in langs]   # found by the session itself
+        found = self._resolve_languages(["en" if w else l for l, w in zip(langs, late)], clips, "clip")
+        info = [(f[0], f[1]) for f in found]
+        self.last_language_info = info
         clip_lang = [f[0] for f in found]
         prev = self.tokenizer.encode(" " + initial_prompt.strip()) if initial_prompt else []
-        prompts = [self._prompt(self._lang_token(l), task, without_timestamps, prev)[0] for l in clip_lang]
+        prompts = [self._prompt(Session.DETECT if w else self._lang_token(l), task, without_timestamps, prev)[0]
+                   for l, w in zip(clip_lang, late)]
         prompt, sot_index = self._prompt(self._lang_token(clip_lang[0]), task, without_timestamps, prev)
         n_new = min(max_new_tokens, self.dims.n_text_ctx - len(prompt))
         caps = None
@@ -1040,11 +1078,20 @@ class WhisperModel:
         eng.set_audio_ctx(0)
         opts = eng.gen_opts(n_new, timestamps=not without_timestamps, sot_index=sot_index)
         out: List[Optional[List[int]]] = [None] * len(clips)
-        with (eng.session(opts, len(prompt), beam=beam, patience=patience) if beam > 1 else eng.session(opts, len(prompt))) as s:
+        kw = dict(detect_language=True) if any(late) else {}   # armed only when a clip asks for it
+        with (eng.session(opts, len(prompt), beam=beam, patience=patience, **kw) if beam > 1 else eng.session(opts, len(prompt), **kw)) as s:
             ids = s.submit([np.ascontiguousarray(c, dtype=np.float32) for c in clips], prompts, caps)
             where = {cid: i for i, cid in enumerate(ids)}
+
+            def note_languages(got):
+                for r in got:
+                    if r.language is not None:
+                        lang, prob, _ = self._session_language(r)
+                        clip_lang[where[r.id]], info[where[r.id]] = lang, (lang, prob)
             if not word_timestamps:
-                for r in s.drain():
+                got = s.drain()
+                note_languages(got)
+                for r in got:
                     out[where[r.id]] = r.tokens
                 return out  # type: ignore[return-value]
             s.hold()
@@ -1052,6 +1099,7 @@ class WhisperModel:
                 got = s.poll()
                 if not got:
                     raise RuntimeError(f"session idle with {s.pending} clips unfinished")
+                note_languages(got)
                 for lang in sorted({clip_lang[where[r.id]] for r in got}):   # one alignment pass per language of the poll
                     grp = [r for r in got if clip_lang[where[r.id]] == lang]
                     words = self._window_words(s, [r.id for r in grp], [r.tokens for r in grp],

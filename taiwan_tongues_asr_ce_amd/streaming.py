@@ -56,19 +56,23 @@ class BatchedWhisperASR(MI355XWhisperASR):
 
     `language` (default "zh", the reference's forced language): None detects every utterance from its pass's encoder state
     (WhisperModel.transcribe_windows(language=None)) and reports the detected language and probability instead of "zh" and
-    1.0, with a warning when the probability is under 0.5 as the reference's adapter logs it.  Lock-step mode only: a
-    continuous session owns the encoder while it is open, and per-request detection inside it is not implemented."""
+    1.0, with a warning when the probability is under 0.5 as the reference's adapter logs it.  In continuous mode None needs
+    `detect_in_session=True` (opt-in): a session owns the encoder while it is open, so every request goes in with the language
+    placeholder and its first decode step finds the language on the device (Engine.session(detect_language=True))."""
 
     def __init__(self, max_clips: int = 6, max_wait_ms: float = 5.0, audio_ctx=None, max_new_tokens: int = 224,
-                 continuous: bool = False, word_timestamps: bool = False, **kwargs):
+                 continuous: bool = False, word_timestamps: bool = False, detect_in_session: bool = False, **kwargs):
         if continuous and audio_ctx is not None:
             raise ValueError("continuous=True encodes the full window: audio_ctx must be None")
         self.continuous = bool(continuous)
         self.word_timestamps = bool(word_timestamps)
         beam = int(kwargs.pop("beam_size", 5))
         self.language = kwargs.pop("language", "zh")
-        if continuous and self.language is None:
-            raise ValueError("language=None needs the lock-step mode (continuous=False): detection inside a session is not implemented")
+        self.detect_in_session = bool(detect_in_session)
+        if self.detect_in_session and not (continuous and self.language is None):
+            raise ValueError("detect_in_session=True is for continuous=True with language=None")
+        if continuous and self.language is None and not self.detect_in_session:
+            raise ValueError("language=None in continuous mode needs detect_in_session=True (or the lock-step mode, continuous=False)")
         self.audio_ctx = audio_ctx            # None = Whisper's 30-s window; "auto"/int = opt-in short window (N2)
         self.max_new_tokens = max_new_tokens
         kwargs.setdefault("max_batch", max(8, max_clips * beam))
@@ -139,7 +143,10 @@ class BatchedWhisperASR(MI355XWhisperASR):
         eng, kw = model.engine, self.default_transcribe_kwargs
         beam = max(1, min(int(kw["beam_size"]), 7))
         prev = model.tokenizer.encode(" " + kw["initial_prompt"].strip()) if kw.get("initial_prompt") else []
-        prompt, sot_index = model._prompt(model._lang_token("zh"), "transcribe", False, prev)
+        from .engine import Session
+        detect = self.language is None and model.is_multilingual
+        fixed = "zh"   # what the session decodes with when nothing is detected (the reference's forced language)
+        prompt, sot_index = model._prompt(Session.DETECT if detect else model._lang_token(fixed), "transcribe", False, prev)
         pending: Dict[int, Tuple[np.ndarray, float, Any, Any]] = {}
 
         def resolve(fut, loop, value):
@@ -148,7 +155,8 @@ class BatchedWhisperASR(MI355XWhisperASR):
         try:
             eng.set_audio_ctx(0)
             opts = eng.gen_opts(min(self.max_new_tokens, model.dims.n_text_ctx - len(prompt)), timestamps=True, sot_index=sot_index)
-            with (eng.session(opts, len(prompt), beam=beam) if beam > 1 else eng.session(opts, len(prompt))) as s:
+            kw_s = dict(detect_language=True) if detect else {}
+            with (eng.session(opts, len(prompt), beam=beam, **kw_s) if beam > 1 else eng.session(opts, len(prompt), **kw_s)) as s:
                 if self.word_timestamps:
                     s.hold()
                 while True:
@@ -168,12 +176,17 @@ class BatchedWhisperASR(MI355XWhisperASR):
                         pending[s.submit([a], [prompt])[0]] = (audio, last_start, fut, loop)
                     got = s.poll(max_steps=1 if beam > 1 else 8)
                     sizes = [min(len(pending[r.id][0]), model.n_window) for r in got]
-                    words = (model._window_words(s, [r.id for r in got], [r.tokens for r in got], sizes, "zh", model._lang_token("zh"))
-                             if self.word_timestamps and got else [None] * len(got))
-                    for r, n, w in zip(got, sizes, words):
+                    langs = [model._session_language(r)[:2] if r.language is not None else (fixed, 1.0) for r in got]
+                    words: List[Any] = [None] * len(got)
+                    for lang in sorted({l for l, _ in langs}) if self.word_timestamps else ():   # one alignment pass per language
+                        k = [i for i, (l, _) in enumerate(langs) if l == lang]
+                        for i, w in zip(k, model._window_words(s, [got[i].id for i in k], [got[i].tokens for i in k],
+                                                               [sizes[i] for i in k], lang, model._lang_token(lang))):
+                            words[i] = w
+                    for r, n, w, lang in zip(got, sizes, words, langs):
                         audio, last_start, fut, loop = pending.pop(r.id)
                         res = model.window_text(r.tokens, n) + ((w,) if w is not None else ())
-                        resolve(fut, loop, self._result_dict(_window_result(audio, *res), last_start))
+                        resolve(fut, loop, self._result_dict(_window_result(audio, *res), last_start, lang))
         except Exception as e:  # the reference logs and returns None per request
             logger.error("continuous transcribe failed: %s", e)
         finally:

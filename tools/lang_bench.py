@@ -10,6 +10,19 @@ after a warm-up of both; median, minimum and maximum are reported, together with
 the two paths and whether the winners agree.  No threshold is asserted.  One JSON object on stdout and, with --out, in that file.
 
     python tools/lang_bench.py [--model large-v3] [--clips 32] [--repeats 50] [--out profiles/lang_detect.json]
+
+--session: language=None through a continuous-batching session.  64 clips (--session-clips) through 32 rows (--clips), seeded
+token budgets 32 ... 128, check_interval 8:
+  (before)  detection before the session - static passes of 32 clips (log-mel, encoder, Engine.detect_language), then an unarmed
+            session whose prompts carry the languages found (what transcribe_stream(language=None) does by default);
+  (inside)  an armed session (Engine.session(detect_language=True)) whose prompts carry the placeholder: one more decode step
+            per clip, no encoder pass beforehand;
+  (given)   the unarmed session alone with the languages given: what a session cost before detection existed, to be set beside
+            tools/refill_bench.py of the previous revision.
+The three are wall times around whole runs, taken alternately over --repeats rounds after a warm-up of each; median, minimum and
+maximum are reported, with whether (inside) returns (before)'s languages and tokens.  Nothing is asserted.
+
+    python tools/lang_bench.py --session [--repeats 5] [--out profiles/lang_detect_session.json]
 """
 from __future__ import annotations
 
@@ -43,7 +56,11 @@ def main():
     ap.add_argument("--clips", type=int, default=32)
     ap.add_argument("--repeats", type=int, default=50)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--session", action="store_true", help="detection before a session against detection inside it")
+    ap.add_argument("--session-clips", type=int, default=64)
     args = ap.parse_args()
+    if args.session:
+        return main_session(args)
     dims = PRESETS[args.model]
     B = args.clips
     eng = Engine(dims, {"f32": COMPUTE_F32, "bf16": COMPUTE_BF16, "f16": COMPUTE_F16}[args.compute], B)
@@ -83,6 +100,75 @@ def main():
         with open(args.out, "w") as f:
             json.dump(out, f, indent=1)
             f.write("\n")
+
+
+def main_session(args):
+    from taiwan_tongues_asr_ce_amd.engine import Session
+    dims = PRESETS[args.model]
+    B, N = args.clips, args.session_clips
+    eng = Engine(dims, {"f32": COMPUTE_F32, "bf16": COMPUTE_BF16, "f16": COMPUTE_F16}[args.compute], B)
+    eng.load_weights(synth.iter_weights(dims))
+    st = eng.special
+    begin, n_lang = eng.language_span()
+    tail = [st.transcribe, st.no_timestamps]
+    opts = eng.gen_opts(128, timestamps=False, suppress_eot=True, check_interval=8)
+    clips = [KINDS[i % 4](i) for i in range(N)]
+    caps = np.random.Generator(np.random.Philox(key=6)).integers(32, 129, size=N).astype(np.int32)
+
+    def run_session(prompts, armed):
+        langs, toks = [None] * N, [None] * N
+        with eng.session(opts, 4, detect_language=armed) as s:
+            ids = s.submit(clips, prompts, caps)
+            where = {cid: i for i, cid in enumerate(ids)}
+            for r in s.drain():
+                langs[where[r.id]], toks[where[r.id]] = r.language, r.tokens
+            stats = s.stats()
+        return langs, toks, stats
+
+    def before():
+        langs = []
+        for i in range(0, N, B):
+            chunk = clips[i:i + B]
+            eng.log_mel(chunk, want_output=False)
+            eng.encode(len(chunk))
+            langs += eng.detect_language(len(chunk))[0].tolist()
+        _, toks, stats = run_session([[st.sot, begin + l] + tail for l in langs], False)
+        return langs, toks, stats
+
+    def inside():
+        return run_session([[st.sot, Session.DETECT] + tail] * N, True)
+
+    found = before()[0]                      # warm-up of every path: graph captures, first-touch allocations
+    inside()
+
+    def given():
+        return run_session([[st.sot, begin + l] + tail for l in found], False)
+    given()
+    t = {"before": [], "inside": [], "given": []}
+    last = {}
+    for _ in range(args.repeats):            # alternating, so that drift and neighbours hit all three alike
+        for name, fn in (("before", before), ("inside", inside), ("given", given)):
+            t0 = time.perf_counter()
+            last[name] = fn()
+            t[name].append((time.perf_counter() - t0) * 1e3)
+    med = {k: statistics.median(v) for k, v in t.items()}
+    out = {"bench": "lang_detect_session", "model": args.model, "compute": args.compute, "rows": B, "clips": N, "n_lang": n_lang,
+           "detect_before_session_ms": spread(t["before"]), "detect_inside_session_ms": spread(t["inside"]),
+           "unarmed_session_languages_given_ms": spread(t["given"]),
+           "saving_ms_per_clip": round((med["before"] - med["inside"]) / N, 3),
+           "inside_over_given": round(med["inside"] / med["given"], 4),
+           "decode_steps": {k: int(last[k][2]["steps"]) for k in last},
+           "encode_ms_session": {k: round(last[k][2]["encode_ms"], 1) for k in last},
+           "languages_equal": last["inside"][0] == last["before"][0], "tokens_equal": last["inside"][1] == last["before"][1],
+           "method": "host wall time around whole runs (every run ends in the session's last synchronise); each path warmed, "
+                     "then alternated"}
+    print(json.dumps(out), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+    eng.close()
 
 
 if __name__ == "__main__":
