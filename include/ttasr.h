@@ -332,6 +332,44 @@ TTASR_API int ttasr_session_poll_lang(ttasr_ctx* ctx, int32_t max_steps, int32_t
                                       float* sum_lp, float* no_speech, int32_t* lang, float* lang_probs, float* lang_logits,
                                       int32_t* n_out);
 
+/* ---- prompt prefill at admission (option "session_prefill", default 0 = off) ------------------------------------------
+ * By default a session forces every prompt token through an ordinary decode step of max_batch rows.  With
+ * ttasr_set_option(ctx, "session_prefill", N), N in [1, n_text_ctx - 2], set BEFORE ttasr_session_begin[_beam] (which reads it,
+ * like "refill_overlap"), a clip's leading prompt positions are computed in one ADMISSION PASS instead - the decoder layers over
+ * the packed prompt rows of the clips admitted together, enqueued on the decode stream between two steps, behind the clips'
+ * cross-KV copies.
+ * The rule, per clip, decided at admission from the clip's own prompt only: let p = prompt_len - 1; if opts->no_speech >= 0,
+ * p = min(p, sot index) - the clip's own sot_index in a beam session, opts->sot_index in a greedy one - so the
+ * <|startoftranscript|> position stays a real step and no_speech is computed where it always was.  If p >= N, positions
+ * 0 .. p - 1 come from the pass and the row (group) starts stepping at position p with prompt[p]; otherwise the clip is forced
+ * as before.  A clip that carries TTASR_TOKEN_DETECT is NEVER prefilled: its detect step rewrites position 0 of its pages.
+ * Beam session: the prefix pages are taken once per group and shared by its rows (BEAM and ROWS groups alike); a clip whose
+ * prefix the page pool cannot supply at that moment is forced as before: a per-clip decision from pool state, taken before
+ * anything is enqueued for the clip.  Such a clip is an unprefilled clip in every respect (bit-identical to the option at 0) and
+ * is NOT counted by ttasr_session_prefill_stats, whose four values hold what the passes did: a host that applies the rule above
+ * to the prompts it submitted finds these clips as the difference to out[1].  (The pool holds max_batch * pages_per_seq pages
+ * and a live row at most pages_per_seq: the case needs hypotheses that have split nearly every page of every group.)
+ * The contract:
+ *   - A clip that is not prefilled is bit-identical (tokens, sum_logprob, no_speech, language results) to the same clip in a
+ *     session with the option at 0, whatever its neighbours do.
+ *   - A prefilled clip's results depend only on the clip, the options and the compute mode - not on which other clips shared
+ *     its admission pass, not on how many passes the admission was cut into, not on "refill_overlap", not on timing.  Every
+ *     kernel form inside the pass (GEMM family, attention block height) is a function of the clip's own prompt length and of
+ *     context constants, never of the pass.
+ *   - f32 engine: the tokens of the forced session, sum_logprob and no_speech up to f32 summation order.  16-bit engines: not
+ *     bit-identical to the forced path (the pass runs the tiled GEMM family, the steps the K-split decode GEMMs), as with the
+ *     static searches' "prefill".
+ * The pass has its own activation workspace (512 rows of f32 residual, h, qkv, attention output and the FFN's hidden rows:
+ * about 14 MB at large-v3), owned by the context: allocated by the first session that enables the option, freed by
+ * ttasr_destroy.  It works with "refill_overlap" 0 and 1 and under "xkv_fp8" = 2 (it reads the 16-bit live slots).  An admission
+ * that holds more than 512 prompt rows is cut into several passes by whole clips.  Hold mode and ttasr_session_align are
+ * untouched.  With the option at 0 a session enqueues the launches and copies it did before the option existed; one thing
+ * differs in form: a row's entry of the admission table is one word wider (its start position, 0), and the admission kernel reads
+ * that word.
+ * ttasr_session_prefill_stats (open session): out[0] passes, out[1] clips prefilled, out[2] positions prefilled (once per
+ * clip, not per beam row), out[3] GPU ms of the passes (events; the call waits for the last pass).  ttasr_session_stats
+ * out[0] and out[4] count only steps and row-steps that ran: prefilled positions are in neither. */
+TTASR_API int ttasr_session_prefill_stats(ttasr_ctx* ctx, double out[4]);
 TTASR_API int ttasr_session_stats(ttasr_ctx* ctx, double out[8]);
 TTASR_API int ttasr_session_rows(ttasr_ctx* ctx, int32_t* row_pos, int32_t* done, int64_t* row_clip);
 TTASR_API int ttasr_session_end(ttasr_ctx* ctx);
@@ -443,7 +481,10 @@ TTASR_API int ttasr_dtw(const float* cost, int32_t n_rows, int32_t n_cols, int32
  * decode steps run (0: synchronously between two step runs on the context's one stream; results identical; read by
  * ttasr_session_begin).  Opt-in: the second stream is a second hardware queue, and several processes sharing a GPU are then
  * time-sliced;
- * Drops the captured decode graphs (except "enc_kernel_timing" and "refill_overlap").  Unknown key or value out of range: TTASR_E_INVALID. */
+ * "session_prefill" [0] (0 ... n_text_ctx - 2; read by ttasr_session_begin / ttasr_session_begin_beam) N > 0: a clip with at least
+ * N prefillable prompt positions gets them from an admission pass instead of N forced decode steps (see "prompt prefill at
+ * admission" above);
+ * Drops the captured decode graphs (except "enc_kernel_timing", "refill_overlap" and "session_prefill").  Unknown key or value out of range: TTASR_E_INVALID. */
 TTASR_API int ttasr_set_option(ttasr_ctx* ctx, const char* key, int32_t value);
 
 /* ---- measurement --------------------------------------------------------------------------------- */

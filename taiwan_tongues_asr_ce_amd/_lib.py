@@ -18,7 +18,7 @@ SYMBOLS = [
     "ttasr_set_option", "ttasr_phase_ms", "ttasr_beam_profile", "ttasr_encoder_kernel_ms", "ttasr_bench_kernel", "ttasr_bench_kernel_signature", "ttasr_sync",
     "ttasr_session_begin", "ttasr_session_begin_beam", "ttasr_session_submit", "ttasr_session_submit_windows", "ttasr_session_poll", "ttasr_session_stats", "ttasr_session_rows", "ttasr_session_end",
     "ttasr_align_batch", "ttasr_session_hold", "ttasr_session_align", "ttasr_session_release", "ttasr_detect_language",
-    "ttasr_session_detect_language", "ttasr_session_poll_lang",
+    "ttasr_session_detect_language", "ttasr_session_poll_lang", "ttasr_session_prefill_stats",
 ]
 
 
@@ -107,6 +107,7 @@ def load() -> C.CDLL:
     lib.ttasr_session_detect_language.argtypes = [vp, i32, i32, i32]
     lib.ttasr_session_poll_lang.argtypes = [vp, i32, i32, i64p, i32p, i32p, f32p, f32p, i32p, f32p, f32p, i32p]
     lib.ttasr_session_stats.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.ttasr_session_prefill_stats.argtypes = [vp, C.POINTER(C.c_double)]
     lib.ttasr_session_rows.argtypes = [vp, i32p, i32p, i64p]
     lib.ttasr_session_end.argtypes = [vp]
     for s in SYMBOLS:

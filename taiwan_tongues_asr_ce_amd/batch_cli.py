@@ -124,11 +124,15 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
                          world: int = 1, load_audio: Callable = _load_audio, log: Callable = print,
                          group_files: int = 0, pipeline_depth: int = 0, continuous: bool = False,
                          cross_kv_fp8: bool = False, language: Optional[str] = TRANSCRIBE_KWARGS["language"],
-                         detect_in_session: bool = False) -> Optional[Dict]:
+                         detect_in_session: bool = False, session_prefill: int = 0) -> Optional[Dict]:
     """language: the forced language of every file (the reference's "zh"), or None = detect each file's language (`--language
     auto`); the detected language and its probability are then part of every entry of `detailed_results`.
     detect_in_session (`--detect-in-session`, with continuous and language None): the session finds each file's language in the
-    first decode step of its first window instead of a detection pass, with its own encoder pass, before the session."""
+    first decode step of its first window instead of a detection pass, with its own encoder pass, before the session.
+    session_prefill (`--session-prefill N`, with continuous): windows whose prompt has at least N prefillable positions get them from
+    one admission pass of the session instead of N forced decode steps (WhisperModel.transcribe_many(session_prefill=N))."""
+    if session_prefill and not continuous:
+        raise ValueError("session_prefill needs continuous=True")
     if continuous:
         if int(pipeline_depth or getattr(model, "pipeline_depth", 1)) > 1:
             log("continuous mode runs one session on one engine context: pipeline depth 1")
@@ -158,6 +162,8 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
             kw["continuous"] = True
             if detect_in_session and language is None:
                 kw["detect_in_session"] = True
+            if session_prefill:
+                kw["session_prefill"] = int(session_prefill)
         depth0 = max(1, int(pipeline_depth or getattr(model, "pipeline_depth", 1)))
         if group_files <= 0 and depth0 > 1 and len(mine) < group * depth0:
             group = max(1, -(-len(mine) // depth0))            # few files: one group per context rather than one big group and an idle lane
@@ -248,11 +254,18 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--detect-in-session", action="store_true",
                     help="opt-in, with --continuous --language auto: each file's language is found inside the session, in the first "
                          "decode step of its first window, instead of a detection pass with its own encoder pass beforehand")
+    ap.add_argument("--session-prefill", type=int, default=0, metavar="N",
+                    help="opt-in, with --continuous: a window whose prompt has at least N prefillable positions (previous text up to "
+                         "<|startoftranscript|>) gets them from one admission pass of the session instead of N forced decode steps; "
+                         "0 = off")
     return ap
 
 
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
+    if args.session_prefill < 0 or (args.session_prefill and not args.continuous):
+        print("--session-prefill needs a value >= 0 and --continuous")
+        return 1
     if not os.path.exists(args.folder):
         print(f"folder does not exist: {args.folder}")
         return 1
@@ -264,7 +277,7 @@ def main(argv=None) -> int:
                          compute_type=args.compute_type, rank=rank, world=world, group_files=args.group_files,
                          max_batch=args.max_batch, pipeline_depth=args.pipeline_depth, continuous=args.continuous,
                          cross_kv_fp8=args.xkv_fp8, language=None if args.language == "auto" else args.language,
-                         detect_in_session=args.detect_in_session)
+                         detect_in_session=args.detect_in_session, session_prefill=args.session_prefill)
     return 0
 
 

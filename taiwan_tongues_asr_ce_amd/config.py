@@ -21,6 +21,13 @@ COMPUTE_F32 = 0
 COMPUTE_BF16 = 1
 COMPUTE_F16 = 2   # IEEE fp16 storage, f32 accumulate: what compute_type="float16" (asr_core.py:141, api/config.py:12) means
 
+# session_prefill=True on the Python surfaces: a clip with at least this many prefillable prompt positions gets them from an admission
+# pass of its continuous-batching session (option "session_prefill").  From the first sweep
+# (tools/refill_bench.py --prev-tokens x --session-prefill, profiles/session_prefill_threshold.jsonl): a pass costs a few ms
+# however short, a forced position about 1 / max_batch of a step per row; prompts of 12 positions lose with the pass, prompts of
+# 20 gain (greedy and beam 5), so the break-even lies between them.
+SESSION_PREFILL_DEFAULT = 16
+
 
 @dataclass(frozen=True)
 class WhisperDims:

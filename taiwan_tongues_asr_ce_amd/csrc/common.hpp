@@ -433,6 +433,16 @@ template <typename T>
 void launch_self_attn_decode_rows(const T* qkv, T* kv_pool, const int32_t* page_table, int pages_per_seq, int64_t pool_layer_off,
                                   int identity_pages, int row0, const int32_t* row_pos, T* out, int B, int H, hipStream_t s, SlabIn sq,
                                   const int32_t* done);
+// Prompt prefill at a session's admission (kernels_prefill.hip; tables: prefill_tables.hpp): one pass over PACKED rows, sequence
+// after sequence.  rows [n_rows][3] = {sequence, position, token}; slots [n_rows] = cross-KV slot of the row; seqs [n_seqs][seq_stride]
+// = {cross-KV slot, first packed row, length, pages ...}; items [n_items][3] = {sequence, first packed query row, rows <= 128}.
+struct PrefillPass { const int32_t *rows, *slots, *seqs, *items; int n_rows, n_seqs, n_items, seq_stride; };
+template <typename T> void launch_prefill_embed(const PrefillPass& P, const T* emb, const T* pos, float* x /*[n_rows][d]*/, int d, hipStream_t s);
+// append + attend: row (s, t) writes K / V of position t into sequence s's pages of this layer's pool and attends to 0 .. t
+template <typename T> void launch_prefill_self_attn(const PrefillPass& P, const T* qkv /*[n_rows][3d]*/, T* pool_layer, T* out /*[n_rows][d]*/, int H, hipStream_t s);
+// ragged MFMA cross-attention (16-bit): q, out [n_rows][d]; K, V = the layer's cross-KV [slot][H][Tk][64], Tk even and >= 4
+template <typename T16>
+void launch_prefill_cross_attn(const PrefillPass& P, const T16* q, const T16* K, const T16* V, T16* out, int H, int Tk, hipStream_t s);
 template <typename T>
 void launch_copy_pages(T* pool, const int32_t* pairs_dev, int n_pairs, int n_layers, int H, int64_t layer_elems, hipStream_t s);
 template <typename T>
@@ -493,9 +503,10 @@ void launch_select(const float* logits, DecState st, RuleParams rp, int B, float
 void launch_advance(int32_t* step, hipStream_t s);
 // the continuous-batching session's select (engine_refill.hip): st.step = per-row positions [B]; each live row advances its own
 void launch_select_rows(const float* logits, DecState st, RuleParams rp, int B, hipStream_t s);
-// row admission of the session: for each of the n entries of `tab` ([n][3 + max_prompt]: row, prompt length, token budget, prompt
-// tokens) every per-row field of the search state is reset, the prompt row and budget are stored, the row's position is set to 0
-// and its first token to prompt[0]; n_done is corrected for the rows that were finished
+// row admission of the session: for each of the n entries of `tab` ([n][4 + max_prompt]: row, prompt length, token budget, start
+// position, prompt tokens) every per-row field of the search state is reset, the prompt row and budget are stored, the row's
+// position is set to `start` (0, or the positions an admission pass prefilled) and its first token to prompt[start]; n_done is
+// corrected for the rows that were finished
 void launch_admit_rows(const int32_t* tab, int n, int B, int max_prompt, DecState st, int32_t* prompt, int32_t* prompt_len, int32_t* row_cap,
                        int32_t* row_pos, hipStream_t s);
 void launch_prep_weight(const void* src, int src_type /*0 f32, 1 bf16 bits, 2 fp16 bits*/, float* dst, int64_t n, int64_t conv_in, float scale,

@@ -22,6 +22,7 @@
 #include "common.hpp"
 #include "align_batch.hpp"
 #include "beam_pages.hpp"
+#include "prefill_tables.hpp"
 
 namespace ttasr_detail {
 
@@ -164,6 +165,13 @@ struct ttasr_ctx {
   void* xkv_stage = nullptr;      // [dec_layers][2][maxB][H][T][64] T: the session's encoder writes the admitted clips' cross-KV here
   int32_t* admit_dev = nullptr;   // [maxB][3 + max_prompt_alloc] row-admission table (launch_admit_rows)
   int32_t* sess_sel = nullptr;    // [maxB][9] beam session: entries, temperatures, seeds and results of the independent-row kernel
+  // prompt prefill at a session's admission (option session_prefill): 0 = off, N > 0 = clips with at least
+  // N prefillable prompt positions get them from an admission pass.  The pass has its OWN activation workspace of kPrefillRowCap
+  // rows (the encoder's is written by an overlapped encode from the second stream), its device tables and the all -1 head
+  // selection of the f32 engine's per-row cross-attention: allocated by the first session that enables the option
+  int session_prefill = 0;
+  float* pf_x = nullptr; void *pf_h = nullptr, *pf_qkv = nullptr, *pf_att = nullptr, *pf_mid = nullptr;
+  int32_t* pf_tab = nullptr; size_t pf_tab_words = 0; int* pf_sel = nullptr;
 
   // batched alignment (engine_align.hip): ONE device block for the pass's tables, softmax maps, cost matrices and spilled DTW
   // traces; allocated by the first call, grown to the largest request, freed by ttasr_destroy
@@ -323,6 +331,7 @@ void enc_mark(ttasr_ctx* c, int cls);
 void sched_encoder(ttasr_ctx* c, int B);                       // conv stem, encoder layers, final LayerNorm, cross-KV
 void sched_cross_kv(ttasr_ctx* c, int B);
 void sched_prefill(ttasr_ctx* c, int n_seq, int npos, int seq_per_clip, int max_prompt, const AlignOut* al = nullptr);
+void sched_admit_prefill(ttasr_ctx* c, const PrefillPass& P);   // the decoder layers over the packed rows of an admission pass, on the decode stream
 int sched_prefill_no_speech(ttasr_ctx* c, int n_seq, int npos, int sot, int no_speech_tok);
 void sched_gemm(ttasr_ctx* c, const GemmArgs& g);              // encoder-side GEMM dispatch (ttasr_bench_kernel)
 void sched_dec_gemm(ttasr_ctx* c, const GemmArgs& g, const void* Wsh);

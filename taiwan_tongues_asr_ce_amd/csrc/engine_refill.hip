@@ -36,6 +36,14 @@
 // kernel runs behind the logits-only step for the first row of each detecting group, its results come back in the step's one
 // synchronisation, and the host patches the group's prompt and leaves its position at 0.  Either way the clip then decodes as if
 // the language had been given: position 0 of its self-attention pages is simply written again.
+//
+// Prompt prefill at admission (option session_prefill = N > 0): a clip whose own prompt has p >= N
+// prefillable positions (session_prefill_positions, prefill_tables.hpp) gets positions 0 .. p - 1 from an ADMISSION PASS - the
+// decoder layers over the packed prompt rows of the clips admitted together (sched_admit_prefill), enqueued on the decode stream
+// behind their cross-KV copies, between two steps - and its row (group) starts stepping at position p with prompt[p].  Greedy: the
+// row's identity pages; beam: prefix pages taken once per group and shared by its rows (BeamPages::share_fresh), the partially
+// filled last one split by the copy-on-write of the first private write.  The pass has its own workspace, so it runs with
+// refill_overlap 0 and 1; a clip's bits do not depend on its pass-mates.  With the option at 0 nothing of this is enqueued.
 #include "engine_ctx.hpp"
 #include <chrono>
 #include <cmath>
@@ -102,7 +110,21 @@ struct Session {
   BeamPages pages;
   std::vector<int32_t> cur_tok, done_rows, pairs;
   std::unique_ptr<SearchScope> scope;   // the session's decode shape, from session_begin to session_end / session_free
+  // prompt prefill at admission: the threshold (0: off); per greedy row the position its clip started stepping at; the pinned
+  // tables of the last admission's passes, alive until ev_pf has completed (pf_busy); (start, stop) events of passes whose time
+  // has not been collected yet; statistics (ttasr_session_prefill_stats)
+  int prefill = 0;
+  std::vector<int32_t> row_start;
+  int32_t* pf_pin = nullptr;
+  hipEvent_t ev_pf = nullptr; bool pf_busy = false;
+  std::vector<hipEvent_t> pf_ev; size_t pf_ev_used = 0;
+  int64_t pf_passes = 0, pf_clips = 0, pf_positions = 0; double pf_ms = 0;
 };
+
+// words of the table block of one admission (pinned and device): every unit admitted at once with the longest prompt
+static size_t prefill_tab_cap(const ttasr_ctx* c) {
+  return prefill_table_words(c->maxB * c->cfg.n_text_ctx, c->maxB, c->maxB * prefill_items_of(c->cfg.n_text_ctx), c->pages_per_seq);
+}
 
 int session_refusal(ttasr_ctx* c) {
   if (c && c->sess) return fail(c, TTASR_E_INVALID, "a continuous-batching session is open on this context (ttasr_session_end first)");
@@ -114,8 +136,12 @@ void session_free(ttasr_ctx* c) {
   if (!S) return;
   if (S->es && S->es != c->stream) { hipStreamSynchronize(S->es); hipStreamDestroy(S->es); }
   for (hipEvent_t e : {S->ev_enc0, S->ev_enc, S->ev_copy, S->ev_dec0, S->ev_dec1}) if (e) hipEventDestroy(e);
+  if (S->pf_busy) hipEventSynchronize(S->ev_pf);   // the last pass still reads its tables
+  for (hipEvent_t e : S->pf_ev) hipEventDestroy(e);
+  if (S->ev_pf) hipEventDestroy(S->ev_pf);
   if (S->pin) hipHostFree(S->pin);
   if (S->lang_pin) hipHostFree(S->lang_pin);
+  if (S->pf_pin) hipHostFree(S->pf_pin);
   delete S;   // with its scope: the context is back to the defaults of a static search
   c->sess = nullptr;
 }
@@ -211,7 +237,70 @@ static int flush_quant_pairs(ttasr_ctx* c, const XkvSlotPairs& qp, int& n) {
   return 0;
 }
 
-// staged clips -> free rows: cross-KV copies and one admit launch on the decode stream
+// The times of the passes enqueued so far -> pf_ms.  Waits for the last pass; behind a poll's synchronisation it has completed.
+static int prefill_collect(ttasr_ctx* c, Session* S) {
+  if (!S->pf_busy) return 0;
+  HIPCHK(c, hipEventSynchronize(S->ev_pf));
+  for (size_t i = 0; i + 1 < S->pf_ev_used; i += 2) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, S->pf_ev[i], S->pf_ev[i + 1]) == hipSuccess) S->pf_ms += ms;
+  }
+  S->pf_ev_used = 0; S->pf_busy = false;
+  return 0;
+}
+
+// The admission passes over the sequences collected by admit(): cut by whole sequences at the workspace's rows, the tables of all
+// passes built in the session's pinned block (it outlives the copy: released by ev_pf) and uploaded in ONE copy, then one
+// sched_admit_prefill per pass on the decode stream, behind the clips' cross-KV copies.
+// The ONE place where an admission may wait for the GPU: the table blocks (pinned and device) are single, so a second admission
+// with prefilled clips first waits for the previous admission's last pass (prefill_collect).  Every poll synchronises the decode
+// stream behind its steps, so the event has completed whenever a poll lies between the two admissions - the usual case; with
+// refill_overlap = 1 two admissions inside one poll (a pass of clips admitted, then the next encode found complete) can make
+// pump() wait for a pass of a few ms.  Results do not depend on it.
+static int run_prefill_passes(ttasr_ctx* c, Session* S, const std::vector<PrefillSeq>& sq) {
+  if (sq.empty()) return 0;
+  TRY(prefill_collect(c, S));   // the previous admission's tables are free
+  hipStream_t s = c->stream;
+  const int pps = c->pages_per_seq;
+  std::vector<int> len(sq.size());
+  for (size_t i = 0; i < sq.size(); ++i) len[i] = sq[i].len;
+  const std::vector<int> cut = prefill_pass_split(len, kPrefillRowCap);
+  std::vector<PrefillPass> passes;
+  size_t w = 0;
+  for (size_t k = 0; k + 1 < cut.size(); ++k) {
+    int rows = 0, items = 0;
+    const int n = cut[k + 1] - cut[k];
+    for (int i = cut[k]; i < cut[k + 1]; ++i) { rows += len[i]; items += prefill_items_of(len[i]); }
+    const size_t o_slots = w + (size_t)rows * 3, o_seqs = o_slots + rows, o_items = o_seqs + (size_t)n * (3 + pps);
+    if (rows > kPrefillRowCap || o_items + (size_t)items * 3 > c->pf_tab_words)
+      return fail(c, TTASR_E_INVALID, "session prefill: pass of %d rows / table of %zu words exceeds the workspace", rows, o_items + (size_t)items * 3);
+    int32_t* const hp = S->pf_pin;
+    prefill_build_tables(&sq[cut[k]], n, pps, hp + w, hp + o_slots, hp + o_seqs, hp + o_items);
+    const int32_t* const dp = c->pf_tab;
+    passes.push_back(PrefillPass{dp + w, dp + o_slots, dp + o_seqs, dp + o_items, rows, n, items, 3 + pps});
+    w = o_items + (size_t)items * 3;
+  }
+  while (S->pf_ev.size() < 2 * passes.size()) {
+    hipEvent_t e;
+    HIPCHK(c, hipEventCreate(&e));
+    S->pf_ev.push_back(e);
+  }
+  HIPCHK(c, hipMemcpyAsync(c->pf_tab, S->pf_pin, w * 4, hipMemcpyHostToDevice, s));
+  for (size_t k = 0; k < passes.size(); ++k) {
+    HIPCHK(c, hipEventRecord(S->pf_ev[2 * k], s));
+    sched_admit_prefill(c, passes[k]);
+    HIPCHK(c, hipEventRecord(S->pf_ev[2 * k + 1], s));
+  }
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(S->ev_pf, s));
+  S->pf_ev_used = 2 * passes.size(); S->pf_busy = true;
+  S->pf_passes += (int64_t)passes.size(); S->pf_clips += (int64_t)sq.size();
+  for (int l : len) S->pf_positions += l;
+  return 0;
+}
+
+// staged clips -> free rows: cross-KV copies, the admission pass of the clips whose prompts are prefilled, and one admit launch
+// on the decode stream
 static int admit(ttasr_ctx* c, Session* S) {
   const int avail = (int)(S->staged.size() - S->staged_next);
   if (avail == 0 || S->enc_pending) return 0;
@@ -231,6 +320,9 @@ static int admit(ttasr_ctx* c, Session* S) {
     if (++nq == XkvSlotPairs::N) return flush_quant_pairs(c, qp, nq);
     return 0;
   };
+  // the clips of this admission whose prompt positions 0 .. len - 1 come from a pass; tokens and pages stay alive until the call returns
+  std::vector<PrefillSeq> pf_seq;
+  std::vector<std::vector<int32_t>> pf_pages;
   if (S->beam) {
     // a free group takes the clip: its cross-KV goes to slot g; the search state is host-side and goes out with the next step
     for (int g = 0; g < S->G && (int)S->staged_next < (int)S->staged.size(); ++g) {
@@ -248,20 +340,33 @@ static int admit(ttasr_ctx* c, Session* S) {
       gr.mode = cl.mode; gr.rows = cl.rows; gr.temp = cl.temp; gr.seed = cl.seed; gr.sot = cl.sot;
       gr.det = cl.det; gr.lang = Session::Lang{};
       gr.max_cand = std::max(1, (int)std::lround(cl.rows * S->patience));
+      // prompt prefill: the prefix pages are taken ONCE for the group and shared by its rows, as the static search's batched
+      // prefill does; a pool that cannot supply them leaves the clip forced (a per-clip decision from pool state)
+      int start = session_prefill_positions(plen, S->o.no_speech >= 0 ? gr.sot : -1, S->prefill, gr.det >= 0);
+      const int n_pg = (start + kPrefillPageTokens - 1) / kPrefillPageTokens;
+      if (start > 0 && (size_t)n_pg > S->pages.free_pages.size()) start = 0;
+      if (start > 0) {
+        pf_pages.emplace_back(n_pg);
+        for (int q = 0; q < n_pg; ++q) pf_pages.back()[q] = S->pages.share_fresh(g * S->beam, S->beam, q);
+        pf_seq.push_back(PrefillSeq{g, start, gr.prompt.data(), nullptr});
+        gr.pos = start;
+      }
       for (int b = 0; b < S->beam; ++b) {   // rows beyond the clip's `rows` stay finished
         const int r = g * S->beam + b;
         S->seqs[r].clear(); S->sums[r] = 0.0; S->fsums[r] = 0.f;
-        S->row_clip[r] = cl.id; S->cur_tok[r] = gr.det >= 0 ? S->lang_sot : gr.prompt[0]; S->done_rows[r] = b < cl.rows ? 0 : 1;
+        S->row_clip[r] = cl.id; S->cur_tok[r] = gr.det >= 0 ? S->lang_sot : gr.prompt[start]; S->done_rows[r] = b < cl.rows ? 0 : 1;
       }
     }
     TRY(flush_quant_pairs(c, qp, nq));
+    for (size_t i = 0; i < pf_seq.size(); ++i) pf_seq[i].pages = pf_pages[i].data();   // (pf_pages no longer grows)
+    TRY(run_prefill_passes(c, S, pf_seq));
     if (S->staged_next == S->staged.size()) {
       S->staged.clear(); S->staged_next = 0;
       HIPCHK(c, hipEventRecord(S->ev_copy, s));
     }
     return 0;
   }
-  const int W = 3 + S->max_prompt;
+  const int W = 4 + S->max_prompt;
   int32_t* tab = S->pin + (size_t)c->maxB * (4 + c->rp.max_new);
   int n = 0, n_det = 0;
   for (int r = 0; r < c->maxB && (int)S->staged_next < (int)S->staged.size(); ++r) {
@@ -274,9 +379,16 @@ static int admit(ttasr_ctx* c, Session* S) {
     int32_t* e = tab + (size_t)n * W;
     const int plen = (int)cl.prompt.size();
     // a row never samples past the text context: the static loop's last sampled position is n_text_ctx - 2
-    e[0] = r; e[1] = plen; e[2] = std::min(cl.cap, c->cfg.n_text_ctx - plen);
-    for (int q = 0; q < S->max_prompt; ++q) e[3 + q] = q < plen ? cl.prompt[q] : 0;
-    S->row_clip[r] = cl.id; S->row_plen[r] = plen;
+    // prompt prefill: positions 0 .. start - 1 come from the admission pass (the row's identity pages), the row steps from `start`
+    const int start = session_prefill_positions(plen, S->o.no_speech >= 0 ? S->o.sot_index : -1, S->prefill, cl.det >= 0);
+    if (start > 0) {
+      pf_pages.emplace_back((start + kPrefillPageTokens - 1) / kPrefillPageTokens);
+      for (size_t q = 0; q < pf_pages.back().size(); ++q) pf_pages.back()[q] = r * c->pages_per_seq + (int)q;
+      pf_seq.push_back(PrefillSeq{r, start, cl.prompt.data(), nullptr});
+    }
+    e[0] = r; e[1] = plen; e[2] = std::min(cl.cap, c->cfg.n_text_ctx - plen); e[3] = start;
+    for (int q = 0; q < S->max_prompt; ++q) e[4 + q] = q < plen ? cl.prompt[q] : 0;
+    S->row_clip[r] = cl.id; S->row_plen[r] = plen; S->row_start[r] = start;
     if (S->armed) {
       S->row_det[r] = cl.det >= 0; S->row_lang[r] = Session::Lang{};
       if (cl.det >= 0) { S->lang_pin[2 * n_det] = r; S->lang_pin[2 * n_det + 1] = cl.det; ++n_det; }
@@ -284,6 +396,8 @@ static int admit(ttasr_ctx* c, Session* S) {
     ++n;
   }
   TRY(flush_quant_pairs(c, qp, nq));
+  for (size_t i = 0; i < pf_seq.size(); ++i) pf_seq[i].pages = pf_pages[i].data();   // (pf_pages no longer grows)
+  TRY(run_prefill_passes(c, S, pf_seq));
   if (n > 0) {
     HIPCHK(c, hipMemcpyAsync(c->admit_dev, tab, (size_t)n * W * 4, hipMemcpyHostToDevice, s));
     launch_admit_rows(c->admit_dev, n, c->maxB, S->max_prompt, c->st, c->prompt_dev, c->plen_dev, c->row_cap_dev, c->row_pos, s);
@@ -300,7 +414,8 @@ static int admit(ttasr_ctx* c, Session* S) {
   return 0;
 }
 
-// admissions and encodes that can happen now (host side; never blocks on the GPU in overlap mode)
+// admissions and encodes that can happen now (host side; never blocks on the GPU in overlap mode - but for the table wait of
+// run_prefill_passes with option session_prefill)
 static int pump(ttasr_ctx* c, Session* S) {
   if (S->enc_pending) {
     const hipError_t q = hipEventQuery(S->ev_enc);
@@ -348,16 +463,35 @@ static int session_begin(ttasr_ctx* c, const ttasr_gen_opts* o, int max_prompt, 
   const int B = c->maxB;
   // first session of this context: its device buffers (kept for the context's lifetime)
   if (!c->row_pos) TRY(dalloc(c, &c->row_pos, (size_t)B * 4));
-  if (!c->admit_dev) TRY(dalloc(c, &c->admit_dev, (size_t)B * (3 + c->max_prompt_alloc) * 4));
+  if (!c->admit_dev) TRY(dalloc(c, &c->admit_dev, (size_t)B * (4 + c->max_prompt_alloc) * 4));
   if (!c->xkv_stage) TRY(dalloc(c, &c->xkv_stage, (size_t)c->xkv_layer_elems * c->cfg.dec_layers * c->esz, false));
+  if (c->session_prefill > 0) {   // first session with prompt prefill: the pass's own workspace and tables (kept like the others)
+    const size_t R = kPrefillRowCap, e = c->esz;
+    if (!c->pf_x) TRY(dalloc(c, &c->pf_x, R * c->d * 4));
+    if (!c->pf_h) TRY(dalloc(c, &c->pf_h, R * c->d * e));
+    if (!c->pf_qkv) TRY(dalloc(c, &c->pf_qkv, R * 3 * c->d * e));
+    if (!c->pf_att) TRY(dalloc(c, &c->pf_att, R * c->d * e));
+    if (!c->pf_mid) TRY(dalloc(c, &c->pf_mid, R * c->ffn * e));
+    if (!c->pf_tab) { c->pf_tab_words = prefill_tab_cap(c); TRY(dalloc(c, &c->pf_tab, c->pf_tab_words * 4)); }
+    if (!c->pf_sel) {
+      TRY(dalloc(c, &c->pf_sel, (size_t)c->H * 4, false));
+      HIPCHK(c, hipMemsetAsync(c->pf_sel, 0xff, (size_t)c->H * 4, c->stream));   // no head writes a softmax map
+    }
+  }
   std::unique_ptr<Session> S(new Session());
+  S->prefill = c->session_prefill;
   S->o = *o; S->o.suppress = nullptr; S->o.begin_suppress = nullptr;   // the rules are uploaded; the caller's arrays are not kept
   S->max_prompt = max_prompt;
   S->overlap = c->refill_overlap;
-  S->row_clip.assign(B, -1); S->row_plen.assign(B, 1); S->held.assign(B, 0);
-  S->pin_words = (size_t)B * (4 + c->rp.max_new) + (size_t)B * (3 + max_prompt);
+  S->row_clip.assign(B, -1); S->row_plen.assign(B, 1); S->held.assign(B, 0); S->row_start.assign(B, 0);
+  S->pin_words = (size_t)B * (4 + c->rp.max_new) + (size_t)B * (4 + max_prompt);
   struct Undo { ttasr_ctx* c; Session* s; ~Undo() { if (s) { c->sess = s; session_free(c); } } } undo{c, nullptr};
   HIPCHK(c, hipHostMalloc((void**)&S->pin, S->pin_words * 4));
+  if (S->prefill > 0) {
+    hipError_t r = hipHostMalloc((void**)&S->pf_pin, prefill_tab_cap(c) * 4);
+    if (r == hipSuccess) r = hipEventCreate(&S->ev_pf);
+    if (r != hipSuccess) { undo.s = S.release(); return fail(c, TTASR_E_HIP, "session prefill tables: %s", hipGetErrorString(r)); }
+  }
   for (hipEvent_t* e : {&S->ev_enc0, &S->ev_enc, &S->ev_copy, &S->ev_dec0, &S->ev_dec1}) {
     const hipError_t r = hipEventCreate(e);
     if (r != hipSuccess) { undo.s = S.release(); return fail(c, TTASR_E_HIP, "hipEventCreate: %s", hipGetErrorString(r)); }
@@ -768,7 +902,7 @@ static int session_poll(ttasr_ctx* c, int max_steps, int cap, int64_t* ids, int3
       const int len = std::min(p[B + r], max_new);
       d.tok.assign(p + 4 * B + (size_t)r * max_new, p + 4 * B + (size_t)r * max_new + len);
       memcpy(&d.lp, &p[2 * B + r], 4); memcpy(&d.ns, &p[3 * B + r], 4);
-      S->live_row_steps += S->row_plen[r] - 1 + len;
+      S->live_row_steps += S->row_plen[r] - 1 - S->row_start[r] + len;   // prefilled positions ran no step
       if (S->armed) {   // a detected clip ran one more live row-step
         S->live_row_steps += S->row_det[r] != 0;
         d.lang = std::move(S->row_lang[r]); S->row_det[r] = 0; S->row_lang[r] = Session::Lang{};
@@ -971,6 +1105,20 @@ int ttasr_session_stats(ttasr_ctx* c, double out[8]) {
     if (!S) return fail(c, TTASR_E_INVALID, "no session is open");
     const double v[8] = {(double)S->steps, (double)S->polls, (double)S->encodes, (double)S->clips_encoded, (double)S->live_row_steps,
                          S->enc_ms, S->dec_ms, (double)(S->queue.size() + S->staged.size() - S->staged_next)};
+    memcpy(out, v, sizeof v);
+    return TTASR_OK;
+  });
+}
+
+int ttasr_session_prefill_stats(ttasr_ctx* c, double out[4]) {
+  return guarded(c, [&]() -> int {
+    if (!c) return TTASR_E_INVALID;
+    if (!out) return fail(c, TTASR_E_INVALID, "out is NULL");
+    Session* S = c->sess;
+    if (!S) return fail(c, TTASR_E_INVALID, "no session is open");
+    HIPCHK(c, hipSetDevice(c->device));
+    TRY(prefill_collect(c, S));
+    const double v[4] = {(double)S->pf_passes, (double)S->pf_clips, (double)S->pf_positions, S->pf_ms};
     memcpy(out, v, sizeof v);
     return TTASR_OK;
   });

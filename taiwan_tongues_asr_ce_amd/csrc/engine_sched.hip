@@ -444,6 +444,58 @@ void run_prefill(ttasr_ctx* c, int n_seq, int npos, int seq_per_clip, int max_pr
   if (pend.n_slab) ln(c->dlnf_g, c->dlnf_b);
 }
 
+// The admission pass of a session (option session_prefill; engine_refill.hip): the decoder layers over the PACKED prompt rows of
+// the admitted clips, on the decode stream, out of the pass's own workspace (c->pf_*).  Only the self-attention K / V of these
+// positions has to survive: no final LayerNorm, no vocabulary GEMM, nothing reads the residual afterwards.
+// A prefilled clip's bits must not depend on its pass-mates, so every kernel form is a function of context constants: the GEMMs
+// run in ONE family whatever the row count - 16-bit: the first of the 256 x 256, 256 x 128 and 128 x 128 tiled kernels that takes
+// the context's widths (a row of a tile depends on its own A row only, and rows past M are loaded clamped and never stored);
+// f32 or option generic_kernels: the generic kernel - the attention work items are cut from each sequence's own length, and the
+// K-split skinny path of run_prefill, whose split follows the pass's row count, is not used.
+template <typename T>
+void run_admit_prefill(ttasr_ctx* c, const PrefillPass& P) {
+  const int d = c->d, ffn = c->ffn, n = P.n_rows;
+  hipStream_t s = c->cur = c->stream;
+  float* x = c->pf_x;
+  void *h = c->pf_h, *qkv = c->pf_qkv, *att = c->pf_att, *mid = c->pf_mid;
+  auto pgemm = [&](const GemmArgs& g) {
+    if constexpr (sizeof(T) == 2) {
+      if (!c->force_basic) {
+        if (gemm_bf16_v3_ok(g)) { launch_gemm_bf16_v3<T>(g, s); return; }
+        if (gemm_bf16_v2_ok(g)) { launch_gemm_bf16_v2<T>(g, s); return; }
+        if (gemm_bf16_fast_ok(g)) { launch_gemm_bf16_fast<T>(g, s); return; }
+      }
+    }
+    launch_gemm_basic<T>(g, s);
+  };
+  auto residual_gemm = [&](const void* A, const void* W, const float* bias, int K) {   // x += W a + b
+    GemmArgs g = lin_args<T>(A, W, n, d, K);
+    g.epi.bias = bias; g.epi.residual = x; g.epi.out_f32 = x;
+    pgemm(g);
+  };
+  launch_prefill_embed<T>(P, (const T*)c->emb, (const T*)c->dpos, x, d, s);
+  for (int l = 0; l < c->cfg.dec_layers; ++l) {
+    const DecLayerW& L = c->dec[l];
+    launch_layernorm<T>(x, L.ln1g, L.ln1b, (T*)h, n, d, s);
+    { GemmArgs g = lin_args<T>(h, L.wqkv, n, 3 * d, d); g.epi.bias = L.bqkv; g.epi.out_t = qkv; pgemm(g); }
+    launch_prefill_self_attn<T>(P, (const T*)qkv, (T*)c->pool + (int64_t)l * c->pool_layer_elems, (T*)att, c->H, s);
+    residual_gemm(att, L.wo, L.bo, d);
+    launch_layernorm<T>(x, L.ln2g, L.ln2b, (T*)h, n, d, s);
+    { GemmArgs g = lin_args<T>(h, L.wqx, n, d, d); g.epi.bias = L.bqx; g.epi.out_t = qkv; pgemm(g); }   // q reuses the qkv buffer
+    const T* Kx = (const T*)c->xkv + (int64_t)l * c->xkv_layer_elems;   // the 16-bit live slots, also under xkv_fp8 = 2
+    bool mfma = false;
+    if constexpr (sizeof(T) == 2) {
+      if (!c->force_basic) { launch_prefill_cross_attn<T>(P, (const T*)qkv, Kx, Kx + c->xkv_which_elems, (T*)att, c->H, c->T, s); mfma = true; }
+    }
+    // per-row form: "sequence" = one packed row, its slot from the table, no head selected for a softmax map
+    if (!mfma) launch_cross_attn_probs_batch<T>((const T*)qkv, Kx, Kx + c->xkv_which_elems, (T*)att, n, 1, c->H, c->T, c->pf_sel, P.slots, nullptr, s);
+    residual_gemm(att, L.wox, L.box, d);
+    launch_layernorm<T>(x, L.ln3g, L.ln3b, (T*)h, n, d, s);
+    { GemmArgs g = lin_args<T>(h, L.w1, n, ffn, d); g.epi.bias = L.b1; g.epi.act = 1; g.epi.out_t = mid; pgemm(g); }
+    residual_gemm(mid, L.w2, L.b2, ffn);
+  }
+}
+
 // How many leading prompt positions can be prefilled: every row must still have a forced token after them and the rows
 // must fit the borrowed encoder workspaces.  Below 2 positions the pass does not pay.  `ns_from_prefill` = the caller can
 // take the no-speech probability from the prefilled <|startoftranscript|> position (prefill_no_speech); otherwise that
@@ -555,6 +607,7 @@ void sched_cross_kv(ttasr_ctx* c, int B) { TT_DISPATCH(c, run_cross_kv<T>(c, B))
 void sched_prefill(ttasr_ctx* c, int n_seq, int npos, int seq_per_clip, int max_prompt, const AlignOut* al) {
   TT_DISPATCH(c, run_prefill<T>(c, n_seq, npos, seq_per_clip, max_prompt, al));
 }
+void sched_admit_prefill(ttasr_ctx* c, const PrefillPass& P) { TT_DISPATCH(c, run_admit_prefill<T>(c, P)); }
 int sched_prefill_no_speech(ttasr_ctx* c, int n_seq, int npos, int sot, int no_speech_tok) {
   TT_DISPATCH(c, return prefill_no_speech<T>(c, n_seq, npos, sot, no_speech_tok));
   return 0;

@@ -59,6 +59,11 @@ int set_option(ttasr_ctx* c, const std::string& key, int v) {
   const bool on = v != 0;
   if (key == "enc_kernel_timing") { c->enc_timing = on; return 0; }   // measurement only: the captured decode graphs stay
   if (key == "refill_overlap") { c->refill_overlap = on; return 0; }   // host-side schedule of the session: the graphs stay
+  if (key == "session_prefill") {   // read by ttasr_session_begin[_beam]; a host-side choice of the admission: the graphs stay
+    if (v < 0 || v > c->cfg.n_text_ctx - 2) return 1;
+    c->session_prefill = v;
+    return 0;
+  }
   if (key == "flash") c->no_flash = !on;
   else if (key == "prefill") c->no_prefill = !on;
   else if (key == "vocab_persistent") c->vocab_persistent = on;

@@ -469,15 +469,16 @@ void launch_session_rows_select(const float* logits, BeamRowState hs, RuleParams
 __global__ __launch_bounds__(64) void admit_rows_kernel(const int32_t* __restrict__ tab, int B, int max_prompt, DecState st,
                                                         int32_t* __restrict__ prompt, int32_t* __restrict__ prompt_len,
                                                         int32_t* __restrict__ row_cap, int32_t* __restrict__ row_pos) {
-  const int32_t* e = tab + (int64_t)blockIdx.x * (3 + max_prompt);
+  const int32_t* e = tab + (int64_t)blockIdx.x * (4 + max_prompt);
   const int row = e[0];
   if (row < 0 || row >= B) return;   // the host validated the table; never write outside the batch
-  for (int j = threadIdx.x; j < max_prompt; j += 64) prompt[(int64_t)row * max_prompt + j] = e[3 + j];
+  const int start = min(max(e[3], 0), max_prompt - 1);   // positions before it were prefilled by the admission pass (0: none)
+  for (int j = threadIdx.x; j < max_prompt; j += 64) prompt[(int64_t)row * max_prompt + j] = e[4 + j];
   if (threadIdx.x == 0) {
     prompt_len[row] = e[1];
     row_cap[row] = e[2];
-    row_pos[row] = 0;
-    st.cur_tok[row] = e[3];
+    row_pos[row] = start;
+    st.cur_tok[row] = e[4 + start];
     st.n_sampled[row] = 0;
     st.last_tok[row] = -1; st.pen_tok[row] = -1; st.last_ts[row] = -1;
     st.sum_logprob[row] = 0.f; st.no_speech[row] = 0.f;

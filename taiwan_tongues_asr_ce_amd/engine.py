@@ -173,6 +173,8 @@ class Engine:
         """Kernel-selection override for tests / A-B measurements (ttasr_set_option; keys in include/ttasr.h).  The library
         reads no environment variable: this call is the only way to leave the measured configuration."""
         self._check(self.lib.ttasr_set_option(self.h, key.encode(), int(value)), f"set_option({key})")
+        if key == "session_prefill":
+            self._session_prefill = int(value)   # what Session restores when its prefill keyword has changed the option
 
     # -- a6..a8 --------------------------------------------------------------------------------
     def encode(self, B: int, want_output: bool = False) -> Optional[np.ndarray]:
@@ -244,7 +246,7 @@ class Engine:
         return GenResult([toks[b, :lens[b]].tolist() for b in range(B)], lp, ns)
 
     def session(self, opts, max_prompt: int, temperature: float = 0.0, beam: int = 1,
-                patience: Optional[float] = None, detect_language=False) -> "Session":
+                patience: Optional[float] = None, detect_language=False, prefill: int = 0) -> "Session":
         """Continuous-batching session (ttasr_session_*): greedy, single-window decoding of clips submitted at any time; each clip
         takes a free row of the max_batch-row decode batch and hands it to the next queued clip when it finishes.  A context
         manager: the session ends when the block is left.  While it is open the engine's other search / encode calls are refused.
@@ -255,8 +257,13 @@ class Engine:
         detect_language=True, or (sot, first language token, count): the session is armed for language identification
         (ttasr_session_detect_language; True = this engine's <|startoftranscript|> and language_span()).  A prompt may then hold
         Session.DETECT directly behind <|startoftranscript|>: the clip's first step finds its language on the device and writes
-        it over the placeholder; SessionResult.language / language_probs carry the answer."""
-        return Session(self, opts, max_prompt, temperature, beam, patience, detect_language)
+        it over the placeholder; SessionResult.language / language_probs carry the answer.
+
+        prefill = N (option "session_prefill"; True = config.SESSION_PREFILL_DEFAULT, 0 = off): a clip whose prompt has at least N
+        prefillable positions gets them from one admission pass instead of N forced decode steps; Session.stats() reports the
+        passes.  The keyword OWNS the option for this session: whatever Engine.set_option("session_prefill", ...) left is
+        replaced for the session_begin and put back when the session closes (options cannot change while a session is open)."""
+        return Session(self, opts, max_prompt, temperature, beam, patience, detect_language, prefill)
 
     def generate_beam(self, prompts: Sequence[Sequence[int]], beam: int, opts, patience: float = 1.0,
                       sot_index: Optional[Sequence[int]] = None) -> GenResult:
@@ -485,6 +492,32 @@ def _align_batch_call(engine: "Engine", fn, what: str, lead, packed, debug: bool
         [w[i, :, :nt[i]].copy() for i in range(n)] if debug else None)
 
 
+def session_prefill_positions(prompt_len: int, sot_index: Optional[int], threshold: int, placeholder: bool = False) -> int:
+    """The per-clip rule of option session_prefill, as the library applies it at admission (csrc/prefill_tables.hpp): how many
+    leading prompt positions an admission pass computes, 0 = the clip is forced token by token.  sot_index = the clip's
+    <|startoftranscript|> index when the no-speech probability is wanted (that position stays a real step), else None;
+    placeholder = the prompt carries Session.DETECT (never prefilled)."""
+    if threshold <= 0 or placeholder:
+        return 0
+    p = prompt_len - 1
+    if sot_index is not None and sot_index >= 0:
+        p = min(p, sot_index)
+    return p if p >= threshold else 0
+
+
+def session_prefill_value(v) -> int:
+    """session_prefill keyword -> option value: False / None / 0 off, True = config.SESSION_PREFILL_DEFAULT, else the integer."""
+    from .config import SESSION_PREFILL_DEFAULT
+    if v is None or v is False:
+        return 0
+    if v is True:
+        return SESSION_PREFILL_DEFAULT
+    v = int(v)
+    if v < 0:
+        raise ValueError(f"session_prefill {v} must be >= 0")
+    return v
+
+
 @dataclass
 class SessionResult:
     id: int
@@ -502,8 +535,9 @@ class Session:
     DETECT = -1   # TTASR_TOKEN_DETECT: the language placeholder of an armed session's prompts
 
     def __init__(self, engine: Engine, opts, max_prompt: int, temperature: float = 0.0, beam: int = 1,
-                 patience: Optional[float] = None, detect_language=False):
+                 patience: Optional[float] = None, detect_language=False, prefill: int = 0):
         self.engine, self.opts, self.max_prompt = engine, opts, int(max_prompt)
+        self.prefill = session_prefill_value(prefill)
         self.max_new_tokens = int(opts.max_new_tokens)
         self.window = 2 * engine.audio_ctx * 160
         self.open = False
@@ -522,12 +556,23 @@ class Session:
                 raise ValueError("a beam session decodes without sampling (temperature must be 0)")
             if beam > engine.max_batch:
                 raise ValueError(f"max_batch {engine.max_batch} holds no group of {beam} rows")
-            engine._check(engine.lib.ttasr_session_begin_beam(engine.h, C.byref(opts), self.max_prompt, beam, C.c_float(patience)),
-                          "session_begin_beam")
-        else:
-            engine._check(engine.lib.ttasr_session_begin(engine.h, C.byref(opts), self.max_prompt, C.c_float(temperature)),
-                          "session_begin")
-        self.open = True
+        # the option is read by session_begin; the keyword owns it for this session: the value the engine had is put back at close()
+        # (a refused begin puts it back at once).  Nothing is called when the option already has the value.
+        self._prefill_before = int(getattr(engine, "_session_prefill", 0))
+        if self.prefill != self._prefill_before:
+            engine.set_option("session_prefill", self.prefill)
+        try:
+            if self.beam:
+                rc, what = engine.lib.ttasr_session_begin_beam(engine.h, C.byref(opts), self.max_prompt, beam, C.c_float(patience)), \
+                    "session_begin_beam"
+            else:
+                rc, what = engine.lib.ttasr_session_begin(engine.h, C.byref(opts), self.max_prompt, C.c_float(temperature)), \
+                    "session_begin"
+            self.open = rc == 0
+        finally:
+            if self.prefill != self._prefill_before and not self.open:
+                engine.set_option("session_prefill", self._prefill_before)
+        engine._check(rc, what)
         if detect_language:   # armed before the first submit; a refusal closes the session again
             try:
                 if detect_language is True:
@@ -553,6 +598,8 @@ class Session:
         if self.open:
             self.open = False
             self.engine._check(self.engine.lib.ttasr_session_end(self.engine.h), "session_end")
+            if self.prefill != self._prefill_before:   # options are refused while a session is open: put back here, behind its end
+                self.engine.set_option("session_prefill", self._prefill_before)
 
     def submit(self, clips: Sequence[np.ndarray], prompts: Sequence[Sequence[int]], max_new: Optional[Sequence[int]] = None
                ) -> List[int]:
@@ -761,5 +808,9 @@ class Session:
     def stats(self) -> Dict[str, float]:
         a = (C.c_double * 8)()
         self.engine._check(self.engine.lib.ttasr_session_stats(self.engine.h, a), "session_stats")
-        return dict(zip(("steps", "polls", "encodes", "clips_encoded", "live_row_steps", "encode_ms", "decode_ms", "queued"),
-                        (float(v) for v in a)))
+        out = dict(zip(("steps", "polls", "encodes", "clips_encoded", "live_row_steps", "encode_ms", "decode_ms", "queued"),
+                       (float(v) for v in a)))
+        b = (C.c_double * 4)()   # the admission passes of option session_prefill (all 0 with the option off)
+        self.engine._check(self.engine.lib.ttasr_session_prefill_stats(self.engine.h, b), "session_prefill_stats")
+        out.update(zip(("prefill_passes", "prefill_clips", "prefill_positions", "prefill_ms"), (float(v) for v in b)))
+        return out

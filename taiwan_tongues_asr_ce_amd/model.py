@@ -805,7 +805,7 @@ class WhisperModel:
                         suppress_blank: bool = True, temperature: Union[float, Sequence[float]] = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0),
                         best_of: int = 5, compression_ratio_threshold: Optional[float] = 2.4, patience: float = 1.0,
                         hotwords: Optional[str] = None, prefix: Optional[str] = None, continuous: bool = False,
-                        multilingual: bool = False, detect_in_session: bool = False
+                        multilingual: bool = False, detect_in_session: bool = False, session_prefill: Union[int, bool] = 0
                         ) -> List[Tuple[List[Segment], TranscriptionInfo]]:
         """Several FILES in lock step: every round takes the next 30-s window of each unfinished file and runs them as
         ONE engine pass (log-mel, encoder, beam search with one previous-text prompt per file), so a folder is
@@ -830,8 +830,16 @@ class WhisperModel:
         multilingual=True: every window is detected again - lock-step form: between its encoder pass and its search, from the
         encoder state that is resident anyway; continuous=True: inside the session, every window goes in with the placeholder -
         and its prompt carries that window's language token (info.window_languages lists them); info.language stays the
-        file-level answer."""
+        file-level answer.
+        session_prefill=N (continuous=True only; True = config.SESSION_PREFILL_DEFAULT): a window whose prompt has at least N
+        prefillable positions - the previous text of condition_on_previous_text, up to <|startoftranscript|> - gets them from one
+        admission pass of the session instead of N forced decode steps (Engine.session(prefill=N)); windows
+        that go in with the language placeholder are forced as before."""
+        from .engine import session_prefill_value
         eng = self.engine
+        session_prefill = session_prefill_value(session_prefill)
+        if session_prefill and not continuous:
+            raise ValueError("session_prefill needs continuous=True (the lock-step passes prefill their prompts already: option prefill)")
         if continuous and not callable(getattr(eng, "session", None)):
             raise ValueError("continuous=True needs an engine with continuous-batching sessions (Engine.session)")
         if detect_in_session and not continuous:
@@ -865,7 +873,7 @@ class WhisperModel:
             fs["language"], fs["lang_tok"], fs["lang_info"] = lang, self._lang_token(lang), (lang, lang_p, all_p)
             fs["decided"] = not w
         if continuous:
-            self._run_continuous(files, p, per_window=multilingual)
+            self._run_continuous(files, p, per_window=multilingual, session_prefill=session_prefill)
         while not continuous:
             active = [fs for fs in files if fs["seek"] < fs["n_total"]]
             if not active:
@@ -919,7 +927,7 @@ class WhisperModel:
         """(language, probability, all probabilities) of a SessionResult that was detected inside its session."""
         return LANGUAGES[r.language], float(r.language_probs[r.language]), self._ranked(r.language_probs)
 
-    def _run_continuous(self, files: List[dict], p: dict, per_window: bool = False):
+    def _run_continuous(self, files: List[dict], p: dict, per_window: bool = False, session_prefill: int = 0):
         """transcribe_many(continuous=True): the windows of all files through one beam session, one window per file in flight.
         A window's attempts follow `_decode_with_fallback` (temperature 0: beam search of beam_size rows, or greedy with one;
         temperature > 0: best_of samples seeded as `transcribe` seeds them), its result `_finish_window`.
@@ -945,6 +953,8 @@ class WhisperModel:
         eng.set_audio_ctx(0)
         arm = per_window or any(not fs["decided"] for fs in todo)
         kw = dict(detect_language=True) if arm else {}   # armed only when a window asks for it
+        if session_prefill:
+            kw["prefill"] = int(session_prefill)          # prompts of at least that many positions: one admission pass, not steps
         with eng.session(opts, n_ctx - 1, beam=width, patience=p["patience"], **kw) as s:
             inflight: Dict[int, dict] = {}
 
@@ -1035,7 +1045,8 @@ class WhisperModel:
                           task: str = "transcribe",
                           without_timestamps: bool = True, max_new_tokens: int = 224,
                           row_max_new: Optional[Sequence[int]] = None, beam_size: int = 1, patience: float = 1.0,
-                          initial_prompt: Optional[str] = None, word_timestamps: bool = False, detect_in_session: bool = False):
+                          initial_prompt: Optional[str] = None, word_timestamps: bool = False, detect_in_session: bool = False,
+                          session_prefill: Union[int, bool] = 0):
         """transcribe_batch's contract (clips <= 30 s each, sampled token ids per clip, input order) for any number of clips,
         through a continuous-batching session: a clip that finishes hands its decode row to the next one instead of waiting for
         the rest of its batch.  row_max_new (optional): one token budget per clip, each in [1, max_new_tokens].
@@ -1047,8 +1058,12 @@ class WhisperModel:
         passes BEFORE the session begins (a session owns the encoder while it is open): one extra encoder pass over those
         clips.  detect_in_session=True: no pass before the session - a None clip goes in with the language placeholder
         (Session.DETECT) and its first decode step finds the language on the device (one more decode step, no encoder work).
-        (language, probability) per clip of the last call: `last_language_info`."""
-        from .engine import Session
+        (language, probability) per clip of the last call: `last_language_info`.
+        session_prefill=N (True = config.SESSION_PREFILL_DEFAULT): a clip whose prompt - the initial_prompt's previous text - has
+        at least N prefillable positions gets them from one admission pass of the session instead of N forced decode steps
+        (Engine.session(prefill=N)); clips that go in with the language placeholder are forced as before."""
+        from .engine import Session, session_prefill_value
+        session_prefill = session_prefill_value(session_prefill)
         if len(clips) == 0:
             self.last_language_info = []
             return []
@@ -1079,6 +1094,8 @@ class WhisperModel:
         opts = eng.gen_opts(n_new, timestamps=not without_timestamps, sot_index=sot_index)
         out: List[Optional[List[int]]] = [None] * len(clips)
         kw = dict(detect_language=True) if any(late) else {}   # armed only when a clip asks for it
+        if session_prefill:
+            kw["prefill"] = int(session_prefill)
         with (eng.session(opts, len(prompt), beam=beam, patience=patience, **kw) if beam > 1 else eng.session(opts, len(prompt), **kw)) as s:
             ids = s.submit([np.ascontiguousarray(c, dtype=np.float32) for c in clips], prompts, caps)
             where = {cid: i for i, cid in enumerate(ids)}

@@ -58,12 +58,21 @@ class BatchedWhisperASR(MI355XWhisperASR):
     (WhisperModel.transcribe_windows(language=None)) and reports the detected language and probability instead of "zh" and
     1.0, with a warning when the probability is under 0.5 as the reference's adapter logs it.  In continuous mode None needs
     `detect_in_session=True` (opt-in): a session owns the encoder while it is open, so every request goes in with the language
-    placeholder and its first decode step finds the language on the device (Engine.session(detect_language=True))."""
+    placeholder and its first decode step finds the language on the device (Engine.session(detect_language=True)).
+
+    `session_prefill=N` (opt-in, continuous=True only; True = config.SESSION_PREFILL_DEFAULT): the initial_prompt's positions in
+    front of <|startoftranscript|> come from one admission pass of the session instead of one forced decode step each, when there
+    are at least N of them (Engine.session(prefill=N)); requests that carry the language placeholder are forced as before."""
 
     def __init__(self, max_clips: int = 6, max_wait_ms: float = 5.0, audio_ctx=None, max_new_tokens: int = 224,
-                 continuous: bool = False, word_timestamps: bool = False, detect_in_session: bool = False, **kwargs):
+                 continuous: bool = False, word_timestamps: bool = False, detect_in_session: bool = False,
+                 session_prefill=0, **kwargs):
+        from .engine import session_prefill_value
         if continuous and audio_ctx is not None:
             raise ValueError("continuous=True encodes the full window: audio_ctx must be None")
+        self.session_prefill = session_prefill_value(session_prefill)
+        if self.session_prefill and not continuous:
+            raise ValueError("session_prefill is for continuous=True (the lock-step passes prefill their prompts already)")
         self.continuous = bool(continuous)
         self.word_timestamps = bool(word_timestamps)
         beam = int(kwargs.pop("beam_size", 5))
@@ -156,6 +165,8 @@ class BatchedWhisperASR(MI355XWhisperASR):
             eng.set_audio_ctx(0)
             opts = eng.gen_opts(min(self.max_new_tokens, model.dims.n_text_ctx - len(prompt)), timestamps=True, sot_index=sot_index)
             kw_s = dict(detect_language=True) if detect else {}
+            if self.session_prefill:
+                kw_s["prefill"] = self.session_prefill
             with (eng.session(opts, len(prompt), beam=beam, **kw_s) if beam > 1 else eng.session(opts, len(prompt), **kw_s)) as s:
                 if self.word_timestamps:
                     s.hold()

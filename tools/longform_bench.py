@@ -96,7 +96,7 @@ def make_engine_class(boost, counters):
     return BenchEngine
 
 
-def run(model, counters, files, kw, continuous):
+def run(model, counters, files, kw, continuous, session_prefill=0):
     for k in ("encode_ms", "decode_ms", "steps", "attempts"):
         counters[k] = 0
     stats = {}
@@ -113,6 +113,8 @@ def run(model, counters, files, kw, continuous):
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         t0 = time.perf_counter()
+        if session_prefill:
+            kw = dict(kw, session_prefill=session_prefill)
         out = model.transcribe_many(files, continuous=continuous, **kw)
         dt = time.perf_counter() - t0
     audio_s = sum(len(f) for f in files) / 16000.0
@@ -125,6 +127,10 @@ def run(model, counters, files, kw, continuous):
                   "decode_steps": int(stats["steps"]), "attempts": int(stats["clips_encoded"]),
                   "mean_live_rows_per_step": round(stats["live_row_steps"] / max(1.0, stats["steps"]), 2),
                   "encoder_passes": int(stats["encodes"])})
+        if session_prefill:   # the admission passes of option session_prefill
+            m.update({"session_prefill": int(session_prefill), "prefill_passes": int(stats["prefill_passes"]),
+                      "prefill_clips": int(stats["prefill_clips"]), "prefill_positions": int(stats["prefill_positions"]),
+                      "prefill_ms": round(stats["prefill_ms"], 1)})
     else:
         m.update({"encode_ms": round(counters["encode_ms"], 1), "decode_ms": round(counters["decode_ms"], 1),
                   "decode_steps": counters["steps"], "attempts": counters["attempts"]})
@@ -146,6 +152,9 @@ def main():
     ap.add_argument("--xkv-fp8", type=int, default=0, choices=[0, 1, 2],
                     help="option xkv_fp8: 0 the 16-bit cross-KV cache, 1 the e4m3 copy for unshared static rows only, 2 wherever a "
                          "kernel for it exists (shared rows, sessions)")
+    ap.add_argument("--session-prefill", type=int, default=0, metavar="N",
+                    help="also run the continuous form with transcribe_many(session_prefill=N): prompts of at least N prefillable "
+                         "positions come from an admission pass of the session instead of forced decode steps")
     args = ap.parse_args()
     counters = {}
     model = WhisperModel(f"synthetic:{args.model}", device="cuda", compute_type="bfloat16", max_batch=args.max_batch,
@@ -161,6 +170,8 @@ def main():
     warm = [f[: 16000 * 45] for f in files[:2]]
     for cont in (False, True):
         run(model, counters, warm, dict(off, max_new_tokens=16), cont)
+    if args.session_prefill:
+        run(model, counters, warm, dict(off, max_new_tokens=16), True, args.session_prefill)
     line = {"metric": "longform_audio_s_per_s", "model": args.model, "compute": "bf16", "xkv_fp8": args.xkv_fp8, "max_batch": args.max_batch, "beam": 5,
             "eot_boost": args.eot_boost, "max_new_tokens": args.max_new, "files": args.files,
             "audio_s": round(sum(len(f) for f in files) / 16000.0, 1)}
@@ -169,6 +180,10 @@ def main():
         sb, b = run(model, counters, files, off, True)
         line["thresholds_off"] = {"lock_step": a, "continuous": b, "ratio": round(b["audio_s_per_s"] / a["audio_s_per_s"], 3),
                                   "files_identical": int(sum(x == y for x, y in zip(sa, sb)))}
+        if args.session_prefill:
+            sp, pm = run(model, counters, files, off, True, args.session_prefill)
+            line["thresholds_off"].update({"continuous_prefill": pm, "ratio_prefill_over_continuous": round(pm["audio_s_per_s"] / b["audio_s_per_s"], 3),
+                                           "files_identical_prefill": int(sum(x == y for x, y in zip(sb, sp)))})
         print(json.dumps(line["thresholds_off"]), file=sys.stderr, flush=True)
     if args.regime in ("ref", "both"):
         ff = files[: args.fallback_files]
@@ -181,6 +196,12 @@ def main():
                                       "lock_step": c, "continuous": d,
                                       "ratio": round(d["audio_s_per_s"] / c["audio_s_per_s"], 3),
                                       "files_identical": int(sum(x == y for x, y in zip(sc, sd)))}
+        if args.session_prefill:
+            sp, pm = run(model, counters, ff, ref, True, args.session_prefill)
+            pm["attempts_per_30s_window"] = round(pm["attempts"] / n_win, 2)
+            line["reference_defaults"].update({"continuous_prefill": pm,
+                                               "ratio_prefill_over_continuous": round(pm["audio_s_per_s"] / d["audio_s_per_s"], 3),
+                                               "files_identical_prefill": int(sum(x == y for x, y in zip(sd, sp)))})
     s = json.dumps(line)
     print(s)
     if args.out:

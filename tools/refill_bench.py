@@ -15,6 +15,14 @@ row of the token embedding is scaled (--eot-boost) so that hypotheses finish at 
   (a) static: lock-step ttasr_generate_beam passes of G = max_batch / K clips (prefill = 0 and enc_gemm = 3, the session's forms);
   (b) the beam session (ttasr_session_begin_beam), refill_overlap = 0;  (c) the same with refill_overlap = 1.
     python tools/refill_bench.py --beam 5 [--clips 120] [--eot-boost 8] [--out profiles/refill_beam_bench.json]
+
+--prev-tokens P[,P...] with --session-prefill N[,N...]: the threshold sweep of option session_prefill.  Only
+the session runs (refill_overlap = 0), once per (P, N): every clip carries a previous-text prompt of P random tokens in front of the
+sot sequence, and clips with at least N prefillable positions get them from an admission pass (N = 0: forced through decode
+steps).  One JSON line per pair - audio-s/s, steps, live rows per step, decode / encoder ms, the four prefill statistics and whether
+the tokens equal the N = 0 run - appended to --out.  With --beam K the same through the beam session.
+    python tools/refill_bench.py --clips 64 --prev-tokens 8,16,32,64,128,223 --session-prefill 0,1,8,16,32,64 [--beam 5] \
+        --out profiles/session_prefill_threshold.jsonl
 """
 from __future__ import annotations
 
@@ -51,7 +59,11 @@ def main():
     ap.add_argument("--xkv-fp8", type=int, default=0, choices=[0, 1, 2],
                     help="option xkv_fp8: 0 the 16-bit cross-KV cache, 1 the e4m3 copy for unshared static rows only, 2 wherever a "
                          "kernel for it exists (shared rows, sessions)")
+    ap.add_argument("--prev-tokens", default=None, help="comma list: previous-text tokens in front of the sot sequence (the session_prefill sweep)")
+    ap.add_argument("--session-prefill", default="0", help="comma list of option session_prefill values for the sweep")
     args = ap.parse_args()
+    if args.prev_tokens is not None:
+        return main_prefill_sweep(args)
     if args.beam:
         return main_beam(args)
     dims = PRESETS[args.model]
@@ -141,6 +153,60 @@ def main():
     if args.out:
         with open(args.out, "w") as f:
             f.write(s + "\n")
+    eng.close()
+
+
+def main_prefill_sweep(args):
+    dims = PRESETS[args.model]
+    K = args.beam
+    B = (30 if args.batch == 32 else args.batch) if K else args.batch
+    N = args.clips
+    new_tokens = args.new_tokens if args.new_tokens != 128 else 96
+    eng = Engine(dims, COMPUTE_BF16, B)
+    eng.load_weights(synth.iter_weights(dims))
+    if args.no_graph:
+        eng.set_option("graph", 0)
+    st = eng.special
+    opts = eng.gen_opts(new_tokens, timestamps=False, suppress_eot=True, no_speech=False, check_interval=args.check_interval)
+    clips = [synth.noise_clip(i) for i in range(N)]
+    caps = np.random.Generator(np.random.Philox(key=args.seed)).integers(32, new_tokens + 1, size=N).astype(np.int32)
+    rng = np.random.default_rng(args.seed)
+    lines = []
+
+    def run(prompts, n_pre):
+        out = [None] * N
+        t0 = time.perf_counter()
+        with (eng.session(opts, len(prompts[0]), beam=K, prefill=n_pre) if K else eng.session(opts, len(prompts[0]), prefill=n_pre)) as s:
+            ids = s.submit(clips, prompts, caps)
+            where = {cid: i for i, cid in enumerate(ids)}
+            for r in s.drain():
+                out[where[r.id]] = r.tokens
+            stt = s.stats()
+        dt = time.perf_counter() - t0
+        return out, stt, dt
+
+    for P in [int(v) for v in args.prev_tokens.split(",")]:
+        prompts = [[st.sot_prev] + rng.integers(300, 20000, size=P).tolist() + [st.sot, st.lang_zh, st.transcribe, st.no_timestamps]
+                   for _ in range(N)]
+        base = None
+        for n_pre in [int(v) for v in args.session_prefill.split(",")]:
+            run(prompts[:B + 2] + prompts[:N - B - 2], n_pre)              # warm-up: graphs, the pass's workspace
+            toks, stt, dt = run(prompts, n_pre)
+            if n_pre == 0:
+                base = toks
+            line = {"metric": "session_prefill_threshold", "model": args.model, "compute": "bf16", "beam": K, "max_batch": B, "clips": N,
+                    "prev_tokens": P, "prompt_tokens": len(prompts[0]), "session_prefill": n_pre,
+                    "audio_s_per_s": round(30.0 * N / dt, 1), "wall_s": round(dt, 3), "decode_steps": int(stt["steps"]),
+                    "mean_live_rows_per_step": round(stt["live_row_steps"] / max(1.0, stt["steps"]), 2),
+                    "decode_ms": round(stt["decode_ms"], 1), "encode_ms": round(stt["encode_ms"], 1),
+                    "prefill_passes": int(stt["prefill_passes"]), "prefill_clips": int(stt["prefill_clips"]),
+                    "prefill_positions": int(stt["prefill_positions"]), "prefill_ms": round(stt["prefill_ms"], 2),
+                    "clips_equal_forced": None if base is None else int(sum(x == y for x, y in zip(toks, base)))}
+            print(json.dumps(line), flush=True)
+            lines.append(line)
+            if args.out:
+                with open(args.out, "a") as f:
+                    f.write(json.dumps(line) + "\n")
     eng.close()
 
 

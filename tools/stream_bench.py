@@ -33,7 +33,8 @@ async def run(args):
         raise SystemExit("--continuous encodes the full window: --audio-ctx must be none")
     asr = BatchedWhisperASR(max_clips=max_clips, max_wait_ms=args.max_wait_ms, beam_size=beam, continuous=args.continuous,
                             audio_ctx=None if args.audio_ctx == "none" else (args.audio_ctx if args.audio_ctx == "auto" else int(args.audio_ctx)),
-                            max_new_tokens=args.new_tokens, model_size=f"synthetic:{args.model}", compute_type="bfloat16")
+                            max_new_tokens=args.new_tokens, model_size=f"synthetic:{args.model}", compute_type="bfloat16",
+                            session_prefill=args.session_prefill)
     utter = [np.clip(synth.noise_clip(1000 + i, int(args.utterance_s * 16000)) * 32768.0, -32768, 32767).astype("<i2").tobytes()
              for i in range(args.streams)]
     lat = []
@@ -59,8 +60,10 @@ async def run(args):
     out = {
         "workload": f"C5 streaming: {args.streams} concurrent streams x {args.rounds} utterances of {args.utterance_s} s, "
                     f"whisper-{args.model} geometry bf16, beam {beam}, <= {args.new_tokens} tokens, audio_ctx={args.audio_ctx}, "
-                    f"period {args.period} s, 1 GPU" + (", continuous beam session" if args.continuous else ""),
-        "latency_ms": {"p50": round(float(np.percentile(lat_ms, 50)), 1), "p99": round(float(np.percentile(lat_ms, 99)), 1),
+                    f"period {args.period} s, 1 GPU" + (", continuous beam session" if args.continuous else "")
+                    + (f", session_prefill {args.session_prefill}" if args.session_prefill else ""),
+        "latency_ms": {"p50": round(float(np.percentile(lat_ms, 50)), 1), "p95": round(float(np.percentile(lat_ms, 95)), 1),
+                       "p99": round(float(np.percentile(lat_ms, 99)), 1),
                        "max": round(float(lat_ms.max()), 1)},
         "audio_s_per_s": round(len(lat) * args.utterance_s / (wall * args.rounds / (args.rounds + 1)), 1),
         "engine_passes": len(sizes), "mean_clips_per_pass": round(float(np.mean(sizes)), 2) if sizes else None,
@@ -82,6 +85,9 @@ def main():
     ap.add_argument("--max-clips", type=int, default=0)
     ap.add_argument("--max-wait-ms", type=float, default=5.0)
     ap.add_argument("--continuous", action="store_true", help="BatchedWhisperASR(continuous=True): one beam session, no passes")
+    ap.add_argument("--session-prefill", type=int, default=0, metavar="N",
+                    help="with --continuous: BatchedWhisperASR(session_prefill=N) - the initial prompt's positions come from an "
+                         "admission pass of the session when there are at least N of them")
     asyncio.run(run(ap.parse_args()))
 
 
