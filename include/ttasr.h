@@ -148,6 +148,28 @@ TTASR_API int ttasr_encode(ttasr_ctx* ctx, int32_t B, float* out_enc_host);
 /* Test hooks. */
 TTASR_API int ttasr_set_encoder_output(ttasr_ctx* ctx, const float* enc_host, int32_t B); /* then builds cross K/V */
 TTASR_API int ttasr_get_cross_kv(ttasr_ctx* ctx, int32_t layer, int32_t which /*0 K, 1 V*/, int32_t B, float* out_host /*[B][H][T][64]*/);
+/* Known-answer hooks for the cross-attention kernels (tests/test_gpu_xattn_kernels.py).
+ *
+ * The e4m3 copy of the cross-KV cache (option "xkv_fp8") as it is resident: the raw OCP e4m3fn bytes of block (layer, which) of the
+ * first B clips and the f32 scale of every (clip, head) block (value = code x scale).  TTASR_E_INVALID when no valid copy exists
+ * (option off, f32 engine, no encode since the option was set); otherwise the argument checks of the 16-bit readback above.
+ * Read-only, and therefore also allowed while a session is open: B then counts cross-KV slots (up to max_batch), and which clip
+ * a slot holds is what the session's row report says (greedy: row = slot; beam: group = slot). */
+TTASR_API int ttasr_get_cross_kv_fp8(ttasr_ctx* ctx, int32_t layer, int32_t which /*0 K, 1 V*/, int32_t B,
+                                     uint8_t* out_codes_host /*[B][H][T][64]*/, float* out_scale_host /*[B][H]*/);
+/* The decode step's cross-attention of `layer`, ONCE, on caller-supplied queries against the resident cache: n_rows rows, row r
+ * reading clip r / kv_div (kv_div >= 1 divides n_rows; n_rows / kv_div clips must be resident).  n_slab = 0: q_host is f32
+ * [n_rows][d_model], cast to the engine type.  n_slab = 1..4 (16-bit engines): q_host is n_slab f32 partial tiles
+ * [n_slab][n_rows][d_model], summed by the kernel (with a zero bias) the way the step's kernels sum the K-split q GEMM.  The query
+ * is used as given: the 1/8 of the attention lives in the q weights, not in the kernels.  done_host: optional int32 [n_rows],
+ * nonzero = finished row (copied to a flag array of the hook's own).  out_host: f32 [n_rows][d_model]; the device output is
+ * zero-filled before the launch, so rows a kernel does not write come back 0.  The launch goes through the very function the
+ * step calls to choose its kernel, so every option that steers the step ("xkv_fp8", "xattn_mq_fp8", "xsplit", "xattn_pipeline",
+ * "xattn_nontemporal", "xattn_deep_items", "xattn_mq_slices") steers this call; sig_buf (optional, sig_len bytes) receives the
+ * signature of what ran, in the spelling of the bench signature call below plus the slice count of the frame-split forms.
+ * Refused in an open session and without resident encoder state; search state and captured step graphs are not touched. */
+TTASR_API int ttasr_cross_attn_probe(ttasr_ctx* ctx, int32_t layer, int32_t n_rows, int32_t kv_div, const float* q_host, int32_t n_slab,
+                                     const int32_t* done_host, float* out_host, char* sig_buf, int32_t sig_len);
 
 /* Short-window option (opt-in, a behavioural change versus Whisper's fixed 30-s training window, the
  * same trade whisper.cpp's `audio_ctx` makes): subsequent log_mel / encode / generate calls use only the first n_ctx

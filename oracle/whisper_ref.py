@@ -704,3 +704,43 @@ def token_timestamps(weights: torch.Tensor, n_prefix: int, num_frames: Optional[
     ti, tj = dtw_path(-w.double().numpy())
     jumps = np.pad(np.diff(ti), (1, 0), constant_values=1).astype(bool)
     return tj[jumps] * time_precision
+
+
+# ---- the e4m3 cross-KV copy and the decode step's cross-attention (csrc/kernels_fp8.hip, kernels_attn.hip) -------------------
+# References for tests/test_gpu_xattn_kernels.py, which reaches the kernels through the known-answer hooks
+# ttasr_get_cross_kv_fp8 / ttasr_cross_attn_probe.
+E4M3_MAX = 448.0
+
+
+def e4m3_encode(x_f32: np.ndarray) -> np.ndarray:
+    """float32 -> OCP e4m3fn codes (uint8): round to nearest, ties to the even code, subnormals kept.  Inputs are expected
+    inside the finite range (|x| < 464, which rounds to 448 or below)."""
+    x = np.ascontiguousarray(x_f32, dtype=np.float32)
+    return torch.from_numpy(x).to(torch.float8_e4m3fn).view(torch.uint8).numpy()
+
+
+def e4m3_decode(codes: np.ndarray) -> np.ndarray:
+    """e4m3fn codes (uint8) -> float64 (exact; 0x7f / 0xff are NaN)."""
+    c = np.ascontiguousarray(codes, dtype=np.uint8)
+    return torch.from_numpy(c).view(torch.float8_e4m3fn).to(torch.float64).numpy()
+
+
+def xkv_quant_ref(block_f32: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """xkv_quant_block restated in float32: block_f32 [..., T, 64] (one block per leading index) -> (codes uint8 of the same
+    shape, scale float32 [...]).  amax; sc = amax * f32(1 / 448), or 1 for an all-zero block; inv = f32(1) / sc (correctly
+    rounded, as HIP's default division is); code = e4m3(v * inv) with ONE float32 multiply."""
+    v = np.ascontiguousarray(block_f32, dtype=np.float32)
+    amax = np.abs(v).max(axis=(-2, -1)).astype(np.float32)
+    sc = np.where(amax > 0, amax * (np.float32(1.0) / np.float32(E4M3_MAX)), np.float32(1.0)).astype(np.float32)
+    inv = (np.float32(1.0) / sc).astype(np.float32)
+    return e4m3_encode(v * inv[..., None, None]), sc
+
+
+def cross_attn_ref(q: np.ndarray, K: np.ndarray, V: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """softmax(q . K^T) . V in float64 per leading index: q [..., 64], K / V [..., T, 64] -> (out [..., 64], scores [..., T]).
+    No 1 / 8: the engine folds head_dim ** -0.5 into the q weights, and the probe supplies q directly."""
+    q, K, V = (np.asarray(a, dtype=np.float64) for a in (q, K, V))
+    s = np.einsum("...c,...tc->...t", q, K)
+    p = np.exp(s - s.max(axis=-1, keepdims=True))
+    p /= p.sum(axis=-1, keepdims=True)
+    return np.einsum("...t,...tc->...c", p, V), s

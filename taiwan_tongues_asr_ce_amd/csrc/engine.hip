@@ -383,6 +383,67 @@ int ttasr_get_cross_kv(ttasr_ctx* c, int32_t layer, int32_t which, int32_t B, fl
   });
 }
 
+int ttasr_get_cross_kv_fp8(ttasr_ctx* c, int32_t layer, int32_t which, int32_t B, uint8_t* out_codes, float* out_scale) {
+  return guarded(c, [&]() -> int {
+  if (!c) return TTASR_E_INVALID;
+  if (!c->finalized) return fail(c, TTASR_E_INVALID, "weights not finalized (call ttasr_finalize_weights first)");
+  if (B < 1 || B > c->maxB) return fail(c, TTASR_E_INVALID, "batch %d outside [1, max_batch=%d]", B, c->maxB);
+  // read-only: also allowed while a session is open, where B counts cross-KV slots (ttasr_session_rows maps them to clips)
+  if (layer < 0 || layer >= c->cfg.dec_layers || which < 0 || which > 1 || !out_codes || !out_scale || (!c->sess && B > c->B_enc))
+    return fail(c, TTASR_E_INVALID, "bad arguments");
+  if (!c->lowp || !c->xkv_fp8 || !c->xkv8 || !c->xkv8_scale || !c->xkv8_valid)
+    return fail(c, TTASR_E_INVALID, "no valid e4m3 copy of the cross-KV cache (16-bit engine, option xkv_fp8, then an encode)");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t n = (size_t)B * c->H * c->T * 64;
+  const uint8_t* src = c->xkv8 + (size_t)layer * c->xkv_layer_elems + (size_t)which * c->xkv_which_elems;
+  const float* sc = c->xkv8_scale + ((size_t)layer * 2 + which) * c->maxB * c->H;
+  HIPCHK(c, hipMemcpyAsync(out_codes, src, n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out_scale, sc, (size_t)B * c->H * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return TTASR_OK;
+  });
+}
+
+int ttasr_cross_attn_probe(ttasr_ctx* c, int32_t layer, int32_t n_rows, int32_t kv_div, const float* q, int32_t n_slab,
+                           const int32_t* done, float* out, char* sig_buf, int32_t sig_len) {
+  return guarded(c, [&]() -> int {
+  TRY(check_ready(c, n_rows));   // refused in an open session
+  if (layer < 0 || layer >= c->cfg.dec_layers || !q || !out || n_slab < 0 || n_slab > 4 || (sig_buf && sig_len < 1))
+    return fail(c, TTASR_E_INVALID, "bad arguments");
+  if (kv_div < 1 || n_rows % kv_div != 0) return fail(c, TTASR_E_INVALID, "kv_div %d does not divide the %d rows", kv_div, n_rows);
+  if (c->B_enc < 1 || n_rows / kv_div > c->B_enc)
+    return fail(c, TTASR_E_INVALID, "%d clips needed but the resident encoder state holds %d", n_rows / kv_div, c->B_enc);
+  if (n_slab > 0 && !c->lowp) return fail(c, TTASR_E_INVALID, "n_slab > 0 needs a 16-bit engine (only its step splits the q GEMM into partial tiles)");
+  hipStream_t s = c->stream;
+  const int d = c->d;
+  if (!c->probe_done) TRY(dalloc(c, &c->probe_done, (size_t)c->maxB * 4));
+  if (!c->probe_zero) TRY(dalloc(c, &c->probe_zero, (size_t)d * 4));
+  SlabIn sq;
+  if (n_slab > 0) {   // the q GEMM's K-split layout of the step: [n_slab][max_batch rows][d] f32, bias added by the consumer (zero here)
+    for (int i = 0; i < n_slab; ++i)
+      HIPCHK(c, hipMemcpyAsync(c->slab + (size_t)i * c->maxB * d, q + (size_t)i * n_rows * d, (size_t)n_rows * d * 4, hipMemcpyHostToDevice, s));
+    sq.slab = c->slab; sq.bias = c->probe_zero; sq.n = n_slab; sq.stride = (int64_t)c->maxB * d; sq.ld = d;
+  } else if (c->lowp) {
+    HIPCHK(c, hipMemcpyAsync(c->dx, q, (size_t)n_rows * d * 4, hipMemcpyHostToDevice, s));
+    TT_DISPATCH(c, launch_cast<T>(c->dx, (T*)c->dq, (int64_t)n_rows * d, s));
+  } else {
+    HIPCHK(c, hipMemcpyAsync(c->dq, q, (size_t)n_rows * d * 4, hipMemcpyHostToDevice, s));
+  }
+  if (done) HIPCHK(c, hipMemcpyAsync(c->probe_done, done, (size_t)n_rows * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemsetAsync(c->datt, 0, (size_t)n_rows * d * c->esz, s));   // rows a kernel does not write come back 0
+  g_kernel_sig[0] = 0; g_kernel_sig_on = true;
+  sched_cross_attn(c, layer, n_rows, kv_div, c->dq, c->datt, sq, done ? c->probe_done : nullptr);
+  g_kernel_sig_on = false;
+  if (sig_buf) snprintf(sig_buf, (size_t)sig_len, "%s", g_kernel_sig);
+  if (c->lowp) { TT_DISPATCH(c, launch_uncast<T>((const T*)c->datt, c->dx, (int64_t)n_rows * d, s));
+                 HIPCHK(c, hipMemcpyAsync(out, c->dx, (size_t)n_rows * d * 4, hipMemcpyDeviceToHost, s)); }
+  else HIPCHK(c, hipMemcpyAsync(out, c->datt, (size_t)n_rows * d * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+  return TTASR_OK;
+  });
+}
+
 int ttasr_decode_reset(ttasr_ctx* c, int32_t B) {
   return guarded(c, [&]() -> int {
   TRY(check_ready(c, B));

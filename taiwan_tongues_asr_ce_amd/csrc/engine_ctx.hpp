@@ -189,6 +189,7 @@ struct ttasr_ctx {
   bool no_prefill = false;  // option prefill = 0: feed prompts token by token (A/B testing)
   bool prefill_tiled = false;  // option prefill_tiled: tiled encoder GEMMs in the prefill pass whatever the row count (A/B testing)
   hipEvent_t ev[8]{};
+  int32_t* probe_done = nullptr; float* probe_zero = nullptr;   // ttasr_cross_attn_probe: its own [maxB] finished flags and a [d] zero bias (allocated by the first call)
   std::string bench_sig;     // signature of the kernel the last ttasr_bench_kernel call launched (ttasr_bench_kernel_signature)
   float phase_ms[4]{0, 0, 0, 0};
   // option enc_kernel_timing: one hipEvent after every launch of run_encoder / run_cross_kv, so the NEXT ttasr_encode also
@@ -338,6 +339,8 @@ void sched_dec_gemm(ttasr_ctx* c, const GemmArgs& g, const void* Wsh);
 int prefill_positions(const ttasr_ctx* c, int min_plen, const ttasr_gen_opts* o, bool ns_from_prefill = false);
 int step_graph(ttasr_ctx* c, int B, int mode, int nsteps = 1);
 void sched_detect_rows(ttasr_ctx* c, int B);                  // decode pass of B rows that ends in the language head (mode 3), launched directly
+// the decode step's cross-attention dispatch of `layer` for rows [0, n) on the context's stream (ttasr_cross_attn_probe)
+void sched_cross_attn(ttasr_ctx* c, int layer, int n, int kv_div, const void* dq, void* datt, const SlabIn& sq, const int32_t* done);
 void drop_graphs(ttasr_ctx* c);
 void drop_rule_graphs(ttasr_ctx* c);
 void drop_lang_graphs(ttasr_ctx* c);                          // the step graphs of armed sessions (StepShape::lang_rows)

@@ -188,6 +188,39 @@ int run_encoder(ttasr_ctx* c, int B) {
   return 0;
 }
 
+// The decode step's cross-attention of layer l for rows [row0, row0 + n): THE place that chooses between the e4m3 forms
+// (kernels_fp8.hip) and the 16-bit / f32 forms behind launch_cross_attn_decode.  Called by run_decode_rows and, with row0 = 0 and
+// caller-supplied queries, by the known-answer hook ttasr_cross_attn_probe - which therefore has no decision logic of its own.
+// dq: T [n][d] queries (unused where sq.n > 0: the query is summed from the K-split partial tiles); datt: T [n][d] output.
+template <typename T>
+void run_cross_attn(ttasr_ctx* c, int l, int row0, int n, int kv_div, const void* dq, void* datt, const SlabIn& sq, const int32_t* done) {
+  hipStream_t s = c->cur;
+  const bool skinny = sizeof(T) == 2 && !c->force_basic;
+  // cross-KV of clip (row / kv_div); a half-batch offset is only used with kv_div == 1
+  const T* Kx = (const T*)c->xkv + (int64_t)l * c->xkv_layer_elems + (int64_t)(row0 / kv_div) * c->H * c->T * 64;
+  bool fp8_done = false;
+  if constexpr (sizeof(T) == 2) {   // opt-in: the e4m3 copy of the cache, unshared rows that fill the chip (the single-pass kernel's case)
+    if (c->xkv_fp8 && c->xkv8_valid && kv_div == 1 && n * c->H >= 256 && skinny && !(c->skip_mask & 8)) {
+      const int64_t off = (int64_t)l * c->xkv_layer_elems + (int64_t)row0 * c->H * c->T * 64;
+      const float* ksc = c->xkv8_scale + ((size_t)l * 2) * c->maxB * c->H + (size_t)row0 * c->H;
+      fp8_done = launch_cross_attn_fp8<T>((const T*)dq, c->xkv8 + off, c->xkv8 + off + c->xkv_which_elems, ksc, ksc + (size_t)c->maxB * c->H,
+                                          (T*)datt, n, c->H, c->T, s, sq, done);
+    } else if (c->xkv_fp8 == 2 && c->xattn_mq_fp8 && c->xkv8_valid && kv_div >= 2 && skinny && !c->no_xsplit && !(c->skip_mask & 8)) {
+      // mode 2: rows that share a clip (beam hypotheses, sampled attempts) - wherever the 16-bit path would take
+      // cross_attn_mq_kernel with kv_div = 2..7, its e4m3 form; every other shape falls through to the 16-bit kernels
+      const int clip0 = row0 / kv_div;
+      const int64_t off = (int64_t)l * c->xkv_layer_elems + (int64_t)clip0 * c->H * c->T * 64;
+      const float* ksc = c->xkv8_scale + ((size_t)l * 2) * c->maxB * c->H + (size_t)clip0 * c->H;
+      fp8_done = launch_cross_attn_mq_fp8<T>((const T*)dq, c->xkv8 + off, c->xkv8 + off + c->xkv_which_elems, ksc, ksc + (size_t)c->maxB * c->H,
+                                             (T*)datt, n, c->H, c->T, kv_div, c->ko, s, c->xsplit_ws + (size_t)row0 * c->H * 8 * 66, sq,
+                                             c->maxB - row0, done);
+    }
+  }
+  if (!fp8_done && !(c->skip_mask & 8))
+    launch_cross_attn_decode<T>((const T*)dq, Kx, Kx + c->xkv_which_elems, (T*)datt, n, c->H, c->T, kv_div, c->ko, s,
+                                c->no_xsplit ? nullptr : c->xsplit_ws + (size_t)row0 * c->H * 8 * 66, sq, c->maxB - row0, QProj{}, done);
+}
+
 // One decoder step for rows [row0, row0 + n) at position *st.step, enqueued on c->cur.
 // mode 0: through logits + select; 1: logits only (test API / beam search); 2: no logits (all rows forced by
 // the prompt), select just advances the forced token; 3: the language head (kernels_lang.hip) over the span c->lang_begin /
@@ -290,29 +323,7 @@ void run_decode_rows(ttasr_ctx* c, int row0, int n, int mode, int total_rows) {
     { GemmArgs g = lin_args<T>(dh, L.wqx, n, d, d);
       sq = split_gemm(g, L.wqx_sh, L.bqx, slices(1, d, d));
       if (!sq.n) { g.epi.bias = L.bqx; g.epi.out_t = dq; dec_gemm<T>(c, g, L.wqx_sh); } }
-    // cross-KV of clip (row / kv_div); a half-batch offset is only used with kv_div == 1
-    const T* Kx = (const T*)c->xkv + (int64_t)l * c->xkv_layer_elems + (int64_t)(row0 / sh.kv_div) * c->H * c->T * 64;
-    bool fp8_done = false;
-    if constexpr (sizeof(T) == 2) {   // opt-in: the e4m3 copy of the cache, unshared rows that fill the chip (the single-pass kernel's case)
-      if (c->xkv_fp8 && c->xkv8_valid && sh.kv_div == 1 && n * c->H >= 256 && skinny && !(c->skip_mask & 8)) {
-        const int64_t off = (int64_t)l * c->xkv_layer_elems + (int64_t)row0 * c->H * c->T * 64;
-        const float* ksc = c->xkv8_scale + ((size_t)l * 2) * c->maxB * c->H + (size_t)row0 * c->H;
-        fp8_done = launch_cross_attn_fp8<T>((const T*)dq, c->xkv8 + off, c->xkv8 + off + c->xkv_which_elems, ksc, ksc + (size_t)c->maxB * c->H,
-                                            (T*)datt, n, c->H, c->T, s, sq, done);
-      } else if (c->xkv_fp8 == 2 && c->xattn_mq_fp8 && c->xkv8_valid && sh.kv_div >= 2 && skinny && !c->no_xsplit && !(c->skip_mask & 8)) {
-        // mode 2: rows that share a clip (beam hypotheses, sampled attempts) - wherever the 16-bit path would take
-        // cross_attn_mq_kernel with kv_div = 2..7, its e4m3 form; every other shape falls through to the 16-bit kernels
-        const int clip0 = row0 / sh.kv_div;
-        const int64_t off = (int64_t)l * c->xkv_layer_elems + (int64_t)clip0 * c->H * c->T * 64;
-        const float* ksc = c->xkv8_scale + ((size_t)l * 2) * c->maxB * c->H + (size_t)clip0 * c->H;
-        fp8_done = launch_cross_attn_mq_fp8<T>((const T*)dq, c->xkv8 + off, c->xkv8 + off + c->xkv_which_elems, ksc, ksc + (size_t)c->maxB * c->H,
-                                               (T*)datt, n, c->H, c->T, sh.kv_div, c->ko, s, c->xsplit_ws + (size_t)row0 * c->H * 8 * 66, sq,
-                                               c->maxB - row0, done);
-      }
-    }
-    if (!fp8_done && !(c->skip_mask & 8))
-      launch_cross_attn_decode<T>((const T*)dq, Kx, Kx + c->xkv_which_elems, (T*)datt, n, c->H, c->T, sh.kv_div, c->ko, s,
-                                  c->no_xsplit ? nullptr : c->xsplit_ws + (size_t)row0 * c->H * 8 * 66, sq, c->maxB - row0, QProj{}, done);
+    run_cross_attn<T>(c, l, row0, n, sh.kv_div, dq, datt, sq, done);
     residual_gemm(datt, L.wox, L.wox_sh, L.box, d, 0);
     ln(L.ln3g, L.ln3b);
     { GemmArgs g = lin_args<T>(dh, L.w1, n, ffn, d); g.epi.bias = L.b1; g.epi.act = 1; g.epi.out_t = dmid; dec_gemm<T>(c, g, L.w1_sh); }
@@ -611,6 +622,10 @@ void sched_admit_prefill(ttasr_ctx* c, const PrefillPass& P) { TT_DISPATCH(c, ru
 int sched_prefill_no_speech(ttasr_ctx* c, int n_seq, int npos, int sot, int no_speech_tok) {
   TT_DISPATCH(c, return prefill_no_speech<T>(c, n_seq, npos, sot, no_speech_tok));
   return 0;
+}
+void sched_cross_attn(ttasr_ctx* c, int layer, int n, int kv_div, const void* dq, void* datt, const SlabIn& sq, const int32_t* done) {
+  c->cur = c->stream;
+  TT_DISPATCH(c, run_cross_attn<T>(c, layer, 0, n, kv_div, dq, datt, sq, done));
 }
 void sched_detect_rows(ttasr_ctx* c, int B) { c->cur = c->stream; TT_DISPATCH(c, run_decode_rows<T>(c, 0, B, 3, B)); }
 void sched_gemm(ttasr_ctx* c, const GemmArgs& g) { TT_DISPATCH(c, gemm<T>(c, g)); }

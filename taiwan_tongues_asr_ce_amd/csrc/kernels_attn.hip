@@ -1049,6 +1049,7 @@ void launch_cross_attn_decode(const T* q, const T* K, const T* V, T* out, int B,
   // the clip's frames (kernels_flash.hip, CROSS) - K and V are streamed once per (clip, head, 128 rows)
   if constexpr (sizeof(T) == 2) {
     if (split_ws && kv_div >= 32 && B % kv_div == 0 && sq.n == 0) {
+      if (g_kernel_sig_on) snprintf(g_kernel_sig, sizeof g_kernel_sig, "enc_attn_flash_kernel<%s, true, 1> clips %d rows %d", sig_type<T>(), B / kv_div, kv_div);
       launch_cross_attn_flash_bf16<T>(q, K, V, out, B / kv_div, kv_div, H, Tk, s);
       return;
     }
@@ -1071,6 +1072,8 @@ void launch_cross_attn_decode(const T* q, const T* K, const T* V, T* out, int B,
     const bool ws_ok = S2 == 1 || (int64_t)B * S2 <= (int64_t)ws_rows * 8;  // one slice: stored directly, no workspace
     if (lds <= 64 * 1024 && ws_ok) {
       const dim3 grid(H, A * groups, S2);
+      if (g_kernel_sig_on) snprintf(g_kernel_sig, sizeof g_kernel_sig, "cross_attn_mq_kernel<%s, %d> grid %d slices %d%s", sig_type<T>(), NQ,
+                                    H * A * groups * S2 * 256, S2, S2 > 1 ? " + cross_attn_merge_kernel" : "");
 #define TTASR_MQ(NQ_) \
   hipLaunchKernelGGL((cross_attn_mq_kernel<T, NQ_>), grid, dim3(256), lds, s, q, K, V, H, Tk, chunk, split_ws, sq, kv_div, groups, nq_last, out, done)
       switch (NQ) {
@@ -1087,6 +1090,8 @@ void launch_cross_attn_decode(const T* q, const T* K, const T* V, T* out, int B,
     int chunk = ((Tk + S - 1) / S + 31) / 32 * 32;
     const int S2 = (Tk + chunk - 1) / chunk;  // every slice non-empty
     size_t lds = sizeof(float) * (chunk + 4 * 64 + 8);
+    if (g_kernel_sig_on) snprintf(g_kernel_sig, sizeof g_kernel_sig, "cross_attn_split_kernel<%s> grid %d slices %d + cross_attn_merge_kernel", sig_type<T>(),
+                                  H * B * S2 * 256, S2);
     hipLaunchKernelGGL(cross_attn_split_kernel<T>, dim3(H, B, S2), dim3(256), lds, s, q, K, V, H, Tk, kv_div, chunk, split_ws, sq, done);
     launch_cross_attn_merge<T>(split_ws, out, B, H, S2, done, s);
     return;

@@ -13,8 +13,11 @@
 //                          the e4m3 copy: 8 values per lane, 8 lanes per frame, 8-byte loads - the 16-bit kernel's register shape
 //   xkv_quant_slots_kernel the quantiser with (source slot, destination slot) pairs: a session quantises an admitted clip from
 //                          its STAGING 16-bit block straight into the live slot of the e4m3 copy
-// Accuracy is reported, not assumed: tools/fp8_agreement.py + bench.py --xkv-fp8 (token agreement with the bf16 engine and the f32
-// parity engine on the headline workload), tests/test_gpu_fp8.py (attention output vs the 16-bit kernel, token equality under margin).
+// Accuracy is reported, not assumed: bench.py --xkv-fp8 (token agreement with the bf16 engine and the f32 parity engine on the
+// headline workload); tests/test_gpu_fp8*.py hold the whole engine to the bf16 engine's (liveness, bit-reproducibility, step logits
+// within 0.12, at least half the rows with equal tokens); tests/test_gpu_xattn_kernels.py holds THESE kernels to a float64 reference
+// through the known-answer hooks ttasr_get_cross_kv_fp8 / ttasr_cross_attn_probe: quantiser codes and scales bit for bit
+// (oracle/whisper_ref.py xkv_quant_ref), attention output over codes x scale within a derived f32 bound.
 #include "common.hpp"
 
 namespace {
@@ -278,6 +281,8 @@ bool launch_cross_attn_fp8(const T* q, const uint8_t* K8, const uint8_t* V8, con
   else {
     if (sq.n > 4 || Tk < 1) return false;
     const size_t lds = sizeof(float) * (Tk + 4 * 64 + 2 * 4);
+    if (g_kernel_sig_on) snprintf(g_kernel_sig, sizeof g_kernel_sig, "cross_attn_fp8_kernel<%s, %s, 4> grid %d", sig_type<T>(), sq.n > 0 ? "true" : "false",
+                                  H * B * 256);
     if (sq.n > 0) hipLaunchKernelGGL((cross_attn_fp8_kernel<T, true, 4>), dim3(H, B), dim3(256), lds, s, q, K8, V8, kscale, vscale, out, done, H, Tk, sq);
     else hipLaunchKernelGGL((cross_attn_fp8_kernel<T, false, 4>), dim3(H, B), dim3(256), lds, s, q, K8, V8, kscale, vscale, out, done, H, Tk, sq);
     return true;
@@ -477,6 +482,8 @@ bool launch_cross_attn_mq_fp8(const T* q, const uint8_t* K8, const uint8_t* V8, 
     const bool ws_ok = S2 == 1 || (int64_t)B * S2 <= (int64_t)ws_rows * 8;  // one slice: stored directly, no workspace
     if (lds > 64 * 1024 || !ws_ok) return false;
     const dim3 grid(H, A, S2);
+    if (g_kernel_sig_on) snprintf(g_kernel_sig, sizeof g_kernel_sig, "cross_attn_mq_fp8_kernel<%s, %d> grid %d slices %d%s", sig_type<T>(), kv_div,
+                                  H * A * S2 * 256, S2, S2 > 1 ? " + cross_attn_merge_kernel" : "");
 #define TTASR_MQ8(NQ_) \
   hipLaunchKernelGGL((cross_attn_mq_fp8_kernel<T, NQ_>), grid, dim3(256), lds, s, q, K8, V8, kscale, vscale, H, Tk, chunk, split_ws, sq, out, done)
     switch (kv_div) {

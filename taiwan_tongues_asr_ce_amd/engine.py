@@ -191,6 +191,32 @@ class Engine:
         self._check(self.lib.ttasr_get_cross_kv(self.h, layer, which, B, _ptr(out)), "get_cross_kv")
         return out
 
+    def cross_kv_fp8(self, layer: int, which: int, B: int):
+        """The resident e4m3 copy (ttasr_get_cross_kv_fp8): (codes uint8 [B][H][T][64], scales float32 [B][H]).  In an open
+        session B counts cross-KV slots."""
+        codes = np.empty((B, self.dims.n_heads, self.audio_ctx, 64), dtype=np.uint8)
+        scale = np.empty((B, self.dims.n_heads), dtype=np.float32)
+        self._check(self.lib.ttasr_get_cross_kv_fp8(self.h, layer, which, B, codes.ctypes.data_as(C.c_void_p),
+                                                    _ptr(scale)), "get_cross_kv_fp8")
+        return codes, scale
+
+    def cross_attn_probe(self, layer: int, q: np.ndarray, kv_div: int = 1, done: Optional[np.ndarray] = None):
+        """One launch of the decode step's cross-attention on the caller's queries (ttasr_cross_attn_probe).  q: float32
+        [n_rows][d_model], or [n_slab][n_rows][d_model] partial tiles (n_slab 1..4).  Returns (out float32 [n_rows][d_model],
+        signature of the kernel that ran)."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        n_slab = q.shape[0] if q.ndim == 3 else 0
+        n_rows = q.shape[-2]
+        assert q.shape[-1] == self.dims.d_model, q.shape
+        out = np.empty((n_rows, self.dims.d_model), dtype=np.float32)
+        flags = None if done is None else np.ascontiguousarray(done, dtype=np.int32)
+        assert flags is None or flags.shape == (n_rows,)
+        buf = C.create_string_buffer(256)
+        self._check(self.lib.ttasr_cross_attn_probe(self.h, layer, n_rows, kv_div, _ptr(q), n_slab,
+                                                    None if flags is None else flags.ctypes.data_as(C.c_void_p), _ptr(out), buf, 256),
+                    "cross_attn_probe")
+        return out, buf.value.decode()
+
     # -- a9, a10 -------------------------------------------------------------------------------
     def gen_opts(self, max_new_tokens: int, timestamps: bool, suppress: Optional[Sequence[int]] = None,
                  begin_suppress: Optional[Sequence[int]] = None, suppress_eot: bool = False, no_speech: bool = True,
