@@ -475,6 +475,44 @@ TTASR_API int ttasr_session_release(ttasr_ctx* ctx, int32_t n, const int64_t* id
  * (no context): CTranslate2 does this step in C++ too. */
 TTASR_API int ttasr_dtw(const float* cost, int32_t n_rows, int32_t n_cols, int32_t* out_row, int32_t* out_col, int32_t* out_len);
 
+/* ---- voice activity detection: the Silero-v5-shaped network, 16 kHz branch (faster-whisper's vad_filter=True, requested at
+ * asr_core.py:163, file_asr.py:284,461, faster_whisper_asr.py:144) ------------------------------------------------------ */
+/* One speech probability per 512-sample frame (32 ms) of every recording of the call, all arithmetic f32 in every compute mode.
+ * Framing: n_frames = ceil(n_samples / 512), the recording zero-padded to 512 * n_frames samples; frame i reads the 64 samples
+ * before it (zeros before sample 0) and its own 512; the LSTM state (h, c) is zero at the start of a recording.  Per frame: right
+ * reflect pad by 64 -> strided correlation with the [258][1][256] STFT basis (stride 128, 4 columns) -> magnitude [129][4] -> four
+ * Conv1d (k = 3, zero pad 1) + ReLU, 129 -> 128 s1, 128 -> 64 s2, 64 -> 64 s2, 64 -> 128 s1 -> LSTM cell 128 -> 128 (gates i, f,
+ * g, o) -> logit = b_out + < w_out, relu(h') >, p = sigmoid(logit).  DESIGN.md section 4.20 has the kernels; faithfulness to the
+ * file Silero ships is NOT checked anywhere (no weights offline): the network is held to a float64 restatement of this text.
+ *
+ * ttasr_vad_load_tensor: one tensor, float32 host data, Silero state-dict name (a leading "_model." is stripped):
+ *   stft.forward_basis_buffer [258,1,256]; encoder.{0..3}.reparam_conv.weight [128,129,3] [64,128,3] [64,64,3] [128,64,3] and
+ *   .bias [128] [64] [64] [128]; decoder.rnn.weight_ih / weight_hh [512,128]; decoder.rnn.bias_ih / bias_hh [512];
+ *   decoder.decoder.2.weight [1,128,1]; decoder.decoder.2.bias [1].
+ *   Unknown name or wrong shape: TTASR_E_WEIGHTS.  After ttasr_vad_finalize, and in an open session: TTASR_E_INVALID.
+ *   The weights (1.3 MB) belong to THIS context: a ttasr_create_shared context loads its own copy.
+ * ttasr_vad_finalize: TTASR_E_WEIGHTS when a tensor is missing; afterwards the weights are read-only.
+ * ttasr_vad_probs: n recordings, recording i = pcm_host[i][0 .. n_samples[i]); out_probs_host[i] (and out_logits_host[i] when
+ *   out_logits_host != NULL: the pre-sigmoid values) receive ceil(n_samples[i] / 512) floats.  A recording of 0 samples is legal
+ *   and writes nothing (its pointers may be NULL).  Refused with TTASR_E_INVALID before anything is enqueued, the context stays
+ *   usable: VAD weights not finalized; n outside [1, max_batch]; a NULL array; a NULL pcm or output row with samples; a negative
+ *   length; an open session; a call already in flight on the context.
+ *   Work proceeds in time chunks of TTASR_VAD_CHUNK_FRAMES frames per recording (about 33 s): host PCM is staged through a
+ *   bounded pinned buffer chunk by chunk, the LSTM state and the 64-sample context carry across chunks, and every kernel's form
+ *   is a function of the frame only - a recording's values do not depend, bit for bit, on its length, on the other recordings of
+ *   the call or on its place in it, and the first k values equal those of the recording cut to 512 k samples.
+ *   Device scratch: n x (4 (64 + 512 C) + 2048 C + 8 C + 1028) bytes with C = TTASR_VAD_CHUNK_FRAMES (4.01 MiB per recording,
+ *   at most max_batch of them; never a function of the recordings' lengths), ONE block owned by the context: allocated by the
+ *   first call, grown when a call brings more recordings, freed by ttasr_destroy; a request that cannot be allocated returns
+ *   TTASR_E_NOMEM and leaves the context usable.  The pinned staging block (8 chunk slots of PCM + max_batch rows of results) is
+ *   allocated by the first call as well.
+ *   The call touches no mel, encoder, search or graph state: a ttasr_generate* after it is bit-identical to one without it. */
+#define TTASR_VAD_CHUNK_FRAMES 1024
+TTASR_API int ttasr_vad_load_tensor(ttasr_ctx* ctx, const char* name, const float* data_host, const int64_t* dims, int32_t ndim);
+TTASR_API int ttasr_vad_finalize(ttasr_ctx* ctx);
+TTASR_API int ttasr_vad_probs(ttasr_ctx* ctx, int32_t n, const float* const* pcm_host, const int64_t* n_samples,
+                              float* const* out_probs_host, float* const* out_logits_host);
+
 /* ---- kernel-selection overrides (tests, A/B measurements) ----------------------------------------- */
 /* The release library reads NO environment variable; every deviation from the measured configuration is an explicit call.
  * Keys (value 0 / 1 unless stated; defaults in brackets): "flash" [1] MFMA flash attention in the encoder (0: the

@@ -19,7 +19,10 @@ SYMBOLS = [
     "ttasr_session_begin", "ttasr_session_begin_beam", "ttasr_session_submit", "ttasr_session_submit_windows", "ttasr_session_poll", "ttasr_session_stats", "ttasr_session_rows", "ttasr_session_end",
     "ttasr_align_batch", "ttasr_session_hold", "ttasr_session_align", "ttasr_session_release", "ttasr_detect_language",
     "ttasr_session_detect_language", "ttasr_session_poll_lang", "ttasr_session_prefill_stats",
+    "ttasr_vad_load_tensor", "ttasr_vad_finalize", "ttasr_vad_probs",
 ]
+
+VAD_CHUNK_FRAMES = 1024   # TTASR_VAD_CHUNK_FRAMES of include/ttasr.h: frames of one recording per time chunk of ttasr_vad_probs
 
 
 class Config(C.Structure):
@@ -112,6 +115,9 @@ def load() -> C.CDLL:
     lib.ttasr_session_prefill_stats.argtypes = [vp, C.POINTER(C.c_double)]
     lib.ttasr_session_rows.argtypes = [vp, i32p, i32p, i64p]
     lib.ttasr_session_end.argtypes = [vp]
+    lib.ttasr_vad_load_tensor.argtypes = [vp, C.c_char_p, vp, i64p, i32]
+    lib.ttasr_vad_finalize.argtypes = [vp]
+    lib.ttasr_vad_probs.argtypes = [vp, i32, C.POINTER(vp), i64p, C.POINTER(vp), C.POINTER(vp)]
     for s in SYMBOLS:
         f = getattr(lib, s)
         if s not in ("ttasr_destroy", "ttasr_last_error", "ttasr_version"):

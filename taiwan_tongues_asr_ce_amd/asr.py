@@ -38,7 +38,8 @@ class MI355XWhisperASR(ASRInterface):
         # so the model needs at least that many rows or transcribe() refuses the beam
         self.asr_pipeline = WhisperModel(model_path, device=device, compute_type=compute_type,
                                          max_batch=max(8, int(kwargs.get("max_batch", 8))),
-                                         cross_kv_fp8=bool(kwargs.get("cross_kv_fp8", False)))   # opt-in e4m3 cross-KV cache
+                                         cross_kv_fp8=bool(kwargs.get("cross_kv_fp8", False)),   # opt-in e4m3 cross-KV cache
+                                         vad_model=kwargs.get("vad_model"))   # Silero-v5 VAD network, run on the device
         # health-check attributes (faster_whisper_asr.py:111-114, streaming_asr.py:455-463)
         self.device, self.compute_type, self.model_size, self.model_path = device, compute_type, model_size, model_path
         self.default_transcribe_kwargs = {  # faster_whisper_asr.py:139-149
@@ -103,8 +104,10 @@ class MI355XWhisperASR(ASRInterface):
             return None
 
     def _vad_is_active(self) -> bool:
-        """True when vad_filter=True really filters: the operator supplied a speech-probability source on the model, or the
-        default kwargs opt into the energy stand-in."""
+        """True when vad_filter=True really filters: the model runs the VAD network on the device, the operator supplied a
+        speech-probability source on the model, or the default kwargs opt into the energy stand-in."""
+        if getattr(self.asr_pipeline, "has_device_vad", False):
+            return True
         if getattr(self.asr_pipeline, "vad_speech_prob_fn", None) is not None:
             return True
         if self.default_transcribe_kwargs.get("vad_speech_prob_fn") is not None:

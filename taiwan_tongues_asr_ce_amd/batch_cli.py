@@ -124,8 +124,11 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
                          world: int = 1, load_audio: Callable = _load_audio, log: Callable = print,
                          group_files: int = 0, pipeline_depth: int = 0, continuous: bool = False,
                          cross_kv_fp8: bool = False, language: Optional[str] = TRANSCRIBE_KWARGS["language"],
-                         detect_in_session: bool = False, session_prefill: int = 0) -> Optional[Dict]:
-    """language: the forced language of every file (the reference's "zh"), or None = detect each file's language (`--language
+                         detect_in_session: bool = False, session_prefill: int = 0, vad_model=None) -> Optional[Dict]:
+    """vad_model (`--vad-model PATH`): the Silero-v5 VAD network for the device (WhisperModel(vad_model=...)); with it the folder
+    keeps its lock-step / continuous / pipelined path and every group is filtered in one device call (vad_filter=True).  A
+    Python vad_speech_prob_fn on the model still means file by file.
+    language: the forced language of every file (the reference's "zh"), or None = detect each file's language (`--language
     auto`); the detected language and its probability are then part of every entry of `detailed_results`.
     detect_in_session (`--detect-in-session`, with continuous and language None): the session finds each file's language in the
     first decode step of its first window instead of a detection pass, with its own encoder pass, before the session.
@@ -144,7 +147,8 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
     if model is None:
         from .model import WhisperModel
         model = WhisperModel(model_path, device=device, device_index=device_index, compute_type=compute_type,
-                             max_batch=max_batch, pipeline_depth=max(1, pipeline_depth), cross_kv_fp8=cross_kv_fp8)
+                             max_batch=max_batch, pipeline_depth=max(1, pipeline_depth), cross_kv_fp8=cross_kv_fp8,
+                             vad_model=vad_model)
     mine = files[rank::world]                                   # shard by file
     results = []
     many = getattr(model, "transcribe_many", None)
@@ -155,6 +159,8 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
         # MI355X-first: `group` files advance in lock step through one engine pass per window round; every file keeps the
         # sequential algorithm (own seek / prompt / fallback), so the outputs equal the one-by-one run
         kw = {k: v for k, v in TRANSCRIBE_KWARGS.items() if k != "vad_filter"}   # no VAD source configured: all-speech
+        if getattr(model, "has_device_vad", False):
+            kw["vad_filter"] = True   # the device network filters a whole group in one call: the reference's vad_filter=True
         kw["language"] = language
         if continuous:
             # one continuous-batching session per group on one engine context: windows of the group's files refill decode rows
@@ -248,6 +254,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--xkv-fp8", action="store_true",
                     help="opt-in serving mode: decode from the e4m3 copy of the cross-attention cache (16-bit compute types; "
                          "WhisperModel(cross_kv_fp8=True)); the summary JSON names the cache that was read")
+    ap.add_argument("--vad-model", default=None, metavar="PATH",
+                    help="Silero-v5 VAD weights (.npz, or a TorchScript / state-dict file when torch is installed): vad_filter=True "
+                         "then runs the network on the device, one call per group of files, and the folder keeps its grouped path")
     ap.add_argument("--language", default=TRANSCRIBE_KWARGS["language"],
                     help="language code forced on every file (default: the reference's zh), or 'auto': detect each file's language "
                          "on the device; the summary JSON then holds language and language_probability per file")
@@ -277,7 +286,8 @@ def main(argv=None) -> int:
                          compute_type=args.compute_type, rank=rank, world=world, group_files=args.group_files,
                          max_batch=args.max_batch, pipeline_depth=args.pipeline_depth, continuous=args.continuous,
                          cross_kv_fp8=args.xkv_fp8, language=None if args.language == "auto" else args.language,
-                         detect_in_session=args.detect_in_session, session_prefill=args.session_prefill)
+                         detect_in_session=args.detect_in_session, session_prefill=args.session_prefill,
+                         vad_model=args.vad_model)
     return 0
 
 

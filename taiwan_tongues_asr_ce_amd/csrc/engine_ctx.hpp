@@ -41,6 +41,7 @@ struct Slot {              // where one named tensor lands on the device
 };
 
 struct Session;            // continuous-batching session state (engine_refill.hip)
+struct VadState;           // voice-activity network: weights, scratch and staging of one context (engine_vad.hip)
 // What run_decode_rows reads about the rows of a step, and (with the batch, the mode and the e4m3 state) what a captured step
 // graph is keyed on.  Installed and restored by SearchScope only.
 struct StepShape {
@@ -176,6 +177,9 @@ struct ttasr_ctx {
   // batched alignment (engine_align.hip): ONE device block for the pass's tables, softmax maps, cost matrices and spilled DTW
   // traces; allocated by the first call, grown to the largest request, freed by ttasr_destroy
   void* align_dev = nullptr; size_t align_dev_bytes = 0;
+  // voice-activity network (engine_vad.hip): created by the first ttasr_vad_load_tensor, freed by ttasr_destroy; per context,
+  // outside the weight-share bookkeeping
+  ttasr_detail::VadState* vad = nullptr;
 
   int B_mel = 0, B_enc = 0, B_dec = 0;
   std::atomic_flag busy = ATOMIC_FLAG_INIT;  // one call in flight per context: a second concurrent call is refused
@@ -368,6 +372,9 @@ struct AlignBatch {   // the host arguments of ttasr_align_batch without the cli
 };
 int align_batch_validate(ttasr_ctx* c, const AlignBatch& a);
 int align_batch_run(ttasr_ctx* c, const AlignBatch& a, const int32_t* slot /*[n]*/, const int32_t* pages /*[n][pages_per_seq]*/);
+
+// ---- engine_vad.hip: the voice-activity network (ttasr_vad_*) ----
+void vad_free(ttasr_ctx* c);         // ttasr_destroy: the scratch block and the pinned staging (the weights live in the arenas)
 
 // ---- engine_search.hip: rules, options, greedy / sampled / beam search ----
 // The decode shape of ONE search (a static search's call, or a session from begin to end / free): installs the StepShape and the

@@ -1,0 +1,244 @@
+// libttasr: the voice-activity network behind the C ABI (one of the engine translation units, see engine_ctx.hpp): weight intake
+// into the kernels' layouts, the context's scratch block and pinned staging, and the chunk loop of ttasr_vad_probs.  The kernels
+// are kernels_vad.hip; the network is the text of include/ttasr.h.  Nothing here touches mel, encoder, search or graph state:
+// the call's only shared resource is the context's stream.
+#include "engine_ctx.hpp"
+#include "vad.hpp"
+
+namespace ttasr_detail {
+
+// The tensor-name table of the C side (a leading "_model." is stripped before the lookup).  kind: how the tensor is laid out on
+// the device - 0 as given, 1 [258][1][256] -> [256][258], 2 conv [out][in][3] -> [in * 3][out], 3 [512][128] -> [128][512].
+struct VadSpec { const char* name; int ndim; int64_t dims[3]; int kind; };
+enum { V_BASIS, V_W0, V_W1, V_W2, V_W3, V_B0, V_B1, V_B2, V_B3, V_WIH, V_WHH, V_BIH, V_BHH, V_WOUT, V_BOUT, V_COUNT };
+static const VadSpec kVadSpec[V_COUNT] = {
+    {"stft.forward_basis_buffer", 3, {258, 1, 256}, 1},
+    {"encoder.0.reparam_conv.weight", 3, {128, 129, 3}, 2}, {"encoder.1.reparam_conv.weight", 3, {64, 128, 3}, 2},
+    {"encoder.2.reparam_conv.weight", 3, {64, 64, 3}, 2},   {"encoder.3.reparam_conv.weight", 3, {128, 64, 3}, 2},
+    {"encoder.0.reparam_conv.bias", 1, {128, 1, 1}, 0},     {"encoder.1.reparam_conv.bias", 1, {64, 1, 1}, 0},
+    {"encoder.2.reparam_conv.bias", 1, {64, 1, 1}, 0},      {"encoder.3.reparam_conv.bias", 1, {128, 1, 1}, 0},
+    {"decoder.rnn.weight_ih", 2, {512, 128, 1}, 3},         {"decoder.rnn.weight_hh", 2, {512, 128, 1}, 0},
+    {"decoder.rnn.bias_ih", 1, {512, 1, 1}, 0},             {"decoder.rnn.bias_hh", 1, {512, 1, 1}, 0},
+    {"decoder.decoder.2.weight", 3, {1, 128, 1}, 0},        {"decoder.decoder.2.bias", 1, {1, 1, 1}, 0},
+};
+
+constexpr int kVadPinSlots = 8;   // chunk slots of PCM in the pinned staging block (8 x 2 MiB)
+
+struct VadState {
+  float* dev[V_COUNT] = {};       // device tensors (arena memory of the context)
+  float* gate_b = nullptr;        // b_ih + b_hh
+  bool loaded[V_COUNT] = {};
+  std::vector<float> bih, bhh;    // host copies until ttasr_vad_finalize adds them
+  bool finalized = false;
+  VadWeights w{};
+  // scratch: pcm [files][kVadSlot] | gx [files][C][512] | out [files][2][C] | state [files][256] | nf [files]
+  char* scratch = nullptr; int scratch_files = 0;
+  // pinned: pcm slots [kVadPinSlots][kVadSlot] | out [max_batch][2][C] | nf [max_batch]
+  char* pinned = nullptr;
+};
+
+void vad_free(ttasr_ctx* c) {
+  if (!c->vad) return;
+  if (c->vad->scratch) hipFree(c->vad->scratch);
+  if (c->vad->pinned) hipHostFree(c->vad->pinned);
+  delete c->vad;
+  c->vad = nullptr;
+}
+
+static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+struct VadScratch { size_t pcm, gx, out, state, nf, total; };
+static VadScratch vad_scratch_layout(int files) {
+  VadScratch l;
+  l.pcm = 0;
+  l.gx = l.pcm + up256((size_t)files * kVadSlot * 4);
+  l.out = l.gx + up256((size_t)files * kVadChunk * 512 * 4);
+  l.state = l.out + up256((size_t)files * 2 * kVadChunk * 4);
+  l.nf = l.state + up256((size_t)files * 256 * 4);
+  l.total = l.nf + up256((size_t)files * 4);
+  return l;
+}
+
+// One device block for `files` recordings, grown to the largest request.  A request that cannot be allocated leaves the context
+// without a block (the next call allocates again) and otherwise as it was.
+static int vad_scratch(ttasr_ctx* c, int files) {
+  VadState* v = c->vad;
+  if (files <= v->scratch_files) return 0;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (v->scratch) hipFree(v->scratch);
+  v->scratch = nullptr; v->scratch_files = 0;
+  const size_t bytes = vad_scratch_layout(files).total;
+  const hipError_t e = hipMalloc((void**)&v->scratch, bytes);
+  if (e != hipSuccess) {
+    v->scratch = nullptr;
+    (void)hipGetLastError();
+    return fail(c, TTASR_E_NOMEM, "VAD scratch (%zu bytes for %d recordings): %s", bytes, files, hipGetErrorString(e));
+  }
+  v->scratch_files = files;
+  return 0;
+}
+
+static int vad_pinned(ttasr_ctx* c) {
+  VadState* v = c->vad;
+  if (v->pinned) return 0;
+  const size_t bytes = (size_t)kVadPinSlots * kVadSlot * 4 + (size_t)c->maxB * 2 * kVadChunk * 4 + (size_t)c->maxB * 4;
+  const hipError_t e = hipHostMalloc((void**)&v->pinned, bytes, hipHostMallocDefault);
+  if (e != hipSuccess) {
+    v->pinned = nullptr;
+    (void)hipGetLastError();
+    return fail(c, TTASR_E_NOMEM, "VAD pinned staging (%zu bytes): %s", bytes, hipGetErrorString(e));
+  }
+  return 0;
+}
+
+static int vad_load(ttasr_ctx* c, const char* name, const float* data, const int64_t* dims, int32_t ndim) {
+  if (!c->vad) c->vad = new VadState();
+  VadState* v = c->vad;
+  if (v->finalized) return fail(c, TTASR_E_INVALID, "VAD weights are finalized: they are read-only");
+  if (strncmp(name, "_model.", 7) == 0) name += 7;
+  int id = -1;
+  for (int i = 0; i < V_COUNT; ++i)
+    if (strcmp(name, kVadSpec[i].name) == 0) id = i;
+  if (id < 0) return fail(c, TTASR_E_WEIGHTS, "unknown VAD tensor '%s'", name);
+  const VadSpec& sp = kVadSpec[id];
+  bool ok = ndim == sp.ndim;
+  size_t n = 1;
+  for (int i = 0; ok && i < ndim; ++i) { ok = dims[i] == sp.dims[i]; n *= (size_t)sp.dims[i]; }
+  if (!ok) return fail(c, TTASR_E_WEIGHTS, "VAD tensor '%s': wrong shape", name);
+  std::vector<float> t(data, data + n);
+  if (sp.kind == 1) {
+    for (int k = 0; k < 258; ++k)
+      for (int m = 0; m < 256; ++m) t[(size_t)m * 258 + k] = data[(size_t)k * 256 + m];
+  } else if (sp.kind == 2) {
+    const int O = (int)sp.dims[0], Cin = (int)sp.dims[1];
+    for (int o = 0; o < O; ++o)
+      for (int ci = 0; ci < Cin; ++ci)
+        for (int j = 0; j < 3; ++j) t[((size_t)ci * 3 + j) * O + o] = data[((size_t)o * Cin + ci) * 3 + j];
+  } else if (sp.kind == 3) {
+    for (int r = 0; r < 512; ++r)
+      for (int k = 0; k < 128; ++k) t[(size_t)k * 512 + r] = data[(size_t)r * 128 + k];
+  }
+  if (id == V_BIH) v->bih.assign(data, data + n);
+  if (id == V_BHH) v->bhh.assign(data, data + n);
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!v->dev[id]) TRY(dalloc(c, &v->dev[id], n * 4));
+  HIPCHK(c, hipMemcpyAsync(v->dev[id], t.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));   // `t` is a stack temporary
+  v->loaded[id] = true;
+  return TTASR_OK;
+}
+
+static int vad_finalize(ttasr_ctx* c) {
+  VadState* v = c->vad;
+  if (!v) return fail(c, TTASR_E_WEIGHTS, "no VAD tensor was loaded");
+  if (v->finalized) return TTASR_OK;
+  for (int i = 0; i < V_COUNT; ++i)
+    if (!v->loaded[i]) return fail(c, TTASR_E_WEIGHTS, "VAD tensor '%s' is missing", kVadSpec[i].name);
+  std::vector<float> gb(512);
+  for (int r = 0; r < 512; ++r) gb[r] = v->bih[r] + v->bhh[r];
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!v->gate_b) TRY(dalloc(c, &v->gate_b, 512 * 4));
+  HIPCHK(c, hipMemcpyAsync(v->gate_b, gb.data(), 512 * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  VadWeights& w = v->w;
+  w.basis_t = v->dev[V_BASIS];
+  for (int l = 0; l < 4; ++l) { w.conv_t[l] = v->dev[V_W0 + l]; w.conv_b[l] = v->dev[V_B0 + l]; }
+  w.wih_t = v->dev[V_WIH]; w.gate_b = v->gate_b; w.whh = v->dev[V_WHH]; w.w_out = v->dev[V_WOUT]; w.b_out = v->dev[V_BOUT];
+  v->finalized = true;
+  return TTASR_OK;
+}
+
+static int vad_probs(ttasr_ctx* c, int32_t n, const float* const* pcm, const int64_t* ns, float* const* out_probs,
+                     float* const* out_logits) {
+  VadState* v = c->vad;
+  if (!v || !v->finalized) return fail(c, TTASR_E_INVALID, "VAD weights not finalized (ttasr_vad_load_tensor, ttasr_vad_finalize first)");
+  if (n < 1 || n > c->maxB) return fail(c, TTASR_E_INVALID, "n %d outside [1, max_batch = %d]", n, c->maxB);
+  if (!pcm || !ns || !out_probs) return fail(c, TTASR_E_INVALID, "NULL argument");
+  int64_t max_frames = 0;
+  std::vector<int64_t> frames(n);
+  for (int i = 0; i < n; ++i) {
+    if (ns[i] < 0) return fail(c, TTASR_E_INVALID, "recording %d: negative length", i);
+    if (ns[i] > 0 && (!pcm[i] || !out_probs[i] || (out_logits && !out_logits[i])))
+      return fail(c, TTASR_E_INVALID, "recording %d: NULL pcm or output row with %lld samples", i, (long long)ns[i]);
+    frames[i] = (ns[i] + kVadWindow - 1) / kVadWindow;
+    max_frames = std::max(max_frames, frames[i]);
+  }
+  TRY(session_refusal(c));
+  HIPCHK(c, hipSetDevice(c->device));
+  if (max_frames == 0) return TTASR_OK;
+  TRY(vad_pinned(c));
+  TRY(vad_scratch(c, n));
+  hipStream_t s = c->stream;
+  const VadScratch l = vad_scratch_layout(v->scratch_files);
+  float* d_pcm = (float*)(v->scratch + l.pcm);
+  float* d_gx = (float*)(v->scratch + l.gx);
+  float* d_out = (float*)(v->scratch + l.out);
+  float* d_state = (float*)(v->scratch + l.state);
+  int32_t* d_nf = (int32_t*)(v->scratch + l.nf);
+  float* p_pcm = (float*)v->pinned;
+  float* p_out = p_pcm + (size_t)kVadPinSlots * kVadSlot;
+  int32_t* p_nf = (int32_t*)(p_out + (size_t)c->maxB * 2 * kVadChunk);
+  HIPCHK(c, hipMemsetAsync(d_state, 0, (size_t)n * 256 * 4, s));   // (h, c) = 0 at the start of every recording
+  for (int64_t k0 = 0; k0 < max_frames; k0 += kVadChunk) {
+    int max_nf = 0, staged = 0;
+    for (int i = 0; i < n; ++i) {
+      const int nf = (int)std::min<int64_t>(std::max<int64_t>(frames[i] - k0, 0), kVadChunk);
+      p_nf[i] = nf;
+      max_nf = std::max(max_nf, nf);
+      if (nf == 0) continue;
+      // the slot: 64 samples in front of the chunk (zeros in front of the recording) | nf frames, zeros behind the last sample
+      if (staged && staged % kVadPinSlots == 0) HIPCHK(c, hipStreamSynchronize(s));   // the slots are free again
+      float* slot = p_pcm + (size_t)(staged % kVadPinSlots) * kVadSlot;
+      const int64_t first = k0 * kVadWindow - kVadContext, count = kVadContext + (int64_t)nf * kVadWindow;
+      const int64_t lo = std::max<int64_t>(first, 0), hi = std::min<int64_t>(first + count, ns[i]);
+      if (lo > first) memset(slot, 0, (size_t)(lo - first) * 4);
+      memcpy(slot + (lo - first), pcm[i] + lo, (size_t)(hi - lo) * 4);
+      if (hi < first + count) memset(slot + (hi - first), 0, (size_t)(first + count - hi) * 4);
+      HIPCHK(c, hipMemcpyAsync(d_pcm + (size_t)i * kVadSlot, slot, (size_t)count * 4, hipMemcpyHostToDevice, s));
+      ++staged;
+    }
+    HIPCHK(c, hipMemcpyAsync(d_nf, p_nf, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    launch_vad_frames(v->w, d_pcm, d_nf, d_gx, n, max_nf, s);
+    launch_vad_lstm(v->w, d_gx, d_nf, d_state, d_out, n, s);
+    HIPCHK(c, hipMemcpyAsync(p_out, d_out, (size_t)n * 2 * kVadChunk * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    HIPCHK(c, hipGetLastError());
+    for (int i = 0; i < n; ++i) {
+      if (p_nf[i] == 0) continue;
+      const float* row = p_out + (size_t)i * 2 * kVadChunk;
+      if (out_logits) memcpy(out_logits[i] + k0, row, (size_t)p_nf[i] * 4);
+      memcpy(out_probs[i] + k0, row + kVadChunk, (size_t)p_nf[i] * 4);
+    }
+  }
+  return TTASR_OK;
+}
+
+}  // namespace ttasr_detail
+
+extern "C" {
+
+int ttasr_vad_load_tensor(ttasr_ctx* c, const char* name, const float* data, const int64_t* dims, int32_t ndim) {
+  return guarded(c, [&]() -> int {
+  if (!c) return TTASR_E_INVALID;
+  if (!name || !data || !dims || ndim < 1 || ndim > 3) return fail(c, name && data && dims ? TTASR_E_WEIGHTS : TTASR_E_INVALID, "VAD tensor: bad argument");
+  TRY(session_refusal(c));
+  return vad_load(c, name, data, dims, ndim);
+  });
+}
+
+int ttasr_vad_finalize(ttasr_ctx* c) {
+  return guarded(c, [&]() -> int {
+  if (!c) return TTASR_E_INVALID;
+  TRY(session_refusal(c));
+  return vad_finalize(c);
+  });
+}
+
+int ttasr_vad_probs(ttasr_ctx* c, int32_t n, const float* const* pcm, const int64_t* n_samples, float* const* out_probs,
+                    float* const* out_logits) {
+  return guarded(c, [&]() -> int {
+  if (!c) return TTASR_E_INVALID;
+  return vad_probs(c, n, pcm, n_samples, out_probs, out_logits);
+  });
+}
+
+}  // extern "C"

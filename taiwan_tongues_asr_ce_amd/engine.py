@@ -75,6 +75,7 @@ class Engine:
         self.shares_weights = share_weights_with is not None
         self.special = SpecialTokens.for_vocab(dims.vocab)
         self.audio_ctx = dims.n_audio_ctx
+        self.has_vad = False   # load_vad() has put the VAD network on this context
 
     # -- plumbing ------------------------------------------------------------------------------
     def _check(self, rc: int, what: str):
@@ -106,6 +107,41 @@ class Engine:
             dims = (C.c_int64 * a.ndim)(*a.shape)
             self._check(self.lib.ttasr_load_tensor(self.h, name.encode(), _ptr(a), dims, a.ndim), f"load_tensor({name})")
         self._check(self.lib.ttasr_finalize_weights(self.h), "finalize_weights")
+
+    # -- voice activity detection ----------------------------------------------------------------
+    def load_vad(self, mapping):
+        """The Silero-v5-shaped VAD network of this context (ttasr_vad_load_tensor + ttasr_vad_finalize): a mapping, or
+        (name, array) pairs, with the names and shapes of vad.SILERO_V5_TENSORS (a leading "_model." is stripped).  Every context
+        holds its own copy, weight-sharing contexts included."""
+        items = mapping.items() if hasattr(mapping, "items") else mapping
+        for name, arr in items:
+            a = np.ascontiguousarray(arr, dtype=np.float32)
+            dims = (C.c_int64 * max(a.ndim, 1))(*a.shape)
+            self._check(self.lib.ttasr_vad_load_tensor(self.h, str(name).encode(), _ptr(a), dims, a.ndim), f"vad_load_tensor({name})")
+        self._check(self.lib.ttasr_vad_finalize(self.h), "vad_finalize")
+        self.has_vad = True
+
+    def vad_probs(self, audios: Sequence[np.ndarray], return_logits: bool = False):
+        """Speech probability per 512-sample frame of every recording (ttasr_vad_probs): a list of float32 arrays of
+        ceil(len / 512) entries; return_logits=True: (probabilities, pre-sigmoid logits).  More recordings than max_batch go
+        through several calls; a recording's values do not depend on its neighbours, so the split is not observable."""
+        pcm = []
+        for i, a in enumerate(audios):
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.ndim != 1:
+                raise ValueError(f"recording {i}: PCM must be one-dimensional, got shape {a.shape}")
+            pcm.append(a)
+        probs = [np.zeros(-(-len(a) // 512), dtype=np.float32) for a in pcm]
+        logits = [np.zeros_like(p) for p in probs] if return_logits else None
+        for i0 in range(0, len(pcm), self.max_batch):
+            sl = slice(i0, i0 + self.max_batch)
+            n = len(pcm[sl])
+            ptrs = (C.c_void_p * n)(*[a.ctypes.data if len(a) else None for a in pcm[sl]])
+            outs = (C.c_void_p * n)(*[p.ctypes.data if len(p) else None for p in probs[sl]])
+            louts = (C.c_void_p * n)(*[p.ctypes.data if len(p) else None for p in logits[sl]]) if return_logits else None
+            ns = np.asarray([len(a) for a in pcm[sl]], dtype=np.int64)
+            self._check(self.lib.ttasr_vad_probs(self.h, n, ptrs, ns.ctypes.data_as(C.POINTER(C.c_int64)), outs, louts), "vad_probs")
+        return (probs, logits) if return_logits else probs
 
     # -- a5 ------------------------------------------------------------------------------------
     def set_audio_ctx(self, n_ctx: int = 0):

@@ -231,8 +231,11 @@ def _read_hf_dir(path: str) -> Tuple[WhisperDims, Iterable[Tuple[str, np.ndarray
 class WhisperModel:
     def __init__(self, model_size_or_path: str, device: str = "auto", device_index: int = 0,
                  compute_type: str = "default", max_batch: int = 8, pipeline_depth: int = 1, cross_kv_fp8: bool = False,
-                 _engine_factory=None, **_unused):
-        """`cross_kv_fp8` (MI355X extension, opt-in serving mode, 16-bit compute types only): every engine context of the model
+                 vad_model=None, _engine_factory=None, **_unused):
+        """`vad_model` (MI355X extension): the Silero-v5 VAD network for vad_filter=True, run on the device - a path (`.npz`, or a
+        TorchScript / state-dict file when torch imports) or a mapping of the tensors of vad.SILERO_V5_TENSORS (`load_vad`).
+        Without it vad_filter=True behaves as before (operator callable, energy opt-in, or a warning).
+        `cross_kv_fp8` (MI355X extension, opt-in serving mode, 16-bit compute types only): every engine context of the model
         reads the e4m3 copy of the decoder's cross-attention cache wherever a kernel for it exists (engine option xkv_fp8 = 2:
         greedy rows, the rows of a beam or a sampled attempt, continuous-batching sessions).  Outputs are no longer those of the
         16-bit cache.  The lock-step and the continuous form of transcribe_many agree bit for bit only under the session's
@@ -301,6 +304,9 @@ class WhisperModel:
         self._lanes[0].load_weights(tensors)
         self._apply_lane_options(self._lanes[0])
         self._tls = threading.local()                             # which lane the calling thread drives (default: 0)
+        self._vad_state = None                                    # the device VAD's tensors, replayed into every lane (_lane)
+        if vad_model is not None:
+            self.load_vad(vad_model)
         self.special = self.engine.special
         self.max_batch = max_batch
         self.is_multilingual = dims.vocab >= 51865
@@ -340,7 +346,46 @@ class WhisperModel:
                 raise RuntimeError("pipeline_depth > 1 needs the HIP engine")
             self._lanes.append(lane)
             self._apply_lane_options(lane)
+            if self.has_device_vad:   # VAD weights are per context: a sharer loads its own 1.3 MB copy
+                lane.load_vad(self._vad_state)
         return self._lanes[i]
+
+    # -- voice activity detection on the device ------------------------------------------------------
+    @property
+    def has_device_vad(self) -> bool:
+        """True once load_vad() has put the VAD network on the model's engine contexts."""
+        return self.__dict__.get("_vad_state") is not None
+
+    def load_vad(self, path_or_mapping) -> None:
+        """Loads the Silero-v5-shaped VAD network (vad.load_silero_state) into every engine context of the model; contexts created
+        later get it too.  From then on vad_filter=True filters with it, unless a vad_speech_prob_fn is given."""
+        state = vad.load_silero_state(path_or_mapping)
+        for lane in self._lanes:
+            lane.load_vad(state)
+        self._vad_state = state
+
+    def vad_speech_probs(self, audios: Sequence[np.ndarray]) -> List[np.ndarray]:
+        """One speech probability per 512-sample frame of every recording, from the device network (Engine.vad_probs: all
+        recordings in one call, max_batch at a time)."""
+        if not self.has_device_vad:
+            raise RuntimeError("no VAD network is loaded (WhisperModel(vad_model=...) or model.load_vad(...))")
+        return self.engine.vad_probs(list(audios))
+
+    def _vad_source(self, params: dict, prob_fn, stacklevel: int = 3):
+        """The speech-probability source of a vad_filter=True call, in this order: an explicit vad_speech_prob_fn, the device
+        network, the vad_parameters={"backend": "energy"} opt-in, none (a warning; the whole clip counts as speech).
+        -> ("fn", callable) | ("device", None) | ("none", None); `backend` is removed from params."""
+        backend = params.pop("backend", None)
+        if prob_fn is not None:
+            return "fn", prob_fn
+        if self.has_device_vad:
+            return "device", None
+        if backend == "energy":
+            warnings.warn("vad_filter=True with the short-time-energy stand-in (NOT equivalent to Silero VAD)", stacklevel=stacklevel)
+            return "fn", None   # get_speech_timestamps' default
+        warnings.warn("vad_filter=True: the Silero VAD network is not available in this build and no "
+                      "vad_speech_prob_fn was given; the whole clip is treated as speech", stacklevel=stacklevel)
+        return "none", None
 
     def transcribe_groups(self, groups: Sequence[Sequence[Union[str, np.ndarray]]], pipeline_depth: Optional[int] = None, **kw
                           ) -> List[List[Tuple[List[Segment], TranscriptionInfo]]]:
@@ -569,16 +614,12 @@ class WhisperModel:
             # The network is not available offline: with a speech-probability function supplied by the operator
             # (`vad_speech_prob_fn=` here or `model.vad_speech_prob_fn`), or with the explicit opt-in
             # vad_parameters={"backend": "energy"}, the full pipeline runs; otherwise the whole clip counts as speech.
+            # With a VAD network loaded (WhisperModel(vad_model=...)) the probabilities come from the device.
             params = dict(kwargs.get("vad_parameters") or {})
-            backend = params.pop("backend", None)
-            prob_fn = kwargs.get("vad_speech_prob_fn") or self.vad_speech_prob_fn
-            if prob_fn is None and backend != "energy":
-                warnings.warn("vad_filter=True: the Silero VAD network is not available in this build and no "
-                              "vad_speech_prob_fn was given; the whole clip is treated as speech", stacklevel=2)
-            else:
-                if prob_fn is None:
-                    warnings.warn("vad_filter=True with the short-time-energy stand-in (NOT equivalent to Silero VAD)",
-                                  stacklevel=2)
+            kind, prob_fn = self._vad_source(params, kwargs.get("vad_speech_prob_fn") or self.vad_speech_prob_fn)
+            if kind == "device":
+                prob_fn = lambda a: self.engine.vad_probs([a])[0]
+            if kind != "none":
                 chunks = vad.get_speech_timestamps(audio, vad.VadOptions(**params), prob_fn)
                 audio_full_len = len(audio)
                 audio = vad.collect_chunks(audio, chunks)
@@ -805,7 +846,8 @@ class WhisperModel:
                         suppress_blank: bool = True, temperature: Union[float, Sequence[float]] = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0),
                         best_of: int = 5, compression_ratio_threshold: Optional[float] = 2.4, patience: float = 1.0,
                         hotwords: Optional[str] = None, prefix: Optional[str] = None, continuous: bool = False,
-                        multilingual: bool = False, detect_in_session: bool = False, session_prefill: Union[int, bool] = 0
+                        multilingual: bool = False, detect_in_session: bool = False, session_prefill: Union[int, bool] = 0,
+                        vad_filter: bool = False, vad_parameters: Optional[dict] = None
                         ) -> List[Tuple[List[Segment], TranscriptionInfo]]:
         """Several FILES in lock step: every round takes the next 30-s window of each unfinished file and runs them as
         ONE engine pass (log-mel, encoder, beam search with one previous-text prompt per file), so a folder is
@@ -834,7 +876,13 @@ class WhisperModel:
         session_prefill=N (continuous=True only; True = config.SESSION_PREFILL_DEFAULT): a window whose prompt has at least N
         prefillable positions - the previous text of condition_on_previous_text, up to <|startoftranscript|> - gets them from one
         admission pass of the session instead of N forced decode steps (Engine.session(prefill=N)); windows
-        that go in with the language placeholder are forced as before."""
+        that go in with the language placeholder are forced as before.
+        vad_filter=True (lock-step and continuous=True alike): every file is filtered as `transcribe` filters it, BEFORE decoding
+        starts - with a VAD network loaded, ONE device call over all files (Engine.vad_probs; with continuous=True before the
+        session begins), else the model's vad_speech_prob_fn, the vad_parameters={"backend": "energy"} opt-in or the warning of
+        `transcribe`.  Each file decodes the concatenation of its speech chunks; its segments are mapped back to the original
+        time line and its info carries duration / duration_after_vad as `transcribe` fills them.  A file the VAD empties yields no
+        segments and takes no decode row."""
         from .engine import session_prefill_value
         eng = self.engine
         session_prefill = session_prefill_value(session_prefill)
@@ -856,13 +904,27 @@ class WhisperModel:
                          patience, temps, best_of, compression_ratio_threshold, bool(word_timestamps), hotwords, prefix)
         if continuous:
             p["beam_size"] = int(beam_size)
-        files = []
+        pcm = []
         for a in audios:
             a = decode_audio(a) if isinstance(a, str) else np.asarray(a)
             if a.ndim != 1:
                 raise ValueError(f"audio must be mono float32 [n] @16 kHz, got shape {a.shape}")
-            fs = self._new_file_state(np.ascontiguousarray(a, dtype=np.float32), initial_prompt)
-            fs["segments"] = []
+            pcm.append(np.ascontiguousarray(a, dtype=np.float32))
+        full_len = [len(a) for a in pcm]
+        speech: List[Optional[list]] = [None] * len(pcm)   # per file: its speech chunks on the original time line (None: not filtered)
+        if vad_filter and pcm:
+            params = dict(vad_parameters or {})
+            kind, prob_fn = self._vad_source(params, self.vad_speech_prob_fn)
+            if kind != "none":
+                options = vad.VadOptions(**params)
+                probs = self.engine.vad_probs(pcm) if kind == "device" else None   # all files, one device call
+                for i, a in enumerate(pcm):
+                    speech[i] = vad.get_speech_timestamps(a, options, (lambda _a, q=probs[i]: q) if probs is not None else prob_fn)
+                    pcm[i] = vad.collect_chunks(a, speech[i])
+        files = []
+        for a, chunks, n_full in zip(pcm, speech, full_len):
+            fs = self._new_file_state(a, initial_prompt)
+            fs["segments"], fs["speech"], fs["full_len"] = [], chunks, n_full
             fs["file_max"] = self._file_feature_max(fs["audio"])   # whole-file dynamic-range floor, as `transcribe`
             files.append(fs)
         multilingual = bool(multilingual) and self.is_multilingual
@@ -912,9 +974,12 @@ class WhisperModel:
                     fs["segments"].extend(self._finish_window(fs, 0, attempt, win_frames, p))
         out = []
         for fs in files:
-            dur = len(fs["audio"]) / SAMPLE_RATE
+            dur_after = len(fs["audio"]) / SAMPLE_RATE
+            dur = fs["full_len"] / SAMPLE_RATE
+            if fs["speech"] is not None:   # back to the original time line, as `transcribe` does
+                fs["segments"] = list(vad.restore_speech_timestamps(fs["segments"], fs["speech"]))
             lang, lang_p, all_p = fs["lang_info"]
-            info = TranscriptionInfo(language=lang, language_probability=lang_p, duration=dur, duration_after_vad=dur,
+            info = TranscriptionInfo(language=lang, language_probability=lang_p, duration=dur, duration_after_vad=dur_after,
                                      all_language_probs=all_p,
                                      transcription_options=dict(beam_size=beam, task=task, without_timestamps=without_timestamps,
                                                                 condition_on_previous_text=condition_on_previous_text,

@@ -15,6 +15,7 @@ network weights exist offline, so:
 """
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass
 from typing import Callable, Dict, List, Optional, Sequence
 
@@ -47,6 +48,95 @@ def energy_speech_prob(audio: np.ndarray, window: int = WINDOW) -> np.ndarray:
     db = 20.0 * np.log10(rms)
     floor = max(float(np.percentile(db, 10)), -60.0)
     return (1.0 / (1.0 + np.exp(-(db - floor - 6.0) / 1.5))).astype(np.float32)
+
+
+# The Silero-v5-shaped network (16 kHz branch) the engine runs on the device (include/ttasr.h ttasr_vad_*; DESIGN.md section
+# 4.20): THE name / shape table of the Python side.  A leading "_model." of a state-dict key is stripped.  UNPINNED: the names and
+# shapes are those of the published v5 TorchScript file as far as they are publicly described; no such file exists offline, so
+# faithfulness to it is not checked anywhere - the network is held to the float64 restatement of tests/vad_reference.py.
+SILERO_V5_TENSORS: Dict[str, tuple] = {
+    "stft.forward_basis_buffer": (258, 1, 256),
+    "encoder.0.reparam_conv.weight": (128, 129, 3), "encoder.0.reparam_conv.bias": (128,),
+    "encoder.1.reparam_conv.weight": (64, 128, 3), "encoder.1.reparam_conv.bias": (64,),
+    "encoder.2.reparam_conv.weight": (64, 64, 3), "encoder.2.reparam_conv.bias": (64,),
+    "encoder.3.reparam_conv.weight": (128, 64, 3), "encoder.3.reparam_conv.bias": (128,),
+    "decoder.rnn.weight_ih": (512, 128), "decoder.rnn.weight_hh": (512, 128),
+    "decoder.rnn.bias_ih": (512,), "decoder.rnn.bias_hh": (512,),
+    "decoder.decoder.2.weight": (1, 128, 1), "decoder.decoder.2.bias": (1,),
+}
+SYNTH_SILERO_SEED = 1   # the seed tests and tools use: on the suite's test signal its probabilities keep clear of both thresholds
+
+
+def stft_basis() -> np.ndarray:
+    """The Hann-windowed DFT basis of the network's STFT, float32 [258, 1, 256]: row b < 129 is cos(2 pi b m / 256) hann[m], row
+    129 + b is -sin(2 pi b m / 256) hann[m] (periodic Hann), so S[b] + i S[129 + b] = rfft(frame * hann)[b]."""
+    m = np.arange(256, dtype=np.float64)
+    hann = 0.5 - 0.5 * np.cos(2.0 * np.pi * m / 256.0)
+    ang = 2.0 * np.pi * np.arange(129, dtype=np.float64)[:, None] * m[None, :] / 256.0
+    return np.concatenate([np.cos(ang) * hann, -np.sin(ang) * hann])[:, None, :].astype(np.float32)
+
+
+def synth_silero_weights(seed: int = SYNTH_SILERO_SEED) -> Dict[str, np.ndarray]:
+    """Seeded synthetic weights in the shapes of SILERO_V5_TENSORS (float32): the STFT basis is the true Hann-windowed DFT basis,
+    everything else is drawn - fan-in scaled, with an output head whose positive weights and negative bias put silence below
+    and noise above 0.5.  Deterministic per seed.  NOT a voice-activity detector: a stand-in that exercises the network."""
+    rng = np.random.default_rng([0x51E20, int(seed)])
+    out: Dict[str, np.ndarray] = {}
+    for name, shape in SILERO_V5_TENSORS.items():
+        if name == "stft.forward_basis_buffer":
+            w = stft_basis()
+        elif name.endswith("reparam_conv.weight"):
+            w = rng.standard_normal(shape) * (1.6 / np.sqrt(shape[1] * shape[2]))
+        elif name.endswith("reparam_conv.bias"):
+            w = rng.standard_normal(shape) * 0.05
+        elif name in ("decoder.rnn.weight_ih", "decoder.rnn.weight_hh"):
+            w = rng.standard_normal(shape) * (1.0 / np.sqrt(shape[1]))
+        elif name in ("decoder.rnn.bias_ih", "decoder.rnn.bias_hh"):
+            w = rng.standard_normal(shape) * 0.1
+        elif name == "decoder.decoder.2.weight":
+            w = np.abs(rng.standard_normal(shape)) * 0.6
+        else:
+            w = np.full(shape, -3.5)
+        out[name] = np.ascontiguousarray(w, dtype=np.float32)
+    return out
+
+
+def load_silero_state(path_or_mapping) -> Dict[str, np.ndarray]:
+    """The VAD tensors of SILERO_V5_TENSORS as float32 arrays, from a mapping (state dict; torch tensors or arrays), an `.npz`
+    file, or - when torch imports - a TorchScript module / state-dict file.  A leading "_model." is stripped; keys outside the
+    table (the 8 kHz branch) are ignored; a missing tensor or a wrong shape raises ValueError."""
+    src = path_or_mapping
+    if isinstance(src, (str, bytes)) or hasattr(src, "__fspath__"):
+        path = os.fspath(src)
+        if str(path).lower().endswith(".npz"):
+            with np.load(path) as z:
+                src = {k: z[k] for k in z.files}
+        else:
+            try:
+                import torch
+            except ImportError as e:
+                raise RuntimeError(f"{path}: reading a TorchScript / state-dict file needs torch; convert it to .npz") from e
+            try:
+                src = torch.jit.load(path, map_location="cpu").state_dict()
+            except Exception:
+                src = torch.load(path, map_location="cpu", weights_only=True)
+                if hasattr(src, "state_dict"):
+                    src = src.state_dict()
+    out: Dict[str, np.ndarray] = {}
+    for key, value in dict(src).items():
+        name = key[len("_model."):] if key.startswith("_model.") else key
+        if name not in SILERO_V5_TENSORS:
+            continue
+        if hasattr(value, "detach"):
+            value = value.detach().cpu().float().numpy()
+        a = np.ascontiguousarray(value, dtype=np.float32)
+        if a.shape != SILERO_V5_TENSORS[name]:
+            raise ValueError(f"VAD tensor {name}: shape {a.shape}, expected {SILERO_V5_TENSORS[name]}")
+        out[name] = a
+    missing = [n for n in SILERO_V5_TENSORS if n not in out]
+    if missing:
+        raise ValueError(f"VAD state is missing {missing}")
+    return out
 
 
 def silero_speech_prob_fn(step: Callable[[np.ndarray, np.ndarray], "tuple[float, np.ndarray]"], context: int = 64,

@@ -1,0 +1,148 @@
+"""Device VAD (Engine.vad_probs: the Silero-v5-shaped network of kernels_vad.hip) - throughput, what it replaces, its share of a
+folder group, and its accuracy cases.  Synthetic weights (vad.synth_silero_weights), large-v3 geometry for the group.
+
+  timing     Engine.vad_probs on 1, 24 and 120 recordings of 60 s and on one of 3600 s: wall time around the call (it ends in
+             a stream synchronise and includes staging the host PCM), 2 warm-up calls, median / min / max of --repeats calls,
+             and audio-s/s from the median.
+  reference  the float32 numpy restatement (tests/vad_reference.py) driven frame by frame through vad.silero_speech_prob_fn on
+             this host, on 60 s: the Python loop the device call replaces.
+  share      WhisperModel.transcribe_many(24 recordings of 60 s, beam 5, <= 64 tokens per window, vad_filter=True) - the folder
+             tool's default group - and the vad_probs call over the same 24 recordings inside it.
+  accuracy   the cases of tests/test_gpu_vad.py: largest distance of the device's logits / probabilities from the float64
+             reference and, beside it, of the float32 reference from float64.
+Nothing is asserted.  One JSON object on stdout and, with --out, in that file.  --hour-only: three calls on the 3600-s recording
+and nothing else (the command a kernel trace is taken of).
+
+    python tools/vad_bench.py [--model large-v3] [--repeats 7] [--out profiles/vad_device.json]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+import warnings
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from taiwan_tongues_asr_ce_amd import vad  # noqa: E402
+
+HEADLINE = 2150.0   # audio-s/s of the engine's headline workload (README.md)
+
+
+def bursts(seed: int, total_s: float) -> np.ndarray:
+    """Noise bursts of 1-3 s between digital silences of 2.5-4 s (the shape of the suite's test signal), cut to total_s."""
+    rng = np.random.default_rng([0xBE7C4, seed])
+    parts, n = [], 0
+    while n < total_s * 16000:
+        gap, burst = int(rng.uniform(2.5, 4.0) * 16000), int(rng.uniform(1.0, 3.0) * 16000)
+        parts += [np.zeros(gap, np.float32), (rng.standard_normal(burst) * rng.uniform(0.08, 0.25)).astype(np.float32)]
+        n += gap + burst
+    return np.concatenate(parts)[: int(total_s * 16000)]
+
+
+def timed(fn, repeats: int, warm: int = 2):
+    for _ in range(warm):
+        fn()
+    xs = []
+    for _ in range(repeats):
+        t = time.perf_counter()
+        fn()
+        xs.append(time.perf_counter() - t)
+    return {"median_s": round(statistics.median(xs), 5), "min_s": round(min(xs), 5), "max_s": round(max(xs), 5), "runs": len(xs)}
+
+
+def accuracy(engine) -> dict:
+    import test_gpu_vad as T
+    from vad_reference import cached_probs, test_signal
+    sig, long = test_signal(), T._long()
+    C = T.CHUNK
+    cases = {"n=1 short lengths": [([T._noise(n, n)], [("noise", n)]) for n in T.LENGTHS],
+             "n=5 mixed": [([T._noise(n, n) for n in lens], [("noise", n) for n in lens]) for lens in T.MIXED],
+             "40-s test signal": [([sig], ["signal"])],
+             "chunk boundary": [([long[:n] for n in (512 * C - 1, 512 * C, 512 * C + 1, 512 * (2 * C + 3))],
+                                 [("long", n) for n in (512 * C - 1, 512 * C, 512 * C + 1, 512 * (2 * C + 3))])]}
+    out = {}
+    for name, calls in cases.items():
+        w = dict(device_logit=0.0, device_prob=0.0, float32_ref_logit=0.0, float32_ref_prob=0.0)
+        for audios, keys in calls:
+            p, l = engine.vad_probs(audios, return_logits=True)
+            for a, k, pi, li in zip(audios, keys, p, l):
+                p64, l64 = cached_probs(T.SEED, k, a)
+                p32, l32 = cached_probs(T.SEED, k, a, np.float32)
+                w["device_logit"] = max(w["device_logit"], float(np.abs(li - l64).max()))
+                w["device_prob"] = max(w["device_prob"], float(np.abs(pi - p64).max()))
+                w["float32_ref_logit"] = max(w["float32_ref_logit"], float(np.abs(l32 - l64).max()))
+                w["float32_ref_prob"] = max(w["float32_ref_prob"], float(np.abs(p32 - p64).max()))
+        out[name] = {k: float(f"{v:.3e}") for k, v in w.items()}
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="large-v3")
+    ap.add_argument("--compute", default="bfloat16")
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--hour-only", action="store_true")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    from taiwan_tongues_asr_ce_amd.model import WhisperModel
+    warnings.simplefilter("ignore")
+    weights = vad.synth_silero_weights()
+    hour = bursts(1000, 3600.0)
+    if args.hour_only:
+        from taiwan_tongues_asr_ce_amd.config import COMPUTE_F32, PRESETS
+        from taiwan_tongues_asr_ce_amd.engine import Engine
+        e = Engine(PRESETS["micro"], COMPUTE_F32, 1)
+        e.load_vad(weights)
+        for _ in range(3):
+            e.vad_probs([hour])
+        print(json.dumps({"hour_only_calls": 3, "frames_per_call": -(-len(hour) // 512)}))
+        return
+    m = WhisperModel(f"synthetic:{args.model}", device="cuda", compute_type=args.compute, max_batch=120, vad_model=weights)
+    eng = m.engine
+    files = [bursts(i, 60.0) for i in range(120)]
+    res = {"tool": "tools/vad_bench.py", "model": args.model, "compute_type": args.compute, "weights": "vad.synth_silero_weights()",
+           "chunk_frames": 1024, "timing": {}}
+    for name, audios in (("1 x 60 s", files[:1]), ("24 x 60 s", files[:24]), ("120 x 60 s", files), ("1 x 3600 s", [hour])):
+        t = timed(lambda: eng.vad_probs(audios), args.repeats)
+        secs = sum(len(a) for a in audios) / 16000.0
+        t["audio_s"] = secs
+        t["audio_s_per_s"] = round(secs / t["median_s"], 1)
+        t["x_headline_2150"] = round(t["audio_s_per_s"] / HEADLINE, 1)
+        res["timing"][name] = t
+    from vad_reference import SileroRef
+    ref = SileroRef(weights, np.float32)
+    fn = vad.silero_speech_prob_fn(lambda frame, state: ref.step(frame, state))
+    t = timed(lambda: fn(files[0]), 3, warm=1)
+    t["audio_s_per_s"] = round(60.0 / t["median_s"], 1)
+    res["reference_float32_numpy_frame_by_frame_60s"] = t
+    kw = dict(language="zh", beam_size=5, temperature=0.0, log_prob_threshold=None, max_new_tokens=64)
+    group = files[:24]
+    m.transcribe_many(group, vad_filter=True, **kw)                     # warm-up: graphs, scratch
+    t_many = timed(lambda: m.transcribe_many(group, vad_filter=True, **kw), 3, warm=0)
+    t_plain = timed(lambda: m.transcribe_many(group, **kw), 3, warm=1)
+    t_vad = res["timing"]["24 x 60 s"]["median_s"]
+    kept = sum(info.duration_after_vad for _, info in m.transcribe_many(group, vad_filter=True, **kw)) / (24 * 60.0)
+    res["share_of_a_24_file_group"] = {
+        "transcribe_many_vad_filter_s": t_many, "vad_probs_s": t_vad, "vad_share": round(t_vad / t_many["median_s"], 4),
+        "transcribe_many_without_vad_s": t_plain, "audio_kept_by_vad": round(kept, 3),
+        "group_audio_s_per_s_with_vad": round(24 * 60.0 / t_many["median_s"], 1),
+        "group_audio_s_per_s_without_vad": round(24 * 60.0 / t_plain["median_s"], 1)}
+    res["accuracy_vs_float64"] = accuracy(eng)
+    text = json.dumps(res, indent=1)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+    m.close()
+
+
+if __name__ == "__main__":
+    main()
