@@ -135,11 +135,20 @@ template <int N, typename Op> __device__ __forceinline__ float stride_reduce(flo
 __device__ __forceinline__ float wave_sum(float v) { return group_reduce<64>(v, OpSum{}); }
 __device__ __forceinline__ float wave_max(float v) { return group_reduce<64>(v, OpMax{}); }
 
-// Kernel arguments live in the kernarg segment and reach SGPRs through s_load; the compiler treats those loads as free to
-// re-materialise and sinks them next to their first use, which in these kernels produced two or three SERIALISED
-// round trips (pointer -> wait -> address -> second pointer -> wait ...) in front of the first weight load - about a
-// microsecond each in a decode chain whose kernels only take 3-8.  Passing every argument through an empty asm at kernel
-// entry makes the values opaque, so all s_loads are issued together, once.
+// Kernel arguments of the decode-chain kernels, in two stages.
+//  1. The LEADING pointer / int parameters arrive PRELOADED in SGPRs (Makefile PRELOAD: up to 14 dwords; a struct passed by
+//     value ends the preloaded sequence).  Every kernel of the decode step therefore lists first, flat, what forms the addresses of
+//     its first load batch, with small bounded values sharing a dword (d, slab counts, head and page counts: bounded by
+//     ttasr_create or checked by the launcher, which records launch_fault and launches nothing when a value does not fit).
+//     Unbounded values (n_audio_ctx, element offsets into the KV caches) stay full width.  The first vector load waits for no
+//     kernarg fetch; a position (*step, done flags) is read by the scalar unit from a preloaded pointer at entry (sload_i32).
+//  2. The TAIL (output pointers, what only the epilogue needs) still lives in the kernarg segment and reaches SGPRs through
+//     s_load.  The compiler treats those loads as free to re-materialise and sinks them next to their first use, which put a
+//     serialised scalar round trip in front of the final stores; passing the tail through an empty asm makes the values opaque at
+//     ONE place.  That place is a pin_tail() lambda behind the first load batch, fenced by __builtin_amdgcn_sched_barrier(0): the
+//     fetch flies under the vector loads.  (Rounds 2-6 pinned every argument at kernel entry: with preload that made each wave
+//     wait for the tail fetch before its first address existed.)  tools/kernel_entry_report.py prints, per kernel, the dwords
+//     preloaded, the scalar loads left and whether a wait precedes the first vector memory instruction.
 template <class T> __device__ __forceinline__ T sgpr_pin(T v) {
   asm volatile("" : "+s"(v));
   return v;

@@ -532,17 +532,28 @@ __global__ __launch_bounds__(NWV * 64) void cross_attn_decode_kernel(const T* q,
 // form runs 6.42-6.48 TB/s: the gain at B = 32 is a shorter tail of the uneven 3-vs-2 workgroup split, not a faster stream.
 // 16-bit storage, 4 waves, decode step only (no PROBS).
 constexpr int XATTN_DEEP_U = 8;              // rows per lane and batch of the deep form
+// Argument order (common.hpp sgpr_pin): the first batch - the flags, the first K rows, the query - needs K, done, the query source
+// (T rows [B][d], or with QSLAB the f32 partial tiles of the K-split q GEMM) and its bias, geo = H | slabs << 5 | rows << 8
+// (H <= 20: ttasr_create; slabs <= 4, rows = gridDim.y < 2^24: launcher - read from the grid it would be one more hidden-argument
+// fetch), Tk, kv_div and the slab stride (< 2^32 elements: launcher): 12 dwords, all preloaded.  V, deep_items and out are the
+// tail, fetched under that batch.
 template <typename T, bool NT, bool QSLAB, int U>
-__global__ __launch_bounds__(256) void cross_attn_pipe_kernel(const T* q, const T* K, const T* V, T* out, const int32_t* done, int H,
-                                                              int Tk, int kv_div, int deep_items, SlabIn sq) {
+__global__ __launch_bounds__(256) void cross_attn_pipe_kernel(const T* K, const int32_t* done, const void* qsrc, const float* sbias, unsigned geo,
+                                                              int Tk, int kv_div, unsigned sstride, const T* V_, int deep_items_, T* out_) {
   static_assert(sizeof(T) == 2, "16-bit storage only");
   constexpr int VEC = 8, LPR = 8, RPI = 8, NWV = 4;
   extern __shared__ float sc[];  // [Tk] scores, then [NWV][64] partial outputs, [2 * NWV] reductions
-  q = sgpr_pin_ptr(q); K = sgpr_pin_ptr(K); V = sgpr_pin_ptr(V); out = sgpr_pin_ptr(out); done = sgpr_pin_ptr(done);
-  H = sgpr_pin(H); Tk = sgpr_pin(Tk); kv_div = sgpr_pin(kv_div); deep_items = sgpr_pin(deep_items);
-  sq.slab = sgpr_pin_ptr(sq.slab); sq.bias = sgpr_pin_ptr(sq.bias); sq.n = sgpr_pin(sq.n); sq.stride = sgpr_pin(sq.stride);
-  sq.ld = sgpr_pin(sq.ld);
-  const int slot = blockIdx.y, nrows = gridDim.y, h = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  K = sgpr_pin_ptr(K); done = sgpr_pin_ptr(done); qsrc = sgpr_pin_ptr(qsrc); sbias = sgpr_pin_ptr(sbias); geo = sgpr_pin(geo);
+  Tk = sgpr_pin(Tk); kv_div = sgpr_pin(kv_div); sstride = sgpr_pin(sstride);
+  const int H = geo & 31;
+  const T* q = (const T*)qsrc;
+  SlabIn sq;
+  sq.slab = (const float*)qsrc; sq.bias = sbias; sq.n = (geo >> 5) & 7; sq.stride = (int64_t)sstride; sq.ld = 64 * H;
+  const T* V;
+  int deep_items;
+  T* out;
+  auto pin_tail = [&]() { V = sgpr_pin_ptr(V_); deep_items = sgpr_pin(deep_items_); out = sgpr_pin_ptr(out_); };   // second stage
+  const int slot = blockIdx.y, nrows = (int)(geo >> 8), h = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int d = H * 64;
   const int sub = lane % LPR, rin = lane / LPR;
   float* part = sc + Tk;
@@ -561,10 +572,11 @@ __global__ __launch_bounds__(256) void cross_attn_pipe_kernel(const T* q, const 
   const int flag = *fp;
   int b = slot;
   const T* Kp; const T* Vp;
+  int64_t kv_off;                      // this item's offset into K and V: V itself arrives with the tail
   auto place = [&](int row) {
     const int bk = kv_div == 1 ? row : row / kv_div;
-    Kp = K + ((int64_t)bk * H + h) * Tk * 64 + sub * VEC;
-    Vp = V + ((int64_t)bk * H + h) * Tk * 64 + sub * VEC;
+    kv_off = ((int64_t)bk * H + h) * Tk * 64 + sub * VEC;
+    Kp = K + kv_off;
   };
   place(b);
   const int n_it = (Tk + NWV * RPI - 1) / (NWV * RPI);
@@ -590,6 +602,9 @@ __global__ __launch_bounds__(256) void cross_attn_pipe_kernel(const T* q, const 
     else RowVec<T>::load(q + (int64_t)row * d + h * 64 + sub * VEC, qv);
   };
   fetch_q(b);
+  __builtin_amdgcn_sched_barrier(0);
+  pin_tail();
+  __builtin_amdgcn_sched_barrier(0);
   int n_live = nrows;
   if (done) {
     // The exits below are workgroup-uniform and sit AFTER the first K batch and the query were requested; the never-taken store
@@ -661,6 +676,7 @@ __global__ __launch_bounds__(256) void cross_attn_pipe_kernel(const T* q, const 
       if (it0 + UU < n_it) score(it0 + UU, rb);
       __builtin_amdgcn_sched_barrier(0);
     }
+    Vp = V + kv_off;
     issue(Vp, 0, ra);   // V rows do not depend on the softmax: in flight under it
     __builtin_amdgcn_sched_barrier(0);
     mloc = wave_max(mloc);
@@ -1121,8 +1137,16 @@ void launch_cross_attn_decode(const T* q, const T* K, const T* V, T* out, int B,
   } while (0)
   if constexpr (sizeof(T) == 2) {
     if ((ko.xattn_variant & 2) && !qp.W) {   // software-pipelined form (default since round 4), 3 rows per lane and batch
-#define TTASR_XP(NT_, QS_) hipLaunchKernelGGL((cross_attn_pipe_kernel<T, NT_, QS_, 3>), dim3(H, B), dim3(256), lds, s, q, K, V, out, done, H, Tk, kv_div, ko.xattn_deep_items, sq)
+#define TTASR_XP(NT_, QS_)                                                                                                                \
+  hipLaunchKernelGGL((cross_attn_pipe_kernel<T, NT_, QS_, 3>), dim3(H, B), dim3(256), lds, s, K, done, QS_ ? (const void*)sq.slab : (const void*)q, \
+                     sq.bias, (unsigned)H | (unsigned)sq.n << 5 | (unsigned)B << 8, Tk, kv_div, (unsigned)sq.stride, V, ko.xattn_deep_items, out)
       const bool nt = ko.xattn_variant & 1, qs = sq.n > 0;
+      if (H < 1 || H > 31 || B < 1 || B >= (1 << 24) || sq.n < 0 || sq.n > 4 || sq.stride < 0 || sq.stride > (int64_t)UINT32_MAX ||
+          (qs && sq.ld != 64 * H)) {
+        launch_fault("cross_attn_pipe: H %d, rows %d, slabs %d (stride %lld, ld %d) do not fit the kernel's argument words", H, B, sq.n,
+                     (long long)sq.stride, sq.ld);
+        return;
+      }
       if (g_kernel_sig_on) snprintf(g_kernel_sig, sizeof g_kernel_sig, "cross_attn_pipe_kernel<%s, %s, %s, 3> grid %d", sig_type<T>(),
                                     nt ? "true" : "false", qs ? "true" : "false", H * B * 256);
       if (nt) { if (qs) TTASR_XP(true, true); else TTASR_XP(true, false); } else { if (qs) TTASR_XP(false, true); else TTASR_XP(false, false); }

@@ -306,20 +306,28 @@ template void launch_layernorm_add<f16_t>(float*, const f16_t*, const float*, co
 // MAXS = LN_ROW_POS with EMBED (the continuous-batching session, engine_refill.hip): pre.step is a PER-ROW position array and
 // row r's positional-embedding row is pos[step[r]] instead of pos[*step].
 // ------------------------------------------------------------------------------------------------
+// Argument order (common.hpp sgpr_pin): the pointers and ints that form the addresses of the load batch lead the list and arrive
+// preloaded in SGPRs (14 dwords, all the compiler preloads); the two output pointers are the tail, fetched under the loads.
+//   slab / plain form: a0 = x, a1 = bias, a2 = slab, a3 unused        embed form: a0 = emb, a1 = pos, a2 = tok, a3 = step
+//   dn = d | n_slab << 16 (d <= 1280, n_slab <= 16: ttasr_create / the launcher), slab_stride in elements (< 2^32: launcher)
 constexpr int LN_ROW_POS = -1;
 template <typename T, int MAXS, bool EMBED>
-__global__ __launch_bounds__(320) void layernorm_rows_kernel(const float* __restrict__ x_, const float* __restrict__ gamma_,
-                                                             const float* __restrict__ beta_, T* __restrict__ out_, int d_,
-                                                             LnPre pre) {
+__global__ __launch_bounds__(320) void layernorm_rows_kernel(const float* __restrict__ gamma_, const float* __restrict__ beta_,
+                                                             const void* a0_, const void* a1_, const void* a2_, const void* a3_,
+                                                             unsigned dn_, unsigned slab_stride_, T* __restrict__ out_, float* x_out_) {
   constexpr int NWAVE = 5;  // always launched with 320 threads (d <= 1280): the cross-wave sums are five fixed reads, no loop
   __shared__ float red[2][8];
-  // every kernel argument fetched in ONE batch at entry (common.hpp sgpr_pin)
-  const float* x = sgpr_pin_ptr(x_); const float* gamma = sgpr_pin_ptr(gamma_); const float* beta = sgpr_pin_ptr(beta_);
-  T* out = sgpr_pin_ptr(out_);
-  const int d = sgpr_pin(d_);
-  pre.bias = sgpr_pin_ptr(pre.bias); pre.slab = sgpr_pin_ptr(pre.slab); pre.n_slab = sgpr_pin(pre.n_slab);
-  pre.slab_stride = sgpr_pin(pre.slab_stride); pre.x_out = sgpr_pin_ptr(pre.x_out);
-  if constexpr (EMBED) { pre.tok = sgpr_pin_ptr(pre.tok); pre.step = sgpr_pin_ptr(pre.step); pre.emb = sgpr_pin_ptr(pre.emb); pre.pos = sgpr_pin_ptr(pre.pos); }
+  const float* gamma = sgpr_pin_ptr(gamma_); const float* beta = sgpr_pin_ptr(beta_);
+  const void* a0 = sgpr_pin_ptr(a0_); const void* a1 = sgpr_pin_ptr(a1_); const void* a2 = sgpr_pin_ptr(a2_); const void* a3 = sgpr_pin_ptr(a3_);
+  const unsigned dn = sgpr_pin(dn_);
+  const int d = dn & 0xffff;
+  struct { const float* bias; const float* slab; int n_slab; int64_t slab_stride; float* x_out; const int32_t* tok; const int32_t* step;
+           const void* emb; const void* pos; } pre;
+  const float* x = (const float*)a0;
+  pre.bias = (const float*)a1; pre.slab = (const float*)a2; pre.n_slab = (int)(dn >> 16); pre.slab_stride = (int64_t)sgpr_pin(slab_stride_);
+  pre.emb = a0; pre.pos = a1; pre.tok = (const int32_t*)a2; pre.step = (const int32_t*)a3;
+  T* out;
+  auto pin_tail = [&]() { out = sgpr_pin_ptr(out_); pre.x_out = sgpr_pin_ptr(x_out_); };   // second stage, behind the load batch
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nv = d >> 2, i = min(tid, nv - 1);
   const bool live = tid < nv;
@@ -327,8 +335,9 @@ __global__ __launch_bounds__(320) void layernorm_rows_kernel(const float* __rest
   float4 v;
   const float4 gm = ((const float4*)gamma)[i], bt = ((const float4*)beta)[i];
   if constexpr (EMBED) {
-    const T* er = (const T*)pre.emb + (int64_t)pre.tok[row] * d;
-    const T* pr = (const T*)pre.pos + (int64_t)(MAXS == LN_ROW_POS ? pre.step[row] : *pre.step) * d;
+    // token and position: written by an earlier kernel of the stream, read by the scalar unit from the preloaded pointers
+    const T* er = (const T*)pre.emb + (int64_t)sload_i32(pre.tok + row) * d;
+    const T* pr = (const T*)pre.pos + (int64_t)sload_i32(MAXS == LN_ROW_POS ? pre.step + row : pre.step) * d;
     if constexpr (sizeof(T) == 4) {
       const float4 a = ((const float4*)er)[i], b = ((const float4*)pr)[i];
       v = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
@@ -348,6 +357,8 @@ __global__ __launch_bounds__(320) void layernorm_rows_kernel(const float* __rest
       for (int s = 0; s < MAXS; ++s)
         sl[s] = ((const float4*)(pre.slab + (int64_t)min(s, pre.n_slab - 1) * pre.slab_stride + (int64_t)row * d))[i];
       __builtin_amdgcn_sched_barrier(0);  // every load above is issued before the first use below: ONE round trip
+      pin_tail();
+      __builtin_amdgcn_sched_barrier(0);
       v.x += bs.x; v.y += bs.y; v.z += bs.z; v.w += bs.w;
       // slab 0 always exists in this instantiation (n_slab >= 1): adding it unconditionally keeps its load from being sunk
       // behind a branch (= a second, serialised round trip)
@@ -355,6 +366,11 @@ __global__ __launch_bounds__(320) void layernorm_rows_kernel(const float* __rest
       for (int s = 0; s < MAXS; ++s)
         if (s == 0 || s < pre.n_slab) { v.x += sl[s].x; v.y += sl[s].y; v.z += sl[s].z; v.w += sl[s].w; }
     }
+  }
+  if constexpr (EMBED || MAXS <= 0) {
+    __builtin_amdgcn_sched_barrier(0);
+    pin_tail();
+    __builtin_amdgcn_sched_barrier(0);
   }
   if (live && (EMBED || MAXS > 0)) ((float4*)(pre.x_out + (int64_t)row * d))[i] = v;
   float s1 = live ? (v.x + v.y) + (v.z + v.w) : 0.f;
@@ -381,25 +397,43 @@ __global__ __launch_bounds__(320) void layernorm_rows_kernel(const float* __rest
     ((uint2*)o)[i] = p;
   }
 }
+static bool ln_rows_words(int d, const LnPre& pre, unsigned& dn, unsigned& stride) {
+  if (d > 1280 || (d & 3)) { launch_fault("layernorm_rows needs d <= 1280, d %% 4 == 0 (got %d)", d); return false; }
+  if (pre.n_slab < 0 || pre.n_slab > 16) { launch_fault("layernorm_rows sums at most 16 slabs (got %d)", pre.n_slab); return false; }
+  if (pre.slab_stride < 0 || pre.slab_stride > (int64_t)UINT32_MAX) {
+    launch_fault("layernorm_rows needs a slab stride below 2^32 elements (got %lld)", (long long)pre.slab_stride); return false;
+  }
+  dn = (unsigned)d | (unsigned)pre.n_slab << 16;
+  stride = (unsigned)pre.slab_stride;
+  return true;
+}
 template <typename T>
 void launch_layernorm_rows(const float* x, const float* gamma, const float* beta, T* out, int rows, int d, const LnPre& pre,
                            hipStream_t s) {
-  if (d > 1280 || (d & 3)) { launch_fault("layernorm_rows needs d <= 1280, d %% 4 == 0 (got %d)", d); return; }
-  if (pre.n_slab > 16) { launch_fault("layernorm_rows sums at most 16 slabs (got %d)", pre.n_slab); return; }
+  unsigned dn, st;
+  if (!ln_rows_words(d, pre, dn, st)) return;
   dim3 grid(rows), block(320);  // five waves whatever d is (ttasr_create: d <= 1280): threads past d / 4 contribute zeros
-  if (pre.tok) hipLaunchKernelGGL((layernorm_rows_kernel<T, 0, true>), grid, block, 0, s, x, gamma, beta, out, d, pre);
-  else if (pre.n_slab == 0) hipLaunchKernelGGL((layernorm_rows_kernel<T, 0, false>), grid, block, 0, s, x, gamma, beta, out, d, pre);
-  else if (pre.n_slab <= 2) hipLaunchKernelGGL((layernorm_rows_kernel<T, 2, false>), grid, block, 0, s, x, gamma, beta, out, d, pre);
-  else if (pre.n_slab <= 4) hipLaunchKernelGGL((layernorm_rows_kernel<T, 4, false>), grid, block, 0, s, x, gamma, beta, out, d, pre);
-  else if (pre.n_slab <= 8) hipLaunchKernelGGL((layernorm_rows_kernel<T, 8, false>), grid, block, 0, s, x, gamma, beta, out, d, pre);
-  else hipLaunchKernelGGL((layernorm_rows_kernel<T, 16, false>), grid, block, 0, s, x, gamma, beta, out, d, pre);
+#define TTASR_LN_ROWS(MAXS_)                                                                                                          \
+  hipLaunchKernelGGL((layernorm_rows_kernel<T, MAXS_, false>), grid, block, 0, s, gamma, beta, (const void*)x, (const void*)pre.bias, \
+                     (const void*)pre.slab, (const void*)nullptr, dn, st, out, pre.x_out)
+  if (pre.tok)
+    hipLaunchKernelGGL((layernorm_rows_kernel<T, 0, true>), grid, block, 0, s, gamma, beta, pre.emb, pre.pos, (const void*)pre.tok,
+                       (const void*)pre.step, dn, st, out, pre.x_out);
+  else if (pre.n_slab == 0) TTASR_LN_ROWS(0);
+  else if (pre.n_slab <= 2) TTASR_LN_ROWS(2);
+  else if (pre.n_slab <= 4) TTASR_LN_ROWS(4);
+  else if (pre.n_slab <= 8) TTASR_LN_ROWS(8);
+  else TTASR_LN_ROWS(16);
+#undef TTASR_LN_ROWS
 }
 // the session's first decoder LayerNorm: embedding form with per-row positions (pre.tok and pre.step = row positions [rows])
 template <typename T>
 void launch_layernorm_rows_embed_pos(const float* gamma, const float* beta, T* out, int rows, int d, const LnPre& pre, hipStream_t s) {
-  if (d > 1280 || (d & 3)) { launch_fault("layernorm_rows needs d <= 1280, d %% 4 == 0 (got %d)", d); return; }
+  unsigned dn, st;
+  if (!ln_rows_words(d, pre, dn, st)) return;
   if (!pre.tok || !pre.step) { launch_fault("layernorm_rows_embed_pos needs tokens and row positions"); return; }
-  hipLaunchKernelGGL((layernorm_rows_kernel<T, LN_ROW_POS, true>), dim3(rows), dim3(320), 0, s, nullptr, gamma, beta, out, d, pre);
+  hipLaunchKernelGGL((layernorm_rows_kernel<T, LN_ROW_POS, true>), dim3(rows), dim3(320), 0, s, gamma, beta, pre.emb, pre.pos,
+                     (const void*)pre.tok, (const void*)pre.step, dn, st, out, pre.x_out);
 }
 template void launch_layernorm_rows_embed_pos<float>(const float*, const float*, float*, int, int, const LnPre&, hipStream_t);
 template void launch_layernorm_rows_embed_pos<bf16_t>(const float*, const float*, bf16_t*, int, int, const LnPre&, hipStream_t);

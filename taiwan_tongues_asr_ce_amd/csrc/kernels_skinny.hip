@@ -100,10 +100,17 @@ static void skinny_allow_big_lds() {
 // ONE = the wave's k-steps fit one batch of loads (steps <= U): straight-line code.  (As a loop, the register reuse of
 // the next iteration forces an early s_waitcnt that, in the first iteration, waits for the bias / residual prefetch
 // before the bulk of the weight loads is even issued: one more serialised round trip.)
+// Argument order (see common.hpp sgpr_pin): everything the first load batch needs - the weight stream, the activation tile and
+// the bias / residual prefetch - leads the list as pointers and ints, so it arrives PRELOADED in SGPRs (13 dwords of the 14 the
+// compiler preloads) and the first address is formed without a kernarg fetch.  pk_ = B | ksplit << 8 | rpb << 16 | x_lds << 24 |
+// act << 25 (B <= 128, ksplit <= 16, rpb 20 / 32: the launcher's own limits).  The tail - the three output pointers and the slab
+// stride, which only the stores at the end use - is fetched by pin_tail() AFTER the first batch has been issued, under the
+// vector loads.  The encoder's GemmEpi does not travel: rowtab / headsplit are refused by the launcher, the rest is flat here.
 template <typename T16, int NW, int RB, int U, bool NT, bool ONE>
 __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const bf16_t* __restrict__ Wsh_, const bf16_t* __restrict__ x_,
-                                                              int B_, int N_, int K_, int ksplit_, int steps_, GemmEpi e,
-                                                              float* __restrict__ slab_, int64_t slab_stride_, int rpb_) {
+                                                              const float* bias_, const float* residual_, unsigned pk_, int N_, int K_,
+                                                              int steps_, int ldc_, float* out_f32_, void* out_t_,
+                                                              float* __restrict__ slab_, int64_t slab_stride_) {
   // U = k-steps in flight per wave (register budget: U * (1 + RB) * 4); the launcher picks the smallest instantiated
   // U >= steps so that no load is issued twice
   // dynamic LDS: the reduction buffer red[wave][row group][b*32 + n] (NW * RB * 4 KiB) and - aliased with it, separated by a
@@ -112,15 +119,20 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const bf16_t* __re
   float (*red)[RB][32 * 32] = (float (*)[RB][32 * 32])smem;
   const bf16_t* Wsh = sgpr_pin_ptr(Wsh_);
   const bf16_t* x = sgpr_pin_ptr(x_);
-  const int B = sgpr_pin(B_), N = sgpr_pin(N_), K = sgpr_pin(K_), ksplit = sgpr_pin(ksplit_);
-  const int rpb = sgpr_pin(rpb_ & 255);      // rows per n-block of the packed matrix (32 or 20: skinny_rows_per_block)
-  const int xl = sgpr_pin(rpb_ >> 8);        // 1: activation tile through LDS (launcher: skinny_x_lds)
+  const unsigned pk = sgpr_pin(pk_);
+  const int B = pk & 255, ksplit = (pk >> 8) & 255, N = sgpr_pin(N_), K = sgpr_pin(K_);
+  const int rpb = (pk >> 16) & 255;          // rows per n-block of the packed matrix (32 or 20: skinny_rows_per_block)
+  const int xl = (pk >> 24) & 1;             // 1: activation tile through LDS (launcher: skinny_x_lds)
   const int steps = sgpr_pin(steps_);  // k-steps per wave = K / 16 / (NW * ksplit), divided on the host: an integer division here is
                                        // ~40 dependent instructions in front of the first load
-  float* slab = sgpr_pin_ptr(slab_);
-  const int64_t slab_stride = sgpr_pin(slab_stride_);
-  e.bias = sgpr_pin_ptr(e.bias); e.residual = sgpr_pin_ptr(e.residual); e.out_f32 = sgpr_pin_ptr(e.out_f32);
-  e.out_t = sgpr_pin_ptr(e.out_t); e.ldc = sgpr_pin(e.ldc); e.act = sgpr_pin(e.act);
+  struct { const float* bias; const float* residual; float* out_f32; void* out_t; int64_t ldc; int act; } e;
+  e.bias = sgpr_pin_ptr(bias_); e.residual = sgpr_pin_ptr(residual_); e.ldc = sgpr_pin(ldc_); e.act = (pk >> 25) & 1;
+  float* slab;
+  int64_t slab_stride;
+  auto pin_tail = [&]() {   // second stage: issued behind the first load batch, waited for here while those loads fly
+    e.out_f32 = sgpr_pin_ptr(out_f32_); e.out_t = sgpr_pin_ptr(out_t_);
+    slab = sgpr_pin_ptr(slab_); slab_stride = sgpr_pin(slab_stride_);
+  };
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nb = blockIdx.x, ks = blockIdx.y;
   const int ks_per = K / 16;
@@ -180,6 +192,8 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const bf16_t* __re
       if constexpr (NT) w[u] = __builtin_nontemporal_load(wp + (int64_t)i * wstep); else w[u] = wp[(int64_t)i * wstep];
     }
     __builtin_amdgcn_sched_barrier(0);
+    pin_tail();
+    __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_waitcnt vmcnt(%0)" :: "n"(U) : "memory");   // tile pieces (and epilogue operands) landed; the U weight loads fly on
 #pragma unroll
     for (int g = 0; g < RB; ++g)
@@ -223,6 +237,8 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const bf16_t* __re
       for (int u = 0; u < U; ++u) xv[g][u] = *(const u32x4*)(xp[g] + min(u, steps - 1) * 16);
     prefetch_epilogue();
     __builtin_amdgcn_sched_barrier(0);  // every load is issued before the first MFMA waits: one round trip
+    pin_tail();
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int u = 0; u < U; ++u)
       if (u < steps) {
@@ -232,6 +248,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const bf16_t* __re
       }
   } else {
     prefetch_epilogue();
+    pin_tail();
     for (int i0 = 0; i0 < steps; i0 += U) {
       u32x4 w[U], xv[RB][U];
 #pragma unroll
@@ -484,6 +501,7 @@ bool launch_gemm_skinny(const T16* Wsh_, const T16* x_, int B, int N, int K, con
   const bf16_t* Wsh = (const bf16_t*)Wsh_;   // raw 16-bit words: the kernel only moves them; T16 picks the MFMA form
   const bf16_t* x = (const bf16_t*)x_;
   if (B < 1 || B > 128 || K % 64 != 0 || e.rowtab || e.headsplit) return false;
+  if (e.ldc < 0 || e.ldc > INT32_MAX || ksplit > 16 || (e.act != 0 && e.act != 1)) return false;   // what the kernel's argument words hold
   const int rb = (B + 31) / 32;  // 32-row groups sharing one weight stream
   const int rpb = skinny_rows_per_block(N, K, ko);
   const int n_blocks = (N + rpb - 1) / rpb;
@@ -505,13 +523,13 @@ bool launch_gemm_skinny(const T16* Wsh_, const T16* x_, int B, int N, int K, con
   do {                                                                                                                                \
     const bool xl_ = ko.skinny_x_lds && ONE_ && (NW_ == 4 || (NW_ == 8 && RB_ == 1));                                                  \
     const size_t lds_ = skinny_lds_bytes(NW_, RB_, steps, xl_);                                                                       \
-    const int rpbx_ = rpb | (xl_ ? 256 : 0);                                                                                          \
+    const unsigned pk_ = (unsigned)B | (unsigned)ksplit << 8 | (unsigned)rpb << 16 | (xl_ ? 1u << 24 : 0u) | (unsigned)e.act << 25; \
     if (ko.skinny_nt) {                                                                                                                \
       if (lds_ > 65536) skinny_allow_big_lds<gemm_skinny_kernel<T16, NW_, RB_, U_, true, ONE_>>();                                     \
-      hipLaunchKernelGGL((gemm_skinny_kernel<T16, NW_, RB_, U_, true, ONE_>), grid, dim3(NW_ * 64), lds_, s, Wsh, x, B, N, K, ksplit, steps, e, slab, slab_stride, rpbx_); \
+      hipLaunchKernelGGL((gemm_skinny_kernel<T16, NW_, RB_, U_, true, ONE_>), grid, dim3(NW_ * 64), lds_, s, Wsh, x, e.bias, e.residual, pk_, N, K, steps, (int)e.ldc, e.out_f32, e.out_t, slab, slab_stride); \
     } else {                                                                                                                          \
       if (lds_ > 65536) skinny_allow_big_lds<gemm_skinny_kernel<T16, NW_, RB_, U_, false, ONE_>>();                                    \
-      hipLaunchKernelGGL((gemm_skinny_kernel<T16, NW_, RB_, U_, false, ONE_>), grid, dim3(NW_ * 64), lds_, s, Wsh, x, B, N, K, ksplit, steps, e, slab, slab_stride, rpbx_); \
+      hipLaunchKernelGGL((gemm_skinny_kernel<T16, NW_, RB_, U_, false, ONE_>), grid, dim3(NW_ * 64), lds_, s, Wsh, x, e.bias, e.residual, pk_, N, K, steps, (int)e.ldc, e.out_f32, e.out_t, slab, slab_stride); \
     }                                                                                                                                 \
   } while (0)
 #define TTASR_SKINNY_U(NW_, RB_, UMAX_)                                            \
