@@ -513,6 +513,50 @@ TTASR_API int ttasr_vad_finalize(ttasr_ctx* ctx);
 TTASR_API int ttasr_vad_probs(ttasr_ctx* ctx, int32_t n, const float* const* pcm_host, const int64_t* n_samples,
                               float* const* out_probs_host, float* const* out_logits_host);
 
+/* ---- file ingest: raw samples of a file -> float32 mono 16 kHz (what librosa.load(..., sr=16000) does in front of every file
+ * entry point of the reference: asr_core.py:156, file_asr.py:271,455; faster-whisper's decode_audio) -------------------------- */
+/* The resampler is scipy.signal.resample_poly with its defaults, written out.  For a recording of n_frames frames at `rate`:
+ *   g = gcd(rate, 16000), up = 16000 / g, down = rate / g, R = max(up, down), half = 10 R, N = 2 half + 1;
+ *   h[m] = up w[m] / sum(w), w[m] = (1 / R) sinc((m - half) / R) kaiser(N, beta = 5)(m), m = 0 .. N - 1, designed in double (the
+ *     Kaiser window's I0 by its power series) and rounded to float32;
+ *   mono[i] = the mean over the channels of frame i's samples scaled to [-1, 1): u8 (v - 128) / 128, s16 / 32768, packed s24
+ *     / 8388608, s32 / 2147483648 (rounded to float32 first), f32 as is, f64 rounded to float32; channels summed in order, then
+ *     one division;
+ *   n_out = ceil(n_frames up / down);
+ *   y[k] = sum_i mono[i] h[k down + half - i up] over the i in [0, n_frames) whose tap index lies in [0, 2 half] (zeros outside
+ *     the recording), accumulated in float32 with i ascending.
+ * Accepted rates: every rate with R <= 1024 (8000, 11025, 12000, 22050, 24000, 32000, 44100, 48000, 88200, 96000, 176400, 192000
+ * among them).  At rate 16000 there is no filter: y = mono, bit for bit what the host conversion gives.
+ *
+ * ttasr_ingest_len: n_out of a recording; negative when the rate is not accepted (or n_frames is outside [0, 2^40]).  No context.
+ * ttasr_ingest_filter: the float32 taps h[0 .. N) of `rate` - min(cap, N) of them are written when out != NULL - and returns N
+ *   (0 at rate 16000: no filter; negative: rate not accepted).  No context, no GPU: the known-answer hook of the design.
+ * ttasr_ingest_pcm: n recordings in one call, recording i = n_frames[i] interleaved frames of channels[i] (1 ... 8) samples in
+ *   format[i] (TTASR_PCM_*, little endian) at raw_host[i] (any alignment); out_pcm_host[i] receives ttasr_ingest_len(rate[i],
+ *   n_frames[i]) floats.  Rates and formats may differ inside a call, n is not limited by max_batch, and no model weights are
+ *   needed.  A recording of 0 frames is legal and writes nothing (its pointers may be NULL).  Refused with TTASR_E_INVALID before
+ *   anything is enqueued, the context stays usable: a rate that is not accepted; a channel count outside [1, 8]; an unknown
+ *   format; a negative frame count; a NULL array; a NULL sample or output row with frames; an open session; a call already in
+ *   flight on the context.
+ *   One 256-thread workgroup computes a tile of consecutive outputs of one recording from an input span it stages in LDS (the
+ *   samples are converted and downmixed on the way in); there are no atomics and an output's operands and their order depend on
+ *   its index only.  Recordings go through the device in chunks of input frames - option "ingest_chunk", 0 = as many as the slots
+ *   hold - each uploaded with the filter's halo on both sides through 4 pinned slots of 8 MiB (results: 4 x 4 MiB; the same again
+ *   in device memory; allocated by the first call, freed by ttasr_destroy).  A recording's values do not depend, bit for bit, on
+ *   the chunk size, on the other recordings of the call or on its place in it.  The tap table of a rate (at most 84 KiB) is built
+ *   by the first call that brings the rate and kept by the context.
+ *   The call touches no mel, encoder, search or graph state. */
+#define TTASR_PCM_U8 0
+#define TTASR_PCM_S16 1
+#define TTASR_PCM_S24 2   /* packed: 3 bytes per sample */
+#define TTASR_PCM_S32 3
+#define TTASR_PCM_F32 4
+#define TTASR_PCM_F64 5
+TTASR_API int64_t ttasr_ingest_len(int32_t rate, int64_t n_frames);
+TTASR_API int32_t ttasr_ingest_filter(int32_t rate, float* out, int32_t cap);
+TTASR_API int ttasr_ingest_pcm(ttasr_ctx* ctx, int32_t n, const void* const* raw_host, const int64_t* n_frames, const int32_t* rate,
+                               const int32_t* channels, const int32_t* format, float* const* out_pcm_host);
+
 /* ---- kernel-selection overrides (tests, A/B measurements) ----------------------------------------- */
 /* The release library reads NO environment variable; every deviation from the measured configuration is an explicit call.
  * Keys (value 0 / 1 unless stated; defaults in brackets): "flash" [1] MFMA flash attention in the encoder (0: the
@@ -544,12 +588,18 @@ TTASR_API int ttasr_vad_probs(ttasr_ctx* ctx, int32_t n, const float* const* pcm
  * "session_prefill" [0] (0 ... n_text_ctx - 2; read by ttasr_session_begin / ttasr_session_begin_beam) N > 0: a clip with at least
  * N prefillable prompt positions gets them from an admission pass instead of N forced decode steps (see "prompt prefill at
  * admission" above);
- * Drops the captured decode graphs (except "enc_kernel_timing", "refill_overlap" and "session_prefill").  Unknown key or value out of range: TTASR_E_INVALID. */
+ * "ingest_chunk" [0] (0 ... 2^30) input frames per chunk of ttasr_ingest_pcm, 0 = as many as the staging slots hold (results do
+ * not depend on it, bit for bit: tests put chunk boundaries inside small inputs with it); "ingest_timing" [0] 1: ttasr_ingest_pcm
+ * waits for every copy and kernel before it enqueues the next and leaves the host-clock split of the call in ttasr_phase_ms
+ * (measurement only: the waits cost the overlap);
+ * Drops the captured decode graphs (except "enc_kernel_timing", "refill_overlap", "session_prefill", "ingest_chunk" and "ingest_timing").  Unknown key or value out of range: TTASR_E_INVALID. */
 TTASR_API int ttasr_set_option(ttasr_ctx* ctx, const char* key, int32_t value);
 
 /* ---- measurement --------------------------------------------------------------------------------- */
 /* hipEvent times (ms) of the last log_mel / encode (stem+layers, cross-KV) / generate calls:
- * out[0]=mel out[1]=encoder out[2]=cross_kv out[3]=decode. */
+ * out[0]=mel out[1]=encoder out[2]=cross_kv out[3]=decode.  After a ttasr_ingest_pcm under option "ingest_timing" = 1 the four
+ * values are that call's host-clock split instead: out[0]=staging copies on the host (into the pinned slots and out of them)
+ * out[1]=uploads out[2]=kernels out[3]=downloads. */
 TTASR_API int ttasr_phase_ms(ttasr_ctx* ctx, float out_ms[4]);
 /* Host-side split of the LAST beam search on this context (ms): out[0] enqueueing (copies, launches), out[1] waiting for the GPU
  * (the one stream synchronisation per searching position), out[2] candidate selection + page bookkeeping on the host, out[3] =

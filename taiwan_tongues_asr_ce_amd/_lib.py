@@ -20,8 +20,11 @@ SYMBOLS = [
     "ttasr_align_batch", "ttasr_session_hold", "ttasr_session_align", "ttasr_session_release", "ttasr_detect_language",
     "ttasr_session_detect_language", "ttasr_session_poll_lang", "ttasr_session_prefill_stats",
     "ttasr_vad_load_tensor", "ttasr_vad_finalize", "ttasr_vad_probs",
+    "ttasr_ingest_len", "ttasr_ingest_filter", "ttasr_ingest_pcm",
 ]
 
+PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = range(6)   # TTASR_PCM_* of include/ttasr.h
+PCM_BYTES = (1, 2, 3, 4, 4, 8)                                    # bytes per sample, by format code
 VAD_CHUNK_FRAMES = 1024   # TTASR_VAD_CHUNK_FRAMES of include/ttasr.h: frames of one recording per time chunk of ttasr_vad_probs
 
 
@@ -118,9 +121,14 @@ def load() -> C.CDLL:
     lib.ttasr_vad_load_tensor.argtypes = [vp, C.c_char_p, vp, i64p, i32]
     lib.ttasr_vad_finalize.argtypes = [vp]
     lib.ttasr_vad_probs.argtypes = [vp, i32, C.POINTER(vp), i64p, C.POINTER(vp), C.POINTER(vp)]
+    lib.ttasr_ingest_len.argtypes = [i32, i64]
+    lib.ttasr_ingest_len.restype = i64
+    lib.ttasr_ingest_filter.argtypes = [i32, f32p, i32]
+    lib.ttasr_ingest_filter.restype = i32
+    lib.ttasr_ingest_pcm.argtypes = [vp, i32, C.POINTER(vp), i64p, i32p, i32p, i32p, C.POINTER(vp)]
     for s in SYMBOLS:
         f = getattr(lib, s)
-        if s not in ("ttasr_destroy", "ttasr_last_error", "ttasr_version"):
+        if s not in ("ttasr_destroy", "ttasr_last_error", "ttasr_version", "ttasr_ingest_len", "ttasr_ingest_filter"):
             f.restype = C.c_int
     _lib = lib
     return lib

@@ -46,6 +46,9 @@ class MI355XWhisperASR(ASRInterface):
             "word_timestamps": False, "vad_filter": True, "beam_size": 5, "condition_on_previous_text": True,
             "initial_prompt": "繁體中文",
         }
+        # device_resample=True: a PATH handed to the pipeline is converted and resampled on the device (WhisperModel.transcribe);
+        # the streaming chunks of `transcribe` below are 16 kHz PCM already and are not touched by it
+        self.device_resample = bool(kwargs.get("device_resample", False))
         self.text_filter = kwargs.get("text_filter")  # utils.filter_text of the reference, injected by the caller
         # faster_whisper_asr.py:186-198 retries an empty VAD-filtered result without VAD - but it re-opens a temp file it deleted
         # at :179, always lands in its `except: pass` and returns None.  The EFFECTIVE reference behaviour (None for a chunk the
@@ -102,6 +105,13 @@ class MI355XWhisperASR(ASRInterface):
         except Exception as e:  # the reference logs and returns None (faster_whisper_asr.py:260-267)
             logger.error("transcribe failed: %s", e)
             return None
+
+    def transcribe_path(self, path: str, **kw):
+        """A FILE through the adapter's default options (the reference's file service drives the same model object with paths:
+        file_asr.py:457-465) -> (segments, info); with device_resample=True on the adapter the file is ingested on the device."""
+        opts = dict(self.default_transcribe_kwargs, language="zh")
+        opts.update(kw)
+        return self.asr_pipeline.transcribe(path, device_resample=self.device_resample, **opts)
 
     def _vad_is_active(self) -> bool:
         """True when vad_filter=True really filters: the model runs the VAD network on the device, the operator supplied a

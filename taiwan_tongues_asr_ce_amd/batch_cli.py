@@ -57,6 +57,12 @@ def _load_audio(path: str):
     return decode_audio(path)
 
 
+def _probe(path: str) -> str:
+    """The path itself, once the file has been opened: a missing or unreadable file is that file's error, not its group's."""
+    with open(path, "rb"):
+        return path
+
+
 def transcribe_file(model, audio_file: str, load_audio: Callable = _load_audio, log: Callable = print, segments=None,
                     language: Optional[str] = TRANSCRIBE_KWARGS["language"], info=None) -> Dict:
     """One unit of work → one entry of `detailed_results`.  `segments`: already transcribed (group mode, with its `info`), else
@@ -124,8 +130,12 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
                          world: int = 1, load_audio: Callable = _load_audio, log: Callable = print,
                          group_files: int = 0, pipeline_depth: int = 0, continuous: bool = False,
                          cross_kv_fp8: bool = False, language: Optional[str] = TRANSCRIBE_KWARGS["language"],
-                         detect_in_session: bool = False, session_prefill: int = 0, vad_model=None) -> Optional[Dict]:
-    """vad_model (`--vad-model PATH`): the Silero-v5 VAD network for the device (WhisperModel(vad_model=...)); with it the folder
+                         detect_in_session: bool = False, session_prefill: int = 0, vad_model=None,
+                         device_resample: bool = False) -> Optional[Dict]:
+    """device_resample (`--device-resample`): the grouped paths hand every group's files to the model as paths and the model
+    converts, downmixes and resamples them in one device call per group (WhisperModel.transcribe_many(device_resample=True))
+    instead of `load_audio` file by file on this thread; the one-by-one path keeps `load_audio`.
+    vad_model (`--vad-model PATH`): the Silero-v5 VAD network for the device (WhisperModel(vad_model=...)); with it the folder
     keeps its lock-step / continuous / pipelined path and every group is filtered in one device call (vad_filter=True).  A
     Python vad_speech_prob_fn on the model still means file by file.
     language: the forced language of every file (the reference's "zh"), or None = detect each file's language (`--language
@@ -170,6 +180,8 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
                 kw["detect_in_session"] = True
             if session_prefill:
                 kw["session_prefill"] = int(session_prefill)
+        if device_resample:
+            kw["device_resample"] = True
         depth0 = max(1, int(pipeline_depth or getattr(model, "pipeline_depth", 1)))
         if group_files <= 0 and depth0 > 1 and len(mine) < group * depth0:
             group = max(1, -(-len(mine) // depth0))            # few files: one group per context rather than one big group and an idle lane
@@ -189,7 +201,7 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
                 audios, loaded = [], []
                 for f in part:
                     try:
-                        audios.append(load_audio(f))
+                        audios.append(_probe(f) if device_resample else load_audio(f))
                         loaded.append(None)
                     except Exception as e:
                         loaded.append(e)
@@ -267,6 +279,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="opt-in, with --continuous: a window whose prompt has at least N prefillable positions (previous text up to "
                          "<|startoftranscript|>) gets them from one admission pass of the session instead of N forced decode steps; "
                          "0 = off")
+    ap.add_argument("--device-resample", action="store_true",
+                    help="opt-in: convert, downmix and resample each group's files in one device call instead of file by file on "
+                         "the host (RIFF/WAVE of any PCM / float format, other containers through soundfile; rates the device "
+                         "does not take fall back to the host path per file)")
     return ap
 
 
@@ -287,7 +303,7 @@ def main(argv=None) -> int:
                          max_batch=args.max_batch, pipeline_depth=args.pipeline_depth, continuous=args.continuous,
                          cross_kv_fp8=args.xkv_fp8, language=None if args.language == "auto" else args.language,
                          detect_in_session=args.detect_in_session, session_prefill=args.session_prefill,
-                         vad_model=args.vad_model)
+                         vad_model=args.vad_model, device_resample=args.device_resample)
     return 0
 
 

@@ -42,6 +42,7 @@ struct Slot {              // where one named tensor lands on the device
 
 struct Session;            // continuous-batching session state (engine_refill.hip)
 struct VadState;           // voice-activity network: weights, scratch and staging of one context (engine_vad.hip)
+struct IngestState;        // file ingest: tap tables per rate and the chunk slots of one context (engine_ingest.hip)
 // What run_decode_rows reads about the rows of a step, and (with the batch, the mode and the e4m3 state) what a captured step
 // graph is keyed on.  Installed and restored by SearchScope only.
 struct StepShape {
@@ -180,6 +181,11 @@ struct ttasr_ctx {
   // voice-activity network (engine_vad.hip): created by the first ttasr_vad_load_tensor, freed by ttasr_destroy; per context,
   // outside the weight-share bookkeeping
   ttasr_detail::VadState* vad = nullptr;
+  // file ingest (engine_ingest.hip): created by the first ttasr_ingest_pcm, freed by ttasr_destroy.  Options: ingest_chunk = input
+  // frames per chunk (0: what the slots hold), ingest_timing = 1: the chunks run one after the other and the call leaves its
+  // host-clock phase split in phase_ms
+  ttasr_detail::IngestState* ingest = nullptr;
+  int ingest_chunk = 0; bool ingest_timing = false;
 
   int B_mel = 0, B_enc = 0, B_dec = 0;
   std::atomic_flag busy = ATOMIC_FLAG_INIT;  // one call in flight per context: a second concurrent call is refused
@@ -375,6 +381,9 @@ int align_batch_run(ttasr_ctx* c, const AlignBatch& a, const int32_t* slot /*[n]
 
 // ---- engine_vad.hip: the voice-activity network (ttasr_vad_*) ----
 void vad_free(ttasr_ctx* c);         // ttasr_destroy: the scratch block and the pinned staging (the weights live in the arenas)
+
+// ---- engine_ingest.hip: file ingest (ttasr_ingest_*) ----
+void ingest_free(ttasr_ctx* c);      // ttasr_destroy: the tap tables, the device and pinned chunk slots and their events
 
 // ---- engine_search.hip: rules, options, greedy / sampled / beam search ----
 // The decode shape of ONE search (a static search's call, or a session from begin to end / free): installs the StepShape and the

@@ -1,0 +1,257 @@
+// libttasr: file ingest behind the C ABI (one of the engine translation units, see engine_ctx.hpp): the filter design in double,
+// the per-rate tap tables of a context, its device and pinned chunk slots, and the chunk loop of ttasr_ingest_pcm.  The kernel is
+// kernels_ingest.hip; the result is the text of include/ttasr.h.  Nothing here touches mel, encoder, search or graph state, and
+// no model weights are needed: the call's only shared resource is the context's stream.
+#include "engine_ctx.hpp"
+#include "ingest.hpp"
+
+#include <chrono>
+
+namespace ttasr_detail {
+
+constexpr int kIngestSlots = 4;                       // chunks in flight: staging copy, upload, kernel and download of neighbours overlap
+constexpr size_t kIngestInBytes = (size_t)8 << 20;    // raw bytes of one chunk slot
+constexpr size_t kIngestOutFloats = (size_t)1 << 20;  // results of one chunk slot
+constexpr int64_t kIngestMaxFrames = (int64_t)1 << 40;
+
+static const int kPcmBytes[6] = {1, 2, 3, 4, 4, 8};   // bytes per sample of the formats, in the order of their codes
+
+// What a rate decides: the ratio, the filter and the tile.  ok = false: the rate is not accepted.
+struct IngestPlan {
+  bool ok = false, filter = false;
+  int up = 1, down = 1, half = 0, N = 0, L = 0, tile = kIngestMaxTile, span = kIngestMaxTile;
+};
+
+static int gcd_i(int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; }
+
+static IngestPlan ingest_plan(int32_t rate) {
+  IngestPlan p;
+  if (rate < 1) return p;
+  const int g = gcd_i(rate, 16000);
+  p.up = 16000 / g; p.down = rate / g;
+  const int R = std::max(p.up, p.down);
+  if (R > kIngestMaxR) return p;
+  p.ok = true;
+  if (rate == 16000) return p;   // convert and downmix only
+  p.filter = true;
+  p.half = 10 * R; p.N = 2 * p.half + 1; p.L = (p.N + p.up - 1) / p.up;
+  // the longest tile (a multiple of the workgroup) whose span fits the usual LDS budget; ratios whose shortest such tile does not
+  // fit take the large budget, with as many outputs as fit there
+  p.tile = 0;
+  for (int t = kIngestMaxTile; t >= kIngestThreads && !p.tile; t -= kIngestThreads)
+    if (ingest_span(t, p.up, p.down, p.half) <= kIngestSpan) p.tile = t;
+  if (!p.tile) {
+    p.tile = kIngestThreads;
+    while (p.tile > 1 && ingest_span(p.tile, p.up, p.down, p.half) > kIngestSpanMax) --p.tile;
+  }
+  p.span = (int)ingest_span(p.tile, p.up, p.down, p.half);
+  return p;
+}
+
+static double bessel_i0(double x) {   // power series: sum_k ((x / 2)^k / k!)^2
+  const double q = x * x / 4;
+  double term = 1, sum = 1;
+  for (int k = 1; k < 500 && term > 1e-20 * sum; ++k) { term *= q / ((double)k * k); sum += term; }
+  return sum;
+}
+
+// h[m] = up w[m] / sum(w), w[m] = (1 / R) sinc((m - half) / R) kaiser_{N, 5}(m): scipy's firwin(N, 1 / R, window = ("kaiser", 5)) * up
+static std::vector<double> ingest_design(const IngestPlan& p) {
+  const int R = std::max(p.up, p.down);
+  const double pi = 3.14159265358979323846, beta = 5.0, i0b = bessel_i0(beta);
+  std::vector<double> w(p.N);
+  double sum = 0;
+  for (int m = 0; m < p.N; ++m) {
+    const double x = (double)(m - p.half) / R, r = (double)(m - p.half) / p.half;
+    const double sinc = x == 0 ? 1.0 : std::sin(pi * x) / (pi * x);
+    w[m] = sinc / R * bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - r * r))) / i0b;
+    sum += w[m];
+  }
+  for (double& v : w) v = v * p.up / sum;
+  return w;
+}
+
+struct IngestFilter { IngestPlan plan; float* dev = nullptr; };
+
+struct IngestState {
+  std::map<int32_t, IngestFilter> filters;   // per rate: the phase-major table [up][L] on the device (its own allocation)
+  char* dev = nullptr;                       // [kIngestSlots] raw | [kIngestSlots] results
+  char* pinned = nullptr;                    // the same layout in pinned host memory
+  hipEvent_t done[kIngestSlots] = {};
+};
+
+void ingest_free(ttasr_ctx* c) {
+  if (!c->ingest) return;
+  for (auto& f : c->ingest->filters) if (f.second.dev) hipFree(f.second.dev);
+  if (c->ingest->dev) hipFree(c->ingest->dev);
+  if (c->ingest->pinned) hipHostFree(c->ingest->pinned);
+  for (auto& e : c->ingest->done) if (e) hipEventDestroy(e);
+  delete c->ingest;
+  c->ingest = nullptr;
+}
+
+static int ingest_blocks(ttasr_ctx* c) {
+  IngestState* g = c->ingest;
+  const size_t bytes = kIngestSlots * (kIngestInBytes + kIngestOutFloats * 4);
+  if (!g->dev) {
+    const hipError_t e = hipMalloc((void**)&g->dev, bytes);
+    if (e != hipSuccess) { g->dev = nullptr; (void)hipGetLastError(); return fail(c, TTASR_E_NOMEM, "ingest device slots (%zu bytes): %s", bytes, hipGetErrorString(e)); }
+  }
+  if (!g->pinned) {
+    const hipError_t e = hipHostMalloc((void**)&g->pinned, bytes, hipHostMallocDefault);
+    if (e != hipSuccess) { g->pinned = nullptr; (void)hipGetLastError(); return fail(c, TTASR_E_NOMEM, "ingest pinned staging (%zu bytes): %s", bytes, hipGetErrorString(e)); }
+  }
+  for (auto& e : g->done)
+    if (!e) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  return 0;
+}
+
+// The table of `rate` on the device, designed and uploaded by the first call that brings the rate.
+static int ingest_filter_dev(ttasr_ctx* c, int32_t rate, const IngestFilter** out) {
+  IngestState* g = c->ingest;
+  auto it = g->filters.find(rate);
+  if (it == g->filters.end()) {
+    IngestFilter f; f.plan = ingest_plan(rate);
+    if (f.plan.filter) {
+      const std::vector<double> h = ingest_design(f.plan);
+      std::vector<float> t((size_t)f.plan.up * f.plan.L, 0.0f);
+      for (int m = 0; m < f.plan.N; ++m) t[(size_t)(m % f.plan.up) * f.plan.L + m / f.plan.up] = (float)h[m];
+      const hipError_t e = hipMalloc((void**)&f.dev, t.size() * 4);
+      if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, TTASR_E_NOMEM, "ingest taps of rate %d (%zu bytes): %s", rate, t.size() * 4, hipGetErrorString(e)); }
+      const hipError_t e2 = hipMemcpy(f.dev, t.data(), t.size() * 4, hipMemcpyHostToDevice);   // `t` is a stack temporary
+      if (e2 != hipSuccess) { hipFree(f.dev); return fail(c, TTASR_E_HIP, "ingest taps of rate %d: %s", rate, hipGetErrorString(e2)); }
+    }
+    it = g->filters.emplace(rate, f).first;
+  }
+  *out = &it->second;
+  return 0;
+}
+
+static int64_t ceil_div(int64_t a, int64_t b) { return a >= 0 ? (a + b - 1) / b : -((-a) / b); }   // b > 0
+static int64_t floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+
+struct IngestPending { bool live = false; float* dst = nullptr; size_t n = 0; };
+
+static int ingest_pcm(ttasr_ctx* c, int32_t n, const void* const* raw, const int64_t* n_frames, const int32_t* rate,
+                      const int32_t* channels, const int32_t* format, float* const* out) {
+  if (n < 0) return fail(c, TTASR_E_INVALID, "n %d is negative", n);
+  if (n == 0) return TTASR_OK;
+  if (!raw || !n_frames || !rate || !channels || !format || !out) return fail(c, TTASR_E_INVALID, "NULL argument");
+  for (int i = 0; i < n; ++i) {
+    if (n_frames[i] < 0 || n_frames[i] > kIngestMaxFrames) return fail(c, TTASR_E_INVALID, "recording %d: %lld frames outside [0, 2^40]", i, (long long)n_frames[i]);
+    if (channels[i] < 1 || channels[i] > 8) return fail(c, TTASR_E_INVALID, "recording %d: %d channels outside [1, 8]", i, channels[i]);
+    if (format[i] < TTASR_PCM_U8 || format[i] > TTASR_PCM_F64) return fail(c, TTASR_E_INVALID, "recording %d: unknown sample format %d", i, format[i]);
+    if (!ingest_plan(rate[i]).ok)
+      return fail(c, TTASR_E_INVALID, "recording %d: rate %d is not accepted (max(up, down) of the ratio to 16000 must be at most %d)", i, rate[i], kIngestMaxR);
+    if (n_frames[i] > 0 && (!raw[i] || !out[i])) return fail(c, TTASR_E_INVALID, "recording %d: NULL sample or output row with %lld frames", i, (long long)n_frames[i]);
+  }
+  TRY(session_refusal(c));
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->ingest) c->ingest = new IngestState();
+  IngestState* g = c->ingest;
+  TRY(ingest_blocks(c));
+  hipStream_t s = c->stream;
+  char* const d_in = g->dev; char* const d_out = g->dev + kIngestSlots * kIngestInBytes;
+  char* const p_in = g->pinned; char* const p_out = g->pinned + kIngestSlots * kIngestInBytes;
+  IngestPending pend[kIngestSlots];
+  const bool timing = c->ingest_timing;
+  using clk = std::chrono::steady_clock;
+  double ms[4] = {0, 0, 0, 0};   // staging copies (both directions, host) | upload | kernel | download
+  auto since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
+  auto retire = [&](int slot) -> int {   // the slot's results to the caller's row
+    if (!pend[slot].live) return 0;
+    HIPCHK(c, hipEventSynchronize(g->done[slot]));
+    const auto t0 = clk::now();
+    memcpy(pend[slot].dst, p_out + (size_t)slot * kIngestOutFloats * 4, pend[slot].n * 4);
+    ms[0] += since(t0);
+    pend[slot].live = false;
+    return 0;
+  };
+  int64_t job = 0;
+  for (int i = 0; i < n; ++i) {
+    if (n_frames[i] == 0) continue;
+    const IngestFilter* f = nullptr;
+    TRY(ingest_filter_dev(c, rate[i], &f));
+    const IngestPlan& P = f->plan;
+    const int64_t nfr = n_frames[i], fb = (int64_t)kPcmBytes[format[i]] * channels[i];
+    const int64_t halo = 2 * (int64_t)P.half / P.up + 2;
+    const int64_t n_out = ceil_div(nfr * P.up, P.down);
+    // frames per chunk: what the raw slot holds beside the halo and what the result slot holds, or the option when it is smaller
+    int64_t C = std::min<int64_t>((int64_t)kIngestInBytes / fb - halo, ((int64_t)kIngestOutFloats - 2) * P.down / P.up);
+    if (c->ingest_chunk > 0) C = std::min<int64_t>(C, c->ingest_chunk);
+    if (C < 1) return fail(c, TTASR_E_INVALID, "recording %d: no chunk of rate %d fits the staging slots", i, rate[i]);
+    const int64_t chunks = ceil_div(nfr, C);
+    for (int64_t ch = 0; ch < chunks; ++ch, ++job) {
+      const int64_t kb = std::min(ceil_div(ch * C * P.up, P.down), n_out);
+      const int64_t ke = ch + 1 == chunks ? n_out : std::min(ceil_div((ch + 1) * C * P.up, P.down), n_out);
+      if (ke <= kb) continue;
+      // the frames these outputs read, cut at the ends of the recording
+      const int64_t lo = std::max<int64_t>(ceil_div(kb * P.down - P.half, P.up), 0);
+      const int64_t hi = std::min<int64_t>(floor_div((ke - 1) * P.down + P.half, P.up), nfr - 1);
+      const int64_t nf = std::max<int64_t>(hi - lo + 1, 0);
+      if (nf * fb > (int64_t)kIngestInBytes || ke - kb > (int64_t)kIngestOutFloats)
+        return fail(c, TTASR_E_INVALID, "recording %d: chunk %lld exceeds its slot (%lld frames, %lld outputs)", i, (long long)ch, (long long)nf, (long long)(ke - kb));
+      const int slot = (int)(job % kIngestSlots);
+      TRY(retire(slot));
+      auto t0 = clk::now();
+      memcpy(p_in + (size_t)slot * kIngestInBytes, (const char*)raw[i] + lo * fb, (size_t)(nf * fb));
+      ms[0] += since(t0);
+      t0 = clk::now();
+      if (nf) HIPCHK(c, hipMemcpyAsync(d_in + (size_t)slot * kIngestInBytes, p_in + (size_t)slot * kIngestInBytes, (size_t)(nf * fb), hipMemcpyHostToDevice, s));
+      if (timing) { HIPCHK(c, hipStreamSynchronize(s)); ms[1] += since(t0); t0 = clk::now(); }
+      IngestJob J;
+      J.raw = (const uint8_t*)(d_in + (size_t)slot * kIngestInBytes);
+      J.out = (float*)(d_out + (size_t)slot * kIngestOutFloats * 4);
+      J.taps = f->dev;
+      J.n_frames = nfr; J.f0 = lo; J.k_begin = kb; J.nf = (int32_t)nf; J.n_out = (int32_t)(ke - kb);
+      J.up = P.up; J.down = P.down; J.half = P.half; J.L = P.L; J.channels = channels[i]; J.format = format[i];
+      J.tile = P.tile; J.span = P.span;
+      launch_ingest(J, s);
+      if (timing) { HIPCHK(c, hipStreamSynchronize(s)); ms[2] += since(t0); t0 = clk::now(); }
+      HIPCHK(c, hipMemcpyAsync(p_out + (size_t)slot * kIngestOutFloats * 4, J.out, (size_t)J.n_out * 4, hipMemcpyDeviceToHost, s));
+      if (timing) { HIPCHK(c, hipStreamSynchronize(s)); ms[3] += since(t0); }
+      HIPCHK(c, hipEventRecord(g->done[slot], s));
+      pend[slot].live = true; pend[slot].dst = out[i] + kb; pend[slot].n = (size_t)J.n_out;
+    }
+  }
+  for (int64_t k = 0; k < kIngestSlots; ++k) TRY(retire((int)((job + k) % kIngestSlots)));   // oldest first
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+  if (timing) for (int k = 0; k < 4; ++k) c->phase_ms[k] = (float)ms[k];
+  return TTASR_OK;
+}
+
+}  // namespace ttasr_detail
+
+extern "C" {
+
+int64_t ttasr_ingest_len(int32_t rate, int64_t n_frames) {
+  const IngestPlan p = ingest_plan(rate);
+  if (!p.ok || n_frames < 0 || n_frames > kIngestMaxFrames) return TTASR_E_INVALID;
+  return (n_frames * p.up + p.down - 1) / p.down;
+}
+
+int32_t ttasr_ingest_filter(int32_t rate, float* out, int32_t cap) {
+  try {
+    const IngestPlan p = ingest_plan(rate);
+    if (!p.ok) return TTASR_E_INVALID;
+    if (!p.filter) return 0;   // 16000: there is no filter
+    if (out && cap > 0) {
+      const std::vector<double> h = ingest_design(p);
+      for (int m = 0; m < std::min(cap, p.N); ++m) out[m] = (float)h[m];
+    }
+    return p.N;
+  } catch (...) {
+    return TTASR_E_NOMEM;
+  }
+}
+
+int ttasr_ingest_pcm(ttasr_ctx* c, int32_t n, const void* const* raw, const int64_t* n_frames, const int32_t* rate,
+                     const int32_t* channels, const int32_t* format, float* const* out_pcm) {
+  return guarded(c, [&]() -> int {
+  if (!c) return TTASR_E_INVALID;
+  return ingest_pcm(c, n, raw, n_frames, rate, channels, format, out_pcm);
+  });
+}
+
+}  // extern "C"

@@ -64,6 +64,12 @@ int set_option(ttasr_ctx* c, const std::string& key, int v) {
     c->session_prefill = v;
     return 0;
   }
+  if (key == "ingest_chunk") {      // host-side chunking of ttasr_ingest_pcm: the graphs stay
+    if (v < 0 || v > 1 << 30) return 1;
+    c->ingest_chunk = v;
+    return 0;
+  }
+  if (key == "ingest_timing") { c->ingest_timing = on; return 0; }   // measurement only
   if (key == "flash") c->no_flash = !on;
   else if (key == "prefill") c->no_prefill = !on;
   else if (key == "vocab_persistent") c->vocab_persistent = on;

@@ -1,0 +1,29 @@
+// File ingest on the device (include/ttasr.h ttasr_ingest_*): what kernels_ingest.hip and engine_ingest.hip share.  The result is
+// defined in the header; DESIGN.md section 4.21 has the kernel's shape and the measurements.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/ttasr.h"
+
+constexpr int kIngestThreads = 256;
+constexpr int kIngestMaxR = 1024;            // accepted ratios: max(up, down) <= 1024
+constexpr int kIngestSpan = 8192;            // floats of LDS a workgroup stages at the usual ratios (32 KiB: four workgroups per CU)
+constexpr int kIngestSpanMax = 36864;        // ... and at ratios whose 256-output tile needs more (144 KiB: one workgroup per CU)
+constexpr int kIngestMaxTile = 4096;         // outputs per workgroup, at most
+
+// One launch: the outputs [k_begin, k_begin + n_out) of one recording from the frames [f0, f0 + nf) of it that `raw` holds
+// (interleaved, in the file's sample format).  Frames outside [0, n_frames) are zeros; a frame inside the recording but outside
+// the staged range reads as zero as well (the host never asks for one: the guard keeps a wrong host off foreign memory).
+struct IngestJob {
+  const uint8_t* raw;      // device, staged frames
+  float* out;              // device, n_out floats
+  const float* taps;       // device, phase-major [up][L]; nullptr: no filter (rate 16000), out[k] = mono[k]
+  int64_t n_frames, f0, k_begin;
+  int32_t nf, n_out, up, down, half, L, channels, format, tile, span;
+};
+
+// Staged floats a tile of `tile` outputs reads: floor(tile * down / up) + floor(2 * half / up) + 2.
+inline int64_t ingest_span(int64_t tile, int up, int down, int half) { return tile * down / up + 2 * (int64_t)half / up + 2; }
+
+void launch_ingest(const IngestJob& j, hipStream_t s);

@@ -143,6 +143,41 @@ class Engine:
             self._check(self.lib.ttasr_vad_probs(self.h, n, ptrs, ns.ctypes.data_as(C.POINTER(C.c_int64)), outs, louts), "vad_probs")
         return (probs, logits) if return_logits else probs
 
+    # -- file ingest -----------------------------------------------------------------------------
+    def ingest(self, raws: Sequence, rates: Sequence[int], channels: Sequence[int], formats: Sequence[int]) -> List[np.ndarray]:
+        """Raw interleaved samples of n recordings -> float32 mono 16 kHz, in ONE device call (ttasr_ingest_pcm): raws[i] is a
+        bytes-like object or a C-contiguous array holding whole frames of channels[i] samples in formats[i] (_lib.PCM_*) at
+        rates[i] Hz.  Rates and formats may differ; n is not limited by max_batch; no weights are needed.  A rate the device does
+        not take (see `ingest_accepts`) raises TtasrError: the caller converts that file on the host."""
+        n = len(raws)
+        if not (len(rates) == len(channels) == len(formats) == n):
+            raise ValueError("raws, rates, channels and formats must have one entry per recording")
+        bufs, frames = [], np.zeros(max(n, 1), dtype=np.int64)
+        for i, r in enumerate(raws):
+            b = np.frombuffer(r, dtype=np.uint8) if isinstance(r, (bytes, bytearray, memoryview)) else np.ascontiguousarray(r).reshape(-1).view(np.uint8)
+            ch, fmt = int(channels[i]), int(formats[i])
+            fb = _lib.PCM_BYTES[fmt] * ch if 0 <= fmt < len(_lib.PCM_BYTES) and ch > 0 else 0
+            if fb and len(b) % fb:
+                raise ValueError(f"recording {i}: {len(b)} bytes are no whole number of {fb}-byte frames")
+            frames[i] = len(b) // fb if fb else len(b)   # bad channels / format: the library refuses the call with a message
+            bufs.append(b)
+        rate = np.asarray(list(rates) or [0], dtype=np.int32)
+        chan = np.asarray(list(channels) or [0], dtype=np.int32)
+        fmts = np.asarray(list(formats) or [0], dtype=np.int32)
+        outs = [np.zeros(max(int(self.lib.ttasr_ingest_len(int(rate[i]), int(frames[i]))), 0), dtype=np.float32) for i in range(n)]
+        if n == 0:
+            return outs
+        ptrs = (C.c_void_p * n)(*[b.ctypes.data if len(b) else None for b in bufs])
+        optr = (C.c_void_p * n)(*[o.ctypes.data if len(o) else None for o in outs])
+        i32p = C.POINTER(C.c_int32)
+        self._check(self.lib.ttasr_ingest_pcm(self.h, n, ptrs, frames.ctypes.data_as(C.POINTER(C.c_int64)), rate.ctypes.data_as(i32p),
+                                              chan.ctypes.data_as(i32p), fmts.ctypes.data_as(i32p), optr), "ingest_pcm")
+        return outs
+
+    def ingest_accepts(self, rate: int) -> bool:
+        """Whether ttasr_ingest_pcm takes recordings at `rate` (max(up, down) of the ratio to 16 kHz at most 1024)."""
+        return self.lib.ttasr_ingest_len(int(rate), 0) >= 0
+
     # -- a5 ------------------------------------------------------------------------------------
     def set_audio_ctx(self, n_ctx: int = 0):
         """Opt-in short window (ttasr_set_audio_ctx): the next log_mel/encode/generate use n_ctx encoder positions

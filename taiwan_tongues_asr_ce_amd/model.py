@@ -110,7 +110,6 @@ def _to_mono_16k(x: np.ndarray, sr: int, sampling_rate: int) -> np.ndarray:
 def decode_audio(path: str, sampling_rate: int = SAMPLE_RATE) -> np.ndarray:
     """Path -> mono float32 @16 kHz.  RIFF/WAV PCM through the stdlib; other containers through soundfile / librosa /
     PyAV when the host has one (the reference decodes with librosa / PyAV: asr_core.py:156, faster-whisper decode_audio)."""
-    import wave
     if not path.lower().endswith((".wav", ".wave")):
         # compressed containers (asr_core.py:118 also globs mp3/flac/m4a/aac): use whichever decoder the host has —
         # none is installed in the build image, so these branches are unexercised here and the error below is what
@@ -137,15 +136,7 @@ def decode_audio(path: str, sampling_rate: int = SAMPLE_RATE) -> np.ndarray:
             return (np.concatenate(chunks).astype(np.float32) / 32768.0) if chunks else np.zeros(0, np.float32)
         except ImportError:
             raise RuntimeError(f"{path}: no decoder for this container (install soundfile, librosa or av); RIFF/WAV needs none")
-    is_float = False
-    try:
-        with wave.open(path, "rb") as w:
-            n_ch, width, sr, n = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes()
-            raw = w.readframes(n)
-    except wave.Error:
-        # the stdlib reader only takes format tag 1; IEEE-float files (tag 3: Audacity / DAW exports) and WAVE_FORMAT_EXTENSIBLE
-        # (tag 0xFFFE: multichannel / > 16-bit writers) are plain RIFF all the same
-        n_ch, width, sr, raw, is_float = _read_riff_wave(path)
+    n_ch, width, sr, raw, is_float = _read_wave(path)
     if is_float:
         x = np.frombuffer(raw, dtype="<f4" if width == 4 else "<f8").astype(np.float32)
     elif width == 2:
@@ -167,6 +158,40 @@ def decode_audio(path: str, sampling_rate: int = SAMPLE_RATE) -> np.ndarray:
         g = gcd(sr, sampling_rate)
         x = resample_poly(x, sampling_rate // g, sr // g).astype(np.float32)
     return np.ascontiguousarray(x, dtype=np.float32)
+
+
+def _read_wave(path: str):
+    """(channels, bytes per sample, rate, data bytes, is_float) of a .wav file: the stdlib reader, or _read_riff_wave for what it
+    does not take."""
+    import wave
+    try:
+        with wave.open(path, "rb") as w:
+            n_ch, width, sr, n = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes()
+            return n_ch, width, sr, w.readframes(n), False
+    except wave.Error:
+        # the stdlib reader only takes format tag 1; IEEE-float files (tag 3: Audacity / DAW exports) and WAVE_FORMAT_EXTENSIBLE
+        # (tag 0xFFFE: multichannel / > 16-bit writers) are plain RIFF all the same
+        return _read_riff_wave(path)
+
+
+def read_audio_raw(path: str):
+    """Path -> (samples, rate, channels, format) for the device ingest (Engine.ingest), or None when this file has to go through
+    decode_audio.  RIFF/WAVE: the data bytes untouched, format = the _lib.PCM_* code of the file's samples.  Other containers:
+    through soundfile when it imports, at the file's own rate, as a float32 array [frames][channels] (format PCM_F32)."""
+    from . import _lib
+    if path.lower().endswith((".wav", ".wave")):
+        n_ch, width, sr, raw, is_float = _read_wave(path)
+        fmt = ({4: _lib.PCM_F32, 8: _lib.PCM_F64} if is_float else
+               {1: _lib.PCM_U8, 2: _lib.PCM_S16, 3: _lib.PCM_S24, 4: _lib.PCM_S32}).get(width)
+        if fmt is None:
+            return None
+        return raw[:len(raw) - len(raw) % (width * n_ch)], sr, n_ch, fmt
+    try:
+        import soundfile as sf  # type: ignore
+        x, sr = sf.read(path, dtype="float32", always_2d=True)
+    except Exception:    # no soundfile, or a container libsndfile does not take: decode_audio tries the other decoders
+        return None
+    return np.ascontiguousarray(x), int(sr), int(x.shape[1]), _lib.PCM_F32
 
 
 def _read_riff_wave(path: str):
@@ -387,6 +412,31 @@ class WhisperModel:
                       "vad_speech_prob_fn was given; the whole clip is treated as speech", stacklevel=stacklevel)
         return "none", None
 
+    # -- file ingest on the device --------------------------------------------------------------------
+    def decode_audio_many(self, paths_or_arrays: Sequence[Union[str, np.ndarray]]) -> List[np.ndarray]:
+        """Every path -> mono float32 @16 kHz with ONE device call for all the files the device takes (read_audio_raw +
+        Engine.ingest on the calling thread's engine context: conversion, downmix and the polyphase resampler run as one kernel
+        over the whole batch); a file it does not take - a container without a reader, a rate outside the accepted ratios, more
+        than 8 channels - goes through decode_audio, as every path does on an engine without `ingest`.  Arrays pass through.
+        The device resampler is decode_audio's (scipy.signal.resample_poly) accumulated in float32 instead of float64."""
+        eng = self.engine
+        out: List[Optional[np.ndarray]] = [None] * len(paths_or_arrays)
+        jobs = []
+        for i, a in enumerate(paths_or_arrays):
+            if not isinstance(a, str):
+                out[i] = np.asarray(a)
+                continue
+            raw = read_audio_raw(a) if callable(getattr(eng, "ingest", None)) else None
+            if raw is not None and 1 <= raw[2] <= 8 and eng.ingest_accepts(raw[1]):
+                jobs.append((i, raw))
+            else:
+                out[i] = decode_audio(a)
+        if jobs:
+            got = eng.ingest([r[0] for _, r in jobs], [r[1] for _, r in jobs], [r[2] for _, r in jobs], [r[3] for _, r in jobs])
+            for (i, _), y in zip(jobs, got):
+                out[i] = y
+        return out
+
     def transcribe_groups(self, groups: Sequence[Sequence[Union[str, np.ndarray]]], pipeline_depth: Optional[int] = None, **kw
                           ) -> List[List[Tuple[List[Segment], TranscriptionInfo]]]:
         """`transcribe_many(group, **kw)` for every group of files, with up to `pipeline_depth` groups in flight: each worker
@@ -394,7 +444,8 @@ class WhisperModel:
         group's log-mel / encoder pass runs under another's decode chain - on one batch the decode phase leaves most of the
         chip idle between its ~45 000 dependent launches (measured +27 % audio-s/s with two contexts).
         Every group is processed exactly as a serial transcribe_many call would process it (same grouping, same engine
-        inputs): the results are identical, file by file, to pipeline_depth = 1; returned in group order."""
+        inputs): the results are identical, file by file, to pipeline_depth = 1; returned in group order.
+        device_resample=True (one of **kw): each worker ingests its group's paths on its own engine context."""
         depth = max(1, min(int(pipeline_depth or self.pipeline_depth), len(groups) or 1, 4))
         if depth == 1:
             return [self.transcribe_many(g, **kw) for g in groups]
@@ -574,9 +625,12 @@ class WhisperModel:
                    max_initial_timestamp: float = 1.0, suppress_blank: bool = True,
                    temperature: Union[float, Sequence[float]] = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0), best_of: int = 5,
                    compression_ratio_threshold: Optional[float] = 2.4, multilingual: bool = False,
-                   language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1, **kwargs
+                   language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1,
+                   device_resample: bool = False, **kwargs
                    ) -> Tuple[Iterator[Segment], TranscriptionInfo]:
-        """language=None: the language is detected from the first `language_detection_segments` 30-s windows (select_language:
+        """device_resample=True (path input only): the file is converted, downmixed and resampled on the device
+        (decode_audio_many) instead of on the host.
+        language=None: the language is detected from the first `language_detection_segments` 30-s windows (select_language:
         the first window whose top probability exceeds `language_detection_threshold`, else the majority).  multilingual=True:
         every window is detected again between its encoder pass and its search, and its prompt carries that window's language
         token (code-switched speech); info.language stays the file-level answer."""
@@ -595,7 +649,7 @@ class WhisperModel:
             if v is not None and v != neutral[k]:
                 warnings.warn(f"transcribe(): option {k}={v!r} is not implemented in this build and is ignored", stacklevel=2)
         if isinstance(audio, str):
-            audio = decode_audio(audio)
+            audio = self.decode_audio_many([audio])[0] if device_resample else decode_audio(audio)
         audio = np.asarray(audio)
         if audio.ndim != 1:
             # asr_core.py:156 loads with mono=False; faster-whisper rejects 2-D input the same way
@@ -847,7 +901,7 @@ class WhisperModel:
                         best_of: int = 5, compression_ratio_threshold: Optional[float] = 2.4, patience: float = 1.0,
                         hotwords: Optional[str] = None, prefix: Optional[str] = None, continuous: bool = False,
                         multilingual: bool = False, detect_in_session: bool = False, session_prefill: Union[int, bool] = 0,
-                        vad_filter: bool = False, vad_parameters: Optional[dict] = None
+                        vad_filter: bool = False, vad_parameters: Optional[dict] = None, device_resample: bool = False
                         ) -> List[Tuple[List[Segment], TranscriptionInfo]]:
         """Several FILES in lock step: every round takes the next 30-s window of each unfinished file and runs them as
         ONE engine pass (log-mel, encoder, beam search with one previous-text prompt per file), so a folder is
@@ -882,7 +936,10 @@ class WhisperModel:
         session begins), else the model's vad_speech_prob_fn, the vad_parameters={"backend": "energy"} opt-in or the warning of
         `transcribe`.  Each file decodes the concatenation of its speech chunks; its segments are mapped back to the original
         time line and its info carries duration / duration_after_vad as `transcribe` fills them.  A file the VAD empties yields no
-        segments and takes no decode row."""
+        segments and takes no decode row.
+        device_resample=True: the paths among `audios` are converted, downmixed and resampled in ONE device call for the group
+        (decode_audio_many) before the VAD and before a session begins, instead of file by file on the calling thread; an engine
+        without `ingest` ignores the flag."""
         from .engine import session_prefill_value
         eng = self.engine
         session_prefill = session_prefill_value(session_prefill)
@@ -905,7 +962,7 @@ class WhisperModel:
         if continuous:
             p["beam_size"] = int(beam_size)
         pcm = []
-        for a in audios:
+        for a in (self.decode_audio_many(audios) if device_resample else audios):
             a = decode_audio(a) if isinstance(a, str) else np.asarray(a)
             if a.ndim != 1:
                 raise ValueError(f"audio must be mono float32 [n] @16 kHz, got shape {a.shape}")

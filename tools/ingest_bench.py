@@ -1,0 +1,101 @@
+"""File ingest: the host path of model.decode_audio against one Engine.ingest call (kernels_ingest.hip), on 32 in-memory
+recordings of 60 s at 44.1 and 48 kHz, 2-channel int16 and mono int16.
+
+  host     decode_audio's conversion path on the sample bytes, one thread, file by file: int16 -> float32 / 32768, the channel
+           mean, scipy.signal.resample_poly, float32.  One pass over the 32 recordings after a warm-up on the first; the time is
+           the sum.
+  device   ONE Engine.ingest call over the 32 recordings, host bytes in to host float32 out (the call ends in a stream
+           synchronise): 2 warm-up calls, median / min / max of --repeats calls.
+  phases   one more call under option ingest_timing = 1, which waits after every copy and kernel and reports the host-clock sums:
+           staging copies on the host (into the pinned slots and out of them), uploads, kernels, downloads.  The waits cost the
+           overlap the timed calls have, so the four do not add up to the device figure.
+Nothing is asserted.  One JSON object on stdout and in --out.
+
+    python tools/ingest_bench.py [--files 32] [--seconds 60] [--repeats 5] [--out profiles/ingest_bench.json]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+from math import gcd
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HEADLINE = 2150.0   # audio-s/s of the engine's greedy headline workload (README.md)
+
+
+def host_ingest(raw: np.ndarray, rate: int, channels: int) -> np.ndarray:
+    """model.decode_audio from the sample bytes on, for 16-bit PCM."""
+    from scipy.signal import resample_poly
+    x = np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32768.0
+    if channels > 1:
+        x = x.reshape(-1, channels).mean(axis=1)
+    g = gcd(rate, 16000)
+    x = resample_poly(x, 16000 // g, rate // g).astype(np.float32)
+    return np.ascontiguousarray(x, dtype=np.float32)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--files", type=int, default=32)
+    ap.add_argument("--seconds", type=float, default=60.0)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ingest_bench.json"))
+    args = ap.parse_args()
+    from taiwan_tongues_asr_ce_amd import _lib
+    from taiwan_tongues_asr_ce_amd.config import COMPUTE_F32, PRESETS
+    from taiwan_tongues_asr_ce_amd.engine import Engine
+    eng = Engine(PRESETS["micro"], COMPUTE_F32, 4)       # ingest needs no weights
+    res = {"tool": "tools/ingest_bench.py", "files": args.files, "seconds_per_file": args.seconds, "format": "int16",
+           "headline_greedy_audio_s_per_s": HEADLINE, "workloads": {}}
+    for rate in (44100, 48000):
+        for channels in (2, 1):
+            n = int(args.seconds * rate)
+            rng = np.random.default_rng([0x16E57, rate, channels])
+            raws = [rng.integers(-6000, 6000, size=n * channels, dtype=np.int16) for _ in range(args.files)]
+            audio_s = args.files * n / rate
+            host_ingest(raws[0], rate, channels)
+            t = time.perf_counter()
+            host = [host_ingest(r, rate, channels) for r in raws]
+            host_s = time.perf_counter() - t
+            call = lambda: eng.ingest(raws, [rate] * len(raws), [channels] * len(raws), [_lib.PCM_S16] * len(raws))  # noqa: E731
+            for _ in range(2):
+                dev = call()
+            xs = []
+            for _ in range(args.repeats):
+                t = time.perf_counter()
+                call()
+                xs.append(time.perf_counter() - t)
+            dev_s = statistics.median(xs)
+            eng.set_option("ingest_timing", 1)
+            call()
+            ph = eng.phase_ms()
+            eng.set_option("ingest_timing", 0)
+            diff = max(float(np.abs(d.astype(np.float64) - h).max()) for d, h in zip(dev, host))
+            res["workloads"][f"{rate} Hz x {channels} ch"] = {
+                "audio_s": round(audio_s, 1), "raw_mb": round(sum(r.nbytes for r in raws) / 1e6, 1),
+                "host_s": round(host_s, 4), "host_audio_s_per_s": round(audio_s / host_s, 1),
+                "device_median_s": round(dev_s, 5), "device_min_s": round(min(xs), 5), "device_max_s": round(max(xs), 5),
+                "device_audio_s_per_s": round(audio_s / dev_s, 1), "device_over_host": round(host_s / dev_s, 2),
+                "device_exceeds_headline": bool(audio_s / dev_s > HEADLINE),
+                "phases_serialised_ms": {"staging_copies_host": round(ph["mel"], 2), "h2d": round(ph["encoder"], 2),
+                                         "kernel": round(ph["cross_kv"], 2), "d2h": round(ph["decode"], 2)},
+                "max_abs_diff_device_vs_host": float(f"{diff:.3e}")}
+            del raws, host, dev
+    eng.close()
+    text = json.dumps(res, indent=1)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
