@@ -501,7 +501,7 @@ TTASR_API int ttasr_dtw(const float* cost, int32_t n_rows, int32_t n_cols, int32
  *   bounded pinned buffer chunk by chunk, the LSTM state and the 64-sample context carry across chunks, and every kernel's form
  *   is a function of the frame only - a recording's values do not depend, bit for bit, on its length, on the other recordings of
  *   the call or on its place in it, and the first k values equal those of the recording cut to 512 k samples.
- *   Device scratch: n x (4 (64 + 512 C) + 2048 C + 8 C + 1028) bytes with C = TTASR_VAD_CHUNK_FRAMES (4.01 MiB per recording,
+ *   Device scratch: n x (4 (64 + 512 C) + 2048 C + 8 C + 1032) bytes with C = TTASR_VAD_CHUNK_FRAMES (4.01 MiB per recording,
  *   at most max_batch of them; never a function of the recordings' lengths), ONE block owned by the context: allocated by the
  *   first call, grown when a call brings more recordings, freed by ttasr_destroy; a request that cannot be allocated returns
  *   TTASR_E_NOMEM and leaves the context usable.  The pinned staging block (8 chunk slots of PCM + max_batch rows of results) is
@@ -512,6 +512,50 @@ TTASR_API int ttasr_vad_load_tensor(ttasr_ctx* ctx, const char* name, const floa
 TTASR_API int ttasr_vad_finalize(ttasr_ctx* ctx);
 TTASR_API int ttasr_vad_probs(ttasr_ctx* ctx, int32_t n, const float* const* pcm_host, const int64_t* n_samples,
                               float* const* out_probs_host, float* const* out_logits_host);
+
+/* ---- stateful streaming VAD: the same network over recordings that arrive in pieces (the streaming server's
+ * vad_pipeline.detect_activity(client), buffering_strategies.py:104-126, asked again for every 1.5-s chunk) ------------------- */
+/* A stream is ONE recording that arrives in pieces.  It owns its LSTM state (h, c) in a device table
+ * [TTASR_VAD_MAX_STREAMS][256] of the context and, on the host inside the context, the last 64 evaluated samples and the pending
+ * samples (at most 511) that do not fill a frame yet.
+ *
+ * ttasr_vad_stream_open: a new stream with zero state and nothing pending; *out_id receives its id (0 ... TTASR_VAD_MAX_STREAMS
+ *   - 1; ids of closed streams are handed out again).  The FIRST open of a context allocates everything the stream path ever
+ *   needs - the 1 MiB state table, the pinned staging, and the scratch block of ttasr_vad_probs sized for max_batch recordings (the
+ *   two paths share that block) - so device memory is the offline block for max_batch recordings plus the table, never a function of
+ *   the number of rows of a push or of their lengths.  Refused (TTASR_E_INVALID) in an open session, because it may allocate,
+ *   without finalized VAD weights, and when TTASR_VAD_MAX_STREAMS streams are open.  TTASR_E_NOMEM leaves the context usable.
+ * ttasr_vad_stream_reset: the stream is as freshly opened.  ttasr_vad_stream_close: its id is free again.  An id that is not open:
+ *   TTASR_E_INVALID.
+ * ttasr_vad_stream_push: n rows; row i appends pcm_host[i][0 .. n_samples[i]) to stream ids[i] (0 samples is legal, its pcm may be
+ *   NULL).  Every complete 512-sample frame of pending + new samples is evaluated, in order; what is left stays pending.  With
+ *   finish != NULL and finish[i] != 0, samples still pending are evaluated as one more frame, zero-padded, and the stream is then as
+ *   reset.  out_frames[i] receives the number of values written to out_probs_host[i] (and out_logits_host[i] when out_logits_host
+ *   != NULL); the caller provides n_samples[i] / 512 + 2 floats per row (a row that receives no value may be NULL).
+ *   THE BIT CONTRACT: the form of every kernel is a function of the frame only, across calls as well as inside one.  However a
+ *   recording x is cut into pushes (pieces of 0, 1, 511, 513 ... samples), however the pushes are interleaved with those of other
+ *   streams, in whatever order the ids stand and however many rows a call has: the concatenated outputs of a stream whose last push
+ *   has finish equal ttasr_vad_probs on x, probabilities and logits, bit for bit; without finish they equal its first
+ *   floor(len / 512) values.  Compute modes do not change a bit either.
+ *   A push walks its rows in groups of at most max_batch and long inputs in time chunks of TTASR_VAD_CHUNK_FRAMES frames, through
+ *   the same chunk loop and per-frame kernels as ttasr_vad_probs; it never allocates.  The stream table is separate from the state
+ *   region ttasr_vad_probs zeroes: an offline call between two pushes changes nothing in any stream.
+ *   Sessions: push, reset and close are legal while a continuous-batching session is open, between session calls; they use the
+ *   context's stream and touch no mel, encoder, search, graph or session state.  ttasr_vad_probs stays refused there.
+ *   Refused with TTASR_E_INVALID before anything is enqueued, the context and every stream stay as they were: VAD weights not
+ *   finalized (no stream can be open); n < 1 or n above the number of open streams; a NULL ids / pcm_host / n_samples /
+ *   out_probs_host / out_frames array; an id that is not open; the same id twice in one call; a negative length; a NULL pcm with
+ *   samples; a NULL output row that would receive values; a call already in flight on the context.
+ *   A TTASR_E_HIP in the middle of a push leaves the streams of THAT call reset (zero state, nothing pending): the caller feeds
+ *   them again from the start of their recordings, or closes them.
+ * Streams belong to their context (a ttasr_create_shared context has its own) and everything is freed by ttasr_destroy. */
+#define TTASR_VAD_MAX_STREAMS 1024
+TTASR_API int ttasr_vad_stream_open(ttasr_ctx* ctx, int32_t* out_id);
+TTASR_API int ttasr_vad_stream_reset(ttasr_ctx* ctx, int32_t id);
+TTASR_API int ttasr_vad_stream_close(ttasr_ctx* ctx, int32_t id);
+TTASR_API int ttasr_vad_stream_push(ttasr_ctx* ctx, int32_t n, const int32_t* ids, const float* const* pcm_host,
+                                    const int64_t* n_samples, const int32_t* finish, float* const* out_probs_host,
+                                    float* const* out_logits_host, int32_t* out_frames);
 
 /* ---- file ingest: raw samples of a file -> float32 mono 16 kHz (what librosa.load(..., sr=16000) does in front of every file
  * entry point of the reference: asr_core.py:156, file_asr.py:271,455; faster-whisper's decode_audio) -------------------------- */

@@ -20,11 +20,13 @@ SYMBOLS = [
     "ttasr_align_batch", "ttasr_session_hold", "ttasr_session_align", "ttasr_session_release", "ttasr_detect_language",
     "ttasr_session_detect_language", "ttasr_session_poll_lang", "ttasr_session_prefill_stats",
     "ttasr_vad_load_tensor", "ttasr_vad_finalize", "ttasr_vad_probs",
+    "ttasr_vad_stream_open", "ttasr_vad_stream_reset", "ttasr_vad_stream_close", "ttasr_vad_stream_push",
     "ttasr_ingest_len", "ttasr_ingest_filter", "ttasr_ingest_pcm",
 ]
 
 PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = range(6)   # TTASR_PCM_* of include/ttasr.h
 PCM_BYTES = (1, 2, 3, 4, 4, 8)                                    # bytes per sample, by format code
+VAD_MAX_STREAMS = 1024    # TTASR_VAD_MAX_STREAMS of include/ttasr.h: open streams of one context (ttasr_vad_stream_*)
 VAD_CHUNK_FRAMES = 1024   # TTASR_VAD_CHUNK_FRAMES of include/ttasr.h: frames of one recording per time chunk of ttasr_vad_probs
 
 
@@ -121,6 +123,10 @@ def load() -> C.CDLL:
     lib.ttasr_vad_load_tensor.argtypes = [vp, C.c_char_p, vp, i64p, i32]
     lib.ttasr_vad_finalize.argtypes = [vp]
     lib.ttasr_vad_probs.argtypes = [vp, i32, C.POINTER(vp), i64p, C.POINTER(vp), C.POINTER(vp)]
+    lib.ttasr_vad_stream_open.argtypes = [vp, i32p]
+    lib.ttasr_vad_stream_reset.argtypes = [vp, i32]
+    lib.ttasr_vad_stream_close.argtypes = [vp, i32]
+    lib.ttasr_vad_stream_push.argtypes = [vp, i32, i32p, C.POINTER(vp), i64p, i32p, C.POINTER(vp), C.POINTER(vp), i32p]
     lib.ttasr_ingest_len.argtypes = [i32, i64]
     lib.ttasr_ingest_len.restype = i64
     lib.ttasr_ingest_filter.argtypes = [i32, f32p, i32]

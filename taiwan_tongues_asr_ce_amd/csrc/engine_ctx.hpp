@@ -41,7 +41,7 @@ struct Slot {              // where one named tensor lands on the device
 };
 
 struct Session;            // continuous-batching session state (engine_refill.hip)
-struct VadState;           // voice-activity network: weights, scratch and staging of one context (engine_vad.hip)
+struct VadState;           // voice-activity network: weights, scratch, staging and streams of one context (engine_vad.hip)
 struct IngestState;        // file ingest: tap tables per rate and the chunk slots of one context (engine_ingest.hip)
 // What run_decode_rows reads about the rows of a step, and (with the batch, the mode and the e4m3 state) what a captured step
 // graph is keyed on.  Installed and restored by SearchScope only.
@@ -380,7 +380,7 @@ int align_batch_validate(ttasr_ctx* c, const AlignBatch& a);
 int align_batch_run(ttasr_ctx* c, const AlignBatch& a, const int32_t* slot /*[n]*/, const int32_t* pages /*[n][pages_per_seq]*/);
 
 // ---- engine_vad.hip: the voice-activity network (ttasr_vad_*) ----
-void vad_free(ttasr_ctx* c);         // ttasr_destroy: the scratch block and the pinned staging (the weights live in the arenas)
+void vad_free(ttasr_ctx* c);         // ttasr_destroy: the scratch block, the pinned staging and the streams' table (the weights live in the arenas)
 
 // ---- engine_ingest.hip: file ingest (ttasr_ingest_*) ----
 void ingest_free(ttasr_ctx* c);      // ttasr_destroy: the tap tables, the device and pinned chunk slots and their events

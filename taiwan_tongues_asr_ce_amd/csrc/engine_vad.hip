@@ -1,7 +1,7 @@
 // libttasr: the voice-activity network behind the C ABI (one of the engine translation units, see engine_ctx.hpp): weight intake
-// into the kernels' layouts, the context's scratch block and pinned staging, and the chunk loop of ttasr_vad_probs.  The kernels
-// are kernels_vad.hip; the network is the text of include/ttasr.h.  Nothing here touches mel, encoder, search or graph state:
-// the call's only shared resource is the context's stream.
+// into the kernels' layouts, the context's scratch block and pinned staging, the chunk loop that ttasr_vad_probs and
+// ttasr_vad_stream_push share, and the streams' host state.  The kernels are kernels_vad.hip; the network is the text of
+// include/ttasr.h.  Nothing here touches mel, encoder, search or graph state: the call's only shared resource is the context's stream.
 #include "engine_ctx.hpp"
 #include "vad.hpp"
 
@@ -24,6 +24,7 @@ static const VadSpec kVadSpec[V_COUNT] = {
 
 constexpr int kVadPinSlots = 8;   // chunk slots of PCM in the pinned staging block (8 x 2 MiB)
 
+struct VadStreams;
 struct VadState {
   float* dev[V_COUNT] = {};       // device tensors (arena memory of the context)
   float* gate_b = nullptr;        // b_ih + b_hh
@@ -31,22 +32,64 @@ struct VadState {
   std::vector<float> bih, bhh;    // host copies until ttasr_vad_finalize adds them
   bool finalized = false;
   VadWeights w{};
-  // scratch: pcm [files][kVadSlot] | gx [files][C][512] | out [files][2][C] | state [files][256] | nf [files]
+  // scratch: pcm [files][kVadSlot] | gx [files][C][512] | out [files][2][C] | state [files][256] | nf [files] | slot [files]
   char* scratch = nullptr; int scratch_files = 0;
-  // pinned: pcm slots [kVadPinSlots][kVadSlot] | out [max_batch][2][C] | nf [max_batch]
+  // pinned: pcm slots [kVadPinSlots][kVadSlot] | out [max_batch][2][C] | nf [max_batch] | slot [max_batch]
   char* pinned = nullptr;
+  VadStreams* streams = nullptr;  // created by the first ttasr_vad_stream_open
 };
+
+// One row of a pass through the chunk loop, as ONE sequence of samples: positions [-64, 0) the context in front of the first frame
+// (ctx; nullptr = zeros), [0, n_head) samples held from earlier (a stream's pending ones), [n_head, n_head + n_pcm) the caller's,
+// zeros behind.  `frames` frames of 512 are evaluated from position 0.
+struct VadRow {
+  const float* ctx; const float* head; int64_t n_head; const float* pcm; int64_t n_pcm;
+  int64_t frames; float* probs; float* logits;
+};
+
+// count samples of the row's sequence from position pos (>= -64) on: what a frame of the network reads is this and nothing else,
+// for a whole recording and for a stream alike
+static void vad_gather(float* dst, const VadRow& r, int64_t pos, int64_t count) {
+  const int64_t end = pos + count, total = r.n_head + r.n_pcm;
+  const struct { int64_t lo, hi; const float* p; } seg[3] = {
+      {-(int64_t)kVadContext, 0, r.ctx}, {0, r.n_head, r.head}, {r.n_head, total, r.pcm}};
+  for (const auto& g : seg) {
+    const int64_t lo = std::max(pos, g.lo), hi = std::min(end, g.hi);
+    if (lo >= hi) continue;
+    if (g.p) memcpy(dst + (lo - pos), g.p + (lo - g.lo), (size_t)(hi - lo) * 4);
+    else memset(dst + (lo - pos), 0, (size_t)(hi - lo) * 4);
+  }
+  const int64_t z = std::max(pos, total);
+  if (z < end) memset(dst + (z - pos), 0, (size_t)(end - z) * 4);
+}
+
+// A stream (include/ttasr.h): its (h, c) is row `id` of the device table; here the last 64 evaluated samples and the samples that
+// do not fill a frame yet.  fresh: the table row is to be zeroed before the stream's next frame (open, reset, finish and a failed
+// push only set the flag, so none of them touches the device).
+struct VadStream { bool open = false, fresh = true; int n_pend = 0; float ctx[kVadContext] = {}; float pend[kVadWindow] = {}; };
+struct VadStreams {
+  float* table = nullptr;                       // [TTASR_VAD_MAX_STREAMS][256], device
+  int n_open = 0;
+  std::vector<VadStream> s = std::vector<VadStream>(TTASR_VAD_MAX_STREAMS);
+  std::vector<VadRow> rows = std::vector<VadRow>(TTASR_VAD_MAX_STREAMS);   // a push's rows (n <= open streams): a push never allocates
+  std::vector<uint8_t> seen = std::vector<uint8_t>(TTASR_VAD_MAX_STREAMS);
+};
+static void vad_stream_clear(VadStream& st) { st.fresh = true; st.n_pend = 0; memset(st.ctx, 0, sizeof st.ctx); }
 
 void vad_free(ttasr_ctx* c) {
   if (!c->vad) return;
   if (c->vad->scratch) hipFree(c->vad->scratch);
   if (c->vad->pinned) hipHostFree(c->vad->pinned);
+  if (c->vad->streams) {
+    if (c->vad->streams->table) hipFree(c->vad->streams->table);
+    delete c->vad->streams;
+  }
   delete c->vad;
   c->vad = nullptr;
 }
 
 static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-struct VadScratch { size_t pcm, gx, out, state, nf, total; };
+struct VadScratch { size_t pcm, gx, out, state, nf, slot, total; };
 static VadScratch vad_scratch_layout(int files) {
   VadScratch l;
   l.pcm = 0;
@@ -54,7 +97,8 @@ static VadScratch vad_scratch_layout(int files) {
   l.out = l.gx + up256((size_t)files * kVadChunk * 512 * 4);
   l.state = l.out + up256((size_t)files * 2 * kVadChunk * 4);
   l.nf = l.state + up256((size_t)files * 256 * 4);
-  l.total = l.nf + up256((size_t)files * 4);
+  l.slot = l.nf + up256((size_t)files * 4);
+  l.total = l.slot + up256((size_t)files * 4);
   return l;
 }
 
@@ -80,7 +124,7 @@ static int vad_scratch(ttasr_ctx* c, int files) {
 static int vad_pinned(ttasr_ctx* c) {
   VadState* v = c->vad;
   if (v->pinned) return 0;
-  const size_t bytes = (size_t)kVadPinSlots * kVadSlot * 4 + (size_t)c->maxB * 2 * kVadChunk * 4 + (size_t)c->maxB * 4;
+  const size_t bytes = (size_t)kVadPinSlots * kVadSlot * 4 + (size_t)c->maxB * 2 * kVadChunk * 4 + (size_t)c->maxB * 8;
   const hipError_t e = hipHostMalloc((void**)&v->pinned, bytes, hipHostMallocDefault);
   if (e != hipSuccess) {
     v->pinned = nullptr;
@@ -147,6 +191,59 @@ static int vad_finalize(ttasr_ctx* c) {
   return TTASR_OK;
 }
 
+// The chunk loop of both paths: n <= scratch_files rows, frames of row i in time chunks of kVadChunk, (h, c) of row i at
+// state[slots[i]] (slots == nullptr: state[i]) carried from chunk to chunk.  Ends synchronised.
+static int vad_run(ttasr_ctx* c, const VadRow* rows, int n, float* d_state, const int32_t* slots) {
+  VadState* v = c->vad;
+  hipStream_t s = c->stream;
+  const VadScratch l = vad_scratch_layout(v->scratch_files);
+  float* d_pcm = (float*)(v->scratch + l.pcm);
+  float* d_gx = (float*)(v->scratch + l.gx);
+  float* d_out = (float*)(v->scratch + l.out);
+  int32_t* d_nf = (int32_t*)(v->scratch + l.nf);
+  int32_t* d_slot = slots ? (int32_t*)(v->scratch + l.slot) : nullptr;
+  float* p_pcm = (float*)v->pinned;
+  float* p_out = p_pcm + (size_t)kVadPinSlots * kVadSlot;
+  int32_t* p_nf = (int32_t*)(p_out + (size_t)c->maxB * 2 * kVadChunk);
+  int32_t* p_slot = p_nf + c->maxB;
+  int64_t max_frames = 0;
+  for (int i = 0; i < n; ++i) max_frames = std::max(max_frames, rows[i].frames);
+  if (max_frames == 0) return TTASR_OK;
+  if (slots) {
+    memcpy(p_slot, slots, (size_t)n * 4);
+    HIPCHK(c, hipMemcpyAsync(d_slot, p_slot, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  }
+  for (int64_t k0 = 0; k0 < max_frames; k0 += kVadChunk) {
+    int max_nf = 0, staged = 0;
+    for (int i = 0; i < n; ++i) {
+      const int nf = (int)std::min<int64_t>(std::max<int64_t>(rows[i].frames - k0, 0), kVadChunk);
+      p_nf[i] = nf;
+      max_nf = std::max(max_nf, nf);
+      if (nf == 0) continue;
+      // the slot: 64 samples in front of the chunk (zeros in front of the recording) | nf frames, zeros behind the last sample
+      if (staged && staged % kVadPinSlots == 0) HIPCHK(c, hipStreamSynchronize(s));   // the slots are free again
+      float* slot = p_pcm + (size_t)(staged % kVadPinSlots) * kVadSlot;
+      const int64_t count = kVadContext + (int64_t)nf * kVadWindow;
+      vad_gather(slot, rows[i], k0 * kVadWindow - kVadContext, count);
+      HIPCHK(c, hipMemcpyAsync(d_pcm + (size_t)i * kVadSlot, slot, (size_t)count * 4, hipMemcpyHostToDevice, s));
+      ++staged;
+    }
+    HIPCHK(c, hipMemcpyAsync(d_nf, p_nf, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    launch_vad_frames(v->w, d_pcm, d_nf, d_gx, n, max_nf, s);
+    launch_vad_lstm(v->w, d_gx, d_nf, d_state, d_slot, d_out, n, s);
+    HIPCHK(c, hipMemcpyAsync(p_out, d_out, (size_t)n * 2 * kVadChunk * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    HIPCHK(c, hipGetLastError());
+    for (int i = 0; i < n; ++i) {
+      if (p_nf[i] == 0) continue;
+      const float* row = p_out + (size_t)i * 2 * kVadChunk;
+      if (rows[i].logits) memcpy(rows[i].logits + k0, row, (size_t)p_nf[i] * 4);
+      memcpy(rows[i].probs + k0, row + kVadChunk, (size_t)p_nf[i] * 4);
+    }
+  }
+  return TTASR_OK;
+}
+
 static int vad_probs(ttasr_ctx* c, int32_t n, const float* const* pcm, const int64_t* ns, float* const* out_probs,
                      float* const* out_logits) {
   VadState* v = c->vad;
@@ -154,62 +251,118 @@ static int vad_probs(ttasr_ctx* c, int32_t n, const float* const* pcm, const int
   if (n < 1 || n > c->maxB) return fail(c, TTASR_E_INVALID, "n %d outside [1, max_batch = %d]", n, c->maxB);
   if (!pcm || !ns || !out_probs) return fail(c, TTASR_E_INVALID, "NULL argument");
   int64_t max_frames = 0;
-  std::vector<int64_t> frames(n);
+  std::vector<VadRow> rows(n);
   for (int i = 0; i < n; ++i) {
     if (ns[i] < 0) return fail(c, TTASR_E_INVALID, "recording %d: negative length", i);
     if (ns[i] > 0 && (!pcm[i] || !out_probs[i] || (out_logits && !out_logits[i])))
       return fail(c, TTASR_E_INVALID, "recording %d: NULL pcm or output row with %lld samples", i, (long long)ns[i]);
-    frames[i] = (ns[i] + kVadWindow - 1) / kVadWindow;
-    max_frames = std::max(max_frames, frames[i]);
+    rows[i] = VadRow{nullptr, nullptr, 0, pcm[i], ns[i], (ns[i] + kVadWindow - 1) / kVadWindow, out_probs[i],
+                     out_logits ? out_logits[i] : nullptr};
+    max_frames = std::max(max_frames, rows[i].frames);
   }
   TRY(session_refusal(c));
   HIPCHK(c, hipSetDevice(c->device));
   if (max_frames == 0) return TTASR_OK;
   TRY(vad_pinned(c));
   TRY(vad_scratch(c, n));
-  hipStream_t s = c->stream;
-  const VadScratch l = vad_scratch_layout(v->scratch_files);
-  float* d_pcm = (float*)(v->scratch + l.pcm);
-  float* d_gx = (float*)(v->scratch + l.gx);
-  float* d_out = (float*)(v->scratch + l.out);
-  float* d_state = (float*)(v->scratch + l.state);
-  int32_t* d_nf = (int32_t*)(v->scratch + l.nf);
-  float* p_pcm = (float*)v->pinned;
-  float* p_out = p_pcm + (size_t)kVadPinSlots * kVadSlot;
-  int32_t* p_nf = (int32_t*)(p_out + (size_t)c->maxB * 2 * kVadChunk);
-  HIPCHK(c, hipMemsetAsync(d_state, 0, (size_t)n * 256 * 4, s));   // (h, c) = 0 at the start of every recording
-  for (int64_t k0 = 0; k0 < max_frames; k0 += kVadChunk) {
-    int max_nf = 0, staged = 0;
-    for (int i = 0; i < n; ++i) {
-      const int nf = (int)std::min<int64_t>(std::max<int64_t>(frames[i] - k0, 0), kVadChunk);
-      p_nf[i] = nf;
-      max_nf = std::max(max_nf, nf);
-      if (nf == 0) continue;
-      // the slot: 64 samples in front of the chunk (zeros in front of the recording) | nf frames, zeros behind the last sample
-      if (staged && staged % kVadPinSlots == 0) HIPCHK(c, hipStreamSynchronize(s));   // the slots are free again
-      float* slot = p_pcm + (size_t)(staged % kVadPinSlots) * kVadSlot;
-      const int64_t first = k0 * kVadWindow - kVadContext, count = kVadContext + (int64_t)nf * kVadWindow;
-      const int64_t lo = std::max<int64_t>(first, 0), hi = std::min<int64_t>(first + count, ns[i]);
-      if (lo > first) memset(slot, 0, (size_t)(lo - first) * 4);
-      memcpy(slot + (lo - first), pcm[i] + lo, (size_t)(hi - lo) * 4);
-      if (hi < first + count) memset(slot + (hi - first), 0, (size_t)(first + count - hi) * 4);
-      HIPCHK(c, hipMemcpyAsync(d_pcm + (size_t)i * kVadSlot, slot, (size_t)count * 4, hipMemcpyHostToDevice, s));
-      ++staged;
-    }
-    HIPCHK(c, hipMemcpyAsync(d_nf, p_nf, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    launch_vad_frames(v->w, d_pcm, d_nf, d_gx, n, max_nf, s);
-    launch_vad_lstm(v->w, d_gx, d_nf, d_state, d_out, n, s);
-    HIPCHK(c, hipMemcpyAsync(p_out, d_out, (size_t)n * 2 * kVadChunk * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    HIPCHK(c, hipGetLastError());
-    for (int i = 0; i < n; ++i) {
-      if (p_nf[i] == 0) continue;
-      const float* row = p_out + (size_t)i * 2 * kVadChunk;
-      if (out_logits) memcpy(out_logits[i] + k0, row, (size_t)p_nf[i] * 4);
-      memcpy(out_probs[i] + k0, row + kVadChunk, (size_t)p_nf[i] * 4);
+  float* d_state = (float*)(v->scratch + vad_scratch_layout(v->scratch_files).state);
+  HIPCHK(c, hipMemsetAsync(d_state, 0, (size_t)n * 256 * 4, c->stream));   // (h, c) = 0 at the start of every recording
+  return vad_run(c, rows.data(), n, d_state, nullptr);
+}
+
+// ---- streams ----
+
+static int vad_stream_open(ttasr_ctx* c, int32_t* out_id) {
+  VadState* v = c->vad;
+  if (!v || !v->finalized) return fail(c, TTASR_E_INVALID, "VAD weights not finalized (ttasr_vad_load_tensor, ttasr_vad_finalize first)");
+  if (!out_id) return fail(c, TTASR_E_INVALID, "NULL argument");
+  TRY(session_refusal(c));   // the first open allocates
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!v->streams) v->streams = new VadStreams();
+  VadStreams* S = v->streams;
+  if (S->n_open >= TTASR_VAD_MAX_STREAMS) return fail(c, TTASR_E_INVALID, "all %d VAD streams of a context are open", S->n_open);
+  // everything a push ever needs: the table, the pinned staging, the scratch block for groups of max_batch rows
+  if (!S->table) {
+    const size_t bytes = (size_t)TTASR_VAD_MAX_STREAMS * 256 * 4;
+    const hipError_t e = hipMalloc((void**)&S->table, bytes);
+    if (e != hipSuccess) {
+      S->table = nullptr;
+      (void)hipGetLastError();
+      return fail(c, TTASR_E_NOMEM, "VAD stream table (%zu bytes): %s", bytes, hipGetErrorString(e));
     }
   }
+  TRY(vad_pinned(c));
+  TRY(vad_scratch(c, c->maxB));
+  int id = 0;
+  while (S->s[id].open) ++id;   // n_open < TTASR_VAD_MAX_STREAMS: one is free
+  S->s[id].open = true;
+  vad_stream_clear(S->s[id]);
+  ++S->n_open;
+  *out_id = id;
   return TTASR_OK;
+}
+
+static VadStream* vad_stream_of(ttasr_ctx* c, int32_t id) {
+  VadStreams* S = c->vad ? c->vad->streams : nullptr;
+  return S && id >= 0 && id < TTASR_VAD_MAX_STREAMS && S->s[id].open ? &S->s[id] : nullptr;
+}
+
+static int vad_stream_push(ttasr_ctx* c, int32_t n, const int32_t* ids, const float* const* pcm, const int64_t* ns,
+                           const int32_t* finish, float* const* out_probs, float* const* out_logits, int32_t* out_frames) {
+  VadState* v = c->vad;
+  if (!v || !v->finalized) return fail(c, TTASR_E_INVALID, "VAD weights not finalized (ttasr_vad_load_tensor, ttasr_vad_finalize first)");
+  VadStreams* S = v->streams;
+  const int n_open = S ? S->n_open : 0;
+  if (n < 1 || n > n_open) return fail(c, TTASR_E_INVALID, "n %d outside [1, open streams = %d]", n, n_open);
+  if (!ids || !pcm || !ns || !out_probs || !out_frames) return fail(c, TTASR_E_INVALID, "NULL argument");
+  VadRow* rows = S->rows.data();
+  memset(S->seen.data(), 0, S->seen.size());
+  for (int i = 0; i < n; ++i) {
+    VadStream* st = vad_stream_of(c, ids[i]);
+    if (!st) return fail(c, TTASR_E_INVALID, "row %d: stream %d is not open", i, ids[i]);
+    if (S->seen[ids[i]]) return fail(c, TTASR_E_INVALID, "row %d: stream %d appears twice in the call", i, ids[i]);
+    S->seen[ids[i]] = 1;
+    if (ns[i] < 0) return fail(c, TTASR_E_INVALID, "row %d: negative length", i);
+    if (ns[i] > 0 && !pcm[i]) return fail(c, TTASR_E_INVALID, "row %d: NULL pcm with %lld samples", i, (long long)ns[i]);
+    const int64_t total = st->n_pend + ns[i];
+    int64_t frames = total / kVadWindow;
+    if (finish && finish[i] && total % kVadWindow) ++frames;   // the zero-padded remainder
+    if (frames > 0 && (!out_probs[i] || (out_logits && !out_logits[i])))
+      return fail(c, TTASR_E_INVALID, "row %d: NULL output row for %lld values", i, (long long)frames);
+    if (frames > INT32_MAX) return fail(c, TTASR_E_INVALID, "row %d: %lld frames in one push", i, (long long)frames);
+    rows[i] = VadRow{st->ctx, st->pend, st->n_pend, pcm[i], ns[i], frames, out_probs[i], out_logits ? out_logits[i] : nullptr};
+  }
+  // from here on a failure leaves the streams of this call reset
+  auto run = [&]() -> int {
+    HIPCHK(c, hipSetDevice(c->device));
+    for (int i = 0; i < n; ++i)
+      if (rows[i].frames > 0 && S->s[ids[i]].fresh)
+        HIPCHK(c, hipMemsetAsync(S->table + (size_t)ids[i] * 256, 0, 256 * 4, c->stream));
+    for (int g0 = 0; g0 < n; g0 += c->maxB)
+      TRY(vad_run(c, rows + g0, std::min(c->maxB, n - g0), S->table, ids + g0));
+    return TTASR_OK;
+  };
+  const int rc = run();
+  float ctx[kVadContext], pend[kVadWindow];
+  for (int i = 0; i < n; ++i) {
+    VadStream& st = S->s[ids[i]];
+    const VadRow& r = rows[i];
+    const int64_t total = r.n_head + r.n_pcm, done = r.frames * kVadWindow;
+    out_frames[i] = rc == TTASR_OK ? (int32_t)r.frames : 0;
+    if (rc != TTASR_OK || (finish && finish[i])) { vad_stream_clear(st); continue; }   // failed, or finished: as freshly opened
+    // done <= total < done + 512: the last 64 evaluated samples and the new remainder, read before either is overwritten
+    if (r.frames > 0) {
+      vad_gather(ctx, r, done - kVadContext, kVadContext);
+      vad_gather(pend, r, done, total - done);
+      memcpy(st.ctx, ctx, sizeof ctx);
+      memcpy(st.pend, pend, (size_t)(total - done) * 4);
+      st.fresh = false;
+    } else if (r.n_pcm > 0) {
+      memcpy(st.pend + st.n_pend, r.pcm, (size_t)r.n_pcm * 4);
+    }
+    st.n_pend = (int)(total - done);
+  }
+  return rc;
 }
 
 }  // namespace ttasr_detail
@@ -238,6 +391,42 @@ int ttasr_vad_probs(ttasr_ctx* c, int32_t n, const float* const* pcm, const int6
   return guarded(c, [&]() -> int {
   if (!c) return TTASR_E_INVALID;
   return vad_probs(c, n, pcm, n_samples, out_probs, out_logits);
+  });
+}
+
+int ttasr_vad_stream_open(ttasr_ctx* c, int32_t* out_id) {
+  return guarded(c, [&]() -> int {
+  if (!c) return TTASR_E_INVALID;
+  return vad_stream_open(c, out_id);
+  });
+}
+
+int ttasr_vad_stream_reset(ttasr_ctx* c, int32_t id) {
+  return guarded(c, [&]() -> int {
+  if (!c) return TTASR_E_INVALID;
+  VadStream* st = vad_stream_of(c, id);
+  if (!st) return fail(c, TTASR_E_INVALID, "VAD stream %d is not open", id);
+  vad_stream_clear(*st);
+  return TTASR_OK;
+  });
+}
+
+int ttasr_vad_stream_close(ttasr_ctx* c, int32_t id) {
+  return guarded(c, [&]() -> int {
+  if (!c) return TTASR_E_INVALID;
+  VadStream* st = vad_stream_of(c, id);
+  if (!st) return fail(c, TTASR_E_INVALID, "VAD stream %d is not open", id);
+  st->open = false;
+  --c->vad->streams->n_open;
+  return TTASR_OK;
+  });
+}
+
+int ttasr_vad_stream_push(ttasr_ctx* c, int32_t n, const int32_t* ids, const float* const* pcm, const int64_t* n_samples,
+                          const int32_t* finish, float* const* out_probs, float* const* out_logits, int32_t* out_frames) {
+  return guarded(c, [&]() -> int {
+  if (!c) return TTASR_E_INVALID;
+  return vad_stream_push(c, n, ids, pcm, n_samples, finish, out_probs, out_logits, out_frames);
   });
 }
 

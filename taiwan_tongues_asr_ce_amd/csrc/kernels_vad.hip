@@ -7,7 +7,9 @@
 //                       frame's sums run in the same fixed order (input index ascending), whichever slot of the tile it has.
 //   vad_lstm_kernel     recurrent: one workgroup of 512 threads per recording walks its frames in order.  Thread r keeps row r of
 //                       W_hh (128 f32) in registers for the whole launch, h lives in LDS and is read as a broadcast; two barriers
-//                       per frame; the output head is a fixed-order wave reduction.  No atomics anywhere.
+//                       per frame; the output head is a fixed-order wave reduction.  No atomics anywhere.  Its (h, c) lives at
+//                       state[slot[row]] (slot == nullptr: state[row]): the offline call keeps one state row per recording of
+//                       the call, a stream push names the rows of the context's stream table.  ONE per-frame body for both.
 //
 // The form of both kernels is a function of the frame only: nothing depends on a recording's length, on the number of recordings
 // or on a recording's place in the call (those decide grid sizes and early exits of whole workgroups, never an operand order).
@@ -145,7 +147,8 @@ __device__ __forceinline__ float vad_sigmoid(float x) { return 1.f / (1.f + expf
 
 // 512 threads = 8 waves, 2 per SIMD: a wave may hold 256 VGPRs, 128 of them row r of W_hh.
 __global__ __launch_bounds__(512) void vad_lstm_kernel(VadWeights w, const float* __restrict__ gx, const int32_t* __restrict__ nf,
-                                                       float* __restrict__ state, float* __restrict__ out) {
+                                                       float* __restrict__ state, const int32_t* __restrict__ slot,
+                                                       float* __restrict__ out) {
   const int file = blockIdx.x;
   const int n = min(nf[file], kVadChunk);
   if (n <= 0) return;   // uniform
@@ -159,7 +162,7 @@ __global__ __launch_bounds__(512) void vad_lstm_kernel(VadWeights w, const float
     const f32x4 v = *(const f32x4*)(w.whh + (size_t)r * 128 + k);
     wr[k] = v[0]; wr[k + 1] = v[1]; wr[k + 2] = v[2]; wr[k + 3] = v[3];
   }
-  float* st = state + (size_t)file * 256;
+  float* st = state + (size_t)(slot ? slot[file] : file) * 256;   // uniform; the host checked the index and that no two rows share one
   float cell = 0.f, wo = 0.f;
   if (r < 128) { s_h[r] = st[r]; cell = st[128 + r]; wo = w.w_out[r]; }
   const float b_out = w.b_out[0];
@@ -216,10 +219,11 @@ void launch_vad_frames(const VadWeights& w, const float* pcm, const int32_t* nf,
   hipLaunchKernelGGL(vad_frames_kernel, dim3((max_nf + FT - 1) / FT, n), dim3(VAD_THREADS), 0, s, w, pcm, nf, gx);
 }
 
-void launch_vad_lstm(const VadWeights& w, const float* gx, const int32_t* nf, float* state, float* out, int n, hipStream_t s) {
+void launch_vad_lstm(const VadWeights& w, const float* gx, const int32_t* nf, float* state, const int32_t* slot, float* out, int n,
+                     hipStream_t s) {
   if (n < 1 || !gx || !nf || !state || !out) {
     launch_fault("vad_lstm: %d recordings", n);
     return;
   }
-  hipLaunchKernelGGL(vad_lstm_kernel, dim3(n), dim3(512), 0, s, w, gx, nf, state, out);
+  hipLaunchKernelGGL(vad_lstm_kernel, dim3(n), dim3(512), 0, s, w, gx, nf, state, slot, out);
 }

@@ -27,7 +27,10 @@ struct VadWeights {
 };
 
 // One time chunk of n recordings.  pcm [n][kVadSlot] staged samples; nf [n] frames of recording i in this chunk (0 ... kVadChunk);
-// gx [n][kVadChunk][512] the hoisted input projection; state [n][256] h | c, carried from chunk to chunk; out [n][2][kVadChunk]
-// logits | probabilities.  max_nf = the largest nf (host copy): sizes the frame kernel's grid only.
+// gx [n][kVadChunk][512] the hoisted input projection; state [...][256] h | c, carried from chunk to chunk (and, for a stream,
+// from call to call); slot [n] (device memory) the state row of each row of the call - distinct, inside the state table - or
+// nullptr for row i -> state row i; out [n][2][kVadChunk] logits | probabilities.  max_nf = the largest nf (host copy): sizes the
+// frame kernel's grid only.
 void launch_vad_frames(const VadWeights& w, const float* pcm, const int32_t* nf, float* gx, int n, int max_nf, hipStream_t s);
-void launch_vad_lstm(const VadWeights& w, const float* gx, const int32_t* nf, float* state, float* out, int n, hipStream_t s);
+void launch_vad_lstm(const VadWeights& w, const float* gx, const int32_t* nf, float* state, const int32_t* slot, float* out, int n,
+                     hipStream_t s);

@@ -143,6 +143,59 @@ class Engine:
             self._check(self.lib.ttasr_vad_probs(self.h, n, ptrs, ns.ctypes.data_as(C.POINTER(C.c_int64)), outs, louts), "vad_probs")
         return (probs, logits) if return_logits else probs
 
+    # -- streaming voice activity detection --------------------------------------------------------
+    def vad_stream_open(self) -> int:
+        """A new VAD stream of this context - one recording that arrives in pieces - with zero state and nothing pending
+        (ttasr_vad_stream_open).  The first open allocates everything the stream path needs, so it is refused inside an open
+        session; at most _lib.VAD_MAX_STREAMS streams are open at a time."""
+        sid = C.c_int32(-1)
+        self._check(self.lib.ttasr_vad_stream_open(self.h, C.byref(sid)), "vad_stream_open")
+        return int(sid.value)
+
+    def vad_stream_reset(self, stream_id: int):
+        """The stream is as freshly opened (ttasr_vad_stream_reset); legal inside an open session."""
+        self._check(self.lib.ttasr_vad_stream_reset(self.h, int(stream_id)), "vad_stream_reset")
+
+    def vad_stream_close(self, stream_id: int):
+        self._check(self.lib.ttasr_vad_stream_close(self.h, int(stream_id)), "vad_stream_close")
+
+    def vad_stream_push(self, ids: Sequence[int], audios: Sequence[np.ndarray], finish: Optional[Sequence[bool]] = None,
+                        return_logits: bool = False):
+        """Append audios[i] (float32 PCM, 0 samples is legal) to stream ids[i], all rows in ONE call (ttasr_vad_stream_push): a
+        list with one float32 array per row, the probabilities of the 512-sample frames the row completed (samples that fill no
+        frame stay pending in the stream); finish[i] evaluates the zero-padded remainder too and leaves the stream as reset.
+        return_logits=True: (probabilities, pre-sigmoid logits).  The concatenated outputs of a stream equal `vad_probs` on the
+        concatenated pieces bit for bit, however the recording is cut and whatever else shares the calls.  Legal inside an open
+        session, between its calls."""
+        n = len(ids)
+        if len(audios) != n or (finish is not None and len(finish) != n):
+            raise ValueError("ids, audios and finish must have one entry per row")
+        if n == 0:
+            return ([], []) if return_logits else []
+        pcm = []
+        for i, a in enumerate(audios):
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.ndim != 1:
+                raise ValueError(f"row {i}: PCM must be one-dimensional, got shape {a.shape}")
+            pcm.append(a)
+        probs = [np.zeros(len(a) // 512 + 2, dtype=np.float32) for a in pcm]
+        logits = [np.zeros_like(p) for p in probs] if return_logits else None
+        i32p = C.POINTER(C.c_int32)
+        idv = np.asarray(list(ids), dtype=np.int32)
+        ns = np.asarray([len(a) for a in pcm], dtype=np.int64)
+        fin = np.asarray([1 if f else 0 for f in finish], dtype=np.int32) if finish is not None else None
+        frames = np.zeros(n, dtype=np.int32)
+        ptrs = (C.c_void_p * n)(*[a.ctypes.data if len(a) else None for a in pcm])
+        outs = (C.c_void_p * n)(*[p.ctypes.data for p in probs])
+        louts = (C.c_void_p * n)(*[p.ctypes.data for p in logits]) if return_logits else None
+        self._check(self.lib.ttasr_vad_stream_push(self.h, n, idv.ctypes.data_as(i32p), ptrs, ns.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                   fin.ctypes.data_as(i32p) if fin is not None else None, outs, louts,
+                                                   frames.ctypes.data_as(i32p)), "vad_stream_push")
+        probs = [p[:k].copy() for p, k in zip(probs, frames)]
+        if return_logits:
+            return probs, [l[:k].copy() for l, k in zip(logits, frames)]
+        return probs
+
     # -- file ingest -----------------------------------------------------------------------------
     def ingest(self, raws: Sequence, rates: Sequence[int], channels: Sequence[int], formats: Sequence[int]) -> List[np.ndarray]:
         """Raw interleaved samples of n recordings -> float32 mono 16 kHz, in ONE device call (ttasr_ingest_pcm): raws[i] is a

@@ -244,6 +244,60 @@ def get_speech_timestamps(audio: np.ndarray, options: Optional[VadOptions] = Non
     return speeches
 
 
+class StreamingSpeechDetector:
+    """Speech chunks of ONE recording that arrives in pieces, on a device stream (Engine.vad_stream_*): holds the stream id and
+    the probabilities so far, so every `feed` costs only the frames its samples complete - the network never runs over the same
+    audio twice, and its state stays on the device between calls.
+
+    The trailing partial frame is NOT evaluated until it fills: `segments` is `get_speech_timestamps` over the audio cut to whole
+    512-sample frames.  That is the one deliberate difference from running the offline VAD over the whole buffer (which
+    zero-pads the last frame); the part left out is never more than 32 ms, well under the 100 ms the streaming trigger allows
+    behind the last segment."""
+
+    def __init__(self, engine, stream_id: Optional[int] = None):
+        self.engine = engine
+        self.stream_id = engine.vad_stream_open() if stream_id is None else int(stream_id)
+        self.n_samples = 0
+        self._probs: List[np.ndarray] = []
+
+    @property
+    def probs(self) -> np.ndarray:
+        if len(self._probs) != 1:
+            self._probs = [np.concatenate(self._probs) if self._probs else np.zeros(0, dtype=np.float32)]
+        return self._probs[0]
+
+    def feed(self, samples: np.ndarray) -> None:
+        """Append float32 PCM (16 kHz) and evaluate the frames it completes."""
+        samples = np.ascontiguousarray(samples, dtype=np.float32)
+        self.extend(len(samples), self.engine.vad_stream_push([self.stream_id], [samples])[0])
+
+    def extend(self, n_samples: int, probs: np.ndarray) -> None:
+        """Book what a push made elsewhere returned for this stream (a backend that pushes many streams in one call)."""
+        self.n_samples += int(n_samples)
+        if len(probs):
+            self._probs.append(np.asarray(probs, dtype=np.float32))
+
+    def segments(self, options: Optional[VadOptions] = None) -> List[Dict[str, int]]:
+        """[{'start': sample, 'end': sample}] of the audio fed so far, cut to whole frames."""
+        probs = self.probs
+        cut = np.broadcast_to(np.float32(0), (len(probs) * WINDOW,))   # get_speech_timestamps reads its length only
+        return get_speech_timestamps(cut, options, lambda _a: probs)
+
+    def reset(self) -> None:
+        self.engine.vad_stream_reset(self.stream_id)
+        self.clear()
+
+    def clear(self) -> None:
+        """Forget the bookkeeping only (the stream itself was reset elsewhere)."""
+        self.n_samples = 0
+        self._probs = []
+
+    def close(self) -> None:
+        if self.stream_id is not None:
+            self.engine.vad_stream_close(self.stream_id)
+            self.stream_id = None
+
+
 def collect_chunks(audio: np.ndarray, chunks: Sequence[Dict[str, int]]) -> np.ndarray:
     if not chunks:
         return np.zeros(0, dtype=np.float32)

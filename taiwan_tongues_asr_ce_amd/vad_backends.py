@@ -1,0 +1,215 @@
+"""Plugin-level drop-in: the reference's VAD adapter interface (api/stt_streaming/src/vad/vad_interface.py:1-16,
+vad_factory.py:7-44, simple_vad.py:7-45; pyannote_vad.py:12-62 is the VAD it cannot deploy offline) with an MI355X backend
+registered under "silero" / "mi355x_silero": the streaming server's `VADFactory.create_vad_pipeline(args.vad_type, **vad_args)`
+call (main.py:196) needs no change beyond the type and `vad_model`.
+
+The server's trigger (SilenceAtEndOfChunk, buffering_strategies.py:110-126; streaming.should_transcribe) asks
+`vad_pipeline.detect_activity(client)` for the voiced segments of the client's WHOLE scratch buffer after every chunk.  The
+reference's real VAD writes that buffer to a wav file and runs its network over all of it each time; `DeviceStreamVAD` keeps one
+device stream per client (Engine.vad_stream_*), evaluates only the samples that arrived since the last call, and puts the calls
+of all clients that arrive together into one device push."""
+from __future__ import annotations
+
+import asyncio
+import logging
+import threading
+import zlib
+from typing import Any, Dict, List, Optional
+
+from . import vad
+from .asr import pcm16_bytes_to_float
+
+logger = logging.getLogger(__name__)
+
+
+class VADInterface:
+    async def detect_activity(self, client) -> List[Dict[str, float]]:
+        """[{"start", "end", "confidence"}] in seconds, of client.scratch_buffer (vad_interface.py:6-16)."""
+        raise NotImplementedError("This method should be implemented by subclasses.")
+
+
+class SimpleVAD(VADInterface):
+    """All audio is speech (simple_vad.py:22-45): [] for an empty buffer and for one shorter than min_duration, else one segment
+    over the whole buffer."""
+
+    def __init__(self, **kwargs):
+        self.min_duration = kwargs.get("min_duration", 0.1)   # simple_vad.py:19
+
+    async def detect_activity(self, client):
+        if len(client.scratch_buffer) == 0:
+            return []
+        duration = len(client.scratch_buffer) / (client.sampling_rate * client.samples_width)
+        if duration < self.min_duration:
+            return []
+        return [{"start": 0.0, "end": duration, "confidence": 1.0}]
+
+
+# pyannote_vad.py:37-45 instantiates its pipeline with onset / offset 0.5 and 0.3 s minimum on and off.  faster-whisper's own
+# default of 2 s of silence never closes a segment inside the 3-s buffers the trigger looks at.
+DEFAULT_STREAM_VAD_OPTIONS = dict(threshold=0.5, min_speech_duration_ms=300, min_silence_duration_ms=300, speech_pad_ms=0)
+
+
+class _ClientStream:
+    """One client's stream: the detector, how many bytes of its scratch buffer the stream has consumed, and their CRC."""
+    __slots__ = ("detector", "consumed", "crc", "needs_reset")
+
+    def __init__(self):
+        self.detector: Optional[vad.StreamingSpeechDetector] = None   # opened by the first push
+        self.consumed = 0
+        self.crc = 0
+        self.needs_reset = False
+
+
+class DeviceStreamVAD(VADInterface):
+    """VADInterface backend on the device's stateful streaming VAD.
+
+    One stream per `client.client_id`, opened on first sight.  Each `detect_activity` converts and pushes only the bytes of
+    `client.scratch_buffer` (s16le, as asr.pcm16_bytes_to_float reads them) beyond what that client's stream has consumed, and
+    returns the detector's segments in seconds with confidence 1.0.  The buffering strategy clears the scratch buffer after a
+    transcription (buffering_strategies.py:113,179): the backend keeps the zlib.crc32 of the consumed prefix, and when the buffer
+    is shorter than what was consumed, or its prefix has another CRC, it resets the stream and starts over.  `forget(client)`
+    closes a client's stream (call it when the client disconnects).
+
+    Concurrent calls that arrive within `max_wait_ms` are coalesced into ONE Engine.vad_stream_push, which runs in an executor
+    thread so the event loop stays free; a push does not wait once every known client is in it.  `pushes_run` records the rows of
+    every push.  The trailing partial frame (< 32 ms) is not evaluated until it fills (vad.StreamingSpeechDetector).
+
+    `vad_parameters`: vad.VadOptions fields over DEFAULT_STREAM_VAD_OPTIONS (the reference's pyannote arguments).
+
+    `engine=None`: the backend owns a VAD-only context (micro geometry, no Whisper weights, max_batch=64) with `vad_model` loaded
+    (a mapping, an .npz or a TorchScript / state-dict file: vad.load_silero_state), so it never contends with the ASR context's
+    calls or session.  `engine=`: it shares that context - whose VAD weights are loaded already, or come from `vad_model` - and
+    the caller serialises the calls; a stream cannot be OPENED while a session is open on that context (a new client's first call
+    then fails), pushes and resets can."""
+
+    def __init__(self, vad_model=None, engine=None, max_wait_ms: float = 2.0, vad_parameters: Optional[Dict[str, Any]] = None,
+                 **kwargs):
+        self.owns_engine = engine is None
+        if engine is None:
+            if vad_model is None:
+                raise ValueError("DeviceStreamVAD needs vad_model= (the Silero-v5 tensors) or an engine= that has them loaded")
+            from .config import COMPUTE_F32, PRESETS
+            from .engine import Engine
+            engine = Engine(PRESETS["micro"], COMPUTE_F32, 64, device=int(kwargs.get("device_index", 0)))
+        if vad_model is not None and not getattr(engine, "has_vad", False):
+            engine.load_vad(vad.load_silero_state(vad_model))
+        self.engine = engine
+        opts = dict(DEFAULT_STREAM_VAD_OPTIONS)
+        opts.update(vad_parameters or {})
+        self.options = vad.VadOptions(**opts)
+        self.max_wait = max_wait_ms / 1000.0
+        self.pushes_run: List[int] = []   # rows of the pushes actually executed (observability / tests)
+        self._streams: Dict[Any, _ClientStream] = {}
+        self._lock = threading.Lock()     # one engine call at a time from this object
+        self._queue: Optional[asyncio.Queue] = None
+        self._worker_task: Optional[asyncio.Task] = None
+        self._loop = None
+
+    # -- the reference's surface -------------------------------------------------------------------
+    async def detect_activity(self, client):
+        st = self._streams.get(client.client_id)
+        if st is None:
+            st = self._streams[client.client_id] = _ClientStream()
+        loop = asyncio.get_running_loop()
+        self._ensure_worker(loop)
+        fut = loop.create_future()
+        await self._queue.put((st, bytes(client.scratch_buffer), fut))
+        chunks = await fut
+        rate = float(vad.SAMPLING_RATE)
+        return [{"start": c["start"] / rate, "end": c["end"] / rate, "confidence": 1.0} for c in chunks]
+
+    def forget(self, client) -> None:
+        st = self._streams.pop(getattr(client, "client_id", client), None)
+        if st is not None and st.detector is not None:
+            with self._lock:
+                st.detector.close()
+
+    def close(self) -> None:
+        if self._worker_task is not None and not self._worker_task.done():
+            self._worker_task.cancel()
+        self._worker_task = None
+        for key in list(self._streams):
+            self.forget(key)
+        if self.owns_engine and self.engine is not None:
+            self.engine.close()
+        self.engine = None
+
+    # -- coalescing ----------------------------------------------------------------------------------
+    def _ensure_worker(self, loop):
+        if self._loop is not loop:   # a new event loop: its own queue and worker
+            self._loop, self._queue, self._worker_task = loop, asyncio.Queue(), None
+        if self._worker_task is None or self._worker_task.done():
+            self._worker_task = loop.create_task(self._worker())
+
+    async def _worker(self):
+        loop = asyncio.get_running_loop()
+        held: list = []
+        while True:
+            batch: list = []
+            carry: list = []
+
+            def place(item):   # a stream takes one row of a push: a second call of the same client goes into the next one
+                (carry if any(item[0] is b[0] for b in batch) else batch).append(item)
+
+            for item in held or [await self._queue.get()]:
+                place(item)
+            deadline = loop.time() + self.max_wait
+            while len(batch) < len(self._streams):   # every known client is in: nobody to wait for
+                timeout = deadline - loop.time()
+                if timeout <= 0:
+                    break
+                try:
+                    place(await asyncio.wait_for(self._queue.get(), timeout))
+                except asyncio.TimeoutError:
+                    break
+            held = carry
+            rows = [self._plan(st, buf) for st, buf, _ in batch]
+            try:
+                probs = await loop.run_in_executor(None, self._run_push, [st for st, _, _ in batch], rows)
+            except Exception as e:
+                logger.error("VAD stream push failed: %s", e)
+                for st, _, fut in batch:
+                    st.needs_reset, st.consumed, st.crc = True, 0, 0   # start over from the whole buffer next time
+                    if not fut.done():
+                        fut.set_exception(e)
+                continue
+            self.pushes_run.append(len(batch))
+            for (st, _, fut), (reset, new), p in zip(batch, rows, probs):
+                if reset:
+                    st.detector.clear()
+                    st.consumed, st.crc = 0, 0
+                st.needs_reset = False
+                st.detector.extend(len(new) // 2, p)
+                st.consumed += len(new)
+                st.crc = zlib.crc32(new, st.crc)
+                if not fut.done():
+                    fut.set_result(st.detector.segments(self.options))
+
+    @staticmethod
+    def _plan(st: _ClientStream, buf: bytes):
+        """(reset, new bytes): the whole samples of `buf` behind the consumed prefix - or, when the buffer is not a continuation
+        of what the stream consumed (shorter, or another CRC over the prefix), a reset and the whole buffer."""
+        reset = st.needs_reset or len(buf) < st.consumed or zlib.crc32(buf[:st.consumed]) != st.crc
+        start = 0 if reset else st.consumed
+        return reset, buf[start:len(buf) - (len(buf) - start) % 2]
+
+    def _run_push(self, streams, rows):
+        with self._lock:
+            for st, (reset, _) in zip(streams, rows):
+                if st.detector is None:
+                    st.detector = vad.StreamingSpeechDetector(self.engine)
+                elif reset:
+                    self.engine.vad_stream_reset(st.detector.stream_id)
+            return self.engine.vad_stream_push([st.detector.stream_id for st in streams],
+                                               [pcm16_bytes_to_float(new) for _, new in rows])
+
+
+class VADFactory:
+    @staticmethod
+    def create_vad_pipeline(type, **kwargs):
+        """vad_factory.py:13-44 knows "simple" only; "silero" / "mi355x_silero" is the device backend."""
+        if type == "simple":
+            return SimpleVAD(**kwargs)
+        if type in ("silero", "mi355x_silero"):
+            return DeviceStreamVAD(**kwargs)
+        raise ValueError(f"unsupported VAD pipeline type: {type} (supported: 'simple', 'silero', 'mi355x_silero')")

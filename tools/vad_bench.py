@@ -13,7 +13,14 @@ folder group, and its accuracy cases.  Synthetic weights (vad.synth_silero_weigh
 Nothing is asserted.  One JSON object on stdout and, with --out, in that file.  --hour-only: three calls on the 3600-s recording
 and nothing else (the command a kernel trace is taken of).
 
+  --stream   the stateful streaming VAD instead (Engine.vad_stream_push), on the context a DeviceStreamVAD backend owns (micro
+             geometry, max_batch 64): for 1, 64, 256 and 1024 open streams the wall time of ONE push of 24 000 samples (the
+             server's 1.5-s chunk) per stream and of one push of 512 samples (one frame) per stream, and beside each the
+             stateless alternative - Engine.vad_probs over the accumulated 3-s buffers of the same streams, what a server
+             without streams runs at every chunk.  2 warm-ups, median / min / max of --repeats.  Records, not gates.
+
     python tools/vad_bench.py [--model large-v3] [--repeats 7] [--out profiles/vad_device.json]
+    python tools/vad_bench.py --stream [--repeats 7] [--out profiles/vad_stream.json]
 """
 from __future__ import annotations
 
@@ -84,14 +91,51 @@ def accuracy(engine) -> dict:
     return out
 
 
+def stream_bench(repeats: int) -> dict:
+    from taiwan_tongues_asr_ce_amd.config import COMPUTE_F32, PRESETS
+    from taiwan_tongues_asr_ce_amd.engine import Engine
+    e = Engine(PRESETS["micro"], COMPUTE_F32, 64)
+    e.load_vad(vad.synth_silero_weights())
+    res = {"tool": "tools/vad_bench.py --stream", "weights": "vad.synth_silero_weights()", "engine": "micro geometry, float32, max_batch 64",
+           "chunk_samples": 24000, "frame_samples": 512, "stateless_buffer_samples": 48000, "streams": {}}
+    base = bursts(2000, 40.0)
+    for n in (1, 64, 256, 1024):
+        buffers = [np.ascontiguousarray(base[(997 * i) % (len(base) - 48000):][:48000]) for i in range(n)]
+        chunks = [b[24000:] for b in buffers]
+        frames = [b[:512] for b in buffers]
+        ids = [e.vad_stream_open() for _ in range(n)]
+        e.vad_stream_push(ids, [b[:24000] for b in buffers])          # the streams hold the first half of their buffers
+        row = {"push_24000": timed(lambda: e.vad_stream_push(ids, chunks), repeats),
+               "push_512": timed(lambda: e.vad_stream_push(ids, frames), repeats),
+               "stateless_vad_probs_48000": timed(lambda: e.vad_probs(buffers), repeats)}
+        row["push_24000"]["frames_per_stream"] = 46.875
+        row["push_24000"]["x_faster_than_stateless"] = round(row["stateless_vad_probs_48000"]["median_s"] / row["push_24000"]["median_s"], 2)
+        row["push_512"]["x_faster_than_stateless"] = round(row["stateless_vad_probs_48000"]["median_s"] / row["push_512"]["median_s"], 2)
+        row["push_24000"]["us_per_stream"] = round(1e6 * row["push_24000"]["median_s"] / n, 1)
+        row["push_512"]["us_per_stream"] = round(1e6 * row["push_512"]["median_s"] / n, 1)
+        res["streams"][str(n)] = row
+        for i in ids:
+            e.vad_stream_close(i)
+    e.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="large-v3")
     ap.add_argument("--compute", default="bfloat16")
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--hour-only", action="store_true")
+    ap.add_argument("--stream", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.stream:
+        text = json.dumps(stream_bench(args.repeats), indent=1)
+        print(text)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     from taiwan_tongues_asr_ce_amd.model import WhisperModel
     warnings.simplefilter("ignore")
     weights = vad.synth_silero_weights()
