@@ -470,6 +470,29 @@ TTASR_API int ttasr_session_align(ttasr_ctx* ctx, int32_t n, const int64_t* ids,
                                   int32_t* out_start_frame_host, float* out_logprob_host, float* out_cost_host,
                                   float* out_weights_host);
 TTASR_API int ttasr_session_release(ttasr_ctx* ctx, int32_t n, const int64_t* ids);
+/* A new search on held clips, with no encoder work (beam sessions; a greedy session refuses it like
+ * ttasr_session_submit_windows).  ids[i] are n DISTINCT held clips.  The group of clip ids[i] starts a new search at the next
+ * step under a new clip id, taken from the session's counter and returned in out_ids[i] (optional); the old id stops being held.
+ * prompt [n][max_prompt], prompt_len, sot_index, max_new, temperature (NULL: all 0), rows and seed mean what they mean in
+ * ttasr_session_submit_windows; the group's mode (BEAM or ROWS), candidate count, page lists and host search state are set up as an
+ * admission sets them, and the rule of option "session_prefill" is applied to the new prompt as at admission (its pass is the
+ * only thing a retry may enqueue).
+ *   - Not touched: the group's cross-KV slot and, under "xkv_fp8" = 2, its e4m3 block and scales.  No log-mel, encoder, cross-KV
+ *     projection, slot copy or quantiser launch is enqueued; ttasr_session_stats out[2], out[3] and out[5] do not move.  Live
+ *     groups and other held clips are untouched.
+ *   - The contract: a retried clip's tokens, sum_logprob and no_speech are bit-identical to the same audio submitted afresh with
+ *     those parameters - a clip that came through ttasr_session_submit against a fresh ttasr_session_submit (a plain clip keeps
+ *     its own mel; rows = beam, temperature 0, sot_index = opts->sot_index are that call's parameters), a window clip against a
+ *     fresh ttasr_session_submit_windows - in f32, bf16 and fp16, with "xkv_fp8" 0 and 2 and "session_prefill" 0 and N.  This
+ *     follows from the session's independence contract above: a clip's cross-KV block does not depend on the pass that encoded
+ *     it, and a search depends only on its group's slot, its parameters and the options.
+ *   - Everything is validated before anything changes, TTASR_E_INVALID: an id that is unknown, not held or listed twice; hold
+ *     mode off; a greedy session; whatever ttasr_session_submit_windows refuses for these arguments; TTASR_TOKEN_DETECT in a
+ *     prompt (the language is known by then).  After a refusal the clips are still held and can be aligned or released.
+ * A session that never calls it enqueues exactly what it did before the call existed. */
+TTASR_API int ttasr_session_retry(ttasr_ctx* ctx, int32_t n, const int64_t* ids, const int32_t* prompt, const int32_t* prompt_len,
+                                  const int32_t* sot_index, const int32_t* max_new, const float* temperature, const int32_t* rows,
+                                  const uint32_t* seed, int64_t* out_ids);
 /* Host-side dynamic time warping over a row-major cost matrix [n_rows][n_cols] (tokens x frames): the monotone path
  * of minimum total cost from (0,0) to (n_rows-1, n_cols-1); out_row / out_col need n_rows + n_cols entries.  Pure CPU
  * (no context): CTranslate2 does this step in C++ too. */

@@ -18,7 +18,7 @@ SYMBOLS = [
     "ttasr_set_option", "ttasr_phase_ms", "ttasr_beam_profile", "ttasr_encoder_kernel_ms", "ttasr_bench_kernel", "ttasr_bench_kernel_signature", "ttasr_sync",
     "ttasr_session_begin", "ttasr_session_begin_beam", "ttasr_session_submit", "ttasr_session_submit_windows", "ttasr_session_poll", "ttasr_session_stats", "ttasr_session_rows", "ttasr_session_end",
     "ttasr_align_batch", "ttasr_session_hold", "ttasr_session_align", "ttasr_session_release", "ttasr_detect_language",
-    "ttasr_session_detect_language", "ttasr_session_poll_lang", "ttasr_session_prefill_stats",
+    "ttasr_session_detect_language", "ttasr_session_poll_lang", "ttasr_session_prefill_stats", "ttasr_session_retry",
     "ttasr_vad_load_tensor", "ttasr_vad_finalize", "ttasr_vad_probs",
     "ttasr_vad_stream_open", "ttasr_vad_stream_reset", "ttasr_vad_stream_close", "ttasr_vad_stream_push",
     "ttasr_ingest_len", "ttasr_ingest_filter", "ttasr_ingest_pcm",
@@ -101,6 +101,7 @@ def load() -> C.CDLL:
     lib.ttasr_session_hold.argtypes = [vp, i32]
     lib.ttasr_session_align.argtypes = [vp, i32, i64p, i32p, i32p, i32, i32p, i32p, i32p, i32, i32, i32p, f32p, f32p, f32p]
     lib.ttasr_session_release.argtypes = [vp, i32, i64p]
+    lib.ttasr_session_retry.argtypes = [vp, i32, i64p, i32p, i32p, i32p, i32p, f32p, i32p, C.POINTER(C.c_uint32), i64p]
     lib.ttasr_dtw.argtypes = [f32p, i32, i32, i32p, i32p, i32p]
     lib.ttasr_set_option.argtypes = [vp, C.c_char_p, i32]
     lib.ttasr_phase_ms.argtypes = [vp, f32p]

@@ -49,6 +49,9 @@ class MI355XWhisperASR(ASRInterface):
         # device_resample=True: a PATH handed to the pipeline is converted and resampled on the device (WhisperModel.transcribe);
         # the streaming chunks of `transcribe` below are 16 kHz PCM already and are not touched by it
         self.device_resample = bool(kwargs.get("device_resample", False))
+        # batched=True: transcribe_path decodes a file through the batched pipeline (WhisperModel.transcribe_batched): its VAD
+        # chunks as independent groups of one session instead of 30-s windows in order
+        self.batched = bool(kwargs.get("batched", False))
         self.text_filter = kwargs.get("text_filter")  # utils.filter_text of the reference, injected by the caller
         # faster_whisper_asr.py:186-198 retries an empty VAD-filtered result without VAD - but it re-opens a temp file it deleted
         # at :179, always lands in its `except: pass` and returns None.  The EFFECTIVE reference behaviour (None for a chunk the
@@ -108,9 +111,13 @@ class MI355XWhisperASR(ASRInterface):
 
     def transcribe_path(self, path: str, **kw):
         """A FILE through the adapter's default options (the reference's file service drives the same model object with paths:
-        file_asr.py:457-465) -> (segments, info); with device_resample=True on the adapter the file is ingested on the device."""
+        file_asr.py:457-465) -> (segments, info); with device_resample=True on the adapter the file is ingested on the device,
+        with batched=True it is decoded by the batched pipeline."""
         opts = dict(self.default_transcribe_kwargs, language="zh")
         opts.update(kw)
+        if self.batched:   # groups carry no previous text: the pipeline has no condition_on_previous_text
+            opts.pop("condition_on_previous_text", None)
+            return self.asr_pipeline.transcribe_batched(path, device_resample=self.device_resample, **opts)
         return self.asr_pipeline.transcribe(path, device_resample=self.device_resample, **opts)
 
     def _vad_is_active(self) -> bool:

@@ -64,15 +64,19 @@ def _probe(path: str) -> str:
 
 
 def transcribe_file(model, audio_file: str, load_audio: Callable = _load_audio, log: Callable = print, segments=None,
-                    language: Optional[str] = TRANSCRIBE_KWARGS["language"], info=None) -> Dict:
+                    language: Optional[str] = TRANSCRIBE_KWARGS["language"], info=None, batched: bool = False) -> Dict:
     """One unit of work → one entry of `detailed_results`.  `segments`: already transcribed (group mode, with its `info`), else
-    runs it.  language=None (`--language auto`): the language is detected, and the entry names it with its probability."""
+    runs it.  language=None (`--language auto`): the language is detected, and the entry names it with its probability.
+    batched: the file goes through the batched pipeline (WhisperModel.transcribe_batched), which has no previous-text option."""
     name = os.path.basename(audio_file)
     out_path = os.path.splitext(audio_file)[0] + "_asr.txt"
     try:
         if isinstance(segments, Exception):
             raise segments
-        if segments is None:
+        if segments is None and batched:
+            kw = {k: v for k, v in TRANSCRIBE_KWARGS.items() if k != "condition_on_previous_text"}
+            segments, info = model.transcribe_batched(load_audio(audio_file), **dict(kw, language=language))
+        elif segments is None:
             segments, info = model.transcribe(load_audio(audio_file), **dict(TRANSCRIBE_KWARGS, language=language))
         text = "".join(seg.text for seg in segments)            # consumes the lazy generator: this is where it runs
         processed = scoring.normalise_transcript(text)
@@ -131,8 +135,11 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
                          group_files: int = 0, pipeline_depth: int = 0, continuous: bool = False,
                          cross_kv_fp8: bool = False, language: Optional[str] = TRANSCRIBE_KWARGS["language"],
                          detect_in_session: bool = False, session_prefill: int = 0, vad_model=None,
-                         device_resample: bool = False) -> Optional[Dict]:
-    """device_resample (`--device-resample`): the grouped paths hand every group's files to the model as paths and the model
+                         device_resample: bool = False, batched: bool = False) -> Optional[Dict]:
+    """batched (`--batched`): every file is decoded by the batched pipeline (WhisperModel.transcribe_batched): its VAD chunks packed
+    into groups of at most 30 s, all groups independent clips of one session.  One file at a time on one engine context; refused
+    together with continuous, which batches across files instead.
+    device_resample (`--device-resample`): the grouped paths hand every group's files to the model as paths and the model
     converts, downmixes and resamples them in one device call per group (WhisperModel.transcribe_many(device_resample=True))
     instead of `load_audio` file by file on this thread; the one-by-one path keeps `load_audio`.
     vad_model (`--vad-model PATH`): the Silero-v5 VAD network for the device (WhisperModel(vad_model=...)); with it the folder
@@ -146,6 +153,8 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
     one admission pass of the session instead of N forced decode steps (WhisperModel.transcribe_many(session_prefill=N))."""
     if session_prefill and not continuous:
         raise ValueError("session_prefill needs continuous=True")
+    if batched and continuous:
+        raise ValueError("batched and continuous exclude each other (one file's groups, or many files' windows, per session)")
     if continuous:
         if int(pipeline_depth or getattr(model, "pipeline_depth", 1)) > 1:
             log("continuous mode runs one session on one engine context: pipeline depth 1")
@@ -163,7 +172,9 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
     results = []
     many = getattr(model, "transcribe_many", None)
     group = group_files if group_files > 0 else max(1, getattr(model, "max_batch", 1) // TRANSCRIBE_KWARGS["beam_size"])
-    if many is None or group < 2 or getattr(model, "vad_speech_prob_fn", None) is not None:
+    if batched:
+        results = [transcribe_file(model, f, load_audio, log, language=language, batched=True) for f in mine]
+    elif many is None or group < 2 or getattr(model, "vad_speech_prob_fn", None) is not None:
         results = [transcribe_file(model, f, load_audio, log, language=language) for f in mine]
     else:
         # MI355X-first: `group` files advance in lock step through one engine pass per window round; every file keeps the
@@ -263,6 +274,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--continuous", action="store_true",
                     help="opt-in: decode each group's windows in one continuous-batching session (finished rows are refilled, "
                          "fallback attempts run in the session); pipeline depth 1.  Same per-file algorithm")
+    ap.add_argument("--batched", action="store_true",
+                    help="opt-in: decode each file through the batched pipeline (VAD chunks packed into groups of at most 30 s, all "
+                         "groups of a file in one session, no previous-text conditioning); not together with --continuous")
     ap.add_argument("--xkv-fp8", action="store_true",
                     help="opt-in serving mode: decode from the e4m3 copy of the cross-attention cache (16-bit compute types; "
                          "WhisperModel(cross_kv_fp8=True)); the summary JSON names the cache that was read")
@@ -291,6 +305,9 @@ def main(argv=None) -> int:
     if args.session_prefill < 0 or (args.session_prefill and not args.continuous):
         print("--session-prefill needs a value >= 0 and --continuous")
         return 1
+    if args.batched and args.continuous:
+        print("--batched and --continuous exclude each other")
+        return 1
     if not os.path.exists(args.folder):
         print(f"folder does not exist: {args.folder}")
         return 1
@@ -303,7 +320,7 @@ def main(argv=None) -> int:
                          max_batch=args.max_batch, pipeline_depth=args.pipeline_depth, continuous=args.continuous,
                          cross_kv_fp8=args.xkv_fp8, language=None if args.language == "auto" else args.language,
                          detect_in_session=args.detect_in_session, session_prefill=args.session_prefill,
-                         vad_model=args.vad_model, device_resample=args.device_resample)
+                         vad_model=args.vad_model, device_resample=args.device_resample, batched=args.batched)
     return 0
 
 

@@ -44,6 +44,12 @@
 // row's identity pages; beam: prefix pages taken once per group and shared by its rows (BeamPages::share_fresh), the partially
 // filled last one split by the copy-on-write of the first private write.  The pass has its own workspace, so it runs with
 // refill_overlap 0 and 1; a clip's bits do not depend on its pass-mates.  With the option at 0 nothing of this is enqueued.
+//
+// A new search on a held clip (ttasr_session_retry; beam sessions): in hold mode a finished clip keeps
+// its group and cross-KV slot, and a retry starts the group over under a new clip id with its own prompt, budget, temperature,
+// rows and seed.  admit() and the retry set the group up through the same start_group(); the retry enqueues no mel, encoder,
+// copy or quantiser work - the slot (and its e4m3 block) is the one the clip's only encoder pass filled - so a retried clip
+// equals the same audio submitted afresh with those parameters.
 #include "engine_ctx.hpp"
 #include <chrono>
 #include <cmath>
@@ -299,6 +305,37 @@ static int run_prefill_passes(ttasr_ctx* c, Session* S, const std::vector<Prefil
   return 0;
 }
 
+// Group g takes clip cl for a new search (admit, and ttasr_session_retry on a held group): mode, candidate count, page lists and
+// host search state; the prefix of a prefilled prompt is collected in pf_seq / pf_pages for the caller's admission pass.  The
+// group's cross-KV slot is the caller's business: admit has just enqueued the copy into it, a retry leaves it as it is.
+static void start_group(ttasr_ctx* c, Session* S, int g, Session::Clip& cl, std::vector<PrefillSeq>& pf_seq,
+                        std::vector<std::vector<int32_t>>& pf_pages) {
+  Session::Group& gr = S->grp[g];
+  const int plen = (int)cl.prompt.size();
+  gr.clip = cl.id; gr.prompt = std::move(cl.prompt); gr.pos = 0; gr.ns = 0.f; gr.finished.clear();
+  // the static search's last sampled position is n_text_ctx - 2: a clip never holds more than n_text_ctx - plen tokens
+  gr.cap = std::min(cl.cap, c->cfg.n_text_ctx - plen);
+  gr.mode = cl.mode; gr.rows = cl.rows; gr.temp = cl.temp; gr.seed = cl.seed; gr.sot = cl.sot;
+  gr.det = cl.det; gr.lang = Session::Lang{};
+  gr.max_cand = std::max(1, (int)std::lround(cl.rows * S->patience));
+  // prompt prefill: the prefix pages are taken ONCE for the group and shared by its rows, as the static search's batched
+  // prefill does; a pool that cannot supply them leaves the clip forced (a per-clip decision from pool state)
+  int start = session_prefill_positions(plen, S->o.no_speech >= 0 ? gr.sot : -1, S->prefill, gr.det >= 0);
+  const int n_pg = (start + kPrefillPageTokens - 1) / kPrefillPageTokens;
+  if (start > 0 && (size_t)n_pg > S->pages.free_pages.size()) start = 0;
+  if (start > 0) {
+    pf_pages.emplace_back(n_pg);
+    for (int q = 0; q < n_pg; ++q) pf_pages.back()[q] = S->pages.share_fresh(g * S->beam, S->beam, q);
+    pf_seq.push_back(PrefillSeq{g, start, gr.prompt.data(), nullptr});
+    gr.pos = start;
+  }
+  for (int b = 0; b < S->beam; ++b) {   // rows beyond the clip's `rows` stay finished
+    const int r = g * S->beam + b;
+    S->seqs[r].clear(); S->sums[r] = 0.0; S->fsums[r] = 0.f;
+    S->row_clip[r] = cl.id; S->cur_tok[r] = gr.det >= 0 ? S->lang_sot : gr.prompt[start]; S->done_rows[r] = b < cl.rows ? 0 : 1;
+  }
+}
+
 // staged clips -> free rows: cross-KV copies, the admission pass of the clips whose prompts are prefilled, and one admit launch
 // on the decode stream
 static int admit(ttasr_ctx* c, Session* S) {
@@ -333,29 +370,7 @@ static int admit(ttasr_ctx* c, Session* S) {
       HIPCHK(c, hipMemcpy2DAsync((char*)c->xkv + (size_t)g * blk, pitch, (const char*)c->xkv_stage + (size_t)j * blk, pitch, blk,
                                  2 * (size_t)c->cfg.dec_layers, hipMemcpyDeviceToDevice, s));
       TRY(quant_pair(j, g));
-      const int plen = (int)cl.prompt.size();
-      gr.clip = cl.id; gr.prompt = std::move(cl.prompt); gr.pos = 0; gr.ns = 0.f; gr.finished.clear();
-      // the static search's last sampled position is n_text_ctx - 2: a clip never holds more than n_text_ctx - plen tokens
-      gr.cap = std::min(cl.cap, c->cfg.n_text_ctx - plen);
-      gr.mode = cl.mode; gr.rows = cl.rows; gr.temp = cl.temp; gr.seed = cl.seed; gr.sot = cl.sot;
-      gr.det = cl.det; gr.lang = Session::Lang{};
-      gr.max_cand = std::max(1, (int)std::lround(cl.rows * S->patience));
-      // prompt prefill: the prefix pages are taken ONCE for the group and shared by its rows, as the static search's batched
-      // prefill does; a pool that cannot supply them leaves the clip forced (a per-clip decision from pool state)
-      int start = session_prefill_positions(plen, S->o.no_speech >= 0 ? gr.sot : -1, S->prefill, gr.det >= 0);
-      const int n_pg = (start + kPrefillPageTokens - 1) / kPrefillPageTokens;
-      if (start > 0 && (size_t)n_pg > S->pages.free_pages.size()) start = 0;
-      if (start > 0) {
-        pf_pages.emplace_back(n_pg);
-        for (int q = 0; q < n_pg; ++q) pf_pages.back()[q] = S->pages.share_fresh(g * S->beam, S->beam, q);
-        pf_seq.push_back(PrefillSeq{g, start, gr.prompt.data(), nullptr});
-        gr.pos = start;
-      }
-      for (int b = 0; b < S->beam; ++b) {   // rows beyond the clip's `rows` stay finished
-        const int r = g * S->beam + b;
-        S->seqs[r].clear(); S->sums[r] = 0.0; S->fsums[r] = 0.f;
-        S->row_clip[r] = cl.id; S->cur_tok[r] = gr.det >= 0 ? S->lang_sot : gr.prompt[start]; S->done_rows[r] = b < cl.rows ? 0 : 1;
-      }
+      start_group(c, S, g, cl, pf_seq, pf_pages);
     }
     TRY(flush_quant_pairs(c, qp, nq));
     for (size_t i = 0; i < pf_seq.size(); ++i) pf_seq[i].pages = pf_pages[i].data();   // (pf_pages no longer grows)
@@ -1011,6 +1026,49 @@ static int session_release(ttasr_ctx* c, int n, const int64_t* ids) {
   return TTASR_OK;
 }
 
+// A new search on held clips (beam session): clip ids[i]'s group starts over at the next step under a new clip id, with its own
+// prompt, budget, temperature, rows and seed, exactly as admit() starts a staged clip - but the group's cross-KV slot (and its
+// e4m3 block and scales) is the one the held clip's encoder pass filled, so no mel, encoder, copy or quantiser work is enqueued.
+// Only the admission pass of option session_prefill runs, for the retried clips whose prompts qualify, as at admission.
+// Everything is validated before anything changes.
+static int session_retry(ttasr_ctx* c, int n, const int64_t* ids, const int32_t* prompt, const int32_t* prompt_len,
+                         const int32_t* sot_index, const int32_t* max_new, const float* temperature, const int32_t* rows,
+                         const uint32_t* seed, int64_t* out_ids) {
+  if (!c) return TTASR_E_INVALID;
+  Session* S = c->sess;
+  if (!S) return fail(c, TTASR_E_INVALID, "no session is open (ttasr_session_begin_beam first)");
+  if (!S->beam) return fail(c, TTASR_E_INVALID, "a retry needs a session opened with ttasr_session_begin_beam");
+  std::vector<int> units;
+  TRY(held_units(c, S, n, ids, units));
+  if (!prompt || !prompt_len || !sot_index || !max_new || !rows || !seed) return fail(c, TTASR_E_INVALID, "NULL argument");
+  std::vector<Session::Clip> cls(n);
+  for (int i = 0; i < n; ++i) {
+    if (rows[i] < 1 || rows[i] > S->beam) return fail(c, TTASR_E_INVALID, "retry %d: rows %d outside [1, %d]", i, rows[i], S->beam);
+    if (temperature && !(std::isfinite(temperature[i]) && temperature[i] >= 0.f))
+      return fail(c, TTASR_E_INVALID, "retry %d: temperature %g must be finite and >= 0", i, temperature[i]);
+    Session::Clip& cl = cls[i];
+    TRY(init_clip(c, S, i, prompt, prompt_len, S->o.no_speech >= 0 ? &sot_index[i] : nullptr, max_new, cl));
+    if (cl.det >= 0) return fail(c, TTASR_E_INVALID, "retry %d: a retried clip's language is known (placeholder at %d)", i, cl.det);
+    cl.sot = sot_index[i];
+    cl.temp = temperature ? temperature[i] : 0.f;
+    cl.rows = rows[i];
+    cl.seed = seed[i];
+    cl.mode = (cl.temp == 0.f && cl.rows > 1) ? Session::BEAM : Session::ROWS;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<PrefillSeq> pf_seq;
+  std::vector<std::vector<int32_t>> pf_pages;
+  for (int i = 0; i < n; ++i) {
+    cls[i].id = S->next_id++;
+    if (out_ids) out_ids[i] = cls[i].id;
+    S->grp[units[i]].held = -1;
+    start_group(c, S, units[i], cls[i], pf_seq, pf_pages);
+  }
+  for (size_t i = 0; i < pf_seq.size(); ++i) pf_seq[i].pages = pf_pages[i].data();   // (pf_pages no longer grows)
+  TRY(run_prefill_passes(c, S, pf_seq));
+  return TTASR_OK;
+}
+
 // The batched alignment pass (engine_align.hip) over held clips: sequence i reads the cross-KV slot of clip ids[i]'s unit and
 // keeps its self-attention K/V in pages no live row uses - the held row's own (greedy: a row owns its pages for good) or free
 // pool pages (beam: a finished group's page lists are back in the pool, and a held group accounts for beam x pages_per_seq of
@@ -1164,6 +1222,14 @@ int ttasr_session_align(ttasr_ctx* c, int32_t n, const int64_t* ids, const int32
 
 int ttasr_session_release(ttasr_ctx* c, int32_t n, const int64_t* ids) {
   return guarded(c, [&]() -> int { return session_release(c, n, ids); });
+}
+
+int ttasr_session_retry(ttasr_ctx* c, int32_t n, const int64_t* ids, const int32_t* prompt, const int32_t* prompt_len,
+                        const int32_t* sot_index, const int32_t* max_new, const float* temperature, const int32_t* rows,
+                        const uint32_t* seed, int64_t* out_ids) {
+  return guarded(c, [&]() -> int {
+    return session_retry(c, n, ids, prompt, prompt_len, sot_index, max_new, temperature, rows, seed, out_ids);
+  });
 }
 
 int ttasr_session_end(ttasr_ctx* c) {

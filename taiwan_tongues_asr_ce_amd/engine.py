@@ -946,6 +946,61 @@ class Session:
         self.engine._check(self.engine.lib.ttasr_session_release(self.engine.h, len(a), a.ctypes.data_as(C.POINTER(C.c_int64))),
                            "session_release")
 
+    def retry(self, ids: Sequence[int], prompts: Sequence[Sequence[int]], sot_index: Sequence[int],
+              max_new: Optional[Sequence[int]] = None, temperature: Optional[Sequence[float]] = None,
+              rows: Optional[Sequence[int]] = None, seed: Optional[Sequence[int]] = None) -> List[int]:
+        """A new search on held clips with no encoder work (beam sessions only; ttasr_session_retry): the group of held clip
+        ids[i] starts over under a new clip id (returned; the old id stops being held) with its own prompt,
+        <|startoftranscript|> index, budget (default opts.max_new_tokens), temperature (default 0), rows (default: the
+        session's beam width) and seed (default 0), all as in submit_windows.  The clip's cross-KV slot is reused as it is.
+        The language placeholder is refused: the language is known by then.  Shapes and ranges are checked here before the
+        library is called."""
+        if self.open and not self.beam:
+            raise ValueError("a retry needs a beam session (Engine.session(beam=..., patience=...))")
+        a = self._ids(ids)
+        n = len(a)
+        if any(len(x) != n for x in (prompts, sot_index)):
+            raise ValueError(f"need one prompt and sot index per clip id ({n}), got prompts {len(prompts)}, sot_index {len(sot_index)}")
+
+        def per_clip(v, default, dtype, name):
+            b = np.full(n, default, dtype=dtype) if v is None else np.ascontiguousarray(v, dtype=dtype)
+            if b.shape != (n,):
+                raise ValueError(f"{name} needs one entry per clip id ({n}), got shape {b.shape}")
+            return b
+        caps = per_clip(max_new, self.max_new_tokens, np.int32, "max_new")
+        if caps.min() < 1 or caps.max() > self.max_new_tokens:
+            raise ValueError(f"max_new entries must lie in [1, {self.max_new_tokens}]")
+        temps = per_clip(temperature, 0.0, np.float32, "temperature")
+        if not (np.all(np.isfinite(temps)) and temps.min() >= 0):
+            raise ValueError("temperatures must be finite and >= 0")
+        rw = per_clip(rows, self.beam, np.int32, "rows")
+        if rw.min() < 1 or rw.max() > self.beam:
+            raise ValueError(f"rows entries must lie in [1, {self.beam}] (the session's group width)")
+        sd = per_clip(seed, 0, np.int64, "seed")
+        if sd.min() < 0 or sd.max() > 0xFFFFFFFF:
+            raise ValueError("seeds must lie in [0, 2**32)")
+        sd = sd.astype(np.uint32)
+        so = per_clip(sot_index, 0, np.int32, "sot_index")
+        pr = np.zeros((n, self.max_prompt), dtype=np.int32)
+        pl = np.zeros(n, dtype=np.int32)
+        for i, p in enumerate(prompts):
+            if not 1 <= len(p) <= self.max_prompt:
+                raise ValueError(f"clip {i}: prompt length {len(p)} outside [1, {self.max_prompt}]")
+            if not 0 <= so[i] < len(p):
+                raise ValueError(f"clip {i}: sot_index {so[i]} outside the {len(p)}-token prompt")
+            if any(int(t) == self.DETECT for t in p):
+                raise ValueError(f"clip {i}: a retried clip's prompt cannot hold the language placeholder")
+            pr[i, :len(p)] = p
+            pl[i] = len(p)
+        out = np.zeros(n, dtype=np.int64)
+        i32p, i64p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_float)
+        self.engine._check(self.engine.lib.ttasr_session_retry(
+            self.engine.h, n, a.ctypes.data_as(i64p), pr.ctypes.data_as(i32p), pl.ctypes.data_as(i32p), so.ctypes.data_as(i32p),
+            caps.ctypes.data_as(i32p), temps.ctypes.data_as(f32p), rw.ctypes.data_as(i32p),
+            sd.ctypes.data_as(C.POINTER(C.c_uint32)), out.ctypes.data_as(i64p)), "session_retry")
+        self.pending += n
+        return out.tolist()
+
     def rows(self) -> Dict[str, np.ndarray]:
         """The batch's rows now (ttasr_session_rows): position, finished flag (1 = finished or free), clip id (-1 = free)."""
         B = self.engine.max_batch

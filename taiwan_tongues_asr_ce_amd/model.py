@@ -58,6 +58,10 @@ class TranscriptionInfo:
     vad_options: Optional[Dict] = None
     # transcribe_many(continuous=True, multilingual=True): the language found for every window that was decoded, in file order
     window_languages: Optional[List[str]] = None
+    # BatchedInferencePipeline: one entry per group - start / end (samples of the recording), its speech pieces and its attempts
+    # as (temperature, avg_logprob, no_speech_prob, compression_ratio); and Session.stats() of the run plus "retries"
+    chunks: Optional[List[Dict]] = None
+    session: Optional[Dict[str, float]] = None
 
 
 _COMPUTE_ALIASES = {
@@ -706,6 +710,13 @@ class WhisperModel:
         if chunks is not None:
             segments = vad.restore_speech_timestamps(segments, chunks)
         return segments, info
+
+    def transcribe_batched(self, audio: Union[str, np.ndarray], **kw) -> Tuple[Iterator[Segment], TranscriptionInfo]:
+        """One long recording through faster-whisper's batched form (batched.BatchedInferencePipeline(self).transcribe, which
+        documents the keywords): VAD chunks packed into groups of at most one window, every group an independent clip of one
+        continuous-batching beam session, fallbacks retried on the held cross-KV."""
+        from .batched import BatchedInferencePipeline
+        return BatchedInferencePipeline(self).transcribe(audio, **kw)
 
     # -- pieces of faster-whisper's generate_segments / generate_with_fallback, shared by the single-file loop and by
     #    transcribe_many (several files in lock step through one engine pass) -------------------------------------

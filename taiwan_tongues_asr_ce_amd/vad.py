@@ -304,6 +304,33 @@ def collect_chunks(audio: np.ndarray, chunks: Sequence[Dict[str, int]]) -> np.nd
     return np.concatenate([audio[c["start"]: c["end"]] for c in chunks]).astype(np.float32, copy=False)
 
 
+def merge_chunks(chunks: Sequence[Dict[str, int]], max_samples: int) -> List[Dict]:
+    """Packs speech chunks greedily into groups of at most max_samples (faster-whisper's merge_segments for its batched
+    pipeline; UNPINNED like the rest of this module): a chunk joins the open group while chunk.end - group.start <= max_samples,
+    otherwise it opens the next group; a chunk longer than max_samples is first cut into pieces of max_samples.
+    -> [{'start', 'end', 'segments': [{'start', 'end'}, ...]}] in chunk order; a group's audio is the concatenation of its
+    segments (collect_chunks), at most end - start <= max_samples samples, and its time line a SpeechTimestampsMap over them."""
+    max_samples = int(max_samples)
+    if max_samples < 1:
+        raise ValueError(f"max_samples {max_samples} must be >= 1")
+    pieces: List[Dict[str, int]] = []
+    for c in chunks:
+        a, b = int(c["start"]), int(c["end"])
+        while b - a > max_samples:
+            pieces.append(dict(start=a, end=a + max_samples))
+            a += max_samples
+        if b > a:
+            pieces.append(dict(start=a, end=b))
+    groups: List[Dict] = []
+    for c in pieces:
+        if groups and c["end"] - groups[-1]["start"] <= max_samples:
+            groups[-1]["end"] = c["end"]
+            groups[-1]["segments"].append(c)
+        else:
+            groups.append(dict(start=c["start"], end=c["end"], segments=[c]))
+    return groups
+
+
 class SpeechTimestampsMap:
     """Maps a time on the concatenated-speech axis back to the original recording."""
 
