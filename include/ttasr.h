@@ -170,6 +170,19 @@ TTASR_API int ttasr_get_cross_kv_fp8(ttasr_ctx* ctx, int32_t layer, int32_t whic
  * Refused in an open session and without resident encoder state; search state and captured step graphs are not touched. */
 TTASR_API int ttasr_cross_attn_probe(ttasr_ctx* ctx, int32_t layer, int32_t n_rows, int32_t kv_div, const float* q_host, int32_t n_slab,
                                      const int32_t* done_host, float* out_host, char* sig_buf, int32_t sig_len);
+/* The cross-attention of the PACKED alignment pass (option "align_packed"; tests/test_gpu_align_packed.py)
+ * of `layer`, once, on caller-supplied queries: n_seq sequences packed one after the other, sequence i with lens_host[i] >= 1 rows
+ * (at most 512 rows in all) reading the resident cross-KV of clip slots_host[i].  q_host: f32 [rows][d_model], cast to the engine
+ * type and used as given.  head_pair_host [n_heads]: -1, or the index in [0, n_pairs) of the map this head writes (every index
+ * exactly once).  No weight of the layer is involved.  out_host: f32 [rows][d_model], the attention output;
+ * out_maps_host: f32 [n_pairs][rows][T], every selected head's softmax over the T frames of the audio window, per packed row
+ * (may be NULL when n_pairs = 0).  16-bit engines run the MFMA kernel of the admission pass - its map-writing instantiation when
+ * a head is selected - and the finishing kernel; the f32 engine and option "generic_kernels" run the per-row kernel: what
+ * ttasr_session_align launches under "align_packed" = 1.  Refused in an open session and without resident encoder state; search
+ * state and captured step graphs are not touched. */
+TTASR_API int ttasr_align_attn_probe(ttasr_ctx* ctx, int32_t layer, int32_t n_seq, const int32_t* lens_host, const int32_t* slots_host,
+                                     const float* q_host, const int32_t* head_pair_host, int32_t n_pairs, float* out_host,
+                                     float* out_maps_host);
 
 /* Short-window option (opt-in, a behavioural change versus Whisper's fixed 30-s training window, the
  * same trade whisper.cpp's `audio_ctx` makes): subsequent log_mel / encode / generate calls use only the first n_ctx
@@ -460,6 +473,13 @@ TTASR_API int ttasr_align_batch(ttasr_ctx* ctx, int32_t n, const int32_t* clip_h
  *   held clip.  A session that never calls it behaves as before.
  * ttasr_session_align: ttasr_align_batch (same arguments, checks, outputs and scratch) for n DISTINCT held clips ids[i],
  *   each with its own cross-KV slot, in self-attention pages no live row uses; on success the clips are released.
+ *   With option "align_packed" = 1 (read by this call) the pass is the PACKED one: the sequences' real positions, no padding,
+ *   in the admission pass's workspace (allocated by the first call that needs it; more than 512 rows: several passes by whole
+ *   sequences) and its one fixed GEMM family.  Arguments, checks, refusals, the release and the output layout are the same
+ *   (positions past a sequence's end are 0 in every output).  Contract: a held clip's start frames, log-probs, cost matrix
+ *   and maps are the same bits whether it is aligned alone or with other clips, in any order, in one call or several, in one
+ *   pass or cut over two (tests/test_gpu_align_packed.py; the padded pass chooses its GEMM family from the row count of the
+ *   whole call and does not promise this).
  * ttasr_session_release: frees held clips without aligning them.
  * An unknown id, an id that is not held, an id listed twice and any of the two calls with hold mode off are TTASR_E_INVALID,
  * and nothing happens.  ttasr_session_end releases everything. */
@@ -655,11 +675,13 @@ TTASR_API int ttasr_ingest_pcm(ttasr_ctx* ctx, int32_t n, const void* const* raw
  * "session_prefill" [0] (0 ... n_text_ctx - 2; read by ttasr_session_begin / ttasr_session_begin_beam) N > 0: a clip with at least
  * N prefillable prompt positions gets them from an admission pass instead of N forced decode steps (see "prompt prefill at
  * admission" above);
+ * "align_packed" [0] (read by ttasr_session_align at call time) 1: the alignment pass over held clips runs packed and
+ * pass-mate-independent (see ttasr_session_align); 0: the padded pass, unchanged;
  * "ingest_chunk" [0] (0 ... 2^30) input frames per chunk of ttasr_ingest_pcm, 0 = as many as the staging slots hold (results do
  * not depend on it, bit for bit: tests put chunk boundaries inside small inputs with it); "ingest_timing" [0] 1: ttasr_ingest_pcm
  * waits for every copy and kernel before it enqueues the next and leaves the host-clock split of the call in ttasr_phase_ms
  * (measurement only: the waits cost the overlap);
- * Drops the captured decode graphs (except "enc_kernel_timing", "refill_overlap", "session_prefill", "ingest_chunk" and "ingest_timing").  Unknown key or value out of range: TTASR_E_INVALID. */
+ * Drops the captured decode graphs (except "enc_kernel_timing", "refill_overlap", "session_prefill", "align_packed", "ingest_chunk" and "ingest_timing").  Unknown key or value out of range: TTASR_E_INVALID. */
 TTASR_API int ttasr_set_option(ttasr_ctx* ctx, const char* key, int32_t value);
 
 /* ---- measurement --------------------------------------------------------------------------------- */

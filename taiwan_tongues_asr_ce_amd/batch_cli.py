@@ -64,8 +64,10 @@ def _probe(path: str) -> str:
 
 
 def transcribe_file(model, audio_file: str, load_audio: Callable = _load_audio, log: Callable = print, segments=None,
-                    language: Optional[str] = TRANSCRIBE_KWARGS["language"], info=None, batched: bool = False) -> Dict:
-    """One unit of work → one entry of `detailed_results`.  `segments`: already transcribed (group mode, with its `info`), else
+                    language: Optional[str] = TRANSCRIBE_KWARGS["language"], info=None, batched: bool = False,
+                    word_timestamps: bool = False) -> Dict:
+    """One unit of work → one entry of `detailed_results`.  word_timestamps: the segments carry words (a file transcribed here
+    is transcribed with them); they are written to `<name>_words.json` beside `<name>_asr.txt`.  `segments`: already transcribed (group mode, with its `info`), else
     runs it.  language=None (`--language auto`): the language is detected, and the entry names it with its probability.
     batched: the file goes through the batched pipeline (WhisperModel.transcribe_batched), which has no previous-text option."""
     name = os.path.basename(audio_file)
@@ -77,8 +79,15 @@ def transcribe_file(model, audio_file: str, load_audio: Callable = _load_audio, 
             kw = {k: v for k, v in TRANSCRIBE_KWARGS.items() if k != "condition_on_previous_text"}
             segments, info = model.transcribe_batched(load_audio(audio_file), **dict(kw, language=language))
         elif segments is None:
-            segments, info = model.transcribe(load_audio(audio_file), **dict(TRANSCRIBE_KWARGS, language=language))
-        text = "".join(seg.text for seg in segments)            # consumes the lazy generator: this is where it runs
+            extra = dict(word_timestamps=True) if word_timestamps else {}
+            segments, info = model.transcribe(load_audio(audio_file), **dict(TRANSCRIBE_KWARGS, language=language, **extra))
+        segments = list(segments)                               # consumes the lazy generator: this is where it runs
+        text = "".join(seg.text for seg in segments)
+        if word_timestamps:
+            with open(os.path.splitext(audio_file)[0] + "_words.json", "w", encoding="utf-8") as f:
+                json.dump([dict(id=seg.id, start=seg.start, end=seg.end, text=seg.text,
+                                words=[dict(word=w.word, start=w.start, end=w.end, probability=float(w.probability))
+                                       for w in (seg.words or [])]) for seg in segments], f, ensure_ascii=False, indent=1)
         processed = scoring.normalise_transcript(text)
         with open(out_path, "w", encoding="utf-8") as f:
             f.write(processed)
@@ -135,8 +144,12 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
                          group_files: int = 0, pipeline_depth: int = 0, continuous: bool = False,
                          cross_kv_fp8: bool = False, language: Optional[str] = TRANSCRIBE_KWARGS["language"],
                          detect_in_session: bool = False, session_prefill: int = 0, vad_model=None,
-                         device_resample: bool = False, batched: bool = False) -> Optional[Dict]:
-    """batched (`--batched`): every file is decoded by the batched pipeline (WhisperModel.transcribe_batched): its VAD chunks packed
+                         device_resample: bool = False, batched: bool = False, word_timestamps: bool = False) -> Optional[Dict]:
+    """word_timestamps (`--word-timestamps`, with the lock-step form or continuous; not with batched): every file's segments are
+    transcribed with words (continuous: one Session.align call per poll through the packed, pass-mate-independent alignment
+    pass, WhisperModel.transcribe_many(continuous=True, word_timestamps=True)) and written to `<name>_words.json` beside
+    `<name>_asr.txt`; texts and scores do not change.
+    batched (`--batched`): every file is decoded by the batched pipeline (WhisperModel.transcribe_batched): its VAD chunks packed
     into groups of at most 30 s, all groups independent clips of one session.  One file at a time on one engine context; refused
     together with continuous, which batches across files instead.
     device_resample (`--device-resample`): the grouped paths hand every group's files to the model as paths and the model
@@ -155,6 +168,8 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
         raise ValueError("session_prefill needs continuous=True")
     if batched and continuous:
         raise ValueError("batched and continuous exclude each other (one file's groups, or many files' windows, per session)")
+    if batched and word_timestamps:
+        raise ValueError("word_timestamps goes with the lock-step form or continuous, not with batched")
     if continuous:
         if int(pipeline_depth or getattr(model, "pipeline_depth", 1)) > 1:
             log("continuous mode runs one session on one engine context: pipeline depth 1")
@@ -175,7 +190,7 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
     if batched:
         results = [transcribe_file(model, f, load_audio, log, language=language, batched=True) for f in mine]
     elif many is None or group < 2 or getattr(model, "vad_speech_prob_fn", None) is not None:
-        results = [transcribe_file(model, f, load_audio, log, language=language) for f in mine]
+        results = [transcribe_file(model, f, load_audio, log, language=language, word_timestamps=word_timestamps) for f in mine]
     else:
         # MI355X-first: `group` files advance in lock step through one engine pass per window round; every file keeps the
         # sequential algorithm (own seek / prompt / fallback), so the outputs equal the one-by-one run
@@ -193,6 +208,8 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
                 kw["session_prefill"] = int(session_prefill)
         if device_resample:
             kw["device_resample"] = True
+        if word_timestamps:
+            kw["word_timestamps"] = True
         depth0 = max(1, int(pipeline_depth or getattr(model, "pipeline_depth", 1)))
         if group_files <= 0 and depth0 > 1 and len(mine) < group * depth0:
             group = max(1, -(-len(mine) // depth0))            # few files: one group per context rather than one big group and an idle lane
@@ -234,7 +251,8 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
                 except Exception as e:  # engine-level failure of the group: fall back to one by one
                     log(f"group transcription failed ({e}); retrying file by file")
                     pairs = [(None, None)] * len(part)
-                results.extend(transcribe_file(model, f, load_audio, log, segments=sg, language=language, info=nfo)
+                results.extend(transcribe_file(model, f, load_audio, log, segments=sg, language=language, info=nfo,
+                                               word_timestamps=word_timestamps)
                                for f, (sg, nfo) in zip(part, pairs))
     if world > 1:
         import torch.distributed as dist
@@ -293,6 +311,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="opt-in, with --continuous: a window whose prompt has at least N prefillable positions (previous text up to "
                          "<|startoftranscript|>) gets them from one admission pass of the session instead of N forced decode steps; "
                          "0 = off")
+    ap.add_argument("--word-timestamps", action="store_true",
+                    help="opt-in: word-level timestamps; every file's segments with their words are written to <name>_words.json "
+                         "beside <name>_asr.txt.  With --continuous the windows that settle in one poll are aligned in one device pass "
+                         "whose result for a file does not depend on the other files; not together with --batched")
     ap.add_argument("--device-resample", action="store_true",
                     help="opt-in: convert, downmix and resample each group's files in one device call instead of file by file on "
                          "the host (RIFF/WAVE of any PCM / float format, other containers through soundfile; rates the device "
@@ -308,6 +330,9 @@ def main(argv=None) -> int:
     if args.batched and args.continuous:
         print("--batched and --continuous exclude each other")
         return 1
+    if args.batched and args.word_timestamps:
+        print("--word-timestamps goes with the lock-step form or --continuous, not with --batched")
+        return 1
     if not os.path.exists(args.folder):
         print(f"folder does not exist: {args.folder}")
         return 1
@@ -320,7 +345,8 @@ def main(argv=None) -> int:
                          max_batch=args.max_batch, pipeline_depth=args.pipeline_depth, continuous=args.continuous,
                          cross_kv_fp8=args.xkv_fp8, language=None if args.language == "auto" else args.language,
                          detect_in_session=args.detect_in_session, session_prefill=args.session_prefill,
-                         vad_model=args.vad_model, device_resample=args.device_resample, batched=args.batched)
+                         vad_model=args.vad_model, device_resample=args.device_resample, batched=args.batched,
+                         word_timestamps=args.word_timestamps)
     return 0
 
 

@@ -29,16 +29,20 @@ constexpr size_t kDtwLdsTraceBytes = 150 * 1024;   // the CU has 160 KiB; three 
 
 // probs [n_pairs][n_seq * npos][Tk] -> mean and std (std 0 -> 1) over each sequence's token rows, per pair and frame:
 // stats [n_seq][n_pairs][2][Tk]
-void launch_align_stats(const float* probs, const AlignSeq* seq, int n_seq, int npos, int n_pairs, int Tk, float* stats, hipStream_t s);
+// seq_row != nullptr (the packed pass, here and below): sequence i starts at packed row seq_row[i] of the n_rows rows instead of
+// i * npos - in probs, in cost and in start
+void launch_align_stats(const float* probs, const AlignSeq* seq, int n_seq, int npos, int n_pairs, int Tk, float* stats, hipStream_t s,
+                        const int32_t* seq_row = nullptr, int n_rows = 0);
 // normalise, median of `width` along time (reflected edges), mean over pairs, negate: cost [n_seq][npos][Tk], C_i = rows x frames
 void launch_align_cost(const float* probs, const float* stats, const AlignSeq* seq, int n_seq, int npos, int max_rows, int n_pairs, int Tk,
-                       int width, float* cost, hipStream_t s);
+                       int width, float* cost, hipStream_t s, const int32_t* seq_row = nullptr, int n_rows = 0);
 // words of 2-bit trace one sequence needs
 __host__ __device__ inline size_t dtw_trace_words(int rows, int frames) { return (size_t)rows * ((frames + 15) / 16); }
 // one workgroup per sequence; start [n_seq][npos]: the frame at which the path first enters each row.  A trace beyond
 // kDtwLdsTraceBytes goes to trace_spill [n_seq][spill_words]
 void launch_align_dtw(const float* cost, const AlignSeq* seq, int n_seq, int npos, int max_rows, int Tk, size_t lds_trace_words,
-                      uint32_t* trace_spill, size_t spill_words, int32_t* start, hipStream_t s, int device);
+                      uint32_t* trace_spill, size_t spill_words, int32_t* start, hipStream_t s, int device,
+                      const int32_t* seq_row = nullptr);
 
 
 }  // namespace ttasr_detail

@@ -452,6 +452,14 @@ template <typename T> void launch_prefill_self_attn(const PrefillPass& P, const 
 // ragged MFMA cross-attention (16-bit): q, out [n_rows][d]; K, V = the layer's cross-KV [slot][H][Tk][64], Tk even and >= 4
 template <typename T16>
 void launch_prefill_cross_attn(const PrefillPass& P, const T16* q, const T16* K, const T16* V, T16* out, int H, int Tk, hipStream_t s);
+// The same kernel with the alignment heads' maps (the packed alignment pass, option align_packed): sel [H] (device) = pair index of
+// the layer's head or -1; a selected head stores its score rows into maps [n_pairs][n_rows][Tk] and {reference, sum} into stat
+// [n_pairs][n_rows][2]; launch_prefill_maps_finish then makes every stored row the softmax over its Tk frames, in place.
+struct PrefillMaps { const int32_t* sel; float* maps; float* stat; int n_rows; };
+template <typename T16>
+void launch_prefill_cross_attn_maps(const PrefillPass& P, const T16* q, const T16* K, const T16* V, T16* out, int H, int Tk,
+                                    const PrefillMaps& mp, hipStream_t s);
+void launch_prefill_maps_finish(float* maps, const float* stat, int n_pairs, int n_rows, int Tk, hipStream_t s);
 template <typename T>
 void launch_copy_pages(T* pool, const int32_t* pairs_dev, int n_pairs, int n_layers, int H, int64_t layer_elems, hipStream_t s);
 template <typename T>

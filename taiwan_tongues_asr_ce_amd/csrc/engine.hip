@@ -446,6 +446,79 @@ int ttasr_cross_attn_probe(ttasr_ctx* c, int32_t layer, int32_t n_rows, int32_t 
   });
 }
 
+int ttasr_align_attn_probe(ttasr_ctx* c, int32_t layer, int32_t n_seq, const int32_t* lens, const int32_t* slots, const float* q,
+                           const int32_t* head_pair, int32_t n_pairs, float* out, float* out_maps) {
+  return guarded(c, [&]() -> int {
+  TRY(check_ready(c, 1));   // refused in an open session
+  if (layer < 0 || layer >= c->cfg.dec_layers || !lens || !slots || !q || !head_pair || !out || n_pairs < 0 || n_pairs > c->H ||
+      (n_pairs > 0 && !out_maps))
+    return fail(c, TTASR_E_INVALID, "bad arguments");
+  if (n_seq < 1 || n_seq > kPrefillRowCap) return fail(c, TTASR_E_INVALID, "n_seq %d outside [1, %d]", n_seq, kPrefillRowCap);
+  if (c->T > 6 * 256) return fail(c, TTASR_E_INVALID, "audio window %d > 1536 frames", c->T);
+  int R = 0, ni = 0;
+  for (int i = 0; i < n_seq; ++i) {
+    if (lens[i] < 1 || lens[i] > kPrefillRowCap || (R += lens[i]) > kPrefillRowCap)
+      return fail(c, TTASR_E_INVALID, "sequence %d: length %d, more than %d rows in all", i, lens[i], kPrefillRowCap);
+    if (slots[i] < 0 || slots[i] >= c->B_enc)
+      return fail(c, TTASR_E_INVALID, "sequence %d: slot %d but the resident encoder state holds %d clips", i, slots[i], c->B_enc);
+    ni += prefill_items_of(lens[i]);
+  }
+  std::vector<char> seen(n_pairs > 0 ? n_pairs : 1, 0);
+  int n_sel = 0;
+  for (int h = 0; h < c->H; ++h) {
+    const int p = head_pair[h];
+    if (p == -1) continue;
+    if (p < 0 || p >= n_pairs || seen[p]) return fail(c, TTASR_E_INVALID, "head %d: pair %d outside [0, %d) or listed twice", h, p, n_pairs);
+    seen[p] = 1; ++n_sel;
+  }
+  if (n_sel != n_pairs) return fail(c, TTASR_E_INVALID, "%d heads selected but n_pairs = %d", n_sel, n_pairs);
+  TRY(prefill_workspace(c));
+  hipStream_t s = c->stream;
+  const int d = c->d, pps = c->pages_per_seq, LH = c->cfg.dec_layers * c->H, T_ = c->T;
+  // host image: rows [R][3] | slots [R] | seqs [n_seq][3 + pps] | items [ni][3] | sel [LH]; device block: image | maps | stat
+  const size_t w_slots = (size_t)R * 3, w_seqs = w_slots + R, w_items = w_seqs + (size_t)n_seq * (3 + pps), w_sel = w_items + (size_t)ni * 3,
+               in_words = w_sel + LH;
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t o_maps = up(in_words * 4), o_stat = o_maps + up((size_t)n_pairs * R * T_ * 4), total = o_stat + up((size_t)n_pairs * R * 8);
+  if (total > c->align_dev_bytes) {
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (c->align_dev) hipFree(c->align_dev);
+    c->align_dev = nullptr; c->align_dev_bytes = 0;
+    const hipError_t e = hipMalloc(&c->align_dev, total);
+    if (e != hipSuccess) { c->align_dev = nullptr; (void)hipGetLastError(); return fail(c, TTASR_E_NOMEM, "probe scratch (%zu bytes): %s", total, hipGetErrorString(e)); }
+    c->align_dev_bytes = total;
+  }
+  std::vector<int32_t> in(in_words, 0), zeros((size_t)std::max(kPrefillRowCap, pps), 0);
+  std::vector<PrefillSeq> sq(n_seq);
+  for (int i = 0; i < n_seq; ++i) sq[i] = PrefillSeq{slots[i], lens[i], zeros.data(), zeros.data()};   // tokens and pages: not read here
+  prefill_build_tables(sq.data(), n_seq, pps, in.data(), in.data() + w_slots, in.data() + w_seqs, in.data() + w_items);
+  int32_t* h_sel = in.data() + w_sel;
+  for (int i = 0; i < LH; ++i) h_sel[i] = -1;
+  for (int h = 0; h < c->H; ++h) h_sel[(size_t)layer * c->H + h] = head_pair[h];
+  char* base = (char*)c->align_dev;
+  const int32_t* dw = (const int32_t*)base;
+  float* d_maps = (float*)(base + o_maps);
+  HIPCHK(c, hipMemcpyAsync(base, in.data(), in_words * 4, hipMemcpyHostToDevice, s));
+  if (c->lowp) {
+    HIPCHK(c, hipMemcpyAsync(c->pf_x, q, (size_t)R * d * 4, hipMemcpyHostToDevice, s));
+    TT_DISPATCH(c, launch_cast<T>(c->pf_x, (T*)c->pf_qkv, (int64_t)R * d, s));
+  } else {
+    HIPCHK(c, hipMemcpyAsync(c->pf_qkv, q, (size_t)R * d * 4, hipMemcpyHostToDevice, s));
+  }
+  HIPCHK(c, hipMemsetAsync(c->pf_att, 0, (size_t)R * d * c->esz, s));
+  const PrefillPass P{dw, dw + w_slots, dw + w_seqs, dw + w_items, R, n_seq, ni, 3 + pps};
+  const PackedAlign al{dw + w_sel, h_sel, d_maps, (float*)(base + o_stat), n_pairs};
+  sched_align_attn(c, layer, P, c->pf_qkv, c->pf_att, al);
+  if (c->lowp) { TT_DISPATCH(c, launch_uncast<T>((const T*)c->pf_att, c->pf_x, (int64_t)R * d, s));
+                 HIPCHK(c, hipMemcpyAsync(out, c->pf_x, (size_t)R * d * 4, hipMemcpyDeviceToHost, s)); }
+  else HIPCHK(c, hipMemcpyAsync(out, c->pf_att, (size_t)R * d * 4, hipMemcpyDeviceToHost, s));
+  if (n_pairs > 0) HIPCHK(c, hipMemcpyAsync(out_maps, d_maps, (size_t)n_pairs * R * T_ * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));   // `in` is a stack temporary; the results are on the host
+  HIPCHK(c, hipGetLastError());
+  return TTASR_OK;
+  });
+}
+
 int ttasr_decode_reset(ttasr_ctx* c, int32_t B) {
   return guarded(c, [&]() -> int {
   TRY(check_ready(c, B));

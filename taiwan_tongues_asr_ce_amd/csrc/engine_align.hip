@@ -136,6 +136,118 @@ int align_batch_run(ttasr_ctx* c, const AlignBatch& a, const int32_t* slot, cons
   return TTASR_OK;
 }
 
+// The same call through the PACKED pass (option align_packed): the sequences' real positions are the
+// packed rows of admission passes (prefill_tables.hpp; more than kPrefillRowCap rows: several passes by whole sequences), every
+// pass runs sched_admit_prefill with the alignment extras out of the context's pf_* workspace and is finished - log-probs, cost
+// matrices, DTW, results on the host - before the next one starts, so the scratch block holds one pass.  Every kernel of a pass
+// works on a row or on a sequence of its own and takes its form from context constants: a sequence's outputs are the same bits
+// whatever else the call or the pass holds.  Outputs keep the [n][max_tokens] layout; positions past a sequence's end are 0.
+int align_packed_run(ttasr_ctx* c, const AlignBatch& a, const int32_t* slot, const int32_t* pages) {
+  const int n = a.n, npos = a.max_tokens, T_ = c->T, pps = c->pages_per_seq, LH = c->cfg.dec_layers * c->H, np = a.n_pairs;
+  hipStream_t s = c->stream;
+  TRY(prefill_workspace(c));
+  std::vector<PrefillSeq> sq(n);
+  std::vector<int> len(n);
+  for (int i = 0; i < n; ++i) {
+    sq[i] = PrefillSeq{slot[i], a.n_tokens[i], a.tokens + (size_t)i * npos, pages + (size_t)i * pps};
+    len[i] = a.n_tokens[i];
+  }
+  const std::vector<int> cut = prefill_pass_split(len, kPrefillRowCap);
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  // one pass: host image rows [R][3] | slots [R] | seqs [ns][3 + pps] | items [ni][3] | target [R] | AlignSeq [ns] | seq_row [ns] |
+  // sel [LH]; device block: image | lp [R] | start [R] | stats [ns][pairs][2][T] | cost [R][T] | maps [pairs][R][T] | stat [pairs][R][2]
+  // | spilled traces
+  struct Lay { int R, ns, ni, max_rows; size_t w_slots, w_seqs, w_items, w_target, w_aseq, w_row, w_sel, in_words, lds_words, spill_words,
+               o_lp, o_start, o_stats, o_cost, o_maps, o_stat, o_spill, total; };
+  auto layout = [&](int k) {
+    Lay L{};
+    L.ns = cut[k + 1] - cut[k];
+    for (int i = cut[k]; i < cut[k + 1]; ++i) {
+      L.R += len[i]; L.ni += prefill_items_of(len[i]);
+      const int rows = a.n_tokens[i] - 1 - a.first_row[i], frames = std::min(T_, std::max(1, a.num_frames[i] / 2));
+      L.max_rows = std::max(L.max_rows, rows);
+      const size_t w = dtw_trace_words(rows, frames);
+      if (w * 4 <= kDtwLdsTraceBytes) L.lds_words = std::max(L.lds_words, w); else L.spill_words = std::max(L.spill_words, w);
+    }
+    L.w_slots = (size_t)L.R * 3; L.w_seqs = L.w_slots + L.R; L.w_items = L.w_seqs + (size_t)L.ns * (3 + pps);
+    L.w_target = L.w_items + (size_t)L.ni * 3; L.w_aseq = L.w_target + L.R; L.w_row = L.w_aseq + (size_t)L.ns * 4;
+    L.w_sel = L.w_row + L.ns; L.in_words = L.w_sel + LH;
+    L.o_lp = up(L.in_words * 4); L.o_start = L.o_lp + up((size_t)L.R * 4); L.o_stats = L.o_start + up((size_t)L.R * 4);
+    L.o_cost = L.o_stats + up((size_t)L.ns * np * 2 * T_ * 4); L.o_maps = L.o_cost + up((size_t)L.R * T_ * 4);
+    L.o_stat = L.o_maps + up((size_t)np * L.R * T_ * 4); L.o_spill = L.o_stat + up((size_t)np * L.R * 2 * 4);
+    L.total = L.o_spill + up((size_t)L.ns * L.spill_words * 4);
+    return L;
+  };
+  size_t total = 0;
+  for (size_t k = 0; k + 1 < cut.size(); ++k) {
+    const Lay L = layout((int)k);
+    if (L.R > kPrefillRowCap) return fail(c, TTASR_E_INVALID, "packed alignment: a pass of %d rows exceeds the workspace", L.R);
+    total = std::max(total, L.total);
+  }
+  TRY(align_scratch(c, total));
+  char* base = (char*)c->align_dev;
+  memset(a.out_start, 0, (size_t)n * npos * 4);
+  if (a.out_lp) memset(a.out_lp, 0, (size_t)n * npos * 4);
+  if (a.out_cost) memset(a.out_cost, 0, (size_t)n * npos * T_ * 4);
+  if (a.out_weights) memset(a.out_weights, 0, (size_t)n * np * npos * T_ * 4);
+  std::vector<int32_t> in, h_start;
+  std::vector<float> h_lp, h_cost, h_maps;
+  for (size_t k = 0; k + 1 < cut.size(); ++k) {
+    const Lay L = layout((int)k);
+    const int R = L.R, ns = L.ns, i0 = cut[k];
+    in.assign(L.in_words, 0);
+    prefill_build_tables(&sq[i0], ns, pps, in.data(), in.data() + L.w_slots, in.data() + L.w_seqs, in.data() + L.w_items);
+    int32_t* h_target = in.data() + L.w_target;
+    AlignSeq* h_seq = (AlignSeq*)(in.data() + L.w_aseq);
+    int32_t* h_row = in.data() + L.w_row;
+    int32_t* h_sel = in.data() + L.w_sel;
+    for (int j = 0; j < ns; ++j) {
+      const int i = i0 + j, row0 = in[L.w_seqs + (size_t)j * (3 + pps) + 1];
+      h_row[j] = row0;
+      for (int t = 0; t + 1 < a.n_tokens[i]; ++t) h_target[row0 + t] = a.tokens[(size_t)i * npos + t + 1];   // the last row predicts nothing
+      AlignSeq& q = h_seq[j];
+      q.first_row = a.first_row[i]; q.n_tokens = a.n_tokens[i]; q.rows = q.n_tokens - 1 - q.first_row;
+      q.frames = std::min(T_, std::max(1, a.num_frames[i] / 2));
+    }
+    for (int i = 0; i < LH; ++i) h_sel[i] = -1;
+    for (int i = 0; i < np; ++i) h_sel[(size_t)a.pairs[2 * i] * c->H + a.pairs[2 * i + 1]] = i;
+    const int32_t* dw = (const int32_t*)base;
+    const PrefillPass P{dw, dw + L.w_slots, dw + L.w_seqs, dw + L.w_items, R, ns, L.ni, 3 + pps};
+    float* d_lp = (float*)(base + L.o_lp);
+    int32_t* d_start = (int32_t*)(base + L.o_start);
+    float *d_stats = (float*)(base + L.o_stats), *d_cost = (float*)(base + L.o_cost), *d_maps = (float*)(base + L.o_maps);
+    const AlignSeq* d_seq = (const AlignSeq*)(dw + L.w_aseq);
+    const int32_t* d_row = dw + L.w_row;
+    HIPCHK(c, hipMemcpyAsync(base, in.data(), L.in_words * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(base + L.o_lp, 0, L.o_stats - L.o_lp, s));
+    if (a.out_cost) HIPCHK(c, hipMemsetAsync(d_cost, 0, (size_t)R * T_ * 4, s));
+    const PackedAlign al{dw + L.w_sel, h_sel, d_maps, (float*)(base + L.o_stat), np};
+    sched_admit_prefill(c, P, &al);
+    if (a.out_lp) sched_packed_logprob(c, R, dw + L.w_target, d_lp);
+    launch_align_stats(d_maps, d_seq, ns, npos, np, T_, d_stats, s, d_row, R);
+    launch_align_cost(d_maps, d_stats, d_seq, ns, npos, L.max_rows, np, T_, a.medfilt, d_cost, s, d_row, R);
+    launch_align_dtw(d_cost, d_seq, ns, npos, L.max_rows, T_, L.lds_words, (uint32_t*)(base + L.o_spill), L.spill_words, d_start, s, c->device,
+                     d_row);
+    h_start.resize(R);
+    HIPCHK(c, hipMemcpyAsync(h_start.data(), d_start, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+    if (a.out_lp) { h_lp.resize(R); HIPCHK(c, hipMemcpyAsync(h_lp.data(), d_lp, (size_t)R * 4, hipMemcpyDeviceToHost, s)); }
+    if (a.out_cost) { h_cost.resize((size_t)R * T_); HIPCHK(c, hipMemcpyAsync(h_cost.data(), d_cost, (size_t)R * T_ * 4, hipMemcpyDeviceToHost, s)); }
+    if (a.out_weights) { h_maps.resize((size_t)np * R * T_); HIPCHK(c, hipMemcpyAsync(h_maps.data(), d_maps, (size_t)np * R * T_ * 4, hipMemcpyDeviceToHost, s)); }
+    HIPCHK(c, hipStreamSynchronize(s));   // the pass is on the host; the block and the workspace are free for the next one
+    HIPCHK(c, hipGetLastError());
+    for (int j = 0; j < ns; ++j) {
+      const int i = i0 + j, row0 = h_row[j], nt = a.n_tokens[i], rows = nt - 1 - a.first_row[i];
+      memcpy(a.out_start + (size_t)i * npos, h_start.data() + row0, (size_t)rows * 4);
+      if (a.out_lp) memcpy(a.out_lp + (size_t)i * npos, h_lp.data() + row0, (size_t)(nt - 1) * 4);
+      if (a.out_cost) memcpy(a.out_cost + (size_t)i * npos * T_, h_cost.data() + (size_t)row0 * T_, (size_t)rows * T_ * 4);
+      if (a.out_weights)
+        for (int p = 0; p < np; ++p)
+          memcpy(a.out_weights + ((size_t)i * np + p) * npos * T_, h_maps.data() + ((size_t)p * R + row0) * T_, (size_t)nt * T_ * 4);
+    }
+  }
+  return TTASR_OK;
+}
+
 }  // namespace ttasr_detail
 
 extern "C" {

@@ -174,6 +174,9 @@ struct ttasr_ctx {
   int session_prefill = 0;
   float* pf_x = nullptr; void *pf_h = nullptr, *pf_qkv = nullptr, *pf_att = nullptr, *pf_mid = nullptr;
   int32_t* pf_tab = nullptr; size_t pf_tab_words = 0; int* pf_sel = nullptr;
+  // option align_packed: ttasr_session_align runs the PACKED pass of the admission (one fixed GEMM family,
+  // work items cut from each sequence's own length) out of the pf_* workspace instead of the padded run_prefill; read at call time
+  bool align_packed = false;
 
   // batched alignment (engine_align.hip): ONE device block for the pass's tables, softmax maps, cost matrices and spilled DTW
   // traces; allocated by the first call, grown to the largest request, freed by ttasr_destroy
@@ -342,7 +345,17 @@ void enc_mark(ttasr_ctx* c, int cls);
 void sched_encoder(ttasr_ctx* c, int B);                       // conv stem, encoder layers, final LayerNorm, cross-KV
 void sched_cross_kv(ttasr_ctx* c, int B);
 void sched_prefill(ttasr_ctx* c, int n_seq, int npos, int seq_per_clip, int max_prompt, const AlignOut* al = nullptr);
-void sched_admit_prefill(ttasr_ctx* c, const PrefillPass& P);   // the decoder layers over the packed rows of an admission pass, on the decode stream
+// the packed alignment pass's extras on top of an admission pass: sel (device [dec_layers][H]: pair or -1) and sel_host (the same),
+// maps (device [n_pairs][n_rows][T]) and stat (device [n_pairs][n_rows][2], 16-bit MFMA form only)
+struct PackedAlign { const int32_t* sel; const int32_t* sel_host; float* maps; float* stat; int n_pairs; };
+// the decoder layers over the packed rows of an admission pass, on the decode stream; al != nullptr: the alignment pass, whose
+// selected heads leave finished softmax maps in al->maps and whose residual rows stay in c->pf_x
+void sched_admit_prefill(ttasr_ctx* c, const PrefillPass& P, const PackedAlign* al = nullptr);
+// one layer's cross-attention of that pass on caller-supplied query rows (ttasr_align_attn_probe): dq, datt [n_rows][d]
+void sched_align_attn(ttasr_ctx* c, int layer, const PrefillPass& P, const void* dq, void* datt, const PackedAlign& al);
+// final LayerNorm + vocabulary projection (the pass's GEMM family) + log p(target[r]) for packed rows [0, n_rows) of c->pf_x
+void sched_packed_logprob(ttasr_ctx* c, int n_rows, const int32_t* target, float* out);
+int prefill_workspace(ttasr_ctx* c);   // engine_refill.hip: the pf_* workspace, allocated by the first caller that needs it
 int sched_prefill_no_speech(ttasr_ctx* c, int n_seq, int npos, int sot, int no_speech_tok);
 void sched_gemm(ttasr_ctx* c, const GemmArgs& g);              // encoder-side GEMM dispatch (ttasr_bench_kernel)
 void sched_dec_gemm(ttasr_ctx* c, const GemmArgs& g, const void* Wsh);
@@ -378,6 +391,8 @@ struct AlignBatch {   // the host arguments of ttasr_align_batch without the cli
 };
 int align_batch_validate(ttasr_ctx* c, const AlignBatch& a);
 int align_batch_run(ttasr_ctx* c, const AlignBatch& a, const int32_t* slot /*[n]*/, const int32_t* pages /*[n][pages_per_seq]*/);
+// the same call through the packed pass (option align_packed): every output of a sequence is a function of that sequence alone
+int align_packed_run(ttasr_ctx* c, const AlignBatch& a, const int32_t* slot, const int32_t* pages);
 
 // ---- engine_vad.hip: the voice-activity network (ttasr_vad_*) ----
 void vad_free(ttasr_ctx* c);         // ttasr_destroy: the scratch block, the pinned staging and the streams' table (the weights live in the arenas)

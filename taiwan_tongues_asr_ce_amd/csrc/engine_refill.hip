@@ -458,6 +458,23 @@ static int pump(ttasr_ctx* c, Session* S) {
   return 0;
 }
 
+// The packed pass's own workspace (admission passes of option session_prefill, the alignment pass of option align_packed and its
+// probe): kPrefillRowCap rows of activations, the device tables and the all -1 head selection.  Kept for the context's lifetime.
+int prefill_workspace(ttasr_ctx* c) {
+  const size_t R = kPrefillRowCap, e = c->esz;
+  if (!c->pf_x) TRY(dalloc(c, &c->pf_x, R * c->d * 4));
+  if (!c->pf_h) TRY(dalloc(c, &c->pf_h, R * c->d * e));
+  if (!c->pf_qkv) TRY(dalloc(c, &c->pf_qkv, R * 3 * c->d * e));
+  if (!c->pf_att) TRY(dalloc(c, &c->pf_att, R * c->d * e));
+  if (!c->pf_mid) TRY(dalloc(c, &c->pf_mid, R * c->ffn * e));
+  if (!c->pf_tab) { c->pf_tab_words = prefill_tab_cap(c); TRY(dalloc(c, &c->pf_tab, c->pf_tab_words * 4)); }
+  if (!c->pf_sel) {
+    TRY(dalloc(c, &c->pf_sel, (size_t)c->H * 4, false));
+    HIPCHK(c, hipMemsetAsync(c->pf_sel, 0xff, (size_t)c->H * 4, c->stream));   // no head writes a softmax map
+  }
+  return 0;
+}
+
 static int session_begin(ttasr_ctx* c, const ttasr_gen_opts* o, int max_prompt, float temperature, StepShape shape) {
   if (!c) return TTASR_E_INVALID;
   if (!c->finalized) return fail(c, TTASR_E_INVALID, "weights not finalized (call ttasr_finalize_weights first)");
@@ -480,19 +497,7 @@ static int session_begin(ttasr_ctx* c, const ttasr_gen_opts* o, int max_prompt, 
   if (!c->row_pos) TRY(dalloc(c, &c->row_pos, (size_t)B * 4));
   if (!c->admit_dev) TRY(dalloc(c, &c->admit_dev, (size_t)B * (4 + c->max_prompt_alloc) * 4));
   if (!c->xkv_stage) TRY(dalloc(c, &c->xkv_stage, (size_t)c->xkv_layer_elems * c->cfg.dec_layers * c->esz, false));
-  if (c->session_prefill > 0) {   // first session with prompt prefill: the pass's own workspace and tables (kept like the others)
-    const size_t R = kPrefillRowCap, e = c->esz;
-    if (!c->pf_x) TRY(dalloc(c, &c->pf_x, R * c->d * 4));
-    if (!c->pf_h) TRY(dalloc(c, &c->pf_h, R * c->d * e));
-    if (!c->pf_qkv) TRY(dalloc(c, &c->pf_qkv, R * 3 * c->d * e));
-    if (!c->pf_att) TRY(dalloc(c, &c->pf_att, R * c->d * e));
-    if (!c->pf_mid) TRY(dalloc(c, &c->pf_mid, R * c->ffn * e));
-    if (!c->pf_tab) { c->pf_tab_words = prefill_tab_cap(c); TRY(dalloc(c, &c->pf_tab, c->pf_tab_words * 4)); }
-    if (!c->pf_sel) {
-      TRY(dalloc(c, &c->pf_sel, (size_t)c->H * 4, false));
-      HIPCHK(c, hipMemsetAsync(c->pf_sel, 0xff, (size_t)c->H * 4, c->stream));   // no head writes a softmax map
-    }
-  }
+  if (c->session_prefill > 0) TRY(prefill_workspace(c));   // first session with prompt prefill: the pass's own workspace and tables
   std::unique_ptr<Session> S(new Session());
   S->prefill = c->session_prefill;
   S->o = *o; S->o.suppress = nullptr; S->o.begin_suppress = nullptr;   // the rules are uploaded; the caller's arrays are not kept
@@ -1091,7 +1096,8 @@ static int session_align(ttasr_ctx* c, int n, const int64_t* ids, const AlignBat
     for (int i = 0; i < n; ++i)
       for (int p = 0; p < pps; ++p) pages[(size_t)i * pps + p] = units[i] * pps + p;
   }
-  TRY(align_batch_run(c, a, slot.data(), pages.data()));
+  // option align_packed, read here: the packed pass, whose bits for a clip do not depend on the other clips of the call
+  TRY(c->align_packed ? align_packed_run(c, a, slot.data(), pages.data()) : align_batch_run(c, a, slot.data(), pages.data()));
   for (int u : units) release_unit(S, u);
   return TTASR_OK;
 }

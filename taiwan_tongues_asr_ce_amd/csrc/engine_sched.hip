@@ -463,8 +463,29 @@ void run_prefill(ttasr_ctx* c, int n_seq, int npos, int seq_per_clip, int max_pr
 // the context's widths (a row of a tile depends on its own A row only, and rows past M are loaded clamped and never stored);
 // f32 or option generic_kernels: the generic kernel - the attention work items are cut from each sequence's own length, and the
 // K-split skinny path of run_prefill, whose split follows the pass's row count, is not used.
+// al != nullptr: the packed alignment pass (option align_packed, engine_align.hip).  The same launches; in a layer that holds a
+// selected head the 16-bit cross-attention is the MAPS = true instantiation of the same kernel, the per-row form gets the
+// layer's selection and the map buffer, and the stored score rows are finished into softmax maps behind the last layer.
 template <typename T>
-void run_admit_prefill(ttasr_ctx* c, const PrefillPass& P) {
+void align_cross_attn(ttasr_ctx* c, int l, const PrefillPass& P, const void* q, void* att, const PackedAlign* al) {
+  hipStream_t s = c->stream;
+  const T* Kx = (const T*)c->xkv + (int64_t)l * c->xkv_layer_elems;   // the 16-bit live slots, also under xkv_fp8 = 2
+  bool any = false;
+  if (al) for (int h = 0; h < c->H; ++h) any |= al->sel_host[(size_t)l * c->H + h] >= 0;
+  if constexpr (sizeof(T) == 2) {
+    if (!c->force_basic) {
+      if (any) launch_prefill_cross_attn_maps<T>(P, (const T*)q, Kx, Kx + c->xkv_which_elems, (T*)att, c->H, c->T,
+                                                 PrefillMaps{al->sel + (size_t)l * c->H, al->maps, al->stat, P.n_rows}, s);
+      else launch_prefill_cross_attn<T>(P, (const T*)q, Kx, Kx + c->xkv_which_elems, (T*)att, c->H, c->T, s);
+      return;
+    }
+  }
+  // per-row form: "sequence" = one packed row, its slot from the table; without a selected head no softmax map is written
+  launch_cross_attn_probs_batch<T>((const T*)q, Kx, Kx + c->xkv_which_elems, (T*)att, P.n_rows, 1, c->H, c->T,
+                                   any ? al->sel + (size_t)l * c->H : c->pf_sel, P.slots, any ? al->maps : nullptr, s);
+}
+template <typename T>
+void run_admit_prefill(ttasr_ctx* c, const PrefillPass& P, const PackedAlign* al) {
   const int d = c->d, ffn = c->ffn, n = P.n_rows;
   hipStream_t s = c->cur = c->stream;
   float* x = c->pf_x;
@@ -493,17 +514,37 @@ void run_admit_prefill(ttasr_ctx* c, const PrefillPass& P) {
     residual_gemm(att, L.wo, L.bo, d);
     launch_layernorm<T>(x, L.ln2g, L.ln2b, (T*)h, n, d, s);
     { GemmArgs g = lin_args<T>(h, L.wqx, n, d, d); g.epi.bias = L.bqx; g.epi.out_t = qkv; pgemm(g); }   // q reuses the qkv buffer
-    const T* Kx = (const T*)c->xkv + (int64_t)l * c->xkv_layer_elems;   // the 16-bit live slots, also under xkv_fp8 = 2
-    bool mfma = false;
-    if constexpr (sizeof(T) == 2) {
-      if (!c->force_basic) { launch_prefill_cross_attn<T>(P, (const T*)qkv, Kx, Kx + c->xkv_which_elems, (T*)att, c->H, c->T, s); mfma = true; }
-    }
-    // per-row form: "sequence" = one packed row, its slot from the table, no head selected for a softmax map
-    if (!mfma) launch_cross_attn_probs_batch<T>((const T*)qkv, Kx, Kx + c->xkv_which_elems, (T*)att, n, 1, c->H, c->T, c->pf_sel, P.slots, nullptr, s);
+    align_cross_attn<T>(c, l, P, qkv, att, al);
     residual_gemm(att, L.wox, L.box, d);
     launch_layernorm<T>(x, L.ln3g, L.ln3b, (T*)h, n, d, s);
     { GemmArgs g = lin_args<T>(h, L.w1, n, ffn, d); g.epi.bias = L.b1; g.epi.act = 1; g.epi.out_t = mid; pgemm(g); }
     residual_gemm(mid, L.w2, L.b2, ffn);
+  }
+  if (al && sizeof(T) == 2 && !c->force_basic) launch_prefill_maps_finish(al->maps, al->stat, al->n_pairs, n, c->T, s);
+}
+
+// log p(target[r] | row r) of the packed residual rows the alignment pass left in c->pf_x: final LayerNorm, the vocabulary
+// projection in the admission pass's fixed GEMM family (a row's logits depend on its own row only), max_batch rows at a time
+// through the step's logits buffer.
+template <typename T>
+void run_packed_logprob(ttasr_ctx* c, int n_rows, const int32_t* target, float* out) {
+  hipStream_t s = c->cur = c->stream;
+  const int d = c->d;
+  launch_layernorm<T>(c->pf_x, c->dlnf_g, c->dlnf_b, (T*)c->pf_h, n_rows, d, s);
+  for (int r0 = 0; r0 < n_rows; r0 += c->maxB) {
+    const int m = std::min(c->maxB, n_rows - r0);
+    GemmArgs g = lin_args<T>((const T*)c->pf_h + (size_t)r0 * d, c->emb, m, c->V, d);
+    g.epi.out_f32 = c->logits; g.epi.ldc = c->ldv;
+    bool done = false;
+    if constexpr (sizeof(T) == 2) {
+      if (!c->force_basic) {
+        if (gemm_bf16_v3_ok(g)) { launch_gemm_bf16_v3<T>(g, s); done = true; }
+        else if (gemm_bf16_v2_ok(g)) { launch_gemm_bf16_v2<T>(g, s); done = true; }
+        else if (gemm_bf16_fast_ok(g)) { launch_gemm_bf16_fast<T>(g, s); done = true; }
+      }
+    }
+    if (!done) launch_gemm_basic<T>(g, s);
+    launch_token_logprob(c->logits, c->ldv, c->V, target + r0, out + r0, m, s);
   }
 }
 
@@ -618,7 +659,15 @@ void sched_cross_kv(ttasr_ctx* c, int B) { TT_DISPATCH(c, run_cross_kv<T>(c, B))
 void sched_prefill(ttasr_ctx* c, int n_seq, int npos, int seq_per_clip, int max_prompt, const AlignOut* al) {
   TT_DISPATCH(c, run_prefill<T>(c, n_seq, npos, seq_per_clip, max_prompt, al));
 }
-void sched_admit_prefill(ttasr_ctx* c, const PrefillPass& P) { TT_DISPATCH(c, run_admit_prefill<T>(c, P)); }
+void sched_admit_prefill(ttasr_ctx* c, const PrefillPass& P, const PackedAlign* al) { TT_DISPATCH(c, run_admit_prefill<T>(c, P, al)); }
+void sched_align_attn(ttasr_ctx* c, int layer, const PrefillPass& P, const void* dq, void* datt, const PackedAlign& al) {
+  c->cur = c->stream;
+  TT_DISPATCH(c, align_cross_attn<T>(c, layer, P, dq, datt, &al));
+  if (c->lowp && !c->force_basic && al.n_pairs > 0) launch_prefill_maps_finish(al.maps, al.stat, al.n_pairs, P.n_rows, c->T, c->stream);
+}
+void sched_packed_logprob(ttasr_ctx* c, int n_rows, const int32_t* target, float* out) {
+  TT_DISPATCH(c, run_packed_logprob<T>(c, n_rows, target, out));
+}
 int sched_prefill_no_speech(ttasr_ctx* c, int n_seq, int npos, int sot, int no_speech_tok) {
   TT_DISPATCH(c, return prefill_no_speech<T>(c, n_seq, npos, sot, no_speech_tok));
   return 0;

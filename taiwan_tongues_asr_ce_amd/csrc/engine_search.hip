@@ -64,6 +64,7 @@ int set_option(ttasr_ctx* c, const std::string& key, int v) {
     c->session_prefill = v;
     return 0;
   }
+  if (key == "align_packed") { c->align_packed = on; return 0; }   // read by ttasr_session_align at call time: the graphs stay
   if (key == "ingest_chunk") {      // host-side chunking of ttasr_ingest_pcm: the graphs stay
     if (v < 0 || v > 1 << 30) return 1;
     c->ingest_chunk = v;

@@ -6,6 +6,9 @@
 //   align_cost_kernel    one workgroup per (sequence, row): per pair the normalised row is staged in LDS, every thread takes the
 //                        median of its frame's window from there; the pairs' medians are averaged and negated
 //   align_dtw_kernel     one workgroup per sequence, one thread per row, one barrier per anti-diagonal (below)
+// Rows of a sequence: the padded pass has sequence i at rows i * npos ..; the packed pass (option align_packed) hands seq_row
+// [n_seq], every sequence's first packed row, and the cost rows and start frames then sit at the packed rows too.  The
+// arithmetic does not know which: equal maps give equal cost matrices and paths.
 #include <mutex>
 
 #include "align_batch.hpp"
@@ -16,11 +19,13 @@ namespace ttasr_detail {
 // Sums run in double: a column holds up to 447 positive softmax values, and the sequential f32 sum of the host code is the
 // largest term of ITS error against exact arithmetic; the loads, not the adds, bound this kernel.
 __global__ __launch_bounds__(256) void align_stats_kernel(const float* __restrict__ probs, const AlignSeq* __restrict__ seq, int npos,
-                                                          int n_pairs, int Tk, int64_t pair_stride, float* __restrict__ stats) {
+                                                          int n_pairs, int Tk, int64_t pair_stride, float* __restrict__ stats,
+                                                          const int32_t* __restrict__ seq_row) {
   const int i = blockIdx.z, p = blockIdx.y, f = blockIdx.x * 256 + threadIdx.x;
   const AlignSeq sq = seq[i];
   if (f >= sq.frames) return;
-  const float* col = probs + (int64_t)p * pair_stride + ((int64_t)i * npos + sq.first_row) * Tk + f;
+  const int64_t base = seq_row ? seq_row[i] : (int64_t)i * npos;
+  const float* col = probs + (int64_t)p * pair_stride + (base + sq.first_row) * Tk + f;
   double sum = 0.0;
   for (int r = 0; r < sq.rows; ++r) sum += (double)col[(int64_t)r * Tk];
   const float mean = (float)(sum / sq.rows);
@@ -35,18 +40,21 @@ __global__ __launch_bounds__(256) void align_stats_kernel(const float* __restric
   out[Tk + f] = sd > 0.f ? sd : 1.f;
 }
 
-void launch_align_stats(const float* probs, const AlignSeq* seq, int n_seq, int npos, int n_pairs, int Tk, float* stats, hipStream_t s) {
+void launch_align_stats(const float* probs, const AlignSeq* seq, int n_seq, int npos, int n_pairs, int Tk, float* stats, hipStream_t s,
+                        const int32_t* seq_row, int n_rows) {
   hipLaunchKernelGGL(align_stats_kernel, dim3((Tk + 255) / 256, n_pairs, n_seq), dim3(256), 0, s, probs, seq, npos, n_pairs, Tk,
-                     (int64_t)n_seq * npos * Tk, stats);
+                     (int64_t)(seq_row ? n_rows : n_seq * npos) * Tk, stats, seq_row);
 }
 
 __global__ __launch_bounds__(256) void align_cost_kernel(const float* __restrict__ probs, const float* __restrict__ stats,
                                                          const AlignSeq* __restrict__ seq, int npos, int n_pairs, int Tk,
-                                                         int64_t pair_stride, int width, float* __restrict__ cost) {
+                                                         int64_t pair_stride, int width, float* __restrict__ cost,
+                                                         const int32_t* __restrict__ seq_row) {
   extern __shared__ float z[];   // [frames] one pair's normalised row
   const int i = blockIdx.y, r = blockIdx.x, tid = threadIdx.x;
   const AlignSeq sq = seq[i];
   if (r >= sq.rows) return;
+  const int64_t base = seq_row ? seq_row[i] : (int64_t)i * npos;
   const int F = sq.frames, pad = width / 2;
   const bool filter = width > 1 && F > pad;   // numpy's median_filter is a no-op on an axis no longer than the padding
   constexpr int NF = 6;                       // frames per thread: 6 x 256 >= the 1500-frame window
@@ -54,7 +62,7 @@ __global__ __launch_bounds__(256) void align_cost_kernel(const float* __restrict
 #pragma unroll
   for (int k = 0; k < NF; ++k) acc[k] = 0.0;
   for (int p = 0; p < n_pairs; ++p) {
-    const float* row = probs + (int64_t)p * pair_stride + ((int64_t)i * npos + sq.first_row + r) * Tk;
+    const float* row = probs + (int64_t)p * pair_stride + (base + sq.first_row + r) * Tk;
     const float* st = stats + ((int64_t)i * n_pairs + p) * 2 * Tk;
     for (int f = tid; f < F; f += 256) z[f] = (row[f] - st[f]) / st[Tk + f];
     __syncthreads();
@@ -86,7 +94,7 @@ __global__ __launch_bounds__(256) void align_cost_kernel(const float* __restrict
     }
     __syncthreads();
   }
-  float* out = cost + ((int64_t)i * npos + r) * Tk;
+  float* out = cost + (base + r) * Tk;
 #pragma unroll
   for (int k = 0; k < NF; ++k) {
     const int f = tid + k * 256;
@@ -95,10 +103,10 @@ __global__ __launch_bounds__(256) void align_cost_kernel(const float* __restrict
 }
 
 void launch_align_cost(const float* probs, const float* stats, const AlignSeq* seq, int n_seq, int npos, int max_rows, int n_pairs, int Tk,
-                       int width, float* cost, hipStream_t s) {
+                       int width, float* cost, hipStream_t s, const int32_t* seq_row, int n_rows) {
   if (Tk > 6 * 256) { launch_fault("align_cost: %d frames > 1536", Tk); return; }
   hipLaunchKernelGGL(align_cost_kernel, dim3(max_rows, n_seq), dim3(256), (size_t)Tk * 4, s, probs, stats, seq, npos, n_pairs, Tk,
-                     (int64_t)n_seq * npos * Tk, width, cost);
+                     (int64_t)(seq_row ? n_rows : n_seq * npos) * Tk, width, cost, seq_row);
 }
 
 // DTW over C [rows][F] of one sequence.  Thread i owns row i and walks it one frame per anti-diagonal k = i + j: the cells of a
@@ -111,13 +119,14 @@ void launch_align_cost(const float* probs, const float* stats, const AlignSeq* s
 // barriers of <= 8 waves: the kernel is latency-bound by construction, and independent sequences run on other CUs.
 __global__ __launch_bounds__(512) void align_dtw_kernel(const float* __restrict__ cost, const AlignSeq* __restrict__ seq, int npos, int Tk,
                                                         size_t lds_trace_words, uint32_t* __restrict__ trace_spill, size_t spill_words,
-                                                        int32_t* __restrict__ start) {
+                                                        int32_t* __restrict__ start, const int32_t* __restrict__ seq_row) {
   extern __shared__ float lds[];   // [3][blockDim] diagonals, then the trace words
   const int s = blockIdx.x, i = threadIdx.x, nt = blockDim.x;
   const AlignSeq sq = seq[s];
   const int rows = sq.rows, F = sq.frames;
+  const int64_t base = seq_row ? seq_row[s] : (int64_t)s * npos;
   uint32_t* trace = dtw_trace_words(rows, F) <= lds_trace_words ? (uint32_t*)(lds + 3 * nt) : trace_spill + (size_t)s * spill_words;
-  const float* crow = cost + ((int64_t)s * npos + min(i, rows - 1)) * Tk;
+  const float* crow = cost + (base + min(i, rows - 1)) * Tk;
   const bool mine = i < rows;
   float left = INFINITY, cnext = crow[0];
   uint32_t tw = 0;
@@ -142,7 +151,7 @@ __global__ __launch_bounds__(512) void align_dtw_kernel(const float* __restrict_
     __syncthreads();
   }
   if (i != 0) return;
-  int32_t* out = start + (int64_t)s * npos;
+  int32_t* out = start + base;
   int r = rows - 1, j = F - 1;
   while (r >= 0 && j >= 0) {
     out[r] = j;
@@ -152,7 +161,7 @@ __global__ __launch_bounds__(512) void align_dtw_kernel(const float* __restrict_
 }
 
 void launch_align_dtw(const float* cost, const AlignSeq* seq, int n_seq, int npos, int max_rows, int Tk, size_t lds_trace_words,
-                      uint32_t* trace_spill, size_t spill_words, int32_t* start, hipStream_t s, int device) {
+                      uint32_t* trace_spill, size_t spill_words, int32_t* start, hipStream_t s, int device, const int32_t* seq_row) {
   if (max_rows < 1 || max_rows > 512) { launch_fault("align_dtw: %d rows outside [1, 512]", max_rows); return; }
   static std::once_flag once[64];
   std::call_once(once[device & 63], []() {
@@ -161,7 +170,7 @@ void launch_align_dtw(const float* cost, const AlignSeq* seq, int n_seq, int npo
   const int nt = (max_rows + 63) / 64 * 64;
   const size_t lds = (size_t)3 * nt * 4 + lds_trace_words * 4;
   hipLaunchKernelGGL(align_dtw_kernel, dim3(n_seq), dim3(nt), lds, s, cost, seq, npos, Tk, lds_trace_words, trace_spill, spill_words,
-                     start);
+                     start, seq_row);
 }
 
 }  // namespace ttasr_detail

@@ -3,7 +3,9 @@
 //   prefill_embed          x[row] = emb[token] + pos[position] into the f32 residual
 //   prefill_self_attn      append launch + attend launch (a position reads keys that other workgroups of the first launch
 //                          write): row (s, t) writes K / V of position t into sequence s's pages and attends to 0 .. t
-//   prefill_cross_attn     16-bit engines: ragged MFMA flash cross-attention, one workgroup per (head, work item)
+//   prefill_cross_attn     16-bit engines: ragged MFMA flash cross-attention, one workgroup per (head, work item); MAPS = true
+//                          (the packed alignment pass, option align_packed) also leaves the selected heads' score rows, which
+//                          prefill_maps_finish turns into softmax maps
 // The f32 engine's cross-attention is the per-row kernel of the alignment pass with row -> slot from the table
 // (launch_cross_attn_probs_batch).  Every row's result depends on the row's own sequence only: nothing here reads the pass's size.
 #include "common.hpp"
@@ -118,6 +120,13 @@ void launch_prefill_self_attn(const PrefillPass& P, const T* qkv, T* pool_layer,
 // SOURCE: the body is enc_attn_flash_kernel<T16, CROSS = true, QW = 1> of kernels_flash.hip with (batch, Tn) replaced by the item
 // table (that template is what the benchmark launches and takes no new modes).  A fix to the swizzles, the clamped tail DMA and
 // its mask index, the first-tile alpha guard, the vmcnt / barrier order or the epilogue's LDS reuse belongs in BOTH places.
+// MAPS = true (the alignment pass of option align_packed, ttasr_align_attn_probe) is the same body; a workgroup whose head is
+// selected (mp.sel[h] = pair >= 0) additionally stores, for its live rows and the keys below n_k,
+//   maps[pair][row][key] = the score in exp2 units, ABSOLUTE: what the MFMA delivered plus the reference it was taken against -
+//                          the one coordinate that does not move with the lazily moved reference
+//   stat[pair][row]      = {final reference, softmax sum against it}
+// and prefill_maps_finish_kernel turns each stored row into exp2(score - reference) / sum in place.  Nothing else changes: the
+// attention output is computed by the same instructions in the same order, and MAPS = false has no argument and no code of it.
 // ------------------------------------------------------------------------------------------------
 typedef short pf_s16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ pf_s16x4 pf_lds_tr16(const char* p) {
@@ -125,11 +134,12 @@ __device__ __forceinline__ pf_s16x4 pf_lds_tr16(const char* p) {
 }
 constexpr int PF_KB = 64;   // keys per tile
 
-template <typename T16>
+template <typename T16, bool MAPS, typename... MP>   // MP = PrefillMaps when MAPS, else empty: MAPS = false keeps its argument list
 __global__ __launch_bounds__(256, 3) void prefill_cross_attn_kernel(const bf16_t* __restrict__ q, bf16_t* __restrict__ out,
                                                                     const int32_t* __restrict__ items, const int32_t* __restrict__ seqs,
                                                                     int seq_stride, int H, const bf16_t* __restrict__ kx,
-                                                                    const bf16_t* __restrict__ vx, int n_k) {
+                                                                    const bf16_t* __restrict__ vx, int n_k, MP... mp_) {
+  static_assert(sizeof...(MP) == (MAPS ? 1 : 0), "MAPS = true takes one PrefillMaps");
   extern __shared__ __attribute__((aligned(16))) char smem[];  // 2 x (K 8 KiB | V 8 KiB); reused for the O transpose
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, hf = lane >> 5;
@@ -160,6 +170,18 @@ __global__ __launch_bounds__(256, 3) void prefill_cross_attn_kernel(const bf16_t
     }
   }
   const bool live = q0 < n_q;
+  // MAPS: this lane's row of the selected head's map (nullptr: head not selected, or a row past the item's count)
+  [[maybe_unused]] float* map_row = nullptr;
+  [[maybe_unused]] float* stat_row = nullptr;
+  if constexpr (MAPS) {
+    const PrefillMaps mp = (mp_, ...);
+    const int pair = __builtin_amdgcn_readfirstlane(mp.sel[h]);
+    if (pair >= 0 && q0 + r < n_q) {
+      const int64_t row = (int64_t)pair * mp.n_rows + row0 + q0 + r;
+      map_row = mp.maps + row * n_k;
+      stat_row = mp.stat + row * 2;
+    }
+  }
 
   // K / V staging by LDS-DMA: a wave-instruction of global_load_lds moves 1 KiB = 8 rows x 128 B straight into the LDS image.  A
   // tile is 8 K pieces + 8 V pieces; wave w issues K pieces 2w, 2w+1 and V pieces 2w, 2w+1.  Lane l of piece p lands in row
@@ -257,6 +279,22 @@ __global__ __launch_bounds__(256, 3) void prefill_cross_attn_kernel(const bf16_t
             if (key >= n_k) s[kb2][j] = -1e30f;
           }
       }
+      if constexpr (MAPS) {
+        // lane (r, hf) holds keys kt*64 + 32 kb2 + 8 g + 4 hf + 0..3 of query r: two 8-byte stores per group (n_k is even, so a
+        // row starts 8-byte aligned and a pair of keys is inside the window or outside it together); a clamped key is never stored
+        if (map_row) {
+#pragma unroll
+          for (int kb2 = 0; kb2 < 2; ++kb2)
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4)
+#pragma unroll
+              for (int e = 0; e < 4; e += 2) {
+                const int key = kt * PF_KB + 32 * kb2 + 8 * g4 + 4 * hf + e;
+                if (!LAST || key < n_k)
+                  *(float2*)(map_row + key) = make_float2(s[kb2][4 * g4 + e] + m_ref, s[kb2][4 * g4 + e + 1] + m_ref);
+              }
+        }
+      }
       // ---- this lane's query column: how far above the reference is the tile's maximum? ----
       float tmax = s[0][0];
 #pragma unroll
@@ -328,6 +366,9 @@ __global__ __launch_bounds__(256, 3) void prefill_cross_attn_kernel(const bf16_t
   char* ob = smem + wave * (32 * 144);  // [32 q][64 d] 16-bit, row stride 144 B (128 + 16 pad); wave-private
   const float l_tot = xor32_reduce(l_run, OpSum{});
   const float inv = 1.0f / l_tot;       // (a wave without a live row never stores what it computes here)
+  if constexpr (MAPS) {
+    if (stat_row && hf == 0) *(float2*)stat_row = make_float2(m_ref, l_tot);   // both halves of a query hold the same reference
+  }
 #pragma unroll
   for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -351,8 +392,26 @@ __global__ __launch_bounds__(256, 3) void prefill_cross_attn_kernel(const bf16_t
 }
 template <typename T16>
 void launch_prefill_cross_attn(const PrefillPass& P, const T16* q, const T16* K, const T16* V, T16* out, int H, int Tk, hipStream_t s) {
-  hipLaunchKernelGGL((prefill_cross_attn_kernel<T16>), dim3(H, P.n_items), dim3(256), 32768, s, (const bf16_t*)q, (bf16_t*)out, P.items,
+  hipLaunchKernelGGL((prefill_cross_attn_kernel<T16, false>), dim3(H, P.n_items), dim3(256), 32768, s, (const bf16_t*)q, (bf16_t*)out, P.items,
                      P.seqs, P.seq_stride, H, (const bf16_t*)K, (const bf16_t*)V, Tk);
+}
+template <typename T16>
+void launch_prefill_cross_attn_maps(const PrefillPass& P, const T16* q, const T16* K, const T16* V, T16* out, int H, int Tk,
+                                    const PrefillMaps& mp, hipStream_t s) {
+  hipLaunchKernelGGL((prefill_cross_attn_kernel<T16, true, PrefillMaps>), dim3(H, P.n_items), dim3(256), 32768, s, (const bf16_t*)q,
+                     (bf16_t*)out, P.items, P.seqs, P.seq_stride, H, (const bf16_t*)K, (const bf16_t*)V, Tk, mp);
+}
+
+// The stored score rows of launch_prefill_cross_attn_maps -> softmax over the n_k frames, in place and in f32: one workgroup per
+// (packed row, pair); p = exp2(score - reference) / sum with the row's own reference and sum (stat), nothing of any other row.
+__global__ __launch_bounds__(256) void prefill_maps_finish_kernel(float* __restrict__ maps, const float* __restrict__ stat, int n_k) {
+  const int64_t row = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+  const float m = stat[2 * row], inv = 1.0f / stat[2 * row + 1];
+  float* p = maps + row * n_k;
+  for (int f = threadIdx.x; f < n_k; f += 256) p[f] = __builtin_amdgcn_exp2f(p[f] - m) * inv;
+}
+void launch_prefill_maps_finish(float* maps, const float* stat, int n_pairs, int n_rows, int Tk, hipStream_t s) {
+  hipLaunchKernelGGL(prefill_maps_finish_kernel, dim3(n_rows, n_pairs), dim3(256), 0, s, maps, stat, Tk);
 }
 
 #define TTASR_PF_ALL(T_)                                                                                          \
@@ -362,3 +421,5 @@ TTASR_PF_ALL(float); TTASR_PF_ALL(bf16_t); TTASR_PF_ALL(f16_t);
 #undef TTASR_PF_ALL
 template void launch_prefill_cross_attn<bf16_t>(const PrefillPass&, const bf16_t*, const bf16_t*, const bf16_t*, bf16_t*, int, int, hipStream_t);
 template void launch_prefill_cross_attn<f16_t>(const PrefillPass&, const f16_t*, const f16_t*, const f16_t*, f16_t*, int, int, hipStream_t);
+template void launch_prefill_cross_attn_maps<bf16_t>(const PrefillPass&, const bf16_t*, const bf16_t*, const bf16_t*, bf16_t*, int, int, const PrefillMaps&, hipStream_t);
+template void launch_prefill_cross_attn_maps<f16_t>(const PrefillPass&, const f16_t*, const f16_t*, const f16_t*, f16_t*, int, int, const PrefillMaps&, hipStream_t);

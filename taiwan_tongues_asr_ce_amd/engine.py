@@ -48,6 +48,10 @@ def default_suppress(st: SpecialTokens, vocab: int) -> List[int]:
 
 
 class Engine:
+    # capability: this engine's sessions can hold finished clips (Session.hold / align / retry / release) and align them with the
+    # packed, pass-mate-independent pass (option "align_packed"); what transcribe_many(continuous=True, word_timestamps=True) needs
+    session_hold = True
+
     def __init__(self, dims: WhisperDims, compute_type: int = COMPUTE_BF16, max_batch: int = 1, device: int = 0,
                  share_weights_with: Optional["Engine"] = None):
         """share_weights_with: another Engine on the same GPU whose (finalized) device weights this one reads instead of loading
@@ -340,6 +344,25 @@ class Engine:
                                                     None if flags is None else flags.ctypes.data_as(C.c_void_p), _ptr(out), buf, 256),
                     "cross_attn_probe")
         return out, buf.value.decode()
+
+    def align_attn_probe(self, layer: int, q: np.ndarray, lens: Sequence[int], slots: Sequence[int], head_pair: Sequence[int]):
+        """The cross-attention of the packed alignment pass on the caller's queries (ttasr_align_attn_probe).  q: float32
+        [sum(lens)][d_model], sequence i = lens[i] consecutive rows reading the cross-KV of clip slots[i]; head_pair [n_heads]:
+        -1 or the index of the map that head writes.  Returns (out float32 [rows][d_model], maps float32 [n_pairs][rows][T])."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        ln, sl = np.ascontiguousarray(lens, dtype=np.int32), np.ascontiguousarray(slots, dtype=np.int32)
+        hp = np.ascontiguousarray(head_pair, dtype=np.int32)
+        rows = int(ln.sum())
+        if q.shape != (rows, self.dims.d_model) or ln.shape != sl.shape or hp.shape != (self.dims.n_heads,):
+            raise ValueError(f"q {q.shape}, lens {ln.shape}, slots {sl.shape}, head_pair {hp.shape}")
+        n_pairs = int((hp >= 0).sum())
+        out = np.empty((rows, self.dims.d_model), dtype=np.float32)
+        maps = np.empty((n_pairs, rows, self.audio_ctx), dtype=np.float32)
+        i32p = C.POINTER(C.c_int32)
+        self._check(self.lib.ttasr_align_attn_probe(self.h, layer, len(ln), ln.ctypes.data_as(i32p), sl.ctypes.data_as(i32p), _ptr(q),
+                                                    hp.ctypes.data_as(i32p), n_pairs, _ptr(out), _ptr(maps) if n_pairs else None),
+                    "align_attn_probe")
+        return out, maps
 
     # -- a9, a10 -------------------------------------------------------------------------------
     def gen_opts(self, max_new_tokens: int, timestamps: bool, suppress: Optional[Sequence[int]] = None,

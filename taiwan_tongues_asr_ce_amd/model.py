@@ -796,10 +796,14 @@ class WhisperModel:
                                     begin_suppress=bsup if p["suppress_blank"] else [],
                                     max_initial_timestamp_index=int(round(p["max_initial_timestamp"] / 0.02)), check_interval=4)
 
-    def _finish_window(self, fs: dict, clip_index: int, attempt, win_frames: int, p) -> List[Segment]:
+    def _finish_window(self, fs: dict, clip_index: int, attempt, win_frames: int, p, defer: Optional[list] = None) -> List[Segment]:
         """Turns one window's chosen attempt into segments and advances the file state `fs` (seek, previous tokens,
         prompt reset, segment counter).  The window's encoder state must still be resident at `clip_index` when word
-        timestamps are wanted."""
+        timestamps are wanted.
+        defer (a list; the continuous form with word_timestamps): the alignment is NOT run here.  A window with kept segments
+        appends one record to `defer` and returns []; the file state advances as always - seek, previous text and the segment
+        counter do not depend on the words - and `_deferred_segments(record, words)` builds the segments once the caller has
+        aligned the window.  A silent or empty window appends nothing."""
         eng, st = self.engine, self.special
         temp_used, toks, avg_lp, ns, cr = attempt
         seek = fs["seek"]
@@ -817,20 +821,27 @@ class WhisperModel:
             if s0 >= s1 or not text.strip():
                 continue
             kept.append(dict(start=s0, end=s1, tokens=list(stoks), text=text, eot=st.eot, words=None))
+        deferred = defer is not None and p["word_timestamps"] and bool(kept)
         if p["word_timestamps"] and kept:
             # faster-whisper add_word_timestamps: one alignment pass over the window's text tokens (the encoder
             # state of this window is still resident), then words are dealt to the segments
             text_tokens = [t for seg in kept for t in seg["tokens"] if t < st.eot]
             task_tok = st.translate if p["task"] == "translate" else st.transcribe
-            found = alignment.find_alignment(eng, self.tokenizer, st, clip_index, text_tokens, win_frames, self.alignment_heads,
-                                             fs.get("language", p["language"]), fs.get("lang_tok", p["lang_tok"]), task_tok)
-            alignment.add_word_timestamps(kept, found, time_offset)
-            for seg in kept:
-                seg["start"], seg["end"] = min(seg["start"], limit), min(seg["end"], limit)
+            if deferred:
+                defer.append(dict(fs=fs, kept=kept, text_tokens=text_tokens, frames=win_frames, offset=time_offset, limit=limit,
+                                  idx=fs["idx"], seek=seek, stats=(temp_used, avg_lp, cr, ns),
+                                  language=fs.get("language", p["language"]), lang_tok=fs.get("lang_tok", p["lang_tok"]), task_tok=task_tok))
+            else:
+                found = alignment.find_alignment(eng, self.tokenizer, st, clip_index, text_tokens, win_frames, self.alignment_heads,
+                                                 fs.get("language", p["language"]), fs.get("lang_tok", p["lang_tok"]), task_tok)
+                alignment.add_word_timestamps(kept, found, time_offset)
+                for seg in kept:
+                    seg["start"], seg["end"] = min(seg["start"], limit), min(seg["end"], limit)
         out = []
         for seg in kept:
-            out.append(Segment(fs["idx"], seek, round(seg["start"], 3), round(seg["end"], 3), seg["text"], seg["tokens"],
-                               temp_used, avg_lp, cr, ns, seg["words"]))
+            if not deferred:
+                out.append(Segment(fs["idx"], seek, round(seg["start"], 3), round(seg["end"], 3), seg["text"], seg["tokens"],
+                                   temp_used, avg_lp, cr, ns, seg["words"]))
             fs["idx"] += 1
             # faster-whisper's all_tokens: the tokens of every YIELDED segment, timestamp tokens included (the
             # previous-text prompt carries them), <|endoftext|> and the undecided tail after the last pair excluded
@@ -839,6 +850,32 @@ class WhisperModel:
             fs["prompt_reset"] = len(fs["prev"])  # prompt_reset_since: nothing carries over
         fs["seek"] += min(advance, win_frames) if advance > 0 else win_frames
         return out
+
+    @staticmethod
+    def _deferred_segments(rec: dict, words: List[dict]) -> List[Segment]:
+        """The segments of a window whose alignment `_finish_window(defer=...)` put off: words dealt to its kept segments as
+        `_finish_window` deals them, ids and statistics as recorded when the window settled."""
+        temp_used, avg_lp, cr, ns = rec["stats"]
+        alignment.add_word_timestamps(rec["kept"], words, rec["offset"])
+        out = []
+        for k, seg in enumerate(rec["kept"]):
+            s0, s1 = min(seg["start"], rec["limit"]), min(seg["end"], rec["limit"])
+            out.append(Segment(rec["idx"] + k, rec["seek"], round(s0, 3), round(s1, 3), seg["text"], seg["tokens"], temp_used, avg_lp,
+                               cr, ns, seg["words"]))
+        return out
+
+    def _align_held(self, s, recs: List[dict]) -> None:
+        """The windows that settled in one poll, each held by the session under rec["id"]: ONE Session.align call (first_row = the
+        sot sequence's length, num_frames = the window's frames, as find_alignment_batch builds them; every window with its own
+        language token), then each window's segments go to its file.  The call releases the clips."""
+        st = self.special
+        sots = [[st.sot, r["lang_tok"], r["task_tok"]] for r in recs]
+        seqs = [sot + [st.no_timestamps] + list(r["text_tokens"]) + [st.eot] for sot, r in zip(sots, recs)]
+        res = s.align([r["id"] for r in recs], seqs, [3] * len(recs), [int(r["frames"]) for r in recs], self.alignment_heads)
+        for k, r in enumerate(recs):
+            words = alignment.words_from_alignment(self.tokenizer, st, r["text_tokens"], res.start_frames[k] / alignment.TOKENS_PER_SECOND,
+                                                   res.logprobs[k], 3, r["language"])
+            r["fs"]["segments"].extend(self._deferred_segments(r, words))
 
     def _file_feature_max(self, audio: np.ndarray) -> float:
         """faster-whisper extracts the features of the whole (VAD-filtered) recording once, so the dynamic-range floor
@@ -912,8 +949,8 @@ class WhisperModel:
                         best_of: int = 5, compression_ratio_threshold: Optional[float] = 2.4, patience: float = 1.0,
                         hotwords: Optional[str] = None, prefix: Optional[str] = None, continuous: bool = False,
                         multilingual: bool = False, detect_in_session: bool = False, session_prefill: Union[int, bool] = 0,
-                        vad_filter: bool = False, vad_parameters: Optional[dict] = None, device_resample: bool = False
-                        ) -> List[Tuple[List[Segment], TranscriptionInfo]]:
+                        vad_filter: bool = False, vad_parameters: Optional[dict] = None, device_resample: bool = False,
+                        retry_held: Optional[bool] = None) -> List[Tuple[List[Segment], TranscriptionInfo]]:
         """Several FILES in lock step: every round takes the next 30-s window of each unfinished file and runs them as
         ONE engine pass (log-mel, encoder, beam search with one previous-text prompt per file), so a folder is
         transcribed at batch throughput while each file keeps exactly the sequential algorithm of `transcribe` — its
@@ -923,9 +960,18 @@ class WhisperModel:
         continuous=True: one continuous-batching beam session instead of lock-step passes (DESIGN.md "Long-form files in the
         session"): every file keeps one window in flight, a window that fails the thresholds goes back in at the next
         temperature (sampled attempts run in the session too), and a file's next window is submitted as soon as its current
-        one is settled.  Each file gets exactly `transcribe()`'s algorithm.  word_timestamps is not supported there: the
-        session can align now (Session.hold / Session.align, used by transcribe_stream and the streaming backend), but moving
-        this path and transcribe() onto the batched device alignment is a follow-up.
+        one is settled.  Each file gets exactly `transcribe()`'s algorithm.
+        continuous=True with word_timestamps=True: the session runs in hold mode with option
+        align_packed = 1.  A window that settles with kept segments stays held and its file's next window is submitted at once
+        (seek and previous text do not depend on the words); when a poll's results are handled, the windows that settled in it
+        are aligned in ONE Session.align call and their words dealt to their segments as `transcribe` deals them; a window that
+        settles silent or empty is released.  Nothing stays held across a poll.  The packed pass makes a window's word times
+        independent of the windows aligned with it: a file gets the same words alone and in any folder.
+        retry_held (continuous=True; default None = True with word_timestamps, else False): a window that fails its thresholds
+        goes up the temperature ladder with Session.retry on its HELD cross-KV - same prompt (carrying a language already
+        detected), budget, rows and seed as the re-submission - so a fallback attempt costs no encoder pass; False re-submits the
+        window as before.  retry_held=True without word_timestamps runs hold mode and releases settled windows.  Both need an
+        engine whose sessions can hold (Engine.session_hold).
 
         language: one code for every file (as before), None (detect every file) or one entry per file, each a code or None.
         The None files are detected from their first windows in batched passes BEFORE decoding starts - with continuous=True
@@ -960,9 +1006,13 @@ class WhisperModel:
             raise ValueError("continuous=True needs an engine with continuous-batching sessions (Engine.session)")
         if detect_in_session and not continuous:
             raise ValueError("detect_in_session=True needs continuous=True (the lock-step form detects from its resident passes)")
-        if continuous and word_timestamps:
-            raise ValueError("word_timestamps=True is not supported with continuous=True (the alignment pass needs the window's "
-                             "encoder state, which the session hands to the next window)")
+        if retry_held is None:
+            retry_held = bool(continuous and word_timestamps)
+        if retry_held and not continuous:
+            raise ValueError("retry_held=True needs continuous=True (the lock-step form re-decodes a failed window alone)")
+        if continuous and (word_timestamps or retry_held) and not getattr(eng, "session_hold", False):
+            raise ValueError("word_timestamps=True / retry_held=True with continuous=True need an engine whose sessions can hold "
+                             "finished windows (Engine.session_hold: Session.hold / align / retry)")
         beam = max(1, min(beam_size, 7, self.max_batch))
         per_pass = max(1, self.max_batch // beam)
         temps = tuple(temperature) if isinstance(temperature, (list, tuple)) else (float(temperature),)
@@ -996,6 +1046,7 @@ class WhisperModel:
             fs["file_max"] = self._file_feature_max(fs["audio"])   # whole-file dynamic-range floor, as `transcribe`
             files.append(fs)
         multilingual = bool(multilingual) and self.is_multilingual
+        session_stats = None   # Session.stats() of a continuous run in hold mode (word_timestamps / retry_held), in every file's info
         # files whose language the session itself finds: they skip the detection pass; "decided" = the file-level answer is known
         late = [l is None and bool(detect_in_session) and self.is_multilingual for l in langs]
         found = self._resolve_languages(["en" if w else l for l, w in zip(langs, late)], [fs["audio"] for fs in files], "file")
@@ -1003,7 +1054,8 @@ class WhisperModel:
             fs["language"], fs["lang_tok"], fs["lang_info"] = lang, self._lang_token(lang), (lang, lang_p, all_p)
             fs["decided"] = not w
         if continuous:
-            self._run_continuous(files, p, per_window=multilingual, session_prefill=session_prefill)
+            session_stats = self._run_continuous(files, p, per_window=multilingual, session_prefill=session_prefill,
+                                                 retry_held=bool(retry_held))
         while not continuous:
             active = [fs for fs in files if fs["seek"] < fs["n_total"]]
             if not active:
@@ -1052,7 +1104,7 @@ class WhisperModel:
                                      transcription_options=dict(beam_size=beam, task=task, without_timestamps=without_timestamps,
                                                                 condition_on_previous_text=condition_on_previous_text,
                                                                 initial_prompt=initial_prompt),
-                                     window_languages=fs.get("window_languages"))
+                                     window_languages=fs.get("window_languages"), session=session_stats)
             out.append((fs["segments"], info))
         return out
 
@@ -1060,14 +1112,16 @@ class WhisperModel:
         """(language, probability, all probabilities) of a SessionResult that was detected inside its session."""
         return LANGUAGES[r.language], float(r.language_probs[r.language]), self._ranked(r.language_probs)
 
-    def _run_continuous(self, files: List[dict], p: dict, per_window: bool = False, session_prefill: int = 0):
+    def _run_continuous(self, files: List[dict], p: dict, per_window: bool = False, session_prefill: int = 0, retry_held: bool = False):
         """transcribe_many(continuous=True): the windows of all files through one beam session, one window per file in flight.
         A window's attempts follow `_decode_with_fallback` (temperature 0: beam search of beam_size rows, or greedy with one;
         temperature > 0: best_of samples seeded as `transcribe` seeds them), its result `_finish_window`.
         A window of a file whose language is not decided yet (fs["decided"] False: detect_in_session), and with per_window
         (multilingual) every window, goes in with the language placeholder; the session's answer replaces it in the window's
-        prompt, so a fallback attempt carries the language already found."""
-        from .engine import GenResult, Session, TtasrError
+        prompt, so a fallback attempt carries the language already found.
+        p["word_timestamps"] or retry_held: hold mode (transcribe_many's docstring).  Every finished attempt is then held; it is
+        retried (retry_held), released (re-submitted, silent, empty, or no words wanted) or - settled with kept segments and words
+        wanted - aligned behind the poll's results with the others of the poll.  Without either, exactly the calls of before."""
         eng = self.engine
         temps, beam = p["temperatures"], p["beam_size"]
         if not 1 <= beam <= 7:
@@ -1080,7 +1134,7 @@ class WhisperModel:
             raise ValueError(f"best_of={p['best_of']}: a continuous session holds at most 7 rows per window")
         todo = [fs for fs in files if fs["seek"] < fs["n_total"]]
         if not todo:
-            return
+            return None
         n_ctx = self.dims.n_text_ctx
         opts = self._window_opts(1, 0, p)   # the session's rules; budgets and sot indices are per window
         eng.set_audio_ctx(0)
@@ -1088,8 +1142,36 @@ class WhisperModel:
         kw = dict(detect_language=True) if arm else {}   # armed only when a window asks for it
         if session_prefill:
             kw["prefill"] = int(session_prefill)          # prompts of at least that many positions: one admission pass, not steps
+        words = bool(p["word_timestamps"])
+        hold = words or retry_held
+        if words:
+            eng.set_option("align_packed", 1)   # read by every Session.align of the run; put back below
+        try:
+            return self._continuous_session(todo, p, opts, n_ctx, width, kw, per_window, rows_sampled, hold, retry_held)
+        finally:
+            if words:
+                eng.set_option("align_packed", 0)
+
+    def _continuous_session(self, todo, p, opts, n_ctx, width, kw, per_window, rows_sampled, hold, retry_held):
+        """The session of `_run_continuous`, open from here to the last window; -> in hold mode Session.stats() plus "windows" (windows
+        decoded) and "retries" (attempts that ran on a held clip's cross-KV), else None."""
+        from .engine import GenResult, Session, TtasrError
+        eng = self.engine
+        temps, beam = p["temperatures"], p["beam_size"]
         with eng.session(opts, n_ctx - 1, beam=width, patience=p["patience"], **kw) as s:
             inflight: Dict[int, dict] = {}
+            if hold:
+                s.hold()
+            settled: List[dict] = []   # this poll's windows that wait for their alignment (held)
+            count = dict(windows=0, retries=0)
+
+            def retry(fs: dict, held_id: int):
+                w = fs["window"]
+                temp = temps[len(w["attempts"])]
+                ids = s.retry([held_id], [w["prompt"]], [w["sot"]], max_new=[w["budget"]], temperature=[temp],
+                              rows=[rows_sampled if temp > 0.0 else beam], seed=[self._fallback_seed(fs["seek"], temp)])
+                inflight[ids[0]] = fs
+                count["retries"] += 1
 
             def submit(fs: dict):
                 w = fs["window"]
@@ -1105,6 +1187,7 @@ class WhisperModel:
                                       fs["prev"][fs["prompt_reset"]:], p["hotwords_tokens"], p["prefix_tokens"] if fs["seek"] == 0 else None)
                 fs["window"] = dict(prompt=pr, sot=si, budget=min(p["max_new"], n_ctx - len(pr)), attempts=[],
                                     frames=min(self.dims.n_frames, fs["n_total"] - fs["seek"]))
+                count["windows"] += 1
                 submit(fs)
 
             for fs in todo:
@@ -1130,14 +1213,32 @@ class WhisperModel:
                     w["attempts"].append((temp, toks, avg_lp, ns, cr))
                     if self._needs_fallback(avg_lp, ns, cr, p):
                         if len(w["attempts"]) < len(temps):
-                            submit(fs)   # the next temperature of the ladder
+                            if retry_held:
+                                retry(fs, r.id)   # the next temperature of the ladder, on the held cross-KV
+                            else:
+                                if hold:
+                                    s.release([r.id])
+                                submit(fs)        # the next temperature of the ladder
                             continue
                         attempt = self._best_attempt(w["attempts"], p)
                     else:
                         attempt = w["attempts"][-1]
-                    fs["segments"].extend(self._finish_window(fs, 0, attempt, w["frames"], p))
+                    n_wait = len(settled)
+                    fs["segments"].extend(self._finish_window(fs, 0, attempt, w["frames"], p, defer=settled if hold else None))
+                    if len(settled) > n_wait:
+                        settled[-1]["id"] = r.id          # stays held until the poll's alignment below
+                    elif hold:
+                        s.release([r.id])                 # silent, empty, or no words wanted
                     if fs["seek"] < fs["n_total"]:
                         next_window(fs)
+                if settled:                               # nothing stays held across a poll
+                    self._align_held(s, settled)
+                    settled.clear()
+            if not hold:
+                return None                               # without hold mode the session sees exactly the calls of before
+            stats = dict(s.stats())
+            stats["windows"], stats["retries"] = float(count["windows"]), float(count["retries"])
+            return stats
 
     # ------------------------------------------------------------------------------------------
     def _pass_languages(self, langs: Sequence[Optional[str]], info: List[Tuple[str, float]]) -> List[str]:

@@ -13,6 +13,11 @@ two forms returned identical segments (they need not: the lock-step form gives a
 beam search even at beam 1, the continuous form runs transcribe()'s per-file algorithm).
 
     python tools/longform_bench.py [--files 24] [--fallback-files 8] [--max-new 224] [--regime off|ref|both] [--out FILE]
+
+--word-timestamps [--retry-held {0,1}] (profiles/continuous_words.json) measures the continuous form only,
+in both regimes: without words (the form above), with words through the packed alignment pass, with words through the padded
+pass (a switch of this tool: the engine's option is forced to 0), with the other value of retry_held, and retry_held=True
+without words.  Alignment ms is the host time inside Session.align, which returns with its results on the host.
 """
 from __future__ import annotations
 
@@ -93,16 +98,34 @@ def make_engine_class(boost, counters):
             s = super().session(*a, **kw)
             counters["on_session"](s)
             return s
+
+        def set_option(self, key, value):
+            # bench-only switch: the words run through the PADDED alignment pass (what ttasr_session_align does with the option off)
+            if key == "align_packed" and counters.get("force_padded"):
+                value = 0
+            super().set_option(key, value)
     return BenchEngine
 
 
-def run(model, counters, files, kw, continuous, session_prefill=0):
-    for k in ("encode_ms", "decode_ms", "steps", "attempts"):
+def run(model, counters, files, kw, continuous, session_prefill=0, words=False, retry_held=None, padded=False):
+    for k in ("encode_ms", "decode_ms", "steps", "attempts", "align_ms", "align_calls", "align_clips"):
         counters[k] = 0
+    counters["force_padded"] = bool(padded)
     stats = {}
+    if words or retry_held is not None:
+        kw = dict(kw, word_timestamps=bool(words), retry_held=retry_held)
 
     def on_session(sess):   # the session's statistics are read just before it ends
-        close = sess.close
+        close, align = sess.close, sess.align
+
+        def timed_align(ids, *a, **k):   # Session.align returns with its results on the host: the host clock covers the pass
+            t0 = time.perf_counter()
+            r = align(ids, *a, **k)
+            counters["align_ms"] += (time.perf_counter() - t0) * 1e3
+            counters["align_calls"] += 1
+            counters["align_clips"] += len(ids)
+            return r
+        sess.align = timed_align
 
         def close_with_stats():
             if sess.open:
@@ -127,6 +150,10 @@ def run(model, counters, files, kw, continuous, session_prefill=0):
                   "decode_steps": int(stats["steps"]), "attempts": int(stats["clips_encoded"]),
                   "mean_live_rows_per_step": round(stats["live_row_steps"] / max(1.0, stats["steps"]), 2),
                   "encoder_passes": int(stats["encodes"])})
+        if words or retry_held is not None:
+            m.update({"word_timestamps": bool(words), "retry_held": retry_held, "align_pass": "padded" if padded else "packed",
+                      "align_ms": round(counters["align_ms"], 1), "align_calls": counters["align_calls"],
+                      "align_clips": counters["align_clips"], "words": sum(len(seg.words or []) for fs in segs for seg in fs)})
         if session_prefill:   # the admission passes of option session_prefill
             m.update({"session_prefill": int(session_prefill), "prefill_passes": int(stats["prefill_passes"]),
                       "prefill_clips": int(stats["prefill_clips"]), "prefill_positions": int(stats["prefill_positions"]),
@@ -155,6 +182,11 @@ def main():
     ap.add_argument("--session-prefill", type=int, default=0, metavar="N",
                     help="also run the continuous form with transcribe_many(session_prefill=N): prompts of at least N prefillable "
                          "positions come from an admission pass of the session instead of forced decode steps")
+    ap.add_argument("--word-timestamps", action="store_true",
+                    help="measure transcribe_many(continuous=True, word_timestamps=True) instead: the continuous form without words, "
+                         "words with the packed alignment pass, words with the padded pass (a bench-only switch), and --retry-held")
+    ap.add_argument("--retry-held", type=int, default=1, choices=[0, 1],
+                    help="with --word-timestamps: the value of retry_held for the words runs; the other value is measured as well")
     args = ap.parse_args()
     counters = {}
     model = WhisperModel(f"synthetic:{args.model}", device="cuda", compute_type="bfloat16", max_batch=args.max_batch,
@@ -175,7 +207,30 @@ def main():
     line = {"metric": "longform_audio_s_per_s", "model": args.model, "compute": "bf16", "xkv_fp8": args.xkv_fp8, "max_batch": args.max_batch, "beam": 5,
             "eot_boost": args.eot_boost, "max_new_tokens": args.max_new, "files": args.files,
             "audio_s": round(sum(len(f) for f in files) / 16000.0, 1)}
-    if args.regime in ("off", "both"):
+    if args.word_timestamps:
+        def strip(fs):   # what must not change when words are added
+            return [[(g.id, g.seek, g.tokens, g.temperature, g.avg_logprob, g.no_speech_prob) for g in f] for f in fs]
+        run(model, counters, warm, dict(off, max_new_tokens=16), True, words=True)
+        line["metric"] = "continuous_words_audio_s_per_s"
+        rh = bool(args.retry_held)
+        for name, fl, kw in (("thresholds_off", files, off), ("reference_defaults", files[: args.fallback_files], ref)):
+            if args.regime not in ("both", {"thresholds_off": "off", "reference_defaults": "ref"}[name]):
+                continue
+            s0, m0 = run(model, counters, fl, kw, True)
+            s1, m1 = run(model, counters, fl, kw, True, words=True, retry_held=rh)
+            s2, m2 = run(model, counters, fl, kw, True, words=True, retry_held=rh, padded=True)
+            s3, m3 = run(model, counters, fl, kw, True, words=True, retry_held=not rh)
+            s4, m4 = run(model, counters, fl, kw, True, retry_held=True)
+            line[name] = {"files": len(fl), "audio_s": round(sum(len(f) for f in fl) / 16000.0, 1), "continuous": m0,
+                          "words_packed": m1, "words_padded": m2, "words_packed_other_retry_held": m3, "no_words_retry_held": m4,
+                          "ratio_words_packed_over_continuous": round(m1["audio_s_per_s"] / m0["audio_s_per_s"], 3),
+                          "ratio_packed_over_padded": round(m1["audio_s_per_s"] / m2["audio_s_per_s"], 3),
+                          "segments_identical_to_continuous": [int(strip(x) == strip(s0)) for x in (s1, s2, s3, s4)],
+                          "word_starts_equal_packed_vs_padded": [
+                              int(sum(a.start == b.start for f, g in zip(s1, s2) for x, y in zip(f, g) for a, b in zip(x.words or [], y.words or []))),
+                              int(sum(len(x.words or []) for f in s1 for x in f))]}
+            print(json.dumps(line[name]), file=sys.stderr, flush=True)
+    elif args.regime in ("off", "both"):
         sa, a = run(model, counters, files, off, False)
         sb, b = run(model, counters, files, off, True)
         line["thresholds_off"] = {"lock_step": a, "continuous": b, "ratio": round(b["audio_s_per_s"] / a["audio_s_per_s"], 3),
@@ -185,7 +240,7 @@ def main():
             line["thresholds_off"].update({"continuous_prefill": pm, "ratio_prefill_over_continuous": round(pm["audio_s_per_s"] / b["audio_s_per_s"], 3),
                                            "files_identical_prefill": int(sum(x == y for x, y in zip(sb, sp)))})
         print(json.dumps(line["thresholds_off"]), file=sys.stderr, flush=True)
-    if args.regime in ("ref", "both"):
+    if not args.word_timestamps and args.regime in ("ref", "both"):
         ff = files[: args.fallback_files]
         sc, c = run(model, counters, ff, ref, False)
         sd, d = run(model, counters, ff, ref, True)
