@@ -644,6 +644,42 @@ TTASR_API int32_t ttasr_ingest_filter(int32_t rate, float* out, int32_t cap);
 TTASR_API int ttasr_ingest_pcm(ttasr_ctx* ctx, int32_t n, const void* const* raw_host, const int64_t* n_frames, const int32_t* rate,
                                const int32_t* channels, const int32_t* format, float* const* out_pcm_host);
 
+/* ---- coded WAVE files and the channel pick (G.711 A-law / mu-law, IMA ADPCM: what telephony and voice loggers write) ---------
+ * All three codecs decode to int16, and the int16 becomes a float as TTASR_PCM_S16 does (/ 32768).  Everything is integer-exact.
+ *   mu-law byte b (WAVE tag 7):  u = ~b & 0xFF, e = (u >> 4) & 7, m = u & 15, v = (((m << 3) + 0x84) << e) - 0x84;
+ *     the sample is -v if u & 0x80, else v (range +-32124).
+ *   A-law byte b (WAVE tag 6):  a = b ^ 0x55, e = (a >> 4) & 7, m = a & 15, v = (m << 4) + 8, and v = (v + 0x100) << (e - 1)
+ *     if e >= 1; the sample is v if a & 0x80, else -v (range +-32256).
+ *   IMA ADPCM (WAVE tag 0x11, 4 bits per sample): the data are blocks of block_align bytes.  A block starts with one 4-byte header
+ *     per channel, in channel order: int16 LE predictor, uint8 step index, one reserved byte; the header predictor is that
+ *     channel's first sample of the block.  The data follow in groups of 4 bytes per channel, interleaved channel by channel; a
+ *     group holds 8 samples of one channel, low nibble first.  Samples per block: spb = 1 + 2 (block_align / channels - 4).  Per
+ *     nibble n, with the 89-entry step table (7, 8, 9, ... 32767) and the index steps {-1, -1, -1, -1, 2, 4, 6, 8} taken at n & 7:
+ *     d = step >> 3, + step if n & 4, + step >> 1 if n & 2, + step >> 2 if n & 1; the predictor moves by -d if n & 8, else by +d,
+ *     and is clamped to int16; the index is clamped to [0, 88].  A header step index above 88 is read as 88.  Bytes behind the
+ *     last whole block are ignored; n_frames is at most blocks * spb (a `fact` chunk may make it shorter).
+ *   Channel pick: pick = -1 is the mean of ttasr_ingest_pcm (channels summed in order, one division); pick = c in [0, channels)
+ *     takes channel c's converted sample as is, with no division - the recording is then channel c as a mono recording.
+ *
+ * ttasr_ingest_wave: ttasr_ingest_pcm for the six TTASR_PCM_* codes above and the three below, with a pick per recording (pick =
+ *   NULL: -1 everywhere).  n_bytes[i] is what raw_host[i] holds; block_align[i] is read for TTASR_PCM_IMA4 only (block_align = NULL
+ *   is legal when no recording is IMA).  Refused like ttasr_ingest_pcm, before anything is enqueued and with the context left
+ *   usable, and also: a pick outside [-1, channels); IMA with a block_align that is no multiple of 4 channels, below 8 channels or
+ *   above 65536; n_frames beyond what n_bytes hold (IMA: beyond (n_bytes / block_align) spb); a NULL n_bytes.
+ *   G.711 is decoded arithmetically inside the ingest kernel.  IMA recordings go through a pre-pass first: one lane per (block,
+ *   channel), consecutive lanes on consecutive blocks of a channel, writes int16 [frames][channels] into a device scratch block of
+ *   the context (8 MiB, allocated by the first call that needs it, freed by ttasr_destroy), which the ingest kernel then reads as
+ *   TTASR_PCM_S16.  IMA chunks are cut on block boundaries: "ingest_chunk" counts frames and is rounded up to whole blocks.
+ *   For every accepted recording the result equals, bit for bit, ttasr_ingest_pcm fed the decoded int16 (with a pick: fed that
+ *   one channel as a mono recording), and depends neither on the chunk size nor on the other recordings of the call nor on its
+ *   place in it. */
+#define TTASR_PCM_ALAW 16
+#define TTASR_PCM_ULAW 17
+#define TTASR_PCM_IMA4 18
+TTASR_API int ttasr_ingest_wave(ttasr_ctx* ctx, int32_t n, const void* const* raw_host, const int64_t* n_bytes, const int64_t* n_frames,
+                                const int32_t* rate, const int32_t* channels, const int32_t* format, const int32_t* block_align,
+                                const int32_t* pick, float* const* out_pcm_host);
+
 /* ---- kernel-selection overrides (tests, A/B measurements) ----------------------------------------- */
 /* The release library reads NO environment variable; every deviation from the measured configuration is an explicit call.
  * Keys (value 0 / 1 unless stated; defaults in brackets): "flash" [1] MFMA flash attention in the encoder (0: the
@@ -677,8 +713,9 @@ TTASR_API int ttasr_ingest_pcm(ttasr_ctx* ctx, int32_t n, const void* const* raw
  * admission" above);
  * "align_packed" [0] (read by ttasr_session_align at call time) 1: the alignment pass over held clips runs packed and
  * pass-mate-independent (see ttasr_session_align); 0: the padded pass, unchanged;
- * "ingest_chunk" [0] (0 ... 2^30) input frames per chunk of ttasr_ingest_pcm, 0 = as many as the staging slots hold (results do
- * not depend on it, bit for bit: tests put chunk boundaries inside small inputs with it); "ingest_timing" [0] 1: ttasr_ingest_pcm
+ * "ingest_chunk" [0] (0 ... 2^30) input frames per chunk of ttasr_ingest_pcm / ttasr_ingest_wave (IMA: rounded up to whole blocks),
+ * 0 = as many as the staging slots hold (results do not depend on it, bit for bit: tests put chunk boundaries inside small inputs
+ * with it); "ingest_timing" [0] 1: ttasr_ingest_pcm
  * waits for every copy and kernel before it enqueues the next and leaves the host-clock split of the call in ttasr_phase_ms
  * (measurement only: the waits cost the overlap);
  * Drops the captured decode graphs (except "enc_kernel_timing", "refill_overlap", "session_prefill", "align_packed", "ingest_chunk" and "ingest_timing").  Unknown key or value out of range: TTASR_E_INVALID. */

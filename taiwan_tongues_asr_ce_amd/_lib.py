@@ -21,11 +21,13 @@ SYMBOLS = [
     "ttasr_session_detect_language", "ttasr_session_poll_lang", "ttasr_session_prefill_stats", "ttasr_session_retry",
     "ttasr_vad_load_tensor", "ttasr_vad_finalize", "ttasr_vad_probs",
     "ttasr_vad_stream_open", "ttasr_vad_stream_reset", "ttasr_vad_stream_close", "ttasr_vad_stream_push",
-    "ttasr_ingest_len", "ttasr_ingest_filter", "ttasr_ingest_pcm",
+    "ttasr_ingest_len", "ttasr_ingest_filter", "ttasr_ingest_pcm", "ttasr_ingest_wave",
 ]
 
 PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = range(6)   # TTASR_PCM_* of include/ttasr.h
 PCM_BYTES = (1, 2, 3, 4, 4, 8)                                    # bytes per sample, by format code
+PCM_ALAW, PCM_ULAW, PCM_IMA4 = 16, 17, 18                         # the coded formats of ttasr_ingest_wave
+CODED_BYTES = {PCM_ALAW: 1, PCM_ULAW: 1}                          # bytes per sample of the G.711 codes (IMA: 4 bits, in blocks)
 VAD_MAX_STREAMS = 1024    # TTASR_VAD_MAX_STREAMS of include/ttasr.h: open streams of one context (ttasr_vad_stream_*)
 VAD_CHUNK_FRAMES = 1024   # TTASR_VAD_CHUNK_FRAMES of include/ttasr.h: frames of one recording per time chunk of ttasr_vad_probs
 
@@ -134,6 +136,7 @@ def load() -> C.CDLL:
     lib.ttasr_ingest_filter.argtypes = [i32, f32p, i32]
     lib.ttasr_ingest_filter.restype = i32
     lib.ttasr_ingest_pcm.argtypes = [vp, i32, C.POINTER(vp), i64p, i32p, i32p, i32p, C.POINTER(vp)]
+    lib.ttasr_ingest_wave.argtypes = [vp, i32, C.POINTER(vp), i64p, i64p, i32p, i32p, i32p, i32p, i32p, C.POINTER(vp)]
     for s in SYMBOLS:
         f = getattr(lib, s)
         if s not in ("ttasr_destroy", "ttasr_last_error", "ttasr_version", "ttasr_ingest_len", "ttasr_ingest_filter"):

@@ -49,6 +49,9 @@ class MI355XWhisperASR(ASRInterface):
         # device_resample=True: a PATH handed to the pipeline is converted and resampled on the device (WhisperModel.transcribe);
         # the streaming chunks of `transcribe` below are 16 kHz PCM already and are not touched by it
         self.device_resample = bool(kwargs.get("device_resample", False))
+        # audio_channel: which channel of a multichannel FILE transcribe_path reads - None / "mix" = the mean (the reference
+        # service's audioChannel 0), "left" (1), "right" (2) or an index from 0; the streaming chunks are mono already
+        self.audio_channel = kwargs.get("audio_channel", None)
         # batched=True: transcribe_path decodes a file through the batched pipeline (WhisperModel.transcribe_batched): its VAD
         # chunks as independent groups of one session instead of 30-s windows in order
         self.batched = bool(kwargs.get("batched", False))
@@ -115,10 +118,12 @@ class MI355XWhisperASR(ASRInterface):
         with batched=True it is decoded by the batched pipeline."""
         opts = dict(self.default_transcribe_kwargs, language="zh")
         opts.update(kw)
+        pick = getattr(self, "audio_channel", None)
+        chan = {} if pick is None or "audio_channel" in opts else {"audio_channel": pick}
         if self.batched:   # groups carry no previous text: the pipeline has no condition_on_previous_text
             opts.pop("condition_on_previous_text", None)
-            return self.asr_pipeline.transcribe_batched(path, device_resample=self.device_resample, **opts)
-        return self.asr_pipeline.transcribe(path, device_resample=self.device_resample, **opts)
+            return self.asr_pipeline.transcribe_batched(path, device_resample=self.device_resample, **dict(chan, **opts))
+        return self.asr_pipeline.transcribe(path, device_resample=self.device_resample, **dict(chan, **opts))
 
     def _vad_is_active(self) -> bool:
         """True when vad_filter=True really filters: the model runs the VAD network on the device, the operator supplied a

@@ -22,6 +22,7 @@ decodable without librosa/PyAV, other containers are reported as per-file errors
 from __future__ import annotations
 
 import argparse
+import functools
 import glob
 import json
 import os
@@ -52,9 +53,9 @@ def find_original_transcript(audio_file: str) -> Optional[str]:
     return None
 
 
-def _load_audio(path: str):
+def _load_audio(path: str, channel: Optional[int] = None):
     from .model import decode_audio
-    return decode_audio(path)
+    return decode_audio(path, channel=channel)
 
 
 def _probe(path: str) -> str:
@@ -144,8 +145,12 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
                          group_files: int = 0, pipeline_depth: int = 0, continuous: bool = False,
                          cross_kv_fp8: bool = False, language: Optional[str] = TRANSCRIBE_KWARGS["language"],
                          detect_in_session: bool = False, session_prefill: int = 0, vad_model=None,
-                         device_resample: bool = False, batched: bool = False, word_timestamps: bool = False) -> Optional[Dict]:
-    """word_timestamps (`--word-timestamps`, with the lock-step form or continuous; not with batched): every file's segments are
+                         device_resample: bool = False, batched: bool = False, word_timestamps: bool = False,
+                         audio_channel=None) -> Optional[Dict]:
+    """audio_channel (`--audio-channel mix|left|right|N`): None / "mix" averages a file's channels as before; "left", "right" or
+    an index from 0 transcribes that channel alone (two-party call recordings; the reference service's audioChannel 0 / 1 / 2 is
+    mix / left / right).  On the host loader and, with device_resample, in the group's one device call.
+    word_timestamps (`--word-timestamps`, with the lock-step form or continuous; not with batched): every file's segments are
     transcribed with words (continuous: one Session.align call per poll through the packed, pass-mate-independent alignment
     pass, WhisperModel.transcribe_many(continuous=True, word_timestamps=True)) and written to `<name>_words.json` beside
     `<name>_asr.txt`; texts and scores do not change.
@@ -174,6 +179,12 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
         if int(pipeline_depth or getattr(model, "pipeline_depth", 1)) > 1:
             log("continuous mode runs one session on one engine context: pipeline depth 1")
         pipeline_depth = 1
+    from .model import parse_audio_channel
+    pick = parse_audio_channel(audio_channel)
+    if pick is not None:
+        if load_audio is not _load_audio:
+            raise ValueError("audio_channel goes with the built-in loader (a custom load_audio picks its own channel)")
+        load_audio = functools.partial(_load_audio, channel=pick)
     files = list_audio_files(folder_path)
     if not files:
         log(f"no audio files in {folder_path}")
@@ -208,6 +219,8 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
                 kw["session_prefill"] = int(session_prefill)
         if device_resample:
             kw["device_resample"] = True
+            if pick is not None:
+                kw["audio_channel"] = pick
         if word_timestamps:
             kw["word_timestamps"] = True
         depth0 = max(1, int(pipeline_depth or getattr(model, "pipeline_depth", 1)))
@@ -319,7 +332,20 @@ def build_parser() -> argparse.ArgumentParser:
                     help="opt-in: convert, downmix and resample each group's files in one device call instead of file by file on "
                          "the host (RIFF/WAVE of any PCM / float format, other containers through soundfile; rates the device "
                          "does not take fall back to the host path per file)")
+    ap.add_argument("--audio-channel", default="mix", metavar="{mix,left,right,N}", type=_audio_channel_arg,
+                    help="which channel of a multichannel file is transcribed: mix = the mean of all (default), left / right = "
+                         "channel 0 / 1, N = channel N counted from 0 (the reference service's audioChannel 0 / 1 / 2 is mix / "
+                         "left / right); a file without that channel is that file's error")
     return ap
+
+
+def _audio_channel_arg(value: str) -> str:
+    from .model import parse_audio_channel
+    try:
+        parse_audio_channel(value)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return value
 
 
 def main(argv=None) -> int:
@@ -346,7 +372,7 @@ def main(argv=None) -> int:
                          cross_kv_fp8=args.xkv_fp8, language=None if args.language == "auto" else args.language,
                          detect_in_session=args.detect_in_session, session_prefill=args.session_prefill,
                          vad_model=args.vad_model, device_resample=args.device_resample, batched=args.batched,
-                         word_timestamps=args.word_timestamps)
+                         word_timestamps=args.word_timestamps, audio_channel=args.audio_channel)
     return 0
 
 

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import alignment, vad
 from .config import HOP, SAMPLE_RATE
-from .model import LANGUAGES, Segment, TranscriptionInfo, Word, decode_audio, select_language
+from .model import LANGUAGES, Segment, TranscriptionInfo, Word, decode_audio, parse_audio_channel, select_language
 
 
 def clip_groups(clip_timestamps, n_samples: int, max_samples: int) -> List[Dict]:
@@ -156,11 +156,12 @@ class BatchedInferencePipeline:
                    without_timestamps: bool = True, word_timestamps: bool = False, multilingual: bool = False,
                    language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1,
                    vad_filter: bool = True, vad_parameters=None, chunk_length: Optional[float] = None,
-                   clip_timestamps=None, batch_size: Optional[int] = None, device_resample: bool = False,
+                   clip_timestamps=None, batch_size: Optional[int] = None, device_resample: bool = False, audio_channel=None,
                    session_prefill: Union[int, bool] = 0, retry_held: bool = True, **kwargs
                    ) -> Tuple[Iterator[Segment], TranscriptionInfo]:
-        """The keyword surface of faster-whisper's BatchedInferencePipeline.transcribe; device_resample, session_prefill and
-        retry_held are extensions of this build.  retry_held=False releases a failing group and submits it again (one more
+        """The keyword surface of faster-whisper's BatchedInferencePipeline.transcribe; device_resample, audio_channel (path
+        input only: one channel of the file instead of the mean, WhisperModel.transcribe), session_prefill and retry_held are
+        extensions of this build.  retry_held=False releases a failing group and submits it again (one more
         encoder pass per attempt): the A/B switch, and the form for engines without Session.retry.
         info.chunks lists the groups with their attempts; info.session is filled when the iterator is exhausted."""
         from .engine import session_prefill_value
@@ -179,8 +180,11 @@ class BatchedInferencePipeline:
         session_prefill = session_prefill_value(session_prefill)
         if not callable(getattr(m.engine, "session", None)):
             raise ValueError("the batched pipeline needs an engine with continuous-batching sessions (Engine.session)")
+        pick = parse_audio_channel(audio_channel)
         if isinstance(audio, str):
-            audio = m.decode_audio_many([audio])[0] if device_resample else decode_audio(audio)
+            audio = m.decode_audio_many([audio], audio_channel=pick)[0] if device_resample else decode_audio(audio, channel=pick)
+        elif pick is not None:
+            raise ValueError("audio_channel picks a channel of a file: an array input is already mono")
         audio = np.asarray(audio)
         if audio.ndim != 1:
             raise ValueError(f"audio must be mono float32 [n] @16 kHz, got shape {audio.shape}")

@@ -42,7 +42,7 @@ struct Slot {              // where one named tensor lands on the device
 
 struct Session;            // continuous-batching session state (engine_refill.hip)
 struct VadState;           // voice-activity network: weights, scratch, staging and streams of one context (engine_vad.hip)
-struct IngestState;        // file ingest: tap tables per rate and the chunk slots of one context (engine_ingest.hip)
+struct IngestState;        // file ingest: tap tables per rate, the chunk slots and the IMA scratch of one context (engine_ingest.hip)
 // What run_decode_rows reads about the rows of a step, and (with the batch, the mode and the e4m3 state) what a captured step
 // graph is keyed on.  Installed and restored by SearchScope only.
 struct StepShape {
@@ -184,7 +184,7 @@ struct ttasr_ctx {
   // voice-activity network (engine_vad.hip): created by the first ttasr_vad_load_tensor, freed by ttasr_destroy; per context,
   // outside the weight-share bookkeeping
   ttasr_detail::VadState* vad = nullptr;
-  // file ingest (engine_ingest.hip): created by the first ttasr_ingest_pcm, freed by ttasr_destroy.  Options: ingest_chunk = input
+  // file ingest (engine_ingest.hip): created by the first ttasr_ingest_pcm / ttasr_ingest_wave, freed by ttasr_destroy.  Options: ingest_chunk = input
   // frames per chunk (0: what the slots hold), ingest_timing = 1: the chunks run one after the other and the call leaves its
   // host-clock phase split in phase_ms
   ttasr_detail::IngestState* ingest = nullptr;

@@ -1,6 +1,6 @@
 // libttasr: file ingest behind the C ABI (one of the engine translation units, see engine_ctx.hpp): the filter design in double,
-// the per-rate tap tables of a context, its device and pinned chunk slots, and the chunk loop of ttasr_ingest_pcm.  The kernel is
-// kernels_ingest.hip; the result is the text of include/ttasr.h.  Nothing here touches mel, encoder, search or graph state, and
+// the per-rate tap tables of a context, its device and pinned chunk slots, the IMA scratch block, and the chunk loop of
+// ttasr_ingest_pcm / ttasr_ingest_wave.  The kernels are kernels_ingest.hip; the result is the text of include/ttasr.h.  Nothing here touches mel, encoder, search or graph state, and
 // no model weights are needed: the call's only shared resource is the context's stream.
 #include "engine_ctx.hpp"
 #include "ingest.hpp"
@@ -13,8 +13,13 @@ constexpr int kIngestSlots = 4;                       // chunks in flight: stagi
 constexpr size_t kIngestInBytes = (size_t)8 << 20;    // raw bytes of one chunk slot
 constexpr size_t kIngestOutFloats = (size_t)1 << 20;  // results of one chunk slot
 constexpr int64_t kIngestMaxFrames = (int64_t)1 << 40;
+constexpr size_t kIngestScratchBytes = (size_t)8 << 20;   // decoded int16 of one IMA chunk (the stream runs chunk after chunk: one block)
+constexpr int kImaMaxBlockAlign = 65536;
 
 static const int kPcmBytes[6] = {1, 2, 3, 4, 4, 8};   // bytes per sample of the formats, in the order of their codes
+
+static bool is_pcm(int32_t f) { return f >= TTASR_PCM_U8 && f <= TTASR_PCM_F64; }
+static bool is_g711(int32_t f) { return f == TTASR_PCM_ALAW || f == TTASR_PCM_ULAW; }
 
 // What a rate decides: the ratio, the filter and the tile.  ok = false: the rate is not accepted.
 struct IngestPlan {
@@ -77,6 +82,7 @@ struct IngestState {
   std::map<int32_t, IngestFilter> filters;   // per rate: the phase-major table [up][L] on the device (its own allocation)
   char* dev = nullptr;                       // [kIngestSlots] raw | [kIngestSlots] results
   char* pinned = nullptr;                    // the same layout in pinned host memory
+  int16_t* scratch = nullptr;                // kIngestScratchBytes: the decoded chunk of an IMA recording (first IMA call)
   hipEvent_t done[kIngestSlots] = {};
 };
 
@@ -85,6 +91,7 @@ void ingest_free(ttasr_ctx* c) {
   for (auto& f : c->ingest->filters) if (f.second.dev) hipFree(f.second.dev);
   if (c->ingest->dev) hipFree(c->ingest->dev);
   if (c->ingest->pinned) hipHostFree(c->ingest->pinned);
+  if (c->ingest->scratch) hipFree(c->ingest->scratch);
   for (auto& e : c->ingest->done) if (e) hipEventDestroy(e);
   delete c->ingest;
   c->ingest = nullptr;
@@ -132,15 +139,45 @@ static int64_t floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a +
 
 struct IngestPending { bool live = false; float* dst = nullptr; size_t n = 0; };
 
-static int ingest_pcm(ttasr_ctx* c, int32_t n, const void* const* raw, const int64_t* n_frames, const int32_t* rate,
-                      const int32_t* channels, const int32_t* format, float* const* out) {
+static int ingest_scratch(ttasr_ctx* c) {
+  IngestState* g = c->ingest;
+  if (g->scratch) return 0;
+  const hipError_t e = hipMalloc((void**)&g->scratch, kIngestScratchBytes);
+  if (e != hipSuccess) { g->scratch = nullptr; (void)hipGetLastError(); return fail(c, TTASR_E_NOMEM, "ingest IMA scratch (%zu bytes): %s", kIngestScratchBytes, hipGetErrorString(e)); }
+  return 0;
+}
+
+// The call behind both entry points.  `wave` = ttasr_ingest_wave: the coded formats are legal, n_bytes is there and checked,
+// block_align and pick may be NULL (no IMA recording / the mean everywhere).  ttasr_ingest_pcm: the three are NULL.
+static int ingest_run(ttasr_ctx* c, bool wave, int32_t n, const void* const* raw, const int64_t* n_bytes, const int64_t* n_frames,
+                      const int32_t* rate, const int32_t* channels, const int32_t* format, const int32_t* block_align,
+                      const int32_t* pick, float* const* out) {
   if (n < 0) return fail(c, TTASR_E_INVALID, "n %d is negative", n);
   if (n == 0) return TTASR_OK;
-  if (!raw || !n_frames || !rate || !channels || !format || !out) return fail(c, TTASR_E_INVALID, "NULL argument");
+  if (!raw || !n_frames || !rate || !channels || !format || !out || (wave && !n_bytes)) return fail(c, TTASR_E_INVALID, "NULL argument");
+  bool any_ima = false;
   for (int i = 0; i < n; ++i) {
     if (n_frames[i] < 0 || n_frames[i] > kIngestMaxFrames) return fail(c, TTASR_E_INVALID, "recording %d: %lld frames outside [0, 2^40]", i, (long long)n_frames[i]);
     if (channels[i] < 1 || channels[i] > 8) return fail(c, TTASR_E_INVALID, "recording %d: %d channels outside [1, 8]", i, channels[i]);
-    if (format[i] < TTASR_PCM_U8 || format[i] > TTASR_PCM_F64) return fail(c, TTASR_E_INVALID, "recording %d: unknown sample format %d", i, format[i]);
+    const bool ima = wave && format[i] == TTASR_PCM_IMA4;
+    if (!is_pcm(format[i]) && !(wave && (is_g711(format[i]) || ima))) return fail(c, TTASR_E_INVALID, "recording %d: unknown sample format %d", i, format[i]);
+    if (wave) {
+      const int32_t pk = pick ? pick[i] : -1;
+      if (pk < -1 || pk >= channels[i]) return fail(c, TTASR_E_INVALID, "recording %d: pick %d outside [-1, %d)", i, pk, channels[i]);
+      if (n_bytes[i] < 0) return fail(c, TTASR_E_INVALID, "recording %d: %lld bytes", i, (long long)n_bytes[i]);
+      int64_t held;
+      if (ima) {
+        if (!block_align) return fail(c, TTASR_E_INVALID, "recording %d: IMA ADPCM without block_align", i);
+        const int32_t ba = block_align[i];
+        if (ba < 8 * channels[i] || ba > kImaMaxBlockAlign || ba % (4 * channels[i]))
+          return fail(c, TTASR_E_INVALID, "recording %d: IMA block_align %d is no multiple of %d in [%d, %d]", i, ba, 4 * channels[i], 8 * channels[i], kImaMaxBlockAlign);
+        held = n_bytes[i] / ba * ima_spb(ba, channels[i]);
+        any_ima = true;
+      } else {
+        held = n_bytes[i] / ((is_g711(format[i]) ? 1 : kPcmBytes[format[i]]) * (int64_t)channels[i]);
+      }
+      if (n_frames[i] > held) return fail(c, TTASR_E_INVALID, "recording %d: %lld frames, but %lld bytes hold %lld", i, (long long)n_frames[i], (long long)n_bytes[i], (long long)held);
+    }
     if (!ingest_plan(rate[i]).ok)
       return fail(c, TTASR_E_INVALID, "recording %d: rate %d is not accepted (max(up, down) of the ratio to 16000 must be at most %d)", i, rate[i], kIngestMaxR);
     if (n_frames[i] > 0 && (!raw[i] || !out[i])) return fail(c, TTASR_E_INVALID, "recording %d: NULL sample or output row with %lld frames", i, (long long)n_frames[i]);
@@ -150,6 +187,7 @@ static int ingest_pcm(ttasr_ctx* c, int32_t n, const void* const* raw, const int
   if (!c->ingest) c->ingest = new IngestState();
   IngestState* g = c->ingest;
   TRY(ingest_blocks(c));
+  if (any_ima) TRY(ingest_scratch(c));
   hipStream_t s = c->stream;
   char* const d_in = g->dev; char* const d_out = g->dev + kIngestSlots * kIngestInBytes;
   char* const p_in = g->pinned; char* const p_out = g->pinned + kIngestSlots * kIngestInBytes;
@@ -173,12 +211,23 @@ static int ingest_pcm(ttasr_ctx* c, int32_t n, const void* const* raw, const int
     const IngestFilter* f = nullptr;
     TRY(ingest_filter_dev(c, rate[i], &f));
     const IngestPlan& P = f->plan;
-    const int64_t nfr = n_frames[i], fb = (int64_t)kPcmBytes[format[i]] * channels[i];
+    const bool ima = format[i] == TTASR_PCM_IMA4;
+    const int64_t ba = ima ? block_align[i] : 0, spb = ima ? ima_spb((int)ba, channels[i]) : 1;
+    const int64_t nfr = n_frames[i], fb = ima ? 0 : (int64_t)(is_g711(format[i]) ? 1 : kPcmBytes[format[i]]) * channels[i];
     const int64_t halo = 2 * (int64_t)P.half / P.up + 2;
     const int64_t n_out = ceil_div(nfr * P.up, P.down);
-    // frames per chunk: what the raw slot holds beside the halo and what the result slot holds, or the option when it is smaller
-    int64_t C = std::min<int64_t>((int64_t)kIngestInBytes / fb - halo, ((int64_t)kIngestOutFloats - 2) * P.down / P.up);
-    if (c->ingest_chunk > 0) C = std::min<int64_t>(C, c->ingest_chunk);
+    // frames per chunk: what the raw slot holds beside the halo and what the result slot holds, or the option when it is smaller.
+    // IMA: whole blocks - the raw slot holds blocks, the scratch block their int16, and the halo may reach into one more block on
+    // either side; the option is rounded up to blocks
+    int64_t C;
+    if (ima) {
+      const int64_t cap = std::min<int64_t>((int64_t)kIngestInBytes / ba * spb, (int64_t)kIngestScratchBytes / (2 * channels[i]));
+      C = std::min<int64_t>(cap - halo - 2 * spb, ((int64_t)kIngestOutFloats - 2) * P.down / P.up) / spb * spb;
+      if (c->ingest_chunk > 0) C = std::min<int64_t>(C, ceil_div(c->ingest_chunk, spb) * spb);
+    } else {
+      C = std::min<int64_t>((int64_t)kIngestInBytes / fb - halo, ((int64_t)kIngestOutFloats - 2) * P.down / P.up);
+      if (c->ingest_chunk > 0) C = std::min<int64_t>(C, c->ingest_chunk);
+    }
     if (C < 1) return fail(c, TTASR_E_INVALID, "recording %d: no chunk of rate %d fits the staging slots", i, rate[i]);
     const int64_t chunks = ceil_div(nfr, C);
     for (int64_t ch = 0; ch < chunks; ++ch, ++job) {
@@ -188,24 +237,42 @@ static int ingest_pcm(ttasr_ctx* c, int32_t n, const void* const* raw, const int
       // the frames these outputs read, cut at the ends of the recording
       const int64_t lo = std::max<int64_t>(ceil_div(kb * P.down - P.half, P.up), 0);
       const int64_t hi = std::min<int64_t>(floor_div((ke - 1) * P.down + P.half, P.up), nfr - 1);
-      const int64_t nf = std::max<int64_t>(hi - lo + 1, 0);
-      if (nf * fb > (int64_t)kIngestInBytes || ke - kb > (int64_t)kIngestOutFloats)
+      int64_t nf = std::max<int64_t>(hi - lo + 1, 0);
+      // what goes up: the frames [lo, lo + nf), or for IMA the whole blocks that hold them - the staged range then begins with
+      // block b_lo's first frame and ends with the recording or with block b_hi
+      int64_t f0 = lo, src = lo * fb, bytes = nf * fb, n_blk = 0;
+      if (ima) {
+        const int64_t b_lo = lo / spb, b_hi = nf ? hi / spb : b_lo - 1;
+        n_blk = b_hi - b_lo + 1;
+        f0 = b_lo * spb; src = b_lo * ba; bytes = n_blk * ba;
+        nf = n_blk ? std::min<int64_t>((b_hi + 1) * spb, nfr) - f0 : 0;
+        if (nf * 2 * channels[i] > (int64_t)kIngestScratchBytes)
+          return fail(c, TTASR_E_INVALID, "recording %d: chunk %lld exceeds the IMA scratch (%lld frames)", i, (long long)ch, (long long)nf);
+      }
+      if (bytes > (int64_t)kIngestInBytes || ke - kb > (int64_t)kIngestOutFloats || (wave && src + bytes > n_bytes[i]))
         return fail(c, TTASR_E_INVALID, "recording %d: chunk %lld exceeds its slot (%lld frames, %lld outputs)", i, (long long)ch, (long long)nf, (long long)(ke - kb));
       const int slot = (int)(job % kIngestSlots);
       TRY(retire(slot));
       auto t0 = clk::now();
-      memcpy(p_in + (size_t)slot * kIngestInBytes, (const char*)raw[i] + lo * fb, (size_t)(nf * fb));
+      memcpy(p_in + (size_t)slot * kIngestInBytes, (const char*)raw[i] + src, (size_t)bytes);
       ms[0] += since(t0);
       t0 = clk::now();
-      if (nf) HIPCHK(c, hipMemcpyAsync(d_in + (size_t)slot * kIngestInBytes, p_in + (size_t)slot * kIngestInBytes, (size_t)(nf * fb), hipMemcpyHostToDevice, s));
+      if (bytes) HIPCHK(c, hipMemcpyAsync(d_in + (size_t)slot * kIngestInBytes, p_in + (size_t)slot * kIngestInBytes, (size_t)bytes, hipMemcpyHostToDevice, s));
       if (timing) { HIPCHK(c, hipStreamSynchronize(s)); ms[1] += since(t0); t0 = clk::now(); }
       IngestJob J;
       J.raw = (const uint8_t*)(d_in + (size_t)slot * kIngestInBytes);
       J.out = (float*)(d_out + (size_t)slot * kIngestOutFloats * 4);
       J.taps = f->dev;
-      J.n_frames = nfr; J.f0 = lo; J.k_begin = kb; J.nf = (int32_t)nf; J.n_out = (int32_t)(ke - kb);
+      J.n_frames = nfr; J.f0 = f0; J.k_begin = kb; J.nf = (int32_t)nf; J.n_out = (int32_t)(ke - kb);
       J.up = P.up; J.down = P.down; J.half = P.half; J.L = P.L; J.channels = channels[i]; J.format = format[i];
-      J.tile = P.tile; J.span = P.span;
+      J.tile = P.tile; J.span = P.span; J.pick = pick ? pick[i] : -1;
+      if (ima) {   // decode the staged blocks into the scratch block; the filter kernel reads that as s16
+        ImaJob D;
+        D.raw = J.raw; D.out = g->scratch; D.n_frames = nf;
+        D.n_blocks = (int32_t)n_blk; D.channels = channels[i]; D.block_align = (int32_t)ba; D.spb = (int32_t)spb;
+        launch_ima_decode(D, s);
+        J.raw = (const uint8_t*)g->scratch; J.format = TTASR_PCM_S16;
+      }
       launch_ingest(J, s);
       if (timing) { HIPCHK(c, hipStreamSynchronize(s)); ms[2] += since(t0); t0 = clk::now(); }
       HIPCHK(c, hipMemcpyAsync(p_out + (size_t)slot * kIngestOutFloats * 4, J.out, (size_t)J.n_out * 4, hipMemcpyDeviceToHost, s));
@@ -250,7 +317,16 @@ int ttasr_ingest_pcm(ttasr_ctx* c, int32_t n, const void* const* raw, const int6
                      const int32_t* channels, const int32_t* format, float* const* out_pcm) {
   return guarded(c, [&]() -> int {
   if (!c) return TTASR_E_INVALID;
-  return ingest_pcm(c, n, raw, n_frames, rate, channels, format, out_pcm);
+  return ingest_run(c, false, n, raw, nullptr, n_frames, rate, channels, format, nullptr, nullptr, out_pcm);
+  });
+}
+
+int ttasr_ingest_wave(ttasr_ctx* c, int32_t n, const void* const* raw, const int64_t* n_bytes, const int64_t* n_frames,
+                      const int32_t* rate, const int32_t* channels, const int32_t* format, const int32_t* block_align,
+                      const int32_t* pick, float* const* out_pcm) {
+  return guarded(c, [&]() -> int {
+  if (!c) return TTASR_E_INVALID;
+  return ingest_run(c, true, n, raw, n_bytes, n_frames, rate, channels, format, block_align, pick, out_pcm);
   });
 }
 

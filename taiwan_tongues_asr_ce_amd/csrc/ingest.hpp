@@ -15,15 +15,31 @@ constexpr int kIngestMaxTile = 4096;         // outputs per workgroup, at most
 // One launch: the outputs [k_begin, k_begin + n_out) of one recording from the frames [f0, f0 + nf) of it that `raw` holds
 // (interleaved, in the file's sample format).  Frames outside [0, n_frames) are zeros; a frame inside the recording but outside
 // the staged range reads as zero as well (the host never asks for one: the guard keeps a wrong host off foreign memory).
+// pick = -1: the mean of the channels; pick = c: channel c as it is.  The formats are the six TTASR_PCM_* sample formats and the
+// two G.711 codes; an IMA recording arrives here as the TTASR_PCM_S16 its pre-pass wrote.
 struct IngestJob {
   const uint8_t* raw;      // device, staged frames
   float* out;              // device, n_out floats
   const float* taps;       // device, phase-major [up][L]; nullptr: no filter (rate 16000), out[k] = mono[k]
   int64_t n_frames, f0, k_begin;
   int32_t nf, n_out, up, down, half, L, channels, format, tile, span;
+  int32_t pick = -1;
 };
 
 // Staged floats a tile of `tile` outputs reads: floor(tile * down / up) + floor(2 * half / up) + 2.
 inline int64_t ingest_span(int64_t tile, int up, int down, int half) { return tile * down / up + 2 * (int64_t)half / up + 2; }
 
 void launch_ingest(const IngestJob& j, hipStream_t s);
+
+// The IMA ADPCM pre-pass: `n_blocks` whole blocks of `block_align` bytes at `raw` -> int16 [frames][channels] at `out`, block b's
+// sample s at frame b * spb + s; frames from `n_frames` on (the cut of the last block, the end of the scratch) are not written.
+struct ImaJob {
+  const uint8_t* raw;      // device, 4-byte aligned
+  int16_t* out;            // device, n_frames * channels int16
+  int64_t n_frames;
+  int32_t n_blocks, channels, block_align, spb;
+};
+
+inline int ima_spb(int block_align, int channels) { return 1 + 2 * (block_align / channels - 4); }
+
+void launch_ima_decode(const ImaJob& j, hipStream_t s);

@@ -1,4 +1,4 @@
-// File ingest (include/ttasr.h ttasr_ingest_pcm): raw interleaved samples -> float32 mono 16 kHz in one kernel.
+// File ingest (include/ttasr.h ttasr_ingest_pcm / ttasr_ingest_wave): raw interleaved samples -> float32 mono 16 kHz in one kernel.
 //
 //   ingest_kernel   one 256-thread workgroup per tile of consecutive outputs of one recording.  The workgroup stages the input
 //                   span of its tile into LDS - raw samples read with consecutive lanes on consecutive frames, converted to
@@ -6,6 +6,10 @@
 //                   accumulates its outputs in f32 over the taps of its phase row, input index ascending.  No atomics; an output's
 //                   operands and their order are a function of its index alone, so neither the tile length nor the chunk, the
 //                   number of recordings or a recording's place in the call can change a bit of it.
+//
+//   ima_decode_kernel  the pre-pass of IMA ADPCM recordings: one lane per (block, channel) walks its block - a serial chain of
+//                   predictor and step index - and writes int16 [frames][channels]; ingest_kernel then reads that as s16.  Lane t
+//                   takes block t % n_blocks of channel t / n_blocks: consecutive lanes read consecutive blocks of one channel.
 //
 // The taps are read from the phase-major table in global memory (at most 84 KiB per rate: it lives in L2 and the vector L1).  With
 // up == 1 there is one row and the tap address is wave-uniform: the UP1 instance reads it through the scalar unit.  With up > 1
@@ -22,7 +26,8 @@ __device__ __forceinline__ int64_t floor_div(int64_t a, int64_t b) {   // b > 0
 }
 
 // One sample as decode_audio converts it: the integer formats scaled by a power of two (exact), 32-bit integers and doubles rounded
-// to float32 (nearest even) first.  Packed 24-bit samples are read byte by byte: they are not dword-aligned.
+// to float32 (nearest even) first.  Packed 24-bit samples are read byte by byte: they are not dword-aligned.  The two G.711 laws
+// expand a byte to its int16 with shifts and adds (the header's formulas; no table), then scale as s16 does.
 template <int FMT>
 __device__ __forceinline__ float ingest_sample(const uint8_t* __restrict__ raw, int64_t idx) {
   if constexpr (FMT == TTASR_PCM_U8) return ((float)raw[idx] - 128.0f) * (1.0f / 128.0f);
@@ -33,12 +38,23 @@ __device__ __forceinline__ float ingest_sample(const uint8_t* __restrict__ raw, 
     return (float)v * (1.0f / 8388608.0f);
   } else if constexpr (FMT == TTASR_PCM_S32) return (float)((const int32_t*)raw)[idx] * (1.0f / 2147483648.0f);
   else if constexpr (FMT == TTASR_PCM_F32) return ((const float*)raw)[idx];
-  else return (float)((const double*)raw)[idx];
+  else if constexpr (FMT == TTASR_PCM_ULAW) {
+    const int u = ~(int)raw[idx] & 0xFF, e = (u >> 4) & 7, m = u & 15;
+    const int v = (((m << 3) + 0x84) << e) - 0x84;
+    return (float)((u & 0x80) ? -v : v) * (1.0f / 32768.0f);
+  } else if constexpr (FMT == TTASR_PCM_ALAW) {
+    const int a = (int)raw[idx] ^ 0x55, e = (a >> 4) & 7, m = a & 15;
+    int v = (m << 4) + 8;
+    if (e >= 1) v = (v + 0x100) << (e - 1);
+    return (float)((a & 0x80) ? v : -v) * (1.0f / 32768.0f);
+  } else return (float)((const double*)raw)[idx];
 }
 
-// mono[i] of the staged range: the channels summed in order, then one division (what numpy's mean over the channel axis does)
+// mono[i] of the staged range: the channels summed in order, then one division (what numpy's mean over the channel axis does);
+// with a pick, that channel's sample as it is
 template <int FMT>
-__device__ __forceinline__ float ingest_frame(const uint8_t* __restrict__ raw, int64_t r, int channels) {
+__device__ __forceinline__ float ingest_frame(const uint8_t* __restrict__ raw, int64_t r, int channels, int pick) {
+  if (pick >= 0) return ingest_sample<FMT>(raw, r * channels + pick);
   float v = ingest_sample<FMT>(raw, r * channels);
   if (channels == 1) return v;
   for (int c = 1; c < channels; ++c) v += ingest_sample<FMT>(raw, r * channels + c);
@@ -50,7 +66,7 @@ __device__ __forceinline__ void ingest_stage(const IngestJob& J, float* s, int64
   for (int q = threadIdx.x; q < J.span; q += kIngestThreads) {
     const int64_t i = i_lo + q, r = i - J.f0;
     float v = 0.0f;
-    if (i >= 0 && i < J.n_frames && r >= 0 && r < J.nf) v = ingest_frame<FMT>(J.raw, r, J.channels);
+    if (i >= 0 && i < J.n_frames && r >= 0 && r < J.nf) v = ingest_frame<FMT>(J.raw, r, J.channels, J.pick);
     s[q] = v;
   }
 }
@@ -68,6 +84,8 @@ __global__ __launch_bounds__(kIngestThreads) void ingest_kernel(const IngestJob 
     case TTASR_PCM_S24: ingest_stage<TTASR_PCM_S24>(J, s, i_lo); break;
     case TTASR_PCM_S32: ingest_stage<TTASR_PCM_S32>(J, s, i_lo); break;
     case TTASR_PCM_F32: ingest_stage<TTASR_PCM_F32>(J, s, i_lo); break;
+    case TTASR_PCM_ALAW: ingest_stage<TTASR_PCM_ALAW>(J, s, i_lo); break;
+    case TTASR_PCM_ULAW: ingest_stage<TTASR_PCM_ULAW>(J, s, i_lo); break;
     default: ingest_stage<TTASR_PCM_F64>(J, s, i_lo); break;
   }
   __syncthreads();
@@ -91,13 +109,52 @@ __global__ __launch_bounds__(kIngestThreads) void ingest_kernel(const IngestJob 
   }
 }
 
+__constant__ int16_t kImaStep[89] = {
+    7, 8, 9, 10, 11, 12, 13, 14, 16, 17, 19, 21, 23, 25, 28, 31, 34, 37, 41, 45, 50, 55, 60, 66, 73, 80, 88, 97, 107, 118, 130, 143,
+    157, 173, 190, 209, 230, 253, 279, 307, 337, 371, 408, 449, 494, 544, 598, 658, 724, 796, 876, 963, 1060, 1166, 1282, 1411,
+    1552, 1707, 1878, 2066, 2272, 2499, 2749, 3024, 3327, 3660, 4026, 4428, 4871, 5358, 5894, 6484, 7132, 7845, 8630, 9493, 10442,
+    11487, 12635, 13899, 15289, 16818, 18500, 20350, 22385, 24623, 27086, 29794, 32767};
+
+__global__ __launch_bounds__(kIngestThreads) void ima_decode_kernel(const ImaJob J) {
+  const int64_t t = (int64_t)blockIdx.x * kIngestThreads + threadIdx.x;
+  if (t >= (int64_t)J.n_blocks * J.channels) return;
+  const int c = (int)(t / J.n_blocks), b = (int)(t - (int64_t)c * J.n_blocks);
+  const uint8_t* __restrict__ blk = J.raw + (size_t)b * J.block_align;
+  const uint32_t head = *(const uint32_t*)(blk + 4 * c);        // block_align is a multiple of 4: every group is a dword
+  int pred = (int16_t)(head & 0xFFFF);
+  int index = (head >> 16) & 0xFF;
+  if (index > 88) index = 88;
+  int64_t fr = (int64_t)b * J.spb;
+  int16_t* __restrict__ out = J.out + c;
+  if (fr < J.n_frames) out[fr * J.channels] = (int16_t)pred;
+  ++fr;
+  const int groups = (J.block_align / J.channels - 4) / 4;
+  const uint8_t* __restrict__ data = blk + 4 * J.channels + 4 * c;
+  for (int g = 0; g < groups && fr < J.n_frames; ++g) {
+    uint32_t w = *(const uint32_t*)(data + (size_t)g * 4 * J.channels);
+    for (int j = 0; j < 8; ++j, w >>= 4, ++fr) {
+      const int n = (int)(w & 15), step = kImaStep[index];
+      int d = step >> 3;
+      if (n & 4) d += step;
+      if (n & 2) d += step >> 1;
+      if (n & 1) d += step >> 2;
+      pred = (n & 8) ? pred - d : pred + d;
+      pred = pred > 32767 ? 32767 : (pred < -32768 ? -32768 : pred);
+      index += (n & 4) ? 2 * (n & 3) + 2 : -1;                   // {-1, -1, -1, -1, 2, 4, 6, 8} at n & 7
+      index = index < 0 ? 0 : (index > 88 ? 88 : index);
+      if (fr < J.n_frames) out[fr * J.channels] = (int16_t)pred;
+    }
+  }
+}
+
 }  // namespace
 
 void launch_ingest(const IngestJob& j, hipStream_t s) {
   if (j.n_out <= 0) return;
   const int64_t need = j.taps ? ingest_span(j.tile, j.up, j.down, j.half) : j.tile;
   if (j.tile < 1 || j.tile > kIngestMaxTile || j.span < need || j.span > kIngestSpanMax || j.channels < 1 || j.channels > 8 ||
-      j.format < TTASR_PCM_U8 || j.format > TTASR_PCM_F64 || j.nf < 0 || (j.taps && (j.up < 1 || j.down < 1 || j.L < 1))) {
+      !((j.format >= TTASR_PCM_U8 && j.format <= TTASR_PCM_F64) || j.format == TTASR_PCM_ALAW || j.format == TTASR_PCM_ULAW) ||
+      j.pick < -1 || j.pick >= j.channels || j.nf < 0 || (j.taps && (j.up < 1 || j.down < 1 || j.L < 1))) {
     launch_fault("ingest: tile %d span %d (needs %lld) channels %d format %d", j.tile, j.span, (long long)need, j.channels, j.format);
     return;
   }
@@ -109,4 +166,15 @@ void launch_ingest(const IngestJob& j, hipStream_t s) {
   const unsigned grid = (unsigned)((j.n_out + j.tile - 1) / j.tile);
   if (j.taps && j.up == 1) ingest_kernel<true><<<grid, kIngestThreads, lds, s>>>(j);
   else ingest_kernel<false><<<grid, kIngestThreads, lds, s>>>(j);
+}
+
+void launch_ima_decode(const ImaJob& j, hipStream_t s) {
+  if (j.n_blocks <= 0 || j.n_frames <= 0) return;
+  if (j.channels < 1 || j.channels > 8 || j.block_align < 8 * j.channels || j.block_align % (4 * j.channels) ||
+      j.spb != ima_spb(j.block_align, j.channels) || ((uintptr_t)j.raw & 3)) {
+    launch_fault("ima decode: %d blocks of %d bytes, %d channels, %d samples per block", j.n_blocks, j.block_align, j.channels, j.spb);
+    return;
+  }
+  const int64_t lanes = (int64_t)j.n_blocks * j.channels;
+  ima_decode_kernel<<<(unsigned)((lanes + kIngestThreads - 1) / kIngestThreads), kIngestThreads, 0, s>>>(j);
 }

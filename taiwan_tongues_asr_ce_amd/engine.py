@@ -201,22 +201,42 @@ class Engine:
         return probs
 
     # -- file ingest -----------------------------------------------------------------------------
-    def ingest(self, raws: Sequence, rates: Sequence[int], channels: Sequence[int], formats: Sequence[int]) -> List[np.ndarray]:
-        """Raw interleaved samples of n recordings -> float32 mono 16 kHz, in ONE device call (ttasr_ingest_pcm): raws[i] is a
-        bytes-like object or a C-contiguous array holding whole frames of channels[i] samples in formats[i] (_lib.PCM_*) at
-        rates[i] Hz.  Rates and formats may differ; n is not limited by max_batch; no weights are needed.  A rate the device does
-        not take (see `ingest_accepts`) raises TtasrError: the caller converts that file on the host."""
+    def ingest(self, raws: Sequence, rates: Sequence[int], channels: Sequence[int], formats: Sequence[int],
+               block_aligns: Optional[Sequence[int]] = None, picks: Optional[Sequence[Optional[int]]] = None,
+               n_frames: Optional[Sequence[Optional[int]]] = None) -> List[np.ndarray]:
+        """Raw interleaved samples of n recordings -> float32 mono 16 kHz, in ONE device call: raws[i] is a bytes-like object or a
+        C-contiguous array holding whole frames of channels[i] samples in formats[i] (_lib.PCM_*) at rates[i] Hz.  Rates and
+        formats may differ; n is not limited by max_batch; no weights are needed.  A rate the device does not take (see
+        `ingest_accepts`) raises TtasrError: the caller converts that file on the host.
+        The coded formats (_lib.PCM_ALAW, PCM_ULAW, PCM_IMA4; block_aligns[i] = the file's block size for IMA, whose trailing
+        bytes short of a block are ignored), picks (None / -1 = the mean of the channels, c = channel c alone) and n_frames (a
+        frame count below what the bytes hold: an IMA file's `fact`) go through ttasr_ingest_wave; a call without any of them
+        is ttasr_ingest_pcm, as before."""
         n = len(raws)
         if not (len(rates) == len(channels) == len(formats) == n):
             raise ValueError("raws, rates, channels and formats must have one entry per recording")
+        for name, v in (("block_aligns", block_aligns), ("picks", picks), ("n_frames", n_frames)):
+            if v is not None and len(v) != n:
+                raise ValueError(f"{name} must have one entry per recording")
+        wave = not (block_aligns is None and picks is None and n_frames is None) or any(int(f) >= _lib.PCM_ALAW for f in formats)
         bufs, frames = [], np.zeros(max(n, 1), dtype=np.int64)
+        nbytes, bal = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(n, 1), dtype=np.int32)
         for i, r in enumerate(raws):
             b = np.frombuffer(r, dtype=np.uint8) if isinstance(r, (bytes, bytearray, memoryview)) else np.ascontiguousarray(r).reshape(-1).view(np.uint8)
             ch, fmt = int(channels[i]), int(formats[i])
-            fb = _lib.PCM_BYTES[fmt] * ch if 0 <= fmt < len(_lib.PCM_BYTES) and ch > 0 else 0
-            if fb and len(b) % fb:
-                raise ValueError(f"recording {i}: {len(b)} bytes are no whole number of {fb}-byte frames")
-            frames[i] = len(b) // fb if fb else len(b)   # bad channels / format: the library refuses the call with a message
+            if fmt == _lib.PCM_IMA4:
+                bal[i] = int(block_aligns[i]) if block_aligns is not None and block_aligns[i] is not None else 0
+                ok = ch > 0 and bal[i] >= 8 * ch and bal[i] % (4 * ch) == 0       # otherwise the library refuses the call with a message
+                frames[i] = len(b) // int(bal[i]) * (1 + 2 * (int(bal[i]) // ch - 4)) if ok else len(b)
+            else:
+                width = _lib.CODED_BYTES.get(fmt) or (_lib.PCM_BYTES[fmt] if 0 <= fmt < len(_lib.PCM_BYTES) else 0)
+                fb = width * ch if ch > 0 else 0
+                if fb and len(b) % fb:
+                    raise ValueError(f"recording {i}: {len(b)} bytes are no whole number of {fb}-byte frames")
+                frames[i] = len(b) // fb if fb else len(b)   # bad channels / format: the library refuses the call with a message
+            if n_frames is not None and n_frames[i] is not None:
+                frames[i] = int(n_frames[i])
+            nbytes[i] = len(b)
             bufs.append(b)
         rate = np.asarray(list(rates) or [0], dtype=np.int32)
         chan = np.asarray(list(channels) or [0], dtype=np.int32)
@@ -226,9 +246,15 @@ class Engine:
             return outs
         ptrs = (C.c_void_p * n)(*[b.ctypes.data if len(b) else None for b in bufs])
         optr = (C.c_void_p * n)(*[o.ctypes.data if len(o) else None for o in outs])
-        i32p = C.POINTER(C.c_int32)
-        self._check(self.lib.ttasr_ingest_pcm(self.h, n, ptrs, frames.ctypes.data_as(C.POINTER(C.c_int64)), rate.ctypes.data_as(i32p),
-                                              chan.ctypes.data_as(i32p), fmts.ctypes.data_as(i32p), optr), "ingest_pcm")
+        i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        if not wave:
+            self._check(self.lib.ttasr_ingest_pcm(self.h, n, ptrs, frames.ctypes.data_as(i64p), rate.ctypes.data_as(i32p),
+                                                  chan.ctypes.data_as(i32p), fmts.ctypes.data_as(i32p), optr), "ingest_pcm")
+            return outs
+        pk = np.asarray([-1 if p is None else int(p) for p in (picks if picks is not None else [None] * n)], dtype=np.int32)
+        self._check(self.lib.ttasr_ingest_wave(self.h, n, ptrs, nbytes.ctypes.data_as(i64p), frames.ctypes.data_as(i64p),
+                                               rate.ctypes.data_as(i32p), chan.ctypes.data_as(i32p), fmts.ctypes.data_as(i32p),
+                                               bal.ctypes.data_as(i32p), pk.ctypes.data_as(i32p), optr), "ingest_wave")
         return outs
 
     def ingest_accepts(self, rate: int) -> bool:

@@ -12,6 +12,13 @@ recordings of 60 s at 44.1 and 48 kHz, 2-channel int16 and mono int16.
 Nothing is asserted.  One JSON object on stdout and in --out.
 
     python tools/ingest_bench.py [--files 32] [--seconds 60] [--repeats 5] [--out profiles/ingest_bench.json]
+
+--codec ulaw | alaw | ima4 (may be given several times) measures telephony files instead: 8 kHz, mono and 2-channel, G.711 bytes or
+IMA ADPCM blocks of 256 bytes per channel (505 samples), random bytes.  The host path is then model.decode_audio's from the data
+bytes on - the G.711 table or the numpy IMA decoder, / 32768, the channel mean, resample_poly - and the device path the same one
+Engine.ingest call (ttasr_ingest_wave).  The result goes to profiles/ingest_bench_codecs.json.
+
+    python tools/ingest_bench.py --codec ulaw --codec alaw --codec ima4
 """
 from __future__ import annotations
 
@@ -42,30 +49,65 @@ def host_ingest(raw: np.ndarray, rate: int, channels: int) -> np.ndarray:
     return np.ascontiguousarray(x, dtype=np.float32)
 
 
+def host_ingest_coded(raw: bytes, rate: int, channels: int, codec: str, block_align: int) -> np.ndarray:
+    """model.decode_audio from the data bytes on, for a coded file."""
+    from scipy.signal import resample_poly
+    from taiwan_tongues_asr_ce_amd import model
+    if codec == "ima4":
+        x = model._ima_decode(raw, channels, block_align, len(raw) // block_align * (1 + 2 * (block_align // channels - 4)))
+    else:
+        x = model._g711_table(codec == "ulaw")[np.frombuffer(raw, dtype=np.uint8)]
+    x = np.frombuffer(np.ascontiguousarray(x).astype("<i2").tobytes(), dtype="<i2").astype(np.float32) / 32768.0
+    if channels > 1:
+        x = x.reshape(-1, channels).mean(axis=1)
+    g = gcd(rate, 16000)
+    x = resample_poly(x, 16000 // g, rate // g).astype(np.float32)
+    return np.ascontiguousarray(x, dtype=np.float32)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--codec", action="append", choices=("ulaw", "alaw", "ima4"), default=None)
     ap.add_argument("--files", type=int, default=32)
     ap.add_argument("--seconds", type=float, default=60.0)
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ingest_bench.json"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "ingest_bench_codecs.json" if args.codec else "ingest_bench.json")
     from taiwan_tongues_asr_ce_amd import _lib
     from taiwan_tongues_asr_ce_amd.config import COMPUTE_F32, PRESETS
     from taiwan_tongues_asr_ce_amd.engine import Engine
     eng = Engine(PRESETS["micro"], COMPUTE_F32, 4)       # ingest needs no weights
     res = {"tool": "tools/ingest_bench.py", "files": args.files, "seconds_per_file": args.seconds, "format": "int16",
            "headline_greedy_audio_s_per_s": HEADLINE, "workloads": {}}
-    for rate in (44100, 48000):
+    if args.codec:
+        res["format"] = "G.711 / IMA ADPCM, random bytes"
+    for codec, rate in [(c, 8000) for c in args.codec] if args.codec else [(None, 44100), (None, 48000)]:
         for channels in (2, 1):
             n = int(args.seconds * rate)
             rng = np.random.default_rng([0x16E57, rate, channels])
-            raws = [rng.integers(-6000, 6000, size=n * channels, dtype=np.int16) for _ in range(args.files)]
+            if codec is None:
+                raws = [rng.integers(-6000, 6000, size=n * channels, dtype=np.int16) for _ in range(args.files)]
+                host_fn = lambda r: host_ingest(r, rate, channels)  # noqa: E731
+                call = lambda: eng.ingest(raws, [rate] * len(raws), [channels] * len(raws), [_lib.PCM_S16] * len(raws))  # noqa: E731
+            else:
+                ba = 256 * channels
+                if codec == "ima4":
+                    n = n // 505 * 505                      # whole blocks
+                    size = n // 505 * ba
+                else:
+                    size = n * channels
+                raws = [rng.integers(0, 256, size=size, dtype=np.uint8) for _ in range(args.files)]
+                code = {"ulaw": _lib.PCM_ULAW, "alaw": _lib.PCM_ALAW, "ima4": _lib.PCM_IMA4}[codec]
+                host_fn = lambda r: host_ingest_coded(r.tobytes(), rate, channels, codec, ba)  # noqa: E731
+                call = lambda: eng.ingest(raws, [rate] * len(raws), [channels] * len(raws), [code] * len(raws),  # noqa: E731
+                                          block_aligns=[ba] * len(raws))
             audio_s = args.files * n / rate
-            host_ingest(raws[0], rate, channels)
+            host_fn(raws[0])
             t = time.perf_counter()
-            host = [host_ingest(r, rate, channels) for r in raws]
+            host = [host_fn(r) for r in raws]
             host_s = time.perf_counter() - t
-            call = lambda: eng.ingest(raws, [rate] * len(raws), [channels] * len(raws), [_lib.PCM_S16] * len(raws))  # noqa: E731
             for _ in range(2):
                 dev = call()
             xs = []
@@ -79,7 +121,7 @@ def main():
             ph = eng.phase_ms()
             eng.set_option("ingest_timing", 0)
             diff = max(float(np.abs(d.astype(np.float64) - h).max()) for d, h in zip(dev, host))
-            res["workloads"][f"{rate} Hz x {channels} ch"] = {
+            res["workloads"][f"{rate} Hz x {channels} ch" + (f" {codec}" if codec else "")] = {
                 "audio_s": round(audio_s, 1), "raw_mb": round(sum(r.nbytes for r in raws) / 1e6, 1),
                 "host_s": round(host_s, 4), "host_audio_s_per_s": round(audio_s / host_s, 1),
                 "device_median_s": round(dev_s, 5), "device_min_s": round(min(xs), 5), "device_max_s": round(max(xs), 5),
