@@ -591,7 +591,9 @@ TTASR_API int ttasr_vad_probs(ttasr_ctx* ctx, int32_t n, const float* const* pcm
  *   samples; a NULL output row that would receive values; a call already in flight on the context.
  *   A TTASR_E_HIP in the middle of a push leaves the streams of THAT call reset (zero state, nothing pending): the caller feeds
  *   them again from the start of their recordings, or closes them.
- * Streams belong to their context (a ttasr_create_shared context has its own) and everything is freed by ttasr_destroy. */
+ * Streams belong to their context (a ttasr_create_shared context has its own) and everything is freed by ttasr_destroy.
+ * The streams described here are FLOAT streams; WIRE streams ("wire streams" below) are fed bytes in a wire format instead.  The
+ * two kinds share the ids and the limit of TTASR_VAD_MAX_STREAMS open streams, and each push call takes its own kind only. */
 #define TTASR_VAD_MAX_STREAMS 1024
 TTASR_API int ttasr_vad_stream_open(ttasr_ctx* ctx, int32_t* out_id);
 TTASR_API int ttasr_vad_stream_reset(ttasr_ctx* ctx, int32_t id);
@@ -680,6 +682,59 @@ TTASR_API int ttasr_ingest_wave(ttasr_ctx* ctx, int32_t n, const void* const* ra
                                 const int32_t* rate, const int32_t* channels, const int32_t* format, const int32_t* block_align,
                                 const int32_t* pick, float* const* out_pcm_host);
 
+/* ---- wire streams: a VAD stream fed the BYTES of a live connection (the streaming server's `rate` 8000 | 16000 and `channel`
+ * 1 | 2 query parameters, the config message's sampleRate / channels; G.711 telephony with one party per channel) ----------------
+ * A wire stream is a VAD stream (above) opened with a wire format: rate, channels (1 ... 8), format (the six TTASR_PCM_* sample
+ * formats, TTASR_PCM_ALAW, TTASR_PCM_ULAW; TTASR_PCM_IMA4 is a block codec and is refused) and pick (-1 the mean of the channels,
+ * c channel c, as in ttasr_ingest_wave).  It is ONE recording that arrives as bytes in pieces; a piece may end inside a sample.
+ * The arithmetic is that of ttasr_ingest_pcm - up, down, half, h, mono, y[k], n_out as defined there - made stateful:
+ *   final outputs: y[k] is final once every input it reads has arrived; its last input is floor((k down + half) / up).  After F
+ *     whole frames the final outputs are k < K(F) = max(0, ceil((F up - half) / down)) (K(F) = F at 16000); with finish all
+ *     n_out(F) = ceil(F up / down) are final, inputs past the end counting as absent, as they do offline;
+ *   history: outputs from K(F) on read at most the last H = floor(2 half / up) frames.  The stream keeps those H mono values -
+ *     converted and downmixed, f32 - in a device table [2][TTASR_VAD_MAX_STREAMS][256] of the context, which is never uploaded;
+ *   pending bytes: bytes that do not fill a frame (channels x sample size, at most 63) wait on the host inside the context.
+ * A stream rate is a rate ttasr_ingest_len accepts with H <= 255: every rate listed above up to 192000 (H = 240); 384000 is not.
+ *
+ * ttasr_ingest_stream_len: the number of final outputs after n_frames frames at `rate` - K(n_frames), or n_out(n_frames) when
+ *   finished != 0; negative for a rate that is no stream rate (or n_frames outside [0, 2^40]).  No context.
+ * ttasr_vad_stream_open_wire: ttasr_vad_stream_open for a wire stream.  The first one of a context also allocates what wire
+ *   streams ever need: the 2 MiB history table, one device block and one pinned block of 8 MiB raw bytes + 8 MiB results + the
+ *   job table; every open builds the tap table of its rate when the context has none yet.  Refused like ttasr_vad_stream_open
+ *   (an open session included), and for TTASR_PCM_IMA4 or an unknown format, channels outside [1, 8], a pick outside
+ *   [-1, channels), and a rate for which ttasr_ingest_stream_len is negative.  Both kinds share the ids and the limit of
+ *   TTASR_VAD_MAX_STREAMS open streams; ttasr_vad_stream_reset (history, pending bytes and VAD state: as freshly opened, without
+ *   touching the device) and ttasr_vad_stream_close serve both.
+ * ttasr_vad_stream_push_wire: n rows; row i appends raw_host[i][0 .. n_bytes[i]) to wire stream ids[i] (0 bytes is legal).  The
+ *   outputs that become final are written to out_pcm_host[i] (out_pcm_host, or a row of it, may be NULL: the samples are not
+ *   returned) and counted in out_pcm_len[i]; out_pcm_cap[i] floats must hold them (ttasr_ingest_stream_len gives the number).  The
+ *   same samples enter the stream's VAD framing exactly as ttasr_vad_stream_push would take them - 512-sample frames, 64-sample
+ *   context, the same finish rule - and out_probs_host / out_logits_host / out_frames mean what they mean there (the caller
+ *   provides final outputs / 512 + 2 floats per row).  With finish[i] the stream is afterwards as reset; bytes that fill no frame
+ *   are dropped then.
+ *   THE BIT CONTRACT.  Let the last push of a stream carry finish.  However the bytes of a recording are cut into pushes (pieces
+ *   of 0 bytes, 1 byte, cuts inside a sample, H - 1 or H + 1 frames), however the pushes share calls with streams of other rates
+ *   and formats, in whatever row order and under any "wire_chunk": the concatenated out_pcm of the stream equals ttasr_ingest_wave
+ *   on the whole recording with the same pick, bit for bit, and the concatenated probabilities and logits equal ttasr_vad_probs on
+ *   that result, bit for bit.  Without finish they equal its first K(F) samples and first floor(K(F) / 512) values.  An output's
+ *   operands and their order depend on its index alone (i ascending, as offline); there are no atomics.
+ *   ONE launch per push chunk serves all rows: a job table in device memory has one entry per row, a 256-thread workgroup takes a
+ *   tile of outputs of one row and stages its span in LDS - the row's history from the table, then the new frames, converted and
+ *   downmixed on the way in - and one more workgroup per row writes the row's new history into the OTHER half of the table (the
+ *   halves flip per chunk and stream: no workgroup reads what another writes).  The results return through the pinned block and
+ *   enter the chunk loop of ttasr_vad_stream_push, which enqueues what it always did.  A push of any size is legal: it is walked
+ *   in chunks of as many frames per row as the row's share (1 / n) of the pools holds, or option "wire_chunk" when that is
+ *   smaller.  The call never allocates and is legal while a session is open, like ttasr_vad_stream_push.
+ *   Refused with TTASR_E_INVALID before anything is enqueued, the context and every stream stay as they were: everything
+ *   ttasr_vad_stream_push refuses; a float stream's id here, or a wire stream's id in ttasr_vad_stream_push; a NULL n_bytes or
+ *   out_pcm_len; an out_pcm_cap[i] (or a NULL out_pcm_cap) below the final outputs of a row whose samples are returned.
+ *   A TTASR_E_HIP in the middle of a push leaves the streams of THAT call reset. */
+TTASR_API int64_t ttasr_ingest_stream_len(int32_t rate, int64_t n_frames, int32_t finished);
+TTASR_API int ttasr_vad_stream_open_wire(ttasr_ctx* ctx, int32_t rate, int32_t channels, int32_t format, int32_t pick, int32_t* out_id);
+TTASR_API int ttasr_vad_stream_push_wire(ttasr_ctx* ctx, int32_t n, const int32_t* ids, const void* const* raw_host, const int64_t* n_bytes,
+                                         const int32_t* finish, float* const* out_pcm_host, const int64_t* out_pcm_cap, int64_t* out_pcm_len,
+                                         float* const* out_probs_host, float* const* out_logits_host, int32_t* out_frames);
+
 /* ---- kernel-selection overrides (tests, A/B measurements) ----------------------------------------- */
 /* The release library reads NO environment variable; every deviation from the measured configuration is an explicit call.
  * Keys (value 0 / 1 unless stated; defaults in brackets): "flash" [1] MFMA flash attention in the encoder (0: the
@@ -715,10 +770,11 @@ TTASR_API int ttasr_ingest_wave(ttasr_ctx* ctx, int32_t n, const void* const* ra
  * pass-mate-independent (see ttasr_session_align); 0: the padded pass, unchanged;
  * "ingest_chunk" [0] (0 ... 2^30) input frames per chunk of ttasr_ingest_pcm / ttasr_ingest_wave (IMA: rounded up to whole blocks),
  * 0 = as many as the staging slots hold (results do not depend on it, bit for bit: tests put chunk boundaries inside small inputs
- * with it); "ingest_timing" [0] 1: ttasr_ingest_pcm
+ * with it); "wire_chunk" [0] (0 ... 2^30) input frames of a row per chunk of ttasr_vad_stream_push_wire, 0 = as many as the row's
+ * share of the pools holds (results do not depend on it either); "ingest_timing" [0] 1: ttasr_ingest_pcm
  * waits for every copy and kernel before it enqueues the next and leaves the host-clock split of the call in ttasr_phase_ms
  * (measurement only: the waits cost the overlap);
- * Drops the captured decode graphs (except "enc_kernel_timing", "refill_overlap", "session_prefill", "align_packed", "ingest_chunk" and "ingest_timing").  Unknown key or value out of range: TTASR_E_INVALID. */
+ * Drops the captured decode graphs (except "enc_kernel_timing", "refill_overlap", "session_prefill", "align_packed", "ingest_chunk", "wire_chunk" and "ingest_timing").  Unknown key or value out of range: TTASR_E_INVALID. */
 TTASR_API int ttasr_set_option(ttasr_ctx* ctx, const char* key, int32_t value);
 
 /* ---- measurement --------------------------------------------------------------------------------- */

@@ -22,6 +22,7 @@ SYMBOLS = [
     "ttasr_vad_load_tensor", "ttasr_vad_finalize", "ttasr_vad_probs",
     "ttasr_vad_stream_open", "ttasr_vad_stream_reset", "ttasr_vad_stream_close", "ttasr_vad_stream_push",
     "ttasr_ingest_len", "ttasr_ingest_filter", "ttasr_ingest_pcm", "ttasr_ingest_wave",
+    "ttasr_ingest_stream_len", "ttasr_vad_stream_open_wire", "ttasr_vad_stream_push_wire",
 ]
 
 PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = range(6)   # TTASR_PCM_* of include/ttasr.h
@@ -137,9 +138,15 @@ def load() -> C.CDLL:
     lib.ttasr_ingest_filter.restype = i32
     lib.ttasr_ingest_pcm.argtypes = [vp, i32, C.POINTER(vp), i64p, i32p, i32p, i32p, C.POINTER(vp)]
     lib.ttasr_ingest_wave.argtypes = [vp, i32, C.POINTER(vp), i64p, i64p, i32p, i32p, i32p, i32p, i32p, C.POINTER(vp)]
+    lib.ttasr_ingest_stream_len.argtypes = [i32, i64, i32]
+    lib.ttasr_ingest_stream_len.restype = i64
+    lib.ttasr_vad_stream_open_wire.argtypes = [vp, i32, i32, i32, i32, i32p]
+    lib.ttasr_vad_stream_push_wire.argtypes = [vp, i32, i32p, C.POINTER(vp), i64p, i32p, C.POINTER(vp), i64p, i64p, C.POINTER(vp),
+                                               C.POINTER(vp), i32p]
     for s in SYMBOLS:
         f = getattr(lib, s)
-        if s not in ("ttasr_destroy", "ttasr_last_error", "ttasr_version", "ttasr_ingest_len", "ttasr_ingest_filter"):
+        if s not in ("ttasr_destroy", "ttasr_last_error", "ttasr_version", "ttasr_ingest_len", "ttasr_ingest_filter",
+                     "ttasr_ingest_stream_len"):
             f.restype = C.c_int
     _lib = lib
     return lib

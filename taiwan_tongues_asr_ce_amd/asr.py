@@ -28,6 +28,10 @@ def pcm16_bytes_to_float(buf: bytes) -> np.ndarray:
 
 
 class MI355XWhisperASR(ASRInterface):
+    # the defaults of the wire= / audio_from= keywords (client_audio): 16 kHz mono s16, converted by the adapter itself
+    wire = None
+    audio_from = None
+
     def __init__(self, **kwargs):
         from .model import WhisperModel
         model_size = kwargs.get("model_size", "large-v3-turbo")  # faster_whisper_asr.py:21
@@ -67,10 +71,27 @@ class MI355XWhisperASR(ASRInterface):
         fn = kwargs.get("vad_speech_prob_fn")
         if fn is not None:   # a speech-probability source handed to the adapter lands on the model (model.vad_speech_prob_fn)
             self.asr_pipeline.vad_speech_prob_fn = fn
+        # wire: what the clients' scratch bytes are - None = 16 kHz mono s16 (the path as ever), a vad.WireFormat, or "client" =
+        # what each client declares.  audio_from: a vad_backends.DeviceStreamVAD(wire=...) that has converted the same bytes on
+        # the device already (client_audio below)
+        self.wire = kwargs.get("wire")
+        self.audio_from = kwargs.get("audio_from")
+
+    def client_audio(self, client) -> np.ndarray:
+        """The client's scratch buffer as 16 kHz mono float32.  wire=None: s16 bytes at 16 kHz, as ever.  Otherwise the converted
+        audio of the `audio_from` backend when its stream has consumed exactly these bytes - the samples whose inputs have all
+        arrived: up to ceil(half / down) samples at the end (10 periods of the lower rate, 1.25 ms at 8 kHz) are not final and
+        are left out - and else the host conversion and the host resampler over the whole buffer (vad.WireFormat.to_16k)."""
+        from . import vad
+        if self.wire is None:
+            return pcm16_bytes_to_float(client.scratch_buffer)
+        buf = bytes(client.scratch_buffer)
+        audio = self.audio_from.audio(client, covering=buf) if self.audio_from is not None else None
+        return audio if audio is not None else vad.resolve_wire(self.wire, client).to_16k(buf)
 
     async def transcribe(self, client) -> Optional[Dict[str, Any]]:
         try:
-            audio = pcm16_bytes_to_float(client.scratch_buffer)
+            audio = self.client_audio(client)
             kw = dict(self.default_transcribe_kwargs)
             kw["language"] = "zh"  # faster_whisper_asr.py:161
             import warnings

@@ -189,6 +189,7 @@ struct ttasr_ctx {
   // host-clock phase split in phase_ms
   ttasr_detail::IngestState* ingest = nullptr;
   int ingest_chunk = 0; bool ingest_timing = false;
+  int wire_chunk = 0;       // option wire_chunk: input frames of a row per internal chunk of ttasr_vad_stream_push_wire (0: what the pools hold)
 
   int B_mel = 0, B_enc = 0, B_dec = 0;
   std::atomic_flag busy = ATOMIC_FLAG_INIT;  // one call in flight per context: a second concurrent call is refused
@@ -399,6 +400,12 @@ void vad_free(ttasr_ctx* c);         // ttasr_destroy: the scratch block, the pi
 
 // ---- engine_ingest.hip: file ingest (ttasr_ingest_*) ----
 void ingest_free(ttasr_ctx* c);      // ttasr_destroy: the tap tables, the device and pinned chunk slots and their events
+// What a wire stream (engine_vad.hip) keeps of its rate: the ratio, the filter and its table on the device (taps == nullptr at
+// 16000: no filter), H = floor(2 half / up) frames of history and the stream kernel's tile.  ok = false: not a stream rate.
+struct WirePlan { bool ok = false; int up = 1, down = 1, half = 0, L = 0, H = 0, tile = 256; const float* taps = nullptr; };
+WirePlan wire_plan(int32_t rate);                                // the arithmetic alone: no context, taps stay nullptr
+int wire_plan_dev(ttasr_ctx* c, int32_t rate, WirePlan* out);    // ... with the table of the rate, built on first use (allocates)
+int64_t wire_final(const WirePlan& p, int64_t n_frames, bool finished);   // K(F), or n_out(F) when finished
 
 // ---- engine_search.hip: rules, options, greedy / sampled / beam search ----
 // The decode shape of ONE search (a static search's call, or a session from begin to end / free): installs the StepShape and the

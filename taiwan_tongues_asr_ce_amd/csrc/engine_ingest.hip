@@ -137,6 +137,37 @@ static int ingest_filter_dev(ttasr_ctx* c, int32_t rate, const IngestFilter** ou
 static int64_t ceil_div(int64_t a, int64_t b) { return a >= 0 ? (a + b - 1) / b : -((-a) / b); }   // b > 0
 static int64_t floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
+// ---- wire streams: what engine_vad.hip needs of a rate ----
+
+WirePlan wire_plan(int32_t rate) {
+  WirePlan w;
+  const IngestPlan p = ingest_plan(rate);
+  if (!p.ok) return w;
+  w.up = p.up; w.down = p.down; w.half = p.half; w.L = p.L; w.H = 2 * p.half / p.up;
+  if (w.H > 255) return w;   // one row of the history table
+  // the longest tile of at most 1024 outputs (a push is short: more, smaller workgroups) whose span fits the usual LDS budget
+  w.tile = 1024;
+  while (w.tile > kIngestThreads && (p.filter ? ingest_span(w.tile, p.up, p.down, p.half) : w.tile) > kWireSpan) w.tile -= kIngestThreads;
+  w.ok = true;
+  return w;
+}
+
+int wire_plan_dev(ttasr_ctx* c, int32_t rate, WirePlan* out) {
+  WirePlan w = wire_plan(rate);
+  if (!w.ok) return fail(c, TTASR_E_INVALID, "rate %d is no stream rate (ttasr_ingest_stream_len)", rate);
+  if (!c->ingest) c->ingest = new IngestState();
+  const IngestFilter* f = nullptr;
+  TRY(ingest_filter_dev(c, rate, &f));
+  w.taps = f->dev;
+  *out = w;
+  return 0;
+}
+
+int64_t wire_final(const WirePlan& p, int64_t n_frames, bool finished) {
+  if (finished) return ceil_div(n_frames * p.up, p.down);
+  return std::max<int64_t>(0, ceil_div(n_frames * p.up - p.half, p.down));
+}
+
 struct IngestPending { bool live = false; float* dst = nullptr; size_t n = 0; };
 
 static int ingest_scratch(ttasr_ctx* c) {
@@ -296,6 +327,12 @@ int64_t ttasr_ingest_len(int32_t rate, int64_t n_frames) {
   const IngestPlan p = ingest_plan(rate);
   if (!p.ok || n_frames < 0 || n_frames > kIngestMaxFrames) return TTASR_E_INVALID;
   return (n_frames * p.up + p.down - 1) / p.down;
+}
+
+int64_t ttasr_ingest_stream_len(int32_t rate, int64_t n_frames, int32_t finished) {
+  const WirePlan p = wire_plan(rate);
+  if (!p.ok || n_frames < 0 || n_frames > kIngestMaxFrames) return TTASR_E_INVALID;
+  return wire_final(p, n_frames, finished != 0);
 }
 
 int32_t ttasr_ingest_filter(int32_t rate, float* out, int32_t cap) {

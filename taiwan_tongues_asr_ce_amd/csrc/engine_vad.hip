@@ -1,8 +1,10 @@
 // libttasr: the voice-activity network behind the C ABI (one of the engine translation units, see engine_ctx.hpp): weight intake
 // into the kernels' layouts, the context's scratch block and pinned staging, the chunk loop that ttasr_vad_probs and
-// ttasr_vad_stream_push share, and the streams' host state.  The kernels are kernels_vad.hip; the network is the text of
+// ttasr_vad_stream_push share, the streams' host state, and wire streams (ttasr_vad_stream_push_wire: bytes through the stream
+// kernel of kernels_ingest.hip, then into that same push).  The kernels are kernels_vad.hip; the network is the text of
 // include/ttasr.h.  Nothing here touches mel, encoder, search or graph state: the call's only shared resource is the context's stream.
 #include "engine_ctx.hpp"
+#include "ingest.hpp"
 #include "vad.hpp"
 
 namespace ttasr_detail {
@@ -66,15 +68,42 @@ static void vad_gather(float* dst, const VadRow& r, int64_t pos, int64_t count) 
 // A stream (include/ttasr.h): its (h, c) is row `id` of the device table; here the last 64 evaluated samples and the samples that
 // do not fill a frame yet.  fresh: the table row is to be zeroed before the stream's next frame (open, reset, finish and a failed
 // push only set the flag, so none of them touches the device).
-struct VadStream { bool open = false, fresh = true; int n_pend = 0; float ctx[kVadContext] = {}; float pend[kVadWindow] = {}; };
+// A WIRE stream adds what stands in front of the network: the format it was opened with, the frames received (F) and the 16 kHz
+// samples handed on (K) so far, the bytes that do not fill a frame yet, and which half of the device history table holds its
+// last H mono values.  A stream with F == 0 reads no history: reset touches no device memory.
+struct VadStream {
+  bool open = false, fresh = true; int n_pend = 0; float ctx[kVadContext] = {}; float pend[kVadWindow] = {};
+  bool wire = false; WirePlan plan; int channels = 1, format = TTASR_PCM_S16, pick = -1, fb = 2;
+  int64_t F = 0, K = 0; int n_raw = 0, half = 0; uint8_t raw[64] = {};
+};
+
+constexpr size_t kWireRawBytes = (size_t)8 << 20;     // raw bytes of all rows of one push chunk
+constexpr size_t kWireOutFloats = (size_t)2 << 20;    // their results
+constexpr size_t kWireJobBytes = (sizeof(WireJob) * TTASR_VAD_MAX_STREAMS + 255) & ~(size_t)255;
+
+// one row of a ttasr_vad_stream_push_wire while the call walks its chunks
+struct WireRow {
+  const uint8_t* src; int64_t n_src, pos /*bytes of [held | src] consumed*/, frames_left, pcm_done; int32_t vad_done;
+  bool fin, done;
+};
+
 struct VadStreams {
   float* table = nullptr;                       // [TTASR_VAD_MAX_STREAMS][256], device
   int n_open = 0;
   std::vector<VadStream> s = std::vector<VadStream>(TTASR_VAD_MAX_STREAMS);
   std::vector<VadRow> rows = std::vector<VadRow>(TTASR_VAD_MAX_STREAMS);   // a push's rows (n <= open streams): a push never allocates
   std::vector<uint8_t> seen = std::vector<uint8_t>(TTASR_VAD_MAX_STREAMS);
+  // wire streams (the first ttasr_vad_stream_open_wire allocates): the history table [2][TTASR_VAD_MAX_STREAMS][256], the device
+  // block job table | raw pool | result pool and its pinned twin, and a wire push's rows with the float push each chunk hands on
+  float* hist = nullptr; char* wire_dev = nullptr; char* wire_pin = nullptr;
+  std::vector<WireRow> wrows;
+  std::vector<int32_t> sub_ids, sub_fin, sub_frames, sub_row;
+  std::vector<const float*> sub_pcm; std::vector<int64_t> sub_ns; std::vector<float*> sub_probs, sub_logits;
 };
-static void vad_stream_clear(VadStream& st) { st.fresh = true; st.n_pend = 0; memset(st.ctx, 0, sizeof st.ctx); }
+static void vad_stream_clear(VadStream& st) {
+  st.fresh = true; st.n_pend = 0; memset(st.ctx, 0, sizeof st.ctx);
+  st.F = st.K = 0; st.n_raw = 0;
+}
 
 void vad_free(ttasr_ctx* c) {
   if (!c->vad) return;
@@ -82,6 +111,9 @@ void vad_free(ttasr_ctx* c) {
   if (c->vad->pinned) hipHostFree(c->vad->pinned);
   if (c->vad->streams) {
     if (c->vad->streams->table) hipFree(c->vad->streams->table);
+    if (c->vad->streams->hist) hipFree(c->vad->streams->hist);
+    if (c->vad->streams->wire_dev) hipFree(c->vad->streams->wire_dev);
+    if (c->vad->streams->wire_pin) hipHostFree(c->vad->streams->wire_pin);
     delete c->vad->streams;
   }
   delete c->vad;
@@ -272,15 +304,56 @@ static int vad_probs(ttasr_ctx* c, int32_t n, const float* const* pcm, const int
 
 // ---- streams ----
 
-static int vad_stream_open(ttasr_ctx* c, int32_t* out_id) {
+static int sample_bytes(int32_t format) {   // 0: no stream format
+  static const int pcm[6] = {1, 2, 3, 4, 4, 8};
+  if (format >= TTASR_PCM_U8 && format <= TTASR_PCM_F64) return pcm[format];
+  return format == TTASR_PCM_ALAW || format == TTASR_PCM_ULAW ? 1 : 0;
+}
+
+// What wire streams need beside the float streams' blocks; a failed allocation leaves what exists in place for the next open.
+static int vad_wire_blocks(ttasr_ctx* c, VadStreams* S) {
+  const struct { void** p; size_t bytes; bool pinned; const char* what; } blk[3] = {
+      {(void**)&S->hist, (size_t)2 * TTASR_VAD_MAX_STREAMS * 256 * 4, false, "wire stream history table"},
+      {(void**)&S->wire_dev, kWireJobBytes + kWireRawBytes + kWireOutFloats * 4, false, "wire stream device pools"},
+      {(void**)&S->wire_pin, kWireJobBytes + kWireRawBytes + kWireOutFloats * 4, true, "wire stream pinned pools"}};
+  for (const auto& b : blk) {
+    if (*b.p) continue;
+    const hipError_t e = b.pinned ? hipHostMalloc(b.p, b.bytes, hipHostMallocDefault) : hipMalloc(b.p, b.bytes);
+    if (e != hipSuccess) {
+      *b.p = nullptr;
+      (void)hipGetLastError();
+      return fail(c, TTASR_E_NOMEM, "%s (%zu bytes): %s", b.what, b.bytes, hipGetErrorString(e));
+    }
+  }
+  if (S->wrows.empty()) {
+    const size_t m = TTASR_VAD_MAX_STREAMS;
+    S->wrows.resize(m); S->sub_ids.resize(m); S->sub_fin.resize(m); S->sub_frames.resize(m); S->sub_row.resize(m);
+    S->sub_pcm.resize(m); S->sub_ns.resize(m); S->sub_probs.resize(m); S->sub_logits.resize(m);
+  }
+  return 0;
+}
+
+// wire == nullptr: a float stream.  Otherwise {rate, channels, format, pick} of a wire stream.
+static int vad_stream_open(ttasr_ctx* c, const int32_t* wire, int32_t* out_id) {
   VadState* v = c->vad;
   if (!v || !v->finalized) return fail(c, TTASR_E_INVALID, "VAD weights not finalized (ttasr_vad_load_tensor, ttasr_vad_finalize first)");
   if (!out_id) return fail(c, TTASR_E_INVALID, "NULL argument");
+  if (wire) {
+    if (!sample_bytes(wire[2])) return fail(c, TTASR_E_INVALID, "format %d is no stream format (the six sample formats, A-law, mu-law)", wire[2]);
+    if (wire[1] < 1 || wire[1] > 8) return fail(c, TTASR_E_INVALID, "%d channels outside [1, 8]", wire[1]);
+    if (wire[3] < -1 || wire[3] >= wire[1]) return fail(c, TTASR_E_INVALID, "pick %d outside [-1, %d)", wire[3], wire[1]);
+    if (!wire_plan(wire[0]).ok) return fail(c, TTASR_E_INVALID, "rate %d is no stream rate (ttasr_ingest_stream_len)", wire[0]);
+  }
   TRY(session_refusal(c));   // the first open allocates
   HIPCHK(c, hipSetDevice(c->device));
   if (!v->streams) v->streams = new VadStreams();
   VadStreams* S = v->streams;
   if (S->n_open >= TTASR_VAD_MAX_STREAMS) return fail(c, TTASR_E_INVALID, "all %d VAD streams of a context are open", S->n_open);
+  WirePlan plan;
+  if (wire) {
+    TRY(vad_wire_blocks(c, S));
+    TRY(wire_plan_dev(c, wire[0], &plan));
+  }
   // everything a push ever needs: the table, the pinned staging, the scratch block for groups of max_batch rows
   if (!S->table) {
     const size_t bytes = (size_t)TTASR_VAD_MAX_STREAMS * 256 * 4;
@@ -295,8 +368,13 @@ static int vad_stream_open(ttasr_ctx* c, int32_t* out_id) {
   TRY(vad_scratch(c, c->maxB));
   int id = 0;
   while (S->s[id].open) ++id;   // n_open < TTASR_VAD_MAX_STREAMS: one is free
-  S->s[id].open = true;
-  vad_stream_clear(S->s[id]);
+  VadStream& st = S->s[id];
+  st.open = true;
+  st.wire = wire != nullptr;
+  if (wire) {
+    st.plan = plan; st.channels = wire[1]; st.format = wire[2]; st.pick = wire[3]; st.fb = sample_bytes(wire[2]) * wire[1];
+  }
+  vad_stream_clear(st);
   ++S->n_open;
   *out_id = id;
   return TTASR_OK;
@@ -307,7 +385,9 @@ static VadStream* vad_stream_of(ttasr_ctx* c, int32_t id) {
   return S && id >= 0 && id < TTASR_VAD_MAX_STREAMS && S->s[id].open ? &S->s[id] : nullptr;
 }
 
-static int vad_stream_push(ttasr_ctx* c, int32_t n, const int32_t* ids, const float* const* pcm, const int64_t* ns,
+// wire: the kind of stream the caller may name - float streams for ttasr_vad_stream_push, wire streams for the chunks of
+// ttasr_vad_stream_push_wire, whose 16 kHz samples enter here
+static int vad_stream_push(ttasr_ctx* c, bool wire, int32_t n, const int32_t* ids, const float* const* pcm, const int64_t* ns,
                            const int32_t* finish, float* const* out_probs, float* const* out_logits, int32_t* out_frames) {
   VadState* v = c->vad;
   if (!v || !v->finalized) return fail(c, TTASR_E_INVALID, "VAD weights not finalized (ttasr_vad_load_tensor, ttasr_vad_finalize first)");
@@ -320,6 +400,7 @@ static int vad_stream_push(ttasr_ctx* c, int32_t n, const int32_t* ids, const fl
   for (int i = 0; i < n; ++i) {
     VadStream* st = vad_stream_of(c, ids[i]);
     if (!st) return fail(c, TTASR_E_INVALID, "row %d: stream %d is not open", i, ids[i]);
+    if (st->wire != wire) return fail(c, TTASR_E_INVALID, "row %d: stream %d is a %s stream", i, ids[i], st->wire ? "wire" : "float");
     if (S->seen[ids[i]]) return fail(c, TTASR_E_INVALID, "row %d: stream %d appears twice in the call", i, ids[i]);
     S->seen[ids[i]] = 1;
     if (ns[i] < 0) return fail(c, TTASR_E_INVALID, "row %d: negative length", i);
@@ -365,6 +446,136 @@ static int vad_stream_push(ttasr_ctx* c, int32_t n, const int32_t* ids, const fl
   return rc;
 }
 
+// count bytes of a row's sequence [the stream's held bytes | the caller's] from byte pos on
+static void wire_bytes(uint8_t* dst, const VadStream& st, const WireRow& r, int64_t pos, int64_t count) {
+  const int64_t from_held = std::max<int64_t>(std::min<int64_t>(st.n_raw - pos, count), 0);
+  if (from_held) memcpy(dst, st.raw + pos, (size_t)from_held);
+  if (count > from_held) memcpy(dst + from_held, r.src + (pos + from_held - st.n_raw), (size_t)(count - from_held));
+}
+
+static int vad_stream_push_wire(ttasr_ctx* c, int32_t n, const int32_t* ids, const void* const* raw, const int64_t* n_bytes,
+                                const int32_t* finish, float* const* out_pcm, const int64_t* out_cap, int64_t* out_len,
+                                float* const* out_probs, float* const* out_logits, int32_t* out_frames) {
+  VadState* v = c->vad;
+  if (!v || !v->finalized) return fail(c, TTASR_E_INVALID, "VAD weights not finalized (ttasr_vad_load_tensor, ttasr_vad_finalize first)");
+  VadStreams* S = v->streams;
+  const int n_open = S ? S->n_open : 0;
+  if (n < 1 || n > n_open) return fail(c, TTASR_E_INVALID, "n %d outside [1, open streams = %d]", n, n_open);
+  if (!ids || !raw || !n_bytes || !out_len || !out_probs || !out_frames) return fail(c, TTASR_E_INVALID, "NULL argument");
+  memset(S->seen.data(), 0, S->seen.size());
+  for (int i = 0; i < n; ++i) {
+    VadStream* st = vad_stream_of(c, ids[i]);
+    if (!st) return fail(c, TTASR_E_INVALID, "row %d: stream %d is not open", i, ids[i]);
+    if (!st->wire) return fail(c, TTASR_E_INVALID, "row %d: stream %d is a float stream", i, ids[i]);
+    if (S->seen[ids[i]]) return fail(c, TTASR_E_INVALID, "row %d: stream %d appears twice in the call", i, ids[i]);
+    S->seen[ids[i]] = 1;
+    if (n_bytes[i] < 0) return fail(c, TTASR_E_INVALID, "row %d: negative length", i);
+    if (n_bytes[i] > 0 && !raw[i]) return fail(c, TTASR_E_INVALID, "row %d: NULL raw with %lld bytes", i, (long long)n_bytes[i]);
+    const bool fin = finish && finish[i];
+    const int64_t frames = (st->n_raw + n_bytes[i]) / st->fb;
+    if (st->F + frames > ((int64_t)1 << 40)) return fail(c, TTASR_E_INVALID, "row %d: more than 2^40 frames in a stream", i);
+    const int64_t outs = wire_final(st->plan, st->F + frames, fin) - st->K;
+    if (out_pcm && out_pcm[i] && (!out_cap || out_cap[i] < outs))
+      return fail(c, TTASR_E_INVALID, "row %d: %lld samples become final, the row holds %lld", i, (long long)outs, (long long)(out_cap ? out_cap[i] : 0));
+    const int64_t total = st->n_pend + outs;
+    const int64_t vf = total / kVadWindow + (fin && total % kVadWindow ? 1 : 0);
+    if (vf > 0 && (!out_probs[i] || (out_logits && !out_logits[i])))
+      return fail(c, TTASR_E_INVALID, "row %d: NULL output row for %lld values", i, (long long)vf);
+    if (vf > INT32_MAX) return fail(c, TTASR_E_INVALID, "row %d: %lld frames in one push", i, (long long)vf);
+    S->wrows[i] = WireRow{(const uint8_t*)raw[i], n_bytes[i], 0, frames, 0, 0, fin, false};
+  }
+  // from here on a failure leaves the streams of this call reset
+  hipStream_t s = c->stream;
+  WireJob* const p_jobs = (WireJob*)S->wire_pin;
+  uint8_t* const p_raw = (uint8_t*)S->wire_pin + kWireJobBytes;
+  float* const p_out = (float*)(S->wire_pin + kWireJobBytes + kWireRawBytes);
+  const WireJob* const d_jobs = (const WireJob*)S->wire_dev;
+  uint8_t* const d_raw = (uint8_t*)S->wire_dev + kWireJobBytes;
+  float* const d_out = (float*)(S->wire_dev + kWireJobBytes + kWireRawBytes);
+  // every row's share of the pools: a chunk takes the frames whose bytes and whose results fit it (or option wire_chunk)
+  const int64_t share_raw = (int64_t)(kWireRawBytes / n) & ~(int64_t)63, share_out = (int64_t)(kWireOutFloats / n);
+  auto run = [&]() -> int {
+    HIPCHK(c, hipSetDevice(c->device));
+    for (int left = n; left > 0;) {
+      int m = 0, sub = 0, max_tiles = 0, span = 1;
+      int64_t raw_used = 0, out_used = 0;
+      for (int i = 0; i < n; ++i) {
+        WireRow& r = S->wrows[i];
+        if (r.done) continue;
+        VadStream& st = S->s[ids[i]];
+        const WirePlan& P = st.plan;
+        int64_t C = std::min<int64_t>(share_raw / st.fb, (share_out - 2) * P.down / P.up);
+        if (c->wire_chunk > 0) C = std::min<int64_t>(C, c->wire_chunk);
+        const int64_t cf = std::min(C, r.frames_left);
+        const bool last = cf == r.frames_left;
+        // without new frames (the tail a finish releases, walked in shares) the history stands and K moves alone
+        const int64_t emit = std::min<int64_t>(wire_final(P, st.F + cf, last && r.fin) - st.K, share_out);
+        if (cf > 0 || emit > 0) {
+          wire_bytes(p_raw + raw_used, st, r, r.pos, cf * st.fb);
+          WireJob& J = p_jobs[m++];
+          J.taps = P.taps; J.raw_off = raw_used; J.f_old = st.F; J.k_begin = st.K;
+          J.nf = (int32_t)cf; J.n_out = (int32_t)emit; J.out_off = (int32_t)out_used;
+          J.hist_in = (st.half * TTASR_VAD_MAX_STREAMS + ids[i]) * 256;
+          J.hist_out = cf > 0 ? ((st.half ^ 1) * TTASR_VAD_MAX_STREAMS + ids[i]) * 256 : -1;
+          J.up = P.up; J.down = P.down; J.half = P.half; J.L = P.L; J.H = P.H; J.tile = P.tile;
+          J.channels = st.channels; J.format = st.format; J.pick = st.pick;
+          max_tiles = std::max<int>(max_tiles, (int)((emit + P.tile - 1) / P.tile));
+          span = std::max<int>(span, P.taps ? (int)ingest_span(P.tile, P.up, P.down, P.half) : P.tile);
+          raw_used += (cf * st.fb + 63) & ~(int64_t)63;
+        }
+        r.done = last && st.K + emit == wire_final(P, st.F + cf, r.fin);
+        if (emit > 0 || (r.done && r.fin)) {
+          S->sub_row[sub] = i; S->sub_ids[sub] = ids[i]; S->sub_fin[sub] = r.done && r.fin;
+          S->sub_pcm[sub] = p_out + out_used; S->sub_ns[sub] = emit;
+          S->sub_probs[sub] = out_probs[i] ? out_probs[i] + r.vad_done : nullptr;
+          S->sub_logits[sub] = out_logits && out_logits[i] ? out_logits[i] + r.vad_done : nullptr;
+          ++sub;
+        }
+        if (r.done) {   // the bytes behind the last whole frame stay with the stream (a finish drops them with everything else)
+          const int64_t end = st.n_raw + r.n_src, keep = end - (r.pos + cf * st.fb);
+          uint8_t held[64];
+          wire_bytes(held, st, r, end - keep, keep);
+          memcpy(st.raw, held, (size_t)keep);
+          st.n_raw = (int)keep;
+          --left;
+        } else {
+          r.pos += cf * st.fb;
+        }
+        r.frames_left -= cf;
+        st.F += cf; st.K += emit;
+        if (cf > 0) st.half ^= 1;
+        out_used += emit;
+      }
+      if (m > 0) {
+        HIPCHK(c, hipMemcpyAsync((void*)d_jobs, p_jobs, (size_t)m * sizeof(WireJob), hipMemcpyHostToDevice, s));
+        if (raw_used) HIPCHK(c, hipMemcpyAsync(d_raw, p_raw, (size_t)raw_used, hipMemcpyHostToDevice, s));
+        launch_wire(d_jobs, m, max_tiles, span, d_raw, d_out, S->hist, s);
+        if (out_used) HIPCHK(c, hipMemcpyAsync(p_out, d_out, (size_t)out_used * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        HIPCHK(c, hipGetLastError());
+      }
+      if (sub == 0) continue;
+      for (int k = 0; k < sub; ++k) {
+        WireRow& r = S->wrows[S->sub_row[k]];
+        float* const dst = out_pcm ? out_pcm[S->sub_row[k]] : nullptr;
+        if (dst && S->sub_ns[k]) memcpy(dst + r.pcm_done, S->sub_pcm[k], (size_t)S->sub_ns[k] * 4);
+        r.pcm_done += S->sub_ns[k];
+      }
+      TRY(vad_stream_push(c, true, sub, S->sub_ids.data(), S->sub_pcm.data(), S->sub_ns.data(), S->sub_fin.data(),
+                          S->sub_probs.data(), out_logits ? S->sub_logits.data() : nullptr, S->sub_frames.data()));
+      for (int k = 0; k < sub; ++k) S->wrows[S->sub_row[k]].vad_done += S->sub_frames[k];
+    }
+    return TTASR_OK;
+  };
+  const int rc = run();
+  for (int i = 0; i < n; ++i) {
+    out_len[i] = rc == TTASR_OK ? S->wrows[i].pcm_done : 0;
+    out_frames[i] = rc == TTASR_OK ? S->wrows[i].vad_done : 0;
+    if (rc != TTASR_OK) vad_stream_clear(S->s[ids[i]]);
+  }
+  return rc;
+}
+
 }  // namespace ttasr_detail
 
 extern "C" {
@@ -397,7 +608,24 @@ int ttasr_vad_probs(ttasr_ctx* c, int32_t n, const float* const* pcm, const int6
 int ttasr_vad_stream_open(ttasr_ctx* c, int32_t* out_id) {
   return guarded(c, [&]() -> int {
   if (!c) return TTASR_E_INVALID;
-  return vad_stream_open(c, out_id);
+  return vad_stream_open(c, nullptr, out_id);
+  });
+}
+
+int ttasr_vad_stream_open_wire(ttasr_ctx* c, int32_t rate, int32_t channels, int32_t format, int32_t pick, int32_t* out_id) {
+  return guarded(c, [&]() -> int {
+  if (!c) return TTASR_E_INVALID;
+  const int32_t wire[4] = {rate, channels, format, pick};
+  return vad_stream_open(c, wire, out_id);
+  });
+}
+
+int ttasr_vad_stream_push_wire(ttasr_ctx* c, int32_t n, const int32_t* ids, const void* const* raw, const int64_t* n_bytes,
+                               const int32_t* finish, float* const* out_pcm, const int64_t* out_pcm_cap, int64_t* out_pcm_len,
+                               float* const* out_probs, float* const* out_logits, int32_t* out_frames) {
+  return guarded(c, [&]() -> int {
+  if (!c) return TTASR_E_INVALID;
+  return vad_stream_push_wire(c, n, ids, raw, n_bytes, finish, out_pcm, out_pcm_cap, out_pcm_len, out_probs, out_logits, out_frames);
   });
 }
 
@@ -426,7 +654,7 @@ int ttasr_vad_stream_push(ttasr_ctx* c, int32_t n, const int32_t* ids, const flo
                           const int32_t* finish, float* const* out_probs, float* const* out_logits, int32_t* out_frames) {
   return guarded(c, [&]() -> int {
   if (!c) return TTASR_E_INVALID;
-  return vad_stream_push(c, n, ids, pcm, n_samples, finish, out_probs, out_logits, out_frames);
+  return vad_stream_push(c, false, n, ids, pcm, n_samples, finish, out_probs, out_logits, out_frames);
   });
 }
 

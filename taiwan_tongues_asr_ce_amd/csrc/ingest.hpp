@@ -31,6 +31,22 @@ inline int64_t ingest_span(int64_t tile, int up, int down, int half) { return ti
 
 void launch_ingest(const IngestJob& j, hipStream_t s);
 
+// Wire streams (ttasr_vad_stream_push_wire): ONE launch for all rows of a push chunk.  Entry r of the job table, in device memory,
+// is row r: the outputs [k_begin, k_begin + n_out) of a stream that had f_old frames before this chunk and brings nf new ones at
+// raw + raw_off (whole frames, 8-byte aligned).  Frame i < f_old is hist_in[i - f_old + H] (the stream's last H mono values,
+// converted and downmixed), frames below 0 and from f_old + nf on are zeros.  hist_out, when not negative, receives the last H
+// mono values after the chunk; hist_in and hist_out are float offsets into the history table and never the same half of it.
+struct WireJob {
+  const float* taps;       // device, phase-major [up][L]; nullptr: no filter
+  int64_t raw_off, f_old, k_begin;
+  int32_t nf, n_out, out_off /*floats into the output pool*/, hist_in, hist_out;
+  int32_t up, down, half, L, H, tile, channels, format, pick;
+};
+constexpr int kWireSpan = kIngestSpan;       // a stream rate's tile always fits the usual LDS budget (H <= 255)
+
+// jobs / raw / out / hist: device.  max_tiles = the largest ceil(n_out / tile) of the table, span = the largest staged span of it.
+void launch_wire(const WireJob* jobs, int n, int max_tiles, int span, const uint8_t* raw, float* out, float* hist, hipStream_t s);
+
 // The IMA ADPCM pre-pass: `n_blocks` whole blocks of `block_align` bytes at `raw` -> int16 [frames][channels] at `out`, block b's
 // sample s at frame b * spb + s; frames from `n_frames` on (the cut of the last block, the end of the scratch) are not written.
 struct ImaJob {

@@ -11,6 +11,11 @@
 //                   predictor and step index - and writes int16 [frames][channels]; ingest_kernel then reads that as s16.  Lane t
 //                   takes block t % n_blocks of channel t / n_blocks: consecutive lanes read consecutive blocks of one channel.
 //
+//   wire_kernel     ingest_kernel for wire streams (ttasr_vad_stream_push_wire): ONE launch for all rows of
+//                   a push chunk, the jobs in a device table, the span staged from the stream's history in a device table and
+//                   then from the new frames, the same sum; one more workgroup per row writes the row's new history into the
+//                   table half the tiles do not read.
+//
 // The taps are read from the phase-major table in global memory (at most 84 KiB per rate: it lives in L2 and the vector L1).  With
 // up == 1 there is one row and the tap address is wave-uniform: the UP1 instance reads it through the scalar unit.  With up > 1
 // neighbouring lanes sit on different rows and gather.  Output and tap indices are 64-bit: k * down passes 2^31 after about five
@@ -71,6 +76,26 @@ __device__ __forceinline__ void ingest_stage(const IngestJob& J, float* s, int64
   }
 }
 
+// THE sum of both kernels: out[kk] = y[k0 + kk] for kk < nk from the staged span s (mono samples from frame i_lo on).  A file
+// and a wire stream agree bit for bit because they both run this: the same operands in the same order, i ascending.
+template <bool UP1>
+__device__ __forceinline__ void ingest_sum(const float* __restrict__ taps, int L, int up, int down, int half, const float* s,
+                                           float* __restrict__ out, int64_t k0, int64_t i_lo, int nk) {
+  for (int kk = threadIdx.x; kk < nk; kk += kIngestThreads) {
+    // y[k] = sum_i mono[i] h[a - i up], a = k down + half: with ih = a / up and p = a % up the taps are row p of the table,
+    // h[p + j up] at i = ih - j, for the j whose tap index is at most 2 half
+    const int64_t a = (k0 + kk) * down + half;
+    int64_t ih; int p, jmax;
+    if constexpr (UP1) { ih = a; p = 0; jmax = 2 * half; }
+    else { ih = a / up; p = (int)(a - ih * up); jmax = (2 * half - p) / up; }
+    const float* __restrict__ row = taps + (size_t)p * L;
+    const float* __restrict__ x = s + (int)(ih - i_lo);
+    float acc = 0.0f;
+    for (int j = jmax; j >= 0; --j) acc = fmaf(x[-j], row[j], acc);   // i ascending
+    out[kk] = acc;
+  }
+}
+
 template <bool UP1>
 __global__ __launch_bounds__(kIngestThreads) void ingest_kernel(const IngestJob J) {
   extern __shared__ float s[];   // [span] mono samples from frame i_lo on
@@ -94,19 +119,69 @@ __global__ __launch_bounds__(kIngestThreads) void ingest_kernel(const IngestJob 
     for (int kk = threadIdx.x; kk < nk; kk += kIngestThreads) out[kk] = s[kk];
     return;
   }
-  for (int kk = threadIdx.x; kk < nk; kk += kIngestThreads) {
-    // y[k] = sum_i mono[i] h[a - i up], a = k down + half: with ih = a / up and p = a % up the taps are row p of the table,
-    // h[p + j up] at i = ih - j, for the j whose tap index is at most 2 half
-    const int64_t a = (k0 + kk) * J.down + J.half;
-    int64_t ih; int p, jmax;
-    if constexpr (UP1) { ih = a; p = 0; jmax = 2 * J.half; }
-    else { ih = a / J.up; p = (int)(a - ih * J.up); jmax = (2 * J.half - p) / J.up; }
-    const float* __restrict__ row = J.taps + (size_t)p * J.L;
-    const float* __restrict__ x = s + (int)(ih - i_lo);
-    float acc = 0.0f;
-    for (int j = jmax; j >= 0; --j) acc = fmaf(x[-j], row[j], acc);   // i ascending
-    out[kk] = acc;
+  ingest_sum<UP1>(J.taps, J.L, J.up, J.down, J.half, s, out, k0, i_lo, nk);
+}
+
+// mono[i] of a wire stream's row: below frame 0 and behind the chunk zeros, in front of the chunk the stream's history
+template <int FMT>
+__device__ __forceinline__ float wire_frame(const WireJob& J, const uint8_t* __restrict__ raw, const float* __restrict__ hist, int64_t i) {
+  if (i < 0) return 0.0f;
+  const int64_t r = i - J.f_old;
+  if (r < 0) return r + J.H >= 0 ? hist[J.hist_in + (int)(r + J.H)] : 0.0f;
+  return r < J.nf ? ingest_frame<FMT>(raw, r, J.channels, J.pick) : 0.0f;
+}
+
+// q-th of `count` mono values from frame i_lo on -> dst[q]
+template <int FMT>
+__device__ __forceinline__ void wire_stage(const WireJob& J, const uint8_t* __restrict__ raw, const float* __restrict__ hist,
+                                           float* dst, int64_t i_lo, int count) {
+  for (int q = threadIdx.x; q < count; q += kIngestThreads) dst[q] = wire_frame<FMT>(J, raw, hist, i_lo + q);
+}
+
+__device__ __forceinline__ void wire_stage_any(const WireJob& J, const uint8_t* __restrict__ raw, const float* __restrict__ hist,
+                                               float* dst, int64_t i_lo, int count) {
+  switch (J.format) {
+    case TTASR_PCM_U8: wire_stage<TTASR_PCM_U8>(J, raw, hist, dst, i_lo, count); break;
+    case TTASR_PCM_S16: wire_stage<TTASR_PCM_S16>(J, raw, hist, dst, i_lo, count); break;
+    case TTASR_PCM_S24: wire_stage<TTASR_PCM_S24>(J, raw, hist, dst, i_lo, count); break;
+    case TTASR_PCM_S32: wire_stage<TTASR_PCM_S32>(J, raw, hist, dst, i_lo, count); break;
+    case TTASR_PCM_F32: wire_stage<TTASR_PCM_F32>(J, raw, hist, dst, i_lo, count); break;
+    case TTASR_PCM_ALAW: wire_stage<TTASR_PCM_ALAW>(J, raw, hist, dst, i_lo, count); break;
+    case TTASR_PCM_ULAW: wire_stage<TTASR_PCM_ULAW>(J, raw, hist, dst, i_lo, count); break;
+    default: wire_stage<TTASR_PCM_F64>(J, raw, hist, dst, i_lo, count); break;
   }
+}
+
+// Wire streams: blockIdx.y is the row of the job table, blockIdx.x a tile of the row's outputs, and the block behind the row's
+// last tile writes the row's new history.  Tiles read the history half the row had before the push chunk (hist_in), the history
+// block writes the other half (hist_out): no workgroup reads what another writes.  The job's fields are uniform over the
+// workgroup: the compiler fetches them through the scalar unit.
+__global__ __launch_bounds__(kIngestThreads) void wire_kernel(const WireJob* __restrict__ jobs, const uint8_t* __restrict__ raw_pool,
+                                                              float* __restrict__ out_pool, float* __restrict__ hist) {
+  extern __shared__ float s[];   // [span] mono samples from frame i_lo on
+  const WireJob J = jobs[blockIdx.y];
+  const int tiles = (J.n_out + J.tile - 1) / J.tile;
+  const int t = (int)blockIdx.x;
+  const uint8_t* __restrict__ raw = raw_pool + J.raw_off;
+  if (t > tiles) return;
+  if (t == tiles) {   // the last H mono values after the chunk
+    if (J.hist_out >= 0) wire_stage_any(J, raw, hist, hist + J.hist_out, J.f_old + J.nf - J.H, J.H);
+    return;
+  }
+  const int64_t k0 = J.k_begin + (int64_t)t * J.tile;
+  const int left = J.n_out - t * J.tile;
+  const int nk = left < J.tile ? left : J.tile;
+  const int64_t i_lo = J.taps ? -floor_div((int64_t)J.half - k0 * J.down, J.up) : k0;   // ceil((k0 down - half) / up)
+  const int span = J.taps ? (int)((int64_t)nk * J.down / J.up) + 2 * J.half / J.up + 2 : nk;
+  wire_stage_any(J, raw, hist, s, i_lo, span);
+  __syncthreads();
+  float* __restrict__ out = out_pool + J.out_off + t * J.tile;
+  if (!J.taps) {
+    for (int kk = threadIdx.x; kk < nk; kk += kIngestThreads) out[kk] = s[kk];
+    return;
+  }
+  if (J.up == 1) ingest_sum<true>(J.taps, J.L, J.up, J.down, J.half, s, out, k0, i_lo, nk);
+  else ingest_sum<false>(J.taps, J.L, J.up, J.down, J.half, s, out, k0, i_lo, nk);
 }
 
 __constant__ int16_t kImaStep[89] = {
@@ -166,6 +241,15 @@ void launch_ingest(const IngestJob& j, hipStream_t s) {
   const unsigned grid = (unsigned)((j.n_out + j.tile - 1) / j.tile);
   if (j.taps && j.up == 1) ingest_kernel<true><<<grid, kIngestThreads, lds, s>>>(j);
   else ingest_kernel<false><<<grid, kIngestThreads, lds, s>>>(j);
+}
+
+void launch_wire(const WireJob* jobs, int n, int max_tiles, int span, const uint8_t* raw, float* out, float* hist, hipStream_t s) {
+  if (n <= 0) return;
+  if (n > 65535 || max_tiles < 0 || span < 1 || span > kWireSpan || !jobs || !raw || !out || !hist) {
+    launch_fault("wire: %d rows, %d tiles, span %d", n, max_tiles, span);
+    return;
+  }
+  wire_kernel<<<dim3((unsigned)max_tiles + 1, (unsigned)n), kIngestThreads, (size_t)span * sizeof(float), s>>>(jobs, raw, out, hist);
 }
 
 void launch_ima_decode(const ImaJob& j, hipStream_t s) {

@@ -80,6 +80,7 @@ class Engine:
         self.special = SpecialTokens.for_vocab(dims.vocab)
         self.audio_ctx = dims.n_audio_ctx
         self.has_vad = False   # load_vad() has put the VAD network on this context
+        self._wire_streams = {}   # wire stream id -> (rate, bytes per frame, samples a finish releases): sizes vad_stream_push_wire's result rows
 
     # -- plumbing ------------------------------------------------------------------------------
     def _check(self, rc: int, what: str):
@@ -148,13 +149,73 @@ class Engine:
         return (probs, logits) if return_logits else probs
 
     # -- streaming voice activity detection --------------------------------------------------------
-    def vad_stream_open(self) -> int:
+    def vad_stream_open(self, wire=None) -> int:
         """A new VAD stream of this context - one recording that arrives in pieces - with zero state and nothing pending
         (ttasr_vad_stream_open).  The first open allocates everything the stream path needs, so it is refused inside an open
-        session; at most _lib.VAD_MAX_STREAMS streams are open at a time."""
+        session; at most _lib.VAD_MAX_STREAMS streams of both kinds are open at a time.
+        wire = (rate, channels, format, pick) with format one of _lib.PCM_* (not PCM_IMA4) and pick None / -1 for the mean of the
+        channels or a channel index, or an object with `.wire_args()` (vad.WireFormat): a WIRE stream
+        (ttasr_vad_stream_open_wire), fed bytes through `vad_stream_push_wire`."""
         sid = C.c_int32(-1)
-        self._check(self.lib.ttasr_vad_stream_open(self.h, C.byref(sid)), "vad_stream_open")
+        if wire is None:
+            self._check(self.lib.ttasr_vad_stream_open(self.h, C.byref(sid)), "vad_stream_open")
+            return int(sid.value)
+        rate, channels, fmt, pick = wire.wire_args() if hasattr(wire, "wire_args") else wire
+        self._check(self.lib.ttasr_vad_stream_open_wire(self.h, int(rate), int(channels), int(fmt), -1 if pick is None else int(pick),
+                                                        C.byref(sid)), "vad_stream_open_wire")
+        tail = self.ingest_stream_len(rate, 1 << 20, True) - self.ingest_stream_len(rate, 1 << 20, False)   # what a finish releases
+        self._wire_streams[int(sid.value)] = (int(rate), int(channels) * (_lib.CODED_BYTES.get(int(fmt)) or _lib.PCM_BYTES[int(fmt)]),
+                                              tail)
         return int(sid.value)
+
+    def ingest_stream_len(self, rate: int, n_frames: int, finished: bool = False) -> int:
+        """Final 16 kHz samples of a wire stream after n_frames frames at `rate` (ttasr_ingest_stream_len): K(n_frames), or all
+        ceil(n_frames up / down) when finished; negative when `rate` is no stream rate."""
+        return int(self.lib.ttasr_ingest_stream_len(int(rate), int(n_frames), 1 if finished else 0))
+
+    def vad_stream_push_wire(self, ids: Sequence[int], raws: Sequence, finish: Optional[Sequence[bool]] = None,
+                             return_logits: bool = False):
+        """Append raws[i] (bytes-like, any length - a piece may end inside a sample) to WIRE stream ids[i], all rows in ONE call
+        (ttasr_vad_stream_push_wire): (pcm, probs[, logits]), one float32 array per row each - the 16 kHz mono samples that became
+        final and the probabilities of the 512-sample frames they completed.  The concatenated pcm of a stream whose last push has
+        finish equals `ingest` of the whole recording bit for bit, and the probabilities `vad_probs` of that, however the bytes
+        are cut.  Legal inside an open session, between its calls."""
+        n = len(ids)
+        if len(raws) != n or (finish is not None and len(finish) != n):
+            raise ValueError("ids, raws and finish must have one entry per row")
+        if n == 0:
+            return ([], [], []) if return_logits else ([], [])
+        bufs = [np.frombuffer(r, dtype=np.uint8) if isinstance(r, (bytes, bytearray, memoryview))
+                else np.ascontiguousarray(r).reshape(-1).view(np.uint8) for r in raws]
+        # room for every sample the bytes can make final: all held frames + the new ones, finished (the library checks it)
+        caps = []
+        for sid, b in zip(ids, bufs):
+            # an id that is no wire stream of this engine: any size will do, the library refuses the call
+            rate, fb, tail = self._wire_streams.get(int(sid), (16000, 1, 0))
+            caps.append(self.ingest_stream_len(rate, len(b) // fb + 2, True) + tail + 2)
+        pcm = [np.zeros(k, dtype=np.float32) for k in caps]
+        probs = [np.zeros(k // 512 + 3, dtype=np.float32) for k in caps]
+        logits = [np.zeros_like(p) for p in probs] if return_logits else None
+        i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        idv = np.asarray(list(ids), dtype=np.int32)
+        nb = np.asarray([len(b) for b in bufs], dtype=np.int64)
+        cap = np.asarray(caps, dtype=np.int64)
+        got = np.zeros(n, dtype=np.int64)
+        fin = np.asarray([1 if f else 0 for f in finish], dtype=np.int32) if finish is not None else None
+        frames = np.zeros(n, dtype=np.int32)
+        ptrs = (C.c_void_p * n)(*[b.ctypes.data if len(b) else None for b in bufs])
+        pouts = (C.c_void_p * n)(*[p.ctypes.data for p in pcm])
+        outs = (C.c_void_p * n)(*[p.ctypes.data for p in probs])
+        louts = (C.c_void_p * n)(*[p.ctypes.data for p in logits]) if return_logits else None
+        self._check(self.lib.ttasr_vad_stream_push_wire(self.h, n, idv.ctypes.data_as(i32p), ptrs, nb.ctypes.data_as(i64p),
+                                                        fin.ctypes.data_as(i32p) if fin is not None else None, pouts,
+                                                        cap.ctypes.data_as(i64p), got.ctypes.data_as(i64p), outs, louts,
+                                                        frames.ctypes.data_as(i32p)), "vad_stream_push_wire")
+        pcm = [p[:k].copy() for p, k in zip(pcm, got)]
+        probs = [p[:k].copy() for p, k in zip(probs, frames)]
+        if return_logits:
+            return pcm, probs, [l[:k].copy() for l, k in zip(logits, frames)]
+        return pcm, probs
 
     def vad_stream_reset(self, stream_id: int):
         """The stream is as freshly opened (ttasr_vad_stream_reset); legal inside an open session."""
@@ -162,6 +223,7 @@ class Engine:
 
     def vad_stream_close(self, stream_id: int):
         self._check(self.lib.ttasr_vad_stream_close(self.h, int(stream_id)), "vad_stream_close")
+        self._wire_streams.pop(int(stream_id), None)
 
     def vad_stream_push(self, ids: Sequence[int], audios: Sequence[np.ndarray], finish: Optional[Sequence[bool]] = None,
                         return_logits: bool = False):

@@ -62,7 +62,11 @@ class BatchedWhisperASR(MI355XWhisperASR):
 
     `session_prefill=N` (opt-in, continuous=True only; True = config.SESSION_PREFILL_DEFAULT): the initial_prompt's positions in
     front of <|startoftranscript|> come from one admission pass of the session instead of one forced decode step each, when there
-    are at least N of them (Engine.session(prefill=N)); requests that carry the language placeholder are forced as before."""
+    are at least N of them (Engine.session(prefill=N)); requests that carry the language placeholder are forced as before.
+
+    `wire=` / `audio_from=` (opt-in, both modes; MI355XWhisperASR.client_audio): what the clients' scratch bytes are when they
+    are not 16 kHz mono s16 - a vad.WireFormat, or "client" for each client's own declaration - and the
+    vad_backends.DeviceStreamVAD(wire=...) whose device streams have converted the same bytes already."""
 
     def __init__(self, max_clips: int = 6, max_wait_ms: float = 5.0, audio_ctx=None, max_new_tokens: int = 224,
                  continuous: bool = False, word_timestamps: bool = False, detect_in_session: bool = False,
@@ -221,7 +225,7 @@ class BatchedWhisperASR(MI355XWhisperASR):
 
     async def transcribe(self, client) -> Optional[Dict[str, Any]]:
         try:
-            audio = pcm16_bytes_to_float(client.scratch_buffer)
+            audio = self.client_audio(client)   # wire=None: the s16 bytes at 16 kHz, as ever (MI355XWhisperASR.client_audio)
             if self.continuous:
                 self._ensure_session()
                 loop = asyncio.get_running_loop()

@@ -36,6 +36,108 @@ class VadOptions:
     speech_pad_ms: int = 400
 
 
+# encoding name -> (TTASR_PCM_* code of include/ttasr.h, bytes per sample): the sample formats model.read_audio_raw reports and
+# the two G.711 laws.  IMA ADPCM is a block codec, not a stream.
+WIRE_ENCODINGS = {"u8": (0, 1), "s16": (1, 2), "s24": (2, 3), "s32": (3, 4), "f32": (4, 4), "f64": (5, 8), "alaw": (16, 1), "ulaw": (17, 1)}
+
+
+@dataclass(frozen=True)
+class WireFormat:
+    """What a live connection sends (the streaming server's `rate` / `channel` query parameters, the config message's sampleRate /
+    channels): interleaved little-endian samples of `encoding` (WIRE_ENCODINGS) at `rate` Hz, `channels` (1 ... 8) per frame;
+    audio_channel picks one of them in model.parse_audio_channel's spellings (None / "mix" = their mean, "left", "right", an
+    index)."""
+    rate: int
+    channels: int = 1
+    encoding: str = "s16"
+    audio_channel: object = None
+
+    def __post_init__(self):
+        if self.encoding not in WIRE_ENCODINGS:
+            raise ValueError(f"encoding {self.encoding!r}: expected one of {sorted(WIRE_ENCODINGS)}")
+        if isinstance(self.rate, bool) or int(self.rate) != self.rate or self.rate < 1:
+            raise ValueError(f"rate {self.rate!r} must be a positive integer")
+        if isinstance(self.channels, bool) or int(self.channels) != self.channels or not 1 <= self.channels <= 8:
+            raise ValueError(f"channels {self.channels!r} outside 1 ... 8")
+        if self.pick is not None and self.pick >= self.channels:
+            raise ValueError(f"audio_channel {self.audio_channel!r} asked of {self.channels} channel{'s' if self.channels != 1 else ''}")
+
+    @property
+    def format(self) -> int:
+        return WIRE_ENCODINGS[self.encoding][0]
+
+    @property
+    def frame_bytes(self) -> int:
+        return WIRE_ENCODINGS[self.encoding][1] * int(self.channels)
+
+    @property
+    def pick(self) -> Optional[int]:
+        from .model import parse_audio_channel
+        return parse_audio_channel(self.audio_channel)
+
+    def wire_args(self):
+        """(rate, channels, format, pick) of ttasr_vad_stream_open_wire."""
+        return int(self.rate), int(self.channels), self.format, -1 if self.pick is None else self.pick
+
+    def to_mono(self, raw) -> np.ndarray:
+        """The whole frames of `raw` on the host -> float32 mono at `rate`: decode_audio's conversion (G.711 through its int16)."""
+        from .model import _g711_table
+        raw = bytes(raw)
+        raw = raw[:len(raw) - len(raw) % self.frame_bytes]
+        e = self.encoding
+        if e in ("alaw", "ulaw"):
+            x = _g711_table(e == "ulaw")[np.frombuffer(raw, dtype=np.uint8)].astype(np.float32) / 32768.0
+        elif e == "u8":
+            x = (np.frombuffer(raw, dtype=np.uint8).astype(np.float32) - 128.0) / 128.0
+        elif e == "s16":
+            x = np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32768.0
+        elif e == "s24":
+            b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
+            x = ((b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)) << 8 >> 8).astype(np.float32) / 8388608.0
+        elif e == "s32":
+            x = np.frombuffer(raw, dtype="<i4").astype(np.float32) / 2147483648.0
+        else:
+            x = np.frombuffer(raw, dtype="<f4" if e == "f32" else "<f8").astype(np.float32)
+        if self.channels > 1:
+            x = x.reshape(-1, self.channels)
+            x = x.mean(axis=1) if self.pick is None else x[:, self.pick]
+        return np.ascontiguousarray(x, dtype=np.float32)
+
+    def to_16k(self, raw) -> np.ndarray:
+        """`to_mono`, then the package's host resampler (model._to_mono_16k: scipy's resample_poly over the WHOLE buffer - run
+        piece by piece it is not cut-invariant, which is what wire streams are for)."""
+        from .model import _to_mono_16k
+        return _to_mono_16k(self.to_mono(raw), int(self.rate), SAMPLING_RATE)
+
+    @staticmethod
+    def of_client(client) -> "WireFormat":
+        """The format a streaming client declares: client.sampling_rate and client.samples_width (bytes per sample), and the
+        optional attributes client.channels, client.encoding and client.audio_channel.  Without an encoding the width decides -
+        2 s16, 3 s24, 4 s32, 8 f64 - and width 1 is refused: u8, A-law and mu-law are all one byte."""
+        width, enc = int(client.samples_width), getattr(client, "encoding", None)
+        if enc is None:
+            if width == 1:
+                raise ValueError("samples_width 1 is ambiguous (u8, alaw, ulaw): the client must carry an encoding")
+            enc = {2: "s16", 3: "s24", 4: "s32", 8: "f64"}.get(width)
+            if enc is None:
+                raise ValueError(f"samples_width {width} is no sample format")
+        elif enc not in WIRE_ENCODINGS or WIRE_ENCODINGS[enc][1] != width:
+            raise ValueError(f"encoding {enc!r} does not have samples_width {width}")
+        return WireFormat(int(client.sampling_rate), int(getattr(client, "channels", 1) or 1), enc, getattr(client, "audio_channel", None))
+
+
+def resolve_wire(wire, client=None) -> Optional[WireFormat]:
+    """The `wire=` keyword of the streaming surfaces: None (16 kHz mono s16, as ever), a WireFormat, or "client" = what the client
+    declares (WireFormat.of_client)."""
+    if wire is None or isinstance(wire, WireFormat):
+        return wire
+    if wire == "client":
+        if client is None:
+            raise ValueError('wire="client" needs a client')
+        return WireFormat.of_client(client)
+    raise ValueError(f"wire {wire!r}: expected None, a WireFormat or 'client'")
+
+
 def energy_speech_prob(audio: np.ndarray, window: int = WINDOW) -> np.ndarray:
     """Stand-in for the Silero network: logistic of the frame's RMS level over an adaptive noise floor
     (10th percentile of the frame levels, at least -60 dBFS).  6 dB above the floor -> 0.5."""
@@ -254,11 +356,19 @@ class StreamingSpeechDetector:
     zero-pads the last frame); the part left out is never more than 32 ms, well under the 100 ms the streaming trigger allows
     behind the last segment."""
 
-    def __init__(self, engine, stream_id: Optional[int] = None):
+    def __init__(self, engine, stream_id: Optional[int] = None, wire: Optional[WireFormat] = None):
+        """wire=WireFormat(...): a WIRE stream - `feed_bytes` takes the connection's bytes in that format, however they are cut,
+        the device converts, downmixes and resamples them in front of the network, and `audio` is the 16 kHz float32 so far
+        (bit for bit Engine.ingest of the bytes fed, up to the samples whose inputs have not all arrived).  `segments` stays in
+        16 kHz samples."""
         self.engine = engine
-        self.stream_id = engine.vad_stream_open() if stream_id is None else int(stream_id)
+        self.wire = wire
+        if stream_id is None:
+            stream_id = engine.vad_stream_open() if wire is None else engine.vad_stream_open(wire=wire)
+        self.stream_id = int(stream_id)
         self.n_samples = 0
         self._probs: List[np.ndarray] = []
+        self._audio: List[np.ndarray] = []
 
     @property
     def probs(self) -> np.ndarray:
@@ -271,11 +381,29 @@ class StreamingSpeechDetector:
         samples = np.ascontiguousarray(samples, dtype=np.float32)
         self.extend(len(samples), self.engine.vad_stream_push([self.stream_id], [samples])[0])
 
-    def extend(self, n_samples: int, probs: np.ndarray) -> None:
-        """Book what a push made elsewhere returned for this stream (a backend that pushes many streams in one call)."""
+    @property
+    def audio(self) -> np.ndarray:
+        """A wire stream's 16 kHz float32 samples so far (empty for a float stream: its caller has them)."""
+        if len(self._audio) != 1:
+            self._audio = [np.concatenate(self._audio) if self._audio else np.zeros(0, dtype=np.float32)]
+        return self._audio[0]
+
+    def feed_bytes(self, raw, finish: bool = False) -> None:
+        """Append bytes in the stream's wire format (any length: a piece may end inside a sample).  finish=True also releases the
+        samples that wait for inputs behind the end, evaluates the zero-padded last frame and leaves the device stream as reset."""
+        if self.wire is None:
+            raise ValueError("feed_bytes is for a detector opened with wire=")
+        pcm, probs = self.engine.vad_stream_push_wire([self.stream_id], [raw], finish=[bool(finish)])
+        self.extend(len(pcm[0]), probs[0], pcm[0])
+
+    def extend(self, n_samples: int, probs: np.ndarray, pcm: Optional[np.ndarray] = None) -> None:
+        """Book what a push made elsewhere returned for this stream (a backend that pushes many streams in one call); pcm: the
+        16 kHz samples a wire push returned."""
         self.n_samples += int(n_samples)
         if len(probs):
             self._probs.append(np.asarray(probs, dtype=np.float32))
+        if pcm is not None and len(pcm):
+            self._audio.append(np.asarray(pcm, dtype=np.float32))
 
     def segments(self, options: Optional[VadOptions] = None) -> List[Dict[str, int]]:
         """[{'start': sample, 'end': sample}] of the audio fed so far, cut to whole frames."""
@@ -291,6 +419,7 @@ class StreamingSpeechDetector:
         """Forget the bookkeeping only (the stream itself was reset elsewhere)."""
         self.n_samples = 0
         self._probs = []
+        self._audio = []
 
     def close(self) -> None:
         if self.stream_id is not None:

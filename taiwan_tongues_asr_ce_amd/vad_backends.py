@@ -51,13 +51,14 @@ DEFAULT_STREAM_VAD_OPTIONS = dict(threshold=0.5, min_speech_duration_ms=300, min
 
 class _ClientStream:
     """One client's stream: the detector, how many bytes of its scratch buffer the stream has consumed, and their CRC."""
-    __slots__ = ("detector", "consumed", "crc", "needs_reset")
+    __slots__ = ("detector", "consumed", "crc", "needs_reset", "wire")
 
-    def __init__(self):
+    def __init__(self, wire: Optional[vad.WireFormat] = None):
         self.detector: Optional[vad.StreamingSpeechDetector] = None   # opened by the first push
         self.consumed = 0
         self.crc = 0
         self.needs_reset = False
+        self.wire = wire              # None: 16 kHz mono s16 through the float push
 
 
 class DeviceStreamVAD(VADInterface):
@@ -80,10 +81,22 @@ class DeviceStreamVAD(VADInterface):
     (a mapping, an .npz or a TorchScript / state-dict file: vad.load_silero_state), so it never contends with the ASR context's
     calls or session.  `engine=`: it shares that context - whose VAD weights are loaded already, or come from `vad_model` - and
     the caller serialises the calls; a stream cannot be OPENED while a session is open on that context (a new client's first call
-    then fails), pushes and resets can."""
+    then fails), pushes and resets can.
+
+    `wire=None`: every client sends 16 kHz mono s16, as above.  `wire=vad.WireFormat(...)`: every client sends that format;
+    `wire="client"`: each client declares its own (vad.WireFormat.of_client: sampling_rate, samples_width and the optional
+    channels / encoding / audio_channel attributes; width 1 without an encoding is refused).  The clients' streams are then WIRE
+    streams: the raw tail of the scratch buffer goes to Engine.vad_stream_push_wire as it is - cut nowhere, a byte that ends
+    inside a sample waits inside the library - and the device converts, downmixes and resamples in front of the network.  The
+    segments stay in seconds of the client's audio.  `audio(client)` is the converted 16 kHz PCM that mirrors the consumed
+    scratch bytes (what an ASR adapter with audio_from= transcribes): the samples whose inputs have all arrived - up to
+    ceil(half / down) samples (10 periods of the lower of the two rates, 1.25 ms at 8 kHz) at the end are not final yet."""
 
     def __init__(self, vad_model=None, engine=None, max_wait_ms: float = 2.0, vad_parameters: Optional[Dict[str, Any]] = None,
-                 **kwargs):
+                 wire=None, **kwargs):
+        if wire is not None and wire != "client" and not isinstance(wire, vad.WireFormat):
+            raise ValueError(f"wire {wire!r}: expected None, a vad.WireFormat or 'client'")
+        self.wire = wire
         self.owns_engine = engine is None
         if engine is None:
             if vad_model is None:
@@ -109,7 +122,8 @@ class DeviceStreamVAD(VADInterface):
     async def detect_activity(self, client):
         st = self._streams.get(client.client_id)
         if st is None:
-            st = self._streams[client.client_id] = _ClientStream()
+            st = _ClientStream(vad.resolve_wire(self.wire, client))   # a client whose declaration is refused gets no stream
+            self._streams[client.client_id] = st
         loop = asyncio.get_running_loop()
         self._ensure_worker(loop)
         fut = loop.create_future()
@@ -117,6 +131,16 @@ class DeviceStreamVAD(VADInterface):
         chunks = await fut
         rate = float(vad.SAMPLING_RATE)
         return [{"start": c["start"] / rate, "end": c["end"] / rate, "confidence": 1.0} for c in chunks]
+
+    def audio(self, client, covering: Optional[bytes] = None):
+        """A wire client's converted 16 kHz float32 PCM so far, or None: for a client without a wire stream, and - with
+        covering= the client's scratch bytes - when the stream has not consumed exactly those bytes (another length or CRC)."""
+        st = self._streams.get(getattr(client, "client_id", client))
+        if st is None or st.wire is None or st.detector is None or st.needs_reset:
+            return None
+        if covering is not None and (len(covering) != st.consumed or zlib.crc32(bytes(covering)) != st.crc):
+            return None
+        return st.detector.audio
 
     def forget(self, client) -> None:
         st = self._streams.pop(getattr(client, "client_id", client), None)
@@ -179,7 +203,10 @@ class DeviceStreamVAD(VADInterface):
                     st.detector.clear()
                     st.consumed, st.crc = 0, 0
                 st.needs_reset = False
-                st.detector.extend(len(new) // 2, p)
+                if st.wire is None:
+                    st.detector.extend(len(new) // 2, p)
+                else:                      # p = (probabilities, the 16 kHz samples the bytes made final)
+                    st.detector.extend(len(p[1]), p[0], p[1])
                 st.consumed += len(new)
                 st.crc = zlib.crc32(new, st.crc)
                 if not fut.done():
@@ -191,23 +218,30 @@ class DeviceStreamVAD(VADInterface):
         of what the stream consumed (shorter, or another CRC over the prefix), a reset and the whole buffer."""
         reset = st.needs_reset or len(buf) < st.consumed or zlib.crc32(buf[:st.consumed]) != st.crc
         start = 0 if reset else st.consumed
+        if st.wire is not None:   # a wire stream takes the tail as it is: bytes that fill no frame wait inside the library
+            return reset, buf[start:]
         return reset, buf[start:len(buf) - (len(buf) - start) % 2]
 
     def _run_push(self, streams, rows):
         with self._lock:
             for st, (reset, _) in zip(streams, rows):
                 if st.detector is None:
-                    st.detector = vad.StreamingSpeechDetector(self.engine)
+                    st.detector = (vad.StreamingSpeechDetector(self.engine) if st.wire is None
+                                   else vad.StreamingSpeechDetector(self.engine, wire=st.wire))
                 elif reset:
                     self.engine.vad_stream_reset(st.detector.stream_id)
-            return self.engine.vad_stream_push([st.detector.stream_id for st in streams],
-                                               [pcm16_bytes_to_float(new) for _, new in rows])
+            if self.wire is None:
+                return self.engine.vad_stream_push([st.detector.stream_id for st in streams],
+                                                   [pcm16_bytes_to_float(new) for _, new in rows])
+            pcm, probs = self.engine.vad_stream_push_wire([st.detector.stream_id for st in streams], [new for _, new in rows])
+            return list(zip(probs, pcm))
 
 
 class VADFactory:
     @staticmethod
     def create_vad_pipeline(type, **kwargs):
-        """vad_factory.py:13-44 knows "simple" only; "silero" / "mi355x_silero" is the device backend."""
+        """vad_factory.py:13-44 knows "simple" only; "silero" / "mi355x_silero" is the device backend (its keywords, wire=
+        among them, pass through)."""
         if type == "simple":
             return SimpleVAD(**kwargs)
         if type in ("silero", "mi355x_silero"):

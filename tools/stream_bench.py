@@ -9,6 +9,7 @@ weights never emit EOT, so `--new-tokens` caps the decode length (16 ≈ a 3-s M
     python tools/stream_bench.py --model large-v3 --streams 8 --rounds 6 --beam 5
     python tools/stream_bench.py --model large-v3 --streams 8 --rounds 6 --beam 5 --audio-ctx auto   # N2 short window
     python tools/stream_bench.py --model large-v3 --streams 8 --rounds 6 --beam 5 --continuous       # beam session backend
+    python tools/stream_bench.py --model large-v3 --streams 8 --rounds 6 --beam 5 --wire ulaw8k      # telephony clients
 """
 import argparse
 import asyncio
@@ -22,6 +23,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(1, os.path.join(ROOT, "tools"))
 
 
 async def run(args):
@@ -31,16 +33,28 @@ async def run(args):
     max_clips = max(1, 32 // beam) if args.max_clips == 0 else args.max_clips
     if args.continuous and args.audio_ctx != "none":
         raise SystemExit("--continuous encodes the full window: --audio-ctx must be none")
+    wire = vad_backend = None
+    if args.wire:
+        from taiwan_tongues_asr_ce_amd import vad
+        from taiwan_tongues_asr_ce_amd.vad_backends import DeviceStreamVAD
+        from vad_bench import WIRES
+        wire = vad.WireFormat(**WIRES[args.wire])
+        vad_backend = DeviceStreamVAD(vad_model=vad.synth_silero_weights(), wire=wire)   # its own VAD-only context
     asr = BatchedWhisperASR(max_clips=max_clips, max_wait_ms=args.max_wait_ms, beam_size=beam, continuous=args.continuous,
                             audio_ctx=None if args.audio_ctx == "none" else (args.audio_ctx if args.audio_ctx == "auto" else int(args.audio_ctx)),
                             max_new_tokens=args.new_tokens, model_size=f"synthetic:{args.model}", compute_type="bfloat16",
-                            session_prefill=args.session_prefill)
+                            session_prefill=args.session_prefill, wire=wire, audio_from=vad_backend)
     utter = [np.clip(synth.noise_clip(1000 + i, int(args.utterance_s * 16000)) * 32768.0, -32768, 32767).astype("<i2").tobytes()
              for i in range(args.streams)]
+    if wire is not None:      # the same utterances as the wire format carries them (tools/vad_bench.py wire_pieces)
+        from vad_bench import wire_pieces
+        utter = wire_pieces(wire, args.streams, args.utterance_s)
     lat = []
 
     async def client(i):
         c = types.SimpleNamespace(scratch_buffer=utter[i], last_start_time=0, client_id=i)
+        if vad_backend is not None:                     # the server asks the VAD first: its stream has converted the bytes
+            await vad_backend.detect_activity(c)
         for r in range(args.rounds + 1):
             t = time.perf_counter()
             res = await asr.transcribe(c)
@@ -55,6 +69,8 @@ async def run(args):
     await asyncio.gather(*(client(i) for i in range(args.streams)))
     wall = time.perf_counter() - t0
     await asr.aclose()
+    if vad_backend is not None:
+        vad_backend.close()
     lat_ms = np.asarray(lat) * 1e3
     sizes = asr.batches_run                              # empty for the continuous backend (no lock-step passes)
     out = {
@@ -88,6 +104,9 @@ def main():
     ap.add_argument("--session-prefill", type=int, default=0, metavar="N",
                     help="with --continuous: BatchedWhisperASR(session_prefill=N) - the initial prompt's positions come from an "
                          "admission pass of the session when there are at least N of them")
+    ap.add_argument("--wire", default=None, choices=("ulaw8k", "s16x2_8k", "s16_48k"),
+                    help="the clients send this wire format: a DeviceStreamVAD(wire=) converts it on the device and "
+                         "BatchedWhisperASR(wire=, audio_from=) transcribes that audio")
     asyncio.run(run(ap.parse_args()))
 
 

@@ -19,8 +19,14 @@ and nothing else (the command a kernel trace is taken of).
              stateless alternative - Engine.vad_probs over the accumulated 3-s buffers of the same streams, what a server
              without streams runs at every chunk.  2 warm-ups, median / min / max of --repeats.  Records, not gates.
 
+  --stream --wire ulaw8k|s16x2_8k|s16_48k   wire streams (Engine.vad_stream_push_wire): one push of 64 streams x 1.5-s pieces in
+             that wire format, in ms per push, beside the same pieces converted and resampled on the host and then pushed as
+             16 kHz floats, and beside the file kernel run per row (Engine.ingest) and then pushed.  --trace-pushes N: N wire
+             pushes and nothing else (the command a kernel trace counts launches of).
+
     python tools/vad_bench.py [--model large-v3] [--repeats 7] [--out profiles/vad_device.json]
     python tools/vad_bench.py --stream [--repeats 7] [--out profiles/vad_stream.json]
+    python tools/vad_bench.py --stream --wire ulaw8k [--repeats 7] [--out profiles/wire_stream.json]
 """
 from __future__ import annotations
 
@@ -120,6 +126,71 @@ def stream_bench(repeats: int) -> dict:
     return res
 
 
+WIRES = {"ulaw8k": dict(rate=8000, channels=1, encoding="ulaw"), "s16x2_8k": dict(rate=8000, channels=2, encoding="s16"),
+         "s16_48k": dict(rate=48000, channels=1, encoding="s16")}
+
+
+def wire_pieces(fmt, n: int, seconds: float):
+    """n pieces of `seconds` in the wire format, cut from the burst signal resampled by plain interpolation (a bench input)."""
+    base = bursts(3000, 40.0)
+    frames = int(seconds * fmt.rate)
+    out = []
+    for i in range(n):
+        at = (997 * i) % (len(base) - int(seconds * 16000) - 1)
+        x = np.interp(np.arange(frames) * (16000.0 / fmt.rate), np.arange(int(seconds * 16000) + 1), base[at:at + int(seconds * 16000) + 1])
+        s16 = np.round(np.clip(x, -1, 1) * 32767).astype(np.int16)
+        if fmt.encoding == "ulaw":   # G.711 mu-law encoder (bench input only): sign, segment of the biased magnitude, four mantissa bits
+            mag = np.minimum(np.abs(s16.astype(np.int32)), 32635) + 0x84
+            seg = np.floor(np.log2(mag)).astype(np.int32) - 7
+            raw = (~(np.where(s16 < 0, 0x80, 0) | (seg << 4) | ((mag >> (seg + 3)) & 15)) & 0xFF).astype(np.uint8).tobytes()
+        else:
+            raw = np.repeat(s16[:, None], fmt.channels, axis=1).astype("<i2").tobytes()
+        out.append(raw)
+    return out
+
+
+def wire_bench(repeats: int, wire: str, n: int = 64, seconds: float = 1.5, trace_pushes: int = 0) -> dict:
+    """--stream --wire: ONE Engine.vad_stream_push_wire of n streams x 1.5-s pieces, and beside it the two ways without it - the
+    pieces converted and resampled on the host (vad.WireFormat.to_16k: scipy's resample_poly per piece, which is NOT cut-invariant:
+    every piece gets edge transients) and then Engine.vad_stream_push, and the pieces through Engine.ingest (the file kernel: one
+    launch per row, not cut-invariant either) and then Engine.vad_stream_push."""
+    from taiwan_tongues_asr_ce_amd.config import COMPUTE_F32, PRESETS
+    from taiwan_tongues_asr_ce_amd.engine import Engine
+    fmt = vad.WireFormat(**WIRES[wire])
+    e = Engine(PRESETS["micro"], COMPUTE_F32, 64)
+    e.load_vad(vad.synth_silero_weights())
+    pieces = wire_pieces(fmt, n, seconds)
+    wids = [e.vad_stream_open(wire=fmt) for _ in range(n)]
+    fids = [e.vad_stream_open() for _ in range(n)]
+    if trace_pushes:
+        for _ in range(trace_pushes):
+            e.vad_stream_push_wire(wids, pieces)
+        e.close()
+        return {"wire_pushes": trace_pushes, "rows": n}
+    rate, ch, code, pick = fmt.wire_args()
+
+    def host_path():
+        e.vad_stream_push(fids, [fmt.to_16k(p) for p in pieces])
+
+    def per_row_path():
+        e.vad_stream_push(fids, e.ingest(pieces, [rate] * n, [ch] * n, [code] * n, picks=[pick] * n))
+
+    res = {"tool": f"tools/vad_bench.py --stream --wire {wire}", "weights": "vad.synth_silero_weights()",
+           "engine": "micro geometry, float32, max_batch 64", "wire": WIRES[wire], "streams": n, "piece_seconds": seconds,
+           "piece_bytes": len(pieces[0]),
+           "push_wire": timed(lambda: e.vad_stream_push_wire(wids, pieces), repeats),
+           "host_convert_resample_then_push": timed(host_path, repeats),
+           "per_row_ingest_kernel_then_push": timed(per_row_path, repeats),
+           "vad_stream_push_of_16k_float_alone": None,
+           "note": "the two alternatives resample every piece on its own: their results carry edge transients at every cut"}
+    ready = [fmt.to_16k(p) for p in pieces]
+    res["vad_stream_push_of_16k_float_alone"] = timed(lambda: e.vad_stream_push(fids, ready), repeats)
+    for k in ("push_wire", "host_convert_resample_then_push", "per_row_ingest_kernel_then_push", "vad_stream_push_of_16k_float_alone"):
+        res[k]["ms_per_push"] = round(1e3 * res[k]["median_s"], 3)
+    e.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="large-v3")
@@ -128,9 +199,12 @@ def main():
     ap.add_argument("--hour-only", action="store_true")
     ap.add_argument("--stream", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--wire", choices=sorted(WIRES), default=None, help="with --stream: wire streams in this format")
+    ap.add_argument("--trace-pushes", type=int, default=0, help="with --stream --wire: this many pushes and nothing else (the command a kernel trace is taken of)")
     args = ap.parse_args()
     if args.stream:
-        text = json.dumps(stream_bench(args.repeats), indent=1)
+        res = wire_bench(args.repeats, args.wire, trace_pushes=args.trace_pushes) if args.wire else stream_bench(args.repeats)
+        text = json.dumps(res, indent=1)
         print(text)
         if args.out:
             with open(args.out, "w") as f:
