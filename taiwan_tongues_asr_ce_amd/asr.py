@@ -10,6 +10,9 @@ from typing import Any, Dict, Optional
 
 import numpy as np
 
+from ._lib import PCM_S16
+from .audio_io import samples_to_float
+
 logger = logging.getLogger(__name__)
 
 
@@ -24,7 +27,7 @@ class ASRInterface:
 def pcm16_bytes_to_float(buf: bytes) -> np.ndarray:
     """The streaming client hands over 16 kHz mono s16le bytes (client.py:32-35; audio_utils.py:5-29 wraps
     them into a wav that faster-whisper decodes to float32 / 32768)."""
-    return np.frombuffer(bytes(buf), dtype="<i2").astype(np.float32) / 32768.0
+    return samples_to_float(bytes(buf), PCM_S16)
 
 
 class MI355XWhisperASR(ASRInterface):

@@ -29,6 +29,7 @@ import os
 from typing import Callable, Dict, List, Optional
 
 from . import scoring
+from .audio_io import decode_audio, parse_audio_channel
 
 AUDIO_PATTERNS = ("*.wav", "*.mp3", "*.flac", "*.m4a", "*.aac")
 TRANSCRIPT_SUFFIXES = ("", "_transcript", "_original", "_reference", "_ground_truth")
@@ -54,7 +55,6 @@ def find_original_transcript(audio_file: str) -> Optional[str]:
 
 
 def _load_audio(path: str, channel: Optional[int] = None):
-    from .model import decode_audio
     return decode_audio(path, channel=channel)
 
 
@@ -179,7 +179,6 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
         if int(pipeline_depth or getattr(model, "pipeline_depth", 1)) > 1:
             log("continuous mode runs one session on one engine context: pipeline depth 1")
         pipeline_depth = 1
-    from .model import parse_audio_channel
     pick = parse_audio_channel(audio_channel)
     if pick is not None:
         if load_audio is not _load_audio:
@@ -340,7 +339,6 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def _audio_channel_arg(value: str) -> str:
-    from .model import parse_audio_channel
     try:
         parse_audio_channel(value)
     except ValueError as e:

@@ -16,8 +16,9 @@ from typing import Dict, Iterator, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import alignment, vad
+from .audio_io import decode_audio, parse_audio_channel
 from .config import HOP, SAMPLE_RATE
-from .model import LANGUAGES, Segment, TranscriptionInfo, Word, decode_audio, parse_audio_channel, select_language
+from .model import LANGUAGES, Segment, TranscriptionInfo, Word, select_language
 
 
 def clip_groups(clip_timestamps, n_samples: int, max_samples: int) -> List[Dict]:

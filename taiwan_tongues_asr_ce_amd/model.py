@@ -20,7 +20,8 @@ from typing import Dict, Iterable, Iterator, List, NamedTuple, Optional, Sequenc
 
 import numpy as np
 
-from . import alignment, ct2, synth, vad
+from . import alignment, audio_io, ct2, synth, vad
+from .audio_io import CodedAudio, decode_audio, parse_audio_channel, read_audio_coded, read_audio_raw  # noqa: F401  (public here too)
 from .config import (COMPUTE_BF16, COMPUTE_F16, COMPUTE_F32, HOP, N_FRAMES, N_SAMPLES, PRESETS, SAMPLE_RATE, SpecialTokens,
                      WhisperDims)
 from .tokenizer import load_tokenizer
@@ -100,276 +101,6 @@ def select_language(tops: Sequence[Tuple[str, float]], threshold: Optional[float
     lang = max(votes, key=lambda k: len(votes[k]))      # dicts keep insertion order: the first of equally frequent languages
     prob, i = max(votes[lang], key=lambda e: e[0])      # the first of equal probabilities
     return lang, prob, i
-
-
-def _to_mono_16k(x: np.ndarray, sr: int, sampling_rate: int) -> np.ndarray:
-    if sr != sampling_rate:
-        from math import gcd
-        from scipy.signal import resample_poly
-        g = gcd(sr, sampling_rate)
-        x = resample_poly(x, sampling_rate // g, sr // g)
-    return np.ascontiguousarray(x, dtype=np.float32)
-
-
-def _pick_channel(path: str, channel: Optional[int], n_ch: int) -> Optional[int]:
-    if channel is None:
-        return None
-    if isinstance(channel, bool) or not isinstance(channel, (int, np.integer)) or not 0 <= channel < n_ch:
-        raise ValueError(f"{path}: channel {channel!r} asked of a file with {n_ch} channel{'s' if n_ch != 1 else ''} "
-                         f"(0 ... {n_ch - 1}, or None for their mean)")
-    return int(channel)
-
-
-def parse_audio_channel(value) -> Optional[int]:
-    """The `audio_channel` option in its spellings -> None (the mean of the channels) or a channel index from 0: None / "mix" /
-    "left" / "right" / an index.  The reference's service field audioChannel maps as 0 -> "mix", 1 -> "left", 2 -> "right"."""
-    if value is None or value == "mix":
-        return None
-    if value in ("left", "right"):
-        return 0 if value == "left" else 1
-    if isinstance(value, str) and value.isdigit():
-        return int(value)
-    if isinstance(value, (int, np.integer)) and not isinstance(value, bool) and value >= 0:
-        return int(value)
-    raise ValueError(f"audio_channel {value!r}: expected None, 'mix', 'left', 'right' or a channel index from 0")
-
-
-def decode_audio(path: str, sampling_rate: int = SAMPLE_RATE, channel: Optional[int] = None) -> np.ndarray:
-    """Path -> mono float32 @16 kHz.  RIFF/WAV (integer and float PCM, G.711 A-law / mu-law, IMA ADPCM) needs nothing beside the
-    stdlib and numpy; other containers go through soundfile / librosa / PyAV when the host has one (the reference decodes with
-    librosa / PyAV: asr_core.py:156, faster-whisper decode_audio).  channel=None averages the channels; an index takes that
-    channel alone."""
-    if not path.lower().endswith((".wav", ".wave")):
-        # compressed containers (asr_core.py:118 also globs mp3/flac/m4a/aac): use whichever decoder the host has —
-        # none is installed in the build image, so these branches are unexercised here and the error below is what
-        # the folder tool records per file
-        try:
-            import soundfile as sf  # type: ignore
-            x, sr = sf.read(path, dtype="float32", always_2d=True)
-        except ImportError:
-            x = None
-        except Exception:
-            x = None  # format not handled by libsndfile: try the next decoder
-        if x is not None:
-            c = _pick_channel(path, channel, x.shape[1])
-            return _to_mono_16k(x.mean(axis=1) if c is None else x[:, c], sr, sampling_rate)
-        if channel is not None:
-            raise RuntimeError(f"{path}: picking a channel of this container needs soundfile; RIFF/WAV needs nothing")
-        try:
-            import librosa  # type: ignore
-            x, _ = librosa.load(path, sr=sampling_rate, mono=True)
-            return np.ascontiguousarray(x, dtype=np.float32)
-        except ImportError:
-            pass
-        try:
-            import av  # type: ignore
-            with av.open(path) as container:
-                resampler = av.audio.resampler.AudioResampler(format="s16", layout="mono", rate=sampling_rate)
-                chunks = [f.to_ndarray().reshape(-1) for frame in container.decode(audio=0) for f in resampler.resample(frame)]
-            return (np.concatenate(chunks).astype(np.float32) / 32768.0) if chunks else np.zeros(0, np.float32)
-        except ImportError:
-            raise RuntimeError(f"{path}: no decoder for this container (install soundfile, librosa or av); RIFF/WAV needs none")
-    n_ch, width, sr, raw, is_float = _read_wave(path)
-    if is_float:
-        x = np.frombuffer(raw, dtype="<f4" if width == 4 else "<f8").astype(np.float32)
-    elif width == 2:
-        x = np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32768.0
-    elif width == 4:
-        x = np.frombuffer(raw, dtype="<i4").astype(np.float32) / 2147483648.0
-    elif width == 3:   # 24-bit PCM, little endian: sign-extend through the top byte of an int32
-        b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
-        x = ((b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)) << 8 >> 8).astype(np.float32) / 8388608.0
-    elif width == 1:
-        x = (np.frombuffer(raw, dtype=np.uint8).astype(np.float32) - 128.0) / 128.0
-    else:
-        raise ValueError(f"unsupported sample width {width}")
-    c = _pick_channel(path, channel, n_ch)
-    if n_ch > 1:
-        x = x.reshape(-1, n_ch).mean(axis=1) if c is None else x.reshape(-1, n_ch)[:, c]
-    if sr != sampling_rate:
-        from math import gcd
-        from scipy.signal import resample_poly
-        g = gcd(sr, sampling_rate)
-        x = resample_poly(x, sampling_rate // g, sr // g).astype(np.float32)
-    return np.ascontiguousarray(x, dtype=np.float32)
-
-
-def _read_wave(path: str, coded: bool = True):
-    """(channels, bytes per sample, rate, data bytes, is_float) of a .wav file: the stdlib reader, or _read_riff_wave for what it
-    does not take.  A coded file (G.711, IMA ADPCM) comes back as the int16 it decodes to, or with coded=False as data None."""
-    import wave
-    try:
-        with wave.open(path, "rb") as w:
-            n_ch, width, sr, n = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes()
-            return n_ch, width, sr, w.readframes(n), False
-    except wave.Error:
-        # the stdlib reader only takes format tag 1; IEEE-float files (tag 3: Audacity / DAW exports) and WAVE_FORMAT_EXTENSIBLE
-        # (tag 0xFFFE: multichannel / > 16-bit writers) are plain RIFF all the same
-        return _read_riff_wave(path, coded)
-
-
-def read_audio_raw(path: str):
-    """Path -> (samples, rate, channels, format) for the device ingest (Engine.ingest), or None when this file has to go through
-    decode_audio.  RIFF/WAVE: the data bytes untouched, format = the _lib.PCM_* code of the file's samples; None for a coded file
-    (G.711, IMA ADPCM: read_audio_coded has those).  Other containers: through soundfile when it imports, at the file's own
-    rate, as a float32 array [frames][channels] (format PCM_F32)."""
-    from . import _lib
-    if path.lower().endswith((".wav", ".wave")):
-        n_ch, width, sr, raw, is_float = _read_wave(path, coded=False)
-        if raw is None:
-            return None
-        fmt = ({4: _lib.PCM_F32, 8: _lib.PCM_F64} if is_float else
-               {1: _lib.PCM_U8, 2: _lib.PCM_S16, 3: _lib.PCM_S24, 4: _lib.PCM_S32}).get(width)
-        if fmt is None:
-            return None
-        return raw[:len(raw) - len(raw) % (width * n_ch)], sr, n_ch, fmt
-    try:
-        import soundfile as sf  # type: ignore
-        x, sr = sf.read(path, dtype="float32", always_2d=True)
-    except Exception:    # no soundfile, or a container libsndfile does not take: decode_audio tries the other decoders
-        return None
-    return np.ascontiguousarray(x), int(sr), int(x.shape[1]), _lib.PCM_F32
-
-
-WAVE_ALAW, WAVE_ULAW, WAVE_IMA_ADPCM = 6, 7, 0x11      # the format tags of the coded files this reader takes
-
-_IMA_INDEX = np.array([-1, -1, -1, -1, 2, 4, 6, 8], dtype=np.int32)
-_IMA_STEP = np.array([
-    7, 8, 9, 10, 11, 12, 13, 14, 16, 17, 19, 21, 23, 25, 28, 31, 34, 37, 41, 45, 50, 55, 60, 66, 73, 80, 88, 97, 107, 118, 130, 143,
-    157, 173, 190, 209, 230, 253, 279, 307, 337, 371, 408, 449, 494, 544, 598, 658, 724, 796, 876, 963, 1060, 1166, 1282, 1411,
-    1552, 1707, 1878, 2066, 2272, 2499, 2749, 3024, 3327, 3660, 4026, 4428, 4871, 5358, 5894, 6484, 7132, 7845, 8630, 9493, 10442,
-    11487, 12635, 13899, 15289, 16818, 18500, 20350, 22385, 24623, 27086, 29794, 32767], dtype=np.int32)
-
-
-def _g711_table(mu_law: bool) -> np.ndarray:
-    """The 256 int16 values of a G.711 law, from the formulas of include/ttasr.h."""
-    b = np.arange(256, dtype=np.int32)
-    if mu_law:
-        u = ~b & 0xFF
-        v = ((((u & 15) << 3) + 0x84) << ((u >> 4) & 7)) - 0x84
-        return np.where(u & 0x80, -v, v).astype(np.int16)
-    a = b ^ 0x55
-    e, v = (a >> 4) & 7, ((a & 15) << 4) + 8
-    v = np.where(e >= 1, (v + 0x100) << np.maximum(e - 1, 0), v)
-    return np.where(a & 0x80, v, -v).astype(np.int16)
-
-
-def _ima_decode(data: bytes, n_ch: int, block_align: int, n_frames: int) -> np.ndarray:
-    """IMA ADPCM blocks -> int16 [n_frames][n_ch] (include/ttasr.h has the definition): every block and channel at once, one
-    loop over the samples of a block."""
-    per = block_align // n_ch - 4                        # data bytes of one channel in a block
-    spb, blocks = 1 + 2 * per, len(data) // block_align
-    b = np.frombuffer(data, dtype=np.uint8, count=blocks * block_align).reshape(blocks, block_align)
-    head = b[:, :4 * n_ch].reshape(blocks, n_ch, 4).astype(np.int32)
-    pred = ((head[..., 0] | (head[..., 1] << 8)) ^ 0x8000) - 0x8000
-    index = np.minimum(head[..., 2], 88)
-    body = b[:, 4 * n_ch:].reshape(blocks, per // 4, n_ch, 4).transpose(0, 2, 1, 3).reshape(blocks, n_ch, per)
-    nib = np.empty((blocks, n_ch, 2 * per), dtype=np.int32)
-    nib[..., 0::2], nib[..., 1::2] = body & 15, body >> 4          # low nibble first
-    out = np.empty((blocks, spb, n_ch), dtype=np.int16)
-    out[:, 0] = pred
-    for k in range(spb - 1):
-        n, step = nib[..., k], _IMA_STEP[index]
-        d = (step >> 3) + np.where(n & 4, step, 0) + np.where(n & 2, step >> 1, 0) + np.where(n & 1, step >> 2, 0)
-        pred = np.clip(np.where(n & 8, pred - d, pred + d), -32768, 32767)
-        index = np.clip(index + _IMA_INDEX[n & 7], 0, 88)
-        out[:, k + 1] = pred
-    return out.reshape(blocks * spb, n_ch)[:n_frames]
-
-
-class CodedAudio(NamedTuple):
-    """What Engine.ingest needs of one RIFF/WAVE file: the data bytes as the file has them, format = the _lib.PCM_* code (the six
-    sample formats, PCM_ALAW, PCM_ULAW, PCM_IMA4), block_align = bytes per frame, or per block for IMA, n_frames = the frames the
-    bytes hold (IMA: what `fact` says when that is less)."""
-    samples: bytes
-    rate: int
-    channels: int
-    format: int
-    block_align: int
-    n_frames: int
-
-
-def _parse_riff(path: str):
-    """(tag, channels, rate, bits, block_align, data bytes, `fact` sample count or None) of a RIFF/WAVE file; EXTENSIBLE resolved
-    to its sub-format."""
-    import struct
-    with open(path, "rb") as f:
-        blob = f.read()
-    if len(blob) < 12 or blob[:4] != b"RIFF" or blob[8:12] != b"WAVE":
-        raise ValueError(f"{path}: not a RIFF/WAVE file")
-    pos, fmt, data, fact = 12, None, None, None
-    while pos + 8 <= len(blob):
-        cid, size = blob[pos:pos + 4], struct.unpack("<I", blob[pos + 4:pos + 8])[0]
-        body = blob[pos + 8:pos + 8 + size]
-        if cid == b"fmt ":
-            fmt = body
-        elif cid == b"fact" and len(body) >= 4:
-            fact = struct.unpack("<I", body[:4])[0]
-        elif cid == b"data":
-            data = body            # (a streamed file's size field of 0 / 0xFFFFFFFF: the slice is whatever is there)
-            if size in (0, 0xFFFFFFFF):
-                data = blob[pos + 8:]
-            break
-        pos += 8 + size + (size & 1)
-    if fmt is None or data is None or len(fmt) < 16:
-        raise ValueError(f"{path}: RIFF/WAVE without fmt / data chunk")
-    tag, n_ch, sr, _, block_align, bits = struct.unpack("<HHIIHH", fmt[:16])
-    if tag == 0xFFFE and len(fmt) >= 26:
-        tag = struct.unpack("<H", fmt[24:26])[0]          # first two bytes of the sub-format GUID
-    return tag, n_ch, sr, bits, block_align, data, fact
-
-
-def _coded_riff(path: str, tag: int, n_ch: int, sr: int, bits: int, block_align: int, data: bytes, fact) -> CodedAudio:
-    from . import _lib
-    if n_ch < 1:
-        raise ValueError(f"{path}: {n_ch} channels")
-    if tag in (WAVE_ALAW, WAVE_ULAW):
-        if bits != 8:
-            raise ValueError(f"{path}: G.711 with {bits} bits per sample")
-        n = len(data) // n_ch
-        return CodedAudio(data[:n * n_ch], sr, n_ch, _lib.PCM_ALAW if tag == WAVE_ALAW else _lib.PCM_ULAW, n_ch, n)
-    if bits != 4 or block_align < 8 * n_ch or block_align % (4 * n_ch):
-        raise ValueError(f"{path}: IMA ADPCM with {bits} bits per sample in blocks of {block_align} bytes for {n_ch} channels")
-    held = len(data) // block_align * (1 + 2 * (block_align // n_ch - 4))
-    return CodedAudio(data, sr, n_ch, _lib.PCM_IMA4, block_align, fact if fact is not None and fact <= held else held)
-
-
-def read_audio_coded(path: str) -> Optional[CodedAudio]:
-    """A RIFF/WAVE path -> CodedAudio for the device ingest, PCM or coded; None for another container (read_audio_raw has
-    those)."""
-    from . import _lib
-    if not path.lower().endswith((".wav", ".wave")):
-        return None
-    n_ch, width, sr, raw, is_float = _read_wave(path, coded=False)
-    if raw is None:
-        return _coded_riff(path, *_parse_riff(path))
-    fmt = ({4: _lib.PCM_F32, 8: _lib.PCM_F64} if is_float else
-           {1: _lib.PCM_U8, 2: _lib.PCM_S16, 3: _lib.PCM_S24, 4: _lib.PCM_S32}).get(width)
-    if fmt is None:
-        return None
-    n = len(raw) // (width * n_ch)
-    return CodedAudio(raw[:n * width * n_ch], sr, n_ch, fmt, width * n_ch, n)
-
-
-def _read_riff_wave(path: str, coded: bool = True):
-    """(channels, bytes per sample, rate, data bytes, is_float) of a RIFF/WAVE file whose `fmt ` chunk says PCM (1), IEEE float
-    (3), G.711 A-law (6) or mu-law (7), IMA ADPCM (0x11) or EXTENSIBLE (0xFFFE) with one of them as its sub-format.  The coded
-    ones are decoded here: their data bytes are the int16 they stand for (coded=False: None instead)."""
-    tag, n_ch, sr, bits, block_align, data, fact = _parse_riff(path)
-    if tag in (WAVE_ALAW, WAVE_ULAW, WAVE_IMA_ADPCM):
-        c = _coded_riff(path, tag, n_ch, sr, bits, block_align, data, fact)
-        if not coded:
-            return n_ch, 2, sr, None, False
-        if tag == WAVE_IMA_ADPCM:
-            x = _ima_decode(c.samples, n_ch, block_align, c.n_frames)
-        else:
-            x = _g711_table(tag == WAVE_ULAW)[np.frombuffer(c.samples, dtype=np.uint8)]
-        return n_ch, 2, sr, np.ascontiguousarray(x).astype("<i2").tobytes(), False
-    if tag not in (1, 3) or n_ch < 1 or bits % 8 or (tag == 3 and bits not in (32, 64)):
-        raise ValueError(f"{path}: unsupported WAVE format tag {tag}, {bits} bits")
-    width = bits // 8
-    data = data[:len(data) - len(data) % (width * n_ch)]
-    return n_ch, width, sr, data, tag == 3
 
 
 def _read_hf_dir(path: str) -> Tuple[WhisperDims, Iterable[Tuple[str, np.ndarray]]]:
@@ -560,11 +291,12 @@ class WhisperModel:
 
     # -- file ingest on the device --------------------------------------------------------------------
     def decode_audio_many(self, paths_or_arrays: Sequence[Union[str, np.ndarray]], audio_channel=None) -> List[np.ndarray]:
-        """Every path -> mono float32 @16 kHz with ONE device call for all the files the device takes (read_audio_coded /
-        read_audio_raw + Engine.ingest on the calling thread's engine context: conversion or G.711 / IMA ADPCM decoding,
-        downmix and the polyphase resampler run on the device over the whole batch); a file it does not take - a container
-        without a reader, a rate outside the accepted ratios, more than 8 channels - goes through decode_audio, as every path
-        does on an engine without `ingest`.  Arrays pass through.
+        """Every path -> mono float32 @16 kHz with ONE device call for all the files the device takes (read_audio_coded +
+        Engine.ingest on the calling thread's engine context: conversion or G.711 / IMA ADPCM decoding, downmix and the
+        polyphase resampler run on the device over the whole batch).  Every path is read once: a file the device does not take
+        - a rate outside the accepted ratios, more than 8 channels, or any file on an engine without `ingest` - is decoded on
+        the host from what was read, as decode_audio does it; a container read_audio_coded has no reader for goes through
+        decode_audio.  Arrays pass through.
         audio_channel (None / "mix", "left", "right" or an index from 0: parse_audio_channel) picks one channel of every path
         instead of their mean; with an array among the inputs it is refused: an array is already mono.
         The device resampler is decode_audio's (scipy.signal.resample_poly) accumulated in float32 instead of float64."""
@@ -579,18 +311,15 @@ class WhisperModel:
                     raise ValueError("audio_channel picks a channel of a file: an array input is already mono")
                 out[i] = np.asarray(a)
                 continue
-            raw = None
-            if callable(getattr(eng, "ingest", None)):
-                raw = read_audio_coded(a)
-                if raw is None:
-                    r = read_audio_raw(a)
-                    if r is not None:      # another container through soundfile: float32 [frames][channels]
-                        raw = CodedAudio(r[0], r[1], r[2], r[3], 4 * r[2], len(r[0]))
-            if raw is not None and 1 <= raw.channels <= 8 and eng.ingest_accepts(raw.rate):
-                _pick_channel(a, pick, raw.channels)
-                jobs.append((i, raw))
-            else:
+            raw = read_audio_coded(a)
+            if raw is None:
                 out[i] = decode_audio(a, channel=pick)
+                continue
+            c = audio_io._pick_channel(a, pick, raw.channels)
+            if callable(getattr(eng, "ingest", None)) and raw.channels <= 8 and eng.ingest_accepts(raw.rate):
+                jobs.append((i, raw))
+            else:      # the host path over what was read
+                out[i] = audio_io.resample(audio_io.decode_coded(raw, c), raw.rate)
         if jobs:
             args = [[getattr(r, k) for _, r in jobs] for k in ("samples", "rate", "channels", "format")]
             if pick is None and all(r.format < _lib.PCM_ALAW for _, r in jobs):

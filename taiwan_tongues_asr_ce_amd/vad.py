@@ -21,6 +21,8 @@ from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
+from . import _lib, audio_io
+
 SAMPLING_RATE = 16000
 WINDOW = 512          # samples per probability frame (32 ms), Silero's frame at 16 kHz
 
@@ -36,16 +38,18 @@ class VadOptions:
     speech_pad_ms: int = 400
 
 
-# encoding name -> (TTASR_PCM_* code of include/ttasr.h, bytes per sample): the sample formats model.read_audio_raw reports and
+# encoding name -> (TTASR_PCM_* code of include/ttasr.h, bytes per sample): the sample formats audio_io.read_audio_raw reports and
 # the two G.711 laws.  IMA ADPCM is a block codec, not a stream.
-WIRE_ENCODINGS = {"u8": (0, 1), "s16": (1, 2), "s24": (2, 3), "s32": (3, 4), "f32": (4, 4), "f64": (5, 8), "alaw": (16, 1), "ulaw": (17, 1)}
+WIRE_ENCODINGS = {name: (code, _lib.CODED_BYTES[code] if code in _lib.CODED_BYTES else _lib.PCM_BYTES[code]) for name, code in (
+    ("u8", _lib.PCM_U8), ("s16", _lib.PCM_S16), ("s24", _lib.PCM_S24), ("s32", _lib.PCM_S32), ("f32", _lib.PCM_F32),
+    ("f64", _lib.PCM_F64), ("alaw", _lib.PCM_ALAW), ("ulaw", _lib.PCM_ULAW))}
 
 
 @dataclass(frozen=True)
 class WireFormat:
     """What a live connection sends (the streaming server's `rate` / `channel` query parameters, the config message's sampleRate /
     channels): interleaved little-endian samples of `encoding` (WIRE_ENCODINGS) at `rate` Hz, `channels` (1 ... 8) per frame;
-    audio_channel picks one of them in model.parse_audio_channel's spellings (None / "mix" = their mean, "left", "right", an
+    audio_channel picks one of them in audio_io.parse_audio_channel's spellings (None / "mix" = their mean, "left", "right", an
     index)."""
     rate: int
     channels: int = 1
@@ -72,8 +76,7 @@ class WireFormat:
 
     @property
     def pick(self) -> Optional[int]:
-        from .model import parse_audio_channel
-        return parse_audio_channel(self.audio_channel)
+        return audio_io.parse_audio_channel(self.audio_channel)
 
     def wire_args(self):
         """(rate, channels, format, pick) of ttasr_vad_stream_open_wire."""
@@ -81,33 +84,14 @@ class WireFormat:
 
     def to_mono(self, raw) -> np.ndarray:
         """The whole frames of `raw` on the host -> float32 mono at `rate`: decode_audio's conversion (G.711 through its int16)."""
-        from .model import _g711_table
         raw = bytes(raw)
-        raw = raw[:len(raw) - len(raw) % self.frame_bytes]
-        e = self.encoding
-        if e in ("alaw", "ulaw"):
-            x = _g711_table(e == "ulaw")[np.frombuffer(raw, dtype=np.uint8)].astype(np.float32) / 32768.0
-        elif e == "u8":
-            x = (np.frombuffer(raw, dtype=np.uint8).astype(np.float32) - 128.0) / 128.0
-        elif e == "s16":
-            x = np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32768.0
-        elif e == "s24":
-            b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
-            x = ((b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)) << 8 >> 8).astype(np.float32) / 8388608.0
-        elif e == "s32":
-            x = np.frombuffer(raw, dtype="<i4").astype(np.float32) / 2147483648.0
-        else:
-            x = np.frombuffer(raw, dtype="<f4" if e == "f32" else "<f8").astype(np.float32)
-        if self.channels > 1:
-            x = x.reshape(-1, self.channels)
-            x = x.mean(axis=1) if self.pick is None else x[:, self.pick]
-        return np.ascontiguousarray(x, dtype=np.float32)
+        x = audio_io.samples_to_float(raw[:len(raw) - len(raw) % self.frame_bytes], self.format, int(self.channels))
+        return np.ascontiguousarray(audio_io.downmix(x, self.pick), dtype=np.float32)
 
     def to_16k(self, raw) -> np.ndarray:
-        """`to_mono`, then the package's host resampler (model._to_mono_16k: scipy's resample_poly over the WHOLE buffer - run
+        """`to_mono`, then the package's host resampler (audio_io.resample: scipy's resample_poly over the WHOLE buffer - run
         piece by piece it is not cut-invariant, which is what wire streams are for)."""
-        from .model import _to_mono_16k
-        return _to_mono_16k(self.to_mono(raw), int(self.rate), SAMPLING_RATE)
+        return audio_io.resample(self.to_mono(raw), int(self.rate), SAMPLING_RATE)
 
     @staticmethod
     def of_client(client) -> "WireFormat":

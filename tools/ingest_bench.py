@@ -1,4 +1,4 @@
-"""File ingest: the host path of model.decode_audio against one Engine.ingest call (kernels_ingest.hip), on 32 in-memory
+"""File ingest: the host path of audio_io.decode_audio against one Engine.ingest call (kernels_ingest.hip), on 32 in-memory
 recordings of 60 s at 44.1 and 48 kHz, 2-channel int16 and mono int16.
 
   host     decode_audio's conversion path on the sample bytes, one thread, file by file: int16 -> float32 / 32768, the channel
@@ -14,7 +14,7 @@ Nothing is asserted.  One JSON object on stdout and in --out.
     python tools/ingest_bench.py [--files 32] [--seconds 60] [--repeats 5] [--out profiles/ingest_bench.json]
 
 --codec ulaw | alaw | ima4 (may be given several times) measures telephony files instead: 8 kHz, mono and 2-channel, G.711 bytes or
-IMA ADPCM blocks of 256 bytes per channel (505 samples), random bytes.  The host path is then model.decode_audio's from the data
+IMA ADPCM blocks of 256 bytes per channel (505 samples), random bytes.  The host path is then audio_io.decode_audio's from the data
 bytes on - the G.711 table or the numpy IMA decoder, / 32768, the channel mean, resample_poly - and the device path the same one
 Engine.ingest call (ttasr_ingest_wave).  The result goes to profiles/ingest_bench_codecs.json.
 
@@ -28,7 +28,6 @@ import os
 import statistics
 import sys
 import time
-from math import gcd
 
 import numpy as np
 
@@ -39,30 +38,17 @@ HEADLINE = 2150.0   # audio-s/s of the engine's greedy headline workload (README
 
 
 def host_ingest(raw: np.ndarray, rate: int, channels: int) -> np.ndarray:
-    """model.decode_audio from the sample bytes on, for 16-bit PCM."""
-    from scipy.signal import resample_poly
-    x = np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32768.0
-    if channels > 1:
-        x = x.reshape(-1, channels).mean(axis=1)
-    g = gcd(rate, 16000)
-    x = resample_poly(x, 16000 // g, rate // g).astype(np.float32)
-    return np.ascontiguousarray(x, dtype=np.float32)
+    """audio_io.decode_audio from the sample bytes on, for 16-bit PCM."""
+    from taiwan_tongues_asr_ce_amd import _lib, audio_io
+    return audio_io.resample(audio_io.downmix(audio_io.samples_to_float(raw, _lib.PCM_S16, channels), None), rate)
 
 
 def host_ingest_coded(raw: bytes, rate: int, channels: int, codec: str, block_align: int) -> np.ndarray:
-    """model.decode_audio from the data bytes on, for a coded file."""
-    from scipy.signal import resample_poly
-    from taiwan_tongues_asr_ce_amd import model
-    if codec == "ima4":
-        x = model._ima_decode(raw, channels, block_align, len(raw) // block_align * (1 + 2 * (block_align // channels - 4)))
-    else:
-        x = model._g711_table(codec == "ulaw")[np.frombuffer(raw, dtype=np.uint8)]
-    x = np.frombuffer(np.ascontiguousarray(x).astype("<i2").tobytes(), dtype="<i2").astype(np.float32) / 32768.0
-    if channels > 1:
-        x = x.reshape(-1, channels).mean(axis=1)
-    g = gcd(rate, 16000)
-    x = resample_poly(x, 16000 // g, rate // g).astype(np.float32)
-    return np.ascontiguousarray(x, dtype=np.float32)
+    """audio_io.decode_audio from the data bytes on, for a coded file."""
+    from taiwan_tongues_asr_ce_amd import _lib, audio_io
+    code = {"ulaw": _lib.PCM_ULAW, "alaw": _lib.PCM_ALAW, "ima4": _lib.PCM_IMA4}[codec]
+    held = len(raw) // block_align * (1 + 2 * (block_align // channels - 4)) if codec == "ima4" else len(raw) // channels
+    return audio_io.resample(audio_io.decode_coded(audio_io.CodedAudio(raw, rate, channels, code, block_align, held)), rate)
 
 
 def main():
