@@ -183,6 +183,46 @@ TTASR_API int ttasr_cross_attn_probe(ttasr_ctx* ctx, int32_t layer, int32_t n_ro
 TTASR_API int ttasr_align_attn_probe(ttasr_ctx* ctx, int32_t layer, int32_t n_seq, const int32_t* lens_host, const int32_t* slots_host,
                                      const float* q_host, const int32_t* head_pair_host, int32_t n_pairs, float* out_host,
                                      float* out_maps_host);
+/* Known-answer hooks for the decoder SELF-attention kernels over the paged KV pool (tests/test_gpu_self_attn_kernels.py; DESIGN.md
+ * section 4.28).  The pool of one layer is [page][2 (K, V)][n_heads][16 positions][64] with max_batch x pages_per_seq pages,
+ * pages_per_seq = ceil(n_text_ctx / 16); page images below have that layout, [n_pages][2][n_heads][16][64] f32.  All four calls are
+ * refused in an open session.  They overwrite search state: after any of them the decode state (KV pool, positions, finished
+ * flags) is UNDEFINED until ttasr_decode_reset, a generate call or a session start; the device page table is the identity again
+ * when ttasr_self_attn_probe returns, captured step graphs are not touched.
+ *
+ * ttasr_self_kv_fill: every element of `layer` (-1: of every layer) becomes `pattern` - its 32 bits on an f32 engine, its low 16
+ * bits on a 16-bit engine (a NaN pattern makes a read outside a row's history visible).
+ * ttasr_self_kv_set: positions [0, n) (1 <= n <= 16) of the listed pages of `layer`, K and V of every head, from the page images
+ * kv_host (cast to the engine type; positions >= n of the images are ignored and their pool elements keep their bits).
+ * ttasr_self_kv_get: the listed pages (pages_host NULL and n_pages = all pages: the whole layer in pool order) as f32, exactly. */
+TTASR_API int ttasr_self_kv_fill(ttasr_ctx* ctx, int32_t layer, uint32_t pattern);
+TTASR_API int ttasr_self_kv_set(ttasr_ctx* ctx, int32_t layer, const int32_t* pages_host, int32_t n_pages, int32_t n, const float* kv_host);
+TTASR_API int ttasr_self_kv_get(ttasr_ctx* ctx, int32_t layer, const int32_t* pages_host, int32_t n_pages, float* out_host);
+/* ONE launch of a named form of the self-attention on caller-supplied rows, through the launcher the engine itself calls:
+ *   TTASR_SELF_STEP     launch_self_attn_decode: n_rows rows at the one position geom_host[0] (n_geom = 1)
+ *   TTASR_SELF_ROWS     launch_self_attn_decode_rows: row r at position geom_host[r] (n_geom = n_rows)
+ *   TTASR_SELF_PREFILL  launch_self_attn_prefill (append launch + attend launch): geom_host = {n_seq, npos}, rows [sequence][position]
+ *   TTASR_SELF_PACKED   launch_prefill_self_attn over the tables prefill_build_tables makes: geom_host = the n_geom sequences' lengths,
+ *                       aux_host = their page lists one after the other (ceil(length / 16) pages each), n_rows = the lengths' sum
+ *   TTASR_SELF_COPY     launch_copy_pages over every layer: aux_host = n_aux / 2 (source, destination) page pairs, at most max_batch
+ *                       pairs; no pairs launch nothing; qkv_host, out_host, layer's rows and geom are not used
+ * qkv_host: f32 [n_rows][3 d_model] (q | k | v), cast to the engine type and used as given (the 1/8 lives in the weights); step and
+ * rows forms on a 16-bit engine also take n_slab = 1..4 f32 partial tiles [n_slab][n_rows][3 d_model], completed by the kernel with a
+ * zero bias the way the step completes the K-split qkv GEMM.  Step and rows forms: the rows are rows [row0, row0 + n_rows) of the
+ * batch (row0 offsets qkv, out and the finished flags, never the pages: row r uses the pages of batch row row0 + r); done_host:
+ * optional int32 [n_rows], nonzero = finished.  Step, rows and prefill forms: aux_host = the device page table
+ * [max_batch][pages_per_seq] for the launch (n_aux = 0: the identity), identity_pages != 0 = the instantiation that computes page ids
+ * instead of loading them.  At most 512 rows in the two prefill forms, positions below n_text_ctx, page ids inside the pool.
+ * out_host: f32 [n_rows][d_model]; the device output is zero-filled before the launch.  sig_buf (optional, sig_len bytes) receives
+ * the instantiation(s) that ran, "name<template arguments> grid <threads>" joined by " + "; "" when nothing was launched. */
+#define TTASR_SELF_STEP 0
+#define TTASR_SELF_ROWS 1
+#define TTASR_SELF_PREFILL 2
+#define TTASR_SELF_PACKED 3
+#define TTASR_SELF_COPY 4
+TTASR_API int ttasr_self_attn_probe(ttasr_ctx* ctx, int32_t form, int32_t layer, int32_t n_rows, const float* qkv_host, int32_t n_slab,
+                                    const int32_t* geom_host, int32_t n_geom, const int32_t* aux_host, int32_t n_aux, int32_t identity_pages,
+                                    int32_t row0, const int32_t* done_host, float* out_host, char* sig_buf, int32_t sig_len);
 
 /* Short-window option (opt-in, a behavioural change versus Whisper's fixed 30-s training window, the
  * same trade whisper.cpp's `audio_ctx` makes): subsequent log_mel / encode / generate calls use only the first n_ctx

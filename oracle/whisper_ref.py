@@ -744,3 +744,49 @@ def cross_attn_ref(q: np.ndarray, K: np.ndarray, V: np.ndarray) -> Tuple[np.ndar
     p = np.exp(s - s.max(axis=-1, keepdims=True))
     p /= p.sum(axis=-1, keepdims=True)
     return np.einsum("...t,...tc->...c", p, V), s
+
+
+# ---- the decoder self-attention over the paged KV pool (csrc/kernels_attn.hip self_attn_decode_kernel, kernels_prefill.hip) ---
+# References for tests/test_gpu_self_attn_kernels.py, which reaches the kernels through the known-answer hooks ttasr_self_kv_* /
+# ttasr_self_attn_probe.  A pool layer is [page][2 (K, V)][H][16][64]; a row's history is gathered
+# through its page list.  The operands are as the kernel reads them: the caller has rounded them to the engine type.
+SELF_PAGE = 16
+
+
+def self_history(pool: np.ndarray, pages: Sequence[int], n: int) -> Tuple[np.ndarray, np.ndarray]:
+    """positions 0 .. n - 1 of a row from its page list: (K [H][n][64], V [H][n][64])"""
+    t = np.arange(n)
+    pg = np.asarray(pages, dtype=np.int64)[t // SELF_PAGE]
+    blk = pool[pg, :, :, t % SELF_PAGE]                      # [n][2][H][64]
+    blk = np.asarray(blk, dtype=np.float64)
+    return blk[:, 0].transpose(1, 0, 2), blk[:, 1].transpose(1, 0, 2)
+
+
+def self_attn_ref(q: np.ndarray, k: np.ndarray, v: np.ndarray, pool: np.ndarray, tables: Sequence[Sequence[int]],
+                  pos: Sequence[int]) -> List[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:
+    """float64 softmax(q . K^T) . V per (row, head) over the row's logical history plus the new key: q, k, v [n][H][64] (this step's
+    rows), pool [pages][2][H][16][64], tables[r] = row r's page list, pos[r] = its position (= cached keys).  No 1 / 8: it lives in
+    the weights.  Returns per row (out [H][64], scores [H][pos + 1], K [H][pos + 1][64], V) with the new key last."""
+    res = []
+    for r in range(len(pos)):
+        K, V = self_history(pool, tables[r], int(pos[r]))
+        K = np.concatenate([K, np.asarray(k[r], np.float64)[:, None]], axis=1)
+        V = np.concatenate([V, np.asarray(v[r], np.float64)[:, None]], axis=1)
+        out, s = cross_attn_ref(np.asarray(q[r], np.float64), K, V)
+        res.append((out, s, K, V))
+    return res
+
+
+def self_attn_causal_ref(q: np.ndarray, k: np.ndarray, v: np.ndarray, lens: Sequence[int]
+                         ) -> List[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:
+    """The two prefill forms: rows are packed sequence after sequence (lens); row (s, t) attends to keys 0 .. t of its own
+    sequence, all of them this pass's rows.  Same returns as self_attn_ref, per packed row."""
+    res, r0 = [], 0
+    for n in lens:
+        K = np.asarray(k[r0:r0 + n], np.float64).transpose(1, 0, 2)
+        V = np.asarray(v[r0:r0 + n], np.float64).transpose(1, 0, 2)
+        for t in range(n):
+            out, s = cross_attn_ref(np.asarray(q[r0 + t], np.float64), K[:, :t + 1], V[:, :t + 1])
+            res.append((out, s, K[:, :t + 1], V[:, :t + 1]))
+        r0 += n
+    return res

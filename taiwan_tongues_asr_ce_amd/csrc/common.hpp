@@ -496,6 +496,10 @@ int cross_attn_splits(int B, int H, int Tk);   // frame slices of a cross-attent
 template <typename T> void launch_cross_attn_merge(const float* ws, T* out, int B, int H, int S, const int32_t* done, hipStream_t s);
 extern thread_local bool g_kernel_sig_on;
 extern thread_local char g_kernel_sig[192];
+// the same for the launchers of the decoder self-attention (ttasr_self_attn_probe): a buffer of its own, nullptr = off, so that
+// what ttasr_bench_kernel_signature reports stays what it was
+constexpr int kSelfAttnSigLen = 256;
+extern thread_local char* g_self_attn_sig;
 template <typename T> inline const char* sig_type() { return sizeof(T) == 4 ? "float" : "unsigned short"; }
 template <> inline const char* sig_type<struct f16_t>() { return "f16_t"; }
 

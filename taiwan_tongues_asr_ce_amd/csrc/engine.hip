@@ -519,6 +519,220 @@ int ttasr_align_attn_probe(ttasr_ctx* c, int32_t layer, int32_t n_seq, const int
   });
 }
 
+// ---- known-answer hooks of the decoder self-attention over the paged KV pool ----
+static constexpr int kSelfProbeRows = 512;   // rows of the two prefill forms
+static int self_probe_workspace(ttasr_ctx* c) {
+  if (c->sprobe_f32) return 0;
+  const int64_t n = std::max<int64_t>(c->pool_layer_elems, (int64_t)kSelfProbeRows * 3 * c->d);
+  const int pps = c->pages_per_seq;
+  TRY(dalloc(c, &c->sprobe_t, (size_t)n * c->esz));
+  TRY(dalloc(c, &c->sprobe_out, (size_t)kSelfProbeRows * c->d * c->esz));
+  TRY(dalloc(c, &c->sprobe_pos, (size_t)c->maxB * 4));
+  TRY(dalloc(c, &c->sprobe_zero, (size_t)3 * c->d * 4));
+  TRY(dalloc(c, &c->sprobe_tab, prefill_table_words(kSelfProbeRows, kSelfProbeRows, 2 * kSelfProbeRows, pps) * 4));
+  if (!c->probe_done) TRY(dalloc(c, &c->probe_done, (size_t)c->maxB * 4));
+  TRY(dalloc(c, &c->sprobe_f32, (size_t)n * 4));
+  c->sprobe_elems = n;
+  return 0;
+}
+static int self_probe_pages_ok(ttasr_ctx* c, const int32_t* pages, int64_t n) {
+  const int total = c->maxB * c->pages_per_seq;
+  for (int64_t i = 0; i < n; ++i)
+    if (pages[i] < 0 || pages[i] >= total) return fail(c, TTASR_E_INVALID, "page %d (entry %lld) outside the pool's %d pages", pages[i], (long long)i, total);
+  return 0;
+}
+
+int ttasr_self_kv_fill(ttasr_ctx* c, int32_t layer, uint32_t pattern) {
+  return guarded(c, [&]() -> int {
+  TRY(check_ready(c, 1));   // refused in an open session
+  if (layer < -1 || layer >= c->cfg.dec_layers) return fail(c, TTASR_E_INVALID, "layer %d", layer);
+  const int64_t n = layer < 0 ? c->pool_layer_elems * c->cfg.dec_layers : c->pool_layer_elems;
+  char* dst = (char*)c->pool + (size_t)std::max(layer, 0) * c->pool_layer_elems * c->esz;
+  if (c->lowp) HIPCHK(c, hipMemsetD16Async((hipDeviceptr_t)dst, (unsigned short)(pattern & 0xffffu), (size_t)n, c->stream));
+  else HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)dst, (int)pattern, (size_t)n, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return TTASR_OK;
+  });
+}
+
+int ttasr_self_kv_set(ttasr_ctx* c, int32_t layer, const int32_t* pages, int32_t n_pages, int32_t n, const float* kv) {
+  return guarded(c, [&]() -> int {
+  TRY(check_ready(c, 1));
+  if (layer < 0 || layer >= c->cfg.dec_layers || !pages || !kv || n_pages < 1 || n_pages > c->maxB * c->pages_per_seq || n < 1 || n > 16)
+    return fail(c, TTASR_E_INVALID, "bad arguments");
+  TRY(self_probe_pages_ok(c, pages, n_pages));
+  TRY(self_probe_workspace(c));
+  hipStream_t s = c->stream;
+  const size_t e = c->esz, page_elems = (size_t)2 * c->H * 16 * 64, cnt = (size_t)n_pages * page_elems;
+  const char* src;
+  if (c->lowp) {
+    HIPCHK(c, hipMemcpyAsync(c->sprobe_f32, kv, cnt * 4, hipMemcpyHostToDevice, s));
+    TT_DISPATCH(c, launch_cast<T>(c->sprobe_f32, (T*)c->sprobe_t, (int64_t)cnt, s));
+    src = (const char*)c->sprobe_t;
+  } else {
+    HIPCHK(c, hipMemcpyAsync(c->sprobe_f32, kv, cnt * 4, hipMemcpyHostToDevice, s));
+    src = (const char*)c->sprobe_f32;
+  }
+  char* layer_base = (char*)c->pool + (size_t)layer * c->pool_layer_elems * e;
+  // per page: 2 H blocks of [16][64]; the first n positions of every block
+  for (int i = 0; i < n_pages; ++i)
+    HIPCHK(c, hipMemcpy2DAsync(layer_base + (size_t)pages[i] * page_elems * e, 1024 * e, src + (size_t)i * page_elems * e, 1024 * e,
+                               (size_t)n * 64 * e, (size_t)2 * c->H, hipMemcpyDeviceToDevice, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+  return TTASR_OK;
+  });
+}
+
+int ttasr_self_kv_get(ttasr_ctx* c, int32_t layer, const int32_t* pages, int32_t n_pages, float* out) {
+  return guarded(c, [&]() -> int {
+  TRY(check_ready(c, 1));
+  const int total = c->maxB * c->pages_per_seq;
+  if (layer < 0 || layer >= c->cfg.dec_layers || !out || n_pages < 1 || n_pages > total || (!pages && n_pages != total))
+    return fail(c, TTASR_E_INVALID, "bad arguments");
+  if (pages) TRY(self_probe_pages_ok(c, pages, n_pages));
+  TRY(self_probe_workspace(c));
+  hipStream_t s = c->stream;
+  const size_t e = c->esz, page_elems = (size_t)2 * c->H * 16 * 64, cnt = (size_t)n_pages * page_elems;
+  const char* layer_base = (const char*)c->pool + (size_t)layer * c->pool_layer_elems * e;
+  const char* src = layer_base;   // pages == NULL: the whole layer in pool order
+  if (pages) {
+    char* stage = c->lowp ? (char*)c->sprobe_t : (char*)c->sprobe_f32;
+    for (int i = 0; i < n_pages; ++i)
+      HIPCHK(c, hipMemcpyAsync(stage + (size_t)i * page_elems * e, layer_base + (size_t)pages[i] * page_elems * e, page_elems * e, hipMemcpyDeviceToDevice, s));
+    src = stage;
+  }
+  if (c->lowp) { TT_DISPATCH(c, launch_uncast<T>((const T*)src, c->sprobe_f32, (int64_t)cnt, s));
+                 HIPCHK(c, hipMemcpyAsync(out, c->sprobe_f32, cnt * 4, hipMemcpyDeviceToHost, s)); }
+  else HIPCHK(c, hipMemcpyAsync(out, src, cnt * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+  return TTASR_OK;
+  });
+}
+
+int ttasr_self_attn_probe(ttasr_ctx* c, int32_t form, int32_t layer, int32_t n_rows, const float* qkv, int32_t n_slab, const int32_t* geom,
+                          int32_t n_geom, const int32_t* aux, int32_t n_aux, int32_t identity_pages, int32_t row0, const int32_t* done,
+                          float* out, char* sig_buf, int32_t sig_len) {
+  return guarded(c, [&]() -> int {
+  TRY(check_ready(c, 1));   // refused in an open session
+  const int d = c->d, pps = c->pages_per_seq, total_pages = c->maxB * pps, ctx = c->cfg.n_text_ctx;
+  if (form < TTASR_SELF_STEP || form > TTASR_SELF_COPY || layer < 0 || layer >= c->cfg.dec_layers || (sig_buf && sig_len < 1) || n_geom < 0 ||
+      n_aux < 0 || (n_geom > 0 && !geom) || (n_aux > 0 && !aux))
+    return fail(c, TTASR_E_INVALID, "bad arguments");
+  TRY(self_probe_workspace(c));
+  hipStream_t s = c->stream;
+  char sig[kSelfAttnSigLen] = "";
+  struct SigScope { explicit SigScope(char* b) { g_self_attn_sig = b; } ~SigScope() { g_self_attn_sig = nullptr; } };
+  if (form == TTASR_SELF_COPY) {   // aux = (source, destination) pairs, every layer
+    if (n_aux % 2 != 0 || n_aux / 2 > c->maxB) return fail(c, TTASR_E_INVALID, "%d pair entries (at most max_batch = %d pairs)", n_aux, c->maxB);
+    TRY(self_probe_pages_ok(c, aux, n_aux));
+    if (n_aux > 0) HIPCHK(c, hipMemcpyAsync(c->pairs_dev, aux, (size_t)n_aux * 4, hipMemcpyHostToDevice, s));
+    { SigScope on(sig);
+      TT_DISPATCH(c, launch_copy_pages<T>((T*)c->pool, c->pairs_dev, n_aux / 2, c->cfg.dec_layers, c->H, c->pool_layer_elems, s)); }
+    if (sig_buf) snprintf(sig_buf, (size_t)sig_len, "%s", sig);
+    HIPCHK(c, hipStreamSynchronize(s));
+    HIPCHK(c, hipGetLastError());
+    return TTASR_OK;
+  }
+  if (!qkv || !out || n_rows < 1 || n_slab < 0 || n_slab > 4) return fail(c, TTASR_E_INVALID, "bad arguments");
+  if (n_slab > 0 && !c->lowp) return fail(c, TTASR_E_INVALID, "n_slab > 0 needs a 16-bit engine (only its step splits the qkv GEMM into partial tiles)");
+  const bool decode = form == TTASR_SELF_STEP || form == TTASR_SELF_ROWS;
+  if (!decode && (n_slab > 0 || done || row0 != 0)) return fail(c, TTASR_E_INVALID, "n_slab, done and row0 belong to the step and rows forms");
+  const size_t e = c->esz;
+  const void* out_dev = nullptr;
+  auto upload_rows = [&](void* dst_t) -> int {   // f32 [n_rows][3 d] from the host, cast to the engine type
+    if (c->lowp) {
+      HIPCHK(c, hipMemcpyAsync(c->sprobe_f32, qkv, (size_t)n_rows * 3 * d * 4, hipMemcpyHostToDevice, s));
+      TT_DISPATCH(c, launch_cast<T>(c->sprobe_f32, (T*)dst_t, (int64_t)n_rows * 3 * d, s));
+    } else {
+      HIPCHK(c, hipMemcpyAsync(dst_t, qkv, (size_t)n_rows * 3 * d * 4, hipMemcpyHostToDevice, s));
+    }
+    return 0;
+  };
+  // the device page table [max_batch][pages_per_seq] of the step, rows and prefill forms: aux, or the identity
+  const bool own_table = form != TTASR_SELF_PACKED && n_aux > 0;
+  std::vector<int32_t> ident((size_t)total_pages);
+  for (int i = 0; i < total_pages; ++i) ident[i] = i;
+  if (own_table) {
+    if (n_aux != total_pages) return fail(c, TTASR_E_INVALID, "page table of %d entries, [max_batch][pages_per_seq] = %d expected", n_aux, total_pages);
+    TRY(self_probe_pages_ok(c, aux, n_aux));
+  }
+  if (decode) {
+    if (row0 < 0 || row0 + n_rows > c->maxB) return fail(c, TTASR_E_INVALID, "rows [%d, %d) outside max_batch = %d", row0, row0 + n_rows, c->maxB);
+    if (n_geom != (form == TTASR_SELF_STEP ? 1 : n_rows)) return fail(c, TTASR_E_INVALID, "%d positions given", n_geom);
+    for (int i = 0; i < n_geom; ++i)
+      if (geom[i] < 0 || geom[i] >= ctx) return fail(c, TTASR_E_INVALID, "position %d outside the text context (%d)", geom[i], ctx);
+    void* dqkv = (char*)c->dqkv + (size_t)row0 * 3 * d * e;
+    void* datt = (char*)c->datt + (size_t)row0 * d * e;
+    SlabIn sq;
+    if (n_slab > 0) {   // the qkv GEMM's K-split layout of the step: [n_slab][max_batch rows][3 d] f32, rows local to the chain, zero bias
+      for (int i = 0; i < n_slab; ++i)
+        HIPCHK(c, hipMemcpyAsync(c->slab + (size_t)i * c->maxB * 3 * d, qkv + (size_t)i * n_rows * 3 * d, (size_t)n_rows * 3 * d * 4, hipMemcpyHostToDevice, s));
+      sq.slab = c->slab; sq.bias = c->sprobe_zero; sq.n = n_slab; sq.stride = (int64_t)c->maxB * 3 * d; sq.ld = 3 * d;
+    } else {
+      TRY(upload_rows(dqkv));
+    }
+    if (form == TTASR_SELF_STEP) HIPCHK(c, hipMemcpyAsync(c->sprobe_pos, geom, 4, hipMemcpyHostToDevice, s));
+    else HIPCHK(c, hipMemcpyAsync(c->sprobe_pos + row0, geom, (size_t)n_rows * 4, hipMemcpyHostToDevice, s));
+    if (done) HIPCHK(c, hipMemcpyAsync(c->probe_done + row0, done, (size_t)n_rows * 4, hipMemcpyHostToDevice, s));
+    const int32_t* done_dev = done ? c->probe_done + row0 : nullptr;
+    HIPCHK(c, hipMemcpyAsync(c->page_table, own_table ? aux : ident.data(), (size_t)total_pages * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(datt, 0, (size_t)n_rows * d * e, s));   // rows a kernel does not write come back 0
+    { SigScope on(sig);
+      if (form == TTASR_SELF_STEP)
+        TT_DISPATCH(c, launch_self_attn_decode<T>((const T*)dqkv, (T*)c->pool, c->page_table, pps, (int64_t)layer * c->pool_layer_elems,
+                                                  identity_pages ? 1 : 0, row0, c->sprobe_pos, (T*)datt, n_rows, c->H, s, sq, done_dev));
+      else
+        TT_DISPATCH(c, launch_self_attn_decode_rows<T>((const T*)dqkv, (T*)c->pool, c->page_table, pps, (int64_t)layer * c->pool_layer_elems,
+                                                       identity_pages ? 1 : 0, row0, c->sprobe_pos, (T*)datt, n_rows, c->H, s, sq, done_dev)); }
+    out_dev = datt;
+  } else if (form == TTASR_SELF_PREFILL) {
+    if (n_geom != 2 || geom[0] < 1 || geom[0] > c->maxB || geom[1] < 1 || geom[1] > ctx || (int64_t)geom[0] * geom[1] != n_rows || n_rows > kSelfProbeRows)
+      return fail(c, TTASR_E_INVALID, "prefill: {n_seq <= max_batch, npos <= n_text_ctx} with n_seq x npos = n_rows <= %d expected", kSelfProbeRows);
+    TRY(upload_rows(c->sprobe_t));
+    HIPCHK(c, hipMemcpyAsync(c->page_table, own_table ? aux : ident.data(), (size_t)total_pages * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(c->sprobe_out, 0, (size_t)n_rows * d * e, s));
+    { SigScope on(sig);
+      TT_DISPATCH(c, launch_self_attn_prefill<T>((const T*)c->sprobe_t, (T*)c->pool, c->page_table, pps, (int64_t)layer * c->pool_layer_elems,
+                                                 identity_pages ? 1 : 0, (T*)c->sprobe_out, geom[0], geom[1], c->H, s)); }
+    out_dev = c->sprobe_out;
+  } else {   // TTASR_SELF_PACKED: geom = the sequences' lengths, aux = their page lists one after the other
+    if (n_geom < 1 || n_geom > kSelfProbeRows) return fail(c, TTASR_E_INVALID, "%d sequences", n_geom);
+    int R = 0, np = 0, ni = 0;
+    for (int i = 0; i < n_geom; ++i) {
+      if (geom[i] < 1 || geom[i] > ctx || (R += geom[i]) > kSelfProbeRows)
+        return fail(c, TTASR_E_INVALID, "sequence %d: length %d, more than %d rows in all", i, geom[i], kSelfProbeRows);
+      np += (geom[i] + 15) / 16; ni += prefill_items_of(geom[i]);
+    }
+    if (R != n_rows || np != n_aux) return fail(c, TTASR_E_INVALID, "%d rows and %d pages given, the lengths need %d and %d", n_rows, n_aux, R, np);
+    TRY(self_probe_pages_ok(c, aux, n_aux));
+    const size_t w_slots = (size_t)R * 3, w_seqs = w_slots + R, w_items = w_seqs + (size_t)n_geom * (3 + pps), words = w_items + (size_t)ni * 3;
+    std::vector<int32_t> in(words, 0), zeros((size_t)ctx, 0);
+    std::vector<PrefillSeq> sqs(n_geom);
+    for (int i = 0, p = 0; i < n_geom; p += (geom[i] + 15) / 16, ++i) sqs[i] = PrefillSeq{0, geom[i], zeros.data(), aux + p};
+    prefill_build_tables(sqs.data(), n_geom, pps, in.data(), in.data() + w_slots, in.data() + w_seqs, in.data() + w_items);
+    HIPCHK(c, hipMemcpyAsync(c->sprobe_tab, in.data(), words * 4, hipMemcpyHostToDevice, s));
+    TRY(upload_rows(c->sprobe_t));
+    HIPCHK(c, hipMemsetAsync(c->sprobe_out, 0, (size_t)n_rows * d * e, s));
+    const int32_t* dw = c->sprobe_tab;
+    const PrefillPass P{dw, dw + w_slots, dw + w_seqs, dw + w_items, R, n_geom, ni, 3 + pps};
+    { SigScope on(sig);
+      TT_DISPATCH(c, launch_prefill_self_attn<T>(P, (const T*)c->sprobe_t, (T*)c->pool + (int64_t)layer * c->pool_layer_elems, (T*)c->sprobe_out, c->H, s)); }
+    HIPCHK(c, hipStreamSynchronize(s));   // `in` is a stack temporary
+    out_dev = c->sprobe_out;
+  }
+  if (own_table) HIPCHK(c, hipMemcpyAsync(c->page_table, ident.data(), (size_t)total_pages * 4, hipMemcpyHostToDevice, s));   // the identity again
+  if (sig_buf) snprintf(sig_buf, (size_t)sig_len, "%s", sig);
+  if (c->lowp) { TT_DISPATCH(c, launch_uncast<T>((const T*)out_dev, c->sprobe_f32, (int64_t)n_rows * d, s));
+                 HIPCHK(c, hipMemcpyAsync(out, c->sprobe_f32, (size_t)n_rows * d * 4, hipMemcpyDeviceToHost, s)); }
+  else HIPCHK(c, hipMemcpyAsync(out, out_dev, (size_t)n_rows * d * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));   // `ident` is a stack temporary; the results are on the host
+  HIPCHK(c, hipGetLastError());
+  return TTASR_OK;
+  });
+}
+
 int ttasr_decode_reset(ttasr_ctx* c, int32_t B) {
   return guarded(c, [&]() -> int {
   TRY(check_ready(c, B));

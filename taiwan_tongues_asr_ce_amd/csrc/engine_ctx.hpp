@@ -204,7 +204,11 @@ struct ttasr_ctx {
   bool prefill_tiled = false;  // option prefill_tiled: tiled encoder GEMMs in the prefill pass whatever the row count (A/B testing)
   hipEvent_t ev[8]{};
   int32_t* probe_done = nullptr; float* probe_zero = nullptr;   // ttasr_cross_attn_probe: its own [maxB] finished flags and a [d] zero bias (allocated by the first call)
-  std::string bench_sig;     // signature of the kernel the last ttasr_bench_kernel call launched (ttasr_bench_kernel_signature)
+  // ttasr_self_attn_probe / ttasr_self_kv_*: an f32 and a T staging block of max(one pool layer, 512 x 3 d) elements, a T output
+  // [512][d], [maxB] positions, a [3 d] zero bias and the packed pass's tables (allocated by the first call)
+  float* sprobe_f32 = nullptr; void *sprobe_t = nullptr, *sprobe_out = nullptr; int32_t *sprobe_pos = nullptr, *sprobe_tab = nullptr;
+  float* sprobe_zero = nullptr; int64_t sprobe_elems = 0;
+  std::string bench_sig;    // signature of the kernel the last ttasr_bench_kernel call launched (ttasr_bench_kernel_signature)
   float phase_ms[4]{0, 0, 0, 0};
   // option enc_kernel_timing: one hipEvent after every launch of run_encoder / run_cross_kv, so the NEXT ttasr_encode also
   // reports where the phase went, in situ (class sums: ttasr_encoder_kernel_ms).  Off in the timed benchmark steps.

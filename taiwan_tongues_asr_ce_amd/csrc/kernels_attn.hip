@@ -120,6 +120,7 @@ void launch_fault(const char* fmt, ...) {
 }
 thread_local bool g_kernel_sig_on = false;
 thread_local char g_kernel_sig[192] = "";
+thread_local char* g_self_attn_sig = nullptr;
 using u32x4_t = __attribute__((ext_vector_type(4))) unsigned;
 
 // Single pass, one memory round trip for pos <= 32*UNROLL cached keys: every lane keeps an online-softmax
@@ -275,6 +276,8 @@ void launch_self_attn_decode(const T* qkv, T* kv_pool, const int32_t* page_table
   if (sq.n > 0) { if (identity_pages) TTASR_SA(true, true); else TTASR_SA(true, false); }
   else { if (identity_pages) TTASR_SA(false, true); else TTASR_SA(false, false); }
 #undef TTASR_SA
+  if (g_self_attn_sig) snprintf(g_self_attn_sig, kSelfAttnSigLen, "self_attn_decode_kernel<%s, 0, %s, %s> grid %d", sig_type<T>(),
+                                sq.n > 0 ? "true" : "false", identity_pages ? "true" : "false", H * B * 256);
 }
 // the session form: row_pos [row0 + B] per-row positions, finished / idle rows leave via `done`; identity pages for the greedy
 // session, the loaded page table (copy-on-write sharing) for the beam session
@@ -288,6 +291,8 @@ void launch_self_attn_decode_rows(const T* qkv, T* kv_pool, const int32_t* page_
   if (sq.n > 0) { if (identity_pages) TTASR_SA(true, true); else TTASR_SA(true, false); }
   else { if (identity_pages) TTASR_SA(false, true); else TTASR_SA(false, false); }
 #undef TTASR_SA
+  if (g_self_attn_sig) snprintf(g_self_attn_sig, kSelfAttnSigLen, "self_attn_decode_kernel<%s, 3, %s, %s> grid %d", sig_type<T>(),
+                                sq.n > 0 ? "true" : "false", identity_pages ? "true" : "false", H * B * 256);
 }
 // prompt prefill: rows = n_seq * npos, row-major [sequence][position]; positions 0..npos-1 of every sequence
 template <typename T>
@@ -299,6 +304,11 @@ void launch_self_attn_prefill(const T* qkv, T* kv_pool, const int32_t* page_tabl
                      (const int32_t*)nullptr, H, npos, SlabIn{})
   if (identity_pages) { TTASR_SP(1, true); TTASR_SP(2, true); } else { TTASR_SP(1, false); TTASR_SP(2, false); }
 #undef TTASR_SP
+  if (g_self_attn_sig) {
+    const char *t = sig_type<T>(), *id = identity_pages ? "true" : "false";
+    snprintf(g_self_attn_sig, kSelfAttnSigLen, "self_attn_decode_kernel<%s, 1, false, %s> grid %d + self_attn_decode_kernel<%s, 2, false, %s> grid %d",
+             t, id, H * n_seq * npos * 256, t, id, H * n_seq * npos * 256);
+  }
 }
 template void launch_self_attn_prefill<float>(const float*, float*, const int32_t*, int, int64_t, int, float*, int, int, int, hipStream_t);
 template void launch_self_attn_prefill<bf16_t>(const bf16_t*, bf16_t*, const int32_t*, int, int64_t, int, bf16_t*, int, int, int,
@@ -320,6 +330,7 @@ __global__ __launch_bounds__(256) void copy_pages_kernel(T* __restrict__ pool, c
 template <typename T>
 void launch_copy_pages(T* pool, const int32_t* pairs_dev, int n_pairs, int n_layers, int H, int64_t layer_elems, hipStream_t s) {
   if (n_pairs > 0) hipLaunchKernelGGL(copy_pages_kernel<T>, dim3(n_pairs, n_layers), dim3(256), 0, s, pool, pairs_dev, H, layer_elems);
+  if (g_self_attn_sig && n_pairs > 0) snprintf(g_self_attn_sig, kSelfAttnSigLen, "copy_pages_kernel<%s> grid %d", sig_type<T>(), n_pairs * n_layers * 256);
 }
 template void launch_copy_pages<float>(float*, const int32_t*, int, int, int, int64_t, hipStream_t);
 template void launch_copy_pages<bf16_t>(bf16_t*, const int32_t*, int, int, int, int64_t, hipStream_t);

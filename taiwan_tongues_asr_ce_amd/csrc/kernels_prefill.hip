@@ -9,6 +9,7 @@
 // The f32 engine's cross-attention is the per-row kernel of the alignment pass with row -> slot from the table
 // (launch_cross_attn_probs_batch).  Every row's result depends on the row's own sequence only: nothing here reads the pass's size.
 #include "common.hpp"
+#include <cstdio>
 #include <type_traits>
 
 constexpr int PF_PAGE = 16;   // positions per KV page (pool layout per layer: [page][2 (K, V)][H][16][64])
@@ -105,6 +106,8 @@ template <typename T>
 void launch_prefill_self_attn(const PrefillPass& P, const T* qkv, T* pool_layer, T* out, int H, hipStream_t s) {
   hipLaunchKernelGGL(prefill_append_kernel<T>, dim3(P.n_rows), dim3(256), 0, s, qkv, pool_layer, P.rows, P.seqs, P.seq_stride, H);
   hipLaunchKernelGGL(prefill_attend_kernel<T>, dim3(H, P.n_rows), dim3(256), 0, s, qkv, (const T*)pool_layer, P.rows, P.seqs, P.seq_stride, out, H);
+  if (g_self_attn_sig) snprintf(g_self_attn_sig, kSelfAttnSigLen, "prefill_append_kernel<%s> grid %d + prefill_attend_kernel<%s> grid %d", sig_type<T>(),
+                                P.n_rows * 256, sig_type<T>(), H * P.n_rows * 256);
 }
 
 // ------------------------------------------------------------------------------------------------

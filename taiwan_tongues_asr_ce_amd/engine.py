@@ -452,6 +452,57 @@ class Engine:
                     "align_attn_probe")
         return out, maps
 
+    # -- known-answer hooks of the decoder self-attention ------------------
+    SELF_FORMS = {"step": 0, "rows": 1, "prefill": 2, "packed": 3, "copy": 4}   # TTASR_SELF_* of include/ttasr.h
+
+    @property
+    def pages_per_seq(self) -> int:
+        return (self.dims.n_text_ctx + 15) // 16
+
+    def self_kv_fill(self, layer: int, pattern: int):
+        """Every element of the layer's self-attention KV pool (-1: of every layer) = the bit pattern (ttasr_self_kv_fill)."""
+        self._check(self.lib.ttasr_self_kv_fill(self.h, layer, pattern & 0xffffffff), "self_kv_fill")
+
+    def self_kv_set(self, layer: int, pages: Sequence[int], kv: np.ndarray, n: int = 16):
+        """Positions [0, n) of the listed pool pages from float32 page images [n_pages][2][H][16][64] (ttasr_self_kv_set)."""
+        pg = np.ascontiguousarray(pages, dtype=np.int32)
+        kv = np.ascontiguousarray(kv, dtype=np.float32)
+        assert kv.shape == (len(pg), 2, self.dims.n_heads, 16, 64), kv.shape
+        self._check(self.lib.ttasr_self_kv_set(self.h, layer, pg.ctypes.data_as(C.c_void_p), len(pg), n, _ptr(kv)), "self_kv_set")
+
+    def self_kv_get(self, layer: int, pages: Optional[Sequence[int]] = None) -> np.ndarray:
+        """Pool pages of a layer as float32 [n_pages][2][H][16][64], exactly; pages None = the whole layer (ttasr_self_kv_get)."""
+        pg = None if pages is None else np.ascontiguousarray(pages, dtype=np.int32)
+        n = self.max_batch * self.pages_per_seq if pg is None else len(pg)
+        out = np.empty((n, 2, self.dims.n_heads, 16, 64), dtype=np.float32)
+        self._check(self.lib.ttasr_self_kv_get(self.h, layer, None if pg is None else pg.ctypes.data_as(C.c_void_p), n, _ptr(out)), "self_kv_get")
+        return out
+
+    def self_attn_probe(self, form: str, layer: int = 0, qkv: Optional[np.ndarray] = None, geom: Sequence[int] = (),
+                        aux: Optional[Sequence[int]] = None, identity_pages: bool = True, row0: int = 0, done: Optional[np.ndarray] = None):
+        """One launch of a named form of the decoder self-attention (ttasr_self_attn_probe).  qkv: float32 [n_rows][3 d_model], or
+        [n_slab][n_rows][3 d_model] partial tiles; geom: the position (step), the rows' positions (rows), (n_seq, npos) (prefill) or
+        the sequences' lengths (packed); aux: the page table [max_batch][pages_per_seq] (step, rows, prefill; None = identity), the
+        page lists (packed) or the (source, destination) pairs (copy).  Returns (out float32 [n_rows][d_model] or None for copy,
+        signature of what ran)."""
+        gm = np.ascontiguousarray(geom, dtype=np.int32).reshape(-1)
+        ax = np.zeros(0, np.int32) if aux is None else np.ascontiguousarray(aux, dtype=np.int32).reshape(-1)
+        buf = C.create_string_buffer(256)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+        if form == "copy":
+            self._check(self.lib.ttasr_self_attn_probe(self.h, 4, 0, 0, None, 0, None, 0, vp(ax), ax.size, 0, 0, None, None, buf, 256), "self_attn_probe")
+            return None, buf.value.decode()
+        qkv = np.ascontiguousarray(qkv, dtype=np.float32)
+        n_slab = qkv.shape[0] if qkv.ndim == 3 else 0
+        n_rows = qkv.shape[-2]
+        assert qkv.shape[-1] == 3 * self.dims.d_model, qkv.shape
+        out = np.empty((n_rows, self.dims.d_model), dtype=np.float32)
+        flags = None if done is None else np.ascontiguousarray(done, dtype=np.int32)
+        assert flags is None or flags.shape == (n_rows,)
+        self._check(self.lib.ttasr_self_attn_probe(self.h, self.SELF_FORMS[form], layer, n_rows, _ptr(qkv), n_slab, vp(gm), gm.size, vp(ax), ax.size,
+                                                   1 if identity_pages else 0, row0, vp(flags), _ptr(out), buf, 256), "self_attn_probe")
+        return out, buf.value.decode()
+
     # -- a9, a10 -------------------------------------------------------------------------------
     def gen_opts(self, max_new_tokens: int, timestamps: bool, suppress: Optional[Sequence[int]] = None,
                  begin_suppress: Optional[Sequence[int]] = None, suppress_eot: bool = False, no_speech: bool = True,

@@ -52,6 +52,7 @@ def test_release_library_has_no_environment_switch(lib):
     blob = open(_lib.LIB_PATH, "rb").read()
     assert b"TTASR_" not in blob
     assert lib.ttasr_set_option(None, b"flash", 0) == -1       # NULL context: refused, no crash
+    assert lib.ttasr_self_attn_probe(None, 0, 0, 1, None, 0, None, 0, None, 0, 1, 0, None, None, None, 0) == -1 and lib.ttasr_self_kv_fill(None, 0, 0) == -1
 
 
 def test_struct_layouts_match_header():
