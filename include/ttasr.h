@@ -722,6 +722,67 @@ TTASR_API int ttasr_ingest_wave(ttasr_ctx* ctx, int32_t n, const void* const* ra
                                 const int32_t* rate, const int32_t* channels, const int32_t* format, const int32_t* block_align,
                                 const int32_t* pick, float* const* out_pcm_host);
 
+/* ---- FLAC files (RFC 9639; the folder tool, the file service and the reference all list *.flac) ----------------------------------
+ * The stream that is accepted: an optional ID3v2 tag, "fLaC", the metadata blocks with STREAMINFO (34 bytes) first and every other
+ * type skipped (type 127 is invalid), then frames back to back up to the end of the data or to a 128-byte ID3v1 tag ("TAG").  1 to 8
+ * channels, 4 to 24 bits per sample, every blocksize from 1 to 65535, both blocking strategies, constant / verbatim / fixed (order
+ * 0 ... 4) / LPC (order 1 ... 32) subframes, both Rice methods with escape partitions, wasted bits, and the three stereo codes.  Ogg
+ * FLAC is out of scope.  Refused, each with a message that says which: 25 to 32 bits; a frame whose rate, channel count or width
+ * differs from STREAMINFO's; a reserved code; a broken CRC-8 or CRC-16; a coded number that does not continue the previous frame
+ * (fixed blocking + 1, variable blocking + the previous blocksize; the first frame may start anywhere); bytes behind the last frame
+ * that are no ID3v1 tag; more than 2^40 samples.
+ *   Frame scan (host): a frame starts where a header is valid - its fields, its CRC-8, the stream's parameters, the continuity - and
+ *     ends at the smallest q where the two bytes before q are the CRC-16 (0x8005, init 0, MSB first) of the frame up to them AND q is
+ *     the end of the data or the start of a valid continuing header: one table-driven CRC pass over the file.  A q where the CRC-16
+ *     holds and a sync code stands, but no valid continuing header, is passed over - such bytes occur inside valid frames - and only
+ *     serves the message: when the frame found at last does not decode while the bytes up to that q do, the file is refused for
+ *     the damaged header at q (its CRC-8, a reserved code, its parameters, its number).  STREAMINFO's frame sizes are not used.
+ *     The samples HELD are the sum of the blocksizes found, whatever STREAMINFO's total says.
+ *   Sample value: an integer v of a `bits`-wide stream is the float v / 2^(bits - 1).  The decoder left-justifies: v << (16 - bits)
+ *     as int16 for bits <= 16, v << (32 - bits) as int32 otherwise, and the result is read as TTASR_PCM_S16 / TTASR_PCM_S32.  All
+ *     decoder arithmetic is integer and wraps; a malformed stream has no undefined behaviour.
+ *   Status word of a frame (the decode body, the same code on the host and on the device): 0 ok, 1 reserved subframe type or field,
+ *     or a padding bit in front of the CRC-16 that is set,
+ *     2 LPC precision 1111 or negative shift, 3 a partition order that does not divide the blocksize or leaves less than the order,
+ *     4 the subframes run past the end of the frame, 5 the header disagrees with the frame table or the stream, 6 the subframes end
+ *     before the frame does.
+ *
+ * The three functions below need no context and no GPU.  `why` (may be NULL), of `why_len` bytes, receives the reason of a refusal.
+ * ttasr_flac_probe: out[0] rate, [1] channels, [2] bits per sample, [3] samples per channel held, [4] the number of FLAC frames,
+ *   [5] the largest blocksize, [6] the byte offset of the first frame, [7] flags: 1 = STREAMINFO carries an MD5, 2 = STREAMINFO's
+ *   total is set and disagrees with what is held.  TTASR_OK, or TTASR_E_INVALID for a refused stream.
+ * ttasr_flac_frames: the scan's known-answer hook.  Returns the number of frames (negative: refused) and writes min(cap, frames)
+ *   rows (byte offset, byte length, first sample) to `table` when it is not NULL.
+ * ttasr_flac_decode: the host decoder.  out[sample][channel] receives the plain integers v (not left-justified); cap_samples is
+ *   the number of samples per channel `out` takes.  Returns the samples per channel decoded, or TTASR_E_INVALID for a refused
+ *   stream, a frame with a status word other than 0 (the message names the frame) or an output that is too small.  The frames are
+ *   decoded one after the other on the calling thread.  The MD5 is the caller's to check (over the samples interleaved, each a
+ *   little-endian signed number of ceil(bits / 8) bytes).
+ *
+ * TTASR_PCM_FLAC in ttasr_ingest_wave: raw_host[i] / n_bytes[i] are the whole file as read, ID3 tags and metadata included;
+ *   rate[i] and channels[i] must equal what the stream says; n_frames[i] is at most the samples held; block_align[i] is ignored;
+ *   pick works as for every other format.  Everything ttasr_flac_probe refuses is refused here too, before anything is enqueued and
+ *   with the context left usable.  Wire streams refuse the format, as they refuse IMA.
+ *   FLAC chunks are cut on FLAC frame boundaries ("ingest_chunk" is rounded up to whole FLAC frames).  A chunk uploads the bytes of
+ *   its frames - and of the frames the filter's halo touches on both sides - behind a table with one entry per frame (offset in the
+ *   slot, length, first sample, blocksize).  The pre-pass runs one lane per FLAC frame over that table: the decode body writes the
+ *   left-justified int16 / int32 [samples][channels] into a device scratch block, which the ingest kernel then reads as
+ *   TTASR_PCM_S16 / TTASR_PCM_S32, unchanged.  The scratch is 64 MiB + 1 MiB of device memory - 32 MiB for the decoded chunk, 32 MiB
+ *   for the lanes' int32 work rows, each 16 of the largest legal frames (65535 samples x 8 channels x 4 B), so that a frame and its
+ *   halo frames always fit, and one status word per frame and slot - with 1 MiB of pinned status words; allocated by the first FLAC
+ *   call, freed by ttasr_destroy.  A chunk must also fit a result slot: a single FLAC frame that resamples to more than 2^20
+ *   outputs (65535 samples at a rate below 1 kHz) is refused, like everything else before anything is enqueued.
+ *   A frame whose content is illegal although its CRC-16 holds makes the call return TTASR_E_INVALID with a message naming the
+ *   recording, the frame and the status word's meaning: every lane writes its status word with an ordinary store and the words
+ *   return with the chunk.  The context stays usable; that call's outputs are unspecified.
+ *   For every accepted recording the result equals, bit for bit, ttasr_ingest_pcm fed the left-justified integers as TTASR_PCM_S16
+ *   / TTASR_PCM_S32 (with a pick: fed that one channel as a mono recording), and depends neither on the chunk size nor on the other
+ *   recordings of the call nor on its place in it. */
+#define TTASR_PCM_FLAC 32
+TTASR_API int ttasr_flac_probe(const void* bytes, int64_t n_bytes, int64_t* out, char* why, int32_t why_len);
+TTASR_API int64_t ttasr_flac_frames(const void* bytes, int64_t n_bytes, int64_t* table, int64_t cap, char* why, int32_t why_len);
+TTASR_API int64_t ttasr_flac_decode(const void* bytes, int64_t n_bytes, int32_t* out, int64_t cap_samples, char* why, int32_t why_len);
+
 /* ---- wire streams: a VAD stream fed the BYTES of a live connection (the streaming server's `rate` 8000 | 16000 and `channel`
  * 1 | 2 query parameters, the config message's sampleRate / channels; G.711 telephony with one party per channel) ----------------
  * A wire stream is a VAD stream (above) opened with a wire format: rate, channels (1 ... 8), format (the six TTASR_PCM_* sample

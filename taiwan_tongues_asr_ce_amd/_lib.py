@@ -24,11 +24,13 @@ SYMBOLS = [
     "ttasr_vad_stream_open", "ttasr_vad_stream_reset", "ttasr_vad_stream_close", "ttasr_vad_stream_push",
     "ttasr_ingest_len", "ttasr_ingest_filter", "ttasr_ingest_pcm", "ttasr_ingest_wave",
     "ttasr_ingest_stream_len", "ttasr_vad_stream_open_wire", "ttasr_vad_stream_push_wire",
+    "ttasr_flac_probe", "ttasr_flac_frames", "ttasr_flac_decode",
 ]
 
 PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = range(6)   # TTASR_PCM_* of include/ttasr.h
 PCM_BYTES = (1, 2, 3, 4, 4, 8)                                    # bytes per sample, by format code
 PCM_ALAW, PCM_ULAW, PCM_IMA4 = 16, 17, 18                         # the coded formats of ttasr_ingest_wave
+PCM_FLAC = 32                                                     # a whole FLAC file as read (ttasr_ingest_wave, ttasr_flac_*)
 CODED_BYTES = {PCM_ALAW: 1, PCM_ULAW: 1}                          # bytes per sample of the G.711 codes (IMA: 4 bits, in blocks)
 VAD_MAX_STREAMS = 1024    # TTASR_VAD_MAX_STREAMS of include/ttasr.h: open streams of one context (ttasr_vad_stream_*)
 VAD_CHUNK_FRAMES = 1024   # TTASR_VAD_CHUNK_FRAMES of include/ttasr.h: frames of one recording per time chunk of ttasr_vad_probs
@@ -148,10 +150,61 @@ def load() -> C.CDLL:
     lib.ttasr_vad_stream_open_wire.argtypes = [vp, i32, i32, i32, i32, i32p]
     lib.ttasr_vad_stream_push_wire.argtypes = [vp, i32, i32p, C.POINTER(vp), i64p, i32p, C.POINTER(vp), i64p, i64p, C.POINTER(vp),
                                                C.POINTER(vp), i32p]
+    lib.ttasr_flac_probe.argtypes = [vp, i64, i64p, C.c_char_p, i32]
+    lib.ttasr_flac_frames.argtypes = [vp, i64, i64p, i64, C.c_char_p, i32]
+    lib.ttasr_flac_frames.restype = i64
+    lib.ttasr_flac_decode.argtypes = [vp, i64, i32p, i64, C.c_char_p, i32]
+    lib.ttasr_flac_decode.restype = i64
     for s in SYMBOLS:
         f = getattr(lib, s)
         if s not in ("ttasr_destroy", "ttasr_last_error", "ttasr_version", "ttasr_ingest_len", "ttasr_ingest_filter",
-                     "ttasr_ingest_stream_len"):
+                     "ttasr_ingest_stream_len", "ttasr_flac_frames", "ttasr_flac_decode"):
             f.restype = C.c_int
     _lib = lib
     return lib
+
+
+class FlacInfo(tuple):
+    """ttasr_flac_probe's eight numbers with names."""
+    rate = property(lambda s: s[0]); channels = property(lambda s: s[1]); bits = property(lambda s: s[2])    # noqa: E702
+    samples = property(lambda s: s[3]); frames = property(lambda s: s[4]); max_blocksize = property(lambda s: s[5])   # noqa: E702
+    first_frame = property(lambda s: s[6]); has_md5 = property(lambda s: bool(s[7] & 1))    # noqa: E702
+    total_disagrees = property(lambda s: bool(s[7] & 2))
+
+
+def _flac_buffer(data):
+    import numpy as np
+    return np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data).reshape(-1).view(np.uint8)
+
+
+def flac_probe(data) -> FlacInfo:
+    """A whole FLAC file as read -> FlacInfo (ttasr_flac_probe: no GPU).  ValueError with the library's reason for a stream it refuses."""
+    b, out, why = _flac_buffer(data), (C.c_int64 * 8)(), C.create_string_buffer(256)
+    if load().ttasr_flac_probe(b.ctypes.data, len(b), out, why, len(why)) != 0:
+        raise ValueError("FLAC: " + why.value.decode("utf-8", "replace"))
+    return FlacInfo(int(v) for v in out)
+
+
+def flac_frames(data):
+    """The frame table of the scan: int64 [frames][3] = byte offset, byte length, first sample (ttasr_flac_frames)."""
+    import numpy as np
+    b, why = _flac_buffer(data), C.create_string_buffer(256)
+    n = load().ttasr_flac_frames(b.ctypes.data, len(b), None, 0, why, len(why))
+    if n < 0:
+        raise ValueError("FLAC: " + why.value.decode("utf-8", "replace"))
+    table = np.zeros((max(n, 1), 3), dtype=np.int64)
+    load().ttasr_flac_frames(b.ctypes.data, len(b), table.ctypes.data_as(C.POINTER(C.c_int64)), n, why, len(why))
+    return table[:n]
+
+
+def flac_decode(data):
+    """A whole FLAC file as read -> (int32 [samples][channels] plain integers, FlacInfo), decoded by the library on the host
+    (ttasr_flac_decode).  ValueError with the library's reason for a stream it refuses or a frame with illegal content."""
+    import numpy as np
+    info = flac_probe(data)
+    b, why = _flac_buffer(data), C.create_string_buffer(256)
+    out = np.zeros((info.samples, info.channels), dtype=np.int32)
+    n = load().ttasr_flac_decode(b.ctypes.data, len(b), out.ctypes.data_as(C.POINTER(C.c_int32)), info.samples, why, len(why))
+    if n < 0:
+        raise ValueError("FLAC: " + why.value.decode("utf-8", "replace"))
+    return out, info

@@ -1,5 +1,6 @@
-"""Audio input on the host: the one RIFF/WAVE parser, the one bytes -> float32 sample conversion (the definition that
-csrc/kernels_ingest.hip and include/ttasr.h restate for the device), the one host resampler, and the readers built from them -
+"""Audio input on the host: the one RIFF/WAVE parser, the native FLAC reader (the library's ttasr_flac_* functions), the one
+bytes -> float32 sample conversion (the definition that csrc/kernels_ingest.hip and include/ttasr.h restate for the device),
+the one host resampler, and the readers built from them -
 `read_audio_coded` / `read_audio_raw` for the device ingest (Engine.ingest) and `decode_audio` for the host path.  Nothing here
 needs the model layer, the engine or a GPU."""
 from __future__ import annotations
@@ -126,7 +127,8 @@ def resample(x: np.ndarray, rate: int, sampling_rate: int = SAMPLE_RATE) -> np.n
 class CodedAudio(NamedTuple):
     """What Engine.ingest needs of one file: the data bytes as the file has them, format = the _lib.PCM_* code (the six sample
     formats, PCM_ALAW, PCM_ULAW, PCM_IMA4), block_align = bytes per frame, or per block for IMA, n_frames = the frames the bytes
-    hold (IMA: what `fact` says when that is less)."""
+    hold (IMA: what `fact` says when that is less).  A FLAC file is format PCM_FLAC: samples = the whole file as read (tags and
+    metadata included), block_align = 0, n_frames = the samples per channel its frames hold."""
     samples: bytes
     rate: int
     channels: int
@@ -164,12 +166,67 @@ def _parse_riff(path: str):
     return tag, n_ch, sr, bits, block_align, data, fact
 
 
+def _id3v2_size(head: bytes) -> int:
+    """Bytes of the ID3v2 tag that the first ten bytes of a file announce, header and footer included; 0: no such tag."""
+    if len(head) < 10 or head[:3] != b"ID3":
+        return 0
+    return 10 + ((head[6] & 0x7F) << 21 | (head[7] & 0x7F) << 14 | (head[8] & 0x7F) << 7 | (head[9] & 0x7F)) + (10 if head[5] & 0x10 else 0)
+
+
+def _flac_marker(blob: bytes) -> int:
+    """Byte offset of the "fLaC" marker of a file that begins with it, or with an ID3v2 tag followed by it; -1: not FLAC."""
+    pos = _id3v2_size(blob[:10])
+    return pos if blob[pos:pos + 4] == b"fLaC" else -1
+
+
+def _read_flac(path: str) -> Optional[CodedAudio]:
+    """CodedAudio of a file whose content is FLAC; None for a missing file or other bytes; ValueError for damaged FLAC.  Only a
+    file that has the marker is read whole: of a tagged file of another kind, the ten bytes of the tag's header and four behind
+    the tag."""
+    try:
+        with open(path, "rb") as f:
+            pos = _id3v2_size(f.read(10))
+            f.seek(pos)
+            if f.read(4) != b"fLaC":
+                return None
+            f.seek(0)
+            blob = f.read()
+    except OSError:
+        return None
+    try:
+        info = _lib.flac_probe(blob)
+    except ValueError as e:
+        raise ValueError(f"{path}: {e}") from None
+    return CodedAudio(blob, info.rate, info.channels, _lib.PCM_FLAC, 0, info.samples)
+
+
+def flac_to_int(c: CodedAudio, verify_md5: bool = True):
+    """A PCM_FLAC CodedAudio -> (int32 [frames][channels] plain integers, bits per sample), decoded by the library on the host.
+    verify_md5: when STREAMINFO carries an MD5 it is checked against the decoded samples (interleaved, little-endian signed
+    numbers of ceil(bits / 8) bytes); a mismatch is a ValueError."""
+    blob = c.samples if isinstance(c.samples, (bytes, bytearray)) else bytes(c.samples)
+    x, info = _lib.flac_decode(blob)
+    if verify_md5 and info.has_md5:
+        import hashlib
+        at = _flac_marker(blob) + 8 + 18            # the marker, STREAMINFO's block header, the 18 bytes in front of its MD5
+        width = (info.bits + 7) // 8
+        le = x.astype("<i4").view(np.uint8).reshape(-1, 4)[:, :width]
+        if hashlib.md5(np.ascontiguousarray(le).tobytes()).digest() != bytes(blob[at:at + 16]):
+            raise ValueError("FLAC: the MD5 of the decoded samples is not the one in STREAMINFO")
+    return x[:c.n_frames], info.bits
+
+
 def read_audio_coded(path: str) -> Optional[CodedAudio]:
-    """Path -> CodedAudio for the device ingest.  RIFF/WAVE (format tag 1, 3, 6, 7, 0x11, or EXTENSIBLE with one of them as its
+    """Path -> CodedAudio for the device ingest.  A file whose content is FLAC (it begins with "fLaC", or with an ID3v2 tag
+    followed by it): the whole file, format PCM_FLAC, needing no decoder library; ValueError when it is damaged or unsupported.
+    RIFF/WAVE (format tag 1, 3, 6, 7, 0x11, or EXTENSIBLE with one of them as its
     sub-format): the data bytes untouched, cut to whole frames.  Other containers: through soundfile when it imports, at the file's
     own rate, as a float32 array [frames][channels] (format PCM_F32); None without soundfile or for a container it does not take
     (decode_audio tries the other decoders)."""
     if not path.lower().endswith((".wav", ".wave")):
+        c = _read_flac(path)
+        if c is not None:
+            return c
         try:
             import soundfile as sf  # type: ignore
             x, sr = sf.read(path, dtype="float32", always_2d=True)
@@ -204,9 +261,18 @@ def read_audio_raw(path: str):
     return None if c is None or c.format >= _lib.PCM_ALAW else c[:4]
 
 
-def decode_coded(c: CodedAudio, channel: Optional[int] = None) -> np.ndarray:
-    """CodedAudio -> mono float32 at the file's own rate, on the host: the mean of the channels, or one of them."""
-    if c.format == _lib.PCM_IMA4:
+def decode_coded(c: CodedAudio, channel: Optional[int] = None, verify_md5: bool = True) -> np.ndarray:
+    """CodedAudio -> mono float32 at the file's own rate, on the host: the mean of the channels, or one of them.  FLAC is decoded by
+    the library (ttasr_flac_decode) to integers v, which become v / 2^(bits - 1) exactly as the left-justified int16 / int32 do;
+    verify_md5 checks the stream's MD5 when it carries one (ValueError on a mismatch)."""
+    if c.format == _lib.PCM_FLAC:
+        v, bits = flac_to_int(c, verify_md5)
+        if bits <= 16:
+            x = (v << (16 - bits)).astype(np.float32) / 32768.0
+        else:
+            x = (v << (32 - bits)).astype(np.float32) / 2147483648.0
+        x = x.reshape(-1) if c.channels == 1 else x
+    elif c.format == _lib.PCM_IMA4:
         x = _ima_decode(c.samples, c.channels, c.block_align, c.n_frames).astype(np.float32) / 32768.0
         x = x.reshape(-1) if c.channels == 1 else x
     else:
@@ -216,10 +282,14 @@ def decode_coded(c: CodedAudio, channel: Optional[int] = None) -> np.ndarray:
 
 def decode_audio(path: str, sampling_rate: int = SAMPLE_RATE, channel: Optional[int] = None) -> np.ndarray:
     """Path -> mono float32 @16 kHz.  RIFF/WAV (integer and float PCM, G.711 A-law / mu-law, IMA ADPCM) needs nothing beside
-    numpy and, for another rate, scipy; other containers go through soundfile / librosa / PyAV when the host has one (the reference
+    numpy and, for another rate, scipy; a file whose content is FLAC is decoded natively by the library, whatever its name, and
+    needs nothing else either (its MD5 is checked when it carries one); other containers go through soundfile / librosa / PyAV when the host has one (the reference
     decodes with librosa / PyAV: asr_core.py:156, faster-whisper decode_audio).  channel=None averages the channels; an index takes
     that channel alone."""
     if not path.lower().endswith((".wav", ".wave")):
+        fl = _read_flac(path)
+        if fl is not None:
+            return resample(decode_coded(fl, _pick_channel(path, channel, fl.channels)), fl.rate, sampling_rate)
         # compressed containers (asr_core.py:118 also globs mp3/flac/m4a/aac): use whichever decoder the host has —
         # none is installed in the build image, so these branches are unexercised here and the error below is what
         # the folder tool records per file

@@ -329,7 +329,8 @@ def build_parser() -> argparse.ArgumentParser:
                          "whose result for a file does not depend on the other files; not together with --batched")
     ap.add_argument("--device-resample", action="store_true",
                     help="opt-in: convert, downmix and resample each group's files in one device call instead of file by file on "
-                         "the host (RIFF/WAVE of any PCM / float format, other containers through soundfile; rates the device "
+                         "the host (RIFF/WAVE of any PCM / float format; FLAC files, decoded on the device frame by frame; other "
+                         "containers through soundfile; rates the device "
                          "does not take fall back to the host path per file)")
     ap.add_argument("--audio-channel", default="mix", metavar="{mix,left,right,N}", type=_audio_channel_arg,
                     help="which channel of a multichannel file is transcribed: mix = the mean of all (default), left / right = "

@@ -4,6 +4,7 @@
 // no model weights are needed: the call's only shared resource is the context's stream.
 #include "engine_ctx.hpp"
 #include "ingest.hpp"
+#include "flac.hpp"
 
 #include <chrono>
 
@@ -15,6 +16,11 @@ constexpr size_t kIngestOutFloats = (size_t)1 << 20;  // results of one chunk sl
 constexpr int64_t kIngestMaxFrames = (int64_t)1 << 40;
 constexpr size_t kIngestScratchBytes = (size_t)8 << 20;   // decoded int16 of one IMA chunk (the stream runs chunk after chunk: one block)
 constexpr int kImaMaxBlockAlign = 65536;
+// FLAC: the decoded chunk (left-justified int16 / int32 [samples][channels]) and the lanes' int32 work rows of the same shape, each
+// 32 MiB = 16 of the largest legal frames (65535 samples x 8 channels x 4 B): a frame, and the frames the filter's halo touches on
+// both sides, always fit.  A chunk has at most kFlacMaxChunkFrames FLAC frames: one status word each, per slot.
+constexpr size_t kFlacScratchBytes = (size_t)32 << 20;
+constexpr int64_t kFlacMaxChunkFrames = 65536;
 
 static const int kPcmBytes[6] = {1, 2, 3, 4, 4, 8};   // bytes per sample of the formats, in the order of their codes
 
@@ -83,6 +89,8 @@ struct IngestState {
   char* dev = nullptr;                       // [kIngestSlots] raw | [kIngestSlots] results
   char* pinned = nullptr;                    // the same layout in pinned host memory
   int16_t* scratch = nullptr;                // kIngestScratchBytes: the decoded chunk of an IMA recording (first IMA call)
+  char* flac_dev = nullptr;                  // decoded chunk | work rows (kFlacScratchBytes each) | [kIngestSlots] status words (first FLAC call)
+  int32_t* flac_status = nullptr;            // pinned: [kIngestSlots][kFlacMaxChunkFrames] status words
   hipEvent_t done[kIngestSlots] = {};
 };
 
@@ -92,6 +100,8 @@ void ingest_free(ttasr_ctx* c) {
   if (c->ingest->dev) hipFree(c->ingest->dev);
   if (c->ingest->pinned) hipHostFree(c->ingest->pinned);
   if (c->ingest->scratch) hipFree(c->ingest->scratch);
+  if (c->ingest->flac_dev) hipFree(c->ingest->flac_dev);
+  if (c->ingest->flac_status) hipHostFree(c->ingest->flac_status);
   for (auto& e : c->ingest->done) if (e) hipEventDestroy(e);
   delete c->ingest;
   c->ingest = nullptr;
@@ -168,7 +178,10 @@ int64_t wire_final(const WirePlan& p, int64_t n_frames, bool finished) {
   return std::max<int64_t>(0, ceil_div(n_frames * p.up - p.half, p.down));
 }
 
-struct IngestPending { bool live = false; float* dst = nullptr; size_t n = 0; };
+struct IngestPending {
+  bool live = false; float* dst = nullptr; size_t n = 0;
+  int rec = 0; int64_t frame0 = 0, n_status = 0;   // FLAC: the recording, the chunk's first FLAC frame and its number of status words
+};
 
 static int ingest_scratch(ttasr_ctx* c) {
   IngestState* g = c->ingest;
@@ -178,6 +191,61 @@ static int ingest_scratch(ttasr_ctx* c) {
   return 0;
 }
 
+static int ingest_flac_scratch(ttasr_ctx* c) {
+  IngestState* g = c->ingest;
+  const size_t status = (size_t)kIngestSlots * kFlacMaxChunkFrames * 4, bytes = 2 * kFlacScratchBytes + status;
+  if (!g->flac_dev) {
+    const hipError_t e = hipMalloc((void**)&g->flac_dev, bytes);
+    if (e != hipSuccess) { g->flac_dev = nullptr; (void)hipGetLastError(); return fail(c, TTASR_E_NOMEM, "ingest FLAC scratch (%zu bytes): %s", bytes, hipGetErrorString(e)); }
+  }
+  if (!g->flac_status) {
+    const hipError_t e = hipHostMalloc((void**)&g->flac_status, status, hipHostMallocDefault);
+    if (e != hipSuccess) { g->flac_status = nullptr; (void)hipGetLastError(); return fail(c, TTASR_E_NOMEM, "ingest FLAC status words (%zu bytes): %s", status, hipGetErrorString(e)); }
+  }
+  return 0;
+}
+
+// A FLAC recording's chunks are whole FLAC frames.  Chunk [a, b) of the frame table owns the outputs whose index k satisfies
+// first sample of a <= k down / up < first sample of b; what it stages is its own frames and those the filter's halo touches.
+struct FlacCut { int64_t kb = 0, ke = 0, fa = 0, fb = -1, bytes = 0, samples = 0; bool ok = true; };
+
+struct FlacCutter {
+  const flac::Probe& B;
+  const IngestPlan& P;
+  int64_t nfr, ch;
+  int64_t n_out() const { return ceil_div(nfr * P.up, P.down); }
+  int64_t frame_of(int64_t smp) const {   // the frame that holds sample smp
+    const std::vector<flac::FrameRec>& F = B.frames;
+    int64_t lo = 0, hi = (int64_t)F.size() - 1;
+    while (lo < hi) { const int64_t m = (lo + hi + 1) / 2; if (F[m].first <= smp) lo = m; else hi = m - 1; }
+    return lo;
+  }
+  FlacCut cut(int64_t a, int64_t b) const {
+    const std::vector<flac::FrameRec>& F = B.frames;
+    FlacCut u;
+    const int64_t sb = b < (int64_t)F.size() ? F[b].first : B.samples, no = n_out();
+    u.kb = std::min(ceil_div(F[a].first * P.up, P.down), no);
+    u.ke = sb >= nfr ? no : std::min(ceil_div(sb * P.up, P.down), no);
+    if (u.ke <= u.kb) return u;
+    const int64_t lo = std::max<int64_t>(ceil_div(u.kb * P.down - P.half, P.up), 0);
+    const int64_t hi = std::min<int64_t>(floor_div((u.ke - 1) * P.down + P.half, P.up), nfr - 1);
+    u.fa = frame_of(lo); u.fb = std::max(frame_of(hi), u.fa);
+    u.samples = F[u.fb].first + F[u.fb].bs - F[u.fa].first;
+    u.bytes = F[u.fb].off + F[u.fb].len - F[u.fa].off;
+    const int64_t nt = u.fb - u.fa + 1;
+    u.ok = nt <= kFlacMaxChunkFrames && nt * (int64_t)sizeof(FlacRec) + u.bytes <= (int64_t)kIngestInBytes &&
+           u.samples * ch * 4 <= (int64_t)kFlacScratchBytes && u.ke - u.kb <= (int64_t)kIngestOutFloats;
+    return u;
+  }
+  // the first frame that does not fit the staging slots even as a chunk of its own, or -1: the chunk loop relies on there being none
+  int64_t misfit() const {
+    const std::vector<flac::FrameRec>& F = B.frames;
+    for (int64_t a = 0; a < (int64_t)F.size() && F[a].first < nfr; ++a)
+      if (!cut(a, a + 1).ok) return a;
+    return -1;
+  }
+};
+
 // The call behind both entry points.  `wave` = ttasr_ingest_wave: the coded formats are legal, n_bytes is there and checked,
 // block_align and pick may be NULL (no IMA recording / the mean everywhere).  ttasr_ingest_pcm: the three are NULL.
 static int ingest_run(ttasr_ctx* c, bool wave, int32_t n, const void* const* raw, const int64_t* n_bytes, const int64_t* n_frames,
@@ -186,18 +254,30 @@ static int ingest_run(ttasr_ctx* c, bool wave, int32_t n, const void* const* raw
   if (n < 0) return fail(c, TTASR_E_INVALID, "n %d is negative", n);
   if (n == 0) return TTASR_OK;
   if (!raw || !n_frames || !rate || !channels || !format || !out || (wave && !n_bytes)) return fail(c, TTASR_E_INVALID, "NULL argument");
-  bool any_ima = false;
+  bool any_ima = false, any_flac = false;
+  std::vector<flac::Probe> probes;           // of the FLAC recordings, by recording: STREAMINFO and the frame table of the scan
   for (int i = 0; i < n; ++i) {
     if (n_frames[i] < 0 || n_frames[i] > kIngestMaxFrames) return fail(c, TTASR_E_INVALID, "recording %d: %lld frames outside [0, 2^40]", i, (long long)n_frames[i]);
     if (channels[i] < 1 || channels[i] > 8) return fail(c, TTASR_E_INVALID, "recording %d: %d channels outside [1, 8]", i, channels[i]);
     const bool ima = wave && format[i] == TTASR_PCM_IMA4;
-    if (!is_pcm(format[i]) && !(wave && (is_g711(format[i]) || ima))) return fail(c, TTASR_E_INVALID, "recording %d: unknown sample format %d", i, format[i]);
+    const bool fl = wave && format[i] == TTASR_PCM_FLAC;
+    if (!is_pcm(format[i]) && !(wave && (is_g711(format[i]) || ima || fl))) return fail(c, TTASR_E_INVALID, "recording %d: unknown sample format %d", i, format[i]);
     if (wave) {
       const int32_t pk = pick ? pick[i] : -1;
       if (pk < -1 || pk >= channels[i]) return fail(c, TTASR_E_INVALID, "recording %d: pick %d outside [-1, %d)", i, pk, channels[i]);
       if (n_bytes[i] < 0) return fail(c, TTASR_E_INVALID, "recording %d: %lld bytes", i, (long long)n_bytes[i]);
       int64_t held;
-      if (ima) {
+      if (fl) {
+        if (!raw[i]) return fail(c, TTASR_E_INVALID, "recording %d: NULL FLAC bytes", i);
+        if (probes.empty()) probes.resize(n);
+        char why[200];
+        if (!flac::scan((const uint8_t*)raw[i], n_bytes[i], probes[i], why, (int32_t)sizeof why)) return fail(c, TTASR_E_INVALID, "recording %d: FLAC: %s", i, why);
+        const flac::Stream& si = probes[i].si;
+        if (rate[i] != si.rate || channels[i] != si.channels)
+          return fail(c, TTASR_E_INVALID, "recording %d: FLAC stream of %d Hz and %d channels given as %d Hz and %d channels", i, si.rate, si.channels, rate[i], channels[i]);
+        held = probes[i].samples;
+        any_flac = true;
+      } else if (ima) {
         if (!block_align) return fail(c, TTASR_E_INVALID, "recording %d: IMA ADPCM without block_align", i);
         const int32_t ba = block_align[i];
         if (ba < 8 * channels[i] || ba > kImaMaxBlockAlign || ba % (4 * channels[i]))
@@ -211,6 +291,12 @@ static int ingest_run(ttasr_ctx* c, bool wave, int32_t n, const void* const* raw
     }
     if (!ingest_plan(rate[i]).ok)
       return fail(c, TTASR_E_INVALID, "recording %d: rate %d is not accepted (max(up, down) of the ratio to 16000 must be at most %d)", i, rate[i], kIngestMaxR);
+    if (fl && n_frames[i] > 0) {   // every chunk of the chunk loop is known to fit before anything is enqueued
+      const IngestPlan plan = ingest_plan(rate[i]);
+      const int64_t a = FlacCutter{probes[i], plan, n_frames[i], channels[i]}.misfit();
+      if (a >= 0)
+        return fail(c, TTASR_E_INVALID, "recording %d: FLAC frame %lld (%u samples at rate %d) does not fit the staging slots", i, (long long)a, probes[i].frames[a].bs, rate[i]);
+    }
     if (n_frames[i] > 0 && (!raw[i] || !out[i])) return fail(c, TTASR_E_INVALID, "recording %d: NULL sample or output row with %lld frames", i, (long long)n_frames[i]);
   }
   TRY(session_refusal(c));
@@ -219,6 +305,7 @@ static int ingest_run(ttasr_ctx* c, bool wave, int32_t n, const void* const* raw
   IngestState* g = c->ingest;
   TRY(ingest_blocks(c));
   if (any_ima) TRY(ingest_scratch(c));
+  if (any_flac) TRY(ingest_flac_scratch(c));
   hipStream_t s = c->stream;
   char* const d_in = g->dev; char* const d_out = g->dev + kIngestSlots * kIngestInBytes;
   char* const p_in = g->pinned; char* const p_out = g->pinned + kIngestSlots * kIngestInBytes;
@@ -230,6 +317,13 @@ static int ingest_run(ttasr_ctx* c, bool wave, int32_t n, const void* const* raw
   auto retire = [&](int slot) -> int {   // the slot's results to the caller's row
     if (!pend[slot].live) return 0;
     HIPCHK(c, hipEventSynchronize(g->done[slot]));
+    pend[slot].live = false;
+    const int32_t* st = g->flac_status ? g->flac_status + (size_t)slot * kFlacMaxChunkFrames : nullptr;
+    for (int64_t k = 0; k < pend[slot].n_status; ++k)
+      if (st[k]) {   // a frame whose content is illegal although its CRC holds: nothing of the call stays in flight
+        (void)hipStreamSynchronize(s);
+        return fail(c, TTASR_E_INVALID, "recording %d: FLAC frame %lld: %s", pend[slot].rec, (long long)(pend[slot].frame0 + k), flac::status_text(st[k]));
+      }
     const auto t0 = clk::now();
     memcpy(pend[slot].dst, p_out + (size_t)slot * kIngestOutFloats * 4, pend[slot].n * 4);
     ms[0] += since(t0);
@@ -237,10 +331,73 @@ static int ingest_run(ttasr_ctx* c, bool wave, int32_t n, const void* const* raw
     return 0;
   };
   int64_t job = 0;
+  // A FLAC recording, chunk after chunk (FlacCutter): the frames a chunk's outputs read go up as one byte range (frames lie back
+  // to back in the file) behind their table, the pre-pass decodes them into the scratch block, and the filter kernel reads that
+  // as s16 / s32.
+  auto run_flac = [&](int i, const IngestFilter* f) -> int {
+    const IngestPlan& P = f->plan;
+    const flac::Probe& B = probes[i];
+    const std::vector<flac::FrameRec>& F = B.frames;
+    const int64_t NF = (int64_t)F.size(), nfr = n_frames[i];
+    const int fmt = B.si.bits <= 16 ? TTASR_PCM_S16 : TTASR_PCM_S32;
+    const FlacCutter cutter{B, P, nfr, channels[i]};
+    const int64_t target = c->ingest_chunk > 0 ? c->ingest_chunk : INT64_MAX;   // rounded up to whole FLAC frames
+    for (int64_t a = 0, b; a < NF && F[a].first < nfr; a = b) {
+      b = a + 1;
+      FlacCut u = cutter.cut(a, b);   // fits: the validation above saw to it
+      while (b < NF && F[b].first < nfr && F[b].first - F[a].first < target) {
+        const FlacCut v = cutter.cut(a, b + 1);
+        if (!v.ok) break;
+        u = v; ++b;
+      }
+      if (u.ke <= u.kb) continue;
+      const int slot = (int)(job % kIngestSlots);
+      ++job;
+      TRY(retire(slot));
+      const int64_t nt = u.fb - u.fa + 1, tbytes = nt * (int64_t)sizeof(FlacRec);
+      char* const pin = p_in + (size_t)slot * kIngestInBytes;
+      char* const din = d_in + (size_t)slot * kIngestInBytes;
+      auto t0 = clk::now();
+      FlacRec* recs = (FlacRec*)pin;
+      for (int64_t k = 0; k < nt; ++k) {
+        const flac::FrameRec& r = F[u.fa + k];
+        recs[k] = FlacRec{(uint32_t)(r.off - F[u.fa].off), (uint32_t)r.len, (uint32_t)(r.first - F[u.fa].first), r.bs};
+      }
+      memcpy(pin + tbytes, (const char*)raw[i] + F[u.fa].off, (size_t)u.bytes);
+      ms[0] += since(t0);
+      t0 = clk::now();
+      HIPCHK(c, hipMemcpyAsync(din, pin, (size_t)(tbytes + u.bytes), hipMemcpyHostToDevice, s));
+      if (timing) { HIPCHK(c, hipStreamSynchronize(s)); ms[1] += since(t0); t0 = clk::now(); }
+      int32_t* const d_status = (int32_t*)(g->flac_dev + 2 * kFlacScratchBytes) + (size_t)slot * kFlacMaxChunkFrames;
+      FlacJob D;
+      D.raw = (const uint8_t*)(din + tbytes); D.table = (const FlacRec*)din;
+      D.out = g->flac_dev; D.work = (int32_t*)(g->flac_dev + kFlacScratchBytes); D.status = d_status;
+      D.raw_bytes = u.bytes; D.cap_samples = u.samples;
+      D.n_frames = (int32_t)nt; D.rate = B.si.rate; D.channels = B.si.channels; D.bits = B.si.bits;
+      launch_flac_decode(D, s);
+      IngestJob J;
+      J.raw = (const uint8_t*)g->flac_dev;
+      J.out = (float*)(d_out + (size_t)slot * kIngestOutFloats * 4);
+      J.taps = f->dev;
+      J.n_frames = nfr; J.f0 = F[u.fa].first; J.k_begin = u.kb; J.nf = (int32_t)u.samples; J.n_out = (int32_t)(u.ke - u.kb);
+      J.up = P.up; J.down = P.down; J.half = P.half; J.L = P.L; J.channels = channels[i]; J.format = fmt;
+      J.tile = P.tile; J.span = P.span; J.pick = pick ? pick[i] : -1;
+      launch_ingest(J, s);
+      if (timing) { HIPCHK(c, hipStreamSynchronize(s)); ms[2] += since(t0); t0 = clk::now(); }
+      HIPCHK(c, hipMemcpyAsync(p_out + (size_t)slot * kIngestOutFloats * 4, J.out, (size_t)J.n_out * 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(c, hipMemcpyAsync(g->flac_status + (size_t)slot * kFlacMaxChunkFrames, d_status, (size_t)nt * 4, hipMemcpyDeviceToHost, s));
+      if (timing) { HIPCHK(c, hipStreamSynchronize(s)); ms[3] += since(t0); }
+      HIPCHK(c, hipEventRecord(g->done[slot], s));
+      pend[slot].live = true; pend[slot].dst = out[i] + u.kb; pend[slot].n = (size_t)J.n_out;
+      pend[slot].rec = i; pend[slot].frame0 = u.fa; pend[slot].n_status = nt;
+    }
+    return 0;
+  };
   for (int i = 0; i < n; ++i) {
     if (n_frames[i] == 0) continue;
     const IngestFilter* f = nullptr;
     TRY(ingest_filter_dev(c, rate[i], &f));
+    if (format[i] == TTASR_PCM_FLAC) { TRY(run_flac(i, f)); continue; }
     const IngestPlan& P = f->plan;
     const bool ima = format[i] == TTASR_PCM_IMA4;
     const int64_t ba = ima ? block_align[i] : 0, spb = ima ? ima_spb((int)ba, channels[i]) : 1;
@@ -309,7 +466,7 @@ static int ingest_run(ttasr_ctx* c, bool wave, int32_t n, const void* const* raw
       HIPCHK(c, hipMemcpyAsync(p_out + (size_t)slot * kIngestOutFloats * 4, J.out, (size_t)J.n_out * 4, hipMemcpyDeviceToHost, s));
       if (timing) { HIPCHK(c, hipStreamSynchronize(s)); ms[3] += since(t0); }
       HIPCHK(c, hipEventRecord(g->done[slot], s));
-      pend[slot].live = true; pend[slot].dst = out[i] + kb; pend[slot].n = (size_t)J.n_out;
+      pend[slot].live = true; pend[slot].dst = out[i] + kb; pend[slot].n = (size_t)J.n_out; pend[slot].n_status = 0;
     }
   }
   for (int64_t k = 0; k < kIngestSlots; ++k) TRY(retire((int)((job + k) % kIngestSlots)));   // oldest first

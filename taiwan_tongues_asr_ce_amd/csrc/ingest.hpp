@@ -16,7 +16,8 @@ constexpr int kIngestMaxTile = 4096;         // outputs per workgroup, at most
 // (interleaved, in the file's sample format).  Frames outside [0, n_frames) are zeros; a frame inside the recording but outside
 // the staged range reads as zero as well (the host never asks for one: the guard keeps a wrong host off foreign memory).
 // pick = -1: the mean of the channels; pick = c: channel c as it is.  The formats are the six TTASR_PCM_* sample formats and the
-// two G.711 codes; an IMA recording arrives here as the TTASR_PCM_S16 its pre-pass wrote.
+// two G.711 codes; an IMA recording arrives here as the TTASR_PCM_S16 its pre-pass wrote, a FLAC recording as the TTASR_PCM_S16 or
+// TTASR_PCM_S32 of its pre-pass.
 struct IngestJob {
   const uint8_t* raw;      // device, staged frames
   float* out;              // device, n_out floats
@@ -59,3 +60,21 @@ struct ImaJob {
 inline int ima_spb(int block_align, int channels) { return 1 + 2 * (block_align / channels - 4); }
 
 void launch_ima_decode(const ImaJob& j, hipStream_t s);
+
+// The FLAC pre-pass: one lane per FLAC frame runs flac.hpp's decode body.  Entry t of `table` (device) is frame t of the staged
+// range: its bytes are raw[off .. off + len), its samples go to frame s0 .. s0 + bs of `out` - left-justified int16 (bits <= 16)
+// or int32 [samples][channels] - through the lane's part of `work` (int32 [channels][bs] at work + s0 * channels), and its status
+// word (flac.hpp; 0 = ok) to status[t], an ordinary store.  A table entry that leaves raw_bytes or cap_samples is not decoded.
+struct FlacRec { uint32_t off, len, s0, bs; };
+struct FlacJob {
+  const uint8_t* raw;      // device, the staged frames' bytes
+  const FlacRec* table;    // device, n_frames entries
+  int32_t* work;           // device, cap_samples * channels int32
+  void* out;               // device, cap_samples * channels int16 / int32
+  int32_t* status;         // device, n_frames words
+  int64_t raw_bytes, cap_samples;
+  int32_t n_frames, rate, channels, bits;
+};
+constexpr int kFlacThreads = 64;             // one wave per workgroup: the frames of a chunk spread over the CUs
+
+void launch_flac_decode(const FlacJob& j, hipStream_t s);

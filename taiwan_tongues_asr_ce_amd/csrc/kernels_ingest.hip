@@ -11,6 +11,12 @@
 //                   predictor and step index - and writes int16 [frames][channels]; ingest_kernel then reads that as s16.  Lane t
 //                   takes block t % n_blocks of channel t / n_blocks: consecutive lanes read consecutive blocks of one channel.
 //
+//   flac_decode_kernel  the pre-pass of FLAC recordings: one lane per FLAC frame runs the decode body of flac.hpp - the one the
+//                   host decoder runs - over its frame's bytes: header, subframes (Rice residual, predictor recurrence) into the
+//                   lane's int32 work rows, then decorrelation and the left-justified interleaved store; ingest_kernel reads that
+//                   as s16 or s32.  A frame is a serial bit stream, so the frame is the unit of parallelism; the lane's status
+//                   word goes out with an ordinary store.  64-thread workgroups, so that a chunk's frames spread over the CUs.
+//
 //   wire_kernel     ingest_kernel for wire streams (ttasr_vad_stream_push_wire): ONE launch for all rows of
 //                   a push chunk, the jobs in a device table, the span staged from the stream's history in a device table and
 //                   then from the new frames, the same sum; one more workgroup per row writes the row's new history into the
@@ -22,6 +28,7 @@
 // minutes of 44.1 kHz audio.
 #include "common.hpp"
 #include "ingest.hpp"
+#include "flac.hpp"
 
 namespace {
 
@@ -222,6 +229,20 @@ __global__ __launch_bounds__(kIngestThreads) void ima_decode_kernel(const ImaJob
   }
 }
 
+__global__ __launch_bounds__(kFlacThreads) void flac_decode_kernel(const FlacJob J) {
+  const int t = (int)(blockIdx.x * kFlacThreads + threadIdx.x);
+  if (t >= J.n_frames) return;
+  const FlacRec r = J.table[t];
+  int32_t e = flac::kHeader;
+  if ((int64_t)r.off + r.len <= J.raw_bytes && (int64_t)r.s0 + r.bs <= J.cap_samples && r.bs >= 1) {
+    const flac::Stream si{J.rate, J.channels, J.bits};
+    const size_t at = (size_t)r.s0 * J.channels;
+    if (J.bits <= 16) e = flac::decode_frame(J.raw + r.off, r.len, si, r.bs, J.work + at, (int16_t*)J.out + at, flac::kStoreS16);
+    else e = flac::decode_frame(J.raw + r.off, r.len, si, r.bs, J.work + at, (int32_t*)J.out + at, flac::kStoreS32);
+  }
+  J.status[t] = e;
+}
+
 }  // namespace
 
 void launch_ingest(const IngestJob& j, hipStream_t s) {
@@ -261,4 +282,15 @@ void launch_ima_decode(const ImaJob& j, hipStream_t s) {
   }
   const int64_t lanes = (int64_t)j.n_blocks * j.channels;
   ima_decode_kernel<<<(unsigned)((lanes + kIngestThreads - 1) / kIngestThreads), kIngestThreads, 0, s>>>(j);
+}
+
+void launch_flac_decode(const FlacJob& j, hipStream_t s) {
+  if (j.n_frames <= 0) return;
+  if (j.channels < 1 || j.channels > 8 || j.bits < 4 || j.bits > 24 || j.raw_bytes < 0 || j.cap_samples < 1 || !j.raw || !j.table ||
+      !j.work || !j.out || !j.status || ((uintptr_t)j.table & 3)) {
+    launch_fault("flac decode: %d frames, %d channels, %d bits, %lld bytes, %lld samples", j.n_frames, j.channels, j.bits,
+                 (long long)j.raw_bytes, (long long)j.cap_samples);
+    return;
+  }
+  flac_decode_kernel<<<(unsigned)((j.n_frames + kFlacThreads - 1) / kFlacThreads), kFlacThreads, 0, s>>>(j);
 }

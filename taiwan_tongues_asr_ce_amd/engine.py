@@ -273,7 +273,10 @@ class Engine:
         The coded formats (_lib.PCM_ALAW, PCM_ULAW, PCM_IMA4; block_aligns[i] = the file's block size for IMA, whose trailing
         bytes short of a block are ignored), picks (None / -1 = the mean of the channels, c = channel c alone) and n_frames (a
         frame count below what the bytes hold: an IMA file's `fact`) go through ttasr_ingest_wave; a call without any of them
-        is ttasr_ingest_pcm, as before."""
+        is ttasr_ingest_pcm, as before.
+        A FLAC recording (_lib.PCM_FLAC) is the whole file as read, tags and metadata included, with the stream's own rate and
+        channel count; its frame count comes from the library's probe (ttasr_flac_probe) unless n_frames[i] gives a smaller one,
+        and a stream the library refuses raises TtasrError with the library's reason."""
         n = len(raws)
         if not (len(rates) == len(channels) == len(formats) == n):
             raise ValueError("raws, rates, channels and formats must have one entry per recording")
@@ -286,7 +289,13 @@ class Engine:
         for i, r in enumerate(raws):
             b = np.frombuffer(r, dtype=np.uint8) if isinstance(r, (bytes, bytearray, memoryview)) else np.ascontiguousarray(r).reshape(-1).view(np.uint8)
             ch, fmt = int(channels[i]), int(formats[i])
-            if fmt == _lib.PCM_IMA4:
+            if fmt == _lib.PCM_FLAC:      # the whole file as read: the samples held come from the probe, unless the caller has them
+                if n_frames is None or n_frames[i] is None:
+                    try:
+                        frames[i] = _lib.flac_probe(b).samples
+                    except ValueError as e:
+                        raise TtasrError(f"ingest_wave: recording {i}: {e}") from None
+            elif fmt == _lib.PCM_IMA4:
                 bal[i] = int(block_aligns[i]) if block_aligns is not None and block_aligns[i] is not None else 0
                 ok = ch > 0 and bal[i] >= 8 * ch and bal[i] % (4 * ch) == 0       # otherwise the library refuses the call with a message
                 frames[i] = len(b) // int(bal[i]) * (1 + 2 * (int(bal[i]) // ch - 4)) if ok else len(b)

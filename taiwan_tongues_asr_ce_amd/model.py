@@ -292,7 +292,7 @@ class WhisperModel:
     # -- file ingest on the device --------------------------------------------------------------------
     def decode_audio_many(self, paths_or_arrays: Sequence[Union[str, np.ndarray]], audio_channel=None) -> List[np.ndarray]:
         """Every path -> mono float32 @16 kHz with ONE device call for all the files the device takes (read_audio_coded +
-        Engine.ingest on the calling thread's engine context: conversion or G.711 / IMA ADPCM decoding, downmix and the
+        Engine.ingest on the calling thread's engine context: conversion or G.711 / IMA ADPCM / FLAC decoding, downmix and the
         polyphase resampler run on the device over the whole batch).  Every path is read once: a file the device does not take
         - a rate outside the accepted ratios, more than 8 channels, or any file on an engine without `ingest` - is decoded on
         the host from what was read, as decode_audio does it; a container read_audio_coded has no reader for goes through
