@@ -836,6 +836,71 @@ TTASR_API int ttasr_vad_stream_push_wire(ttasr_ctx* ctx, int32_t n, const int32_
                                          const int32_t* finish, float* const* out_pcm_host, const int64_t* out_pcm_cap, int64_t* out_pcm_len,
                                          float* const* out_probs_host, float* const* out_logits_host, int32_t* out_frames);
 
+/* ---- segmentation VAD: the PyanNet-shaped network (the streaming server's PyannoteVAD, pyannote_vad.py:12-62, which runs
+ * pyannote/segmentation under VoiceActivityDetection(onset 0.5, offset 0.5, min_duration_on 0.3, min_duration_off 0.3)) ----------- */
+/* UNPINNED against the published pyannote/segmentation checkpoint: neither pyannote.audio nor the checkpoint exists offline, so
+ * the tensor names, the ParamSincFB filter formula, the Hamming aggregation window and the Binarize rules are restated from
+ * memory, and the network is held to a float64 restatement of THIS text on synthetic weights.
+ *
+ * The network (PyanNet defaults; all arithmetic f32 on the device in every compute mode).  Input: 16 kHz mono float32, in chunks
+ * of 80 000 samples; chunk k starts at sample 8 000 k; a recording of n samples has K(n) = 0 chunks for n = 0, 1 for n <= 80 000,
+ * else 1 + ceil((n - 80 000) / 8 000); the last chunk is zero-padded.  Per chunk (every norm: biased variance, eps 1e-5):
+ *   1. InstanceNorm1d(1, affine) over the chunk;
+ *   2. sinc convolution 1 -> 80 channels, kernel 251, stride 10, no bias, with the materialised filters [80,1,251] (the host
+ *      builds them in float64 from the checkpoint's 40 low_hz_ / band_hz_ pairs: min_low_hz = min_band_hz = 50, 125-point half
+ *      Hamming window, 40 cosine then 40 sine filters, each divided by twice its band), then abs: 80 000 -> 7 975;
+ *   3. MaxPool1d(3,3) -> 2 658, InstanceNorm1d(80, affine), leaky_relu(0.01);
+ *   4. Conv1d(80 -> 60, k 5) -> 2 654, pool 3 -> 884, InstanceNorm1d(60, affine), leaky_relu;
+ *   5. Conv1d(60 -> 60, k 5) -> 880, pool 3 -> 293 frames, InstanceNorm1d(60, affine), leaky_relu;
+ *   6. LSTM, input 60, hidden 128, 4 layers, bidirectional, gates i, f, g, o with bias_ih + bias_hh, layers 1-3 on the 256-wide
+ *      forward | backward concatenation, zero initial state per chunk;
+ *   7. Linear(256 -> 128), leaky_relu, Linear(128 -> 128), leaky_relu, Linear(128 -> C), sigmoid; C in [1, 8] = classifier.weight's
+ *      first dimension.
+ * A frame's receptive field is 991 samples and its step 270: frame j is centred on sample 495 + 270 j.  The speech score of a
+ * chunk frame is the maximum over its C classes.  Aggregation (deterministic overlap-add): chunk k's frame f lands on recording
+ * frame s(k) + f, s(k) = (8 000 k + 135) / 270 in integer division; score[j] = sum_k w[f] p_k[f] / sum_k w[f] over the chunks
+ * that cover j, k ascending, w = hamming(293) = 0.54 - 0.46 cos(2 pi f / 292) rounded to f32; a recording has
+ * F(n) = min(ceil(n / 270), s(K - 1) + 293) frames.
+ *
+ * ttasr_seg_load_tensor: one tensor, float32 host data, PyanNet state-dict name: sincnet.wav_norm1d.weight | bias [1];
+ *   sincnet.conv1d.0.filters [80,1,251] (derived, see 2.); sincnet.norm1d.{0,1,2}.weight | bias [80] [60] [60];
+ *   sincnet.conv1d.1.weight [60,80,5], .bias [60]; sincnet.conv1d.2.weight [60,60,5], .bias [60];
+ *   lstm.weight_ih_l{0..3}[_reverse] [512,60] (layer 0) / [512,256]; lstm.weight_hh_l*[_reverse] [512,128];
+ *   lstm.bias_ih_l*[_reverse], lstm.bias_hh_l*[_reverse] [512]; linear.0.weight [128,256], linear.1.weight [128,128], their .bias
+ *   [128]; classifier.weight [C,128], classifier.bias [C]: 51 tensors.  Unknown name or wrong shape: TTASR_E_WEIGHTS.  After
+ *   ttasr_seg_finalize, and in an open session: TTASR_E_INVALID.  The weights (5.9 MB) belong to THIS context.
+ * ttasr_seg_finalize: TTASR_E_WEIGHTS when a tensor is missing or the classifier's weight and bias disagree on C; afterwards the
+ *   weights are read-only.  ttasr_seg_classes: C of the finalized network (TTASR_E_INVALID before).
+ * ttasr_seg_chunks / ttasr_seg_frames: K(n) and F(n); no context; negative for n outside [0, 2^40].
+ * ttasr_seg_scores: n recordings, recording i = pcm_host[i][0 .. n_samples[i]); out_scores_host[i] receives F(n_i) floats.  The
+ *   two optional arrays are the known-answer hooks: row i of out_chunk_probs_host / out_chunk_logits_host, when the array is not
+ *   NULL, receives [K_i][293][C] per-class probabilities / pre-sigmoid logits.  A recording of 0 samples is legal and writes
+ *   nothing (its pointers may be NULL).  Refused with TTASR_E_INVALID before anything is enqueued, the context stays usable:
+ *   weights not finalized; n outside [1, max_batch]; a NULL array; a NULL pcm or output row with samples; a length outside
+ *   [0, 2^40]; an open session; a call already in flight on the context.
+ *   Work proceeds in groups of at most TTASR_SEG_GROUP chunks - the recordings in call order, chunks ascending - and every
+ *   kernel's form is a function of the chunk only: a chunk's 293 x C values depend on its 80 000 samples alone, bit for bit - not
+ *   on the recording it is cut from, the other recordings of the call, its place in the call, the group it runs in, the compute
+ *   mode or option "seg_lstm_rows" - and a frame's score on its covering chunks, summed in ascending order.
+ *   Device scratch: ONE block owned by the context, allocated by the first call, never a function of the recordings' lengths,
+ *   freed by ttasr_destroy: per chunk of a group 4 x (80 000 PCM + 80 x 2 658 + 60 x 884 + 60 x 293 stage outputs + 2 x 293 x 512
+ *   gate inputs + 2 x 293 x 256 layer outputs + 2 x 293 x 8 head outputs + 293 scores + 326 aggregated frames) + 1 664 bytes of
+ *   statistics and tables = 3 276 124 bytes, times TTASR_SEG_GROUP, + 10 x 293 x 4 (the scores of the chunks in front of a group)
+ *   + 293 x 4 (the window), every region rounded up to 256 bytes: 200 MiB.  Host PCM goes through a pinned staging block of
+ *   TTASR_SEG_GROUP x 320 000 bytes (+ the group's tables and results, 21 MiB in all), allocated by the first call as well.
+ *   A block that cannot be allocated: TTASR_E_NOMEM, the context stays usable.
+ *   The call touches no mel, encoder, search, graph, session or Silero state: a ttasr_generate* or ttasr_vad_probs after it is
+ *   bit-identical to one without it. */
+#define TTASR_SEG_GROUP 64
+#define TTASR_SEG_CHUNK_FRAMES 293
+TTASR_API int ttasr_seg_load_tensor(ttasr_ctx* ctx, const char* name, const float* data_host, const int64_t* dims, int32_t ndim);
+TTASR_API int ttasr_seg_finalize(ttasr_ctx* ctx);
+TTASR_API int ttasr_seg_classes(ttasr_ctx* ctx);
+TTASR_API int64_t ttasr_seg_chunks(int64_t n_samples);
+TTASR_API int64_t ttasr_seg_frames(int64_t n_samples);
+TTASR_API int ttasr_seg_scores(ttasr_ctx* ctx, int32_t n, const float* const* pcm_host, const int64_t* n_samples,
+                               float* const* out_scores_host, float* const* out_chunk_probs_host, float* const* out_chunk_logits_host);
+
 /* ---- kernel-selection overrides (tests, A/B measurements) ----------------------------------------- */
 /* The release library reads NO environment variable; every deviation from the measured configuration is an explicit call.
  * Keys (value 0 / 1 unless stated; defaults in brackets): "flash" [1] MFMA flash attention in the encoder (0: the
@@ -875,7 +940,9 @@ TTASR_API int ttasr_vad_stream_push_wire(ttasr_ctx* ctx, int32_t n, const int32_
  * share of the pools holds (results do not depend on it either); "ingest_timing" [0] 1: ttasr_ingest_pcm
  * waits for every copy and kernel before it enqueues the next and leaves the host-clock split of the call in ttasr_phase_ms
  * (measurement only: the waits cost the overlap);
- * Drops the captured decode graphs (except "enc_kernel_timing", "refill_overlap", "session_prefill", "align_packed", "ingest_chunk", "wire_chunk" and "ingest_timing").  Unknown key or value out of range: TTASR_E_INVALID. */
+ * "seg_lstm_rows" [0] chunks per recurrence workgroup of ttasr_seg_scores: 0 = the measured choice, 1 | 2 | 4 force that form
+ * (bit-identical: a gate row's summation order does not depend on it; A/B);
+ * Drops the captured decode graphs (except "enc_kernel_timing", "refill_overlap", "session_prefill", "align_packed", "ingest_chunk", "wire_chunk", "ingest_timing" and "seg_lstm_rows").  Unknown key or value out of range: TTASR_E_INVALID. */
 TTASR_API int ttasr_set_option(ttasr_ctx* ctx, const char* key, int32_t value);
 
 /* ---- measurement --------------------------------------------------------------------------------- */

@@ -25,6 +25,7 @@ SYMBOLS = [
     "ttasr_ingest_len", "ttasr_ingest_filter", "ttasr_ingest_pcm", "ttasr_ingest_wave",
     "ttasr_ingest_stream_len", "ttasr_vad_stream_open_wire", "ttasr_vad_stream_push_wire",
     "ttasr_flac_probe", "ttasr_flac_frames", "ttasr_flac_decode",
+    "ttasr_seg_load_tensor", "ttasr_seg_finalize", "ttasr_seg_classes", "ttasr_seg_chunks", "ttasr_seg_frames", "ttasr_seg_scores",
 ]
 
 PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = range(6)   # TTASR_PCM_* of include/ttasr.h
@@ -33,6 +34,8 @@ PCM_ALAW, PCM_ULAW, PCM_IMA4 = 16, 17, 18                         # the coded fo
 PCM_FLAC = 32                                                     # a whole FLAC file as read (ttasr_ingest_wave, ttasr_flac_*)
 CODED_BYTES = {PCM_ALAW: 1, PCM_ULAW: 1}                          # bytes per sample of the G.711 codes (IMA: 4 bits, in blocks)
 VAD_MAX_STREAMS = 1024    # TTASR_VAD_MAX_STREAMS of include/ttasr.h: open streams of one context (ttasr_vad_stream_*)
+SEG_GROUP = 64            # TTASR_SEG_GROUP of include/ttasr.h: chunks of one pass of ttasr_seg_scores through its kernels
+SEG_CHUNK_FRAMES = 293    # TTASR_SEG_CHUNK_FRAMES: frames of one 80 000-sample chunk of the segmentation network
 VAD_CHUNK_FRAMES = 1024   # TTASR_VAD_CHUNK_FRAMES of include/ttasr.h: frames of one recording per time chunk of ttasr_vad_probs
 
 
@@ -155,10 +158,18 @@ def load() -> C.CDLL:
     lib.ttasr_flac_frames.restype = i64
     lib.ttasr_flac_decode.argtypes = [vp, i64, i32p, i64, C.c_char_p, i32]
     lib.ttasr_flac_decode.restype = i64
+    lib.ttasr_seg_load_tensor.argtypes = [vp, C.c_char_p, vp, i64p, i32]
+    lib.ttasr_seg_finalize.argtypes = [vp]
+    lib.ttasr_seg_classes.argtypes = [vp]
+    lib.ttasr_seg_chunks.argtypes = [i64]
+    lib.ttasr_seg_chunks.restype = i64
+    lib.ttasr_seg_frames.argtypes = [i64]
+    lib.ttasr_seg_frames.restype = i64
+    lib.ttasr_seg_scores.argtypes = [vp, i32, C.POINTER(vp), i64p, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     for s in SYMBOLS:
         f = getattr(lib, s)
         if s not in ("ttasr_destroy", "ttasr_last_error", "ttasr_version", "ttasr_ingest_len", "ttasr_ingest_filter",
-                     "ttasr_ingest_stream_len", "ttasr_flac_frames", "ttasr_flac_decode"):
+                     "ttasr_ingest_stream_len", "ttasr_flac_frames", "ttasr_flac_decode", "ttasr_seg_chunks", "ttasr_seg_frames"):
             f.restype = C.c_int
     _lib = lib
     return lib

@@ -150,6 +150,7 @@ void ttasr_destroy(ttasr_ctx* c) {
   for (void* p : c->allocs) hipFree(p);
   if (c->align_dev) hipFree(c->align_dev);
   vad_free(c);
+  seg_free(c);
   ingest_free(c);
   if (c->pinned_i32) hipHostFree(c->pinned_i32);
   if (c->pinned_beam) hipHostFree(c->pinned_beam);

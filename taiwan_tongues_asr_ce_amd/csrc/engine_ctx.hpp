@@ -41,6 +41,7 @@ struct Slot {              // where one named tensor lands on the device
 };
 
 struct Session;            // continuous-batching session state (engine_refill.hip)
+struct SegState;           // segmentation network: weights, scratch and staging of one context (engine_seg.hip)
 struct VadState;           // voice-activity network: weights, scratch, staging and streams of one context (engine_vad.hip)
 struct IngestState;        // file ingest: tap tables per rate, the chunk slots and the IMA scratch of one context (engine_ingest.hip)
 // What run_decode_rows reads about the rows of a step, and (with the batch, the mode and the e4m3 state) what a captured step
@@ -189,6 +190,10 @@ struct ttasr_ctx {
   // host-clock phase split in phase_ms
   ttasr_detail::IngestState* ingest = nullptr;
   int ingest_chunk = 0; bool ingest_timing = false;
+  // segmentation network (engine_seg.hip): created by the first ttasr_seg_load_tensor, freed by ttasr_destroy.  Option seg_lstm_rows:
+  // chunks per recurrence workgroup (0: the measured choice; 1, 2, 4 force one; results identical)
+  ttasr_detail::SegState* seg = nullptr;
+  int seg_lstm_rows = 0;
   int wire_chunk = 0;       // option wire_chunk: input frames of a row per internal chunk of ttasr_vad_stream_push_wire (0: what the pools hold)
 
   int B_mel = 0, B_enc = 0, B_dec = 0;
@@ -401,6 +406,9 @@ int align_packed_run(ttasr_ctx* c, const AlignBatch& a, const int32_t* slot, con
 
 // ---- engine_vad.hip: the voice-activity network (ttasr_vad_*) ----
 void vad_free(ttasr_ctx* c);         // ttasr_destroy: the scratch block, the pinned staging and the streams' table (the weights live in the arenas)
+
+// ---- engine_seg.hip: the segmentation network (ttasr_seg_*) ----
+void seg_free(ttasr_ctx* c);         // ttasr_destroy: the scratch block and the pinned staging (the weights live in the arenas)
 
 // ---- engine_ingest.hip: file ingest (ttasr_ingest_*) ----
 void ingest_free(ttasr_ctx* c);      // ttasr_destroy: the tap tables, the device and pinned chunk slots and their events

@@ -75,6 +75,11 @@ int set_option(ttasr_ctx* c, const std::string& key, int v) {
     c->wire_chunk = v;
     return 0;
   }
+  if (key == "seg_lstm_rows") {     // which recurrence form ttasr_seg_scores launches (bit-identical): the graphs stay
+    if (v != 0 && v != 1 && v != 2 && v != 4) return 1;
+    c->seg_lstm_rows = v;
+    return 0;
+  }
   if (key == "ingest_timing") { c->ingest_timing = on; return 0; }   // measurement only
   if (key == "flash") c->no_flash = !on;
   else if (key == "prefill") c->no_prefill = !on;

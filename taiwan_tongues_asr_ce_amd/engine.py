@@ -80,6 +80,8 @@ class Engine:
         self.special = SpecialTokens.for_vocab(dims.vocab)
         self.audio_ctx = dims.n_audio_ctx
         self.has_vad = False   # load_vad() has put the VAD network on this context
+        self.has_segmentation = False   # load_segmentation() has put the segmentation network on this context
+        self.seg_classes = 0
         self._wire_streams = {}   # wire stream id -> (rate, bytes per frame, samples a finish releases): sizes vad_stream_push_wire's result rows
 
     # -- plumbing ------------------------------------------------------------------------------
@@ -147,6 +149,47 @@ class Engine:
             ns = np.asarray([len(a) for a in pcm[sl]], dtype=np.int64)
             self._check(self.lib.ttasr_vad_probs(self.h, n, ptrs, ns.ctypes.data_as(C.POINTER(C.c_int64)), outs, louts), "vad_probs")
         return (probs, logits) if return_logits else probs
+
+    # -- segmentation VAD (the PyanNet-shaped network) ---------------------------------------------
+    def load_segmentation(self, weights):
+        """The PyanNet-shaped segmentation network of this context (ttasr_seg_load_tensor + ttasr_seg_finalize): a mapping, or
+        (name, array) pairs, with the names and shapes of vad.PYANNET_TENSORS (vad.load_pyannet_state builds the sinc filters
+        from a checkpoint's cutoffs).  Every context holds its own copy."""
+        items = weights.items() if hasattr(weights, "items") else weights
+        for name, arr in items:
+            a = np.ascontiguousarray(arr, dtype=np.float32)
+            dims = (C.c_int64 * max(a.ndim, 1))(*a.shape)
+            self._check(self.lib.ttasr_seg_load_tensor(self.h, str(name).encode(), _ptr(a), dims, a.ndim), f"seg_load_tensor({name})")
+        self._check(self.lib.ttasr_seg_finalize(self.h), "seg_finalize")
+        self.seg_classes = int(self.lib.ttasr_seg_classes(self.h))
+        self.has_segmentation = True
+
+    def segmentation_scores(self, audios: Sequence[np.ndarray], return_chunks: bool = False):
+        """The aggregated speech score per 270-sample frame of every recording (ttasr_seg_scores): a list of float32 arrays of
+        ttasr_seg_frames(len) entries.  return_chunks=True: (scores, probabilities, logits), the last two per recording as
+        float32 [chunks, 293, classes] - what every 80 000-sample chunk gave before the overlap-add.  More recordings than
+        max_batch go through several calls; a recording's values do not depend on its neighbours."""
+        if not getattr(self, "has_segmentation", False):
+            raise TtasrError("no segmentation network on this engine: load_segmentation first")
+        pcm = []
+        for i, a in enumerate(audios):
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.ndim != 1:
+                raise ValueError(f"recording {i}: PCM must be one-dimensional, got shape {a.shape}")
+            pcm.append(a)
+        ncls = self.seg_classes
+        scores = [np.zeros(self.lib.ttasr_seg_frames(len(a)), dtype=np.float32) for a in pcm]
+        shapes = [(self.lib.ttasr_seg_chunks(len(a)), _lib.SEG_CHUNK_FRAMES, ncls) for a in pcm]
+        probs = [np.zeros(s, dtype=np.float32) for s in shapes] if return_chunks else None
+        logits = [np.zeros(s, dtype=np.float32) for s in shapes] if return_chunks else None
+        rows = lambda arrs: (C.c_void_p * len(arrs))(*[a.ctypes.data if a.size else None for a in arrs])   # noqa: E731
+        for i0 in range(0, len(pcm), self.max_batch):
+            sl = slice(i0, i0 + self.max_batch)
+            ns = np.asarray([len(a) for a in pcm[sl]], dtype=np.int64)
+            self._check(self.lib.ttasr_seg_scores(self.h, len(ns), rows(pcm[sl]), ns.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                  rows(scores[sl]), rows(probs[sl]) if return_chunks else None,
+                                                  rows(logits[sl]) if return_chunks else None), "seg_scores")
+        return (scores, probs, logits) if return_chunks else scores
 
     # -- streaming voice activity detection --------------------------------------------------------
     def vad_stream_open(self, wire=None) -> int:

@@ -225,6 +225,186 @@ def load_silero_state(path_or_mapping) -> Dict[str, np.ndarray]:
     return out
 
 
+# The PyanNet-shaped segmentation network the engine runs on the device (include/ttasr.h ttasr_seg_*):
+# THE name / shape table of the Python side, "C" standing for the number of classes (1 ... 8, classifier.weight's first
+# dimension).  UNPINNED against the published pyannote/segmentation checkpoint: the tensor names, the ParamSincFB filter formula
+# (sinc_filters), the aggregation window and the Binarize rules (pyannote_speech_timestamps) are restated from memory - neither
+# pyannote.audio nor the checkpoint exists offline - and the network is held to the float64 restatement of
+# tests/pyannet_reference.py on synthetic weights.  "sincnet.conv1d.0.filters" is DERIVED: load_pyannet_state builds it from the
+# checkpoint's sincnet.conv1d.0.filterbank.low_hz_ / band_hz_ [40, 1].
+PYANNET_CHUNK, PYANNET_STEP, PYANNET_FRAMES = 80000, 8000, 293      # samples of a chunk, between chunk starts; frames of a chunk
+PYANNET_FRAME_STEP, PYANNET_FRAME_CENTRE = 270, 495                 # frame j is centred on sample 495 + 270 j
+PYANNET_MAX_CLASSES = 8
+PYANNET_CUTOFFS = ("sincnet.conv1d.0.filterbank.low_hz_", "sincnet.conv1d.0.filterbank.band_hz_")
+
+
+def _pyannet_table() -> Dict[str, tuple]:
+    t: Dict[str, tuple] = {"sincnet.wav_norm1d.weight": (1,), "sincnet.wav_norm1d.bias": (1,),
+                           "sincnet.conv1d.0.filters": (80, 1, 251)}
+    for i, ch in enumerate((80, 60, 60)):
+        t[f"sincnet.norm1d.{i}.weight"] = (ch,)
+        t[f"sincnet.norm1d.{i}.bias"] = (ch,)
+    t["sincnet.conv1d.1.weight"], t["sincnet.conv1d.1.bias"] = (60, 80, 5), (60,)
+    t["sincnet.conv1d.2.weight"], t["sincnet.conv1d.2.bias"] = (60, 60, 5), (60,)
+    for layer in range(4):
+        for sfx in (f"_l{layer}", f"_l{layer}_reverse"):
+            t["lstm.weight_ih" + sfx] = (512, 60 if layer == 0 else 256)
+            t["lstm.weight_hh" + sfx] = (512, 128)
+            t["lstm.bias_ih" + sfx] = (512,)
+            t["lstm.bias_hh" + sfx] = (512,)
+    t["linear.0.weight"], t["linear.0.bias"] = (128, 256), (128,)
+    t["linear.1.weight"], t["linear.1.bias"] = (128, 128), (128,)
+    t["classifier.weight"], t["classifier.bias"] = ("C", 128), ("C",)
+    return t
+
+
+PYANNET_TENSORS: Dict[str, tuple] = _pyannet_table()   # 51 tensors
+# the seed tests and tools use, with the classifier's gain and bias: on the suite's test signal the float64 reference's aggregated
+# score goes below 0.35 and above 0.65 and Binarize finds at least 3 segments
+SYNTH_PYANNET_SEED, SYNTH_PYANNET_GAIN, SYNTH_PYANNET_BIAS = 0, 4.0, -1.0
+
+
+def sinc_filters(low_hz_, band_hz_, sample_rate: int = SAMPLING_RATE) -> np.ndarray:
+    """The materialised sinc filterbank, float32 [80, 1, 251], from the 40 learnable cutoff pairs - ParamSincFB's formula, restated
+    from memory (UNPINNED), in float64: low = 50 + |low_hz_|, high = clip(low + 50 + |band_hz_|, 50, sr / 2), band = high - low;
+    with n = 2 pi m / sr for m = -125 ... -1 and win = the first 125 points of the 251-point periodic Hamming window
+    0.54 - 0.46 cos(2 pi i / 251):  cosine filter = [L | 2 band | reversed L], L = (sin(high n) - sin(low n)) / (n / 2) * win;
+    sine filter = [L | 0 | -reversed L], L = (cos(low n) - cos(high n)) / (n / 2) * win; each divided by 2 band; the 40 cosine
+    filters first, then the 40 sine filters."""
+    low_p = np.asarray(low_hz_, dtype=np.float64).reshape(-1)
+    band_p = np.asarray(band_hz_, dtype=np.float64).reshape(-1)
+    if low_p.shape != (40,) or band_p.shape != (40,):
+        raise ValueError(f"sinc cutoffs: {low_p.size} low and {band_p.size} band values, expected 40 of each")
+    low = 50.0 + np.abs(low_p)
+    high = np.clip(low + 50.0 + np.abs(band_p), 50.0, sample_rate / 2.0)
+    band = high - low
+    n = 2.0 * np.pi * np.arange(-125, 0, dtype=np.float64) / sample_rate
+    win = 0.54 - 0.46 * np.cos(2.0 * np.pi * np.arange(125, dtype=np.float64) / 251.0)
+    fl, fh = low[:, None] * n[None, :], high[:, None] * n[None, :]
+    cos_left = (np.sin(fh) - np.sin(fl)) / (n / 2.0) * win
+    sin_left = (np.cos(fl) - np.cos(fh)) / (n / 2.0) * win
+    cos_f = np.concatenate([cos_left, 2.0 * band[:, None], cos_left[:, ::-1]], axis=1)
+    sin_f = np.concatenate([sin_left, np.zeros((40, 1)), -sin_left[:, ::-1]], axis=1)
+    filters = np.concatenate([cos_f, sin_f]) / (2.0 * np.concatenate([band, band])[:, None])
+    return np.ascontiguousarray(filters[:, None, :], dtype=np.float32)
+
+
+def mel_cutoffs(sample_rate: int = SAMPLING_RATE):
+    """(low_hz_, band_hz_) [40, 1] of a freshly initialised filterbank: 41 points equally spaced on the mel scale from 30 Hz to
+    sr / 2 - 100 Hz; low = the first 40, band = their differences."""
+    to_mel = lambda hz: 2595.0 * np.log10(1.0 + hz / 700.0)   # noqa: E731
+    hz = 700.0 * (10.0 ** (np.linspace(to_mel(30.0), to_mel(sample_rate / 2.0 - 100.0), 41) / 2595.0) - 1.0)
+    return hz[:-1, None].astype(np.float32), np.diff(hz)[:, None].astype(np.float32)
+
+
+def synth_pyannet_weights(seed: int = SYNTH_PYANNET_SEED, classes: int = 3) -> Dict[str, np.ndarray]:
+    """Seeded synthetic weights in the shapes of PYANNET_TENSORS (float32): the filters are sinc_filters of the mel-spaced initial
+    cutoffs, every matrix is drawn N(0, 1.5 / sqrt(fan_in)), the norms' weights around 1, the biases small, and the classifier
+    carries SYNTH_PYANNET_GAIN and SYNTH_PYANNET_BIAS so that the scores move across 0.5.  Deterministic per (seed, classes).
+    NOT a voice-activity detector: a stand-in that exercises the network."""
+    if not 1 <= int(classes) <= PYANNET_MAX_CLASSES:
+        raise ValueError(f"classes {classes} outside 1 ... {PYANNET_MAX_CLASSES}")
+    rng = np.random.default_rng([0x9A22E7, int(seed)])
+    out: Dict[str, np.ndarray] = {}
+    for name, shape in PYANNET_TENSORS.items():
+        shape = tuple(int(classes) if d == "C" else d for d in shape)
+        if name == "sincnet.conv1d.0.filters":
+            w = sinc_filters(*mel_cutoffs())
+        elif "norm1d" in name:
+            w = (1.0 + 0.1 * rng.standard_normal(shape)) if name.endswith("weight") else 0.1 * rng.standard_normal(shape)
+        elif name == "classifier.weight":
+            w = rng.standard_normal(shape) * (SYNTH_PYANNET_GAIN * 1.5 / np.sqrt(shape[1]))
+        elif name == "classifier.bias":
+            w = np.full(shape, SYNTH_PYANNET_BIAS)
+        elif name.endswith("weight") or "weight_" in name:
+            w = rng.standard_normal(shape) * (1.5 / np.sqrt(np.prod(shape[1:])))
+        else:
+            w = rng.standard_normal(shape) * 0.05
+        out[name] = np.ascontiguousarray(w, dtype=np.float32)
+    return out
+
+
+def load_pyannet_state(path_or_mapping) -> Dict[str, np.ndarray]:
+    """The tensors of PYANNET_TENSORS as float32 arrays, from a mapping (state dict; torch tensors or arrays), an `.npz` file, or -
+    when torch imports - a torch file, with an optional "state_dict" level (a Lightning checkpoint).  The filters come from
+    "sincnet.conv1d.0.filters" when the source has it, else from the cutoffs PYANNET_CUTOFFS through sinc_filters.  Keys outside
+    the table are ignored; a missing tensor or a wrong shape raises ValueError."""
+    src = path_or_mapping
+    if isinstance(src, (str, bytes)) or hasattr(src, "__fspath__"):
+        path = os.fspath(src)
+        if str(path).lower().endswith(".npz"):
+            with np.load(path) as z:
+                src = {k: z[k] for k in z.files}
+        else:
+            try:
+                import torch
+            except ImportError as e:
+                raise RuntimeError(f"{path}: reading a torch checkpoint needs torch; convert it to .npz") from e
+            src = torch.load(path, map_location="cpu", weights_only=True)
+    src = dict(src)
+    if "state_dict" in src and hasattr(src["state_dict"], "items"):
+        src = dict(src["state_dict"])
+    to_np = lambda v: np.asarray(v.detach().cpu().float().numpy() if hasattr(v, "detach") else v)   # noqa: E731
+    out: Dict[str, np.ndarray] = {}
+    if "sincnet.conv1d.0.filters" not in src and all(k in src for k in PYANNET_CUTOFFS):
+        out["sincnet.conv1d.0.filters"] = sinc_filters(*(to_np(src[k]) for k in PYANNET_CUTOFFS))
+    classes = None
+    for name, shape in PYANNET_TENSORS.items():
+        if name not in src:
+            continue
+        a = np.ascontiguousarray(to_np(src[name]), dtype=np.float32)
+        if "C" in shape:
+            if a.ndim != len(shape) or not 1 <= a.shape[0] <= PYANNET_MAX_CLASSES or (classes is not None and a.shape[0] != classes):
+                raise ValueError(f"segmentation tensor {name}: shape {a.shape}, expected {shape} with one C in 1 ... {PYANNET_MAX_CLASSES}")
+            classes = a.shape[0]
+            shape = tuple(classes if d == "C" else d for d in shape)
+        if a.shape != shape:
+            raise ValueError(f"segmentation tensor {name}: shape {a.shape}, expected {shape}")
+        out[name] = a
+    missing = [n for n in PYANNET_TENSORS if n not in out]
+    if missing:
+        raise ValueError(f"segmentation state is missing {missing}")
+    return {n: out[n] for n in PYANNET_TENSORS}
+
+
+def pyannote_speech_timestamps(n_samples: int, scores, onset: float = 0.5, offset: float = 0.5, min_duration_on: float = 0.3,
+                               min_duration_off: float = 0.3, pad_onset: float = 0.0, pad_offset: float = 0.0,
+                               sampling_rate: int = SAMPLING_RATE) -> List[Dict[str, int]]:
+    """pyannote's Binarize over a recording's aggregated scores (Engine.segmentation_scores), restated (UNPINNED) ->
+    [{'start': sample, 'end': sample}], the chunk-list format of get_speech_timestamps.  Frame j stands at
+    t_j = (495 + 270 j) / 16 000 s.  Hysteresis: a segment opens at the frame whose score goes above `onset` (at frame 0 when
+    the first score is above it) and closes at the frame whose score goes below `offset`; a segment still open ends at the last
+    frame.  Then the pads are applied (start - pad_onset, end + pad_offset), segments whose gap is <= min_duration_off are merged,
+    segments shorter than min_duration_on are dropped, and the rest is clipped to [0, n_samples]."""
+    scores = np.asarray(scores, dtype=np.float64).reshape(-1)
+    at = lambda j: (PYANNET_FRAME_CENTRE + PYANNET_FRAME_STEP * j) / float(sampling_rate)   # noqa: E731
+    segs: List[List[float]] = []
+    if len(scores):
+        active, start = bool(scores[0] > onset), at(0)
+        for j in range(1, len(scores)):
+            if active and scores[j] < offset:
+                segs.append([start - pad_onset, at(j) + pad_offset])
+                active = False
+            elif not active and scores[j] > onset:
+                start, active = at(j), True
+        if active:
+            segs.append([start - pad_onset, at(len(scores) - 1) + pad_offset])
+    merged: List[List[float]] = []
+    for s in segs:
+        if merged and s[0] - merged[-1][1] <= min_duration_off:
+            merged[-1][1] = max(merged[-1][1], s[1])
+        else:
+            merged.append(list(s))
+    out = []
+    for a, b in merged:
+        if b - a < min_duration_on:
+            continue
+        a, b = max(int(round(a * sampling_rate)), 0), min(int(round(b * sampling_rate)), int(n_samples))
+        if b > a:
+            out.append({"start": a, "end": b})
+    return out
+
+
 def silero_speech_prob_fn(step: Callable[[np.ndarray, np.ndarray], "tuple[float, np.ndarray]"], context: int = 64,
                           state_shape: Sequence[int] = (2, 1, 128)) -> Callable[[np.ndarray], np.ndarray]:
     """Adapter for an operator-supplied Silero VAD network (the ONNX file faster-whisper ships; not available offline):

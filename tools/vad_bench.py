@@ -24,6 +24,14 @@ and nothing else (the command a kernel trace is taken of).
              16 kHz floats, and beside the file kernel run per row (Engine.ingest) and then pushed.  --trace-pushes N: N wire
              pushes and nothing else (the command a kernel trace counts launches of).
 
+  --pyannote   the PyanNet-shaped segmentation network instead (Engine.segmentation_scores, kernels_seg.hip), micro geometry,
+             float32, max_batch 64, synthetic weights: audio-s/s on one synthetic hour and on 64 x 30 s; every recurrence form
+             (option seg_lstm_rows = 1, 2, 4 chunks per workgroup) on recordings of 1, 8, 64 and 7 000 chunks; the latency of
+             DevicePyannoteVAD.detect_activity for 1, 8 and 64 concurrent clients with 3-s buffers; and beside them the float32
+             torch restatement of the network on 16 host threads over one group of 64 chunks.  --kernel-stats FILE merges the
+             per-kernel split of a kernel trace's statistics CSV (taken of --pyannote --hour-only: three calls on the hour).
+
+    python tools/vad_bench.py --pyannote [--repeats 5] [--kernel-stats stats.csv] [--out profiles/pyannote_vad.json]
     python tools/vad_bench.py [--model large-v3] [--repeats 7] [--out profiles/vad_device.json]
     python tools/vad_bench.py --stream [--repeats 7] [--out profiles/vad_stream.json]
     python tools/vad_bench.py --stream --wire ulaw8k [--repeats 7] [--out profiles/wire_stream.json]
@@ -191,6 +199,110 @@ def wire_bench(repeats: int, wire: str, n: int = 64, seconds: float = 1.5, trace
     return res
 
 
+def torch_pyannet_float32(weights, threads: int = 16):
+    """The float32 torch restatement of the network: fn(x [chunks, 80000]) -> probabilities [chunks, 293, C] on `threads` host threads."""
+    import torch
+    import torch.nn.functional as F
+    torch.set_num_threads(threads)
+    w = {k: torch.from_numpy(np.asarray(v, dtype=np.float32)) for k, v in weights.items()}
+    lstm = torch.nn.LSTM(60, 128, num_layers=4, bidirectional=True, batch_first=True)
+    lstm.load_state_dict({k[5:]: v for k, v in w.items() if k.startswith("lstm.")})
+
+    def fn(x):
+        with torch.no_grad():
+            y = torch.from_numpy(x)[:, None, :]
+            y = F.instance_norm(y, weight=w["sincnet.wav_norm1d.weight"], bias=w["sincnet.wav_norm1d.bias"], eps=1e-5)
+            y = torch.abs(F.conv1d(y, w["sincnet.conv1d.0.filters"], stride=10))
+            for i in range(3):
+                if i:
+                    y = F.conv1d(y, w[f"sincnet.conv1d.{i}.weight"], w[f"sincnet.conv1d.{i}.bias"])
+                y = F.leaky_relu(F.instance_norm(F.max_pool1d(y, 3, 3), weight=w[f"sincnet.norm1d.{i}.weight"],
+                                                 bias=w[f"sincnet.norm1d.{i}.bias"], eps=1e-5))
+            y = lstm(y.transpose(1, 2))[0]
+            for i in range(2):
+                y = F.leaky_relu(F.linear(y, w[f"linear.{i}.weight"], w[f"linear.{i}.bias"]))
+            return torch.sigmoid(F.linear(y, w["classifier.weight"], w["classifier.bias"])).numpy()
+    return fn
+
+
+def kernel_split(path: str) -> dict:
+    """The seg_* rows of a kernel trace's statistics CSV (Name, Calls, TotalDurationNs): calls, total ms and share per kernel."""
+    import csv
+    import re
+    with open(path) as f:
+        rows = [(re.search(r"seg_\w+(<[^>]*>)?", r["Name"]), r) for r in csv.DictReader(f)]
+    rows = [(m.group(0), r) for m, r in rows if m]
+    total = sum(float(r["TotalDurationNs"]) for _, r in rows) or 1.0
+    return {name: {"calls": int(r["Calls"]), "total_ms": round(float(r["TotalDurationNs"]) / 1e6, 3),
+                   "share": round(float(r["TotalDurationNs"]) / total, 4)} for name, r in rows}
+
+
+def pyannote_bench(repeats: int, hour_only: bool, kernel_stats) -> dict:
+    import asyncio
+
+    from taiwan_tongues_asr_ce_amd import _lib, vad_backends
+    from taiwan_tongues_asr_ce_amd.config import COMPUTE_F32, PRESETS
+    from taiwan_tongues_asr_ce_amd.engine import Engine
+    weights = vad.synth_pyannet_weights()
+    e = Engine(PRESETS["micro"], COMPUTE_F32, 64)
+    e.load_segmentation(weights)
+    hour = bursts(3000, 3600.0)
+    if hour_only:
+        for _ in range(3):
+            e.segmentation_scores([hour])
+        return {"hour_only_calls": 3, "chunks_per_call": int(e.lib.ttasr_seg_chunks(len(hour)))}
+    res = {"tool": "tools/vad_bench.py --pyannote", "weights": "vad.synth_pyannet_weights()", "engine": "micro geometry, float32, max_batch 64",
+           "group_chunks": _lib.SEG_GROUP, "timing": {}, "recurrence_forms": {}, "detect_activity_3s_buffers": {}}
+    clips = [bursts(3100 + i, 30.0) for i in range(64)]
+    for name, audios in (("1 x 3600 s", [hour]), ("64 x 30 s", clips)):
+        t = timed(lambda: e.segmentation_scores(audios), repeats)
+        secs = sum(len(a) for a in audios) / 16000.0
+        t.update(audio_s=secs, chunks=int(sum(e.lib.ttasr_seg_chunks(len(a)) for a in audios)), audio_s_per_s=round(secs / t["median_s"], 1))
+        res["timing"][name] = t
+    for chunks in (1, 8, 64, 7000):
+        x = hour[:80000 + 8000 * (chunks - 1)]
+        row = {}
+        for rows in (1, 2, 4):
+            e.set_option("seg_lstm_rows", rows)
+            t = timed(lambda: e.segmentation_scores([x]), repeats)
+            row[f"rows_{rows}"] = dict(t, ms_per_chunk=round(1e3 * t["median_s"] / chunks, 4))
+        e.set_option("seg_lstm_rows", 0)
+        row["fastest"] = min(("rows_1", "rows_2", "rows_4"), key=lambda k: row[k]["median_s"])
+        res["recurrence_forms"][str(chunks)] = row
+
+    class Client:
+        sampling_rate, samples_width = 16000, 2
+
+        def __init__(self, cid, audio):
+            self.client_id, self.scratch_buffer = cid, bytearray((np.clip(audio, -1, 1) * 32767).astype("<i2").tobytes())
+
+    for n in (1, 8, 64):
+        backend = vad_backends.DevicePyannoteVAD(engine=e, max_wait_ms=2.0)
+        clients = [Client(i, hour[(99991 * i) % (len(hour) - 48000):][:48000]) for i in range(n)]
+
+        async def once():
+            return await asyncio.gather(*[backend.detect_activity(c) for c in clients])
+
+        loop = asyncio.new_event_loop()
+        t = timed(lambda: loop.run_until_complete(once()), repeats)
+        t["device_calls"] = sorted(set(backend.calls_run))
+        t["ms_per_client"] = round(1e3 * t["median_s"] / n, 3)
+        res["detect_activity_3s_buffers"][str(n)] = t
+        backend.close()
+        loop.close()
+    fn = torch_pyannet_float32(weights, 16)
+    group = np.stack([hour[8000 * k:8000 * k + 80000] for k in range(64)])
+    t = timed(lambda: fn(group), 3, warm=1)
+    t.update(chunks=64, host_threads=16, ms_per_chunk=round(1e3 * t["median_s"] / 64, 3), audio_s_per_s_of_a_long_recording=round(64 * 0.5 / t["median_s"], 1))
+    res["torch_float32_restatement_64_chunks"] = t
+    got = e.segmentation_scores([hour[:80000 + 8000 * 63]], return_chunks=True)[1][0]
+    res["device_vs_torch_float32_max_abs_probability"] = float(f"{np.abs(got - fn(group)).max():.3e}")
+    if kernel_stats:
+        res["kernel_split_of_three_hour_calls"] = kernel_split(kernel_stats)
+    e.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="large-v3")
@@ -201,7 +313,16 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--wire", choices=sorted(WIRES), default=None, help="with --stream: wire streams in this format")
     ap.add_argument("--trace-pushes", type=int, default=0, help="with --stream --wire: this many pushes and nothing else (the command a kernel trace is taken of)")
+    ap.add_argument("--pyannote", action="store_true", help="the segmentation network (Engine.segmentation_scores)")
+    ap.add_argument("--kernel-stats", default=None, help="with --pyannote: a kernel trace's statistics CSV of --pyannote --hour-only")
     args = ap.parse_args()
+    if args.pyannote:
+        text = json.dumps(pyannote_bench(args.repeats, args.hour_only, args.kernel_stats), indent=1)
+        print(text)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     if args.stream:
         res = wire_bench(args.repeats, args.wire, trace_pushes=args.trace_pushes) if args.wire else stream_bench(args.repeats)
         text = json.dumps(res, indent=1)
