@@ -145,15 +145,16 @@ void ttasr_destroy(ttasr_ctx* c) {
   ttasr_ctx* owner = c->weight_owner;
   session_free(c);
   drop_graphs(c);
-  for (auto& e : c->ev) if (e) hipEventDestroy(e);
+  // the owners the context holds go here, in this order, while the device is set and before the stream: not with `delete c`
+  for (auto& e : c->ev) e.reset();
   for (auto& e : c->enc_ev) hipEventDestroy(e);
   for (void* p : c->allocs) hipFree(p);
-  if (c->align_dev) hipFree(c->align_dev);
+  c->align_dev.reset();
   vad_free(c);
   seg_free(c);
   ingest_free(c);
-  if (c->pinned_i32) hipHostFree(c->pinned_i32);
-  if (c->pinned_beam) hipHostFree(c->pinned_beam);
+  c->pinned_i32.reset();
+  c->pinned_beam.reset();
   if (c->stream) hipStreamDestroy(c->stream);
   delete c;
   if (owner) {
@@ -479,16 +480,10 @@ int ttasr_align_attn_probe(ttasr_ctx* c, int32_t layer, int32_t n_seq, const int
   // host image: rows [R][3] | slots [R] | seqs [n_seq][3 + pps] | items [ni][3] | sel [LH]; device block: image | maps | stat
   const size_t w_slots = (size_t)R * 3, w_seqs = w_slots + R, w_items = w_seqs + (size_t)n_seq * (3 + pps), w_sel = w_items + (size_t)ni * 3,
                in_words = w_sel + LH;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t o_maps = up(in_words * 4), o_stat = o_maps + up((size_t)n_pairs * R * T_ * 4), total = o_stat + up((size_t)n_pairs * R * 8);
-  if (total > c->align_dev_bytes) {
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (c->align_dev) hipFree(c->align_dev);
-    c->align_dev = nullptr; c->align_dev_bytes = 0;
-    const hipError_t e = hipMalloc(&c->align_dev, total);
-    if (e != hipSuccess) { c->align_dev = nullptr; (void)hipGetLastError(); return fail(c, TTASR_E_NOMEM, "probe scratch (%zu bytes): %s", total, hipGetErrorString(e)); }
-    c->align_dev_bytes = total;
-  }
+  Carve cv;
+  cv.take(in_words * 4);
+  const size_t o_maps = cv.take((size_t)n_pairs * R * T_ * 4), o_stat = cv.take((size_t)n_pairs * R * 8);
+  TRY(c->align_dev.ensure(c, cv.used, "probe scratch"));
   std::vector<int32_t> in(in_words, 0), zeros((size_t)std::max(kPrefillRowCap, pps), 0);
   std::vector<PrefillSeq> sq(n_seq);
   for (int i = 0; i < n_seq; ++i) sq[i] = PrefillSeq{slots[i], lens[i], zeros.data(), zeros.data()};   // tokens and pages: not read here
@@ -496,7 +491,7 @@ int ttasr_align_attn_probe(ttasr_ctx* c, int32_t layer, int32_t n_seq, const int
   int32_t* h_sel = in.data() + w_sel;
   for (int i = 0; i < LH; ++i) h_sel[i] = -1;
   for (int h = 0; h < c->H; ++h) h_sel[(size_t)layer * c->H + h] = head_pair[h];
-  char* base = (char*)c->align_dev;
+  char* base = c->align_dev;
   const int32_t* dw = (const int32_t*)base;
   float* d_maps = (float*)(base + o_maps);
   HIPCHK(c, hipMemcpyAsync(base, in.data(), in_words * 4, hipMemcpyHostToDevice, s));
@@ -919,11 +914,10 @@ int ttasr_align(ttasr_ctx* c, int32_t clip, const int32_t* tokens, int32_t n_tok
   }
   hipStream_t s = c->stream;
   const size_t n_w = (size_t)n_pairs * n_tok * c->T;
-  float* probs = nullptr; int32_t* sel_dev = nullptr; float* lp_dev = nullptr;
-  struct Free { void** p; ~Free() { if (*p) hipFree(*p); } } f1{(void**)&probs}, f2{(void**)&sel_dev}, f3{(void**)&lp_dev};
-  if (hipMalloc(&probs, n_w * 4) != hipSuccess || hipMalloc(&sel_dev, sel.size() * 4) != hipSuccess ||
-      hipMalloc(&lp_dev, (size_t)n_tok * 4) != hipSuccess)
-    return fail(c, TTASR_E_NOMEM, "alignment buffers (%zu bytes)", n_w * 4);
+  DevBlock<float> probs, lp_dev; DevBlock<int32_t> sel_dev;   // of this call
+  TRY(probs.ensure(c, n_w * 4, "alignment maps"));
+  TRY(sel_dev.ensure(c, sel.size() * 4, "alignment head selection"));
+  TRY(lp_dev.ensure(c, (size_t)n_tok * 4, "alignment log-probs"));
   HIPCHK(c, hipMemcpyAsync(sel_dev, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpyAsync(c->prompt_dev, tokens, (size_t)n_tok * 4, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipStreamSynchronize(s));  // sel is a stack temporary

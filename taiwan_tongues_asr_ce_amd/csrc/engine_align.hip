@@ -39,23 +39,6 @@ int align_batch_validate(ttasr_ctx* c, const AlignBatch& a) {
   return 0;
 }
 
-// The context's alignment scratch: one device block, grown to the largest request and freed by ttasr_destroy.  A request that
-// cannot be allocated leaves the context without a block (the next call allocates again) and otherwise as it was.
-static int align_scratch(ttasr_ctx* c, size_t bytes) {
-  if (bytes <= c->align_dev_bytes) return 0;
-  HIPCHK(c, hipStreamSynchronize(c->stream));   // the old block may still be read
-  if (c->align_dev) hipFree(c->align_dev);
-  c->align_dev = nullptr; c->align_dev_bytes = 0;
-  const hipError_t e = hipMalloc(&c->align_dev, bytes);
-  if (e != hipSuccess) {
-    c->align_dev = nullptr;
-    (void)hipGetLastError();
-    return fail(c, TTASR_E_NOMEM, "alignment scratch (%zu bytes): %s", bytes, hipGetErrorString(e));
-  }
-  c->align_dev_bytes = bytes;
-  return 0;
-}
-
 // validated arguments -> pass, post-processing, DTW, results on the host.  slot [n]: cross-KV slot of every sequence; pages
 // [n][pages_per_seq]: the self-attention pages the sequence's K/V may use.
 int align_batch_run(ttasr_ctx* c, const AlignBatch& a, const int32_t* slot, const int32_t* pages) {
@@ -85,12 +68,13 @@ int align_batch_run(ttasr_ctx* c, const AlignBatch& a, const int32_t* slot, cons
   for (int i = 0; i < LH; ++i) h_sel[i] = -1;
   for (int i = 0; i < a.n_pairs; ++i) h_sel[(size_t)a.pairs[2 * i] * c->H + a.pairs[2 * i + 1]] = i;
   // device block: inputs | lp [R] | start [R] | stats [n][pairs][2][T] | cost [R][T] | probs [pairs][R][T] | spilled traces
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t o_lp = up(in_words * 4), o_start = o_lp + up((size_t)R * 4), o_stats = o_start + up((size_t)R * 4),
-               o_cost = o_stats + up((size_t)n * a.n_pairs * 2 * T_ * 4), o_probs = o_cost + up((size_t)R * T_ * 4),
-               o_spill = o_probs + up((size_t)a.n_pairs * R * T_ * 4), total = o_spill + up((size_t)n * spill_words * 4);
-  TRY(align_scratch(c, total));
-  char* base = (char*)c->align_dev;
+  Carve cv;
+  cv.take(in_words * 4);
+  const size_t o_lp = cv.take((size_t)R * 4), o_start = cv.take((size_t)R * 4), o_stats = cv.take((size_t)n * a.n_pairs * 2 * T_ * 4),
+               o_cost = cv.take((size_t)R * T_ * 4), o_probs = cv.take((size_t)a.n_pairs * R * T_ * 4),
+               o_spill = cv.take((size_t)n * spill_words * 4);
+  TRY(c->align_dev.ensure(c, cv.used, "alignment scratch"));   // the context's block, grown to the largest request
+  char* base = c->align_dev;
   const int32_t* d_tok = (const int32_t*)base;
   const AlignSeq* d_seq = (const AlignSeq*)(d_tok + R);
   const int32_t* d_slot = (const int32_t*)(d_seq + n);
@@ -153,7 +137,6 @@ int align_packed_run(ttasr_ctx* c, const AlignBatch& a, const int32_t* slot, con
     len[i] = a.n_tokens[i];
   }
   const std::vector<int> cut = prefill_pass_split(len, kPrefillRowCap);
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
   // one pass: host image rows [R][3] | slots [R] | seqs [ns][3 + pps] | items [ni][3] | target [R] | AlignSeq [ns] | seq_row [ns] |
   // sel [LH]; device block: image | lp [R] | start [R] | stats [ns][pairs][2][T] | cost [R][T] | maps [pairs][R][T] | stat [pairs][R][2]
   // | spilled traces
@@ -172,10 +155,12 @@ int align_packed_run(ttasr_ctx* c, const AlignBatch& a, const int32_t* slot, con
     L.w_slots = (size_t)L.R * 3; L.w_seqs = L.w_slots + L.R; L.w_items = L.w_seqs + (size_t)L.ns * (3 + pps);
     L.w_target = L.w_items + (size_t)L.ni * 3; L.w_aseq = L.w_target + L.R; L.w_row = L.w_aseq + (size_t)L.ns * 4;
     L.w_sel = L.w_row + L.ns; L.in_words = L.w_sel + LH;
-    L.o_lp = up(L.in_words * 4); L.o_start = L.o_lp + up((size_t)L.R * 4); L.o_stats = L.o_start + up((size_t)L.R * 4);
-    L.o_cost = L.o_stats + up((size_t)L.ns * np * 2 * T_ * 4); L.o_maps = L.o_cost + up((size_t)L.R * T_ * 4);
-    L.o_stat = L.o_maps + up((size_t)np * L.R * T_ * 4); L.o_spill = L.o_stat + up((size_t)np * L.R * 2 * 4);
-    L.total = L.o_spill + up((size_t)L.ns * L.spill_words * 4);
+    Carve cv;
+    cv.take(L.in_words * 4);
+    L.o_lp = cv.take((size_t)L.R * 4); L.o_start = cv.take((size_t)L.R * 4); L.o_stats = cv.take((size_t)L.ns * np * 2 * T_ * 4);
+    L.o_cost = cv.take((size_t)L.R * T_ * 4); L.o_maps = cv.take((size_t)np * L.R * T_ * 4);
+    L.o_stat = cv.take((size_t)np * L.R * 2 * 4); L.o_spill = cv.take((size_t)L.ns * L.spill_words * 4);
+    L.total = cv.used;
     return L;
   };
   size_t total = 0;
@@ -184,8 +169,8 @@ int align_packed_run(ttasr_ctx* c, const AlignBatch& a, const int32_t* slot, con
     if (L.R > kPrefillRowCap) return fail(c, TTASR_E_INVALID, "packed alignment: a pass of %d rows exceeds the workspace", L.R);
     total = std::max(total, L.total);
   }
-  TRY(align_scratch(c, total));
-  char* base = (char*)c->align_dev;
+  TRY(c->align_dev.ensure(c, total, "alignment scratch"));
+  char* base = c->align_dev;
   memset(a.out_start, 0, (size_t)n * npos * 4);
   if (a.out_lp) memset(a.out_lp, 0, (size_t)n * npos * 4);
   if (a.out_cost) memset(a.out_cost, 0, (size_t)n * npos * T_ * 4);

@@ -206,7 +206,7 @@ int build_workspaces(ttasr_ctx* c) {
   TRY(dalloc(c, &c->topk_lp, (size_t)B * 8 * 4)); TRY(dalloc(c, &c->topk_id, (size_t)B * 8 * 4));
   TRY(dalloc(c, &c->row_state, (size_t)B * 4 * 4));
   c->st.mask = c->mask_dev;
-  HIPCHK(c, hipHostMalloc((void**)&c->pinned_i32, 4096));
+  TRY(c->pinned_i32.ensure(c, 4096, "pinned scratch"));
   // mel constants
   std::vector<float> fb = mel_filters(c->M), cs(400), sn(400), wn(400);
   for (int i = 0; i < 400; ++i) {
@@ -221,7 +221,7 @@ int build_workspaces(ttasr_ctx* c) {
   HIPCHK(c, hipMemcpyAsync(c->dsin, sn.data(), 1600, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->window, wn.data(), 1600, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (auto& e : c->ev) HIPCHK(c, hipEventCreate(&e));
+  for (auto& e : c->ev) TRY(event_create(c, e));
   return 0;
 }
 

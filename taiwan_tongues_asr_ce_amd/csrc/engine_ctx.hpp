@@ -23,9 +23,31 @@
 #include "align_batch.hpp"
 #include "beam_pages.hpp"
 #include "prefill_tables.hpp"
+#include "owned.hpp"
 
 namespace ttasr_detail {
 
+// The production policies of owned.hpp.  Memory: quiesce is the synchronisation of the context's stream, nomem is
+// fail(c, TTASR_E_NOMEM, "<what> (<bytes> bytes): <error>") (both defined next to HIPCHK below); a failed allocation leaves no sticky error.
+struct HipMem {
+  static int quiesce(ttasr_ctx* c);
+  static int nomem(ttasr_ctx* c, const char* what, size_t bytes, const char* err);
+  static const char* text(hipError_t e) { if (e == hipSuccess) return nullptr; (void)hipGetLastError(); return hipGetErrorString(e); }
+};
+struct DeviceMem : HipMem {
+  static const char* alloc(void** p, size_t bytes) { return text(hipMalloc(p, bytes)); }
+  static void release(void* p) { (void)hipFree(p); }
+};
+struct PinnedMem : HipMem {
+  static const char* alloc(void** p, size_t bytes) { return text(hipHostMalloc(p, bytes, hipHostMallocDefault)); }
+  static void release(void* p) { (void)hipHostFree(p); }
+};
+struct EventKind { using type = hipEvent_t; static void destroy(hipEvent_t e) { (void)hipEventDestroy(e); } };
+struct StreamKind { using type = hipStream_t; static void destroy(hipStream_t s) { (void)hipStreamDestroy(s); } };
+template <class T = char> using DevBlock = Block<DeviceMem, T>;
+template <class T = char> using PinBlock = Block<PinnedMem, T>;
+using Event = Handle<EventKind>;         // created by event_create (below)
+using OwnStream = Handle<StreamKind>;    // a stream its holder created: never an alias of the context's stream
 
 extern thread_local std::string g_create_error;   // error text of a failed ttasr_create (engine_alloc.hip)
 
@@ -149,14 +171,14 @@ struct ttasr_ctx {
   bool ragged_exit = true;          // option ragged_exit [1]: finished rows (st.done) leave the attention kernels of the decode step
                                     // (0: the static batch of rounds 1-5 - every row streams its cross-KV until the last one ends; A/B)
   RuleDyn* rule_dyn_dev = nullptr; RuleDyn rule_dyn_host{};  // per-window rule scalars read by select_kernel (common.hpp RuleDyn)
-  int32_t* pinned_i32 = nullptr;  // host pinned scratch
+  PinBlock<int32_t> pinned_i32;  // host pinned scratch
   // beam search (round 6): every per-position host <-> device exchange goes through ONE pinned block - page tables, fed tokens,
   // row histories and copy-on-write pairs out, top-k candidates back - so the copies are truly asynchronous (a pageable source
   // makes hipMemcpyAsync stage and block: measured ~0.5 ms of host time per position in round 5's loop) and a searching position
   // costs ONE stream synchronisation instead of two.  The beam session's steps use the same block (BeamExchange below carves
   // it for either search): a context never runs a static search while a session is open (session_refusal).  Allocated by the
-  // first search for the largest one this context can run, freed by ttasr_destroy.
-  char* pinned_beam = nullptr;
+  // first search for the largest one this context can run; ttasr_destroy resets it before the stream goes.
+  PinBlock<> pinned_beam;
   float beam_prof_ms[4]{0, 0, 0, 0};   // last beam search: host time enqueueing, waiting for the GPU, selecting candidates; positions
   int max_new_alloc = 0, max_prompt_alloc = 0;
 
@@ -180,8 +202,8 @@ struct ttasr_ctx {
   bool align_packed = false;
 
   // batched alignment (engine_align.hip): ONE device block for the pass's tables, softmax maps, cost matrices and spilled DTW
-  // traces; allocated by the first call, grown to the largest request, freed by ttasr_destroy
-  void* align_dev = nullptr; size_t align_dev_bytes = 0;
+  // traces; allocated by the first call, grown to the largest request (ensure), reset by ttasr_destroy
+  DevBlock<> align_dev;
   // voice-activity network (engine_vad.hip): created by the first ttasr_vad_load_tensor, freed by ttasr_destroy; per context,
   // outside the weight-share bookkeeping
   ttasr_detail::VadState* vad = nullptr;
@@ -207,7 +229,7 @@ struct ttasr_ctx {
   bool no_xsplit = false;   // option xsplit = 0: never split the cross-attention frames over workgroups (A/B testing)
   bool no_prefill = false;  // option prefill = 0: feed prompts token by token (A/B testing)
   bool prefill_tiled = false;  // option prefill_tiled: tiled encoder GEMMs in the prefill pass whatever the row count (A/B testing)
-  hipEvent_t ev[8]{};
+  Event ev[8];
   int32_t* probe_done = nullptr; float* probe_zero = nullptr;   // ttasr_cross_attn_probe: its own [maxB] finished flags and a [d] zero bias (allocated by the first call)
   // ttasr_self_attn_probe / ttasr_self_kv_*: an f32 and a T staging block of max(one pool layer, 512 x 3 d) elements, a T output
   // [512][d], [maxB] positions, a [3 d] zero bias and the packed pass's tables (allocated by the first call)
@@ -244,6 +266,21 @@ int fail(ttasr_ctx* c, int code, const char* fmt, ...);
                                       __FILE__, __LINE__);                                                    \
   } while (0)
 
+inline int HipMem::quiesce(ttasr_ctx* c) { HIPCHK(c, hipStreamSynchronize(c->stream)); return 0; }   // enqueued work may still read the block
+inline int HipMem::nomem(ttasr_ctx* c, const char* what, size_t bytes, const char* err) {
+  return fail(c, TTASR_E_NOMEM, "%s (%zu bytes): %s", what, bytes, err);
+}
+inline int event_create(ttasr_ctx* c, Event& e, unsigned flags = hipEventDefault) {
+  if (!e) HIPCHK(c, hipEventCreateWithFlags(&e.h, flags));
+  return 0;
+}
+inline int stream_create(ttasr_ctx* c, OwnStream& s) { HIPCHK(c, hipStreamCreateWithFlags(&s.h, hipStreamNonBlocking)); return 0; }
+// bytes per sample of a format that arrives as samples - the six PCM formats in the order of their codes, A-law, mu-law - else 0
+inline int sample_bytes(int32_t format) {
+  static const int pcm[6] = {1, 2, 3, 4, 4, 8};
+  if (format >= TTASR_PCM_U8 && format <= TTASR_PCM_F64) return pcm[format];
+  return format == TTASR_PCM_ALAW || format == TTASR_PCM_ULAW ? 1 : 0;
+}
 
 // No C++ exception may cross the C ABI (std::bad_alloc from a host vector would otherwise terminate the caller's process)
 template <class F>
@@ -392,7 +429,7 @@ inline WindowSpan window_span(const ttasr_ctx* c, int64_t file_samples, int64_t 
 
 // ---- engine_refill.hip: the continuous-batching session (greedy and beam search) ----
 int session_refusal(ttasr_ctx* c);   // TTASR_E_INVALID with a message while a session is open, else 0
-void session_free(ttasr_ctx* c);     // ttasr_destroy: the session's stream, events and pinned memory
+void session_free(ttasr_ctx* c);     // ttasr_destroy: deletes the session, which owns its stream, events and pinned memory
 
 // ---- engine_align.hip: the batched alignment pass (ttasr_align_batch, ttasr_session_align) ----
 struct AlignBatch {   // the host arguments of ttasr_align_batch without the clips
@@ -405,13 +442,13 @@ int align_batch_run(ttasr_ctx* c, const AlignBatch& a, const int32_t* slot /*[n]
 int align_packed_run(ttasr_ctx* c, const AlignBatch& a, const int32_t* slot, const int32_t* pages);
 
 // ---- engine_vad.hip: the voice-activity network (ttasr_vad_*) ----
-void vad_free(ttasr_ctx* c);         // ttasr_destroy: the scratch block, the pinned staging and the streams' table (the weights live in the arenas)
+void vad_free(ttasr_ctx* c);         // ttasr_destroy: deletes the state, which owns its side blocks (the weights live in the arenas)
 
 // ---- engine_seg.hip: the segmentation network (ttasr_seg_*) ----
-void seg_free(ttasr_ctx* c);         // ttasr_destroy: the scratch block and the pinned staging (the weights live in the arenas)
+void seg_free(ttasr_ctx* c);         // ttasr_destroy: deletes the state, which owns its side blocks (the weights live in the arenas)
 
 // ---- engine_ingest.hip: file ingest (ttasr_ingest_*) ----
-void ingest_free(ttasr_ctx* c);      // ttasr_destroy: the tap tables, the device and pinned chunk slots and their events
+void ingest_free(ttasr_ctx* c);      // ttasr_destroy: deletes the state, which owns its tap tables, chunk slots and events
 // What a wire stream (engine_vad.hip) keeps of its rate: the ratio, the filter and its table on the device (taps == nullptr at
 // 16000: no filter), H = floor(2 half / up) frames of history and the stream kernel's tile.  ok = false: not a stream rate.
 struct WirePlan { bool ok = false; int up = 1, down = 1, half = 0, L = 0, H = 0, tile = 256; const float* taps = nullptr; };

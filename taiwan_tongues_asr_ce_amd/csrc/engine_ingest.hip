@@ -22,8 +22,6 @@ constexpr int kImaMaxBlockAlign = 65536;
 constexpr size_t kFlacScratchBytes = (size_t)32 << 20;
 constexpr int64_t kFlacMaxChunkFrames = 65536;
 
-static const int kPcmBytes[6] = {1, 2, 3, 4, 4, 8};   // bytes per sample of the formats, in the order of their codes
-
 static bool is_pcm(int32_t f) { return f >= TTASR_PCM_U8 && f <= TTASR_PCM_F64; }
 static bool is_g711(int32_t f) { return f == TTASR_PCM_ALAW || f == TTASR_PCM_ULAW; }
 
@@ -82,27 +80,19 @@ static std::vector<double> ingest_design(const IngestPlan& p) {
   return w;
 }
 
-struct IngestFilter { IngestPlan plan; float* dev = nullptr; };
+struct IngestFilter { IngestPlan plan; DevBlock<float> dev; };
 
 struct IngestState {
   std::map<int32_t, IngestFilter> filters;   // per rate: the phase-major table [up][L] on the device (its own allocation)
-  char* dev = nullptr;                       // [kIngestSlots] raw | [kIngestSlots] results
-  char* pinned = nullptr;                    // the same layout in pinned host memory
-  int16_t* scratch = nullptr;                // kIngestScratchBytes: the decoded chunk of an IMA recording (first IMA call)
-  char* flac_dev = nullptr;                  // decoded chunk | work rows (kFlacScratchBytes each) | [kIngestSlots] status words (first FLAC call)
-  int32_t* flac_status = nullptr;            // pinned: [kIngestSlots][kFlacMaxChunkFrames] status words
-  hipEvent_t done[kIngestSlots] = {};
+  DevBlock<> dev;                            // [kIngestSlots] raw | [kIngestSlots] results
+  PinBlock<> pinned;                         // the same layout in pinned host memory
+  DevBlock<int16_t> scratch;                 // kIngestScratchBytes: the decoded chunk of an IMA recording (first IMA call)
+  DevBlock<> flac_dev;                       // decoded chunk | work rows (kFlacScratchBytes each) | [kIngestSlots] status words (first FLAC call)
+  PinBlock<int32_t> flac_status;             // pinned: [kIngestSlots][kFlacMaxChunkFrames] status words
+  Event done[kIngestSlots];
 };
 
 void ingest_free(ttasr_ctx* c) {
-  if (!c->ingest) return;
-  for (auto& f : c->ingest->filters) if (f.second.dev) hipFree(f.second.dev);
-  if (c->ingest->dev) hipFree(c->ingest->dev);
-  if (c->ingest->pinned) hipHostFree(c->ingest->pinned);
-  if (c->ingest->scratch) hipFree(c->ingest->scratch);
-  if (c->ingest->flac_dev) hipFree(c->ingest->flac_dev);
-  if (c->ingest->flac_status) hipHostFree(c->ingest->flac_status);
-  for (auto& e : c->ingest->done) if (e) hipEventDestroy(e);
   delete c->ingest;
   c->ingest = nullptr;
 }
@@ -110,16 +100,9 @@ void ingest_free(ttasr_ctx* c) {
 static int ingest_blocks(ttasr_ctx* c) {
   IngestState* g = c->ingest;
   const size_t bytes = kIngestSlots * (kIngestInBytes + kIngestOutFloats * 4);
-  if (!g->dev) {
-    const hipError_t e = hipMalloc((void**)&g->dev, bytes);
-    if (e != hipSuccess) { g->dev = nullptr; (void)hipGetLastError(); return fail(c, TTASR_E_NOMEM, "ingest device slots (%zu bytes): %s", bytes, hipGetErrorString(e)); }
-  }
-  if (!g->pinned) {
-    const hipError_t e = hipHostMalloc((void**)&g->pinned, bytes, hipHostMallocDefault);
-    if (e != hipSuccess) { g->pinned = nullptr; (void)hipGetLastError(); return fail(c, TTASR_E_NOMEM, "ingest pinned staging (%zu bytes): %s", bytes, hipGetErrorString(e)); }
-  }
-  for (auto& e : g->done)
-    if (!e) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  TRY(g->dev.ensure(c, bytes, "ingest device slots"));
+  TRY(g->pinned.ensure(c, bytes, "ingest pinned staging"));
+  for (auto& e : g->done) TRY(event_create(c, e, hipEventDisableTiming));
   return 0;
 }
 
@@ -133,12 +116,11 @@ static int ingest_filter_dev(ttasr_ctx* c, int32_t rate, const IngestFilter** ou
       const std::vector<double> h = ingest_design(f.plan);
       std::vector<float> t((size_t)f.plan.up * f.plan.L, 0.0f);
       for (int m = 0; m < f.plan.N; ++m) t[(size_t)(m % f.plan.up) * f.plan.L + m / f.plan.up] = (float)h[m];
-      const hipError_t e = hipMalloc((void**)&f.dev, t.size() * 4);
-      if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, TTASR_E_NOMEM, "ingest taps of rate %d (%zu bytes): %s", rate, t.size() * 4, hipGetErrorString(e)); }
+      TRY(f.dev.ensure(c, t.size() * 4, "ingest taps"));
       const hipError_t e2 = hipMemcpy(f.dev, t.data(), t.size() * 4, hipMemcpyHostToDevice);   // `t` is a stack temporary
-      if (e2 != hipSuccess) { hipFree(f.dev); return fail(c, TTASR_E_HIP, "ingest taps of rate %d: %s", rate, hipGetErrorString(e2)); }
+      if (e2 != hipSuccess) return fail(c, TTASR_E_HIP, "ingest taps of rate %d: %s", rate, hipGetErrorString(e2));
     }
-    it = g->filters.emplace(rate, f).first;
+    it = g->filters.emplace(rate, std::move(f)).first;
   }
   *out = &it->second;
   return 0;
@@ -183,26 +165,13 @@ struct IngestPending {
   int rec = 0; int64_t frame0 = 0, n_status = 0;   // FLAC: the recording, the chunk's first FLAC frame and its number of status words
 };
 
-static int ingest_scratch(ttasr_ctx* c) {
-  IngestState* g = c->ingest;
-  if (g->scratch) return 0;
-  const hipError_t e = hipMalloc((void**)&g->scratch, kIngestScratchBytes);
-  if (e != hipSuccess) { g->scratch = nullptr; (void)hipGetLastError(); return fail(c, TTASR_E_NOMEM, "ingest IMA scratch (%zu bytes): %s", kIngestScratchBytes, hipGetErrorString(e)); }
-  return 0;
-}
+static int ingest_scratch(ttasr_ctx* c) { return c->ingest->scratch.ensure(c, kIngestScratchBytes, "ingest IMA scratch"); }
 
 static int ingest_flac_scratch(ttasr_ctx* c) {
   IngestState* g = c->ingest;
-  const size_t status = (size_t)kIngestSlots * kFlacMaxChunkFrames * 4, bytes = 2 * kFlacScratchBytes + status;
-  if (!g->flac_dev) {
-    const hipError_t e = hipMalloc((void**)&g->flac_dev, bytes);
-    if (e != hipSuccess) { g->flac_dev = nullptr; (void)hipGetLastError(); return fail(c, TTASR_E_NOMEM, "ingest FLAC scratch (%zu bytes): %s", bytes, hipGetErrorString(e)); }
-  }
-  if (!g->flac_status) {
-    const hipError_t e = hipHostMalloc((void**)&g->flac_status, status, hipHostMallocDefault);
-    if (e != hipSuccess) { g->flac_status = nullptr; (void)hipGetLastError(); return fail(c, TTASR_E_NOMEM, "ingest FLAC status words (%zu bytes): %s", status, hipGetErrorString(e)); }
-  }
-  return 0;
+  const size_t status = (size_t)kIngestSlots * kFlacMaxChunkFrames * 4;
+  TRY(g->flac_dev.ensure(c, 2 * kFlacScratchBytes + status, "ingest FLAC scratch"));
+  return g->flac_status.ensure(c, status, "ingest FLAC status words");
 }
 
 // A FLAC recording's chunks are whole FLAC frames.  Chunk [a, b) of the frame table owns the outputs whose index k satisfies
@@ -285,7 +254,7 @@ static int ingest_run(ttasr_ctx* c, bool wave, int32_t n, const void* const* raw
         held = n_bytes[i] / ba * ima_spb(ba, channels[i]);
         any_ima = true;
       } else {
-        held = n_bytes[i] / ((is_g711(format[i]) ? 1 : kPcmBytes[format[i]]) * (int64_t)channels[i]);
+        held = n_bytes[i] / (sample_bytes(format[i]) * (int64_t)channels[i]);
       }
       if (n_frames[i] > held) return fail(c, TTASR_E_INVALID, "recording %d: %lld frames, but %lld bytes hold %lld", i, (long long)n_frames[i], (long long)n_bytes[i], (long long)held);
     }
@@ -376,7 +345,7 @@ static int ingest_run(ttasr_ctx* c, bool wave, int32_t n, const void* const* raw
       D.n_frames = (int32_t)nt; D.rate = B.si.rate; D.channels = B.si.channels; D.bits = B.si.bits;
       launch_flac_decode(D, s);
       IngestJob J;
-      J.raw = (const uint8_t*)g->flac_dev;
+      J.raw = (const uint8_t*)g->flac_dev.get();
       J.out = (float*)(d_out + (size_t)slot * kIngestOutFloats * 4);
       J.taps = f->dev;
       J.n_frames = nfr; J.f0 = F[u.fa].first; J.k_begin = u.kb; J.nf = (int32_t)u.samples; J.n_out = (int32_t)(u.ke - u.kb);
@@ -401,7 +370,7 @@ static int ingest_run(ttasr_ctx* c, bool wave, int32_t n, const void* const* raw
     const IngestPlan& P = f->plan;
     const bool ima = format[i] == TTASR_PCM_IMA4;
     const int64_t ba = ima ? block_align[i] : 0, spb = ima ? ima_spb((int)ba, channels[i]) : 1;
-    const int64_t nfr = n_frames[i], fb = ima ? 0 : (int64_t)(is_g711(format[i]) ? 1 : kPcmBytes[format[i]]) * channels[i];
+    const int64_t nfr = n_frames[i], fb = ima ? 0 : (int64_t)sample_bytes(format[i]) * channels[i];
     const int64_t halo = 2 * (int64_t)P.half / P.up + 2;
     const int64_t n_out = ceil_div(nfr * P.up, P.down);
     // frames per chunk: what the raw slot holds beside the halo and what the result slot holds, or the option when it is smaller.
@@ -459,7 +428,7 @@ static int ingest_run(ttasr_ctx* c, bool wave, int32_t n, const void* const* raw
         D.raw = J.raw; D.out = g->scratch; D.n_frames = nf;
         D.n_blocks = (int32_t)n_blk; D.channels = channels[i]; D.block_align = (int32_t)ba; D.spb = (int32_t)spb;
         launch_ima_decode(D, s);
-        J.raw = (const uint8_t*)g->scratch; J.format = TTASR_PCM_S16;
+        J.raw = (const uint8_t*)g->scratch.get(); J.format = TTASR_PCM_S16;
       }
       launch_ingest(J, s);
       if (timing) { HIPCHK(c, hipStreamSynchronize(s)); ms[2] += since(t0); t0 = clk::now(); }

@@ -85,16 +85,17 @@ struct Session {
   bool armed = false; int lang_sot = 0, lang_begin = 0, lang_n = 0;
   std::vector<char> row_det;
   std::vector<Lang> row_lang;
-  int32_t* lang_pin = nullptr;
+  PinBlock<int32_t> lang_pin;
   std::deque<Done> finished;       // finished clips not yet returned by a poll
   // hold mode (ttasr_session_hold): a finished clip keeps its unit - row (greedy) or group (beam) - and its cross-KV slot until
   // ttasr_session_align or ttasr_session_release; its rows are finished rows (done = 1), out of the attention kernels
   bool hold = false;
   std::vector<char> held;          // [maxB] greedy: the row's clip has finished and is held (row_clip keeps its id)
-  int32_t* pin = nullptr;          // pinned: done | n_sampled | sum_logprob | no_speech [maxB] each, tokens [maxB][max_new], admit table
+  PinBlock<int32_t> pin;           // pinned: done | n_sampled | sum_logprob | no_speech [maxB] each, tokens [maxB][max_new], admit table
   size_t pin_words = 0;
-  hipStream_t es = nullptr;        // encode stream (== the context's stream when refill_overlap = 0)
-  hipEvent_t ev_enc0 = nullptr, ev_enc = nullptr, ev_copy = nullptr, ev_dec0 = nullptr, ev_dec1 = nullptr;
+  hipStream_t es = nullptr;        // encode stream: es_own's, or the context's stream when refill_overlap = 0 (not the session's to destroy)
+  OwnStream es_own;
+  Event ev_enc0, ev_enc, ev_copy, ev_dec0, ev_dec1;
   bool overlap = true;
   // statistics (ttasr_session_stats)
   int64_t steps = 0, polls = 0, encodes = 0, clips_encoded = 0, live_row_steps = 0;
@@ -121,10 +122,15 @@ struct Session {
   // has not been collected yet; statistics (ttasr_session_prefill_stats)
   int prefill = 0;
   std::vector<int32_t> row_start;
-  int32_t* pf_pin = nullptr;
-  hipEvent_t ev_pf = nullptr; bool pf_busy = false;
-  std::vector<hipEvent_t> pf_ev; size_t pf_ev_used = 0;
+  PinBlock<int32_t> pf_pin;
+  Event ev_pf; bool pf_busy = false;
+  std::vector<Event> pf_ev; size_t pf_ev_used = 0;
   int64_t pf_passes = 0, pf_clips = 0, pf_positions = 0; double pf_ms = 0;
+  // before the members go: the encode stream is idle when it is destroyed, and the last pass no longer reads its pinned tables
+  ~Session() {
+    if (es_own) hipStreamSynchronize(es_own);
+    if (pf_busy) hipEventSynchronize(ev_pf);
+  }
 };
 
 // words of the table block of one admission (pinned and device): every unit admitted at once with the longest prompt
@@ -138,17 +144,7 @@ int session_refusal(ttasr_ctx* c) {
 }
 
 void session_free(ttasr_ctx* c) {
-  Session* S = c->sess;
-  if (!S) return;
-  if (S->es && S->es != c->stream) { hipStreamSynchronize(S->es); hipStreamDestroy(S->es); }
-  for (hipEvent_t e : {S->ev_enc0, S->ev_enc, S->ev_copy, S->ev_dec0, S->ev_dec1}) if (e) hipEventDestroy(e);
-  if (S->pf_busy) hipEventSynchronize(S->ev_pf);   // the last pass still reads its tables
-  for (hipEvent_t e : S->pf_ev) hipEventDestroy(e);
-  if (S->ev_pf) hipEventDestroy(S->ev_pf);
-  if (S->pin) hipHostFree(S->pin);
-  if (S->lang_pin) hipHostFree(S->lang_pin);
-  if (S->pf_pin) hipHostFree(S->pf_pin);
-  delete S;   // with its scope: the context is back to the defaults of a static search
+  delete c->sess;   // with its scope: the context is back to the defaults of a static search
   c->sess = nullptr;
 }
 
@@ -287,9 +283,8 @@ static int run_prefill_passes(ttasr_ctx* c, Session* S, const std::vector<Prefil
     w = o_items + (size_t)items * 3;
   }
   while (S->pf_ev.size() < 2 * passes.size()) {
-    hipEvent_t e;
-    HIPCHK(c, hipEventCreate(&e));
-    S->pf_ev.push_back(e);
+    S->pf_ev.emplace_back();
+    TRY(event_create(c, S->pf_ev.back()));
   }
   HIPCHK(c, hipMemcpyAsync(c->pf_tab, S->pf_pin, w * 4, hipMemcpyHostToDevice, s));
   for (size_t k = 0; k < passes.size(); ++k) {
@@ -505,23 +500,15 @@ static int session_begin(ttasr_ctx* c, const ttasr_gen_opts* o, int max_prompt, 
   S->overlap = c->refill_overlap;
   S->row_clip.assign(B, -1); S->row_plen.assign(B, 1); S->held.assign(B, 0); S->row_start.assign(B, 0);
   S->pin_words = (size_t)B * (4 + c->rp.max_new) + (size_t)B * (4 + max_prompt);
-  struct Undo { ttasr_ctx* c; Session* s; ~Undo() { if (s) { c->sess = s; session_free(c); } } } undo{c, nullptr};
-  HIPCHK(c, hipHostMalloc((void**)&S->pin, S->pin_words * 4));
+  // every return from here to the end deletes the session with what it owns so far
+  TRY(S->pin.ensure(c, S->pin_words * 4, "session pinned block"));
   if (S->prefill > 0) {
-    hipError_t r = hipHostMalloc((void**)&S->pf_pin, prefill_tab_cap(c) * 4);
-    if (r == hipSuccess) r = hipEventCreate(&S->ev_pf);
-    if (r != hipSuccess) { undo.s = S.release(); return fail(c, TTASR_E_HIP, "session prefill tables: %s", hipGetErrorString(r)); }
+    TRY(S->pf_pin.ensure(c, prefill_tab_cap(c) * 4, "session prefill tables"));
+    TRY(event_create(c, S->ev_pf));
   }
-  for (hipEvent_t* e : {&S->ev_enc0, &S->ev_enc, &S->ev_copy, &S->ev_dec0, &S->ev_dec1}) {
-    const hipError_t r = hipEventCreate(e);
-    if (r != hipSuccess) { undo.s = S.release(); return fail(c, TTASR_E_HIP, "hipEventCreate: %s", hipGetErrorString(r)); }
-  }
-  if (S->overlap) {
-    const hipError_t r = hipStreamCreateWithFlags(&S->es, hipStreamNonBlocking);
-    if (r != hipSuccess) { S->es = nullptr; undo.s = S.release(); return fail(c, TTASR_E_HIP, "hipStreamCreate: %s", hipGetErrorString(r)); }
-  } else {
-    S->es = c->stream;
-  }
+  for (Event* e : {&S->ev_enc0, &S->ev_enc, &S->ev_copy, &S->ev_dec0, &S->ev_dec1}) TRY(event_create(c, *e));
+  if (S->overlap) TRY(stream_create(c, S->es_own));
+  S->es = S->overlap ? S->es_own.h : c->stream;
   // the search state of a static search, except: every row free - finished (done = 1, n_done = max_batch) - at position 0 with a
   // valid token and a one-token prompt
   hipStream_t s = c->stream;
@@ -963,7 +950,7 @@ static int session_detect_language(ttasr_ctx* c, int sot, int lang_begin, int n_
   HIPCHK(c, hipSetDevice(c->device));
   const int B = c->maxB;
   if (!c->lang_sess) TRY(dalloc(c, &c->lang_sess, (size_t)B * 261 * 4));
-  if (!S->lang_pin) HIPCHK(c, hipHostMalloc((void**)&S->lang_pin, (size_t)B * 260 * 4));
+  TRY(S->lang_pin.ensure(c, (size_t)B * 260 * 4, "session language block"));
   // a session that ended between a clip's admission and its detect step left a flag up
   HIPCHK(c, hipMemsetAsync(c->lang_sess, 0, (size_t)B * 4, c->stream));
   if (c->sess_lang_begin != lang_begin || c->sess_lang_n != n_lang || c->sess_lang_stride != S->max_prompt) drop_lang_graphs(c);
@@ -1105,8 +1092,6 @@ static int session_align(ttasr_ctx* c, int n, const int64_t* ids, const AlignBat
 static int session_end(ttasr_ctx* c) {
   if (!c) return TTASR_E_INVALID;
   if (!c->sess) return fail(c, TTASR_E_INVALID, "no session is open");
-  Session* S = c->sess;
-  if (S->es && S->es != c->stream) hipStreamSynchronize(S->es);
   session_free(c);   // the session's scope ends: default decode shape, the rows' finished flags cleared (as after every search)
   hipMemsetAsync(c->st.n_done, 0, 16, c->stream);
   const hipError_t e = hipStreamSynchronize(c->stream);

@@ -307,9 +307,9 @@ int beam_pick(const std::map<std::vector<int>, double>& finished, const std::vec
 
 int beam_exchange(ttasr_ctx* c, int R, int K, BeamExchange& x) {
   const int pps = c->pages_per_seq;
-  if (!c->pinned_beam)   // the largest search this context can run: max_batch rows, beam 7
-    HIPCHK(c, hipHostMalloc((void**)&c->pinned_beam, beam_exchange_words(c->maxB, pps, 8) * 4));
-  int32_t* p = (int32_t*)c->pinned_beam;
+  // the largest search this context can run: max_batch rows, beam 7
+  TRY(c->pinned_beam.ensure(c, beam_exchange_words(c->maxB, pps, 8) * 4, "beam exchange block"));
+  int32_t* p = (int32_t*)c->pinned_beam.get();
   auto take = [&](size_t n) { int32_t* q = p; p += n; return q; };
   x.tbl = take((size_t)R * pps); x.tok = take(R); x.pos = take(R); x.done = take(R); x.state = take(4 * (size_t)R); x.pairs = take(2 * (size_t)R);
   x.lp = (float*)take((size_t)R * K); x.id = take((size_t)R * K); x.ns = (float*)take(R);

@@ -40,8 +40,6 @@ static std::vector<SegSpec> seg_specs() {
   return v;
 }
 
-static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // The scratch block (device) and its pinned twin.  Device: every region of SegBuffers for kSegGroup chunks, the tables a group
 // brings (chunk descriptors, aggregation jobs) and the Hamming window.  Pinned: the PCM of a group, its tables and its results.
 struct SegLayout {
@@ -51,24 +49,22 @@ struct SegLayout {
 static SegLayout seg_layout() {
   SegLayout l;
   const size_t G = kSegGroup;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += up256(bytes); return at; };
-  l.pcm = take(G * kSegChunk * 4); l.desc = take(G * sizeof(SegDesc)); l.jobs = take(G * sizeof(SegAggJob));
-  l.st0 = take(G * 8);
-  l.a1 = take(G * kSegC1 * kSegL1 * 4); l.st1 = take(G * kSegC1 * 8);
-  l.a2 = take(G * kSegC2 * kSegL2 * 4); l.st2 = take(G * kSegC2 * 8);
-  l.a3 = take(G * kSegC2 * kSegT * 4);  l.st3 = take(G * kSegC2 * 8);
-  l.gx = take(G * 2 * kSegT * 512 * 4);
-  l.y0 = take(G * kSegT * 256 * 4); l.y1 = take(G * kSegT * 256 * 4);
-  l.probs = take(G * kSegT * kSegMaxC * 4); l.logits = take(G * kSegT * kSegMaxC * 4);
-  l.score = take((G + kSegCarry) * kSegT * 4);
-  l.agg = take(G * kSegAggRow * 4);
-  l.window = take(kSegT * 4);
-  l.total = o;
-  o = 0;
-  l.p_pcm = take(G * kSegChunk * 4); l.p_desc = take(G * sizeof(SegDesc)); l.p_jobs = take(G * sizeof(SegAggJob));
-  l.p_probs = take(G * kSegT * kSegMaxC * 4); l.p_logits = take(G * kSegT * kSegMaxC * 4); l.p_agg = take(G * kSegAggRow * 4);
-  l.p_total = o;
+  Carve d, p;
+  l.pcm = d.take(G * kSegChunk * 4); l.desc = d.take(G * sizeof(SegDesc)); l.jobs = d.take(G * sizeof(SegAggJob));
+  l.st0 = d.take(G * 8);
+  l.a1 = d.take(G * kSegC1 * kSegL1 * 4); l.st1 = d.take(G * kSegC1 * 8);
+  l.a2 = d.take(G * kSegC2 * kSegL2 * 4); l.st2 = d.take(G * kSegC2 * 8);
+  l.a3 = d.take(G * kSegC2 * kSegT * 4);  l.st3 = d.take(G * kSegC2 * 8);
+  l.gx = d.take(G * 2 * kSegT * 512 * 4);
+  l.y0 = d.take(G * kSegT * 256 * 4); l.y1 = d.take(G * kSegT * 256 * 4);
+  l.probs = d.take(G * kSegT * kSegMaxC * 4); l.logits = d.take(G * kSegT * kSegMaxC * 4);
+  l.score = d.take((G + kSegCarry) * kSegT * 4);
+  l.agg = d.take(G * kSegAggRow * 4);
+  l.window = d.take(kSegT * 4);
+  l.total = d.used;
+  l.p_pcm = p.take(G * kSegChunk * 4); l.p_desc = p.take(G * sizeof(SegDesc)); l.p_jobs = p.take(G * sizeof(SegAggJob));
+  l.p_probs = p.take(G * kSegT * kSegMaxC * 4); l.p_logits = p.take(G * kSegT * kSegMaxC * 4); l.p_agg = p.take(G * kSegAggRow * 4);
+  l.p_total = p.used;
   return l;
 }
 
@@ -81,44 +77,27 @@ struct SegState {
   int c_weight = 0, c_bias = 0;                // C as classifier.weight and classifier.bias brought it
   bool finalized = false;
   SegWeights w{};
-  char* scratch = nullptr; char* pinned = nullptr;
+  DevBlock<> scratch; PinBlock<> pinned;
 };
 
 void seg_free(ttasr_ctx* c) {
-  if (!c->seg) return;
-  if (c->seg->scratch) hipFree(c->seg->scratch);
-  if (c->seg->pinned) hipHostFree(c->seg->pinned);
   delete c->seg;
   c->seg = nullptr;
 }
 
-// Both blocks, allocated by the first call; a request that cannot be allocated leaves the context without them (the next call
-// allocates again) and otherwise as it was.
+// Both blocks, allocated by the first call; the device block's first allocation brings the Hamming window
 static int seg_blocks(ttasr_ctx* c) {
   SegState* v = c->seg;
   const SegLayout l = seg_layout();
   if (!v->scratch) {
-    const hipError_t e = hipMalloc((void**)&v->scratch, l.total);
-    if (e != hipSuccess) {
-      v->scratch = nullptr;
-      (void)hipGetLastError();
-      return fail(c, TTASR_E_NOMEM, "segmentation scratch (%zu bytes): %s", l.total, hipGetErrorString(e));
-    }
+    TRY(v->scratch.ensure(c, l.total, "segmentation scratch"));
     // w = np.hamming(293) rounded to f32
     std::vector<float> win(kSegT);
     for (int i = 0; i < kSegT; ++i) win[i] = (float)(0.54 - 0.46 * cos(2.0 * 3.14159265358979323846 * i / (kSegT - 1)));
     HIPCHK(c, hipMemcpyAsync(v->scratch + l.window, win.data(), kSegT * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));   // `win` is a stack temporary
   }
-  if (!v->pinned) {
-    const hipError_t e = hipHostMalloc((void**)&v->pinned, l.p_total, hipHostMallocDefault);
-    if (e != hipSuccess) {
-      v->pinned = nullptr;
-      (void)hipGetLastError();
-      return fail(c, TTASR_E_NOMEM, "segmentation pinned staging (%zu bytes): %s", l.p_total, hipGetErrorString(e));
-    }
-  }
-  return 0;
+  return v->pinned.ensure(c, l.p_total, "segmentation pinned staging");
 }
 
 static int seg_load(ttasr_ctx* c, const char* name, const float* data, const int64_t* dims, int32_t ndim) {

@@ -35,10 +35,11 @@ struct VadState {
   bool finalized = false;
   VadWeights w{};
   // scratch: pcm [files][kVadSlot] | gx [files][C][512] | out [files][2][C] | state [files][256] | nf [files] | slot [files]
-  char* scratch = nullptr; int scratch_files = 0;
+  DevBlock<> scratch; int scratch_files = 0;
   // pinned: pcm slots [kVadPinSlots][kVadSlot] | out [max_batch][2][C] | nf [max_batch] | slot [max_batch]
-  char* pinned = nullptr;
-  VadStreams* streams = nullptr;  // created by the first ttasr_vad_stream_open
+  PinBlock<> pinned;
+  std::unique_ptr<VadStreams> streams;   // created by the first ttasr_vad_stream_open
+  ~VadState();                           // where VadStreams is complete
 };
 
 // One row of a pass through the chunk loop, as ONE sequence of samples: positions [-64, 0) the context in front of the first frame
@@ -88,14 +89,14 @@ struct WireRow {
 };
 
 struct VadStreams {
-  float* table = nullptr;                       // [TTASR_VAD_MAX_STREAMS][256], device
+  DevBlock<float> table;                        // [TTASR_VAD_MAX_STREAMS][256], device
   int n_open = 0;
   std::vector<VadStream> s = std::vector<VadStream>(TTASR_VAD_MAX_STREAMS);
   std::vector<VadRow> rows = std::vector<VadRow>(TTASR_VAD_MAX_STREAMS);   // a push's rows (n <= open streams): a push never allocates
   std::vector<uint8_t> seen = std::vector<uint8_t>(TTASR_VAD_MAX_STREAMS);
   // wire streams (the first ttasr_vad_stream_open_wire allocates): the history table [2][TTASR_VAD_MAX_STREAMS][256], the device
   // block job table | raw pool | result pool and its pinned twin, and a wire push's rows with the float push each chunk hands on
-  float* hist = nullptr; char* wire_dev = nullptr; char* wire_pin = nullptr;
+  DevBlock<float> hist; DevBlock<> wire_dev; PinBlock<> wire_pin;
   std::vector<WireRow> wrows;
   std::vector<int32_t> sub_ids, sub_fin, sub_frames, sub_row;
   std::vector<const float*> sub_pcm; std::vector<int64_t> sub_ns; std::vector<float*> sub_probs, sub_logits;
@@ -105,65 +106,39 @@ static void vad_stream_clear(VadStream& st) {
   st.F = st.K = 0; st.n_raw = 0;
 }
 
+VadState::~VadState() = default;
 void vad_free(ttasr_ctx* c) {
-  if (!c->vad) return;
-  if (c->vad->scratch) hipFree(c->vad->scratch);
-  if (c->vad->pinned) hipHostFree(c->vad->pinned);
-  if (c->vad->streams) {
-    if (c->vad->streams->table) hipFree(c->vad->streams->table);
-    if (c->vad->streams->hist) hipFree(c->vad->streams->hist);
-    if (c->vad->streams->wire_dev) hipFree(c->vad->streams->wire_dev);
-    if (c->vad->streams->wire_pin) hipHostFree(c->vad->streams->wire_pin);
-    delete c->vad->streams;
-  }
   delete c->vad;
   c->vad = nullptr;
 }
 
-static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 struct VadScratch { size_t pcm, gx, out, state, nf, slot, total; };
 static VadScratch vad_scratch_layout(int files) {
   VadScratch l;
-  l.pcm = 0;
-  l.gx = l.pcm + up256((size_t)files * kVadSlot * 4);
-  l.out = l.gx + up256((size_t)files * kVadChunk * 512 * 4);
-  l.state = l.out + up256((size_t)files * 2 * kVadChunk * 4);
-  l.nf = l.state + up256((size_t)files * 256 * 4);
-  l.slot = l.nf + up256((size_t)files * 4);
-  l.total = l.slot + up256((size_t)files * 4);
+  Carve cv;
+  l.pcm = cv.take((size_t)files * kVadSlot * 4);
+  l.gx = cv.take((size_t)files * kVadChunk * 512 * 4);
+  l.out = cv.take((size_t)files * 2 * kVadChunk * 4);
+  l.state = cv.take((size_t)files * 256 * 4);
+  l.nf = cv.take((size_t)files * 4);
+  l.slot = cv.take((size_t)files * 4);
+  l.total = cv.used;
   return l;
 }
 
-// One device block for `files` recordings, grown to the largest request.  A request that cannot be allocated leaves the context
-// without a block (the next call allocates again) and otherwise as it was.
+// One device block for `files` recordings, grown to the largest request (the layout is that of scratch_files recordings)
 static int vad_scratch(ttasr_ctx* c, int files) {
   VadState* v = c->vad;
   if (files <= v->scratch_files) return 0;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (v->scratch) hipFree(v->scratch);
-  v->scratch = nullptr; v->scratch_files = 0;
-  const size_t bytes = vad_scratch_layout(files).total;
-  const hipError_t e = hipMalloc((void**)&v->scratch, bytes);
-  if (e != hipSuccess) {
-    v->scratch = nullptr;
-    (void)hipGetLastError();
-    return fail(c, TTASR_E_NOMEM, "VAD scratch (%zu bytes for %d recordings): %s", bytes, files, hipGetErrorString(e));
-  }
-  v->scratch_files = files;
-  return 0;
+  const int rc = v->scratch.ensure(c, vad_scratch_layout(files).total, "VAD scratch");
+  if (!v->scratch) v->scratch_files = 0;   // could not be allocated: the next call allocates again
+  else if (rc == 0) v->scratch_files = files;
+  return rc;
 }
 
 static int vad_pinned(ttasr_ctx* c) {
-  VadState* v = c->vad;
-  if (v->pinned) return 0;
-  const size_t bytes = (size_t)kVadPinSlots * kVadSlot * 4 + (size_t)c->maxB * 2 * kVadChunk * 4 + (size_t)c->maxB * 8;
-  const hipError_t e = hipHostMalloc((void**)&v->pinned, bytes, hipHostMallocDefault);
-  if (e != hipSuccess) {
-    v->pinned = nullptr;
-    (void)hipGetLastError();
-    return fail(c, TTASR_E_NOMEM, "VAD pinned staging (%zu bytes): %s", bytes, hipGetErrorString(e));
-  }
-  return 0;
+  return c->vad->pinned.ensure(c, (size_t)kVadPinSlots * kVadSlot * 4 + (size_t)c->maxB * 2 * kVadChunk * 4 + (size_t)c->maxB * 8,
+                               "VAD pinned staging");
 }
 
 static int vad_load(ttasr_ctx* c, const char* name, const float* data, const int64_t* dims, int32_t ndim) {
@@ -234,7 +209,7 @@ static int vad_run(ttasr_ctx* c, const VadRow* rows, int n, float* d_state, cons
   float* d_out = (float*)(v->scratch + l.out);
   int32_t* d_nf = (int32_t*)(v->scratch + l.nf);
   int32_t* d_slot = slots ? (int32_t*)(v->scratch + l.slot) : nullptr;
-  float* p_pcm = (float*)v->pinned;
+  float* p_pcm = (float*)v->pinned.get();
   float* p_out = p_pcm + (size_t)kVadPinSlots * kVadSlot;
   int32_t* p_nf = (int32_t*)(p_out + (size_t)c->maxB * 2 * kVadChunk);
   int32_t* p_slot = p_nf + c->maxB;
@@ -304,27 +279,11 @@ static int vad_probs(ttasr_ctx* c, int32_t n, const float* const* pcm, const int
 
 // ---- streams ----
 
-static int sample_bytes(int32_t format) {   // 0: no stream format
-  static const int pcm[6] = {1, 2, 3, 4, 4, 8};
-  if (format >= TTASR_PCM_U8 && format <= TTASR_PCM_F64) return pcm[format];
-  return format == TTASR_PCM_ALAW || format == TTASR_PCM_ULAW ? 1 : 0;
-}
-
 // What wire streams need beside the float streams' blocks; a failed allocation leaves what exists in place for the next open.
 static int vad_wire_blocks(ttasr_ctx* c, VadStreams* S) {
-  const struct { void** p; size_t bytes; bool pinned; const char* what; } blk[3] = {
-      {(void**)&S->hist, (size_t)2 * TTASR_VAD_MAX_STREAMS * 256 * 4, false, "wire stream history table"},
-      {(void**)&S->wire_dev, kWireJobBytes + kWireRawBytes + kWireOutFloats * 4, false, "wire stream device pools"},
-      {(void**)&S->wire_pin, kWireJobBytes + kWireRawBytes + kWireOutFloats * 4, true, "wire stream pinned pools"}};
-  for (const auto& b : blk) {
-    if (*b.p) continue;
-    const hipError_t e = b.pinned ? hipHostMalloc(b.p, b.bytes, hipHostMallocDefault) : hipMalloc(b.p, b.bytes);
-    if (e != hipSuccess) {
-      *b.p = nullptr;
-      (void)hipGetLastError();
-      return fail(c, TTASR_E_NOMEM, "%s (%zu bytes): %s", b.what, b.bytes, hipGetErrorString(e));
-    }
-  }
+  TRY(S->hist.ensure(c, (size_t)2 * TTASR_VAD_MAX_STREAMS * 256 * 4, "wire stream history table"));
+  TRY(S->wire_dev.ensure(c, kWireJobBytes + kWireRawBytes + kWireOutFloats * 4, "wire stream device pools"));
+  TRY(S->wire_pin.ensure(c, kWireJobBytes + kWireRawBytes + kWireOutFloats * 4, "wire stream pinned pools"));
   if (S->wrows.empty()) {
     const size_t m = TTASR_VAD_MAX_STREAMS;
     S->wrows.resize(m); S->sub_ids.resize(m); S->sub_fin.resize(m); S->sub_frames.resize(m); S->sub_row.resize(m);
@@ -346,8 +305,8 @@ static int vad_stream_open(ttasr_ctx* c, const int32_t* wire, int32_t* out_id) {
   }
   TRY(session_refusal(c));   // the first open allocates
   HIPCHK(c, hipSetDevice(c->device));
-  if (!v->streams) v->streams = new VadStreams();
-  VadStreams* S = v->streams;
+  if (!v->streams) v->streams.reset(new VadStreams());
+  VadStreams* S = v->streams.get();
   if (S->n_open >= TTASR_VAD_MAX_STREAMS) return fail(c, TTASR_E_INVALID, "all %d VAD streams of a context are open", S->n_open);
   WirePlan plan;
   if (wire) {
@@ -355,15 +314,7 @@ static int vad_stream_open(ttasr_ctx* c, const int32_t* wire, int32_t* out_id) {
     TRY(wire_plan_dev(c, wire[0], &plan));
   }
   // everything a push ever needs: the table, the pinned staging, the scratch block for groups of max_batch rows
-  if (!S->table) {
-    const size_t bytes = (size_t)TTASR_VAD_MAX_STREAMS * 256 * 4;
-    const hipError_t e = hipMalloc((void**)&S->table, bytes);
-    if (e != hipSuccess) {
-      S->table = nullptr;
-      (void)hipGetLastError();
-      return fail(c, TTASR_E_NOMEM, "VAD stream table (%zu bytes): %s", bytes, hipGetErrorString(e));
-    }
-  }
+  TRY(S->table.ensure(c, (size_t)TTASR_VAD_MAX_STREAMS * 256 * 4, "VAD stream table"));
   TRY(vad_pinned(c));
   TRY(vad_scratch(c, c->maxB));
   int id = 0;
@@ -381,7 +332,7 @@ static int vad_stream_open(ttasr_ctx* c, const int32_t* wire, int32_t* out_id) {
 }
 
 static VadStream* vad_stream_of(ttasr_ctx* c, int32_t id) {
-  VadStreams* S = c->vad ? c->vad->streams : nullptr;
+  VadStreams* S = c->vad ? c->vad->streams.get() : nullptr;
   return S && id >= 0 && id < TTASR_VAD_MAX_STREAMS && S->s[id].open ? &S->s[id] : nullptr;
 }
 
@@ -391,7 +342,7 @@ static int vad_stream_push(ttasr_ctx* c, bool wire, int32_t n, const int32_t* id
                            const int32_t* finish, float* const* out_probs, float* const* out_logits, int32_t* out_frames) {
   VadState* v = c->vad;
   if (!v || !v->finalized) return fail(c, TTASR_E_INVALID, "VAD weights not finalized (ttasr_vad_load_tensor, ttasr_vad_finalize first)");
-  VadStreams* S = v->streams;
+  VadStreams* S = v->streams.get();
   const int n_open = S ? S->n_open : 0;
   if (n < 1 || n > n_open) return fail(c, TTASR_E_INVALID, "n %d outside [1, open streams = %d]", n, n_open);
   if (!ids || !pcm || !ns || !out_probs || !out_frames) return fail(c, TTASR_E_INVALID, "NULL argument");
@@ -458,7 +409,7 @@ static int vad_stream_push_wire(ttasr_ctx* c, int32_t n, const int32_t* ids, con
                                 float* const* out_probs, float* const* out_logits, int32_t* out_frames) {
   VadState* v = c->vad;
   if (!v || !v->finalized) return fail(c, TTASR_E_INVALID, "VAD weights not finalized (ttasr_vad_load_tensor, ttasr_vad_finalize first)");
-  VadStreams* S = v->streams;
+  VadStreams* S = v->streams.get();
   const int n_open = S ? S->n_open : 0;
   if (n < 1 || n > n_open) return fail(c, TTASR_E_INVALID, "n %d outside [1, open streams = %d]", n, n_open);
   if (!ids || !raw || !n_bytes || !out_len || !out_probs || !out_frames) return fail(c, TTASR_E_INVALID, "NULL argument");
@@ -486,11 +437,11 @@ static int vad_stream_push_wire(ttasr_ctx* c, int32_t n, const int32_t* ids, con
   }
   // from here on a failure leaves the streams of this call reset
   hipStream_t s = c->stream;
-  WireJob* const p_jobs = (WireJob*)S->wire_pin;
-  uint8_t* const p_raw = (uint8_t*)S->wire_pin + kWireJobBytes;
+  WireJob* const p_jobs = (WireJob*)S->wire_pin.get();
+  uint8_t* const p_raw = (uint8_t*)S->wire_pin.get() + kWireJobBytes;
   float* const p_out = (float*)(S->wire_pin + kWireJobBytes + kWireRawBytes);
-  const WireJob* const d_jobs = (const WireJob*)S->wire_dev;
-  uint8_t* const d_raw = (uint8_t*)S->wire_dev + kWireJobBytes;
+  const WireJob* const d_jobs = (const WireJob*)S->wire_dev.get();
+  uint8_t* const d_raw = (uint8_t*)S->wire_dev.get() + kWireJobBytes;
   float* const d_out = (float*)(S->wire_dev + kWireJobBytes + kWireRawBytes);
   // every row's share of the pools: a chunk takes the frames whose bytes and whose results fit it (or option wire_chunk)
   const int64_t share_raw = (int64_t)(kWireRawBytes / n) & ~(int64_t)63, share_out = (int64_t)(kWireOutFloats / n);
