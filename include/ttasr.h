@@ -138,6 +138,15 @@ TTASR_API int ttasr_log_mel(ttasr_ctx* ctx, const float* pcm, int64_t pcm_stride
 TTASR_API int ttasr_log_mel_windows(ttasr_ctx* ctx, const float* const* file_pcm_of_host, const int64_t* file_samples_of_host,
                           const int64_t* seek_frames_host, int32_t B, const float* floor_max_host, float* out_window_max_host,
                           float* out_mel_host);
+/* The same with windows that may END before the recording does (clip_timestamps of the window loop): window b keeps the
+ * whole-file STFT's frames [seek, seek + min(n_frames_host[b], 2*n_audio_ctx, frames left in the file)).  The cut limits which
+ * frames are valid, not which samples are read: the frames just before the cut see their true neighbour samples BEYOND it, so the
+ * kept frames are bit for bit those of the uncut window.  Every later frame is 0 in feature space (pad_or_trim of the feature
+ * slice features[:, seek:seek + n]) and out_window_max_host covers the kept frames only.  n_frames_host[b] < 1 (or NULL):
+ * TTASR_E_INVALID.  ttasr_log_mel_windows is this call without a cut. */
+TTASR_API int ttasr_log_mel_windows_cut(ttasr_ctx* ctx, const float* const* file_pcm_of_host, const int64_t* file_samples_of_host,
+                          const int64_t* seek_frames_host, int32_t B, const float* floor_max_host, float* out_window_max_host,
+                          float* out_mel_host, const int64_t* n_frames_host);
 /* Test hook: place a caller-computed mel [B][n_mels][2*n_audio_ctx] as the encoder input. */
 TTASR_API int ttasr_set_mel(ttasr_ctx* ctx, const float* mel_host, int32_t B);
 

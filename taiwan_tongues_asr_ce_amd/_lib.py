@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(HERE, "libttasr.so")
 # every symbol include/ttasr.h declares (tests check the .so exports exactly these)
 SYMBOLS = [
     "ttasr_create", "ttasr_create_shared", "ttasr_destroy", "ttasr_last_error", "ttasr_version", "ttasr_load_tensor", "ttasr_load_tensor_device",
-    "ttasr_finalize_weights", "ttasr_log_mel", "ttasr_log_mel_windows", "ttasr_set_mel", "ttasr_encode", "ttasr_set_encoder_output",
+    "ttasr_finalize_weights", "ttasr_log_mel", "ttasr_log_mel_windows", "ttasr_log_mel_windows_cut", "ttasr_set_mel", "ttasr_encode", "ttasr_set_encoder_output",
     "ttasr_get_cross_kv", "ttasr_get_cross_kv_fp8", "ttasr_cross_attn_probe", "ttasr_align_attn_probe",
     "ttasr_self_kv_fill", "ttasr_self_kv_set", "ttasr_self_kv_get", "ttasr_self_attn_probe", "ttasr_set_audio_ctx", "ttasr_generate", "ttasr_generate_capped", "ttasr_generate_beam", "ttasr_generate_beam_ragged", "ttasr_generate_sample", "ttasr_decode_reset", "ttasr_decode_step", "ttasr_apply_rules", "ttasr_align", "ttasr_dtw",
     "ttasr_set_option", "ttasr_phase_ms", "ttasr_beam_profile", "ttasr_encoder_kernel_ms", "ttasr_bench_kernel", "ttasr_bench_kernel_signature", "ttasr_sync",
@@ -89,6 +89,7 @@ def load() -> C.CDLL:
     lib.ttasr_finalize_weights.argtypes = [vp]
     lib.ttasr_log_mel.argtypes = [vp, vp, i64, i64p, i32, i32, vp]
     lib.ttasr_log_mel_windows.argtypes = [vp, C.POINTER(vp), i64p, i64p, i32, vp, vp, vp]
+    lib.ttasr_log_mel_windows_cut.argtypes = [vp, C.POINTER(vp), i64p, i64p, i32, vp, vp, vp, i64p]
     lib.ttasr_set_mel.argtypes = [vp, vp, i32]
     lib.ttasr_encode.argtypes = [vp, i32, vp]
     lib.ttasr_set_encoder_output.argtypes = [vp, vp, i32]

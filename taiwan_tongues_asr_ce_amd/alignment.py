@@ -253,3 +253,41 @@ def add_word_timestamps(segments: List[dict], alignment: List[dict], time_offset
             else:
                 seg["end"] = words[-1].end
         seg["words"] = words
+
+
+# ---- hallucination_silence_threshold: which words look invented ---------------------------------------------------------
+# openai-whisper's transcribe() (word_anomaly_score / is_segment_anomaly), which faster-whisper copies, restated from memory:
+# unpinned.  tests/test_hallucination_silence_host.py pins this restatement with tables around every constant.
+ANOMALY_PUNCTUATION = "\"'“¿([{-\"'.。,，!！?？:：”)]}、"
+
+
+def _word_fields(word) -> Tuple[str, float, float, float]:
+    """(text, start, end, probability) of a Word or of a {word, start, end, probability} dict."""
+    if isinstance(word, dict):
+        return word["word"], word["start"], word["end"], word["probability"]
+    return word.word, word.start, word.end, word.probability
+
+
+def word_anomaly_score(word) -> float:
+    """How unlikely one aligned word is to be speech: +1 for a probability below 0.15, +15 per second short of 0.133 s, +1 per
+    second beyond 2 s."""
+    _, start, end, probability = _word_fields(word)
+    duration = end - start
+    score = 0.0
+    if probability < 0.15:
+        score += 1.0
+    if duration < 0.133:
+        score += (0.133 - duration) * 15
+    if duration > 2.0:
+        score += duration - 2.0
+    return score
+
+
+def is_segment_anomaly(segment) -> bool:
+    """True when the first 8 words of the segment (a dict with "words", or None) that are not pure punctuation score 3 or more
+    together, or nearly one each (sum + 0.01 >= their number); False without words."""
+    if segment is None or not segment.get("words"):
+        return False
+    words = [w for w in segment["words"] if _word_fields(w)[0] not in ANOMALY_PUNCTUATION][:8]
+    score = sum(word_anomaly_score(w) for w in words)
+    return score >= 3 or score + 0.01 >= len(words)

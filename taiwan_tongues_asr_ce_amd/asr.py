@@ -139,7 +139,9 @@ class MI355XWhisperASR(ASRInterface):
     def transcribe_path(self, path: str, **kw):
         """A FILE through the adapter's default options (the reference's file service drives the same model object with paths:
         file_asr.py:457-465) -> (segments, info); with device_resample=True on the adapter the file is ingested on the device,
-        with batched=True it is decoded by the batched pipeline."""
+        with batched=True it is decoded by the batched pipeline.  Keywords go to WhisperModel.transcribe as they are -
+        clip_timestamps, hallucination_silence_threshold, prompt_reset_on_temperature and suppress_tokens among them (with
+        batched=True the pipeline's own clip_timestamps meaning holds)."""
         opts = dict(self.default_transcribe_kwargs, language="zh")
         opts.update(kw)
         pick = getattr(self, "audio_channel", None)

@@ -66,8 +66,9 @@ def _probe(path: str) -> str:
 
 def transcribe_file(model, audio_file: str, load_audio: Callable = _load_audio, log: Callable = print, segments=None,
                     language: Optional[str] = TRANSCRIBE_KWARGS["language"], info=None, batched: bool = False,
-                    word_timestamps: bool = False) -> Dict:
-    """One unit of work → one entry of `detailed_results`.  word_timestamps: the segments carry words (a file transcribed here
+                    word_timestamps: bool = False, options: Optional[Dict] = None) -> Dict:
+    """options: further transcribe() keywords of a file transcribed here (clip_timestamps, hallucination_silence_threshold).
+    One unit of work → one entry of `detailed_results`.  word_timestamps: the segments carry words (a file transcribed here
     is transcribed with them); they are written to `<name>_words.json` beside `<name>_asr.txt`.  `segments`: already transcribed (group mode, with its `info`), else
     runs it.  language=None (`--language auto`): the language is detected, and the entry names it with its probability.
     batched: the file goes through the batched pipeline (WhisperModel.transcribe_batched), which has no previous-text option."""
@@ -80,7 +81,7 @@ def transcribe_file(model, audio_file: str, load_audio: Callable = _load_audio, 
             kw = {k: v for k, v in TRANSCRIBE_KWARGS.items() if k != "condition_on_previous_text"}
             segments, info = model.transcribe_batched(load_audio(audio_file), **dict(kw, language=language))
         elif segments is None:
-            extra = dict(word_timestamps=True) if word_timestamps else {}
+            extra = dict(options or {}, **(dict(word_timestamps=True) if word_timestamps else {}))
             segments, info = model.transcribe(load_audio(audio_file), **dict(TRANSCRIBE_KWARGS, language=language, **extra))
         segments = list(segments)                               # consumes the lazy generator: this is where it runs
         text = "".join(seg.text for seg in segments)
@@ -146,8 +147,14 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
                          cross_kv_fp8: bool = False, language: Optional[str] = TRANSCRIBE_KWARGS["language"],
                          detect_in_session: bool = False, session_prefill: int = 0, vad_model=None,
                          device_resample: bool = False, batched: bool = False, word_timestamps: bool = False,
-                         audio_channel=None) -> Optional[Dict]:
-    """audio_channel (`--audio-channel mix|left|right|N`): None / "mix" averages a file's channels as before; "left", "right" or
+                         audio_channel=None, clip_timestamps: str = "0",
+                         hallucination_silence_threshold: Optional[float] = None) -> Optional[Dict]:
+    """clip_timestamps (`--clip-timestamps "a,b,..."`): only those spans (seconds: start,end,start,end,...) of every file are
+    decoded (WhisperModel.transcribe).  hallucination_silence_threshold (`--hallucination-silence-threshold S`): silence longer
+    than S seconds around text whose words look invented is skipped; it works on word times and so implies word_timestamps.
+    Both go with the one-by-one and the lock-step form; refused with continuous (ValueError before a model is built) and with
+    batched, which has its own clip_timestamps meaning.
+    audio_channel (`--audio-channel mix|left|right|N`): None / "mix" averages a file's channels as before; "left", "right" or
     an index from 0 transcribes that channel alone (two-party call recordings; the reference service's audioChannel 0 / 1 / 2 is
     mix / left / right).  On the host loader and, with device_resample, in the group's one device call.
     word_timestamps (`--word-timestamps`, with the lock-step form or continuous; not with batched): every file's segments are
@@ -175,6 +182,17 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
         raise ValueError("batched and continuous exclude each other (one file's groups, or many files' windows, per session)")
     if batched and word_timestamps:
         raise ValueError("word_timestamps goes with the lock-step form or continuous, not with batched")
+    options = {}
+    if clip_timestamps is not None and str(clip_timestamps).strip() not in ("", "0"):
+        options["clip_timestamps"] = clip_timestamps
+    if hallucination_silence_threshold is not None:
+        options["hallucination_silence_threshold"] = float(hallucination_silence_threshold)
+        word_timestamps = True
+    if options and continuous:
+        from .model import refuse_in_session
+        refuse_in_session("process_audio_folder(continuous=True) / --continuous", clip_timestamps, hallucination_silence_threshold)
+    if options and batched:
+        raise ValueError("clip_timestamps / hallucination_silence_threshold go with the one-by-one or the lock-step form, not with batched")
     if continuous:
         if int(pipeline_depth or getattr(model, "pipeline_depth", 1)) > 1:
             log("continuous mode runs one session on one engine context: pipeline depth 1")
@@ -200,7 +218,8 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
     if batched:
         results = [transcribe_file(model, f, load_audio, log, language=language, batched=True) for f in mine]
     elif many is None or group < 2 or getattr(model, "vad_speech_prob_fn", None) is not None:
-        results = [transcribe_file(model, f, load_audio, log, language=language, word_timestamps=word_timestamps) for f in mine]
+        results = [transcribe_file(model, f, load_audio, log, language=language, word_timestamps=word_timestamps, options=options)
+                   for f in mine]
     else:
         # MI355X-first: `group` files advance in lock step through one engine pass per window round; every file keeps the
         # sequential algorithm (own seek / prompt / fallback), so the outputs equal the one-by-one run
@@ -222,6 +241,7 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
                 kw["audio_channel"] = pick
         if word_timestamps:
             kw["word_timestamps"] = True
+        kw.update(options)   # with vad_filter and clips, transcribe_many decides per file and warns, as transcribe does
         depth0 = max(1, int(pipeline_depth or getattr(model, "pipeline_depth", 1)))
         if group_files <= 0 and depth0 > 1 and len(mine) < group * depth0:
             group = max(1, -(-len(mine) // depth0))            # few files: one group per context rather than one big group and an idle lane
@@ -264,7 +284,7 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
                     log(f"group transcription failed ({e}); retrying file by file")
                     pairs = [(None, None)] * len(part)
                 results.extend(transcribe_file(model, f, load_audio, log, segments=sg, language=language, info=nfo,
-                                               word_timestamps=word_timestamps)
+                                               word_timestamps=word_timestamps, options=options)
                                for f, (sg, nfo) in zip(part, pairs))
     if world > 1:
         import torch.distributed as dist
@@ -327,6 +347,12 @@ def build_parser() -> argparse.ArgumentParser:
                     help="opt-in: word-level timestamps; every file's segments with their words are written to <name>_words.json "
                          "beside <name>_asr.txt.  With --continuous the windows that settle in one poll are aligned in one device pass "
                          "whose result for a file does not depend on the other files; not together with --batched")
+    ap.add_argument("--clip-timestamps", default="0", metavar="a,b,...",
+                    help="decode only these spans of every file: seconds as start,end,start,end,... (an odd count runs the last span "
+                         "to the end of the file); not together with --continuous or --batched")
+    ap.add_argument("--hallucination-silence-threshold", type=float, default=None, metavar="S",
+                    help="skip silence longer than S seconds around text whose words look invented; implies --word-timestamps; not "
+                         "together with --continuous or --batched")
     ap.add_argument("--device-resample", action="store_true",
                     help="opt-in: convert, downmix and resample each group's files in one device call instead of file by file on "
                          "the host (RIFF/WAVE of any PCM / float format; FLAC files, decoded on the device frame by frame; other "
@@ -358,6 +384,11 @@ def main(argv=None) -> int:
     if args.batched and args.word_timestamps:
         print("--word-timestamps goes with the lock-step form or --continuous, not with --batched")
         return 1
+    if args.clip_timestamps.strip() not in ("", "0") or args.hallucination_silence_threshold is not None:
+        if args.continuous or args.batched:
+            print("--clip-timestamps / --hallucination-silence-threshold go with the one-by-one or the lock-step form "
+                  "(--group-files), not with --continuous or --batched")
+            return 1
     if not os.path.exists(args.folder):
         print(f"folder does not exist: {args.folder}")
         return 1
@@ -371,7 +402,8 @@ def main(argv=None) -> int:
                          cross_kv_fp8=args.xkv_fp8, language=None if args.language == "auto" else args.language,
                          detect_in_session=args.detect_in_session, session_prefill=args.session_prefill,
                          vad_model=args.vad_model, device_resample=args.device_resample, batched=args.batched,
-                         word_timestamps=args.word_timestamps, audio_channel=args.audio_channel)
+                         word_timestamps=args.word_timestamps, audio_channel=args.audio_channel,
+                         clip_timestamps=args.clip_timestamps, hallucination_silence_threshold=args.hallucination_silence_threshold)
     return 0
 
 

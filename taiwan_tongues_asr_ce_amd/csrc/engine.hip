@@ -253,13 +253,19 @@ int ttasr_log_mel(ttasr_ctx* c, const float* pcm, int64_t pcm_stride, const int6
   });
 }
 
-int ttasr_log_mel_windows(ttasr_ctx* c, const float* const* file_pcm_of, const int64_t* file_samples_of, const int64_t* seek_frames,
-                          int32_t B, const float* floor_max, float* out_window_max, float* out_mel) {
+// ttasr_log_mel_windows_cut (cut_required; n_frames must be given) and ttasr_log_mel_windows (n_frames == nullptr: no cut).  A cut only lowers a window's valid-frame count
+// (geom[2]): the samples copied and read stay those of the uncut window, so the kept frames are the whole-file STFT's, bit for bit.
+static int log_mel_windows(ttasr_ctx* c, const float* const* file_pcm_of, const int64_t* file_samples_of, const int64_t* seek_frames,
+                           const int64_t* n_frames, bool cut_required, int32_t B, const float* floor_max, float* out_window_max,
+                           float* out_mel) {
   return guarded(c, [&]() -> int {
   if (!c) return TTASR_E_INVALID;
   TRY(session_refusal(c));
   if (B < 1 || B > c->maxB) return fail(c, TTASR_E_INVALID, "batch %d outside [1, %d]", B, c->maxB);
   if (!file_pcm_of || !file_samples_of || !seek_frames) return fail(c, TTASR_E_INVALID, "NULL argument");
+  if (cut_required && !n_frames) return fail(c, TTASR_E_INVALID, "n_frames is NULL");
+  for (int b = 0; n_frames && b < B; ++b)
+    if (n_frames[b] < 1) return fail(c, TTASR_E_INVALID, "n_frames[%d]=%lld: a window keeps at least one frame", b, (long long)n_frames[b]);
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const int64_t stride = c->n_samples + 512;
@@ -275,6 +281,7 @@ int ttasr_log_mel_windows(ttasr_ctx* c, const float* const* file_pcm_of, const i
     const WindowSpan w = window_span(c, file_samples, seek);
     ns[b] = w.n;
     memcpy(&geom[3 * (size_t)b], w.geom, sizeof w.geom);
+    if (n_frames) geom[3 * (size_t)b + 2] = std::min(geom[3 * (size_t)b + 2], n_frames[b]);   // the clip ends before the window does
     if (ns[b] > 0) HIPCHK(c, hipMemcpyAsync(c->pcm_dev + (int64_t)b * stride, file_pcm + w.first, ns[b] * 4, hipMemcpyHostToDevice, s));
   }
   HIPCHK(c, hipMemcpyAsync(c->nsamp_dev, ns.data(), B * 8, hipMemcpyHostToDevice, s));
@@ -299,6 +306,16 @@ int ttasr_log_mel_windows(ttasr_ctx* c, const float* const* file_pcm_of, const i
   c->B_mel = B;
   return TTASR_OK;
   });
+}
+
+int ttasr_log_mel_windows(ttasr_ctx* c, const float* const* file_pcm_of, const int64_t* file_samples_of, const int64_t* seek_frames,
+                          int32_t B, const float* floor_max, float* out_window_max, float* out_mel) {
+  return log_mel_windows(c, file_pcm_of, file_samples_of, seek_frames, nullptr, false, B, floor_max, out_window_max, out_mel);
+}
+
+int ttasr_log_mel_windows_cut(ttasr_ctx* c, const float* const* file_pcm_of, const int64_t* file_samples_of, const int64_t* seek_frames,
+                              int32_t B, const float* floor_max, float* out_window_max, float* out_mel, const int64_t* n_frames) {
+  return log_mel_windows(c, file_pcm_of, file_samples_of, seek_frames, n_frames, true, B, floor_max, out_window_max, out_mel);
 }
 
 int ttasr_set_mel(ttasr_ctx* c, const float* mel, int32_t B) {

@@ -399,11 +399,13 @@ class Engine:
         return out
 
     def log_mel_windows(self, audio, seeks: Sequence[int], floor_max: Optional[Sequence[float]] = None,
-                        want_output: bool = False, want_max: bool = False):
+                        want_output: bool = False, want_max: bool = False, n_frames: Optional[Sequence[int]] = None):
         """Windows of recordings (ttasr_log_mel_windows): window b starts at 10-ms frame seeks[b] of `audio` (one float32
         array = all windows belong to that recording) or of audio[b] (a sequence: one recording per window, several files in
         lock step); frames are those of the whole-file STFT, frames past the end of the recording are 0 in feature space,
         and the dynamic-range floor comes from floor_max[b] (the whole-file log-mel maximum) when given.
+        n_frames (ttasr_log_mel_windows_cut): window b keeps at most n_frames[b] >= 1 frames - a clip that ends before the
+        recording does; the kept frames are those of the uncut window, the rest is 0 and the maxima cover the kept frames.
         Returns (mel or None, per-window maxima or None)."""
         sk = np.ascontiguousarray(seeks, dtype=np.int64)
         B = len(sk)
@@ -415,9 +417,15 @@ class Engine:
         out = np.empty((B, self.dims.n_mels, 2 * self.audio_ctx), dtype=np.float32) if want_output else None
         mx = np.empty(B, dtype=np.float32) if want_max else None
         i64p = C.POINTER(C.c_int64)
-        self._check(self.lib.ttasr_log_mel_windows(self.h, ptrs, lens.ctypes.data_as(i64p), sk.ctypes.data_as(i64p), B,
-                                                   _ptr(fm) if fm is not None else None, _ptr(mx) if want_max else None,
-                                                   _ptr(out) if want_output else None), "log_mel_windows")
+        args = (self.h, ptrs, lens.ctypes.data_as(i64p), sk.ctypes.data_as(i64p), B, _ptr(fm) if fm is not None else None,
+                _ptr(mx) if want_max else None, _ptr(out) if want_output else None)
+        if n_frames is None:
+            self._check(self.lib.ttasr_log_mel_windows(*args), "log_mel_windows")
+        else:
+            nf = np.ascontiguousarray(n_frames, dtype=np.int64)
+            if nf.shape != (B,):
+                raise ValueError(f"n_frames needs one frame count per window ({B}), got shape {nf.shape}")
+            self._check(self.lib.ttasr_log_mel_windows_cut(*args, nf.ctypes.data_as(i64p)), "log_mel_windows_cut")
         return out, mx
 
     def log_mel_device(self, dev_ptr: int, stride: int, n_samples: Sequence[int]):

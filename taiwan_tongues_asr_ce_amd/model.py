@@ -103,6 +103,115 @@ def select_language(tops: Sequence[Tuple[str, float]], threshold: Optional[float
     return lang, prob, i
 
 
+def parse_clip_timestamps(clip_timestamps, n_total: int) -> List[Tuple[int, int]]:
+    """`clip_timestamps` of transcribe() -> the (start, end) pairs of 10-ms frames the window loop walks, as openai-whisper's
+    transcribe() builds its seek_clips (restated from memory: unpinned): a comma-separated string of seconds ("0", the default; ""
+    counts as "0") or a sequence of seconds; a seek point is round(t * 100); an odd count means the last clip runs to the end of the
+    recording.  Here every point is clamped to the recording's n_total frames - a clip that starts past the end is empty - and a
+    negative, non-finite or non-numeric value raises ValueError."""
+    if isinstance(clip_timestamps, str):
+        parts = [t.strip() for t in clip_timestamps.split(",")] if clip_timestamps.strip() else []
+    elif isinstance(clip_timestamps, (list, tuple, np.ndarray)):
+        parts = list(clip_timestamps)
+    else:
+        raise ValueError(f"clip_timestamps={clip_timestamps!r}: a comma-separated string of seconds or a list of seconds")
+    points = []
+    for t in parts:
+        try:
+            v = float(t)
+        except (TypeError, ValueError):
+            raise ValueError(f"clip_timestamps: {t!r} is not a number of seconds") from None
+        if not np.isfinite(v) or v < 0:
+            raise ValueError(f"clip_timestamps: {t!r} is not a finite, non-negative number of seconds")
+        points.append(min(int(round(v * 100)), int(n_total)))
+    if not points:
+        points.append(0)
+    if len(points) % 2:
+        points.append(int(n_total))
+    return list(zip(points[::2], points[1::2]))
+
+
+def _clip_lists(clip_timestamps, n: int) -> list:
+    """`clip_timestamps` of a many-file surface -> one entry per file: a string or a flat sequence of seconds holds for every file,
+    a sequence of strings / sequences is one entry per file."""
+    if not isinstance(clip_timestamps, str) and isinstance(clip_timestamps, (list, tuple)) and \
+            any(isinstance(c, (str, list, tuple, np.ndarray)) for c in clip_timestamps):
+        if len(clip_timestamps) != n:
+            raise ValueError(f"clip_timestamps needs one entry per file ({n}), got {len(clip_timestamps)}")
+        return list(clip_timestamps)
+    return [clip_timestamps] * n
+
+
+def _frames_of(n_samples: int) -> int:
+    """Frames of the whole-file STFT: len // HOP (the feature extractor drops its last frame); a tail shorter than one hop still
+    yields one (all-padding) window, as faster-whisper's 160 samples of end padding do."""
+    return max(n_samples // HOP, 1) if n_samples else 0
+
+
+LOCK_STEP_ONLY = ("{what}: clip_timestamps and hallucination_silence_threshold are not available in a continuous-batching session "
+                  "(ttasr_session_submit_windows has no cut, and a session aligns a window after its file has moved on); use the "
+                  "lock-step form, transcribe_many(..., continuous=False)")
+
+
+def refuse_in_session(what: str, clip_timestamps="0", hallucination_silence_threshold=None) -> None:
+    """The ValueError of every continuous surface for a non-neutral clip_timestamps / hallucination_silence_threshold; raised
+    before any session opens.  The neutral clip values are those that parse to the whole recording whatever its length: "0", "",
+    [0], [], None.  [0, duration] is refused here although the lock-step loop treats it as the default: a recording's length
+    is not known where these surfaces check their arguments."""
+    neutral_clip = clip_timestamps is None or (isinstance(clip_timestamps, str) and clip_timestamps.strip() in ("", "0")) or \
+        (isinstance(clip_timestamps, (list, tuple)) and all(isinstance(c, (int, float)) for c in clip_timestamps)
+         and [float(c) for c in clip_timestamps] in ([], [0.0]))
+    if not neutral_clip or hallucination_silence_threshold is not None:
+        raise ValueError(LOCK_STEP_ONLY.format(what=what))
+
+
+def skip_hallucinations(kept: List[dict], single_timestamp_ending: bool, seek: int, win_frames: int, next_seek: int,
+                        threshold: float, last_speech_end: float, n_total: int, n_window: int = N_FRAMES
+                        ) -> Tuple[List[dict], int, bool]:
+    """hallucination_silence_threshold for one window whose words are dealt to its kept segments (dicts with start, end, words),
+    as openai-whisper's transcribe() applies it (restated from memory: unpinned).  seek / win_frames: the window's first frame
+    and frame count; next_seek: where the segment rule would go on; last_speech_end: the last word end of the windows before;
+    n_total: frames of the recording; n_window: frames of a full window - the rules measure the silence left in the window to
+    seek + n_window, also when the window itself is shorter.  -> (segments to yield, next seek, True when the window yields
+    nothing and leaves the previous text and the prompt reset alone).
+    1. The window does not end in a single timestamp and its last word ends after the window's start: go on at that word's end
+       when more than `threshold` of the window follows it, else behind the window.
+    2. The first segment with words is anomalous (alignment.is_segment_anomaly) and starts more than `threshold` into the
+       window: yield nothing and go on where it starts.
+    3. The first anomalous segment with silence on both sides - before: more than `threshold` since the last kept segment's
+       end, a start below `threshold`, or less than 2 s into the window; after: more than `threshold` to the next segment with
+       words (the window's end without one), that segment anomalous too, or less than 2 s of the window left - is dropped with
+       everything after it; go on at max(1 s into the window, its start), or at the end of the recording when less than
+       `threshold` of audio follows its end."""
+    time_offset = seek * HOP / SAMPLE_RATE
+    window_end = (seek + n_window) * HOP / SAMPLE_RATE
+    with_words = [seg for seg in kept if seg.get("words")]
+    if not single_timestamp_ending and with_words:
+        last_word_end = with_words[-1]["words"][-1].end
+        if last_word_end > time_offset:
+            next_seek = int(round(last_word_end * 100)) if window_end - last_word_end > threshold else seek + win_frames
+    if with_words and alignment.is_segment_anomaly(with_words[0]):
+        gap = with_words[0]["start"] - time_offset
+        if gap > threshold:
+            return [], seek + max(int(round(gap * 100)), 1), True
+    last_end = last_speech_end
+    for i, seg in enumerate(kept):
+        if not seg.get("words"):
+            continue
+        if alignment.is_segment_anomaly(seg):
+            nxt = next((n for n in kept[i + 1:] if n.get("words")), None)
+            next_start = nxt["words"][0].start if nxt is not None else time_offset + win_frames * HOP / SAMPLE_RATE
+            before = seg["start"] - last_end > threshold or seg["start"] < threshold or seg["start"] - time_offset < 2.0
+            after = next_start - seg["end"] > threshold or alignment.is_segment_anomaly(nxt) or window_end - seg["end"] < 2.0
+            if before and after:
+                next_seek = int(round(max(time_offset + 1, seg["start"]) * 100))
+                if n_total * HOP / SAMPLE_RATE - seg["end"] < threshold:
+                    next_seek = n_total
+                return kept[:i], next_seek, False
+        last_end = seg["end"]
+    return kept, next_seek, False
+
+
 def _read_hf_dir(path: str) -> Tuple[WhisperDims, Iterable[Tuple[str, np.ndarray]]]:
     with open(os.path.join(path, "config.json"), "r", encoding="utf-8") as f:
         cfg = json.load(f)
@@ -339,6 +448,8 @@ class WhisperModel:
         chip idle between its ~45 000 dependent launches (measured +27 % audio-s/s with two contexts).
         Every group is processed exactly as a serial transcribe_many call would process it (same grouping, same engine
         inputs): the results are identical, file by file, to pipeline_depth = 1; returned in group order.
+        clip_timestamps, hallucination_silence_threshold, prompt_reset_on_temperature, suppress_tokens (among **kw): as in
+        transcribe_many; a per-file clip list holds for the files of EVERY group, so it needs groups of one length.
         device_resample=True (one of **kw): each worker ingests its group's paths on its own engine context; audio_channel (one
         of **kw) picks a channel of every path, as in transcribe_many."""
         depth = max(1, min(int(pipeline_depth or self.pipeline_depth), len(groups) or 1, 4))
@@ -521,9 +632,24 @@ class WhisperModel:
                    temperature: Union[float, Sequence[float]] = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0), best_of: int = 5,
                    compression_ratio_threshold: Optional[float] = 2.4, multilingual: bool = False,
                    language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1,
-                   device_resample: bool = False, audio_channel=None, **kwargs
+                   device_resample: bool = False, audio_channel=None, clip_timestamps: Union[str, Sequence[float]] = "0",
+                   hallucination_silence_threshold: Optional[float] = None, prompt_reset_on_temperature: float = 0.5,
+                   suppress_tokens: Optional[Sequence[int]] = (-1,), **kwargs
                    ) -> Tuple[Iterator[Segment], TranscriptionInfo]:
-        """device_resample=True (path input only): the file is converted, downmixed and resampled on the device
+        """clip_timestamps ("0"; a comma-separated string or a list of seconds: start, end, start, end, ...; an odd count runs the
+        last clip to the end; an end past the recording is clamped): only those spans are decoded (parse_clip_timestamps).  A
+        window ends where its clip does (Engine.log_mel_windows(n_frames=...)), the dynamic-range floor stays the whole
+        recording's, previous-text conditioning carries across clips as across windows, language=None detects from the windows
+        that start at the first clip's start, and vad_filter=True with clips other than the whole recording skips the VAD with a
+        warning.  "0", [0] and [0, duration] are today's run, bit for bit.
+        hallucination_silence_threshold (seconds; None): with word_timestamps=True, silence longer than this around a segment
+        whose words look invented (alignment.is_segment_anomaly) is skipped and the segment dropped (skip_hallucinations has the
+        rules); without word_timestamps one warning says it has no effect.
+        prompt_reset_on_temperature (0.5): a window decoded above this temperature is not carried into the next prompt.
+        suppress_tokens ([-1]): -1 stands for the model's list, other ids are added to it; without -1 only the given ids and
+        the task / start tokens no search may emit are suppressed; an id outside the vocabulary raises ValueError.
+        These four restate openai-whisper's transcribe(), which faster-whisper copies, from memory: unpinned.
+        device_resample=True (path input only): the file is converted, downmixed and resampled on the device
         (decode_audio_many) instead of on the host.
         audio_channel (path input only; None / "mix", "left", "right" or an index from 0): that channel of the file alone
         instead of the mean of its channels, on either path.  Refused with an array, which is already mono.
@@ -534,8 +660,7 @@ class WhisperModel:
         # faster-whisper options this build does not implement are never silently ignored when they differ from
         # their defaults (the reference call sites pass none of them)
         neutral = {"patience": None, "vad_parameters": None, "vad_speech_prob_fn": None, "length_penalty": 1, "repetition_penalty": 1,
-                   "no_repeat_ngram_size": 0, "clip_timestamps": "0",
-                   "hallucination_silence_threshold": None, "prompt_reset_on_temperature": 0.5, "suppress_tokens": [-1],
+                   "no_repeat_ngram_size": 0,
                    "prepend_punctuations": alignment.PREPEND_PUNCTUATIONS, "append_punctuations": alignment.APPEND_PUNCTUATIONS,
                    "chunk_length": None, "log_progress": False}
         for k, v in kwargs.items():
@@ -545,6 +670,8 @@ class WhisperModel:
                 raise TypeError(f"transcribe() got an unexpected keyword argument {k!r}")
             if v is not None and v != neutral[k]:
                 warnings.warn(f"transcribe(): option {k}={v!r} is not implemented in this build and is ignored", stacklevel=2)
+        suppress = self._user_suppress(suppress_tokens)
+        threshold = self._silence_threshold(hallucination_silence_threshold, word_timestamps)
         pick = parse_audio_channel(audio_channel)
         if isinstance(audio, str):
             audio = self.decode_audio_many([audio], audio_channel=pick)[0] if device_resample else decode_audio(audio, channel=pick)
@@ -563,6 +690,11 @@ class WhisperModel:
             raise ValueError(f"beam_size={beam_size} needs {beam_size} decode rows but this model was built with "
                              f"max_batch={self.max_batch}; construct WhisperModel(..., max_batch>={beam_size})")
         chunks = None
+        clips = parse_clip_timestamps(clip_timestamps, _frames_of(len(audio)))
+        if vad_filter and clips != [(0, _frames_of(len(audio)))]:
+            # faster-whisper filters only at the default clip_timestamps (from memory: unpinned); the clips are times of the recording
+            warnings.warn("vad_filter=True is skipped: clip_timestamps already names the spans to decode", stacklevel=2)
+            vad_filter = False
         if vad_filter:
             # faster-whisper: Silero VAD -> speech chunks -> transcribe their concatenation -> restore the time line.
             # The network is not available offline: with a speech-probability function supplied by the operator
@@ -577,6 +709,7 @@ class WhisperModel:
                 chunks = vad.get_speech_timestamps(audio, vad.VadOptions(**params), prob_fn)
                 audio_full_len = len(audio)
                 audio = vad.collect_chunks(audio, chunks)
+                clips = parse_clip_timestamps("0", _frames_of(len(audio)))
         duration_after_vad = len(audio) / SAMPLE_RATE
         duration = (audio_full_len if chunks is not None else len(audio)) / SAMPLE_RATE
         if int(language_detection_segments) < 1:
@@ -584,7 +717,9 @@ class WhisperModel:
         if language is None:
             if self.is_multilingual:
                 k = int(language_detection_segments)
-                found = self.detect_language_batch([audio[i * self.n_window:] for i in range(k) if i == 0 or i * self.n_window < len(audio)])
+                first = clips[0][0] * HOP   # detection reads the windows that start where the first clip does
+                found = self.detect_language_batch([audio[first + i * self.n_window:] for i in range(k)
+                                                    if i == 0 or first + i * self.n_window < len(audio)])
                 language, lang_p, i = select_language([(f[0], f[1]) for f in found], language_detection_threshold)
                 all_p = found[i][2]
             else:
@@ -602,7 +737,9 @@ class WhisperModel:
                                            tuple(temperature) if isinstance(temperature, (list, tuple)) else (float(temperature),),
                                            best_of, compression_ratio_threshold, bool(word_timestamps),
                                            kwargs.get("hotwords"), kwargs.get("prefix"),
-                                           multilingual=bool(multilingual) and self.is_multilingual)
+                                           multilingual=bool(multilingual) and self.is_multilingual, clips=clips,
+                                           suppress_tokens=suppress, prompt_reset_on_temperature=float(prompt_reset_on_temperature),
+                                           hallucination_silence_threshold=threshold)
         if chunks is not None:
             segments = vad.restore_speech_timestamps(segments, chunks)
         return segments, info
@@ -617,6 +754,29 @@ class WhisperModel:
 
     # -- pieces of faster-whisper's generate_segments / generate_with_fallback, shared by the single-file loop and by
     #    transcribe_many (several files in lock step through one engine pass) -------------------------------------
+    def _user_suppress(self, suppress_tokens) -> Optional[Tuple[int, ...]]:
+        """`suppress_tokens` of transcribe() checked: None for the default [-1] (the model's list, as _window_opts builds it), else
+        the ids as a tuple.  An id other than -1 outside the vocabulary raises ValueError."""
+        ids = [] if suppress_tokens is None else [int(t) for t in suppress_tokens]
+        for t in ids:
+            if t != -1 and not 0 <= t < self.dims.vocab:
+                raise ValueError(f"suppress_tokens: id {t} is outside the vocabulary [0, {self.dims.vocab})")
+        return None if ids and all(t == -1 for t in ids) else tuple(ids)
+
+    @staticmethod
+    def _silence_threshold(threshold, word_timestamps: bool, stacklevel: int = 3) -> Optional[float]:
+        """`hallucination_silence_threshold` checked: it works on word times, so without word_timestamps it is None here after one
+        warning (openai-whisper's command line says the same)."""
+        if threshold is None:
+            return None
+        threshold = float(threshold)
+        if not np.isfinite(threshold) or threshold < 0:
+            raise ValueError(f"hallucination_silence_threshold={threshold!r}: a finite, non-negative number of seconds or None")
+        if not word_timestamps:
+            warnings.warn("hallucination_silence_threshold has no effect without word_timestamps=True", stacklevel=stacklevel)
+            return None
+        return threshold
+
     def _score(self, res, row: int):
         """(tokens, avg_logprob, no_speech_prob, compression_ratio) of one decoded row."""
         st = self.special
@@ -688,6 +848,12 @@ class WhisperModel:
         if cfg.get("suppress_ids"):
             sup = sorted({int(t) for t in cfg["suppress_ids"] if 0 <= int(t) < self.dims.vocab} |
                          {st.transcribe, st.translate, st.sot, st.sot_prev} | ({st.sot_lm} if st.sot_lm >= 0 else set()))
+        user = p.get("suppress_tokens")
+        if user is not None:   # faster-whisper get_suppressed_tokens: -1 = the model's list, the rest is added; never the task / start tokens
+            from .engine import default_suppress
+            model_list = default_suppress(st, self.dims.vocab)
+            always = [t for t in (st.translate, st.transcribe, st.sot, st.sot_prev, st.no_speech, st.sot_lm) if t >= 0]
+            sup = sorted({t for t in user if t >= 0} | set((sup or model_list) if -1 in user else always))
         bsup = [int(t) for t in cfg["suppress_ids_begin"] if 0 <= int(t) < self.dims.vocab] if cfg.get("suppress_ids_begin") else [220, st.eot]
         return self.engine.gen_opts(budget, timestamps=not p["without_timestamps"], sot_index=sot_index, suppress=sup,
                                     begin_suppress=bsup if p["suppress_blank"] else [],
@@ -734,6 +900,19 @@ class WhisperModel:
                 alignment.add_word_timestamps(kept, found, time_offset)
                 for seg in kept:
                     seg["start"], seg["end"] = min(seg["start"], limit), min(seg["end"], limit)
+        next_seek = seek + (min(advance, win_frames) if advance > 0 else win_frames)
+        if p.get("hallucination_silence_threshold") is not None and p["word_timestamps"] and not deferred:
+            body = [t for t in toks if t != st.eot]
+            single_end = len(body) >= 2 and body[-1] >= st.timestamp_begin and body[-2] < st.timestamp_begin
+            kept, next_seek, nothing = skip_hallucinations(kept, single_end, seek, win_frames, next_seek,
+                                                           p["hallucination_silence_threshold"], fs.get("last_speech_end", 0.0),
+                                                           fs["n_total"], self.dims.n_frames)
+            if nothing:   # leading silence before invented text: the window is looked at again from where that text starts
+                fs["seek"] = next_seek
+                return []
+            ends = [seg["words"][-1].end for seg in kept if seg["words"]]
+            if ends:
+                fs["last_speech_end"] = ends[-1]
         out = []
         for seg in kept:
             if not deferred:
@@ -743,9 +922,9 @@ class WhisperModel:
             # faster-whisper's all_tokens: the tokens of every YIELDED segment, timestamp tokens included (the
             # previous-text prompt carries them), <|endoftext|> and the undecided tail after the last pair excluded
             fs["prev"].extend(t for t in seg["tokens"] if t != st.eot)
-        if not p["condition"] or temp_used > 0.5:  # faster-whisper: prompt_reset_on_temperature = 0.5
+        if not p["condition"] or temp_used > p.get("prompt_reset_on_temperature", 0.5):  # faster-whisper's default: 0.5
             fs["prompt_reset"] = len(fs["prev"])  # prompt_reset_since: nothing carries over
-        fs["seek"] += min(advance, win_frames) if advance > 0 else win_frames
+        fs["seek"] = next_seek
         return out
 
     @staticmethod
@@ -791,42 +970,74 @@ class WhisperModel:
             best = max(best, float(np.max(mx)))
         return best
 
-    def _new_file_state(self, audio: np.ndarray, initial_prompt: Optional[str]) -> dict:
+    def _new_file_state(self, audio: np.ndarray, initial_prompt: Optional[str], clips: Optional[List[Tuple[int, int]]] = None) -> dict:
+        """clips: the (start, end) frame pairs of parse_clip_timestamps; None = the whole recording."""
         prev: List[int] = []
         if initial_prompt:
             prev.extend(self.tokenizer.encode(" " + initial_prompt.strip()))
-        # frames of the whole-file STFT: len // HOP (the feature extractor drops its last frame); a tail shorter than one hop
-        # still yields one (all-padding) window, as faster-whisper's 160 samples of end padding do
-        return dict(audio=audio, n_total=max(len(audio) // HOP, 1) if len(audio) else 0, prev=prev, prompt_reset=0,
-                    seek=0, idx=0)
+        n_total = _frames_of(len(audio))
+        clips = list(clips) if clips else [(0, n_total)]
+        return dict(audio=audio, n_total=n_total, prev=prev, prompt_reset=0, seek=clips[0][0], idx=0, clips=clips, clip=0)
+
+    def _next_window(self, fs: dict) -> Optional[int]:
+        """Moves fs["seek"] to the next frame a clip of the file wants decoded - up to the start of the current clip, or on to the
+        next clip once the current one is used up (openai-whisper's seek_clips loop) - and returns the frames of the window that
+        starts there: min(the model's window, frames left in the recording, frames left in the clip).  None: the file is done."""
+        clips = fs["clips"]
+        while fs["clip"] < len(clips):
+            start, end = clips[fs["clip"]]
+            if fs["seek"] < start:
+                fs["seek"] = start
+            if fs["seek"] < min(end, fs["n_total"]):
+                return min(self.dims.n_frames, fs["n_total"] - fs["seek"], end - fs["seek"])
+            fs["clip"] += 1
+            if fs["clip"] < len(clips):
+                fs["seek"] = clips[fs["clip"]][0]
+        return None
+
+    def _window_features(self, group: Sequence[dict], frames: Sequence[int]) -> None:
+        """The feature call of one pass: window i starts at group[i]'s seek and keeps frames[i] frames.  The cut form of the call is
+        used only when a clip ends a window before the model's window or the recording would."""
+        eng = self.engine
+        whole = [min(self.dims.n_frames, fs["n_total"] - fs["seek"]) for fs in group]
+        cut = dict(n_frames=list(frames)) if any(n < w for n, w in zip(frames, whole)) else {}
+        eng.log_mel_windows([fs["audio"] for fs in group], [fs["seek"] for fs in group], floor_max=[fs["file_max"] for fs in group], **cut)
 
     def _params(self, language, task, condition, without_timestamps, max_new_tokens, no_speech_threshold, log_prob_threshold,
                 max_initial_timestamp, suppress_blank, beam_size, patience, temperatures, best_of,
-                compression_ratio_threshold, word_timestamps, hotwords=None, prefix=None) -> dict:
+                compression_ratio_threshold, word_timestamps, hotwords=None, prefix=None, suppress_tokens=None,
+                prompt_reset_on_temperature=0.5, hallucination_silence_threshold=None) -> dict:
         enc = lambda t: self.tokenizer.encode(" " + t.strip()) if t else None
         return dict(hotwords_tokens=enc(hotwords), prefix_tokens=enc(prefix), language=language, lang_tok=self._lang_token(language), task=task, condition=condition,
                     without_timestamps=without_timestamps, max_new=max_new_tokens or (self.dims.n_text_ctx // 2),
                     no_speech_threshold=no_speech_threshold, log_prob_threshold=log_prob_threshold,
                     max_initial_timestamp=max_initial_timestamp, suppress_blank=suppress_blank, beam_size=beam_size,
                     patience=patience, temperatures=tuple(temperatures), best_of=best_of,
-                    compression_ratio_threshold=compression_ratio_threshold, word_timestamps=word_timestamps)
+                    compression_ratio_threshold=compression_ratio_threshold, word_timestamps=word_timestamps,
+                    suppress_tokens=suppress_tokens, prompt_reset_on_temperature=prompt_reset_on_temperature,
+                    hallucination_silence_threshold=hallucination_silence_threshold)
 
     def _generate_segments(self, audio, language, task, condition, initial_prompt, without_timestamps, max_new_tokens,
                            no_speech_threshold, log_prob_threshold, max_initial_timestamp, suppress_blank, beam_size=1,
                            patience=1.0, temperatures=(0.0,), best_of=5, compression_ratio_threshold=2.4,
-                           word_timestamps=False, hotwords=None, prefix=None, multilingual=False) -> Iterator[Segment]:
+                           word_timestamps=False, hotwords=None, prefix=None, multilingual=False, clips=None, suppress_tokens=None,
+                           prompt_reset_on_temperature=0.5, hallucination_silence_threshold=None) -> Iterator[Segment]:
         eng = self.engine
         p = self._params(language, task, condition, without_timestamps, max_new_tokens, no_speech_threshold,
                          log_prob_threshold, max_initial_timestamp, suppress_blank, beam_size, patience, temperatures, best_of,
-                         compression_ratio_threshold, word_timestamps, hotwords, prefix)
-        fs = self._new_file_state(audio, initial_prompt)
+                         compression_ratio_threshold, word_timestamps, hotwords, prefix, suppress_tokens,
+                         prompt_reset_on_temperature, hallucination_silence_threshold)
+        fs = self._new_file_state(audio, initial_prompt, clips)
         eng.set_audio_ctx(0)
-        file_max = self._file_feature_max(audio)   # before the first window: the floor is the recording's, not the window's
-        while fs["seek"] < fs["n_total"]:
+        # before the first window: the floor is the recording's, not the window's - and not the clips'
+        fs["file_max"] = self._file_feature_max(audio)
+        while True:
+            win_frames = self._next_window(fs)
+            if win_frames is None:
+                break
             seek = fs["seek"]
-            win_frames = min(self.dims.n_frames, fs["n_total"] - seek)
             eng.set_audio_ctx(0)
-            eng.log_mel_windows(audio, [seek], floor_max=[file_max])
+            self._window_features([fs], [win_frames])
             eng.encode(1)
             if multilingual:   # this window's language, from the encoder state that is resident anyway
                 p["language"] = self._detect_resident(1)[0][0]
@@ -847,7 +1058,10 @@ class WhisperModel:
                         hotwords: Optional[str] = None, prefix: Optional[str] = None, continuous: bool = False,
                         multilingual: bool = False, detect_in_session: bool = False, session_prefill: Union[int, bool] = 0,
                         vad_filter: bool = False, vad_parameters: Optional[dict] = None, device_resample: bool = False,
-                        retry_held: Optional[bool] = None, audio_channel=None) -> List[Tuple[List[Segment], TranscriptionInfo]]:
+                        retry_held: Optional[bool] = None, audio_channel=None,
+                        clip_timestamps: Union[str, Sequence] = "0", hallucination_silence_threshold: Optional[float] = None,
+                        prompt_reset_on_temperature: float = 0.5, suppress_tokens: Optional[Sequence[int]] = (-1,)
+                        ) -> List[Tuple[List[Segment], TranscriptionInfo]]:
         """Several FILES in lock step: every round takes the next 30-s window of each unfinished file and runs them as
         ONE engine pass (log-mel, encoder, beam search with one previous-text prompt per file), so a folder is
         transcribed at batch throughput while each file keeps exactly the sequential algorithm of `transcribe` — its
@@ -895,9 +1109,18 @@ class WhisperModel:
         (decode_audio_many) before the VAD and before a session begins, instead of file by file on the calling thread; an engine
         without `ingest` ignores the flag.
         audio_channel (None / "mix", "left", "right" or an index from 0): that channel of every path instead of the mean of its
-        channels, with or without device_resample; refused when an array is among `audios`."""
+        channels, with or without device_resample; refused when an array is among `audios`.
+        clip_timestamps, hallucination_silence_threshold, prompt_reset_on_temperature, suppress_tokens: as in `transcribe`;
+        clip_timestamps is one value for every file (a string or a flat list of seconds) or one such value per file, and a file
+        with clips other than its whole recording is not VAD-filtered (a warning).  With a threshold a window's words decide
+        its file's next seek: the lock-step form aligns a window before its file advances, as it always did.  continuous=True
+        refuses the first two at any but their neutral values with a ValueError before the session opens ([0, duration] too:
+        refuse_in_session): a session's window cannot end before the recording does, and it aligns a window after its file
+        has moved on."""
         from .engine import session_prefill_value
         eng = self.engine
+        if continuous:
+            refuse_in_session("transcribe_many(continuous=True)", clip_timestamps, hallucination_silence_threshold)
         session_prefill = session_prefill_value(session_prefill)
         if session_prefill and not continuous:
             raise ValueError("session_prefill needs continuous=True (the lock-step passes prefill their prompts already: option prefill)")
@@ -918,7 +1141,9 @@ class WhisperModel:
         langs = self._check_languages(language, len(audios), "file")
         p = self._params(next((l for l in langs if l is not None), "en"), task, condition_on_previous_text, without_timestamps,
                          max_new_tokens, no_speech_threshold, log_prob_threshold, max_initial_timestamp, suppress_blank, beam,
-                         patience, temps, best_of, compression_ratio_threshold, bool(word_timestamps), hotwords, prefix)
+                         patience, temps, best_of, compression_ratio_threshold, bool(word_timestamps), hotwords, prefix,
+                         self._user_suppress(suppress_tokens), float(prompt_reset_on_temperature),
+                         self._silence_threshold(hallucination_silence_threshold, word_timestamps))
         if continuous:
             p["beam_size"] = int(beam_size)
         pcm = []
@@ -932,6 +1157,10 @@ class WhisperModel:
             pcm.append(np.ascontiguousarray(a, dtype=np.float32))
         full_len = [len(a) for a in pcm]
         speech: List[Optional[list]] = [None] * len(pcm)   # per file: its speech chunks on the original time line (None: not filtered)
+        file_clips = [parse_clip_timestamps(c, _frames_of(len(a))) for c, a in zip(_clip_lists(clip_timestamps, len(pcm)), pcm)]
+        clipped = [c != [(0, _frames_of(len(a)))] for c, a in zip(file_clips, pcm)]
+        if vad_filter and any(clipped):
+            warnings.warn("vad_filter=True is skipped for the files whose clip_timestamps already name the spans to decode", stacklevel=2)
         if vad_filter and pcm:
             params = dict(vad_parameters or {})
             kind, prob_fn = self._vad_source(params, self.vad_speech_prob_fn)
@@ -939,11 +1168,13 @@ class WhisperModel:
                 options = vad.VadOptions(**params)
                 probs = self.engine.vad_probs(pcm) if kind == "device" else None   # all files, one device call
                 for i, a in enumerate(pcm):
+                    if clipped[i]:
+                        continue
                     speech[i] = vad.get_speech_timestamps(a, options, (lambda _a, q=probs[i]: q) if probs is not None else prob_fn)
                     pcm[i] = vad.collect_chunks(a, speech[i])
         files = []
-        for a, chunks, n_full in zip(pcm, speech, full_len):
-            fs = self._new_file_state(a, initial_prompt)
+        for a, chunks, n_full, clips in zip(pcm, speech, full_len, file_clips):
+            fs = self._new_file_state(a, initial_prompt, clips if chunks is None else None)
             fs["segments"], fs["speech"], fs["full_len"] = [], chunks, n_full
             fs["file_max"] = self._file_feature_max(fs["audio"])   # whole-file dynamic-range floor, as `transcribe`
             files.append(fs)
@@ -951,7 +1182,8 @@ class WhisperModel:
         session_stats = None   # Session.stats() of a continuous run in hold mode (word_timestamps / retry_held), in every file's info
         # files whose language the session itself finds: they skip the detection pass; "decided" = the file-level answer is known
         late = [l is None and bool(detect_in_session) and self.is_multilingual for l in langs]
-        found = self._resolve_languages(["en" if w else l for l, w in zip(langs, late)], [fs["audio"] for fs in files], "file")
+        found = self._resolve_languages(["en" if w else l for l, w in zip(langs, late)],
+                                        [fs["audio"][fs["clips"][0][0] * HOP:] for fs in files], "file")   # from the first clip's start
         for fs, (lang, lang_p, all_p), w in zip(files, found, late):
             fs["language"], fs["lang_tok"], fs["lang_info"] = lang, self._lang_token(lang), (lang, lang_p, all_p)
             fs["decided"] = not w
@@ -959,14 +1191,17 @@ class WhisperModel:
             session_stats = self._run_continuous(files, p, per_window=multilingual, session_prefill=session_prefill,
                                                  retry_held=bool(retry_held))
         while not continuous:
-            active = [fs for fs in files if fs["seek"] < fs["n_total"]]
+            active = []
+            for fs in files:
+                fs["frames"] = self._next_window(fs)   # None: the file is done
+                if fs["frames"] is not None:
+                    active.append(fs)
             if not active:
                 break
             for g in range(0, len(active), per_pass):
                 group = active[g:g + per_pass]
                 eng.set_audio_ctx(0)
-                eng.log_mel_windows([fs["audio"] for fs in group], [fs["seek"] for fs in group],
-                                    floor_max=[fs["file_max"] for fs in group])
+                self._window_features(group, [fs["frames"] for fs in group])
                 eng.encode(len(group))
                 if multilingual:   # the windows' own languages, from the encoder state of the pass
                     for fs, r in zip(group, self._detect_resident(len(group))):
@@ -984,13 +1219,13 @@ class WhisperModel:
                 redo = []
                 for i, fs in enumerate(group):
                     toks, avg_lp, ns, cr = first[i]
-                    win_frames = min(self.dims.n_frames, fs["n_total"] - fs["seek"])
+                    win_frames = fs["frames"]
                     if temps[0] <= 0.0 and self._needs_fallback(avg_lp, ns, cr, p) and len(temps) > 1:
                         redo.append((fs, prompts[i], sots[i], first[i], win_frames))
                     else:
                         fs["segments"].extend(self._finish_window(fs, i, (temps[0], toks, avg_lp, ns, cr), win_frames, p))
                 for fs, pr, si, fst, win_frames in redo:   # rare: this window alone, through the whole ladder
-                    eng.log_mel_windows(fs["audio"], [fs["seek"]], floor_max=[fs["file_max"]])
+                    self._window_features([fs], [win_frames])
                     eng.encode(1)
                     attempt = self._decode_with_fallback(pr, self._window_opts(len(pr), si, p), fs["seek"], p, first=fst)
                     fs["segments"].extend(self._finish_window(fs, 0, attempt, win_frames, p))
@@ -1182,7 +1417,7 @@ class WhisperModel:
                           without_timestamps: bool = True, max_new_tokens: int = 224,
                           row_max_new: Optional[Sequence[int]] = None, beam_size: int = 1, patience: float = 1.0,
                           initial_prompt: Optional[str] = None, word_timestamps: bool = False, detect_in_session: bool = False,
-                          session_prefill: Union[int, bool] = 0):
+                          session_prefill: Union[int, bool] = 0, clip_timestamps="0", hallucination_silence_threshold=None):
         """transcribe_batch's contract (clips <= 30 s each, sampled token ids per clip, input order) for any number of clips,
         through a continuous-batching session: a clip that finishes hands its decode row to the next one instead of waiting for
         the rest of its batch.  row_max_new (optional): one token budget per clip, each in [1, max_new_tokens].
@@ -1197,8 +1432,11 @@ class WhisperModel:
         (language, probability) per clip of the last call: `last_language_info`.
         session_prefill=N (True = config.SESSION_PREFILL_DEFAULT): a clip whose prompt - the initial_prompt's previous text - has
         at least N prefillable positions gets them from one admission pass of the session instead of N forced decode steps
-        (Engine.session(prefill=N)); clips that go in with the language placeholder are forced as before."""
+        (Engine.session(prefill=N)); clips that go in with the language placeholder are forced as before.
+        clip_timestamps / hallucination_silence_threshold: accepted at their neutral values only; anything else is a ValueError
+        before the session opens (they belong to the window loop: transcribe, lock-step transcribe_many)."""
         from .engine import Session, session_prefill_value
+        refuse_in_session("transcribe_stream", clip_timestamps, hallucination_silence_threshold)
         session_prefill = session_prefill_value(session_prefill)
         if len(clips) == 0:
             self.last_language_info = []

@@ -64,14 +64,29 @@ class BatchedWhisperASR(MI355XWhisperASR):
     front of <|startoftranscript|> come from one admission pass of the session instead of one forced decode step each, when there
     are at least N of them (Engine.session(prefill=N)); requests that carry the language placeholder are forced as before.
 
+    `clip_timestamps` / `hallucination_silence_threshold`: options of the file-level window loop (WhisperModel.transcribe and the
+    lock-step transcribe_many); here they are accepted at their neutral values only, anything else is a ValueError before a model
+    is built - with continuous=True because a session cannot run them (the message names the lock-step transcribe_many), and with
+    continuous=False as well, where an utterance is a single window of transcribe_windows and neither option has a meaning
+    (refused rather than ignored).
+
     `wire=` / `audio_from=` (opt-in, both modes; MI355XWhisperASR.client_audio): what the clients' scratch bytes are when they
     are not 16 kHz mono s16 - a vad.WireFormat, or "client" for each client's own declaration - and the
     vad_backends.DeviceStreamVAD(wire=...) whose device streams have converted the same bytes already."""
 
     def __init__(self, max_clips: int = 6, max_wait_ms: float = 5.0, audio_ctx=None, max_new_tokens: int = 224,
                  continuous: bool = False, word_timestamps: bool = False, detect_in_session: bool = False,
-                 session_prefill=0, **kwargs):
+                 session_prefill=0, clip_timestamps="0", hallucination_silence_threshold=None, **kwargs):
         from .engine import session_prefill_value
+        from .model import refuse_in_session
+        # the window-loop options of WhisperModel.transcribe: an utterance here is one window, and a session cannot run them
+        try:
+            refuse_in_session("BatchedWhisperASR(continuous=True)", clip_timestamps, hallucination_silence_threshold)
+        except ValueError:
+            if continuous:
+                raise
+            raise ValueError("BatchedWhisperASR decodes single-window utterances: clip_timestamps and hallucination_silence_threshold "
+                             "belong to the file-level loop (WhisperModel.transcribe / transcribe_many)") from None
         if continuous and audio_ctx is not None:
             raise ValueError("continuous=True encodes the full window: audio_ctx must be None")
         self.session_prefill = session_prefill_value(session_prefill)
