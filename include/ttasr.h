@@ -910,6 +910,79 @@ TTASR_API int64_t ttasr_seg_frames(int64_t n_samples);
 TTASR_API int ttasr_seg_scores(ttasr_ctx* ctx, int32_t n, const float* const* pcm_host, const int64_t* n_samples,
                                float* const* out_scores_host, float* const* out_chunk_probs_host, float* const* out_chunk_logits_host);
 
+/* ---- speaker embeddings: the XVectorSincNet-shaped network (the embedding model that pairs with pyannote/segmentation in a
+ * pyannote-style diarization pipeline; the reference service's DIA subtitle type, api/file_asr.py:591-632, has no speaker
+ * labelling behind it yet) ------------------------------------------------------------------------------------------------------- */
+/* UNPINNED against the published pyannote/embedding checkpoint: neither pyannote.audio nor the checkpoint exists offline, so the
+ * tensor names, the layer table, the pooling formula and the nearest-neighbour resampling of the weights are restated from
+ * memory, and the network is held to a float64 restatement of THIS text on synthetic weights (tests/xvector_reference.py).
+ *
+ * The network (all arithmetic f32 on the device in every compute mode).  Input and chunking are ttasr_seg_scores': 16 kHz mono
+ * float32, chunks of 80 000 samples, chunk k starts at sample 8 000 k, K(n) = ttasr_seg_chunks(n), the last chunk zero-padded.
+ * Per chunk:
+ *   1. the SincNet front end of the segmentation network with weights of its own (steps 1.-5. of that text: waveform
+ *      InstanceNorm1d(1, affine); 80 sinc filters of 251 taps, stride 10, abs, MaxPool1d(3), InstanceNorm1d(80, affine),
+ *      leaky_relu(0.01); Conv1d(80 -> 60, k 5), pool 3, norm, leaky_relu; Conv1d(60 -> 60, k 5), pool 3, norm, leaky_relu):
+ *      [60][293];
+ *   2. five TDNN blocks, each Conv1d (no padding, with bias) -> leaky_relu(0.01) -> BatchNorm1d in eval mode
+ *      ((x - running_mean) / sqrt(running_var + 1e-5) * weight + bias):
+ *        block   cin -> cout   kernel   dilation   frames out
+ *          1      60 ->  512     5         1          289
+ *          2     512 ->  512     3         2          285
+ *          3     512 ->  512     3         3          279
+ *          4     512 ->  512     1         1          279
+ *          5     512 -> 1500     1         1          279
+ *   3. weighted statistics pooling, once per mask w[293] >= 0 of the chunk: w'[j] = w[(293 j) / 279] in integer division for
+ *      j < 279 (torch's interpolate(mode="nearest"); frames 20, 41, 62, ..., 292 of the 293 - fourteen of them, 146 and 292 among
+ *      them - are read by no j), v1 = sum w', v2 = sum w'^2, mean_c = sum w' x_c / v1,
+ *      var_c = sum w' (x_c - mean_c)^2 / (v1 - v2 / v1 + 1e-8), std_c = sqrt(var_c); the result is [mean | std], 3 000 values;
+ *   4. embedding = Linear(3 000 -> D), D = embedding.weight's first dimension, 1 <= D <= TTASR_SPK_MAX_DIM.
+ *
+ * ttasr_spk_load_tensor: one tensor, float32 host data, state-dict name: the 13 sincnet.* names and shapes of
+ *   ttasr_seg_load_tensor (sincnet.conv1d.0.filters derived from the checkpoint's cutoffs in the same way);
+ *   tdnns.{0,3,6,9,12}.weight [cout,cin,kernel] and .bias [cout]; tdnns.{2,5,8,11,14}.weight | bias | running_mean | running_var
+ *   [cout] (num_batches_tracked is not a tensor of the network); embedding.weight [D,3000], embedding.bias [D]: 45 tensors.
+ *   Unknown name or wrong shape: TTASR_E_WEIGHTS.  After ttasr_spk_finalize, and in an open session: TTASR_E_INVALID.  The weights
+ *   (up to 13.5 MB) belong to THIS context.
+ * ttasr_spk_finalize: TTASR_E_WEIGHTS when a tensor is missing or embedding.weight and embedding.bias disagree on D; afterwards
+ *   the weights are read-only.  ttasr_spk_dim: D of the finalized network (TTASR_E_INVALID before).
+ * ttasr_spk_embed: n recordings, recording i = pcm_host[i][0 .. n_samples[i]) with K_i = ttasr_seg_chunks(n_samples[i]) chunks;
+ *   weights_host[i] is float32 [K_i][S][293], S = n_masks in [1, TTASR_SPK_MAX_MASKS]: S frame-weight masks for every chunk, on the
+ *   segmentation network's frame grid; out_emb_host[i] receives [K_i][S][D].  The optional array out_stats_host is the
+ *   known-answer hook: row i, when the array is not NULL, receives the pooled [K_i][S][3000].  A one-hot mask on a frame that the
+ *   resampling reads makes `mean` the block-5 output of ONE frame, so the hook shows single frames without reading the 1.6 MB of
+ *   a chunk's block-5 output back.  A mask whose RESAMPLED weights sum to 0 (all zeros, or weight on unread frames only): its D
+ *   and 3 000 values are written as quiet NaN, nothing is computed from them, and the other masks of the chunk are unaffected.  A
+ *   recording of 0 samples is legal and writes nothing (its pointers may be NULL).  Refused with TTASR_E_INVALID before anything
+ *   is enqueued, the context stays usable: weights not finalized; n outside [1, max_batch]; n_masks out of range; a NULL array; a
+ *   NULL pcm, weights or output row with samples; a length outside [0, 2^40]; a weight that is negative or not finite; an open
+ *   session; a call already in flight on the context.
+ *   Work proceeds in groups of at most TTASR_SPK_GROUP chunks - the recordings in call order, chunks ascending.  The TDNN blocks
+ *   do not read the masks: they run once per chunk and their output is pooled S times.  Every tile of the block kernels lies
+ *   inside one chunk, an output row of the GEMM body is a function of its own operand row and the weights with k ascending, and
+ *   the pooling's sums run over the frames in ascending order: the D and 3 000 values of (chunk, mask) depend on the chunk's
+ *   80 000 samples and that mask alone, bit for bit - not on the recording, the call, the group, S, the other masks or the
+ *   compute mode.
+ *   Device scratch: ONE block owned by the context, allocated by the first call, never a function of the recordings' lengths,
+ *   freed by ttasr_destroy: per chunk of a group 4 x (80 000 PCM + 80 x 2 658 + 60 x 884 + 60 x 293 stage outputs + 2 x 289 x 512
+ *   ping-pong block outputs + 279 x 1 500 block-5 output + 8 x (293 weights + 1 flag + 3 000 pooled + 512 embedding)) + 1 616
+ *   bytes of statistics and tables = 4 434 192 bytes, times TTASR_SPK_GROUP, every region rounded up to 256 bytes: 68 MiB.
+ *   TTASR_SPK_GROUP = 16: block 2's grid is then 5 x 4 x 16 = 320 workgroups on 256 CUs, and a group's reference costs a test a
+ *   few seconds.  Host data goes through a pinned staging block of TTASR_SPK_GROUP x 320 000 bytes of PCM + the group's tables,
+ *   masks and results: 7 MiB, allocated by the first call as well.  A block that cannot be allocated: TTASR_E_NOMEM, the context
+ *   stays usable.
+ *   The call touches no mel, encoder, search, graph, session, Silero or segmentation state: a ttasr_generate*, ttasr_vad_probs
+ *   or ttasr_seg_scores after it is bit-identical to one without it. */
+#define TTASR_SPK_GROUP 16
+#define TTASR_SPK_MAX_MASKS 8
+#define TTASR_SPK_MAX_DIM 512
+#define TTASR_SPK_STATS 3000
+TTASR_API int ttasr_spk_load_tensor(ttasr_ctx* ctx, const char* name, const float* data_host, const int64_t* dims, int32_t ndim);
+TTASR_API int ttasr_spk_finalize(ttasr_ctx* ctx);
+TTASR_API int ttasr_spk_dim(ttasr_ctx* ctx);
+TTASR_API int ttasr_spk_embed(ttasr_ctx* ctx, int32_t n, const float* const* pcm_host, const int64_t* n_samples, int32_t n_masks,
+                              const float* const* weights_host, float* const* out_emb_host, float* const* out_stats_host);
+
 /* ---- kernel-selection overrides (tests, A/B measurements) ----------------------------------------- */
 /* The release library reads NO environment variable; every deviation from the measured configuration is an explicit call.
  * Keys (value 0 / 1 unless stated; defaults in brackets): "flash" [1] MFMA flash attention in the encoder (0: the

@@ -26,6 +26,7 @@ SYMBOLS = [
     "ttasr_ingest_stream_len", "ttasr_vad_stream_open_wire", "ttasr_vad_stream_push_wire",
     "ttasr_flac_probe", "ttasr_flac_frames", "ttasr_flac_decode",
     "ttasr_seg_load_tensor", "ttasr_seg_finalize", "ttasr_seg_classes", "ttasr_seg_chunks", "ttasr_seg_frames", "ttasr_seg_scores",
+    "ttasr_spk_load_tensor", "ttasr_spk_finalize", "ttasr_spk_dim", "ttasr_spk_embed",
 ]
 
 PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = range(6)   # TTASR_PCM_* of include/ttasr.h
@@ -36,6 +37,8 @@ CODED_BYTES = {PCM_ALAW: 1, PCM_ULAW: 1}                          # bytes per sa
 VAD_MAX_STREAMS = 1024    # TTASR_VAD_MAX_STREAMS of include/ttasr.h: open streams of one context (ttasr_vad_stream_*)
 SEG_GROUP = 64            # TTASR_SEG_GROUP of include/ttasr.h: chunks of one pass of ttasr_seg_scores through its kernels
 SEG_CHUNK_FRAMES = 293    # TTASR_SEG_CHUNK_FRAMES: frames of one 80 000-sample chunk of the segmentation network
+SPK_GROUP = 16            # TTASR_SPK_GROUP of include/ttasr.h: chunks of one pass of ttasr_spk_embed through its kernels
+SPK_MAX_MASKS, SPK_MAX_DIM, SPK_STATS = 8, 512, 3000   # TTASR_SPK_MAX_MASKS, TTASR_SPK_MAX_DIM, TTASR_SPK_STATS
 VAD_CHUNK_FRAMES = 1024   # TTASR_VAD_CHUNK_FRAMES of include/ttasr.h: frames of one recording per time chunk of ttasr_vad_probs
 
 
@@ -167,6 +170,10 @@ def load() -> C.CDLL:
     lib.ttasr_seg_frames.argtypes = [i64]
     lib.ttasr_seg_frames.restype = i64
     lib.ttasr_seg_scores.argtypes = [vp, i32, C.POINTER(vp), i64p, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    lib.ttasr_spk_load_tensor.argtypes = [vp, C.c_char_p, vp, i64p, i32]
+    lib.ttasr_spk_finalize.argtypes = [vp]
+    lib.ttasr_spk_dim.argtypes = [vp]
+    lib.ttasr_spk_embed.argtypes = [vp, i32, C.POINTER(vp), i64p, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     for s in SYMBOLS:
         f = getattr(lib, s)
         if s not in ("ttasr_destroy", "ttasr_last_error", "ttasr_version", "ttasr_ingest_len", "ttasr_ingest_filter",

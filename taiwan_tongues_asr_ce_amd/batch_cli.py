@@ -66,8 +66,11 @@ def _probe(path: str) -> str:
 
 def transcribe_file(model, audio_file: str, load_audio: Callable = _load_audio, log: Callable = print, segments=None,
                     language: Optional[str] = TRANSCRIBE_KWARGS["language"], info=None, batched: bool = False,
-                    word_timestamps: bool = False, options: Optional[Dict] = None) -> Dict:
-    """options: further transcribe() keywords of a file transcribed here (clip_timestamps, hallucination_silence_threshold).
+                    word_timestamps: bool = False, options: Optional[Dict] = None, diarize: Optional[Dict] = None) -> Dict:
+    """diarize: not None = the file is also diarized (model.diarize(audio, **diarize)) and `<name>_dia.srt` is written beside
+    `<name>_asr.txt`: one cue per segment, its text prefixed with the speaker whose turns overlap it longest
+    (diarization.dia_srt: the reference service's SRT conventions).  A failure there is logged and leaves the ASR result as it is.
+    options: further transcribe() keywords of a file transcribed here (clip_timestamps, hallucination_silence_threshold).
     One unit of work → one entry of `detailed_results`.  word_timestamps: the segments carry words (a file transcribed here
     is transcribed with them); they are written to `<name>_words.json` beside `<name>_asr.txt`.  `segments`: already transcribed (group mode, with its `info`), else
     runs it.  language=None (`--language auto`): the language is detected, and the entry names it with its probability.
@@ -94,6 +97,16 @@ def transcribe_file(model, audio_file: str, load_audio: Callable = _load_audio, 
         with open(out_path, "w", encoding="utf-8") as f:
             f.write(processed)
         log(f"{name}: {processed}")
+        if diarize is not None:
+            try:
+                from . import diarization
+                turns = model.diarize(load_audio(audio_file), **diarize)
+                who = diarization.assign_speakers(segments, turns)
+                with open(os.path.splitext(audio_file)[0] + "_dia.srt", "wb") as f:
+                    f.write(diarization.dia_srt([(s.start, s.end, w, s.text) for s, w in zip(segments, who)]).encode("utf-8"))
+                log(f"{name}: {len(turns)} turns of {len(set(t.speaker for t in turns))} speakers")
+            except Exception as e:
+                log(f"{name}: diarization failed: {e}")
         entry = {"audio_file": name, "asr_result": processed, "original_transcript": None, "cer_result": None,
                  "has_original_transcript": False}
         if language is None and info is not None:   # auto mode only: the forced-language run keeps the reference's keys exactly
@@ -148,8 +161,13 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
                          detect_in_session: bool = False, session_prefill: int = 0, vad_model=None,
                          device_resample: bool = False, batched: bool = False, word_timestamps: bool = False,
                          audio_channel=None, clip_timestamps: str = "0",
-                         hallucination_silence_threshold: Optional[float] = None) -> Optional[Dict]:
-    """clip_timestamps (`--clip-timestamps "a,b,..."`): only those spans (seconds: start,end,start,end,...) of every file are
+                         hallucination_silence_threshold: Optional[float] = None, diarize: bool = False, seg_model=None,
+                         spk_model=None, num_speakers: Optional[int] = None) -> Optional[Dict]:
+    """diarize (`--diarize --seg-model PATH --spk-model PATH [--num-speakers N]`): every file is also diarized on the device
+    (WhisperModel.load_diarization, WhisperModel.diarize) and `<name>_dia.srt`, the speaker-labelled subtitle, is written beside
+    the unchanged `<name>_asr.txt`; with every form of the run, after the file's segments are there.  A model handed in that
+    already holds the networks needs no paths.
+    clip_timestamps (`--clip-timestamps "a,b,..."`): only those spans (seconds: start,end,start,end,...) of every file are
     decoded (WhisperModel.transcribe).  hallucination_silence_threshold (`--hallucination-silence-threshold S`): silence longer
     than S seconds around text whose words look invented is skipped; it works on word times and so implies word_timestamps.
     Both go with the one-by-one and the lock-step form; refused with continuous (ValueError before a model is built) and with
@@ -211,15 +229,22 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
         model = WhisperModel(model_path, device=device, device_index=device_index, compute_type=compute_type,
                              max_batch=max_batch, pipeline_depth=max(1, pipeline_depth), cross_kv_fp8=cross_kv_fp8,
                              vad_model=vad_model)
+    dia = None
+    if diarize:
+        if seg_model is not None and spk_model is not None:
+            model.load_diarization(seg_model, spk_model)
+        elif not getattr(model, "has_diarization", False):
+            raise ValueError("diarize needs seg_model and spk_model (--seg-model, --spk-model)")
+        dia = dict(num_speakers=num_speakers)
     mine = files[rank::world]                                   # shard by file
     results = []
     many = getattr(model, "transcribe_many", None)
     group = group_files if group_files > 0 else max(1, getattr(model, "max_batch", 1) // TRANSCRIBE_KWARGS["beam_size"])
     if batched:
-        results = [transcribe_file(model, f, load_audio, log, language=language, batched=True) for f in mine]
+        results = [transcribe_file(model, f, load_audio, log, language=language, batched=True, diarize=dia) for f in mine]
     elif many is None or group < 2 or getattr(model, "vad_speech_prob_fn", None) is not None:
-        results = [transcribe_file(model, f, load_audio, log, language=language, word_timestamps=word_timestamps, options=options)
-                   for f in mine]
+        results = [transcribe_file(model, f, load_audio, log, language=language, word_timestamps=word_timestamps, options=options,
+                                   diarize=dia) for f in mine]
     else:
         # MI355X-first: `group` files advance in lock step through one engine pass per window round; every file keeps the
         # sequential algorithm (own seek / prompt / fallback), so the outputs equal the one-by-one run
@@ -284,7 +309,7 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
                     log(f"group transcription failed ({e}); retrying file by file")
                     pairs = [(None, None)] * len(part)
                 results.extend(transcribe_file(model, f, load_audio, log, segments=sg, language=language, info=nfo,
-                                               word_timestamps=word_timestamps, options=options)
+                                               word_timestamps=word_timestamps, options=options, diarize=dia)
                                for f, (sg, nfo) in zip(part, pairs))
     if world > 1:
         import torch.distributed as dist
@@ -362,6 +387,15 @@ def build_parser() -> argparse.ArgumentParser:
                     help="which channel of a multichannel file is transcribed: mix = the mean of all (default), left / right = "
                          "channel 0 / 1, N = channel N counted from 0 (the reference service's audioChannel 0 / 1 / 2 is mix / "
                          "left / right); a file without that channel is that file's error")
+    ap.add_argument("--diarize", action="store_true",
+                    help="opt-in: also answer who spoke when; <name>_dia.srt, the speaker-labelled subtitle (cues 'SPEAKER_xx: text'), "
+                         "is written beside <name>_asr.txt.  Needs --seg-model and --spk-model")
+    ap.add_argument("--seg-model", default=None, metavar="PATH",
+                    help="with --diarize: pyannote/segmentation-shaped weights (.npz, or a torch checkpoint when torch is installed)")
+    ap.add_argument("--spk-model", default=None, metavar="PATH",
+                    help="with --diarize: pyannote/embedding-shaped (XVectorSincNet) weights, same formats")
+    ap.add_argument("--num-speakers", type=int, default=None, metavar="N",
+                    help="with --diarize: the number of speakers of every file, when it is known (default: found by clustering)")
     return ap
 
 
@@ -389,6 +423,12 @@ def main(argv=None) -> int:
             print("--clip-timestamps / --hallucination-silence-threshold go with the one-by-one or the lock-step form "
                   "(--group-files), not with --continuous or --batched")
             return 1
+    if args.diarize and not (args.seg_model and args.spk_model):
+        print("--diarize needs --seg-model PATH and --spk-model PATH")
+        return 1
+    if not args.diarize and (args.seg_model or args.spk_model or args.num_speakers is not None):
+        print("--seg-model / --spk-model / --num-speakers go with --diarize")
+        return 1
     if not os.path.exists(args.folder):
         print(f"folder does not exist: {args.folder}")
         return 1
@@ -403,7 +443,8 @@ def main(argv=None) -> int:
                          detect_in_session=args.detect_in_session, session_prefill=args.session_prefill,
                          vad_model=args.vad_model, device_resample=args.device_resample, batched=args.batched,
                          word_timestamps=args.word_timestamps, audio_channel=args.audio_channel,
-                         clip_timestamps=args.clip_timestamps, hallucination_silence_threshold=args.hallucination_silence_threshold)
+                         clip_timestamps=args.clip_timestamps, hallucination_silence_threshold=args.hallucination_silence_threshold,
+                         diarize=args.diarize, seg_model=args.seg_model, spk_model=args.spk_model, num_speakers=args.num_speakers)
     return 0
 
 

@@ -152,6 +152,7 @@ void ttasr_destroy(ttasr_ctx* c) {
   c->align_dev.reset();
   vad_free(c);
   seg_free(c);
+  spk_free(c);
   ingest_free(c);
   c->pinned_i32.reset();
   c->pinned_beam.reset();

@@ -64,6 +64,7 @@ struct Slot {              // where one named tensor lands on the device
 
 struct Session;            // continuous-batching session state (engine_refill.hip)
 struct SegState;           // segmentation network: weights, scratch and staging of one context (engine_seg.hip)
+struct SpkState;           // speaker-embedding network: weights, scratch and staging of one context (engine_spk.hip)
 struct VadState;           // voice-activity network: weights, scratch, staging and streams of one context (engine_vad.hip)
 struct IngestState;        // file ingest: tap tables per rate, the chunk slots and the IMA scratch of one context (engine_ingest.hip)
 // What run_decode_rows reads about the rows of a step, and (with the batch, the mode and the e4m3 state) what a captured step
@@ -216,6 +217,8 @@ struct ttasr_ctx {
   // chunks per recurrence workgroup (0: the measured choice; 1, 2, 4 force one; results identical)
   ttasr_detail::SegState* seg = nullptr;
   int seg_lstm_rows = 0;
+  // speaker-embedding network (engine_spk.hip): created by the first ttasr_spk_load_tensor, freed by ttasr_destroy
+  ttasr_detail::SpkState* spk = nullptr;
   int wire_chunk = 0;       // option wire_chunk: input frames of a row per internal chunk of ttasr_vad_stream_push_wire (0: what the pools hold)
 
   int B_mel = 0, B_enc = 0, B_dec = 0;
@@ -446,6 +449,9 @@ void vad_free(ttasr_ctx* c);         // ttasr_destroy: deletes the state, which 
 
 // ---- engine_seg.hip: the segmentation network (ttasr_seg_*) ----
 void seg_free(ttasr_ctx* c);         // ttasr_destroy: deletes the state, which owns its side blocks (the weights live in the arenas)
+
+// ---- engine_spk.hip: the speaker-embedding network (ttasr_spk_*) ----
+void spk_free(ttasr_ctx* c);         // ttasr_destroy: deletes the state, which owns its side blocks (the weights live in the arenas)
 
 // ---- engine_ingest.hip: file ingest (ttasr_ingest_*) ----
 void ingest_free(ttasr_ctx* c);      // ttasr_destroy: deletes the state, which owns its tap tables, chunk slots and events

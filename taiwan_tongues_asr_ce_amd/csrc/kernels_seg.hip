@@ -336,9 +336,9 @@ __global__ __launch_bounds__(256) void seg_agg_kernel(const SegAggJob* __restric
 
 }  // namespace
 
-void launch_seg_network(const SegWeights& w, const SegBuffers& b, int n, int rows, hipStream_t s) {
-  if (n < 1 || n > kSegGroup || (rows != 1 && rows != 2 && rows != 4) || !b.pcm || !b.desc || !b.gx || w.classes < 1 || w.classes > kSegMaxC) {
-    launch_fault("seg_network: %d chunks, %d rows per recurrence workgroup", n, rows);
+void launch_seg_frontend(const SegWeights& w, const SegBuffers& b, int n, hipStream_t s) {
+  if (n < 1 || n > kSegGroup || !b.pcm || !b.desc || !b.st0 || !b.a1 || !b.st1 || !b.a2 || !b.st2 || !b.a3 || !b.st3) {
+    launch_fault("seg_frontend: %d chunks", n);
     return;
   }
   hipLaunchKernelGGL(seg_stats_kernel, dim3(n), dim3(256), 0, s, b.pcm, b.desc, kSegChunk, b.st0);
@@ -350,6 +350,14 @@ void launch_seg_network(const SegWeights& w, const SegBuffers& b, int n, int row
   hipLaunchKernelGGL((seg_conv_kernel<kSegC2, kSegL2, kSegT>), dim3((kSegT + SP - 1) / SP, n), dim3(256), 0, s, (const float*)b.a2,
                      (const float*)b.st2, w.norm_w[1], w.norm_b[1], w.conv_t[1], w.conv_b[1], b.a3);
   hipLaunchKernelGGL(seg_stats_kernel, dim3(n * kSegC2), dim3(256), 0, s, (const float*)b.a3, (const SegDesc*)nullptr, kSegT, b.st3);
+}
+
+void launch_seg_network(const SegWeights& w, const SegBuffers& b, int n, int rows, hipStream_t s) {
+  if (n < 1 || n > kSegGroup || (rows != 1 && rows != 2 && rows != 4) || !b.pcm || !b.desc || !b.gx || w.classes < 1 || w.classes > kSegMaxC) {
+    launch_fault("seg_network: %d chunks, %d rows per recurrence workgroup", n, rows);
+    return;
+  }
+  launch_seg_frontend(w, b, n, s);
   const dim3 pgrid((kSegT + PT - 1) / PT, 4, n), lgrid((n + rows - 1) / rows, 2);
   for (int l = 0; l < kSegLayers; ++l) {
     float* out = b.y[l & 1];

@@ -55,6 +55,10 @@ struct SegBuffers {
   const SegAggJob* jobs; const float* window; float* agg_out;
 };
 
+// n chunks through the front end alone (waveform norm, sinc stage, two conv stages and the statistics of the third): a3 and st3
+// are its results; the third InstanceNorm and leaky_relu are applied by whoever reads them.  The first launches of
+// launch_seg_network, and the front end of the speaker-embedding network (kernels_spk.hip) with that network's weights.
+void launch_seg_frontend(const SegWeights& w, const SegBuffers& b, int n, hipStream_t s);
 // n chunks through the front end, the LSTM (rows = chunks per recurrence workgroup: 1, 2 or 4) and the head
 void launch_seg_network(const SegWeights& w, const SegBuffers& b, int n, int rows, hipStream_t s);
 // n_jobs aggregation jobs, the longest of max_frames output frames

@@ -82,6 +82,8 @@ class Engine:
         self.has_vad = False   # load_vad() has put the VAD network on this context
         self.has_segmentation = False   # load_segmentation() has put the segmentation network on this context
         self.seg_classes = 0
+        self.has_speaker_embedding = False   # load_speaker_embedding() has put the speaker-embedding network on this context
+        self.spk_dim = 0
         self._wire_streams = {}   # wire stream id -> (rate, bytes per frame, samples a finish releases): sizes vad_stream_push_wire's result rows
 
     # -- plumbing ------------------------------------------------------------------------------
@@ -190,6 +192,55 @@ class Engine:
                                                   rows(scores[sl]), rows(probs[sl]) if return_chunks else None,
                                                   rows(logits[sl]) if return_chunks else None), "seg_scores")
         return (scores, probs, logits) if return_chunks else scores
+
+    # -- speaker embeddings (the XVectorSincNet-shaped network) --------------------------------------
+    def load_speaker_embedding(self, weights):
+        """The XVectorSincNet-shaped speaker-embedding network of this context (ttasr_spk_load_tensor + ttasr_spk_finalize): a
+        mapping, or (name, array) pairs, with the names and shapes of diarization.XVECTOR_TENSORS
+        (diarization.load_xvector_state builds the sinc filters from a checkpoint's cutoffs).  Every context holds its own copy."""
+        items = weights.items() if hasattr(weights, "items") else weights
+        for name, arr in items:
+            a = np.ascontiguousarray(arr, dtype=np.float32)
+            dims = (C.c_int64 * max(a.ndim, 1))(*a.shape)
+            self._check(self.lib.ttasr_spk_load_tensor(self.h, str(name).encode(), _ptr(a), dims, a.ndim), f"spk_load_tensor({name})")
+        self._check(self.lib.ttasr_spk_finalize(self.h), "spk_finalize")
+        self.spk_dim = int(self.lib.ttasr_spk_dim(self.h))
+        self.has_speaker_embedding = True
+
+    def speaker_embeddings(self, audios: Sequence[np.ndarray], weights: Sequence[np.ndarray], return_stats: bool = False):
+        """One embedding per (chunk, mask) of every recording (ttasr_spk_embed): weights[i] is [chunks, S, 293] frame weights
+        >= 0 on the segmentation network's chunks and frames, one S for the call; the result is a list of float32
+        [chunks, S, D] arrays, rows of quiet NaN where a mask's resampled weights sum to 0.  return_stats=True:
+        (embeddings, pooled statistics [chunks, S, 3000]).  More recordings than max_batch go through several calls; a row's
+        values do not depend on its neighbours."""
+        if not getattr(self, "has_speaker_embedding", False):
+            raise TtasrError("no speaker-embedding network on this engine: load_speaker_embedding first")
+        pcm, wts = [], []
+        if len(audios) != len(weights):
+            raise ValueError(f"{len(audios)} recordings and {len(weights)} weight arrays")
+        n_masks = None
+        for i, (a, w) in enumerate(zip(audios, weights)):
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            w = np.ascontiguousarray(w, dtype=np.float32)
+            if a.ndim != 1:
+                raise ValueError(f"recording {i}: PCM must be one-dimensional, got shape {a.shape}")
+            k = int(self.lib.ttasr_seg_chunks(len(a)))
+            if w.ndim != 3 or w.shape[0] != k or w.shape[2] != _lib.SEG_CHUNK_FRAMES or (n_masks is not None and w.shape[1] != n_masks):
+                raise ValueError(f"recording {i}: weights of shape {w.shape}, expected ({k}, S, {_lib.SEG_CHUNK_FRAMES}) with one S for the call")
+            n_masks = w.shape[1]
+            pcm.append(a)
+            wts.append(w)
+        if n_masks is None or not 1 <= n_masks <= _lib.SPK_MAX_MASKS:
+            raise ValueError(f"masks per chunk {n_masks} outside 1 ... {_lib.SPK_MAX_MASKS}")
+        emb = [np.zeros((w.shape[0], n_masks, self.spk_dim), dtype=np.float32) for w in wts]
+        stats = [np.zeros((w.shape[0], n_masks, _lib.SPK_STATS), dtype=np.float32) for w in wts] if return_stats else None
+        rows = lambda arrs: (C.c_void_p * len(arrs))(*[a.ctypes.data if a.size else None for a in arrs])   # noqa: E731
+        for i0 in range(0, len(pcm), self.max_batch):
+            sl = slice(i0, i0 + self.max_batch)
+            ns = np.asarray([len(a) for a in pcm[sl]], dtype=np.int64)
+            self._check(self.lib.ttasr_spk_embed(self.h, len(ns), rows(pcm[sl]), ns.ctypes.data_as(C.POINTER(C.c_int64)), n_masks,
+                                                 rows(wts[sl]), rows(emb[sl]), rows(stats[sl]) if return_stats else None), "spk_embed")
+        return (emb, stats) if return_stats else emb
 
     # -- streaming voice activity detection --------------------------------------------------------
     def vad_stream_open(self, wire=None) -> int:

@@ -398,6 +398,48 @@ class WhisperModel:
                       "vad_speech_prob_fn was given; the whole clip is treated as speech", stacklevel=stacklevel)
         return "none", None
 
+    # -- speaker diarization ------------------------------------------------------------------------------
+    @property
+    def has_diarization(self) -> bool:
+        """True once load_diarization() has put the segmentation and the speaker-embedding network on lane 0."""
+        return bool(self.__dict__.get("_diarization"))
+
+    def load_diarization(self, seg_weights, spk_weights) -> None:
+        """Loads the PyanNet-shaped segmentation network (vad.load_pyannet_state) and the XVectorSincNet-shaped speaker-embedding
+        network (diarization.load_xvector_state) into lane 0, the context diarize() runs on (a few hundred MB of scratch belong to
+        a context that runs them, so the other lanes stay without).  A segmentation network lane 0 already holds is kept."""
+        from . import diarization
+        lane = self._lanes[0]
+        if not getattr(lane, "has_segmentation", False):
+            lane.load_segmentation(vad.load_pyannet_state(seg_weights))
+        lane.load_speaker_embedding(diarization.load_xvector_state(spk_weights))
+        self._diarization = True
+
+    def diarize(self, audio: Union[str, np.ndarray], num_speakers: Optional[int] = None, audio_channel=None, **kw) -> list:
+        """Who spoke when: a list of diarization.Turn(start, end, speaker) in seconds, speakers "SPEAKER_00", "SPEAKER_01", ... in
+        order of first appearance.  Two device calls - the segmentation network, then the speaker embeddings of every chunk's
+        local speakers - with the masks on the host between them, then clustering and reconstruction on the host
+        (diarization.diarize; its keywords - threshold, onset, min_duration_on, min_duration_off, ... - pass through).
+        num_speakers forces the number of clusters."""
+        from . import diarization
+        if not self.has_diarization:
+            raise RuntimeError("no diarization networks are loaded (model.load_diarization(seg_weights, spk_weights))")
+        if isinstance(audio, str):
+            audio = decode_audio(audio, channel=parse_audio_channel(audio_channel))
+        return diarization.diarize(self._lanes[0], np.asarray(audio, dtype=np.float32), num_speakers=num_speakers, **kw)
+
+    def transcribe_diarized(self, audio: Union[str, np.ndarray], num_speakers: Optional[int] = None,
+                            diarization_options: Optional[dict] = None, **kw) -> Tuple[list, TranscriptionInfo]:
+        """transcribe(audio, **kw) with every segment's speaker: ([(Segment, speaker or None), ...], info).  The speaker of a
+        segment is the one whose turns overlap it longest (diarization.assign_speakers); Segment keeps its fields."""
+        from . import diarization
+        if isinstance(audio, str):   # read once, for both passes
+            audio = decode_audio(audio, channel=parse_audio_channel(kw.pop("audio_channel", None)))
+        turns = self.diarize(audio, num_speakers=num_speakers, **(diarization_options or {}))
+        segments, info = self.transcribe(audio, **kw)
+        segments = list(segments)
+        return list(zip(segments, diarization.assign_speakers(segments, turns))), info
+
     # -- file ingest on the device --------------------------------------------------------------------
     def decode_audio_many(self, paths_or_arrays: Sequence[Union[str, np.ndarray]], audio_channel=None) -> List[np.ndarray]:
         """Every path -> mono float32 @16 kHz with ONE device call for all the files the device takes (read_audio_coded +
