@@ -243,7 +243,13 @@ TTASR_API int ttasr_set_audio_ctx(ttasr_ctx* ctx, int32_t n_ctx);
 /* ---- a9-a10: decoder (ctranslate2 Whisper.generate) --------------------------------------------- */
 /* Greedy search.  prompt_host: [B][max_prompt] ids, prompt_len_host[b] of them valid (>=1).
  * out_tokens_host: [B][max_new_tokens] sampled ids (EOT included when emitted), out_len_host[b] count.
- * out_sum_logprob_host / out_no_speech_host: optional [B]. */
+ * out_sum_logprob_host / out_no_speech_host: optional [B].
+ * A row whose logits leave NO selectable token at some step - every id masked by the rules, or every logit NaN (non-finite
+ * weights, mel or encoder output reach this through the test hooks above) - ends there: the token is EOT, the step's
+ * log-probability increment is -inf (so out_sum_logprob is -inf and the clip's average fails every log-prob threshold), the row is
+ * finished.  The same holds for ttasr_generate_capped, ttasr_generate_sample, the rows of a continuous-batching session and the
+ * independent rows of a beam session; beam search answers the case with TTASR_E_INVALID "no live candidate".  No token id outside
+ * [0, vocab) is ever produced.  A row with SOME NaN logits never selects them, but its log-probabilities are NaN. */
 TTASR_API int ttasr_generate(ttasr_ctx* ctx, int32_t B, const int32_t* prompt_host, const int32_t* prompt_len_host,
                    int32_t max_prompt, const ttasr_gen_opts* opts, int32_t* out_tokens_host, int32_t* out_len_host,
                    float* out_sum_logprob_host, float* out_no_speech_host);
@@ -295,6 +301,67 @@ TTASR_API int ttasr_decode_step(ttasr_ctx* ctx, const int32_t* tokens_host, int3
  * sampled-token histories padded with -1 -> processed rows (masked entries = -inf) and the selected id. */
 TTASR_API int ttasr_apply_rules(ttasr_ctx* ctx, const float* rows_host, const int32_t* hist_host, int32_t hist_stride,
                       int32_t n, const ttasr_gen_opts* opts, float* out_rows_host, int32_t* out_choice_host);
+/* Known-answer hook for the token-selection kernels (kernels_decode.hip; tests/test_gpu_select_kernels.py):
+ * ONE launch of a named form, through the launcher the engine itself calls, on caller-supplied raw logits rows_host f32 [n][vocab]
+ * (1 <= n <= max_batch), which are copied into the engine's logits block at its row stride.  The hook has no decision logic:
+ *   TTASR_SELECT_STEP     launch_select (no processed-row output, the step ticket, total_rows = n) at the position positions_host[0]
+ *   TTASR_SELECT_ROWS     launch_select_rows: row r at its own position positions_host[r]
+ *   TTASR_SELECT_SESSION  launch_session_rows_select over n_entries <= max_batch entries {row < n, position, key row, flags
+ *                         (1 choose, 2 no-speech)} with a temperature and a seed per entry -> out_f32 [n_entries][3] = {choice (int
+ *                         bits, -1: entry does not choose), log-probability increment, no-speech}
+ *   TTASR_SELECT_TOPK     launch_beam_topk, 1 <= k <= 8 -> out_f32 [n][k] log-probabilities, out_i32 [n][k] ids (-1: fewer than k
+ *                         allowed tokens, log-probability -inf), no_speech [n] when want_no_speech != 0
+ *   TTASR_SELECT_LOGPROB  launch_token_logprob: out_f32 [n] = log softmax(row r)[targets_host[r]]
+ *   TTASR_SELECT_PROB     launch_token_prob: out_f32 [n] = softmax(row r)[token]
+ * opts, temperature, seed: the rules of the launch (STEP, ROWS, SESSION, TOPK; temperature > 0 = the sampling instantiation of STEP
+ * and ROWS).  hist_host [n][hist_stride]: sampled-token histories padded with -1, as ttasr_apply_rules (NULL: empty histories).
+ * STEP and ROWS: prompt_host [n][max_prompt] with prompt_len_host [n] (NULL: no forced tokens) and the initial done, row_cap,
+ * sum_logprob [n] (NULL: live rows, no budget, 0) and n_done; they return the WHOLE search state after the launch - cur_tok,
+ * n_sampled, last_tok, pen_tok, last_ts, done [n], positions (STEP: {*step, the ticket word}; ROWS: [n]), n_done [1], sum_logprob,
+ * no_speech [n], out_tokens [n][opts->max_new_tokens] (-1 where nothing was stored; cur_tok starts at -1 too).  Any output pointer
+ * may be NULL.  sig_buf (optional, sig_len bytes) receives the instantiation that ran.  Refused in an open session.  The call
+ * overwrites search state: it is UNDEFINED afterwards until ttasr_decode_reset, a generate call or a session start. */
+#define TTASR_SELECT_STEP 0
+#define TTASR_SELECT_ROWS 1
+#define TTASR_SELECT_SESSION 2
+#define TTASR_SELECT_TOPK 3
+#define TTASR_SELECT_LOGPROB 4
+#define TTASR_SELECT_PROB 5
+typedef struct ttasr_select_io {
+  /* in */
+  const float* rows_host;
+  const ttasr_gen_opts* opts;
+  const int32_t* hist_host;
+  const int32_t* positions_host;
+  const int32_t* prompt_host;
+  const int32_t* prompt_len_host;
+  const int32_t* done_host;
+  const int32_t* row_cap_host;
+  const float* sum_logprob_host;
+  const int32_t* entries_host;       /* SESSION [n_entries][4] */
+  const float* entry_temp_host;      /* SESSION [n_entries] */
+  const uint32_t* entry_seed_host;   /* SESSION [n_entries] */
+  const int32_t* targets_host;       /* LOGPROB [n] */
+  /* out (each optional) */
+  int32_t* out_cur_tok;
+  int32_t* out_n_sampled;
+  int32_t* out_last_tok;
+  int32_t* out_pen_tok;
+  int32_t* out_last_ts;
+  int32_t* out_done;
+  int32_t* out_positions;
+  int32_t* out_n_done;
+  float* out_sum_logprob;
+  float* out_no_speech;
+  int32_t* out_tokens;
+  float* out_f32;
+  int32_t* out_i32;
+  /* scalars */
+  int32_t n, hist_stride, max_prompt, n_done, n_entries, k, want_no_speech, token;
+  float temperature;
+  uint32_t seed;
+} ttasr_select_io;
+TTASR_API int ttasr_select_probe(ttasr_ctx* ctx, int32_t form, const ttasr_select_io* io, char* sig_buf, int32_t sig_len);
 
 /* ---- continuous batching: greedy single-window decoding with slot refill ----------------------------------------------
  * Clips are submitted at any time; each takes a free row of the context's max_batch-row decode batch, decodes until EOT or its

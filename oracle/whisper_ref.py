@@ -790,3 +790,141 @@ def self_attn_causal_ref(q: np.ndarray, k: np.ndarray, v: np.ndarray, lens: Sequ
             res.append((out, s, K[:, :t + 1], V[:, :t + 1]))
         r0 += n
     return res
+
+
+# --------------------------------------------------------------------------------------------------
+# a10 once more, as ONE row's complete selection in float64 (tests/select_cases.py, tests/test_gpu_select_kernels.py): what the
+# token-selection kernels of kernels_decode.hip must return for a raw f32 logits row.  The mask is apply_rules' ([HF-LP]:1816
+# begin suppress, :1869 suppress, :2000-2047 timestamp rules); the forced-timestamp rule ([HF-LP]:2040-2047) is evaluated here in
+# float64 so that its margin is known.  Non-finite logits: an allowed NaN is never chosen (every comparison with it is false) and
+# is ignored by the maxima, but it poisons every sum it enters - the log-normaliser and with it every log-probability of the row
+# are NaN, and a NaN among the timestamps keeps the forced rule off (NaN > x is false); -inf elements behave as masked ones.
+# --------------------------------------------------------------------------------------------------
+@dataclass
+class SelectRef:
+    masked: np.ndarray               # bool [V]: the processed mask, the forced-timestamp rule included
+    forced: bool                     # the timestamp-mass rule fired
+    margin: float                    # logsumexp(allowed timestamps) - max(allowed text); nan when timestamps are off or a side is empty
+    m: float                         # largest allowed logit (-inf: nothing selectable)
+    lse: float                       # logsumexp of the allowed set
+    choice: int                      # lowest index among exact equals; -1: nothing selectable
+    lp: float                        # log-probability increment of the choice (-inf when nothing is selectable)
+    gap: float                       # choice's lead over the best other allowed value (0: exact tie, inf: single candidate)
+    no_speech: Optional[float]       # softmax(raw row)[no_speech]
+    topk_id: Optional[np.ndarray] = None    # value descending, then id ascending; -1 where fewer than k tokens are allowed
+    topk_lp: Optional[np.ndarray] = None    # -inf there
+    sample_choice: int = -1          # argmax(s / T + sample_gumbel(seed, key row, position))
+    sample_lp: float = NEG_INF
+    sample_gap: float = float("inf")  # perturbed top-2 gap
+
+
+def select_ref(row: np.ndarray, sampled: Sequence[int], rules: Rules, no_speech: int = -1, k: int = 0,
+               temperature: float = 0.0, seed: int = 0, key_row: int = 0, position: int = 0) -> SelectRef:
+    row = np.asarray(row, dtype=np.float32)
+    V = row.shape[0]
+    s32 = apply_rules(torch.from_numpy(row), list(sampled), rules, ts_prob_rule=False).numpy()
+    s = s32.astype(np.float64)
+    tb = rules.timestamp_begin if rules.timestamps else V
+    live = ~np.isnan(s) & ~np.isneginf(s)          # selectable: allowed, and neither NaN nor -inf
+
+    def lse_of(x: np.ndarray) -> float:
+        if x.size == 0:
+            return NEG_INF
+        if np.isnan(x).any():
+            return float("nan")
+        mx = x.max()
+        return NEG_INF if np.isneginf(mx) else (float("inf") if np.isposinf(mx) else float(mx + np.log(np.exp(x - mx).sum())))
+
+    allowed = ~np.isneginf(s)                       # NaN elements stay in the sums
+    margin, forced = float("nan"), False
+    if rules.timestamps:
+        txt = s[:tb][live[:tb]]
+        if allowed[tb:].any():
+            l_ts = lse_of(s[tb:][allowed[tb:]])
+            margin = l_ts - (txt.max() if txt.size else NEG_INF)
+            forced = bool(margin > 0) and bool(live[tb:].any())
+    if forced:
+        s = s.copy(); s[:tb] = NEG_INF
+        live[:tb] = False; allowed[:tb] = False
+    masked = np.isneginf(s)
+    ns = None
+    if no_speech >= 0:
+        raw = row.astype(np.float64)
+        l_raw = lse_of(raw)
+        ns = float(np.exp(raw[no_speech] - l_raw)) if np.isfinite(l_raw) else float("nan")
+    lse = lse_of(s[allowed])
+    if not live.any():
+        out = SelectRef(masked, forced, margin, NEG_INF, lse, -1, NEG_INF, float("inf"), ns)
+    else:
+        vals = np.where(live, s, NEG_INF)
+        choice = int(np.argmax(vals))               # first maximum
+        m = float(vals[choice])
+        rest = vals.copy(); rest[choice] = NEG_INF
+        out = SelectRef(masked, forced, margin, m, lse, choice, float(m - lse), float(m - rest.max()), ns)
+    if k > 0:
+        ids = np.full(k, -1, dtype=np.int64); lps = np.full(k, NEG_INF)
+        idx = np.flatnonzero(live)
+        order = idx[np.lexsort((idx, -s[idx]))][:k]
+        ids[:len(order)] = order; lps[:len(order)] = s[order] - lse
+        out.topk_id, out.topk_lp = ids, lps
+    if temperature > 0 and live.any():
+        g = sample_gumbel(seed, key_row, position, V).astype(np.float64)
+        z = np.where(live, (s32 / np.float32(temperature)).astype(np.float64) + g, NEG_INF)
+        if forced:
+            z[:tb] = NEG_INF
+        c = int(np.argmax(z))
+        rest = z.copy(); rest[c] = NEG_INF
+        out.sample_choice, out.sample_lp, out.sample_gap = c, float(s[c] - lse), float(z[c] - rest.max())
+    return out
+
+
+@dataclass
+class SelectRow:
+    """The search state of one row as select_body keeps it (DecState of csrc/common.hpp) with what it feeds next."""
+    n_sampled: int = 0
+    last_tok: int = -1
+    pen_tok: int = -1
+    last_ts: int = -1
+    done: int = 0
+    sum_logprob: float = 0.0
+    cur_tok: int = -1
+    stored: Optional[Tuple[int, int]] = None   # (index into out_tokens, token) of this step
+    newly_done: bool = False
+    advanced: bool = False                     # ROWS form: the row's own position moved on
+    captured_ns: bool = False
+    chose: bool = False                        # the row took its choice (not forced, not finished before)
+
+
+def select_history(sampled: Sequence[int], rules: Rules) -> SelectRow:
+    """The state a history leaves behind (timestamps are recorded only in timestamp mode)."""
+    sampled = list(sampled)
+    ts = [t for t in sampled if t >= rules.timestamp_begin] if rules.timestamps else []
+    return SelectRow(len(sampled), sampled[-1] if sampled else -1, sampled[-2] if len(sampled) > 1 else -1, ts[-1] if ts else -1)
+
+
+def select_transition(st: SelectRow, position: int, choice: int, lp: float, rules: Rules, max_new: int, row_cap: int,
+                      prompt: Optional[Sequence[int]] = None, sot_index: int = 0, want_no_speech: bool = False,
+                      rows_form: bool = False) -> SelectRow:
+    """The comment block at select_body restated: a row inside its prompt is fed the next prompt token, a finished row is fed EOT
+    (state untouched in both); otherwise the choice is fed, added to the sum, stored at out_tokens[n_sampled] when it fits, and
+    the history moves on; the row finishes on EOT, at the call's budget or at its own.  The no-speech probability is captured at
+    the <|startoftranscript|> position whatever the row does there (the ROWS form: live rows only).  (choice, lp) of a row with
+    nothing selectable are (eot, -inf)."""
+    o = SelectRow(st.n_sampled, st.last_tok, st.pen_tok, st.last_ts, st.done, st.sum_logprob)
+    o.captured_ns = want_no_speech and position == sot_index and not (rows_form and st.done)
+    o.advanced = rows_form and not st.done
+    if prompt is not None and position + 1 < len(prompt):
+        o.cur_tok = int(prompt[position + 1])
+    elif st.done:
+        o.cur_tok = rules.eot
+    else:
+        o.cur_tok, o.chose = choice, True
+        o.sum_logprob = st.sum_logprob + lp
+        if st.n_sampled < max_new:
+            o.stored = (st.n_sampled, choice)
+        o.n_sampled, o.pen_tok, o.last_tok = st.n_sampled + 1, st.last_tok, choice
+        if rules.timestamps and choice >= rules.timestamp_begin:
+            o.last_ts = choice
+        if choice == rules.eot or st.n_sampled + 1 >= min(max_new, row_cap):
+            o.done, o.newly_done = 1, True
+    return o

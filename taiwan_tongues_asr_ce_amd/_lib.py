@@ -15,7 +15,7 @@ SYMBOLS = [
     "ttasr_create", "ttasr_create_shared", "ttasr_destroy", "ttasr_last_error", "ttasr_version", "ttasr_load_tensor", "ttasr_load_tensor_device",
     "ttasr_finalize_weights", "ttasr_log_mel", "ttasr_log_mel_windows", "ttasr_log_mel_windows_cut", "ttasr_set_mel", "ttasr_encode", "ttasr_set_encoder_output",
     "ttasr_get_cross_kv", "ttasr_get_cross_kv_fp8", "ttasr_cross_attn_probe", "ttasr_align_attn_probe",
-    "ttasr_self_kv_fill", "ttasr_self_kv_set", "ttasr_self_kv_get", "ttasr_self_attn_probe", "ttasr_set_audio_ctx", "ttasr_generate", "ttasr_generate_capped", "ttasr_generate_beam", "ttasr_generate_beam_ragged", "ttasr_generate_sample", "ttasr_decode_reset", "ttasr_decode_step", "ttasr_apply_rules", "ttasr_align", "ttasr_dtw",
+    "ttasr_self_kv_fill", "ttasr_self_kv_set", "ttasr_self_kv_get", "ttasr_self_attn_probe", "ttasr_set_audio_ctx", "ttasr_generate", "ttasr_generate_capped", "ttasr_generate_beam", "ttasr_generate_beam_ragged", "ttasr_generate_sample", "ttasr_decode_reset", "ttasr_decode_step", "ttasr_apply_rules", "ttasr_select_probe", "ttasr_align", "ttasr_dtw",
     "ttasr_set_option", "ttasr_phase_ms", "ttasr_beam_profile", "ttasr_encoder_kernel_ms", "ttasr_bench_kernel", "ttasr_bench_kernel_signature", "ttasr_sync",
     "ttasr_session_begin", "ttasr_session_begin_beam", "ttasr_session_submit", "ttasr_session_submit_windows", "ttasr_session_poll", "ttasr_session_stats", "ttasr_session_rows", "ttasr_session_end",
     "ttasr_align_batch", "ttasr_session_hold", "ttasr_session_align", "ttasr_session_release", "ttasr_detect_language",
@@ -53,6 +53,20 @@ class GenOpts(C.Structure):
         "max_new_tokens", "eot", "no_timestamps", "timestamp_begin", "no_speech", "sot_index", "timestamps",
         "max_initial_timestamp_index", "suppress_eot", "n_suppress", "n_begin_suppress", "check_interval")] + [
         ("suppress", C.POINTER(C.c_int32)), ("begin_suppress", C.POINTER(C.c_int32))]
+
+
+SELECT_FORMS = {"step": 0, "rows": 1, "session": 2, "topk": 3, "logprob": 4, "prob": 5}   # TTASR_SELECT_* of include/ttasr.h
+
+
+class SelectIO(C.Structure):
+    """ttasr_select_io: 13 input pointers, 13 output pointers, 8 int32 scalars, temperature, seed."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "rows_host", "opts", "hist_host", "positions_host", "prompt_host", "prompt_len_host", "done_host", "row_cap_host",
+        "sum_logprob_host", "entries_host", "entry_temp_host", "entry_seed_host", "targets_host",
+        "out_cur_tok", "out_n_sampled", "out_last_tok", "out_pen_tok", "out_last_ts", "out_done", "out_positions", "out_n_done",
+        "out_sum_logprob", "out_no_speech", "out_tokens", "out_f32", "out_i32")] + [(n, C.c_int32) for n in (
+        "n", "hist_stride", "max_prompt", "n_done", "n_entries", "k", "want_no_speech", "token")] + [
+        ("temperature", C.c_float), ("seed", C.c_uint32)]
 
 
 def build(verbose: bool = False) -> str:
@@ -113,6 +127,7 @@ def load() -> C.CDLL:
     lib.ttasr_decode_reset.argtypes = [vp, i32]
     lib.ttasr_decode_step.argtypes = [vp, i32p, i32, vp]
     lib.ttasr_apply_rules.argtypes = [vp, vp, i32p, i32, i32, C.POINTER(GenOpts), vp, i32p]
+    lib.ttasr_select_probe.argtypes = [vp, i32, C.POINTER(SelectIO), C.c_char_p, i32]
     lib.ttasr_align.argtypes = [vp, i32, i32p, i32, i32p, i32, f32p, f32p]
     lib.ttasr_detect_language.argtypes = [vp, i32, i32, i32, i32, i32p, f32p, f32p]
     lib.ttasr_align_batch.argtypes = [vp, i32, i32p, i32p, i32p, i32, i32p, i32p, i32p, i32, i32, i32p, f32p, f32p, f32p]

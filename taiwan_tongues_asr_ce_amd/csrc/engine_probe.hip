@@ -1,0 +1,184 @@
+// libttasr: the known-answer hook of the token-selection kernels, ttasr_select_probe (one of the engine translation units, see
+// engine_ctx.hpp).  It stages the caller's rows, histories and state in the buffers the searches use, calls ONE launcher of
+// kernels_decode.hip with the arguments the engine passes it, and copies the results back.  No decision of its own: what is
+// chosen, summed or finished is what the kernel did.
+#include "engine_ctx.hpp"
+
+namespace ttasr_detail {
+
+// the per-row history state the searches keep: length, last, penultimate, last timestamp (the kernel records a timestamp only
+// in timestamp mode, so a history decoded without timestamps has none)
+struct HistState { std::vector<int32_t> n, last, pen, lts; };
+static HistState hist_state(const int32_t* hist, int stride, int rows, const ttasr_gen_opts* o) {
+  HistState h{std::vector<int32_t>(rows, 0), std::vector<int32_t>(rows, -1), std::vector<int32_t>(rows, -1), std::vector<int32_t>(rows, -1)};
+  if (!hist) return h;
+  for (int r = 0; r < rows; ++r) {
+    int k = 0;
+    for (; k < stride && hist[(size_t)r * stride + k] >= 0; ++k) {
+      const int t = hist[(size_t)r * stride + k];
+      h.pen[r] = h.last[r]; h.last[r] = t;
+      if (o->timestamps && t >= o->timestamp_begin) h.lts[r] = t;
+    }
+    h.n[r] = k;
+  }
+  return h;
+}
+
+static int select_probe(ttasr_ctx* c, int form, const ttasr_select_io& io, char* sig_buf, int sig_len) {
+  const int n = io.n, V = c->V;
+  if (form < TTASR_SELECT_STEP || form > TTASR_SELECT_PROB) return fail(c, TTASR_E_INVALID, "select probe: form %d", form);
+  if (!io.rows_host || n < 1 || n > c->maxB) return fail(c, TTASR_E_INVALID, "select probe: rows NULL or n %d outside [1, max_batch=%d]", n, c->maxB);
+  const bool ruled = form <= TTASR_SELECT_TOPK, stateful = form == TTASR_SELECT_STEP || form == TTASR_SELECT_ROWS;
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const ttasr_gen_opts* o = io.opts;
+  HistState h;
+  std::vector<int32_t> ent, pos;
+  int max_new = 1;
+  if (ruled) {
+    if (!o) return fail(c, TTASR_E_INVALID, "select probe: opts is NULL");
+    if (io.hist_host && io.hist_stride < 1) return fail(c, TTASR_E_INVALID, "select probe: hist_stride %d", io.hist_stride);
+    if (o->no_speech < -1 || o->no_speech >= V) return fail(c, TTASR_E_INVALID, "select probe: no_speech id %d outside the vocabulary", o->no_speech);
+    if (!(io.temperature >= 0.f) || !(io.temperature < INFINITY)) return fail(c, TTASR_E_INVALID, "select probe: temperature");
+    const bool prompted = stateful && io.prompt_host;
+    const int max_prompt = prompted ? io.max_prompt : 1;
+    if (prompted) {
+      if (!io.prompt_len_host || max_prompt < 1 || max_prompt > c->max_prompt_alloc) return fail(c, TTASR_E_INVALID, "select probe: max_prompt %d", max_prompt);
+      for (int r = 0; r < n; ++r) {
+        const int len = io.prompt_len_host[r];
+        if (len < 1 || len > max_prompt) return fail(c, TTASR_E_INVALID, "select probe: prompt %d: length %d outside [1, %d]", r, len, max_prompt);
+        for (int j = 0; j < max_prompt; ++j) {
+          const int t = io.prompt_host[(size_t)r * max_prompt + j];
+          if (t < 0 || t >= V) return fail(c, TTASR_E_INVALID, "select probe: prompt %d: token %d outside the vocabulary", r, t);
+        }
+      }
+    }
+    if (stateful) {
+      const int np = form == TTASR_SELECT_STEP ? 1 : n;
+      if (!io.positions_host) return fail(c, TTASR_E_INVALID, "select probe: positions is NULL");
+      for (int r = 0; r < np; ++r)
+        if (io.positions_host[r] < 0 || io.positions_host[r] >= c->cfg.n_text_ctx)
+          return fail(c, TTASR_E_INVALID, "select probe: position %d outside [0, %d)", io.positions_host[r], c->cfg.n_text_ctx);
+      if (io.n_done < 0 || io.n_done > c->maxB) return fail(c, TTASR_E_INVALID, "select probe: n_done %d", io.n_done);
+    }
+    if (form == TTASR_SELECT_SESSION) {
+      const int ne = io.n_entries;
+      if (ne < 1 || ne > c->maxB || !io.entries_host || !io.entry_temp_host || !io.entry_seed_host)
+        return fail(c, TTASR_E_INVALID, "select probe: 1 .. max_batch entries with temperatures and seeds expected");
+      for (int e = 0; e < ne; ++e) {
+        const int32_t* q = io.entries_host + 4 * e;
+        if (q[0] < 0 || q[0] >= n || q[1] < 0 || q[1] >= c->cfg.n_text_ctx || q[2] < 0 || q[3] < 0 || q[3] > 3)
+          return fail(c, TTASR_E_INVALID, "select probe: entry %d {%d, %d, %d, %d}", e, q[0], q[1], q[2], q[3]);
+        if (!(io.entry_temp_host[e] >= 0.f) || !(io.entry_temp_host[e] < INFINITY)) return fail(c, TTASR_E_INVALID, "select probe: entry %d: temperature", e);
+      }
+    }
+    if (form == TTASR_SELECT_TOPK && (io.k < 1 || io.k > 8)) return fail(c, TTASR_E_INVALID, "select probe: k %d outside [1, 8]", io.k);
+    RuleParams old = c->rp;
+    TRY(upload_rules(c, o, max_prompt));   // validates max_new_tokens and the token ids; synchronises the stream
+    c->rp.temperature = stateful ? io.temperature : 0.f; c->rp.seed = io.seed;
+    TRY(commit_rules(c, old));
+    TRY(reset_search(c, n));
+    max_new = c->rp.max_new;
+    h = hist_state(io.hist_host, io.hist_stride, n, o);
+  } else if (form == TTASR_SELECT_LOGPROB) {
+    if (!io.targets_host) return fail(c, TTASR_E_INVALID, "select probe: targets is NULL");
+    for (int r = 0; r < n; ++r)
+      if (io.targets_host[r] < 0 || io.targets_host[r] >= V) return fail(c, TTASR_E_INVALID, "select probe: target %d outside the vocabulary", io.targets_host[r]);
+  } else if (io.token < 0 || io.token >= V) {
+    return fail(c, TTASR_E_INVALID, "select probe: token %d outside the vocabulary", io.token);
+  }
+  HIPCHK(c, hipMemcpy2DAsync(c->logits, (size_t)c->ldv * 4, io.rows_host, (size_t)V * 4, (size_t)V * 4, n, hipMemcpyHostToDevice, s));
+  auto up = [&](void* dst, const void* src, size_t bytes) -> int { HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s)); return 0; };
+  auto down = [&](void* dst, const void* src, size_t bytes) -> int { if (dst) HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s)); return 0; };
+  const size_t n4 = (size_t)n * 4;
+  g_kernel_sig[0] = 0;
+  if (stateful) {
+    TRY(up(c->st.n_sampled, h.n.data(), n4)); TRY(up(c->st.last_tok, h.last.data(), n4));
+    TRY(up(c->st.pen_tok, h.pen.data(), n4)); TRY(up(c->st.last_ts, h.lts.data(), n4));
+    if (io.done_host) TRY(up(c->st.done, io.done_host, n4));
+    if (io.row_cap_host) TRY(up(c->row_cap_dev, io.row_cap_host, n4));
+    if (io.sum_logprob_host) TRY(up(c->st.sum_logprob, io.sum_logprob_host, n4));
+    TRY(up(c->st.n_done, &io.n_done, 4));
+    HIPCHK(c, hipMemsetAsync(c->st.cur_tok, 0xff, n4, s));
+    HIPCHK(c, hipMemsetAsync(c->st.out_tokens, 0xff, n4 * max_new, s));
+    DecState st = c->st; st.prompt = nullptr; st.prompt_len = nullptr;
+    if (io.prompt_host) {
+      TRY(up(c->prompt_dev, io.prompt_host, n4 * io.max_prompt)); TRY(up(c->plen_dev, io.prompt_len_host, n4));
+      st.prompt = c->prompt_dev; st.prompt_len = c->plen_dev;
+    }
+    if (form == TTASR_SELECT_STEP) {
+      TRY(up(c->st.step, io.positions_host, 4));   // reset_search cleared the ticket word behind it
+      g_kernel_sig_on = true;
+      launch_select(c->logits, st, c->rp, n, nullptr, s, c->st.step + 1, n);
+      g_kernel_sig_on = false;
+      TRY(down(io.out_positions, c->st.step, 8));
+    } else {
+      if (!c->row_pos) TRY(dalloc(c, &c->row_pos, (size_t)c->maxB * 4));
+      TRY(up(c->row_pos, io.positions_host, n4));
+      st.step = c->row_pos;
+      g_kernel_sig_on = true;
+      launch_select_rows(c->logits, st, c->rp, n, s);
+      g_kernel_sig_on = false;
+      TRY(down(io.out_positions, c->row_pos, n4));
+    }
+    TRY(down(io.out_cur_tok, c->st.cur_tok, n4)); TRY(down(io.out_n_sampled, c->st.n_sampled, n4));
+    TRY(down(io.out_last_tok, c->st.last_tok, n4)); TRY(down(io.out_pen_tok, c->st.pen_tok, n4));
+    TRY(down(io.out_last_ts, c->st.last_ts, n4)); TRY(down(io.out_done, c->st.done, n4));
+    TRY(down(io.out_n_done, c->st.n_done, 4)); TRY(down(io.out_sum_logprob, c->st.sum_logprob, n4));
+    TRY(down(io.out_no_speech, c->st.no_speech, n4)); TRY(down(io.out_tokens, c->st.out_tokens, n4 * max_new));
+  } else if (ruled) {
+    // the host-owned row histories of the beam searches: [4][n] in the row-state block (engine_ctx.hpp beam_row_state)
+    TRY(up(c->row_state, h.n.data(), n4)); TRY(up(c->row_state + n, h.last.data(), n4));
+    TRY(up(c->row_state + 2 * n, h.pen.data(), n4)); TRY(up(c->row_state + 3 * n, h.lts.data(), n4));
+    if (form == TTASR_SELECT_SESSION) {
+      const int ne = io.n_entries;
+      if (!c->sess_sel) TRY(dalloc(c, &c->sess_sel, (size_t)c->maxB * 9 * 4));
+      // device layout as the session's: entries [4 ne] | temperatures [ne] | seeds [ne], results behind the input block
+      int32_t* const d_ent = c->sess_sel;
+      float* const d_out = (float*)(d_ent + 6 * c->maxB);
+      TRY(up(d_ent, io.entries_host, (size_t)ne * 16)); TRY(up(d_ent + 4 * ne, io.entry_temp_host, (size_t)ne * 4));
+      TRY(up(d_ent + 5 * ne, io.entry_seed_host, (size_t)ne * 4));
+      const SessRowsArgs sa{d_ent, (const float*)(d_ent + 4 * ne), (const uint32_t*)(d_ent + 5 * ne), d_out};
+      g_kernel_sig_on = true;
+      launch_session_rows_select(c->logits, beam_row_state(c, n), c->rp, sa, ne, s);
+      g_kernel_sig_on = false;
+      TRY(down(io.out_f32, d_out, (size_t)ne * 12));
+    } else {
+      g_kernel_sig_on = true;
+      launch_beam_topk(c->logits, beam_row_state(c, n), c->rp, n, io.k, c->topk_lp, c->topk_id, io.want_no_speech ? c->st.no_speech : nullptr, s);
+      g_kernel_sig_on = false;
+      TRY(down(io.out_f32, c->topk_lp, n4 * io.k)); TRY(down(io.out_i32, c->topk_id, n4 * io.k));
+      if (io.want_no_speech) TRY(down(io.out_no_speech, c->st.no_speech, n4));
+    }
+  } else {
+    g_kernel_sig_on = true;
+    if (form == TTASR_SELECT_LOGPROB) {
+      TRY(up(c->prompt_dev, io.targets_host, n4));
+      launch_token_logprob(c->logits, c->ldv, V, c->prompt_dev, c->topk_lp, n, s);
+    } else {
+      launch_token_prob(c->logits, c->ldv, V, io.token, c->topk_lp, n, s);
+    }
+    g_kernel_sig_on = false;
+    TRY(down(io.out_f32, c->topk_lp, n4));
+  }
+  HIPCHK(c, hipStreamSynchronize(s));   // the staged vectors are stack temporaries
+  HIPCHK(c, hipGetLastError());
+  c->B_dec = 0;   // the search state no longer belongs to a step-level decode
+  if (sig_buf && sig_len > 0) snprintf(sig_buf, (size_t)sig_len, "%s", g_kernel_sig);
+  return TTASR_OK;
+}
+
+}  // namespace ttasr_detail
+
+extern "C" {
+
+int ttasr_select_probe(ttasr_ctx* c, int32_t form, const ttasr_select_io* io, char* sig_buf, int32_t sig_len) {
+  return guarded(c, [&]() -> int {
+  if (!c) return TTASR_E_INVALID;
+  TRY(session_refusal(c));
+  if (!io) return fail(c, TTASR_E_INVALID, "select probe: io is NULL");
+  return select_probe(c, form, *io, sig_buf, sig_len);
+  });
+}
+
+}  // extern "C"

@@ -681,7 +681,9 @@ static int beam_step(ttasr_ctx* c, Session* S) {
     if (!(en[3] & 1)) continue;
     int choice;
     memcpy(&choice, &x.sel[3 * e], 4);
-    if (choice < 0 || choice >= c->V) return fail(c, TTASR_E_INVALID, "session row %d: no live token (every token masked)", r);
+    // a range guard only: the kernel answers a row with nothing selectable itself (EOT, increment -inf), so no id outside the
+    // vocabulary is expected here any more
+    if (choice < 0 || choice >= c->V) return fail(c, TTASR_E_INVALID, "session row %d: token %d outside the vocabulary", r, choice);
     S->seqs[r].push_back(choice);
     S->fsums[r] += x.sel[3 * e + 1];
     if (choice == o.eot || (int)S->seqs[r].size() >= gr.cap) S->done_rows[r] = 1;

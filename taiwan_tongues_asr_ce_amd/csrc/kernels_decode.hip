@@ -229,7 +229,7 @@ __device__ __forceinline__ void select_totals(const float (&s_sum)[3][16], float
 }
 // thread 0: the forced-timestamp rule, the log-normaliser and the greedy choice, stored to the caller's shared variables
 // (s_force: the timestamp rule fired; s_live = 1: a choice was made).  The same statements as select_body's decision, in the
-// same order.
+// same order.  A row with no selectable element leaves s_choice = 0x7fffffff: the caller answers it (EOT, -inf) as select_body does.
 __device__ __forceinline__ void select_decide(const SelectMax& m, float t0, float t1, const RuleParams& p, int& s_force, int& s_live,
                                               int& s_choice, float& s_cv, float& s_lse) {
   const float mx_all = m.mx_all;
@@ -259,7 +259,9 @@ __device__ __forceinline__ void select_sample(RowRegs& R, int V, int tid, int la
   if (wave == 0) {
     ArgMax x = lane < 16 ? s_am[0][lane] : ArgMax{-INFINITY, 0x7fffffff};
     x = am_wave(x);
-    if (lane == 0) { s_choice = x.i; s_cv = row[x.i]; }
+    // nothing to draw from (unreachable behind the callers' dead-row answer: they sample only rows that have a choice): the
+    // caller's choice stands and no index outside the row is formed
+    if (lane == 0 && x.i != 0x7fffffff) { s_choice = x.i; s_cv = row[x.i]; }
   }
   __syncthreads();
 }
@@ -366,10 +368,14 @@ __device__ __forceinline__ void select_body(const float* logits, DecState st, Ru
         const bool pick_ts = m.mx_ts > m.mx_txt;  // ties go to the lower index, i.e. text
         s_choice = pick_ts ? m.i_ts : m.i_txt; s_cv = pick_ts ? m.mx_ts : m.mx_txt; s_lse = __logf(t0 + t1) + m.mx_all;
       }
+      // no selectable element (everything masked, or every logit NaN: `v > a.v` was never true, the index is still the
+      // sentinel): the row ends here - EOT with a log-probability increment of -inf, so the clip's avg_logprob fails every
+      // threshold; s_live = 2 keeps the sampling pass off the row.  No index outside [0, V) leaves the kernel.
+      if (s_choice == 0x7fffffff) { s_choice = p.eot; s_cv = -INFINITY; s_lse = 0.f; s_live = 2; }
     }
   }
   __syncthreads();
-  if (SAMPLE && s_live)  // pass 3: Gumbel-max sample over the allowed set
+  if (SAMPLE && s_live == 1)  // pass 3: Gumbel-max sample over the allowed set
     select_sample(R, p.V, tid, lane, wave, s_i[2] != 0, tb, sample_key(p.seed, b, step), p.temperature, row, s_am, s_choice, s_cv);
   if (tid == 0 && s_live) {
     const int choice = s_choice;
@@ -405,6 +411,7 @@ __global__ __launch_bounds__(1024) void select_rows_kernel(const float* logits, 
 
 void launch_select_rows(const float* logits, DecState st, RuleParams rp, int B, hipStream_t s) {
   if (rp.V > LOGIT_NIT * 4096) { launch_fault("select: vocabulary %d > %d", rp.V, LOGIT_NIT * 4096); return; }
+  if (g_kernel_sig_on) snprintf(g_kernel_sig, sizeof g_kernel_sig, "select_rows_kernel<%s> grid %d", rp.temperature > 0.f ? "true" : "false", B * 1024);
   if (rp.temperature > 0.f) hipLaunchKernelGGL((select_rows_kernel<true>), dim3(B), dim3(1024), 0, s, logits, st, rp);
   else hipLaunchKernelGGL((select_rows_kernel<false>), dim3(B), dim3(1024), 0, s, logits, st, rp);
 }
@@ -450,9 +457,10 @@ __global__ __launch_bounds__(1024) void session_rows_select_kernel(const float* 
     select_totals(s_sum, t0, t1, t2);
     a.out[3 * e + 2] = want_ns ? __expf(row[p.no_speech] - m.mx_raw) / t2 : 0.f;
     select_decide(m, t0, t1, p, s_i[2], s_i[3], s_choice, s_cv, s_lse);
+    if (s_choice == 0x7fffffff) { s_choice = p.eot; s_cv = -INFINITY; s_lse = 0.f; s_i[3] = 2; }   // no selectable element: as select_body
   }
   __syncthreads();
-  if (choose && temperature > 0.f)
+  if (choose && temperature > 0.f && s_i[3] == 1)
     select_sample(R, p.V, tid, lane, wave, s_i[2] != 0, tb, sample_key(seed, key_row, pos), temperature, row, s_am, s_choice, s_cv);
   if (tid == 0) {
     a.out[3 * e] = __int_as_float(choose ? s_choice : -1);
@@ -461,6 +469,7 @@ __global__ __launch_bounds__(1024) void session_rows_select_kernel(const float* 
 }
 void launch_session_rows_select(const float* logits, BeamRowState hs, RuleParams rp, SessRowsArgs a, int n, hipStream_t s) {
   if (rp.V > LOGIT_NIT * 4096) { launch_fault("select: vocabulary %d > %d", rp.V, LOGIT_NIT * 4096); return; }
+  if (g_kernel_sig_on && n > 0) snprintf(g_kernel_sig, sizeof g_kernel_sig, "session_rows_select_kernel grid %d", n * 1024);
   if (n > 0) hipLaunchKernelGGL(session_rows_select_kernel, dim3(n), dim3(1024), 0, s, logits, hs, rp, a);
 }
 
@@ -495,6 +504,7 @@ void launch_select(const float* logits, DecState st, RuleParams rp, int B, float
                    int total_rows) {
   if (rp.V > LOGIT_NIT * 4096) { launch_fault("select: vocabulary %d > %d", rp.V, LOGIT_NIT * 4096); return; }
   const bool sample = rp.temperature > 0.f;
+  if (g_kernel_sig_on) snprintf(g_kernel_sig, sizeof g_kernel_sig, "select_kernel<%s, %s> grid %d", sample ? "true" : "false", out_rows ? "true" : "false", B * 1024);
 #define TTASR_SELECT(S_, H_) hipLaunchKernelGGL((select_kernel<S_, H_>), dim3(B), dim3(1024), 0, s, logits, st, rp, out_rows, ticket, total_rows)
   if (out_rows) { if (sample) TTASR_SELECT(true, true); else TTASR_SELECT(false, true); }
   else { if (sample) TTASR_SELECT(true, false); else TTASR_SELECT(false, false); }
@@ -544,9 +554,11 @@ __global__ __launch_bounds__(256) void token_prob_kernel(const float* __restrict
   if (tid == 0) out[b] = __expf(row[tok] - m) / ((red[0] + red[1]) + (red[2] + red[3]));
 }
 void launch_token_prob(const float* logits, int ldv, int V, int tok, float* out, int rows, hipStream_t s) {
+  if (g_kernel_sig_on) snprintf(g_kernel_sig, sizeof g_kernel_sig, "token_prob_kernel grid %d", rows * 256);
   hipLaunchKernelGGL(token_prob_kernel, dim3(rows), dim3(256), 0, s, logits, ldv, V, tok, out);
 }
 void launch_token_logprob(const float* logits, int ldv, int V, const int32_t* target, float* out, int rows, hipStream_t s) {
+  if (g_kernel_sig_on) snprintf(g_kernel_sig, sizeof g_kernel_sig, "token_logprob_kernel grid %d", rows * 256);
   hipLaunchKernelGGL(token_logprob_kernel, dim3(rows), dim3(256), 0, s, logits, ldv, V, target, out);
 }
 
@@ -647,5 +659,6 @@ __global__ __launch_bounds__(1024) void beam_topk_kernel(const float* __restrict
 
 void launch_beam_topk(const float* logits, BeamRowState st, RuleParams rp, int R, int k, float* out_lp, int32_t* out_id,
                       float* out_no_speech, hipStream_t s) {
+  if (g_kernel_sig_on) snprintf(g_kernel_sig, sizeof g_kernel_sig, "beam_topk_kernel grid %d k %d", R * 1024, k);
   hipLaunchKernelGGL(beam_topk_kernel, dim3(R), dim3(1024), 0, s, logits, st, rp, k, out_lp, out_id, out_no_speech);
 }

@@ -813,6 +813,79 @@ class Engine:
                     "apply_rules")
         return out, choice
 
+    def select_probe(self, form: str, rows: np.ndarray, opts=None, hist: Optional[np.ndarray] = None, positions=None,
+                     temperature: float = 0.0, seed: int = 0, prompt: Optional[np.ndarray] = None, prompt_len=None, done=None,
+                     row_cap=None, sum_logprob=None, n_done: int = 0, entries=None, entry_temp=None, entry_seed=None, k: int = 0,
+                     want_no_speech: bool = False, targets=None, token: int = 0) -> Dict[str, object]:
+        """One launch of a named form of the token-selection kernels on the caller's raw logits rows float32 [n][vocab]
+        (ttasr_select_probe): "step", "rows" (the whole search state after the launch, by field name, plus "positions"),
+        "session" ("choice" int32, "lp", "no_speech" per entry), "topk" ("lp", "id" [n][k], "no_speech"), "logprob", "prob"
+        ("out" [n]).  Every result carries "sig", the instantiation that ran.  The search state is undefined afterwards."""
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        n = rows.shape[0]
+        assert rows.ndim == 2 and rows.shape[1] == self.dims.vocab, rows.shape
+        io = _lib.SelectIO()
+        keep = [rows]
+
+        def arr(a, dt, shape=None):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dt)
+            assert shape is None or a.shape == shape, (a.shape, shape)
+            keep.append(a)
+            return a.ctypes.data
+
+        def out(name, shape, dt):
+            a = np.zeros(shape, dtype=dt)
+            setattr(io, name, a.ctypes.data)
+            return a
+
+        io.rows_host, io.n = rows.ctypes.data, n
+        io.opts = C.addressof(opts) if opts is not None else None
+        if hist is not None:
+            hist = np.ascontiguousarray(hist, dtype=np.int32)
+            assert hist.ndim == 2 and hist.shape[0] == n, hist.shape
+            io.hist_host, io.hist_stride = arr(hist, np.int32), hist.shape[1]
+        io.temperature, io.seed = float(temperature), int(seed) & 0xFFFFFFFF
+        res: Dict[str, object] = {}
+        if form in ("step", "rows"):
+            io.positions_host = arr(np.atleast_1d(positions), np.int32, (1,) if form == "step" else (n,))
+            if prompt is not None:
+                prompt = np.ascontiguousarray(prompt, dtype=np.int32)
+                assert prompt.ndim == 2 and prompt.shape[0] == n, prompt.shape
+                io.prompt_host, io.max_prompt = arr(prompt, np.int32), prompt.shape[1]
+                io.prompt_len_host = arr(prompt_len, np.int32, (n,))
+            io.done_host, io.row_cap_host = arr(done, np.int32, (n,)), arr(row_cap, np.int32, (n,))
+            io.sum_logprob_host, io.n_done = arr(sum_logprob, np.float32, (n,)), int(n_done)
+            for f in ("cur_tok", "n_sampled", "last_tok", "pen_tok", "last_ts", "done"):
+                res[f] = out("out_" + f, n, np.int32)
+            res["positions"] = out("out_positions", 2 if form == "step" else n, np.int32)
+            res["n_done"] = out("out_n_done", 1, np.int32)
+            res["sum_logprob"], res["no_speech"] = out("out_sum_logprob", n, np.float32), out("out_no_speech", n, np.float32)
+            res["out_tokens"] = out("out_tokens", (n, opts.max_new_tokens), np.int32)
+        elif form == "session":
+            ent = np.ascontiguousarray(entries, dtype=np.int32).reshape(-1, 4)
+            io.entries_host, io.n_entries = arr(ent, np.int32), len(ent)
+            io.entry_temp_host, io.entry_seed_host = arr(entry_temp, np.float32, (len(ent),)), arr(entry_seed, np.uint32, (len(ent),))
+            raw = out("out_f32", (len(ent), 3), np.float32)
+        elif form == "topk":
+            io.k, io.want_no_speech = int(k), int(bool(want_no_speech))
+            res["lp"], res["id"] = out("out_f32", (n, k), np.float32), out("out_i32", (n, k), np.int32)
+            if want_no_speech:
+                res["no_speech"] = out("out_no_speech", n, np.float32)
+        elif form == "logprob":
+            io.targets_host = arr(targets, np.int32, (n,))
+            res["out"] = out("out_f32", n, np.float32)
+        elif form == "prob":
+            io.token = int(token)
+            res["out"] = out("out_f32", n, np.float32)
+        buf = C.create_string_buffer(192)
+        self._check(self.lib.ttasr_select_probe(self.h, _lib.SELECT_FORMS[form], C.byref(io), buf, 192), "select_probe")
+        if form == "session":
+            res["choice"], res["lp"], res["no_speech"] = raw[:, 0].copy().view(np.int32), raw[:, 1].copy(), raw[:, 2].copy()
+        res["sig"] = buf.value.decode()
+        return res
+
     # -- measurement ---------------------------------------------------------------------------
     def phase_ms(self) -> Dict[str, float]:
         a = (C.c_float * 4)()

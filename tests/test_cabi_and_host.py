@@ -58,6 +58,18 @@ def test_release_library_has_no_environment_switch(lib):
 def test_struct_layouts_match_header():
     assert ctypes.sizeof(_lib.Config) == 12 * 4
     assert ctypes.sizeof(_lib.GenOpts) == 12 * 4 + 2 * ctypes.sizeof(ctypes.c_void_p)
+    # ttasr_select_io: the header's fields in the header's order - 26 pointers, 8 int32, a float and a uint32
+    hdr = open(os.path.join(ROOT, "include", "ttasr.h")).read()
+    body = hdr[hdr.index("typedef struct ttasr_select_io {") + len("typedef struct ttasr_select_io {"):hdr.index("} ttasr_select_io;")]
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    names = [piece.split()[-1].lstrip("*") for decl in body.split(";") if decl.strip() for piece in decl.split(",")]
+    assert names == [f[0] for f in _lib.SelectIO._fields_], names
+    assert ctypes.sizeof(_lib.SelectIO) == 26 * ctypes.sizeof(ctypes.c_void_p) + 10 * 4
+
+
+def test_select_probe_refuses_a_null_context(lib):
+    io = _lib.SelectIO()
+    assert lib.ttasr_select_probe(None, 0, ctypes.byref(io), None, 0) == -1
 
 
 def test_create_rejects_bad_geometry_and_no_gpu(lib):
