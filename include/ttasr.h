@@ -363,6 +363,50 @@ typedef struct ttasr_select_io {
 } ttasr_select_io;
 TTASR_API int ttasr_select_probe(ttasr_ctx* ctx, int32_t form, const ttasr_select_io* io, char* sig_buf, int32_t sig_len);
 
+/* ---- sequence bias: a logits processor that rewards listed token sequences --------------------
+ * The definition is HF Transformers' SequenceBiasLogitsProcessor.  The table maps token sequences to float biases.  A row's
+ * history is its whole token sequence so far: the prompt, then every sampled token.  A sequence of length 1 always applies to its
+ * token; a sequence of length L > 1 applies to its LAST token when the history holds at least L tokens and its last L - 1 tokens
+ * equal the sequence's first L - 1.  Per vocabulary id the sum starts at 0, takes the length-1 bias, then the matching longer
+ * sequences in table order, in float32, and is added to the raw logit once, in front of the Whisper rules (a suppressed id stays
+ * -inf); log-probabilities are those of the processed distribution.
+ *
+ * ttasr_set_sequence_bias installs n_seq sequences - sequence i = tokens_host[offsets_host[i] .. offsets_host[i + 1]) with
+ * bias_host[i], offsets_host [n_seq + 1] - replacing the table of THIS context (a context of ttasr_create_shared has its own);
+ * n_seq = 0 clears it.  Refused with a message, the old table kept: a length outside 1 .. 16, more than 4096 distinct last tokens,
+ * more than 8192 sequences longer than one token, a bias that is not finite, an id outside the vocabulary, a repeated sequence,
+ * an open session.  The table lives in a device block of fixed capacity whose counts the kernel reads from the block: replacing
+ * it invalidates no captured graph.  While a table is installed it applies to ttasr_generate, _capped, _sample and
+ * ttasr_generate_beam[_ragged]; ttasr_decode_step, ttasr_align*, ttasr_detect_language and ttasr_apply_rules stay raw, and
+ * ttasr_session_begin[_beam] is refused.  With no table every launch chain is what it is without this feature.
+ *
+ * ttasr_seq_bias_probe: the known-answer hook of the kernel (tests/test_gpu_seq_bias_kernels.py): ONE launch, through the
+ * launcher the engine calls, with the installed table on rows_host f32 [n][vocab] -> out_rows_host [n][vocab].
+ *   TTASR_SEQ_BIAS_WINDOW  the beam search's form: hist_host [n][15] with hist_host[r][15 - k] = the k-th token back,
+ *                          hist_len_host [n] = min(history length, 16), or -1: the row is left alone
+ *   TTASR_SEQ_BIAS_STATE   the greedy loop's form: out_tokens_host [n][max_new] with n_sampled_host [n], behind them prompt_host
+ *                          [n][max_prompt] with prompt_len_host [n] (NULL: no prompt), done_host [n] (NULL: live rows) and
+ *                          `position`, the position of the token being fed: a row with position + 1 < prompt length is forced
+ *                          and, like a finished row, left alone
+ * The call overwrites search state, as ttasr_select_probe does. */
+TTASR_API int ttasr_set_sequence_bias(ttasr_ctx* ctx, int32_t n_seq, const int32_t* tokens_host, const int32_t* offsets_host,
+                                      const float* bias_host);
+#define TTASR_SEQ_BIAS_WINDOW 0
+#define TTASR_SEQ_BIAS_STATE 1
+typedef struct ttasr_seq_bias_io {
+  const float* rows_host;
+  const int32_t* hist_host;
+  const int32_t* hist_len_host;
+  const int32_t* prompt_host;
+  const int32_t* prompt_len_host;
+  const int32_t* out_tokens_host;
+  const int32_t* n_sampled_host;
+  const int32_t* done_host;
+  float* out_rows_host;
+  int32_t n, max_prompt, max_new, position;
+} ttasr_seq_bias_io;
+TTASR_API int ttasr_seq_bias_probe(ttasr_ctx* ctx, int32_t form, const ttasr_seq_bias_io* io, char* sig_buf, int32_t sig_len);
+
 /* ---- continuous batching: greedy single-window decoding with slot refill ----------------------------------------------
  * Clips are submitted at any time; each takes a free row of the context's max_batch-row decode batch, decodes until EOT or its
  * own token budget, and its row is handed to the next queued clip.  The batch always runs at max_batch rows (the full-width

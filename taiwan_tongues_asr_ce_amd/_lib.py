@@ -15,7 +15,7 @@ SYMBOLS = [
     "ttasr_create", "ttasr_create_shared", "ttasr_destroy", "ttasr_last_error", "ttasr_version", "ttasr_load_tensor", "ttasr_load_tensor_device",
     "ttasr_finalize_weights", "ttasr_log_mel", "ttasr_log_mel_windows", "ttasr_log_mel_windows_cut", "ttasr_set_mel", "ttasr_encode", "ttasr_set_encoder_output",
     "ttasr_get_cross_kv", "ttasr_get_cross_kv_fp8", "ttasr_cross_attn_probe", "ttasr_align_attn_probe",
-    "ttasr_self_kv_fill", "ttasr_self_kv_set", "ttasr_self_kv_get", "ttasr_self_attn_probe", "ttasr_set_audio_ctx", "ttasr_generate", "ttasr_generate_capped", "ttasr_generate_beam", "ttasr_generate_beam_ragged", "ttasr_generate_sample", "ttasr_decode_reset", "ttasr_decode_step", "ttasr_apply_rules", "ttasr_select_probe", "ttasr_align", "ttasr_dtw",
+    "ttasr_self_kv_fill", "ttasr_self_kv_set", "ttasr_self_kv_get", "ttasr_self_attn_probe", "ttasr_set_audio_ctx", "ttasr_generate", "ttasr_generate_capped", "ttasr_generate_beam", "ttasr_generate_beam_ragged", "ttasr_generate_sample", "ttasr_decode_reset", "ttasr_decode_step", "ttasr_apply_rules", "ttasr_select_probe", "ttasr_set_sequence_bias", "ttasr_seq_bias_probe", "ttasr_align", "ttasr_dtw",
     "ttasr_set_option", "ttasr_phase_ms", "ttasr_beam_profile", "ttasr_encoder_kernel_ms", "ttasr_bench_kernel", "ttasr_bench_kernel_signature", "ttasr_sync",
     "ttasr_session_begin", "ttasr_session_begin_beam", "ttasr_session_submit", "ttasr_session_submit_windows", "ttasr_session_poll", "ttasr_session_stats", "ttasr_session_rows", "ttasr_session_end",
     "ttasr_align_batch", "ttasr_session_hold", "ttasr_session_align", "ttasr_session_release", "ttasr_detect_language",
@@ -67,6 +67,16 @@ class SelectIO(C.Structure):
         "out_sum_logprob", "out_no_speech", "out_tokens", "out_f32", "out_i32")] + [(n, C.c_int32) for n in (
         "n", "hist_stride", "max_prompt", "n_done", "n_entries", "k", "want_no_speech", "token")] + [
         ("temperature", C.c_float), ("seed", C.c_uint32)]
+
+
+SEQ_BIAS_FORMS = {"window": 0, "state": 1}   # TTASR_SEQ_BIAS_* of include/ttasr.h
+
+
+class SeqBiasIO(C.Structure):
+    """ttasr_seq_bias_io: 8 input pointers, the output rows, 4 int32 scalars."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "rows_host", "hist_host", "hist_len_host", "prompt_host", "prompt_len_host", "out_tokens_host", "n_sampled_host", "done_host",
+        "out_rows_host")] + [(n, C.c_int32) for n in ("n", "max_prompt", "max_new", "position")]
 
 
 def build(verbose: bool = False) -> str:
@@ -128,6 +138,8 @@ def load() -> C.CDLL:
     lib.ttasr_decode_step.argtypes = [vp, i32p, i32, vp]
     lib.ttasr_apply_rules.argtypes = [vp, vp, i32p, i32, i32, C.POINTER(GenOpts), vp, i32p]
     lib.ttasr_select_probe.argtypes = [vp, i32, C.POINTER(SelectIO), C.c_char_p, i32]
+    lib.ttasr_set_sequence_bias.argtypes = [vp, i32, i32p, i32p, f32p]
+    lib.ttasr_seq_bias_probe.argtypes = [vp, i32, C.POINTER(SeqBiasIO), C.c_char_p, i32]
     lib.ttasr_align.argtypes = [vp, i32, i32p, i32, i32p, i32, f32p, f32p]
     lib.ttasr_detect_language.argtypes = [vp, i32, i32, i32, i32, i32p, f32p, f32p]
     lib.ttasr_align_batch.argtypes = [vp, i32, i32p, i32p, i32p, i32, i32p, i32p, i32p, i32, i32, i32p, f32p, f32p, f32p]

@@ -62,6 +62,9 @@ class MI355XWhisperASR(ASRInterface):
         # batched=True: transcribe_path decodes a file through the batched pipeline (WhisperModel.transcribe_batched): its VAD
         # chunks as independent groups of one session instead of 30-s windows in order
         self.batched = bool(kwargs.get("batched", False))
+        # prompt_words (the reference service's promptWords: names and proper nouns, comma-separated) with prompt_word_boost, or a
+        # ready sequence_bias table: the keyword biasing of transcribe_path (WhisperModel.transcribe documents the three)
+        self.bias_options = {k: kwargs[k] for k in ("prompt_words", "prompt_word_boost", "sequence_bias") if kwargs.get(k) is not None}
         self.text_filter = kwargs.get("text_filter")  # utils.filter_text of the reference, injected by the caller
         # faster_whisper_asr.py:186-198 retries an empty VAD-filtered result without VAD - but it re-opens a temp file it deleted
         # at :179, always lands in its `except: pass` and returns None.  The EFFECTIVE reference behaviour (None for a chunk the
@@ -143,6 +146,7 @@ class MI355XWhisperASR(ASRInterface):
         clip_timestamps, hallucination_silence_threshold, prompt_reset_on_temperature and suppress_tokens among them (with
         batched=True the pipeline's own clip_timestamps meaning holds)."""
         opts = dict(self.default_transcribe_kwargs, language="zh")
+        opts.update(getattr(self, "bias_options", {}))   # batched=True refuses them: the batched pipeline is a session
         opts.update(kw)
         pick = getattr(self, "audio_channel", None)
         chan = {} if pick is None or "audio_channel" in opts else {"audio_channel": pick}

@@ -162,8 +162,13 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
                          device_resample: bool = False, batched: bool = False, word_timestamps: bool = False,
                          audio_channel=None, clip_timestamps: str = "0",
                          hallucination_silence_threshold: Optional[float] = None, diarize: bool = False, seg_model=None,
-                         spk_model=None, num_speakers: Optional[int] = None) -> Optional[Dict]:
-    """diarize (`--diarize --seg-model PATH --spk-model PATH [--num-speakers N]`): every file is also diarized on the device
+                         spk_model=None, num_speakers: Optional[int] = None, prompt_words=None,
+                         prompt_word_boost: Optional[float] = None) -> Optional[Dict]:
+    """prompt_words (`--prompt-words a,b,c [--prompt-word-boost X]`): names and proper nouns of the recordings (the reference
+    service's promptWords); tokens that continue one of them get a bonus on their logits (WhisperModel.transcribe: prompt_words,
+    prompt_word_boost).  With the one-by-one and the lock-step form, on every engine context of a pipelined run; refused with
+    continuous and with batched (ValueError before a model is built), whose sessions do not apply the table.
+    diarize (`--diarize --seg-model PATH --spk-model PATH [--num-speakers N]`): every file is also diarized on the device
     (WhisperModel.load_diarization, WhisperModel.diarize) and `<name>_dia.srt`, the speaker-labelled subtitle, is written beside
     the unchanged `<name>_asr.txt`; with every form of the run, after the file's segments are there.  A model handed in that
     already holds the networks needs no paths.
@@ -211,6 +216,13 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
         refuse_in_session("process_audio_folder(continuous=True) / --continuous", clip_timestamps, hallucination_silence_threshold)
     if options and batched:
         raise ValueError("clip_timestamps / hallucination_silence_threshold go with the one-by-one or the lock-step form, not with batched")
+    if prompt_words:
+        from .seq_bias import refuse_in_session as refuse_bias
+        if continuous or batched:
+            refuse_bias("process_audio_folder(continuous=True / batched=True) / --continuous / --batched", prompt_words=prompt_words)
+        options["prompt_words"] = prompt_words
+        if prompt_word_boost is not None:
+            options["prompt_word_boost"] = float(prompt_word_boost)
     if continuous:
         if int(pipeline_depth or getattr(model, "pipeline_depth", 1)) > 1:
             log("continuous mode runs one session on one engine context: pipeline depth 1")
@@ -378,6 +390,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--hallucination-silence-threshold", type=float, default=None, metavar="S",
                     help="skip silence longer than S seconds around text whose words look invented; implies --word-timestamps; not "
                          "together with --continuous or --batched")
+    ap.add_argument("--prompt-words", default=None, metavar="a,b,c",
+                    help="keywords of the recordings' content - names, proper nouns - separated by commas: tokens that continue one "
+                         "of them get a bonus on their logits; not together with --continuous or --batched")
+    ap.add_argument("--prompt-word-boost", type=float, default=None, metavar="X",
+                    help="with --prompt-words: the bonus (default 2.0, a starting value that has not been measured on real speech)")
     ap.add_argument("--device-resample", action="store_true",
                     help="opt-in: convert, downmix and resample each group's files in one device call instead of file by file on "
                          "the host (RIFF/WAVE of any PCM / float format; FLAC files, decoded on the device frame by frame; other "
@@ -423,6 +440,12 @@ def main(argv=None) -> int:
             print("--clip-timestamps / --hallucination-silence-threshold go with the one-by-one or the lock-step form "
                   "(--group-files), not with --continuous or --batched")
             return 1
+    if args.prompt_words and (args.continuous or args.batched):
+        print("--prompt-words goes with the one-by-one or the lock-step form (--group-files), not with --continuous or --batched")
+        return 1
+    if args.prompt_word_boost is not None and not args.prompt_words:
+        print("--prompt-word-boost goes with --prompt-words")
+        return 1
     if args.diarize and not (args.seg_model and args.spk_model):
         print("--diarize needs --seg-model PATH and --spk-model PATH")
         return 1
@@ -444,7 +467,8 @@ def main(argv=None) -> int:
                          vad_model=args.vad_model, device_resample=args.device_resample, batched=args.batched,
                          word_timestamps=args.word_timestamps, audio_channel=args.audio_channel,
                          clip_timestamps=args.clip_timestamps, hallucination_silence_threshold=args.hallucination_silence_threshold,
-                         diarize=args.diarize, seg_model=args.seg_model, spk_model=args.spk_model, num_speakers=args.num_speakers)
+                         diarize=args.diarize, seg_model=args.seg_model, spk_model=args.spk_model, num_speakers=args.num_speakers,
+                         prompt_words=args.prompt_words, prompt_word_boost=args.prompt_word_boost)
     return 0
 
 

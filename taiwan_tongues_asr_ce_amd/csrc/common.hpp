@@ -524,6 +524,14 @@ void launch_select(const float* logits, DecState st, RuleParams rp, int B, float
 void launch_advance(int32_t* step, hipStream_t s);
 // the continuous-batching session's select (engine_refill.hip): st.step = per-row positions [B]; each live row advances its own
 void launch_select_rows(const float* logits, DecState st, RuleParams rp, int B, hipStream_t s);
+// sequence-bias logits processor (kernels_bias.hip), run in front of a selection launch: the row histories it matches against, in
+// the state form (the search state of the greedy / sampled loops: out_tokens .. step, the fields of DecState) or the window form
+// (win [rows][15], win_len [rows]: what the beam search uploads); tab = the context's table block (seq_bias.hpp)
+struct SeqBiasHist {
+  const int32_t *out_tokens, *n_sampled, *prompt, *prompt_len, *done, *step; const RuleDyn* dyn;
+  const int32_t *win, *win_len;
+};
+void launch_seq_bias(float* logits, int ldv, const int32_t* tab, const SeqBiasHist& h, bool state_form, int rows, hipStream_t s);
 // row admission of the session: for each of the n entries of `tab` ([n][4 + max_prompt]: row, prompt length, token budget, start
 // position, prompt tokens) every per-row field of the search state is reset, the prompt row and budget are stored, the row's
 // position is set to `start` (0, or the positions an admission pass prefilled) and its first token to prompt[start]; n_done is

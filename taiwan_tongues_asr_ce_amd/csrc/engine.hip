@@ -150,6 +150,7 @@ void ttasr_destroy(ttasr_ctx* c) {
   for (auto& e : c->enc_ev) hipEventDestroy(e);
   for (void* p : c->allocs) hipFree(p);
   c->align_dev.reset();
+  c->seq_bias_dev.reset();
   vad_free(c);
   seg_free(c);
   spk_free(c);

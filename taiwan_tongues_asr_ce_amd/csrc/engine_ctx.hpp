@@ -24,6 +24,7 @@
 #include "beam_pages.hpp"
 #include "prefill_tables.hpp"
 #include "owned.hpp"
+#include "seq_bias.hpp"
 
 namespace ttasr_detail {
 
@@ -74,8 +75,10 @@ struct StepShape {
   int identity_pages = 1;    // page_table is the identity map (greedy): the self-attention kernel computes page ids
   bool rows_pos = false;     // per-row positions (continuous-batching session: row_pos instead of st.step)
   bool lang_rows = false;    // the language head runs behind the select of every step (greedy session armed by ttasr_session_detect_language)
+  bool seq_bias = false;     // a sequence-bias table is installed: the bias kernel runs in front of the select of every step
   bool operator==(const StepShape& o) const {
-    return kv_div == o.kv_div && identity_pages == o.identity_pages && rows_pos == o.rows_pos && lang_rows == o.lang_rows;
+    return kv_div == o.kv_div && identity_pages == o.identity_pages && rows_pos == o.rows_pos && lang_rows == o.lang_rows &&
+           seq_bias == o.seq_bias;
   }
 };
 struct EncLayerW { float *ln1g, *ln1b, *bqkv, *bo, *ln2g, *ln2b, *b1, *b2; void *wqkv, *wo, *w1, *w2; };
@@ -205,6 +208,11 @@ struct ttasr_ctx {
   // batched alignment (engine_align.hip): ONE device block for the pass's tables, softmax maps, cost matrices and spilled DTW
   // traces; allocated by the first call, grown to the largest request (ensure), reset by ttasr_destroy
   DevBlock<> align_dev;
+  // sequence bias (ttasr_set_sequence_bias, seq_bias.hpp): ONE device block of fixed capacity - the table and the beam search's row
+  // windows - allocated by the first install, reset by ttasr_destroy; seq_bias_n = sequences installed (0: no table, nothing of
+  // the feature is launched)
+  DevBlock<int32_t> seq_bias_dev;
+  int seq_bias_n = 0;
   // voice-activity network (engine_vad.hip): created by the first ttasr_vad_load_tensor, freed by ttasr_destroy; per context,
   // outside the weight-share bookkeeping
   ttasr_detail::VadState* vad = nullptr;
@@ -505,8 +513,9 @@ int beam_pick(const std::map<std::vector<int>, double>& finished, const std::vec
 struct BeamExchange {
   int32_t *tbl, *tok, *pos, *done, *state, *pairs; float* lp; int32_t* id; float* ns;
   int32_t* ent; float* temp; uint32_t* seed; float* sel;
+  int32_t* win;   // sequence bias: the rows' last kSeqBiasW history tokens [R][kSeqBiasW], then their history lengths [R]
 };
-inline size_t beam_exchange_words(int R, int pps, int K) { return (size_t)R * (pps + 19 + 2 * K); }
+inline size_t beam_exchange_words(int R, int pps, int K) { return (size_t)R * (pps + 19 + 2 * K + kSeqBiasW + 1); }
 int beam_exchange(ttasr_ctx* c, int R, int K, BeamExchange& x);   // allocates the block on first use
 inline BeamRowState beam_row_state(const ttasr_ctx* c, int R) {
   return BeamRowState{c->row_state, c->row_state + R, c->row_state + 2 * R, c->row_state + 3 * R, c->mask_dev};
@@ -516,6 +525,13 @@ inline BeamRowState beam_row_state(const ttasr_ctx* c, int R) {
 int enqueue_page_copies(ttasr_ctx* c, const std::vector<int32_t>& pairs, const BeamExchange& x);
 int enqueue_row_histories(ttasr_ctx* c, const std::vector<std::vector<int>>& seqs, int R, int timestamp_begin, const BeamExchange& x);
 int enqueue_candidates(ttasr_ctx* c, int R, int K, bool no_speech, const BeamExchange& x);
+// sequence bias: the window of every row from the newest tokens of its history (hist[r]: all of them, or at least the last
+// kSeqBiasMaxLen; searching[r] == 0: the row is left alone), uploaded for the bias launch of enqueue_candidates.  Nothing happens
+// without a table.
+int enqueue_bias_windows(ttasr_ctx* c, const std::vector<std::vector<int>>& hist, const std::vector<char>& searching, int R, const BeamExchange& x);
+// the table block's regions on the device
+inline const int32_t* seq_bias_win(const ttasr_ctx* c) { return c->seq_bias_dev.get() + kSeqBiasWinAt; }
+int seq_bias_refusal(ttasr_ctx* c);   // TTASR_E_INVALID with a message while a table is installed (sessions), else 0
 int beam_search_impl(ttasr_ctx* c, int32_t A, int32_t beam, const int32_t* prompt, int32_t max_prompt, const int32_t* plens,
                      const int32_t* sots, const ttasr_gen_opts* o, float patience, int32_t* out_tokens, int32_t* out_len,
                      float* out_lp, float* out_ns);

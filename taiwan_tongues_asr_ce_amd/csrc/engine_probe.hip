@@ -1,7 +1,8 @@
 // libttasr: the known-answer hook of the token-selection kernels, ttasr_select_probe (one of the engine translation units, see
 // engine_ctx.hpp).  It stages the caller's rows, histories and state in the buffers the searches use, calls ONE launcher of
 // kernels_decode.hip with the arguments the engine passes it, and copies the results back.  No decision of its own: what is
-// chosen, summed or finished is what the kernel did.
+// chosen, summed or finished is what the kernel did.  Behind it: the sequence-bias table's install (ttasr_set_sequence_bias) and the
+// hook of its kernel (ttasr_seq_bias_probe), built the same way.
 #include "engine_ctx.hpp"
 
 namespace ttasr_detail {
@@ -168,9 +169,116 @@ static int select_probe(ttasr_ctx* c, int form, const ttasr_select_io& io, char*
   return TTASR_OK;
 }
 
+// ---- sequence bias: the table's install and the known-answer hook of its kernel (kernels_bias.hip) ----
+static int set_sequence_bias(ttasr_ctx* c, int n_seq, const int32_t* tokens, const int32_t* offsets, const float* bias) {
+  if (n_seq < 0) return fail(c, TTASR_E_INVALID, "sequence bias: n_seq %d", n_seq);
+  if (n_seq > 0 && (!tokens || !offsets || !bias)) return fail(c, TTASR_E_INVALID, "sequence bias: NULL argument");
+  SeqBiasHostTable t;
+  if (n_seq > 0) {
+    const std::string why = seq_bias_build(n_seq, tokens, offsets, bias, c->V, t);
+    if (!why.empty()) return fail(c, TTASR_E_INVALID, "sequence bias: %s", why.c_str());
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));   // nothing enqueued reads the old table any more
+  if (n_seq == 0) { c->seq_bias_n = 0; return TTASR_OK; }
+  TRY(c->seq_bias_dev.ensure(c, seq_bias_block_words(c->maxB) * 4, "sequence-bias block"));
+  int32_t* const d = c->seq_bias_dev.get();
+  const int32_t head[4] = {(int32_t)t.groups.size(), (int32_t)t.entries.size(), 0, 0};
+  c->seq_bias_n = 0;   // a failed copy leaves no half-written table in service
+  HIPCHK(c, hipMemcpyAsync(d, head, sizeof head, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d + kSeqBiasGroupsAt, t.groups.data(), t.groups.size() * sizeof(SeqBiasGroup), hipMemcpyHostToDevice, c->stream));
+  if (!t.entries.empty()) {
+    HIPCHK(c, hipMemcpyAsync(d + kSeqBiasEntriesAt, t.entries.data(), t.entries.size() * sizeof(SeqBiasEntry), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + kSeqBiasPrefixAt, t.prefix.data(), t.prefix.size() * 4, hipMemcpyHostToDevice, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));   // the sources are stack temporaries
+  c->seq_bias_n = n_seq;
+  return TTASR_OK;
+}
+
+static int seq_bias_probe(ttasr_ctx* c, int form, const ttasr_seq_bias_io& io, char* sig_buf, int sig_len) {
+  const int n = io.n, V = c->V;
+  if (form != TTASR_SEQ_BIAS_WINDOW && form != TTASR_SEQ_BIAS_STATE) return fail(c, TTASR_E_INVALID, "sequence-bias probe: form %d", form);
+  if (c->seq_bias_n <= 0) return fail(c, TTASR_E_INVALID, "sequence-bias probe: no table installed");
+  if (!io.rows_host || !io.out_rows_host || n < 1 || n > c->maxB)
+    return fail(c, TTASR_E_INVALID, "sequence-bias probe: rows NULL or n %d outside [1, max_batch=%d]", n, c->maxB);
+  const bool state = form == TTASR_SEQ_BIAS_STATE;
+  if (state) {
+    if (!io.out_tokens_host || !io.n_sampled_host) return fail(c, TTASR_E_INVALID, "sequence-bias probe: out_tokens / n_sampled is NULL");
+    if (io.max_new < 1 || io.max_new > c->max_new_alloc) return fail(c, TTASR_E_INVALID, "sequence-bias probe: max_new %d outside [1, %d]", io.max_new, c->max_new_alloc);
+    if (io.position < 0 || io.position >= c->cfg.n_text_ctx) return fail(c, TTASR_E_INVALID, "sequence-bias probe: position %d", io.position);
+    if (io.prompt_host && (!io.prompt_len_host || io.max_prompt < 1 || io.max_prompt > c->max_prompt_alloc))
+      return fail(c, TTASR_E_INVALID, "sequence-bias probe: max_prompt %d", io.max_prompt);
+    for (int r = 0; r < n; ++r) {
+      if (io.n_sampled_host[r] < 0 || io.n_sampled_host[r] > io.max_new)
+        return fail(c, TTASR_E_INVALID, "sequence-bias probe: row %d: n_sampled %d outside [0, %d]", r, io.n_sampled_host[r], io.max_new);
+      if (io.prompt_host && (io.prompt_len_host[r] < 1 || io.prompt_len_host[r] > io.max_prompt))
+        return fail(c, TTASR_E_INVALID, "sequence-bias probe: row %d: prompt length %d outside [1, %d]", r, io.prompt_len_host[r], io.max_prompt);
+    }
+  } else {
+    if (!io.hist_host || !io.hist_len_host) return fail(c, TTASR_E_INVALID, "sequence-bias probe: hist / hist_len is NULL");
+    for (int r = 0; r < n; ++r)
+      if (io.hist_len_host[r] < -1 || io.hist_len_host[r] > kSeqBiasMaxLen)
+        return fail(c, TTASR_E_INVALID, "sequence-bias probe: row %d: history length %d outside [-1, %d]", r, io.hist_len_host[r], kSeqBiasMaxLen);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  auto up = [&](void* dst, const void* src, size_t bytes) -> int { HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s)); return 0; };
+  const size_t n4 = (size_t)n * 4;
+  HIPCHK(c, hipMemcpy2DAsync(c->logits, (size_t)c->ldv * 4, io.rows_host, (size_t)V * 4, (size_t)V * 4, n, hipMemcpyHostToDevice, s));
+  SeqBiasHist h{};
+  const int32_t pos = io.position;
+  if (state) {
+    // the strides the kernel reads; the next search's commit_rules uploads its own
+    c->rule_dyn_host.max_prompt = io.prompt_host ? io.max_prompt : 1;
+    c->rule_dyn_host.max_new = io.max_new;
+    TRY(up(c->rule_dyn_dev, &c->rule_dyn_host, sizeof(RuleDyn)));
+    TRY(up(c->st.out_tokens, io.out_tokens_host, n4 * io.max_new)); TRY(up(c->st.n_sampled, io.n_sampled_host, n4));
+    if (io.done_host) TRY(up(c->st.done, io.done_host, n4)); else HIPCHK(c, hipMemsetAsync(c->st.done, 0, n4, s));
+    TRY(up(c->st.step, &pos, 4));
+    h = SeqBiasHist{c->st.out_tokens, c->st.n_sampled, nullptr, nullptr, c->st.done, c->st.step, c->rule_dyn_dev, nullptr, nullptr};
+    if (io.prompt_host) {
+      TRY(up(c->prompt_dev, io.prompt_host, n4 * io.max_prompt)); TRY(up(c->plen_dev, io.prompt_len_host, n4));
+      h.prompt = c->prompt_dev; h.prompt_len = c->plen_dev;
+    }
+  } else {
+    int32_t* const win = (int32_t*)seq_bias_win(c);
+    TRY(up(win, io.hist_host, n4 * kSeqBiasW)); TRY(up(win + (size_t)n * kSeqBiasW, io.hist_len_host, n4));
+    h.win = win; h.win_len = win + (size_t)n * kSeqBiasW;
+  }
+  g_kernel_sig[0] = 0;
+  g_kernel_sig_on = true;
+  launch_seq_bias(c->logits, c->ldv, c->seq_bias_dev.get(), h, state, n, s);
+  g_kernel_sig_on = false;
+  HIPCHK(c, hipMemcpy2DAsync(io.out_rows_host, (size_t)V * 4, c->logits, (size_t)c->ldv * 4, (size_t)V * 4, n, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));   // the staged scalars are stack temporaries
+  HIPCHK(c, hipGetLastError());
+  if (state) HIPCHK(c, hipMemsetAsync(c->st.done, 0, n4, s));   // finished flags belong to a search: later step-level calls see live rows
+  c->B_dec = 0;   // the search state no longer belongs to a step-level decode
+  if (sig_buf && sig_len > 0) snprintf(sig_buf, (size_t)sig_len, "%s", g_kernel_sig);
+  return TTASR_OK;
+}
+
 }  // namespace ttasr_detail
 
 extern "C" {
+
+int ttasr_set_sequence_bias(ttasr_ctx* c, int32_t n_seq, const int32_t* tokens_host, const int32_t* offsets_host, const float* bias_host) {
+  return guarded(c, [&]() -> int {
+  if (!c) return TTASR_E_INVALID;
+  TRY(session_refusal(c));
+  return set_sequence_bias(c, n_seq, tokens_host, offsets_host, bias_host);
+  });
+}
+
+int ttasr_seq_bias_probe(ttasr_ctx* c, int32_t form, const ttasr_seq_bias_io* io, char* sig_buf, int32_t sig_len) {
+  return guarded(c, [&]() -> int {
+  if (!c) return TTASR_E_INVALID;
+  TRY(session_refusal(c));
+  if (!io) return fail(c, TTASR_E_INVALID, "sequence-bias probe: io is NULL");
+  return seq_bias_probe(c, form, *io, sig_buf, sig_len);
+  });
+}
 
 int ttasr_select_probe(ttasr_ctx* c, int32_t form, const ttasr_select_io* io, char* sig_buf, int32_t sig_len) {
   return guarded(c, [&]() -> int {

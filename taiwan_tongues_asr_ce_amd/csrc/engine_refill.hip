@@ -474,6 +474,7 @@ static int session_begin(ttasr_ctx* c, const ttasr_gen_opts* o, int max_prompt, 
   if (!c) return TTASR_E_INVALID;
   if (!c->finalized) return fail(c, TTASR_E_INVALID, "weights not finalized (call ttasr_finalize_weights first)");
   TRY(session_refusal(c));
+  TRY(seq_bias_refusal(c));
   if (!o) return fail(c, TTASR_E_INVALID, "opts is NULL");
   if (!(temperature == 0.f)) return fail(c, TTASR_E_INVALID, "a session decodes greedily (temperature %g: only 0)", temperature);
   // value 2 of the option is the session-capable mode: admitted clips are quantised from the staging buffer into their live slots

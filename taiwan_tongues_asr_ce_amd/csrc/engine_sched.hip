@@ -347,6 +347,11 @@ void run_decode_rows(ttasr_ctx* c, int row0, int n, int mode, int total_rows) {
     st.cur_tok += row0; st.n_sampled += row0; st.last_tok += row0; st.pen_tok += row0; st.last_ts += row0; st.done += row0;
     st.sum_logprob += row0; st.no_speech += row0; st.out_tokens += (size_t)row0 * c->rp.max_new; st.row_cap += row0;
     if (st.prompt) { st.prompt += (size_t)row0 * c->rp.max_prompt; st.prompt_len += row0; }
+    // a table is installed (static searches only): the bias lands on the raw logits of the rows that choose at this step, in
+    // front of the rules (mode 2 computes no logits: every row is forced)
+    if (sh.seq_bias && !rows_pos && mode == 0)
+      launch_seq_bias(logits, c->ldv, c->seq_bias_dev.get(),
+                      SeqBiasHist{st.out_tokens, st.n_sampled, st.prompt, st.prompt_len, st.done, c->st.step, st.dyn, nullptr, nullptr}, true, n, s);
     if (rows_pos) { st.step = c->row_pos + row0; launch_select_rows(logits, st, c->rp, n, s); }
     else launch_select(logits, st, c->rp, n, nullptr, s, c->st.step + 1, total_rows);
     if (rows_pos && sh.lang_rows && mode == 0) {

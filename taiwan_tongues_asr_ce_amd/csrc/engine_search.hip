@@ -171,7 +171,9 @@ int generate_rows(ttasr_ctx* c, int R, int rows_per_clip, const int32_t* prompt,
       max_cap = std::max(max_cap, (int)row_cap[r]);
     }
   }
-  SearchScope scope(c, StepShape{rows_per_clip, 1, false}, c->prompt_dev, c->plen_dev, R);
+  StepShape shape{rows_per_clip, 1, false};
+  shape.seq_bias = c->seq_bias_n > 0;
+  SearchScope scope(c, shape, c->prompt_dev, c->plen_dev, R);
   RuleParams old = c->rp;
   TRY(upload_rules(c, o, max_prompt));
   c->rp.temperature = temperature; c->rp.seed = seed;
@@ -314,6 +316,7 @@ int beam_exchange(ttasr_ctx* c, int R, int K, BeamExchange& x) {
   x.tbl = take((size_t)R * pps); x.tok = take(R); x.pos = take(R); x.done = take(R); x.state = take(4 * (size_t)R); x.pairs = take(2 * (size_t)R);
   x.lp = (float*)take((size_t)R * K); x.id = take((size_t)R * K); x.ns = (float*)take(R);
   x.ent = take(4 * (size_t)R); x.temp = (float*)take(R); x.seed = (uint32_t*)take(R); x.sel = (float*)take(3 * (size_t)R);
+  x.win = take((size_t)R * (kSeqBiasW + 1));
   return 0;
 }
 
@@ -335,8 +338,32 @@ int enqueue_row_histories(ttasr_ctx* c, const std::vector<std::vector<int>>& seq
   return 0;
 }
 
+int enqueue_bias_windows(ttasr_ctx* c, const std::vector<std::vector<int>>& hist, const std::vector<char>& searching, int R, const BeamExchange& x) {
+  if (c->seq_bias_n <= 0) return 0;
+  int32_t* const len = x.win + (size_t)R * kSeqBiasW;
+  for (int r = 0; r < R; ++r) {
+    const int n = (int)hist[r].size(), w = std::min(n, kSeqBiasW);
+    int32_t* const row = x.win + (size_t)r * kSeqBiasW;
+    for (int k = 1; k <= kSeqBiasW; ++k) row[kSeqBiasW - k] = k <= w ? hist[r][n - k] : -1;
+    len[r] = searching[r] ? std::min(n, kSeqBiasMaxLen) : -1;
+  }
+  HIPCHK(c, hipMemcpyAsync((void*)seq_bias_win(c), x.win, (size_t)R * (kSeqBiasW + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+
+int seq_bias_refusal(ttasr_ctx* c) {
+  if (c && c->seq_bias_n > 0)
+    return fail(c, TTASR_E_INVALID, "a sequence-bias table is installed on this context: sessions do not apply it (ttasr_set_sequence_bias with n_seq = 0 first)");
+  return 0;
+}
+
 int enqueue_candidates(ttasr_ctx* c, int R, int K, bool no_speech, const BeamExchange& x) {
   hipStream_t s = c->stream;
+  if (c->seq_bias_n > 0 && !c->sess) {   // windows: enqueue_bias_windows, in front of this call
+    const int32_t* win = seq_bias_win(c);
+    launch_seq_bias(c->logits, c->ldv, c->seq_bias_dev.get(),
+                    SeqBiasHist{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, win, win + (size_t)R * kSeqBiasW}, false, R, s);
+  }
   launch_beam_topk(c->logits, beam_row_state(c, R), c->rp, R, K, c->topk_lp, c->topk_id, no_speech ? c->st.no_speech : nullptr, s);
   HIPCHK(c, hipMemcpyAsync(x.lp, c->topk_lp, (size_t)R * K * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipMemcpyAsync(x.id, c->topk_id, (size_t)R * K * 4, hipMemcpyDeviceToHost, s));
@@ -364,6 +391,8 @@ int beam_search_impl(ttasr_ctx* c, int32_t A, int32_t beam, const int32_t* promp
     TRY(check_prompt(c, a, prompt + (size_t)a * max_prompt, plens[a], max_prompt, o->no_speech >= 0 && out_ns ? &sot : nullptr));
     min_plen = std::min(min_plen, (int)plens[a]); min_sot = std::min(min_sot, (int)sot);
   }
+  // (the logits-only steps of the search hold no bias launch - it runs with the candidates - so the shape, and with it the
+  // step graphs, are those of a context without a table)
   SearchScope scope(c, StepShape{beam, 0, false}, nullptr, nullptr, R);
   RuleParams old_rp = c->rp;
   TRY(upload_rules(c, o, max_prompt));
@@ -441,6 +470,18 @@ int beam_search_impl(ttasr_ctx* c, int32_t A, int32_t beam, const int32_t* promp
       done_dirty = false;
     }
     if (any_sampling || any_ns) TRY(enqueue_row_histories(c, seqs, R, o->timestamp_begin, x));
+    if ((any_sampling || any_ns) && c->seq_bias_n > 0) {   // the history of a searching row is its prompt, then its hypothesis
+      std::vector<std::vector<int>> hist(R);
+      std::vector<char> searching(R, 0);
+      for (int r = 0; r < R; ++r) {
+        const int a = r / beam, total = plens[a] + (int)seqs[r].size();
+        if (done[a] || pos + 1 < plens[a]) continue;
+        searching[r] = 1;
+        for (int k = std::min(total, kSeqBiasMaxLen); k >= 1; --k)
+          hist[r].push_back(total - k < plens[a] ? prompt[(size_t)a * max_prompt + total - k] : seqs[r][total - k - plens[a]]);
+      }
+      TRY(enqueue_bias_windows(c, hist, searching, R, x));
+    }
     // 2. one decoder step over the R rows (logits only; the search itself runs on the host) and, behind it, the candidates
     TRY(step_graph(c, R, 1));
     if (any_sampling || any_ns) TRY(enqueue_candidates(c, R, K, any_ns, x));

@@ -886,6 +886,61 @@ class Engine:
         res["sig"] = buf.value.decode()
         return res
 
+    # -- sequence bias ---------------------------------------------------------------------------
+    def set_sequence_bias(self, mapping=None):
+        """Installs a sequence-bias table on this engine context ({tuple of ids: bias}, or an iterable of (ids, bias), in table
+        order; None or empty clears it): ttasr_set_sequence_bias.  While installed, generate / generate_beam / generate_sample add
+        the table's biases to the raw logits in front of the Whisper rules (HF SequenceBiasLogitsProcessor) and sessions are
+        refused.  Everything the library would refuse raises ValueError here, before the library is called."""
+        from . import seq_bias
+        table = seq_bias.check_table(mapping, self.dims.vocab) if mapping else []
+        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        if not table:
+            self._check(self.lib.ttasr_set_sequence_bias(self.h, 0, None, None, None), "set_sequence_bias")
+            return
+        tokens, offsets, biases = seq_bias.flatten(table)
+        self._check(self.lib.ttasr_set_sequence_bias(self.h, len(table), tokens.ctypes.data_as(i32p), offsets.ctypes.data_as(i32p),
+                                                     biases.ctypes.data_as(f32p)), "set_sequence_bias")
+
+    def seq_bias_probe(self, form: str, rows: np.ndarray, hist: Optional[np.ndarray] = None, hist_len=None,
+                       prompt: Optional[np.ndarray] = None, prompt_len=None, out_tokens: Optional[np.ndarray] = None,
+                       n_sampled=None, done=None, position: int = 0) -> Tuple[np.ndarray, str]:
+        """One launch of the sequence-bias kernel with the installed table on raw logits rows float32 [n][vocab]
+        (ttasr_seq_bias_probe) -> (the processed rows, the instantiation that ran).  "window": hist int32 [n][15] with
+        hist[r][15 - k] = the k-th token back and hist_len [n] = min(history length, 16) or -1 (row left alone).  "state":
+        out_tokens [n][max_new] with n_sampled [n], optionally prompt [n][max_prompt] with prompt_len [n] and done [n], and the
+        position of the token being fed.  The search state is undefined afterwards."""
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        n = rows.shape[0]
+        assert rows.ndim == 2 and rows.shape[1] == self.dims.vocab, rows.shape
+        io = _lib.SeqBiasIO()
+        keep = [rows]
+
+        def arr(a, shape):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.int32)
+            assert a.shape == shape, (a.shape, shape)
+            keep.append(a)
+            return a.ctypes.data
+
+        out = np.empty_like(rows)
+        io.rows_host, io.out_rows_host, io.n, io.position = rows.ctypes.data, out.ctypes.data, n, int(position)
+        if form == "window":
+            io.hist_host, io.hist_len_host = arr(hist, (n, 15)), arr(hist_len, (n,))
+        else:
+            out_tokens = np.ascontiguousarray(out_tokens, dtype=np.int32)
+            io.max_new = out_tokens.shape[1]
+            io.out_tokens_host, io.n_sampled_host = arr(out_tokens, (n, io.max_new)), arr(n_sampled, (n,))
+            if prompt is not None:
+                prompt = np.ascontiguousarray(prompt, dtype=np.int32)
+                io.max_prompt = prompt.shape[1]
+                io.prompt_host, io.prompt_len_host = arr(prompt, (n, io.max_prompt)), arr(prompt_len, (n,))
+            io.done_host = arr(done, (n,))
+        buf = C.create_string_buffer(192)
+        self._check(self.lib.ttasr_seq_bias_probe(self.h, _lib.SEQ_BIAS_FORMS[form], C.byref(io), buf, 192), "seq_bias_probe")
+        return out, buf.value.decode()
+
     # -- measurement ---------------------------------------------------------------------------
     def phase_ms(self) -> Dict[str, float]:
         a = (C.c_float * 4)()

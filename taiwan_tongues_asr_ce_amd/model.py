@@ -10,6 +10,9 @@ is libttasr (HIP).  There is no CPU path: `device="cpu"` raises, as a failed CUD
 """
 from __future__ import annotations
 
+import contextlib
+import functools
+import inspect
 import json
 import os
 import threading
@@ -20,7 +23,7 @@ from typing import Dict, Iterable, Iterator, List, NamedTuple, Optional, Sequenc
 
 import numpy as np
 
-from . import alignment, audio_io, ct2, synth, vad
+from . import alignment, audio_io, ct2, seq_bias, synth, vad
 from .audio_io import CodedAudio, decode_audio, parse_audio_channel, read_audio_coded, read_audio_raw  # noqa: F401  (public here too)
 from .config import (COMPUTE_BF16, COMPUTE_F16, COMPUTE_F32, HOP, N_FRAMES, N_SAMPLES, PRESETS, SAMPLE_RATE, SpecialTokens,
                      WhisperDims)
@@ -239,6 +242,21 @@ def _read_hf_dir(path: str) -> Tuple[WhisperDims, Iterable[Tuple[str, np.ndarray
     return dims, tensors()
 
 
+def _lock_step_bias(fn):
+    """transcribe_many's keywords sequence_bias / prompt_words / prompt_word_boost: the table is resolved once (prompt_words is
+    tokenised here), refused with continuous=True before any device work, installed on the calling thread's engine context for
+    the call and cleared when it ends, on error paths too."""
+    sig = inspect.signature(fn)
+
+    @functools.wraps(fn)
+    def call(self, *args, sequence_bias=None, prompt_words=None, prompt_word_boost=None, **kw):
+        if sig.bind(self, *args, **kw).arguments.get("continuous"):
+            seq_bias.refuse_in_session(f"{fn.__name__}(continuous=True)", sequence_bias, prompt_words)
+        with self._sequence_bias(self._bias_table(sequence_bias, prompt_words, prompt_word_boost)):
+            return fn(self, *args, **kw)
+    return call
+
+
 class WhisperModel:
     def __init__(self, model_size_or_path: str, device: str = "auto", device_index: int = 0,
                  compute_type: str = "default", max_batch: int = 8, pipeline_depth: int = 1, cross_kv_fp8: bool = False,
@@ -347,6 +365,31 @@ class WhisperModel:
             return
         for key, value in getattr(self, "_lane_options", ()):   # a bare model (tests build one without __init__) has none
             setter(key, value)
+
+    # -- keyword biasing (seq_bias.py) ------------------------------------------
+    def _bias_table(self, sequence_bias, prompt_words, prompt_word_boost):
+        """The sequence-bias table of one call from its three options, checked (None: the call has none)."""
+        return seq_bias.resolve(sequence_bias, prompt_words, prompt_word_boost, self.tokenizer.encode, self.dims.vocab)
+
+    @contextlib.contextmanager
+    def _sequence_bias(self, table):
+        """`table` installed on the calling thread's engine context (its lane) from here to the end of the block, whatever ends it."""
+        if table is None:
+            yield
+            return
+        setter = getattr(self.engine, "set_sequence_bias", None)
+        if setter is None:
+            raise ValueError("sequence_bias / prompt_words need an engine with Engine.set_sequence_bias")
+        setter(table)
+        try:
+            yield
+        finally:
+            setter(None)
+
+    def _biased_segments(self, segments, table):
+        """The lazy segments of `transcribe` with the table installed while they are produced."""
+        with self._sequence_bias(table):
+            yield from segments
 
     def _lane(self, i: int):
         """Engine context `i` (created on first use, sharing lane 0's device weights and the model's engine options)."""
@@ -492,8 +535,16 @@ class WhisperModel:
         inputs): the results are identical, file by file, to pipeline_depth = 1; returned in group order.
         clip_timestamps, hallucination_silence_threshold, prompt_reset_on_temperature, suppress_tokens (among **kw): as in
         transcribe_many; a per-file clip list holds for the files of EVERY group, so it needs groups of one length.
+        sequence_bias / prompt_words / prompt_word_boost (among **kw): one table, built once, installed by every worker on its own
+        engine context for each of its groups.
         device_resample=True (one of **kw): each worker ingests its group's paths on its own engine context; audio_channel (one
         of **kw) picks a channel of every path, as in transcribe_many."""
+        if any(kw.get(k) is not None for k in ("sequence_bias", "prompt_words")):
+            # tokenised and checked once; every worker's transcribe_many installs the table on its own engine context
+            if kw.get("continuous"):
+                seq_bias.refuse_in_session("transcribe_groups(continuous=True)", kw.get("sequence_bias"), kw.get("prompt_words"))
+            table = self._bias_table(kw.pop("sequence_bias", None), kw.pop("prompt_words", None), kw.pop("prompt_word_boost", None))
+            kw = dict(kw, sequence_bias=dict(table) if table else None)
         depth = max(1, min(int(pipeline_depth or self.pipeline_depth), len(groups) or 1, 4))
         if depth == 1:
             return [self.transcribe_many(g, **kw) for g in groups]
@@ -676,9 +727,20 @@ class WhisperModel:
                    language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1,
                    device_resample: bool = False, audio_channel=None, clip_timestamps: Union[str, Sequence[float]] = "0",
                    hallucination_silence_threshold: Optional[float] = None, prompt_reset_on_temperature: float = 0.5,
-                   suppress_tokens: Optional[Sequence[int]] = (-1,), **kwargs
+                   suppress_tokens: Optional[Sequence[int]] = (-1,), sequence_bias=None, prompt_words=None,
+                   prompt_word_boost: Optional[float] = None, **kwargs
                    ) -> Tuple[Iterator[Segment], TranscriptionInfo]:
-        """clip_timestamps ("0"; a comma-separated string or a list of seconds: start, end, start, end, ...; an odd count runs the
+        """sequence_bias ({tuple of token ids: bias}; None): HF Transformers' SequenceBiasLogitsProcessor on the device - a sequence
+        of one token always adds its bias to that token's raw logit, a longer one adds it to its last token when the history
+        (prompt, then everything sampled, timestamps included) ends in its first tokens; the Whisper rules run afterwards and
+        avg_logprob is that of the biased distribution.  At most 16 tokens per sequence, 4096 distinct last tokens, 8192 sequences
+        longer than one token, finite biases (Engine.set_sequence_bias).
+        prompt_words (a comma-separated string or a list of names and proper nouns; None): expanded into such a table
+        (seq_bias.expand_prompt_words: every prefix of two or more tokens of each phrase, with and without a leading space, gets
+        prompt_word_boost, the first token alone half of it).  The prompt is not touched: combine with hotwords yourself.
+        prompt_word_boost (None = 2.0): a starting value nobody has measured - no trained checkpoint is available offline.
+        The table is installed while the segments are produced and cleared afterwards; detection and alignment passes stay raw.
+        clip_timestamps ("0"; a comma-separated string or a list of seconds: start, end, start, end, ...; an odd count runs the
         last clip to the end; an end past the recording is clamped): only those spans are decoded (parse_clip_timestamps).  A
         window ends where its clip does (Engine.log_mel_windows(n_frames=...)), the dynamic-range floor stays the whole
         recording's, previous-text conditioning carries across clips as across windows, language=None detects from the windows
@@ -714,6 +776,7 @@ class WhisperModel:
                 warnings.warn(f"transcribe(): option {k}={v!r} is not implemented in this build and is ignored", stacklevel=2)
         suppress = self._user_suppress(suppress_tokens)
         threshold = self._silence_threshold(hallucination_silence_threshold, word_timestamps)
+        bias_table = self._bias_table(sequence_bias, prompt_words, prompt_word_boost)
         pick = parse_audio_channel(audio_channel)
         if isinstance(audio, str):
             audio = self.decode_audio_many([audio], audio_channel=pick)[0] if device_resample else decode_audio(audio, channel=pick)
@@ -782,6 +845,8 @@ class WhisperModel:
                                            multilingual=bool(multilingual) and self.is_multilingual, clips=clips,
                                            suppress_tokens=suppress, prompt_reset_on_temperature=float(prompt_reset_on_temperature),
                                            hallucination_silence_threshold=threshold)
+        if bias_table is not None:
+            segments = self._biased_segments(segments, bias_table)
         if chunks is not None:
             segments = vad.restore_speech_timestamps(segments, chunks)
         return segments, info
@@ -792,6 +857,8 @@ class WhisperModel:
         continuous-batching beam session, fallbacks retried on the held cross-KV.  audio_channel (path input only) picks one
         channel of the file instead of the mean of its channels."""
         from .batched import BatchedInferencePipeline
+        seq_bias.refuse_in_session("transcribe_batched", kw.pop("sequence_bias", None), kw.pop("prompt_words", None))
+        kw.pop("prompt_word_boost", None)
         return BatchedInferencePipeline(self).transcribe(audio, **kw)
 
     # -- pieces of faster-whisper's generate_segments / generate_with_fallback, shared by the single-file loop and by
@@ -1089,6 +1156,7 @@ class WhisperModel:
             attempt = self._decode_with_fallback(prompt, self._window_opts(len(prompt), sot_index, p), seek, p)
             yield from self._finish_window(fs, 0, attempt, win_frames, p)
 
+    @_lock_step_bias
     def transcribe_many(self, audios: Sequence[Union[str, np.ndarray]],
                         language: Union[None, str, Sequence[Optional[str]]] = "zh", task: str = "transcribe",
                         beam_size: int = 5, word_timestamps: bool = False, condition_on_previous_text: bool = True,
@@ -1104,7 +1172,10 @@ class WhisperModel:
                         clip_timestamps: Union[str, Sequence] = "0", hallucination_silence_threshold: Optional[float] = None,
                         prompt_reset_on_temperature: float = 0.5, suppress_tokens: Optional[Sequence[int]] = (-1,)
                         ) -> List[Tuple[List[Segment], TranscriptionInfo]]:
-        """Several FILES in lock step: every round takes the next 30-s window of each unfinished file and runs them as
+        """sequence_bias, prompt_words, prompt_word_boost (keywords; as in `transcribe`): the table is installed on this call's
+        engine context for the call and cleared when it ends; refused with continuous=True (ValueError before any device work).
+
+        Several FILES in lock step: every round takes the next 30-s window of each unfinished file and runs them as
         ONE engine pass (log-mel, encoder, beam search with one previous-text prompt per file), so a folder is
         transcribed at batch throughput while each file keeps exactly the sequential algorithm of `transcribe` — its
         own seek, prompt, thresholds.  A window that fails the temperature-0 thresholds is re-decoded alone through the
@@ -1459,7 +1530,8 @@ class WhisperModel:
                           without_timestamps: bool = True, max_new_tokens: int = 224,
                           row_max_new: Optional[Sequence[int]] = None, beam_size: int = 1, patience: float = 1.0,
                           initial_prompt: Optional[str] = None, word_timestamps: bool = False, detect_in_session: bool = False,
-                          session_prefill: Union[int, bool] = 0, clip_timestamps="0", hallucination_silence_threshold=None):
+                          session_prefill: Union[int, bool] = 0, clip_timestamps="0", hallucination_silence_threshold=None,
+                          sequence_bias=None, prompt_words=None):
         """transcribe_batch's contract (clips <= 30 s each, sampled token ids per clip, input order) for any number of clips,
         through a continuous-batching session: a clip that finishes hands its decode row to the next one instead of waiting for
         the rest of its batch.  row_max_new (optional): one token budget per clip, each in [1, max_new_tokens].
@@ -1476,9 +1548,11 @@ class WhisperModel:
         at least N prefillable positions gets them from one admission pass of the session instead of N forced decode steps
         (Engine.session(prefill=N)); clips that go in with the language placeholder are forced as before.
         clip_timestamps / hallucination_silence_threshold: accepted at their neutral values only; anything else is a ValueError
-        before the session opens (they belong to the window loop: transcribe, lock-step transcribe_many)."""
+        before the session opens (they belong to the window loop: transcribe, lock-step transcribe_many).
+        sequence_bias / prompt_words: refused when given (a session's kernels do not apply the table)."""
         from .engine import Session, session_prefill_value
         refuse_in_session("transcribe_stream", clip_timestamps, hallucination_silence_threshold)
+        seq_bias.refuse_in_session("transcribe_stream", sequence_bias, prompt_words)
         session_prefill = session_prefill_value(session_prefill)
         if len(clips) == 0:
             self.last_language_info = []

@@ -87,6 +87,9 @@ class BatchedWhisperASR(MI355XWhisperASR):
                 raise
             raise ValueError("BatchedWhisperASR decodes single-window utterances: clip_timestamps and hallucination_silence_threshold "
                              "belong to the file-level loop (WhisperModel.transcribe / transcribe_many)") from None
+        if continuous:   # keyword biasing is a lock-step feature: a session's kernels do not apply the table
+            from .seq_bias import refuse_in_session as refuse_bias
+            refuse_bias("BatchedWhisperASR(continuous=True)", kwargs.get("sequence_bias"), kwargs.get("prompt_words"))
         if continuous and audio_ctx is not None:
             raise ValueError("continuous=True encodes the full window: audio_ctx must be None")
         self.session_prefill = session_prefill_value(session_prefill)
