@@ -1094,6 +1094,66 @@ TTASR_API int ttasr_spk_dim(ttasr_ctx* ctx);
 TTASR_API int ttasr_spk_embed(ttasr_ctx* ctx, int32_t n, const float* const* pcm_host, const int64_t* n_samples, int32_t n_masks,
                               const float* const* weights_host, float* const* out_emb_host, float* const* out_stats_host);
 
+/* ---- audio enhancement ("dspMode"): denoise, high-pass, level -------------------------------------- */
+/* One length-preserving call over float32 mono 16 kHz recordings: out has the samples of the input, so times, VAD frames and
+ * word timestamps keep their meaning.  The definition is THIS PROJECT'S OWN (the product publishes none); its effect on CER is
+ * unmeasured.  tests/enhance_cases.py pins it as a float64 reference.
+ *
+ * Input x[0..L), output z[0..L).  N = 512, hop 128, bins k = 0..256, window w[n] = sin(pi (n + 0.5) / N) for analysis and
+ * synthesis (its shifted squares sum to exactly 2).  L < N: out = x, bit for bit; only stage 8 may still apply.
+ *   1. Frames: T = ceil(L / 128) + 3; frame t reads samples s = t 128 - 384 + n, n = 0..511; indices outside [0, L) are reflected
+ *      without repeating the edge (s < 0 -> -s, s >= L -> 2 (L - 1) - s).  Every real sample lies in exactly four frames.
+ *   2. Spectrum: X[t,k] = sum_n w[n] x_t[n] e^{-2 pi i k n / N}, P = |X|^2.
+ *   3. Two box means of P along t, clipped to [0, T - 1] and divided by the number of frames summed: S (radius 2) drives the
+ *      gain, Q (radius 16) the noise tracker.
+ *   4. Noise floor: M[b,k] = min of Q over the 32 frames of block b, NB = ceil(T / 32);
+ *      Nf[t,k] = oversubtract * min(M[b',k], b' in [max(0, b - 6), min(NB - 1, b + 6)]), b = floor(t / 32).
+ *   5. Gain (TTASR_DSP_DENOISE): G = max(1 - Nf / S, 0) where S > 0, else 0; then G = max(G, 10^(-strength_db / 20)).  Without
+ *      the flag G = 1.
+ *   6. High-pass (TTASR_DSP_HIGHPASS): G[t,0] = G[t,1] = 0 (DC and the 31.25 Hz bin).
+ *   7. Synthesis: y_t[n] = w[n] Re IDFT(G X)[n] (Hermitian extension, factor 1 / N); out[s] = 0.5 * the sum over the four frames
+ *      that hold s, ascending t.
+ *   8. Level (TTASR_DSP_LEVEL): p = max |out|, g = 1 if p == 0 else min(peak_target / p, max_gain), z = g out.
+ * Every stage is continuous in x (max, min and clamps only; S = 0 has X = 0).
+ *
+ * ttasr_enhance_frames(n_samples) = T for n_samples >= 512, 0 for shorter recordings (no frame exists), TTASR_E_INVALID for a
+ *   negative length.  No context.
+ * ttasr_enhance: n recordings, recording i = pcm_host[i][0 .. n_samples[i]) -> out_pcm_host[i][0 .. n_samples[i]) (may be the
+ *   input row itself); out_gain, when not NULL, receives the n level gains g (1 without TTASR_DSP_LEVEL).  n is not limited by
+ *   max_batch, no model weights are needed, a recording of 0 samples is legal (its rows may be NULL, its gain is 1).
+ *   Refused with TTASR_E_INVALID and a message before anything is enqueued, the context stays usable: n < 0; a NULL array;
+ *   flags 0 or with unknown bits; a parameter that is not finite; strength_db outside [0, 40]; oversubtract outside (0, 16];
+ *   peak_target outside (0, 1]; max_gain < 1; a length that is negative or above 2^36; a NULL row with samples; an open session; a
+ *   call already in flight on the context.
+ *   CONTRACT: a recording's result is a function of its samples and the parameters alone, bit for bit - not of the other
+ *   recordings, their order, option "enhance_chunk" or the run.  No atomics; an output's operands and their order depend on its
+ *   index alone.
+ *   Device memory: ONE block owned by the context - the tables, the longest recording's samples and result (8 B per sample), its
+ *   block minima [NB][257] and the partial maxima - allocated by the first call, grown on demand, freed by ttasr_destroy.  A block
+ *   that cannot be allocated: TTASR_E_NOMEM, the context stays usable.  Recordings go through the stream one after the other,
+ *   each cut into chunks of option "enhance_chunk" samples: per chunk one upload and the noise pass over the blocks whose samples
+ *   have arrived, then per chunk the gain and synthesis pass and the partial maxima, then the gain, then per chunk the scaling and
+ *   the download.  The call touches no mel, encoder, search, graph, session or network state.
+ * ttasr_enhance_probe: the known-answer hook.  ONE recording through the launchers ttasr_enhance calls, every output optional
+ *   (NULL = not wanted): out_S, out_Nf, out_G float32 [T][257] (S and Nf are computed whatever the flags say; G is what the
+ *   flags make of it) and out_pcm [n_samples] BEFORE the level stage.  n_samples < 512: no frame exists, only out_pcm is
+ *   written.  The refusals of ttasr_enhance. */
+#define TTASR_DSP_DENOISE 1
+#define TTASR_DSP_HIGHPASS 2
+#define TTASR_DSP_LEVEL 4
+typedef struct ttasr_dsp_params {
+  float strength_db;    /* [0, 40]: the gain never falls below 10^(-strength_db / 20); default 12 */
+  float oversubtract;   /* (0, 16]; default 3 */
+  float peak_target;    /* (0, 1]; default 10^(-1 / 20) */
+  float max_gain;       /* >= 1; default 10 */
+  int32_t flags;        /* TTASR_DSP_*, at least one */
+} ttasr_dsp_params;
+TTASR_API int64_t ttasr_enhance_frames(int64_t n_samples);
+TTASR_API int ttasr_enhance(ttasr_ctx* ctx, int32_t n, const float* const* pcm_host, const int64_t* n_samples,
+                            const ttasr_dsp_params* params, float* const* out_pcm_host, float* out_gain);
+TTASR_API int ttasr_enhance_probe(ttasr_ctx* ctx, const float* pcm_host, int64_t n_samples, const ttasr_dsp_params* params,
+                                  float* out_S, float* out_Nf, float* out_G, float* out_pcm);
+
 /* ---- kernel-selection overrides (tests, A/B measurements) ----------------------------------------- */
 /* The release library reads NO environment variable; every deviation from the measured configuration is an explicit call.
  * Keys (value 0 / 1 unless stated; defaults in brackets): "flash" [1] MFMA flash attention in the encoder (0: the
@@ -1135,7 +1195,9 @@ TTASR_API int ttasr_spk_embed(ttasr_ctx* ctx, int32_t n, const float* const* pcm
  * (measurement only: the waits cost the overlap);
  * "seg_lstm_rows" [0] chunks per recurrence workgroup of ttasr_seg_scores: 0 = the measured choice, 1 | 2 | 4 force that form
  * (bit-identical: a gate row's summation order does not depend on it; A/B);
- * Drops the captured decode graphs (except "enc_kernel_timing", "refill_overlap", "session_prefill", "align_packed", "ingest_chunk", "wire_chunk", "ingest_timing" and "seg_lstm_rows").  Unknown key or value out of range: TTASR_E_INVALID. */
+ * "enhance_chunk" [0] (0 ... 2^30) samples per chunk of ttasr_enhance / ttasr_enhance_probe, 0 = 2^22 (results do not depend on
+ * it, bit for bit: tests put chunk boundaries inside frames, blocks and the floor's 13-block window with it);
+ * Drops the captured decode graphs (except "enc_kernel_timing", "refill_overlap", "session_prefill", "align_packed", "ingest_chunk", "wire_chunk", "ingest_timing", "seg_lstm_rows" and "enhance_chunk").  Unknown key or value out of range: TTASR_E_INVALID. */
 TTASR_API int ttasr_set_option(ttasr_ctx* ctx, const char* key, int32_t value);
 
 /* ---- measurement --------------------------------------------------------------------------------- */

@@ -27,6 +27,7 @@ SYMBOLS = [
     "ttasr_flac_probe", "ttasr_flac_frames", "ttasr_flac_decode",
     "ttasr_seg_load_tensor", "ttasr_seg_finalize", "ttasr_seg_classes", "ttasr_seg_chunks", "ttasr_seg_frames", "ttasr_seg_scores",
     "ttasr_spk_load_tensor", "ttasr_spk_finalize", "ttasr_spk_dim", "ttasr_spk_embed",
+    "ttasr_enhance_frames", "ttasr_enhance", "ttasr_enhance_probe",
 ]
 
 PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = range(6)   # TTASR_PCM_* of include/ttasr.h
@@ -70,6 +71,11 @@ class SelectIO(C.Structure):
 
 
 SEQ_BIAS_FORMS = {"window": 0, "state": 1}   # TTASR_SEQ_BIAS_* of include/ttasr.h
+
+
+class DspParamsC(C.Structure):
+    """ttasr_dsp_params: strength_db, oversubtract, peak_target, max_gain, flags (TTASR_DSP_DENOISE 1 | HIGHPASS 2 | LEVEL 4)."""
+    _fields_ = [(n, C.c_float) for n in ("strength_db", "oversubtract", "peak_target", "max_gain")] + [("flags", C.c_int32)]
 
 
 class SeqBiasIO(C.Structure):
@@ -201,10 +207,15 @@ def load() -> C.CDLL:
     lib.ttasr_spk_finalize.argtypes = [vp]
     lib.ttasr_spk_dim.argtypes = [vp]
     lib.ttasr_spk_embed.argtypes = [vp, i32, C.POINTER(vp), i64p, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    lib.ttasr_enhance_frames.argtypes = [i64]
+    lib.ttasr_enhance_frames.restype = i64
+    lib.ttasr_enhance.argtypes = [vp, i32, C.POINTER(vp), i64p, C.POINTER(DspParamsC), C.POINTER(vp), f32p]
+    lib.ttasr_enhance_probe.argtypes = [vp, vp, i64, C.POINTER(DspParamsC), vp, vp, vp, vp]
     for s in SYMBOLS:
         f = getattr(lib, s)
         if s not in ("ttasr_destroy", "ttasr_last_error", "ttasr_version", "ttasr_ingest_len", "ttasr_ingest_filter",
-                     "ttasr_ingest_stream_len", "ttasr_flac_frames", "ttasr_flac_decode", "ttasr_seg_chunks", "ttasr_seg_frames"):
+                     "ttasr_ingest_stream_len", "ttasr_flac_frames", "ttasr_flac_decode", "ttasr_seg_chunks", "ttasr_seg_frames",
+                     "ttasr_enhance_frames"):
             f.restype = C.c_int
     _lib = lib
     return lib

@@ -65,6 +65,11 @@ class MI355XWhisperASR(ASRInterface):
         # prompt_words (the reference service's promptWords: names and proper nouns, comma-separated) with prompt_word_boost, or a
         # ready sequence_bias table: the keyword biasing of transcribe_path (WhisperModel.transcribe documents the three)
         self.bias_options = {k: kwargs[k] for k in ("prompt_words", "prompt_word_boost", "sequence_bias") if kwargs.get(k) is not None}
+        # dsp_mode (the reference service's dspMode; None / 0 = off, 1 = denoise + high-pass + level, or dsp.DspParams / a dict of
+        # its fields): transcribe_path enhances the FILE on the device before anything reads it; the streaming chunks of
+        # `transcribe` are live utterances and are never enhanced
+        from .dsp import resolve as resolve_dsp
+        self.dsp_mode = resolve_dsp(kwargs.get("dsp_mode"))
         self.text_filter = kwargs.get("text_filter")  # utils.filter_text of the reference, injected by the caller
         # faster_whisper_asr.py:186-198 retries an empty VAD-filtered result without VAD - but it re-opens a temp file it deleted
         # at :179, always lands in its `except: pass` and returns None.  The EFFECTIVE reference behaviour (None for a chunk the
@@ -144,9 +149,11 @@ class MI355XWhisperASR(ASRInterface):
         file_asr.py:457-465) -> (segments, info); with device_resample=True on the adapter the file is ingested on the device,
         with batched=True it is decoded by the batched pipeline.  Keywords go to WhisperModel.transcribe as they are -
         clip_timestamps, hallucination_silence_threshold, prompt_reset_on_temperature and suppress_tokens among them (with
-        batched=True the pipeline's own clip_timestamps meaning holds)."""
+        batched=True the pipeline's own clip_timestamps meaning holds).  MI355XWhisperASR(dsp_mode=...) adds dsp_mode to them."""
         opts = dict(self.default_transcribe_kwargs, language="zh")
         opts.update(getattr(self, "bias_options", {}))   # batched=True refuses them: the batched pipeline is a session
+        if getattr(self, "dsp_mode", None) is not None:
+            opts["dsp_mode"] = self.dsp_mode
         opts.update(kw)
         pick = getattr(self, "audio_channel", None)
         chan = {} if pick is None or "audio_channel" in opts else {"audio_channel": pick}

@@ -58,6 +58,25 @@ def _load_audio(path: str, channel: Optional[int] = None):
     return decode_audio(path, channel=channel)
 
 
+class _EnhancedOnce:
+    """The loader of a run that both enhances (dsp_mode) and diarizes: a file's samples are loaded and enhanced ONCE
+    (WhisperModel.decode_audio_many(dsp_mode=...): on the device, from the path itself with device_resample) and kept until
+    `forget`, so the transcription and the diarization of the file read the same enhanced samples and neither enhances again."""
+
+    def __init__(self, model, base: Callable, params, from_path: bool, pick: Optional[int]):
+        self.model, self.base, self.params, self.from_path, self.pick, self.kept = model, base, params, from_path, pick, {}
+
+    def __call__(self, path: str):
+        if path not in self.kept:
+            src = _probe(path) if self.from_path else self.base(path)
+            self.kept[path] = self.model.decode_audio_many([src], audio_channel=self.pick if self.from_path else None,
+                                                           dsp_mode=self.params)[0]
+        return self.kept[path]
+
+    def forget(self) -> None:
+        self.kept.clear()
+
+
 def _probe(path: str) -> str:
     """The path itself, once the file has been opened: a missing or unreadable file is that file's error, not its group's."""
     with open(path, "rb"):
@@ -70,7 +89,8 @@ def transcribe_file(model, audio_file: str, load_audio: Callable = _load_audio, 
     """diarize: not None = the file is also diarized (model.diarize(audio, **diarize)) and `<name>_dia.srt` is written beside
     `<name>_asr.txt`: one cue per segment, its text prefixed with the speaker whose turns overlap it longest
     (diarization.dia_srt: the reference service's SRT conventions).  A failure there is logged and leaves the ASR result as it is.
-    options: further transcribe() keywords of a file transcribed here (clip_timestamps, hallucination_silence_threshold).
+    options: further transcribe() keywords of a file transcribed here (clip_timestamps, hallucination_silence_threshold, dsp_mode;
+    with batched: dsp_mode alone).
     One unit of work → one entry of `detailed_results`.  word_timestamps: the segments carry words (a file transcribed here
     is transcribed with them); they are written to `<name>_words.json` beside `<name>_asr.txt`.  `segments`: already transcribed (group mode, with its `info`), else
     runs it.  language=None (`--language auto`): the language is detected, and the entry names it with its probability.
@@ -82,7 +102,7 @@ def transcribe_file(model, audio_file: str, load_audio: Callable = _load_audio, 
             raise segments
         if segments is None and batched:
             kw = {k: v for k, v in TRANSCRIBE_KWARGS.items() if k != "condition_on_previous_text"}
-            segments, info = model.transcribe_batched(load_audio(audio_file), **dict(kw, language=language))
+            segments, info = model.transcribe_batched(load_audio(audio_file), **dict(kw, language=language, **(options or {})))
         elif segments is None:
             extra = dict(options or {}, **(dict(word_timestamps=True) if word_timestamps else {}))
             segments, info = model.transcribe(load_audio(audio_file), **dict(TRANSCRIBE_KWARGS, language=language, **extra))
@@ -163,8 +183,14 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
                          audio_channel=None, clip_timestamps: str = "0",
                          hallucination_silence_threshold: Optional[float] = None, diarize: bool = False, seg_model=None,
                          spk_model=None, num_speakers: Optional[int] = None, prompt_words=None,
-                         prompt_word_boost: Optional[float] = None) -> Optional[Dict]:
-    """prompt_words (`--prompt-words a,b,c [--prompt-word-boost X]`): names and proper nouns of the recordings (the reference
+                         prompt_word_boost: Optional[float] = None, dsp_mode=None,
+                         dsp_strength: Optional[float] = None) -> Optional[Dict]:
+    """dsp_mode (`--dsp-mode {0,1} [--dsp-strength DB]`; the reference service's dspMode): 1 = every file is denoised, high-passed
+    and levelled on the device before anything reads it (WhisperModel.transcribe: dsp_mode; dsp.DspParams or a dict of its fields
+    is accepted here too), with every form of the run; with `diarize` a file is enhanced once and its transcription and its diarization read the
+    same samples (_EnhancedOnce); dsp_strength replaces
+    DspParams.strength_db.  Off by default; its effect on CER is unmeasured.
+    prompt_words (`--prompt-words a,b,c [--prompt-word-boost X]`): names and proper nouns of the recordings (the reference
     service's promptWords); tokens that continue one of them get a bonus on their logits (WhisperModel.transcribe: prompt_words,
     prompt_word_boost).  With the one-by-one and the lock-step form, on every engine context of a pipelined run; refused with
     continuous and with batched (ValueError before a model is built), whose sessions do not apply the table.
@@ -223,6 +249,14 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
         options["prompt_words"] = prompt_words
         if prompt_word_boost is not None:
             options["prompt_word_boost"] = float(prompt_word_boost)
+    from . import dsp
+    dsp_params = dsp.resolve(dsp_mode)
+    if dsp_strength is not None:
+        if dsp_params is None:
+            raise ValueError("dsp_strength goes with dsp_mode (--dsp-strength with --dsp-mode 1)")
+        dsp_params = dsp.replace(dsp_params, strength_db=float(dsp_strength)).check()
+    dsp_options = {} if dsp_params is None else {"dsp_mode": dsp_params}
+    options.update(dsp_options)
     if continuous:
         if int(pipeline_depth or getattr(model, "pipeline_depth", 1)) > 1:
             log("continuous mode runs one session on one engine context: pipeline depth 1")
@@ -248,15 +282,27 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
         elif not getattr(model, "has_diarization", False):
             raise ValueError("diarize needs seg_model and spk_model (--seg-model, --spk-model)")
         dia = dict(num_speakers=num_speakers)
+    once = None
+    if dia is not None and dsp_params is not None:
+        # two passes read every file: the loader enhances it once for both, and neither pass is asked to enhance
+        once = load_audio = _EnhancedOnce(model, load_audio, dsp_params, bool(device_resample), pick)
+        options = {k: v for k, v in options.items() if k != "dsp_mode"}
+        dsp_options = {}
+
+    def one_file(f, **kw):
+        try:
+            return transcribe_file(model, f, load_audio, log, language=language, diarize=dia, **kw)
+        finally:
+            if once is not None:
+                once.forget()
     mine = files[rank::world]                                   # shard by file
     results = []
     many = getattr(model, "transcribe_many", None)
     group = group_files if group_files > 0 else max(1, getattr(model, "max_batch", 1) // TRANSCRIBE_KWARGS["beam_size"])
     if batched:
-        results = [transcribe_file(model, f, load_audio, log, language=language, batched=True, diarize=dia) for f in mine]
+        results = [one_file(f, batched=True, options=dsp_options) for f in mine]
     elif many is None or group < 2 or getattr(model, "vad_speech_prob_fn", None) is not None:
-        results = [transcribe_file(model, f, load_audio, log, language=language, word_timestamps=word_timestamps, options=options,
-                                   diarize=dia) for f in mine]
+        results = [one_file(f, word_timestamps=word_timestamps, options=options) for f in mine]
     else:
         # MI355X-first: `group` files advance in lock step through one engine pass per window round; every file keeps the
         # sequential algorithm (own seek / prompt / fallback), so the outputs equal the one-by-one run
@@ -272,7 +318,7 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
                 kw["detect_in_session"] = True
             if session_prefill:
                 kw["session_prefill"] = int(session_prefill)
-        if device_resample:
+        if device_resample and once is None:
             kw["device_resample"] = True
             if pick is not None:
                 kw["audio_channel"] = pick
@@ -293,12 +339,14 @@ def process_audio_folder(folder_path: str, model=None, model_path: str = "models
         span = 2 * depth if groups_fn is not None else 1
         for g0 in range(0, len(parts), span):
             chunk = parts[g0:g0 + span]
+            if once is not None:
+                once.forget()   # the chunk before is written: its enhanced samples go
             loaded_of, audios_of = [], []
             for part in chunk:
                 audios, loaded = [], []
                 for f in part:
                     try:
-                        audios.append(_probe(f) if device_resample else load_audio(f))
+                        audios.append(_probe(f) if device_resample and once is None else load_audio(f))
                         loaded.append(None)
                     except Exception as e:
                         loaded.append(e)
@@ -395,6 +443,11 @@ def build_parser() -> argparse.ArgumentParser:
                          "of them get a bonus on their logits; not together with --continuous or --batched")
     ap.add_argument("--prompt-word-boost", type=float, default=None, metavar="X",
                     help="with --prompt-words: the bonus (default 2.0, a starting value that has not been measured on real speech)")
+    ap.add_argument("--dsp-mode", type=int, choices=(0, 1), default=0,
+                    help="audio optimisation (the reference service's dspMode): 1 = denoise, high-pass and level every file on the device "
+                         "before it is transcribed (default 0 = off; the effect on CER has not been measured)")
+    ap.add_argument("--dsp-strength", type=float, default=None, metavar="DB",
+                    help="with --dsp-mode 1: the deepest attenuation of the denoiser in dB, 0 ... 40 (default 12)")
     ap.add_argument("--device-resample", action="store_true",
                     help="opt-in: convert, downmix and resample each group's files in one device call instead of file by file on "
                          "the host (RIFF/WAVE of any PCM / float format; FLAC files, decoded on the device frame by frame; other "
@@ -446,6 +499,9 @@ def main(argv=None) -> int:
     if args.prompt_word_boost is not None and not args.prompt_words:
         print("--prompt-word-boost goes with --prompt-words")
         return 1
+    if args.dsp_strength is not None and not args.dsp_mode:
+        print("--dsp-strength goes with --dsp-mode 1")
+        return 1
     if args.diarize and not (args.seg_model and args.spk_model):
         print("--diarize needs --seg-model PATH and --spk-model PATH")
         return 1
@@ -468,7 +524,8 @@ def main(argv=None) -> int:
                          word_timestamps=args.word_timestamps, audio_channel=args.audio_channel,
                          clip_timestamps=args.clip_timestamps, hallucination_silence_threshold=args.hallucination_silence_threshold,
                          diarize=args.diarize, seg_model=args.seg_model, spk_model=args.spk_model, num_speakers=args.num_speakers,
-                         prompt_words=args.prompt_words, prompt_word_boost=args.prompt_word_boost)
+                         prompt_words=args.prompt_words, prompt_word_boost=args.prompt_word_boost,
+                         dsp_mode=args.dsp_mode, dsp_strength=args.dsp_strength)
     return 0
 
 

@@ -158,15 +158,19 @@ class BatchedInferencePipeline:
                    language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1,
                    vad_filter: bool = True, vad_parameters=None, chunk_length: Optional[float] = None,
                    clip_timestamps=None, batch_size: Optional[int] = None, device_resample: bool = False, audio_channel=None,
-                   session_prefill: Union[int, bool] = 0, retry_held: bool = True, **kwargs
+                   session_prefill: Union[int, bool] = 0, retry_held: bool = True, dsp_mode=None, **kwargs
                    ) -> Tuple[Iterator[Segment], TranscriptionInfo]:
         """The keyword surface of faster-whisper's BatchedInferencePipeline.transcribe; device_resample, audio_channel (path
         input only: one channel of the file instead of the mean, WhisperModel.transcribe), session_prefill and retry_held are
         extensions of this build.  retry_held=False releases a failing group and submits it again (one more
         encoder pass per attempt): the A/B switch, and the form for engines without Session.retry.
+        dsp_mode (dsp.resolve; None = off): the recording is enhanced once (Engine.enhance) before the VAD and before the
+        session opens.
         info.chunks lists the groups with their attempts; info.session is filled when the iterator is exhausted."""
+        from . import dsp
         from .engine import session_prefill_value
         m = self.model
+        dsp_params = dsp.resolve(dsp_mode)
         neutral = {"vad_speech_prob_fn": None, "length_penalty": 1, "repetition_penalty": 1, "no_repeat_ngram_size": 0,
                    "hallucination_silence_threshold": None, "prompt_reset_on_temperature": 0.5, "suppress_tokens": [-1],
                    "prepend_punctuations": alignment.PREPEND_PUNCTUATIONS, "append_punctuations": alignment.APPEND_PUNCTUATIONS,
@@ -208,6 +212,8 @@ class BatchedInferencePipeline:
             raise ValueError(f"best_of={best_of}: a session holds at most 7 rows per group")
         if language is not None:
             m._lang_token(language)   # raises on a code this build cannot name
+        if dsp_params is not None:   # every argument is checked: the first device work of the call, in front of the VAD
+            audio = m.engine.enhance([audio], params=dsp_params)[0]
 
         groups, vad_options = self._groups(audio, bool(vad_filter), vad_parameters,
                                            kwargs.get("vad_speech_prob_fn") or m.vad_speech_prob_fn, clip_timestamps, chunk_length)

@@ -155,6 +155,7 @@ void ttasr_destroy(ttasr_ctx* c) {
   seg_free(c);
   spk_free(c);
   ingest_free(c);
+  enhance_free(c);
   c->pinned_i32.reset();
   c->pinned_beam.reset();
   if (c->stream) hipStreamDestroy(c->stream);

@@ -67,6 +67,7 @@ struct Session;            // continuous-batching session state (engine_refill.h
 struct SegState;           // segmentation network: weights, scratch and staging of one context (engine_seg.hip)
 struct SpkState;           // speaker-embedding network: weights, scratch and staging of one context (engine_spk.hip)
 struct VadState;           // voice-activity network: weights, scratch, staging and streams of one context (engine_vad.hip)
+struct EnhState;           // audio enhancement: the device block of one context (engine_enhance.hip)
 struct IngestState;        // file ingest: tap tables per rate, the chunk slots and the IMA scratch of one context (engine_ingest.hip)
 // What run_decode_rows reads about the rows of a step, and (with the batch, the mode and the e4m3 state) what a captured step
 // graph is keyed on.  Installed and restored by SearchScope only.
@@ -227,6 +228,10 @@ struct ttasr_ctx {
   int seg_lstm_rows = 0;
   // speaker-embedding network (engine_spk.hip): created by the first ttasr_spk_load_tensor, freed by ttasr_destroy
   ttasr_detail::SpkState* spk = nullptr;
+  // audio enhancement (engine_enhance.hip): created by the first ttasr_enhance / ttasr_enhance_probe, freed by ttasr_destroy.  Option
+  // enhance_chunk = samples per chunk (0: 2^22)
+  ttasr_detail::EnhState* enhance = nullptr;
+  int enhance_chunk = 0;
   int wire_chunk = 0;       // option wire_chunk: input frames of a row per internal chunk of ttasr_vad_stream_push_wire (0: what the pools hold)
 
   int B_mel = 0, B_enc = 0, B_dec = 0;
@@ -460,6 +465,9 @@ void seg_free(ttasr_ctx* c);         // ttasr_destroy: deletes the state, which 
 
 // ---- engine_spk.hip: the speaker-embedding network (ttasr_spk_*) ----
 void spk_free(ttasr_ctx* c);         // ttasr_destroy: deletes the state, which owns its side blocks (the weights live in the arenas)
+
+// ---- engine_enhance.hip: audio enhancement (ttasr_enhance*) ----
+void enhance_free(ttasr_ctx* c);     // ttasr_destroy: deletes the state, which owns its device block
 
 // ---- engine_ingest.hip: file ingest (ttasr_ingest_*) ----
 void ingest_free(ttasr_ctx* c);      // ttasr_destroy: deletes the state, which owns its tap tables, chunk slots and events

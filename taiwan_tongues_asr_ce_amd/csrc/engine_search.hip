@@ -70,6 +70,11 @@ int set_option(ttasr_ctx* c, const std::string& key, int v) {
     c->ingest_chunk = v;
     return 0;
   }
+  if (key == "enhance_chunk") {     // host-side chunking of ttasr_enhance: the graphs stay
+    if (v < 0 || v > 1 << 30) return 1;
+    c->enhance_chunk = v;
+    return 0;
+  }
   if (key == "wire_chunk") {        // host-side chunking of ttasr_vad_stream_push_wire: the graphs stay
     if (v < 0 || v > 1 << 30) return 1;
     c->wire_chunk = v;

@@ -941,6 +941,58 @@ class Engine:
         self._check(self.lib.ttasr_seq_bias_probe(self.h, _lib.SEQ_BIAS_FORMS[form], C.byref(io), buf, 192), "seq_bias_probe")
         return out, buf.value.decode()
 
+    # -- audio enhancement ("dspMode") ------------------------------------------------------------
+    def _dsp_params(self, params, fields):
+        from . import dsp
+        p = params if params is not None else dsp.DspParams()
+        own = {k: v for k, v in fields.items() if k != "flags"}   # flags=: the raw TTASR_DSP_* word, as given (tests of the refusals)
+        if own:
+            p = dsp.replace(p, **own)
+        c = _lib.DspParamsC()
+        c.strength_db, c.oversubtract, c.peak_target, c.max_gain = p.strength_db, p.oversubtract, p.peak_target, p.max_gain
+        c.flags = int(fields["flags"]) if "flags" in fields else p.flags
+        return c
+
+    def enhance(self, audios: Sequence[np.ndarray], params=None, return_gain: bool = False, **fields):
+        """Denoise, high-pass and level float32 mono 16 kHz recordings on the device (ttasr_enhance; dsp.DspParams, or its fields
+        as keywords, default all three stages): a list of float32 arrays of the inputs' lengths; return_gain=True: (that list,
+        the level gains float32 [n]).  A recording's result depends on its samples and the parameters alone, bit for bit.  The
+        parameters go to the library as given: what it refuses raises TtasrError."""
+        p = self._dsp_params(params, fields)
+        pcm = []
+        for i, a in enumerate(audios):
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.ndim != 1:
+                raise ValueError(f"recording {i}: PCM must be one-dimensional, got shape {a.shape}")
+            pcm.append(a)
+        n = len(pcm)
+        outs = [np.empty_like(a) for a in pcm]
+        gain = np.ones(n, dtype=np.float32)
+        ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data if len(a) else None for a in pcm])
+        optrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data if len(a) else None for a in outs])
+        ns = np.asarray([len(a) for a in pcm], dtype=np.int64)
+        self._check(self.lib.ttasr_enhance(self.h, n, ptrs, ns.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(p), optrs,
+                                           gain.ctypes.data_as(C.POINTER(C.c_float))), "enhance")
+        return (outs, gain) if return_gain else outs
+
+    def enhance_probe(self, audio: np.ndarray, params=None, **fields) -> Dict[str, Optional[np.ndarray]]:
+        """The enhancement's known-answer hook (ttasr_enhance_probe): one recording through the launchers Engine.enhance runs ->
+        {"S", "Nf", "G": float32 [T][257] (None for a recording shorter than 512 samples), "out": the result BEFORE the level
+        stage}."""
+        p = self._dsp_params(params, fields)
+        a = np.ascontiguousarray(audio, dtype=np.float32)
+        if a.ndim != 1:
+            raise ValueError(f"PCM must be one-dimensional, got shape {a.shape}")
+        T = int(self.lib.ttasr_enhance_frames(len(a)))
+        if T < 0:
+            raise ValueError(f"{len(a)} samples: not a length ttasr_enhance takes")
+        res: Dict[str, Optional[np.ndarray]] = {k: (np.zeros((T, 257), dtype=np.float32) if T else None) for k in ("S", "Nf", "G")}
+        res["out"] = np.zeros(len(a), dtype=np.float32)
+        ptr = lambda v: v.ctypes.data if v is not None and v.size else None   # noqa: E731
+        self._check(self.lib.ttasr_enhance_probe(self.h, ptr(a), len(a), C.byref(p), ptr(res["S"]), ptr(res["Nf"]), ptr(res["G"]),
+                                                 ptr(res["out"])), "enhance_probe")
+        return res
+
     # -- measurement ---------------------------------------------------------------------------
     def phase_ms(self) -> Dict[str, float]:
         a = (C.c_float * 4)()

@@ -23,7 +23,7 @@ from typing import Dict, Iterable, Iterator, List, NamedTuple, Optional, Sequenc
 
 import numpy as np
 
-from . import alignment, audio_io, ct2, seq_bias, synth, vad
+from . import alignment, audio_io, ct2, dsp, seq_bias, synth, vad
 from .audio_io import CodedAudio, decode_audio, parse_audio_channel, read_audio_coded, read_audio_raw  # noqa: F401  (public here too)
 from .config import (COMPUTE_BF16, COMPUTE_F16, COMPUTE_F32, HOP, N_FRAMES, N_SAMPLES, PRESETS, SAMPLE_RATE, SpecialTokens,
                      WhisperDims)
@@ -458,33 +458,44 @@ class WhisperModel:
         lane.load_speaker_embedding(diarization.load_xvector_state(spk_weights))
         self._diarization = True
 
-    def diarize(self, audio: Union[str, np.ndarray], num_speakers: Optional[int] = None, audio_channel=None, **kw) -> list:
+    def diarize(self, audio: Union[str, np.ndarray], num_speakers: Optional[int] = None, audio_channel=None, dsp_mode=None,
+                **kw) -> list:
         """Who spoke when: a list of diarization.Turn(start, end, speaker) in seconds, speakers "SPEAKER_00", "SPEAKER_01", ... in
         order of first appearance.  Two device calls - the segmentation network, then the speaker embeddings of every chunk's
         local speakers - with the masks on the host between them, then clustering and reconstruction on the host
         (diarization.diarize; its keywords - threshold, onset, min_duration_on, min_duration_off, ... - pass through).
-        num_speakers forces the number of clusters."""
+        num_speakers forces the number of clusters.  dsp_mode (dsp.resolve; None = off): both networks read the enhanced
+        recording (Engine.enhance, once)."""
         from . import diarization
+        dsp_params = dsp.resolve(dsp_mode)
         if not self.has_diarization:
             raise RuntimeError("no diarization networks are loaded (model.load_diarization(seg_weights, spk_weights))")
         if isinstance(audio, str):
             audio = decode_audio(audio, channel=parse_audio_channel(audio_channel))
-        return diarization.diarize(self._lanes[0], np.asarray(audio, dtype=np.float32), num_speakers=num_speakers, **kw)
+        audio = np.asarray(audio, dtype=np.float32)
+        if dsp_params is not None:
+            audio = self._lanes[0].enhance([audio], params=dsp_params)[0]
+        return diarization.diarize(self._lanes[0], audio, num_speakers=num_speakers, **kw)
 
     def transcribe_diarized(self, audio: Union[str, np.ndarray], num_speakers: Optional[int] = None,
-                            diarization_options: Optional[dict] = None, **kw) -> Tuple[list, TranscriptionInfo]:
+                            diarization_options: Optional[dict] = None, dsp_mode=None, **kw) -> Tuple[list, TranscriptionInfo]:
         """transcribe(audio, **kw) with every segment's speaker: ([(Segment, speaker or None), ...], info).  The speaker of a
-        segment is the one whose turns overlap it longest (diarization.assign_speakers); Segment keeps its fields."""
+        segment is the one whose turns overlap it longest (diarization.assign_speakers); Segment keeps its fields.
+        dsp_mode (dsp.resolve; None = off): the recording is enhanced once (Engine.enhance) and both passes read the result."""
         from . import diarization
+        dsp_params = dsp.resolve(dsp_mode)
         if isinstance(audio, str):   # read once, for both passes
             audio = decode_audio(audio, channel=parse_audio_channel(kw.pop("audio_channel", None)))
+        if dsp_params is not None:
+            audio = self.engine.enhance([np.asarray(audio, dtype=np.float32)], params=dsp_params)[0]
         turns = self.diarize(audio, num_speakers=num_speakers, **(diarization_options or {}))
         segments, info = self.transcribe(audio, **kw)
         segments = list(segments)
         return list(zip(segments, diarization.assign_speakers(segments, turns))), info
 
     # -- file ingest on the device --------------------------------------------------------------------
-    def decode_audio_many(self, paths_or_arrays: Sequence[Union[str, np.ndarray]], audio_channel=None) -> List[np.ndarray]:
+    def decode_audio_many(self, paths_or_arrays: Sequence[Union[str, np.ndarray]], audio_channel=None, dsp_mode=None
+                          ) -> List[np.ndarray]:
         """Every path -> mono float32 @16 kHz with ONE device call for all the files the device takes (read_audio_coded +
         Engine.ingest on the calling thread's engine context: conversion or G.711 / IMA ADPCM / FLAC decoding, downmix and the
         polyphase resampler run on the device over the whole batch).  Every path is read once: a file the device does not take
@@ -493,9 +504,12 @@ class WhisperModel:
         decode_audio.  Arrays pass through.
         audio_channel (None / "mix", "left", "right" or an index from 0: parse_audio_channel) picks one channel of every path
         instead of their mean; with an array among the inputs it is refused: an array is already mono.
-        The device resampler is decode_audio's (scipy.signal.resample_poly) accumulated in float32 instead of float64."""
+        The device resampler is decode_audio's (scipy.signal.resample_poly) accumulated in float32 instead of float64.
+        dsp_mode (dsp.resolve; None = off): every result - arrays that passed through included - goes through ONE
+        Engine.enhance call once it is mono float32 at 16 kHz."""
         from . import _lib
         eng = self.engine
+        dsp_params = dsp.resolve(dsp_mode)
         pick = parse_audio_channel(audio_channel)
         out: List[Optional[np.ndarray]] = [None] * len(paths_or_arrays)
         jobs = []
@@ -523,6 +537,8 @@ class WhisperModel:
                                  n_frames=[r.n_frames for _, r in jobs])
             for (i, _), y in zip(jobs, got):
                 out[i] = y
+        if dsp_params is not None:
+            return eng.enhance([np.asarray(a, dtype=np.float32) for a in out], params=dsp_params)
         return out
 
     def transcribe_groups(self, groups: Sequence[Sequence[Union[str, np.ndarray]]], pipeline_depth: Optional[int] = None, **kw
@@ -538,7 +554,10 @@ class WhisperModel:
         sequence_bias / prompt_words / prompt_word_boost (among **kw): one table, built once, installed by every worker on its own
         engine context for each of its groups.
         device_resample=True (one of **kw): each worker ingests its group's paths on its own engine context; audio_channel (one
-        of **kw) picks a channel of every path, as in transcribe_many."""
+        of **kw) picks a channel of every path, as in transcribe_many.
+        dsp_mode (one of **kw): checked once here; each worker enhances its group's recordings on its own engine context."""
+        if kw.get("dsp_mode") is not None:
+            kw = dict(kw, dsp_mode=dsp.resolve(kw["dsp_mode"]))
         if any(kw.get(k) is not None for k in ("sequence_bias", "prompt_words")):
             # tokenised and checked once; every worker's transcribe_many installs the table on its own engine context
             if kw.get("continuous"):
@@ -728,9 +747,14 @@ class WhisperModel:
                    device_resample: bool = False, audio_channel=None, clip_timestamps: Union[str, Sequence[float]] = "0",
                    hallucination_silence_threshold: Optional[float] = None, prompt_reset_on_temperature: float = 0.5,
                    suppress_tokens: Optional[Sequence[int]] = (-1,), sequence_bias=None, prompt_words=None,
-                   prompt_word_boost: Optional[float] = None, **kwargs
+                   prompt_word_boost: Optional[float] = None, dsp_mode=None, **kwargs
                    ) -> Tuple[Iterator[Segment], TranscriptionInfo]:
-        """sequence_bias ({tuple of token ids: bias}; None): HF Transformers' SequenceBiasLogitsProcessor on the device - a sequence
+        """dsp_mode (None; the reference service's dspMode): None / 0 / False = off, nothing new runs; 1 / True = denoise, high-pass
+        and level (the product's 1); a dsp.DspParams or a dict of its fields = as given.  The recording is enhanced ONCE on the
+        device (Engine.enhance: length-preserving, so every time keeps its meaning) as soon as it is mono float32 at 16 kHz;
+        VAD, language detection, log-mel and alignment all read the enhanced samples.  The definition is this project's own and
+        its effect on CER is unmeasured.
+        sequence_bias ({tuple of token ids: bias}; None): HF Transformers' SequenceBiasLogitsProcessor on the device - a sequence
         of one token always adds its bias to that token's raw logit, a longer one adds it to its last token when the history
         (prompt, then everything sampled, timestamps included) ends in its first tokens; the Whisper rules run afterwards and
         avg_logprob is that of the biased distribution.  At most 16 tokens per sequence, 4096 distinct last tokens, 8192 sequences
@@ -777,6 +801,7 @@ class WhisperModel:
         suppress = self._user_suppress(suppress_tokens)
         threshold = self._silence_threshold(hallucination_silence_threshold, word_timestamps)
         bias_table = self._bias_table(sequence_bias, prompt_words, prompt_word_boost)
+        dsp_params = dsp.resolve(dsp_mode)
         pick = parse_audio_channel(audio_channel)
         if isinstance(audio, str):
             audio = self.decode_audio_many([audio], audio_channel=pick)[0] if device_resample else decode_audio(audio, channel=pick)
@@ -794,12 +819,16 @@ class WhisperModel:
         if beam_size > self.max_batch:
             raise ValueError(f"beam_size={beam_size} needs {beam_size} decode rows but this model was built with "
                              f"max_batch={self.max_batch}; construct WhisperModel(..., max_batch>={beam_size})")
+        if int(language_detection_segments) < 1:
+            raise ValueError("language_detection_segments must be >= 1")
         chunks = None
         clips = parse_clip_timestamps(clip_timestamps, _frames_of(len(audio)))
         if vad_filter and clips != [(0, _frames_of(len(audio)))]:
             # faster-whisper filters only at the default clip_timestamps (from memory: unpinned); the clips are times of the recording
             warnings.warn("vad_filter=True is skipped: clip_timestamps already names the spans to decode", stacklevel=2)
             vad_filter = False
+        if dsp_params is not None:   # every argument is checked: the first device work of the call, in front of the VAD
+            audio = self.engine.enhance([audio], params=dsp_params)[0]
         if vad_filter:
             # faster-whisper: Silero VAD -> speech chunks -> transcribe their concatenation -> restore the time line.
             # The network is not available offline: with a speech-probability function supplied by the operator
@@ -817,8 +846,6 @@ class WhisperModel:
                 clips = parse_clip_timestamps("0", _frames_of(len(audio)))
         duration_after_vad = len(audio) / SAMPLE_RATE
         duration = (audio_full_len if chunks is not None else len(audio)) / SAMPLE_RATE
-        if int(language_detection_segments) < 1:
-            raise ValueError("language_detection_segments must be >= 1")
         if language is None:
             if self.is_multilingual:
                 k = int(language_detection_segments)
@@ -855,7 +882,8 @@ class WhisperModel:
         """One long recording through faster-whisper's batched form (batched.BatchedInferencePipeline(self).transcribe, which
         documents the keywords): VAD chunks packed into groups of at most one window, every group an independent clip of one
         continuous-batching beam session, fallbacks retried on the held cross-KV.  audio_channel (path input only) picks one
-        channel of the file instead of the mean of its channels."""
+        channel of the file instead of the mean of its channels; dsp_mode (as in `transcribe`) enhances the recording once, before
+        the VAD and before the session opens."""
         from .batched import BatchedInferencePipeline
         seq_bias.refuse_in_session("transcribe_batched", kw.pop("sequence_bias", None), kw.pop("prompt_words", None))
         kw.pop("prompt_word_boost", None)
@@ -1170,9 +1198,12 @@ class WhisperModel:
                         vad_filter: bool = False, vad_parameters: Optional[dict] = None, device_resample: bool = False,
                         retry_held: Optional[bool] = None, audio_channel=None,
                         clip_timestamps: Union[str, Sequence] = "0", hallucination_silence_threshold: Optional[float] = None,
-                        prompt_reset_on_temperature: float = 0.5, suppress_tokens: Optional[Sequence[int]] = (-1,)
-                        ) -> List[Tuple[List[Segment], TranscriptionInfo]]:
-        """sequence_bias, prompt_words, prompt_word_boost (keywords; as in `transcribe`): the table is installed on this call's
+                        prompt_reset_on_temperature: float = 0.5, suppress_tokens: Optional[Sequence[int]] = (-1,),
+                        dsp_mode=None) -> List[Tuple[List[Segment], TranscriptionInfo]]:
+        """dsp_mode (as in `transcribe`; lock-step and continuous=True alike): every file is enhanced in ONE Engine.enhance call
+        over the group once the files are mono float32 at 16 kHz - before the VAD, before language detection and before a session
+        begins.
+        sequence_bias, prompt_words, prompt_word_boost (keywords; as in `transcribe`): the table is installed on this call's
         engine context for the call and cleared when it ends; refused with continuous=True (ValueError before any device work).
 
         Several FILES in lock step: every round takes the next 30-s window of each unfinished file and runs them as
@@ -1232,6 +1263,7 @@ class WhisperModel:
         has moved on."""
         from .engine import session_prefill_value
         eng = self.engine
+        dsp_params = dsp.resolve(dsp_mode)
         if continuous:
             refuse_in_session("transcribe_many(continuous=True)", clip_timestamps, hallucination_silence_threshold)
         session_prefill = session_prefill_value(session_prefill)
@@ -1274,6 +1306,8 @@ class WhisperModel:
         clipped = [c != [(0, _frames_of(len(a)))] for c, a in zip(file_clips, pcm)]
         if vad_filter and any(clipped):
             warnings.warn("vad_filter=True is skipped for the files whose clip_timestamps already name the spans to decode", stacklevel=2)
+        if dsp_params is not None and pcm:   # the arguments are checked: one call for the group, in front of the VAD
+            pcm = list(eng.enhance(pcm, params=dsp_params))
         if vad_filter and pcm:
             params = dict(vad_parameters or {})
             kind, prob_fn = self._vad_source(params, self.vad_speech_prob_fn)
@@ -1531,7 +1565,7 @@ class WhisperModel:
                           row_max_new: Optional[Sequence[int]] = None, beam_size: int = 1, patience: float = 1.0,
                           initial_prompt: Optional[str] = None, word_timestamps: bool = False, detect_in_session: bool = False,
                           session_prefill: Union[int, bool] = 0, clip_timestamps="0", hallucination_silence_threshold=None,
-                          sequence_bias=None, prompt_words=None):
+                          sequence_bias=None, prompt_words=None, dsp_mode=None):
         """transcribe_batch's contract (clips <= 30 s each, sampled token ids per clip, input order) for any number of clips,
         through a continuous-batching session: a clip that finishes hands its decode row to the next one instead of waiting for
         the rest of its batch.  row_max_new (optional): one token budget per clip, each in [1, max_new_tokens].
@@ -1549,7 +1583,10 @@ class WhisperModel:
         (Engine.session(prefill=N)); clips that go in with the language placeholder are forced as before.
         clip_timestamps / hallucination_silence_threshold: accepted at their neutral values only; anything else is a ValueError
         before the session opens (they belong to the window loop: transcribe, lock-step transcribe_many).
-        sequence_bias / prompt_words: refused when given (a session's kernels do not apply the table)."""
+        sequence_bias / prompt_words: refused when given (a session's kernels do not apply the table).
+        dsp_mode: refused when it asks for enhancement (dsp.refuse_streaming): a live utterance needs a causal, stateful noise
+        tracker, which is out of scope."""
+        dsp.refuse_streaming(dsp_mode, "transcribe_stream")
         from .engine import Session, session_prefill_value
         refuse_in_session("transcribe_stream", clip_timestamps, hallucination_silence_threshold)
         seq_bias.refuse_in_session("transcribe_stream", sequence_bias, prompt_words)

@@ -77,8 +77,12 @@ class BatchedWhisperASR(MI355XWhisperASR):
     def __init__(self, max_clips: int = 6, max_wait_ms: float = 5.0, audio_ctx=None, max_new_tokens: int = 224,
                  continuous: bool = False, word_timestamps: bool = False, detect_in_session: bool = False,
                  session_prefill=0, clip_timestamps="0", hallucination_silence_threshold=None, **kwargs):
+        from .dsp import refuse_streaming
         from .engine import session_prefill_value
         from .model import refuse_in_session
+        # enhancement reads a whole recording: refused before a model is built or a worker starts
+        refuse_streaming(kwargs.get("dsp_mode"), "BatchedWhisperASR")
+        kwargs.pop("dsp_mode", None)
         # the window-loop options of WhisperModel.transcribe: an utterance here is one window, and a session cannot run them
         try:
             refuse_in_session("BatchedWhisperASR(continuous=True)", clip_timestamps, hallucination_silence_threshold)
