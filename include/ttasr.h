@@ -232,6 +232,29 @@ TTASR_API int ttasr_self_kv_get(ttasr_ctx* ctx, int32_t layer, const int32_t* pa
 TTASR_API int ttasr_self_attn_probe(ttasr_ctx* ctx, int32_t form, int32_t layer, int32_t n_rows, const float* qkv_host, int32_t n_slab,
                                     const int32_t* geom_host, int32_t n_geom, const int32_t* aux_host, int32_t n_aux, int32_t identity_pages,
                                     int32_t row0, const int32_t* done_host, float* out_host, char* sig_buf, int32_t sig_len);
+/* Known-answer hook for the ENCODER attention kernels (tests/test_gpu_enc_attn_kernels.py): ONE launch on
+ * caller-supplied operands, through the function the engine itself calls to choose its kernel.
+ *   TTASR_ENC_SELF   the encoder layer's self-attention: a_host = qkv, f32 [B][T][3 d_model] (q | k | v per row), B <= max_batch,
+ *                    1 <= T <= n_audio_ctx; k_host, v_host and Tk are not used.  Options "flash", "flash_qw" and "generic_kernels"
+ *                    steer the launch exactly as they steer ttasr_encode (16-bit engines: the MFMA flash kernel with 64 or 32
+ *                    queries per wave, or the plain kernel; the f32 engine: the plain kernel).
+ *   TTASR_ENC_CROSS  (16-bit engines) the cross-attention launcher with T rows per clip: a_host = q, f32 [B clips][T][d_model],
+ *                    1 <= T <= n_text_ctx; k_host / v_host = f32 [B][n_heads][Tk][64], 1 <= Tk <= n_audio_ctx.  The launcher gets
+ *                    kv_div = T and a frame-split workspace, so its own rule applies: the flash kernel's many-row form from 32 rows
+ *                    per clip upward, the decode step's kernels below.
+ * Operands are cast to the engine type and used as given (the 1/8 of the attention lives in the q weights).  out_host: f32
+ * [B][T][d_model].  The device output is filled with a NaN pattern (0x7fc0 in 16 bits, 0x7fc00000 in f32) before the launch and
+ * has one guard row of the same pattern behind it: a row no kernel writes comes back NaN, and the call returns
+ * TTASR_ENC_GUARD_TOUCHED (1; out_host is filled all the same) when the guard row did not keep its pattern - the one positive
+ * return value of the library.  sig_buf (optional, sig_len bytes) receives the signature of what ran, "name<template arguments>
+ * grid <threads>" (cross form: the launcher's own text).  Refused in an open session.  Operands, output and workspace live in a
+ * block of the hook's own (allocated by the first call): resident mel / encoder / cross-KV state, search state and captured
+ * graphs are not touched. */
+#define TTASR_ENC_SELF 0
+#define TTASR_ENC_CROSS 1
+#define TTASR_ENC_GUARD_TOUCHED 1
+TTASR_API int ttasr_enc_attn_probe(ttasr_ctx* ctx, int32_t form, int32_t B, int32_t T, const float* a_host, const float* k_host,
+                                   const float* v_host, int32_t Tk, float* out_host, char* sig_buf, int32_t sig_len);
 
 /* Short-window option (opt-in, a behavioural change versus Whisper's fixed 30-s training window, the
  * same trade whisper.cpp's `audio_ctx` makes): subsequent log_mel / encode / generate calls use only the first n_ctx

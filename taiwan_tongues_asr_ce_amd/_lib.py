@@ -15,7 +15,7 @@ SYMBOLS = [
     "ttasr_create", "ttasr_create_shared", "ttasr_destroy", "ttasr_last_error", "ttasr_version", "ttasr_load_tensor", "ttasr_load_tensor_device",
     "ttasr_finalize_weights", "ttasr_log_mel", "ttasr_log_mel_windows", "ttasr_log_mel_windows_cut", "ttasr_set_mel", "ttasr_encode", "ttasr_set_encoder_output",
     "ttasr_get_cross_kv", "ttasr_get_cross_kv_fp8", "ttasr_cross_attn_probe", "ttasr_align_attn_probe",
-    "ttasr_self_kv_fill", "ttasr_self_kv_set", "ttasr_self_kv_get", "ttasr_self_attn_probe", "ttasr_set_audio_ctx", "ttasr_generate", "ttasr_generate_capped", "ttasr_generate_beam", "ttasr_generate_beam_ragged", "ttasr_generate_sample", "ttasr_decode_reset", "ttasr_decode_step", "ttasr_apply_rules", "ttasr_select_probe", "ttasr_set_sequence_bias", "ttasr_seq_bias_probe", "ttasr_align", "ttasr_dtw",
+    "ttasr_self_kv_fill", "ttasr_self_kv_set", "ttasr_self_kv_get", "ttasr_self_attn_probe", "ttasr_enc_attn_probe", "ttasr_set_audio_ctx", "ttasr_generate", "ttasr_generate_capped", "ttasr_generate_beam", "ttasr_generate_beam_ragged", "ttasr_generate_sample", "ttasr_decode_reset", "ttasr_decode_step", "ttasr_apply_rules", "ttasr_select_probe", "ttasr_set_sequence_bias", "ttasr_seq_bias_probe", "ttasr_align", "ttasr_dtw",
     "ttasr_set_option", "ttasr_phase_ms", "ttasr_beam_profile", "ttasr_encoder_kernel_ms", "ttasr_bench_kernel", "ttasr_bench_kernel_signature", "ttasr_sync",
     "ttasr_session_begin", "ttasr_session_begin_beam", "ttasr_session_submit", "ttasr_session_submit_windows", "ttasr_session_poll", "ttasr_session_stats", "ttasr_session_rows", "ttasr_session_end",
     "ttasr_align_batch", "ttasr_session_hold", "ttasr_session_align", "ttasr_session_release", "ttasr_detect_language",
@@ -134,6 +134,7 @@ def load() -> C.CDLL:
     lib.ttasr_self_kv_set.argtypes = [vp, i32, vp, i32, i32, vp]
     lib.ttasr_self_kv_get.argtypes = [vp, i32, vp, i32, vp]
     lib.ttasr_self_attn_probe.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, C.c_char_p, i32]
+    lib.ttasr_enc_attn_probe.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, vp, C.c_char_p, i32]
     lib.ttasr_set_audio_ctx.argtypes = [vp, i32]
     lib.ttasr_generate.argtypes = [vp, i32, i32p, i32p, i32, C.POINTER(GenOpts), i32p, i32p, f32p, f32p]
     lib.ttasr_generate_capped.argtypes = [vp, i32, i32p, i32p, i32, C.POINTER(GenOpts), i32p, i32p, i32p, f32p, f32p]

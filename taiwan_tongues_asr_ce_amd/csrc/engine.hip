@@ -151,6 +151,7 @@ void ttasr_destroy(ttasr_ctx* c) {
   for (void* p : c->allocs) hipFree(p);
   c->align_dev.reset();
   c->seq_bias_dev.reset();
+  c->enc_probe_dev.reset();
   vad_free(c);
   seg_free(c);
   spk_free(c);
@@ -1112,13 +1113,7 @@ int ttasr_bench_kernel(ttasr_ctx* c, const char* name, int32_t B, int32_t iters,
       sched_gemm(c, g);
       bytes = ((double)B * T_ * ffn + ffn * d) * e + (delta ? e : 8.0) * B * T_ * d; flops = 2.0 * B * T_ * d * ffn;
     } else if (k == "enc_attn") {
-      TT_DISPATCH(c, {
-        bool flash = false;
-        if constexpr (sizeof(T) == 2) {
-          if (!c->force_basic && !c->no_flash) { launch_enc_attn_flash_bf16<T>((const T*)c->qkv, (T*)c->att, B, c->T, c->H, c->ko, s); flash = true; }
-        }
-        if (!flash) launch_enc_attn_simple<T>((const T*)c->qkv, (T*)c->att, B, c->T, c->H, s);
-      });
+      sched_enc_attn(c, c->qkv, c->att, B, c->T, s);
       bytes = (double)B * T_ * 4.0 * d * e; flops = 4.0 * B * T_ * T_ * d;
     } else if (k == "dec_gemm_fc1") {
       GemmArgs g; g.A = c->dh; g.W = c->dec[0].w1; g.M = B; g.N = c->ffn; g.K = c->d; g.lda = c->d; g.ldw = c->d;

@@ -214,6 +214,10 @@ struct ttasr_ctx {
   // the feature is launched)
   DevBlock<int32_t> seq_bias_dev;
   int seq_bias_n = 0;
+  // ttasr_enc_attn_probe: ONE device block of its own - f32 staging, the operands in the engine type, the output with its guard
+  // row, the frame-split workspace of the cross form - allocated by the first call, grown to the largest request, reset by
+  // ttasr_destroy.  The encoder's and the decode step's own buffers are never touched.
+  DevBlock<> enc_probe_dev;
   // voice-activity network (engine_vad.hip): created by the first ttasr_vad_load_tensor, freed by ttasr_destroy; per context,
   // outside the weight-share bookkeeping
   ttasr_detail::VadState* vad = nullptr;
@@ -427,6 +431,8 @@ int step_graph(ttasr_ctx* c, int B, int mode, int nsteps = 1);
 void sched_detect_rows(ttasr_ctx* c, int B);                  // decode pass of B rows that ends in the language head (mode 3), launched directly
 // the decode step's cross-attention dispatch of `layer` for rows [0, n) on the context's stream (ttasr_cross_attn_probe)
 void sched_cross_attn(ttasr_ctx* c, int layer, int n, int kv_div, const void* dq, void* datt, const SlabIn& sq, const int32_t* done);
+// the encoder's self-attention dispatch on stream s: qkv T [B][T_][3 d] -> att T [B][T_][d] (run_encoder's choice; ttasr_enc_attn_probe)
+void sched_enc_attn(ttasr_ctx* c, const void* qkv, void* att, int B, int T_, hipStream_t s);
 void drop_graphs(ttasr_ctx* c);
 void drop_rule_graphs(ttasr_ctx* c);
 void drop_lang_graphs(ttasr_ctx* c);                          // the step graphs of armed sessions (StepShape::lang_rows)

@@ -2,7 +2,7 @@
 // engine_ctx.hpp).  It stages the caller's rows, histories and state in the buffers the searches use, calls ONE launcher of
 // kernels_decode.hip with the arguments the engine passes it, and copies the results back.  No decision of its own: what is
 // chosen, summed or finished is what the kernel did.  Behind it: the sequence-bias table's install (ttasr_set_sequence_bias) and the
-// hook of its kernel (ttasr_seq_bias_probe), built the same way.
+// hook of its kernel (ttasr_seq_bias_probe), built the same way; and the hook of the encoder attention kernels (ttasr_enc_attn_probe).
 #include "engine_ctx.hpp"
 
 namespace ttasr_detail {
@@ -259,9 +259,82 @@ static int seq_bias_probe(ttasr_ctx* c, int form, const ttasr_seq_bias_io& io, c
   return TTASR_OK;
 }
 
+// ---- encoder attention: the known-answer hook of enc_attn_flash_kernel (both instantiation families) and enc_attn_simple_kernel ----
+// Stages the caller's operands in a block of the hook's own (c->enc_probe_dev), fills the output and one guard row behind it with a
+// NaN pattern, launches ONCE through the function the engine calls (sched_enc_attn | launch_cross_attn_decode) and copies the rows
+// back.  Nothing resident - mel, encoder state, cross-KV, search state, graphs - is read or written.
+static int enc_attn_probe(ttasr_ctx* c, int form, int B, int T_, const float* a, const float* k, const float* v, int Tk, float* out,
+                          char* sig_buf, int sig_len) {
+  const bool cross = form == TTASR_ENC_CROSS;
+  if (form != TTASR_ENC_SELF && !cross) return fail(c, TTASR_E_INVALID, "encoder attention probe: form %d", form);
+  if (!a || !out || (sig_buf && sig_len < 1)) return fail(c, TTASR_E_INVALID, "encoder attention probe: NULL argument");
+  const int d = c->d, H = c->H;
+  const size_t e = c->esz;
+  if (cross) {
+    if (!c->lowp) return fail(c, TTASR_E_INVALID, "encoder attention probe: the cross form needs a 16-bit engine");
+    if (!k || !v) return fail(c, TTASR_E_INVALID, "encoder attention probe: k / v is NULL");
+    if (T_ < 1 || T_ > c->cfg.n_text_ctx) return fail(c, TTASR_E_INVALID, "encoder attention probe: %d rows per clip outside [1, n_text_ctx=%d]", T_, c->cfg.n_text_ctx);
+    if (Tk < 1 || Tk > c->cfg.n_audio_ctx) return fail(c, TTASR_E_INVALID, "encoder attention probe: %d frames outside [1, n_audio_ctx=%d]", Tk, c->cfg.n_audio_ctx);
+  } else if (T_ < 1 || T_ > c->cfg.n_audio_ctx) {
+    return fail(c, TTASR_E_INVALID, "encoder attention probe: T %d outside [1, n_audio_ctx=%d]", T_, c->cfg.n_audio_ctx);
+  }
+  const int64_t rows = (int64_t)B * T_, n_in = rows * (cross ? d : 3 * d), n_kv = cross ? (int64_t)B * H * Tk * 64 : 0, n_out = rows * d;
+  Carve cv;
+  const size_t o_f32 = cv.take((size_t)std::max(std::max(n_in, n_kv), n_out) * 4), o_a = cv.take((size_t)n_in * e), o_k = cv.take((size_t)n_kv * e),
+               o_v = cv.take((size_t)n_kv * e), o_out = cv.take((size_t)(n_out + d) * e), o_ws = cv.take(cross ? (size_t)rows * H * 8 * 66 * 4 : 0);
+  TRY(c->enc_probe_dev.ensure(c, cv.used, "encoder attention probe scratch"));
+  hipStream_t s = c->stream;
+  char* base = c->enc_probe_dev;
+  float* f32 = (float*)(base + o_f32);
+  auto stage = [&](const float* src, size_t at, int64_t n) -> int {   // f32 from the host, cast to the engine type
+    if (c->lowp) {
+      HIPCHK(c, hipMemcpyAsync(f32, src, (size_t)n * 4, hipMemcpyHostToDevice, s));
+      TT_DISPATCH(c, launch_cast<T>(f32, (T*)(base + at), n, s));
+    } else {
+      HIPCHK(c, hipMemcpyAsync(base + at, src, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    }
+    return 0;
+  };
+  TRY(stage(a, o_a, n_in));
+  if (cross) { TRY(stage(k, o_k, n_kv)); TRY(stage(v, o_v, n_kv)); }
+  // a NaN in either 16-bit type / in f32: a row the kernel does not write and a write behind the last row are both visible
+  constexpr unsigned short kFill16 = 0x7fc0; constexpr int kFill32 = 0x7fc00000;
+  if (c->lowp) HIPCHK(c, hipMemsetD16Async((hipDeviceptr_t)(base + o_out), kFill16, (size_t)(n_out + d), s));
+  else HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)(base + o_out), kFill32, (size_t)(n_out + d), s));
+  g_kernel_sig[0] = 0; g_kernel_sig_on = true;
+  if (cross) {
+    // kv_div = rows per clip and a workspace for every row: the launcher's own rule decides (flash from 32 rows per clip upward)
+    TT_DISPATCH(c, launch_cross_attn_decode<T>((const T*)(base + o_a), (const T*)(base + o_k), (const T*)(base + o_v), (T*)(base + o_out), (int)rows,
+                                               H, Tk, T_, c->ko, s, (float*)(base + o_ws), SlabIn{}, (int)rows));
+  } else {
+    sched_enc_attn(c, base + o_a, base + o_out, B, T_, s);
+  }
+  g_kernel_sig_on = false;
+  if (sig_buf) snprintf(sig_buf, (size_t)sig_len, "%s", g_kernel_sig);
+  std::vector<char> guard((size_t)d * e);
+  HIPCHK(c, hipMemcpyAsync(guard.data(), base + o_out + (size_t)n_out * e, guard.size(), hipMemcpyDeviceToHost, s));
+  if (c->lowp) { TT_DISPATCH(c, launch_uncast<T>((const T*)(base + o_out), f32, n_out, s));
+                 HIPCHK(c, hipMemcpyAsync(out, f32, (size_t)n_out * 4, hipMemcpyDeviceToHost, s)); }
+  else HIPCHK(c, hipMemcpyAsync(out, base + o_out, (size_t)n_out * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+  bool intact = true;
+  for (int i = 0; i < d && intact; ++i)
+    intact = c->lowp ? ((const unsigned short*)guard.data())[i] == kFill16 : ((const int*)guard.data())[i] == kFill32;
+  return intact ? TTASR_OK : TTASR_ENC_GUARD_TOUCHED;
+}
+
 }  // namespace ttasr_detail
 
 extern "C" {
+
+int ttasr_enc_attn_probe(ttasr_ctx* c, int32_t form, int32_t B, int32_t T, const float* a_host, const float* k_host, const float* v_host,
+                         int32_t Tk, float* out_host, char* sig_buf, int32_t sig_len) {
+  return guarded(c, [&]() -> int {
+  TRY(check_ready(c, B));   // refused in an open session
+  return enc_attn_probe(c, form, B, T, a_host, k_host, v_host, Tk, out_host, sig_buf, sig_len);
+  });
+}
 
 int ttasr_set_sequence_bias(ttasr_ctx* c, int32_t n_seq, const int32_t* tokens_host, const int32_t* offsets_host, const float* bias_host) {
   return guarded(c, [&]() -> int {

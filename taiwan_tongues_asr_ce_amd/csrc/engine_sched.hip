@@ -112,6 +112,26 @@ int run_cross_kv(ttasr_ctx* c, int B) {
   return 0;
 }
 
+// The encoder's self-attention over qkv [B][T_][3 d] -> att [B][T_][d]: THE place that chooses between the MFMA flash kernel
+// (kernels_flash.hip; 16-bit engines, options generic_kernels = 0 and flash = 1; flash_qw picks 64 or 32 queries per wave) and the
+// plain f32 kernel (kernels_attn.hip).  Called by run_encoder, by ttasr_bench_kernel "enc_attn" and, on caller-supplied rows, by the
+// known-answer hook ttasr_enc_attn_probe - which therefore has no decision logic of its own.
+template <typename T>
+void run_enc_attn(ttasr_ctx* c, const void* qkv, void* att, int B, int T_, hipStream_t s) {
+  if constexpr (sizeof(T) == 2) {
+    if (!c->force_basic && !c->no_flash) {
+      const int qw = c->ko.flash_qw >= 2 ? 2 : 1;
+      if (g_kernel_sig_on) snprintf(g_kernel_sig, sizeof g_kernel_sig, "enc_attn_flash_kernel<%s, false, %d> grid %d", sig_type<T>(), qw,
+                                    (T_ + 128 * qw - 1) / (128 * qw) * c->H * B * 256);
+      launch_enc_attn_flash_bf16<T>((const T*)qkv, (T*)att, B, T_, c->H, c->ko, s);
+      return;
+    }
+  }
+  if (g_kernel_sig_on) snprintf(g_kernel_sig, sizeof g_kernel_sig, "enc_attn_simple_kernel<%s> grid %d", sig_type<T>(), (T_ + 15) / 16 * c->H * B * 256);
+  launch_enc_attn_simple<T>((const T*)qkv, (T*)att, B, T_, c->H, s);
+}
+void sched_enc_attn(ttasr_ctx* c, const void* qkv, void* att, int B, int T_, hipStream_t s) { TT_DISPATCH(c, run_enc_attn<T>(c, qkv, att, B, T_, s)); }
+
 template <typename T>
 int run_encoder(ttasr_ctx* c, int B) {
   const int d = c->d, T_ = c->T, F = c->F, M = c->M, ffn = c->ffn;
@@ -169,11 +189,7 @@ int run_encoder(ttasr_ctx* c, int B) {
     ln(L.ln1g, L.ln1b, c->h);
     { GemmArgs g = lin_args<T>(c->h, L.wqkv, R, 3 * d, d); g.epi.bias = L.bqkv; g.epi.out_t = c->qkv; gemm<T>(c, g); }
     enc_mark(c, EC_QKV);
-    bool flash = false;
-    if constexpr (sizeof(T) == 2) {
-      if (!c->force_basic && !c->no_flash) { launch_enc_attn_flash_bf16<T>((const T*)c->qkv, (T*)c->att, B, T_, c->H, c->ko, s); flash = true; }
-    }
-    if (!flash) launch_enc_attn_simple<T>((const T*)c->qkv, (T*)c->att, B, T_, c->H, s);
+    run_enc_attn<T>(c, c->qkv, c->att, B, T_, s);
     enc_mark(c, EC_ATTN);
     residual_gemm(c->att, L.wo, L.bo, d, EC_OUT);
     ln(L.ln2g, L.ln2b, c->h, true);

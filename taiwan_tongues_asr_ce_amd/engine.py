@@ -614,6 +614,31 @@ class Engine:
                                                    1 if identity_pages else 0, row0, vp(flags), _ptr(out), buf, 256), "self_attn_probe")
         return out, buf.value.decode()
 
+    def enc_attn_probe(self, qkv: Optional[np.ndarray] = None, q: Optional[np.ndarray] = None, k: Optional[np.ndarray] = None,
+                       v: Optional[np.ndarray] = None):
+        """One launch of the encoder attention on the caller's operands (ttasr_enc_attn_probe).  Self form: qkv float32
+        [B][T][3 d_model].  Cross form (16-bit engines): q float32 [clips][n_q][d_model], k and v float32 [clips][n_heads][Tk][64].
+        Returns (out float32 [B][T][d_model] - NaN where no kernel wrote, signature of what ran, whether the guard row behind the
+        output kept its fill pattern)."""
+        d, buf = self.dims.d_model, C.create_string_buffer(256)
+        if qkv is not None:
+            assert q is None and k is None and v is None
+            a = np.ascontiguousarray(qkv, dtype=np.float32)
+            assert a.ndim == 3 and a.shape[2] == 3 * d, a.shape
+            form, kk, vv, Tk = 0, None, None, 0
+        else:
+            a = np.ascontiguousarray(q, dtype=np.float32)
+            kk, vv = np.ascontiguousarray(k, dtype=np.float32), np.ascontiguousarray(v, dtype=np.float32)
+            assert a.ndim == 3 and a.shape[2] == d, a.shape
+            assert kk.shape == vv.shape == (a.shape[0], self.dims.n_heads, kk.shape[2], 64), (kk.shape, vv.shape)
+            form, Tk = 1, kk.shape[2]
+        out = np.empty((a.shape[0], a.shape[1], d), dtype=np.float32)
+        rc = self.lib.ttasr_enc_attn_probe(self.h, form, a.shape[0], a.shape[1], _ptr(a), None if kk is None else _ptr(kk),
+                                           None if vv is None else _ptr(vv), Tk, _ptr(out), buf, 256)
+        if rc != 1:   # TTASR_ENC_GUARD_TOUCHED: the output is there, the guard row is not what it was
+            self._check(rc, "enc_attn_probe")
+        return out, buf.value.decode(), rc == 0
+
     # -- a9, a10 -------------------------------------------------------------------------------
     def gen_opts(self, max_new_tokens: int, timestamps: bool, suppress: Optional[Sequence[int]] = None,
                  begin_suppress: Optional[Sequence[int]] = None, suppress_eot: bool = False, no_speech: bool = True,

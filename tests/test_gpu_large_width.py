@@ -77,8 +77,9 @@ def test_width_parity_f32_and_bf16(dims):
 
 @pytest.mark.gpu
 def test_flash_attention_matches_the_plain_attention_kernel_at_ragged_windows():
-    """The MFMA flash kernel (kernels_flash.hip: 64-key tiles, last tile masked, softmax denominator summed by an all-ones
-    MFMA over the bf16-rounded weights) against the one-query-per-wave kernel (option `flash = 0`) on the same bf16 q, k, v:
+    """The MFMA flash kernel (kernels_flash.hip: 64-key tiles, last tile masked, softmax denominator summed in float32 registers
+    over the UNROUNDED weights while the PV MFMA takes them rounded to the storage type; the kernel itself is held to a float64
+    reference in test_gpu_enc_attn_kernels.py) against the plain float32 kernel (option `flash = 0`) on the same bf16 q, k, v:
     the 2-layer encoder output agrees to bf16 rounding at windows that end inside a key tile (1500 = 23 x 64 + 28; 150),
     exactly on one (64, 128), on a single partial tile (20) and on an even tile count (200)."""
     from taiwan_tongues_asr_ce_amd.engine import Engine
