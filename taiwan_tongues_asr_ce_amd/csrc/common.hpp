@@ -221,6 +221,7 @@ struct KernelOpts {
   int skinny_nt = 1;           // option weights_nontemporal: nontemporal weight loads in the decode GEMMs
   int skinny_narrow = 1;       // option dec_narrow_blocks: 20-row n-blocks where they fill the CUs evenly (fixed once the weights are packed)
   int skinny_x_lds = 1;        // option dec_x_lds: the decode GEMMs stage their activation tile through LDS (0 = fragment loads from memory; bit-identical)
+  int skinny_red_swz = 1;      // option dec_red_swizzle: XOR-swizzled chunk slots in the decode GEMMs' cross-wave reduction buffer (0 = linear rows, 8-way store conflict; bit-identical)
   int flash_qw = 2;            // option flash_qw: query blocks of 32 per wave in the encoder's flash attention (1 = the round-5 form)
 };
 

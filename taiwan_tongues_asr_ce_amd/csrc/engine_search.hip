@@ -121,6 +121,7 @@ int set_option(ttasr_ctx* c, const std::string& key, int v) {
   else if (key == "xattn_mq_fp8") c->xattn_mq_fp8 = on;
   else if (key == "weights_nontemporal") c->ko.skinny_nt = on;
   else if (key == "dec_x_lds") c->ko.skinny_x_lds = on;
+  else if (key == "dec_red_swizzle") c->ko.skinny_red_swz = on;
   else if (key == "ragged_exit") c->ragged_exit = on;
   else if (key == "flash_qw") { if (v < 1 || v > 2) return 1; c->ko.flash_qw = v; }
   else if (key == "xattn_mq_slices") { if (v < 0 || v > 8) return 1; c->ko.xattn_mq_slices = v; }

@@ -16,6 +16,16 @@
 // residual) issued before the first use: one memory round trip per kernel (each extra one costs ~1.5 us in
 // the decode chain).  NW waves split K inside the workgroup (LDS reduce, fixed order).
 //
+// The LDS reduce sits on the critical path (last MFMA -> store -> barrier -> load -> the kernel's only global store), after the
+// last weight byte has arrived.  Each wave parks its 32 x 32 f32 tile as red[wave][row group][b][32] with four ds_write_b128 per
+// row group; a ds_write_b128 is served in groups of 8 consecutive lanes over 32 banks, and those 8 lanes hold 8 different b with
+// the same 16-byte chunk - with linear rows the same four banks, an 8-way conflict: 64 LDS-array cycles per store instead of 8,
+// for every wave of the workgroup on the one LDS.  So chunk c of row b is stored at chunk slot c ^ (b & 7) (option
+// dec_red_swizzle, default on; no size change, so the aliasing with the activation tile stays): stores and loads conflict-free
+// for every NW / RB form (tools/lds_bank_model.py, tests/test_lds_bank_model.py), same values added in the same order.
+// Measured, three interleaved rounds on one device (profiles/dec_red_swizzle_ab.jsonl): 429.0-429.4 -> 420.4-420.5 ms per
+// benchmark step of 131 decode passes, bit-identical tokens.
+//
 // What bounds these kernels (round 2, rocprofv3 timeline of the real chain): a CU takes in only ~25 GB/s of HBM-cold
 // bytes (its outstanding-miss queue over ~1 us of latency), and after every kernel boundary the activation rows come from
 // the Infinity Cache, not L2.  So a GEMM wants its weights spread over ALL 256 CUs in pieces of <= ~40 KB: every decode GEMM
@@ -103,7 +113,7 @@ static void skinny_allow_big_lds() {
 // Argument order (see common.hpp sgpr_pin): everything the first load batch needs - the weight stream, the activation tile and
 // the bias / residual prefetch - leads the list as pointers and ints, so it arrives PRELOADED in SGPRs (13 dwords of the 14 the
 // compiler preloads) and the first address is formed without a kernarg fetch.  pk_ = B | ksplit << 8 | rpb << 16 | x_lds << 24 |
-// act << 25 (B <= 128, ksplit <= 16, rpb 20 / 32: the launcher's own limits).  The tail - the three output pointers and the slab
+// act << 25 | red_swz << 26 (B <= 128, ksplit <= 16, rpb 20 / 32: the launcher's own limits).  The tail - the three output pointers and the slab
 // stride, which only the stores at the end use - is fetched by pin_tail() AFTER the first batch has been issued, under the
 // vector loads.  The encoder's GemmEpi does not travel: rowtab / headsplit are refused by the launcher, the rest is flat here.
 template <typename T16, int NW, int RB, int U, bool NT, bool ONE>
@@ -113,8 +123,8 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const bf16_t* __re
                                                               float* __restrict__ slab_, int64_t slab_stride_) {
   // U = k-steps in flight per wave (register budget: U * (1 + RB) * 4); the launcher picks the smallest instantiated
   // U >= steps so that no load is issued twice
-  // dynamic LDS: the reduction buffer red[wave][row group][b*32 + n] (NW * RB * 4 KiB) and - aliased with it, separated by a
-  // barrier - the activation tile of the LDS-staged form (skinny_lds_bytes)
+  // dynamic LDS: the reduction buffer red[wave][row group][b*32 + n] (NW * RB * 4 KiB; the 16-byte chunks of a row swizzled, see
+  // the reduction below) and - aliased with it, separated by a barrier - the activation tile of the LDS-staged form (skinny_lds_bytes)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float (*red)[RB][32 * 32] = (float (*)[RB][32 * 32])smem;
   const bf16_t* Wsh = sgpr_pin_ptr(Wsh_);
@@ -123,6 +133,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const bf16_t* __re
   const int B = pk & 255, ksplit = (pk >> 8) & 255, N = sgpr_pin(N_), K = sgpr_pin(K_);
   const int rpb = (pk >> 16) & 255;          // rows per n-block of the packed matrix (32 or 20: skinny_rows_per_block)
   const int xl = (pk >> 24) & 1;             // 1: activation tile through LDS (launcher: skinny_x_lds)
+  const int sw = (pk >> 26) & 1 ? 7 : 0;     // 7: swizzled reduction buffer (launcher: skinny_red_swz; see the reduction below), 0: linear rows
   const int steps = sgpr_pin(steps_);  // k-steps per wave = K / 16 / (NW * ksplit), divided on the host: an integer division here is
                                        // ~40 dependent instructions in front of the first load
   struct { const float* bias; const float* residual; float* out_f32; void* out_t; int64_t ldc; int act; } e;
@@ -270,20 +281,29 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const bf16_t* __re
     }
   }
   // D: col = lane & 31 = batch row b, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) = output n
+  // Reduction buffer layout: row b keeps its 32 floats (128 B = the 32 banks a store sees), but its 16-byte chunk c = 2q + hi
+  // (hi = lane >> 5) sits at chunk slot c ^ (b & 7).  A ds_write_b128 is served in groups of 8 consecutive lanes: they share q
+  // and hi and differ in b, so with linear rows (sw = 0) all eight hit the same four banks - 8-way, 64 LDS cycles per store
+  // instead of 8, on the critical path between the last MFMA and the barrier.  XOR-ed with b & 7 the eight lanes take the eight
+  // different slots: conflict-free.  The reader (thread = row tid >> 3, chunk tid & 7) undoes the same XOR; its ds_read_b128
+  // groups stay conflict-free (the XOR permutes slots inside one row only: tools/lds_bank_model.py checks every group of both).
+  // Same values in the same order: bit-identical to the linear form.
+  const int wsl = (lane & 31) * 32 + 4 * ((lane >> 5) ^ (lane & sw));   // chunk slot of q = 0; q only flips bits 1-2: (2q + hi) ^ m = 2q ^ (hi ^ m)
+  const int rsl = (tid >> 3) * 32 + 4 * ((tid & 7) ^ ((tid >> 3) & sw));
 #pragma unroll
   for (int g = 0; g < RB; ++g)
 #pragma unroll
     for (int q = 0; q < 4; ++q)
-      *(float4*)&red[wave][g][(lane & 31) * 32 + 8 * q + 4 * (lane >> 5)] =
+      *(float4*)&red[wave][g][wsl ^ (8 * q)] =
           make_float4(acc[g][4 * q], acc[g][4 * q + 1], acc[g][4 * q + 2], acc[g][4 * q + 3]);
   __syncthreads();
   if (!ecell) return;
 #pragma unroll
   for (int g = 0; g < RB; ++g) {
-    float4 v = *(const float4*)&red[0][g][(tid >> 3) * 32 + 4 * (tid & 7)];
+    float4 v = *(const float4*)&red[0][g][rsl];
 #pragma unroll
     for (int w = 1; w < NW; ++w) {
-      const float4 t = *(const float4*)&red[w][g][(tid >> 3) * 32 + 4 * (tid & 7)];
+      const float4 t = *(const float4*)&red[w][g][rsl];
       v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
     }
     v.x += ebias.x; v.y += ebias.y; v.z += ebias.z; v.w += ebias.w;
@@ -342,13 +362,15 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const bf16_t* __re
 // kernel with NW = 8: the logits are bit-identical to it.
 // ------------------------------------------------------------------------------------------------
 template <typename T16, int RB, bool NT>
-__global__ __launch_bounds__(512) void gemm_vocab_kernel(const bf16_t* __restrict__ Wsh_, const bf16_t* __restrict__ x_, int B_, int N_,
+__global__ __launch_bounds__(512) void gemm_vocab_kernel(const bf16_t* __restrict__ Wsh_, const bf16_t* __restrict__ x_, int pk_, int N_,
                                                          int K_, int steps_, float* __restrict__ out_, int64_t ldc_) {
   constexpr int NW = 8, U = 10;
   extern __shared__ __attribute__((aligned(16))) float vred[];   // [2][NW][RB][32 * 32]
   const bf16_t* Wsh = sgpr_pin_ptr(Wsh_);
   const bf16_t* x = sgpr_pin_ptr(x_);
-  const int B = sgpr_pin(B_), N = sgpr_pin(N_), K = sgpr_pin(K_), steps = sgpr_pin(steps_);
+  const int pk = sgpr_pin(pk_);   // B | red_swz << 8 (B <= 64)
+  const int B = pk & 255, N = sgpr_pin(N_), K = sgpr_pin(K_), steps = sgpr_pin(steps_);
+  const int sw = (pk >> 8) & 1 ? 7 : 0;   // swizzled reduction buffer: the layout of gemm_skinny_kernel's, see there
   float* out = sgpr_pin_ptr(out_);
   const int64_t ldc = sgpr_pin(ldc_);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -373,6 +395,8 @@ __global__ __launch_bounds__(512) void gemm_vocab_kernel(const bf16_t* __restric
 #pragma unroll
     for (int u = 0; u < U; ++u) xv[g][u] = *(const u32x4*)(xp + min(u, steps - 1) * 16);
   }
+  const int wsl = (lane & 31) * 32 + 4 * ((lane >> 5) ^ (lane & sw));
+  const int rsl = (tid >> 3) * 32 + 4 * ((tid & 7) ^ ((tid >> 3) & sw));
   int par = 0;
   auto block = [&](int nb_cur, u32x4 (&wc)[U], u32x4 (&wn)[U]) {
     load_w(nb_cur + gridDim.x, wn);               // next block's fragments: in flight under this block's MFMAs + reduction
@@ -392,17 +416,17 @@ __global__ __launch_bounds__(512) void gemm_vocab_kernel(const bf16_t* __restric
     for (int g = 0; g < RB; ++g)
 #pragma unroll
       for (int q = 0; q < 4; ++q)
-        *(float4*)&red[(wave * RB + g) * 1024 + (lane & 31) * 32 + 8 * q + 4 * (lane >> 5)] =
+        *(float4*)&red[(wave * RB + g) * 1024 + (wsl ^ (8 * q))] =
             make_float4(acc[g][4 * q], acc[g][4 * q + 1], acc[g][4 * q + 2], acc[g][4 * q + 3]);
     __syncthreads();   // one barrier per block: the other LDS buffer is only rewritten after the NEXT barrier
     if (tid < 256) {
       const int en = nb_cur * 32 + 4 * (tid & 7);
 #pragma unroll
       for (int g = 0; g < RB; ++g) {
-        float4 v = *(const float4*)&red[(0 * RB + g) * 1024 + (tid >> 3) * 32 + 4 * (tid & 7)];
+        float4 v = *(const float4*)&red[(0 * RB + g) * 1024 + rsl];
 #pragma unroll
         for (int w = 1; w < NW; ++w) {
-          const float4 t = *(const float4*)&red[(w * RB + g) * 1024 + (tid >> 3) * 32 + 4 * (tid & 7)];
+          const float4 t = *(const float4*)&red[(w * RB + g) * 1024 + rsl];
           v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
         }
         const int b = g * 32 + (tid >> 3);
@@ -456,10 +480,11 @@ bool launch_gemm_vocab(const T16* Wsh, const T16* x, int B, int N, int K, float*
   const int rb = (B + 31) / 32, steps = K / 128, n_blocks = (N + 31) / 32;
   const int grid = n_blocks < n_cu ? n_blocks : n_cu;
   const size_t lds = (size_t)2 * 8 * rb * 1024 * sizeof(float);   // 64 KiB per row group
+  const int pk = B | (ko.skinny_red_swz ? 1 << 8 : 0);
 #define TTASR_VOCAB(RB_)                                                                                                           \
   do {                                                                                                                             \
-    if (ko.skinny_nt) hipLaunchKernelGGL((gemm_vocab_kernel<T16, RB_, true>), dim3(grid), dim3(512), lds, s, (const bf16_t*)Wsh, (const bf16_t*)x, B, N, K, steps, out, ldc); \
-    else hipLaunchKernelGGL((gemm_vocab_kernel<T16, RB_, false>), dim3(grid), dim3(512), lds, s, (const bf16_t*)Wsh, (const bf16_t*)x, B, N, K, steps, out, ldc); \
+    if (ko.skinny_nt) hipLaunchKernelGGL((gemm_vocab_kernel<T16, RB_, true>), dim3(grid), dim3(512), lds, s, (const bf16_t*)Wsh, (const bf16_t*)x, pk, N, K, steps, out, ldc); \
+    else hipLaunchKernelGGL((gemm_vocab_kernel<T16, RB_, false>), dim3(grid), dim3(512), lds, s, (const bf16_t*)Wsh, (const bf16_t*)x, pk, N, K, steps, out, ldc); \
   } while (0)
   if (rb == 1) TTASR_VOCAB(1); else TTASR_VOCAB(2);
 #undef TTASR_VOCAB
@@ -523,7 +548,7 @@ bool launch_gemm_skinny(const T16* Wsh_, const T16* x_, int B, int N, int K, con
   do {                                                                                                                                \
     const bool xl_ = ko.skinny_x_lds && ONE_ && (NW_ == 4 || (NW_ == 8 && RB_ == 1));                                                  \
     const size_t lds_ = skinny_lds_bytes(NW_, RB_, steps, xl_);                                                                       \
-    const unsigned pk_ = (unsigned)B | (unsigned)ksplit << 8 | (unsigned)rpb << 16 | (xl_ ? 1u << 24 : 0u) | (unsigned)e.act << 25; \
+    const unsigned pk_ = (unsigned)B | (unsigned)ksplit << 8 | (unsigned)rpb << 16 | (xl_ ? 1u << 24 : 0u) | (unsigned)e.act << 25 | (ko.skinny_red_swz ? 1u << 26 : 0u); \
     if (ko.skinny_nt) {                                                                                                                \
       if (lds_ > 65536) skinny_allow_big_lds<gemm_skinny_kernel<T16, NW_, RB_, U_, true, ONE_>>();                                     \
       hipLaunchKernelGGL((gemm_skinny_kernel<T16, NW_, RB_, U_, true, ONE_>), grid, dim3(NW_ * 64), lds_, s, Wsh, x, e.bias, e.residual, pk_, N, K, steps, (int)e.ldc, e.out_f32, e.out_t, slab, slab_stride); \

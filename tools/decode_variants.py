@@ -34,11 +34,12 @@ VARIANTS = {
     "d4qkv1": {"ksplit_out": 4, "ksplit_qkv": 1}, "d4qkv1q2": {"ksplit_out": 4, "ksplit_qkv": 1, "ksplit_q": 2},
     "d4qkv1f16": {"ksplit_out": 4, "ksplit_qkv": 1, "ksplit_fc2": 16}, "d2qkv1": {"ksplit_out": 2, "ksplit_qkv": 1},
     "x_regs": {"dec_x_lds": 0},
+    "red_linear": {"dec_red_swizzle": 0},                 # linear rows in the GEMMs' cross-wave reduction buffer (8-way store conflict)
     "vocab_generic": {"vocab_persistent": 0},             # round-2 vocabulary GEMM: one workgroup per 32 outputs
     "w_plain": {"weights_nontemporal": 0},
     "xattn_plain": {"xattn_nontemporal": 0},
 }
-DEFAULTS = {"dec_x_lds": 1, "vocab_persistent": 1, "prefill_ns_min": 2, "ksplit_out": 0, "ksplit_q": 0, "ksplit_qkv": 0, "ksplit_fc2": 0, "weights_nontemporal": 1,
+DEFAULTS = {"dec_x_lds": 1, "dec_red_swizzle": 1, "vocab_persistent": 1, "prefill_ns_min": 2, "ksplit_out": 0, "ksplit_q": 0, "ksplit_qkv": 0, "ksplit_fc2": 0, "weights_nontemporal": 1,
             "xattn_nontemporal": 1}
 
 
